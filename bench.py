@@ -88,7 +88,21 @@ def parse_args():
                          "without a safe candidate (no stage of the sweep reads them) and its Lipschitz key, which no sweep reads, is left out; "
                          "1 evaluated but not stored; 0 the whole posterior stays resident.  The other levels are reported beside the main line "
                          "(config.full_posterior, config.lean_1) with result_identical")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its caller -- every entry of the sweep's result "
+                         "(indices, points, counts, u*, L, ...) -- as DIR/<name>.npy in float64 (rank 0; the inputs are seeded, so two "
+                         "builds run with the same arguments can be compared file for file)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(res, path):
+    """The sweep's result dict as one float64 .npy per entry (indices and counts are exact in float64)."""
+    os.makedirs(path, exist_ok=True)
+    for name, v in res.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.asarray(v, dtype=np.float64))
 
 
 def cpu_baseline(cfg, count, sample, prefix=None):
@@ -434,6 +448,8 @@ def main():
         eng.set_option("bilinear", 0)
     elapsed, rows, res = timed_resident(eng, step, args.steps, args.warmup, barrier)
     elapsed = max_over_ranks(group, elapsed)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res, args.dump_outputs)        # (host copies: res is the last timed step's own result)
     comm = comm_record(eng, step, transport) if world > 1 else None
     # N > 1: config D (BASELINE.json configs[3]) strong-scaled over the same ranks, every rank takes part
     d_rec = extra_record(eng, dcfg, None, "D", "safeopt", 3, barrier, group=group, transport=transport) if dcfg is not None else None

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -33,3 +34,19 @@ def test_bench_line_contract_on_a_small_run():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and "sample" in c and c["unit"] == "candidates/s"
     assert d["config"]["guard_audit_violations"] == 0
+
+
+def test_dump_outputs_hold_the_last_timed_result_and_repeat(tmp_path):
+    """--dump-outputs: every entry of the last timed sweep's result as float64 .npy, the same files from two runs with the same
+    arguments (seeded inputs), and the counts / indices the bench line reports."""
+    runs = [_run("--config", "B", "--steps", "3", "--warmup", "1", "--no-extra", "--cpu-sample", "0", "--dump-outputs", str(tmp_path / r))
+            for r in ("a", "b")]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "minimizer_index.npy" in names and "u_star.npy" in names
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b), f
+    r = runs[1]["config"]["result"]
+    assert runs[1]["steps"] == 3
+    for k in ("count_S", "count_M", "count_G", "minimizer_index", "expander_index", "expander_index_c"):
+        assert np.array_equal(np.load(tmp_path / "b" / f"{k}.npy"), np.asarray(r[k], dtype=np.float64)), k
