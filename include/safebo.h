@@ -84,7 +84,10 @@ typedef struct sbo_sweep_opts {
   int32_t lean;                    /* the caller wants the sweep's result only -- sets, indices, counts, u*, the constraints' L.  1: the
                                       sweep may leave mean / var unwritten where no later stage of it reads them (the objective on posterior
                                       tiles without a safe candidate: u*, M and the arg-max reductions are over S only,
-                                      models/SafeOpt.py:47-66); 2: it need not even evaluate them there (the result is the same).  A lean
+                                      models/SafeOpt.py:47-66); 2: it need not even evaluate them there (the result is the same), nor
+                                      the constraint on the posterior tiles whose enclosure (per plan, from its first full evaluation)
+                                      proves every candidate unsafe at this b and outside the guard band (sbo_profile.k1_tiles_skipped;
+                                      one-constraint column path, from the plan's second sweep on).  A lean
                                       SafeOpt sweep of a model with constraints reports L[0] = 0: the objective's Lipschitz key is read by
                                       no sweep of the reference (its expanders use the constraints' keys, models/SafeOpt.py:110,
                                       models/GoOSE.py:100), and the interpolating posteriors then leave its gradient fields out.
@@ -194,6 +197,12 @@ typedef struct sbo_profile {
    * only CHECKS it: guard_dm = analytic + rounding floor, or 1e300 (plan not trusted, every sweep re-evaluates exactly) when
    * 4 x probe exceeds that.  Zero for the exact kernels and for K1t (whose band is 16 x 2048 probes, measured).                       */
   double guard_analytic_dm[SBO_MAX_Q], guard_analytic_dv[SBO_MAX_Q], guard_probe_dm[SBO_MAX_Q], guard_probe_dv[SBO_MAX_Q];
+  /* r06: posterior tiles (64 x 128 candidates) of the constraint that the last sweep left unevaluated -- a lean 2 sweep on the column
+   * path (set_path 1) whose plan's per-cell enclosures of mean / var prove every candidate of the tile unsafe and outside the band.  */
+  int64_t k1_tiles_skipped;
+  /* of guard_audit_samples: samples on such tiles, where the audit checks the reference values against the tile's enclosure (widened
+   * by the band) instead of the stored ones.  Cumulative, as guard_audit_samples.                                                    */
+  int64_t guard_audit_skipped;
 } sbo_profile;
 
 /* ---- library / context ------------------------------------------------------------------- */

@@ -77,6 +77,7 @@ class Profile(C.Structure):
         ("guard_audit_samples", C.c_int64), ("guard_audit_violations", C.c_int64), ("guard_audit_worst", C.c_double),
         ("guard_analytic_dm", C.c_double * SBO_MAX_Q), ("guard_analytic_dv", C.c_double * SBO_MAX_Q),
         ("guard_probe_dm", C.c_double * SBO_MAX_Q), ("guard_probe_dv", C.c_double * SBO_MAX_Q),
+        ("k1_tiles_skipped", C.c_int64), ("guard_audit_skipped", C.c_int64),
     ]
 
 

@@ -997,7 +997,7 @@ struct PostCtx {
   unsigned int* lds_bits;   // [4 waves][128 columns] pieces of role 1
   double umin;              // role 2: min ucb_0 over the thread's safe candidates (+inf: none)
   double xmin;              // role 1: min of a lower bound of ucb_1 over its safe candidates; role 2: of lcb_0 (the tile's range for the set phase)
-  bool skip_store;          // lean sweep, objective tile without a safe candidate: mean / var are not stored (role 0)
+  bool skip_store;          // lean sweep: an objective tile without a safe candidate, or a constraint tile its enclosure proves unsafe -- mean / var are not stored (role 0)
 };
 
 // One GEMM phase of k_bpost on the workgroup's 128 x 128 tile: A images / B fragments of `KB` k-blocks per row block /
@@ -1087,6 +1087,31 @@ __device__ __forceinline__ void post_classify_row(PostCtx& cx, unsigned int pos,
       }
     }
   }
+}
+// r06: does post_classify_row leave EVERY (m, v) of the box [mlo, mhi] x [vlo, vhi] with ge = 0, le = 1, outside the undecided branch
+// and -- with a band in force -- outside the band test (no contribution to cB)?  Then a tile whose cells all pass adds nothing but
+// |U| and the Lipschitz key, and need not be evaluated.  The predicate repeats the epilogue's arithmetic at the box's corners:
+// m * m, bb * v and their products with c are monotone in the operand under rounding to nearest, so the corner bounds every point.
+// The band test's differences are tested with a relative margin of 2^-40 of the operands on top (the build does not contract,
+// Makefile: the margin only keeps the argument independent of that).  NaN anywhere: not decided.
+__device__ __forceinline__ bool encl_unsafe(double mlo, double mhi, double vlo, double vhi, double bconf, double bb, bool gb_on, const LcbBand& lb) {
+  constexpr double c = 1.0 + 0x1p-48, tiny = 1e-250, huge = 1e300, mg = 0x1p-40;
+  if (!(bconf >= 0.0 && vlo >= 0.0 && vlo <= vhi && mlo <= mhi)) return false;          // (NaN: false)
+  const double Ql = bb * vlo, Qh = bb * vhi;
+  // classification: m < 0 is le outright; 0 <= m <= mhi needs rng, Q > tiny and P c <= Q (then ge is false: P <= P c <= Q < Q c)
+  if (!(mhi < 0.0)) {
+    const double Ph = mhi * mhi;
+    if (!(Ph < huge && Qh < huge && Ql > tiny && Ph * c <= Ql)) return false;
+  }
+  if (!gb_on) return true;
+  // band: |P - Q| > |m| c1 + c0 for every point -- Q above every P by the margin, or (all m < 0) every P above Q
+  const double amax = fmax(fabs(mlo), fabs(mhi)), amin = (mlo <= 0.0 && mhi >= 0.0) ? 0.0 : fmin(fabs(mlo), fabs(mhi));
+  const double Pmax = amax * amax, Pmin = amin * amin;
+  const double rhs = fma(amax, lb.c1, lb.c0);
+  if (!(amax < 1e150 && Qh < huge && rhs < huge)) return false;
+  const bool qdom = (Ql - Pmax) - mg * (Ql + Pmax) > rhs * (1.0 + mg);
+  const bool pdom = mhi < 0.0 && (Pmin - Qh) - mg * (Pmin + Qh) > rhs * (1.0 + mg);
+  return qdom || pdom;
 }
 // role 2: a safe candidate of the objective -- u* = min over S of ucb_0 (models/SafeOpt.py:47-51), the exact bound only when the
 // cheap lower bound could beat the thread's running minimum (as k_classify's objective pass), and the smallest var_0 over S
@@ -1308,7 +1333,7 @@ __device__ __forceinline__ void post_epilogue(PostCtx& cx, double* __restrict__ 
           for (int s2 = 0; s2 < 8; ++s2) post_classify_mv(cx, g0 + s2 * 16, mv[s2], vr[s2]);
           continue;
         }
-        if (PH <= 1 && RB == 1 && ROLE == 2 && cx.skip_store) continue;     // (lean sweep: nobody reads this tile's mean / var)
+        if (PH <= 1 && RB == 1 && ROLE != 0 && cx.skip_store) continue;     // (lean sweep: nobody reads this tile's mean / var)
 #pragma unroll
         for (int s2 = 0; s2 < 8; ++s2) {
           const double v = acc[i][s2][t];
@@ -1485,6 +1510,35 @@ __device__ unsigned long long g_phase_clk[kPhaseClkRows][8];
 #define SBO_CLK(i) do { } while (0)
 #endif
 
+// r06: the enclosures of the constraint's posterior per 8 x 8 cell of every 64 x 128 column-path tile, taken from what the constraint's
+// launch stored -- once per plan, behind its first launch that evaluated every tile.  k_bpost is deterministic for a plan (the same
+// operands, the same k-order of the matrix instructions; b and the band enter only the classification), so [min, max] of the stored
+// values encloses exactly what any later launch of the plan computes: no bound on derivatives, no rounding allowance.  Layout
+// [tile][cell = 16 r + c][m_lo, m_hi, v_lo, v_hi]; a cell holding NaN or inf gets NaN (encl_unsafe: never decided).
+// THE INVARIANT THIS RESTS ON: phases 0 / 1 of the constraint's launch compute the same bits on every launch of a plan.  Anything that
+// changes their operands, k-steps or k-order between sweeps of one plan (a per-sweep truncation, another tile shape, a different
+// accumulation order) must clear BilinearPlan::encl_ready.  The standing audit checks it where it samples an evaluated tile: the stored
+// values must lie inside the recorded enclosure bit for bit (guard.hip: k_audit_compare).
+__global__ __launch_bounds__(128) void k_bl_enclose(const double* __restrict__ mean, const double* __restrict__ var, long long cnt0,
+                                                    double* __restrict__ encl) {
+  const int cell = threadIdx.x, cr = cell >> 4, cc = cell & 15;
+  const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+  const size_t base = ((size_t)blockIdx.y * 64 + (size_t)cr * 8) * (size_t)cnt0 + (size_t)blockIdx.x * 128 + (size_t)cc * 8;
+  double mlo = 1e308, mhi = -1e308, vlo = 1e308, vhi = -1e308;
+  bool fin = true;
+  for (int r = 0; r < 8; ++r) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const double m = mean[base + (size_t)r * cnt0 + k], v = var[base + (size_t)r * cnt0 + k];
+      fin = fin && fabs(m) <= 1e308 && fabs(v) <= 1e308;                  // (NaN: false)
+      mlo = fmin(mlo, m); mhi = fmax(mhi, m); vlo = fmin(vlo, v); vhi = fmax(vhi, v);
+    }
+  }
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  double4 e = fin ? double4{mlo, mhi, vlo, vhi} : double4{nan, nan, nan, nan};
+  reinterpret_cast<double4*>(encl)[tile * 128 + cell] = e;
+}
+
 // RB: row blocks per wave.  2 = the 128 x 128 tile above; 1 = a 64 x 128 tile for grids whose 128 x 128 tiles would leave
 // CUs without a workgroup (1024 x 1024 x 3 outputs: 192 tiles on 256 CUs) -- half the reuse of a B fragment, twice the
 // workgroups.
@@ -1592,7 +1646,29 @@ __global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelCon
   // lean sweeps, level 2: the objective's posterior of a tile without a safe candidate is not even evaluated -- u*, M and the
   // arg-max reductions read it on S only (models/SafeOpt.py:47-66); the tile still runs the gradient phases the gate asks for
   // (L_0 is a maximum over the whole grid), and with K1b's operands the mean phase those continue from
-  const bool skip_tile = ROLE == 2 && obits && tile_nS == 0ull && px.lean >= 2;
+  // r06, the same for the constraint: a tile whose every 8 x 8 cell the plan's enclosure proves unsafe at this b (encl_unsafe: ge = 0,
+  // le = 1, no undecided branch, outside the band test) is not evaluated either -- its words, counts and keys are those of a tile in
+  // which every candidate is in U, written here; its gradient phases run as the gate says.  Nothing of this sweep reads its mean /
+  // var: the set phase reads the constraint's posterior on tiles with a safe candidate only (G within S), and the audit checks a
+  // sample that lands here against the enclosure instead (guard.hip).
+  bool cskip = false;
+  if (ROLE == 1 && cbits && px.lean >= 2 && px.encl != nullptr) {
+    bool dec = true;
+    if (cx.tid < 128) {
+      const double4 e = reinterpret_cast<const double4*>(px.encl)[ctile * 128 + cx.tid];
+      dec = encl_unsafe(e.x, e.y, e.z, e.w, cx.bconf, cx.bb, cx.gb_on, cx.lband);
+    }
+    cskip = __syncthreads_and(dec ? 1 : 0) != 0;
+    if (cx.tid == 0) px.skip[ctile] = cskip ? 1 : 0;
+    if (cskip) {
+      cx.role = 0;
+      cx.skip_store = true;
+      cx.cU = 64 * 128 / 256;               // (every candidate in U, spread over the threads: the partials sum to 8192)
+      for (int i = cx.tid; i < 4 * 128; i += 256) cx.lds_bits[i] = 0xffff0000u;      // (S pieces 0, U pieces all ones)
+      if (cx.tid == 0) atomicAdd(&px.cb.slots[(size_t)kSlotSkip * kColSlots + (ctile & (kColSlots - 1))], 1ull);
+    }
+  }
+  const bool skip_tile = (ROLE == 2 && obits && tile_nS == 0ull && px.lean >= 2) || cskip;
   if (!skip_tile)
     post_phase<0, RB, ROLE>(cx, BtA + (size_t)o * sBtA, P0f + (size_t)o * sP0f, KB0, eff ? eff[4 * o * es] : KS0, vo, sf2, ystd * ystd, 0.0, gmax, acc, xn0, pre,
                             VAo, SBo, KBm);
@@ -2381,6 +2457,7 @@ int bilinear_setup(sbo_ctx* c) {
   pl.valid = true;
   pl.usable = false;
   pl.band_ready = false;
+  pl.encl_ready = false;
   pl.setup_ms = 0.0;
   const auto t_begin = std::chrono::steady_clock::now();
   const bool timing = getenv("SBO_BL_TIMING") != nullptr;
@@ -3464,12 +3541,29 @@ int launch_posterior_bilinear(sbo_ctx* c) {
     if ((rc = ensure(c->cpart, sizeof(unsigned long long) * kFuseRow * ((size_t)c->fuse_rows + 4 * (size_t)c->n_cu + 64)))) return rc;
     c->cpart_cap = (int)(c->cpart.bytes / (sizeof(unsigned long long) * kFuseRow));
   }
+  bool record_encl = false;
+  double* encl = nullptr;
   if (colw) {
     if ((rc = col_words_prepare(c, cnt0, nlines, &px.cb))) return rc;
     px.lean = c->col_lean;
     c->col_active = true;
     c->col_forked = true;
     fuse = false;                      // (no byte masks: the words are the classification)
+    // r06: the constraint's enclosures per 8 x 8 cell (per plan) and a skip byte per tile (per sweep); a lean-2 sweep hands them to
+    // the constraint's launch once the plan's first launch has recorded them
+    const size_t ntiles = (size_t)gx * gy, ebytes = sizeof(double) * 4 * 128 * ntiles;
+    const void* was = c->bl_encl.p;
+    if ((rc = ensure(c->bl_encl, ebytes + ntiles))) return rc;
+    if (c->bl_encl.p != was) c->bl.encl_ready = false;
+    encl = (double*)c->bl_encl.p;
+    record_encl = !c->bl.encl_ready;
+    c->k1_encl_tiles = ntiles;
+    c->k1_encl_check = !record_encl;
+    if (!record_encl && c->col_lean >= 2) {
+      px.encl = encl;
+      px.skip = (uint8_t*)c->bl_encl.p + ebytes;
+      c->k1_skip_armed = true;
+    }
   }
   // (the fused classification counts its sign tests inside the plan's guard band)
   const GuardBand* gb_fused = (c->guard_band && !c->is_shadow && c->bl.band_ready && c->gb.p) ? (const GuardBand*)c->gb.p : nullptr;
@@ -3490,6 +3584,12 @@ int launch_posterior_bilinear(sbo_ctx* c) {
                           (double*)c->mean.p, (double*)c->var.p, (double*)c->bl_lpart.p, (const double*)c->bl_small.p /* xn0 */,
                           fuse ? (uint8_t*)(q > 2 ? c->fuseS.p : c->maskS.p) : (uint8_t*)nullptr, fuse ? (uint8_t*)(q > 2 ? c->fuseU.p : c->maskU.p) : (uint8_t*)nullptr, c->fuse_b,
                           (unsigned long long*)c->cpart.p, c->cpart_cap, gb_fused, (const int*)pl.eff, pl.gtmax, pl.gkey, 0, px);
+    if (colw && part == 0 && record_encl) {
+      // (the plan's first constraint launch evaluated and stored every tile: its enclosures, ~270 MB read once per plan)
+      hipLaunchKernelGGL(k_bl_enclose, dim3(gx, gy), dim3(128), 0, c->stream, (const double*)c->mean.p + (size_t)cs.n_local,
+                         (const double*)c->var.p + (size_t)cs.n_local, cnt0, encl);
+      c->bl.encl_ready = true;
+    }
   }
   if (c->lmax_defer) {
     c->lmax_pending = true;

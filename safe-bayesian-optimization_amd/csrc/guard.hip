@@ -458,7 +458,12 @@ int guard_band_from_probes(sbo_ctx* c, const double* pm, const double* pv, const
 template <int D>
 __global__ __launch_bounds__(256) void k_audit_pick(const CandSpec cs, int P, unsigned long long offset, unsigned long long stride, int q,
                                                     const double* __restrict__ mean, const double* __restrict__ var, double* __restrict__ pts,
-                                                    double* __restrict__ apx /* [2][q][P] */) {
+                                                    double* __restrict__ apx /* [2][q][P] */,
+                                                    const double* __restrict__ encl /* r06: nullptr, or the constraint's per-cell enclosures
+                                                    (bilinear.hip: k_bl_enclose) of the K1b column-path launch that just ran */,
+                                                    const uint8_t* __restrict__ skip /* nullptr, or its skip bytes (a lean-2 launch) */,
+                                                    int gx /* 64 x 128 tiles per tile row */,
+                                                    double* __restrict__ aenc /* [5][P]: 1 on a skipped tile, 2 on an evaluated one; m_lo, m_hi, v_lo, v_hi */) {
   const long long N = cs.n_local;
   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < P; k += gridDim.x * blockDim.x) {
     const long long g = (long long)((offset + (unsigned long long)k * stride) % (unsigned long long)N);
@@ -469,20 +474,42 @@ __global__ __launch_bounds__(256) void k_audit_pick(const CandSpec cs, int P, un
       apx[(size_t)o * P + k] = mean[(size_t)o * N + g];
       apx[(size_t)(q + o) * P + k] = var[(size_t)o * N + g];
     }
+    if (encl) {
+      // (column path: line g / count0, column g % count0; tile (line / 64, column / 128), cell ((line % 64) / 8, (column % 128) / 8))
+      const long long cnt0 = cs.count[0], line = g / cnt0, col = g % cnt0;
+      const size_t tile = (size_t)(line >> 6) * (size_t)gx + (size_t)(col >> 7);
+      aenc[k] = (skip && skip[tile] != 0) ? 1.0 : 2.0;
+      const double* e = encl + (tile * 128 + (size_t)(((line & 63) >> 3) * 16 + ((col & 127) >> 3))) * 4;
+      for (int j = 0; j < 4; ++j) aenc[(size_t)(1 + j) * P + k] = e[j];
+    }
   }
 }
-// cnt: [0] violations, [1] samples (value pairs compared), [2] bit pattern of the largest deviation in units of the band
+// cnt: [0] violations, [1] samples (value pairs compared), [2] bit pattern of the largest deviation in units of the band, [3] samples on
+// constraint tiles the sweep left unevaluated: there the claim is the skip's -- the exact values lie in the tile's enclosure of what the
+// posterior kernel computes, widened by the band --, and the deviation is the distance from that interval
 __global__ __launch_bounds__(256) void k_audit_compare(int P, int q, int o_first, const double* __restrict__ apx, const double* __restrict__ ref_m,
                                                        const double* __restrict__ ref_v, const GuardBand* __restrict__ gb,
-                                                       unsigned long long* __restrict__ cnt, double scale /* 1, or the test hook's factor on the band */) {
-  long long viol = 0, smp = 0;
+                                                       unsigned long long* __restrict__ cnt, double scale /* 1, or the test hook's factor on the band */,
+                                                       const double* __restrict__ aenc /* nullptr, or k_audit_pick's [5][P] (constraint 1) */) {
+  long long viol = 0, smp = 0, nsk = 0;
   double worst = 0.0;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < P * (q - o_first); e += gridDim.x * blockDim.x) {
     const int o = o_first + e / P, k = e % P;
-    const double dm = fabs(apx[(size_t)o * P + k] - ref_m[(size_t)o * P + k]), dv = fabs(apx[(size_t)(q + o) * P + k] - ref_v[(size_t)o * P + k]);
+    double dm = fabs(apx[(size_t)o * P + k] - ref_m[(size_t)o * P + k]), dv = fabs(apx[(size_t)(q + o) * P + k] - ref_v[(size_t)o * P + k]);
+    // (an evaluated constraint tile of a launch with enclosures: what it stored lies inside them, bit for bit -- NaN counts)
+    const bool drift = aenc && o == 1 && aenc[k] == 2.0 &&
+                       !(apx[(size_t)o * P + k] >= aenc[(size_t)1 * P + k] && apx[(size_t)o * P + k] <= aenc[(size_t)2 * P + k] &&
+                         apx[(size_t)(q + o) * P + k] >= aenc[(size_t)3 * P + k] && apx[(size_t)(q + o) * P + k] <= aenc[(size_t)4 * P + k]);
+    if (aenc && o == 1 && aenc[k] == 1.0) {
+      const double rm = ref_m[(size_t)o * P + k], rv = ref_v[(size_t)o * P + k];
+      dm = fmax(fmax(aenc[(size_t)1 * P + k] - rm, rm - aenc[(size_t)2 * P + k]), 0.0);
+      dv = fmax(fmax(aenc[(size_t)3 * P + k] - rv, rv - aenc[(size_t)4 * P + k]), 0.0);
+      if (!(rm == rm) || !(rv == rv)) dm = dv = __longlong_as_double(0x7ff8000000000000ll);    // (fmax drops NaN: counted as a violation)
+      ++nsk;
+    }
     const double bm = gb->dm[o] * scale, bv = gb->dv[o] * scale;
     const double rm = dm / bm, rv = dv / bv;
-    const bool bad = !(dm <= bm) || !(dv <= bv);                            // (NaN counts)
+    const bool bad = !(dm <= bm) || !(dv <= bv) || drift;                   // (NaN counts)
     viol += bad;
     ++smp;
     const double r = rm > rv ? rm : rv;
@@ -490,12 +517,14 @@ __global__ __launch_bounds__(256) void k_audit_compare(int P, int q, int o_first
   }
   viol = block_sum_i64(viol);
   smp = block_sum_i64(smp);
+  nsk = block_sum_i64(nsk);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) worst = fmax(worst, __shfl_xor(worst, off));
   if ((threadIdx.x & 63) == 0 && worst > 0.0) atomicMax(&cnt[2], (unsigned long long)__double_as_longlong(worst));
   if (threadIdx.x == 0) {
     if (viol) atomicAdd(&cnt[0], (unsigned long long)viol);
     atomicAdd(&cnt[1], (unsigned long long)smp);
+    if (nsk) atomicAdd(&cnt[3], (unsigned long long)nsk);
   }
 }
 
@@ -506,6 +535,7 @@ void guard_audit_harvest(sbo_ctx* c, bool wait) {
   const unsigned long long* hc = (const unsigned long long*)(c->h_back + 7168);
   c->audit_violations += (long long)hc[0];
   c->audit_samples += (long long)hc[1];
+  c->audit_skipped += (long long)hc[3];
   double w;
   memcpy(&w, &hc[2], 8);
   c->audit_worst = std::max(c->audit_worst, w);
@@ -523,12 +553,23 @@ int guard_audit_enqueue(sbo_ctx* c, int first_output) {
   if (c->audit_pending) return SBO_OK;                 // (the previous audit is still running: this sweep's is skipped, none queues up)
   const int P = c->guard_audit, q = c->mc.q;
   int rc;
-  if ((rc = ensure(c->audit_pts, sizeof(double) * (size_t)P * 2)) || (rc = ensure(c->audit_val, sizeof(double) * (size_t)P * q * 4)) ||
+  if ((rc = ensure(c->audit_pts, sizeof(double) * (size_t)P * 2)) || (rc = ensure(c->audit_val, sizeof(double) * (size_t)P * (q * 4 + 5))) ||
       (rc = ensure(c->audit_cnt, 64)))
     return rc;
   double* apx = (double*)c->audit_val.p;
   double* ref_m = apx + (size_t)2 * q * P;
   double* ref_v = ref_m + (size_t)q * P;
+  double* aenc = ref_v + (size_t)q * P;
+  // (r06: a K1b column-path launch on a plan with recorded enclosures -- bilinear.hip: k_bl_enclose -- leaves two things to check at the
+  // constraint's samples.  On a tile a lean sweep left unevaluated the stored values are not this sweep's: the exact values must lie in
+  // the tile's enclosure widened by the band.  On an evaluated tile the stored values must lie in the enclosure exactly -- the skip rests
+  // on every launch of a plan computing what its first one did.  The sample copies the skip byte and the enclosure, before the next
+  // sweep may overwrite either.  Only for the launch that just ran, on the layout bl_encl has for this grid.)
+  const long long cnt0 = c->cs.count[0];
+  const size_t ntiles = c->cs.kind == 1 && c->cs.d == 2 && cnt0 > 0 ? (size_t)(cnt0 / 128) * (size_t)(c->cs.n_local / cnt0 / 64) : 0;
+  const bool encl = c->k1_encl_check && c->last_k1 == 4 && c->bl.encl_ready && first_output <= 1 && ntiles > 0 && c->k1_encl_tiles == ntiles &&
+                    c->bl_encl.bytes >= (sizeof(double) * 4 * 128 + 1) * ntiles;
+  const bool skips = encl && c->k1_skip_armed;
   hipStream_t st = c->stream_audit;
   // the sample is taken behind the posterior (its stop event ev[1] -- no record of its own on the main stream: that would be a bubble
   // in the sweep) ...
@@ -536,14 +577,15 @@ int guard_audit_enqueue(sbo_ctx* c, int first_output) {
   SBO_HIP(hipMemsetAsync(c->audit_cnt.p, 0, 64, st));
   const unsigned long long stride = 1000003ull;
   hipLaunchKernelGGL(k_audit_pick<2>, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, c->cs, P, c->audit_offset, stride, q, (const double*)c->mean.p,
-                     (const double*)c->var.p, (double*)c->audit_pts.p, apx);
+                     (const double*)c->var.p, (double*)c->audit_pts.p, apx, encl ? (const double*)c->bl_encl.p : (const double*)nullptr,
+                     skips ? (const uint8_t*)c->bl_encl.p + sizeof(double) * 4 * 128 * ntiles : (const uint8_t*)nullptr, (int)(cnt0 / 128), aenc);
   c->audit_offset += (unsigned long long)P * stride + 17ull;
   // ... and before anything overwrites mean / var again (the next posterior launch waits for this event)
   SBO_HIP(hipEventRecord(c->ev_audit[0], st));
   if ((rc = launch_ref<2>(c, st, (const double*)c->audit_pts.p, P, 0, ref_m, ref_v, nullptr, &c->audit_part))) return rc;
   hipLaunchKernelGGL(k_audit_compare, dim3(8), dim3(256), 0, st, P, q, first_output, (const double*)apx, (const double*)ref_m, (const double*)ref_v,
-                     (const GuardBand*)c->gb.p, (unsigned long long*)c->audit_cnt.p, c->audit_scale);
-  SBO_HIP(hipMemcpyAsync(c->h_back + 7168, c->audit_cnt.p, 24, hipMemcpyDeviceToHost, st));
+                     (const GuardBand*)c->gb.p, (unsigned long long*)c->audit_cnt.p, c->audit_scale, encl ? (const double*)aenc : (const double*)nullptr);
+  SBO_HIP(hipMemcpyAsync(c->h_back + 7168, c->audit_cnt.p, 32, hipMemcpyDeviceToHost, st));
   SBO_HIP(hipEventRecord(c->ev_audit[1], st));
   SBO_HIP(hipGetLastError());
   c->audit_pending = true;

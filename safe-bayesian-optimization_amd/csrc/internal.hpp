@@ -63,7 +63,8 @@ struct ColBits {
 constexpr int kColSlots = 64;
 enum ColSlotField { kSlotUmin = 0 /* min key of ucb_0 over S */, kSlotS, kSlotU, kSlotB /* counts */, kSlotVmin0, kSlotVmin1 /* min keys */,
                     kSlotRmax1 /* max key */, kSlotL0, kSlotL1 /* max of the gradient norms' bit patterns */,
-                    kSlotRowMask /* word s: bit t set iff tile t of tile row s holds a safe candidate */, kColSlotFields };
+                    kSlotRowMask /* word s: bit t set iff tile t of tile row s holds a safe candidate */,
+                    kSlotSkip /* count: constraint tiles its enclosure proved unsafe, left unevaluated (r06) */, kColSlotFields };
 __host__ __device__ inline bool col_slot_is_min(int f) { return f == kSlotUmin || f == kSlotVmin0 || f == kSlotVmin1; }
 // what a k_bpost launch is told beyond its operands (r05: one launch per output on the column path)
 struct PostExtra {
@@ -73,6 +74,10 @@ struct PostExtra {
   long long fstride; // fused classification of several constraints: stride of the S / U byte planes (constraint o writes plane o - 1; 0: one constraint, the masks themselves)
   int nograd;    // 1: the gradient phases (Lipschitz keys) run in a launch of their own (k_bpost<.., 3>, K1i's deferred gate): none here
   ColBits cb;    // Sw == nullptr: no bit words (byte masks or no classification at all)
+  // lean >= 2, the constraint's launch (r06): the plan's enclosures of its mean / var, [tiles][128 cells of 8 x 8][m_lo, m_hi, v_lo, v_hi]
+  // (k_bl_enclose), and one byte per tile that says whether the tile was left unevaluated; nullptr: every tile is evaluated
+  const double* encl;
+  uint8_t* skip;
 };
 
 // K1b (bilinear.hip): device tables of the reduced-basis posterior on a 2-D grid, valid for one (model, candidates) pair
@@ -91,6 +96,7 @@ struct BilinearPlan {
   const double* gtmax = nullptr;              // device: largest gradient samples per k_bpost tile + slacks (k_bl_gradcoarse), or none
   const unsigned long long* gkey = nullptr;   // device: the grid's largest gradient samples
   bool band_ready = false;   // the guard band of this plan has been measured (guard.hip: guard_band_bilinear)
+  bool encl_ready = false;   // bl_encl holds the enclosures of the constraint's mean / var per 8 x 8 cell (k_bl_enclose, r06)
 };
 
 // K1i: the first sweep of a model by interpolation from Chebyshev nodes (bilinear.hip)
@@ -204,6 +210,7 @@ struct sbo_ctx {
   bool audit_pending = false;
   unsigned long long audit_offset = 0;
   long long audit_samples = 0, audit_violations = 0;
+  long long audit_skipped = 0;     // of audit_samples: constraint samples on tiles a lean sweep left unevaluated (checked against the enclosure)
   double audit_worst = 0.0;        // largest deviation seen, in units of the band
   bool gb_mirrored = false;        // the plan's band kernel also wrote the block to pinned host memory (h_back + kGbMirrorOffset): valid once a sweep has synchronised
   bool gb_host_valid = false;      // gb_host mirrors `gb` (read back on demand by sbo_profile_get; dropped when a plan writes the block)
@@ -259,6 +266,11 @@ struct sbo_ctx {
   void* ev_bi_params = nullptr;   // hipEvent_t: the plan's copy of the block (and everything before it on the main stream) has run
   sbo::DevBuf bl_grad;  // K1b: which tiles run the gradient phases (per plan)
   sbo::DevBuf bl_lpart; // K1b: per-wave Lipschitz partials of k_bpost
+  sbo::DevBuf bl_encl;  // K1b column path: per-cell enclosures of the constraint's posterior (per plan) + a skip byte per tile (per sweep)
+  // what the last posterior launch leaves for the standing audit (guard.hip), cleared by every enqueue of a posterior (api.hip):
+  bool k1_skip_armed = false;   // it could leave constraint tiles unevaluated: bl_encl's skip bytes are its record
+  bool k1_encl_check = false;   // a K1b column-path launch on a plan whose enclosures were recorded: what it stored lies inside them
+  size_t k1_encl_tiles = 0;     // tiles of the grid bl_encl was laid out for (the skip bytes sit behind 4 x 128 doubles per tile)
   sbo::DevBuf cpart;   // per-workgroup partials of k_classify, field-major [kClassifyRow][cpart_cap]
   int cpart_cap = 0;   // row capacity the last writer of cpart laid its rows out with
   long long comm_bytes = 0;   // collectives of the running sweep: bytes handed over (send side), calls, and -- option comm_events --

@@ -947,6 +947,7 @@ static bool grid_path_ok(const sbo_ctx* c) {
 
 int launch_posterior(sbo_ctx* c) {
   c->gb_active = false;                    // (the approximating paths K1b / K1t switch their guard band on themselves)
+  c->k1_skip_armed = c->k1_encl_check = false;   // (so does the K1b column path its records for the audit, guard.hip)
   // block-triangular contraction as issued: npad (npad + 16) / 2 multiply-adds per candidate and output
   const double tri_flops = (double)c->mc.q * c->mc.npad * (c->mc.npad + 16.0) * (double)c->cs.n_local;
   if (grid_path_ok(c)) {

@@ -50,6 +50,7 @@ struct SweepScalars {
   double arg_d[kArgSlots];
   long long n_guard;
   long long guard_slot[kArgSlots];
+  long long tiles_skipped;                 // column path, lean 2: constraint tiles of the posterior left unevaluated (r06: kSlotSkip)
   // ---- device only ----
   unsigned long long ticket;               // workgroups of k_goose_finals that have finished their slot (zeroed with the block)
   long long n_guard_cls;                   // the classification's share of n_guard, the value it starts from
@@ -1832,6 +1833,12 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
   const int lean = o->lean;
   c->col_lean = c->col_request ? (lean >= 2 ? 2 : (lean ? 1 : 0)) : 0;
   c->sweep_lean = (lean && q >= 2 && !reuse) ? 1 : 0;
+  // (the lean flag belongs to this sweep's posterior launches: a posterior run after it -- sbo_posterior_run, the guard's full
+  // re-evaluation -- computes every key again)
+  struct LeanEnd {
+    sbo_ctx* c;
+    ~LeanEnd() { c->sweep_lean = 0; }
+  } lean_end{c};
   c->col_active = false;
   if (!reuse && (rc = sbo_posterior_enqueue_(c))) { c->col_request = false; return rc; }
   c->col_request = false;
@@ -1951,6 +1958,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
   c->prof.posterior_flops = reuse ? 0.0 : q * (nn * nn + (2 * dd + 10) * nn) * (double)n;
   sweep_times(c);
   c->prof.set_path = colpath ? 1 : 0;
+  c->prof.k1_tiles_skipped = colpath ? h.tiles_skipped : 0;
 
   memset(res, 0, sizeof(*res));
   res->count_S = h.count_S;

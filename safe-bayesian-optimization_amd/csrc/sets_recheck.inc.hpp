@@ -276,6 +276,8 @@ static int rc_refine(sbo_ctx* c, const long long* list, long long nf, bool guard
     double* em = (double*)c->gb_vals.p;
     double* ev = em + (size_t)nf * q;
     if ((rc = guard_exact_list(c, (const double*)pbuf.p, nf, em, ev))) return rc;
+    // (the standing audit takes its sample of what the posterior kernel stored before the exact values replace it)
+    if (c->audit_pending) SBO_HIP(hipStreamWaitEvent(c->stream, c->ev_audit[0], 0));
     hipLaunchKernelGGL(k_rc_scatter, dim3(nbf), dim3(256), 0, c->stream, list, nf, q, n, (const double*)em, (const double*)ev,
                        (double*)c->mean.p, (double*)c->var.p, (uint8_t*)c->rc_refined.p);
     SBO_HIP(hipGetLastError());
