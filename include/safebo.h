@@ -328,6 +328,8 @@ int sbo_profile_get(sbo_ctx* ctx, sbo_profile* out);
  *   "grad_defer"       first sweep of a model on fp64 2-D grids (K1i): where the Lipschitz keys' gradient phases run.  0: inside the posterior
  *                      launches, behind the gate's kernels (r04); 1 (default): in a launch of their own on a side stream beside the posterior
  *                      launches -- behind the gate on large grids, on every tile without a gate on small ones; 2: always without, 3: always with
+ *   "k1_sched"         1: lean-2 sweeps on that path launch the constraint's and the objective's GEMM posterior over lists of the tiles they
+ *                      evaluate, built per sweep (tiles left out are written by the lists' kernels); 0: one workgroup per tile (A/B checker)
  *   "col_overlap"      1: on that path the expander chain (distance transform, verdicts) runs on a second stream beside the objective's
  *                      posterior launch; 0: every kernel on the main stream
  *   "set_fuse"         1: 2-D grids of one rank share launches between independent set-phase kernels; 0: one launch per kernel

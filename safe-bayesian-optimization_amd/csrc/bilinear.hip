@@ -1497,6 +1497,21 @@ __device__ __forceinline__ void post_phase(PostCtx& cx, const double* __restrict
 // take 0.1 ms); [4] = gradient phases the workgroup ran.  The host sums the rows.
 constexpr int kPhaseClkRows = 1 << 14;
 __device__ unsigned long long g_phase_clk[kPhaseClkRows][8];
+// r07: and a row per workgroup of the column path's two launches (the last sweep's: overwritten by every launch), in dispatch order
+// (linear block index): [0] entry, [1] start of the partial rows (post_partials, the words and their Usum / slot atomics), [2] exit --
+// all wall_clock64 --, [3] tile | kind << 24 (0 evaluated, 1 skipped: partial rows only, 2 skipped but its gradient phases run,
+// 3 past the tile list: exited at once) | 1 << 31 (row written), [4] HW_REG_HW_ID, [5] HW_REG_XCC_ID.  tools/dev_wg_timeline.py.
+constexpr int kWgTraceRows = 1 << 13;
+__device__ unsigned long long g_wg_trace[2][kWgTraceRows][8];
+__device__ __forceinline__ void wg_trace_row(int o, unsigned long long t0, unsigned long long t1, unsigned long long t2, unsigned int tile, unsigned int kind) {
+  unsigned int hw, xcc;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  unsigned long long* r = g_wg_trace[o & 1][(blockIdx.y * gridDim.x + blockIdx.x) & (kWgTraceRows - 1)];
+  r[0] = t0; r[1] = t1; r[2] = t2;
+  r[3] = (unsigned long long)(tile & 0xffffffu) | ((unsigned long long)kind << 24) | (1ull << 31);
+  r[4] = hw; r[5] = xcc;
+}
 #define SBO_CLK(i)                                                                                \
   do {                                                                                           \
     __syncthreads();                                                                             \
@@ -1539,6 +1554,179 @@ __global__ __launch_bounds__(128) void k_bl_enclose(const double* __restrict__ m
   reinterpret_cast<double4*>(encl)[tile * 128 + cell] = e;
 }
 
+// r07: the tile lists of a lean-2 column-path sweep (option k1_sched).  One workgroup per tile left 1451 of config H's 2048 constraint
+// workgroups and 1533 of its objective ones doing nothing but their partial rows, interleaved with the evaluated tiles: the evaluated
+// ones ran as two partial rounds of workgroups.  Instead the constraint's launch and the objective's run over lists of the tiles that
+// need a workgroup -- a 1-D grid, workgroup i takes entry i and exits at once past the list -- so the evaluated tiles are dispatched
+// first and fit the CUs in one round.  What a left-out tile produced is written here, bit for bit what its workgroup wrote.
+//
+// The constraint's tiles, one wave each (before the constraint's launch): the skip decision of k_bpost (encl_unsafe on every cell of
+// the tile, at this sweep's b and band) and the gradient gate's decision for output 1.  cls: 0 = skipped, no gradient phase (written
+// here: S = 0 and U = all ones words, its Lipschitz row, its partial row of the classification -- |U| = 8192, no keys; Usum and the
+// slot block in k_bl_sched_list1); 1 = evaluated with gradient phases, 2 = skipped but runs gradient phases, 3 = evaluated.  The skip
+// byte of every tile for the audit (guard.hip).
+__global__ __launch_bounds__(256) void k_bl_sched_tiles1(const ModelConst mc, const double* __restrict__ encl, int ntiles, int tgx, int tgy,
+                                                         unsigned int cnt0, double bconf, const GuardBand* __restrict__ gb,
+                                                         const double* __restrict__ gtmax, const unsigned long long* __restrict__ gkey, int q,
+                                                         uint8_t* __restrict__ skip, uint8_t* __restrict__ cls, unsigned long long* __restrict__ Sw,
+                                                         unsigned long long* __restrict__ Uw, double* __restrict__ Lpart,
+                                                         unsigned long long* __restrict__ cpart, int pcap) {
+  const int lane = threadIdx.x & 63, tile = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  if (tile >= ntiles) return;
+  const double bb = bconf * bconf;
+  const bool gb_on = gb != nullptr;
+  const LcbBand lb = gb_on ? lcb_band(bb, gb->dm[1], gb->dv[1]) : LcbBand{0.0, 0.0};
+  bool ok = true;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const double4 e = reinterpret_cast<const double4*>(encl)[(size_t)tile * 128 + h * 64 + lane];
+    ok = ok && encl_unsafe(e.x, e.y, e.z, e.w, bconf, bb, gb_on, lb);
+  }
+  const bool dec = __ballot(!ok) == 0ull;
+  // (k_bpost's gate, output 1, and the largest coarse sample it folds in)
+  bool run2 = true, run3 = true;
+  double gfold = 0.0;
+  if (gtmax) {
+    const size_t nt = (size_t)ntiles;
+    const double* slack = gtmax + (size_t)q * 2 * nt;
+    const double ystd = mc.Y_std[1];
+    const double cg0 = ystd * mc.inv_ell[1][0] * mc.X_rstd[0], cg1 = ystd * mc.inv_ell[1][1] * mc.X_rstd[1];
+    const double t0 = gtmax[(size_t)2 * nt + tile], t1 = gtmax[(size_t)3 * nt + tile];
+    const double G0 = __longlong_as_double((long long)gkey[2]), G1 = __longlong_as_double((long long)gkey[3]);
+    run2 = !(t0 + slack[2] < G0 * (1.0 - 1e-12));
+    run3 = !(t1 + slack[3] < G1 * (1.0 - 1e-12));
+    gfold = fmax(fabs(cg0 * t0), fabs(cg1 * t1));
+  }
+  const bool grad = run2 || run3;
+  const unsigned int k = dec ? (grad ? 2u : 0u) : (grad ? 1u : 3u);
+  if (lane == 0) {
+    skip[tile] = dec ? 1 : 0;
+    cls[tile] = (uint8_t)k;
+  }
+  if (k != 0u) return;
+  const int bx = tile % tgx, by = tile / tgx;
+  const size_t w0 = (size_t)by * cnt0 + (size_t)bx * 128;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    Sw[w0 + h * 64 + lane] = 0ull;
+    Uw[w0 + h * 64 + lane] = ~0ull;
+  }
+  if (lane == 0) Lpart[((size_t)tgy + by) * tgx + bx] = fmax(0.0, gfold);
+  // (post_partials' row of a tile with every candidate in U: no safe candidate, no decision in the band, no keys)
+  if (lane < kFuseRow) {
+    unsigned long long v = 0ull;
+    if (lane == 0) v = ~0ull;
+    else if (lane == 2) v = 64ull * 128ull;
+    else if (lane >= kFuseVmin && lane < kFuseRmax) v = ~0ull;
+    cpart[(size_t)lane * pcap + tile] = v;
+  }
+}
+
+// Positions in a list of the tiles a 1024-thread workgroup holds in one round (tile = 1024 round + thread), three classes: a ballot per
+// class gives the rank inside the wave, every thread sums the 16 waves' counts from LDS.  Returns the thread's position in the list for
+// its class k (0..2; -1: none) -- base[k] + the tiles of class k before it in this round -- and adds the round's totals to base[].
+__device__ __forceinline__ unsigned int sched_rank3(int k, unsigned int (&base)[3], unsigned int* __restrict__ sh /* [3][16] */) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  unsigned int rank = 0u;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const unsigned long long m = __ballot(k == j);
+    if (k == j) rank = (unsigned int)__popcll(m & below);
+    if (lane == 0) sh[j * 16 + wave] = (unsigned int)__popcll(m);
+  }
+  __syncthreads();
+  unsigned int pos = 0u, tot[3] = {0u, 0u, 0u};
+#pragma unroll
+  for (int j = 0; j < 3; ++j)
+    for (int w = 0; w < 16; ++w) {
+      const unsigned int c = sh[j * 16 + w];
+      if (k == j && w < wave) pos += c;
+      tot[j] += c;
+    }
+  __syncthreads();
+  const unsigned int r = k >= 0 ? base[k] + pos + rank : 0u;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) base[j] += tot[j];
+  return r;
+}
+
+// The constraint's list (one workgroup, behind k_bl_sched_tiles1): classes 1, 2, 3 in that order -- the tiles with gradient phases,
+// the longest, first --, tile order within a class.  The skipped tiles' shares of the set phase's inputs: Usum (bit by of every
+// column of tile (bx, by) without a workgroup; plain stores -- the launch's own tiles OR theirs in behind), |U|, the skip count and
+// the Lipschitz key into slot 0 (sums and a maximum: the slot a tile joins does not change them).
+__global__ __launch_bounds__(1024) void k_bl_sched_list1(const uint8_t* __restrict__ cls, int ntiles, int tgx, const double* __restrict__ Lpart1,
+                                                         unsigned int* __restrict__ list, unsigned long long* __restrict__ Usum,
+                                                         unsigned long long* __restrict__ slots) {
+  __shared__ unsigned int sh[3 * 16];
+  __shared__ unsigned long long umask[64];
+  __shared__ unsigned long long lmax;
+  __shared__ unsigned int nlight;
+  const int t = threadIdx.x;
+  if (t < 64) umask[t] = 0ull;
+  if (t == 0) { lmax = 0ull; nlight = 0u; }
+  __syncthreads();
+  // (two passes: the counts per class first, so that classes 2 and 3 start behind every tile of the classes before them)
+  unsigned int cnt[3] = {0u, 0u, 0u};
+  for (int r = 0; r * 1024 < ntiles; ++r) {
+    const int i = r * 1024 + t;
+    (void)sched_rank3(i < ntiles ? (int)cls[i] - 1 : -1, cnt, sh);
+  }
+  unsigned int base[3] = {0u, cnt[0], cnt[0] + cnt[1]};
+  unsigned int nl = 0u;
+  unsigned long long gm = 0ull;
+  for (int r = 0; r * 1024 < ntiles; ++r) {
+    const int i = r * 1024 + t;
+    const int k = i < ntiles ? (int)cls[i] - 1 : -1;
+    const unsigned int p = sched_rank3(k, base, sh);
+    if (k >= 0) list[1 + p] = (unsigned int)i | (k == 1 ? 0x80000000u : 0u);
+    if (i < ntiles && k < 0) {
+      ++nl;
+      atomicOr(&umask[i % tgx], 1ull << (i / tgx));
+      const unsigned long long g = (unsigned long long)__double_as_longlong(Lpart1[i]);
+      gm = g > gm ? g : gm;
+    }
+  }
+  if (nl) { atomicAdd(&nlight, nl); atomicMax(&lmax, gm); }
+  if (t == 0) list[0] = cnt[0] + cnt[1] + cnt[2];
+  __syncthreads();
+  for (int c = t; c < tgx * 128; c += 1024) Usum[c] = umask[c >> 7];
+  if (t == 0) {
+    const unsigned long long nskip = (unsigned long long)nlight + cnt[1];
+    if (nlight) {
+      atomicAdd(&slots[(size_t)kSlotU * kColSlots], 64ull * 128ull * nlight);
+      atomicMax(&slots[(size_t)kSlotL1 * kColSlots], lmax);
+    }
+    if (nskip) atomicAdd(&slots[(size_t)kSlotSkip * kColSlots], nskip);
+  }
+}
+
+// The objective's list (one workgroup, behind the constraint's launch): the tiles that hold a safe candidate (field 1 of the
+// constraint's partial rows), in tile order.  The others' objective rows as their workgroups wrote them in a lean-2 sweep (no safe
+// candidate, no gradient phase): no u* key, no range of lcb_0, no variance key, Lipschitz row 0.
+__global__ __launch_bounds__(1024) void k_bl_sched_list2(unsigned long long* __restrict__ cpart, int pcap, int ntiles, unsigned int* __restrict__ list,
+                                                         double* __restrict__ Lpart0) {
+  __shared__ unsigned int sh[3 * 16];
+  const int t = threadIdx.x;
+  const unsigned long long* nS = cpart + (size_t)1 * pcap;
+  unsigned long long* orow = cpart + ntiles;
+  unsigned int base[3] = {0u, 0u, 0u};
+  for (int r = 0; r * 1024 < ntiles; ++r) {
+    const int i = r * 1024 + t;
+    const bool in = i < ntiles, has = in && nS[i] != 0ull;
+    const unsigned int p = sched_rank3(has ? 0 : -1, base, sh);
+    if (has) {
+      list[1 + p] = (unsigned int)i;
+    } else if (in) {
+      Lpart0[i] = 0.0;
+#pragma unroll
+      for (int lane = 0; lane < kFuseRow; ++lane)
+        orow[(size_t)lane * pcap + i] = (lane <= 1 || (lane >= kFuseVmin && lane < kFuseRmax)) ? ~0ull : 0ull;
+    }
+  }
+  if (t == 0) list[0] = base[0];
+}
+
 // RB: row blocks per wave.  2 = the 128 x 128 tile above; 1 = a 64 x 128 tile for grids whose 128 x 128 tiles would leave
 // CUs without a workgroup (1024 x 1024 x 3 outputs: 192 tiles on 256 CUs) -- half the reuse of a B fragment, twice the
 // workgroups.
@@ -1562,10 +1750,25 @@ __global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelCon
                                                   const PostExtra px /* column path: one launch per output (o0), the S / U column words */) {
   extern __shared__ double lds[];               // [2][A: 8 x 256 | B: 8 x 256] (+ 2 KB of bit pieces behind them, column path)
   const int o = px.o0 + (int)blockIdx.z;
+  // r07: a launch over a tile list (PostExtra::tlist) takes its tile from entry blockIdx.x of a 1-D grid; every index below that names
+  // the tile -- row block, strip, the words, the partial rows, the gate's table -- comes from (bx, by) and the tile grid (tgx, tgy)
+  const bool listed = ROLE != 0 && px.tlist != nullptr;
+  unsigned int ent = 0u;
+  if (listed) {
+    if (blockIdx.x >= px.tlist[0]) {
+#ifdef SBO_PHASE_CLOCKS
+      if (threadIdx.x == 0) { const unsigned long long t_ = wall_clock64(); wg_trace_row(o, t_, t_, t_, 0xffffffu, 3u); }
+#endif
+      return;                                   // (past the list: the tile was written by the list's kernels)
+    }
+    ent = px.tlist[1 + blockIdx.x];
+  }
+  const unsigned int tgx = listed ? (unsigned int)px.tgx : gridDim.x, tgy = listed ? (unsigned int)px.tgy : gridDim.y;
+  const unsigned int bx = listed ? (ent & 0xffffffu) % tgx : blockIdx.x, by = listed ? (ent & 0xffffffu) / tgx : blockIdx.y;
   PostCtx cx;
   cx.lds = lds;
   cx.tid = threadIdx.x; cx.lane = cx.tid & 63; cx.wave = cx.tid >> 6;
-  cx.rb0 = blockIdx.y * (4 * RB); cx.cs0 = blockIdx.x * 8; cx.nrb = nrb; cx.ncs = ncs;
+  cx.rb0 = by * (4 * RB); cx.cs0 = bx * 8; cx.nrb = nrb; cx.ncs = ncs;
   cx.ucnt0 = (unsigned int)cs.count[0];
   cx.nlines = nlines;
   cx.full = (long long)(cx.rb0 + 4 * RB) * 16 <= nlines && (long long)(cx.cs0 + 8) * 16 <= cs.count[0];
@@ -1598,7 +1801,7 @@ __global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelCon
   cx.rmax = -1.0;
   // column path: a tile is 64 rows (one segment of the column words) x 128 columns
   const bool cbits = RB == 1 && ROLE == 1 && px.cb.Sw != nullptr && o == 1, obits = RB == 1 && ROLE == 2 && px.cb.Sw != nullptr && o == 0;
-  const size_t ctile = (size_t)blockIdx.y * gridDim.x + blockIdx.x, ntile = (size_t)gridDim.x * gridDim.y;
+  const size_t ctile = (size_t)by * tgx + bx, ntile = (size_t)tgx * tgy;
   // (objective: how many safe candidates the constraint's launch counted in this tile -- field 1 of its partial row)
   const unsigned long long tile_nS = obits ? cpart[(size_t)1 * pcap + ctile] : 0ull;
   cx.role = cbits ? 1 : ((obits && tile_nS != 0ull) ? 2 : 0);
@@ -1623,7 +1826,9 @@ __global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelCon
   const int KS1 = imode ? eff[4 * (4 * o + 1)] : KSm, KS2 = imode ? eff[4 * (4 * o + 2)] : KSm, KS3 = imode ? eff[4 * (4 * o + 3)] : KSm;
 #ifdef SBO_PHASE_CLOCKS
   unsigned long long clk_ = wall_clock64();
-  const unsigned int clk_row_ = ((unsigned int)o * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+  const unsigned long long clk_in_ = clk_;
+  unsigned long long clk_part_ = clk_;
+  const unsigned int clk_row_ = ((unsigned int)o * tgy + by) * tgx + bx;
 #endif
   // The gradient phases (their maxima are the Lipschitz keys, models/SafeOpt.py:68-83) run on the tiles that can hold the grid's
   // maximum: the tile's largest coarse sample + the plan's bound on what lies between the samples reaches the grid's largest
@@ -1632,7 +1837,7 @@ __global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelCon
   bool run2 = true, run3 = true;
   double gfold = 0.0;                       // (uniform: scalar registers -- folded in behind the phases)
   if (gtmax) {
-    const size_t nt = (size_t)gridDim.x * gridDim.y, tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const size_t nt = ntile, tile = ctile;
     const double* slack = gtmax + (size_t)px.q * 2 * nt;
     const double t0 = gtmax[((size_t)o * 2 + 0) * nt + tile], t1 = gtmax[((size_t)o * 2 + 1) * nt + tile];
     const double G0 = __longlong_as_double((long long)gkey[2 * o + 0]), G1 = __longlong_as_double((long long)gkey[2 * o + 1]);
@@ -1651,21 +1856,26 @@ __global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelCon
   // which every candidate is in U, written here; its gradient phases run as the gate says.  Nothing of this sweep reads its mean /
   // var: the set phase reads the constraint's posterior on tiles with a safe candidate only (G within S), and the audit checks a
   // sample that lands here against the enclosure instead (guard.hip).
+  // (r07, a listed launch: the list's kernel took the decision, wrote the skip byte and counted the tile; its entry carries it)
   bool cskip = false;
   if (ROLE == 1 && cbits && px.lean >= 2 && px.encl != nullptr) {
-    bool dec = true;
-    if (cx.tid < 128) {
-      const double4 e = reinterpret_cast<const double4*>(px.encl)[ctile * 128 + cx.tid];
-      dec = encl_unsafe(e.x, e.y, e.z, e.w, cx.bconf, cx.bb, cx.gb_on, cx.lband);
+    if (listed) {
+      cskip = (ent >> 31) != 0u;
+    } else {
+      bool dec = true;
+      if (cx.tid < 128) {
+        const double4 e = reinterpret_cast<const double4*>(px.encl)[ctile * 128 + cx.tid];
+        dec = encl_unsafe(e.x, e.y, e.z, e.w, cx.bconf, cx.bb, cx.gb_on, cx.lband);
+      }
+      cskip = __syncthreads_and(dec ? 1 : 0) != 0;
+      if (cx.tid == 0) px.skip[ctile] = cskip ? 1 : 0;
+      if (cskip && cx.tid == 0) atomicAdd(&px.cb.slots[(size_t)kSlotSkip * kColSlots + (ctile & (kColSlots - 1))], 1ull);
     }
-    cskip = __syncthreads_and(dec ? 1 : 0) != 0;
-    if (cx.tid == 0) px.skip[ctile] = cskip ? 1 : 0;
     if (cskip) {
       cx.role = 0;
       cx.skip_store = true;
       cx.cU = 64 * 128 / 256;               // (every candidate in U, spread over the threads: the partials sum to 8192)
       for (int i = cx.tid; i < 4 * 128; i += 256) cx.lds_bits[i] = 0xffff0000u;      // (S pieces 0, U pieces all ones)
-      if (cx.tid == 0) atomicAdd(&px.cb.slots[(size_t)kSlotSkip * kColSlots + (ctile & (kColSlots - 1))], 1ull);
     }
   }
   const bool skip_tile = (ROLE == 2 && obits && tile_nS == 0ull && px.lean >= 2) || cskip;
@@ -1677,7 +1887,7 @@ __global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelCon
     // the thread's own S bits: rows 16 wave + 4 t + (lane >> 4) of the segment, column (cs0 + s2) 16 + (lane & 15)
 #pragma unroll
     for (int s2 = 0; s2 < 8; ++s2) {
-      const unsigned long long w = px.cb.Sw[(size_t)blockIdx.y * cx.ucnt0 + (unsigned int)(cx.cs0 + s2) * 16u + (cx.lane & 15)];
+      const unsigned long long w = px.cb.Sw[(size_t)by * cx.ucnt0 + (unsigned int)(cx.cs0 + s2) * 16u + (cx.lane & 15)];
       cx.bw[s2] = (unsigned int)(w >> (16 * cx.wave + (cx.lane >> 4))) & 0x1111u;
     }
   }
@@ -1691,6 +1901,9 @@ __global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelCon
   if (run3) post_phase<3, RB, ROLE>(cx, A3, SBo, KBm, KS3, nullptr, cg1, 0.0, 0.0, gmax, acc, xn0, pre, nullptr, nullptr, 0);
   gmax = fmax(gmax, gfold);
   SBO_CLK(2);
+#ifdef SBO_PHASE_CLOCKS
+  clk_part_ = clk_;
+#endif
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const double other = __shfl_xor(gmax, off);
@@ -1701,9 +1914,9 @@ __global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelCon
   // a row per wave made that merge (one workgroup, 16384 rows of 88 bytes on config H) the longest job of the launch it shares
   // (column path: the constraint's rows first, the objective's rows behind them)
   post_partials<4>(cx.lds, cx.lane, cx.wave, gmax, fuse || cbits, cx.cS, cx.cU, obits ? -cx.umin : cx.rmax, cx.cB, cx.vminS,
-                   Lpart + ((size_t)o * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x,
+                   Lpart + ((size_t)o * tgy + by) * tgx + bx,
                    cpart + (obits ? ntile : (fmulti && o >= 1 ? (size_t)(o - 1) * ntile : (size_t)0)) + ctile, pcap, obits,
-                   (cbits || obits) ? px.cb.slots : nullptr, (int)(ctile & (kColSlots - 1)), o, cbits ? (int)blockIdx.y : -1, (int)blockIdx.x, cx.xmin, fmulti);
+                   (cbits || obits) ? px.cb.slots : nullptr, (int)(ctile & (kColSlots - 1)), o, cbits ? (int)by : -1, (int)bx, cx.xmin, fmulti);
   if (cbits && cx.tid < 128) {
     // the tile's words: column tid, the four waves' 16-row pieces (written before the barriers of post_partials)
     unsigned long long sw = 0ull, uw = 0ull;
@@ -1714,15 +1927,17 @@ __global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelCon
       uw |= (unsigned long long)(pc >> 16) << (16 * w);
     }
     const size_t col = (size_t)cx.cs0 * 16u + cx.tid;
-    px.cb.Sw[(size_t)blockIdx.y * cx.ucnt0 + col] = sw;
-    px.cb.Uw[(size_t)blockIdx.y * cx.ucnt0 + col] = uw;
-    if (uw != 0ull) atomicOr(&px.cb.Usum[col], 1ull << blockIdx.y);
+    px.cb.Sw[(size_t)by * cx.ucnt0 + col] = sw;
+    px.cb.Uw[(size_t)by * cx.ucnt0 + col] = uw;
+    if (uw != 0ull) atomicOr(&px.cb.Usum[col], 1ull << by);
   }
   SBO_CLK(3);
 #ifdef SBO_PHASE_CLOCKS
   if (threadIdx.x == 0) {
     g_phase_clk[clk_row_ & (kPhaseClkRows - 1)][4] += (unsigned long long)((run2 ? 1 : 0) + (run3 ? 1 : 0));
     g_phase_clk[clk_row_ & (kPhaseClkRows - 1)][5] += 1ull;
+    if (ROLE != 0)
+      wg_trace_row(o, clk_in_, clk_part_, clk_, (unsigned int)ctile, skip_tile ? ((!cskip || !(run2 || run3)) ? 1u : 2u) : 0u);
   }
 #endif
 }
@@ -1736,6 +1951,17 @@ extern "C" int sbo_debug_phase_clocks(unsigned long long* out /* [16]: sums over
   if (reset) {
     std::fill(h.begin(), h.end(), 0ull);
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase_clk), h.data(), sizeof(unsigned long long) * h.size()) != hipSuccess) return 1;
+  }
+  return 0;
+}
+// r07: the per-workgroup rows of the column path's two launches (g_wg_trace: [o][dispatch index][8]); reset: zero them afterwards
+extern "C" int sbo_debug_wg_trace(unsigned long long* out /* [2][rows][8] */, int rows, int reset) {
+  if (rows != kWgTraceRows) return 2;
+  const size_t bytes = sizeof(unsigned long long) * 2 * kWgTraceRows * 8;
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wg_trace), bytes) != hipSuccess) return 1;
+  if (reset) {
+    std::vector<unsigned long long> z(bytes / sizeof(unsigned long long), 0ull);
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_wg_trace), z.data(), bytes) != hipSuccess) return 1;
   }
   return 0;
 }
@@ -3543,6 +3769,8 @@ int launch_posterior_bilinear(sbo_ctx* c) {
   }
   bool record_encl = false;
   double* encl = nullptr;
+  uint8_t* sched_cls = nullptr;
+  unsigned int *sched_l1 = nullptr, *sched_l2 = nullptr;
   if (colw) {
     if ((rc = col_words_prepare(c, cnt0, nlines, &px.cb))) return rc;
     px.lean = c->col_lean;
@@ -3564,6 +3792,14 @@ int launch_posterior_bilinear(sbo_ctx* c) {
       px.skip = (uint8_t*)c->bl_encl.p + ebytes;
       c->k1_skip_armed = true;
     }
+    // r07: lean 2 -- the objective's launch over the tiles with a safe candidate, and, once the enclosures decide skips, the
+    // constraint's over the tiles that need a workgroup (k_bl_sched_tiles1 and on).  [class bytes][list 1][list 2]
+    if (c->k1_sched && c->col_lean >= 2) {
+      if ((rc = ensure(c->bl_sched, ((ntiles + 15) & ~(size_t)15) + 2 * sizeof(unsigned int) * (ntiles + 1)))) return rc;
+      sched_cls = (uint8_t*)c->bl_sched.p;
+      sched_l1 = (unsigned int*)(sched_cls + ((ntiles + 15) & ~(size_t)15));
+      sched_l2 = sched_l1 + ntiles + 1;
+    }
   }
   // (the fused classification counts its sign tests inside the plan's guard band)
   const GuardBand* gb_fused = (c->guard_band && !c->is_shadow && c->bl.band_ready && c->gb.p) ? (const GuardBand*)c->gb.p : nullptr;
@@ -3577,7 +3813,25 @@ int launch_posterior_bilinear(sbo_ctx* c) {
     px.o0 = colw ? 1 - part : 0;
     const bool last = !colw || part == 1;
     auto kpost = !colw ? k_bpost<rbw, 0> : (part == 0 ? k_bpost<rbw, 1> : k_bpost<rbw, 2>);
-    hipExtLaunchKernelGGL(kpost, dim3(gx, gy, (unsigned)(colw ? 1 : q)), dim3(256), lds, c->stream, nullptr,
+    // r07: the tile lists (k_bl_sched_tiles1 / _list1 / _list2), built on this stream right in front of the launch that reads them
+    px.tlist = nullptr;
+    if (sched_l1 && part == 0 && px.encl) {
+      hipLaunchKernelGGL(k_bl_sched_tiles1, dim3((gx * gy + 3) / 4), dim3(256), 0, c->stream, mc, (const double*)px.encl, (int)(gx * gy), (int)gx,
+                         (int)gy, (unsigned int)cnt0, c->fuse_b, gb_fused, pl.gtmax, pl.gkey, q, px.skip, sched_cls, px.cb.Sw, px.cb.Uw,
+                         (double*)c->bl_lpart.p, (unsigned long long*)c->cpart.p, c->cpart_cap);
+      hipLaunchKernelGGL(k_bl_sched_list1, dim3(1), dim3(1024), 0, c->stream, (const uint8_t*)sched_cls, (int)(gx * gy), (int)gx,
+                         (const double*)c->bl_lpart.p + (size_t)rows_out, sched_l1, px.cb.Usum, px.cb.slots);
+      px.tlist = sched_l1;
+    }
+    if (sched_l2 && part == 1) {
+      hipLaunchKernelGGL(k_bl_sched_list2, dim3(1), dim3(1024), 0, c->stream, (unsigned long long*)c->cpart.p, c->cpart_cap, (int)(gx * gy), sched_l2,
+                         (double*)c->bl_lpart.p);
+      px.tlist = sched_l2;
+    }
+    px.tgx = (int)gx;
+    px.tgy = (int)gy;
+    const dim3 grid = px.tlist ? dim3(gx * gy) : dim3(gx, gy, (unsigned)(colw ? 1 : q));
+    hipExtLaunchKernelGGL(kpost, grid, dim3(256), lds, c->stream, nullptr,
                           (c->lmax_defer && last) ? c->ev[1] : ((colw && part == 0) ? c->ev_col[0] : nullptr), 0,
                           mc, cs, (const double*)c->bl_BtA.p, pl.sBtA, (const double*)c->bl_P0f.p, pl.sP0f, (const double*)c->bl_VA.p,
                           pl.sVA, (const double*)c->bl_SBf.p, pl.sSBf, pl.KB0, pl.KS0, pl.KBm, pl.KSm, pl.KBm2, pl.nrb, pl.ncs0, nlines,

@@ -78,6 +78,11 @@ struct PostExtra {
   // (k_bl_enclose), and one byte per tile that says whether the tile was left unevaluated; nullptr: every tile is evaluated
   const double* encl;
   uint8_t* skip;
+  // lean >= 2, k1_sched (r07): nullptr, or the tile list of this launch -- [0] = entries, then one entry per workgroup of a 1-D grid:
+  // the tile (by * tgx + bx) in bits 0..23, bit 31 = a constraint tile the list's kernel proved unsafe that still runs the gradient
+  // phases.  Workgroup i takes entry i, and exits at once when i >= [0].  Tiles not in the list were written by the list's kernels.
+  const unsigned int* tlist;
+  int tgx, tgy;  // the tile grid (tiles per row, tile rows) behind the list
 };
 
 // K1b (bilinear.hip): device tables of the reduced-basis posterior on a 2-D grid, valid for one (model, candidates) pair
@@ -271,6 +276,8 @@ struct sbo_ctx {
   bool k1_skip_armed = false;   // it could leave constraint tiles unevaluated: bl_encl's skip bytes are its record
   bool k1_encl_check = false;   // a K1b column-path launch on a plan whose enclosures were recorded: what it stored lies inside them
   size_t k1_encl_tiles = 0;     // tiles of the grid bl_encl was laid out for (the skip bytes sit behind 4 x 128 doubles per tile)
+  sbo::DevBuf bl_sched;         // K1b column path, lean 2 (r07): per-tile classes + the tile lists of the constraint's and the objective's launch
+  int k1_sched = 1;             // option: 1 = those two launches take their tiles from per-sweep lists (lean 2); 0: one workgroup per tile
   sbo::DevBuf cpart;   // per-workgroup partials of k_classify, field-major [kClassifyRow][cpart_cap]
   int cpart_cap = 0;   // row capacity the last writer of cpart laid its rows out with
   long long comm_bytes = 0;   // collectives of the running sweep: bytes handed over (send side), calls, and -- option comm_events --
