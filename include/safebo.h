@@ -154,6 +154,22 @@ typedef struct sbo_tr_result {
   int32_t guard_passes, reserved_g;
 } sbo_tr_result;
 
+/* StableOpt's robust min-max on a joint (xc, d) grid (models/StableOpt.py:139-164): axes 0 .. n_control_axes - 1 of the resident grid
+ * are the controls xc, the rest the disturbance d (the slow axes: every disturbance point is one contiguous plane of the control
+ * sub-grid).  Flat indices of xc / d are those of the two sub-grids (axis 0 / axis n_control_axes the fastest).                        */
+typedef struct sbo_robust_result {
+  int64_t index;                 /* argmin over robust-safe xc (min_d lcb_c >= 0 for every constraint c) of max_d bound_0; -1: none    */
+  double  xc[SBO_MAX_D];
+  double  value;                 /* min over robust-safe xc of max_d bound_0 (+inf when index == -1)                                    */
+  int64_t worst_d_index;         /* argmax_d bound_0(xc*, d), ties -> lowest index (-1 when index == -1)                                */
+  double  worst_d[SBO_MAX_D];
+  int64_t candidate_index;       /* global flat index of (xc*, d*) on the joint grid                                                   */
+  int64_t count_control, count_disturbance, count_safe;   /* |xc grid|, |d grid|, robust-safe controls                                 */
+  int64_t guard_band, guard_rechecks;    /* as in sbo_safeopt_result; the re-evaluation reruns the exact kernel on the whole grid (rechecks
+                                            = this rank's candidates)                                                                   */
+  int32_t guard_passes, reserved_g;
+} sbo_robust_result;
+
 /* per-kernel device time of the last sweep / posterior call, measured with HIP events on the
  * library's stream (feeds bench.py's roofline.achieved) */
 typedef struct sbo_profile {
@@ -244,6 +260,12 @@ int sbo_model_set_list(sbo_ctx* ctx, int dtype, const char* kernel, int n, int d
                        const double* X_std, const double* Y_mean, const double* Y_std, const double* X_norm,
                        const double* Y_norm, const double* hypopt, const double* const* invK_list);
 
+/* The same with the prior mean given: mean_prior[q] in normalised units (models/GP_Robust.py:322-324 uses zero for every output).
+ * mean_prior == NULL behaves exactly like sbo_model_set_list (GP_Safe's prior: 0 for the objective, -2 Y_mean / Y_std otherwise). */
+int sbo_model_set_prior(sbo_ctx* ctx, int dtype, const char* kernel, int n, int d, int q, const double* X_mean,
+                        const double* X_std, const double* Y_mean, const double* Y_std, const double* X_norm,
+                        const double* Y_norm, const double* hypopt, const double* const* invK_list, const double* mean_prior);
+
 /* ---- candidates (resident in HBM until replaced) ------------------------------------------- */
 /* One more observation (normalised coordinates / outputs, the caller's frozen X_mean, X_std, Y_mean, Y_std) under the
  * hyper-parameters of the last sbo_model_set: the lower factor gains one row and alpha is updated in O(n^2) on the
@@ -277,6 +299,14 @@ int sbo_sweep_safeopt(sbo_ctx* ctx, const sbo_sweep_opts* opts, sbo_safeopt_resu
 int sbo_sweep_goose(sbo_ctx* ctx, const sbo_sweep_opts* opts, sbo_goose_result* result);
 /* trust-region acquisition of models/GP_TR.py:43-51 on the resident candidates: x_0[d] centre, r radius */
 int sbo_sweep_tr(sbo_ctx* ctx, const sbo_sweep_opts* opts, const double* x_0, double r, sbo_tr_result* result);
+/* Robust min-max of models/StableOpt.py:139-152 on the resident grid (sbo_candidates_grid / _sharded; a point list is SBO_E_INVALID):
+ * kind (SBO_MEAN / SBO_UCB / SBO_LCB) is the objective's bound, the constraints always use their LCB.  n_control_axes in [1, d - 1].
+ * fp64 models only (SBO_F32: SBO_E_UNSUPPORTED -- an fp32 posterior with an fp64 recheck is not implemented here).  opts.lean and
+ * opts.reference_quirk_L_index are ignored, opts.want_masks too (the masks of the last SafeOpt / GoOSE sweep stay as they were);
+ * opts.posterior_ready is honoured.  sbo_profile: posterior_ms, argreduce_ms (reduction over d + mask + arg-min), guard_ms, total_ms. */
+int sbo_sweep_robust(sbo_ctx* ctx, const sbo_sweep_opts* opts, int n_control_axes, int kind, sbo_robust_result* result);
+/* the per-control arrays of the last robust sweep: f_out[Nc] = max_d bound_0, g_out[q - 1][Nc] = min_d lcb_c; either may be NULL */
+int sbo_robust_get(sbo_ctx* ctx, double* f_out, double* g_out);
 /* BO.explore_safeset(target) for a target of the caller's choosing (models/GoOSE.py:116-119): the candidate of the LAST sweep's safe set
  * closest to target[d] (scipy cdist's Euclidean distance, ties -> lowest flat index); x_out[SBO_MAX_D] may be NULL.
  * SBO_E_EMPTY_SAFE_SET when S_t is empty.  (sbo_sweep_goose answers the same question for its own target in its result.) */

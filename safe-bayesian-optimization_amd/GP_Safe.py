@@ -25,6 +25,9 @@ FLOAT32_EPS = float(np.finfo(np.float32).eps)
 
 
 class GP:
+    noise_lower_bound = -5.0     # lower bound of log sigma_n in the fit (models/GP_Safe.py:205)
+    mean_prior_zero = False      # True: prior mean 0 for every output (models/GP_Robust.py:322-324)
+
     def __init__(self, plant_system, device: int = 0, dtype: str = "f64", seed: int = 42) -> None:
         self.plant_system = plant_system
         self.n_fun = len(plant_system)
@@ -52,9 +55,13 @@ class GP:
     def _sync_model(self):
         """Upload ``inference_datasets`` when it changed since the last upload."""
         if self._uploaded_version != self._model_version:
-            self.engine.set_model(self.inference_datasets, dtype=self.dtype, kernel=self.kernel)
+            self.engine.set_model(self.inference_datasets, dtype=self.dtype, kernel=self.kernel, mean_prior=self._mean_prior())
             self._uploaded_version = self._model_version
             self._cand_token = None
+
+    def _mean_prior(self, ds=None):
+        ds = self.inference_datasets if ds is None else ds
+        return np.zeros(np.asarray(ds["Y_mean"]).shape[0]) if self.mean_prior_zero else None
 
     # ---- data sampling (models/GP_Safe.py:30-78) -------------------------------------------------------------
     def Ball_sampling(self, x_dim, n_sample, r_i, key=None):
@@ -118,7 +125,7 @@ class GP:
         """One GP per output; bounds [-1.5, 1.5]^(d+1) x [-5, -2] searched by SciPy DE (models/GP_Safe.py:194-234),
         then invK = inv(K + (sn2 + float32 eps) I)."""
         d = self.nx_dim
-        bounds = np.array([[-1.5, 1.5]] * (d + 1) + [[-5.0, -2.0]])
+        bounds = np.array([[-1.5, 1.5]] * (d + 1) + [[self.noise_lower_bound, -2.0]])
         hypopt = np.zeros((d + 2, self.ny_dim))
         invKopt = []
         for i in range(self.ny_dim):
@@ -219,7 +226,8 @@ class GP:
         is the batched form the reference reaches with ``vmap`` and returns (mean[N, q], var[N, q])."""
         if inference_dataset is not None and inference_dataset is not self.inference_datasets:
             eng = self.engine
-            eng.set_model(inference_dataset, dtype=self.dtype, kernel=getattr(self, "kernel", "RBF"))
+            eng.set_model(inference_dataset, dtype=self.dtype, kernel=getattr(self, "kernel", "RBF"),
+                          mean_prior=self._mean_prior(inference_dataset))
             self._uploaded_version = -1
         else:
             self._sync_model()

@@ -1,0 +1,188 @@
+"""Host-side mirror of the reference's StableOpt class (models/StableOpt.py) on the MI355X sweep engine.
+
+The reference solves the robust problem min_xc max_d f(xc, d) s.t. min_d lcb_c(xc, d) >= 0 with a SciPy differential evolution over
+xc whose every callback runs SLSQP multistarts over d, one scalar posterior per step (models/StableOpt.py:96-152).  Here the same
+definitions are evaluated on the joint tensor grid of ``bound`` (controls, the fast axes) x ``bound_d`` (disturbances, the slow
+axes) by one device sweep (``sbo_sweep_robust``): the posterior of every grid point, max / min over the disturbance planes, the
+robust-safe mask and a masked arg-min.  Method names and return conventions follow the reference:
+
+    GP_m = StableOpt.BO(plant_system, bound, bound_d, b)             # + grid=(..), grid_d=(..) points per axis
+    xc_star, value = GP_m.Minimize_Maximise(GP_m.ucb)
+    d_star, worst = GP_m.Maximise_d_with_constraints(GP_m.ucb, xc_star)
+
+``mean/ucb/lcb(xc, d, i)`` take 1-D ``xc`` and ``d`` (a scalar, as the reference) or, batched, ``xc`` [N, nxc] with ``d`` [N, nd].
+The single-``xc`` inner problems (``Maximise_d``, ``Minimise_d``, ``Maximise_d_with_constraints``) run on the candidate list
+{xc} x (disturbance grid) through ``sbo_bounds``; on the grid, ties go to the lowest index (np.argmax / np.argmin order).
+"""
+from __future__ import annotations
+
+import numpy as np
+from scipy.stats import qmc
+
+from .GP_Robust import GP
+
+
+def _axis_points(lo, hi, cnt):
+    """Grid positions of one axis exactly as the device computes them (csrc: cand_coords): lo + i step, the last one hi."""
+    if cnt == 1:
+        return np.array([lo])
+    step = (hi - lo) / (cnt - 1)
+    x = lo + np.arange(cnt) * step
+    x[-1] = hi
+    return x
+
+
+class BO(GP):
+    def __init__(self, plant_system, bound, bound_d, b, grid=None, grid_d=None, device: int = 0, dtype: str = "f64", seed: int = 42):
+        GP.__init__(self, plant_system, device=device, dtype=dtype, seed=seed)
+        self.bound = np.asarray(bound, dtype=np.float64)
+        self.bound_d = np.asarray(bound_d, dtype=np.float64)
+        if self.bound.ndim != 2 or self.bound_d.ndim != 2 or self.bound.shape[1] != 2 or self.bound_d.shape[1] != 2:
+            raise ValueError("bound and bound_d must be [n, 2] arrays")
+        self.nxc_dim = self.bound.shape[0]      # controlled dimensions
+        self.nd_dim = self.bound_d.shape[0]     # disturbance dimensions
+        self.b = b
+        self.grid = tuple(int(g) for g in (grid if grid is not None else (201,) * self.nxc_dim))
+        self.grid_d = tuple(int(g) for g in (grid_d if grid_d is not None else (101,) * self.nd_dim))
+        if len(self.grid) != self.nxc_dim or len(self.grid_d) != self.nd_dim or min(self.grid + self.grid_d) < 1:
+            raise ValueError("grid / grid_d must give a positive point count per control / disturbance axis")
+        self._cand_token = None
+
+    # ---- plant ------------------------------------------------------------------------------------------------
+    def calculate_plant_outputs(self, x, noise=0):
+        """Each plant returns (output, disturbance) (models/StableOpt.py:23-30): (outputs[q], the last plant's disturbance)."""
+        plant_output, disturbance = [], 0.0
+        for plant in self.plant_system:
+            output, disturbance = plant(x, noise)
+            plant_output.append(output)
+        return np.array(plant_output), disturbance
+
+    def Data_sampling_with_perbutation(self, n_sample, x=None, r=None):
+        """Sobol samples of xc over ``bound`` and d over ``bound_d`` (models/StableOpt.py:32-43, scipy.stats.qmc in place of sobol_seq);
+        the reference calls the plants with (xc_samples, d_samples) as their two arguments."""
+        if x is not None or r is not None:
+            raise ValueError("only the x=None, r=None form is defined (models/StableOpt.py:33)")
+        fx = qmc.Sobol(self.nxc_dim, scramble=False).random(n_sample)
+        fd = qmc.Sobol(self.nd_dim, scramble=False).random(n_sample)
+        xc = fx * (self.bound[:, 1] - self.bound[:, 0]) + self.bound[:, 0]
+        d = fd * (self.bound_d[:, 1] - self.bound_d[:, 0]) + self.bound_d[:, 0]
+        plant_output = self.calculate_plant_outputs(xc, d)[0]
+        return np.hstack((xc, d)), plant_output
+
+    def Data_sampling_output_and_perturbation(self, n_sample, x_0, r, noise=0.):
+        """Ball samples around x_0; every plant returns (output, disturbance) (models/StableOpt.py:45-62): (X, Y, D)."""
+        x_0 = np.asarray(x_0, dtype=np.float64)
+        X = self.Ball_sampling(x_0.shape[0], n_sample, r, self.key) + x_0
+        Y = np.zeros((n_sample, self.n_fun))
+        D = np.zeros((n_sample, self.nd_dim))
+        for i in range(n_sample):
+            for j in range(self.n_fun):
+                y, dist = self.plant_system[j](X[i], noise)
+                Y[i, j] = y
+            D[i] = dist
+        return X, Y, D
+
+    # ---- bounds (models/StableOpt.py:64-95) --------------------------------------------------------------------
+    def _bound_value(self, xc, d, i, kind):
+        xc = np.asarray(xc, dtype=np.float64)
+        d = np.asarray(d, dtype=np.float64)
+        if xc.ndim == 1 and d.ndim == 1:
+            pts = np.concatenate((xc, d))[None, :]
+            single = True
+        elif xc.ndim == 2 and d.ndim == 2 and xc.shape[0] == d.shape[0]:
+            pts = np.hstack((xc, d))
+            single = False
+        else:
+            raise ValueError("xc or d needs to be in 1d")
+        self._sync_model()
+        self.engine.set_points(pts)
+        self._cand_token = None            # (the resident joint grid is gone)
+        out = self.engine.bounds(self.b, i, kind)
+        return out[0] if single else out
+
+    def mean(self, xc, d, i):
+        return self._bound_value(xc, d, i, "mean")
+
+    def ucb(self, xc, d, i):
+        return self._bound_value(xc, d, i, "ucb")
+
+    def lcb(self, xc, d, i):
+        return self._bound_value(xc, d, i, "lcb")
+
+    def _kind_of(self, fun):
+        for kind in ("ucb", "lcb", "mean"):
+            if fun == getattr(self, kind):
+                return kind
+        raise ValueError("fun needs to be either self.ucb, lcb or mean")
+
+    # ---- grids ------------------------------------------------------------------------------------------------------
+    def disturbance_points(self):
+        """[Nd, nd] points of the disturbance grid in flat order (axis 0 fastest)."""
+        axes = [_axis_points(lo, hi, c) for (lo, hi), c in zip(self.bound_d, self.grid_d)]
+        mesh = np.meshgrid(*axes, indexing="ij")
+        return np.stack([m.ravel(order="F") for m in mesh], axis=1)
+
+    def control_point(self, index: int):
+        return self._sub_point(index, self.bound, self.grid)
+
+    def disturbance_point(self, index: int):
+        return self._sub_point(index, self.bound_d, self.grid_d)
+
+    @staticmethod
+    def _sub_point(g, bound, grid):
+        x = np.empty(len(grid))
+        for a, cnt in enumerate(grid):
+            i = g % cnt
+            g //= cnt
+            x[a] = _axis_points(bound[a, 0], bound[a, 1], cnt)[i]
+        return x
+
+    def _grid_resident(self):
+        self._sync_model()
+        token = (self._model_version, self.grid, self.grid_d)
+        if self._cand_token != token:
+            lo = np.concatenate((self.bound[:, 0], self.bound_d[:, 0]))
+            hi = np.concatenate((self.bound[:, 1], self.bound_d[:, 1]))
+            self.engine.set_grid(lo, hi, self.grid + self.grid_d)
+            self._cand_token = token
+
+    def _on_disturbance_grid(self, xc, i, kind):
+        xc = np.asarray(xc, dtype=np.float64).reshape(-1)
+        if xc.shape != (self.nxc_dim,):
+            raise ValueError("xc needs to be in 1d")
+        D = self.disturbance_points()
+        return D, self._bound_value(np.repeat(xc[None, :], D.shape[0], axis=0), D, i, kind)
+
+    # ---- robust problems (models/StableOpt.py:97-164) -------------------------------------------------------------
+    def Maximise_d(self, fun, xc, i):
+        """max over the disturbance grid of fun(xc, d, i)."""
+        return float(np.max(self._on_disturbance_grid(xc, i, self._kind_of(fun))[1]))
+
+    def Minimise_d(self, fun, xc, i):
+        """min over the disturbance grid of fun(xc, d, i)."""
+        return float(np.min(self._on_disturbance_grid(xc, i, self._kind_of(fun))[1]))
+
+    def robust_sweep(self, fun=None) -> dict:
+        """One ``sbo_sweep_robust`` on the joint grid: the engine's result dict (index, xc, value, worst_d_index, worst_d, counts, guard)."""
+        kind = "ucb" if fun is None else self._kind_of(fun)
+        self._grid_resident()
+        return self.engine.sweep_robust(self.b, self.nxc_dim, kind)
+
+    def robust_arrays(self):
+        """(f[Nc], g[q - 1, Nc]) of the last ``Minimize_Maximise`` / ``robust_sweep``: max_d of the objective's bound, min_d lcb_c."""
+        return self.engine.robust_arrays()
+
+    def Minimize_Maximise(self, fun):
+        """argmin_xc max_d fun(xc, d, 0) s.t. min_d lcb_c(xc, d) >= 0 for every constraint -> (xc*, value).  No robust-safe control:
+        (None, inf) -- the reference's DE would return an infeasible point."""
+        res = self.robust_sweep(fun)
+        if res["index"] < 0:
+            return None, float("inf")
+        return res["xc"], res["value"]
+
+    def Maximise_d_with_constraints(self, fun, xc):
+        """argmax over the disturbance grid of fun(xc, d, 0) -> (d*, value); the constraints are not imposed, as in the reference
+        (models/StableOpt.py:154-164 builds them but does not pass them to DE)."""
+        D, v = self._on_disturbance_grid(xc, 0, self._kind_of(fun))
+        j = int(np.argmax(v))
+        return D[j], float(v[j])

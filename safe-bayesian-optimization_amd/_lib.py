@@ -64,6 +64,13 @@ class TRResult(C.Structure):
                 ("reserved_g", C.c_int32)]
 
 
+class RobustResult(C.Structure):
+    _fields_ = [("index", C.c_int64), ("xc", C.c_double * SBO_MAX_D), ("value", C.c_double), ("worst_d_index", C.c_int64),
+                ("worst_d", C.c_double * SBO_MAX_D), ("candidate_index", C.c_int64), ("count_control", C.c_int64),
+                ("count_disturbance", C.c_int64), ("count_safe", C.c_int64), ("guard_band", C.c_int64), ("guard_rechecks", C.c_int64),
+                ("guard_passes", C.c_int32), ("reserved_g", C.c_int32)]
+
+
 class Profile(C.Structure):
     _fields_ = [
         ("posterior_ms", C.c_double), ("classify_ms", C.c_double), ("expander_ms", C.c_double),
@@ -100,6 +107,7 @@ SYMBOLS = [
     ("sbo_comm_init_relay", C.c_int, [_P, C.c_int, C.c_int, RELAY_ALLREDUCE, RELAY_ALLGATHER, _P]),
     ("sbo_model_set", C.c_int, [_P, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("sbo_model_set_list", C.c_int, [_P, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("sbo_model_set_prior", C.c_int, [_P, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("sbo_model_append", C.c_int, [_P, _P, _P]),
     ("sbo_candidates_points", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int64]),
     ("sbo_candidates_grid", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, C.c_int64]),
@@ -110,6 +118,8 @@ SYMBOLS = [
     ("sbo_sweep_safeopt", C.c_int, [_P, C.POINTER(SweepOpts), C.POINTER(SafeOptResult)]),
     ("sbo_sweep_goose", C.c_int, [_P, C.POINTER(SweepOpts), C.POINTER(GooseResult)]),
     ("sbo_sweep_tr", C.c_int, [_P, C.POINTER(SweepOpts), _P, C.c_double, C.POINTER(TRResult)]),
+    ("sbo_sweep_robust", C.c_int, [_P, C.POINTER(SweepOpts), C.c_int, C.c_int, C.POINTER(RobustResult)]),
+    ("sbo_robust_get", C.c_int, [_P, _P, _P]),
     ("sbo_explore_safeset", C.c_int, [_P, _P, C.POINTER(C.c_int64), _P]),
     ("sbo_masks_get", C.c_int, [_P, C.c_int, C.c_int, _P]),
     ("sbo_nll_batch", C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),

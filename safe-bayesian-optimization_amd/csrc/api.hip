@@ -211,6 +211,7 @@ int sbo_shutdown(sbo_ctx* c) {
                     &c->maskU, &c->maskM, &c->maskG, &c->maskO, &c->dist2, &c->dist2b, &c->coarse, &c->fitbuf, &c->fitwork, &c->scal, &c->partial, &c->amb, &c->runmeta, &c->bl_P0f, &c->bl_P1A, &c->bl_T4f, &c->bl_BtA, &c->bl_SBf, &c->bl_VA, &c->bl_small, &c->bl_work, &c->bl_cheb, &c->bl_basis, &c->mwork, &c->rc_mean, &c->rc_var, &c->rc_list, &c->rc_refined, &c->Fplain, &c->alpha64, &c->blockmin, &c->blockmax, &c->cpart, &c->invk_img, &c->bl_lpart, &c->bl_grad, &c->scanlist, &c->gw, &c->Wfull, &c->Uwin, &c->ubits, &c->lane1.dist2, &c->lane1.dist2b, &c->lane1.coarse, &c->lane1.blockmin, &c->lane1.blockmax, &c->lane1.scanlist, &c->lane1.amb, &c->lane1.gw, &c->lane1.runmeta, &c->lane1.scal, &c->gather, &c->xch, &c->shard_first, &c->E0f, &c->Er, &c->AXg, &c->tn_pts, &c->tn_vals, &c->tn_work, &c->tn_W0t, &c->tn_W1t, &c->tn_probe, &c->tn_scr, &c->tn_tail, &c->fuseS, &c->fuseU, &c->tn_gather, &c->bi_params, &c->gb, &c->gb_pts, &c->gb_vals, &c->gb_probe, &c->gb_part, &c->list_scr, &c->cbS, &c->cbU, &c->cbM, &c->cbG, &c->cbUsum, &c->col_img, &c->col_bmin, &c->col_fin, &c->col_slots, &c->col_cimg, &c->col_cbmin, &c->audit_pts, &c->audit_val, &c->audit_part, &c->audit_cnt, &c->bl_encl, &c->bl_sched})
     release(*b);
   for (auto& b : c->tn_W) release(b);
+  for (DevBuf* b : {&c->rob, &c->rob_mask, &c->rob_part}) release(*b);
   for (auto& ev : c->ev)
     if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : c->ev_join)
@@ -401,7 +402,7 @@ int sbo_set_option(sbo_ctx* c, const char* key, int64_t value) {
 
 static int model_set_impl(sbo_ctx* c, int dtype, const char* kernel, int n, int d, int q, const double* X_mean,
                           const double* X_std, const double* Y_mean, const double* Y_std, const double* X_norm,
-                          const double* Y_norm, const double* hypopt, const double* const* invK) {
+                          const double* Y_norm, const double* hypopt, const double* const* invK, const double* mean_prior = nullptr) {
   // (a standing audit of the last sweep reads the outgoing model's matrix out of the build workspace this call reuses)
   if (c) guard_audit_harvest(c, true);
   if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
@@ -417,6 +418,7 @@ static int model_set_impl(sbo_ctx* c, int dtype, const char* kernel, int n, int 
   c->has_model = false;
   c->posterior_valid = false;
   c->masks_valid = false;
+  c->rob_valid = false;
   ModelConst& mc = c->mc;
   memset(&mc, 0, sizeof(mc));
   mc.n = n; mc.d = d; mc.q = q;
@@ -430,6 +432,7 @@ static int model_set_impl(sbo_ctx* c, int dtype, const char* kernel, int n, int 
     mc.Y_mean[o] = Y_mean[o];
     mc.Y_std[o] = Y_std[o];
     mc.mp[o] = (o == 0) ? 0.0 : (-2.0 * Y_mean[o]) / Y_std[o];          // GP_Safe.py:331-332
+    if (mean_prior) mc.mp[o] = mean_prior[o];                            // the caller's prior (GP_Robust.py:322-324: zero)
     mc.sf2[o] = std::exp(2.0 * hypopt[(size_t)d * q + o]);               // GP_Safe.py:338
     mc.sn2[o] = std::exp(2.0 * hypopt[(size_t)(d + 1) * q + o]) + f32eps;   // GP_Safe.py:229
     for (int a = 0; a < d; ++a) {
@@ -486,6 +489,18 @@ int sbo_model_set_list(sbo_ctx* c, int dtype, const char* kernel, int n, int d, 
   return model_set_impl(c, dtype, kernel, n, d, q, X_mean, X_std, Y_mean, Y_std, X_norm, Y_norm, hypopt, invK_list);
 }
 
+int sbo_model_set_prior(sbo_ctx* c, int dtype, const char* kernel, int n, int d, int q, const double* X_mean,
+                        const double* X_std, const double* Y_mean, const double* Y_std, const double* X_norm,
+                        const double* Y_norm, const double* hypopt, const double* const* invK_list, const double* mean_prior) {
+  if (invK_list && q >= 1 && q <= SBO_MAX_Q)
+    for (int o = 0; o < q; ++o)
+      if (!invK_list[o]) return fail(SBO_E_INVALID, "invK_list holds a NULL matrix");
+  if (mean_prior && q >= 1 && q <= SBO_MAX_Q)
+    for (int o = 0; o < q; ++o)
+      if (!std::isfinite(mean_prior[o])) return fail(SBO_E_INVALID, "mean_prior must be finite");
+  return model_set_impl(c, dtype, kernel, n, d, q, X_mean, X_std, Y_mean, Y_std, X_norm, Y_norm, hypopt, invK_list, mean_prior);
+}
+
 // one more observation under frozen hyper-parameters and normalisation, O(n^2) on the
 // device instead of a refit (the reference always refits and renormalises, models/GP_Safe.py:283-304 -- this is an
 // opt-in fast path, not its behaviour).
@@ -530,6 +545,7 @@ int sbo_model_append(sbo_ctx* c, const double* x_norm_new, const double* y_norm_
   if (c->shadow && c->shadow->has_model && (rc = sbo_model_append(c->shadow, x_norm_new, y_norm_new))) return rc;
   c->posterior_valid = false;
   c->masks_valid = false;
+  c->rob_valid = false;
   c->bl.valid = false;
     c->bi.valid = false;
   return SBO_OK;
@@ -564,6 +580,7 @@ int sbo_candidates_points(sbo_ctx* c, const void* points, int points_dtype, int6
   c->grid_total = n_local;
   c->sharded = false;
   c->has_cand = true;
+  c->rob_valid = false;
   c->bl.valid = false;
     c->bi.valid = false;
   c->posterior_valid = false;
@@ -595,6 +612,7 @@ int sbo_candidates_grid(sbo_ctx* c, int d, const double* lo, const double* hi, c
   for (auto& g : c->halo_guess) g = -1;
   c->sharded = false;
   c->has_cand = true;
+  c->rob_valid = false;
   c->bl.valid = false;
     c->bi.valid = false;
   c->posterior_valid = false;

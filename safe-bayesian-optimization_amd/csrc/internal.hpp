@@ -372,6 +372,11 @@ struct sbo_ctx {
   sbo::DevBuf rc_list;           // flagged candidate indices (long long) + counters (64-byte head)
   sbo::DevBuf rc_refined;        // uint8 [n_local]: this candidate's entries of rc_mean / rc_var are fp64 values
   bool rc_active = false;        // the running set phase works on a partly refined fp32 posterior (verdicts carry bands)
+  // robust sweep (robust.hip): per-control arrays of the last one, the mask of robust-safe controls, the split partials
+  sbo::DevBuf rob, rob_mask, rob_part;
+  long long rob_nc = 0;
+  int rob_q = 0;
+  bool rob_valid = false;   // sbo_robust_get may read `rob` (cleared by a model or candidate change)
   // comm
   void* comm = nullptr;  // ncclComm_t
   int world = 1, rank = 0;

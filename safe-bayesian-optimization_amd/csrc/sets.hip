@@ -2536,6 +2536,42 @@ static int sweep_tr_t(sbo_ctx* c, const sbo_sweep_opts* o, const double* x0, dou
   return SBO_OK;
 }
 
+// StableOpt's robust sweep (robust.hip): arg-min of f = max_d bound_0 over the robust-safe controls, each value known to +- fb
+struct ValRobust {
+  static constexpr bool kUniform = false;
+  __device__ __forceinline__ double uni() const { return 0.0; }
+  const double* f;
+  const double* fb;
+  bool banded;
+  __device__ __forceinline__ void bind(const GuardBand*) {}
+  __device__ __forceinline__ double operator()(long long g, double& d) const {
+    d = banded ? fb[g] : 0.0;
+    return f[g];
+  }
+};
+__global__ void k_robust_out(const SweepScalars* sc, long long* out4) {
+  out4[0] = sc->arg_idx[0];
+  out4[1] = sc->count_M;
+  out4[2] = sc->guard_slot[0];
+  out4[3] = __double_as_longlong(sc->arg_val[0]);
+}
+int robust_argmin(sbo_ctx* c, const double* f, const double* fb, const uint8_t* mask, long long Nc, bool gb_on, long long* out4) {
+  int rc;
+  if ((rc = ensure(c->scal, sizeof(SweepScalars)))) return rc;
+  const int nb = (int)std::max<long long>(1, std::min<long long>((Nc + 255) / 256, (long long)c->n_cu * 4));
+  if ((rc = ensure(c->partial, partial_stride(nb)))) return rc;
+  SweepScalars* sc = (SweepScalars*)c->scal.p;
+  SBO_HIP(hipMemsetAsync(sc, 0, sizeof(SweepScalars), c->stream));
+  if (Nc > 0)
+    hipLaunchKernelGGL((k_arg_masked<double, false, ValRobust>), dim3(nb), dim3(256), 0, c->stream, ValRobust{f, fb, gb_on}, mask, Nc, 0LL,
+                       (Best*)c->partial.p, (const GuardBand*)nullptr);
+  hipLaunchKernelGGL((k_arg_final<false>), dim3(1), dim3(256), 0, c->stream, (const Best*)c->partial.p, Nc > 0 ? nb : 0, sc, 0, &sc->count_M,
+                     gb_on ? 1 : 0);
+  hipLaunchKernelGGL(k_robust_out, dim3(1), dim3(1), 0, c->stream, (const SweepScalars*)sc, out4);
+  SBO_HIP(hipGetLastError());
+  return SBO_OK;
+}
+
 }  // namespace sbo
 
 using namespace sbo;

@@ -78,9 +78,10 @@ class SweepEngine:
         L.check(self._lib.sbo_comm_barrier(self._ctx))
 
     # ---- model -------------------------------------------------------------------------------
-    def set_model(self, ds: dict, dtype="f64", kernel: str = "RBF", use_invK: bool = True):
+    def set_model(self, ds: dict, dtype="f64", kernel: str = "RBF", use_invK: bool = True, mean_prior=None):
         """Upload the ``inference_datasets`` dict.  ``use_invK=False`` lets the library factor
-        K + (sn2 + float32 eps) I itself (Cholesky, contraction with L^-1)."""
+        K + (sn2 + float32 eps) I itself (Cholesky, contraction with L^-1).  ``mean_prior`` [q] (normalised units) replaces
+        GP_Safe's prior mean (0 for the objective, -2 Y_mean / Y_std for the constraints); models/GP_Robust.py uses zeros."""
         self.tag, self.np_dtype = _DTYPES[dtype]
         X_norm = _f64(ds["X_norm"])
         Y_norm = _f64(ds["Y_norm"])
@@ -96,7 +97,18 @@ class SweepEngine:
             raise ValueError("X_mean/X_std must be [d], Y_mean/Y_std must be [q]")
         args = [self._ctx, self.tag, kernel.encode(), n, d, q, _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]), _ptr(arrs[3]),
                 _ptr(X_norm), _ptr(Y_norm), _ptr(hyp)]
-        if use_invK:
+        if mean_prior is not None:
+            mp = _f64(mean_prior).reshape(-1)
+            if mp.shape != (q,):
+                raise ValueError("mean_prior must be [q]")
+            ptrs = None
+            if use_invK:
+                parts = [_f64(a) for a in ds["invKopt"]]
+                if len(parts) != q or any(a.shape != (n, n) for a in parts):
+                    raise ValueError("invKopt must hold q matrices of shape [n, n]")
+                ptrs = (C.c_void_p * q)(*[a.ctypes.data for a in parts])
+            L.check(self._lib.sbo_model_set_prior(*args, ptrs, _ptr(mp)))
+        elif use_invK:
             # `invKopt` is a list of q separate [n, n] arrays in the reference (models/GP_Safe.py:231-232): handed over as such
             parts = [_f64(a) for a in ds["invKopt"]]
             if len(parts) != q or any(a.shape != (n, n) for a in parts):
@@ -229,6 +241,32 @@ class SweepEngine:
         return {"index": int(res.index), "x": np.array(res.x[:self.d]), "lcb": float(res.lcb),
                 "count_S": int(res.count_S), "count_T": int(res.count_T), "guard_band": int(res.guard_band),
                 "guard_rechecks": int(res.guard_rechecks), "guard_passes": int(res.guard_passes)}
+
+    def sweep_robust(self, b: float, n_control_axes: int, kind: str = "ucb", posterior_ready: bool = False) -> dict:
+        """StableOpt's robust min-max on the resident grid (models/StableOpt.py:139-164): axes 0 .. n_control_axes - 1 are the controls
+        xc, the rest the disturbance d.  argmin over xc with min_d lcb_c >= 0 (every constraint) of max_d ``kind``_0; ``index`` is the
+        flat index in the control sub-grid (-1 and ``value`` = inf when no control is robust-safe)."""
+        k = {"mean": L.SBO_MEAN, "ucb": L.SBO_UCB, "lcb": L.SBO_LCB}.get(kind)
+        if k is None:
+            raise ValueError("kind must be 'mean', 'ucb' or 'lcb'")
+        res = L.RobustResult()
+        opts = self._opts(b, True, False, posterior_ready)
+        L.check(self._lib.sbo_sweep_robust(self._ctx, C.byref(opts), int(n_control_axes), k, C.byref(res)))
+        nc = int(n_control_axes)
+        self._robust_shape = (int(res.count_control), self.q)
+        return {"index": int(res.index), "xc": np.array(res.xc[:nc]), "value": float(res.value),
+                "worst_d_index": int(res.worst_d_index), "worst_d": np.array(res.worst_d[:self.d - nc]),
+                "candidate_index": int(res.candidate_index), "count_control": int(res.count_control),
+                "count_disturbance": int(res.count_disturbance), "count_safe": int(res.count_safe),
+                "guard_band": int(res.guard_band), "guard_rechecks": int(res.guard_rechecks), "guard_passes": int(res.guard_passes)}
+
+    def robust_arrays(self):
+        """Per-control arrays of the last robust sweep: f[Nc] = max_d bound_0, g[q - 1, Nc] = min_d lcb_c."""
+        nc, q = getattr(self, "_robust_shape", (0, self.q))
+        f = np.empty(nc, dtype=np.float64)
+        g = np.empty((max(q - 1, 0), nc), dtype=np.float64)
+        L.check(self._lib.sbo_robust_get(self._ctx, _ptr(f), _ptr(g) if g.size else None))
+        return f, g
 
     def explore_safeset(self, target):
         """``BO.explore_safeset(target)`` (models/GoOSE.py:116-119) for a caller's own target: (flat index, x) of the candidate of the
