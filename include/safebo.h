@@ -331,6 +331,31 @@ int sbo_fit_de(sbo_ctx* ctx, int n, int d, const double* X_norm, const double* y
                const double* init_pop, uint64_t seed, int maxiter, double tol, double atol, double* best_x, double* best_energy,
                int* generations);
 
+/* NLL and its analytic gradient for P hyper-parameter vectors (the jac = grad(NLL) of models/GP_Classic.py:219-226):
+ * nll_out[p] is bit for bit sbo_nll_batch's out[p]; grad_out[p, d+2] = dNLL/dh with Q = K^-1 - alpha alpha^T, Kf = K's noise-free
+ * part: sum_ik Q_ik Kf_ik (x_ia - x_ka)^2 / W_a (a < d), 2 sum_ik Q_ik Kf_ik, 2 sn2 tr Q.  A member whose factor fails gets
+ * +inf and a NaN gradient.  Needs 8 (n d + 4 n) bytes of LDS <= 150 KiB (SBO_E_UNSUPPORTED above). */
+int sbo_nll_grad_batch(sbo_ctx* ctx, int n, int d, const double* X_norm, const double* y, int P, const double* hyper,
+                       double* nll_out, double* grad_out);
+
+/* per-start outcome of sbo_fit_local */
+enum sbo_fit_status {
+  SBO_FIT_FTOL = 0,        /* |f_k - f_k+1| < ftol after an accepted step                  */
+  SBO_FIT_GTOL = 1,        /* ||projected gradient||_inf <= gtol                           */
+  SBO_FIT_MAXITER = 2,     /* maxiter accepted steps                                       */
+  SBO_FIT_LINESEARCH = 3,  /* no Armijo point along steepest descent                       */
+  SBO_FIT_NOT_PD = 4       /* the clipped start has no factor (or no finite gradient)      */
+};
+
+/* GP_Classic's multistart fit (models/GP_Classic.py:194-240) in one launch: for every output o < q (column o of Y_norm[n, q]) and
+ * every start s < P (starts[P, d+2], shared by all outputs), a projected BFGS on the box [lo, hi]^(d+2) with Armijo backtracking
+ * along the projection arc, one workgroup per (o, s).  best_x[q, d+2] / best_nll[q]: the lowest NLL per
+ * output, ties to the lowest start.  Optional (NULL allowed): x_out[q, P, d+2], nll_out[q, P], iters_out / evals_out [q, P],
+ * pgnorm_out[q, P] (projected-gradient inf-norm at the result, NaN for SBO_FIT_NOT_PD), status_out[q, P] (sbo_fit_status). */
+int sbo_fit_local(sbo_ctx* ctx, int n, int d, int q, const double* X_norm, const double* Y_norm, int P, const double* starts,
+                  const double* lo, const double* hi, int maxiter, double ftol, double gtol, double* best_x, double* best_nll,
+                  double* x_out, double* nll_out, int* iters_out, int* evals_out, double* pgnorm_out, int* status_out);
+
 /* ---- plant evaluation ------------------------------------------ */
 /* The reference's William-Otto reactor (problems/WilliamOttoReactor_Problem.py:19-93), noise-free, for n input rows
  * u[n, 2] = (Fb, Tr): out[n, 3] = (get_objective, get_constraint1, get_constraint2), each the steady state of the six

@@ -28,6 +28,8 @@ SBO_E_EMPTY_SAFE_SET = -6
 SBO_E_COMM = -7
 SBO_E_UNSUPPORTED = -8
 
+SBO_FIT_FTOL, SBO_FIT_GTOL, SBO_FIT_MAXITER, SBO_FIT_LINESEARCH, SBO_FIT_NOT_PD = 0, 1, 2, 3, 4
+
 
 class SweepOpts(C.Structure):
     _fields_ = [("b", C.c_double), ("reference_quirk_L_index", C.c_int32), ("want_masks", C.c_int32),
@@ -125,6 +127,9 @@ SYMBOLS = [
     ("sbo_nll_batch", C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
     ("sbo_fit_de", C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, C.c_uint64, C.c_int, C.c_double, C.c_double, _P, _P,
                              C.POINTER(C.c_int)]),
+    ("sbo_nll_grad_batch", C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
+    ("sbo_fit_local", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_double, C.c_double, _P, _P,
+                                _P, _P, _P, _P, _P, _P]),
     ("sbo_plant_wo", C.c_int, [_P, C.c_int64, _P, _P]),
     ("sbo_profile_get", C.c_int, [_P, C.POINTER(Profile)]),
     ("sbo_set_option", C.c_int, [_P, C.c_char_p, C.c_int64]),

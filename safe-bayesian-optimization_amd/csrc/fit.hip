@@ -8,6 +8,7 @@
 // One workgroup per population member.  The factor is built as K = U^T U with U upper triangular stored row-major so
 // that every inner loop walks contiguous memory; the right-hand side y rides along as an extra column, so the forward
 // solve costs no extra synchronisation.  Matrices live in an HBM workspace (L2-resident at the reference's sizes).
+#include <algorithm>
 #include <cmath>
 #include <vector>
 #include "device_common.hpp"
@@ -265,5 +266,384 @@ extern "C" int sbo_fit_de(sbo_ctx* c, int n, int d, const double* X_norm, const 
   for (int a = 0; a < D; ++a) best_x[a] = hp[(size_t)best * D + a];
   *best_energy = he[best];
   if (generations) *generations = gen;
+  return SBO_OK;
+}
+
+// ---- analytic gradient of the NLL and the multistart local fit (models/GP_Classic.py:168-240) -------------------------------
+// GP_Classic minimises the same objective as GP_Safe with SciPy SLSQP from Sobol starts and jac = grad(NLL).  With
+// alpha = K^-1 y, Q = K^-1 - alpha alpha^T and Kf the noise-free part of K (W_a = exp(2 h_a), sn2 = exp(2 h_{d+1})):
+//     dNLL/dh_a     = sum_ik Q_ik Kf_ik (x_ia - x_ka)^2 / W_a      (a < d)
+//     dNLL/dh_d     = 2 sum_ik Q_ik Kf_ik
+//     dNLL/dh_{d+1} = 2 sn2 tr Q
+// nll_member leaves K = U^T U (U upper, row-major) and z = U^-T y.  The strictly lower triangle of the same buffer then takes
+// V = U^-T (row j of V at U[j n + i], i < j; the diagonal 1 / U_jj lives in LDS), so K^-1 = V^T V is formed entry by entry as the
+// contraction consumes it: K^-1_ik = sum_{j >= max(i, k)} V_ji V_jk.  Every sum runs in a fixed order; the workgroup reduction
+// is a butterfly per wave and then the waves in index order, so repeated calls give the same bits.
+namespace sbo {
+
+constexpr int kFitD = SBO_MAX_D + 2;
+
+// LDS of the gradient kernels: nll_member's [n d + 2 n] followed by col[n] and dinv[n]
+inline size_t nll_grad_lds(int n, int d) { return sizeof(double) * ((size_t)n * d + 4 * (size_t)n); }
+
+// NLL (bit for bit nll_member's) and its gradient grad[d + 2] (LDS, valid in every thread on return) of one h[d + 2].
+__device__ double nll_grad_member(int n, int d, const double* __restrict__ X, const double* __restrict__ y, const double* h,
+                                  double* __restrict__ U, double* smem_d, double* grad) {
+  __shared__ double sh_f;
+  __shared__ double sh_part[16][kFitD];               // per-wave partial sums (at most 1024 threads)
+  const double f = nll_member(n, d, X, y, h, U, smem_d);
+  const int tid = threadIdx.x, D = d + 2;
+  const int lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+  if (tid == 0) sh_f = f;
+  __syncthreads();
+  const double nll = sh_f;
+  if (!(nll < INFINITY)) {                            // a pivot <= 0: no factor, no gradient
+    if (tid == 0)
+      for (int a = 0; a < D; ++a) grad[a] = NAN;
+    __syncthreads();
+    return nll;
+  }
+  double* Xa = smem_d;                                // nll_member's X W^-1/2, still in place
+  double* alpha = Xa + (size_t)n * d;                 // (nll_member's sq: no longer needed)
+  const double* z = alpha + n;
+  double* col = alpha + 2 * n;
+  double* dinv = col + n;
+  for (int i = tid; i < n; i += blockDim.x) dinv[i] = 1.0 / U[(size_t)i * n + i];
+  __syncthreads();
+  // V = U^-T row by row: V_ji = -(1 / U_jj) sum_{m = i}^{j-1} U_mj V_mi
+  for (int j = 1; j < n; ++j) {
+    for (int m = tid; m < j; m += blockDim.x) col[m] = U[(size_t)m * n + j];
+    __syncthreads();
+    for (int i = tid; i < j; i += blockDim.x) {
+      double s = 0.0;
+      for (int m = j - 1; m > i; --m) s += col[m] * U[(size_t)m * n + i];      // (a common m per step: coalesced over i)
+      s += col[i] * dinv[i];
+      U[(size_t)j * n + i] = -dinv[j] * s;
+    }
+    __syncthreads();
+  }
+  // alpha = K^-1 y = V^T z
+  for (int i = tid; i < n; i += blockDim.x) {
+    double s = 0.0;
+    for (int j = n - 1; j > i; --j) s += U[(size_t)j * n + i] * z[j];
+    alpha[i] = s + dinv[i] * z[i];
+  }
+  __syncthreads();
+  const double sf2 = exp(2.0 * h[d]);
+  const double sn2 = exp(2.0 * h[d + 1]);
+  double acc[SBO_MAX_D], acc_f = 0.0, acc_tr = 0.0;    // (length-scale terms, signal term, trace of Q)
+#pragma unroll
+  for (int a = 0; a < SBO_MAX_D; ++a) acc[a] = 0.0;
+  // pairs i <= k of the symmetric sum (off-diagonal pairs count twice); lanes take consecutive k of one row i
+  for (long long idx = tid; idx < (long long)n * n; idx += blockDim.x) {
+    const int i = (int)(idx / n), k = (int)(idx % n);
+    if (k < i) continue;
+    double kinv = 0.0;
+    for (int j = n - 1; j > k; --j) kinv += U[(size_t)j * n + i] * U[(size_t)j * n + k];
+    kinv += (k > i ? U[(size_t)k * n + i] : dinv[k]) * dinv[k];
+    const double qik = kinv - alpha[i] * alpha[k];
+    double r2[SBO_MAX_D];
+    double dist = 0.0;
+#pragma unroll
+    for (int a = 0; a < SBO_MAX_D; ++a) {
+      if (a < d) {
+        const double r = Xa[i * d + a] - Xa[k * d + a];
+        r2[a] = r * r;
+        dist += r2[a];
+      }
+    }
+    const double w = (k == i ? 1.0 : 2.0) * (qik * (sf2 * exp(-0.5 * dist)));
+#pragma unroll
+    for (int a = 0; a < SBO_MAX_D; ++a)
+      if (a < d) acc[a] += w * r2[a];
+    acc_f += w;
+    if (k == i) acc_tr += qik;
+  }
+#pragma unroll
+  for (int a = 0; a < SBO_MAX_D + 2; ++a) {
+    double v = a < SBO_MAX_D ? acc[a] : a == SBO_MAX_D ? acc_f : acc_tr;
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    const int slot = a < SBO_MAX_D ? a : a - SBO_MAX_D + d;
+    if (lane == 0 && (a < d || a >= SBO_MAX_D)) sh_part[wave][slot] = v;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int a = 0; a < D; ++a) {
+      double s = 0.0;
+      for (int w = 0; w < nw; ++w) s += sh_part[w][a];
+      grad[a] = a < d ? s : a == d ? 2.0 * s : 2.0 * sn2 * s;
+    }
+  }
+  __syncthreads();
+  return nll;
+}
+
+__global__ __launch_bounds__(1024) void k_nll_grad_batch(int n, int d, const double* __restrict__ X, const double* __restrict__ y,
+                                                         const double* __restrict__ hyper, double* __restrict__ work,
+                                                         double* __restrict__ nll_out, double* __restrict__ grad_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ double g[kFitD];
+  const int p = blockIdx.x, D = d + 2;
+  const double v = nll_grad_member(n, d, X, y, hyper + (size_t)p * D, work + (size_t)p * n * n, reinterpret_cast<double*>(smem), g);
+  if (threadIdx.x == 0) {
+    nll_out[p] = v;
+    for (int a = 0; a < D; ++a) grad_out[(size_t)p * D + a] = g[a];
+  }
+}
+
+// ---- projected BFGS on the box, one workgroup per (output, start) ------------------------------------------------------------
+// Thread 0 runs the (d + 2)-dimensional algebra on LDS state; the whole workgroup evaluates NLL + gradient at thread 0's trial
+// point.  See DESIGN.md section 10 for the contract.
+struct FitState {
+  double x[kFitD], g[kFitD], p[kFitD], lo[kFitD], hi[kFitD], H[kFitD * kFitD];
+  double f, t;
+  int phase, iter, nev, halvings, status, h_identity;
+};
+enum { FIT_PH_START = 0, FIT_PH_SEARCH = 1 };
+
+__device__ __forceinline__ double clip_to(double v, double lo, double hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+__device__ double fit_pgnorm(const FitState& S, int D) {
+  double pg = 0.0;
+  for (int a = 0; a < D; ++a) pg = fmax(pg, fabs(clip_to(S.x[a] - S.g[a], S.lo[a], S.hi[a]) - S.x[a]));
+  return pg;
+}
+
+__device__ void fit_reset_h(FitState& S, int D) {
+  for (int a = 0; a < D * D; ++a) S.H[a] = 0.0;
+  for (int a = 0; a < D; ++a) S.H[a * D + a] = 1.0;
+  S.h_identity = 1;
+}
+
+// Start a new iteration at the accepted point: true with the first trial of the line search in `trial`, false when done.
+__device__ bool fit_new_iteration(FitState& S, int D, double* trial, int maxiter, double gtol) {
+  if (fit_pgnorm(S, D) <= gtol) { S.status = SBO_FIT_GTOL; return false; }
+  if (S.iter >= maxiter) { S.status = SBO_FIT_MAXITER; return false; }
+  bool fr[kFitD];
+  for (int a = 0; a < D; ++a)         // held: at a bound with the gradient pointing out of the box
+    fr[a] = !((S.x[a] <= S.lo[a] && S.g[a] > 0.0) || (S.x[a] >= S.hi[a] && S.g[a] < 0.0));
+  double gp = 0.0;
+  for (int a = 0; a < D; ++a) {
+    double s = 0.0;
+    if (fr[a])
+      for (int b = 0; b < D; ++b)
+        if (fr[b]) s += S.H[a * D + b] * S.g[b];
+    S.p[a] = -s;
+    gp += S.g[a] * S.p[a];
+  }
+  if (!(gp < 0.0)) {                  // not a descent direction: restart from steepest descent
+    fit_reset_h(S, D);
+    for (int a = 0; a < D; ++a) S.p[a] = fr[a] ? -S.g[a] : 0.0;
+  }
+  double pn = 0.0;
+  for (int a = 0; a < D; ++a) pn = fmax(pn, fabs(S.p[a]));
+  S.t = S.h_identity ? fmin(1.0, 1.0 / pn) : 1.0;   // a steepest-descent step moves at most one unit of log scale
+  S.halvings = 0;
+  S.phase = FIT_PH_SEARCH;
+  for (int a = 0; a < D; ++a) trial[a] = clip_to(S.x[a] + S.t * S.p[a], S.lo[a], S.hi[a]);
+  return true;
+}
+
+// Consume the evaluation (ft, tg) of `trial`; true when `trial` holds the next point to evaluate.
+__device__ __noinline__ bool fit_advance(FitState& S, int D, double ft, const double* tg, double* trial, int maxiter, double ftol, double gtol) {
+  ++S.nev;
+  bool ok = ft < INFINITY;
+  for (int a = 0; a < D; ++a) ok = ok && isfinite(tg[a]);
+  if (S.phase == FIT_PH_START) {
+    for (int a = 0; a < D; ++a) { S.x[a] = trial[a]; S.g[a] = tg[a]; }
+    S.f = ft;
+    if (!ok) { S.status = SBO_FIT_NOT_PD; return false; }
+    return fit_new_iteration(S, D, trial, maxiter, gtol);
+  }
+  double dec = 0.0;
+  bool moved = false;
+  for (int a = 0; a < D; ++a) {
+    dec += S.g[a] * (trial[a] - S.x[a]);
+    moved = moved || trial[a] != S.x[a];
+  }
+  if (ok && moved && ft <= S.f + 1e-4 * dec) {                       // Armijo along the projection arc
+    double s[kFitD], yv[kFitD], sy = 0.0, ss = 0.0, yy = 0.0;
+    for (int a = 0; a < D; ++a) {
+      s[a] = trial[a] - S.x[a];
+      yv[a] = tg[a] - S.g[a];
+      sy += s[a] * yv[a];
+      ss += s[a] * s[a];
+      yy += yv[a] * yv[a];
+      S.x[a] = trial[a];
+      S.g[a] = tg[a];
+    }
+    const double fprev = S.f;
+    S.f = ft;
+    ++S.iter;
+    if (sy > 1e-10 * sqrt(ss * yy)) {                                // BFGS update of the inverse Hessian, skipped unless s^T y > 0
+      if (S.h_identity) {
+        const double scale = sy / yy;
+        for (int a = 0; a < D; ++a) S.H[a * D + a] = scale;
+        S.h_identity = 0;
+      }
+      double Hy[kFitD], yHy = 0.0;
+      for (int a = 0; a < D; ++a) {
+        double v = 0.0;
+        for (int b = 0; b < D; ++b) v += S.H[a * D + b] * yv[b];
+        Hy[a] = v;
+        yHy += yv[a] * v;
+      }
+      const double rho = 1.0 / sy;
+      const double c = rho * rho * yHy + rho;
+      for (int a = 0; a < D; ++a)
+        for (int b = 0; b < D; ++b) S.H[a * D + b] += c * s[a] * s[b] - rho * (Hy[a] * s[b] + s[a] * Hy[b]);
+    }
+    if (fabs(fprev - S.f) < ftol) { S.status = SBO_FIT_FTOL; return false; }
+    return fit_new_iteration(S, D, trial, maxiter, gtol);
+  }
+  if (moved && S.halvings < 60) {                                    // backtrack
+    ++S.halvings;
+    S.t *= 0.5;
+    for (int a = 0; a < D; ++a) trial[a] = clip_to(S.x[a] + S.t * S.p[a], S.lo[a], S.hi[a]);
+    return true;
+  }
+  if (S.h_identity) { S.status = SBO_FIT_LINESEARCH; return false; }
+  fit_reset_h(S, D);                                                 // the quasi-Newton direction failed: one steepest-descent try
+  ++S.iter;
+  return fit_new_iteration(S, D, trial, maxiter, gtol);
+}
+
+__global__ __launch_bounds__(1024) void k_fit_local(int n, int d, int P, const double* __restrict__ X, const double* __restrict__ yT,
+                                                    const double* __restrict__ starts, const double* __restrict__ lo,
+                                                    const double* __restrict__ hi, int maxiter, double ftol, double gtol,
+                                                    double* __restrict__ work, double* __restrict__ h_out, double* __restrict__ f_out,
+                                                    double* __restrict__ pg_out, int* __restrict__ it_out, int* __restrict__ ev_out,
+                                                    int* __restrict__ st_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ FitState S;
+  __shared__ double trial[kFitD], tg[kFitD];
+  __shared__ int go;
+  const int m = blockIdx.x, o = m / P, s = m % P, D = d + 2;
+  if (threadIdx.x == 0) {
+    for (int a = 0; a < D; ++a) {
+      S.lo[a] = lo[a];
+      S.hi[a] = hi[a];
+      trial[a] = clip_to(starts[(size_t)s * D + a], lo[a], hi[a]);   // SLSQP clips x0 into the bounds
+    }
+    fit_reset_h(S, D);
+    S.phase = FIT_PH_START;
+    S.iter = S.nev = 0;
+    S.status = -1;
+    go = 1;
+  }
+  __syncthreads();
+  double* U = work + (size_t)m * n * n;
+  const double* y = yT + (size_t)o * n;
+  while (go) {
+    const double ft = nll_grad_member(n, d, X, y, trial, U, reinterpret_cast<double*>(smem), tg);
+    if (threadIdx.x == 0) go = fit_advance(S, D, ft, tg, trial, maxiter, ftol, gtol);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    for (int a = 0; a < D; ++a) h_out[(size_t)m * D + a] = S.x[a];
+    f_out[m] = S.f;
+    pg_out[m] = S.status == SBO_FIT_NOT_PD ? NAN : fit_pgnorm(S, D);
+    it_out[m] = S.iter;
+    ev_out[m] = S.nev;
+    st_out[m] = S.status;
+  }
+}
+
+}  // namespace sbo
+
+extern "C" int sbo_nll_grad_batch(sbo_ctx* c, int n, int d, const double* X_norm, const double* y, int P, const double* hyper,
+                                  double* nll_out, double* grad_out) {
+  if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
+  if (n < 1 || n > SBO_MAX_N || d < 1 || d > SBO_MAX_D || P < 1) return fail(SBO_E_INVALID, "n, d or P out of range");
+  if (!X_norm || !y || !hyper || !nll_out || !grad_out) return fail(SBO_E_INVALID, "NULL argument");
+  SBO_HIP(hipSetDevice(c->device));
+  const int D = d + 2;
+  const size_t lds = nll_grad_lds(n, d);
+  if (lds > 150 * 1024) return fail(SBO_E_UNSUPPORTED, "n * d too large for the fit kernel's LDS staging");
+  int rc;
+  const size_t in_elems = (size_t)n * d + n + 2 * (size_t)P * D + P;
+  if ((rc = ensure(c->fitbuf, sizeof(double) * in_elems))) return rc;
+  if ((rc = ensure(c->fitwork, sizeof(double) * (size_t)P * n * n))) return rc;
+  double* dX = (double*)c->fitbuf.p;
+  double* dy = dX + (size_t)n * d;
+  double* dh = dy + n;
+  double* dg = dh + (size_t)P * D;
+  double* dout = dg + (size_t)P * D;
+  SBO_HIP(hipMemcpyAsync(dX, X_norm, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemcpyAsync(dh, hyper, sizeof(double) * (size_t)P * D, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_nll_grad_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_nll_grad_batch, dim3(P), dim3(n >= 96 ? 1024 : 256), lds, c->stream, n, d, (const double*)dX, (const double*)dy,
+                     (const double*)dh, (double*)c->fitwork.p, dout, dg);
+  SBO_HIP(hipGetLastError());
+  SBO_HIP(hipMemcpyAsync(nll_out, dout, sizeof(double) * P, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipMemcpyAsync(grad_out, dg, sizeof(double) * (size_t)P * D, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipStreamSynchronize(c->stream));
+  return SBO_OK;
+}
+
+extern "C" int sbo_fit_local(sbo_ctx* c, int n, int d, int q, const double* X_norm, const double* Y_norm, int P, const double* starts,
+                             const double* lo, const double* hi, int maxiter, double ftol, double gtol, double* best_x, double* best_nll,
+                             double* x_out, double* nll_out, int* iters_out, int* evals_out, double* pgnorm_out, int* status_out) {
+  if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
+  if (n < 1 || n > SBO_MAX_N || d < 1 || d > SBO_MAX_D || q < 1 || q > SBO_MAX_Q || P < 1 || maxiter < 0)
+    return fail(SBO_E_INVALID, "n, d, q, P or maxiter out of range");
+  if (!X_norm || !Y_norm || !starts || !lo || !hi || !best_x || !best_nll) return fail(SBO_E_INVALID, "NULL argument");
+  if (!(ftol >= 0.0) || !(gtol >= 0.0)) return fail(SBO_E_INVALID, "ftol and gtol must be >= 0");
+  const int D = d + 2;
+  for (int a = 0; a < D; ++a)
+    if (!(lo[a] <= hi[a])) return fail(SBO_E_INVALID, "bounds need lo <= hi");
+  SBO_HIP(hipSetDevice(c->device));
+  const size_t lds = nll_grad_lds(n, d);
+  if (lds > 150 * 1024) return fail(SBO_E_UNSUPPORTED, "n * d too large for the fit kernel's LDS staging");
+  const size_t M = (size_t)q * P;
+  int rc;
+  const size_t in_elems = (size_t)n * d + (size_t)q * n + (size_t)P * D + 2 * (size_t)D + M * D + 2 * M + 3 * M;
+  if ((rc = ensure(c->fitbuf, sizeof(double) * in_elems))) return rc;
+  if ((rc = ensure(c->fitwork, sizeof(double) * M * n * n))) return rc;
+  std::vector<double> yT((size_t)q * n);               // one contiguous column per output
+  for (int i = 0; i < n; ++i)
+    for (int o = 0; o < q; ++o) yT[(size_t)o * n + i] = Y_norm[(size_t)i * q + o];
+  double* dX = (double*)c->fitbuf.p;
+  double* dy = dX + (size_t)n * d;
+  double* dst = dy + (size_t)q * n;
+  double* dlo = dst + (size_t)P * D;
+  double* dhi = dlo + D;
+  double* dh = dhi + D;
+  double* df = dh + M * D;
+  double* dpg = df + M;
+  int* dit = reinterpret_cast<int*>(dpg + M);
+  int* dev = dit + M;
+  int* dstat = dev + M;
+  SBO_HIP(hipMemcpyAsync(dX, X_norm, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemcpyAsync(dy, yT.data(), sizeof(double) * (size_t)q * n, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemcpyAsync(dst, starts, sizeof(double) * (size_t)P * D, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemcpyAsync(dlo, lo, sizeof(double) * D, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemcpyAsync(dhi, hi, sizeof(double) * D, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fit_local), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_fit_local, dim3((unsigned)M), dim3(n >= 96 ? 1024 : 256), lds, c->stream, n, d, P, (const double*)dX,
+                     (const double*)dy, (const double*)dst, (const double*)dlo, (const double*)dhi, maxiter, ftol, gtol,
+                     (double*)c->fitwork.p, dh, df, dpg, dit, dev, dstat);
+  SBO_HIP(hipGetLastError());
+  std::vector<double> hh(M * D), hf(M), hpg(M);
+  std::vector<int> hit(3 * M);
+  SBO_HIP(hipMemcpyAsync(hh.data(), dh, sizeof(double) * M * D, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipMemcpyAsync(hf.data(), df, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipMemcpyAsync(hpg.data(), dpg, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipMemcpyAsync(hit.data(), dit, sizeof(int) * 3 * M, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipStreamSynchronize(c->stream));
+  for (int o = 0; o < q; ++o) {
+    int best = 0;                                      // jnp.argmin: the first of equal values
+    for (int s = 1; s < P; ++s)
+      if (hf[(size_t)o * P + s] < hf[(size_t)o * P + best]) best = s;
+    for (int a = 0; a < D; ++a) best_x[(size_t)o * D + a] = hh[((size_t)o * P + best) * D + a];
+    best_nll[o] = hf[(size_t)o * P + best];
+  }
+  if (x_out) std::copy(hh.begin(), hh.end(), x_out);
+  if (nll_out) std::copy(hf.begin(), hf.end(), nll_out);
+  if (pgnorm_out) std::copy(hpg.begin(), hpg.end(), pgnorm_out);
+  if (iters_out) std::copy(hit.begin(), hit.begin() + M, iters_out);
+  if (evals_out) std::copy(hit.begin() + M, hit.begin() + 2 * M, evals_out);
+  if (status_out) std::copy(hit.begin() + 2 * M, hit.end(), status_out);
   return SBO_OK;
 }

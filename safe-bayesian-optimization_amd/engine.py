@@ -14,6 +14,8 @@ import numpy as np
 
 from . import _lib as L
 
+FLOAT32_EPS = float(np.finfo(np.float32).eps)
+
 _DTYPES = {"f64": (L.SBO_F64, np.float64), "f32": (L.SBO_F32, np.float32),
            np.float64: (L.SBO_F64, np.float64), np.float32: (L.SBO_F32, np.float32)}
 
@@ -311,6 +313,47 @@ class SweepEngine:
         L.check(self._lib.sbo_fit_de(self._ctx, X.shape[0], X.shape[1], _ptr(X), _ptr(yv), pop.shape[0], _ptr(lo), _ptr(hi), _ptr(pop),
                                      int(seed), int(maxiter), float(tol), float(atol), _ptr(best), C.byref(energy), C.byref(gens)))
         return best, float(energy.value), int(gens.value)
+
+    def nll_grad_batch(self, X_norm, y, hypers):
+        """``negative_loglikelihood`` and its analytic gradient (models/GP_Classic.py:219, ``grad(NLL)``) for a population:
+        hypers[P, d+2] -> (NLL[P], grad[P, d+2]).  The NLL is bit for bit ``nll_batch``'s; a failed factor gives inf and NaNs."""
+        X = _f64(X_norm)
+        yv = _f64(np.asarray(y).reshape(-1))
+        H = _f64(hypers)
+        if X.ndim != 2 or H.ndim != 2 or H.shape[1] != X.shape[1] + 2 or yv.shape[0] != X.shape[0]:
+            raise ValueError("X_norm [n, d], y [n], hypers [P, d + 2]")
+        nll = np.empty(H.shape[0], dtype=np.float64)
+        grad = np.empty(H.shape, dtype=np.float64)
+        L.check(self._lib.sbo_nll_grad_batch(self._ctx, X.shape[0], X.shape[1], _ptr(X), _ptr(yv), H.shape[0], _ptr(H), _ptr(nll),
+                                             _ptr(grad)))
+        return nll, grad
+
+    def fit_local(self, X_norm, Y_norm, bounds, starts, maxiter: int = 10000, ftol: float = FLOAT32_EPS, gtol: float = 1e-8) -> dict:
+        """GP_Classic's multistart fit (models/GP_Classic.py:194-240) in one launch (``sbo_fit_local``): a projected BFGS on the box
+        bounds[d+2, 2] from every start of starts[P, d+2], for every column of Y_norm[n, q].  Returns ``best_x`` [q, d+2] and
+        ``best_nll`` [q] (ties to the lowest start) and the per-start ``x`` [q, P, d+2], ``nll``, ``iters``, ``evals``, ``pgnorm``
+        and ``status`` [q, P] (``_lib.SBO_FIT_*``)."""
+        X = _f64(X_norm)
+        Y = _f64(Y_norm)
+        if Y.ndim == 1:
+            Y = Y[:, None].copy()
+        B = _f64(bounds)
+        S = _f64(starts)
+        if X.ndim != 2 or Y.ndim != 2 or Y.shape[0] != X.shape[0]:
+            raise ValueError("X_norm [n, d], Y_norm [n, q]")
+        n, d = X.shape
+        q, D = Y.shape[1], d + 2
+        if B.shape != (D, 2) or S.ndim != 2 or S.shape[1] != D:
+            raise ValueError("bounds [d+2, 2], starts [P, d+2]")
+        P = S.shape[0]
+        lo, hi = _f64(B[:, 0]), _f64(B[:, 1])
+        out = {"best_x": np.empty((q, D)), "best_nll": np.empty(q), "x": np.empty((q, P, D)), "nll": np.empty((q, P)),
+               "iters": np.empty((q, P), dtype=np.int32), "evals": np.empty((q, P), dtype=np.int32), "pgnorm": np.empty((q, P)),
+               "status": np.empty((q, P), dtype=np.int32)}
+        L.check(self._lib.sbo_fit_local(self._ctx, n, d, q, _ptr(X), _ptr(Y), P, _ptr(S), _ptr(lo), _ptr(hi), int(maxiter), float(ftol),
+                                        float(gtol), _ptr(out["best_x"]), _ptr(out["best_nll"]), _ptr(out["x"]), _ptr(out["nll"]),
+                                        _ptr(out["iters"]), _ptr(out["evals"]), _ptr(out["pgnorm"]), _ptr(out["status"])))
+        return out
 
     def plant_wo(self, U) -> np.ndarray:
         """William-Otto reactor outputs (objective, constraint 1, constraint 2) for input rows U[N, 2] = (Fb, Tr)."""
