@@ -200,7 +200,7 @@ int sbo_shutdown(sbo_ctx* c) {
   if (c->stream4) (void)hipStreamSynchronize(c->stream4);
   if (c->shadow) {
     sbo_ctx* s = c->shadow;
-    for (DevBuf* b : {&s->Fpk, &s->As, &s->sqA, &s->alpha, &s->Xn, &s->pts, &s->mean, &s->var, &s->scal, &s->mwork, &s->Fplain, &s->alpha64})
+    for (DevBuf* b : {&s->Fpk, &s->As, &s->sqA, &s->alpha, &s->Xn, &s->pts, &s->mean, &s->var, &s->scal, &s->mwork, &s->appendbuf, &s->Fplain, &s->alpha64})
       release(*b);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
     delete s;
@@ -208,7 +208,7 @@ int sbo_shutdown(sbo_ctx* c) {
   }
   sbo_comm_destroy_internal(c);
   for (DevBuf* b : {&c->Fpk, &c->As, &c->sqA, &c->alpha, &c->Xn, &c->pts, &c->mean, &c->var, &c->maskS,
-                    &c->maskU, &c->maskM, &c->maskG, &c->maskO, &c->dist2, &c->dist2b, &c->coarse, &c->fitbuf, &c->fitwork, &c->scal, &c->partial, &c->amb, &c->runmeta, &c->bl_P0f, &c->bl_P1A, &c->bl_T4f, &c->bl_BtA, &c->bl_SBf, &c->bl_VA, &c->bl_small, &c->bl_work, &c->bl_cheb, &c->bl_basis, &c->mwork, &c->rc_mean, &c->rc_var, &c->rc_list, &c->rc_refined, &c->Fplain, &c->alpha64, &c->blockmin, &c->blockmax, &c->cpart, &c->invk_img, &c->bl_lpart, &c->bl_grad, &c->scanlist, &c->gw, &c->Wfull, &c->Uwin, &c->ubits, &c->lane1.dist2, &c->lane1.dist2b, &c->lane1.coarse, &c->lane1.blockmin, &c->lane1.blockmax, &c->lane1.scanlist, &c->lane1.amb, &c->lane1.gw, &c->lane1.runmeta, &c->lane1.scal, &c->gather, &c->xch, &c->shard_first, &c->E0f, &c->Er, &c->AXg, &c->tn_pts, &c->tn_vals, &c->tn_work, &c->tn_W0t, &c->tn_W1t, &c->tn_probe, &c->tn_scr, &c->tn_tail, &c->fuseS, &c->fuseU, &c->tn_gather, &c->bi_params, &c->gb, &c->gb_pts, &c->gb_vals, &c->gb_probe, &c->gb_part, &c->list_scr, &c->cbS, &c->cbU, &c->cbM, &c->cbG, &c->cbUsum, &c->col_img, &c->col_bmin, &c->col_fin, &c->col_slots, &c->col_cimg, &c->col_cbmin, &c->audit_pts, &c->audit_val, &c->audit_part, &c->audit_cnt, &c->bl_encl, &c->bl_sched})
+                    &c->maskU, &c->maskM, &c->maskG, &c->maskO, &c->dist2, &c->dist2b, &c->coarse, &c->fitbuf, &c->fitwork, &c->scal, &c->partial, &c->amb, &c->runmeta, &c->bl_P0f, &c->bl_P1A, &c->bl_T4f, &c->bl_BtA, &c->bl_SBf, &c->bl_VA, &c->bl_small, &c->bl_work, &c->bl_cheb, &c->bl_basis, &c->mwork, &c->appendbuf, &c->rc_mean, &c->rc_var, &c->rc_list, &c->rc_refined, &c->Fplain, &c->alpha64, &c->blockmin, &c->blockmax, &c->cpart, &c->invk_img, &c->bl_lpart, &c->bl_grad, &c->scanlist, &c->gw, &c->Wfull, &c->Uwin, &c->ubits, &c->lane1.dist2, &c->lane1.dist2b, &c->lane1.coarse, &c->lane1.blockmin, &c->lane1.blockmax, &c->lane1.scanlist, &c->lane1.amb, &c->lane1.gw, &c->lane1.runmeta, &c->lane1.scal, &c->gather, &c->xch, &c->shard_first, &c->E0f, &c->Er, &c->AXg, &c->tn_pts, &c->tn_vals, &c->tn_work, &c->tn_W0t, &c->tn_W1t, &c->tn_probe, &c->tn_scr, &c->tn_tail, &c->fuseS, &c->fuseU, &c->tn_gather, &c->bi_params, &c->gb, &c->gb_pts, &c->gb_vals, &c->gb_probe, &c->gb_part, &c->list_scr, &c->cbS, &c->cbU, &c->cbM, &c->cbG, &c->cbUsum, &c->col_img, &c->col_bmin, &c->col_fin, &c->col_slots, &c->col_cimg, &c->col_cbmin, &c->audit_pts, &c->audit_val, &c->audit_part, &c->audit_cnt, &c->bl_encl, &c->bl_sched})
     release(*b);
   for (auto& b : c->tn_W) release(b);
   for (DevBuf* b : {&c->rob, &c->rob_mask, &c->rob_part}) release(*b);
@@ -510,11 +510,13 @@ int sbo_model_append(sbo_ctx* c, const double* x_norm_new, const double* y_norm_
   if (!c->has_model || !c->Fplain.p) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
   ModelConst& mc = c->mc;
   const int n = mc.n, d = mc.d, q = mc.q;
+  for (int a = 0; a < d; ++a)
+    if (!std::isfinite(x_norm_new[a])) return fail(SBO_E_INVALID, "x_norm_new must be finite");
+  for (int o = 0; o < q; ++o)
+    if (!std::isfinite(y_norm_new[o])) return fail(SBO_E_INVALID, "y_norm_new must be finite");
   if (n + 1 > SBO_MAX_N) return fail(SBO_E_UNSUPPORTED, "model is at its capacity: rebuild it with sbo_model_set");
   SBO_HIP(hipSetDevice(c->device));
   { const int rcf = factor_sync(c); if (rcf) return rcf; }     // (the update works on the resident factor)
-  c->invk_img_valid = false;                                    // (the images of the caller's invK do not follow an append)
-  c->invk_w_valid = false;
   // cross-covariances of the new point with the expanded distance of the reference (GP_Safe.py:115-119, 166)
   std::vector<double> kvec((size_t)q * n);
   double kappa[kMaxQ], rho[kMaxQ];
@@ -533,8 +535,13 @@ int sbo_model_append(sbo_ctx* c, const double* x_norm_new, const double* y_norm_
     kappa[o] = mc.sf2[o] + mc.sn2[o];
     rho[o] = y_norm_new[o] - mc.mp[o];
   }
-  int rc = model_append(c, kvec, kappa, rho);
+  // every output's update is computed and checked before anything is written: a refused append leaves the model as it was
+  int rc = model_append_check(c, kvec, kappa, rho);
   if (rc) return rc;
+  if (c->shadow && c->shadow->has_model && (rc = sbo_model_append(c->shadow, x_norm_new, y_norm_new))) return rc;
+  if ((rc = model_append_commit(c))) return rc;
+  c->invk_img_valid = false;                                    // (the images of the caller's invK do not follow an append)
+  c->invk_w_valid = false;
   // the derived arrays with the new row (device), then the re-pack of the factor images
   c->h_Xnorm.insert(c->h_Xnorm.end(), x_norm_new, x_norm_new + d);
   mc.n = n + 1;
@@ -542,12 +549,11 @@ int sbo_model_append(sbo_ctx* c, const double* x_norm_new, const double* y_norm_
   if ((rc = model_prep(c, c->h_Xnorm.data()))) return rc;
   if ((rc = model_repack(c))) return rc;
   ++c->model_serial;
-  if (c->shadow && c->shadow->has_model && (rc = sbo_model_append(c->shadow, x_norm_new, y_norm_new))) return rc;
   c->posterior_valid = false;
   c->masks_valid = false;
   c->rob_valid = false;
   c->bl.valid = false;
-    c->bi.valid = false;
+  c->bi.valid = false;
   return SBO_OK;
 }
 

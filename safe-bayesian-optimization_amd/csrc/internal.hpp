@@ -161,6 +161,7 @@ struct sbo_ctx {
   int f_cap = 0;                 // leading dimension / capacity of Fplain: n after a build, n + 256.. once an append has grown it
   int a_ld = 0;                  // stride of alpha64: npad after a build, f_cap after an append
   sbo::DevBuf mwork;             // model build workspace (uploads, fp64 copies of the derived arrays, the factorisation's scratch)
+  sbo::DevBuf appendbuf;         // sbo_model_append's uploads and scratch (apart from mwork: a refused append leaves the uploaded invK in place)
   // Caller's invK on a K1b-capable grid (option chol_async): the GEMM posterior's tables contract with invK itself -- packed
   // here as full matrix-core images, exactly the matrix of models/GP_Safe.py:341-343 -- so the reverse Cholesky factor M (needed
   // by the O(n^2) kernels K1g / K1 / K1c and by sbo_model_append only) is built on stream4 while the caller goes on; whoever
@@ -405,7 +406,8 @@ int model_build(sbo_ctx* c, const double* const* host_invK, const double* X_norm
 int model_prep(sbo_ctx* c, const double* X_norm);
 int model_factor_enqueue(sbo_ctx* c);
 int model_pack_invk(sbo_ctx* c);         // images of the caller's invK for the K1b tables, when the grid arrived after the model   // the deferred factor chain of a caller's invK, behind everything on the critical path
-int model_append(sbo_ctx* c, const std::vector<double>& kvec /*[q][n]*/, const double* kappa, const double* rho);
+int model_append_check(sbo_ctx* c, const std::vector<double>& kvec /*[q][n]*/, const double* kappa, const double* rho);
+int model_append_commit(sbo_ctx* c);   // (after model_append_check succeeded; mc.n still the old n)
 int model_repack(sbo_ctx* c);
 bool bilinear_applicable(const sbo_ctx* c);
 int bilinear_basis_enqueue(sbo_ctx* c, hipStream_t st, bool force_big);

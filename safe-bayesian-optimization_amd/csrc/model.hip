@@ -484,16 +484,16 @@ __global__ void k_cast_alpha(const double* __restrict__ src, int sstride, int n,
 // One more observation with frozen hyper-parameters and normalisation.  With k = K(X, x_new),
 // kappa = sf2 + sn2 and u = invK k = M^T (M k), s = kappa - k.u, the inverse of the bordered matrix is
 // [[invK + u u^T / s, -u / s], [-u^T / s, 1 / s]]: the lower factor simply gains the row (-u^T / sqrt(s), 1 / sqrt(s)),
-// and alpha_new = (alpha + u (k.alpha - rho) / s, (rho - k.alpha) / s).  O(n^2), one workgroup per output.
-__global__ __launch_bounds__(1024) void k_model_append(int n, int ld, double* __restrict__ F, double* __restrict__ alpha,
+// and alpha_new = (alpha + u (k.alpha - rho) / s, (rho - k.alpha) / s).  O(n^2), one workgroup per output, in two launches:
+// k_model_append computes u, s and k.alpha into scratch and flags s <= 0; k_model_append_commit writes the factor's new row and
+// alpha -- launched only once the host has seen no output flagged, so that a refused append leaves the model as it was.
+__global__ __launch_bounds__(1024) void k_model_append(int n, int ld, const double* __restrict__ F, const double* __restrict__ alpha,
                                                        const double* __restrict__ kvec, const double* __restrict__ kappa,
-                                                       const double* __restrict__ rho, double* __restrict__ scratch,
-                                                       int* __restrict__ bad) {
+                                                       double* __restrict__ scratch, double* __restrict__ sk, int* __restrict__ bad) {
   __shared__ double red[32];
-  __shared__ double sh_s, sh_ka;
   const int o = blockIdx.x, tid = threadIdx.x;
-  double* M = F + (size_t)o * ld * ld;
-  double* al = alpha + (size_t)o * ld;
+  const double* M = F + (size_t)o * ld * ld;
+  const double* al = alpha + (size_t)o * ld;
   const double* k = kvec + (size_t)o * n;
   double* t = scratch + (size_t)o * 2 * ld;
   double* u = t + ld;
@@ -526,18 +526,25 @@ __global__ __launch_bounds__(1024) void k_model_append(int n, int ld, double* __
   if (tid == 0) {
     const double s = kappa[o] - ku;
     if (!(s > 0.0)) bad[o] = 1;
-    sh_s = s > 0.0 ? s : 1.0;
-    sh_ka = ka;
+    sk[2 * o] = s;
+    sk[2 * o + 1] = ka;
   }
-  __syncthreads();
-  const double s = sh_s, rs = 1.0 / sqrt(s), coef = (sh_ka - rho[o]) / s;
+}
+__global__ __launch_bounds__(1024) void k_model_append_commit(int n, int ld, double* __restrict__ F, double* __restrict__ alpha,
+                                                              const double* __restrict__ rho, const double* __restrict__ scratch,
+                                                              const double* __restrict__ sk) {
+  const int o = blockIdx.x, tid = threadIdx.x;
+  double* M = F + (size_t)o * ld * ld;
+  double* al = alpha + (size_t)o * ld;
+  const double* u = scratch + (size_t)o * 2 * ld + ld;
+  const double s = sk[2 * o], ka = sk[2 * o + 1], rs = 1.0 / sqrt(s), coef = (ka - rho[o]) / s;
   for (int j = tid; j < n; j += blockDim.x) {
     M[(size_t)n * ld + j] = -u[j] * rs;
     al[j] += u[j] * coef;
   }
   if (tid == 0) {
     M[(size_t)n * ld + n] = rs;
-    al[n] = (rho[o] - sh_ka) / s;
+    al[n] = (rho[o] - ka) / s;
   }
   for (int j = n + 1 + tid; j < ld; j += blockDim.x) M[(size_t)n * ld + j] = 0.0;
 }
@@ -824,8 +831,10 @@ static int model_repack_t(sbo_ctx* c) {
 }
 int model_repack(sbo_ctx* c) { return c->dtype == SBO_F64 ? model_repack_t<double>(c) : model_repack_t<float>(c); }
 
-// kvec [q][n] cross-covariances of the new point, kappa[q] = sf2 + sn2, rho[q] = y_norm_new - mp; appends row n.
-int model_append(sbo_ctx* c, const std::vector<double>& kvec, const double* kappa, const double* rho) {
+// kvec [q][n] cross-covariances of the new point, kappa[q] = sf2 + sn2, rho[q] = y_norm_new - mp.  model_append_check
+// computes the update of row n into c->appendbuf and fails with SBO_E_INVALID when an output's s <= 0; nothing of the model
+// changes (growing the factor's capacity copies it and keeps its values).  model_append_commit then writes the update.
+int model_append_check(sbo_ctx* c, const std::vector<double>& kvec, const double* kappa, const double* rho) {
   const int n = c->mc.n, q = c->mc.q;
   int rc;
   if (n + 1 > c->f_cap || c->a_ld != c->f_cap) {
@@ -854,24 +863,36 @@ int model_append(sbo_ctx* c, const std::vector<double>& kvec, const double* kapp
     c->a_ld = cap;
   }
   const int cap = c->f_cap;
-  if ((rc = ensure(c->mwork, sizeof(double) * ((size_t)q * n + 2 * (size_t)q + 2 * (size_t)q * cap) + sizeof(int) * q))) return rc;
-  double* dk = (double*)c->mwork.p;
+  // appendbuf (doubles): kvec [q][n] | kappa [q] | rho [q] | scratch [q][2 cap] | (s, k.alpha) [q][2] | bad [q] (ints)
+  if ((rc = ensure(c->appendbuf, sizeof(double) * ((size_t)q * n + 4 * (size_t)q + 2 * (size_t)q * cap) + sizeof(int) * q))) return rc;
+  double* dk = (double*)c->appendbuf.p;
   double* dkappa = dk + (size_t)q * n;
   double* drho = dkappa + q;
   double* dscratch = drho + q;
-  int* dbad = (int*)(dscratch + 2 * (size_t)q * cap);
+  double* dsk = dscratch + 2 * (size_t)q * cap;
+  int* dbad = (int*)(dsk + 2 * (size_t)q);
   SBO_HIP(hipMemcpyAsync(dk, kvec.data(), sizeof(double) * (size_t)q * n, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(dkappa, kappa, sizeof(double) * q, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(drho, rho, sizeof(double) * q, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemsetAsync(dbad, 0, sizeof(int) * q, c->stream));
-  hipLaunchKernelGGL(k_model_append, dim3(q), dim3(1024), 0, c->stream, n, cap, (double*)c->Fplain.p, (double*)c->alpha64.p,
-                     (const double*)dk, (const double*)dkappa, (const double*)drho, dscratch, dbad);
+  hipLaunchKernelGGL(k_model_append, dim3(q), dim3(1024), 0, c->stream, n, cap, (const double*)c->Fplain.p, (const double*)c->alpha64.p,
+                     (const double*)dk, (const double*)dkappa, dscratch, dsk, dbad);
   SBO_HIP(hipGetLastError());
   std::vector<int> hbad(q, 0);
   SBO_HIP(hipMemcpyAsync(hbad.data(), dbad, sizeof(int) * q, hipMemcpyDeviceToHost, c->stream));
   SBO_HIP(hipStreamSynchronize(c->stream));
   for (int o = 0; o < q; ++o)
     if (hbad[o]) return fail(SBO_E_INVALID, "appended observation makes K singular (duplicate point without noise?)");
+  return SBO_OK;
+}
+int model_append_commit(sbo_ctx* c) {
+  const int n = c->mc.n, q = c->mc.q, cap = c->f_cap;
+  double* drho = (double*)c->appendbuf.p + (size_t)q * n + q;
+  double* dscratch = drho + q;
+  double* dsk = dscratch + 2 * (size_t)q * cap;
+  hipLaunchKernelGGL(k_model_append_commit, dim3(q), dim3(1024), 0, c->stream, n, cap, (double*)c->Fplain.p, (double*)c->alpha64.p,
+                     (const double*)drho, (const double*)dscratch, (const double*)dsk);
+  SBO_HIP(hipGetLastError());
   return SBO_OK;
 }
 
