@@ -227,7 +227,6 @@ int sbo_shutdown(sbo_ctx* c) {
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->ev_factor) (void)hipEventDestroy(c->ev_factor);
   if (c->ev_w) (void)hipEventDestroy(c->ev_w);
-  if (c->bi.exec) (void)hipGraphExecDestroy((hipGraphExec_t)c->bi.exec);
   if (c->h_bi_params) (void)hipHostFree(c->h_bi_params);
   if (c->ev_bi_params) (void)hipEventDestroy((hipEvent_t)c->ev_bi_params);
   if (c->stream4) (void)hipStreamDestroy(c->stream4);
@@ -263,9 +262,7 @@ int sbo_set_option(sbo_ctx* c, const char* key, int64_t value) {
   }
   if (!strcmp(key, "cheb_tol_e17")) {
     c->cheb_tol = (double)value * 1e-17;
-    c->bl.valid = false;
-    c->bi.valid = false;
-    c->posterior_valid = false;
+    plans_invalidate(c);
     return SBO_OK;
   }
   if (!strcmp(key, "tensor_guess_pct")) {
@@ -293,9 +290,7 @@ int sbo_set_option(sbo_ctx* c, const char* key, int64_t value) {
   if (!strcmp(key, "bilinear")) {
     if (value < 0 || value > 2) return fail(SBO_E_INVALID, "bilinear must be 0 (off), 1 (on; a model's first sweep by node interpolation) or 2 (on, K1b's plan from the first sweep)");
     c->bilinear = (int)value;
-    c->bl.valid = false;
-    c->bi.valid = false;
-    c->posterior_valid = false;
+    plans_invalidate(c);
     return SBO_OK;
   }
   if (!strcmp(key, "phase_events")) {
@@ -375,10 +370,8 @@ int sbo_set_option(sbo_ctx* c, const char* key, int64_t value) {
   if (!strcmp(key, "guard_band")) {
     if (value < 0 || value > 2) return fail(SBO_E_INVALID, "guard_band must be 0 (off), 1 (on) or 2 (re-evaluate on every sweep)");
     c->guard_band = (int)value;
-    c->bl.valid = false;
-    c->bi.valid = false;                    // (plans measure their band when they are built)
+    plans_invalidate(c);                    // (plans measure their band when they are built)
     c->tn_valid = false;
-    c->posterior_valid = false;
     return SBO_OK;
   }
   if (!strcmp(key, "fp64_recheck")) {
@@ -442,8 +435,7 @@ static int model_set_impl(sbo_ctx* c, int dtype, const char* kernel, int n, int 
     }
   }
   c->dtype = dtype;
-  c->bl.valid = false;
-    c->bi.valid = false;
+  plans_invalidate(c);
   ++c->model_serial;
   // derived arrays (As, sqA, Xn, rhs), factorisation, alpha and the fragment images of the factor: on the device (model.hip)
   int rc = model_build(c, invK, X_norm, Y_norm);
@@ -549,11 +541,9 @@ int sbo_model_append(sbo_ctx* c, const double* x_norm_new, const double* y_norm_
   if ((rc = model_prep(c, c->h_Xnorm.data()))) return rc;
   if ((rc = model_repack(c))) return rc;
   ++c->model_serial;
-  c->posterior_valid = false;
   c->masks_valid = false;
   c->rob_valid = false;
-  c->bl.valid = false;
-  c->bi.valid = false;
+  plans_invalidate(c);
   return SBO_OK;
 }
 
@@ -587,9 +577,7 @@ int sbo_candidates_points(sbo_ctx* c, const void* points, int points_dtype, int6
   c->sharded = false;
   c->has_cand = true;
   c->rob_valid = false;
-  c->bl.valid = false;
-    c->bi.valid = false;
-  c->posterior_valid = false;
+  plans_invalidate(c);
   c->masks_valid = false;
   return SBO_OK;
 }
@@ -619,9 +607,7 @@ int sbo_candidates_grid(sbo_ctx* c, int d, const double* lo, const double* hi, c
   c->sharded = false;
   c->has_cand = true;
   c->rob_valid = false;
-  c->bl.valid = false;
-    c->bi.valid = false;
-  c->posterior_valid = false;
+  plans_invalidate(c);
   c->masks_valid = false;
   return SBO_OK;
 }

@@ -2,7 +2,8 @@
 //
 // Reference arithmetic replaced: GP.GP_inference, models/GP_Safe.py:326-347, evaluated at every point of a
 // linspace x linspace grid (test/test_SafeOpt.py:324-345).  The math and the host-side construction of the bases are
-// in bilinear_host.hpp; this file holds the plan (device tables) and the kernels:
+// in bilinear_host.hpp; this file holds the plan (device tables) and the kernels, with two parts of the same translation unit:
+// bilinear_post.inc.hpp (stage 2 and the launch of both stages) and bilinear_interp.inc.hpp (K1i's plan):
 //
 //   stage 1 (k_bstage1) Bt[x1, k0]  = sum_k1 P1[k1, x1] T4qq[k0, k1]        (lines of the grid  x  pair index of axis 0)
 //   stage 2 (k_bpost)  quad[x1,x0] = sum_k0 Bt[x1, k0] P0[k0, x0]   ->  var = max(0, sf2 - quad) Y_std^2
@@ -957,1101 +958,7 @@ __global__ __launch_bounds__(256) void k_bl_sbf(const BlDims dm, const double* _
   }
 }
 
-// Fused stage 2: variance, mean and gradient keys of a 128 x 128 tile of the grid (8 row blocks x 8 column strips) per
-// workgroup.  Four GEMM phases share the accumulators; operands are staged through LDS one 16-deep k-block at a time
-// (double-buffered), so every fragment is fetched from L2 once per workgroup instead of once per wave:
-//   phase 0  quad = Bt    . P0          (KS0 k-steps)  ->  var  = max(0, sf2 - quad) Y_std^2
-//   phase 1  s1   = V[0]  . S0          (KSm)          ->  mean = (mp + s1) Y_std + Y_mean
-//   phase 2  g0   = [V[1]; V[0]] . [S0; -xn0 S0]  (2 KSm)   gradient sum of axis 0 (the candidate's own xn0 sits in B)
-//   phase 3  g1   = V1x   . S0          (KSm)              gradient sum of axis 1 (xn1 of the line is folded into V1x)
-
-// = kClassifyRow of sets.hip: u* key, |S|, |U|, decisions inside the guard band, min-variance keys over S, radius keys
-constexpr int kFuseRow = 4 + 2 * kMaxQ;
-constexpr int kFuseVmin = 4, kFuseRmax = 4 + kMaxQ;
-struct PostCtx {
-  double* lds;
-  int tid, lane, wave, rb0, cs0, nrb, ncs;
-  int st_rb, st_cs, st_off, a_lo, b_st, a_rd;
-  unsigned int ucnt0;
-  long long nlines;
-  bool full;          // the workgroup's 128 x 128 tile lies inside the grid: epilogues skip their bounds tests
-  bool imode;         // K1i: every phase is a plain GEMM on its own Chebyshev coefficients (the gradient phases start from zero)
-  // fused classification (one-constraint sweeps): the mean epilogue of the constraint's output reads back the variances this
-  // thread stored in the variance phase and writes the S / U bytes; null = off
-  const double* var_rd;
-  uint8_t *S, *U;
-  double bconf, bb;   // confidence multiplier and its square
-  int cS, cU;         // this thread's counts
-  double rmax;        // max ucb over its safe candidates (-1: none; ucb >= lcb >= 0 on S)
-  // guard band of this posterior (guard.hip): sign tests the band of the constraint's output could move are counted, and the
-  // smallest variance over the thread's safe candidates is kept (gdm < 0: no band in force)
-  LcbBand lband;
-  bool gb_on;
-  double vminS;
-  int cB;
-  // column-word classification (r05): role 1 = the constraint's tile packs its S / U bits (bw: S in the low, U in the high 16
-  // bits, bit 4 t + (lane >> 4) of the wave's 16 rows, one word per strip); role 2 = the objective's tile reads the S bits of its
-  // candidates back (bw: its own four bits per strip at 0, 4, 8, 12) and keeps u* / min var_0 over them
-  int role;
-  unsigned int bw[8];
-  unsigned int* lds_bits;   // [4 waves][128 columns] pieces of role 1
-  double umin;              // role 2: min ucb_0 over the thread's safe candidates (+inf: none)
-  double xmin;              // role 1: min of a lower bound of ucb_1 over its safe candidates; role 2: of lcb_0 (the tile's range for the set phase)
-  bool skip_store;          // lean sweep: an objective tile without a safe candidate, or a constraint tile its enclosure proves unsafe -- mean / var are not stored (role 0)
-};
-
-// One GEMM phase of k_bpost on the workgroup's 128 x 128 tile: A images / B fragments of `KB` k-blocks per row block /
-// strip, `KS` k-steps run.  PH selects the epilogue: 0 variance, 1 mean, 2 / 3 gradient component of axis 0 / 1.
-// The accumulators belong to the caller: phase 2 does not start from zero but from phase 1's sums scaled by -xn0 of the
-// candidate's column, g0 = V1 . S0 - xn0 (V0 . S0) -- six k-steps instead of twelve for the stacked [V1; V0] operand.
-// S / U bits of one candidate from its stored mean / var: the arithmetic of k_classify (models/SafeOpt.py:37-43, 57-59, 73-77)
-// (the sign of lcb without the square root -- lcb_sign, device_common.hpp -- and the exact ucb, for the radius key, only when
-// its cheap upper bound beats this thread's running maximum: the IEEE f64 square root is a dozen dependent instructions on the
-// datapath the matrix cores use, which is what made this epilogue cost the kernel as much as the separate pass saved)
-__device__ __forceinline__ void post_classify_mv(PostCtx& cx, size_t g, double m, double v) {
-  const LcbSign sg = cx.gb_on ? lcb_sign_gb(m, v, cx.bconf, cx.bb, cx.lband, cx.cB) : lcb_sign(m, v, cx.bconf, cx.bb);
-  cx.S[g] = sg.ge;
-  cx.U[g] = sg.le;
-  cx.cS += sg.ge;
-  cx.cU += sg.le;
-  if (sg.ge) {
-    cx.vminS = v < cx.vminS ? v : cx.vminS;
-    if (!(ucb_upper(m, v, cx.bconf) <= cx.rmax)) {
-      const double ucb = add_rn(m, mul_rn(cx.bconf, sqrt_rn(v)));
-      if (ucb > cx.rmax) cx.rmax = ucb;
-    }
-  }
-}
-__device__ __forceinline__ void post_classify(PostCtx& cx, size_t g, double m) { post_classify_mv(cx, g, m, cx.var_rd[g]); }
-// the same decisions as bits of the strip's word (role 1): no byte stores
-// The classification of one tile row (eight strips) of the constraint, branch-lean: the kernel is bound by instruction issue on
-// the datapath the matrix cores share, and three quarters of a grid's tiles hold no safe candidate at all.  The sign of
-// lcb = m - b sqrt(v) as lcb_sign decides it (device_common.hpp) -- from m^2 against b^2 v wherever that is safe, as plain predicates
-// without branches; what they leave open (a bound within a few ulp of zero, NaN, out-of-range products: rare) takes the IEEE
-// square root behind ONE wave-uniform test per row.  |S| and |U| are the populations of the bit words at the end (no counters
-// here); everything that concerns safe candidates only -- the smallest variance, the tile's range of ucb_1 -- runs behind a second
-// uniform test, so a tile without a safe candidate never enters it.  Decisions identical to post_classify_mv.
-__device__ __forceinline__ void post_classify_row(PostCtx& cx, unsigned int pos, const double (&mv)[8], const double (&vr)[8]) {
-  constexpr double c = 1.0 + 0x1p-48, tiny = 1e-250, huge = 1e300;
-  unsigned int gem = 0u, lem = 0u, und = 0u;
-  const bool bok = cx.bconf >= 0.0;
-#pragma unroll
-  for (int s2 = 0; s2 < 8; ++s2) {
-    const double m = mv[s2], v = vr[s2];
-    const double P = m * m, Q = cx.bb * v;
-    if (cx.gb_on) {
-      const double gap = P > Q ? P - Q : Q - P, am = m < 0 ? -m : m;
-      cx.cB += !(gap > fma(am, cx.lband.c1, cx.lband.c0));               // (NaN operands count as near)
-    }
-    const bool ok = bok && v >= 0.0, rng = P < huge && Q < huge;
-    const bool neg = ok && m < 0.0;
-    const bool ge = ok && !neg && rng && P > tiny && P >= Q * c;
-    const bool le = neg || (ok && rng && !ge && Q > tiny && P * c <= Q && m >= 0.0);
-    gem |= ge ? (1u << s2) : 0u;
-    lem |= le ? (1u << s2) : 0u;
-    und |= (!ge && !le) ? (1u << s2) : 0u;
-  }
-  if (__ballot(und != 0u) != 0ull) {
-#pragma unroll
-    for (int s2 = 0; s2 < 8; ++s2) {
-      if ((und >> s2) & 1u) {
-        const double sd = mul_rn(cx.bconf, sqrt_rn(vr[s2]));
-        gem |= (mv[s2] >= sd) ? (1u << s2) : 0u;
-        lem |= (mv[s2] <= sd) ? (1u << s2) : 0u;
-      }
-    }
-  }
-#pragma unroll
-  for (int s2 = 0; s2 < 8; ++s2) cx.bw[s2] |= (((gem >> s2) & 1u) | (((lem >> s2) & 1u) << 16)) << pos;
-  if (__ballot(gem != 0u) != 0ull) {
-#pragma unroll
-    for (int s2 = 0; s2 < 8; ++s2) {
-      if ((gem >> s2) & 1u) {
-        const double m = mv[s2], v = vr[s2];
-        cx.vminS = v < cx.vminS ? v : cx.vminS;
-        // bounds of ucb_1 from one single-precision square root (ucb_upper / ucb_lower, device_common.hpp: the hardware's 1-ulp root
-        // is well inside their 2^-20 slack): the exact bound only when it could raise the radius key; the lower bound feeds the
-        // tile's range
-        const float sf = __builtin_amdgcn_sqrtf((float)v);
-        const double s_up = (double)sf * (1.0 + 0x1p-20) + 1e-18;
-        double s_lo = (double)sf * (1.0 - 0x1p-20) - 1e-18;
-        s_lo = s_lo > 0.0 ? s_lo : 0.0;
-        const bool fin = sf < 3.0e38f;
-        const double xu = m + cx.bconf * s_up, xl = m + cx.bconf * (fin ? s_lo : 0.0);
-        const double up = fin ? xu + (xu < 0 ? -xu : xu) * 0x1p-50 : 1e300, lo = xl - (xl < 0 ? -xl : xl) * 0x1p-50;
-        cx.xmin = lo < cx.xmin ? lo : cx.xmin;
-        if (!(up <= cx.rmax)) {
-          const double ucb = add_rn(m, mul_rn(cx.bconf, sqrt_rn(v)));
-          if (ucb > cx.rmax) cx.rmax = ucb;
-        }
-      }
-    }
-  }
-}
-// r06: does post_classify_row leave EVERY (m, v) of the box [mlo, mhi] x [vlo, vhi] with ge = 0, le = 1, outside the undecided branch
-// and -- with a band in force -- outside the band test (no contribution to cB)?  Then a tile whose cells all pass adds nothing but
-// |U| and the Lipschitz key, and need not be evaluated.  The predicate repeats the epilogue's arithmetic at the box's corners:
-// m * m, bb * v and their products with c are monotone in the operand under rounding to nearest, so the corner bounds every point.
-// The band test's differences are tested with a relative margin of 2^-40 of the operands on top (the build does not contract,
-// Makefile: the margin only keeps the argument independent of that).  NaN anywhere: not decided.
-__device__ __forceinline__ bool encl_unsafe(double mlo, double mhi, double vlo, double vhi, double bconf, double bb, bool gb_on, const LcbBand& lb) {
-  constexpr double c = 1.0 + 0x1p-48, tiny = 1e-250, huge = 1e300, mg = 0x1p-40;
-  if (!(bconf >= 0.0 && vlo >= 0.0 && vlo <= vhi && mlo <= mhi)) return false;          // (NaN: false)
-  const double Ql = bb * vlo, Qh = bb * vhi;
-  // classification: m < 0 is le outright; 0 <= m <= mhi needs rng, Q > tiny and P c <= Q (then ge is false: P <= P c <= Q < Q c)
-  if (!(mhi < 0.0)) {
-    const double Ph = mhi * mhi;
-    if (!(Ph < huge && Qh < huge && Ql > tiny && Ph * c <= Ql)) return false;
-  }
-  if (!gb_on) return true;
-  // band: |P - Q| > |m| c1 + c0 for every point -- Q above every P by the margin, or (all m < 0) every P above Q
-  const double amax = fmax(fabs(mlo), fabs(mhi)), amin = (mlo <= 0.0 && mhi >= 0.0) ? 0.0 : fmin(fabs(mlo), fabs(mhi));
-  const double Pmax = amax * amax, Pmin = amin * amin;
-  const double rhs = fma(amax, lb.c1, lb.c0);
-  if (!(amax < 1e150 && Qh < huge && rhs < huge)) return false;
-  const bool qdom = (Ql - Pmax) - mg * (Ql + Pmax) > rhs * (1.0 + mg);
-  const bool pdom = mhi < 0.0 && (Pmin - Qh) - mg * (Pmin + Qh) > rhs * (1.0 + mg);
-  return qdom || pdom;
-}
-// role 2: a safe candidate of the objective -- u* = min over S of ucb_0 (models/SafeOpt.py:47-51), the exact bound only when the
-// cheap lower bound could beat the thread's running minimum (as k_classify's objective pass), and the smallest var_0 over S
-__device__ __forceinline__ void post_objective(PostCtx& cx, bool set, double m, double v) {
-  if (set) {
-    cx.vminS = v < cx.vminS ? v : cx.vminS;
-    const float sf = __builtin_amdgcn_sqrtf((float)v);
-    const double s_up = (double)sf * (1.0 + 0x1p-20) + 1e-18;
-    double s_lo = (double)sf * (1.0 - 0x1p-20) - 1e-18;
-    s_lo = s_lo > 0.0 ? s_lo : 0.0;
-    const bool fin = sf < 3.0e38f;
-    const double xl = m + cx.bconf * (fin ? s_lo : 0.0), yl = m - cx.bconf * s_up;
-    const double ulo = xl - (xl < 0 ? -xl : xl) * 0x1p-50;                      // ucb_0 >= ulo
-    const double llo = fin ? yl - (yl < 0 ? -yl : yl) * 0x1p-50 : -1e300;       // lcb_0 >= llo: the tile's range for the minimiser
-    cx.xmin = llo < cx.xmin ? llo : cx.xmin;
-    if (ulo < cx.umin) {
-      const double ucb = add_rn(m, mul_rn(cx.bconf, sqrt_rn(v)));
-      cx.umin = ucb < cx.umin ? ucb : cx.umin;
-    }
-  }
-}
-
-// End of a posterior kernel: the waves' Lipschitz maxima (already reduced over the lanes) and, with the fused classification,
-// their counts and radius maxima, merged through LDS into ONE value / row per workgroup.  `sh`: NW x 4 doubles of LDS nobody
-// reads any more (barrier first).
-template <int NW>
-__device__ __forceinline__ void post_partials(double* sh, int lane, int wave, double gmax, bool fuse, int cS_, int cU_, double rmax_,
-                                              int cB_, double vmin_, double* __restrict__ lrow, unsigned long long* __restrict__ crow /* this
-                                              workgroup's row of the field-major partials */, int pcap,
-                                              bool objrow = false /* the row of an objective tile (column path): rmax_ carries -min ucb_0 over
-                                              its safe candidates (so that the maximum below is the minimum), vmin_ their smallest var_0 */,
-                                              unsigned long long* __restrict__ slots = nullptr /* column path: the scalars also join slot
-                                              `slot` of every field by atomics (internal.hpp: ColSlotField) */, int slot = 0, int o = 0,
-                                              int tile_row = -1, int tile_col = 0,
-                                              double xmin_ = 1e300 /* column path: the tile's smallest lower bound of ucb_1 (constraint rows,
-                                              field 0) / of lcb_0 (objective rows, field 1) over its safe candidates */,
-                                              bool multi = false /* several constraints: this row is constraint o's (its plane's populations are
-                                              not |S| / |U|; its variance / radius keys are taken over ITS safe candidates, a superset of S) */) {
-  int cS = cS_, cU = cU_, cB = cB_;
-  double rm = rmax_, vm = vmin_, xm = xmin_;
-  if (fuse || objrow) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      cS += __shfl_xor(cS, off);
-      cU += __shfl_xor(cU, off);
-      cB += __shfl_xor(cB, off);
-      const double other = __shfl_xor(rm, off);
-      rm = other > rm ? other : rm;
-      const double ov = __shfl_xor(vm, off);
-      vm = ov < vm ? ov : vm;
-      const double ox = __shfl_xor(xm, off);
-      xm = ox < xm ? ox : xm;
-    }
-  }
-  __syncthreads();
-  if (lane == 0) {
-    sh[wave * 6 + 0] = gmax;
-    sh[wave * 6 + 1] = rm;
-    reinterpret_cast<int*>(sh + wave * 6 + 2)[0] = cS;
-    reinterpret_cast<int*>(sh + wave * 6 + 2)[1] = cU;
-    reinterpret_cast<int*>(sh + wave * 6 + 3)[0] = cB;
-    sh[wave * 6 + 4] = vm;
-    sh[wave * 6 + 5] = xm;
-  }
-  __syncthreads();
-  if (wave == 0) {
-    double g = sh[0], r = sh[1], vmn = sh[4], xmn = sh[5];
-    long long s_ = 0, u_ = 0, b_ = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      g = sh[w * 6] > g ? sh[w * 6] : g;
-      r = sh[w * 6 + 1] > r ? sh[w * 6 + 1] : r;
-      vmn = sh[w * 6 + 4] < vmn ? sh[w * 6 + 4] : vmn;
-      xmn = sh[w * 6 + 5] < xmn ? sh[w * 6 + 5] : xmn;
-      s_ += reinterpret_cast<const int*>(sh + w * 6 + 2)[0];
-      u_ += reinterpret_cast<const int*>(sh + w * 6 + 2)[1];
-      b_ += reinterpret_cast<const int*>(sh + w * 6 + 3)[0];
-    }
-    if (lane == 0) *lrow = g;
-    if (slots) {
-      // (no return values: the wave does not wait for them)
-      if (lane == 0) atomicMax(&slots[(size_t)(o == 0 ? kSlotL0 : kSlotL1) * kColSlots + slot], (unsigned long long)__double_as_longlong(g));
-      if (objrow) {
-        if (lane == 1 && r > -1e300) atomicMin(&slots[(size_t)kSlotUmin * kColSlots + slot], ord_key(-r));
-        if (lane == 2 && vmn < 1e300) atomicMin(&slots[(size_t)kSlotVmin0 * kColSlots + slot], ord_key(vmn));
-      } else {
-        if (lane == 1 && s_ != 0) atomicAdd(&slots[(size_t)kSlotS * kColSlots + slot], (unsigned long long)s_);
-        if (lane == 2 && u_ != 0) atomicAdd(&slots[(size_t)kSlotU * kColSlots + slot], (unsigned long long)u_);
-        if (lane == 3 && b_ != 0) atomicAdd(&slots[(size_t)kSlotB * kColSlots + slot], (unsigned long long)b_);
-        if (lane == 4 && vmn < 1e300) atomicMin(&slots[(size_t)kSlotVmin1 * kColSlots + slot], ord_key(vmn));
-        if (lane == 5 && r >= 0.0) atomicMax(&slots[(size_t)kSlotRmax1 * kColSlots + slot], ord_key(r));
-        if (lane == 6 && s_ != 0 && tile_row >= 0) atomicOr(&slots[(size_t)kSlotRowMask * kColSlots + tile_row], 1ull << tile_col);
-      }
-    }
-    if (objrow && lane < kFuseRow) {
-      // [u* key, 0, 0, 0, min-variance key of output 0, none.., no radius keys]
-      unsigned long long v = 0ull;
-      if (lane == 0) v = r > -1e300 ? ord_key(-r) : ~0ull;
-      else if (lane == 1) v = xmn < 1e300 ? ord_key(xmn) : ~0ull;                 // (the tile's range of lcb_0 over S: sets_colpath's minimiser)
-      else if (lane >= kFuseVmin && lane < kFuseRmax) v = (lane == kFuseVmin && vmn < 1e300) ? ord_key(vmn) : ~0ull;
-      crow[(size_t)lane * pcap] = v;
-    } else
-    if (fuse && lane < kFuseRow) {
-      // partial row of the classification, merged by k_classify_final: [u* key (none here), |S|, |U|, decisions inside the guard
-      // band, min-variance keys over S (output 1 only), radius keys (constraint 1 only)]
-      unsigned long long v = 0ull;
-      if (lane == 0) v = (slots && xmn < 1e300) ? ord_key(xmn) : ~0ull;           // (column path: the tile's lower end of ucb_1 over S)
-      else if (lane == 1) v = multi ? 0ull : (unsigned long long)s_;
-      else if (lane == 2) v = multi ? 0ull : (unsigned long long)u_;
-      else if (lane == 3) v = (unsigned long long)b_;
-      else if (lane >= kFuseVmin && lane < kFuseRmax) v = (lane == kFuseVmin + (o >= 1 ? o : 1) && vmn < 1e300) ? ord_key(vmn) : ~0ull;
-      else if (lane == kFuseRmax + (o >= 1 ? o : 1)) v = r >= 0.0 ? ord_key(r) : 0ull;       // radius key of this constraint
-      crow[(size_t)lane * pcap] = v;
-    }
-  }
-}
-
-// Epilogue of phase PH for the RB x 8 accumulator tiles of a wave (row blocks cx.rb0 + RB cx.wave + i, strips cx.cs0 + s2)
-template <int PH, int RB, int ROLE>
-__device__ __forceinline__ void post_epilogue(PostCtx& cx, double* __restrict__ outp, double c0, double c1, double c2, double& gmax_io,
-                                              d4_t (&acc)[RB][8]) {
-  // gradient phases: max |c0 v| = fl(|c0| max |v|) -- rounding is monotone --, so the tile keeps max |v| (one v_max_f64 with
-  // |.| modifiers per element on the datapath the matrix cores share) and scales once
-  double gmax = 0.0;
-  struct Fold {
-    double& io; const double& raw; double c0; bool on;
-    __device__ ~Fold() {
-      if (on) {
-        double ga = c0 * raw;
-        ga = ga < 0 ? -ga : ga;
-        io = ga > io ? ga : io;
-      }
-    }
-  } fold{gmax_io, gmax, c0, PH >= 2};
-  // epilogue: accumulator element t of lane l is row 4 t + (l >> 4), column l & 15 of its 16 x 16 tile
-  const unsigned int col_in = cx.lane & 15, row_in = cx.lane >> 4;
-  if (PH == 1 && RB == 1 && ROLE != 0 && cx.role != 0) {
-    // Column path (r05; its tiles are all interior).  Role 1, the constraint: the classification with its S / U decisions packed as
-    // bits of the strip's word.  Role 2, the objective: u* and the range of lcb_0 over the tile's safe candidates (bits read back
-    // from the constraint's launch).  Both need the variances this thread stored in the variance phase: the eight of row t + 1 are
-    // requested BEFORE row t's means are stored (the stores may alias anything as far as the compiler knows, so it would not move
-    // the loads across them itself) -- three of the four round trips to L2 run under the arithmetic of the row before.
-    auto row_g0 = [&](int t) {
-      const unsigned int line = (unsigned int)(cx.rb0 + cx.wave) * 16u + 4u * t + row_in;
-      return (size_t)line * cx.ucnt0 + (unsigned int)cx.cs0 * 16u + col_in;
-    };
-    // (the objective's tiles: 2 us per launch on config H; the constraint's epilogue holds too much in registers for it -- with the
-    // prefetch its allocation spilt 22 vector registers and the launch took 138 us against 132)
-    constexpr bool kPrefetch = ROLE == 2;
-    double vn[8];
-    if (kPrefetch) {
-      const size_t g0 = row_g0(0);
-#pragma unroll
-      for (int s2 = 0; s2 < 8; ++s2) vn[s2] = cx.var_rd[g0 + s2 * 16];
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const size_t g0 = row_g0(t), g1 = row_g0(t + 1 < 4 ? t + 1 : t);
-      double* const rowp = outp + g0;
-      if (ROLE == 1) {
-        double vr[8], mv[8];
-#pragma unroll
-        for (int s2 = 0; s2 < 8; ++s2) vr[s2] = cx.var_rd[g0 + s2 * 16];
-#pragma unroll
-        for (int s2 = 0; s2 < 8; ++s2) {
-          mv[s2] = (c0 + acc[0][s2][t]) * c1 + c2;
-          rowp[s2 * 16] = mv[s2];
-        }
-        post_classify_row(cx, 4u * t + row_in, mv, vr);
-      } else {
-#pragma unroll
-        for (int s2 = 0; s2 < 8; ++s2) {
-          const double v = vn[s2];
-          if (t + 1 < 4) vn[s2] = cx.var_rd[g1 + s2 * 16];       // (the next row's variance: a row of arithmetic ahead of its use)
-          const double m = (c0 + acc[0][s2][t]) * c1 + c2;
-          rowp[s2 * 16] = m;
-          post_objective(cx, ((cx.bw[s2] >> (4 * t)) & 1u) != 0u, m, v);
-        }
-      }
-    }
-    if (ROLE == 1) {
-      // |S| / |U| of this thread: the populations of its words (S low half, U high half)
-#pragma unroll
-      for (int s2 = 0; s2 < 8; ++s2) { cx.cS += __popc(cx.bw[s2] & 0xffffu); cx.cU += __popc(cx.bw[s2] >> 16); }
-      // the wave's 16 rows of every column: the four lanes that hold a column OR their bits together, lanes 0..15 put the piece
-      // (S low half, U high half) where the end of the kernel assembles the 64-bit words of the tile
-#pragma unroll
-      for (int s2 = 0; s2 < 8; ++s2) {
-        unsigned int w = cx.bw[s2];
-        w |= (unsigned int)__shfl_xor((int)w, 16);
-        w |= (unsigned int)__shfl_xor((int)w, 32);
-        if (cx.lane < 16) cx.lds_bits[cx.wave * 128 + s2 * 16 + cx.lane] = w;
-      }
-    }
-    return;
-  }
-  if (cx.full) {
-    // interior tile: no bounds tests, one pointer per row, the eight strips at immediate offsets.  The matrix cores
-    // share the f64 VALU datapath, so every instruction saved here is matrix time.
-#pragma unroll
-    for (int i = 0; i < RB; ++i)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const unsigned int line = (unsigned int)(cx.rb0 + RB * cx.wave + i) * 16u + 4u * t + row_in;
-        const size_t g0 = (size_t)line * cx.ucnt0 + (unsigned int)cx.cs0 * 16u + col_in;
-        double* const rowp = outp + g0;
-        if (PH == 1 && ROLE == 0 && cx.S) {
-          // fused classification: the eight variances of this row first (all loads in flight; the byte stores below may
-          // alias anything as far as the compiler knows), then bounds, S / U bytes and the partial sums
-          double vr[8], mv[8];
-#pragma unroll
-          for (int s2 = 0; s2 < 8; ++s2) vr[s2] = cx.var_rd[g0 + s2 * 16];
-#pragma unroll
-          for (int s2 = 0; s2 < 8; ++s2) {
-            mv[s2] = (c0 + acc[i][s2][t]) * c1 + c2;
-            rowp[s2 * 16] = mv[s2];
-          }
-#pragma unroll
-          for (int s2 = 0; s2 < 8; ++s2) post_classify_mv(cx, g0 + s2 * 16, mv[s2], vr[s2]);
-          continue;
-        }
-        if (PH <= 1 && RB == 1 && ROLE != 0 && cx.skip_store) continue;     // (lean sweep: nobody reads this tile's mean / var)
-#pragma unroll
-        for (int s2 = 0; s2 < 8; ++s2) {
-          const double v = acc[i][s2][t];
-          if (PH == 0) {
-            double var = c0 - v;
-            var = var > 0.0 ? var : 0.0;
-            rowp[s2 * 16] = var * c1;
-          } else if (PH == 1) {
-            rowp[s2 * 16] = (c0 + v) * c1 + c2;
-          } else {
-            gmax = fmax(gmax, fabs(v));
-          }
-        }
-      }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < RB; ++i) {
-    const int rb = cx.rb0 + RB * cx.wave + i;
-    if (rb >= cx.nrb) continue;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const unsigned int line = (unsigned int)rb * 16u + 4u * t + row_in;
-      if ((long long)line >= cx.nlines) continue;
-      double* const rowp = outp + (size_t)line * cx.ucnt0;
-#pragma unroll
-      for (int s2 = 0; s2 < 8; ++s2) {
-        const unsigned int x0 = (unsigned int)(cx.cs0 + s2) * 16u + col_in;
-        if (cx.cs0 + s2 >= cx.ncs || x0 >= cx.ucnt0) continue;
-        const double v = acc[i][s2][t];
-        if (PH == 0) {
-          double var = c0 - v;                                              // models/GP_Safe.py:343, clipped at 0
-          var = var > 0.0 ? var : 0.0;
-          rowp[x0] = var * c1;                                              // :347
-        } else if (PH == 1) {
-          const double m = (c0 + v) * c1 + c2;                              // :342, :346
-          rowp[x0] = m;
-          if (ROLE == 0 && cx.S) post_classify(cx, (size_t)line * cx.ucnt0 + x0, m);
-        } else {
-          // component of the gradient of the un-normalised mean (analytic jax.grad(self.mean), SafeOpt.py:68-71)
-          gmax = fmax(gmax, fabs(v));
-        }
-      }
-    }
-  }
-}
-
-template <int PH, int RB, int ROLE>
-__device__ __forceinline__ void post_phase(PostCtx& cx, const double* __restrict__ A, const double* __restrict__ B, int KB,
-                                           int KS, double* __restrict__ outp, double c0, double c1, double c2, double& gmax,
-                                           d4_t (&acc)[RB][8], const double* __restrict__ xn0, d4_t (&pre)[4],
-                                           const double* __restrict__ An, const double* __restrict__ Bn, int KBn) {
-  const double* Ap = A + (size_t)cx.st_rb * KB * 256 + cx.st_off;
-  const double* Bp = B + (size_t)cx.st_cs * KB * 256 + cx.st_off;
-  const int nkb = (KS + 3) >> 2;
-  double* const lds = cx.lds;
-  auto stage = [&](double* buf, const d4_t& r0, const d4_t& r1, const d4_t& q0, const d4_t& q1) {
-    if (RB == 2 || cx.a_lo >= 0) {
-      *reinterpret_cast<d4_t*>(buf + cx.a_lo) = d4_t{r0[0], r0[1], r1[0], r1[1]};
-      *reinterpret_cast<d4_t*>(buf + cx.a_lo + 32) = d4_t{r0[2], r0[3], r1[2], r1[3]};
-    }
-    *reinterpret_cast<d4_t*>(buf + cx.b_st) = q0;
-    *reinterpret_cast<d4_t*>(buf + cx.b_st + 4) = q1;
-  };
-  if (PH == 2 && !cx.imode) {
-#pragma unroll
-    for (int s2 = 0; s2 < 8; ++s2) {
-      const unsigned int x = (unsigned int)(cx.cs0 + s2) * 16u + (cx.lane & 15);
-      const double f = x < cx.ucnt0 ? -xn0[x] : 0.0;
-#pragma unroll
-      for (int i = 0; i < RB; ++i) acc[i][s2] = d4_t{acc[i][s2][0] * f, acc[i][s2][1] * f, acc[i][s2][2] * f, acc[i][s2][3] * f};
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < RB; ++i)
-#pragma unroll
-      for (int s2 = 0; s2 < 8; ++s2) acc[i][s2] = d4_t{0.0, 0.0, 0.0, 0.0};
-  }
-  const bool stage_a = RB == 2 || cx.a_lo >= 0;
-  // the first k-block's 64 + 64 bytes of this thread: requested by the previous phase before its epilogue (`pre`), so that
-  // their latency runs under that epilogue instead of in front of this loop; phase 0 asks here
-  // (128 x 128 tiles only: the 64 x 128 form runs three workgroups per CU on 168 registers and would spill the four)
-  d4_t &ra0 = pre[0], &ra1 = pre[1], &rb0v = pre[2], &rb1v = pre[3];
-  if (PH == 0 || RB == 1) {
-    ra0 = ra1 = d4_t{0.0, 0.0, 0.0, 0.0};
-    if (stage_a) { ra0 = *reinterpret_cast<const d4_t*>(Ap); ra1 = *reinterpret_cast<const d4_t*>(Ap + 4); }
-    rb0v = *reinterpret_cast<const d4_t*>(Bp);
-    rb1v = *reinterpret_cast<const d4_t*>(Bp + 4);
-  }
-  __syncthreads();                             // the previous phase has finished reading the buffers
-  stage(lds, ra0, ra1, rb0v, rb1v);
-  __syncthreads();
-#pragma unroll 1
-  for (int kb = 0; kb < nkb; ++kb) {
-    const int cur = kb & 1;
-    if (kb + 1 < nkb) {
-      if (stage_a) {
-        ra0 = *reinterpret_cast<const d4_t*>(Ap + (size_t)(kb + 1) * 256);
-        ra1 = *reinterpret_cast<const d4_t*>(Ap + (size_t)(kb + 1) * 256 + 4);
-      }
-      rb0v = *reinterpret_cast<const d4_t*>(Bp + (size_t)(kb + 1) * 256);
-      rb1v = *reinterpret_cast<const d4_t*>(Bp + (size_t)(kb + 1) * 256 + 4);
-    }
-    constexpr int BUF = RB == 2 ? 4096 : 3072, BOFF = RB == 2 ? 2048 : 1024;   // doubles per buffer: 4 RB A images, 8 B strips
-    const double* LA = lds + cur * BUF + (RB * cx.wave) * 256 + cx.a_rd;
-    const double* LB = lds + cur * BUF + BOFF + cx.lane;
-    const int kkn = KS - kb * 4 < 4 ? KS - kb * 4 : 4;
-    // operands of k-step kk + 1 are requested before the products of kk are issued (two register sets, no copies): the LDS
-    // latency of a k-step's ten reads otherwise sits in front of its 64 matrix instructions
-    d4_t fa[2][RB];
-    double fb[2][8];
-    auto ld = [&](int kk, d4_t (&a)[RB], double (&b)[8]) {
-#pragma unroll
-      for (int i = 0; i < RB; ++i) {
-        const d2_t l = *reinterpret_cast<const d2_t*>(LA + i * 256 + kk * 64), h = *reinterpret_cast<const d2_t*>(LA + i * 256 + kk * 64 + 32);
-        a[i] = d4_t{l[0], l[1], h[0], h[1]};
-      }
-#pragma unroll
-      for (int s2 = 0; s2 < 8; ++s2) b[s2] = LB[(s2 * 4 + kk) * 64];
-    };
-    auto mm = [&](const d4_t (&a)[RB], const double (&b)[8]) {
-#pragma unroll
-      for (int s2 = 0; s2 < 8; ++s2)
-#pragma unroll
-        for (int i = 0; i < RB; ++i) acc[i][s2] = MM<double>::mfma(a[i], b[s2], acc[i][s2]);
-    };
-    if constexpr (RB == 2) {
-      ld(0, fa[0], fb[0]);
-      int kk = 0;
-#pragma unroll 1
-      for (; kk + 1 < kkn; kk += 2) {
-        ld(kk + 1, fa[1], fb[1]);
-        mm(fa[0], fb[0]);
-        if (kk + 2 < kkn) ld(kk + 2, fa[0], fb[0]);
-        mm(fa[1], fb[1]);
-      }
-      if (kk < kkn) mm(fa[0], fb[0]);
-    } else {                               // (three workgroups per CU and 168 registers: no room for a second operand set)
-#pragma unroll 1
-      for (int kk = 0; kk < kkn; ++kk) {
-        ld(kk, fa[0], fb[0]);
-        mm(fa[0], fb[0]);
-      }
-    }
-    if (kb + 1 < nkb) stage(lds + (cur ^ 1) * BUF, ra0, ra1, rb0v, rb1v);
-    __syncthreads();
-  }
-  if (RB == 2 && An) {
-    const double* Apn = An + (size_t)cx.st_rb * KBn * 256 + cx.st_off;
-    const double* Bpn = Bn + (size_t)cx.st_cs * KBn * 256 + cx.st_off;
-    if (stage_a) { ra0 = *reinterpret_cast<const d4_t*>(Apn); ra1 = *reinterpret_cast<const d4_t*>(Apn + 4); }
-    rb0v = *reinterpret_cast<const d4_t*>(Bpn);
-    rb1v = *reinterpret_cast<const d4_t*>(Bpn + 4);
-  }
-  post_epilogue<PH, RB, ROLE>(cx, outp, c0, c1, c2, gmax, acc);
-}
-
-#ifdef SBO_PHASE_CLOCKS
-// Diagnostic build only (make phaseclk -> libsafebo_phaseclk.so, tools/dev_phase_clocks.py): the constant 100 MHz counter at the
-// phase boundaries of every k_bpost workgroup, a row per workgroup (same-address atomics from 4096 workgroups would themselves
-// take 0.1 ms); [4] = gradient phases the workgroup ran.  The host sums the rows.
-constexpr int kPhaseClkRows = 1 << 14;
-__device__ unsigned long long g_phase_clk[kPhaseClkRows][8];
-// r07: and a row per workgroup of the column path's two launches (the last sweep's: overwritten by every launch), in dispatch order
-// (linear block index): [0] entry, [1] start of the partial rows (post_partials, the words and their Usum / slot atomics), [2] exit --
-// all wall_clock64 --, [3] tile | kind << 24 (0 evaluated, 1 skipped: partial rows only, 2 skipped but its gradient phases run,
-// 3 past the tile list: exited at once) | 1 << 31 (row written), [4] HW_REG_HW_ID, [5] HW_REG_XCC_ID.  tools/dev_wg_timeline.py.
-constexpr int kWgTraceRows = 1 << 13;
-__device__ unsigned long long g_wg_trace[2][kWgTraceRows][8];
-__device__ __forceinline__ void wg_trace_row(int o, unsigned long long t0, unsigned long long t1, unsigned long long t2, unsigned int tile, unsigned int kind) {
-  unsigned int hw, xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-  unsigned long long* r = g_wg_trace[o & 1][(blockIdx.y * gridDim.x + blockIdx.x) & (kWgTraceRows - 1)];
-  r[0] = t0; r[1] = t1; r[2] = t2;
-  r[3] = (unsigned long long)(tile & 0xffffffu) | ((unsigned long long)kind << 24) | (1ull << 31);
-  r[4] = hw; r[5] = xcc;
-}
-#define SBO_CLK(i)                                                                                \
-  do {                                                                                           \
-    __syncthreads();                                                                             \
-    if (threadIdx.x == 0) {                                                                      \
-      const unsigned long long now_ = wall_clock64();                                            \
-      g_phase_clk[clk_row_ & (kPhaseClkRows - 1)][i] += now_ - clk_;                             \
-      clk_ = now_;                                                                               \
-    }                                                                                            \
-  } while (0)
-#else
-#define SBO_CLK(i) do { } while (0)
-#endif
-
-// r06: the enclosures of the constraint's posterior per 8 x 8 cell of every 64 x 128 column-path tile, taken from what the constraint's
-// launch stored -- once per plan, behind its first launch that evaluated every tile.  k_bpost is deterministic for a plan (the same
-// operands, the same k-order of the matrix instructions; b and the band enter only the classification), so [min, max] of the stored
-// values encloses exactly what any later launch of the plan computes: no bound on derivatives, no rounding allowance.  Layout
-// [tile][cell = 16 r + c][m_lo, m_hi, v_lo, v_hi]; a cell holding NaN or inf gets NaN (encl_unsafe: never decided).
-// THE INVARIANT THIS RESTS ON: phases 0 / 1 of the constraint's launch compute the same bits on every launch of a plan.  Anything that
-// changes their operands, k-steps or k-order between sweeps of one plan (a per-sweep truncation, another tile shape, a different
-// accumulation order) must clear BilinearPlan::encl_ready.  The standing audit checks it where it samples an evaluated tile: the stored
-// values must lie inside the recorded enclosure bit for bit (guard.hip: k_audit_compare).
-__global__ __launch_bounds__(128) void k_bl_enclose(const double* __restrict__ mean, const double* __restrict__ var, long long cnt0,
-                                                    double* __restrict__ encl) {
-  const int cell = threadIdx.x, cr = cell >> 4, cc = cell & 15;
-  const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-  const size_t base = ((size_t)blockIdx.y * 64 + (size_t)cr * 8) * (size_t)cnt0 + (size_t)blockIdx.x * 128 + (size_t)cc * 8;
-  double mlo = 1e308, mhi = -1e308, vlo = 1e308, vhi = -1e308;
-  bool fin = true;
-  for (int r = 0; r < 8; ++r) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const double m = mean[base + (size_t)r * cnt0 + k], v = var[base + (size_t)r * cnt0 + k];
-      fin = fin && fabs(m) <= 1e308 && fabs(v) <= 1e308;                  // (NaN: false)
-      mlo = fmin(mlo, m); mhi = fmax(mhi, m); vlo = fmin(vlo, v); vhi = fmax(vhi, v);
-    }
-  }
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  double4 e = fin ? double4{mlo, mhi, vlo, vhi} : double4{nan, nan, nan, nan};
-  reinterpret_cast<double4*>(encl)[tile * 128 + cell] = e;
-}
-
-// r07: the tile lists of a lean-2 column-path sweep (option k1_sched).  One workgroup per tile left 1451 of config H's 2048 constraint
-// workgroups and 1533 of its objective ones doing nothing but their partial rows, interleaved with the evaluated tiles: the evaluated
-// ones ran as two partial rounds of workgroups.  Instead the constraint's launch and the objective's run over lists of the tiles that
-// need a workgroup -- a 1-D grid, workgroup i takes entry i and exits at once past the list -- so the evaluated tiles are dispatched
-// first and fit the CUs in one round.  What a left-out tile produced is written here, bit for bit what its workgroup wrote.
-//
-// The constraint's tiles, one wave each (before the constraint's launch): the skip decision of k_bpost (encl_unsafe on every cell of
-// the tile, at this sweep's b and band) and the gradient gate's decision for output 1.  cls: 0 = skipped, no gradient phase (written
-// here: S = 0 and U = all ones words, its Lipschitz row, its partial row of the classification -- |U| = 8192, no keys; Usum and the
-// slot block in k_bl_sched_list1); 1 = evaluated with gradient phases, 2 = skipped but runs gradient phases, 3 = evaluated.  The skip
-// byte of every tile for the audit (guard.hip).
-__global__ __launch_bounds__(256) void k_bl_sched_tiles1(const ModelConst mc, const double* __restrict__ encl, int ntiles, int tgx, int tgy,
-                                                         unsigned int cnt0, double bconf, const GuardBand* __restrict__ gb,
-                                                         const double* __restrict__ gtmax, const unsigned long long* __restrict__ gkey, int q,
-                                                         uint8_t* __restrict__ skip, uint8_t* __restrict__ cls, unsigned long long* __restrict__ Sw,
-                                                         unsigned long long* __restrict__ Uw, double* __restrict__ Lpart,
-                                                         unsigned long long* __restrict__ cpart, int pcap) {
-  const int lane = threadIdx.x & 63, tile = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-  if (tile >= ntiles) return;
-  const double bb = bconf * bconf;
-  const bool gb_on = gb != nullptr;
-  const LcbBand lb = gb_on ? lcb_band(bb, gb->dm[1], gb->dv[1]) : LcbBand{0.0, 0.0};
-  bool ok = true;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const double4 e = reinterpret_cast<const double4*>(encl)[(size_t)tile * 128 + h * 64 + lane];
-    ok = ok && encl_unsafe(e.x, e.y, e.z, e.w, bconf, bb, gb_on, lb);
-  }
-  const bool dec = __ballot(!ok) == 0ull;
-  // (k_bpost's gate, output 1, and the largest coarse sample it folds in)
-  bool run2 = true, run3 = true;
-  double gfold = 0.0;
-  if (gtmax) {
-    const size_t nt = (size_t)ntiles;
-    const double* slack = gtmax + (size_t)q * 2 * nt;
-    const double ystd = mc.Y_std[1];
-    const double cg0 = ystd * mc.inv_ell[1][0] * mc.X_rstd[0], cg1 = ystd * mc.inv_ell[1][1] * mc.X_rstd[1];
-    const double t0 = gtmax[(size_t)2 * nt + tile], t1 = gtmax[(size_t)3 * nt + tile];
-    const double G0 = __longlong_as_double((long long)gkey[2]), G1 = __longlong_as_double((long long)gkey[3]);
-    run2 = !(t0 + slack[2] < G0 * (1.0 - 1e-12));
-    run3 = !(t1 + slack[3] < G1 * (1.0 - 1e-12));
-    gfold = fmax(fabs(cg0 * t0), fabs(cg1 * t1));
-  }
-  const bool grad = run2 || run3;
-  const unsigned int k = dec ? (grad ? 2u : 0u) : (grad ? 1u : 3u);
-  if (lane == 0) {
-    skip[tile] = dec ? 1 : 0;
-    cls[tile] = (uint8_t)k;
-  }
-  if (k != 0u) return;
-  const int bx = tile % tgx, by = tile / tgx;
-  const size_t w0 = (size_t)by * cnt0 + (size_t)bx * 128;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    Sw[w0 + h * 64 + lane] = 0ull;
-    Uw[w0 + h * 64 + lane] = ~0ull;
-  }
-  if (lane == 0) Lpart[((size_t)tgy + by) * tgx + bx] = fmax(0.0, gfold);
-  // (post_partials' row of a tile with every candidate in U: no safe candidate, no decision in the band, no keys)
-  if (lane < kFuseRow) {
-    unsigned long long v = 0ull;
-    if (lane == 0) v = ~0ull;
-    else if (lane == 2) v = 64ull * 128ull;
-    else if (lane >= kFuseVmin && lane < kFuseRmax) v = ~0ull;
-    cpart[(size_t)lane * pcap + tile] = v;
-  }
-}
-
-// Positions in a list of the tiles a 1024-thread workgroup holds in one round (tile = 1024 round + thread), three classes: a ballot per
-// class gives the rank inside the wave, every thread sums the 16 waves' counts from LDS.  Returns the thread's position in the list for
-// its class k (0..2; -1: none) -- base[k] + the tiles of class k before it in this round -- and adds the round's totals to base[].
-__device__ __forceinline__ unsigned int sched_rank3(int k, unsigned int (&base)[3], unsigned int* __restrict__ sh /* [3][16] */) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  unsigned int rank = 0u;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const unsigned long long m = __ballot(k == j);
-    if (k == j) rank = (unsigned int)__popcll(m & below);
-    if (lane == 0) sh[j * 16 + wave] = (unsigned int)__popcll(m);
-  }
-  __syncthreads();
-  unsigned int pos = 0u, tot[3] = {0u, 0u, 0u};
-#pragma unroll
-  for (int j = 0; j < 3; ++j)
-    for (int w = 0; w < 16; ++w) {
-      const unsigned int c = sh[j * 16 + w];
-      if (k == j && w < wave) pos += c;
-      tot[j] += c;
-    }
-  __syncthreads();
-  const unsigned int r = k >= 0 ? base[k] + pos + rank : 0u;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) base[j] += tot[j];
-  return r;
-}
-
-// The constraint's list (one workgroup, behind k_bl_sched_tiles1): classes 1, 2, 3 in that order -- the tiles with gradient phases,
-// the longest, first --, tile order within a class.  The skipped tiles' shares of the set phase's inputs: Usum (bit by of every
-// column of tile (bx, by) without a workgroup; plain stores -- the launch's own tiles OR theirs in behind), |U|, the skip count and
-// the Lipschitz key into slot 0 (sums and a maximum: the slot a tile joins does not change them).
-__global__ __launch_bounds__(1024) void k_bl_sched_list1(const uint8_t* __restrict__ cls, int ntiles, int tgx, const double* __restrict__ Lpart1,
-                                                         unsigned int* __restrict__ list, unsigned long long* __restrict__ Usum,
-                                                         unsigned long long* __restrict__ slots) {
-  __shared__ unsigned int sh[3 * 16];
-  __shared__ unsigned long long umask[64];
-  __shared__ unsigned long long lmax;
-  __shared__ unsigned int nlight;
-  const int t = threadIdx.x;
-  if (t < 64) umask[t] = 0ull;
-  if (t == 0) { lmax = 0ull; nlight = 0u; }
-  __syncthreads();
-  // (two passes: the counts per class first, so that classes 2 and 3 start behind every tile of the classes before them)
-  unsigned int cnt[3] = {0u, 0u, 0u};
-  for (int r = 0; r * 1024 < ntiles; ++r) {
-    const int i = r * 1024 + t;
-    (void)sched_rank3(i < ntiles ? (int)cls[i] - 1 : -1, cnt, sh);
-  }
-  unsigned int base[3] = {0u, cnt[0], cnt[0] + cnt[1]};
-  unsigned int nl = 0u;
-  unsigned long long gm = 0ull;
-  for (int r = 0; r * 1024 < ntiles; ++r) {
-    const int i = r * 1024 + t;
-    const int k = i < ntiles ? (int)cls[i] - 1 : -1;
-    const unsigned int p = sched_rank3(k, base, sh);
-    if (k >= 0) list[1 + p] = (unsigned int)i | (k == 1 ? 0x80000000u : 0u);
-    if (i < ntiles && k < 0) {
-      ++nl;
-      atomicOr(&umask[i % tgx], 1ull << (i / tgx));
-      const unsigned long long g = (unsigned long long)__double_as_longlong(Lpart1[i]);
-      gm = g > gm ? g : gm;
-    }
-  }
-  if (nl) { atomicAdd(&nlight, nl); atomicMax(&lmax, gm); }
-  if (t == 0) list[0] = cnt[0] + cnt[1] + cnt[2];
-  __syncthreads();
-  for (int c = t; c < tgx * 128; c += 1024) Usum[c] = umask[c >> 7];
-  if (t == 0) {
-    const unsigned long long nskip = (unsigned long long)nlight + cnt[1];
-    if (nlight) {
-      atomicAdd(&slots[(size_t)kSlotU * kColSlots], 64ull * 128ull * nlight);
-      atomicMax(&slots[(size_t)kSlotL1 * kColSlots], lmax);
-    }
-    if (nskip) atomicAdd(&slots[(size_t)kSlotSkip * kColSlots], nskip);
-  }
-}
-
-// The objective's list (one workgroup, behind the constraint's launch): the tiles that hold a safe candidate (field 1 of the
-// constraint's partial rows), in tile order.  The others' objective rows as their workgroups wrote them in a lean-2 sweep (no safe
-// candidate, no gradient phase): no u* key, no range of lcb_0, no variance key, Lipschitz row 0.
-__global__ __launch_bounds__(1024) void k_bl_sched_list2(unsigned long long* __restrict__ cpart, int pcap, int ntiles, unsigned int* __restrict__ list,
-                                                         double* __restrict__ Lpart0) {
-  __shared__ unsigned int sh[3 * 16];
-  const int t = threadIdx.x;
-  const unsigned long long* nS = cpart + (size_t)1 * pcap;
-  unsigned long long* orow = cpart + ntiles;
-  unsigned int base[3] = {0u, 0u, 0u};
-  for (int r = 0; r * 1024 < ntiles; ++r) {
-    const int i = r * 1024 + t;
-    const bool in = i < ntiles, has = in && nS[i] != 0ull;
-    const unsigned int p = sched_rank3(has ? 0 : -1, base, sh);
-    if (has) {
-      list[1 + p] = (unsigned int)i;
-    } else if (in) {
-      Lpart0[i] = 0.0;
-#pragma unroll
-      for (int lane = 0; lane < kFuseRow; ++lane)
-        orow[(size_t)lane * pcap + i] = (lane <= 1 || (lane >= kFuseVmin && lane < kFuseRmax)) ? ~0ull : 0ull;
-    }
-  }
-  if (t == 0) list[0] = base[0];
-}
-
-// RB: row blocks per wave.  2 = the 128 x 128 tile above; 1 = a 64 x 128 tile for grids whose 128 x 128 tiles would leave
-// CUs without a workgroup (1024 x 1024 x 3 outputs: 192 tiles on 256 CUs) -- half the reuse of a B fragment, twice the
-// workgroups.
-template <int RB, int ROLE = 0 /* column path: 1 = the constraint's launch (S / U column words), 2 = the objective's (u* over S) */>
-__global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelConst mc, const CandSpec cs, const double* __restrict__ BtA, size_t sBtA,
-                                                  const double* __restrict__ P0f, size_t sP0f, const double* __restrict__ VA,
-                                                  size_t sVA, const double* __restrict__ SBf, size_t sSBf, int KB0, int KS0, int KBm,
-                                                  int KSm, int KBm2, int nrb, int ncs, long long nlines, double* __restrict__ mean_out,
-                                                  double* __restrict__ var_out, double* __restrict__ Lpart,
-                                                  const double* __restrict__ xn0, uint8_t* __restrict__ Sfuse, uint8_t* __restrict__ Ufuse,
-                                                  double bconf, unsigned long long* __restrict__ cpart /* [kFuseRow][pcap]: a row per workgroup of output 1 */,
-                                                  int pcap,
-                                                  const GuardBand* __restrict__ gb /* nullptr: no guard band */,
-                                                  const int* __restrict__ eff /* nullptr, or the Chebyshev core's k-steps of the variance phase at [4 o] */,
-                                                  const double* __restrict__ gtmax /* nullptr (every tile runs the gradient phases), or the plan's
-                                                  largest gradient samples per tile [q][2][tiles], followed by the slacks [q][2] */,
-                                                  const unsigned long long* __restrict__ gkey /* the grid's largest samples [q][2] */,
-                                                  int imode /* K1i (interpolation from Chebyshev nodes): BtA / VA hold the stage-1 images of four
-                                                  coefficient sets per output (quadratic form, mean sum, two gradient sums), SBf the Chebyshev table
-                                                  P0f; the k-steps of every phase come from eff[4 (4 o + phase)] */,
-                                                  const PostExtra px /* column path: one launch per output (o0), the S / U column words */) {
-  extern __shared__ double lds[];               // [2][A: 8 x 256 | B: 8 x 256] (+ 2 KB of bit pieces behind them, column path)
-  const int o = px.o0 + (int)blockIdx.z;
-  // r07: a launch over a tile list (PostExtra::tlist) takes its tile from entry blockIdx.x of a 1-D grid; every index below that names
-  // the tile -- row block, strip, the words, the partial rows, the gate's table -- comes from (bx, by) and the tile grid (tgx, tgy)
-  const bool listed = ROLE != 0 && px.tlist != nullptr;
-  unsigned int ent = 0u;
-  if (listed) {
-    if (blockIdx.x >= px.tlist[0]) {
-#ifdef SBO_PHASE_CLOCKS
-      if (threadIdx.x == 0) { const unsigned long long t_ = wall_clock64(); wg_trace_row(o, t_, t_, t_, 0xffffffu, 3u); }
-#endif
-      return;                                   // (past the list: the tile was written by the list's kernels)
-    }
-    ent = px.tlist[1 + blockIdx.x];
-  }
-  const unsigned int tgx = listed ? (unsigned int)px.tgx : gridDim.x, tgy = listed ? (unsigned int)px.tgy : gridDim.y;
-  const unsigned int bx = listed ? (ent & 0xffffffu) % tgx : blockIdx.x, by = listed ? (ent & 0xffffffu) / tgx : blockIdx.y;
-  PostCtx cx;
-  cx.lds = lds;
-  cx.tid = threadIdx.x; cx.lane = cx.tid & 63; cx.wave = cx.tid >> 6;
-  cx.rb0 = by * (4 * RB); cx.cs0 = bx * 8; cx.nrb = nrb; cx.ncs = ncs;
-  cx.ucnt0 = (unsigned int)cs.count[0];
-  cx.nlines = nlines;
-  cx.full = (long long)(cx.rb0 + 4 * RB) * 16 <= nlines && (long long)(cx.cs0 + 8) * 16 <= cs.count[0];
-  cx.imode = imode != 0;
-  // staging role of this thread: 64 bytes of one A image and 64 bytes of one B strip per k-block.
-  // LDS image of an A block: per k-step the 16 lane-chunks are split into their first and second 16 bytes
-  // ([16 x 16 B][16 x 16 B]) so that both ds_read_b128 of a fragment load touch 256 contiguous bytes (no bank conflicts)
-  const int st_i = cx.tid >> 5, st_j = cx.tid & 31;
-  cx.st_off = st_j * 8;
-  cx.st_rb = cx.rb0 + st_i < nrb ? cx.rb0 + st_i : nrb - 1;
-  cx.st_cs = cx.cs0 + st_i < ncs ? cx.cs0 + st_i : ncs - 1;
-  cx.a_lo = st_i < 4 * RB ? st_i * 256 + (st_j >> 3) * 64 + (st_j & 7) * 4 : -1;   // (RB = 1: four images, half the threads stage one)
-  cx.b_st = (RB == 2 ? 2048 : 1024) + st_i * 256 + cx.st_off;
-  cx.a_rd = (((cx.lane >> 4) << 2) + (cx.lane & 3)) * 2;
-  // per-output operands; VA holds [V0 | V1;V0 | V1x] as three image sets, SBf holds [S0 | S0;-xn0 S0] as two fragment sets
-  const double* VAo = VA + (size_t)o * sVA;
-  const double* SBo = SBf + (size_t)o * sSBf;
-  const double sf2 = mc.sf2[o], ystd = mc.Y_std[o];
-  double* const vo = var_out + (size_t)o * cs.n_local;
-  double* const mo = mean_out + (size_t)o * cs.n_local;
-  // (one constraint: the masks themselves; several, r05: constraint o writes byte plane o - 1, AND-ed by k_classify_and)
-  const bool fuse = Sfuse != nullptr && o >= 1;
-  const bool fmulti = px.fstride != 0;
-  cx.var_rd = vo;
-  cx.S = fuse ? Sfuse + (size_t)(o - 1) * (size_t)px.fstride : nullptr;
-  cx.U = fuse ? Ufuse + (size_t)(o - 1) * (size_t)px.fstride : Ufuse;
-  cx.bconf = bconf;
-  cx.bb = bconf * bconf;
-  cx.cS = cx.cU = cx.cB = 0;
-  cx.rmax = -1.0;
-  // column path: a tile is 64 rows (one segment of the column words) x 128 columns
-  const bool cbits = RB == 1 && ROLE == 1 && px.cb.Sw != nullptr && o == 1, obits = RB == 1 && ROLE == 2 && px.cb.Sw != nullptr && o == 0;
-  const size_t ctile = (size_t)by * tgx + bx, ntile = (size_t)tgx * tgy;
-  // (objective: how many safe candidates the constraint's launch counted in this tile -- field 1 of its partial row)
-  const unsigned long long tile_nS = obits ? cpart[(size_t)1 * pcap + ctile] : 0ull;
-  cx.role = cbits ? 1 : ((obits && tile_nS != 0ull) ? 2 : 0);
-  cx.skip_store = obits && tile_nS == 0ull && px.lean != 0;
-  cx.lds_bits = reinterpret_cast<unsigned int*>(lds + 2 * (RB == 2 ? 4096 : 3072));
-  cx.umin = 1e300;
-  cx.xmin = 1e300;
-#pragma unroll
-  for (int s2 = 0; s2 < 8; ++s2) cx.bw[s2] = 0u;
-  cx.gb_on = (fuse || cbits) && gb != nullptr;
-  cx.lband = cx.gb_on ? lcb_band(cx.bb, gb->dm[o >= 1 ? o : 1], gb->dv[o >= 1 ? o : 1]) : LcbBand{0.0, 0.0};
-  cx.vminS = 1e300;
-  double gmax = 0.0;
-  // (Tried: odd outputs running the three short phases first and the variance phase last, so that the two workgroups of a
-  // CU do not reach their phase changes together -- no gain on config B, 2.5 % slower on H; one order for all.)
-  d4_t acc[RB][8];
-  d4_t pre[4];
-  const double* const A2 = VAo + (size_t)nrb * KBm * 256;
-  const double* const B2 = imode ? SBo : SBo + (size_t)ncs * KBm * 256;
-  const double* const A3 = VAo + (size_t)nrb * (KBm + KBm2) * 256;
-  const int es = imode ? 4 : 1;
-  const int KS1 = imode ? eff[4 * (4 * o + 1)] : KSm, KS2 = imode ? eff[4 * (4 * o + 2)] : KSm, KS3 = imode ? eff[4 * (4 * o + 3)] : KSm;
-#ifdef SBO_PHASE_CLOCKS
-  unsigned long long clk_ = wall_clock64();
-  const unsigned long long clk_in_ = clk_;
-  unsigned long long clk_part_ = clk_;
-  const unsigned int clk_row_ = ((unsigned int)o * tgy + by) * tgx + bx;
-#endif
-  // The gradient phases (their maxima are the Lipschitz keys, models/SafeOpt.py:68-83) run on the tiles that can hold the grid's
-  // maximum: the tile's largest coarse sample + the plan's bound on what lies between the samples reaches the grid's largest
-  // sample (k_bl_gradbound / k_bl_gradcoarse above).  Every tile folds its own samples in (true grid values).  NaN: run.
-  const double cg0 = ystd * mc.inv_ell[o][0] * mc.X_rstd[0], cg1 = ystd * mc.inv_ell[o][1] * mc.X_rstd[1];
-  bool run2 = true, run3 = true;
-  double gfold = 0.0;                       // (uniform: scalar registers -- folded in behind the phases)
-  if (gtmax) {
-    const size_t nt = ntile, tile = ctile;
-    const double* slack = gtmax + (size_t)px.q * 2 * nt;
-    const double t0 = gtmax[((size_t)o * 2 + 0) * nt + tile], t1 = gtmax[((size_t)o * 2 + 1) * nt + tile];
-    const double G0 = __longlong_as_double((long long)gkey[2 * o + 0]), G1 = __longlong_as_double((long long)gkey[2 * o + 1]);
-    run2 = !(t0 + slack[2 * o + 0] < G0 * (1.0 - 1e-12));
-    run3 = !(t1 + slack[2 * o + 1] < G1 * (1.0 - 1e-12));
-    const double f0 = fabs(cg0 * t0), f1 = fabs(cg1 * t1);
-    gfold = fmax(f0, f1);
-  }
-  if (px.nograd) { run2 = run3 = false; gfold = 0.0; }          // (the keys come from a launch of the gradient phases alone: k_bgrad)
-  if (ROLE == 2 && px.lean) { run2 = run3 = false; gfold = 0.0; }   // (a lean sweep: nobody reads the objective's key, include/safebo.h)
-  // lean sweeps, level 2: the objective's posterior of a tile without a safe candidate is not even evaluated -- u*, M and the
-  // arg-max reductions read it on S only (models/SafeOpt.py:47-66); the tile still runs the gradient phases the gate asks for
-  // (L_0 is a maximum over the whole grid), and with K1b's operands the mean phase those continue from
-  // r06, the same for the constraint: a tile whose every 8 x 8 cell the plan's enclosure proves unsafe at this b (encl_unsafe: ge = 0,
-  // le = 1, no undecided branch, outside the band test) is not evaluated either -- its words, counts and keys are those of a tile in
-  // which every candidate is in U, written here; its gradient phases run as the gate says.  Nothing of this sweep reads its mean /
-  // var: the set phase reads the constraint's posterior on tiles with a safe candidate only (G within S), and the audit checks a
-  // sample that lands here against the enclosure instead (guard.hip).
-  // (r07, a listed launch: the list's kernel took the decision, wrote the skip byte and counted the tile; its entry carries it)
-  bool cskip = false;
-  if (ROLE == 1 && cbits && px.lean >= 2 && px.encl != nullptr) {
-    if (listed) {
-      cskip = (ent >> 31) != 0u;
-    } else {
-      bool dec = true;
-      if (cx.tid < 128) {
-        const double4 e = reinterpret_cast<const double4*>(px.encl)[ctile * 128 + cx.tid];
-        dec = encl_unsafe(e.x, e.y, e.z, e.w, cx.bconf, cx.bb, cx.gb_on, cx.lband);
-      }
-      cskip = __syncthreads_and(dec ? 1 : 0) != 0;
-      if (cx.tid == 0) px.skip[ctile] = cskip ? 1 : 0;
-      if (cskip && cx.tid == 0) atomicAdd(&px.cb.slots[(size_t)kSlotSkip * kColSlots + (ctile & (kColSlots - 1))], 1ull);
-    }
-    if (cskip) {
-      cx.role = 0;
-      cx.skip_store = true;
-      cx.cU = 64 * 128 / 256;               // (every candidate in U, spread over the threads: the partials sum to 8192)
-      for (int i = cx.tid; i < 4 * 128; i += 256) cx.lds_bits[i] = 0xffff0000u;      // (S pieces 0, U pieces all ones)
-    }
-  }
-  const bool skip_tile = (ROLE == 2 && obits && tile_nS == 0ull && px.lean >= 2) || cskip;
-  if (!skip_tile)
-    post_phase<0, RB, ROLE>(cx, BtA + (size_t)o * sBtA, P0f + (size_t)o * sP0f, KB0, eff ? eff[4 * o * es] : KS0, vo, sf2, ystd * ystd, 0.0, gmax, acc, xn0, pre,
-                            VAo, SBo, KBm);
-  SBO_CLK(0);
-  if (ROLE == 2 && cx.role == 2) {
-    // the thread's own S bits: rows 16 wave + 4 t + (lane >> 4) of the segment, column (cs0 + s2) 16 + (lane & 15)
-#pragma unroll
-    for (int s2 = 0; s2 < 8; ++s2) {
-      const unsigned long long w = px.cb.Sw[(size_t)by * cx.ucnt0 + (unsigned int)(cx.cs0 + s2) * 16u + (cx.lane & 15)];
-      cx.bw[s2] = (unsigned int)(w >> (16 * cx.wave + (cx.lane >> 4))) & 0x1111u;
-    }
-  }
-  // (the mean phase requests the first operands of whichever phase follows it)
-  if (!skip_tile || (run2 && !imode))
-    post_phase<1, RB, ROLE>(cx, VAo, SBo, KBm, KS1, mo, mc.mp[o], ystd, mc.Y_mean[o], gmax, acc, xn0, pre, run2 ? A2 : A3, run2 ? B2 : SBo,
-                            run2 ? KBm2 : KBm);
-  SBO_CLK(1);
-  // phase 2 continues on phase 1's sums: only the V1 half (the first KSm k-steps) of the stacked operands is run
-  if (run2) post_phase<2, RB, ROLE>(cx, A2, B2, KBm2, KS2, nullptr, cg0, 0.0, 0.0, gmax, acc, xn0, pre, A3, SBo, KBm);
-  if (run3) post_phase<3, RB, ROLE>(cx, A3, SBo, KBm, KS3, nullptr, cg1, 0.0, 0.0, gmax, acc, xn0, pre, nullptr, nullptr, 0);
-  gmax = fmax(gmax, gfold);
-  SBO_CLK(2);
-#ifdef SBO_PHASE_CLOCKS
-  clk_part_ = clk_;
-#endif
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double other = __shfl_xor(gmax, off);
-    gmax = other > gmax ? other : gmax;
-  }
-  // one plain store per WORKGROUP, merged by k_lmax_reduce / the classification's final merge: every workgroup of this launch
-  // is resident at once and ends at the same time, so atomics on the q keys would queue up in L2 as the kernel's tail -- and
-  // a row per wave made that merge (one workgroup, 16384 rows of 88 bytes on config H) the longest job of the launch it shares
-  // (column path: the constraint's rows first, the objective's rows behind them)
-  post_partials<4>(cx.lds, cx.lane, cx.wave, gmax, fuse || cbits, cx.cS, cx.cU, obits ? -cx.umin : cx.rmax, cx.cB, cx.vminS,
-                   Lpart + ((size_t)o * tgy + by) * tgx + bx,
-                   cpart + (obits ? ntile : (fmulti && o >= 1 ? (size_t)(o - 1) * ntile : (size_t)0)) + ctile, pcap, obits,
-                   (cbits || obits) ? px.cb.slots : nullptr, (int)(ctile & (kColSlots - 1)), o, cbits ? (int)by : -1, (int)bx, cx.xmin, fmulti);
-  if (cbits && cx.tid < 128) {
-    // the tile's words: column tid, the four waves' 16-row pieces (written before the barriers of post_partials)
-    unsigned long long sw = 0ull, uw = 0ull;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const unsigned int pc = cx.lds_bits[w * 128 + cx.tid];
-      sw |= (unsigned long long)(pc & 0xffffu) << (16 * w);
-      uw |= (unsigned long long)(pc >> 16) << (16 * w);
-    }
-    const size_t col = (size_t)cx.cs0 * 16u + cx.tid;
-    px.cb.Sw[(size_t)by * cx.ucnt0 + col] = sw;
-    px.cb.Uw[(size_t)by * cx.ucnt0 + col] = uw;
-    if (uw != 0ull) atomicOr(&px.cb.Usum[col], 1ull << by);
-  }
-  SBO_CLK(3);
-#ifdef SBO_PHASE_CLOCKS
-  if (threadIdx.x == 0) {
-    g_phase_clk[clk_row_ & (kPhaseClkRows - 1)][4] += (unsigned long long)((run2 ? 1 : 0) + (run3 ? 1 : 0));
-    g_phase_clk[clk_row_ & (kPhaseClkRows - 1)][5] += 1ull;
-    if (ROLE != 0)
-      wg_trace_row(o, clk_in_, clk_part_, clk_, (unsigned int)ctile, skip_tile ? ((!cskip || !(run2 || run3)) ? 1u : 2u) : 0u);
-  }
-#endif
-}
-#ifdef SBO_PHASE_CLOCKS
-extern "C" int sbo_debug_phase_clocks(unsigned long long* out /* [16]: sums over the rows below `split` | from `split` on */, int reset, int split) {
-  std::vector<unsigned long long> h((size_t)kPhaseClkRows * 8);
-  if (hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_phase_clk), sizeof(unsigned long long) * h.size()) != hipSuccess) return 1;
-  for (int k = 0; k < 16; ++k) out[k] = 0;
-  for (size_t r = 0; r < (size_t)kPhaseClkRows; ++r)
-    for (int k = 0; k < 8; ++k) out[(r < (size_t)split ? 0 : 8) + k] += h[r * 8 + k];
-  if (reset) {
-    std::fill(h.begin(), h.end(), 0ull);
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase_clk), h.data(), sizeof(unsigned long long) * h.size()) != hipSuccess) return 1;
-  }
-  return 0;
-}
-// r07: the per-workgroup rows of the column path's two launches (g_wg_trace: [o][dispatch index][8]); reset: zero them afterwards
-extern "C" int sbo_debug_wg_trace(unsigned long long* out /* [2][rows][8] */, int rows, int reset) {
-  if (rows != kWgTraceRows) return 2;
-  const size_t bytes = sizeof(unsigned long long) * 2 * kWgTraceRows * 8;
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wg_trace), bytes) != hipSuccess) return 1;
-  if (reset) {
-    std::vector<unsigned long long> z(bytes / sizeof(unsigned long long), 0ull);
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_wg_trace), z.data(), bytes) != hipSuccess) return 1;
-  }
-  return 0;
-}
-#endif
-
-
-// K1i's deferred gradient launch (r05): the two gradient series of every output on the tiles the gate names, nothing else -- on
-// stream3 behind the gate's kernels, beside the posterior launches, which then carry no gradient phases (PostExtra::nograd).  A
-// resident-sized grid walks the (output, tile) table: a tile the gate excludes costs two loads, and its row of the Lipschitz partials
-// holds its largest coarse sample as before.  Rows [q][tiles] as k_bpost writes them; column path: the workgroup's maximum per output
-// also joins the slot block.
-__global__ __launch_bounds__(256, 3) void k_bgrad(const ModelConst mc, const CandSpec cs, const double* __restrict__ VA, size_t sVA,
-                                                  const double* __restrict__ P0f, int KB, int nrb, int ncs, long long nlines, int gx, int gy,
-                                                  const int* __restrict__ eff, const double* __restrict__ gtmax,
-                                                  const unsigned long long* __restrict__ gkey, const double* __restrict__ xn0, int q,
-                                                  double* __restrict__ Lpart, unsigned long long* __restrict__ slots,
-                                                  int o_first /* 1: a lean sweep -- nobody reads the objective's key, its rows stay zero */) {
-  extern __shared__ double lds[];
-  PostCtx cx;
-  cx.lds = lds;
-  cx.tid = threadIdx.x; cx.lane = cx.tid & 63; cx.wave = cx.tid >> 6;
-  cx.nrb = nrb; cx.ncs = ncs;
-  cx.ucnt0 = (unsigned int)cs.count[0];
-  cx.nlines = nlines;
-  cx.imode = true;
-  const int st_i = cx.tid >> 5, st_j = cx.tid & 31;
-  cx.st_off = st_j * 8;
-  cx.a_lo = st_i < 4 ? st_i * 256 + (st_j >> 3) * 64 + (st_j & 7) * 4 : -1;
-  cx.b_st = 1024 + st_i * 256 + cx.st_off;
-  cx.a_rd = (((cx.lane >> 4) << 2) + (cx.lane & 3)) * 2;
-  cx.var_rd = nullptr; cx.S = nullptr; cx.U = nullptr;
-  cx.bconf = 0.0; cx.bb = 0.0; cx.cS = cx.cU = cx.cB = 0; cx.rmax = -1.0;
-  cx.lband = LcbBand{0.0, 0.0}; cx.gb_on = false; cx.vminS = 1e300;
-  cx.role = 0; cx.lds_bits = nullptr; cx.umin = 1e300; cx.xmin = 1e300; cx.skip_store = false;
-#pragma unroll
-  for (int s2 = 0; s2 < 8; ++s2) cx.bw[s2] = 0u;
-  const size_t nt = (size_t)gx * gy;
-  const double* slack = gtmax ? gtmax + (size_t)q * 2 * nt : nullptr;       // (no gate: every tile runs both phases)
-  d4_t acc[1][8];
-  d4_t pre[4];
-  for (size_t tile = blockIdx.x; o_first > 0 && tile < nt; tile += gridDim.x)
-    if (cx.tid == 0) Lpart[tile] = 0.0;
-  for (int o = o_first; o < q; ++o) {
-    const double ystd = mc.Y_std[o];
-    const double cg0 = ystd * mc.inv_ell[o][0] * mc.X_rstd[0], cg1 = ystd * mc.inv_ell[o][1] * mc.X_rstd[1];
-    const double G0 = gtmax ? __longlong_as_double((long long)gkey[2 * o + 0]) : 0.0, G1 = gtmax ? __longlong_as_double((long long)gkey[2 * o + 1]) : 0.0;
-    const double s0 = gtmax ? slack[2 * o + 0] : 0.0, s1 = gtmax ? slack[2 * o + 1] : 0.0;
-    const int KS2 = eff[4 * (4 * o + 2)], KS3 = eff[4 * (4 * o + 3)];
-    const double* VAo = VA + (size_t)o * sVA;
-    const double* A2 = VAo + (size_t)nrb * KB * 256;
-    const double* A3 = VAo + (size_t)nrb * (2 * KB) * 256;
-    double wg_max = 0.0;
-    for (size_t tile = blockIdx.x; tile < nt; tile += gridDim.x) {
-      const double t0 = gtmax ? gtmax[((size_t)o * 2 + 0) * nt + tile] : 0.0, t1 = gtmax ? gtmax[((size_t)o * 2 + 1) * nt + tile] : 0.0;
-      const bool run2 = !(t0 + s0 < G0 * (1.0 - 1e-12)), run3 = !(t1 + s1 < G1 * (1.0 - 1e-12));          // (NaN: run)
-      double g = fmax(fabs(cg0 * t0), fabs(cg1 * t1));
-      if (run2 || run3) {
-        const int bx = (int)(tile % (size_t)gx), by = (int)(tile / (size_t)gx);
-        cx.rb0 = by * 4; cx.cs0 = bx * 8;
-        cx.full = (long long)(cx.rb0 + 4) * 16 <= nlines && (long long)(cx.cs0 + 8) * 16 <= cs.count[0];
-        cx.st_rb = cx.rb0 + st_i < nrb ? cx.rb0 + st_i : nrb - 1;
-        cx.st_cs = cx.cs0 + st_i < ncs ? cx.cs0 + st_i : ncs - 1;
-        double gmax = 0.0;
-        if (run2) post_phase<2, 1, 0>(cx, A2, P0f, KB, KS2, nullptr, cg0, 0.0, 0.0, gmax, acc, xn0, pre, nullptr, nullptr, 0);
-        if (run3) post_phase<3, 1, 0>(cx, A3, P0f, KB, KS3, nullptr, cg1, 0.0, 0.0, gmax, acc, xn0, pre, nullptr, nullptr, 0);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-          const double other = __shfl_xor(gmax, off);
-          gmax = other > gmax ? other : gmax;
-        }
-        __syncthreads();
-        if (cx.lane == 0) lds[cx.wave] = gmax;
-        __syncthreads();
-        gmax = fmax(fmax(lds[0], lds[1]), fmax(lds[2], lds[3]));
-        __syncthreads();
-        g = fmax(g, gmax);
-      }
-      if (cx.tid == 0) Lpart[(size_t)o * nt + tile] = g;
-      wg_max = fmax(wg_max, g);
-    }
-    if (slots && cx.tid == 0)
-      atomicMax(&slots[(size_t)(o == 0 ? kSlotL0 : kSlotL1) * kColSlots + (blockIdx.x & (kColSlots - 1))], (unsigned long long)__double_as_longlong(wg_max));
-  }
-}
-
-// Lipschitz keys of a K1b launch: Lmax[o] = max of the per-wave partials (values >= 0, so the bit pattern orders them)
-__global__ __launch_bounds__(256) void k_lmax_reduce(const double* __restrict__ Lpart, int per_out, unsigned long long* __restrict__ Lmax) {
-  __shared__ double sh[4];
-  lmax_reduce_body((int)blockIdx.x, sh, Lpart, per_out, Lmax);
-}
+#include "bilinear_post.inc.hpp"
 
 // ---- Chebyshev core of the variance phase (r03) ---------------------------------------------------------------------------
 // The pair form above contracts  quad = sum_{k0, k1} T4[k0][k1] P0_k0(x0) P1_k1(x1)  over K = r (r + 1) / 2 ~ 276 pair products
@@ -2682,7 +1589,8 @@ int bilinear_setup(sbo_ctx* c) {
   BilinearPlan& pl = c->bl;
   pl.valid = true;
   pl.usable = false;
-  pl.band_ready = false;
+  pl.ops = GemmOps();
+  GemmOps& g = pl.ops;
   pl.encl_ready = false;
   pl.setup_ms = 0.0;
   const auto t_begin = std::chrono::steady_clock::now();
@@ -2743,21 +1651,18 @@ int bilinear_setup(sbo_ctx* c) {
     if (gemm > 0.7 * tri) return SBO_OK;
   }
   const long long nlines_pad = (long long)nrb * 16;
-  pl.KB0 = KB0; pl.KB1 = KB1; pl.r0u = r0u; pl.ncs0 = ncs0; pl.nrb = nrb; pl.nlines_pad = nlines_pad;
-  pl.sP0f = 0;                                              // (one table of Chebyshev polynomials for every output)
-  pl.sP1A = 0;
+  pl.r0u = r0u; pl.nlines_pad = nlines_pad;
+  g.KB0 = KB0; g.KB1 = KB1; g.ncs0 = ncs0; g.nrb = nrb;
+  g.sP0f = g.sP1A = 0;                                     // (one table of Chebyshev polynomials for every output)
   const size_t nP0f = (size_t)ncs0 * KB0 * 4 * 64, nP1A = (size_t)nrb * KB1 * 256;
-  pl.sT4f = (size_t)KB0 * KB1 * 4 * 64;
-  pl.sBtA = (size_t)nrb * KB0 * 256;
+  g.sT4f = (size_t)KB0 * KB1 * 4 * 64;
+  g.sBtA = g.sBt1 = (size_t)nrb * KB0 * 256;
   // mean phases: K = r0p (basis size rounded to whole k-steps); the axis-0 gradient phase concatenates two such operands
   const int r0p = (r0u + 3) / 4 * 4;
   const int KBm = (r0p + 15) / 16, KBm2 = (2 * r0p + 15) / 16;
-  pl.KBm = KBm;
-  pl.KBm2 = KBm2;
-  pl.KSm = r0p / 4;
-  pl.KS0 = KB0 * 4;
-  pl.sVA = (size_t)nrb * (2 * KBm + KBm2) * 256;     // image sets  V0 | [V1; V0] | V1x
-  pl.sSBf = (size_t)ncs0 * (KBm + KBm2) * 256;      // fragment sets  S0 | [S0; -xn0 S0]
+  g.KBm = KBm; g.KBm2 = KBm2; g.KSm = r0p / 4; g.KS0 = KB0 * 4;
+  g.sVA = (size_t)nrb * (2 * KBm + KBm2) * 256;     // image sets  V0 | [V1; V0] | V1x
+  g.sSBf = (size_t)ncs0 * (KBm + KBm2) * 256;      // fragment sets  S0 | [S0; -xn0 S0]
   if ((rc = ensure(c->bl_P0f, sizeof(double) * nP0f))) return rc;
   if ((rc = ensure(c->bl_P1A, sizeof(double) * nP1A))) return rc;
   // Chebyshev core scratch: PC0 | PC1 | T4 plain | Y^T | Chat | eff (ints)
@@ -2768,10 +1673,11 @@ int bilinear_setup(sbo_ctx* c) {
   const size_t nPC0 = D0m * (size_t)KBp0 * 16, nPC1 = D1m * (size_t)KBp1 * 16, nT4p = (size_t)KBp0 * KBp1 * 256, nYt = D1m * (size_t)KBp0 * 16,
                nCh = D0m * D1m;
   if ((rc = ensure(c->bl_cheb, sizeof(double) * (size_t)q * (nPC0 + nPC1 + nT4p + nYt + nCh) + 256))) return rc;
-  if ((rc = ensure(c->bl_T4f, sizeof(double) * pl.sT4f * q))) return rc;
-  if ((rc = ensure(c->bl_SBf, sizeof(double) * pl.sSBf * q))) return rc;     // mean-phase B fragments
-  if ((rc = ensure(c->bl_VA, sizeof(double) * pl.sVA * q))) return rc;      // mean-phase A images
-  if ((rc = ensure(c->bl_BtA, sizeof(double) * pl.sBtA * q))) return rc;
+  if ((rc = ensure(c->bl_T4f, sizeof(double) * g.sT4f * q))) return rc;
+  if ((rc = ensure(c->bl_SBf, sizeof(double) * g.sSBf * q))) return rc;     // mean-phase B fragments
+  if ((rc = ensure(c->bl_VA, sizeof(double) * g.sVA * q))) return rc;      // mean-phase A images
+  if ((rc = ensure(c->bl_BtA, sizeof(double) * g.sBtA * q))) return rc;
+  g.BtA = (double*)c->bl_BtA.p; g.P0f = (double*)c->bl_P0f.p; g.VA = (double*)c->bl_VA.p; g.SBf = (double*)c->bl_SBf.p;
   const int KBn = mc.npad / 16, ncsR = (Rmax + 15) / 16;
   const size_t nZf = (size_t)ncsR * KBn * 256;                // fragments of Z, of C, images of C^T: same size
   const size_t ldg = (size_t)ncsR * 16;
@@ -2845,14 +1751,12 @@ int bilinear_setup(sbo_ctx* c) {
   hipLaunchKernelGGL(k_bl_mb, blocks((size_t)3 * r0u * r1u * 64, uq), dim3(256), 0, ys, dm, dU, (const double*)c->alpha64.p,
                      c->a_ld, (const double*)c->Xn.p, mc.dpad, dMb);
   hipLaunchKernelGGL(k_bl_vb, blocks((size_t)3 * r0u * nlines, uq), dim3(256), 0, ys, dm, (const double*)dMb, (const double*)dS1, dVb);
-  hipLaunchKernelGGL(k_bl_va, blocks(pl.sVA, uq), dim3(256), 0, ys, dm, (const double*)dVb, (const double*)dxn1, pl.sVA,
+  hipLaunchKernelGGL(k_bl_va, blocks(g.sVA, uq), dim3(256), 0, ys, dm, (const double*)dVb, (const double*)dxn1, g.sVA,
                      (double*)c->bl_VA.p);
-  hipLaunchKernelGGL(k_bl_sbf, blocks(pl.sSBf, uq), dim3(256), 0, ys, dm, (const double*)dS0, (const double*)dxn0, pl.sSBf,
+  hipLaunchKernelGGL(k_bl_sbf, blocks(g.sSBf, uq), dim3(256), 0, ys, dm, (const double*)dS0, (const double*)dxn0, g.sSBf,
                      (double*)c->bl_SBf.p);
   // where the gradient phases of k_bpost have to run (k_bl_gradbound / k_bl_gradcoarse): [q][2][tiles] largest samples | [q][2]
   // slacks | [q][2] keys of the grid's largest samples | scratch of the coefficient kernel
-  pl.gtmax = nullptr;
-  pl.gkey = nullptr;
   {
     static_assert(kGradNpx * kGradNpl == 128, "k_bl_gradcoarse: one sample per thread");
     const int ntx = (ncs0 + 7) / 8, nty = (nrb + 3) / 4;
@@ -2876,8 +1780,8 @@ int bilinear_setup(sbo_ctx* c) {
                        (const double*)dxn1, ntx, gt, gkey);
     hipLaunchKernelGGL(k_bl_gradmax, dim3(2 * uq), dim3(256), 0, ys, (const double*)gt, (int)nt, gkey);
     if (std::isfinite(dxi0) && std::isfinite(dxi1)) {
-      pl.gtmax = gt;
-      pl.gkey = gkey;
+      g.gtmax = gt;
+      g.gkey = gkey;
     }
   }
   // guard band of this plan (guard.hip): the exact evaluator at the probe points runs here, beside the core's GEMM chain
@@ -2912,10 +1816,10 @@ int bilinear_setup(sbo_ctx* c) {
     hipLaunchKernelGGL((k_bgemm<4, 0, 2>), dim3((unsigned)((ncsD0 + 3) / 4), (unsigned)((nrbD1 + 3) / 4), uq), dim3(256), 0, xs, (const double*)Yt,
                        nYt, (const double*)PC0, nPC0, KBp0, nrbD1, ncsD0, Chat, nCh, (double*)nullptr, (long long)D0m);
     hipLaunchKernelGGL(k_cheb_trunc, dim3(uq), dim3(1024), 0, xs, dm, (const double*)Chat, c->cheb_tol, eff);
-    hipLaunchKernelGGL(k_cheb_t4f, blocks(pl.sT4f, uq), dim3(256), 0, xs, dm, (const double*)Chat, pl.sT4f, (double*)c->bl_T4f.p);
+    hipLaunchKernelGGL(k_cheb_t4f, blocks(g.sT4f, uq), dim3(256), 0, xs, dm, (const double*)Chat, g.sT4f, (double*)c->bl_T4f.p);
     // (the counts also travel to the host, unwaited: the profile's flop count reads them after the next sweep's own sync)
     SBO_HIP(hipMemcpyAsync(c->h_back + 5376, eff, sizeof(int) * 4 * q, hipMemcpyDeviceToHost, xs));
-    pl.eff = eff;
+    g.eff = eff;
   }
   if (ys != xs) SBO_HIP(hipStreamWaitEvent(xs, c->ev_join[3], 0));
   if (band && zs != ys) SBO_HIP(hipStreamWaitEvent(xs, c->ev_join[6], 0));
@@ -2925,7 +1829,7 @@ int bilinear_setup(sbo_ctx* c) {
     double* pm = gref_m + 2 * (size_t)q * kGbProbes;
     double* pv = pm + (size_t)q * kGbProbes;
     const double* Chat = (const double*)c->bl_cheb.p + (size_t)q * (nPC0 + nPC1 + nT4p + nYt);
-    hipLaunchKernelGGL(k_gb_probe_k1b, dim3((unsigned)((kGbProbes + 3) / 4), uq), dim3(256), 0, xs, mc, cs, dm, Chat, (const int*)pl.eff,
+    hipLaunchKernelGGL(k_gb_probe_k1b, dim3((unsigned)((kGbProbes + 3) / 4), uq), dim3(256), 0, xs, mc, cs, dm, Chat, (const int*)g.eff,
                        (const double*)dxn0, (const double*)dxn1, (const double*)dS0, (const double*)dVb, pm, pv);
     GbAnalytic an;
     memset(&an, 0, sizeof(an));
@@ -2938,18 +1842,18 @@ int bilinear_setup(sbo_ctx* c) {
     an.dpad = mc.dpad;
     for (int t = 0; t < 4; ++t) an.ab[t] = c->bl_basis_ab[t];
     an.ref_g = gref_g;
-    if ((rc = guard_band_from_probes(c, pm, pv, gref_m, gref_v, reinterpret_cast<const double*>(pl.eff + 4 * q), an))) return rc;
-    pl.band_ready = true;
+    if ((rc = guard_band_from_probes(c, pm, pv, gref_m, gref_v, reinterpret_cast<const double*>(g.eff + 4 * q), an))) return rc;
+    g.band_ready = true;
   }
   SBO_HIP(hipGetLastError());
   lap("enqueue");
-  if (timing && pl.gtmax) {
+  if (timing && g.gtmax) {
     // (diagnostic: how many tiles keep their gradient phases)
     const int ntx = (ncs0 + 7) / 8, nty = (nrb + 3) / 4;
     const size_t nt = (size_t)ntx * nty;
     std::vector<double> h((size_t)q * 2 * nt + 4 * (size_t)q);
     SBO_HIP(hipStreamSynchronize(xs));
-    SBO_HIP(hipMemcpy(h.data(), pl.gtmax, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+    SBO_HIP(hipMemcpy(h.data(), g.gtmax, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
     const double* sl = h.data() + (size_t)q * 2 * nt;
     for (int o = 0; o < q; ++o)
       for (int k = 0; k < 2; ++k) {
@@ -2966,916 +1870,6 @@ int bilinear_setup(sbo_ctx* c) {
 }
 
 
-// ---- K1i: the first sweep of a model by interpolation from Chebyshev nodes (r04) -----------------------------------------------
-// The reference refits its models after every sample (models/GP_Safe.py:283-304) and sweeps each of them ONCE
-// (test/test_SafeOpt.py:144-179), so what an iteration pays for K1b is its plan: axis bases by pivoted Gram-Schmidt (0.16 ms the
-// host has to wait for -- their ranks size everything after them), the core's contraction over rank^2 columns, guard probes:
-// ~0.45 ms of a 1.07 ms iteration on config H.  K1b's own evaluation stage does not care where its Chebyshev coefficients come
-// from.  So, for the first sweep of a model with a caller's invK:
-//   1. the posterior's two scalar fields per output -- quad = k*^T invK k* and s1 = k*^T alpha -- EXACTLY (the reference formula,
-//      models/GP_Safe.py:341-343, with the matrix as given) at the Dn x Dn tensor grid of Chebyshev nodes of the first kind on the
-//      grid's box: K*^T as B fragments from two n x Dn tables of axis factors (the kernel is separable), C = invK K*^T on the matrix
-//      cores (k_bgemm on the packed images of invK), then column dots quad_c = Z_c . C_c, s1_c = Z_c . alpha;
-//   2. a 2-D discrete cosine transform of each field -> its Chebyshev coefficients, and those of the two gradient sums of the mean
-//      by the derivative recurrence (d_{m-1} = d_{m+1} + 2 m c_m);
-//   3. the coefficients through k_cheb_trunc / k_cheb_t4f / k_bstage1 / k_bpost as K1b's core goes: four coefficient sets per output.
-// Nothing of this needs a number from the device on the host: the plan is enqueued by sbo_model_set behind the upload and the
-// first sweep follows in stream order; the bases and K1b's own plan are built when the same model is swept a second time.
-// Accuracy: Dn from the length scales as K1t chooses it (32 / 48 / 64); measured on the BASELINE models 1e-13 (mean) and 1e-12
-// (variance: the rounding of the reference formula itself) -- and measured again for every plan at the guard band's probe points
-// (values and gradient), so the sweep's decisions stay those of the exact kernel whatever the interpolation error is.
-constexpr int kIMaxDn = 64;
-constexpr double kGbAliasFactor = 4.0;   // aliasing estimate of an interpolant's band, in units of the last four degrees' coefficient sum
-constexpr double kGbInf = 1.0e300;          // a probe that is not finite: everything is "inside the band" (guard.hip)
-struct InterpDims {
-  int Dn, q, n, npad, dpad;
-  double mid[2], half[2];                  // node interval of each axis, normalised coordinates
-};
-// Everything of a plan that changes with the MODEL (hyper-parameters, normalisation, the box in normalised coordinates) reaches the
-// plan's kernels through this block in device memory -- launch arguments then depend on the grid and on n only, and the plan of the
-// next model of the same shape is the same HIP graph with another block (interp_setup).
-struct InterpParams {
-  ModelConst mc;
-  InterpDims id;
-  BlDims dm;
-  double dxi0, dxi1;                       // half a sampling cell of the gradient gate in xi units
-};
-// E[(2 o + axis)][p][j] = (axis == 0 ? sf2 : 1) exp(-1/2 (As_j,axis - xn_p vinv)^2)   (k_bl_zf multiplies the two axes)
-__global__ __launch_bounds__(256) void k_i_etab(const InterpParams* __restrict__ P, const double* __restrict__ As, double* __restrict__ E) {
-  const ModelConst& mc = P->mc;
-  const InterpDims& id = P->id;
-  const int job = blockIdx.y, o = job >> 1, axis = job & 1;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < id.Dn * id.n; e += gridDim.x * blockDim.x) {
-    const int p = e / id.n, j = e % id.n;
-    const double xn = id.mid[axis] + id.half[axis] * cospi(((double)p + 0.5) / (double)id.Dn);
-    const double dlt = As[((size_t)o * id.npad + j) * id.dpad + axis] - xn * mc.vinv[o][axis];
-    E[((size_t)job * kBlMaxR + p) * id.n + j] = (axis == 0 ? mc.sf2[o] : 1.0) * exp(-0.5 * dlt * dlt);
-  }
-}
-// node values from the fragments of Z = K*^T and C = invK Z ([ncsR][KBn * 4][64], k = observation): V[o][0][c] = sum_j Z_jc C_jc,
-// V[o][1][c] = sum_j Z_jc alpha_j.  A wave per strip of 16 columns.
-__global__ __launch_bounds__(64) void k_i_nodevals(int KBn, int n, const double* __restrict__ Zfall, const double* __restrict__ Cfall, size_t nZf,
-                                                   const double* __restrict__ alpha, int ald, int ncols, double* __restrict__ V) {
-  const int o = blockIdx.y, cs = blockIdx.x, l = threadIdx.x;
-  const double* Zf = Zfall + (size_t)o * nZf + (size_t)cs * KBn * 256;
-  const double* Cf = Cfall + (size_t)o * nZf + (size_t)cs * KBn * 256;
-  double aq[4] = {0.0, 0.0, 0.0, 0.0}, am[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int ks = 0; ks < KBn * 4; ks += 4) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int k = ks + u, j = (k >> 2) * 16 + MM<double>::jslot(k & 3, l >> 4);
-      const double z = Zf[(size_t)k * 64 + l];
-      aq[u] = fma(z, Cf[(size_t)k * 64 + l], aq[u]);
-      am[u] = fma(z, j < n ? alpha[(size_t)o * ald + j] : 0.0, am[u]);
-    }
-  }
-  double sq = (aq[0] + aq[1]) + (aq[2] + aq[3]), sm = (am[0] + am[1]) + (am[2] + am[3]);
-  sq += __shfl_xor(sq, 16); sm += __shfl_xor(sm, 16);
-  sq += __shfl_xor(sq, 32); sm += __shfl_xor(sm, 32);
-  const int c = cs * 16 + l;
-  if (l < 16 && c < ncols) {
-    V[((size_t)o * 2 + 0) * ncols + c] = sq;
-    V[((size_t)o * 2 + 1) * ncols + c] = sm;
-  }
-}
-// Chebyshev coefficients of the node fields, ChatT[4 o + f][b][a] (b: degree along axis 1, a: along axis 0; the layout k_cheb_trunc /
-// k_cheb_t4f read): f = 0 quad, 1 s1, 2 / 3 the gradient sums g_a = (d s1 / d xn_a) / inv_ell_a of the two axes (k_bpost scales by
-// Y_std inv_ell X_rstd).  One workgroup per output; node c = p Dn + s (p: axis 0).  T[m][k] = w_m cos(m pi (k + 1/2) / Dn) / Dn.
-__global__ __launch_bounds__(1024) void k_i_dct(const InterpParams* __restrict__ P_, const double* __restrict__ V, double* __restrict__ ChatT_all) {
-  const ModelConst& mc = P_->mc;
-  const InterpDims& id = P_->id;
-  extern __shared__ double sh[];                 // T [Dn][Dn + 1] | field [Dn][Dn + 1] | tmp [Dn][Dn + 1]  (rows padded: column walks)
-  const int Dn = id.Dn, o = blockIdx.x >> 1, f = blockIdx.x & 1, tid = threadIdx.x, N2 = Dn * Dn, P = Dn + 1;
-  double *T = sh, *F = sh + Dn * P, *W = sh + 2 * Dn * P;
-  for (int e = tid; e < N2; e += blockDim.x) {
-    const int m = e / Dn, k = e % Dn;
-    T[m * P + k] = (m == 0 ? 1.0 : 2.0) / (double)Dn * cospi((double)m * ((double)k + 0.5) / (double)Dn);
-    F[m * P + k] = V[((size_t)o * 2 + f) * N2 + e];                                         // F[p][s]
-  }
-  __syncthreads();
-  for (int e = tid; e < N2; e += blockDim.x) {                                                // W[a][s] = sum_p T[a][p] F[p][s]
-    const int a = e / Dn, s_ = e % Dn;
-    double a0 = 0.0, a1 = 0.0;
-    for (int p = 0; p + 1 < Dn; p += 2) {
-      a0 = fma(T[a * P + p], F[p * P + s_], a0);
-      a1 = fma(T[a * P + p + 1], F[(p + 1) * P + s_], a1);
-    }
-    W[a * P + s_] = a0 + a1;
-  }
-  __syncthreads();
-  double* out = ChatT_all + (size_t)(4 * o + f) * N2;
-  for (int e = tid; e < N2; e += blockDim.x) {                                                // C[a][b] = sum_s W[a][s] T[b][s]
-    const int b = e / Dn, a = e % Dn;
-    double a0 = 0.0, a1 = 0.0;
-    for (int s_ = 0; s_ + 1 < Dn; s_ += 2) {
-      a0 = fma(W[a * P + s_], T[b * P + s_], a0);
-      a1 = fma(W[a * P + s_ + 1], T[b * P + s_ + 1], a1);
-    }
-    out[e] = a0 + a1;                                                                         // ChatT[b][a]
-    F[b * P + a] = a0 + a1;
-  }
-  if (f == 0) return;                            // (uniform: the workgroup of the mean sum goes on to its derivatives)
-  __syncthreads();
-  // derivative series of s1: along axis 0 (index a) for g_0, along axis 1 (index b) for g_1; d xi / d xn = 1 / half
-  double* g0 = ChatT_all + (size_t)(4 * o + 2) * N2;
-  double* g1 = ChatT_all + (size_t)(4 * o + 3) * N2;
-  const double sc0 = 1.0 / (id.half[0] * mc.inv_ell[o][0]), sc1 = 1.0 / (id.half[1] * mc.inv_ell[o][1]);
-  for (int r = tid; r < 2 * Dn; r += blockDim.x) {
-    const int line = r % Dn;
-    const bool along0 = r < Dn;
-    // coefficients c_m of this line: along axis 0 the line is a row b of F (stride 1), along axis 1 a column a (stride P)
-    const int fb = along0 ? line * P : line, fs = along0 ? 1 : P;
-    const int ob = along0 ? line * Dn : line, os = along0 ? 1 : Dn;
-    double* dst = along0 ? g0 : g1;
-    const double sc = along0 ? sc0 : sc1;
-    double d2 = 0.0, d1 = 0.0;                  // d_{m+1}, d_m while walking m = Dn - 1 .. 1
-    dst[ob + (Dn - 1) * os] = 0.0;
-    for (int m = Dn - 1; m >= 1; --m) {
-      const double dm1 = d2 + 2.0 * (double)m * F[fb + m * fs];            // d_{m-1}
-      dst[ob + (m - 1) * os] = (m == 1 ? 0.5 * dm1 : dm1) * sc;
-      d2 = d1;
-      d1 = dm1;
-    }
-  }
-}
-// ---- K1i: where the gradient phases have to run (as k_bl_gradcoarse does it for K1b) -------------------------------------------
-// The coarse kernel of K1b takes a rank-r0 bilinear form sum_p Vb[p][line] S0[p][x0]; a Chebyshev series is one with
-// S0[a][x0] = T_a(xi0(x0)) and Vb[comp][a][line] = sum_b ChatT_comp[b][a] T_b(xi1(line)).
-// K1i's tables of the grid positions in ONE launch (the plan is bound by the host's enqueue rate on the smaller grids: every launch
-// less is ~7 us): normalised positions xn0 / xn1 (k_bl_axes), Chebyshev polynomials as B fragments of axis 0 / A images of axis 1
-// (k_cheb_tab<1> / <0>) and the plain table of axis 0 for the gradient gate.  A thread per position.
-__global__ __launch_bounds__(256) void k_i_tabs(const InterpParams* __restrict__ P_, const CandSpec cs, long long line0, double* __restrict__ xn0,
-                                                double* __restrict__ xn1, double* __restrict__ P0f, double* __restrict__ P1A,
-                                                double* __restrict__ S0all) {
-  const ModelConst& mc = P_->mc;
-  const BlDims& dm = P_->dm;
-  const int KB = dm.KB0, Dn = dm.D0m;
-  const long long n0 = (long long)dm.ncs0 * 16, n1 = (long long)dm.nrb * 16;
-  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n0 + n1; t += (long long)gridDim.x * blockDim.x) {
-    const int axis = t < n0 ? 0 : 1;
-    const long long x = axis == 0 ? t : t - n0, count = axis == 0 ? dm.cnt0 : dm.nlines;
-    double xi = 0.0;
-    if (x < count) {
-      const long long i = axis == 0 ? x : line0 + x, tot = cs.count[axis];
-      const double xr = (i == tot - 1 && tot > 1) ? cs.hi[axis] : __dadd_rn(cs.lo[axis], __dmul_rn((double)i, cs.step[axis]));
-      const double xn = (xr - mc.X_mean[axis]) / mc.X_std[axis];
-      if (axis == 0) xn0[x] = xn; else xn1[x] = xn;
-      xi = (2.0 * xn - (dm.a[axis] + dm.b[axis])) / (dm.b[axis] - dm.a[axis]);
-      xi = xi < 1.0 ? xi : 1.0;
-      xi = xi > -1.0 ? xi : -1.0;
-    }
-    double t0 = 1.0, t1 = xi;
-    for (int k = 0; k < KB * 16; ++k) {
-      double v = k == 0 ? t0 : t1;
-      if (k >= 2) { v = 2.0 * xi * t1 - t0; t0 = t1; t1 = v; }
-      if (x >= count) v = 0.0;
-      const int kb = k >> 4, j = k & 15, kk = j >> 2, slot = j & 3;
-      if (axis == 0) {
-        P0f[(((size_t)(x >> 4) * (KB * 4) + (size_t)(kb * 4 + kk)) << 6) + (size_t)(slot * 16 + (x & 15))] = v;
-        if (x < count && k < Dn)
-          for (int o = 0; o < dm.q / 4; ++o) S0all[((size_t)o * Dn + k) * dm.cnt0 + x] = v;
-      } else {
-        P1A[(((size_t)(x >> 4) * KB + kb) << 8) + (size_t)MM<double>::pack_pos((int)(x & 15), slot, kk)] = v;
-      }
-    }
-  }
-}
-// Vb[o][comp + 1][a][line] for the two gradient sums (comp 0: zero -- the slot K1b's form multiplies by xn); blockIdx.y = o.
-// A thread per (line, eight degrees a -- blockIdx.z): its T_b(xi1) in registers, the coefficients through LDS.
-template <int DM>
-__global__ __launch_bounds__(256) void k_i_rtab(const InterpParams* __restrict__ P_, const double* __restrict__ ChatT_all, const int* __restrict__ eff,
-                                                const double* __restrict__ xn1, double* __restrict__ Vball) {
-  const BlDims& dm = P_->dm;
-  __shared__ double Cs[DM * DM];
-  const int o = blockIdx.y, Dn = dm.D0m;
-  const long long line = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  double tb[DM];
-  {
-    double xi = 0.0;
-    if (line < dm.nlines) {
-      xi = (2.0 * xn1[line] - (dm.a[1] + dm.b[1])) / (dm.b[1] - dm.a[1]);
-      xi = xi < 1.0 ? xi : 1.0;
-      xi = xi > -1.0 ? xi : -1.0;
-    }
-    tb[0] = 1.0;
-    if (DM > 1) tb[1] = xi;
-#pragma unroll
-    for (int b = 2; b < DM; ++b) tb[b] = 2.0 * xi * tb[b - 1] - tb[b - 2];
-  }
-  double* Vb = Vball + (size_t)o * 3 * Dn * dm.nlines;
-  for (int comp = 0; comp < 2; ++comp) {
-    const double* Ch = ChatT_all + (size_t)(4 * o + 2 + comp) * Dn * Dn;
-    const int B = eff[4 * (4 * o + 2 + comp) + 2] * 16;                    // degrees of axis 1 the kernels run
-    __syncthreads();
-    for (int e = threadIdx.x; e < Dn * Dn; e += blockDim.x) Cs[e] = Ch[e];
-    __syncthreads();
-    if (line < dm.nlines) {
-      for (int a = blockIdx.z * 8; a < (int)blockIdx.z * 8 + 8 && a < Dn; ++a) {
-        double s = 0.0;
-#pragma unroll
-        for (int b = 0; b < DM; ++b)
-          if (b < B) s = fma(Cs[b * Dn + a], tb[b], s);
-        Vb[((size_t)(comp + 1) * Dn + a) * dm.nlines + line] = s;
-        if (comp == 0) Vb[(size_t)a * dm.nlines + line] = 0.0;
-      }
-    }
-  }
-}
-// bound on what a gradient sum moves by over half a sampling cell, from its coefficients: sum |C| a^2 dxi0 + sum |C| b^2 dxi1
-__global__ __launch_bounds__(256) void k_i_gradslack(const InterpParams* __restrict__ P_, const double* __restrict__ ChatT_all,
-                                                     double* __restrict__ slack /* [q][2] */) {
-  const BlDims& dm = P_->dm;
-  const double dxi0 = P_->dxi0, dxi1 = P_->dxi1;
-  __shared__ double red[4][2];
-  const int oc = blockIdx.x, o = oc >> 1, comp = oc & 1, Dn = dm.D0m, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const double* Ch = ChatT_all + (size_t)(4 * o + 2 + comp) * Dn * Dn;
-  double sa = 0.0, sb = 0.0;
-  for (int e = tid; e < Dn * Dn; e += blockDim.x) {
-    const double v = fabs(Ch[e]), a = (double)(e % Dn), b = (double)(e / Dn);
-    sa = fma(v, a * a, sa);
-    sb = fma(v, b * b, sb);
-  }
-  sa = wave_sum(sa);
-  sb = wave_sum(sb);
-  if (lane == 0) { red[wave][0] = sa; red[wave][1] = sb; }
-  __syncthreads();
-  if (tid == 0) {
-    sa = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-    sb = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-    slack[oc] = (sa * dxi0 + sb * dxi1) * (1.0 + 1e-9);
-  }
-}
-// the plan's own values at the guard band's probe points: raw[f][p] = sum over the degrees the kernels run of ChatT T_a(xi0) T_b(xi1),
-// a wave per (probe, coefficient set)
-__global__ __launch_bounds__(256) void k_gb_probe_series(const CandSpec cs, const InterpParams* __restrict__ P_, const double* __restrict__ ChatT_all,
-                                                         const int* __restrict__ eff, const double* __restrict__ xn0, const double* __restrict__ xn1,
-                                                         double* __restrict__ raw) {
-  const BlDims& dm = P_->dm;
-  const int f = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, D0 = dm.D0m;
-  const int p = blockIdx.x * 4 + wave;
-  if (p >= kGbProbes) return;
-  const int A = eff[4 * f] * 4, B = eff[4 * f + 2] * 16;
-  const double* Ch = ChatT_all + (size_t)f * D0 * dm.D1m;
-  long long x0, x1;
-  gb_probe_xy(cs, dm.nlines, p, x0, x1);
-  auto xi_of = [&](double xn, int axis) {
-    double xi = (2.0 * xn - (dm.a[axis] + dm.b[axis])) / (dm.b[axis] - dm.a[axis]);
-    xi = xi < 1.0 ? xi : 1.0;
-    return xi > -1.0 ? xi : -1.0;
-  };
-  const double xi0 = xi_of(xn0[x0], 0), xi1 = xi_of(xn1[x1], 1);
-  double sum = 0.0;
-  for (int b = lane; b < B; b += 64) {
-    double tb0 = 1.0, tb1 = xi1, tb = b == 0 ? 1.0 : xi1;
-    for (int k = 2; k <= b; ++k) { tb = 2.0 * xi1 * tb1 - tb0; tb0 = tb1; tb1 = tb; }
-    const double* rowp = Ch + (size_t)b * D0;
-    double row = 0.0, ta0 = 1.0, ta1 = xi0;
-    for (int a = 0; a < A; ++a) {
-      double ta = a == 0 ? 1.0 : xi0;
-      if (a >= 2) { ta = 2.0 * xi0 * ta1 - ta0; ta0 = ta1; ta1 = ta; }
-      row = fma(rowp[a], ta, row);
-    }
-    sum = fma(row, tb, sum);
-  }
-  sum = wave_sum(sum);
-  if (lane == 0) raw[(size_t)f * kGbProbes + p] = sum;
-}
-// K1i's band from its probes (as guard.hip's k_gb_band, with the mean's truncation tail and a MEASURED band of the Lipschitz
-// keys: the gradient sums are derivatives of an interpolant).  raw [4 q][P]; ref_g [q][2][P] the exact gradient components.
-__global__ __launch_bounds__(256) void k_gb_band_i(const InterpParams* __restrict__ P_, const double* __restrict__ raw, const double* __restrict__ ref_m,
-                                                   const double* __restrict__ ref_v, const double* __restrict__ ref_g,
-                                                   const double* __restrict__ tail /* [4 q] tails | [4 q] frames */, const double* __restrict__ alpha,
-                                                   int a_ld, GuardBand* gb, GuardBand* gb_mirror /* pinned host copy (sbo_profile_get) */) {
-  const ModelConst& mc = P_->mc;
-  __shared__ double sh[4][6];
-  __shared__ double sha[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int o = 0; o < mc.q; ++o) {
-    const double ys = mc.Y_std[o];
-    double e[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};          // |dm|, |dv|, |m|, |v|, |dg|, |g|
-    bool bad = false;
-    for (int p = tid; p < kGbProbes; p += blockDim.x) {
-      double var = mc.sf2[o] - raw[(size_t)(4 * o) * kGbProbes + p];
-      var = (var > 0.0 ? var : 0.0) * (ys * ys);
-      const double m = (mc.mp[o] + raw[(size_t)(4 * o + 1) * kGbProbes + p]) * ys + mc.Y_mean[o];
-      const double rm = ref_m[(size_t)o * kGbProbes + p], rv = ref_v[(size_t)o * kGbProbes + p];
-      const double dm_ = fabs(m - rm), dv_ = fabs(var - rv);
-      bad = bad || !(dm_ < kGbInf) || !(dv_ < kGbInf);
-      e[0] = fmax(e[0], dm_); e[1] = fmax(e[1], dv_); e[2] = fmax(e[2], fabs(rm)); e[3] = fmax(e[3], fabs(rv));
-      for (int a = 0; a < 2; ++a) {
-        const double g = ys * mc.inv_ell[o][a] * mc.X_rstd[a] * raw[(size_t)(4 * o + 2 + a) * kGbProbes + p];
-        const double rg = ref_g[((size_t)o * 2 + a) * kGbProbes + p];
-        bad = bad || !(fabs(g - rg) < kGbInf);
-        e[4] = fmax(e[4], fabs(g - rg));
-        e[5] = fmax(e[5], fabs(rg));
-      }
-    }
-    // (a probe whose deviation is not finite: fmax drops a NaN, so the flag joins the reduction itself -- every thread holds at most
-    // one of the 144 probes, and only lane 1's flag used to be published)
-    if (bad) e[0] = kGbInf;
-    double a1p = 0.0;                                         // ||alpha_o||_1 (the worst-case rounding of the mean's sum: the check below)
-    for (int j = tid; j < mc.n; j += blockDim.x) a1p += fabs(alpha[(size_t)o * a_ld + j]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) a1p += __shfl_xor(a1p, off);
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) e[k] = fmax(e[k], __shfl_xor(e[k], off));
-    __syncthreads();
-    if (lane == 0) {
-      for (int k = 0; k < 6; ++k) sh[wave][k] = e[k];
-      sha[wave] = a1p;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      for (int w = 1; w < 4; ++w)
-        for (int k = 0; k < 6; ++k) e[k] = fmax(e[k], sh[w][k]);
-      e[0] = fmax(e[0], sh[0][0]);
-      const double eps = 2.220446049250313e-16;
-      const bool inf = !(e[0] < kGbInf);
-      // analytic part (r05): the dropped coefficients of the series that is run (|T_a T_b| <= 1), and the interpolation error of the node
-      // fields -- at most twice the sum of the TRUE coefficients beyond the node count, which is extrapolated from the last four degrees
-      // held (kGbAliasFactor x their sum: twice a geometric continuation at a ratio <= 0.8 per degree; the posterior of an RBF kernel is
-      // entire, its coefficients decay faster than any such ratio once they decay at all)
-      const double* frame = tail + 4 * mc.q;
-      const double an_m = (tail[4 * o + 1] + kGbAliasFactor * frame[4 * o + 1]) * ys;
-      const double an_v = (tail[4 * o] + kGbAliasFactor * frame[4 * o]) * ys * ys;
-      const double fl_m = 64.0 * eps * fmax(e[2], fabs(mc.Y_mean[o]) + ys), fl_v = 64.0 * eps * fmax(e[3], mc.sf2[o] * ys * ys);
-      gb->an_m[o] = an_m; gb->an_v[o] = an_v; gb->pr_m[o] = e[0]; gb->pr_v[o] = e[1];
-      // ... plus the measured rounding level of the plan's sums; the check: a probe deviation that truncation + the worst-case rounding
-      // of the reference formula do not explain (GuardBand, device_common.hpp)
-      const double a1 = (sha[0] + sha[1]) + (sha[2] + sha[3]);
-      const bool distrust = e[0] > an_m + gb_round_mean(mc.n, mc.sf2[o], a1, ys) || e[1] > an_v + gb_round_var(mc.n, mc.sf2[o], mc.sn2[o], ys);
-      gb->dm[o] = (inf || distrust) ? kGbInf : an_m + kGbSafety * e[0] + fl_m;
-      gb->dv[o] = (inf || distrust) ? kGbInf : an_v + kGbSafety * e[1] + fl_v;
-      gb->rl[o] = (e[5] > 0.0 && !inf) ? 16.0 * e[4] / e[5] + 1e-9 : 1e-3;
-      if (gb_mirror) {
-        gb_mirror->dm[o] = gb->dm[o]; gb_mirror->dv[o] = gb->dv[o]; gb_mirror->rl[o] = gb->rl[o];
-        gb_mirror->an_m[o] = an_m; gb_mirror->an_v[o] = an_v; gb_mirror->pr_m[o] = e[0]; gb_mirror->pr_v[o] = e[1];
-      }
-    }
-    __syncthreads();
-  }
-}
-
-bool interp_applicable(const sbo_ctx* c) {
-  if (c->bilinear != 1 || c->is_shadow || !bilinear_applicable(c)) return false;
-  // (the node values come from the reference formula on the caller's matrix: the packed images sbo_model_set made of it)
-  // (a grid that arrived after the model: the images are packed on demand from the upload that still sits in the build workspace)
-  return c->mc.factor == SBO_FACTOR_INVK && c->chol_async && (c->invk_img_valid || c->invk_w_valid) && c->mc.npad % 16 == 0 &&
-         c->dtype == SBO_F64;
-}
-
-// Enqueues the plan for the current (model, grid) on the context's streams; nothing waits for the device.
-int interp_setup(sbo_ctx* c) {
-  InterpPlan& ip = c->bi;
-  ip.valid = true;
-  ip.usable = false;
-  ip.used = false;
-  ip.serial = c->model_serial;
-  const ModelConst& mc = c->mc;
-  const CandSpec& cs = c->cs;
-  const int n = mc.n, q = mc.q;
-  const long long cnt0 = cs.count[0], nlines = cs.n_local / cnt0, line0 = cs.first / cnt0;
-  double ab[4];
-  if (!basis_intervals(c, ab)) return SBO_OK;
-  // nodes per axis from the shortest length scale (tensor.hip's rule for its first two axes), one count for both
-  int Dn = 32;
-  for (int a = 0; a < 2; ++a) {
-    double tmax = 0.0;
-    for (int o = 0; o < q; ++o) tmax = std::max(tmax, (ab[2 * a + 1] - ab[2 * a]) * std::sqrt(mc.inv_ell[o][a]));
-    const double want = 7.6 * tmax;
-    const int need = want <= 32 ? 32 : (want <= 48 ? 48 : (want <= 64 ? 64 : 1 << 20));
-    Dn = std::max(Dn, need);
-  }
-  if (Dn > kIMaxDn || 2 * Dn > cnt0 || 2 * Dn > cs.count[1]) return SBO_OK;      // (not worth it / not resolvable: K1b's plan takes over)
-  const int QP = 4 * q;
-  if (QP > 4 * kMaxQ) return SBO_OK;
-  int rc;
-  if (!c->invk_img_valid && (rc = model_pack_invk(c))) return rc;
-  BlDims dm;
-  memset(&dm, 0, sizeof(dm));
-  const int KB = Dn / 16, KBn = mc.npad / 16, ncols = Dn * Dn, ncsR = ncols / 16;
-  const int ncs0 = (int)((cnt0 + 15) / 16), nrb = (int)((nlines + 15) / 16);
-  dm.q = QP; dm.n = n; dm.KBn = KBn; dm.ncsR = ncsR;
-  for (int o = 0; o < kMaxQ; ++o) { dm.r0[o] = Dn; dm.r1[o] = Dn; dm.rc0[o] = Dn; dm.rc1[o] = Dn; }
-  dm.r0u = dm.r1u = Dn; dm.KB0 = dm.KB1 = KB; dm.D0m = dm.D1m = Dn; dm.ncs0 = ncs0; dm.nrb = nrb; dm.cnt0 = cnt0; dm.nlines = nlines;
-  for (int a = 0; a < 2; ++a) { dm.a[a] = ab[2 * a]; dm.b[a] = ab[2 * a + 1]; }
-  InterpDims id;
-  id.Dn = Dn; id.q = q; id.n = n; id.npad = mc.npad; id.dpad = mc.dpad;
-  for (int a = 0; a < 2; ++a) { id.mid[a] = 0.5 * (ab[2 * a] + ab[2 * a + 1]); id.half[a] = 0.5 * (ab[2 * a + 1] - ab[2 * a]); }
-  ip.Dn = Dn; ip.KB = KB; ip.ncs0 = ncs0; ip.nrb = nrb;
-  ip.sT4f = (size_t)KB * KB * 256;
-  ip.sBtA = (size_t)nrb * KB * 256;
-  const size_t nP0f = (size_t)ncs0 * KB * 256, nP1A = (size_t)nrb * KB * 256, nZf = (size_t)ncsR * KBn * 256;
-  if ((rc = ensure(c->bl_P0f, sizeof(double) * nP0f))) return rc;
-  if ((rc = ensure(c->bl_P1A, sizeof(double) * nP1A))) return rc;
-  if ((rc = ensure(c->bl_T4f, sizeof(double) * ip.sT4f * QP))) return rc;
-  if ((rc = ensure(c->bl_BtA, sizeof(double) * ip.sBtA * QP))) return rc;
-  if ((rc = ensure(c->bl_small, sizeof(double) * ((size_t)cnt0 + (size_t)nlines)))) return rc;
-  // bl_work: E tables [2 q][kBlMaxR][n] | Zf | Cf | CtA (3 x q x nZf) | node fields [q][2][Dn^2]
-  const size_t nE = (size_t)2 * q * kBlMaxR * n;
-  if ((rc = ensure(c->bl_work, sizeof(double) * (nE + 3 * (size_t)q * nZf + (size_t)q * 2 * ncols)))) return rc;
-  // bl_cheb: ChatT [4 q][Dn^2] | eff (4 QP ints) + tails (QP doubles)
-  if ((rc = ensure(c->bl_cheb, sizeof(double) * ((size_t)QP * ncols + 4 * (size_t)QP + 16)))) return rc;
-  double* E = (double*)c->bl_work.p;
-  double* Zf = E + nE;
-  double* Cf = Zf + (size_t)q * nZf;
-  double* CtA = Cf + (size_t)q * nZf;
-  double* V = CtA + (size_t)q * nZf;
-  double* Chat = (double*)c->bl_cheb.p;
-  int* eff = (int*)(Chat + (size_t)QP * ncols);
-  double* dxn0 = (double*)c->bl_small.p;
-  double* dxn1 = dxn0 + cnt0;
-  const unsigned uq = (unsigned)q;
-  auto blocks = [&](size_t total, unsigned y) { return dim3((unsigned)std::min<size_t>((total + 255) / 256, 1u << 16), y); };
-  hipStream_t xs = c->stream, ys = c->stream2 ? c->stream2 : c->stream, zs = (ys != xs && c->stream3) ? c->stream3 : ys;
-  const bool band = c->guard_band != 0;
-  // buffers of the gate and of the probes (before the plan's signature is taken: it holds their addresses)
-  const int ntx = (ncs0 + 7) / 8, nty = (nrb + 3) / 4;
-  const size_t nt = (size_t)ntx * nty, head = (size_t)q * 2 * nt + 4 * (size_t)q;
-  const size_t nS0 = (size_t)q * Dn * cnt0, nVb = (size_t)q * 3 * Dn * nlines;
-  if ((rc = ensure(c->bl_grad, sizeof(double) * (head + nS0 + nVb)))) return rc;
-  if ((rc = ensure(c->gb_pts, sizeof(double) * ((size_t)QP * kGbProbes + 2 * (size_t)kGbProbes + 2 * (size_t)q * kGbProbes)))) return rc;
-  if ((rc = ensure(c->bi_params, sizeof(InterpParams)))) return rc;
-  if (!c->h_bi_params && hipHostMalloc(&c->h_bi_params, sizeof(InterpParams), hipHostMallocDefault) != hipSuccess)
-    return fail(SBO_E_NOMEM, "pinned staging of the plan's parameters");
-  double* gt = (double*)c->bl_grad.p;
-  double* slack = gt + (size_t)q * 2 * nt;
-  unsigned long long* gkey = (unsigned long long*)(slack + 2 * q);
-  double* S0i = (double*)(gkey + 2 * q);
-  double* Vbi = S0i + nS0;
-  double* raw = (double*)c->gb_pts.p;
-  double* ppts = raw + (size_t)QP * kGbProbes;
-  double* pgrad = ppts + 2 * (size_t)kGbProbes;
-  // ---- what changes with the model: one block, read by the plan's kernels from device memory
-  InterpParams hp;
-  memset(&hp, 0, sizeof(hp));
-  hp.mc = mc;
-  hp.id = id;
-  hp.dm = dm;
-  hp.dxi0 = cs.count[0] > 1 ? 0.5 * kGradStep * std::fabs(cs.step[0] / mc.X_std[0]) / id.half[0] : 0.0;
-  hp.dxi1 = cs.count[1] > 1 ? 0.5 * kGradStep * std::fabs(cs.step[1] / mc.X_std[1]) / id.half[1] : 0.0;
-  const InterpParams* dP = (const InterpParams*)c->bi_params.p;
-  const bool gate = std::isfinite(hp.dxi0) && std::isfinite(hp.dxi1);
-  ip.grad_S0 = S0i; ip.grad_Vb = Vbi; ip.grad_gt = gt; ip.grad_key = gkey;
-  ip.gtmax = gate ? gt : nullptr;
-  ip.gkey = gate ? gkey : nullptr;
-  // ---- the plan as a HIP graph.  Its ~20 launches on three streams take the host ~0.15 ms to enqueue -- more than the device needs for
-  // them on config B.  Launch arguments depend on the grid, on n and on addresses only (signature below); a model whose signature
-  // equals the previous one's replays the captured graph with its own parameter block: one hipGraphLaunch.  (The reference's loop grows
-  // n by one per iteration: there every plan is enqueued the plain way, at no extra cost -- a graph is captured only when a
-  // signature REPEATS.)
-  InterpSig sig;
-  memset(&sig, 0, sizeof(sig));
-  sig.cs = cs;
-  sig.Dn = Dn; sig.q = q; sig.n = n; sig.npad = mc.npad; sig.dpad = mc.dpad; sig.guard = c->guard_band; sig.a_ld = c->a_ld; sig.gate = gate ? 1 : 0;
-  sig.cheb_tol = c->cheb_tol;
-  {
-    const void* ptrs[] = {c->As.p, c->sqA.p, c->alpha.p, c->alpha64.p, c->Xn.p, c->invk_img.p, c->invk_plain, c->bl_P0f.p, c->bl_P1A.p, c->bl_T4f.p,
-                          c->bl_BtA.p, c->bl_small.p, c->bl_work.p, c->bl_cheb.p, c->bl_grad.p, c->gb_pts.p, c->gb_probe.p, c->gb_part.p, c->gb.p,
-                          c->bi_params.p, c->h_bi_params, (const void*)xs, (const void*)ys, (const void*)zs};
-    static_assert(sizeof(ptrs) / sizeof(ptrs[0]) <= sizeof(sig.ptr) / sizeof(sig.ptr[0]), "signature slots");
-    for (size_t i = 0; i < sizeof(ptrs) / sizeof(ptrs[0]); ++i) sig.ptr[i] = ptrs[i];
-  }
-  auto finish = [&]() {
-    if (band) c->gb_host_valid = false;
-    ip.eff = eff;
-    ip.band_ready = band;
-    ip.usable = true;
-    return SBO_OK;
-  };
-  const bool repeat = ip.sig_valid && !memcmp(&sig, &ip.sig, sizeof(sig));
-  // (the previous plan's copy of the block has normally run long ago -- a sweep has synchronised since --, but two model changes in
-  // a row must not let the first plan's copy read the second model's block)
-  if (c->ev_bi_params) SBO_HIP(hipEventSynchronize((hipEvent_t)c->ev_bi_params));
-  else {
-    hipEvent_t ev;
-    SBO_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    c->ev_bi_params = ev;
-  }
-  memcpy(c->h_bi_params, &hp, sizeof(hp));
-  if (repeat && ip.exec) {
-    SBO_HIP(hipGraphLaunch((hipGraphExec_t)ip.exec, xs));
-    SBO_HIP(hipEventRecord((hipEvent_t)c->ev_bi_params, xs));
-    return finish();
-  }
-  if (!repeat) {
-    if (ip.exec) { (void)hipGraphExecDestroy((hipGraphExec_t)ip.exec); ip.exec = nullptr; }
-    // (measured, ROCm 7.2: the replayed graph is SLOWER than the plain launches -- config B iteration 0.48 -> 0.91 ms, H 0.97 -> 1.38:
-    // the runtime walks the three branches as one chain with ~15 us between nodes.  Off unless SBO_PLAN_GRAPH=1.)
-    static const bool want_graph = getenv("SBO_PLAN_GRAPH") != nullptr;
-    ip.graph_ok = want_graph && ys != xs;
-  }
-  // (a captured plan joins all its branches at its end: the deferred gate is for the plain launches only)
-  const bool defer = gate && c->grad_defer && !ip.graph_ok && !(repeat && ip.exec) && zs != xs && zs != ys;
-  ip.grad_deferred = defer;
-  // (no gate at all -- the deferred launch runs both gradient phases on every tile -- where the grid is small enough for the gate's
-  // three launches to cost more than the phases they save: A/B r05, config B 0.419 -> 0.398 ms per iteration, config H 0.870 -> 0.920.
-  // grad_defer = 2: always; 3: never)
-  const bool nogate = defer && (c->grad_defer == 2 || (c->grad_defer == 1 && (long long)ntx * nty * q <= 4ll * c->n_cu));
-  if (nogate) { ip.gtmax = nullptr; ip.gkey = nullptr; }
-  auto enqueue = [&]() -> int {
-    SBO_HIP(hipMemcpyAsync(c->bi_params.p, c->h_bi_params, sizeof(InterpParams), hipMemcpyHostToDevice, xs));
-    if (ys != xs) {
-      SBO_HIP(hipEventRecord(c->ev[7], xs));               // (the model's arrays and the block are in place at this point of the main stream)
-      SBO_HIP(hipStreamWaitEvent(ys, c->ev[7], 0));
-      if (zs != ys) SBO_HIP(hipStreamWaitEvent(zs, c->ev[7], 0));
-    }
-    // (enqueue order: the plan is host-bound on the smaller grids -- Z's one long kernel first, then the head of X, then Y's one launch)
-    double *gref_m = nullptr, *gref_v = nullptr;
-    int rc2;
-    if (band) {
-      // Z: the guard band's references at the probe points -- the reference formula (guard.hip) and the exact gradient
-      if ((rc2 = guard_probe_reference(c, zs, &gref_m, &gref_v, &dP->mc))) return rc2;
-      if ((rc2 = guard_probe_gradients(c, zs, ppts, pgrad, &dP->mc))) return rc2;
-      if (zs != ys) SBO_HIP(hipEventRecord(c->ev_join[6], zs));
-    }
-    // X: node fields and their coefficients
-    hipLaunchKernelGGL(k_i_etab, blocks((size_t)Dn * n, 2 * uq), dim3(256), 0, xs, dP, (const double*)c->As.p, E);
-    hipLaunchKernelGGL(k_bl_zf, blocks(nZf, uq), dim3(256), 0, xs, dm, (const double*)E, nZf, Zf);
-    // (A/B r05: nine column strips per wave -- exactly one wave per SIMD on config H instead of 2.25 -- took 120 us against 93: the
-    // fragment loads of a lone wave are not hidden by anything)
-    hipLaunchKernelGGL((k_bgemm<4, 0, 1>), dim3((unsigned)((ncsR + 3) / 4), (unsigned)((KBn + 3) / 4), uq), dim3(256), 0, xs,
-                       (const double*)c->invk_img.p, (size_t)mc.npad * mc.npad, (const double*)Zf, nZf, KBn, KBn, ncsR, Cf, nZf, CtA, 0ll);
-    hipLaunchKernelGGL(k_i_nodevals, dim3((unsigned)ncsR, uq), dim3(64), 0, xs, KBn, n, (const double*)Zf, (const double*)Cf, nZf,
-                       (const double*)c->alpha64.p, c->a_ld, ncols, V);
-    {
-      const size_t lds = sizeof(double) * 3 * (size_t)Dn * (Dn + 1);
-      SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_i_dct), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(k_i_dct, dim3(2 * uq), dim3(1024), lds, xs, dP, (const double*)V, Chat);
-    }
-    // (deferred tail, r05: the fork of the gate's and the band's side chains rides on this kernel as its stop event -- a record of its own
-    // would be a bubble in the chain)
-    if (defer) hipExtLaunchKernelGGL(k_cheb_trunc, dim3((unsigned)QP), dim3(1024), 0, xs, nullptr, c->ev_grad[0], 0, dm, (const double*)Chat, c->cheb_tol, eff);
-    else hipLaunchKernelGGL(k_cheb_trunc, dim3((unsigned)QP), dim3(1024), 0, xs, dm, (const double*)Chat, c->cheb_tol, eff);
-    hipLaunchKernelGGL(k_cheb_t4f, blocks(ip.sT4f, (unsigned)QP), dim3(256), 0, xs, dm, (const double*)Chat, ip.sT4f, (double*)c->bl_T4f.p);
-    // ... and which tiles of k_bpost can hold the largest gradient component (the gate of K1b's gradient phases, fed from the series.
-    // A/B r04: without the gate -- 80 us of plan kernels against 45 us of gradient phases on every tile -- the iteration times are the
-    // same within the spread)
-    // (deferred gate, r05: these kernels are 80 us of small launches whose result only the Lipschitz keys need.  They run on stream3 --
-    // behind the guard reference there, beside the plan's tail and the posterior launches --, followed by a launch of the gradient
-    // phases alone on the tiles they name (launch_posterior_interp); the posterior launches carry none)
-    hipStream_t gs = defer ? zs : xs;
-    if (defer) SBO_HIP(hipStreamWaitEvent(gs, c->ev_grad[0], 0));
-    if (!nogate) hipLaunchKernelGGL(k_i_gradslack, dim3(2 * uq), dim3(256), 0, gs, dP, (const double*)Chat, slack);
-    // Y: the tables of the grid positions (one launch)
-    hipLaunchKernelGGL(k_i_tabs, dim3((unsigned)std::min<long long>(((long long)(ncs0 + nrb) * 16 + 255) / 256, 4096)), dim3(256), 0, ys, dP, cs, line0,
-                       dxn0, dxn1, (double*)c->bl_P0f.p, (double*)c->bl_P1A.p, S0i);
-    if (ys != xs) SBO_HIP(hipEventRecord(c->ev_join[3], ys));
-    if (ys != xs) SBO_HIP(hipStreamWaitEvent(xs, c->ev_join[3], 0));
-    // (X again, with the tables of Y: the lines' sums of the gradient series and the sums at the cell centres of every tile)
-    if (defer && ys != gs) SBO_HIP(hipStreamWaitEvent(gs, c->ev_join[3], 0));
-    if (gate && !nogate) {
-      switch (Dn) {
-        case 32: hipLaunchKernelGGL((k_i_rtab<32>), dim3((unsigned)((nlines + 255) / 256), uq, (unsigned)(Dn / 8)), dim3(256), 0, gs, dP, (const double*)Chat, (const int*)eff, (const double*)dxn1, Vbi); break;
-        case 48: hipLaunchKernelGGL((k_i_rtab<48>), dim3((unsigned)((nlines + 255) / 256), uq, (unsigned)(Dn / 8)), dim3(256), 0, gs, dP, (const double*)Chat, (const int*)eff, (const double*)dxn1, Vbi); break;
-        default: hipLaunchKernelGGL((k_i_rtab<64>), dim3((unsigned)((nlines + 255) / 256), uq, (unsigned)(Dn / 8)), dim3(256), 0, gs, dP, (const double*)Chat, (const int*)eff, (const double*)dxn1, Vbi); break;
-      }
-      hipLaunchKernelGGL(k_bl_gradcoarse, dim3((unsigned)(ntx * nty), uq), dim3(128), 0, gs, dm, (const double*)S0i, (const double*)Vbi,
-                         (const double*)dxn0, (const double*)dxn1, ntx, gt, gkey);
-      hipLaunchKernelGGL(k_bl_gradmax, dim3(2 * uq), dim3(256), 0, gs, (const double*)gt, ntx * nty, gkey);
-    }
-    if (band) {
-      // (deferred: the plan's own values at the probes and the band from them on Y -- idle since its tables -- beside the series' fragments
-      // and stage 1; the posterior launch, whose classification reads the band, waits for ev_grad[3]: launch_posterior_interp)
-      hipStream_t bs = defer ? ys : xs;
-      if (defer) SBO_HIP(hipStreamWaitEvent(bs, c->ev_grad[0], 0));
-      if (zs != ys) SBO_HIP(hipStreamWaitEvent(bs, c->ev_join[6], 0));
-      hipLaunchKernelGGL(k_gb_probe_series, dim3((unsigned)((kGbProbes + 3) / 4), (unsigned)QP), dim3(256), 0, bs, cs, dP, (const double*)Chat,
-                         (const int*)eff, (const double*)dxn0, (const double*)dxn1, raw);
-      hipLaunchKernelGGL(k_gb_band_i, dim3(1), dim3(256), 0, bs, dP, (const double*)raw, (const double*)gref_m, (const double*)gref_v,
-                         (const double*)pgrad, reinterpret_cast<const double*>(eff + 4 * QP), (const double*)c->alpha64.p, c->a_ld, (GuardBand*)c->gb.p,
-                         (GuardBand*)(c->h_back + kGbMirrorOffset));
-      c->gb_mirrored = true;
-      if (defer) SBO_HIP(hipEventRecord(c->ev_grad[3], bs));
-    }
-    SBO_HIP(hipGetLastError());
-    return SBO_OK;
-  };
-  // the second model of this signature: capture what the first one enqueued the plain way (every buffer is allocated by now), then
-  // replay.  Anything the runtime refuses in a capture switches the graph off for this signature, and the plan goes out the plain way.
-  const bool reference_ok = !band || guard_reference_is_direct(c);
-  if (repeat && ip.graph_ok && reference_ok && c->invk_img_valid) {
-    hipGraph_t g = nullptr;
-    bool ok = hipStreamBeginCapture(xs, hipStreamCaptureModeThreadLocal) == hipSuccess;
-    if (ok) {
-      const int rce = enqueue();
-      const hipError_t ee = hipStreamEndCapture(xs, &g);
-      ok = rce == SBO_OK && ee == hipSuccess && g != nullptr;
-    }
-    hipGraphExec_t ex = nullptr;
-    if (ok) ok = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess && ex != nullptr;
-    if (g) (void)hipGraphDestroy(g);
-    if (ok) {
-      ip.exec = ex;
-      SBO_HIP(hipGraphLaunch(ex, xs));
-      SBO_HIP(hipEventRecord((hipEvent_t)c->ev_bi_params, xs));
-      return finish();
-    }
-    (void)hipGetLastError();
-    ip.graph_ok = false;
-  }
-  ip.sig = sig;
-  ip.sig_valid = true;
-  if ((rc = enqueue())) return rc;
-  SBO_HIP(hipEventRecord((hipEvent_t)c->ev_bi_params, xs));
-  return finish();
-}
-
-// Column path (r05): can this launch deliver the classification as column words?  One constraint, fp64 grid of whole 64 x 128
-// tiles (every workgroup's tile inside the grid), at most 64 segments (Usum is one word per column); the sweep asked for it.
-static bool col_words_ok(const sbo_ctx* c, long long cnt0, long long nlines) {
-  if (!c->col_request || !c->col_path) return false;
-  const bool shape = c->mc.q == 2 && c->cs.kind == 1 && c->cs.d == 2 && c->cs.first == 0 && cnt0 % 128 == 0 && nlines % 64 == 0 &&
-                     nlines / 64 <= 64 && nlines >= 64 && cnt0 >= 128 && cnt0 <= 4096 && c->world == 1 && !c->comm_selftest;
-  // (auto: from four tiles per CU and output on -- config H.  Below that the two launches per sweep cost more than the column
-  // kernels save: config B, 512 tiles per output, 0.171 ms against 0.162 with the byte masks.  Option col_path = 2: whenever the shape fits.)
-  const long long tiles = (cnt0 / 128) * (nlines / 64);
-  return shape && (c->col_path == 2 || tiles >= 4ll * c->n_cu);
-}
-static int col_words_prepare(sbo_ctx* c, long long cnt0, long long nlines, ColBits* cb) {
-  const size_t words = (size_t)(nlines / 64) * (size_t)cnt0;
-  int rc;
-  if ((rc = ensure(c->cbS, 8 * words)) || (rc = ensure(c->cbU, 8 * words)) || (rc = ensure(c->cbM, 8 * words)) || (rc = ensure(c->cbG, 8 * words))) return rc;
-  const bool fresh = c->cbUsum.bytes < 8 * (size_t)cnt0;
-  if ((rc = ensure(c->cbUsum, 8 * (size_t)cnt0))) return rc;
-  if (fresh || c->usum_dirty) SBO_HIP(hipMemsetAsync(c->cbUsum.p, 0, c->cbUsum.bytes, c->stream));
-  c->usum_dirty = true;       // (until the column path's second kernel has cleared it again)
-  const size_t sbytes = sizeof(unsigned long long) * kColSlotFields * kColSlots;
-  if (c->col_slots.bytes < sbytes) c->slots_clean = false;
-  if ((rc = ensure(c->col_slots, sbytes))) return rc;
-  if (!c->slots_clean) {
-    unsigned long long init[kColSlotFields * kColSlots];
-    for (int f = 0; f < kColSlotFields; ++f)
-      for (int k = 0; k < kColSlots; ++k) init[f * kColSlots + k] = col_slot_is_min(f) ? ~0ull : 0ull;
-    SBO_HIP(hipMemcpyAsync(c->col_slots.p, init, sbytes, hipMemcpyHostToDevice, c->stream));
-    SBO_HIP(hipStreamSynchronize(c->stream));           // (first use, or after a failed sweep: `init` is on this stack)
-  }
-  c->slots_clean = false;     // (until the sweep's finals have reset the block)
-  cb->Sw = (unsigned long long*)c->cbS.p;
-  cb->Uw = (unsigned long long*)c->cbU.p;
-  cb->Usum = (unsigned long long*)c->cbUsum.p;
-  cb->slots = (unsigned long long*)c->col_slots.p;
-  return SBO_OK;
-}
-
-int launch_posterior_interp(sbo_ctx* c) {
-  InterpPlan& ip = c->bi;
-  const ModelConst& mc = c->mc;
-  const CandSpec& cs = c->cs;
-  const int q = mc.q, QP = 4 * q, KB = ip.KB;
-  const long long cnt0 = cs.count[0], nlines = cs.n_local / cnt0;
-  ip.used = true;
-  constexpr int S1 = 3;
-  const unsigned gx = (unsigned)((ip.ncs0 + 7) / 8), gy = (unsigned)((ip.nrb + 3) / 4);
-  const unsigned rows_out = gx * gy;
-  const size_t lds = sizeof(double) * 2 * 3072 + 2048;
-  int rc;
-  // (deferred gate: the posterior launches write their -- empty -- Lipschitz rows behind the real ones, which the gradient launch fills)
-  const bool defer = ip.grad_deferred && c->stream3 != nullptr;
-  if ((rc = ensure(c->bl_lpart, sizeof(double) * (size_t)rows_out * q * 2))) return rc;
-  const bool fuse_wanted = c->fuse_request == 1 || (c->fuse_request == 2 && ((long long)gx * gy * q >= 4ll * c->n_cu || q > 2));   // (several constraints: the separate pass costs more than one constraint's)
-  bool fuse = fuse_wanted && q >= 2 && c->maskS.p && c->maskU.p && c->maskS.bytes >= (size_t)cs.n_local && c->maskU.bytes >= (size_t)cs.n_local &&
-              (q == 2 || (c->fuseS.bytes >= (size_t)cs.n_local * (q - 1) && c->fuseU.bytes >= (size_t)cs.n_local * (q - 1)));
-  const bool colw = fuse && col_words_ok(c, cnt0, nlines);
-  PostExtra px;
-  memset(&px, 0, sizeof(px));
-  px.q = q;
-  c->col_active = false;
-  c->fuse_rows = 0;
-  if (fuse) {
-    c->fuse_rows = (int)rows_out * (colw ? 2 : (q - 1));
-    px.fstride = q > 2 ? (long long)cs.n_local : 0ll;
-    if ((rc = ensure(c->cpart, sizeof(unsigned long long) * kFuseRow * ((size_t)c->fuse_rows + 4 * (size_t)c->n_cu + 64)))) return rc;
-    c->cpart_cap = (int)(c->cpart.bytes / (sizeof(unsigned long long) * kFuseRow));
-  }
-  if (colw) {
-    if ((rc = col_words_prepare(c, cnt0, nlines, &px.cb))) return rc;
-    px.lean = c->col_lean;
-    c->col_active = true;
-    c->col_forked = true;
-    fuse = false;                      // (no byte masks: the words are the classification)
-  }
-  const GuardBand* gb_fused = (c->guard_band && ip.band_ready && c->gb.p) ? (const GuardBand*)c->gb.p : nullptr;
-  // stage 1 (behind col_words_prepare: the gradient launch, which follows this kernel on another stream, merges into the slot block)
-  if (defer)
-    hipExtLaunchKernelGGL((k_bstage1<S1>), dim3((unsigned)((KB + S1 - 1) / S1), (unsigned)((ip.nrb + 3) / 4), (unsigned)QP), dim3(256), 0, c->stream, nullptr,
-                          c->ev_grad[1], 0, (const double*)c->bl_P1A.p, (size_t)0, (const double*)c->bl_T4f.p, ip.sT4f, KB, ip.nrb, KB,
-                          (double*)c->bl_BtA.p, ip.sBtA, (const int*)ip.eff);
-  else
-    hipLaunchKernelGGL((k_bstage1<S1>), dim3((unsigned)((KB + S1 - 1) / S1), (unsigned)((ip.nrb + 3) / 4), (unsigned)QP), dim3(256), 0, c->stream,
-                       (const double*)c->bl_P1A.p, (size_t)0, (const double*)c->bl_T4f.p, ip.sT4f, KB, ip.nrb, KB, (double*)c->bl_BtA.p, ip.sBtA,
-                       (const int*)ip.eff);
-  if (defer && ip.band_ready) SBO_HIP(hipStreamWaitEvent(c->stream, c->ev_grad[3], 0));     // (the band: written on Y beside stage 1)
-  SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bpost<1, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bpost<1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bpost<1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const double* BtA = (const double*)c->bl_BtA.p;
-  double* const lrows = (double*)c->bl_lpart.p;
-  if (defer) {
-    // the gradient phases alone, behind the gate on stream3 and behind stage 1 (its images): one launch for all outputs
-    hipStream_t gs = c->stream3;
-    SBO_HIP(hipStreamWaitEvent(gs, c->ev_grad[1], 0));
-    SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bgrad), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_bgrad, dim3((unsigned)std::min<long long>((long long)rows_out, 2ll * c->n_cu)), dim3(256), lds, gs, mc, cs, BtA + ip.sBtA,
-                       4 * ip.sBtA, (const double*)c->bl_P0f.p, KB, ip.nrb, ip.ncs0, nlines, (int)gx, (int)gy, (const int*)ip.eff, ip.gtmax, ip.gkey,
-                       (const double*)c->bl_small.p, q, lrows, colw ? px.cb.slots : (unsigned long long*)nullptr, (c->sweep_lean && q >= 2) ? 1 : 0);
-    SBO_HIP(hipEventRecord(c->ev_grad[2], gs));
-    c->grad_pending = true;
-    px.nograd = 1;
-  }
-  // (column path: the constraint's launch first -- the objective's tiles read its words and its counts of safe candidates per tile)
-  for (int part = 0; part < (colw ? 2 : 1); ++part) {
-    px.o0 = colw ? 1 - part : 0;
-    const bool last = !colw || part == 1;
-    auto kpost = !colw ? k_bpost<1, 0> : (part == 0 ? k_bpost<1, 1> : k_bpost<1, 2>);
-    // (the constraint's launch carries the fork event of the overlapped sweep: the expander chain starts behind it on stream3
-    // while the objective's launch runs here)
-    hipExtLaunchKernelGGL(kpost, dim3(gx, gy, (unsigned)(colw ? 1 : q)), dim3(256), lds, c->stream, nullptr,
-                          (c->lmax_defer && last) ? c->ev[1] : ((colw && part == 0) ? c->ev_col[0] : nullptr), 0, mc, cs, BtA,
-                          4 * ip.sBtA, (const double*)c->bl_P0f.p, (size_t)0, BtA + ip.sBtA, 4 * ip.sBtA, (const double*)c->bl_P0f.p, (size_t)0, KB,
-                          KB * 4, KB, KB * 4, KB, ip.nrb, ip.ncs0, nlines, (double*)c->mean.p, (double*)c->var.p,
-                          defer ? lrows + (size_t)rows_out * q : lrows,
-                          (const double*)c->bl_small.p /* xn0 */, fuse ? (uint8_t*)(q > 2 ? c->fuseS.p : c->maskS.p) : (uint8_t*)nullptr,
-                          fuse ? (uint8_t*)(q > 2 ? c->fuseU.p : c->maskU.p) : (uint8_t*)nullptr, c->fuse_b, (unsigned long long*)c->cpart.p, c->cpart_cap, gb_fused,
-                          (const int*)ip.eff, ip.gtmax, ip.gkey, 1, px);
-  }
-  // (whoever merges the Lipschitz rows on this stream -- the reduction below, a sweep's first small kernel -- waits for the gradient launch;
-  // the column path reads the keys from the slot block on stream3 itself, in stream order behind that launch: sets_colpath.inc.hpp)
-  if (defer && !colw) {
-    SBO_HIP(hipStreamWaitEvent(c->stream, c->ev_grad[2], 0));
-    c->grad_pending = false;
-  }
-  if (c->lmax_defer) {
-    c->lmax_pending = true;
-    c->lmax_per_out = (int)rows_out;
-  } else {
-    hipExtLaunchKernelGGL(k_lmax_reduce, dim3((unsigned)q), dim3(256), 0, c->stream, nullptr, c->ev[1], 0, (const double*)c->bl_lpart.p,
-                          (int)rows_out, (unsigned long long*)c->Lmax.p);
-  }
-  c->k1_stop_attached = true;
-  c->gb_active = c->guard_band && ip.band_ready;
-  // flops issued: stage 1 of four coefficient sets per output + four full phases of stage 2 (an upper bound: the counts the kernels
-  // run to stay on the device -- a read-back per plan is a launch the host-bound plan does not need)
-  const double tiles2 = (double)ip.nrb * ip.ncs0;
-  c->last_k1_flops = (double)q * 2.0 * 1024.0 * 4.0 * (4.0 * (double)ip.nrb * KB * KB + tiles2 * KB * 4);
-  SBO_HIP(hipGetLastError());
-  return SBO_OK;
-}
-
-int launch_posterior_bilinear(sbo_ctx* c) {
-  const BilinearPlan& pl = c->bl;
-  const ModelConst& mc = c->mc;
-  const CandSpec& cs = c->cs;
-  const int q = mc.q;
-  const long long cnt0 = cs.count[0], nlines = cs.n_local / cnt0, line0 = cs.first / cnt0;
-  // stage 1: Bt = P1^T T4qq^T, written as the packed A operand of stage 2 (three strips per workgroup measured best on
-  // config B: 27.7 us against 28.8 with two and 31.3 with four; the per-wave k_bgemm<2, 0, 0> took 32.6)
-  constexpr int S1 = 3;
-  hipLaunchKernelGGL((k_bstage1<S1>), dim3((unsigned)((pl.KB0 + S1 - 1) / S1), (unsigned)((pl.nrb + 3) / 4), (unsigned)q), dim3(256), 0,
-                     c->stream, (const double*)c->bl_P1A.p, pl.sP1A, (const double*)c->bl_T4f.p, pl.sT4f, pl.KB1, pl.nrb, pl.KB0,
-                     (double*)c->bl_BtA.p, pl.sBtA, (const int*)pl.eff);
-  // stage 2 (fused): variance, mean, Lipschitz keys.  64 x 128 tiles (k_bpost<1>, three workgroups per CU): with the Chebyshev
-  // core the variance phase is ~12 k-steps and no longer dominates, and the third workgroup per CU is worth more than the
-  // B-fragment reuse of a 128 x 128 tile (r03: config B 0.204 -> 0.189 ms per sweep, H 0.547 -> 0.543)
-  const unsigned gx = (unsigned)((pl.ncs0 + 7) / 8);
-  constexpr int rbw = 1;
-  const size_t lds = sizeof(double) * 2 * 3072 + 2048;
-  const unsigned gy = (unsigned)((pl.nrb + 4 * rbw - 1) / (4 * rbw));
-  const unsigned rows_out = gx * gy;                      // partial rows per output: one per workgroup
-  int rc;
-  if ((rc = ensure(c->bl_lpart, sizeof(double) * (size_t)rows_out * q))) return rc;
-  // a sweep may ask for the S / U bytes, |S|, |U| and the radius key straight from the mean epilogue of the constraint
-  // (one-constraint models; the masks are allocated by the sweep before it enqueues the posterior)
-  // (r03: with the sqrt-free sign tests the fused epilogue saves the separate pass 76 us on config H and costs the GEMM 36;
-  // on config B, two workgroups per CU, the two cancel -- "auto" asks for at least four workgroups per CU)
-  const bool fuse_wanted = c->fuse_request == 1 || (c->fuse_request == 2 && ((long long)gx * gy * q >= 4ll * c->n_cu || q > 2));   // (several constraints: the separate pass costs more than one constraint's)
-  bool fuse = fuse_wanted && q >= 2 && c->maskS.p && c->maskU.p && c->maskS.bytes >= (size_t)cs.n_local &&
-              c->maskU.bytes >= (size_t)cs.n_local &&
-              (q == 2 || (c->fuseS.bytes >= (size_t)cs.n_local * (q - 1) && c->fuseU.bytes >= (size_t)cs.n_local * (q - 1)));
-  const bool colw = fuse && col_words_ok(c, cnt0, nlines);
-  PostExtra px;
-  memset(&px, 0, sizeof(px));
-  px.q = q;
-  c->col_active = false;
-  c->fuse_rows = 0;
-  if (fuse) {
-    c->fuse_rows = (int)rows_out * (colw ? 2 : (q - 1));
-    px.fstride = q > 2 ? (long long)cs.n_local : 0ll;
-    // (room behind the rows for the partials of the objective pass, see sweep_common_front)
-    if ((rc = ensure(c->cpart, sizeof(unsigned long long) * kFuseRow * ((size_t)c->fuse_rows + 4 * (size_t)c->n_cu + 64)))) return rc;
-    c->cpart_cap = (int)(c->cpart.bytes / (sizeof(unsigned long long) * kFuseRow));
-  }
-  bool record_encl = false;
-  double* encl = nullptr;
-  uint8_t* sched_cls = nullptr;
-  unsigned int *sched_l1 = nullptr, *sched_l2 = nullptr;
-  if (colw) {
-    if ((rc = col_words_prepare(c, cnt0, nlines, &px.cb))) return rc;
-    px.lean = c->col_lean;
-    c->col_active = true;
-    c->col_forked = true;
-    fuse = false;                      // (no byte masks: the words are the classification)
-    // r06: the constraint's enclosures per 8 x 8 cell (per plan) and a skip byte per tile (per sweep); a lean-2 sweep hands them to
-    // the constraint's launch once the plan's first launch has recorded them
-    const size_t ntiles = (size_t)gx * gy, ebytes = sizeof(double) * 4 * 128 * ntiles;
-    const void* was = c->bl_encl.p;
-    if ((rc = ensure(c->bl_encl, ebytes + ntiles))) return rc;
-    if (c->bl_encl.p != was) c->bl.encl_ready = false;
-    encl = (double*)c->bl_encl.p;
-    record_encl = !c->bl.encl_ready;
-    c->k1_encl_tiles = ntiles;
-    c->k1_encl_check = !record_encl;
-    if (!record_encl && c->col_lean >= 2) {
-      px.encl = encl;
-      px.skip = (uint8_t*)c->bl_encl.p + ebytes;
-      c->k1_skip_armed = true;
-    }
-    // r07: lean 2 -- the objective's launch over the tiles with a safe candidate, and, once the enclosures decide skips, the
-    // constraint's over the tiles that need a workgroup (k_bl_sched_tiles1 and on).  [class bytes][list 1][list 2]
-    if (c->k1_sched && c->col_lean >= 2) {
-      if ((rc = ensure(c->bl_sched, ((ntiles + 15) & ~(size_t)15) + 2 * sizeof(unsigned int) * (ntiles + 1)))) return rc;
-      sched_cls = (uint8_t*)c->bl_sched.p;
-      sched_l1 = (unsigned int*)(sched_cls + ((ntiles + 15) & ~(size_t)15));
-      sched_l2 = sched_l1 + ntiles + 1;
-    }
-  }
-  // (the fused classification counts its sign tests inside the plan's guard band)
-  const GuardBand* gb_fused = (c->guard_band && !c->is_shadow && c->bl.band_ready && c->gb.p) ? (const GuardBand*)c->gb.p : nullptr;
-  SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bpost<rbw, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bpost<rbw, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bpost<rbw, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  // the K1 stop event rides on the last launch (hipExtLaunchKernel): a separate hipEventRecord behind it is a barrier packet
-  // the next kernel waits ~6 us for.  A sweep merges the Lipschitz partials in its own first small kernel (lmax_defer).
-  // (column path: the constraint's launch first -- the objective's tiles read its words and its counts of safe candidates per tile)
-  for (int part = 0; part < (colw ? 2 : 1); ++part) {
-    px.o0 = colw ? 1 - part : 0;
-    const bool last = !colw || part == 1;
-    auto kpost = !colw ? k_bpost<rbw, 0> : (part == 0 ? k_bpost<rbw, 1> : k_bpost<rbw, 2>);
-    // r07: the tile lists (k_bl_sched_tiles1 / _list1 / _list2), built on this stream right in front of the launch that reads them
-    px.tlist = nullptr;
-    if (sched_l1 && part == 0 && px.encl) {
-      hipLaunchKernelGGL(k_bl_sched_tiles1, dim3((gx * gy + 3) / 4), dim3(256), 0, c->stream, mc, (const double*)px.encl, (int)(gx * gy), (int)gx,
-                         (int)gy, (unsigned int)cnt0, c->fuse_b, gb_fused, pl.gtmax, pl.gkey, q, px.skip, sched_cls, px.cb.Sw, px.cb.Uw,
-                         (double*)c->bl_lpart.p, (unsigned long long*)c->cpart.p, c->cpart_cap);
-      hipLaunchKernelGGL(k_bl_sched_list1, dim3(1), dim3(1024), 0, c->stream, (const uint8_t*)sched_cls, (int)(gx * gy), (int)gx,
-                         (const double*)c->bl_lpart.p + (size_t)rows_out, sched_l1, px.cb.Usum, px.cb.slots);
-      px.tlist = sched_l1;
-    }
-    if (sched_l2 && part == 1) {
-      hipLaunchKernelGGL(k_bl_sched_list2, dim3(1), dim3(1024), 0, c->stream, (unsigned long long*)c->cpart.p, c->cpart_cap, (int)(gx * gy), sched_l2,
-                         (double*)c->bl_lpart.p);
-      px.tlist = sched_l2;
-    }
-    px.tgx = (int)gx;
-    px.tgy = (int)gy;
-    const dim3 grid = px.tlist ? dim3(gx * gy) : dim3(gx, gy, (unsigned)(colw ? 1 : q));
-    hipExtLaunchKernelGGL(kpost, grid, dim3(256), lds, c->stream, nullptr,
-                          (c->lmax_defer && last) ? c->ev[1] : ((colw && part == 0) ? c->ev_col[0] : nullptr), 0,
-                          mc, cs, (const double*)c->bl_BtA.p, pl.sBtA, (const double*)c->bl_P0f.p, pl.sP0f, (const double*)c->bl_VA.p,
-                          pl.sVA, (const double*)c->bl_SBf.p, pl.sSBf, pl.KB0, pl.KS0, pl.KBm, pl.KSm, pl.KBm2, pl.nrb, pl.ncs0, nlines,
-                          (double*)c->mean.p, (double*)c->var.p, (double*)c->bl_lpart.p, (const double*)c->bl_small.p /* xn0 */,
-                          fuse ? (uint8_t*)(q > 2 ? c->fuseS.p : c->maskS.p) : (uint8_t*)nullptr, fuse ? (uint8_t*)(q > 2 ? c->fuseU.p : c->maskU.p) : (uint8_t*)nullptr, c->fuse_b,
-                          (unsigned long long*)c->cpart.p, c->cpart_cap, gb_fused, (const int*)pl.eff, pl.gtmax, pl.gkey, 0, px);
-    if (colw && part == 0 && record_encl) {
-      // (the plan's first constraint launch evaluated and stored every tile: its enclosures, ~270 MB read once per plan)
-      hipLaunchKernelGGL(k_bl_enclose, dim3(gx, gy), dim3(128), 0, c->stream, (const double*)c->mean.p + (size_t)cs.n_local,
-                         (const double*)c->var.p + (size_t)cs.n_local, cnt0, encl);
-      c->bl.encl_ready = true;
-    }
-  }
-  if (c->lmax_defer) {
-    c->lmax_pending = true;
-    c->lmax_per_out = (int)rows_out;
-  } else {
-    hipExtLaunchKernelGGL(k_lmax_reduce, dim3((unsigned)q), dim3(256), 0, c->stream, nullptr, c->ev[1], 0, (const double*)c->bl_lpart.p,
-                          (int)rows_out, (unsigned long long*)c->Lmax.p);
-  }
-  c->k1_stop_attached = true;
-  (void)line0;
-  c->gb_active = c->guard_band && !c->is_shadow && c->bl.band_ready;     // (the band came with the plan: bilinear_setup)
-  // flops issued on the matrix cores: stage 1 + the four phases of stage 2 (KS0 + 3 KSm k-steps: the axis-0 gradient phase
-  // runs on the mean phase's sums; 16 x 16 x 4 steps, 2 flops per multiply-add)
-  const double tiles2 = (double)pl.nrb * pl.ncs0, tiles1 = (double)pl.nrb * pl.KB0;
-  c->last_k1_flops = (double)q * 2.0 * 1024.0 * (4.0 * tiles1 * pl.KB1 + tiles2 * (pl.KS0 + 3 * pl.KSm));
-  if (pl.eff) {
-    // Chebyshev core: the counts the kernels actually run to (k_cheb_trunc; copied to the pinned block when the plan was built --
-    // they have arrived long before a sweep's result is read: a plan build is followed by the sweep's own synchronisation
-    // before anyone asks for the profile).  Until then the upper bound above stands.
-    const int* he = (const int*)(c->h_back + 5376);
-    double f = 0.0;
-    bool ok = true;
-    for (int o = 0; o < q; ++o) {
-      const int ks = he[4 * o], kb0 = he[4 * o + 1], kb1 = he[4 * o + 2];
-      if (ks < 1 || ks > pl.KS0 || kb0 < 1 || kb0 > pl.KB0 || kb1 < 1 || kb1 > pl.KB1) { ok = false; break; }
-      // (the gradient phases run on the few tiles that can hold the maximum: not counted)
-      f += 2.0 * 1024.0 * (4.0 * (double)pl.nrb * kb0 * kb1 + tiles2 * (ks + (pl.gtmax ? 1 : 3) * pl.KSm));
-    }
-    if (ok) c->last_k1_flops = f;
-  }
-  SBO_HIP(hipGetLastError());
-  return SBO_OK;
-}
+#include "bilinear_interp.inc.hpp"
 
 }  // namespace sbo

@@ -48,7 +48,7 @@ __device__ __forceinline__ long long block_sum_i64(long long v) {        // vali
 // as a partial; k_ref_finish sums the chunks.  pts == nullptr: the candidates are K1b's probe points (gb_probe_index).
 template <int D>
 __global__ __launch_bounds__(256) void k_ref_list(const ModelConst mc_val, const ModelConst* __restrict__ mcp /* non-null: the model's constants in
-                                                  device memory (a plan replayed as a HIP graph: bilinear.hip) */, const CandSpec cs, const double* __restrict__ pts, long long N,
+                                                  device memory (K1i's parameter block: bilinear.hip) */, const CandSpec cs, const double* __restrict__ pts, long long N,
                                                   long long nlines, const double* __restrict__ As, const double* __restrict__ sqA,
                                                   const double* __restrict__ alpha, int ald, const double* __restrict__ Mx, size_t mstride,
                                                   int ccols, double* __restrict__ part /* [chunks][2][q][N] */) {
@@ -417,7 +417,6 @@ int guard_band_host(sbo_ctx* c, const double* dm, const double* dv, const double
 // axis tables are made on, beside the GEMM chain of the Chebyshev core -- and, once K1b's own values at the probes are there
 // (pm / pv, bilinear.hip), the band from the deviations.  Everything on the device, in stream order: nothing waits for the host,
 // and the band is in place before the plan's first posterior launch (whose fused classification reads it).
-bool guard_reference_is_direct(const sbo_ctx* c) { return ref_direct(c); }
 int guard_probe_reference(sbo_ctx* c, hipStream_t side, double** ref_m, double** ref_v, const ModelConst* mcp) {
   const int q = c->mc.q;
   const long long nlines = c->cs.n_local / c->cs.count[0];

@@ -85,22 +85,34 @@ struct PostExtra {
   int tgx, tgy;  // the tile grid (tiles per row, tile rows) behind the list
 };
 
+// The operands of the GEMM posterior -- stage 1 (k_bstage1) and k_bpost -- as the plan that made them lays them out (K1b:
+// bilinear_setup, K1i: interp_setup); launch_posterior_gemm launches on them.  Device pointers and per-output strides in elements.
+// (The pointers are taken when the plan is built.  Only the two plan builders resize the bl_* buffers, and neither runs while the
+// other's plan can still be launched: K1i's is built only while K1b's is invalid, K1b's only once K1i's is used or unusable.)
+struct GemmOps {
+  int sets = 1;          // stage 1: coefficient sets per output (grid z = sets q)
+  int KB1 = 0;           // stage 1: k-blocks (the 16-blocks of axis 1)
+  size_t sP1A = 0, sT4f = 0, sBt1 = 0;   // stage 1: per-set strides of its A operand (P1A), of T4f and of its output (BtA)
+  double *BtA = nullptr, *P0f = nullptr, *VA = nullptr, *SBf = nullptr;
+  size_t sBtA = 0, sP0f = 0, sVA = 0, sSBf = 0;
+  int KB0 = 0, KS0 = 0, KBm = 0, KSm = 0, KBm2 = 0;   // k-blocks / k-steps of the variance phase; of the mean phases
+  int ncs0 = 0, nrb = 0;   // 16-column strips of axis 0, 16-row blocks of the local lines
+  int* eff = nullptr;    // device: the counts the kernels run to (k_cheb_trunc), followed by the truncation tails
+  const double* gtmax = nullptr;              // device: largest gradient samples per k_bpost tile + slacks (k_bl_gradcoarse), or none
+  const unsigned long long* gkey = nullptr;   // device: the grid's largest gradient samples
+  bool band_ready = false;   // the guard band of this plan has been measured
+  int imode = 0;         // k_bpost's K1i mode: four coefficient sets per output, the k-steps of every phase from eff
+};
+
 // K1b (bilinear.hip): device tables of the reduced-basis posterior on a 2-D grid, valid for one (model, candidates) pair
 struct BilinearPlan {
   bool valid = false;    // built (or found unusable) for the current model and candidates
   bool usable = false;   // the bases qualified: the posterior runs as two GEMMs
-  int KB0 = 0, KB1 = 0;  // 16-blocks of the pair indices of axis 0 / axis 1
-  int r0u = 0, ncs0 = 0, nrb = 0;
-  int KS0 = 0, KBm = 0, KSm = 0, KBm2 = 0;   // k-steps of the variance phase; k-blocks / k-steps of the mean phases
-  size_t sVA = 0, sSBf = 0;
+  int r0u = 0;
   long long nlines_pad = 0;
-  size_t sP0f = 0, sP1A = 0, sT4f = 0, sBtA = 0;   // per-output strides (elements)
   int r0[kMaxQ] = {0}, r1[kMaxQ] = {0};
   double setup_ms = 0.0;
-  int* eff = nullptr;    // device: per-output counts the kernels run to (k_cheb_trunc), followed by the truncation tails (q doubles)
-  const double* gtmax = nullptr;              // device: largest gradient samples per k_bpost tile + slacks (k_bl_gradcoarse), or none
-  const unsigned long long* gkey = nullptr;   // device: the grid's largest gradient samples
-  bool band_ready = false;   // the guard band of this plan has been measured (guard.hip: guard_band_bilinear)
+  GemmOps ops;           // (eff: per-output counts; band_ready: guard.hip, guard_band_bilinear)
   bool encl_ready = false;   // bl_encl holds the enclosures of the constraint's mean / var per 8 x 8 cell (k_bl_enclose, r06)
 };
 
@@ -109,28 +121,11 @@ struct InterpPlan {
   bool valid = false;    // enqueued (or found not applicable) for model `serial` and the current grid
   bool usable = false;
   bool used = false;     // a sweep has run on it: the next one builds K1b's own plan
-  bool band_ready = false;
   unsigned long long serial = 0;
-  int Dn = 0, KB = 0, ncs0 = 0, nrb = 0;
-  size_t sT4f = 0, sBtA = 0;
-  int* eff = nullptr;    // device: per coefficient set (4 per output) the counts the kernels run to, then the truncation tails
-  const double* gtmax = nullptr;              // which tiles run the gradient phases (as BilinearPlan's)
-  const unsigned long long* gkey = nullptr;
-  double *grad_S0 = nullptr, *grad_Vb = nullptr, *grad_gt = nullptr;
-  unsigned long long* grad_key = nullptr;
-  // the plan as a HIP graph: captured when a signature repeats, replayed with the next model's parameter block
-  struct Sig {
-    CandSpec cs;
-    int Dn, q, n, npad, dpad, guard, a_ld, gate;
-    double cheb_tol;
-    const void* ptr[32];
-  } sig;
-  bool sig_valid = false, graph_ok = false;
-  void* exec = nullptr;                       // hipGraphExec_t
+  GemmOps ops;           // (eff: per coefficient set, 4 per output)
   bool grad_deferred = false;                 // the gate's kernels run on stream3 beside the plan's tail: the posterior launches carry no
-                                              // gradient phases, a launch of those alone follows the gate there (launch_posterior_interp)
+                                              // gradient phases, a launch of those alone follows the gate there (launch_posterior_gemm)
 };
-using InterpSig = InterpPlan::Sig;
 
 }  // namespace sbo
 
@@ -267,7 +262,7 @@ struct sbo_ctx {
   sbo::DevBuf blockmin; // per-block minima along the last axis (blocked last-axis scans)
   sbo::DevBuf gw;      // GoOSE: source weights (ucb_c on sources, -inf elsewhere), T [max shard]
   sbo::InterpPlan bi;   // K1i plan (first sweep of a model)
-  sbo::DevBuf bi_params; // ... its per-model parameter block (device) and the pinned staging the graph's copy node reads
+  sbo::DevBuf bi_params; // ... its per-model parameter block (device; the plan's kernels read it by pointer) and its pinned staging
   void* h_bi_params = nullptr;
   void* ev_bi_params = nullptr;   // hipEvent_t: the plan's copy of the block (and everything before it on the main stream) has run
   sbo::DevBuf bl_grad;  // K1b: which tiles run the gradient phases (per plan)
@@ -413,11 +408,15 @@ bool bilinear_applicable(const sbo_ctx* c);
 int bilinear_basis_enqueue(sbo_ctx* c, hipStream_t st, bool force_big);
 bool interp_applicable(const sbo_ctx* c);
 int interp_setup(sbo_ctx* c);
-int launch_posterior_interp(sbo_ctx* c);
 int guard_probe_gradients(sbo_ctx* c, hipStream_t st, double* ppts, double* grad_out, const sbo::ModelConst* mcp = nullptr);
-bool guard_reference_is_direct(const sbo_ctx* c);
 int bilinear_setup(sbo_ctx* c);
-int launch_posterior_bilinear(sbo_ctx* c);
+int launch_posterior_gemm(sbo_ctx* c, bool interp);   // on the operands of K1i's plan (interp) or of K1b's
+// both GEMM-posterior plans (and the posterior) out of date: a new model, new candidates, or an option the plans are built with
+inline void plans_invalidate(sbo_ctx* c) {
+  c->bl.valid = false;
+  c->bi.valid = false;
+  c->posterior_valid = false;
+}
 bool tensor_applicable(const sbo_ctx* c);
 int launch_posterior_tensor(sbo_ctx* c, bool* declined);
 int launch_posterior_on_axes(sbo_ctx* c, int d, const long long* count, const double* axc, double* mean_out, double* var_out, double* grad_out,

@@ -960,13 +960,13 @@ int launch_posterior(sbo_ctx* c) {
         if (!(c->bi.valid && c->bi.serial == c->model_serial) && (rc = interp_setup(c))) return rc;
         if (c->bi.usable && !c->bi.used) {
           c->last_k1 = 6;
-          return launch_posterior_interp(c);
+          return launch_posterior_gemm(c, true);
         }
       }
       if (!c->bl.valid && (rc = bilinear_setup(c))) return rc;
       if (c->bl.usable) {
         c->last_k1 = 4;
-        return launch_posterior_bilinear(c);       // (writes the Lipschitz keys itself)
+        return launch_posterior_gemm(c, false);    // (writes the Lipschitz keys itself)
       }
     }
     // fp64 grids of three / four axes: exact values at Chebyshev nodes, interpolated to the grid (K1t) when the plan qualifies
