@@ -637,6 +637,8 @@ int sbo_candidates_grid_sharded(sbo_ctx* c, int d, const double* lo, const doubl
   return SBO_OK;
 }
 
+}  // extern "C"
+
 static int check_ready(sbo_ctx* c) {
   if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
   if (!c->has_model) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
@@ -645,8 +647,10 @@ static int check_ready(sbo_ctx* c) {
   return SBO_OK;
 }
 
-// K1 without synchronisation or timing (used inside the sweeps)
-int sbo_posterior_enqueue(sbo_ctx* c) {
+int sbo::posterior_enqueue(sbo_ctx* c, const PostRequest& req, PostOutcome* out) {
+  PostOutcome none;
+  if (!out) out = &none;
+  *out = PostOutcome{};
   int rc = check_ready(c);
   if (rc) return rc;
   SBO_HIP(hipSetDevice(c->device));
@@ -654,10 +658,12 @@ int sbo_posterior_enqueue(sbo_ctx* c) {
   if ((rc = alloc_workspace(c))) return rc;
   // (a standing audit of the last sweep may not have taken its sample of mean / var yet: it is a few microseconds of work on its stream)
   if (c->audit_pending) SBO_HIP(hipStreamWaitEvent(c->stream, c->ev_audit[0], 0));
-  if (c->cs.n_local > 0 && (rc = launch_posterior(c))) return rc;
+  if (c->cs.n_local > 0 && (rc = launch_posterior(c, req, *out))) return rc;
   c->posterior_valid = true;
   return SBO_OK;
 }
+
+extern "C" {
 
 double sbo_algorithmic_flops(const sbo_ctx* c) {
   const double n = c->mc.n, d = c->mc.d, q = c->mc.q;
@@ -669,9 +675,9 @@ int sbo_posterior_run(sbo_ctx* c) {
   if (rc) return rc;
   SBO_HIP(hipSetDevice(c->device));
   SBO_HIP(hipEventRecord(c->ev[0], c->stream));
-  if ((rc = sbo_posterior_enqueue(c))) return rc;
-  if (!c->k1_stop_attached) SBO_HIP(hipEventRecord(c->ev[1], c->stream));
-  c->k1_stop_attached = false;
+  PostOutcome out;
+  if ((rc = posterior_enqueue(c, PostRequest{}, &out))) return rc;
+  SBO_HIP(k1_stop(c, out));
   SBO_HIP(hipEventSynchronize(c->ev[1]));
   float ms = 0;
   SBO_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));

@@ -1100,8 +1100,8 @@ __global__ __launch_bounds__(256) void k_lmax_reduce(const double* __restrict__ 
 
 // Column path (r05): can this launch deliver the classification as column words?  One constraint, fp64 grid of whole 64 x 128
 // tiles (every workgroup's tile inside the grid), at most 64 segments (Usum is one word per column); the sweep asked for it.
-static bool col_words_ok(const sbo_ctx* c, long long cnt0, long long nlines) {
-  if (!c->col_request || !c->col_path) return false;
+static bool col_words_ok(const sbo_ctx* c, const PostRequest& req, long long cnt0, long long nlines) {
+  if (!req.col || !c->col_path) return false;
   const bool shape = c->mc.q == 2 && c->cs.kind == 1 && c->cs.d == 2 && c->cs.first == 0 && cnt0 % 128 == 0 && nlines % 64 == 0 &&
                      nlines / 64 <= 64 && nlines >= 64 && cnt0 >= 128 && cnt0 <= 4096 && c->world == 1 && !c->comm_selftest;
   // (auto: from four tiles per CU and output on -- config H.  Below that the two launches per sweep cost more than the column
@@ -1137,7 +1137,7 @@ static int col_words_prepare(sbo_ctx* c, long long cnt0, long long nlines, ColBi
 
 // The GEMM posterior on the operands of a plan -- K1i's when `interp`, else K1b's: stage 1, the k_bpost launches and the Lipschitz tail.
 // Only K1i has the deferred gradient launch (k_bgrad on stream3); only K1b the column path's enclosures and tile lists (r06, r07).
-int launch_posterior_gemm(sbo_ctx* c, bool interp) {
+int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostOutcome& out) {
   const GemmOps& g = interp ? c->bi.ops : c->bl.ops;
   const ModelConst& mc = c->mc;
   const CandSpec& cs = c->cs;
@@ -1171,27 +1171,26 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp) {
   // (one-constraint models; the masks are allocated by the sweep before it enqueues the posterior)
   // (r03: with the sqrt-free sign tests the fused epilogue saves the separate pass 76 us on config H and costs the GEMM 36;
   // on config B, two workgroups per CU, the two cancel -- "auto" asks for at least four workgroups per CU)
-  const bool fuse_wanted = c->fuse_request == 1 || (c->fuse_request == 2 && ((long long)gx * gy * q >= 4ll * c->n_cu || q > 2));   // (several constraints: the separate pass costs more than one constraint's)
+  const bool fuse_wanted = req.fuse == 1 || (req.fuse == 2 && ((long long)gx * gy * q >= 4ll * c->n_cu || q > 2));   // (several constraints: the separate pass costs more than one constraint's)
   bool fuse = fuse_wanted && q >= 2 && c->maskS.p && c->maskU.p && c->maskS.bytes >= (size_t)cs.n_local && c->maskU.bytes >= (size_t)cs.n_local &&
               (q == 2 || (c->fuseS.bytes >= (size_t)cs.n_local * (q - 1) && c->fuseU.bytes >= (size_t)cs.n_local * (q - 1)));
-  const bool colw = fuse && col_words_ok(c, cnt0, nlines);
+  const bool colw = fuse && col_words_ok(c, req, cnt0, nlines);
   PostExtra px;
   memset(&px, 0, sizeof(px));
   px.q = q;
-  c->col_active = false;
-  c->fuse_rows = 0;
   if (fuse) {
-    c->fuse_rows = (int)rows_out * (colw ? 2 : (q - 1));
+    out.fuse_rows = (int)rows_out * (colw ? 2 : (q - 1));
     px.fstride = q > 2 ? (long long)cs.n_local : 0ll;
     // (room behind the rows for the partials of the objective pass, see sweep_common_front)
-    if ((rc = ensure(c->cpart, sizeof(unsigned long long) * kFuseRow * ((size_t)c->fuse_rows + 4 * (size_t)c->n_cu + 64)))) return rc;
+    if ((rc = ensure(c->cpart, sizeof(unsigned long long) * kFuseRow * ((size_t)out.fuse_rows + 4 * (size_t)c->n_cu + 64)))) return rc;
     c->cpart_cap = (int)(c->cpart.bytes / (sizeof(unsigned long long) * kFuseRow));
   }
   if (colw) {
     if ((rc = col_words_prepare(c, cnt0, nlines, &px.cb))) return rc;
-    px.lean = c->col_lean;
-    c->col_active = true;
-    c->col_forked = true;
+    px.lean = req.col_lean;
+    out.col_active = true;
+    out.col_forked = true;
+    out.col_lean = req.col_lean;
     fuse = false;                      // (no byte masks: the words are the classification)
   }
   bool record_encl = false;
@@ -1209,14 +1208,14 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp) {
     record_encl = !c->bl.encl_ready;
     c->k1_encl_tiles = ntiles;
     c->k1_encl_check = !record_encl;
-    if (!record_encl && c->col_lean >= 2) {
+    if (!record_encl && req.col_lean >= 2) {
       px.encl = encl;
       px.skip = (uint8_t*)c->bl_encl.p + ebytes;
       c->k1_skip_armed = true;
     }
     // r07: lean 2 -- the objective's launch over the tiles with a safe candidate, and, once the enclosures decide skips, the
     // constraint's over the tiles that need a workgroup (k_bl_sched_tiles1 and on).  [class bytes][list 1][list 2]
-    if (c->k1_sched && c->col_lean >= 2) {
+    if (c->k1_sched && req.col_lean >= 2) {
       if ((rc = ensure(c->bl_sched, ((ntiles + 15) & ~(size_t)15) + 2 * sizeof(unsigned int) * (ntiles + 1)))) return rc;
       sched_cls = (uint8_t*)c->bl_sched.p;
       sched_l1 = (unsigned int*)(sched_cls + ((ntiles + 15) & ~(size_t)15));
@@ -1238,13 +1237,13 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp) {
     SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bgrad), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_bgrad, dim3((unsigned)std::min<long long>((long long)rows_out, 2ll * c->n_cu)), dim3(256), lds, gs, mc, cs, g.VA,
                        g.sVA, g.P0f, g.KB0, g.nrb, g.ncs0, nlines, (int)gx, (int)gy, (const int*)g.eff, g.gtmax, g.gkey,
-                       (const double*)c->bl_small.p, q, lrows, colw ? px.cb.slots : (unsigned long long*)nullptr, (c->sweep_lean && q >= 2) ? 1 : 0);
+                       (const double*)c->bl_small.p, q, lrows, colw ? px.cb.slots : (unsigned long long*)nullptr, (req.sweep_lean && q >= 2) ? 1 : 0);
     SBO_HIP(hipEventRecord(c->ev_grad[2], gs));
     c->grad_pending = true;
     px.nograd = 1;
   }
   // the K1 stop event rides on the last launch (hipExtLaunchKernel): a separate hipEventRecord behind it is a barrier packet
-  // the next kernel waits ~6 us for.  A sweep merges the Lipschitz partials in its own first small kernel (lmax_defer).
+  // the next kernel waits ~6 us for.  A sweep merges the Lipschitz partials in its own first small kernel (req.lmax_defer).
   // (column path: the constraint's launch first -- the objective's tiles read its words and its counts of safe candidates per tile)
   for (int part = 0; part < (colw ? 2 : 1); ++part) {
     px.o0 = colw ? 1 - part : 0;
@@ -1254,7 +1253,7 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp) {
     px.tlist = nullptr;
     if (sched_l1 && part == 0 && px.encl) {
       hipLaunchKernelGGL(k_bl_sched_tiles1, dim3((gx * gy + 3) / 4), dim3(256), 0, c->stream, mc, (const double*)px.encl, (int)(gx * gy), (int)gx,
-                         (int)gy, (unsigned int)cnt0, c->fuse_b, gb_fused, g.gtmax, g.gkey, q, px.skip, sched_cls, px.cb.Sw, px.cb.Uw,
+                         (int)gy, (unsigned int)cnt0, req.fuse_b, gb_fused, g.gtmax, g.gkey, q, px.skip, sched_cls, px.cb.Sw, px.cb.Uw,
                          lrows, (unsigned long long*)c->cpart.p, c->cpart_cap);
       hipLaunchKernelGGL(k_bl_sched_list1, dim3(1), dim3(1024), 0, c->stream, (const uint8_t*)sched_cls, (int)(gx * gy), (int)gx,
                          (const double*)lrows + (size_t)rows_out, sched_l1, px.cb.Usum, px.cb.slots);
@@ -1269,11 +1268,11 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp) {
     px.tgy = (int)gy;
     const dim3 grid = px.tlist ? dim3(gx * gy) : dim3(gx, gy, (unsigned)(colw ? 1 : q));
     hipExtLaunchKernelGGL(kpost, grid, dim3(256), lds, c->stream, nullptr,
-                          (c->lmax_defer && last) ? c->ev[1] : ((colw && part == 0) ? c->ev_col[0] : nullptr), 0,
+                          (req.lmax_defer && last) ? c->ev[1] : ((colw && part == 0) ? c->ev_col[0] : nullptr), 0,
                           mc, cs, g.BtA, g.sBtA, g.P0f, g.sP0f, g.VA, g.sVA, g.SBf, g.sSBf, g.KB0, g.KS0, g.KBm, g.KSm, g.KBm2, g.nrb, g.ncs0,
                           nlines, (double*)c->mean.p, (double*)c->var.p, defer ? lrows + (size_t)rows_out * q : lrows,
                           (const double*)c->bl_small.p /* xn0 */, fuse ? (uint8_t*)(q > 2 ? c->fuseS.p : c->maskS.p) : (uint8_t*)nullptr,
-                          fuse ? (uint8_t*)(q > 2 ? c->fuseU.p : c->maskU.p) : (uint8_t*)nullptr, c->fuse_b, (unsigned long long*)c->cpart.p,
+                          fuse ? (uint8_t*)(q > 2 ? c->fuseU.p : c->maskU.p) : (uint8_t*)nullptr, req.fuse_b, (unsigned long long*)c->cpart.p,
                           c->cpart_cap, gb_fused, (const int*)g.eff, g.gtmax, g.gkey, g.imode, px);
     if (colw && part == 0 && record_encl) {
       // (the plan's first constraint launch evaluated and stored every tile: its enclosures, ~270 MB read once per plan)
@@ -1288,14 +1287,14 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp) {
     SBO_HIP(hipStreamWaitEvent(c->stream, c->ev_grad[2], 0));
     c->grad_pending = false;
   }
-  if (c->lmax_defer) {
-    c->lmax_pending = true;
-    c->lmax_per_out = (int)rows_out;
+  if (req.lmax_defer) {
+    out.lmax_pending = true;
+    out.lmax_per_out = (int)rows_out;
   } else {
     hipExtLaunchKernelGGL(k_lmax_reduce, dim3((unsigned)q), dim3(256), 0, c->stream, nullptr, c->ev[1], 0, (const double*)lrows,
                           (int)rows_out, (unsigned long long*)c->Lmax.p);
   }
-  c->k1_stop_attached = true;
+  out.stop_attached = true;
   c->gb_active = c->guard_band && !c->is_shadow && g.band_ready;     // (the band came with the plan)
   const double tiles2 = (double)g.nrb * g.ncs0;
   if (interp) {

@@ -541,7 +541,8 @@ void guard_audit_harvest(sbo_ctx* c, bool wait) {
   c->audit_pending = false;
 }
 
-int guard_audit_enqueue(sbo_ctx* c, int first_output) {
+int guard_audit_enqueue(sbo_ctx* c, const PostOutcome& out) {
+  const int first_output = out.col_lean ? 1 : 0;      // (a lean column-path launch left the objective's values incomplete)
   if (c->guard_audit <= 0 || !c->gb_active || !c->guard_band || c->is_shadow || !(c->last_k1 == 4 || c->last_k1 == 6) || !ref_direct(c) || c->mc.dpad != 2 ||
       c->cs.n_local <= 0 || !c->stream_audit || first_output >= c->mc.q)
     return SBO_OK;

@@ -116,6 +116,30 @@ struct BilinearPlan {
   bool encl_ready = false;   // bl_encl holds the enclosures of the constraint's mean / var per 8 x 8 cell (k_bl_enclose, r06)
 };
 
+// What one posterior launch is asked to do (posterior_enqueue).  A default request is a plain posterior run: every value and
+// Lipschitz key, no classification, the approximating kernels wherever they qualify.
+struct PostRequest {
+  int fuse = 0;             // classification fused into K1b's mean epilogue (one-constraint sweeps): 0 no, 1 yes, 2 when the launch
+                            // is large enough for it to pay (option fuse_classify = -1)
+  double fuse_b = 0.0;      // ... at the sweep's confidence multiplier
+  bool lmax_defer = false;  // K1b leaves its per-wave Lipschitz partials for the sweep's first small kernel to merge
+  bool col = false;         // column path (sets_colpath.inc.hpp): the classification as column words, one launch per output
+  int col_lean = 0;         // ... objective tiles without a safe candidate need not store mean / var (1), nor be evaluated (2)
+  int sweep_lean = 0;       // a lean SafeOpt sweep: the objective's Lipschitz key L_0 (no sweep reads it) is not computed by K1t / K1i
+  bool exact = false;       // no approximating posterior (K1b, K1i, K1t): the exact kernels only
+};
+
+// What the launch reports back (filled by the launcher: all zero unless a GEMM posterior ran)
+struct PostOutcome {
+  bool col_active = false;     // the launch delivered the classification as column words (col_set_phase runs)
+  bool col_forked = false;     // ... and the constraint's launch carried ev_col[0]
+  int col_lean = 0;            // ... at this lean level (non-zero: the objective's mean / var are incomplete)
+  int fuse_rows = 0;           // > 0: the kernel wrote S / U and that many partial rows at the head of cpart
+  bool lmax_pending = false;   // the Lipschitz partials (lmax_per_out rows per output in bl_lpart) wait for the sweep to merge them
+  int lmax_per_out = 0;
+  bool stop_attached = false;  // the last kernel carries ev[1] as its stop event (no separate record, which costs a ~6 us bubble)
+};
+
 // K1i: the first sweep of a model by interpolation from Chebyshev nodes (bilinear.hip)
 struct InterpPlan {
   bool valid = false;    // enqueued (or found not applicable) for model `serial` and the current grid
@@ -175,9 +199,6 @@ struct sbo_ctx {
   // K1t (tensor.hip): fp64 grids of three / four axes by Chebyshev interpolation from exact node values
   int tensor_cheb = 1;             // option: 0 = always K1g
   int tensor_guess_pct = 100;      // option (test hook): scales the first guess of the node counts; a short guess exercises the probe's second attempt
-  const double* k1g_axc = nullptr; // K1g launch arguments of launch_posterior_on_axes (explicit axis positions, gradient output)
-  void* k1g_grad = nullptr;
-  bool tensor_busy = false;        // the exact node / probe launch of K1t is running through launch_posterior
   sbo::DevBuf tn_pts, tn_vals, tn_work, tn_W0t, tn_W1t, tn_probe, tn_scr;
   sbo::DevBuf tn_gather;     // ranks > 1: this rank's slab of the node tensors | every rank's (all-gather)
   sbo::DevBuf tn_W[SBO_MAX_D];
@@ -283,19 +304,11 @@ struct sbo_ctx {
   double comm_host_ms = 0.0;  // (relay transport: wall clock of the staged collectives)
   hipEvent_t comm_ev[16]{};
   int host_syncs = 0;  // host waits on the device inside the running sweep call (sbo_profile.host_syncs)
-  // classification fused into the posterior (K1b, one constraint): a sweep sets fuse_request / fuse_b before it enqueues the
-  // posterior; fuse_rows > 0 afterwards = the kernel wrote S / U and that many partial rows at the head of cpart
   sbo::DevBuf fuseS, fuseU;   // [(q - 1)][N] byte planes of a fused classification of several constraints (r05)
-  int fuse_request = 0;    // 0 no, 1 yes, 2 when the GEMM launch is large enough for it to pay (option fuse_classify = -1)
-  double fuse_b = 0.0;
-  int fuse_rows = 0;
   // Column path (r05, sets_colpath.inc.hpp): a one-rank SafeOpt sweep of a one-constraint model on a 2-D grid of whole
-  // 64 x 128 tiles asks (col_request) for the classification as column words; the GEMM posterior then runs one launch per
+  // 64 x 128 tiles asks (PostRequest::col) for the classification as column words; the GEMM posterior then runs one launch per
   // output -- constraint first: S / U words, |S| per tile; objective second: u* and min var_0 over S from its own epilogue --
-  // and says so (col_active).  The words stay resident for sbo_masks_get (masks_bits: expanded to bytes on demand).
-  bool col_request = false, col_active = false;
-  int sweep_lean = 0;      // the running SafeOpt sweep is lean: the objective's Lipschitz key L_0 (no sweep reads it) is not computed by K1t / K1i
-  int col_lean = 0;        // the running request: objective tiles without a safe candidate need not store mean / var
+  // and says so (PostOutcome::col_active).  The words stay resident for sbo_masks_get (masks_bits: expanded to bytes on demand).
   bool slots_clean = false;// the slot block holds its neutral elements (the finals of the last column sweep reset it)
   bool usum_dirty = false; // Usum holds bits of an earlier launch (cleared by the column path's second kernel; by a memset after a failure)
   int col_path = 1;        // option: 0 = never
@@ -310,14 +323,8 @@ struct sbo_ctx {
   hipEvent_t ev_grad[4]{};     // K1i's deferred tail: fork (plan: the series are in place) / stage 1 has run / the keys are merged / the band is written
   bool grad_pending = false;   // a deferred gradient launch is in flight on stream3: whoever reads the Lipschitz partials elsewhere waits for ev_grad[2]
   int grad_defer = 1;          // option: 0 = the gate stays in front of the posterior launch (r04)
-  bool col_forked = false;     // the constraint's launch of the running posterior carried ev_col[0]
   bool masks_bits = false;     // the masks of the last sweep live in the column words (byte buffers stale)
   bool col_G_bytes = false;    // ... except G, which the exhaustive recheck finished in byte form
-  // Lipschitz keys of K1b: a sweep sets lmax_defer before it enqueues the posterior; the posterior then leaves its per-wave
-  // partials (lmax_per_out per output) for the sweep's k_classify_final / k_edt_axis0_pair to merge (lmax_pending)
-  bool lmax_defer = false;
-  bool lmax_pending = false;
-  int lmax_per_out = 0;
   sbo::DevBuf Wfull;   // multi-rank GoOSE: source weights of the whole grid (all-gathered), T [grid_total]
   sbo::DevBuf Uwin;    // multi-rank: U mask of the expander transform's window (own planes + halo), uint8
   long long uwin_first = 0, uwin_n = 0;   // flat range the window covers
@@ -343,7 +350,6 @@ struct sbo_ctx {
   unsigned char* h_back = nullptr;        // pinned host landing area of the end-of-sweep read-back (scalars + Lipschitz keys)
   int last_sweep = 0;  // 1 safeopt, 2 goose (what the masks hold)
   bool masks_valid = false;
-  bool k1_stop_attached = false;   // the last K1 kernel carries ev[1] as its stop event (no separate record, which costs a ~6 us bubble)
   bool amb_clean = false;   // the recheck / scan counters of the scalar block are still zero (no k_reset_amb needed)
   // profile
   sbo_profile prof{};
@@ -394,8 +400,13 @@ void release(DevBuf& b);
 void drain_streams(sbo_ctx* c);
 int factor_sync(sbo_ctx* c);      // wait for a deferred factorisation (sbo_ctx::factor_pending); SBO_E_INVALID when invK was not positive definite   // after a failed call: wait for whatever it left on the main and side streams
 
+// the posterior inside a sweep, without synchronisation or timing (api.hip); `out` (nullptr: not wanted) is reset first
+int posterior_enqueue(sbo_ctx* c, const PostRequest& req, PostOutcome* out);
+// the K1 stop event ev[1] behind a posterior enqueue: the last kernel carried it, or a record of its own
+inline hipError_t k1_stop(sbo_ctx* c, const PostOutcome& out) { return out.stop_attached ? hipSuccess : hipEventRecord(c->ev[1], c->stream); }
+
 // launchers implemented in the .hip files -----------------------------------------------------
-int launch_posterior(sbo_ctx* c);
+int launch_posterior(sbo_ctx* c, const PostRequest& req, PostOutcome& out);
 int launch_bound(sbo_ctx* c, double b, int index, int kind, void* dev_out);
 int model_build(sbo_ctx* c, const double* const* host_invK, const double* X_norm, const double* Y_norm);
 int model_prep(sbo_ctx* c, const double* X_norm);
@@ -410,7 +421,7 @@ bool interp_applicable(const sbo_ctx* c);
 int interp_setup(sbo_ctx* c);
 int guard_probe_gradients(sbo_ctx* c, hipStream_t st, double* ppts, double* grad_out, const sbo::ModelConst* mcp = nullptr);
 int bilinear_setup(sbo_ctx* c);
-int launch_posterior_gemm(sbo_ctx* c, bool interp);   // on the operands of K1i's plan (interp) or of K1b's
+int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostOutcome& out);   // on the operands of K1i's plan (interp) or of K1b's
 // both GEMM-posterior plans (and the posterior) out of date: a new model, new candidates, or an option the plans are built with
 inline void plans_invalidate(sbo_ctx* c) {
   c->bl.valid = false;
@@ -418,7 +429,7 @@ inline void plans_invalidate(sbo_ctx* c) {
   c->posterior_valid = false;
 }
 bool tensor_applicable(const sbo_ctx* c);
-int launch_posterior_tensor(sbo_ctx* c, bool* declined);
+int launch_posterior_tensor(sbo_ctx* c, const PostRequest& req, bool* declined);
 int launch_posterior_on_axes(sbo_ctx* c, int d, const long long* count, const double* axc, double* mean_out, double* var_out, double* grad_out,
                              unsigned long long* lmax);
 // the exact posterior of the generic kernel on an explicit fp64 list [N][d] (device), into caller-given arrays [q][N]
@@ -441,7 +452,7 @@ struct GbAnalytic {
 };
 int guard_band_from_probes(sbo_ctx* c, const double* pm, const double* pv, const double* ref_m, const double* ref_v, const double* tail, const GbAnalytic& an);
 int guard_band_host(sbo_ctx* c, const double* dm, const double* dv, const double* rl, const double* parts = nullptr /* analytic dm | dv | probe dm | dv, kMaxQ each */);
-int guard_audit_enqueue(sbo_ctx* c, int first_output);   // behind the posterior launch of a sweep (first_output 1: a lean sweep left the objective's values incomplete)
+int guard_audit_enqueue(sbo_ctx* c, const PostOutcome& out);   // behind the posterior launch of a sweep (out.col_lean: the objective's values are incomplete)
 void guard_audit_harvest(sbo_ctx* c, bool wait);         // collect a finished audit's counts (wait: block until it has finished)
 }  // namespace sbo
 

@@ -805,77 +805,87 @@ __global__ void k_soa_to_aos(const T* __restrict__ soa, long long n, int q, T* _
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------
+// What the generic kernels (K1, K1c, K1g) read and write: the resident candidates and posterior buffers (launch_posterior), or a
+// caller's list / node axes with arrays of its own (launch_posterior_on_list / _on_axes)
+struct PostTarget {
+  CandSpec cs;
+  void *mean, *var;                // [q][cs.n_local] of the model dtype
+  unsigned long long* Lmax;        // [kMaxQ] Lipschitz keys
+  const double* axc = nullptr;     // K1g, fp64 grids of three / four axes: explicit axis positions, and the signed gradient
+  double* grad = nullptr;          // components of the mean [q][d][N] (launch_posterior_on_axes)
+};
+
 template <typename T, int S, int D>
-static int launch_posterior_t(sbo_ctx* c) {
+static int launch_posterior_t(sbo_ctx* c, const PostTarget& t) {
   const ModelConst& mc = c->mc;
   constexpr int P = 16 * S;
   const int nfr = mc.npad / 4;
   const size_t lds = sizeof(T) * ((size_t)S * nfr * 64 + kWaves * P + (kWaves / S) * P * (1 + D));
   auto kern = k_posterior<T, S, D>;
   SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const long long tiles = (c->cs.n_local + P - 1) / P;
+  const long long tiles = (t.cs.n_local + P - 1) / P;
   if (tiles > 0x7fffffffLL) return fail(SBO_E_UNSUPPORTED, "too many candidate tiles for one launch");
   dim3 grid((unsigned)tiles, (unsigned)mc.q), block(256);
-  hipLaunchKernelGGL(kern, grid, block, lds, c->stream, mc, c->cs, (const T*)c->Fpk.p, c->fpk_stride,
+  hipLaunchKernelGGL(kern, grid, block, lds, c->stream, mc, t.cs, (const T*)c->Fpk.p, c->fpk_stride,
                      (const T*)c->As.p, (const T*)c->sqA.p, (const T*)c->alpha.p, (const T*)c->Xn.p,
-                     (T*)c->mean.p, (T*)c->var.p, (unsigned long long*)c->Lmax.p);
+                     (T*)t.mean, (T*)t.var, t.Lmax);
   SBO_HIP(hipGetLastError());
   return SBO_OK;
 }
 
 template <typename T, int S>
-static int launch_posterior_d(sbo_ctx* c) {
+static int launch_posterior_d(sbo_ctx* c, const PostTarget& t) {
   switch (c->mc.dpad) {
-    case 2: return launch_posterior_t<T, S, 2>(c);
-    case 4: return launch_posterior_t<T, S, 4>(c);
-    case 8: return launch_posterior_t<T, S, 8>(c);
+    case 2: return launch_posterior_t<T, S, 2>(c, t);
+    case 4: return launch_posterior_t<T, S, 4>(c, t);
+    case 8: return launch_posterior_t<T, S, 8>(c, t);
   }
   return fail(SBO_E_UNSUPPORTED, "unsupported padded dimension");
 }
 
 template <typename T, int D>
-static int launch_posterior_chunked_t(sbo_ctx* c) {
+static int launch_posterior_chunked_t(sbo_ctx* c, const PostTarget& t) {
   const ModelConst& mc = c->mc;
   constexpr int P = 16 * kWaves, CB = ChunkCfg<T>::CB;
   const size_t lds = sizeof(T) * ((size_t)kWaves * CB * 4 * 64 + kWaves * P + (size_t)P * (1 + D));
   auto kern = k_posterior_chunked<T, D>;
   SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const long long tiles = (c->cs.n_local + P - 1) / P;
+  const long long tiles = (t.cs.n_local + P - 1) / P;
   if (tiles > 0x7fffffffLL) return fail(SBO_E_UNSUPPORTED, "too many candidate tiles for one launch");
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)mc.q), dim3(256), lds, c->stream, mc, c->cs, (const T*)c->Fpk.p,
+  hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)mc.q), dim3(256), lds, c->stream, mc, t.cs, (const T*)c->Fpk.p,
                      c->fpk_stride, (const T*)c->As.p, (const T*)c->sqA.p, (const T*)c->alpha.p, (const T*)c->Xn.p,
-                     (T*)c->mean.p, (T*)c->var.p, (unsigned long long*)c->Lmax.p);
+                     (T*)t.mean, (T*)t.var, t.Lmax);
   SBO_HIP(hipGetLastError());
   return SBO_OK;
 }
 
 template <typename T>
-static int launch_posterior_chunked(sbo_ctx* c) {
+static int launch_posterior_chunked(sbo_ctx* c, const PostTarget& t) {
   switch (c->mc.dpad) {
-    case 2: return launch_posterior_chunked_t<T, 2>(c);
-    case 4: return launch_posterior_chunked_t<T, 4>(c);
-    case 8: return launch_posterior_chunked_t<T, 8>(c);
+    case 2: return launch_posterior_chunked_t<T, 2>(c, t);
+    case 4: return launch_posterior_chunked_t<T, 4>(c, t);
+    case 8: return launch_posterior_chunked_t<T, 8>(c, t);
   }
   return fail(SBO_E_UNSUPPORTED, "unsupported padded dimension");
 }
 
 template <typename T>
-static int launch_posterior_s(sbo_ctx* c) {
+static int launch_posterior_s(sbo_ctx* c, const PostTarget& t) {
   // strips per workgroup: the K* tile [npad, 16 S] must fit the 160 KiB LDS with room for two workgroups
   // per CU when it can (latency hiding across the generation / contraction phases).
   const size_t per_strip = sizeof(T) * (size_t)c->mc.npad * 16;
   const size_t budget = 144 * 1024;
-  if (per_strip * 4 <= budget) return launch_posterior_d<T, 4>(c);
-  if (per_strip * 2 <= budget) return launch_posterior_d<T, 2>(c);
-  if (per_strip <= budget) return launch_posterior_d<T, 1>(c);
+  if (per_strip * 4 <= budget) return launch_posterior_d<T, 4>(c, t);
+  if (per_strip * 2 <= budget) return launch_posterior_d<T, 2>(c, t);
+  if (per_strip <= budget) return launch_posterior_d<T, 1>(c, t);
   return fail(SBO_E_UNSUPPORTED, "n too large for the LDS-resident cross-covariance tile");
 }
 
 template <typename T, int D, int S>
-static int launch_posterior_grid_ts(sbo_ctx* c) {
+static int launch_posterior_grid_ts(sbo_ctx* c, const PostTarget& t) {
   constexpr int P = 16 * S;
   const ModelConst& mc = c->mc;
-  const CandSpec& cs = c->cs;
+  const CandSpec& cs = t.cs;
   const int npad = mc.npad, nfr = npad / 4, q = mc.q, d = cs.d;
   const long long cnt0 = cs.count[0];
   const long long ntile0 = (cnt0 + 15) / 16;
@@ -896,13 +906,13 @@ static int launch_posterior_grid_ts(sbo_ctx* c) {
   const long long total = (long long)gt.e0_stride + (long long)gt.er_stride_o;
   hipLaunchKernelGGL((k_build_tables<T>), dim3((unsigned)std::min<long long>((total + 255) / 256, 4096), q), dim3(256), 0,
                      c->stream, mc, cs, (const T*)c->As.p, mc.dpad, (T*)c->E0f.p, gt.e0_stride, (T*)c->Er.p, gt.er_stride_o,
-                     gt.er_off[1], gt.er_off[2], gt.er_off[3], gt.er_off[4], gt.er_off[5], gt.er_off[6], gt.er_off[7], c->k1g_axc);
+                     gt.er_off[1], gt.er_off[2], gt.er_off[3], gt.er_off[4], gt.er_off[5], gt.er_off[6], gt.er_off[7], t.axc);
   if ((rc = ensure(c->AXg, sizeof(T) * (size_t)q * npad * (1 + D)))) return rc;
   hipLaunchKernelGGL((k_build_ax<T>), dim3(1, q), dim3(256), 0, c->stream, mc, (const T*)c->alpha.p, (const T*)c->Xn.p, D,
                      (T*)c->AXg.p);
   const size_t lds = sizeof(T) * ((size_t)S * npad + 8 + (size_t)(2 + D) * kWaves * 4 * P);
   // (explicit axis positions + gradient output: its own instance, fp64 grids of up to four axes only -- the plain one keeps its registers)
-  const bool ax = c->k1g_axc != nullptr;
+  const bool ax = t.axc != nullptr;
   if (ax && !(sizeof(T) == 8 && D == 4 && S == 4)) return fail(SBO_E_UNSUPPORTED, "internal: explicit axes are an fp64 path of three / four axes");
   auto kern = ax ? k_posterior_grid<T, S, D, (sizeof(T) == 8 && D == 4 && S == 4)> : k_posterior_grid<T, S, D, false>;
   SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -916,22 +926,22 @@ static int launch_posterior_grid_ts(sbo_ctx* c) {
   const long long wgs = std::min<long long>(tiles, ((long long)c->n_cu * per_cu + q - 1) / q);
   hipLaunchKernelGGL(kern, dim3((unsigned)std::max<long long>(wgs, 1), (unsigned)q), dim3(256), lds, c->stream, mc, cs, gt,
                      (const T*)c->Fpk.p, c->fpk_stride, (const T*)c->E0f.p, (const T*)c->Er.p, (const T*)c->AXg.p,
-                     (unsigned int)tiles, (T*)c->mean.p, (T*)c->var.p, (unsigned long long*)c->Lmax.p, c->k1g_axc, (T*)c->k1g_grad);
+                     (unsigned int)tiles, (T*)t.mean, (T*)t.var, t.Lmax, t.axc, (T*)t.grad);
   SBO_HIP(hipGetLastError());
   return SBO_OK;
 }
 
 template <typename T, int D>
-static int launch_posterior_grid_t(sbo_ctx* c) {
-  return launch_posterior_grid_ts<T, D, 4>(c);
+static int launch_posterior_grid_t(sbo_ctx* c, const PostTarget& t) {
+  return launch_posterior_grid_ts<T, D, 4>(c, t);
 }
 
 template <typename T>
-static int launch_posterior_grid(sbo_ctx* c) {
+static int launch_posterior_grid(sbo_ctx* c, const PostTarget& t) {
   switch (c->mc.dpad) {
-    case 2: return launch_posterior_grid_t<T, 2>(c);
-    case 4: return launch_posterior_grid_t<T, 4>(c);
-    case 8: return launch_posterior_grid_t<T, 8>(c);
+    case 2: return launch_posterior_grid_t<T, 2>(c, t);
+    case 4: return launch_posterior_grid_t<T, 4>(c, t);
+    case 8: return launch_posterior_grid_t<T, 8>(c, t);
   }
   return fail(SBO_E_UNSUPPORTED, "unsupported padded dimension");
 }
@@ -945,14 +955,23 @@ static bool grid_path_ok(const sbo_ctx* c) {
   return cs.first % cnt0 == 0 && cs.n_local % cnt0 == 0;
 }
 
-int launch_posterior(sbo_ctx* c) {
+// generic candidates: the single-phase kernel while the whole K* tile of 64 candidates fits LDS with two workgroups per CU, the
+// chunked kernel beyond that (and on request: posterior_path 2)
+static bool generic_chunked(const sbo_ctx* c) {
+  const size_t tile_bytes = (c->dtype == SBO_F64 ? 8u : 4u) * (size_t)c->mc.npad * 64;
+  return c->posterior_path == 2 || tile_bytes > 64 * 1024;
+}
+static int launch_generic(sbo_ctx* c, const PostTarget& t);   // (defined below launch_posterior: the code object keeps its kernel order)
+
+int launch_posterior(sbo_ctx* c, const PostRequest& req, PostOutcome& out) {
   c->gb_active = false;                    // (the approximating paths K1b / K1t switch their guard band on themselves)
   c->k1_skip_armed = c->k1_encl_check = false;   // (so does the K1b column path its records for the audit, guard.hip)
   // block-triangular contraction as issued: npad (npad + 16) / 2 multiply-adds per candidate and output
   const double tri_flops = (double)c->mc.q * c->mc.npad * (c->mc.npad + 16.0) * (double)c->cs.n_local;
+  const PostTarget t{c->cs, c->mean.p, c->var.p, (unsigned long long*)c->Lmax.p};
   if (grid_path_ok(c)) {
     // fp64 2-D grids: two GEMMs in a reduced basis (K1b) when the axis bases qualify, else the separable tables (K1g)
-    if (bilinear_applicable(c)) {
+    if (!req.exact && bilinear_applicable(c)) {
       int rc;
       // the first sweep of a model: interpolation from Chebyshev nodes (K1i, enqueued by sbo_model_set -- or here, when the grid
       // came after the model); K1b's plan is built when the same model is swept again
@@ -960,103 +979,81 @@ int launch_posterior(sbo_ctx* c) {
         if (!(c->bi.valid && c->bi.serial == c->model_serial) && (rc = interp_setup(c))) return rc;
         if (c->bi.usable && !c->bi.used) {
           c->last_k1 = 6;
-          return launch_posterior_gemm(c, true);
+          return launch_posterior_gemm(c, true, req, out);
         }
       }
       if (!c->bl.valid && (rc = bilinear_setup(c))) return rc;
       if (c->bl.usable) {
         c->last_k1 = 4;
-        return launch_posterior_gemm(c, false);    // (writes the Lipschitz keys itself)
+        return launch_posterior_gemm(c, false, req, out);    // (writes the Lipschitz keys itself)
       }
     }
     // fp64 grids of three / four axes: exact values at Chebyshev nodes, interpolated to the grid (K1t) when the plan qualifies
-    if (!c->tensor_busy && tensor_applicable(c)) {
+    if (!req.exact && tensor_applicable(c)) {
       bool declined = true;
-      const int rct = launch_posterior_tensor(c, &declined);
+      const int rct = launch_posterior_tensor(c, req, &declined);
       if (rct || !declined) return rct;
     }
     { const int rcf = factor_sync(c); if (rcf) return rcf; }     // (the O(n^2) kernels contract with the factor images)
-    SBO_HIP(hipMemsetAsync(c->Lmax.p, 0, sizeof(unsigned long long) * kMaxQ, c->stream));
+    SBO_HIP(hipMemsetAsync(t.Lmax, 0, sizeof(unsigned long long) * kMaxQ, c->stream));
     c->last_k1 = 3;
     c->last_k1_flops = tri_flops;
-    return c->dtype == SBO_F64 ? launch_posterior_grid<double>(c) : launch_posterior_grid<float>(c);
+    return c->dtype == SBO_F64 ? launch_posterior_grid<double>(c, t) : launch_posterior_grid<float>(c, t);
   }
-  // generic candidates: the single-phase kernel while the whole K* tile of 64 candidates fits LDS with two workgroups
-  // per CU, the chunked kernel beyond that (and on request: posterior_path 2)
   { const int rcf = factor_sync(c); if (rcf) return rcf; }
-  SBO_HIP(hipMemsetAsync(c->Lmax.p, 0, sizeof(unsigned long long) * kMaxQ, c->stream));
-  const size_t tile_bytes = (c->dtype == SBO_F64 ? 8u : 4u) * (size_t)c->mc.npad * 64;
   c->last_k1_flops = tri_flops;
-  c->last_k1 = (c->posterior_path == 2 || tile_bytes > 64 * 1024) ? 2 : 1;
-  if (c->posterior_path == 2 || tile_bytes > 64 * 1024)
-    return c->dtype == SBO_F64 ? launch_posterior_chunked<double>(c) : launch_posterior_chunked<float>(c);
-  return c->dtype == SBO_F64 ? launch_posterior_s<double>(c) : launch_posterior_s<float>(c);
+  c->last_k1 = generic_chunked(c) ? 2 : 1;
+  return launch_generic(c, t);
+}
+
+// the generic candidates' kernels on `t` (whoever launches for the resident posterior records last_k1 / last_k1_flops)
+static int launch_generic(sbo_ctx* c, const PostTarget& t) {
+  SBO_HIP(hipMemsetAsync(t.Lmax, 0, sizeof(unsigned long long) * kMaxQ, c->stream));
+  if (generic_chunked(c)) return c->dtype == SBO_F64 ? launch_posterior_chunked<double>(c, t) : launch_posterior_chunked<float>(c, t);
+  return c->dtype == SBO_F64 ? launch_posterior_s<double>(c, t) : launch_posterior_s<float>(c, t);
 }
 
 // K1g on a tensor grid with explicit axis positions (fp64 models; K1t's Chebyshev nodes), into caller-given arrays: mean / var
-// [q][N], signed gradient components of the mean [q][d][N], N = prod count, axis 0 fastest.  The context's candidate description
-// and posterior buffers are swapped for the call; `lmax` receives the Lipschitz keys of this point set.
+// [q][N], signed gradient components of the mean [q][d][N], N = prod count, axis 0 fastest; `lmax` receives the Lipschitz keys
+// of this point set.  The resident posterior and its records are not touched.
 int launch_posterior_on_axes(sbo_ctx* c, int d, const long long* count, const double* axc, double* mean_out, double* var_out, double* grad_out,
                              unsigned long long* lmax) {
   if (c->dtype != SBO_F64) return fail(SBO_E_UNSUPPORTED, "internal: explicit axes are an fp64 path");
   { const int rcf = factor_sync(c); if (rcf) return rcf; }
-  const CandSpec keep_cs = c->cs;
-  const DevBuf keep_m = c->mean, keep_v = c->var, keep_l = c->Lmax;
-  memset(&c->cs, 0, sizeof(c->cs));
-  c->cs.kind = 1;
-  c->cs.d = d;
+  PostTarget t{};
+  t.cs.kind = 1;
+  t.cs.d = d;
   long long N = 1;
-  for (int a = 0; a < d; ++a) { c->cs.count[a] = count[a]; N *= count[a]; }
-  for (int a = d; a < kMaxD; ++a) c->cs.count[a] = 1;
-  c->cs.n_local = N;
-  c->mean.p = mean_out;
-  c->var.p = var_out;
-  c->Lmax.p = lmax;
-  c->k1g_axc = axc;
-  c->k1g_grad = grad_out;
-  int rc = hipMemsetAsync(lmax, 0, sizeof(unsigned long long) * kMaxQ, c->stream) == hipSuccess ? SBO_OK : fail(SBO_E_HIP, "memset of the key scratch");
-  if (!rc) rc = launch_posterior_grid<double>(c);
-  c->k1g_axc = nullptr;
-  c->k1g_grad = nullptr;
-  c->cs = keep_cs;
-  c->mean = keep_m;
-  c->var = keep_v;
-  c->Lmax = keep_l;
-  return rc;
+  for (int a = 0; a < d; ++a) { t.cs.count[a] = count[a]; N *= count[a]; }
+  for (int a = d; a < kMaxD; ++a) t.cs.count[a] = 1;
+  t.cs.n_local = N;
+  t.mean = mean_out;
+  t.var = var_out;
+  t.Lmax = lmax;
+  t.axc = axc;
+  t.grad = grad_out;
+  SBO_HIP(hipMemsetAsync(lmax, 0, sizeof(unsigned long long) * kMaxQ, c->stream));
+  return launch_posterior_grid<double>(c, t);
 }
 
-// the exact posterior of the generic kernel on an explicit fp64 list, into caller-given arrays (the context's candidate
-// description and posterior buffers are swapped for the call; its plans and flags are left as they were)
+// the exact posterior of the generic kernel on an explicit fp64 list, into caller-given arrays.  The resident posterior and its
+// records (last_k1, last_k1_flops, gb_active: they describe what mean / var hold) are not touched.
 int launch_posterior_on_list(sbo_ctx* c, const double* pts, long long N, double* mean_out, double* var_out) {
   if (c->dtype != SBO_F64) return fail(SBO_E_UNSUPPORTED, "internal: exact lists are an fp64 path");
-  const CandSpec keep_cs = c->cs;
-  const DevBuf keep_m = c->mean, keep_v = c->var, keep_l = c->Lmax;
-  const int keep_k1 = c->last_k1;
-  const double keep_flops = c->last_k1_flops;
-  const bool keep_gb = c->gb_active, keep_busy = c->tensor_busy;
   int rc;
   if ((rc = ensure(c->list_scr, 512))) return rc;
-  memset(&c->cs, 0, sizeof(c->cs));
-  c->cs.kind = 0;
-  c->cs.d = keep_cs.d;
-  c->cs.pts_dtype = SBO_F64;
-  c->cs.pts = pts;
-  c->cs.n_local = N;
-  c->cs.first = 0;
-  c->mean.p = mean_out;
-  c->var.p = var_out;
-  c->Lmax.p = c->list_scr.p;                   // (the Lipschitz keys of the list are of no interest)
-  c->tensor_busy = true;                       // (launch_posterior must not come back to the tensor path)
-  rc = launch_posterior(c);
-  c->tensor_busy = keep_busy;
-  c->cs = keep_cs;
-  c->mean = keep_m;
-  c->var = keep_v;
-  c->Lmax = keep_l;
-  c->last_k1 = keep_k1;
-  c->last_k1_flops = keep_flops;
-  c->gb_active = keep_gb;
-  return rc;
+  PostTarget t{};
+  t.cs.kind = 0;
+  t.cs.d = c->cs.d;
+  t.cs.pts_dtype = SBO_F64;
+  t.cs.pts = pts;
+  t.cs.n_local = N;
+  t.cs.first = 0;
+  t.mean = mean_out;
+  t.var = var_out;
+  t.Lmax = (unsigned long long*)c->list_scr.p;   // (the Lipschitz keys of the list are of no interest)
+  { const int rcf = factor_sync(c); if (rcf) return rcf; }
+  return launch_generic(c, t);
 }
 
 int launch_bound(sbo_ctx* c, double b, int index, int kind, void* dev_out) {

@@ -16,8 +16,6 @@
 #include "device_common.hpp"
 #include "internal.hpp"
 
-extern "C" int sbo_posterior_enqueue(sbo_ctx* c);
-
 namespace sbo {
 
 int comm_allreduce_max_u64(sbo_ctx* c, unsigned long long* dev, int count);
@@ -386,15 +384,10 @@ int sweep_robust(sbo_ctx* c, const sbo_sweep_opts* o, int nca, int kind, sbo_rob
   SBO_HIP(hipEventRecord(c->ev[0], c->stream));
   c->host_syncs = 0;
   const bool reuse = o->posterior_ready && c->posterior_valid;
-  c->fuse_request = 0;                      // (no classification rides on this posterior; the lean options do not apply)
-  c->col_request = false;
-  c->col_lean = 0;
-  c->lmax_defer = false;
-  c->sweep_lean = 0;
-  if (!reuse && (rc = sbo_posterior_enqueue(c))) return rc;
-  if (!c->k1_stop_attached) SBO_HIP(hipEventRecord(c->ev[1], c->stream));
-  c->k1_stop_attached = false;
-  if (!reuse && (rc = guard_audit_enqueue(c, 0))) return rc;
+  PostOutcome out;                          // (a plain request: no classification rides on this posterior, the lean options do not apply)
+  if (!reuse && (rc = posterior_enqueue(c, PostRequest{}, &out))) return rc;
+  SBO_HIP(k1_stop(c, out));
+  if (!reuse && (rc = guard_audit_enqueue(c, out))) return rc;
   const GuardBand* gb = robust_gb(c);
   const int k1_first = c->last_k1;
   PhaseOut P{};
@@ -418,14 +411,9 @@ int sweep_robust(sbo_ctx* c, const sbo_sweep_opts* o, int nca, int kind, sbo_rob
   if (want[0]) {
     hipEvent_t g0 = c->ev[5], g1 = c->ev[6];
     SBO_HIP(hipEventRecord(g0, c->stream));
-    const int kb = c->bilinear, kt = c->tensor_cheb;
-    c->bilinear = 0;
-    c->tensor_cheb = 0;
-    rc = sbo_posterior_enqueue(c);
-    c->bilinear = kb;
-    c->tensor_cheb = kt;
-    if (rc) return rc;
-    c->k1_stop_attached = false;
+    PostRequest exact;
+    exact.exact = true;
+    if ((rc = posterior_enqueue(c, exact, &out))) return rc;
     c->last_k1 = k1_first;                  // (sbo_profile.posterior_kernel names the sweep's own posterior, as after the other sweeps' rechecks)
     if ((rc = robust_phase(c, o, kind, nc, nullptr, P))) return rc;
     SBO_HIP(hipEventRecord(g1, c->stream));

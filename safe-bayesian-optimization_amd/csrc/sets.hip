@@ -1074,9 +1074,18 @@ static int reduce_blocks(const sbo_ctx* c) {
   return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)c->n_cu * 4));   // (per-block reduction tails cost more than extra grid-stride turns: x4 measured best)
 }
 
-// mask buffers of a sweep; called before the posterior is enqueued (K1b may write S / U itself) -- `b` is the sweep's
-// confidence multiplier, handed to the posterior with the request to classify
-static int sweep_masks(sbo_ctx* c, double b, bool may_fuse) {
+// what a sweep asks of its posterior launch: K1b may classify in its mean epilogue at the sweep's confidence multiplier `b`, and
+// leaves its Lipschitz partials for the sweep (every sweep merges them in its k_classify_final)
+static PostRequest sweep_request(const sbo_ctx* c, double b, bool may_fuse) {
+  PostRequest req;
+  req.fuse = (may_fuse && c->mc.q >= 2) ? (c->fuse_classify < 0 ? 2 : c->fuse_classify) : 0;
+  req.fuse_b = b;
+  req.lmax_defer = may_fuse;
+  return req;
+}
+
+// mask buffers of a sweep; called before the posterior is enqueued (K1b may write S / U itself)
+static int sweep_masks(sbo_ctx* c, const PostRequest& req) {
   const long long n = c->cs.n_local;
   const int q = c->mc.q;
   int rc;
@@ -1089,14 +1098,9 @@ static int sweep_masks(sbo_ctx* c, double b, bool may_fuse) {
   if ((rc = ensure(c->maskG, (size_t)n * std::max(1, q - 1)))) return rc;
   c->masks_bits = false;
   c->col_G_bytes = false;
-  c->fuse_request = (may_fuse && q >= 2) ? (c->fuse_classify < 0 ? 2 : c->fuse_classify) : 0;
-  if (c->fuse_request && q > 2) {            // (one S / U byte plane per constraint: bilinear.hip, k_classify_and)
+  if (req.fuse && q > 2) {            // (one S / U byte plane per constraint: bilinear.hip, k_classify_and)
     if ((rc = ensure(c->fuseS, (size_t)n * (q - 1))) || (rc = ensure(c->fuseU, (size_t)n * (q - 1)))) return rc;
   }
-  c->lmax_defer = may_fuse;        // (every sweep merges K1b's Lipschitz partials in its k_classify_final)
-  c->lmax_pending = false;
-  c->fuse_b = b;
-  c->fuse_rows = 0;
   return SBO_OK;
 }
 
@@ -1116,10 +1120,11 @@ static void launch_final(sbo_ctx* c, FinalJob* fj) {
                         fj->nparts, fj->pcap, fj->q, fj->sc, fj->Lpart, fj->per_out, fj->Lmax, fj->sc_copy, fj->gb, fj->b);
 }
 
-// `defer`: the merge of the classification's partials is handed back instead of launched (SafeOpt on one rank: it rides in
-// the expander's first launch, which reads the U mask only)
+// `post`: what the sweep's posterior launch left (fused classification rows, Lipschitz partials to merge); `defer`: the merge of
+// the classification's partials is handed back instead of launched (SafeOpt on one rank: it rides in the expander's first
+// launch, which reads the U mask only)
 template <typename T>
-static int sweep_common_front(sbo_ctx* c, const sbo_sweep_opts* o, FinalJob* defer = nullptr) {
+static int sweep_common_front(sbo_ctx* c, const sbo_sweep_opts* o, const PostOutcome& post, FinalJob* defer = nullptr) {
   const long long n = c->cs.n_local;
   const int q = c->mc.q;
   int rc;
@@ -1137,16 +1142,15 @@ static int sweep_common_front(sbo_ctx* c, const sbo_sweep_opts* o, FinalJob* def
     if ((rc = ensure(c->lane1.scal, 4096))) return rc;
     fj.sc_copy = (SweepScalars*)c->lane1.scal.p;
   }
-  if (c->lmax_pending) {
+  if (post.lmax_pending) {
     fj.Lpart = (const double*)c->bl_lpart.p;
-    fj.per_out = c->lmax_per_out;
+    fj.per_out = post.lmax_per_out;
     fj.Lmax = (unsigned long long*)c->Lmax.p;
-    c->lmax_pending = false;
   }
   // four workgroups per CU measured best (2: 24.6 us, 4: 21.5, 8: 27.1 on config B's 4 M candidates; on config C's 1 M: 1024 /
   // 512 / 256 workgroups 0.1455 / 0.1463 / 0.1530 ms per sweep -- fewer is not better there either)
   int ncb = std::max(1, c->n_cu * 4);
-  if (c->fuse_rows > 0 && n > 0) {
+  if (post.fuse_rows > 0 && n > 0) {
     // S / U bytes, |S|, |U| and the radius key came out of the posterior kernel (which sized the row buffer: cpart_cap): only u*
     // is left, over the safe candidates
     const int nob = std::max(1, c->n_cu * 4);
@@ -1154,12 +1158,12 @@ static int sweep_common_front(sbo_ctx* c, const sbo_sweep_opts* o, FinalJob* def
     if (q > 2) {
       const PlaneAnd pa{(const uint8_t*)c->fuseS.p, (const uint8_t*)c->fuseU.p, n, q - 1, (uint8_t*)c->maskU.p};
       hipLaunchKernelGGL(k_classify_and<T>, dim3((unsigned)nob), dim3(256), 0, c->stream, (const T*)c->mean.p, (const T*)c->var.p, n, (T)o->b, pa,
-                         (uint8_t*)c->maskS.p, rows + c->fuse_rows, c->cpart_cap);
+                         (uint8_t*)c->maskS.p, rows + post.fuse_rows, c->cpart_cap);
     } else
     hipLaunchKernelGGL(k_classify_obj<T>, dim3((unsigned)nob), dim3(256), 0, c->stream, (const T*)c->mean.p, (const T*)c->var.p, n, (T)o->b,
-                       (const uint8_t*)c->maskS.p, rows + c->fuse_rows, c->cpart_cap);
+                       (const uint8_t*)c->maskS.p, rows + post.fuse_rows, c->cpart_cap);
     fj.part = (const unsigned long long*)rows;
-    fj.nparts = c->fuse_rows + nob;
+    fj.nparts = post.fuse_rows + nob;
     fj.pcap = c->cpart_cap;
     if (defer) *defer = fj;
     else launch_final(c, &fj);
@@ -1646,8 +1650,6 @@ static void coords_of(const sbo_ctx* c, long long gidx, double* x) {
   }
 }
 
-int sbo_posterior_enqueue_(sbo_ctx* c);
-
 // (ranks > 1) C1: global u*, L and radius keys; C2: every rank's U mask as bit words (one all-gather carries both)
 template <typename T>
 static int sweep_exchange_front(sbo_ctx* c, const sbo_sweep_opts* o, bool need_U) {
@@ -1826,34 +1828,25 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
   sweep_comm_reset(c);
   SBO_HIP(hipEventRecord(c->ev[0], c->stream));
   const bool reuse = o->posterior_ready && c->posterior_valid;
-  if ((rc = sweep_masks(c, o->b, !reuse))) return rc;
+  PostRequest req = sweep_request(c, o->b, !reuse);
   // column path (sets_colpath.inc.hpp): a fresh posterior of a one-constraint fp64 model on one rank may deliver the classification
-  // as column words (the GEMM posterior decides whether its launch qualifies: col_active)
-  c->col_request = !reuse && std::is_same<T, double>::value && q == 2 && !multi_rank(c) && !c->rc_active && c->result_mirror && n > 0;
+  // as column words (the GEMM posterior decides whether its launch qualifies: PostOutcome::col_active)
+  req.col = !reuse && std::is_same<T, double>::value && q == 2 && !multi_rank(c) && !c->rc_active && c->result_mirror && n > 0;
   const int lean = o->lean;
-  c->col_lean = c->col_request ? (lean >= 2 ? 2 : (lean ? 1 : 0)) : 0;
-  c->sweep_lean = (lean && q >= 2 && !reuse) ? 1 : 0;
-  // (the lean flag belongs to this sweep's posterior launches: a posterior run after it -- sbo_posterior_run, the guard's full
-  // re-evaluation -- computes every key again)
-  struct LeanEnd {
-    sbo_ctx* c;
-    ~LeanEnd() { c->sweep_lean = 0; }
-  } lean_end{c};
-  c->col_active = false;
-  if (!reuse && (rc = sbo_posterior_enqueue_(c))) { c->col_request = false; return rc; }
-  c->col_request = false;
-  c->fuse_request = 0;
-  c->lmax_defer = false;
-  if (!c->k1_stop_attached) SBO_HIP(hipEventRecord(c->ev[1], c->stream));
-  c->k1_stop_attached = false;
-  if (!reuse && !c->rc_active && (rc = guard_audit_enqueue(c, (c->col_active && c->col_lean) ? 1 : 0))) return rc;
+  req.col_lean = req.col ? (lean >= 2 ? 2 : (lean ? 1 : 0)) : 0;
+  req.sweep_lean = (lean && q >= 2 && !reuse) ? 1 : 0;
+  if ((rc = sweep_masks(c, req))) return rc;
+  PostOutcome post;
+  if (!reuse && (rc = posterior_enqueue(c, req, &post))) return rc;
+  SBO_HIP(k1_stop(c, post));
+  if (!reuse && !c->rc_active && (rc = guard_audit_enqueue(c, post))) return rc;
   SweepScalars h;
   unsigned long long Lk[kMaxQ];
-  const bool colpath = c->col_active;
+  const bool colpath = post.col_active;
   if (colpath) {
     // (a lean sweep left the objective's mean / var unwritten where no later stage reads them: whoever wants the posterior re-runs K1)
-    if (c->col_lean) c->posterior_valid = false;
-    if ((rc = col_set_phase(c, o, h, Lk))) return rc;
+    if (post.col_lean) c->posterior_valid = false;
+    if ((rc = col_set_phase(c, o, post, h, Lk))) return rc;
   } else {
   MinimizerJob mj;
   const int nb = reduce_blocks(c);
@@ -1870,7 +1863,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
   const bool lanes = lanes_on(c);
   {
     const bool defer = q >= 2 && !multi_rank(c) && c->set_fuse && n > 0 && !lanes;   // (lanes fork right behind the merge)
-    if ((rc = sweep_common_front<T>(c, o, defer ? &mj.fin : nullptr))) return rc;
+    if ((rc = sweep_common_front<T>(c, o, post, defer ? &mj.fin : nullptr))) return rc;
     if ((rc = sweep_exchange_front<T>(c, o, true))) return rc;
     // (single rank: the minimiser rides in the first constraint's k_set_mid; with ranks > 1 it is queued here, ahead of the
     // host's wait for the C1 keys)
@@ -2281,18 +2274,16 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_result* 
   sweep_comm_reset(c);
   SBO_HIP(hipEventRecord(c->ev[0], c->stream));
   const bool reuse = o->posterior_ready && c->posterior_valid;
-  if ((rc = sweep_masks(c, o->b, !reuse))) return rc;
-  c->sweep_lean = 0;
-  if (!reuse && (rc = sbo_posterior_enqueue_(c))) return rc;
-  c->fuse_request = 0;
-  c->lmax_defer = false;
-  if (!c->k1_stop_attached) SBO_HIP(hipEventRecord(c->ev[1], c->stream));
-  c->k1_stop_attached = false;
-  if (!reuse && !c->rc_active && (rc = guard_audit_enqueue(c, 0))) return rc;
+  const PostRequest req = sweep_request(c, o->b, !reuse);
+  if ((rc = sweep_masks(c, req))) return rc;
+  PostOutcome post;
+  if (!reuse && (rc = posterior_enqueue(c, req, &post))) return rc;
+  SBO_HIP(k1_stop(c, post));
+  if (!reuse && !c->rc_active && (rc = guard_audit_enqueue(c, post))) return rc;
   const int nb = reduce_blocks(c);
   const bool lanes = lanes_on(c);
   {
-    if ((rc = sweep_common_front<T>(c, o, nullptr))) return rc;
+    if ((rc = sweep_common_front<T>(c, o, post, nullptr))) return rc;
     if ((rc = sweep_exchange_front<T>(c, o, true))) return rc;
     if ((rc = ensure(c->maskO, (size_t)std::max<long long>(n, 1) * std::max(1, q - 1)))) return rc;
     if (c->phase_events) SBO_HIP(hipEventRecord(c->ev[2], c->stream));
@@ -2328,7 +2319,6 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_result* 
   if (n > 0)
     hipLaunchKernelGGL((k_arg_masked_multi<T, false, ValLcb<T>>), dim3((unsigned)nb, (unsigned)q), dim3(256), 0, c->stream, lcb0,
                        (const uint8_t*)c->maskS.p, (const uint8_t*)c->maskO.p, n, (long long)c->cs.first, pbase, pstride, 0, gb_of(c));
-  c->lmax_pending = false;
   SweepScalars h;
   bool is_max[kArgSlots];
   for (int t = 0; t < kArgSlots; ++t) is_max[t] = false;
@@ -2477,15 +2467,13 @@ static int sweep_tr_t(sbo_ctx* c, const sbo_sweep_opts* o, const double* x0, dou
   int rc;
   SBO_HIP(hipEventRecord(c->ev[0], c->stream));
   const bool reuse = o->posterior_ready && c->posterior_valid;
-  if ((rc = sweep_masks(c, o->b, !reuse))) return rc;
-  c->sweep_lean = 0;
-  if (!reuse && (rc = sbo_posterior_enqueue_(c))) return rc;
-  c->fuse_request = 0;
-  c->lmax_defer = false;
-  if (!c->k1_stop_attached) SBO_HIP(hipEventRecord(c->ev[1], c->stream));
-  c->k1_stop_attached = false;
-  if (!reuse && !c->rc_active && (rc = guard_audit_enqueue(c, 0))) return rc;
-  if ((rc = sweep_common_front<T>(c, o))) return rc;
+  const PostRequest req = sweep_request(c, o->b, !reuse);
+  if ((rc = sweep_masks(c, req))) return rc;
+  PostOutcome post;
+  if (!reuse && (rc = posterior_enqueue(c, req, &post))) return rc;
+  SBO_HIP(k1_stop(c, post));
+  if (!reuse && !c->rc_active && (rc = guard_audit_enqueue(c, post))) return rc;
+  if ((rc = sweep_common_front<T>(c, o, post))) return rc;
   SweepScalars* sc = (SweepScalars*)c->scal.p;
   const int nb = reduce_blocks(c);
   double* dev_x0 = (double*)c->scal.p + 256;
@@ -2575,14 +2563,6 @@ int robust_argmin(sbo_ctx* c, const double* f, const double* fb, const uint8_t* 
 }  // namespace sbo
 
 using namespace sbo;
-
-extern "C" {
-
-int sbo_posterior_enqueue(sbo_ctx* c);
-}
-namespace sbo {
-int sbo_posterior_enqueue_(sbo_ctx* c) { return sbo_posterior_enqueue(c); }
-}
 
 extern "C" {
 

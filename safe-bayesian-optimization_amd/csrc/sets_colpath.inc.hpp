@@ -996,14 +996,14 @@ static void col_expand(sbo_ctx* c, const DevBuf& words, uint8_t* out) {
                      (const unsigned long long*)words.p, (int)c->cs.count[0], n, out);
 }
 
-// ---- host: the set phase behind a posterior launch that delivered column words (sbo_ctx::col_active) -------------------------------
+// ---- host: the set phase behind a posterior launch that delivered column words (PostOutcome::col_active) ---------------------------
 // Two chains (option "col_overlap", default on).  The EXPANDER chain needs the constraint's posterior only -- S / U words, the radius
 // and Lipschitz keys of the constraint --, so it runs on the high-priority stream3 behind the constraint's k_bpost launch (fork event
 // carried by that launch) WHILE the objective's k_bpost launch runs on the main stream: k_col_a, k_col_cs, k_col_decide, k_col_scan are
 // latency-bound kernels whose waiting the matrix kernel fills.  The OBJECTIVE chain follows its own launch on the main stream: u*
 // merged by every workgroup of k_col_min, M and its arg-max; the main stream then waits for the chain's join event and k_col_finals
 // merges both.  What the set phase adds to K1 is the minimiser, the join and the finals.
-static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, SweepScalars& h, unsigned long long* Lk) {
+static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const PostOutcome& post, SweepScalars& h, unsigned long long* Lk) {
   const long long n = c->cs.n_local;
   const int q = c->mc.q;                 // == 2
   int rc;
@@ -1034,7 +1034,7 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, SweepScalars& h, u
   ColScal2* sc2 = (ColScal2*)c->col_fin.p;
   unsigned long long* tickets = (unsigned long long*)((char*)c->col_fin.p + 64);
   ColFinRow* fin = (ColFinRow*)((char*)c->col_fin.p + 128);
-  const bool overlap = c->col_overlap && c->stream3 && c->col_forked;
+  const bool overlap = c->col_overlap && c->stream3 && post.col_forked;
   hipStream_t xs = c->stream, es = overlap ? c->stream3 : c->stream;      // objective chain / expander chain
   if (fresh_fin) SBO_HIP(hipMemsetAsync(c->col_fin.p, 0, 4096, es));       // (tickets: the last workgroup of a slot resets its own)
   const int nb = reduce_blocks(c);
@@ -1061,8 +1061,7 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, SweepScalars& h, u
     c->col_ckey = (long long)gm.W << 32 | gm.H;
   }
   ColBits cb{(unsigned long long*)c->cbS.p, (unsigned long long*)c->cbU.p, (unsigned long long*)c->cbUsum.p, (unsigned long long*)c->col_slots.p};
-  c->lmax_pending = false;        // (the Lipschitz keys come out of the slot block)
-  c->col_forked = false;
+  // (the Lipschitz keys come out of the slot block: the posterior's partial rows are not merged)
 
   // ---- expander chain
   if (overlap) SBO_HIP(hipStreamWaitEvent(es, c->ev_col[0], 0));
@@ -1101,7 +1100,7 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, SweepScalars& h, u
   // (grids sized to be resident at once: the waves loop over the units of the tiles with a safe candidate)
   const int ndw = std::max(1, c->n_cu * 4);
   const unsigned long long* rows = (const unsigned long long*)c->cpart.p;        // the posterior's partial rows: constraint tiles, then objective tiles
-  const int ntiles = c->fuse_rows / 2;
+  const int ntiles = post.fuse_rows / 2;
   hipLaunchKernelGGL(k_col_decide, dim3((unsigned)ndw), dim3(256), 0, es, gm, (const unsigned long long*)cb.Sw, (const unsigned long long*)cb.slots,
                      rows, rows + (size_t)(kRowRmax + 1) * c->cpart_cap, (const unsigned short*)c->col_cimg.p, (const unsigned short*)c->col_cbmin.p,
                      2.0 * gm.delta + 2.0 * kCoarse * hmax, cb.Usum, (const unsigned short*)c->col_img.p, cv, sc, (unsigned long long*)c->cbG.p, (long long*)c->scanlist.p);

@@ -295,7 +295,8 @@ static int rc_refine(sbo_ctx* c, const long long* list, long long nf, bool guard
   s->posterior_path = 0;
   if ((rc = ensure(s->mean, sizeof(double) * (size_t)nf * q))) return rc;
   if ((rc = ensure(s->var, sizeof(double) * (size_t)nf * q))) return rc;
-  if ((rc = launch_posterior(s))) return rc;
+  PostOutcome none;
+  if ((rc = launch_posterior(s, PostRequest{}, none))) return rc;
   hipLaunchKernelGGL(k_rc_scatter, dim3(nbf), dim3(256), 0, c->stream, list, nf, q, n, (const double*)s->mean.p, (const double*)s->var.p,
                      (double*)c->rc_mean.p, (double*)c->rc_var.p, (uint8_t*)c->rc_refined.p);
   SBO_HIP(hipGetLastError());
@@ -356,8 +357,7 @@ static int sweep_safeopt_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeop
   SBO_HIP(hipEventRecord(c->ev_join[0], c->stream));
   // (guard: the posterior is resident -- unless the first pass was a lean sweep, which left part of it unwritten: K1 once more, in full)
   const bool reuse = (kGuard && c->posterior_valid) || (o->posterior_ready && c->posterior_valid);
-  if (!reuse && (rc = sbo_posterior_enqueue_(c))) return rc;
-  c->k1_stop_attached = false;
+  if (!reuse && (rc = posterior_enqueue(c, PostRequest{}, nullptr))) return rc;
   SBO_HIP(hipEventRecord(c->ev_join[1], c->stream));
   RcBand bd;
   if ((rc = rc_bands(c, kGuard, bd))) return rc;
@@ -578,8 +578,7 @@ static int rc_front_all(sbo_ctx* c, const sbo_sweep_opts* o, RcBand& bd, long lo
   const int q = c->mc.q;
   int rc;
   const bool reuse = kGuard || (o->posterior_ready && c->posterior_valid);
-  if (!reuse && (rc = sbo_posterior_enqueue_(c))) return rc;
-  c->k1_stop_attached = false;
+  if (!reuse && (rc = posterior_enqueue(c, PostRequest{}, nullptr))) return rc;
   if ((rc = rc_bands(c, kGuard, bd))) return rc;
   if ((rc = ensure(c->rc_list, kRcList + sizeof(long long) * (size_t)std::max<long long>(n, 1) * 2))) return rc;
   if (!kGuard) {

@@ -510,10 +510,11 @@ static int launch_final(sbo_ctx* c, const double* in, size_t stride_q, const Ten
 }
 
 // all `nq` stacked node tensors (stride Nn: q means, q variances, q d gradient components) to the grid
-static int interpolate(sbo_ctx* c, const TensorDims& td, const double* nodes, long long Nn, int nq, const double** cur_out, size_t* stride_out) {
+static int interpolate(sbo_ctx* c, const TensorDims& td, const double* nodes, long long Nn, int nq, int sweep_lean, const double** cur_out,
+                       size_t* stride_out) {
   const int d = td.d;
   int rc;
-  const int gskip = (c->sweep_lean && td.q >= 2) ? d : 0;      // (a lean sweep: nobody reads L_0)
+  const int gskip = (sweep_lean && td.q >= 2) ? d : 0;      // (a lean sweep: nobody reads L_0)
   // axes d-1 .. 2 on the small tensors (ping-pong in tn_work), then the planes
   const double* cur = nodes;
   size_t cur_stride = (size_t)Nn;
@@ -551,7 +552,7 @@ static int interpolate(sbo_ctx* c, const TensorDims& td, const double* nodes, lo
 }
 
 // SBO_OK with *declined = true: the plan does not qualify (K1g runs)
-int launch_posterior_tensor(sbo_ctx* c, bool* declined) {
+int launch_posterior_tensor(sbo_ctx* c, const PostRequest& req, bool* declined) {
   *declined = true;
   const ModelConst& mc = c->mc;
   const CandSpec& cs = c->cs;
@@ -680,7 +681,7 @@ int launch_posterior_tensor(sbo_ctx* c, bool* declined) {
     c->tn_flops = 0.0;
     const double* cur = nullptr;
     size_t cur_stride = 0;
-    if ((rc = interpolate(c, td, nmean, Nn, 2 * q + nqg, &cur, &cur_stride))) return rc;
+    if ((rc = interpolate(c, td, nmean, Nn, 2 * q + nqg, req.sweep_lean, &cur, &cur_stride))) return rc;
     if (!same_grid) {
       // accuracy probe: 2048 grid points, exact against interpolated
       std::vector<long long> idx(kTProbes);
@@ -744,7 +745,7 @@ int launch_posterior_tensor(sbo_ctx* c, bool* declined) {
           av[o] = std::max(av[o], std::fabs(xv));
         }
         for (int a = 0; a < d; ++a)
-          for (int i = 0; i < kTProbes && !(o == 0 && c->sweep_lean && q >= 2); ++i) {      // (lean: output 0's gradient cores were not made)
+          for (int i = 0; i < kTProbes && !(o == 0 && req.sweep_lean && q >= 2); ++i) {      // (lean: output 0's gradient cores were not made)
             const double dg = std::fabs(h[((size_t)4 * q + nqg + (size_t)o * d + a) * kTProbes + i] - h[((size_t)4 * q + (size_t)o * d + a) * kTProbes + i]);
             finite = finite && std::isfinite(dg);
             eg[o] = std::max(eg[o], dg);
