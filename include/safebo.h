@@ -219,6 +219,12 @@ typedef struct sbo_profile {
   /* of guard_audit_samples: samples on such tiles, where the audit checks the reference values against the tile's enclosure (widened
    * by the band) instead of the stored ones.  Cumulative, as guard_audit_samples.                                                    */
   int64_t guard_audit_skipped;
+  /* Spatial index of an explicit list (option "list_index"; zero when the last sweep did not use it): device time of building its
+   * sorted order (Morton keys, radix sort, sorted copy of the points) when the last sweep built it, 0 when it reused it; the
+   * (candidate, U point) pairs the expander walk evaluated at its leaves, and the nodes whose box it skipped, summed over the
+   * constraints.  GoOSE's coverage search on the sorted order does not count pairs.                                                */
+  double list_index_build_ms;
+  int64_t list_index_leaf_pairs, list_index_nodes_skipped;
 } sbo_profile;
 
 /* ---- library / context ------------------------------------------------------------------- */
@@ -403,6 +409,10 @@ int sbo_profile_get(sbo_ctx* ctx, sbo_profile* out);
  *   "guard_audit_scale_ppm" test hook: the audit compares against the band x value / 1e6 (default 1000000); setting it clears the counts
  *   "guard_audit_every" one sweep in this many carries an audit (default 16; the first sweep after setting it does).  An audit shares
  *                      the card with the sweep it follows (~35 us of config H's set phase at 1024 samples, n = 512): 1 audits every sweep
+ *   "list_index"       explicit candidate lists: expander sets (SafeOpt, GoOSE's source filter) and GoOSE's coverage search on a spatial
+ *                      index of the list (Morton order, boxes of the U members; verdicts identical to the exhaustive ones).  -1 (default):
+ *                      only for lists above 2097152 candidates, where the exhaustive expander sets are refused; 1: at any size (A/B checker);
+ *                      0: never (lists above the cap: SBO_E_UNSUPPORTED for expander sets).  One rank only
  *   "guard_band"       1: sweeps on an approximating posterior (K1b / K1i / K1t) count the decisions inside its band and re-evaluate exactly
  *                      when there are any; 0: masks of the approximating posterior as they come; 2: the re-evaluation on every sweep (test) */
 int sbo_set_option(sbo_ctx* ctx, const char* key, int64_t value);

@@ -4,7 +4,8 @@
     x_target, target_lcb     = GP_m.Target()                   # argmin over the optimistic sets   :80-114
     x_new                    = GP_m.explore_safeset(x_target)  # argmin_{S_t} ||x - target||_2     :116-119
 
-all three read one device sweep of the candidate grid (cached until the model changes).
+all three read one device sweep of the candidate grid, or of ``candidates=`` (an [N, d] array of scattered points, as for
+SafeOpt.BO), cached until the model changes.
 """
 from __future__ import annotations
 
@@ -15,9 +16,10 @@ from .SafeOpt import BO as _SafeOptBO
 
 class BO(_SafeOptBO):
     def __init__(self, plant_system, bound, b, grid=None, device: int = 0, dtype: str = "f64",
-                 reference_quirk_L_index: bool = True, seed: int = 42):
+                 reference_quirk_L_index: bool = True, seed: int = 42, candidates=None, list_index: int | None = None):
         _SafeOptBO.__init__(self, plant_system, bound, b, grid=grid, device=device, dtype=dtype,
-                            reference_quirk_L_index=reference_quirk_L_index, seed=seed)
+                            reference_quirk_L_index=reference_quirk_L_index, seed=seed, candidates=candidates,
+                            list_index=list_index)
         self._goose_cache = None
 
     def goose_sweep(self, want_masks: bool = False) -> dict:
@@ -36,7 +38,7 @@ class BO(_SafeOptBO):
     def Target(self):
         res = self.goose_sweep()
         if res["target_index"] < 0:      # no optimistic point on this grid
-            return np.full(len(self.grid), np.nan), np.inf
+            return np.full(self.bound.shape[0], np.nan), np.inf
         return res["target_x"], res["target_lcb"]
 
     def explore_safeset(self, target):

@@ -6,6 +6,7 @@ evaluated on a candidate grid over ``bound`` by one device sweep (SURVEY.md Appe
 reference's method names and return conventions so ``test/test_SafeOpt.py``-style drivers run unchanged:
 
     GP_m = SafeOpt.BO(plant_system, bound, b)                 # + grid=(n0, n1, ..) candidates per axis
+                                                              #   or candidates=pts, an [N, d] array of scattered points
     minimizer, std_minimizer = GP_m.Minimizer()
     expander, std_expander = GP_m.Expander()
 
@@ -21,13 +22,26 @@ from .GP_Safe import GP
 
 class BO(GP):
     def __init__(self, plant_system, bound, b, grid=None, device: int = 0, dtype: str = "f64",
-                 reference_quirk_L_index: bool = True, seed: int = 42):
+                 reference_quirk_L_index: bool = True, seed: int = 42, candidates=None, list_index: int | None = None):
         GP.__init__(self, plant_system, device=device, dtype=dtype, seed=seed)
         self.bound = np.asarray(bound, dtype=np.float64)
         self.b = b
         d = self.bound.shape[0]
+        if grid is not None and candidates is not None:
+            raise ValueError("pass either grid= or candidates=, not both")
+        # scattered candidates [N, d] (for d >= 5 a tensor grid cannot resolve the box): masks are flat, in the caller's order, and
+        # Minimizer / Expander / Target / explore_safeset return rows of them.  Lists above 2^21 points take the spatial index of
+        # the list (engine option "list_index", passed through when given here).
+        self.candidates = None
+        if candidates is not None:
+            pts = np.asarray(candidates)
+            pts = np.ascontiguousarray(pts if pts.dtype == np.float32 else pts.astype(np.float64))
+            if pts.ndim != 2 or pts.shape[1] != d or pts.shape[0] < 1:
+                raise ValueError(f"candidates must be [N, {d}]")
+            self.candidates = pts
+        self.list_index = list_index
         # candidate grid over the box; default = the 400 points per axis of create_data_for_plot (test_SafeOpt.py:325)
-        self.grid = tuple(int(g) for g in (grid if grid is not None else (400,) * d))
+        self.grid = None if self.candidates is not None else tuple(int(g) for g in (grid if grid is not None else (400,) * d))
         self.reference_quirk_L_index = reference_quirk_L_index
         self._sweep_cache = None      # (model_version, result dict)
         self._cand_token = None
@@ -63,9 +77,14 @@ class BO(GP):
     # ---- the sweep ----------------------------------------------------------------------------------------------
     def _grid_resident(self):
         self._sync_model()
+        if self.list_index is not None:
+            self.engine.set_option("list_index", int(self.list_index))
         token = (self._model_version, self.grid)
         if self._cand_token != token:
-            self.engine.set_grid(self.bound[:, 0], self.bound[:, 1], self.grid)
+            if self.candidates is not None:
+                self.engine.set_points(self.candidates)
+            else:
+                self.engine.set_grid(self.bound[:, 0], self.bound[:, 1], self.grid)
             self._cand_token = token
 
     def sweep(self, want_masks: bool = False) -> dict:
@@ -78,9 +97,10 @@ class BO(GP):
         return res
 
     def masks(self) -> dict:
-        """S / U / M / G_c masks of the current model, reshaped to the grid (axis 0 fastest -> last array axis)."""
+        """S / U / M / G_c masks of the current model, reshaped to the grid (axis 0 fastest -> last array axis); flat, in the
+        caller's order, with ``candidates=``."""
         self.sweep(want_masks=True)
-        shape = self.grid[::-1]
+        shape = self.grid[::-1] if self.candidates is None else (self.candidates.shape[0],)
         out = {k: self.engine.mask(k).reshape(shape) for k in ("S", "U", "M")}
         for c in range(1, self.n_fun):
             out[f"G{c}"] = self.engine.mask("G", c).reshape(shape)
@@ -130,6 +150,8 @@ class BO(GP):
 
     # ---- helpers ----------------------------------------------------------------------------------------------------
     def _grid_point(self, g: int):
+        if self.candidates is not None:
+            return self.candidates[g].astype(np.float64)
         x = np.empty(len(self.grid))
         for a, cnt in enumerate(self.grid):
             i = g % cnt

@@ -46,6 +46,22 @@ struct DevBuf {
   size_t bytes = 0;
 };
 
+// Spatial index of an explicit candidate list (sets_index.inc.hpp): Morton order of the points, built at the first sweep that
+// needs it and kept until the candidates change (option "list_index")
+struct ListIndex {
+  bool valid = false;
+  bool built_now = false;        // built by the running sweep (its time goes into sbo_profile.list_index_build_ms)
+  bool ran = false;              // the running sweep walked the index (its counters go into sbo_profile)
+  long long n = 0;
+  int d = 0;
+  int perm_half = 0;             // which half of `vals` holds the sorted permutation
+  DevBuf box;                    // bounding box (ord keys), kIdxBoxHead words
+  DevBuf keys, vals, hist;       // radix sort: keys / values twice (ping-pong), per-tile digit counts
+  DevBuf xs;                     // sorted coordinates, fp64 [n][d]
+  DevBuf stats;                  // walk counters of the running sweep: leaf pairs, nodes skipped
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+
 // Column-word form of the masks of a 2-D grid (r05): word [s][i] holds the bits of column i (axis 0) for the 64 rows
 // 64 s .. 64 s + 63 of axis 1 -- exactly what one 64 x 128 tile of the GEMM posterior (k_bpost) knows about a column, so the
 // constraint's mean epilogue emits the S / U words itself (128 coalesced 8-byte stores per tile instead of 16384 byte
@@ -271,13 +287,16 @@ struct sbo_ctx {
   // (the chains only write its recheck / scan counters).  The host swaps these in and out of the fields above around the
   // calls that enqueue a lane-1 constraint (sets.hip: lane_swap).
   struct SetLane {
-    sbo::DevBuf dist2, dist2b, coarse, blockmin, blockmax, scanlist, amb, gw, runmeta, scal;
+    sbo::DevBuf dist2, dist2b, coarse, blockmin, blockmax, scanlist, amb, gw, runmeta, scal, lxtree;
     bool amb_clean = false;
   } lane1;
   int set_lanes = 1;       // 0: all constraints on the main stream, one after the other
   sbo::DevBuf partial; // arg-reduce per-block partials
   sbo::DevBuf amb;     // ambiguous-index list for the exact recheck
   sbo::DevBuf runmeta; // GoOSE: per-run bounding boxes / radii of the coverage search
+  sbo::ListIndex lx;    // spatial index of an explicit list (sets_index.inc.hpp)
+  sbo::DevBuf lxtree;   // ... this sweep's boxes of U members / sorted U mask, or GoOSE's sorted weights and masks (per lane)
+  int list_index = -1;  // option: -1 the index for explicit lists above the exhaustive cap only, 0 never, 1 always
   sbo::DevBuf scanlist; // candidates left open by the coarse expander decision (wave-per-candidate scan)
   sbo::DevBuf blockmax; // per-block largest source weight along axis 0 (blocked axis-0 pass of the power transform)
   sbo::DevBuf blockmin; // per-block minima along the last axis (blocked last-axis scans)

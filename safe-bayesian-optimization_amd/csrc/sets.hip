@@ -999,6 +999,7 @@ __global__ __launch_bounds__(256) void k_set_mid(const MidJobs<T> j) {
 
 #include "sets_exchange.inc.hpp"
 #include "sets_goose.inc.hpp"
+#include "sets_index.inc.hpp"
 
 // Tail of a single-rank GoOSE sweep, two launches instead of four and no copy behind them (r03):
 // k_goose_finals = k_sweep_finals<false> (a workgroup per slot) whose last workgroup to finish also does k_pick_target's job;
@@ -1307,6 +1308,7 @@ static void lane_swap(sbo_ctx* c) {
   std::swap(c->runmeta, l.runmeta);
   std::swap(c->scal, l.scal);
   std::swap(c->amb_clean, l.amb_clean);
+  std::swap(c->lxtree, l.lxtree);
 }
 // after the classification's scalars are final on the main stream: lane 1 waits for them and takes its copy of the block
 // after the classification's scalars are final on the main stream (k_classify_final has written lane 1's snapshot of them)
@@ -1328,6 +1330,163 @@ struct LaneScope {          // enqueue-time view of lane 1 (odd lanes swap the c
 };
 
 constexpr long long kListExpanderMax = 1ll << 21;     // explicit lists: largest candidate set with exhaustive expander sets
+
+// ---- spatial index of explicit lists (sets_index.inc.hpp) ----------------------------------------------------------------
+// option list_index: -1 (default) only where the exhaustive expander sets refuse the list (above kListExpanderMax), 1 always, 0 never
+static bool list_index_on(const sbo_ctx* c) {
+  if (c->cs.kind != 0 || multi_rank(c) || c->cs.n_local <= 0 || c->list_index == 0) return false;
+  return c->list_index == 1 || c->cs.n_local > kListExpanderMax;
+}
+static int idx_dpad(int d) { return d <= 2 ? 2 : (d <= 4 ? 4 : 8); }
+
+template <int D>
+static void list_index_sort_d(sbo_ctx* c, unsigned long long* k0, unsigned* v0, unsigned long long* k1, unsigned* v1, int ntiles) {
+  ListIndex& x = c->lx;
+  const long long n = c->cs.n_local;
+  const unsigned nb = (unsigned)std::min<long long>((n + 255) / 256, (long long)c->n_cu * 16);
+  unsigned long long* box = (unsigned long long*)x.box.p;
+  unsigned* hist = (unsigned*)x.hist.p;
+  unsigned* dtot = hist + (size_t)256 * ntiles;
+  hipLaunchKernelGGL(k_idx_box_init, dim3(1), dim3(64), 0, c->stream, box);
+  hipLaunchKernelGGL((k_idx_box<D>), dim3(nb), dim3(256), 0, c->stream, c->cs, box);
+  hipLaunchKernelGGL((k_idx_keys<D>), dim3(nb), dim3(256), 0, c->stream, c->cs, (const unsigned long long*)box, k0, v0);
+  const int passes = (idx_bits_per_axis(c->cs.d) * c->cs.d + 7) / 8;
+  for (int p = 0; p < passes; ++p) {
+    hipLaunchKernelGGL(k_idx_hist, dim3((unsigned)ntiles), dim3(256), 0, c->stream, (const unsigned long long*)k0, n, 8 * p, hist, ntiles);
+    hipLaunchKernelGGL(k_idx_scan_rows, dim3(256), dim3(256), 0, c->stream, hist, ntiles, dtot);
+    hipLaunchKernelGGL(k_idx_scatter, dim3((unsigned)ntiles), dim3(256), 0, c->stream, (const unsigned long long*)k0, (const unsigned*)v0, k1, v1,
+                       n, 8 * p, (const unsigned*)hist, (const unsigned*)dtot, ntiles);
+    std::swap(k0, k1);
+    std::swap(v0, v1);
+  }
+  x.perm_half = v0 == (unsigned*)x.vals.p ? 0 : 1;
+  hipLaunchKernelGGL((k_idx_sorted_coords<D>), dim3(nb), dim3(256), 0, c->stream, c->cs, (const unsigned*)v0, (double*)x.xs.p);
+}
+
+// at the start of a sweep that walks the index: the sorted order (once per list, on the main stream ahead of both lanes) and
+// cleared walk counters
+static int list_index_prepare(sbo_ctx* c) {
+  ListIndex& x = c->lx;
+  x.built_now = x.ran = false;
+  if (!list_index_on(c)) return SBO_OK;
+  const long long n = c->cs.n_local;
+  if (n > 0x7fffffffll - kSortTile) return fail(SBO_E_UNSUPPORTED, "the list index holds at most 2147479551 candidates");
+  int rc;
+  if ((rc = ensure(x.stats, 64))) return rc;
+  SBO_HIP(hipMemsetAsync(x.stats.p, 0, 2 * sizeof(unsigned long long), c->stream));
+  if (x.valid && x.n == n && x.d == c->cs.d) return SBO_OK;
+  x.valid = false;
+  const int ntiles = (int)((n + kSortTile - 1) / kSortTile);
+  if ((rc = ensure(x.box, sizeof(unsigned long long) * kIdxBoxHead))) return rc;
+  if ((rc = ensure(x.keys, 2 * sizeof(unsigned long long) * (size_t)n))) return rc;
+  if ((rc = ensure(x.vals, 2 * sizeof(unsigned) * (size_t)n))) return rc;
+  if ((rc = ensure(x.hist, sizeof(unsigned) * ((size_t)256 * ntiles + 256)))) return rc;
+  if ((rc = ensure(x.xs, sizeof(double) * (size_t)n * c->cs.d))) return rc;
+  if (!x.ev0) SBO_HIP(hipEventCreate(&x.ev0));
+  if (!x.ev1) SBO_HIP(hipEventCreate(&x.ev1));
+  SBO_HIP(hipEventRecord(x.ev0, c->stream));
+  unsigned long long* k0 = (unsigned long long*)x.keys.p;
+  unsigned* v0 = (unsigned*)x.vals.p;
+  switch (idx_dpad(c->cs.d)) {
+    case 2: list_index_sort_d<2>(c, k0, v0, k0 + n, v0 + n, ntiles); break;
+    case 4: list_index_sort_d<4>(c, k0, v0, k0 + n, v0 + n, ntiles); break;
+    default: list_index_sort_d<8>(c, k0, v0, k0 + n, v0 + n, ntiles); break;
+  }
+  SBO_HIP(hipGetLastError());
+  SBO_HIP(hipEventRecord(x.ev1, c->stream));
+  x.valid = true;
+  x.built_now = true;
+  x.n = n;
+  x.d = c->cs.d;
+  return SBO_OK;
+}
+
+// after the sweep has completed: build time and walk counters into the profile
+static int list_index_profile(sbo_ctx* c) {
+  ListIndex& x = c->lx;
+  c->prof.list_index_build_ms = 0.0;
+  c->prof.list_index_leaf_pairs = c->prof.list_index_nodes_skipped = 0;
+  if (x.built_now) {
+    float ms = 0.f;
+    SBO_HIP(hipEventElapsedTime(&ms, x.ev0, x.ev1));
+    c->prof.list_index_build_ms = ms;
+  }
+  if (x.ran) {
+    unsigned long long st[2] = {0, 0};
+    SBO_HIP(hipMemcpy(st, x.stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    c->prof.list_index_leaf_pairs = (int64_t)st[0];
+    c->prof.list_index_nodes_skipped = (int64_t)st[1];
+  }
+  x.built_now = x.ran = false;
+  return SBO_OK;
+}
+
+// layout of this sweep's hierarchy in the lane's lxtree buffer: [sorted U mask][nodes of levels 0 .. nlev - 1]
+static int list_index_tree(sbo_ctx* c, int D, IdxTree* t) {
+  const long long n = c->cs.n_local;
+  memset(t, 0, sizeof(*t));
+  t->n = n;
+  t->d = c->cs.d;
+  long long cnt = (n + kIdxLeaf - 1) / kIdxLeaf, off = 0;
+  int lev = 0;
+  for (;;) {
+    if (lev >= kIdxMaxLevels) return fail(SBO_E_UNSUPPORTED, "list index: too many levels");
+    t->cnt[lev] = cnt;
+    t->off[lev] = off;
+    off += cnt;
+    ++lev;
+    if (cnt <= kIdxFan) break;
+    cnt = (cnt + kIdxFan - 1) / kIdxFan;
+  }
+  t->nlev = lev;
+  const size_t ub = ((size_t)n + 255) / 256 * 256;
+  int rc;
+  if ((rc = ensure(c->lxtree, ub + sizeof(double) * 2 * D * (size_t)off))) return rc;
+  t->Us = (uint8_t*)c->lxtree.p;
+  t->nodes = (double*)((char*)c->lxtree.p + ub);
+  t->perm = (const unsigned*)c->lx.vals.p + (size_t)c->lx.perm_half * n;
+  t->xs = (const double*)c->lx.xs.p;
+  t->box = (const unsigned long long*)c->lx.box.p;
+  t->stats = (unsigned long long*)c->lx.stats.p;
+  return SBO_OK;
+}
+
+// G_c of an explicit list on the index: boxes of this sweep's U members, then the walk (in-band verdicts of a guard band go to
+// amb, for k_expander_exact behind it)
+template <typename T, int D>
+static int list_index_expander(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, int lidx, uint8_t* G) {
+  if (!c->lx.valid) return fail(SBO_E_INVALID, "list index not built for this sweep");
+  const long long n = c->cs.n_local;
+  IdxTree t;
+  int rc;
+  if ((rc = list_index_tree(c, D, &t))) return rc;
+  SBO_HIP(hipMemsetAsync(G, 0, (size_t)n, c->stream));
+  hipLaunchKernelGGL((k_idx_leaves<D>), dim3((unsigned)t.cnt[0]), dim3(256), 0, c->stream, t, (const uint8_t*)c->maskU.p);
+  for (int lev = 1; lev < t.nlev; ++lev)
+    hipLaunchKernelGGL((k_idx_parents<D>), dim3((unsigned)((t.cnt[lev] + 3) / 4)), dim3(256), 0, c->stream, t, lev);
+  RcExp rx;                                  // (as launch_exact: the guard band of an approximating posterior's fast path)
+  memset(&rx, 0, sizeof(rx));
+  if (gb_of(c) && !c->rc_active) {
+    rx.gb_c = cidx;
+    rx.gb_l = c->gb_slow ? -1 : lidx;
+  }
+  const T* mean_c = (const T*)c->mean.p + (size_t)cidx * n;
+  const T* var_c = (const T*)c->var.p + (size_t)cidx * n;
+  const unsigned nb = (unsigned)std::min<long long>((n + 3) / 4, (long long)c->n_cu * 16);
+  hipLaunchKernelGGL((k_idx_expander<T, D>), dim3(nb), dim3(256), 0, c->stream, t, mean_c, var_c, (T)o->b, (const uint8_t*)c->maskS.p,
+                     (const unsigned long long*)c->Lmax.p, lidx, (SweepScalars*)c->scal.p, G, (long long*)c->amb.p, rx);
+  SBO_HIP(hipGetLastError());
+  c->lx.ran = true;
+  return SBO_OK;
+}
+template <typename T>
+static int list_index_expander_d(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, int lidx, uint8_t* G) {
+  switch (idx_dpad(c->cs.d)) {
+    case 2: return list_index_expander<T, 2>(c, o, cidx, lidx, G);
+    case 4: return list_index_expander<T, 4>(c, o, cidx, lidx, G);
+    default: return list_index_expander<T, 8>(c, o, cidx, lidx, G);
+  }
+}
 
 // the minimiser launch of a SafeOpt sweep, held back so that the first constraint's expander can take it into k_set_mid
 struct MinimizerJob {
@@ -1611,6 +1770,11 @@ static int expander_set(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, uint8_t* 
   } else {
     // explicit candidate lists, and grid ranges that are not whole hyper-planes: exhaustive evaluation
     launch_minimizer<T>(c, o, mj);
+    if (list_index_on(c)) {
+      // (explicit lists on the spatial index: the same verdicts with the pairs that cannot matter left out)
+      if ((rc = list_index_expander_d<T>(c, o, cidx, lidx, G))) return rc;
+      return launch_exact_d<T>(c, o, cidx, lidx, G);
+    }
     // (quadratic: every safe candidate against every U point, like the reference's vmap -- fine for the lists a campaign
     // uses, seconds at the cap)
     if (n > kListExpanderMax)
@@ -1827,6 +1991,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
   int rc;
   sweep_comm_reset(c);
   SBO_HIP(hipEventRecord(c->ev[0], c->stream));
+  if ((rc = list_index_prepare(c))) return rc;          // (explicit lists on the spatial index: its sorted order, once per list)
   const bool reuse = o->posterior_ready && c->posterior_valid;
   PostRequest req = sweep_request(c, o->b, !reuse);
   // column path (sets_colpath.inc.hpp): a fresh posterior of a one-constraint fp64 model on one rank may deliver the classification
@@ -1940,6 +2105,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
   }
   SBO_HIP(hipEventElapsedTime(&t04, c->ev[0], c->ev[4]));
   memset(&c->prof, 0, sizeof(c->prof));
+  if ((rc = list_index_profile(c))) return rc;
   c->prof.posterior_ms = t01;
   c->prof.classify_ms = t12;
   c->prof.expander_ms = t23;
@@ -2223,6 +2389,30 @@ static int goose_sets(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, const uint8
   const long long nsrc_runs = run_hi - run_lo;
   if (nsrc_runs > 0x7fffffffll) return fail(SBO_E_UNSUPPORTED, "too many source runs");
   if ((rc = ensure(c->runmeta, sizeof(RunMeta) * (size_t)std::max<long long>(nsrc_runs, 1)))) return rc;
+  if (list_index_on(c) && c->lx.valid) {
+    // sources and targets in the index's sorted order: the runs' boxes are compact, so the box test skips whole runs.  Coverage
+    // is a union of balls: the order of the search cannot change a verdict, and O goes back to the caller's order.
+    const size_t ub = ((size_t)n + 255) / 256 * 256;
+    if ((rc = ensure(c->lxtree, 2 * ub + sizeof(T) * (size_t)n))) return rc;
+    uint8_t* Us = (uint8_t*)c->lxtree.p;
+    uint8_t* Os = Us + ub;
+    T* Ws = (T*)(Os + ub);
+    const unsigned* perm = (const unsigned*)c->lx.vals.p + (size_t)c->lx.perm_half * n;
+    const unsigned gb = (unsigned)std::min<long long>((n + 255) / 256, (long long)c->n_cu * 16);
+    hipLaunchKernelGGL((k_idx_gather<T>), dim3(gb), dim3(256), 0, c->stream, W, perm, n, Ws);
+    hipLaunchKernelGGL((k_idx_gather<uint8_t>), dim3(gb), dim3(256), 0, c->stream, (const uint8_t*)c->maskU.p, perm, n, Us);
+    CandSpec csx = c->cs;
+    csx.pts = c->lx.xs.p;
+    csx.pts_dtype = SBO_F64;
+    hipLaunchKernelGGL((k_goose_run_meta<T, D>), dim3((unsigned)nsrc_runs), dim3(256), 0, c->stream, csx, (const T*)Ws,
+                       (const unsigned long long*)c->Lmax.p, lidx, 0ll, (RunMeta*)c->runmeta.p);
+    hipLaunchKernelGGL((k_goose_optimistic<T, D>), dim3((unsigned)((n + kRun - 1) / kRun)), dim3(256), 0, c->stream, csx, csx, (const T*)Ws,
+                       (const uint8_t*)Us, (const unsigned long long*)c->Lmax.p, lidx, (const RunMeta*)c->runmeta.p, 0ll,
+                       (int)nsrc_runs, Os);
+    hipLaunchKernelGGL(k_idx_scatter_u8, dim3(gb), dim3(256), 0, c->stream, (const uint8_t*)Os, perm, n, O);
+    SBO_HIP(hipGetLastError());
+    return SBO_OK;
+  }
   hipLaunchKernelGGL((k_goose_run_meta<T, D>), dim3((unsigned)nsrc_runs), dim3(256), 0, c->stream, css, W,
                      (const unsigned long long*)c->Lmax.p, lidx, run_lo, (RunMeta*)c->runmeta.p);
   hipLaunchKernelGGL((k_goose_optimistic<T, D>), dim3((unsigned)((n + kRun - 1) / kRun)), dim3(256), 0, c->stream, c->cs, css, W,
@@ -2273,6 +2463,7 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_result* 
   int rc;
   sweep_comm_reset(c);
   SBO_HIP(hipEventRecord(c->ev[0], c->stream));
+  if ((rc = list_index_prepare(c))) return rc;          // (explicit lists on the spatial index: its sorted order, once per list)
   const bool reuse = o->posterior_ready && c->posterior_valid;
   const PostRequest req = sweep_request(c, o->b, !reuse);
   if ((rc = sweep_masks(c, req))) return rc;
@@ -2447,6 +2638,7 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_result* 
   }
   SBO_HIP(hipEventElapsedTime(&t04, c->ev[0], c->ev[4]));
   memset(&c->prof, 0, sizeof(c->prof));
+  if ((rc = list_index_profile(c))) return rc;
   c->prof.posterior_ms = t01;
   c->prof.classify_ms = t12;
   c->prof.expander_ms = t23;
