@@ -9,10 +9,15 @@ candidates resident in HBM.
 Workload at every N: the configuration the north-star target is quoted on -- config H, Benoit 2-D, 4096 x 4096 implicit
 grid, n = 512 observations, q = 2 outputs, fp64 -- STRONG-scaled: the grid is sharded over the ranks by whole rows of its
 slowest axis; the ranks exchange u* / L / radius keys and the fully-unsafe mask (one all-gather) and the arg-max candidates
-(one sum all-reduce).  BASELINE.json configs[1] (config B, 2048 x 2048, n = 128) and the other configs are measured in
-``extra`` of the same process at N = 1; at N > 1 ``extra`` holds config D (128^4, BASELINE.json configs[3]) strong-scaled.
+(one sum all-reduce).  With ``--full``, BASELINE.json configs[1] (config B, 2048 x 2048, n = 128) and the other configs are
+measured in ``extra`` of the same process at N = 1; at N > 1 ``extra`` holds config D (128^4, BASELINE.json configs[3]) strong-scaled.
 
-What the JSON line reports (N = 1 adds the last five):
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the headline, ``config`` (workload,
+result, guard-band audit) and the ``roofline`` figures that the timed steps' own HIP events give.  Everything that takes runs of
+its own -- the other lean levels, the one-stream set phase, the objective tiles written, ``comm``, ``iteration``, ``table_kernel``,
+``extra`` and ``cpu_baseline`` -- is measured only with ``--full``.
+
+What the JSON line reports (``--full`` adds ``comm`` and, at N = 1, the last five):
   value / ms_per_step   sweeps of ONE RESIDENT MODEL (the metric of BASELINE.json: device time of the whole sweep with the
                         inputs resident in HBM), K timed steps between barriers.
   roofline              matrix-core side: the posterior kernels (K1).  ``achieved`` = min(ALGORITHMIC flops of SURVEY.md
@@ -21,7 +26,8 @@ What the JSON line reports (N = 1 adds the last five):
                         does not grow with n); ``executed`` the issued flops.
   roofline.hbm          HBM side: the set phase K3-K5 (classification, minimiser, expander transform, arg-max) --
                         SURVEY.md 8(d) bytes (2 q s + 4 per candidate) / set-phase device time, against 8.0 TB/s
-                        (datasheet) and 6.29 TB/s (measured copy rate of the guide).
+                        (datasheet) and 6.29 TB/s (measured copy rate of the guide).  On the column path a plain run prices the
+                        set phase that sticks out behind K1; --full prices the one-stream run and keeps that one as ``exposed``.
   comm                  (N > 1) collectives per sweep: calls, bytes a rank sends, event-timed microseconds per call (from a few
                         extra sweeps with option comm_events, outside the timed region).
   iteration             what ONE SafeOpt ITERATION costs: the reference refits and sweeps once per model
@@ -73,7 +79,11 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="H", help="synthetic config (H = 4096^2, n = 512: the north-star target's; B = BASELINE.json configs[1])")
     ap.add_argument("--n", type=int, default=None, help="override the number of observations")
-    ap.add_argument("--cpu-sample", type=int, default=1 << 21, help="candidates timed by the CPU baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, measure and check everything that takes runs of its own: the other lean levels, the "
+                         "one-stream set phase, the objective tiles written, comm, iteration, table_kernel, extra and cpu_baseline "
+                         "(off: the run does only what value / ms_per_step need)")
+    ap.add_argument("--cpu-sample", type=int, default=1 << 21, help="candidates timed by the CPU baseline of --full (0 = skip)")
     ap.add_argument("--points", type=int, default=10_000_000, help="candidates per rank for the scattered config E")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong",
                     help="strong: fixed grid, sharded over the ranks (default); weak: the grid's slowest axis grows with the ranks")
@@ -81,7 +91,7 @@ def parse_args():
                     help="auto: fp64 2-D grids use the bilinear GEMM posterior (K1b) when its bases qualify; "
                          "table: force the separable-table kernel (K1g), the O(n^2)-per-candidate contraction")
     ap.add_argument("--sweep", choices=["safeopt", "goose"], default="safeopt")
-    ap.add_argument("--no-extra", action="store_true", help="skip the iteration / table-kernel / H / C records")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the iteration / table-kernel / H / C records")
     ap.add_argument("--lean", type=int, choices=[0, 1, 2], default=2,
                     help="sbo_sweep_opts.lean of the SafeOpt sweeps: 2 (default) the caller wants the sweep's RESULT -- sets, indices, counts, u*, "
                          "the constraints' Lipschitz keys --: the objective's mean / var are neither stored nor evaluated on posterior tiles "
@@ -295,10 +305,10 @@ def timed_iterations(eng, models, dtype, step, steps, warmup, barrier):
                           "exact node values + Chebyshev coefficients, K1i) + one full sweep; wall clock between barriers"}
 
 
-def make_configs(name, n=None):
-    """(config, alternate data set of the same config).  Built with a handful of BLAS threads and before any timed region:
-    the BLAS pool's idle workers spin for tens of milliseconds after a call, and on a box whose CPU quota is smaller than
-    its visible cores that gets the timing thread throttled."""
+def make_configs(name, n=None, with_alt=True):
+    """(config, alternate data set of the same config, or None without ``with_alt``).  Built with a handful of BLAS threads and
+    before any timed region: the BLAS pool's idle workers spin for tens of milliseconds after a call, and on a box whose CPU
+    quota is smaller than its visible cores that gets the timing thread throttled."""
     from safebo_amd import synthetic
     try:
         from threadpoolctl import threadpool_limits
@@ -308,7 +318,7 @@ def make_configs(name, n=None):
         ctx = contextlib.nullcontext()
     with ctx:
         cfg = synthetic.make_config(name, n=n)
-        alt = synthetic.make_config(name, n=n, seed=synthetic.SEED0 + 100 + cfg["index"])
+        alt = synthetic.make_config(name, n=n, seed=synthetic.SEED0 + 100 + cfg["index"]) if with_alt else None
     return cfg, alt
 
 
@@ -402,12 +412,13 @@ def main():
         from safebo_amd import distributed
         group = distributed.init_from_env()       # stdlib TCP rendezvous among the launcher's ranks (no torch)
 
-    cfg, alt = make_configs(args.config, n=args.n)
+    # (a plain run builds the headline's data set alone: the alternate one and the other configs feed --full's records only)
+    cfg, alt = make_configs(args.config, n=args.n, with_alt=args.full)
     scattered = cfg["count"] is None                      # config E: explicit list of scattered candidates
     default_run = args.config == "H" and args.n is None and args.sweep == "safeopt" and args.posterior == "auto"
-    extras = world == 1 and not args.no_extra and not scattered
+    extras = args.full and world == 1 and not args.no_extra and not scattered
     extra_cfgs = {name: make_configs(name) for name in (("B", "C", "D", "E") if extras and default_run else ())}
-    dcfg = make_configs("D")[0] if (world > 1 and not args.no_extra and default_run and args.scaling == "strong") else None
+    dcfg = make_configs("D")[0] if (args.full and world > 1 and not args.no_extra and default_run and args.scaling == "strong") else None
     if scattered:
         per_rank = args.points if args.scaling == "weak" else args.points // world
         n_total = per_rank * world
@@ -450,7 +461,7 @@ def main():
     elapsed = max_over_ranks(group, elapsed)
     if args.dump_outputs and rank == 0:
         dump_outputs(res, args.dump_outputs)        # (host copies: res is the last timed step's own result)
-    comm = comm_record(eng, step, transport) if world > 1 else None
+    comm = comm_record(eng, step, transport) if args.full and world > 1 else None
     # N > 1: config D (BASELINE.json configs[3]) strong-scaled over the same ranks, every rank takes part
     d_rec = extra_record(eng, dcfg, None, "D", "safeopt", 3, barrier, group=group, transport=transport) if dcfg is not None else None
 
@@ -468,7 +479,7 @@ def main():
         roof["store_roofline_frac"] = store_bytes / (roof["kernel_ms"] * 1e-3) / 1e12 / HBM_PEAK_TBS
         roof["store_roofline_definition"] = ("2 q s bytes per candidate (the posterior API's output, SURVEY.md 8(d)) / K1 device time / 8 TB/s; a lean sweep "
                                              "writes fewer bytes than that (config.lean), the figure prices the time against the full output")
-        if args.sweep == "safeopt" and args.lean and int(rows[-1].get("set_path", 0)) == 1 and not scattered and world == 1:
+        if args.full and args.sweep == "safeopt" and args.lean and int(rows[-1].get("set_path", 0)) == 1 and not scattered and world == 1:
             # ... and against what THIS sweep writes: every constraint's mean / var, the objective's on the 64 x 128 posterior tiles that
             # hold a safe candidate (counted from the S mask of one more sweep, outside the timed region)
             eng.sweep_safeopt(cfg["b"], want_masks=True, lean=args.lean)
@@ -506,7 +517,7 @@ def main():
                        "set_path": {0: "byte masks", 1: "column words written by the GEMM posterior (sets_colpath.inc.hpp)"}[int(rows[-1].get("set_path", 0))]},
             "roofline": roof,
         }
-        if args.sweep == "safeopt" and world == 1 and not args.no_extra:
+        if args.full and args.sweep == "safeopt" and world == 1 and not args.no_extra:
             # the same sweep at the other lean levels, same process (short timed runs): what storing / evaluating the objective's
             # posterior where no stage of the sweep reads it costs
             for lv, key in ((0, "full_posterior"), (1, "lean_1"), (2, "lean_2")):
@@ -517,7 +528,7 @@ def main():
                 out["config"][key] = {"lean": lv, "ms_per_step": el_v * 1e3 / max(20, args.steps // 4), "value": n_total * max(20, args.steps // 4) / el_v,
                                       "device_ms_per_step": float(np.mean([p["total_ms"] for p in rows_v])),
                                       "kernel_ms": float(np.mean([p["posterior_ms"] for p in rows_v])), "result_identical": bool(same)}
-        if args.sweep == "safeopt" and world == 1 and not args.no_extra and int(rows[-1].get("set_path", 0)) == 1:
+        if args.full and args.sweep == "safeopt" and world == 1 and not args.no_extra and int(rows[-1].get("set_path", 0)) == 1:
             # column path: the expander chain runs on a second stream BESIDE the objective's posterior launch, so the time between the K1
             # stop event and the end of the sweep (`set_phase_ms` above) is only what sticks out behind K1 -- priced against the survey's
             # bytes it would exceed the copy rate.  The same sweep on ONE stream (option col_overlap = 0) gives the set phase's own
@@ -562,7 +573,7 @@ def main():
                             extra_record(eng, *extra_cfgs["C"], "C", "safeopt", 40, barrier, lean=args.lean),
                             extra_record(eng, *extra_cfgs["D"], "D", "safeopt", 10, barrier, table_kernel=True, lean=args.lean),
                             extra_record(eng, extra_cfgs["E"][0], None, "E", "safeopt", 3, barrier, points=10_000_000)]
-        if world == 1 and args.cpu_sample > 0 and not scattered:
+        if args.full and world == 1 and args.cpu_sample > 0 and not scattered:
             # the workload of `value` itself: a prefix of this config's grid (a bounded sample -- H whole would be minutes of CPU
             # work: n = 512 costs 16 x config B's flops per candidate), and beside it config B's whole grid as in earlier rounds
             whole = n_total <= 1 << 22

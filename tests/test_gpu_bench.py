@@ -1,4 +1,5 @@
-"""The bench line's contract (task statement): one JSON line with the metric, the roofline and the CPU baseline of the same run."""
+"""The bench line's contract (task statement): one JSON line with the metric and the roofline of the timed steps; with --full also
+the CPU baseline and the records that take runs of their own."""
 import json
 import os
 import subprocess
@@ -20,7 +21,7 @@ def _run(*args):
 
 
 def test_bench_line_contract_on_a_small_run():
-    d = _run("--config", "B", "--steps", "6", "--warmup", "2", "--no-extra", "--cpu-sample", "65536")
+    d = _run("--config", "B", "--steps", "6", "--warmup", "2", "--no-extra", "--cpu-sample", "65536", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
               "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -34,6 +35,23 @@ def test_bench_line_contract_on_a_small_run():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and "sample" in c and c["unit"] == "candidates/s"
     assert d["config"]["guard_audit_violations"] == 0
+
+
+def test_plain_run_measures_the_headline_alone():
+    """Without --full the default config's run times its steps and reports them, and nothing that takes runs of its own."""
+    d = _run("--gpus", "1", "--steps", "4", "--warmup", "2")
+    assert d["steps"] == 4 and d["warmup"] == 2 and d["higher_is_better"] is True and d["unit"] == "candidates/s" and d["dtype"] == "f64"
+    assert abs(d["value"] - 4096 * 4096 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-9
+    for k in ("cpu_baseline", "iteration", "table_kernel", "extra", "comm"):
+        assert k not in d, k
+    for k in ("full_posterior", "lean_1", "lean_2", "iteration_ms", "iteration_value"):
+        assert k not in d["config"], k
+    r = d["roofline"]
+    for k in ("store_roofline_frac_written", "objective_tiles_with_a_safe_candidate", "table_kernel_frac"):
+        assert k not in r, k
+    assert "one_stream" not in r["hbm"] and "exposed" not in r["hbm"]
+    assert 0.0 < r["kernel_ms"] < r["device_ms_per_step"] <= d["ms_per_step"] and r["set_phase_ms"] == r["set_phase_exposed_ms"]
+    assert d["config"]["lean"] == 2 and d["config"]["guard_audit_violations"] == 0 and d["config"]["result"]["guard_band"] == 0
 
 
 def test_dump_outputs_hold_the_last_timed_result_and_repeat(tmp_path):

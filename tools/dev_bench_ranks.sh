@@ -8,7 +8,7 @@ python bench.py --steps 3 --warmup 1 --cpu-sample 0 --no-extra > $out/H_1.json 2
 python bench.py --config D --steps 2 --warmup 1 --cpu-sample 0 --no-extra > $out/D_1.json 2> $out/D_1.err || exit 1
 for n in 2 4; do
   SBO_BENCH_DEVICE=0 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29617 + n)) \
-    bench.py --gpus $n --steps 3 --warmup 1 > $out/N_$n.json 2> $out/N_$n.err || { tail -5 $out/N_$n.err; exit 1; }
+    bench.py --gpus $n --steps 3 --warmup 1 --full > $out/N_$n.json 2> $out/N_$n.err || { tail -5 $out/N_$n.err; exit 1; }
 done
 python - $out <<'PY'
 import json, sys

@@ -2,7 +2,7 @@
 # rocprofv3 recipe (run through gpurun from the repo root): tools/gpu_profile.sh TAG CONFIG STEPS [full|-] ["extra bench args"]
 #   trace/               rocprofv3 --kernel-trace --stats of the resident-model sweeps of CONFIG (--no-extra)
 #   pmc_fetch|write|sq/  counter passes, each in its own run (no tracing domains next to --pmc)
-#   bench.json           with "full": the default bench line (what the driver runs); else the --no-extra line of CONFIG
+#   bench.json           with "full": the bench line of the default config with --full (every record); else the --no-extra line of CONFIG
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$1
@@ -12,7 +12,7 @@ EXTRA=${5:-}            # further bench.py arguments, e.g. "--sweep goose"
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 if [ "$4" = "full" ]; then
-  python3 $R/bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 1
+  python3 $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit 1
 else
   python3 $R/bench.py --config $CFG --steps $STEPS --warmup 3 --cpu-sample 0 --no-extra $EXTRA > $OUT/bench.json 2> $OUT/bench.err || exit 1
 fi
