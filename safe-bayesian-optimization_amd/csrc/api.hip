@@ -668,6 +668,7 @@ int sbo::posterior_enqueue(sbo_ctx* c, const PostRequest& req, PostOutcome* out)
   if (c->audit_pending) SBO_HIP(hipStreamWaitEvent(c->stream, c->ev_audit[0], 0));
   if (c->cs.n_local > 0 && (rc = launch_posterior(c, req, *out))) return rc;
   c->posterior_valid = true;
+  c->post_l0_missing = req.sweep_lean != 0;
   return SBO_OK;
 }
 

@@ -462,8 +462,13 @@ __global__ __launch_bounds__(256) void k_audit_pick(const CandSpec cs, int P, un
                                                     (bilinear.hip: k_bl_enclose) of the K1b column-path launch that just ran */,
                                                     const uint8_t* __restrict__ skip /* nullptr, or its skip bytes (a lean-2 launch) */,
                                                     int gx /* 64 x 128 tiles per tile row */,
-                                                    double* __restrict__ aenc /* [5][P]: 1 on a skipped tile, 2 on an evaluated one; m_lo, m_hi, v_lo, v_hi */) {
+                                                    double* __restrict__ aenc /* [5][P]: 1 on a skipped tile, 2 on an evaluated one; m_lo, m_hi, v_lo, v_hi */,
+                                                    const GuardBand* __restrict__ gb, GuardBand* __restrict__ gb_snap) {
   const long long N = cs.n_local;
+  // (the band this sweep's values rest on: the next sweep may rebuild its plan -- and rewrite gb -- while the comparison still waits)
+  constexpr int kGbWords = (int)(sizeof(GuardBand) / sizeof(double));
+  if (blockIdx.x == 0)
+    for (int w = threadIdx.x; w < kGbWords; w += blockDim.x) reinterpret_cast<double*>(gb_snap)[w] = reinterpret_cast<const double*>(gb)[w];
   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < P; k += gridDim.x * blockDim.x) {
     const long long g = (long long)((offset + (unsigned long long)k * stride) % (unsigned long long)N);
     double x[D];
@@ -543,7 +548,7 @@ void guard_audit_harvest(sbo_ctx* c, bool wait) {
 
 int guard_audit_enqueue(sbo_ctx* c, const PostOutcome& out) {
   const int first_output = out.col_lean ? 1 : 0;      // (a lean column-path launch left the objective's values incomplete)
-  if (c->guard_audit <= 0 || !c->gb_active || !c->guard_band || c->is_shadow || !(c->last_k1 == 4 || c->last_k1 == 6) || !ref_direct(c) || c->mc.dpad != 2 ||
+  if (c->guard_audit <= 0 || !c->gb_active || !c->guard_band || !c->gb.p || c->is_shadow || !(c->last_k1 == 4 || c->last_k1 == 6) || !ref_direct(c) || c->mc.dpad != 2 ||
       c->cs.n_local <= 0 || !c->stream_audit || first_output >= c->mc.q)
     return SBO_OK;
   // (the audit shares the card with the sweep it follows -- ~35 us of a config-H sweep's set phase for 1024 samples at n = 512 --, so
@@ -553,13 +558,14 @@ int guard_audit_enqueue(sbo_ctx* c, const PostOutcome& out) {
   if (c->audit_pending) return SBO_OK;                 // (the previous audit is still running: this sweep's is skipped, none queues up)
   const int P = c->guard_audit, q = c->mc.q;
   int rc;
-  if ((rc = ensure(c->audit_pts, sizeof(double) * (size_t)P * 2)) || (rc = ensure(c->audit_val, sizeof(double) * (size_t)P * (q * 4 + 5))) ||
+  if ((rc = ensure(c->audit_pts, sizeof(double) * (size_t)P * 2)) || (rc = ensure(c->audit_val, sizeof(double) * (size_t)P * (q * 4 + 5) + sizeof(GuardBand))) ||
       (rc = ensure(c->audit_cnt, 64)))
     return rc;
   double* apx = (double*)c->audit_val.p;
   double* ref_m = apx + (size_t)2 * q * P;
   double* ref_v = ref_m + (size_t)q * P;
   double* aenc = ref_v + (size_t)q * P;
+  GuardBand* gb_snap = reinterpret_cast<GuardBand*>(aenc + (size_t)5 * P);
   // (r06: a K1b column-path launch on a plan with recorded enclosures -- bilinear.hip: k_bl_enclose -- leaves two things to check at the
   // constraint's samples.  On a tile a lean sweep left unevaluated the stored values are not this sweep's: the exact values must lie in
   // the tile's enclosure widened by the band.  On an evaluated tile the stored values must lie in the enclosure exactly -- the skip rests
@@ -578,13 +584,14 @@ int guard_audit_enqueue(sbo_ctx* c, const PostOutcome& out) {
   const unsigned long long stride = 1000003ull;
   hipLaunchKernelGGL(k_audit_pick<2>, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, c->cs, P, c->audit_offset, stride, q, (const double*)c->mean.p,
                      (const double*)c->var.p, (double*)c->audit_pts.p, apx, encl ? (const double*)c->bl_encl.p : (const double*)nullptr,
-                     skips ? (const uint8_t*)c->bl_encl.p + sizeof(double) * 4 * 128 * ntiles : (const uint8_t*)nullptr, (int)(cnt0 / 128), aenc);
+                     skips ? (const uint8_t*)c->bl_encl.p + sizeof(double) * 4 * 128 * ntiles : (const uint8_t*)nullptr, (int)(cnt0 / 128), aenc,
+                     (const GuardBand*)c->gb.p, gb_snap);
   c->audit_offset += (unsigned long long)P * stride + 17ull;
-  // ... and before anything overwrites mean / var again (the next posterior launch waits for this event)
+  // ... and before anything overwrites mean / var or the band again (the next posterior launch waits for this event)
   SBO_HIP(hipEventRecord(c->ev_audit[0], st));
   if ((rc = launch_ref<2>(c, st, (const double*)c->audit_pts.p, P, 0, ref_m, ref_v, nullptr, &c->audit_part))) return rc;
   hipLaunchKernelGGL(k_audit_compare, dim3(8), dim3(256), 0, st, P, q, first_output, (const double*)apx, (const double*)ref_m, (const double*)ref_v,
-                     (const GuardBand*)c->gb.p, (unsigned long long*)c->audit_cnt.p, c->audit_scale, encl ? (const double*)aenc : (const double*)nullptr);
+                     (const GuardBand*)gb_snap, (unsigned long long*)c->audit_cnt.p, c->audit_scale, encl ? (const double*)aenc : (const double*)nullptr);
   SBO_HIP(hipMemcpyAsync(c->h_back + 7168, c->audit_cnt.p, 32, hipMemcpyDeviceToHost, st));
   SBO_HIP(hipEventRecord(c->ev_audit[1], st));
   SBO_HIP(hipGetLastError());

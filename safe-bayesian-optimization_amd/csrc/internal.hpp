@@ -229,6 +229,7 @@ struct sbo_ctx {
   sbo::DevBuf tn_tail;             // K1t: [2 q][d] keys of the node tensors' coefficient tails per axis (k_t_fiber_tail)
   double tn_band[7 * SBO_MAX_Q] = {0};   // the plan's guard band (dm | dv | rl | analytic dm | dv | probe dm | dv per output)
   int tn_bump = 0;                 // ladder steps added to the first guess on this grid (a previous model's plan needed its second attempt)
+  bool tn_lean_probe = false;      // the plan's probe left out output 0's gradient (decided by a lean sweep): a full sweep probes it again
   // Guard band of the approximating posteriors K1b / K1t (device_common.hpp: GuardBand; guard.hip)
   int guard_band = 1;              // option: 1 count + re-evaluate exactly when the count is non-zero; 0 off; 2 re-evaluate on every sweep (test)
   bool gb_active = false;          // the posterior in mean / var came from an approximating kernel; `gb` holds (or will hold, in stream order) its band
@@ -272,6 +273,7 @@ struct sbo_ctx {
   // posterior workspace, SoA [q][n_local] of the model dtype
   sbo::DevBuf mean, var;
   bool posterior_valid = false;
+  bool post_l0_missing = false;  // the resident posterior came from a lean sweep's launch: L_0 (Lmax[0]) was not computed
   int last_k1 = 0;               // kernel family of the last posterior launch (sbo_profile.posterior_kernel)
   double last_k1_flops = 0.0;    // matrix-core flops it issued
   sbo::DevBuf Lmax;    // [kMaxQ] uint64 keys: max ||grad MEAN_i||_inf over the candidates

@@ -1992,7 +1992,8 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
   sweep_comm_reset(c);
   SBO_HIP(hipEventRecord(c->ev[0], c->stream));
   if ((rc = list_index_prepare(c))) return rc;          // (explicit lists on the spatial index: its sorted order, once per list)
-  const bool reuse = o->posterior_ready && c->posterior_valid;
+  // (a posterior a lean sweep launched lacks the objective's Lipschitz key: a full sweep does not reuse it)
+  const bool reuse = o->posterior_ready && c->posterior_valid && (o->lean || !c->post_l0_missing);
   PostRequest req = sweep_request(c, o->b, !reuse);
   // column path (sets_colpath.inc.hpp): a fresh posterior of a one-constraint fp64 model on one rank may deliver the classification
   // as column words (the GEMM posterior decides whether its launch qualifies: PostOutcome::col_active)
@@ -2464,7 +2465,7 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_result* 
   sweep_comm_reset(c);
   SBO_HIP(hipEventRecord(c->ev[0], c->stream));
   if ((rc = list_index_prepare(c))) return rc;          // (explicit lists on the spatial index: its sorted order, once per list)
-  const bool reuse = o->posterior_ready && c->posterior_valid;
+  const bool reuse = o->posterior_ready && c->posterior_valid && !c->post_l0_missing;    // (GoOSE reports L_0: not from a lean launch)
   const PostRequest req = sweep_request(c, o->b, !reuse);
   if ((rc = sweep_masks(c, req))) return rc;
   PostOutcome post;

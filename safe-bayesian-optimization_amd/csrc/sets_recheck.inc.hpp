@@ -356,7 +356,7 @@ static int sweep_safeopt_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeop
   if (!kGuard && n == 0 && !multi_rank(c)) return sweep_safeopt_t<float>(c, o, res);
   SBO_HIP(hipEventRecord(c->ev_join[0], c->stream));
   // (guard: the posterior is resident -- unless the first pass was a lean sweep, which left part of it unwritten: K1 once more, in full)
-  const bool reuse = (kGuard && c->posterior_valid) || (o->posterior_ready && c->posterior_valid);
+  const bool reuse = (kGuard && c->posterior_valid) || (o->posterior_ready && c->posterior_valid && (o->lean || !c->post_l0_missing));
   if (!reuse && (rc = posterior_enqueue(c, PostRequest{}, nullptr))) return rc;
   SBO_HIP(hipEventRecord(c->ev_join[1], c->stream));
   RcBand bd;

@@ -579,6 +579,10 @@ int launch_posterior_tensor(sbo_ctx* c, const PostRequest& req, bool* declined) 
   const bool same_box = c->tn_valid && c->tn_first == cs.first && c->tn_nlocal == cs.n_local && !memcmp(c->tn_count, cs.count, sizeof(long long) * kTMaxD) &&
                         !memcmp(c->tn_lo, cs.lo, sizeof(double) * kTMaxD) && !memcmp(c->tn_hi, cs.hi, sizeof(double) * kTMaxD);
   if (!same_box) c->tn_bump = 0;
+  // a plan a lean sweep decided never probed output 0's gradient (its band has no measured part for L_0): the first full sweep on it
+  // keeps its degrees and runs the probe once more, so the band is what a full sweep deciding the plan would have measured
+  const bool reprobe = same_grid && c->tn_usable && c->tn_lean_probe && !(req.sweep_lean && q >= 2);
+  const bool probe = !same_grid || reprobe;
   int level0[kTMaxD], base0[kTMaxD] = {0, 0, 0, 0};
   if (same_grid) {
     if (!c->tn_usable) return SBO_OK;
@@ -671,7 +675,7 @@ int launch_posterior_tensor(sbo_ctx* c, const PostRequest& req, bool* declined) 
       if ((rc = launch_posterior_on_axes(c, d, cnt, (const double*)c->tn_pts.p, nmean, nvar, ngrad, (unsigned long long*)c->tn_scr.p))) return rc;
     }
     // (the coefficient tails of the node tensors of mean and variance along every axis: the analytic part of the plan's band, below)
-    if (!same_grid) {
+    if (probe) {
       if ((rc = ensure(c->tn_tail, sizeof(unsigned long long) * 2 * kMaxQ * kTMaxD))) return rc;
       SBO_HIP(hipMemsetAsync(c->tn_tail.p, 0, sizeof(unsigned long long) * 2 * kMaxQ * kTMaxD, c->stream));
       hipLaunchKernelGGL(k_t_fiber_tail, dim3(kTFibers, (unsigned)d, (unsigned)(2 * q)), dim3(64), 0, c->stream, td, (const double*)nmean, Nn,
@@ -682,7 +686,7 @@ int launch_posterior_tensor(sbo_ctx* c, const PostRequest& req, bool* declined) 
     const double* cur = nullptr;
     size_t cur_stride = 0;
     if ((rc = interpolate(c, td, nmean, Nn, 2 * q + nqg, req.sweep_lean, &cur, &cur_stride))) return rc;
-    if (!same_grid) {
+    if (probe) {
       // accuracy probe: 2048 grid points, exact against interpolated
       std::vector<long long> idx(kTProbes);
       unsigned long long sd = 0x9e3779b97f4a7c15ull ^ (unsigned long long)c->model_serial;
@@ -807,6 +811,7 @@ int launch_posterior_tensor(sbo_ctx* c, const PostRequest& req, bool* declined) 
         c->tn_dn[a] = td.Dn[a];
       }
       c->tn_usable = ok_all != 0ull;
+      c->tn_lean_probe = req.sweep_lean && q >= 2;
       if (!c->tn_usable) continue;           // one step up the ladder, or give up
       if (attempt > 0) c->tn_bump = std::min(2, c->tn_bump + 1);
     }
