@@ -365,6 +365,47 @@ int sbo_fit_local(sbo_ctx* ctx, int n, int d, int q, const double* X_norm, const
                   const double* lo, const double* hi, int maxiter, double ftol, double gtol, double* best_x, double* best_nll,
                   double* x_out, double* nll_out, int* iters_out, int* evals_out, double* pgnorm_out, int* status_out);
 
+/* ---- local refinement of an acquisition optimum off the grid ------------ */
+/* per-seed outcome of sbo_refine */
+enum sbo_refine_status {
+  SBO_REFINE_CONVERGED = 0,        /* the barrier path reached its floor with a small projected gradient; the point was accepted  */
+  SBO_REFINE_MAX_EVAL = 1,         /* max_eval evaluations ran out; the best accepted point is returned                           */
+  SBO_REFINE_NO_PROGRESS = 2,      /* no iterate passed the exact check (or the solver could not start): the seed is returned     */
+  SBO_REFINE_INFEASIBLE_SEED = 3,  /* the seed fails the S predicate (box, ball, lcb_c >= 0, finite): returned unchanged, never best */
+  SBO_REFINE_ON_BOUNDARY = 4       /* the seed is feasible with some lcb_c == 0 or on the ball's sphere: returned unchanged        */
+};
+
+typedef struct sbo_refine_opts {
+  double   b;                      /* confidence multiplier, as sbo_sweep_opts.b                                                 */
+  int32_t  objective;              /* output index o in [0, q)                                                                   */
+  int32_t  kind;                   /* SBO_MEAN / SBO_UCB / SBO_LCB / SBO_VAR of output o                                         */
+  int32_t  maximize;               /* 0: minimise, 1: maximise                                                                   */
+  uint32_t constraint_mask;        /* bit c (1 <= c < q): enforce lcb_c(x) >= 0; bit 0 must be clear                             */
+  double   lo[SBO_MAX_D], hi[SBO_MAX_D];   /* box (finite, lo <= hi); seeds outside it are infeasible, not clipped            */
+  int32_t  use_ball;               /* 1: also ||x - x_0||_2 <= r (no 1e-8 shift, as sbo_sweep_tr)                                */
+  int32_t  max_eval;               /* posterior + gradient evaluations per seed; <= 0: 400; at most min(20000, max(400, 4e9 / n^2)) */
+  double   x_0[SBO_MAX_D], r;      /* ball centre and radius (use_ball: finite, r > 0)                                           */
+  double   tol;                    /* projected-gradient inf-norm of the barrier function, box-scaled; <= 0: 1e-9                */
+} sbo_refine_opts;
+
+typedef struct sbo_refine_result {
+  int64_t best;                    /* seed whose returned point has the best objective (ties: lowest index), -1 if none usable   */
+  double  best_x[SBO_MAX_D], best_value;
+  int64_t evaluations;             /* posterior + gradient evaluations, summed over seeds                                        */
+  int32_t converged;               /* seeds with SBO_REFINE_CONVERGED                                                            */
+  int32_t reserved;
+} sbo_refine_result;
+
+/* Refine each seed[n_seeds][d] to a local optimum of `kind` of output `objective` over {x in the box, lcb_c(x) >= 0 for every c in
+ * constraint_mask, ||x - x_0|| <= r when use_ball}: one workgroup per seed, a projected BFGS on a log-barrier function of the exact
+ * fp64 posterior (the model's factor M with M^T M = invK).  Every returned point is re-evaluated by the exact list evaluator -- the
+ * values sbo_bounds gives there -- and is feasible under the sweep's S predicate and no worse than its seed (the seed itself at
+ * worst).  x_out[n_seeds][d], value_out[n_seeds] (the exact objective at the returned point) and status_out[n_seeds]
+ * (sbo_refine_status) may be NULL.  Deterministic.  Does not touch the resident candidates, posterior, masks, guard band or audit;
+ * no collectives (every rank refines on its replicated model).  fp64 models only (SBO_F32: SBO_E_UNSUPPORTED). */
+int sbo_refine(sbo_ctx* ctx, const sbo_refine_opts* opts, int64_t n_seeds, const double* seeds, double* x_out, double* value_out,
+               int32_t* status_out, sbo_refine_result* result);
+
 /* ---- plant evaluation ------------------------------------------ */
 /* The reference's William-Otto reactor (problems/WilliamOttoReactor_Problem.py:19-93), noise-free, for n input rows
  * u[n, 2] = (Fb, Tr): out[n, 3] = (get_objective, get_constraint1, get_constraint2), each the steady state of the six
@@ -409,6 +450,8 @@ int sbo_profile_get(sbo_ctx* ctx, sbo_profile* out);
  *   "guard_audit_scale_ppm" test hook: the audit compares against the band x value / 1e6 (default 1000000); setting it clears the counts
  *   "guard_audit_every" one sweep in this many carries an audit (default 16; the first sweep after setting it does).  An audit shares
  *                      the card with the sweep it follows (~35 us of config H's set phase at 1024 samples, n = 512): 1 audits every sweep
+ *   "refine_lds"       1 (default): sbo_refine stages the used outputs' triangles of M in LDS when they fit 144 KiB; 0: it always streams
+ *                      M's rows from L2 (the tier of larger models; results are bit-identical either way)
  *   "list_index"       explicit candidate lists: expander sets (SafeOpt, GoOSE's source filter) and GoOSE's coverage search on a spatial
  *                      index of the list (Morton order, boxes of the U members; verdicts identical to the exhaustive ones).  -1 (default):
  *                      only for lists above 2097152 candidates, where the exhaustive expander sets are refused; 1: at any size (A/B checker);

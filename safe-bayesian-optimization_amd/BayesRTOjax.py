@@ -31,9 +31,11 @@ from ._lib import EmptySafeSetError
 
 
 class BayesianOpt(GP_Classic.GP):
-    def __init__(self, plant_system, grid=None, device: int = 0, dtype: str = "f64", seed: int = 42):
+    def __init__(self, plant_system, grid=None, device: int = 0, dtype: str = "f64", seed: int = 42, refine: bool = False):
         GP_Classic.GP.__init__(self, plant_system, device=device, dtype=dtype, seed=seed)
         self.grid = None if grid is None else tuple(int(g) for g in grid)
+        self.refine = bool(refine)    # the acquisition's winner, x_0 and multi_start ball draws are refined off the grid
+        self._ms_rng = np.random.default_rng(seed)
 
     # ---- acquisition (models/BayesRTOjax.py:17-107) ----------------------------------------------------------------
     def _grid_counts(self):
@@ -55,11 +57,30 @@ class BayesianOpt(GP_Classic.GP):
             return -1, None, np.inf
         return res["index"], res["x"], res["lcb"]
 
-    def minimize_acquisition(self, r, x_0, data_storage, b=0, multi_start=5):
-        """(d, value): the displacement from x_0 of the acquisition's minimiser and its LCB, or (0, plant_temporary[0][0])."""
+    def minimize_acquisition(self, r, x_0, data_storage, b=0, multi_start=5, refine=None):
+        """(d, value): the displacement from x_0 of the acquisition's minimiser and its LCB, or (0, plant_temporary[0][0]).
+        ``refine`` (default: the constructor's): the sweep's winner, x_0 and ``multi_start`` points drawn in the ball are refined
+        off the grid (SweepEngine.refine); draws that are not safe under the model are dropped by their status.  The refined point
+        is taken only if x_0 + d itself is safe under the model, inside the ball and no worse than the grid answer."""
         x_0 = np.asarray(x_0, dtype=np.float64)
         stay = float(data_storage.data["plant_temporary"][0][0])
         index, x, lcb = self._acquisition_sweep(r, x_0, b)
+        if (self.refine if refine is None else bool(refine)) and r > 0:
+            seeds = ([x] if index >= 0 else []) + [x_0]
+            m = int(multi_start)
+            if m > 0:
+                dirs = self._ms_rng.standard_normal((m, self.nx_dim))
+                dirs /= np.maximum(np.linalg.norm(dirs, axis=1, keepdims=True), 1e-300)
+                rad = r * self._ms_rng.uniform(size=(m, 1)) ** (1.0 / self.nx_dim)
+                seeds += list(x_0 + rad * dirs)
+            out = self.engine.refine(b, np.asarray(seeds), 0, "lcb", lo=x_0 - r, hi=x_0 + r, x_0=x_0, r=r)
+            if out["best"] >= 0:
+                # the caller applies x_0 + d: that point, not the refined one, must be safe (x_0 + (x - x_0) need not round to x)
+                xa = x_0 + (out["best_x"] - x_0)
+                self.engine.set_points(xa[None, :])
+                lcb_a = [float(self.engine.bounds(b, c, "lcb")[0]) for c in range(self.n_fun)]
+                if all(v >= 0.0 for v in lcb_a[1:]) and np.sqrt(np.sum((xa - x_0) ** 2)) <= r and lcb_a[0] <= lcb:
+                    index, x, lcb = out["best"], xa, lcb_a[0]
         if index >= 0 and lcb < stay:
             return x - x_0, lcb
         return np.zeros_like(x_0), stay

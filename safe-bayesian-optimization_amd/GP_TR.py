@@ -12,14 +12,22 @@ from .SafeOpt import BO as _SafeOptBO
 
 
 class BO(_SafeOptBO):
-    def __init__(self, plant_system, bound, b, TR_parameters, grid=None, device: int = 0, dtype: str = "f64", seed: int = 42):
-        _SafeOptBO.__init__(self, plant_system, bound, b, grid=grid, device=device, dtype=dtype, seed=seed)
+    def __init__(self, plant_system, bound, b, TR_parameters, grid=None, device: int = 0, dtype: str = "f64", seed: int = 42,
+                 refine: bool = False):
+        _SafeOptBO.__init__(self, plant_system, bound, b, grid=grid, device=device, dtype=dtype, seed=seed, refine=refine)
         self.TR_parameters = TR_parameters
 
-    def minimize_obj_lcb(self, r, x_0):
+    def minimize_obj_lcb(self, r, x_0, refine=None):
+        """``refine`` (default: the constructor's): the grid winner and x_0 (when it is safe under the model) are refined off the
+        grid inside the ball -- the grid alone stalls at x_0 once r falls below its spacing."""
         self._grid_resident()
         res = self.engine.sweep_tr(self.b, x_0, r)
         self._sweep_cache = None
+        if self._refining(refine):
+            x0 = np.asarray(x_0, dtype=np.float64)
+            seeds = ([res["x"]] if res["index"] >= 0 else []) + [x0]
+            fallback = (res["x"], res["lcb"]) if res["index"] >= 0 else (x0.copy(), np.inf)
+            return self._refine_from(seeds, "lcb", fallback, x_0=x0, r=r)
         if res["index"] < 0:            # nothing safe inside the ball on this grid (the reference's DE would return an
             return np.asarray(x_0, dtype=np.float64).copy(), np.inf   # infeasible point): stay at the centre
         return res["x"], res["lcb"]

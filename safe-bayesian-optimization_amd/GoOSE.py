@@ -16,10 +16,11 @@ from .SafeOpt import BO as _SafeOptBO
 
 class BO(_SafeOptBO):
     def __init__(self, plant_system, bound, b, grid=None, device: int = 0, dtype: str = "f64",
-                 reference_quirk_L_index: bool = True, seed: int = 42, candidates=None, list_index: int | None = None):
+                 reference_quirk_L_index: bool = True, seed: int = 42, candidates=None, list_index: int | None = None,
+                 refine: bool = False):
         _SafeOptBO.__init__(self, plant_system, bound, b, grid=grid, device=device, dtype=dtype,
                             reference_quirk_L_index=reference_quirk_L_index, seed=seed, candidates=candidates,
-                            list_index=list_index)
+                            list_index=list_index, refine=refine)
         self._goose_cache = None
 
     def goose_sweep(self, want_masks: bool = False) -> dict:
@@ -31,8 +32,12 @@ class BO(_SafeOptBO):
         self._goose_cache = (key, res)
         return res
 
-    def minimize_obj_lcb(self):
+    def minimize_obj_lcb(self, refine=None):
+        """``refine`` (default: the constructor's): the sweep's arg-min refined off the grid under the same constraints; the
+        sweep's sets (S, O_c, the target) are not changed by it."""
         res = self.goose_sweep()
+        if self._refining(refine):
+            return self._refine_from([res["safe_min_x"]], "lcb", (res["safe_min_x"], res["safe_min_lcb"]))
         return res["safe_min_x"], res["safe_min_lcb"]
 
     def Target(self):

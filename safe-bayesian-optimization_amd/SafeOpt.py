@@ -22,8 +22,10 @@ from .GP_Safe import GP
 
 class BO(GP):
     def __init__(self, plant_system, bound, b, grid=None, device: int = 0, dtype: str = "f64",
-                 reference_quirk_L_index: bool = True, seed: int = 42, candidates=None, list_index: int | None = None):
+                 reference_quirk_L_index: bool = True, seed: int = 42, candidates=None, list_index: int | None = None,
+                 refine: bool = False):
         GP.__init__(self, plant_system, device=device, dtype=dtype, seed=seed)
+        self.refine = bool(refine)    # acquisitions polish the sweep's winner off the grid (SweepEngine.refine)
         self.bound = np.asarray(bound, dtype=np.float64)
         self.b = b
         d = self.bound.shape[0]
@@ -107,14 +109,30 @@ class BO(GP):
         return out
 
     # ---- acquisition (models/SafeOpt.py:47-124) --------------------------------------------------------------------
-    def minimize_obj_ucb(self, safe_set_cons=None):
+    def minimize_obj_ucb(self, safe_set_cons=None, refine=None):
         """min over S_t of ucb_0 -> (x, value); ``safe_set_cons`` is accepted for signature parity and ignored:
-        the safe-set constraints are the sweep's S mask."""
+        the safe-set constraints are the sweep's S mask.  ``refine`` (default: the constructor's): the sweep's arg-min is
+        refined off the grid under the same constraints (the sweep's sets are not changed)."""
         res = self.sweep(want_masks=True)
         S = self.engine.mask("S")
         ucb0 = self.engine.bounds(self.b, 0, "ucb")
         g = int(np.argmin(np.where(S, ucb0, np.inf)))
+        if self._refining(refine):
+            return self._refine_from([self._grid_point(g)], "ucb", (self._grid_point(g), res["u_star"]))
         return self._grid_point(g), res["u_star"]
+
+    def _refining(self, refine):
+        return self.refine if refine is None else bool(refine)
+
+    def _refine_from(self, seeds, kind, fallback, x_0=None, r=None, lo=None, hi=None):
+        """(best_x, best_value) of SweepEngine.refine from ``seeds`` (objective output 0, every constraint), or ``fallback``
+        when no seed is usable."""
+        self._sync_model()
+        out = self.engine.refine(self.b, np.asarray(seeds, dtype=np.float64), 0, kind,
+                                 lo=self.bound[:, 0] if lo is None else lo, hi=self.bound[:, 1] if hi is None else hi, x_0=x_0, r=r)
+        if out["best"] < 0:
+            return fallback
+        return out["best_x"], out["best_value"]
 
     def Minimizer(self):
         res = self.sweep()

@@ -29,6 +29,7 @@ SBO_E_COMM = -7
 SBO_E_UNSUPPORTED = -8
 
 SBO_FIT_FTOL, SBO_FIT_GTOL, SBO_FIT_MAXITER, SBO_FIT_LINESEARCH, SBO_FIT_NOT_PD = 0, 1, 2, 3, 4
+SBO_REFINE_CONVERGED, SBO_REFINE_MAX_EVAL, SBO_REFINE_NO_PROGRESS, SBO_REFINE_INFEASIBLE_SEED, SBO_REFINE_ON_BOUNDARY = 0, 1, 2, 3, 4
 
 
 class SweepOpts(C.Structure):
@@ -71,6 +72,18 @@ class RobustResult(C.Structure):
                 ("worst_d", C.c_double * SBO_MAX_D), ("candidate_index", C.c_int64), ("count_control", C.c_int64),
                 ("count_disturbance", C.c_int64), ("count_safe", C.c_int64), ("guard_band", C.c_int64), ("guard_rechecks", C.c_int64),
                 ("guard_passes", C.c_int32), ("reserved_g", C.c_int32)]
+
+
+class RefineOpts(C.Structure):
+    _fields_ = [("b", C.c_double), ("objective", C.c_int32), ("kind", C.c_int32), ("maximize", C.c_int32),
+                ("constraint_mask", C.c_uint32), ("lo", C.c_double * SBO_MAX_D), ("hi", C.c_double * SBO_MAX_D),
+                ("use_ball", C.c_int32), ("max_eval", C.c_int32), ("x_0", C.c_double * SBO_MAX_D), ("r", C.c_double),
+                ("tol", C.c_double)]
+
+
+class RefineResult(C.Structure):
+    _fields_ = [("best", C.c_int64), ("best_x", C.c_double * SBO_MAX_D), ("best_value", C.c_double), ("evaluations", C.c_int64),
+                ("converged", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Profile(C.Structure):
@@ -131,6 +144,7 @@ SYMBOLS = [
     ("sbo_nll_grad_batch", C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
     ("sbo_fit_local", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_double, C.c_double, _P, _P,
                                 _P, _P, _P, _P, _P, _P]),
+    ("sbo_refine", C.c_int, [_P, C.POINTER(RefineOpts), C.c_int64, _P, _P, _P, _P, C.POINTER(RefineResult)]),
     ("sbo_plant_wo", C.c_int, [_P, C.c_int64, _P, _P]),
     ("sbo_profile_get", C.c_int, [_P, C.POINTER(Profile)]),
     ("sbo_set_option", C.c_int, [_P, C.c_char_p, C.c_int64]),

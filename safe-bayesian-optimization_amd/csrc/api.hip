@@ -208,7 +208,7 @@ int sbo_shutdown(sbo_ctx* c) {
   }
   sbo_comm_destroy_internal(c);
   for (DevBuf* b : {&c->Fpk, &c->As, &c->sqA, &c->alpha, &c->Xn, &c->pts, &c->mean, &c->var, &c->maskS,
-                    &c->maskU, &c->maskM, &c->maskG, &c->maskO, &c->dist2, &c->dist2b, &c->coarse, &c->fitbuf, &c->fitwork, &c->scal, &c->partial, &c->amb, &c->runmeta, &c->bl_P0f, &c->bl_P1A, &c->bl_T4f, &c->bl_BtA, &c->bl_SBf, &c->bl_VA, &c->bl_small, &c->bl_work, &c->bl_cheb, &c->bl_basis, &c->mwork, &c->appendbuf, &c->rc_mean, &c->rc_var, &c->rc_list, &c->rc_refined, &c->Fplain, &c->alpha64, &c->blockmin, &c->blockmax, &c->cpart, &c->invk_img, &c->bl_lpart, &c->bl_grad, &c->scanlist, &c->gw, &c->Wfull, &c->Uwin, &c->ubits, &c->lane1.dist2, &c->lane1.dist2b, &c->lane1.coarse, &c->lane1.blockmin, &c->lane1.blockmax, &c->lane1.scanlist, &c->lane1.amb, &c->lane1.gw, &c->lane1.runmeta, &c->lane1.scal, &c->gather, &c->xch, &c->shard_first, &c->E0f, &c->Er, &c->AXg, &c->tn_pts, &c->tn_vals, &c->tn_work, &c->tn_W0t, &c->tn_W1t, &c->tn_probe, &c->tn_scr, &c->tn_tail, &c->fuseS, &c->fuseU, &c->tn_gather, &c->bi_params, &c->gb, &c->gb_pts, &c->gb_vals, &c->gb_probe, &c->gb_part, &c->list_scr, &c->cbS, &c->cbU, &c->cbM, &c->cbG, &c->cbUsum, &c->col_img, &c->col_bmin, &c->col_fin, &c->col_slots, &c->col_cimg, &c->col_cbmin, &c->audit_pts, &c->audit_val, &c->audit_part, &c->audit_cnt, &c->bl_encl, &c->bl_sched, &c->lxtree, &c->lane1.lxtree, &c->lx.box, &c->lx.keys, &c->lx.vals, &c->lx.hist, &c->lx.xs, &c->lx.stats})
+                    &c->maskU, &c->maskM, &c->maskG, &c->maskO, &c->dist2, &c->dist2b, &c->coarse, &c->fitbuf, &c->fitwork, &c->refbuf, &c->scal, &c->partial, &c->amb, &c->runmeta, &c->bl_P0f, &c->bl_P1A, &c->bl_T4f, &c->bl_BtA, &c->bl_SBf, &c->bl_VA, &c->bl_small, &c->bl_work, &c->bl_cheb, &c->bl_basis, &c->mwork, &c->appendbuf, &c->rc_mean, &c->rc_var, &c->rc_list, &c->rc_refined, &c->Fplain, &c->alpha64, &c->blockmin, &c->blockmax, &c->cpart, &c->invk_img, &c->bl_lpart, &c->bl_grad, &c->scanlist, &c->gw, &c->Wfull, &c->Uwin, &c->ubits, &c->lane1.dist2, &c->lane1.dist2b, &c->lane1.coarse, &c->lane1.blockmin, &c->lane1.blockmax, &c->lane1.scanlist, &c->lane1.amb, &c->lane1.gw, &c->lane1.runmeta, &c->lane1.scal, &c->gather, &c->xch, &c->shard_first, &c->E0f, &c->Er, &c->AXg, &c->tn_pts, &c->tn_vals, &c->tn_work, &c->tn_W0t, &c->tn_W1t, &c->tn_probe, &c->tn_scr, &c->tn_tail, &c->fuseS, &c->fuseU, &c->tn_gather, &c->bi_params, &c->gb, &c->gb_pts, &c->gb_vals, &c->gb_probe, &c->gb_part, &c->list_scr, &c->cbS, &c->cbU, &c->cbM, &c->cbG, &c->cbUsum, &c->col_img, &c->col_bmin, &c->col_fin, &c->col_slots, &c->col_cimg, &c->col_cbmin, &c->audit_pts, &c->audit_val, &c->audit_part, &c->audit_cnt, &c->bl_encl, &c->bl_sched, &c->lxtree, &c->lane1.lxtree, &c->lx.box, &c->lx.keys, &c->lx.vals, &c->lx.hist, &c->lx.xs, &c->lx.stats})
     release(*b);
   for (auto& b : c->tn_W) release(b);
   for (DevBuf* b : {&c->rob, &c->rob_mask, &c->rob_part}) release(*b);
@@ -384,6 +384,11 @@ int sbo_set_option(sbo_ctx* c, const char* key, int64_t value) {
     if (value && !c->comm && !c->relay_allreduce)
       return fail(SBO_E_INVALID, "comm_selftest needs a communicator: call sbo_comm_init(ctx, 1, 0, id) with a unique id first");
     c->comm_selftest = value ? 1 : 0;
+    return SBO_OK;
+  }
+  if (!strcmp(key, "refine_lds")) {
+    if (value < 0 || value > 1) return fail(SBO_E_INVALID, "refine_lds must be 0 (stream M) or 1 (LDS when it fits)");
+    c->refine_lds = (int)value;
     return SBO_OK;
   }
   if (!strcmp(key, "list_index")) {

@@ -282,6 +282,7 @@ struct sbo_ctx {
   sbo::DevBuf dist2;   // double [n_local] distance-transform scratch (x2 for ping-pong)
   sbo::DevBuf dist2b;
   sbo::DevBuf fitbuf, fitwork;   // hyper-parameter objective: inputs/outputs and the P x n x n factor workspace
+  sbo::DevBuf refbuf;            // sbo_refine: seeds, candidates, their exact values and the results (refine.hip)
   sbo::DevBuf coarse;  // coarse U mask + its distance transform (expander pre-decision)
   sbo::DevBuf scal;    // small device scalar block (keys, counters, arg-reduce results)
   // Second lane of the set phase (models with two or more constraints, one rank): the per-constraint chains of a sweep are
@@ -298,6 +299,7 @@ struct sbo_ctx {
   sbo::DevBuf runmeta; // GoOSE: per-run bounding boxes / radii of the coverage search
   sbo::ListIndex lx;    // spatial index of an explicit list (sets_index.inc.hpp)
   sbo::DevBuf lxtree;   // ... this sweep's boxes of U members / sorted U mask, or GoOSE's sorted weights and masks (per lane)
+  int refine_lds = 1;   // option (A/B checker): 1 sbo_refine stages M in LDS when it fits, 0 it always streams M's rows
   int list_index = -1;  // option: -1 the index for explicit lists above the exhaustive cap only, 0 never, 1 always
   sbo::DevBuf scanlist; // candidates left open by the coarse expander decision (wave-per-candidate scan)
   sbo::DevBuf blockmax; // per-block largest source weight along axis 0 (blocked axis-0 pass of the power transform)

@@ -1044,7 +1044,7 @@ int launch_posterior_on_list(sbo_ctx* c, const double* pts, long long N, double*
   if ((rc = ensure(c->list_scr, 512))) return rc;
   PostTarget t{};
   t.cs.kind = 0;
-  t.cs.d = c->cs.d;
+  t.cs.d = c->mc.d;               // (the model's d: a refine may run with no candidates resident)
   t.cs.pts_dtype = SBO_F64;
   t.cs.pts = pts;
   t.cs.n_local = N;

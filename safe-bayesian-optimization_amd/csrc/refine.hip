@@ -1,0 +1,602 @@
+// refine.hip -- sbo_refine: local refinement of an acquisition optimum off the candidate grid.
+//
+// The sweeps restate every continuous acquisition of the reference (SciPy DE in models/SafeOpt.py:47-51, models/GoOSE.py:63-67,
+// models/GP_TR.py:43-51; SLSQP multistarts in models/BayesRTOjax.py:17-85) as an arg-min over candidates.  This file polishes such
+// a winner: one workgroup per seed runs a projected BFGS on a log-barrier function of the exact fp64 posterior (box by projection,
+// lcb_c >= 0 and the trust-region ball by the barrier), the whole iteration inside one launch as k_fit_local does (fit.hip).  The
+// candidates it returns are then re-evaluated by the library's exact list evaluator (launch_posterior_on_list, the values
+// sbo_bounds gives at those points) and accepted only when they pass the sweep's S predicate there and are no worse than the seed.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+#include "internal.hpp"
+#include "device_common.hpp"
+
+namespace sbo {
+
+constexpr int kRefWaves = 16;                    // (1024 threads at most)
+constexpr double kRefMu0 = 1e-3;                 // barrier weight of the first stage (normalised objective units)
+constexpr double kRefMuStep = 0.1;               // geometric decrease per stage ...
+constexpr double kRefMuFloor = 1e-11;            // ... down to this floor
+constexpr int kRefDefaultEval = 400;             // posterior + gradient evaluations per seed
+constexpr int kRefMaxEval = 20000;               // ceiling of max_eval, lowered further for large n (sbo_refine)
+constexpr double kRefDefaultTol = 1e-9;          // projected-gradient inf-norm of the barrier function, in box-scaled coordinates
+constexpr size_t kRefLdsM = 144 * 1024;          // LDS tier: the used outputs' packed lower triangles of M fit in this many bytes
+
+struct RefineArgs {
+  ModelConst mc;
+  int nu;                    // distinct outputs evaluated (objective first)
+  int obj_slot;              // (always 0)
+  int con_slots;             // bit u: slot u is a constraint (lcb >= 0)
+  int kind, maximize, use_ball, max_eval, f_cap, a_ld, pad;
+  int outs[kMaxQ];           // slot -> output index
+  double b, tol, r;
+  double lo[kMaxD], hi[kMaxD], x0[kMaxD];
+};
+
+// one evaluation: per used slot the un-normalised mean / var and their gradients
+struct RefEval {
+  double m[kMaxQ], v[kMaxQ], gm[kMaxQ][kMaxD], gv[kMaxQ][kMaxD];
+  int clamp[kMaxQ];
+};
+
+struct RefState {
+  double x[kMaxD], g[kMaxD], p[kMaxD], H[kMaxD * kMaxD], D2[kMaxD], span[kMaxD], xb[kMaxD];
+  double fo, B, go[kMaxD], gB[kMaxD];     // objective part and barrier sum at x, with gradients
+  double f, mu, t, obj, objb;             // f = fo + mu B; obj / objb: sign-adjusted objective at x / at xb
+  int phase, nev, halvings, status, h_identity, nbar;
+};
+enum { REF_PH_START = 0, REF_PH_SEARCH = 1 };
+
+__device__ __forceinline__ double ref_clip(double v, double lo, double hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+// sums of cnt per-thread values over the workgroup: butterfly within a wave, then the waves in order (thread 0) -> out[]
+__device__ __forceinline__ void ref_block_sum(const double* v, int cnt, double (*part)[kMaxD + 1], double* out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+#pragma unroll
+  for (int k = 0; k < kMaxD + 1; ++k) {
+    if (k < cnt) {
+      double s = v[k];
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+      if (lane == 0) part[wave][k] = s;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int k = 0; k < cnt; ++k) {
+      double s = 0.0;
+      for (int w = 0; w < nw; ++w) s += part[w][k];
+      out[k] = s;
+    }
+  __syncthreads();
+}
+
+// mean / var and their gradients at x (LDS) for every used output.  M rows: LDS packed triangles (kLds) or Fplain (stride f_cap).
+template <bool kLds>
+__device__ void ref_eval(const RefineArgs& A, const double* x, const double* F, const double* Ml, const double* alpha,
+                         const double* Xn, double* kv, double* uv, double (*part)[kMaxD + 1], double* red, double* uup, RefEval& E) {
+  const ModelConst& mc = A.mc;
+  const int n = mc.n, d = mc.d, dp = mc.dpad;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6, bd = blockDim.x;
+  const size_t tri = (size_t)n * (n + 1) / 2;
+  double xn[kMaxD];
+#pragma unroll
+  for (int a = 0; a < kMaxD; ++a) xn[a] = a < d ? (x[a] - mc.X_mean[a]) / mc.X_std[a] : 0.0;
+  for (int u = 0; u < A.nu; ++u) {
+    const int o = A.outs[u];
+    const double* Mo = kLds ? Ml + (size_t)u * tri : F + (size_t)o * A.f_cap * A.f_cap;
+    const double* al = alpha + (size_t)o * A.a_ld;
+    const double sf2 = mc.sf2[o];
+    double ie[kMaxD];
+#pragma unroll
+    for (int a = 0; a < kMaxD; ++a) ie[a] = mc.inv_ell[o][a];
+    // k_j, k . alpha and its gradient
+    double acc[kMaxD + 1];
+#pragma unroll
+    for (int a = 0; a < kMaxD + 1; ++a) acc[a] = 0.0;
+    for (int j = tid; j < n; j += bd) {
+      double diff[kMaxD], dist = 0.0;
+#pragma unroll
+      for (int a = 0; a < kMaxD; ++a) {
+        diff[a] = a < d ? Xn[(size_t)j * dp + a] - xn[a] : 0.0;
+        if (a < d) dist += diff[a] * diff[a] * ie[a];
+      }
+      const double kj = sf2 * exp(-0.5 * dist);
+      kv[j] = kj;
+      const double ak = al[j] * kj;
+      acc[0] += ak;
+#pragma unroll
+      for (int a = 0; a < kMaxD; ++a)
+        if (a < d) acc[1 + a] += ak * diff[a] * ie[a];
+    }
+    ref_block_sum(acc, d + 1, part, red);         // (its barriers also publish kv)
+    // u = M k (one wave per row, rows in order), u . u
+    double uu = 0.0;
+    for (int i = wave; i < n; i += nw) {
+      const double* row = Mo + (kLds ? (size_t)i * (i + 1) / 2 : (size_t)i * A.f_cap);
+      double s = 0.0;
+      for (int j = lane; j <= i; j += 64) s += row[j] * kv[j];
+      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+      if (lane == 0) {
+        uv[i] = s;
+        uu += s * s;
+      }
+    }
+    if (lane == 0) uup[wave] = uu;
+    __syncthreads();
+    // w = M^T u, and sum_j w_j dk_j / dx
+    double gacc[kMaxD + 1];
+#pragma unroll
+    for (int a = 0; a < kMaxD + 1; ++a) gacc[a] = 0.0;
+    for (int j0 = 0; j0 < n; j0 += bd) {
+      const int j = j0 + tid;
+      const int jw = j0 + (wave << 6);              // the wave's first column: rows above it hold nothing for the wave
+      double w = 0.0;
+      for (int i = jw; i < n; ++i)
+        if (i >= j && j < n) w += Mo[(kLds ? (size_t)i * (i + 1) / 2 : (size_t)i * A.f_cap) + j] * uv[i];
+      if (j < n) {
+        const double wk = w * kv[j];
+#pragma unroll
+        for (int a = 0; a < kMaxD; ++a)
+          if (a < d) gacc[a] += wk * (Xn[(size_t)j * dp + a] - xn[a]) * ie[a];
+      }
+    }
+    ref_block_sum(gacc, d, part, red + kMaxD + 1);
+    if (tid == 0) {
+      double s = 0.0;
+      for (int w = 0; w < nw; ++w) s += uup[w];
+      const double ys = mc.Y_std[o], vn = sf2 - s;
+      E.m[u] = ys * (mc.mp[o] + red[0]) + mc.Y_mean[o];
+      E.v[u] = ys * ys * (vn > 0.0 ? vn : 0.0);
+      E.clamp[u] = !(vn > 0.0);
+      for (int a = 0; a < d; ++a) {
+        E.gm[u][a] = ys * red[1 + a] / mc.X_std[a];
+        E.gv[u][a] = -2.0 * ys * ys * red[kMaxD + 1 + a] / mc.X_std[a];
+      }
+    }
+    __syncthreads();                                // (kv / uv are rewritten for the next output)
+  }
+}
+
+// objective part (fo, go; obj = sign-adjusted objective) and barrier sum (B, gB) at x from an evaluation; false: the trial is rejected
+__device__ bool ref_terms(const RefineArgs& A, const RefEval& E, const double* x, double& fo, double* go, double& B, double* gB, double& obj) {
+  const int d = A.mc.d;
+  const double b = A.b;
+  double f, gf[kMaxD];
+  const int u0 = A.obj_slot;
+  if (A.kind == SBO_MEAN || ((A.kind == SBO_UCB || A.kind == SBO_LCB) && b == 0.0)) {
+    f = E.m[u0];
+    for (int a = 0; a < d; ++a) gf[a] = E.gm[u0][a];
+  } else if (A.kind == SBO_VAR) {
+    if (E.clamp[u0]) return false;
+    f = E.v[u0];
+    for (int a = 0; a < d; ++a) gf[a] = E.gv[u0][a];
+  } else {
+    if (E.clamp[u0] || !(E.v[u0] > 0.0)) return false;
+    const double sd = sqrt(E.v[u0]), sg = A.kind == SBO_UCB ? 1.0 : -1.0;
+    f = E.m[u0] + sg * b * sd;
+    for (int a = 0; a < d; ++a) gf[a] = E.gm[u0][a] + sg * b * E.gv[u0][a] / (2.0 * sd);
+  }
+  const double sg = A.maximize ? -1.0 : 1.0, ys = A.mc.Y_std[A.outs[u0]];
+  obj = sg * f;
+  fo = obj / ys;
+  bool ok = isfinite(fo);
+  for (int a = 0; a < d; ++a) {
+    go[a] = sg * gf[a] / ys;
+    gB[a] = 0.0;
+    ok = ok && isfinite(go[a]);
+  }
+  B = 0.0;
+  for (int u = 0; u < A.nu; ++u) {
+    if (!((A.con_slots >> u) & 1)) continue;
+    double gc = E.m[u], ggc[kMaxD];
+    for (int a = 0; a < d; ++a) ggc[a] = E.gm[u][a];
+    if (b != 0.0) {
+      if (E.clamp[u] || !(E.v[u] > 0.0)) return false;
+      const double sd = sqrt(E.v[u]);
+      gc = E.m[u] - b * sd;
+      for (int a = 0; a < d; ++a) ggc[a] -= b * E.gv[u][a] / (2.0 * sd);
+    }
+    if (!(gc > 0.0)) return false;
+    B -= log(gc / A.mc.Y_std[A.outs[u]]);
+    for (int a = 0; a < d; ++a) gB[a] -= ggc[a] / gc;
+  }
+  if (A.use_ball) {
+    double ss = 0.0;
+    for (int a = 0; a < d; ++a) ss += (x[a] - A.x0[a]) * (x[a] - A.x0[a]);
+    const double h = A.r * A.r - ss;
+    if (!(h > 0.0)) return false;
+    B -= log(h / (A.r * A.r));
+    for (int a = 0; a < d; ++a) gB[a] += 2.0 * (x[a] - A.x0[a]) / h;
+  }
+  ok = ok && isfinite(B);
+  for (int a = 0; a < d; ++a) ok = ok && isfinite(gB[a]);
+  return ok;
+}
+
+__device__ double ref_pgnorm(const RefState& S, const RefineArgs& A) {
+  double pg = 0.0;
+  for (int a = 0; a < A.mc.d; ++a)
+    if (S.span[a] > 0.0) pg = fmax(pg, fabs(ref_clip(S.x[a] - S.D2[a] * S.g[a], A.lo[a], A.hi[a]) - S.x[a]) / S.span[a]);
+  return pg;
+}
+
+__device__ void ref_reset_h(RefState& S, int d) {
+  for (int a = 0; a < d * d; ++a) S.H[a] = 0.0;
+  for (int a = 0; a < d; ++a) S.H[a * d + a] = S.D2[a];
+  S.h_identity = 1;
+}
+
+// Next search direction at the accepted point (lowering the barrier weight between stages): true with the first trial in `trial`
+__device__ bool ref_new_iteration(RefState& S, const RefineArgs& A, double* trial) {
+  const int d = A.mc.d;
+  for (;;) {
+    S.f = S.fo + S.mu * S.B;
+    for (int a = 0; a < d; ++a) S.g[a] = S.go[a] + S.mu * S.gB[a];
+    const double stol = S.mu > kRefMuFloor ? fmax(A.tol, S.mu) : A.tol;
+    if (ref_pgnorm(S, A) > stol) break;
+    if (S.mu <= kRefMuFloor) { S.status = SBO_REFINE_CONVERGED; return false; }
+    S.mu = fmax(kRefMuFloor, S.mu * kRefMuStep);
+  }
+  bool fr[kMaxD];
+  for (int a = 0; a < d; ++a)         // held: at a face with the gradient pointing out of the box (or a degenerate axis)
+    fr[a] = S.span[a] > 0.0 && !((S.x[a] <= A.lo[a] && S.g[a] > 0.0) || (S.x[a] >= A.hi[a] && S.g[a] < 0.0));
+  double gp = 0.0;
+  for (int a = 0; a < d; ++a) {
+    double s = 0.0;
+    if (fr[a])
+      for (int c = 0; c < d; ++c)
+        if (fr[c]) s += S.H[a * d + c] * S.g[c];
+    S.p[a] = -s;
+    gp += S.g[a] * S.p[a];
+  }
+  if (!(gp < 0.0)) {                  // not a descent direction: restart from (scaled) steepest descent
+    ref_reset_h(S, d);
+    for (int a = 0; a < d; ++a) S.p[a] = fr[a] ? -S.D2[a] * S.g[a] : 0.0;
+  }
+  double pn = 0.0;
+  for (int a = 0; a < d; ++a)
+    if (S.span[a] > 0.0) pn = fmax(pn, fabs(S.p[a]) / S.span[a]);
+  S.t = S.h_identity ? fmin(1.0, 0.1 / pn) : 1.0;   // a steepest-descent step moves at most a tenth of the (ball-limited) box
+  S.halvings = 0;
+  S.phase = REF_PH_SEARCH;
+  for (int a = 0; a < d; ++a) trial[a] = ref_clip(S.x[a] + S.t * S.p[a], A.lo[a], A.hi[a]);
+  return true;
+}
+
+// the end of a stage's line search without an acceptable point: the next stage, or the end at the floor
+__device__ bool ref_stage_end(RefState& S, const RefineArgs& A, double* trial) {
+  if (S.mu <= kRefMuFloor) { S.status = SBO_REFINE_CONVERGED; return false; }
+  S.mu = fmax(kRefMuFloor, S.mu * kRefMuStep);
+  return ref_new_iteration(S, A, trial);
+}
+
+// consume the evaluation of `trial`; true when `trial` holds the next point to evaluate
+__device__ __noinline__ bool ref_advance(RefState& S, const RefineArgs& A, const RefEval& E, double* trial) {
+  const int d = A.mc.d;
+  ++S.nev;
+  double fo, go[kMaxD], B, gB[kMaxD], obj;
+  const bool ok = ref_terms(A, E, trial, fo, go, B, gB, obj);
+  if (S.phase == REF_PH_START) {
+    if (!ok) { S.status = SBO_REFINE_NO_PROGRESS; return false; }   // the solver's own arithmetic cannot start at the seed
+    S.fo = fo; S.B = B; S.obj = S.objb = obj;
+    for (int a = 0; a < d; ++a) { S.go[a] = go[a]; S.gB[a] = gB[a]; }
+    S.mu = S.nbar ? kRefMu0 : kRefMuFloor;
+    if (S.nev >= A.max_eval) { S.status = SBO_REFINE_MAX_EVAL; return false; }
+    return ref_new_iteration(S, A, trial);
+  }
+  const double ft = fo + S.mu * B;
+  double dec = 0.0;
+  bool moved = false;
+  for (int a = 0; a < d; ++a) {
+    dec += S.g[a] * (trial[a] - S.x[a]);
+    moved = moved || trial[a] != S.x[a];
+  }
+  if (ok && moved && ft <= S.f + 1e-4 * dec) {                        // Armijo along the projection arc
+    double s[kMaxD], yv[kMaxD], sy = 0.0, ss = 0.0, yy = 0.0;
+    for (int a = 0; a < d; ++a) {
+      s[a] = trial[a] - S.x[a];
+      yv[a] = (go[a] + S.mu * gB[a]) - S.g[a];
+      sy += s[a] * yv[a];
+      ss += s[a] * s[a];
+      yy += yv[a] * yv[a];
+      S.x[a] = trial[a];
+      S.go[a] = go[a];
+      S.gB[a] = gB[a];
+    }
+    const double fprev = S.f;
+    S.fo = fo; S.B = B; S.obj = obj;
+    if (obj < S.objb) {
+      S.objb = obj;
+      for (int a = 0; a < d; ++a) S.xb[a] = S.x[a];
+    }
+    if (sy > 1e-10 * sqrt(ss * yy)) {                                 // BFGS update of the inverse Hessian, skipped unless s^T y > 0
+      if (S.h_identity) {
+        double yDy = 0.0;
+        for (int a = 0; a < d; ++a) yDy += yv[a] * S.D2[a] * yv[a];
+        const double scale = sy / yDy;
+        for (int a = 0; a < d; ++a) S.H[a * d + a] = scale * S.D2[a];
+        S.h_identity = 0;
+      }
+      double Hy[kMaxD], yHy = 0.0;
+      for (int a = 0; a < d; ++a) {
+        double v = 0.0;
+        for (int c = 0; c < d; ++c) v += S.H[a * d + c] * yv[c];
+        Hy[a] = v;
+        yHy += yv[a] * v;
+      }
+      const double rho = 1.0 / sy;
+      const double cc = rho * rho * yHy + rho;
+      for (int a = 0; a < d; ++a)
+        for (int c = 0; c < d; ++c) S.H[a * d + c] += cc * s[a] * s[c] - rho * (Hy[a] * s[c] + s[a] * Hy[c]);
+    }
+    if (S.nev >= A.max_eval) { S.status = SBO_REFINE_MAX_EVAL; return false; }
+    if (fabs(fprev - (S.fo + S.mu * S.B)) <= 1e-15 * (1.0 + fabs(fprev))) return ref_stage_end(S, A, trial);
+    return ref_new_iteration(S, A, trial);
+  }
+  if (S.nev >= A.max_eval) { S.status = SBO_REFINE_MAX_EVAL; return false; }
+  if (moved && S.halvings < 60) {                                    // backtrack
+    ++S.halvings;
+    S.t *= 0.5;
+    for (int a = 0; a < d; ++a) trial[a] = ref_clip(S.x[a] + S.t * S.p[a], A.lo[a], A.hi[a]);
+    return true;
+  }
+  if (S.h_identity) return ref_stage_end(S, A, trial);
+  ref_reset_h(S, d);                                                 // the quasi-Newton direction failed: one steepest-descent try
+  return ref_new_iteration(S, A, trial);
+}
+
+// the exact bound of models/SafeOpt.py:34-45 as k_bound computes it (posterior.hip)
+__device__ __forceinline__ double ref_bound(double m, double v, double b, int kind) {
+  if (kind == SBO_MEAN) return m;
+  if (kind == SBO_VAR) return v;
+  const double sd = mul_rn(b, sqrt_rn(v));
+  return kind == SBO_UCB ? add_rn(m, sd) : sub_rn(m, sd);
+}
+
+// the sweep's S predicate at x under exact values (mean / var [q][ld] at column g): 0 infeasible, 1 feasible, 2 feasible on a
+// barrier's boundary (some lcb_c == 0, or the ball's sphere)
+__device__ int ref_feasible(const RefineArgs& A, const double* x, const double* m, const double* v, long long ld, long long g) {
+  const int d = A.mc.d;
+  bool edge = false;
+  for (int a = 0; a < d; ++a)
+    if (!(x[a] >= A.lo[a] && x[a] <= A.hi[a])) return 0;          // (NaN / inf included)
+  if (A.use_ball) {
+    double ss = 0.0;
+    for (int a = 0; a < d; ++a) {
+      const double df = x[a] - A.x0[a];
+      ss = (a == 0) ? df * df : ss + df * df;                      // (k_ball_mask's formula)
+    }
+    const double dist = sqrt(ss);
+    if (!(dist <= A.r)) return 0;
+    edge = edge || dist == A.r;
+  }
+  for (int u = 0; u < A.nu; ++u) {
+    if (!((A.con_slots >> u) & 1)) continue;
+    const int o = A.outs[u];
+    const double l = ref_bound(m[(size_t)o * ld + g], v[(size_t)o * ld + g], A.b, SBO_LCB);
+    if (!(l >= 0.0)) return 0;
+    edge = edge || l == 0.0;
+  }
+  return edge ? 2 : 1;
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(1024) void k_refine(const RefineArgs* __restrict__ Ap, const double* __restrict__ F, const double* __restrict__ alpha,
+                                                 const double* __restrict__ Xn, const double* __restrict__ seeds,
+                                                 const double* __restrict__ m0, const double* __restrict__ v0, long long S,
+                                                 double* __restrict__ cand, int* __restrict__ st_out, int* __restrict__ nev_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ RefState R;
+  __shared__ RefEval E;
+  __shared__ double trial[kMaxD], red[2 * (kMaxD + 1)], uup[kRefWaves];
+  __shared__ double part[kRefWaves][kMaxD + 1];
+  __shared__ int go;
+  const RefineArgs& A = *Ap;                        // (in global memory: a kernarg copy indexed by output would go to scratch)
+  const ModelConst& mc = A.mc;
+  const int n = mc.n, d = mc.d;
+  const long long s = blockIdx.x;
+  double* kv = reinterpret_cast<double*>(smem);
+  double* uv = kv + n;
+  double* Ml = uv + n;
+  if (kLds) {                                       // the used outputs' triangles of M, packed row after row
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const size_t tri = (size_t)n * (n + 1) / 2;
+    for (int u = 0; u < A.nu; ++u) {
+      const double* Fo = F + (size_t)A.outs[u] * A.f_cap * A.f_cap;
+      for (int i = wave; i < n; i += nw)
+        for (int j = lane; j <= i; j += 64) Ml[u * tri + (size_t)i * (i + 1) / 2 + j] = Fo[(size_t)i * A.f_cap + j];
+    }
+  }
+  if (threadIdx.x == 0) {
+    for (int a = 0; a < d; ++a) {
+      trial[a] = seeds[s * d + a];
+      R.x[a] = R.xb[a] = trial[a];
+      const double w = A.hi[a] - A.lo[a];
+      R.span[a] = A.use_ball ? fmin(w, 2.0 * A.r) : w;
+      R.D2[a] = R.span[a] * R.span[a];
+    }
+    const int fe = ref_feasible(A, trial, m0, v0, S, s);
+    R.nev = 0;
+    R.status = fe == 0 ? SBO_REFINE_INFEASIBLE_SEED : fe == 2 ? SBO_REFINE_ON_BOUNDARY : -1;
+    R.nbar = __popc((unsigned)A.con_slots) + (A.use_ball ? 1 : 0);
+    R.phase = REF_PH_START;
+    ref_reset_h(R, d);
+    go = R.status < 0;
+  }
+  __syncthreads();
+  while (go) {
+    ref_eval<kLds>(A, trial, F, Ml, alpha, Xn, kv, uv, part, red, uup, E);
+    if (threadIdx.x == 0) go = ref_advance(R, A, E, trial);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    for (int a = 0; a < d; ++a) {
+      cand[(2 * s) * d + a] = R.x[a];
+      cand[(2 * s + 1) * d + a] = R.xb[a];
+    }
+    st_out[s] = R.status;
+    nev_out[s] = R.nev;
+  }
+}
+
+// acceptance under exact values: the final iterate or the best-objective iterate when feasible there and no worse than the seed
+// (the better of the two, ties to the final iterate), else the seed
+__global__ void k_refine_accept(const RefineArgs* __restrict__ Ap, long long S, const double* __restrict__ seeds, const double* __restrict__ m0,
+                                const double* __restrict__ v0, const double* __restrict__ cand, const double* __restrict__ m1,
+                                const double* __restrict__ v1, int* __restrict__ st, double* __restrict__ x_out,
+                                double* __restrict__ val_out) {
+  const RefineArgs& A = *Ap;
+  const int d = A.mc.d, o = A.outs[A.obj_slot];
+  const double sg = A.maximize ? -1.0 : 1.0;
+  for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < S; s += (long long)gridDim.x * blockDim.x) {
+    const double fs = ref_bound(m0[(size_t)o * S + s], v0[(size_t)o * S + s], A.b, A.kind);
+    int status = st[s];
+    int pick = -1;                                   // -1 seed, 0 final iterate, 1 best iterate
+    double fv = fs;
+    if (status != SBO_REFINE_INFEASIBLE_SEED && status != SBO_REFINE_ON_BOUNDARY) {
+      double best = 0.0;
+      for (int k = 0; k < 2; ++k) {
+        const long long g = 2 * s + k;
+        if (!ref_feasible(A, cand + g * d, m1, v1, 2 * S, g)) continue;
+        const double f = ref_bound(m1[(size_t)o * 2 * S + g], v1[(size_t)o * 2 * S + g], A.b, A.kind);
+        if (!(sg * f <= sg * fs)) continue;
+        if (pick < 0 || sg * f < best) { pick = k; best = sg * f; fv = f; }
+      }
+      if (pick < 0) status = SBO_REFINE_NO_PROGRESS;
+    }
+    const double* xs = pick < 0 ? seeds + s * d : cand + (2 * s + pick) * d;
+    for (int a = 0; a < d; ++a) x_out[s * d + a] = xs[a];
+    val_out[s] = fv;
+    st[s] = status;
+  }
+}
+
+}  // namespace sbo
+
+using namespace sbo;
+
+extern "C" int sbo_refine(sbo_ctx* c, const sbo_refine_opts* opts, int64_t n_seeds, const double* seeds, double* x_out,
+                          double* value_out, int32_t* status_out, sbo_refine_result* result) {
+  if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
+  if (!opts || !seeds || !result) return fail(SBO_E_INVALID, "NULL argument");
+  if (!c->has_model) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
+  if (c->dtype != SBO_F64) return fail(SBO_E_UNSUPPORTED, "sbo_refine needs an fp64 model");
+  const ModelConst& mc = c->mc;
+  const int d = mc.d, q = mc.q;
+  if (n_seeds < 1 || n_seeds > (1LL << 24)) return fail(SBO_E_INVALID, "n_seeds out of range");
+  if (opts->objective < 0 || opts->objective >= q) return fail(SBO_E_INVALID, "objective output out of range");
+  if (opts->kind < SBO_MEAN || opts->kind > SBO_VAR) return fail(SBO_E_INVALID, "bad bound kind");
+  if (opts->maximize != 0 && opts->maximize != 1) return fail(SBO_E_INVALID, "maximize must be 0 or 1");
+  if ((opts->constraint_mask & 1u) || (q < 32 && (opts->constraint_mask >> q) != 0))
+    return fail(SBO_E_INVALID, "constraint_mask: bit 0 must be clear and no bit may reach q");
+  if (!(opts->b >= 0.0) || !std::isfinite(opts->b)) return fail(SBO_E_INVALID, "confidence multiplier b must be finite and >= 0");
+  if (std::isnan(opts->tol)) return fail(SBO_E_INVALID, "tol is NaN");
+  for (int a = 0; a < d; ++a)
+    if (!std::isfinite(opts->lo[a]) || !std::isfinite(opts->hi[a]) || !(opts->lo[a] <= opts->hi[a]))
+      return fail(SBO_E_INVALID, "box needs finite lo <= hi");
+  if (opts->use_ball != 0 && opts->use_ball != 1) return fail(SBO_E_INVALID, "use_ball must be 0 or 1");
+  if (opts->use_ball) {
+    if (!(opts->r > 0.0) || !std::isfinite(opts->r)) return fail(SBO_E_INVALID, "ball radius must be finite and > 0");
+    for (int a = 0; a < d; ++a)
+      if (!std::isfinite(opts->x_0[a])) return fail(SBO_E_INVALID, "ball centre must be finite");
+  }
+  SBO_HIP(hipSetDevice(c->device));
+  int rc;
+  if ((rc = factor_sync(c))) return rc;             // (Fplain may still be in the making: the deferred factor chain)
+  RefineArgs A{};
+  A.mc = mc;
+  A.outs[0] = opts->objective;
+  A.nu = 1;
+  for (int o = 1; o < q; ++o) {
+    if (!((opts->constraint_mask >> o) & 1u)) continue;
+    if (o == opts->objective) { A.con_slots |= 1; continue; }
+    A.con_slots |= 1 << A.nu;
+    A.outs[A.nu++] = o;
+  }
+  A.obj_slot = 0;
+  A.kind = opts->kind;
+  A.maximize = opts->maximize;
+  A.use_ball = opts->use_ball;
+  // one launch holds a CU for max_eval evaluations of O(n^2) each: the ceiling keeps a call near a few seconds at n = 2048
+  const int eval_cap = (int)std::min<double>(kRefMaxEval, std::max<double>(kRefDefaultEval, 4e9 / ((double)mc.n * mc.n)));
+  A.max_eval = opts->max_eval > 0 ? std::min(opts->max_eval, eval_cap) : kRefDefaultEval;
+  A.f_cap = c->f_cap;
+  A.a_ld = c->a_ld;
+  A.b = opts->b;
+  A.tol = opts->tol > 0.0 ? opts->tol : kRefDefaultTol;
+  A.r = opts->use_ball ? opts->r : 0.0;
+  for (int a = 0; a < d; ++a) {
+    A.lo[a] = opts->lo[a];
+    A.hi[a] = opts->hi[a];
+    A.x0[a] = opts->use_ball ? opts->x_0[a] : 0.0;
+  }
+  const long long S = n_seeds;
+  // scratch: the arguments | seeds | mean0 var0 [q][S] | cand [2 S][d] | mean1 var1 [q][2 S] | x_out [S][d] | val [S] | status, evaluations [S]
+  const size_t ael = (sizeof(RefineArgs) + 255) / 256 * 32;
+  const size_t el = ael + (size_t)S * d + 2 * (size_t)q * S + 2 * (size_t)S * d + 4 * (size_t)q * S + (size_t)S * d + S + S;
+  if ((rc = ensure(c->refbuf, sizeof(double) * el))) return rc;
+  RefineArgs* dA = (RefineArgs*)c->refbuf.p;
+  double* dseed = (double*)c->refbuf.p + ael;
+  double* m0 = dseed + (size_t)S * d;
+  double* v0 = m0 + (size_t)q * S;
+  double* cand = v0 + (size_t)q * S;
+  double* m1 = cand + 2 * (size_t)S * d;
+  double* v1 = m1 + 2 * (size_t)q * S;
+  double* dx = v1 + 2 * (size_t)q * S;
+  double* dval = dx + (size_t)S * d;
+  int* dst = reinterpret_cast<int*>(dval + S);
+  int* dnev = dst + S;
+  SBO_HIP(hipMemcpyAsync(dA, &A, sizeof(RefineArgs), hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemcpyAsync(dseed, seeds, sizeof(double) * (size_t)S * d, hipMemcpyHostToDevice, c->stream));
+  if ((rc = launch_posterior_on_list(c, dseed, S, m0, v0))) return rc;
+  const int n = mc.n;
+  const size_t tri_bytes = sizeof(double) * (size_t)A.nu * n * (n + 1) / 2;
+  const bool lds_tier = c->refine_lds && tri_bytes <= kRefLdsM;
+  const size_t lds = sizeof(double) * 2 * (size_t)n + (lds_tier ? tri_bytes : 0);
+  const int threads = n > 256 ? 1024 : 256;
+  if (S > 0x7fffffffLL) return fail(SBO_E_UNSUPPORTED, "too many seeds for one launch");
+  if (lds_tier) {
+    SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_refine<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_refine<true>, dim3((unsigned)S), dim3(threads), lds, c->stream, (const RefineArgs*)dA, (const double*)c->Fplain.p,
+                       (const double*)c->alpha64.p, (const double*)c->Xn.p, (const double*)dseed, (const double*)m0,
+                       (const double*)v0, S, cand, dst, dnev);
+  } else {
+    SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_refine<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_refine<false>, dim3((unsigned)S), dim3(threads), lds, c->stream, (const RefineArgs*)dA, (const double*)c->Fplain.p,
+                       (const double*)c->alpha64.p, (const double*)c->Xn.p, (const double*)dseed, (const double*)m0,
+                       (const double*)v0, S, cand, dst, dnev);
+  }
+  SBO_HIP(hipGetLastError());
+  if ((rc = launch_posterior_on_list(c, cand, 2 * S, m1, v1))) return rc;
+  hipLaunchKernelGGL(k_refine_accept, dim3((unsigned)std::min<long long>((S + 255) / 256, 1024)), dim3(256), 0, c->stream, (const RefineArgs*)dA, S,
+                     (const double*)dseed, (const double*)m0, (const double*)v0, (const double*)cand, (const double*)m1,
+                     (const double*)v1, dst, dx, dval);
+  SBO_HIP(hipGetLastError());
+  std::vector<double> hx((size_t)S * d), hv(S);
+  std::vector<int> hs(2 * (size_t)S);
+  SBO_HIP(hipMemcpyAsync(hx.data(), dx, sizeof(double) * (size_t)S * d, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipMemcpyAsync(hv.data(), dval, sizeof(double) * S, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipMemcpyAsync(hs.data(), dst, sizeof(int) * 2 * (size_t)S, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipStreamSynchronize(c->stream));
+  sbo_refine_result res{};
+  res.best = -1;
+  res.best_value = NAN;
+  const double sg = opts->maximize ? -1.0 : 1.0;
+  for (long long s = 0; s < S; ++s) {
+    res.evaluations += hs[S + s];
+    if (hs[s] == SBO_REFINE_CONVERGED) ++res.converged;
+    if (hs[s] == SBO_REFINE_INFEASIBLE_SEED || std::isnan(hv[s])) continue;
+    if (res.best < 0 || sg * hv[s] < sg * res.best_value) {           // (ties: the lowest index)
+      res.best = s;
+      res.best_value = hv[s];
+    }
+  }
+  for (int a = 0; a < SBO_MAX_D; ++a) res.best_x[a] = (res.best >= 0 && a < d) ? hx[(size_t)res.best * d + a] : 0.0;
+  *result = res;
+  if (x_out) std::copy(hx.begin(), hx.end(), x_out);
+  if (value_out) std::copy(hv.begin(), hv.end(), value_out);
+  if (status_out)
+    for (long long s = 0; s < S; ++s) status_out[s] = hs[s];
+  return SBO_OK;
+}

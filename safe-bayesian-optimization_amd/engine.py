@@ -281,6 +281,64 @@ class SweepEngine:
         L.check(self._lib.sbo_explore_safeset(self._ctx, _ptr(t), C.byref(idx), _ptr(x)))
         return int(idx.value), x[:self.d].copy()
 
+    def refine(self, b: float, seeds, objective: int = 0, kind: str = "lcb", maximize: bool = False, constraints=None, *, lo, hi,
+               x_0=None, r=None, max_eval: int | None = None, tol: float | None = None) -> dict:
+        """Local refinement off the grid: each seed [d] of ``seeds`` [S, d] moves to a local optimum of
+        ``kind`` ("mean" / "ucb" / "lcb" / "var") of output ``objective`` (minimised, or maximised) over the box [lo, hi], the
+        constraints lcb_c >= 0 (``constraints``: output indices, None = every constraint output, [] = none) and, with ``x_0`` and
+        ``r``, the ball ||x - x_0|| <= r.  Every returned point is feasible under the exact values ``bounds`` gives there and no worse
+        than its seed.  Returns per seed ``x`` [S, d], ``value`` [S], ``status`` [S] (SBO_REFINE_*), and ``best`` (-1 if no seed was
+        usable), ``best_x``, ``best_value``, ``evaluations``, ``converged``.  The resident candidates, posterior and masks are not
+        touched."""
+        k = {"mean": L.SBO_MEAN, "ucb": L.SBO_UCB, "lcb": L.SBO_LCB, "var": L.SBO_VAR}.get(kind)
+        if k is None:
+            raise ValueError("kind must be 'mean', 'ucb', 'lcb' or 'var'")
+        d = self.d
+        S = _f64(seeds)
+        if S.ndim == 1:
+            S = S.reshape(1, -1)
+        if d < 1 or S.ndim != 2 or S.shape[1] != d:
+            raise ValueError("seeds must be [S, d] for the model's d")
+        S = np.ascontiguousarray(S)
+        opts = L.RefineOpts()
+        opts.b = float(b)
+        opts.objective = int(objective)
+        opts.kind = k
+        opts.maximize = int(bool(maximize))
+        cons = range(1, self.q) if constraints is None else constraints
+        mask = 0
+        for c in cons:
+            c = int(c)
+            if c < 0 or c >= 32:
+                raise ValueError("constraint index out of range")
+            mask |= 1 << c
+        opts.constraint_mask = mask
+        lo, hi = _f64(lo).reshape(-1), _f64(hi).reshape(-1)
+        if lo.shape != (d,) or hi.shape != (d,):
+            raise ValueError("lo and hi must have shape [d]")
+        for a in range(d):
+            opts.lo[a], opts.hi[a] = lo[a], hi[a]
+        if (x_0 is None) != (r is None):
+            raise ValueError("the ball needs both x_0 and r")
+        if x_0 is not None:
+            x0 = _f64(x_0).reshape(-1)
+            if x0.shape != (d,):
+                raise ValueError("x_0 must have shape [d]")
+            opts.use_ball = 1
+            for a in range(d):
+                opts.x_0[a] = x0[a]
+            opts.r = float(r)
+        opts.max_eval = int(max_eval) if max_eval is not None else 0
+        opts.tol = float(tol) if tol is not None else 0.0
+        n = S.shape[0]
+        x = np.empty((n, d))
+        val = np.empty(n)
+        st = np.empty(n, dtype=np.int32)
+        res = L.RefineResult()
+        L.check(self._lib.sbo_refine(self._ctx, C.byref(opts), n, _ptr(S), _ptr(x), _ptr(val), _ptr(st), C.byref(res)))
+        return {"x": x, "value": val, "status": st, "best": int(res.best), "best_x": np.array(res.best_x[:d]),
+                "best_value": float(res.best_value), "evaluations": int(res.evaluations), "converged": int(res.converged)}
+
     def mask(self, which: str, c: int = 0) -> np.ndarray:
         w = {"S": L.SBO_MASK_S, "U": L.SBO_MASK_U, "M": L.SBO_MASK_M, "G": L.SBO_MASK_G, "O": L.SBO_MASK_O}[which]
         out = np.empty(self.n_local, dtype=np.uint8)
