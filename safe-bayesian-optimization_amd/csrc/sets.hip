@@ -766,7 +766,8 @@ struct ValDist {           // Euclidean distance to the target, as scipy.spatial
   CandSpec cs;
   const double* target;
   __device__ __forceinline__ void bind(const GuardBand*) {}
-  __device__ __forceinline__ T operator()(long long g, double& d) const {
+  // (a double for every T: distances that differ in fp64 can collide when rounded to float, and the arg-min is the fp64 one)
+  __device__ __forceinline__ double operator()(long long g, double& d) const {
     d = 0.0;                               // (geometry: exact)
     double x[D];
     cand_coords<D>(cs, g, x);
@@ -778,7 +779,7 @@ struct ValDist {           // Euclidean distance to the target, as scipy.spatial
         ss += df * df;
       }
     }
-    return (T)sqrt(ss);
+    return sqrt(ss);
   }
 };
 
@@ -786,6 +787,7 @@ struct ValDist {           // Euclidean distance to the target, as scipy.spatial
 template <typename T, bool MAX, typename V>
 __device__ __forceinline__ void arg_masked_body(int bid, int nwg, const V& val_in, const uint8_t* __restrict__ mask, long long n,
                                                 long long first, Best* partial, const GuardBand* __restrict__ gb) {
+  using VT = decltype(val_in(0ll, *(double*)nullptr));   // the source's own value type (T, or double for distances)
   V val = val_in;
   val.bind(gb);
   Best best = best_none<MAX>();
@@ -797,14 +799,14 @@ __device__ __forceinline__ void arg_masked_body(int bid, int nwg, const V& val_i
     const long long base = t * 512;
     const unsigned long long w = ((const unsigned long long*)(mask + base))[lane];
     if (__ballot(w != 0ull) == 0ull) continue;
-    T v[8];
+    VT v[8];
     double dd[8];
     bool set[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       set[k] = tile_byte(w, k, lane);
       dd[k] = 0.0;
-      v[k] = set[k] ? val(base + k * 64 + lane, dd[k]) : (T)0;
+      v[k] = set[k] ? val(base + k * 64 + lane, dd[k]) : (VT)0;
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -819,7 +821,7 @@ __device__ __forceinline__ void arg_masked_body(int bid, int nwg, const V& val_i
     if (mask[g]) {
       ++cnt;
       double d = 0.0;
-      const T v = val(g, d);
+      const VT v = val(g, d);
       if constexpr (V::kUniform) best_take_uni<MAX>(best, (double)v, first + g);
       else best_take<MAX>(best, (double)v, d, first + g);
     }

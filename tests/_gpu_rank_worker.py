@@ -7,8 +7,10 @@ import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
+sys.path.insert(0, HERE)
 
 
 def main():
@@ -26,9 +28,19 @@ def main():
         cfg_name, dtype = cfg_name[:-4], "f32"
     if cfg_name.endswith(":guard"):                    # every sweep re-evaluates its guard-band candidates (option guard_band 2)
         cfg_name, guard = cfg_name[:-6], 2
-    cfg = synthetic.make_config(cfg_name, n=n)
+    tie = cfg_name.startswith("tie:")
+    if tie:                                            # "tie:<mirror grid>:<q>": a tests/tie_cases.py mirror model on the exact kernel
+        import tie_cases
+        _, grid, q = cfg_name.split(":")
+        lo, hi, _ = tie_cases.mirror_grid(grid)
+        cfg = {"ds": tie_cases.mirror_model(q=int(q), n=n), "bound": np.stack([lo, hi], axis=1), "q": int(q)}
+    else:
+        cfg = synthetic.make_config(cfg_name, n=n)
     eng = safebo_amd.SweepEngine(0)
     distributed.join(eng, dist, relay=True)
+    if tie:
+        eng.set_option("bilinear", 0)
+        eng.set_option("tensor_cheb", 0)
     if guard is not None:
         eng.set_option("guard_band", guard)
     eng.set_model(cfg["ds"], dtype=dtype, use_invK=(dtype == "f64"))
@@ -48,7 +60,10 @@ def main():
             masks.update({f"O{c}": eng.mask("O", c) for c in range(1, cfg["q"])})
         except safebo_amd.EmptySafeSetError:
             gres = {"empty_safe_set": True}
-    if dtype == "f32" or guard is not None:
+    if tie:
+        # (a ball centred on the mirror line: the trust region's winner ties across the ranks as well)
+        tres = eng.sweep_tr(b, np.array([0.25] + [0.0] * (cfg["bound"].shape[0] - 1)), 0.75, posterior_ready=True)
+    elif dtype == "f32" or guard is not None:
         # the trust-region sweep of GP_TR (ball of radius 0.3 of the box around its centre) across the ranks
         x0 = cfg["bound"].mean(axis=1)
         tres = eng.sweep_tr(b, x0, 0.3 * float(np.min(cfg["bound"][:, 1] - cfg["bound"][:, 0])))

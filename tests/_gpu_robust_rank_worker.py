@@ -20,8 +20,14 @@ def main():
     from test_gpu_robust import make_model
 
     dist = distributed.init_from_env()
-    ds, lo, hi = make_model(spec["d"], spec["q"], spec["n"], spec["seed"])
     eng = safebo_amd.SweepEngine(0)
+    if spec.get("tie"):                                # a tests/tie_cases.py mirror model (mirrored in the sharded axis), exact kernel
+        import tie_cases
+        ds, lo, hi = tie_cases.mirror_model(q=spec["q"]), np.array(spec["lo"]), np.array(spec["hi"])
+        eng.set_option("bilinear", 0)
+        eng.set_option("tensor_cheb", 0)
+    else:
+        ds, lo, hi = make_model(spec["d"], spec["q"], spec["n"], spec["seed"])
     distributed.join(eng, dist, relay=True)
     eng.set_model(ds, mean_prior=np.zeros(spec["q"]))
     eng.set_grid_sharded(lo, hi, spec["count"])
