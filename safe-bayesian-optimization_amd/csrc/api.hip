@@ -154,9 +154,11 @@ int sbo_init(int device_id, sbo_ctx** out) {
   // the sweep's scalar block and, 3 KB further, the Lipschitz keys: one allocation, so one read-back covers both
   // (layout of the 4 KB: SweepScalars at 0, the explore target / trust-region centre at 2048, the keys at 3072, a
   // collective's scratch word at 4000)
-  int rc = ensure(c->scal, 4096);
+  c->lane[0].stream = c->stream;
+  c->lane[1].stream = c->stream2;
+  int rc = ensure(c->lane[0].scal, 4096);
   if (rc) { delete c; return rc; }
-  c->Lmax.p = (char*)c->scal.p + 3072;   // (a view: not in the release list)
+  c->Lmax.p = (char*)c->lane[0].scal.p + 3072;   // (a view: not in the release list)
   c->Lmax.bytes = 512;
   *out = c;
   return SBO_OK;
@@ -182,9 +184,11 @@ static int shadow_ensure(sbo_ctx* c) {
   s->h_back = c->h_back;
   s->fp64_recheck = 0;
   s->bilinear = 0;
-  int rc = ensure(s->scal, 4096);
+  s->lane[0].stream = c->stream;
+  s->lane[1].stream = c->stream2;
+  int rc = ensure(s->lane[0].scal, 4096);
   if (rc) { delete s; return rc; }
-  s->Lmax.p = (char*)s->scal.p + 3072;
+  s->Lmax.p = (char*)s->lane[0].scal.p + 3072;
   s->Lmax.bytes = 512;
   c->shadow = s;
   return SBO_OK;
@@ -200,7 +204,7 @@ int sbo_shutdown(sbo_ctx* c) {
   if (c->stream4) (void)hipStreamSynchronize(c->stream4);
   if (c->shadow) {
     sbo_ctx* s = c->shadow;
-    for (DevBuf* b : {&s->Fpk, &s->As, &s->sqA, &s->alpha, &s->Xn, &s->pts, &s->mean, &s->var, &s->scal, &s->mwork, &s->appendbuf, &s->Fplain, &s->alpha64})
+    for (DevBuf* b : {&s->Fpk, &s->As, &s->sqA, &s->alpha, &s->Xn, &s->pts, &s->mean, &s->var, &s->lane[0].scal, &s->mwork, &s->appendbuf, &s->Fplain, &s->alpha64})
       release(*b);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
     delete s;
@@ -208,8 +212,10 @@ int sbo_shutdown(sbo_ctx* c) {
   }
   sbo_comm_destroy_internal(c);
   for (DevBuf* b : {&c->Fpk, &c->As, &c->sqA, &c->alpha, &c->Xn, &c->pts, &c->mean, &c->var, &c->maskS,
-                    &c->maskU, &c->maskM, &c->maskG, &c->maskO, &c->dist2, &c->dist2b, &c->coarse, &c->fitbuf, &c->fitwork, &c->refbuf, &c->scal, &c->partial, &c->amb, &c->runmeta, &c->bl_P0f, &c->bl_P1A, &c->bl_T4f, &c->bl_BtA, &c->bl_SBf, &c->bl_VA, &c->bl_small, &c->bl_work, &c->bl_cheb, &c->bl_basis, &c->mwork, &c->appendbuf, &c->rc_mean, &c->rc_var, &c->rc_list, &c->rc_refined, &c->Fplain, &c->alpha64, &c->blockmin, &c->blockmax, &c->cpart, &c->invk_img, &c->bl_lpart, &c->bl_grad, &c->scanlist, &c->gw, &c->Wfull, &c->Uwin, &c->ubits, &c->lane1.dist2, &c->lane1.dist2b, &c->lane1.coarse, &c->lane1.blockmin, &c->lane1.blockmax, &c->lane1.scanlist, &c->lane1.amb, &c->lane1.gw, &c->lane1.runmeta, &c->lane1.scal, &c->gather, &c->xch, &c->shard_first, &c->E0f, &c->Er, &c->AXg, &c->tn_pts, &c->tn_vals, &c->tn_work, &c->tn_W0t, &c->tn_W1t, &c->tn_probe, &c->tn_scr, &c->tn_tail, &c->fuseS, &c->fuseU, &c->tn_gather, &c->bi_params, &c->gb, &c->gb_pts, &c->gb_vals, &c->gb_probe, &c->gb_part, &c->list_scr, &c->cbS, &c->cbU, &c->cbM, &c->cbG, &c->cbUsum, &c->col_img, &c->col_bmin, &c->col_fin, &c->col_slots, &c->col_cimg, &c->col_cbmin, &c->audit_pts, &c->audit_val, &c->audit_part, &c->audit_cnt, &c->bl_encl, &c->bl_sched, &c->lxtree, &c->lane1.lxtree, &c->lx.box, &c->lx.keys, &c->lx.vals, &c->lx.hist, &c->lx.xs, &c->lx.stats})
+                    &c->maskU, &c->maskM, &c->maskG, &c->maskO, &c->fitbuf, &c->fitwork, &c->refbuf, &c->partial, &c->bl_P0f, &c->bl_P1A, &c->bl_T4f, &c->bl_BtA, &c->bl_SBf, &c->bl_VA, &c->bl_small, &c->bl_work, &c->bl_cheb, &c->bl_basis, &c->mwork, &c->appendbuf, &c->rc_mean, &c->rc_var, &c->rc_list, &c->rc_refined, &c->Fplain, &c->alpha64, &c->cpart, &c->invk_img, &c->bl_lpart, &c->bl_grad, &c->Wfull, &c->Uwin, &c->ubits, &c->gather, &c->xch, &c->shard_first, &c->E0f, &c->Er, &c->AXg, &c->tn_pts, &c->tn_vals, &c->tn_work, &c->tn_W0t, &c->tn_W1t, &c->tn_probe, &c->tn_scr, &c->tn_tail, &c->fuseS, &c->fuseU, &c->tn_gather, &c->bi_params, &c->gb, &c->gb_pts, &c->gb_vals, &c->gb_probe, &c->gb_part, &c->list_scr, &c->cbS, &c->cbU, &c->cbM, &c->cbG, &c->cbUsum, &c->col_img, &c->col_bmin, &c->col_fin, &c->col_slots, &c->col_cimg, &c->col_cbmin, &c->audit_pts, &c->audit_val, &c->audit_part, &c->audit_cnt, &c->bl_encl, &c->bl_sched, &c->lx.box, &c->lx.keys, &c->lx.vals, &c->lx.hist, &c->lx.xs, &c->lx.stats})
     release(*b);
+  for (auto& ln : c->lane)
+    for (DevBuf* b : ln.bufs()) release(*b);
   for (auto& b : c->tn_W) release(b);
   for (DevBuf* b : {&c->rob, &c->rob_mask, &c->rob_part}) release(*b);
   for (auto& ev : c->ev)

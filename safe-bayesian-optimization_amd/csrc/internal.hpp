@@ -279,32 +279,36 @@ struct sbo_ctx {
   sbo::DevBuf Lmax;    // [kMaxQ] uint64 keys: max ||grad MEAN_i||_inf over the candidates
   // set workspace
   sbo::DevBuf maskS, maskU, maskM, maskG, maskO;   // uint8 [n_local] (G/O: [(q-1)][n_local])
-  sbo::DevBuf dist2;   // double [n_local] distance-transform scratch (x2 for ping-pong)
-  sbo::DevBuf dist2b;
   sbo::DevBuf fitbuf, fitwork;   // hyper-parameter objective: inputs/outputs and the P x n x n factor workspace
   sbo::DevBuf refbuf;            // sbo_refine: seeds, candidates, their exact values and the results (refine.hip)
-  sbo::DevBuf coarse;  // coarse U mask + its distance transform (expander pre-decision)
-  sbo::DevBuf scal;    // small device scalar block (keys, counters, arg-reduce results)
-  // Second lane of the set phase (models with two or more constraints, one rank): the per-constraint chains of a sweep are
-  // independent, so every other constraint is enqueued on stream2 with its own scratch and its own copy of the scalar block
-  // (the chains only write its recheck / scan counters).  The host swaps these in and out of the fields above around the
-  // calls that enqueue a lane-1 constraint (sets.hip: lane_swap).
+  // What one per-constraint chain of the set phase enqueues on and scribbles in.  Lane 0 is the main stream's: everything before
+  // the fork and after the join, every sweep of a model with one constraint and every sweep on several ranks uses it alone.  With
+  // two or more constraints on one rank the chains are independent, so every other constraint goes to lane 1: stream2, its own
+  // scratch, and a snapshot of the scalar block that k_classify_final writes (the chains only write its recheck / scan counters;
+  // the finals merge them).  The chain's functions take the lane as a parameter (sets.hip); no field here changes to select one.
   struct SetLane {
-    sbo::DevBuf dist2, dist2b, coarse, blockmin, blockmax, scanlist, amb, gw, runmeta, scal, lxtree;
-    bool amb_clean = false;
-  } lane1;
+    hipStream_t stream = nullptr;  // not owned: sbo_ctx::stream (lane 0) / stream2 (lane 1), set where those are created (api.hip)
+    sbo::DevBuf dist2, dist2b;     // double [n_local] distance-transform scratch (x2 for ping-pong)
+    sbo::DevBuf coarse;            // coarse U mask + its distance transform (expander pre-decision)
+    sbo::DevBuf blockmin;          // per-block minima along the last axis (blocked last-axis scans)
+    sbo::DevBuf blockmax;          // per-block largest source weight along axis 0 (blocked axis-0 pass of the power transform)
+    sbo::DevBuf scanlist;          // candidates left open by the coarse expander decision (wave-per-candidate scan)
+    sbo::DevBuf amb;               // ambiguous-index list for the exact recheck
+    sbo::DevBuf gw;                // GoOSE: source weights (ucb_c on sources, -inf elsewhere), T [max shard]
+    sbo::DevBuf runmeta;           // GoOSE: per-run bounding boxes / radii of the coverage search
+    sbo::DevBuf lxtree;            // list index: this sweep's boxes of U members / sorted U mask, or GoOSE's sorted weights and masks
+    // small device scalar block (keys, counters, arg-reduce results), 4 KB.  Lane 0's is THE block of the sweep: Lmax (+ 3072),
+    // the explore target / trust-region centre (+ 2048) and a collective's scratch word (+ 4000) are views into it
+    sbo::DevBuf scal;
+    bool amb_clean = false;        // the recheck / scan counters of `scal` are still zero (no k_reset_amb needed)
+    // every buffer above, for sbo_shutdown: a new one is added here and nowhere else
+    std::vector<sbo::DevBuf*> bufs() { return {&dist2, &dist2b, &coarse, &blockmin, &blockmax, &scanlist, &amb, &gw, &runmeta, &lxtree, &scal}; }
+  } lane[2];
   int set_lanes = 1;       // 0: all constraints on the main stream, one after the other
   sbo::DevBuf partial; // arg-reduce per-block partials
-  sbo::DevBuf amb;     // ambiguous-index list for the exact recheck
-  sbo::DevBuf runmeta; // GoOSE: per-run bounding boxes / radii of the coverage search
-  sbo::ListIndex lx;    // spatial index of an explicit list (sets_index.inc.hpp)
-  sbo::DevBuf lxtree;   // ... this sweep's boxes of U members / sorted U mask, or GoOSE's sorted weights and masks (per lane)
+  sbo::ListIndex lx;    // spatial index of an explicit list (sets_index.inc.hpp); a sweep's hierarchy on it: SetLane::lxtree
   int refine_lds = 1;   // option (A/B checker): 1 sbo_refine stages M in LDS when it fits, 0 it always streams M's rows
   int list_index = -1;  // option: -1 the index for explicit lists above the exhaustive cap only, 0 never, 1 always
-  sbo::DevBuf scanlist; // candidates left open by the coarse expander decision (wave-per-candidate scan)
-  sbo::DevBuf blockmax; // per-block largest source weight along axis 0 (blocked axis-0 pass of the power transform)
-  sbo::DevBuf blockmin; // per-block minima along the last axis (blocked last-axis scans)
-  sbo::DevBuf gw;      // GoOSE: source weights (ucb_c on sources, -inf elsewhere), T [max shard]
   sbo::InterpPlan bi;   // K1i plan (first sweep of a model)
   sbo::DevBuf bi_params; // ... its per-model parameter block (device; the plan's kernels read it by pointer) and its pinned staging
   void* h_bi_params = nullptr;
@@ -373,7 +377,6 @@ struct sbo_ctx {
   unsigned char* h_back = nullptr;        // pinned host landing area of the end-of-sweep read-back (scalars + Lipschitz keys)
   int last_sweep = 0;  // 1 safeopt, 2 goose (what the masks hold)
   bool masks_valid = false;
-  bool amb_clean = false;   // the recheck / scan counters of the scalar block are still zero (no k_reset_amb needed)
   // profile
   sbo_profile prof{};
   hipEvent_t ev[8]{};

@@ -1107,7 +1107,16 @@ static int sweep_masks(sbo_ctx* c, const PostRequest& req) {
   return SBO_OK;
 }
 
-// (second lane of the set phase, see sbo_ctx::lane1 and lane_swap below)
+// (two lanes of the set phase, see sbo_ctx::SetLane and lanes_fork below)
+// the local candidates are whole hyper-planes of a grid's slowest axis (what the separable transforms need); *plane_out:
+// candidates per step of that axis
+static bool whole_planes(const sbo_ctx* c, long long* plane_out = nullptr) {
+  long long plane = 1;
+  for (int a = 0; a < c->cs.d - 1; ++a) plane *= c->cs.count[a];
+  if (plane_out) *plane_out = plane;
+  return c->cs.kind == 1 && c->cs.first % plane == 0 && c->cs.n_local % plane == 0;
+}
+
 static bool lanes_on(const sbo_ctx* c) { return c->set_lanes && !multi_rank(c) && c->mc.q >= 3 && c->cs.n_local > 0 && c->stream2; }
 
 // the guard band in force for the running sweep: the posterior in the mean / var buffers came from an approximating kernel
@@ -1131,10 +1140,10 @@ static int sweep_common_front(sbo_ctx* c, const sbo_sweep_opts* o, const PostOut
   const long long n = c->cs.n_local;
   const int q = c->mc.q;
   int rc;
-  if ((rc = ensure(c->scal, sizeof(SweepScalars)))) return rc;
+  if ((rc = ensure(c->lane[0].scal, sizeof(SweepScalars)))) return rc;
   const int nb = reduce_blocks(c);
   if ((rc = ensure(c->partial, partial_stride(nb)))) return rc;
-  SweepScalars* sc = (SweepScalars*)c->scal.p;
+  SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
   FinalJob fj;
   fj.pending = true;
   fj.q = q;
@@ -1142,8 +1151,8 @@ static int sweep_common_front(sbo_ctx* c, const sbo_sweep_opts* o, const PostOut
   fj.gb = gb_of(c);
   fj.b = o->b;
   if (lanes_on(c)) {
-    if ((rc = ensure(c->lane1.scal, 4096))) return rc;
-    fj.sc_copy = (SweepScalars*)c->lane1.scal.p;
+    if ((rc = ensure(c->lane[1].scal, 4096))) return rc;
+    fj.sc_copy = (SweepScalars*)c->lane[1].scal.p;
   }
   if (post.lmax_pending) {
     fj.Lpart = (const double*)c->bl_lpart.p;
@@ -1170,7 +1179,7 @@ static int sweep_common_front(sbo_ctx* c, const sbo_sweep_opts* o, const PostOut
     fj.pcap = c->cpart_cap;
     if (defer) *defer = fj;
     else launch_final(c, &fj);
-    c->amb_clean = true;
+    c->lane[0].amb_clean = true;
     SBO_HIP(hipGetLastError());
     return SBO_OK;
   }
@@ -1184,15 +1193,15 @@ static int sweep_common_front(sbo_ctx* c, const sbo_sweep_opts* o, const PostOut
   fj.pcap = c->cpart_cap;
   if (defer) *defer = fj;
   else launch_final(c, &fj);
-  c->amb_clean = true;
+  c->lane[0].amb_clean = true;
   SBO_HIP(hipGetLastError());
   return SBO_OK;
 }
 
 template <typename T, int D>
-static int launch_exact(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, int lidx, uint8_t* G) {
+static int launch_exact(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, int cidx, int lidx, uint8_t* G) {
   const long long n = c->cs.n_local;
-  SweepScalars* sc = (SweepScalars*)c->scal.p;
+  SweepScalars* sc = (SweepScalars*)ln.scal.p;
   const T* mean_c = (const T*)c->mean.p + (size_t)cidx * n;
   const T* var_c = (const T*)c->var.p + (size_t)cidx * n;
   CandSpec csU = c->cs;          // the witness set: every candidate that can matter (ranks > 1: the transform's window)
@@ -1208,19 +1217,19 @@ static int launch_exact(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, int lidx,
     rx.gb_c = cidx;
     rx.gb_l = c->gb_slow ? -1 : lidx;
   }
-  hipLaunchKernelGGL((k_expander_exact<T, D>), dim3(1024), dim3(256), 0, c->stream, c->cs, csU, mean_c, var_c, (T)o->b,
+  hipLaunchKernelGGL((k_expander_exact<T, D>), dim3(1024), dim3(256), 0, ln.stream, c->cs, csU, mean_c, var_c, (T)o->b,
                      Uall, (const unsigned long long*)c->Lmax.p, lidx, sc,
-                     (const long long*)c->amb.p, G, rx);
+                     (const long long*)ln.amb.p, G, rx);
   SBO_HIP(hipGetLastError());
   return SBO_OK;
 }
 
 template <typename T>
-static int launch_exact_d(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, int lidx, uint8_t* G) {
+static int launch_exact_d(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, int cidx, int lidx, uint8_t* G) {
   switch (c->mc.dpad) {
-    case 2: return launch_exact<T, 2>(c, o, cidx, lidx, G);
-    case 4: return launch_exact<T, 4>(c, o, cidx, lidx, G);
-    case 8: return launch_exact<T, 8>(c, o, cidx, lidx, G);
+    case 2: return launch_exact<T, 2>(c, ln, o, cidx, lidx, G);
+    case 4: return launch_exact<T, 4>(c, ln, o, cidx, lidx, G);
+    case 8: return launch_exact<T, 8>(c, ln, o, cidx, lidx, G);
   }
   return fail(SBO_E_UNSUPPORTED, "unsupported padded dimension");
 }
@@ -1247,13 +1256,13 @@ __global__ void k_halo_check(SweepScalars* sc, const unsigned long long* Lkeys, 
 }
 // the window's halo for constraint cidx: the guess from the previous sweep (checked on the device), or the keys of this one
 // (the host waits for their read-back)
-static int halo_for(sbo_ctx* c, int cidx, int lidx, double hl, long long planes_total, long long* H_out) {
+static int halo_for(sbo_ctx* c, sbo_ctx::SetLane& ln, int cidx, int lidx, double hl, long long planes_total, long long* H_out) {
   if (c->halo_spec && c->halo_guess[cidx] >= 0) {
     long long H = std::min(planes_total, c->halo_guess[cidx]);
     // (test hook: this rank alone guesses one plane -- tests/test_gpu_parity.py: the rerun must be every rank's decision)
     static const bool test_short = getenv("SBO_TEST_HALO_SHORT") != nullptr;
     if (test_short) H = std::min<long long>(H, 1);
-    hipLaunchKernelGGL(k_halo_check, dim3(1), dim3(1), 0, c->stream, (SweepScalars*)c->scal.p, (const unsigned long long*)c->Lmax.p, lidx, cidx,
+    hipLaunchKernelGGL(k_halo_check, dim3(1), dim3(1), 0, ln.stream, (SweepScalars*)ln.scal.p, (const unsigned long long*)c->Lmax.p, lidx, cidx,
                        hl, H, planes_total);
     *H_out = H;
     return SBO_OK;
@@ -1283,40 +1292,22 @@ static void halo_learn(sbo_ctx* c, const SweepScalars& h, const unsigned long lo
 }
 
 // G_c for constraint cidx (1..q-1) into G[n]
-static void launch_edt_axis0(sbo_ctx* c, const uint8_t* U, long long nlines, int count0, double h0, double* D, hipStream_t st = nullptr) {
-  if (!st) st = c->stream;
+static void launch_edt_axis0(sbo_ctx* c, sbo_ctx::SetLane& ln, const uint8_t* U, long long nlines, int count0, double h0, double* D) {
   if ((count0 & 63) == 0 && count0 <= 4096 && ((uintptr_t)U & 7) == 0)
     hipLaunchKernelGGL(k_edt_axis0_waves, dim3((unsigned)std::max<long long>(1, std::min<long long>((nlines + 3) / 4, (long long)c->n_cu * 16))), dim3(256), 0,
-                       st, U, nlines, count0, h0, D);
+                       ln.stream, U, nlines, count0, h0, D);
   else if (count0 <= kAxis0Max && count0 >= 128)
-    hipLaunchKernelGGL(k_edt_axis0_wg<false>, dim3((unsigned)std::min<long long>(nlines, 1 << 20)), dim3(256), 0, st, U, nlines,
+    hipLaunchKernelGGL(k_edt_axis0_wg<false>, dim3((unsigned)std::min<long long>(nlines, 1 << 20)), dim3(256), 0, ln.stream, U, nlines,
                        count0, h0, D, CoarseGrid{});
   else
-    hipLaunchKernelGGL(k_edt_axis0, dim3((unsigned)((nlines + 3) / 4)), dim3(256), 0, st, U, nlines, count0, h0, D);
+    hipLaunchKernelGGL(k_edt_axis0, dim3((unsigned)((nlines + 3) / 4)), dim3(256), 0, ln.stream, U, nlines, count0, h0, D);
 }
 
-// ---- second lane of the set phase (see sbo_ctx::lane1) ----------------------------------------------------------------
-static void lane_swap(sbo_ctx* c) {
-  auto& l = c->lane1;
-  std::swap(c->stream, c->stream2);
-  std::swap(c->dist2, l.dist2);
-  std::swap(c->dist2b, l.dist2b);
-  std::swap(c->coarse, l.coarse);
-  std::swap(c->blockmin, l.blockmin);
-  std::swap(c->blockmax, l.blockmax);
-  std::swap(c->scanlist, l.scanlist);
-  std::swap(c->amb, l.amb);
-  std::swap(c->gw, l.gw);
-  std::swap(c->runmeta, l.runmeta);
-  std::swap(c->scal, l.scal);
-  std::swap(c->amb_clean, l.amb_clean);
-  std::swap(c->lxtree, l.lxtree);
-}
-// after the classification's scalars are final on the main stream: lane 1 waits for them and takes its copy of the block
+// ---- the two lanes of the set phase (see sbo_ctx::SetLane): the only places that name both streams -----------------------
 // after the classification's scalars are final on the main stream (k_classify_final has written lane 1's snapshot of them)
 static int lanes_fork(sbo_ctx* c) {
   SBO_HIP(hipStreamWaitEvent(c->stream2, c->ev_join[4], 0));          // (recorded by the k_classify_final launch)
-  c->lane1.amb_clean = true;
+  c->lane[1].amb_clean = true;
   return SBO_OK;
 }
 static int lanes_join(sbo_ctx* c) {
@@ -1324,12 +1315,6 @@ static int lanes_join(sbo_ctx* c) {
   SBO_HIP(hipStreamWaitEvent(c->stream, c->ev_join[5], 0));
   return SBO_OK;
 }
-struct LaneScope {          // enqueue-time view of lane 1 (odd lanes swap the context's stream / scratch in, and back out)
-  sbo_ctx* c;
-  bool on;
-  LaneScope(sbo_ctx* c_, bool on_) : c(c_), on(on_) { if (on) lane_swap(c); }
-  ~LaneScope() { if (on) lane_swap(c); }
-};
 
 constexpr long long kListExpanderMax = 1ll << 21;     // explicit lists: largest candidate set with exhaustive expander sets
 
@@ -1424,7 +1409,7 @@ static int list_index_profile(sbo_ctx* c) {
 }
 
 // layout of this sweep's hierarchy in the lane's lxtree buffer: [sorted U mask][nodes of levels 0 .. nlev - 1]
-static int list_index_tree(sbo_ctx* c, int D, IdxTree* t) {
+static int list_index_tree(sbo_ctx* c, sbo_ctx::SetLane& ln, int D, IdxTree* t) {
   const long long n = c->cs.n_local;
   memset(t, 0, sizeof(*t));
   t->n = n;
@@ -1443,9 +1428,9 @@ static int list_index_tree(sbo_ctx* c, int D, IdxTree* t) {
   t->nlev = lev;
   const size_t ub = ((size_t)n + 255) / 256 * 256;
   int rc;
-  if ((rc = ensure(c->lxtree, ub + sizeof(double) * 2 * D * (size_t)off))) return rc;
-  t->Us = (uint8_t*)c->lxtree.p;
-  t->nodes = (double*)((char*)c->lxtree.p + ub);
+  if ((rc = ensure(ln.lxtree, ub + sizeof(double) * 2 * D * (size_t)off))) return rc;
+  t->Us = (uint8_t*)ln.lxtree.p;
+  t->nodes = (double*)((char*)ln.lxtree.p + ub);
   t->perm = (const unsigned*)c->lx.vals.p + (size_t)c->lx.perm_half * n;
   t->xs = (const double*)c->lx.xs.p;
   t->box = (const unsigned long long*)c->lx.box.p;
@@ -1456,16 +1441,16 @@ static int list_index_tree(sbo_ctx* c, int D, IdxTree* t) {
 // G_c of an explicit list on the index: boxes of this sweep's U members, then the walk (in-band verdicts of a guard band go to
 // amb, for k_expander_exact behind it)
 template <typename T, int D>
-static int list_index_expander(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, int lidx, uint8_t* G) {
+static int list_index_expander(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, int cidx, int lidx, uint8_t* G) {
   if (!c->lx.valid) return fail(SBO_E_INVALID, "list index not built for this sweep");
   const long long n = c->cs.n_local;
   IdxTree t;
   int rc;
-  if ((rc = list_index_tree(c, D, &t))) return rc;
-  SBO_HIP(hipMemsetAsync(G, 0, (size_t)n, c->stream));
-  hipLaunchKernelGGL((k_idx_leaves<D>), dim3((unsigned)t.cnt[0]), dim3(256), 0, c->stream, t, (const uint8_t*)c->maskU.p);
+  if ((rc = list_index_tree(c, ln, D, &t))) return rc;
+  SBO_HIP(hipMemsetAsync(G, 0, (size_t)n, ln.stream));
+  hipLaunchKernelGGL((k_idx_leaves<D>), dim3((unsigned)t.cnt[0]), dim3(256), 0, ln.stream, t, (const uint8_t*)c->maskU.p);
   for (int lev = 1; lev < t.nlev; ++lev)
-    hipLaunchKernelGGL((k_idx_parents<D>), dim3((unsigned)((t.cnt[lev] + 3) / 4)), dim3(256), 0, c->stream, t, lev);
+    hipLaunchKernelGGL((k_idx_parents<D>), dim3((unsigned)((t.cnt[lev] + 3) / 4)), dim3(256), 0, ln.stream, t, lev);
   RcExp rx;                                  // (as launch_exact: the guard band of an approximating posterior's fast path)
   memset(&rx, 0, sizeof(rx));
   if (gb_of(c) && !c->rc_active) {
@@ -1475,18 +1460,18 @@ static int list_index_expander(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, in
   const T* mean_c = (const T*)c->mean.p + (size_t)cidx * n;
   const T* var_c = (const T*)c->var.p + (size_t)cidx * n;
   const unsigned nb = (unsigned)std::min<long long>((n + 3) / 4, (long long)c->n_cu * 16);
-  hipLaunchKernelGGL((k_idx_expander<T, D>), dim3(nb), dim3(256), 0, c->stream, t, mean_c, var_c, (T)o->b, (const uint8_t*)c->maskS.p,
-                     (const unsigned long long*)c->Lmax.p, lidx, (SweepScalars*)c->scal.p, G, (long long*)c->amb.p, rx);
+  hipLaunchKernelGGL((k_idx_expander<T, D>), dim3(nb), dim3(256), 0, ln.stream, t, mean_c, var_c, (T)o->b, (const uint8_t*)c->maskS.p,
+                     (const unsigned long long*)c->Lmax.p, lidx, (SweepScalars*)ln.scal.p, G, (long long*)ln.amb.p, rx);
   SBO_HIP(hipGetLastError());
   c->lx.ran = true;
   return SBO_OK;
 }
 template <typename T>
-static int list_index_expander_d(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, int lidx, uint8_t* G) {
+static int list_index_expander_d(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, int cidx, int lidx, uint8_t* G) {
   switch (idx_dpad(c->cs.d)) {
-    case 2: return list_index_expander<T, 2>(c, o, cidx, lidx, G);
-    case 4: return list_index_expander<T, 4>(c, o, cidx, lidx, G);
-    default: return list_index_expander<T, 8>(c, o, cidx, lidx, G);
+    case 2: return list_index_expander<T, 2>(c, ln, o, cidx, lidx, G);
+    case 4: return list_index_expander<T, 4>(c, ln, o, cidx, lidx, G);
+    default: return list_index_expander<T, 8>(c, ln, o, cidx, lidx, G);
   }
 }
 
@@ -1498,37 +1483,35 @@ struct MinimizerJob {
   FinalJob fin;                 // the classification's merge, when it too waits for the expander's first launch
 };
 template <typename T>
-static void launch_minimizer(sbo_ctx* c, const sbo_sweep_opts* o, MinimizerJob* mj) {
+static void launch_minimizer(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, MinimizerJob* mj) {
   if (mj) launch_final(c, &mj->fin);
   if (!mj || !mj->pending) return;
   mj->pending = false;
-  hipLaunchKernelGGL((k_minimizer<T>), dim3(mj->nb), dim3(256), 0, c->stream, (const T*)c->mean.p, (const T*)c->var.p, c->cs.n_local,
-                     (long long)c->cs.first, (T)o->b, (const uint8_t*)c->maskS.p, (uint8_t*)c->maskM.p, (SweepScalars*)c->scal.p,
+  hipLaunchKernelGGL((k_minimizer<T>), dim3(mj->nb), dim3(256), 0, ln.stream, (const T*)c->mean.p, (const T*)c->var.p, c->cs.n_local,
+                     (long long)c->cs.first, (T)o->b, (const uint8_t*)c->maskS.p, (uint8_t*)c->maskM.p, (SweepScalars*)ln.scal.p,
                      mj->partial, gb_of(c));
 }
 
 // `lazy_exact`: the exhaustive recheck of in-band candidates (k_expander_exact) is NOT launched -- the caller looks at the
 // sweep's n_amb afterwards and runs it (and everything behind it) only when something was listed, which is rare
 template <typename T>
-static int expander_set(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, uint8_t* G, MinimizerJob* mj = nullptr, bool lazy_exact = false) {
+static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, int cidx, uint8_t* G, MinimizerJob* mj = nullptr, bool lazy_exact = false) {
   const long long n = c->cs.n_local;
-  if (n == 0) { launch_minimizer<T>(c, o, mj); return SBO_OK; }
+  if (n == 0) { launch_minimizer<T>(c, ln, o, mj); return SBO_OK; }
   const int q = c->mc.q;
   const int lidx = o->reference_quirk_L_index ? q - 1 : cidx;   // models/SafeOpt.py:110 (loop-leaked i)
-  SweepScalars* sc = (SweepScalars*)c->scal.p;
+  SweepScalars* sc = (SweepScalars*)ln.scal.p;
   const T* mean_c = (const T*)c->mean.p + (size_t)cidx * n;
   const T* var_c = (const T*)c->var.p + (size_t)cidx * n;
   const int nb = reduce_blocks(c);
   int rc;
-  if ((rc = ensure(c->amb, sizeof(long long) * (size_t)n))) return rc;
-  if (!c->amb_clean) hipLaunchKernelGGL(k_reset_amb, dim3(1), dim3(1), 0, c->stream, sc);   // (k_classify_final left the counters at zero)
-  c->amb_clean = false;
-  const int d_ = c->cs.d;
-  long long plane = 1;                       // candidates per step of the slowest axis
-  for (int a = 0; a < d_ - 1; ++a) plane *= c->cs.count[a];
-  const bool plane_aligned = c->cs.kind == 1 && c->cs.first % plane == 0 && n % plane == 0;
-  if (c->cs.kind == 1 && plane_aligned) {
-    const int d = d_;
+  if ((rc = ensure(ln.amb, sizeof(long long) * (size_t)n))) return rc;
+  if (!ln.amb_clean) hipLaunchKernelGGL(k_reset_amb, dim3(1), dim3(1), 0, ln.stream, sc);   // (k_classify_final left the counters at zero)
+  ln.amb_clean = false;
+  long long plane;                           // candidates per step of the slowest axis
+  const bool plane_aligned = whole_planes(c, &plane);
+  if (plane_aligned) {
+    const int d = c->cs.d;
     // Window of the transform: this rank's hyper-planes of the slowest axis plus, with ranks > 1, a halo of
     // ceil(cap / h) planes on either side taken from the all-gathered U mask (cap = largest radius that can matter,
     // from the keys of collective C1).  Witnesses further away cannot change a verdict, so the window is exact.
@@ -1538,7 +1521,7 @@ static int expander_set(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, uint8_t* 
     if (multi_rank(c)) {
       const double hl = d >= 2 ? c->cs.step[d - 1] : c->cs.step[0];
       long long H;
-      if ((rc = halo_for(c, cidx, lidx, hl, planes_total, &H))) return rc;
+      if ((rc = halo_for(c, ln, cidx, lidx, hl, planes_total, &H))) return rc;
       p0 = std::max(0ll, p0 - H);
       p1 = std::min(planes_total, p1 + H);
     }
@@ -1550,14 +1533,14 @@ static int expander_set(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, uint8_t* 
       // bytes of the window only, out of the all-gathered bit words (the gather itself was queued ahead of the host's wait)
       if ((rc = ensure(c->Uwin, (size_t)nt))) return rc;
       const unsigned long long* recvw = (const unsigned long long*)c->ubits.p + c->gather_words + kC1Head;   // (past the own block and a head)
-      hipLaunchKernelGGL(k_unpack_shards, dim3((unsigned)std::min<long long>((nt + 255) / 256, 1 << 16)), dim3(256), 0, c->stream, recvw,
+      hipLaunchKernelGGL(k_unpack_shards, dim3((unsigned)std::min<long long>((nt + 255) / 256, 1 << 16)), dim3(256), 0, ln.stream, recvw,
                          c->gather_words, c->world, (const long long*)c->shard_first.p, p0 * plane, nt, (uint8_t*)c->Uwin.p);
       c->uwin_first = p0 * plane;
       c->uwin_n = nt;
       Uall = (const uint8_t*)c->Uwin.p;
     }
-    if ((rc = ensure(c->dist2, sizeof(double) * (size_t)nt))) return rc;
-    if (d > 2 && (rc = ensure(c->dist2b, sizeof(double) * (size_t)nt))) return rc;
+    if ((rc = ensure(ln.dist2, sizeof(double) * (size_t)nt))) return rc;
+    if (d > 2 && (rc = ensure(ln.dist2b, sizeof(double) * (size_t)nt))) return rc;
     const int count0 = d >= 2 ? (int)c->cs.count[0] : (int)nt;  // d == 1: the window is one line
     const long long nlines = nt / count0;
     // coarse transform of the window (tiny): lets most candidates decide without the per-candidate scan
@@ -1584,8 +1567,8 @@ static int expander_set(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, uint8_t* 
       cg.enabled = 1;
       cg.delta = (kCoarse - 1) * std::sqrt(h2) * (1.0 + 1e-9);
       const size_t cbytes = ((size_t)nc * (1 + 2 * sizeof(double)) + 64 + 255) / 256 * 256;
-      if ((rc = ensure(c->coarse, cbytes))) return rc;
-      dc0 = (double*)c->coarse.p;
+      if ((rc = ensure(ln.coarse, cbytes))) return rc;
+      dc0 = (double*)ln.coarse.p;
       dc1 = dc0 + nc;
       Uc = (uint8_t*)(dc1 + nc);
     }
@@ -1596,8 +1579,8 @@ static int expander_set(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, uint8_t* 
     // 2-D grids: the two axis-0 passes share a launch, and so do the coarse last-axis scan, the minimiser and the block minima
     const bool paired = d == 2 && coarse_ok && c->set_fuse && count0 <= kAxis0Max && count0 >= 128 && cc0 >= 128;
     bool bmin_done = false, u16 = false;
-    double* din = (double*)c->dist2.p;
-    double* dout = (double*)c->dist2b.p;
+    double* din = (double*)ln.dist2.p;
+    double* dout = (double*)ln.dist2b.p;
     long long stride = count0;
     if (paired) {
       // fine lines of whole words, up to 4096 positions: a wave per line
@@ -1616,10 +1599,10 @@ static int expander_set(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, uint8_t* 
       // verdict kernel scans the image itself and expects squared distances as doubles
       u16 = count0 < 65535 && want_bmin && blk_ <= 64 && c->scan_waves;
       if (u16)
-        hipLaunchKernelGGL(k_edt_axis0_pair<true>, dim3((unsigned)(nfine + ncoarse + (fin.pending ? 1 : 0))), dim3(256), 0, c->stream, Uall,
+        hipLaunchKernelGGL(k_edt_axis0_pair<true>, dim3((unsigned)(nfine + ncoarse + (fin.pending ? 1 : 0))), dim3(256), 0, ln.stream, Uall,
                            nlines, count0, c->cs.step[0], din, nfine, ncoarse, clines, cc0, c->cs.step[0] * kCoarse, dc0, cg, fin, wave_lines);
       else
-        hipLaunchKernelGGL(k_edt_axis0_pair<false>, dim3((unsigned)(nfine + ncoarse + (fin.pending ? 1 : 0))), dim3(256), 0, c->stream, Uall,
+        hipLaunchKernelGGL(k_edt_axis0_pair<false>, dim3((unsigned)(nfine + ncoarse + (fin.pending ? 1 : 0))), dim3(256), 0, ln.stream, Uall,
                            nlines, count0, c->cs.step[0], din, nfine, ncoarse, clines, cc0, c->cs.step[0] * kCoarse, dc0, cg, fin, wave_lines);
       MidJobs<T> j;
       memset(&j, 0, sizeof(j));
@@ -1650,24 +1633,24 @@ static int expander_set(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, uint8_t* 
       }
       if (want_bmin) {
         const int nblocks = (last_cnt_ + blk_ - 1) / blk_;
-        if ((rc = ensure(c->blockmin, sizeof(double) * (size_t)nblocks * (size_t)stride))) return rc;
+        if ((rc = ensure(ln.blockmin, sizeof(double) * (size_t)nblocks * (size_t)stride))) return rc;
         j.nm = (int)std::min<long long>((stride + 63) / 64 * nblocks, 1 << 20);
         j.din = din;
         j.stride = stride;
         j.cnt = last_cnt_;
         j.blk = blk_;
-        j.bmin = (double*)c->blockmin.p;
+        j.bmin = (double*)ln.blockmin.p;
         bmin_done = true;
       }
       j.h0 = c->cs.step[0];
-      if (u16) hipLaunchKernelGGL((k_set_mid<T, true>), dim3((unsigned)(j.ns + j.nb + j.nm)), dim3(256), 0, c->stream, j);
-      else hipLaunchKernelGGL((k_set_mid<T, false>), dim3((unsigned)(j.ns + j.nb + j.nm)), dim3(256), 0, c->stream, j);
+      if (u16) hipLaunchKernelGGL((k_set_mid<T, true>), dim3((unsigned)(j.ns + j.nb + j.nm)), dim3(256), 0, ln.stream, j);
+      else hipLaunchKernelGGL((k_set_mid<T, false>), dim3((unsigned)(j.ns + j.nb + j.nm)), dim3(256), 0, ln.stream, j);
       cg.Dc = dc1;
     } else {
-      launch_minimizer<T>(c, o, mj);
-      launch_edt_axis0(c, Uall, nlines, count0, c->cs.step[0], din);
+      launch_minimizer<T>(c, ln, o, mj);
+      launch_edt_axis0(c, ln, Uall, nlines, count0, c->cs.step[0], din);
       for (int a = 1; a < d - 1; ++a) {
-        hipLaunchKernelGGL(k_edt_scan, dim3((unsigned)std::min<long long>((nt + 255) / 256, 1 << 20)), dim3(256), 0, c->stream,
+        hipLaunchKernelGGL(k_edt_scan, dim3((unsigned)std::min<long long>((nt + 255) / 256, 1 << 20)), dim3(256), 0, ln.stream,
                            (const double*)din, dout, nt, stride, (int)c->cs.count[a], c->cs.step[a],
                            (const SweepScalars*)sc, cidx, (const unsigned long long*)c->Lmax.p, lidx, 0, 0.0);
         std::swap(din, dout);
@@ -1676,16 +1659,16 @@ static int expander_set(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, uint8_t* 
       if (coarse_ok) {
         if (cc0 <= kAxis0Max && cc0 >= 128) {
           // the coarse axis-0 pass forms the cells' bits from the fine mask itself
-          hipLaunchKernelGGL(k_edt_axis0_wg<true>, dim3((unsigned)std::min<long long>(clines, 1 << 20)), dim3(256), 0, c->stream, Uall,
+          hipLaunchKernelGGL(k_edt_axis0_wg<true>, dim3((unsigned)std::min<long long>(clines, 1 << 20)), dim3(256), 0, ln.stream, Uall,
                              clines, cc0, c->cs.step[0] * kCoarse, dc0, cg);
         } else {
-          hipLaunchKernelGGL(k_coarsen_mask, dim3((unsigned)std::min<long long>((nc + 255) / 256, 1 << 16)), dim3(256), 0, c->stream,
+          hipLaunchKernelGGL(k_coarsen_mask, dim3((unsigned)std::min<long long>((nc + 255) / 256, 1 << 16)), dim3(256), 0, ln.stream,
                              Uall, cg, nc, Uc);
-          launch_edt_axis0(c, (const uint8_t*)Uc, clines, cc0, c->cs.step[0] * kCoarse, dc0);
+          launch_edt_axis0(c, ln, (const uint8_t*)Uc, clines, cc0, c->cs.step[0] * kCoarse, dc0);
         }
         long long cstride = cc0;
         for (int a = 1; a < d; ++a) {
-          hipLaunchKernelGGL(k_edt_scan, dim3((unsigned)std::min<long long>((nc + 255) / 256, 1 << 16)), dim3(256), 0, c->stream,
+          hipLaunchKernelGGL(k_edt_scan, dim3((unsigned)std::min<long long>((nc + 255) / 256, 1 << 16)), dim3(256), 0, ln.stream,
                              (const double*)dc0, dc1, nc, cstride, (int)cg.ccount[a], c->cs.step[a] * kCoarse, (const SweepScalars*)sc,
                              cidx, (const unsigned long long*)c->Lmax.p, lidx, 0, cap_extra);
           std::swap(dc0, dc1);
@@ -1699,19 +1682,19 @@ static int expander_set(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, uint8_t* 
     const int last_cnt = d >= 2 ? (int)wplanes : 1;
     const double last_h = d >= 2 ? c->cs.step[d - 1] : 0.0;
     {
-      const double* bmin = bmin_done ? (const double*)c->blockmin.p : nullptr;
+      const double* bmin = bmin_done ? (const double*)ln.blockmin.p : nullptr;
       const int blk = blk_;
       if (!bmin_done && want_bmin) {
         const long long nb_ = (long long)((last_cnt + blk - 1) / blk) * stride;
-        if ((rc = ensure(c->blockmin, sizeof(double) * (size_t)nb_))) return rc;
-        hipLaunchKernelGGL(k_block_min, dim3((unsigned)std::min<long long>((stride + 63) / 64 * ((last_cnt + blk - 1) / blk), 1 << 20)), dim3(256), 0, c->stream,
-                           (const double*)din, stride, last_cnt, blk, (double*)c->blockmin.p);
-        bmin = (const double*)c->blockmin.p;
+        if ((rc = ensure(ln.blockmin, sizeof(double) * (size_t)nb_))) return rc;
+        hipLaunchKernelGGL(k_block_min, dim3((unsigned)std::min<long long>((stride + 63) / 64 * ((last_cnt + blk - 1) / blk), 1 << 20)), dim3(256), 0, ln.stream,
+                           (const double*)din, stride, last_cnt, blk, (double*)ln.blockmin.p);
+        bmin = (const double*)ln.blockmin.p;
       }
       long long* slist = nullptr;
       if (bmin && blk <= 64 && c->scan_waves) {
-        if ((rc = ensure(c->scanlist, 2 * sizeof(long long) * (size_t)n))) return rc;   // (candidate, ucb) pairs
-        slist = (long long*)c->scanlist.p;
+        if ((rc = ensure(ln.scanlist, 2 * sizeof(long long) * (size_t)n))) return rc;   // (candidate, ucb) pairs
+        slist = (long long*)ln.scanlist.p;
       }
       const long long len0 = d >= 2 ? count0 : n;               // positions per line / local lines
       const long long nl = n / len0;
@@ -1731,15 +1714,15 @@ static int expander_set(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, uint8_t* 
       }
       const dim3 dgrid((unsigned)((len0 + 255) / 256), (unsigned)std::min<long long>((nl + kDecideLines - 1) / kDecideLines, 65535));
 #define SBO_DECIDE(LIST)                                                                                                            \
-  hipLaunchKernelGGL((k_edt_decide<T, LIST>), dgrid, dim3(256), 0, c->stream, (const double*)din, nl, (int)len0, goff / len0, goff, \
+  hipLaunchKernelGGL((k_edt_decide<T, LIST>), dgrid, dim3(256), 0, ln.stream, (const double*)din, nl, (int)len0, goff / len0, goff, \
                      d >= 2 ? stride : 1, last_cnt, last_h, d, xscale, mean_c, var_c, (T)o->b, (const uint8_t*)c->maskS.p,          \
-                     (const unsigned long long*)c->Lmax.p, lidx, sc, G, (long long*)c->amb.p, cg, bmin, blk, slist, rx)
+                     (const unsigned long long*)c->Lmax.p, lidx, sc, G, (long long*)ln.amb.p, cg, bmin, blk, slist, rx)
       // (grids whose lines are whole 8-byte mask words: eight candidates per lane, see k_edt_decide8)
       const bool wide = slist && len0 % 8 == 0 && d >= 2 && cg.enabled && ((uintptr_t)G & 7) == 0 &&
                         ((uintptr_t)c->maskS.p & 7) == 0;
       if (wide) {
         const dim3 g8((unsigned)((len0 / 8 + 255) / 256), (unsigned)std::min<long long>(nl, 65535));
-        hipLaunchKernelGGL((k_edt_decide8<T>), g8, dim3(256), 0, c->stream, nl, (int)len0, goff / len0, goff, d, xscale, mean_c, var_c, (T)o->b,
+        hipLaunchKernelGGL((k_edt_decide8<T>), g8, dim3(256), 0, ln.stream, nl, (int)len0, goff / len0, goff, d, xscale, mean_c, var_c, (T)o->b,
                            (const uint8_t*)c->maskS.p, (const unsigned long long*)c->Lmax.p, lidx, sc, G, cg, slist, rx);
       } else if (slist) SBO_DECIDE(true);
       else SBO_DECIDE(false);
@@ -1752,14 +1735,14 @@ static int expander_set(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, uint8_t* 
         const int gl = c->scan_waves == 8 || c->scan_waves == 32 || c->scan_waves == 64 ? c->scan_waves : 16;
 #define SBO_SCAN_LIST(GL)                                                                                                       \
   if (u16)                                                                                                                      \
-    hipLaunchKernelGGL((k_edt_scan_list<T, GL, DistU16>), dim3(scan_wgs), dim3(256), 0, c->stream,                              \
+    hipLaunchKernelGGL((k_edt_scan_list<T, GL, DistU16>), dim3(scan_wgs), dim3(256), 0, ln.stream,                              \
                        DistU16{reinterpret_cast<const unsigned short*>(din), c->cs.step[0]}, goff, stride, last_cnt,            \
                        last_h, d, xscale, mean_c, var_c, (T)o->b, (const unsigned long long*)c->Lmax.p, lidx, sc, G,            \
-                       (long long*)c->amb.p, bmin, blk, (const long long*)slist, rx);                                           \
+                       (long long*)ln.amb.p, bmin, blk, (const long long*)slist, rx);                                           \
   else                                                                                                                          \
-  hipLaunchKernelGGL((k_edt_scan_list<T, GL, DistF64>), dim3(scan_wgs), dim3(256), 0, c->stream, DistF64{(const double*)din, 0.0}, goff, stride, last_cnt, \
+  hipLaunchKernelGGL((k_edt_scan_list<T, GL, DistF64>), dim3(scan_wgs), dim3(256), 0, ln.stream, DistF64{(const double*)din, 0.0}, goff, stride, last_cnt, \
                      last_h, d, xscale, mean_c, var_c, (T)o->b, (const unsigned long long*)c->Lmax.p, lidx, sc, G,              \
-                     (long long*)c->amb.p, bmin, blk, (const long long*)slist, rx)
+                     (long long*)ln.amb.p, bmin, blk, (const long long*)slist, rx)
         switch (gl) {
           case 8: SBO_SCAN_LIST(8); break;
           case 32: SBO_SCAN_LIST(32); break;
@@ -1771,11 +1754,11 @@ static int expander_set(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, uint8_t* 
     }
   } else {
     // explicit candidate lists, and grid ranges that are not whole hyper-planes: exhaustive evaluation
-    launch_minimizer<T>(c, o, mj);
+    launch_minimizer<T>(c, ln, o, mj);
     if (list_index_on(c)) {
       // (explicit lists on the spatial index: the same verdicts with the pairs that cannot matter left out)
-      if ((rc = list_index_expander_d<T>(c, o, cidx, lidx, G))) return rc;
-      return launch_exact_d<T>(c, o, cidx, lidx, G);
+      if ((rc = list_index_expander_d<T>(c, ln, o, cidx, lidx, G))) return rc;
+      return launch_exact_d<T>(c, ln, o, cidx, lidx, G);
     }
     // (quadratic: every safe candidate against every U point, like the reference's vmap -- fine for the lists a campaign
     // uses, seconds at the cap)
@@ -1783,12 +1766,12 @@ static int expander_set(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, uint8_t* 
       return fail(SBO_E_UNSUPPORTED, "expander sets need a grid of whole hyper-planes, or at most 2097152 candidates (exhaustive)");
     if (multi_rank(c))
       return fail(SBO_E_UNSUPPORTED, "expander sets on explicit candidate lists are single-rank");
-    hipLaunchKernelGGL(k_list_safe, dim3(nb), dim3(256), 0, c->stream, (const uint8_t*)c->maskS.p, n, sc, G,
-                       (long long*)c->amb.p);
+    hipLaunchKernelGGL(k_list_safe, dim3(nb), dim3(256), 0, ln.stream, (const uint8_t*)c->maskS.p, n, sc, G,
+                       (long long*)ln.amb.p);
   }
   SBO_HIP(hipGetLastError());
-  if (lazy_exact && c->cs.kind == 1 && plane_aligned) return SBO_OK;
-  return launch_exact_d<T>(c, o, cidx, lidx, G);
+  if (lazy_exact && plane_aligned) return SBO_OK;
+  return launch_exact_d<T>(c, ln, o, cidx, lidx, G);
 }
 
 static void coords_of(const sbo_ctx* c, long long gidx, double* x) {
@@ -1820,7 +1803,7 @@ static void coords_of(const sbo_ctx* c, long long gidx, double* x) {
 template <typename T>
 static int sweep_exchange_front(sbo_ctx* c, const sbo_sweep_opts* o, bool need_U) {
   const int q = c->mc.q;
-  SweepScalars* sc = (SweepScalars*)c->scal.p;
+  SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
   if (!multi_rank(c)) return SBO_OK;   // (the radius keys, max over S of ucb_c, come out of k_classify)
   int rc;
   if (!c->sharded && q > 1 && need_U)
@@ -1873,7 +1856,7 @@ static int sweep_exchange_wait(sbo_ctx* c) {
 // C3 + host merge: every rank's slots and counters -> global ones.  slot_is_max[i] selects arg-max / arg-min.
 static int sweep_exchange_back(sbo_ctx* c, SweepScalars& h, const bool* slot_is_max, unsigned long long* Lk = nullptr,
                                hipEvent_t done_ev = nullptr, bool mirrored = false /* the last kernel wrote h_back and carries done_ev */) {
-  SweepScalars* sc = (SweepScalars*)c->scal.p;
+  SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
   // (the Lipschitz keys ride in the same read-back: one synchronisation per sweep)
   // (pinned landing area: pageable destinations are staged by the runtime, ~20 us per copy)
   // (the Lipschitz keys live 3 KB into the same allocation: sbo_create)
@@ -2020,10 +2003,8 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
   const int nb = reduce_blocks(c);
   // one constraint on one rank: the exhaustive recheck of in-band candidates (almost never any) is launched only when the
   // result block says that something was listed -- one launch (~5 us) less on the common path
-  long long plane_ = 1;
-  for (int a = 0; a < c->cs.d - 1; ++a) plane_ *= c->cs.count[a];
-  const bool lazy_exact = c->exact_lazy && q == 2 && !multi_rank(c) && !c->rc_active && c->result_mirror && n > 0 && c->cs.kind == 1 &&
-                          c->cs.first % plane_ == 0 && n % plane_ == 0;      // (grids: lists decide every expander exhaustively)
+  const bool lazy_exact = c->exact_lazy && q == 2 && !multi_rank(c) && !c->rc_active && c->result_mirror && n > 0 &&
+                          whole_planes(c);      // (grids: lists decide every expander exhaustively)
   // partials of the q arg-max reductions side by side: merged by one launch at the end (k_safeopt_finals)
   const size_t pstride = partial_stride(nb);
   if ((rc = ensure(c->partial, pstride * (size_t)q))) return rc;
@@ -2038,18 +2019,18 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
     mj.pending = n > 0;
     mj.nb = nb;
     mj.partial = (Best*)pbase;
-    if (q < 2 || multi_rank(c)) launch_minimizer<T>(c, o, &mj);
+    if (q < 2 || multi_rank(c)) launch_minimizer<T>(c, c->lane[0], o, &mj);
     if (c->phase_events) SBO_HIP(hipEventRecord(c->ev[2], c->stream));
     if (lanes && (rc = lanes_fork(c))) return rc;
     for (int cc = 1; cc < q; ++cc) {
       uint8_t* G = (uint8_t*)c->maskG.p + (size_t)(cc - 1) * n;
-      LaneScope lane(c, lanes && ((cc - 1) & 1));              // constraints alternate between the two lanes
-      if ((rc = expander_set<T>(c, o, cc, G, lane.on ? nullptr : &mj, lazy_exact))) return rc;
+      const bool side = lanes && ((cc - 1) & 1);                 // constraints alternate between the two lanes
+      if ((rc = expander_set<T>(c, c->lane[side], o, cc, G, side ? nullptr : &mj, lazy_exact))) return rc;
     }
-    launch_minimizer<T>(c, o, &mj);
+    launch_minimizer<T>(c, c->lane[0], o, &mj);
     if (lanes && (rc = lanes_join(c))) return rc;
   }
-  SweepScalars* sc = (SweepScalars*)c->scal.p;
+  SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
   if (c->phase_events) SBO_HIP(hipEventRecord(c->ev[3], c->stream));
   if (n > 0 && q > 1) {
     hipLaunchKernelGGL((k_arg_masked_multi<T, true, ValArray<T>>), dim3((unsigned)nb, (unsigned)(q - 1)), dim3(256), 0, c->stream,
@@ -2059,7 +2040,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
   const bool mirrored = !multi_rank(c) && c->result_mirror;
   hipExtLaunchKernelGGL(k_sweep_finals<true>, dim3((unsigned)q), dim3(256), 0, c->stream, nullptr, mirrored ? c->ev[4] : nullptr, 0,
                         (const unsigned char*)pbase, pstride, n > 0 ? nb : 0, sc,
-                        lanes ? (const SweepScalars*)c->lane1.scal.p : (const SweepScalars*)nullptr,
+                        lanes ? (const SweepScalars*)c->lane[1].scal.p : (const SweepScalars*)nullptr,
                         mirrored ? c->h_back : (unsigned char*)nullptr, (const unsigned long long*)c->Lmax.p, gb_of(c) ? 1 : 0);
   SBO_HIP(hipGetLastError());
   bool is_max[kArgSlots];
@@ -2068,7 +2049,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
   if (lazy_exact && (h.n_amb > 0 || c->exact_lazy == 2)) {      // (2: always, the test of this path)
     // in-band candidates after all: their exhaustive recheck, then the expanders' arg-max and the finals once more
     const int lidx = o->reference_quirk_L_index ? q - 1 : 1;
-    if ((rc = launch_exact_d<T>(c, o, 1, lidx, (uint8_t*)c->maskG.p))) return rc;
+    if ((rc = launch_exact_d<T>(c, c->lane[0], o, 1, lidx, (uint8_t*)c->maskG.p))) return rc;
     hipLaunchKernelGGL((k_arg_masked_multi<T, true, ValArray<T>>), dim3((unsigned)nb, 1u), dim3(256), 0, c->stream,
                        ValArray<T>{(const T*)c->var.p, 0.0}, (const uint8_t*)nullptr, (const uint8_t*)c->maskG.p, n, (long long)c->cs.first, pbase,
                        pstride, 1, gb_of(c));
@@ -2183,7 +2164,7 @@ static int sweep_tr_t(sbo_ctx* c, const sbo_sweep_opts* o, const double* x0, dou
 #include "sets_recheck.inc.hpp"
 
 template <typename T, int D>
-static int goose_sets(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, const uint8_t* src, uint8_t* O) {
+static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, int cidx, const uint8_t* src, uint8_t* O) {
   const long long n = c->cs.n_local;
   const int q = c->mc.q;
   const int lidx = o->reference_quirk_L_index ? q - 1 : cidx;   // models/GoOSE.py:100 (loop-leaked i)
@@ -2192,12 +2173,12 @@ static int goose_sets(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, const uint8
   int rc;
   long long maxlocal = n;
   for (int r = 0; r < c->world && multi_rank(c); ++r) maxlocal = std::max(maxlocal, c->first_of[r + 1] - c->first_of[r]);
-  if ((rc = ensure(c->gw, sizeof(T) * (size_t)std::max<long long>(maxlocal, 1)))) return rc;
+  if ((rc = ensure(ln.gw, sizeof(T) * (size_t)std::max<long long>(maxlocal, 1)))) return rc;
   if (n > 0)
-    hipLaunchKernelGGL((k_goose_weights<T>), dim3(reduce_blocks(c)), dim3(256), 0, c->stream, mean_c, var_c, n, (T)o->b, src,
-                       (T*)c->gw.p, (SweepScalars*)c->scal.p);
+    hipLaunchKernelGGL((k_goose_weights<T>), dim3(reduce_blocks(c)), dim3(256), 0, ln.stream, mean_c, var_c, n, (T)o->b, src,
+                       (T*)ln.gw.p, (SweepScalars*)ln.scal.p);
   CandSpec css = c->cs;                 // the source candidates
-  const T* W = (const T*)c->gw.p;
+  const T* W = (const T*)ln.gw.p;
   long long run_lo = 0, run_hi = (n + kRun - 1) / kRun;
   long long win_p0 = 0, win_p1 = 0;     // ranks > 1: window of hyper-planes holding every source that can matter
   bool w_is_window = false;             // ranks > 1, slab exchange: W holds exactly the window [win_p0, win_p1)
@@ -2212,7 +2193,7 @@ static int goose_sets(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, const uint8
     const long long own0 = p0, own1 = p1;
     const double hl = c->cs.step[d - 1];
     long long H;
-    if ((rc = halo_for(c, cidx, lidx, hl, planes_total, &H))) return rc;
+    if ((rc = halo_for(c, ln, cidx, lidx, hl, planes_total, &H))) return rc;
     p0 = std::max(0ll, p0 - H);
     p1 = std::min(planes_total, p1 + H);
     win_p0 = p0;
@@ -2231,19 +2212,19 @@ static int goose_sets(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, const uint8
       if ((rc = ensure(c->Wfull, sizeof(T) * (size_t)(p1 - p0) * plane))) return rc;
       T* send = (T*)c->gather.p;
       T* recv = send + 2 * slab;
-      SBO_HIP(hipMemcpyAsync(send, c->gw.p, sizeof(T) * slab, hipMemcpyDeviceToDevice, c->stream));
-      SBO_HIP(hipMemcpyAsync(send + slab, (const T*)c->gw.p + (size_t)n - slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, c->stream));
+      SBO_HIP(hipMemcpyAsync(send, ln.gw.p, sizeof(T) * slab, hipMemcpyDeviceToDevice, ln.stream));
+      SBO_HIP(hipMemcpyAsync(send + slab, (const T*)ln.gw.p + (size_t)n - slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, ln.stream));
       if ((rc = comm_allgather_bytes(c, send, recv, sizeof(T) * slab * 2))) return rc;
       T* win = (T*)c->Wfull.p;
       size_t at = 0;
       if (own0 > p0) {       // previous rank's top slab (p0 = own0 - H exactly, since H <= its planes)
-        SBO_HIP(hipMemcpyAsync(win, recv + (size_t)(c->rank - 1) * 2 * slab + slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, c->stream));
+        SBO_HIP(hipMemcpyAsync(win, recv + (size_t)(c->rank - 1) * 2 * slab + slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, ln.stream));
         at = slab;
       }
-      SBO_HIP(hipMemcpyAsync(win + at, c->gw.p, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+      SBO_HIP(hipMemcpyAsync(win + at, ln.gw.p, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, ln.stream));
       at += (size_t)n;
       if (p1 > own1)
-        SBO_HIP(hipMemcpyAsync(win + at, recv + (size_t)(c->rank + 1) * 2 * slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, c->stream));
+        SBO_HIP(hipMemcpyAsync(win + at, recv + (size_t)(c->rank + 1) * 2 * slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, ln.stream));
       css.first = p0 * plane;
       css.n_local = (p1 - p0) * plane;
       W = (const T*)win;
@@ -2254,9 +2235,9 @@ static int goose_sets(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, const uint8
       // wide halo: all-gather the whole weight shards
       if ((rc = ensure(c->gather, sizeof(T) * (size_t)maxlocal * c->world))) return rc;
       if ((rc = ensure(c->Wfull, sizeof(T) * (size_t)c->grid_total))) return rc;
-      if ((rc = comm_allgather_bytes(c, c->gw.p, c->gather.p, sizeof(T) * (size_t)maxlocal))) return rc;
+      if ((rc = comm_allgather_bytes(c, ln.gw.p, c->gather.p, sizeof(T) * (size_t)maxlocal))) return rc;
       hipLaunchKernelGGL(k_compact_shards<T>, dim3((unsigned)std::min<long long>((c->grid_total + 255) / 256, 1 << 16)), dim3(256), 0,
-                         c->stream, (const T*)c->gather.p, maxlocal, c->world, (const long long*)c->shard_first.p, c->grid_total,
+                         ln.stream, (const T*)c->gather.p, maxlocal, c->world, (const long long*)c->shard_first.p, c->grid_total,
                          (T*)c->Wfull.p);
       css.first = 0;
       css.n_local = c->grid_total;
@@ -2266,25 +2247,24 @@ static int goose_sets(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, const uint8
     }
   }
   if (n == 0) return SBO_OK;           // (an empty shard still took part in the all-gather)
-  long long plane1 = 1;
-  for (int a = 0; a < c->cs.d - 1; ++a) plane1 *= c->cs.count[a];
-  const bool plane_aligned = c->cs.kind == 1 && c->cs.first % plane1 == 0 && n % plane1 == 0;
+  long long plane1;
+  const bool plane_aligned = whole_planes(c, &plane1);
   if (plane_aligned && !c->goose_pairs) {
     // grids: power-distance transform of the source weights over the window, verdict by sign, exact recheck in the band
     const int d = c->cs.d;
-    SweepScalars* sc = (SweepScalars*)c->scal.p;
+    SweepScalars* sc = (SweepScalars*)ln.scal.p;
     const long long own0 = c->cs.first / plane1;
     const long long w0 = multi_rank(c) ? win_p0 : own0, w1 = multi_rank(c) ? win_p1 : own0 + n / plane1;
     const long long wplanes = w1 - w0, nt = wplanes * plane1, goff = (own0 - w0) * plane1;
     const T* Wwin = (multi_rank(c) && !w_is_window) ? W + w0 * plane1 : W;
-    if ((rc = ensure(c->dist2, sizeof(double) * (size_t)nt))) return rc;
-    if (d > 2 && (rc = ensure(c->dist2b, sizeof(double) * (size_t)nt))) return rc;
-    if ((rc = ensure(c->amb, sizeof(long long) * (size_t)n))) return rc;
+    if ((rc = ensure(ln.dist2, sizeof(double) * (size_t)nt))) return rc;
+    if (d > 2 && (rc = ensure(ln.dist2b, sizeof(double) * (size_t)nt))) return rc;
+    if ((rc = ensure(ln.amb, sizeof(long long) * (size_t)n))) return rc;
     double xscale = 0.0;
     for (int a = 0; a < d; ++a) xscale = std::max(xscale, std::max(std::fabs(c->cs.lo[a]), std::fabs(c->cs.hi[a])));
     const int count0 = d >= 2 ? (int)c->cs.count[0] : (int)nt;
     const unsigned gridn = (unsigned)std::min<long long>((nt + 255) / 256, 1 << 20);
-    c->amb_clean = false;                          // (k_goose_weights cleared the counters)
+    ln.amb_clean = false;                          // (k_goose_weights cleared the counters)
     // coarse bounds of the window: decide most candidates (and skip their axis-0 scans) without touching the fine arrays
     CoarseGrid cg;
     memset(&cg, 0, sizeof(cg));
@@ -2300,16 +2280,16 @@ static int goose_sets(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, const uint8
     const double *pc_lo = nullptr, *pc_hi = nullptr;
     if (coarse_ok) {
       cg.enabled = 1;
-      if ((rc = ensure(c->coarse, (size_t)nc * 5 * sizeof(double) + 64))) return rc;
-      double* lo0 = (double*)c->coarse.p;
+      if ((rc = ensure(ln.coarse, (size_t)nc * 5 * sizeof(double) + 64))) return rc;
+      double* lo0 = (double*)ln.coarse.p;
       double* lo1 = lo0 + nc;
       double* hi0 = lo1 + nc;
       double* hi1 = hi0 + nc;
-      hipLaunchKernelGGL((k_pdt_cell_min<T>), dim3((unsigned)std::min<long long>((nc * 8 + 255) / 256, 1 << 18)), dim3(256), 0, c->stream, Wwin, cg, nc,
+      hipLaunchKernelGGL((k_pdt_cell_min<T>), dim3((unsigned)std::min<long long>((nc * 8 + 255) / 256, 1 << 18)), dim3(256), 0, ln.stream, Wwin, cg, nc,
                          (const unsigned long long*)c->Lmax.p, lidx, lo0, hi0);
       long long cstride = 1;
       for (int a = 0; a < d; ++a) {
-        hipLaunchKernelGGL(k_pdt_coarse_scan, dim3((unsigned)std::min<long long>((2 * nc * 8 + 255) / 256, 1 << 18)), dim3(256), 0, c->stream, (const double*)lo0, lo1, (const double*)hi0,
+        hipLaunchKernelGGL(k_pdt_coarse_scan, dim3((unsigned)std::min<long long>((2 * nc * 8 + 255) / 256, 1 << 18)), dim3(256), 0, ln.stream, (const double*)lo0, lo1, (const double*)hi0,
                            hi1, nc, cstride, (int)cg.ccount[a], c->cs.step[a], (const SweepScalars*)sc, cidx,
                            (const unsigned long long*)c->Lmax.p, lidx, d, xscale);
         std::swap(lo0, lo1);
@@ -2326,26 +2306,26 @@ static int goose_sets(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, const uint8
       // config C's 1024 x 1024 grid of the Williams-Otto plant: 33 -> 19 us per constraint against the thread-per-position kernel)
       const size_t lds = sizeof(double) * ((size_t)count0 + (count0 + kAnchor - 1) / kAnchor) + sizeof(int) * 2 * ((size_t)(count0 + kAnchor - 1) / kAnchor + 2);
       SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pdt_axis0_lds<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL((k_pdt_axis0_lds<T>), dim3((unsigned)std::min<long long>(nt / count0, 1 << 16)), dim3(256), lds, c->stream, Wwin,
+      hipLaunchKernelGGL((k_pdt_axis0_lds<T>), dim3((unsigned)std::min<long long>(nt / count0, 1 << 16)), dim3(256), lds, ln.stream, Wwin,
                          nt / count0, count0, c->cs.step[0], (const SweepScalars*)sc, cidx, (const unsigned long long*)c->Lmax.p, lidx, d,
-                         xscale, cg, pc_lo, blk0, (double*)c->dist2.p);
+                         xscale, cg, pc_lo, blk0, (double*)ln.dist2.p);
     } else {
       if (c->scan_blocks && count0 >= 16 * blk0) {
         const long long nbw = (nt / count0) * ((count0 + blk0 - 1) / blk0);
-        if ((rc = ensure(c->blockmax, sizeof(T) * (size_t)nbw))) return rc;
-        hipLaunchKernelGGL((k_block_max_w<T>), dim3((unsigned)std::min<long long>((nbw + 255) / 256, 1 << 20)), dim3(256), 0, c->stream,
-                           Wwin, nt, count0, blk0, (T*)c->blockmax.p);
-        wbmax = (const T*)c->blockmax.p;
+        if ((rc = ensure(ln.blockmax, sizeof(T) * (size_t)nbw))) return rc;
+        hipLaunchKernelGGL((k_block_max_w<T>), dim3((unsigned)std::min<long long>((nbw + 255) / 256, 1 << 20)), dim3(256), 0, ln.stream,
+                           Wwin, nt, count0, blk0, (T*)ln.blockmax.p);
+        wbmax = (const T*)ln.blockmax.p;
       }
-      hipLaunchKernelGGL((k_pdt_axis0<T>), dim3(gridn), dim3(256), 0, c->stream, Wwin, nt, count0, c->cs.step[0],
+      hipLaunchKernelGGL((k_pdt_axis0<T>), dim3(gridn), dim3(256), 0, ln.stream, Wwin, nt, count0, c->cs.step[0],
                          (const SweepScalars*)sc, cidx, (const unsigned long long*)c->Lmax.p, lidx, d, xscale, cg, pc_lo, wbmax,
-                         blk0, (double*)c->dist2.p);
+                         blk0, (double*)ln.dist2.p);
     }
-    double* pin = (double*)c->dist2.p;
-    double* pout = (double*)c->dist2b.p;
+    double* pin = (double*)ln.dist2.p;
+    double* pout = (double*)ln.dist2b.p;
     long long stride = count0;
     for (int a = 1; a < d - 1; ++a) {
-      hipLaunchKernelGGL(k_pdt_scan, dim3(gridn), dim3(256), 0, c->stream, (const double*)pin, pout, nt, stride,
+      hipLaunchKernelGGL(k_pdt_scan, dim3(gridn), dim3(256), 0, ln.stream, (const double*)pin, pout, nt, stride,
                          (int)c->cs.count[a], c->cs.step[a], (const SweepScalars*)sc, cidx,
                          (const unsigned long long*)c->Lmax.p, lidx, d, xscale);
       std::swap(pin, pout);
@@ -2357,33 +2337,33 @@ static int goose_sets(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, const uint8
     const int blk = last_cnt >= 8192 ? 64 : 32;
     if (d >= 2 && last_cnt >= 4 * blk && c->scan_blocks) {
       const long long nb_ = (long long)((last_cnt + blk - 1) / blk) * stride;
-      if ((rc = ensure(c->blockmin, sizeof(double) * (size_t)nb_))) return rc;
-      hipLaunchKernelGGL(k_block_min, dim3((unsigned)std::min<long long>((stride + 63) / 64 * ((last_cnt + blk - 1) / blk), 1 << 20)), dim3(256), 0, c->stream,
-                         (const double*)pin, stride, last_cnt, blk, (double*)c->blockmin.p);
-      bmin = (const double*)c->blockmin.p;
+      if ((rc = ensure(ln.blockmin, sizeof(double) * (size_t)nb_))) return rc;
+      hipLaunchKernelGGL(k_block_min, dim3((unsigned)std::min<long long>((stride + 63) / 64 * ((last_cnt + blk - 1) / blk), 1 << 20)), dim3(256), 0, ln.stream,
+                         (const double*)pin, stride, last_cnt, blk, (double*)ln.blockmin.p);
+      bmin = (const double*)ln.blockmin.p;
     }
     const long long len0 = d >= 2 ? count0 : n, nl = n / len0;    // positions per line / local lines
     long long* slist = nullptr;                    // open points of the verdict: listed and scanned by groups of lanes
     if (bmin && blk <= 64 && c->scan_waves) {
-      if ((rc = ensure(c->scanlist, sizeof(long long) * (size_t)n))) return rc;
-      slist = (long long*)c->scanlist.p;
+      if ((rc = ensure(ln.scanlist, sizeof(long long) * (size_t)n))) return rc;
+      slist = (long long*)ln.scanlist.p;
     }
     hipLaunchKernelGGL(k_pdt_decide, dim3((unsigned)((len0 + 255) / 256), (unsigned)std::min<long long>((nl + kDecideLines - 1) / kDecideLines, 65535)),
-                       dim3(256), 0, c->stream, (const double*)pin, nl, (int)len0, goff / len0, goff, d >= 2 ? stride : 1, last_cnt, last_h, d,
-                       xscale, (const uint8_t*)c->maskU.p, (const unsigned long long*)c->Lmax.p, lidx, sc, cidx, O, (long long*)c->amb.p, cg,
+                       dim3(256), 0, ln.stream, (const double*)pin, nl, (int)len0, goff / len0, goff, d >= 2 ? stride : 1, last_cnt, last_h, d,
+                       xscale, (const uint8_t*)c->maskU.p, (const unsigned long long*)c->Lmax.p, lidx, sc, cidx, O, (long long*)ln.amb.p, cg,
                        pc_lo, pc_hi, bmin, blk, slist);
     if (slist) {
       if (c->scan_waves == 32 || c->scan_waves == 64)
-        hipLaunchKernelGGL((k_pdt_scan_list<32>), dim3(2048), dim3(256), 0, c->stream, (const double*)pin, goff, stride, last_cnt, last_h, d,
-                           xscale, (const unsigned long long*)c->Lmax.p, lidx, sc, cidx, O, (long long*)c->amb.p, bmin, blk,
+        hipLaunchKernelGGL((k_pdt_scan_list<32>), dim3(2048), dim3(256), 0, ln.stream, (const double*)pin, goff, stride, last_cnt, last_h, d,
+                           xscale, (const unsigned long long*)c->Lmax.p, lidx, sc, cidx, O, (long long*)ln.amb.p, bmin, blk,
                            (const long long*)slist);
       else
-        hipLaunchKernelGGL((k_pdt_scan_list<16>), dim3(2048), dim3(256), 0, c->stream, (const double*)pin, goff, stride, last_cnt, last_h, d,
-                           xscale, (const unsigned long long*)c->Lmax.p, lidx, sc, cidx, O, (long long*)c->amb.p, bmin, blk,
+        hipLaunchKernelGGL((k_pdt_scan_list<16>), dim3(2048), dim3(256), 0, ln.stream, (const double*)pin, goff, stride, last_cnt, last_h, d,
+                           xscale, (const unsigned long long*)c->Lmax.p, lidx, sc, cidx, O, (long long*)ln.amb.p, bmin, blk,
                            (const long long*)slist);
     }
-    hipLaunchKernelGGL((k_goose_exact<T, D>), dim3(1024), dim3(256), 0, c->stream, c->cs, css, W,
-                       (const unsigned long long*)c->Lmax.p, lidx, sc, cidx, (const long long*)c->amb.p, O,
+    hipLaunchKernelGGL((k_goose_exact<T, D>), dim3(1024), dim3(256), 0, ln.stream, c->cs, css, W,
+                       (const unsigned long long*)c->Lmax.p, lidx, sc, cidx, (const long long*)ln.amb.p, O,
                        (gb_of(c) && !c->rc_active && !c->gb_slow) ? 1 : 0);
     SBO_HIP(hipGetLastError());
     return SBO_OK;
@@ -2391,46 +2371,46 @@ static int goose_sets(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, const uint8
   // explicit lists and ragged grid ranges: pruned exact pair evaluation over runs of 256 candidates
   const long long nsrc_runs = run_hi - run_lo;
   if (nsrc_runs > 0x7fffffffll) return fail(SBO_E_UNSUPPORTED, "too many source runs");
-  if ((rc = ensure(c->runmeta, sizeof(RunMeta) * (size_t)std::max<long long>(nsrc_runs, 1)))) return rc;
+  if ((rc = ensure(ln.runmeta, sizeof(RunMeta) * (size_t)std::max<long long>(nsrc_runs, 1)))) return rc;
   if (list_index_on(c) && c->lx.valid) {
     // sources and targets in the index's sorted order: the runs' boxes are compact, so the box test skips whole runs.  Coverage
     // is a union of balls: the order of the search cannot change a verdict, and O goes back to the caller's order.
     const size_t ub = ((size_t)n + 255) / 256 * 256;
-    if ((rc = ensure(c->lxtree, 2 * ub + sizeof(T) * (size_t)n))) return rc;
-    uint8_t* Us = (uint8_t*)c->lxtree.p;
+    if ((rc = ensure(ln.lxtree, 2 * ub + sizeof(T) * (size_t)n))) return rc;
+    uint8_t* Us = (uint8_t*)ln.lxtree.p;
     uint8_t* Os = Us + ub;
     T* Ws = (T*)(Os + ub);
     const unsigned* perm = (const unsigned*)c->lx.vals.p + (size_t)c->lx.perm_half * n;
     const unsigned gb = (unsigned)std::min<long long>((n + 255) / 256, (long long)c->n_cu * 16);
-    hipLaunchKernelGGL((k_idx_gather<T>), dim3(gb), dim3(256), 0, c->stream, W, perm, n, Ws);
-    hipLaunchKernelGGL((k_idx_gather<uint8_t>), dim3(gb), dim3(256), 0, c->stream, (const uint8_t*)c->maskU.p, perm, n, Us);
+    hipLaunchKernelGGL((k_idx_gather<T>), dim3(gb), dim3(256), 0, ln.stream, W, perm, n, Ws);
+    hipLaunchKernelGGL((k_idx_gather<uint8_t>), dim3(gb), dim3(256), 0, ln.stream, (const uint8_t*)c->maskU.p, perm, n, Us);
     CandSpec csx = c->cs;
     csx.pts = c->lx.xs.p;
     csx.pts_dtype = SBO_F64;
-    hipLaunchKernelGGL((k_goose_run_meta<T, D>), dim3((unsigned)nsrc_runs), dim3(256), 0, c->stream, csx, (const T*)Ws,
-                       (const unsigned long long*)c->Lmax.p, lidx, 0ll, (RunMeta*)c->runmeta.p);
-    hipLaunchKernelGGL((k_goose_optimistic<T, D>), dim3((unsigned)((n + kRun - 1) / kRun)), dim3(256), 0, c->stream, csx, csx, (const T*)Ws,
-                       (const uint8_t*)Us, (const unsigned long long*)c->Lmax.p, lidx, (const RunMeta*)c->runmeta.p, 0ll,
+    hipLaunchKernelGGL((k_goose_run_meta<T, D>), dim3((unsigned)nsrc_runs), dim3(256), 0, ln.stream, csx, (const T*)Ws,
+                       (const unsigned long long*)c->Lmax.p, lidx, 0ll, (RunMeta*)ln.runmeta.p);
+    hipLaunchKernelGGL((k_goose_optimistic<T, D>), dim3((unsigned)((n + kRun - 1) / kRun)), dim3(256), 0, ln.stream, csx, csx, (const T*)Ws,
+                       (const uint8_t*)Us, (const unsigned long long*)c->Lmax.p, lidx, (const RunMeta*)ln.runmeta.p, 0ll,
                        (int)nsrc_runs, Os);
-    hipLaunchKernelGGL(k_idx_scatter_u8, dim3(gb), dim3(256), 0, c->stream, (const uint8_t*)Os, perm, n, O);
+    hipLaunchKernelGGL(k_idx_scatter_u8, dim3(gb), dim3(256), 0, ln.stream, (const uint8_t*)Os, perm, n, O);
     SBO_HIP(hipGetLastError());
     return SBO_OK;
   }
-  hipLaunchKernelGGL((k_goose_run_meta<T, D>), dim3((unsigned)nsrc_runs), dim3(256), 0, c->stream, css, W,
-                     (const unsigned long long*)c->Lmax.p, lidx, run_lo, (RunMeta*)c->runmeta.p);
-  hipLaunchKernelGGL((k_goose_optimistic<T, D>), dim3((unsigned)((n + kRun - 1) / kRun)), dim3(256), 0, c->stream, c->cs, css, W,
-                     (const uint8_t*)c->maskU.p, (const unsigned long long*)c->Lmax.p, lidx, (const RunMeta*)c->runmeta.p,
+  hipLaunchKernelGGL((k_goose_run_meta<T, D>), dim3((unsigned)nsrc_runs), dim3(256), 0, ln.stream, css, W,
+                     (const unsigned long long*)c->Lmax.p, lidx, run_lo, (RunMeta*)ln.runmeta.p);
+  hipLaunchKernelGGL((k_goose_optimistic<T, D>), dim3((unsigned)((n + kRun - 1) / kRun)), dim3(256), 0, ln.stream, c->cs, css, W,
+                     (const uint8_t*)c->maskU.p, (const unsigned long long*)c->Lmax.p, lidx, (const RunMeta*)ln.runmeta.p,
                      run_lo, (int)nsrc_runs, O);
   SBO_HIP(hipGetLastError());
   return SBO_OK;
 }
 
 template <typename T>
-static int goose_sets_d(sbo_ctx* c, const sbo_sweep_opts* o, int cidx, const uint8_t* src, uint8_t* O) {
+static int goose_sets_d(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, int cidx, const uint8_t* src, uint8_t* O) {
   switch (c->mc.dpad) {
-    case 2: return goose_sets<T, 2>(c, o, cidx, src, O);
-    case 4: return goose_sets<T, 4>(c, o, cidx, src, O);
-    case 8: return goose_sets<T, 8>(c, o, cidx, src, O);
+    case 2: return goose_sets<T, 2>(c, ln, o, cidx, src, O);
+    case 4: return goose_sets<T, 4>(c, ln, o, cidx, src, O);
+    case 8: return goose_sets<T, 8>(c, ln, o, cidx, src, O);
   }
   return fail(SBO_E_UNSUPPORTED, "unsupported padded dimension");
 }
@@ -2488,21 +2468,19 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_result* 
     for (int cc = 1; cc < q; ++cc) {
       uint8_t* G = (uint8_t*)c->maskG.p + (size_t)(cc - 1) * n;
       uint8_t* O = (uint8_t*)c->maskO.p + (size_t)(cc - 1) * n;
-      LaneScope lane(c, lanes && ((cc - 1) & 1));              // constraints alternate between the two lanes
+      sbo_ctx::SetLane& ln = c->lane[lanes && ((cc - 1) & 1)];   // constraints alternate between the two lanes
       // (a large explicit list has no transform to build G_c with: all of S_t stays the source set there)
-      long long plane = 1;
-      for (int a = 0; a < c->cs.d - 1; ++a) plane *= c->cs.count[a];
-      const bool can_expand = n <= (1ll << 17) || (c->cs.kind == 1 && c->cs.first % plane == 0 && n % plane == 0);   // (larger lists: S_t is the source set)
+      const bool can_expand = n <= (1ll << 17) || whole_planes(c);   // (larger lists: S_t is the source set)
       const uint8_t* src = (const uint8_t*)c->maskS.p;
       if (can_expand) {
-        if ((rc = expander_set<T>(c, o, cc, G))) return rc;
+        if ((rc = expander_set<T>(c, ln, o, cc, G))) return rc;
         src = G;
       }
-      if ((rc = goose_sets_d<T>(c, o, cc, src, O))) return rc;
+      if ((rc = goose_sets_d<T>(c, ln, o, cc, src, O))) return rc;
     }
     if (lanes && (rc = lanes_join(c))) return rc;
   }
-  SweepScalars* sc = (SweepScalars*)c->scal.p;
+  SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
   if (c->phase_events) SBO_HIP(hipEventRecord(c->ev[3], c->stream));
   // arg-min of lcb_0 over S_t and over every O_c: the bound is computed for the masked candidates only; one launch, the q
   // reductions side by side
@@ -2519,11 +2497,11 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_result* 
   // Single rank: the explore step (target choice, distances, arg-min over S) is enqueued before the read-back, one host
   // round trip per sweep; ranks > 1 need the merged target slots first and take a second one below.
   const bool fused_explore = !multi_rank(c) && q > 1;
-  double* dev_t = (double*)c->scal.p + 256;
+  double* dev_t = (double*)c->lane[0].scal.p + 256;
   // (one rank: the finals and the target choice in one launch, the last merge writes the host's block itself)
   const int gbon = gb_of(c) ? 1 : 0;
   const bool short_tail = fused_explore && c->result_mirror && (c->mc.dpad == 2 || c->mc.dpad == 4 || c->mc.dpad == 8);
-  const SweepScalars* l1 = lanes ? (const SweepScalars*)c->lane1.scal.p : (const SweepScalars*)nullptr;
+  const SweepScalars* l1 = lanes ? (const SweepScalars*)c->lane[1].scal.p : (const SweepScalars*)nullptr;
   if (short_tail) {
     switch (c->mc.dpad) {
       case 2: hipLaunchKernelGGL((k_goose_finals<2>), dim3((unsigned)q), dim3(256), 0, c->stream, (const unsigned char*)pbase, pstride, n > 0 ? nb : 0, q, sc, l1, c->cs, dev_t, gbon); break;
@@ -2669,9 +2647,9 @@ static int sweep_tr_t(sbo_ctx* c, const sbo_sweep_opts* o, const double* x0, dou
   SBO_HIP(k1_stop(c, post));
   if (!reuse && !c->rc_active && (rc = guard_audit_enqueue(c, post))) return rc;
   if ((rc = sweep_common_front<T>(c, o, post))) return rc;
-  SweepScalars* sc = (SweepScalars*)c->scal.p;
+  SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
   const int nb = reduce_blocks(c);
-  double* dev_x0 = (double*)c->scal.p + 256;
+  double* dev_x0 = (double*)c->lane[0].scal.p + 256;
   SBO_HIP(hipMemcpyAsync(dev_x0, x0, sizeof(double) * c->cs.d, hipMemcpyHostToDevice, c->stream));
   if (n > 0) {
     switch (c->mc.dpad) {
@@ -2740,10 +2718,10 @@ __global__ void k_robust_out(const SweepScalars* sc, long long* out4) {
 }
 int robust_argmin(sbo_ctx* c, const double* f, const double* fb, const uint8_t* mask, long long Nc, bool gb_on, long long* out4) {
   int rc;
-  if ((rc = ensure(c->scal, sizeof(SweepScalars)))) return rc;
+  if ((rc = ensure(c->lane[0].scal, sizeof(SweepScalars)))) return rc;
   const int nb = (int)std::max<long long>(1, std::min<long long>((Nc + 255) / 256, (long long)c->n_cu * 4));
   if ((rc = ensure(c->partial, partial_stride(nb)))) return rc;
-  SweepScalars* sc = (SweepScalars*)c->scal.p;
+  SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
   SBO_HIP(hipMemsetAsync(sc, 0, sizeof(SweepScalars), c->stream));
   if (Nc > 0)
     hipLaunchKernelGGL((k_arg_masked<double, false, ValRobust>), dim3(nb), dim3(256), 0, c->stream, ValRobust{f, fb, gb_on}, mask, Nc, 0LL,
@@ -2835,12 +2813,12 @@ int sbo_explore_safeset(sbo_ctx* c, const double* target, int64_t* index_out, do
   SBO_HIP(hipSetDevice(c->device));
   const long long n = c->cs.n_local;
   int rc;
-  if ((rc = ensure(c->scal, sizeof(SweepScalars)))) return rc;
+  if ((rc = ensure(c->lane[0].scal, sizeof(SweepScalars)))) return rc;
   const int nb = reduce_blocks(c);
   if ((rc = ensure(c->partial, partial_stride(nb)))) return rc;
   if (c->masks_bits && n > 0) col_expand(c, c->cbS, (uint8_t*)c->maskS.p);
-  SweepScalars* sc = (SweepScalars*)c->scal.p;
-  double* dev_t = (double*)c->scal.p + 256;
+  SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
+  double* dev_t = (double*)c->lane[0].scal.p + 256;
   double t8[SBO_MAX_D] = {0};
   for (int a = 0; a < c->cs.d; ++a) t8[a] = target[a];
   SBO_HIP(hipMemcpyAsync(dev_t, t8, sizeof(t8), hipMemcpyHostToDevice, c->stream));

@@ -1025,8 +1025,9 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const PostOutcome&
   for (int a = 0; a < 2; ++a) { h2 += c->cs.step[a] * c->cs.step[a]; hmax = std::max(hmax, c->cs.step[a]); }
   gm.delta = (kCoarse - 1) * std::sqrt(h2) * (1.0 + 1e-9);
   const int lidx = o->reference_quirk_L_index ? q - 1 : 1;     // models/SafeOpt.py:110 (loop-leaked i)
-  if ((rc = ensure(c->scal, sizeof(SweepScalars)))) return rc;
-  SweepScalars* sc = (SweepScalars*)c->scal.p;
+  sbo_ctx::SetLane& ln = c->lane[0];     // (one constraint: the main lane's scalar block and lists, whichever stream the chains run on)
+  if ((rc = ensure(ln.scal, sizeof(SweepScalars)))) return rc;
+  SweepScalars* sc = (SweepScalars*)ln.scal.p;
   // (their own small block: the objective's scalars, the finals' tickets and intermediate rows)
   static_assert(128 + 2 * kColFinParts * sizeof(ColFinRow) <= 4096, "column path scalar block");
   const bool fresh_fin = c->col_fin.bytes < 4096;
@@ -1047,8 +1048,8 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const PostOutcome&
   unsigned char* pbase = (unsigned char*)c->partial.p;
   Best* reg0 = (Best*)pbase;
   Best* reg1 = (Best*)(pbase + 2 * pstride);
-  if ((rc = ensure(c->amb, sizeof(long long) * (size_t)n))) return rc;
-  if ((rc = ensure(c->scanlist, 2 * sizeof(long long) * (size_t)n))) return rc;
+  if ((rc = ensure(ln.amb, sizeof(long long) * (size_t)n))) return rc;
+  if ((rc = ensure(ln.scanlist, 2 * sizeof(long long) * (size_t)n))) return rc;
   if ((rc = ensure(c->col_img, sizeof(unsigned short) * (size_t)n + 64))) return rc;
   if ((rc = ensure(c->col_bmin, sizeof(unsigned short) * (size_t)gm.H * gm.NBp + 64))) return rc;
   // coarse column image / block minima (rows padded to whole 64-row coarse segments; block-minimum entries beyond the row stay 0xffff)
@@ -1103,10 +1104,10 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const PostOutcome&
   const int ntiles = post.fuse_rows / 2;
   hipLaunchKernelGGL(k_col_decide, dim3((unsigned)ndw), dim3(256), 0, es, gm, (const unsigned long long*)cb.Sw, (const unsigned long long*)cb.slots,
                      rows, rows + (size_t)(kRowRmax + 1) * c->cpart_cap, (const unsigned short*)c->col_cimg.p, (const unsigned short*)c->col_cbmin.p,
-                     2.0 * gm.delta + 2.0 * kCoarse * hmax, cb.Usum, (const unsigned short*)c->col_img.p, cv, sc, (unsigned long long*)c->cbG.p, (long long*)c->scanlist.p);
+                     2.0 * gm.delta + 2.0 * kCoarse * hmax, cb.Usum, (const unsigned short*)c->col_img.p, cv, sc, (unsigned long long*)c->cbG.p, (long long*)ln.scanlist.p);
   hipLaunchKernelGGL(k_col_scan, dim3((unsigned)nsc), dim3(256), 0, es, gm, (const unsigned short*)c->col_img.p, (const unsigned short*)c->col_bmin.p,
-                     cv, sc, (unsigned long long*)c->cbG.p, (long long*)c->amb.p, (const long long*)c->scanlist.p);
-  c->amb_clean = false;
+                     cv, sc, (unsigned long long*)c->cbG.p, (long long*)ln.amb.p, (const long long*)ln.scanlist.p);
+  ln.amb_clean = false;
   if (overlap) {
     SBO_HIP(hipEventRecord(c->ev_col[1], es));
     SBO_HIP(hipStreamWaitEvent(xs, c->ev_col[1], 0));
@@ -1145,7 +1146,7 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const PostOutcome&
     // masks, then the expanders' arg-max and the finals once more (slot 0 is where that merge expects it)
     col_expand(c, c->cbU, (uint8_t*)c->maskU.p);
     col_expand(c, c->cbG, (uint8_t*)c->maskG.p);
-    if ((rc = launch_exact_d<double>(c, o, 1, lidx, (uint8_t*)c->maskG.p))) return rc;
+    if ((rc = launch_exact_d<double>(c, ln, o, 1, lidx, (uint8_t*)c->maskG.p))) return rc;
     hipLaunchKernelGGL((k_arg_masked_multi<double, true, ValArray<double>>), dim3((unsigned)nb, 1u), dim3(256), 0, c->stream,
                        ValArray<double>{(const double*)c->var.p, 0.0}, (const uint8_t*)nullptr, (const uint8_t*)c->maskG.p, n, (long long)c->cs.first, pbase,
                        pstride, 1, gb_of(c));

@@ -718,7 +718,7 @@ static int sweep_tr_recheck(sbo_ctx* c, const sbo_sweep_opts* o, const double* x
   if (q == 1) {
     // arg-min lcb_0 over the ball: the ball as a mask (exact geometry), then the contenders inside it
     if ((rc = ensure(c->maskM, (size_t)n))) return rc;
-    double* dev_x0 = (double*)c->scal.p + 256;
+    double* dev_x0 = (double*)c->lane[0].scal.p + 256;
     SBO_HIP(hipMemcpyAsync(dev_x0, x0, sizeof(double) * c->cs.d, hipMemcpyHostToDevice, c->stream));
     const unsigned nbk = (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)c->n_cu * 4));
     switch (c->mc.dpad) {
