@@ -365,6 +365,44 @@ int sbo_fit_local(sbo_ctx* ctx, int n, int d, int q, const double* X_norm, const
                   const double* lo, const double* hi, int maxiter, double ftol, double gtol, double* best_x, double* best_nll,
                   double* x_out, double* nll_out, int* iters_out, int* evals_out, double* pgnorm_out, int* status_out);
 
+/* sbo_fit_de for q outputs side by side: column o of Y_norm[n, q] is searched with seeds[o] from the shared init_pop[P, d+2], one
+ * launch per generation for all outputs (one workgroup per member and output) and one read-back of the q P energies per convergence
+ * check (every 8th generation and the last).  Output o comes out bit for bit as sbo_fit_de gives it for that column and seed:
+ * best_x[q, d+2], best_energy[q], generations[q] (may be NULL).  An output that has converged is frozen while the others go on. */
+int sbo_fit_de_batch(sbo_ctx* ctx, int n, int d, int q, const double* X_norm, const double* Y_norm, int P, const double* lo,
+                     const double* hi, const double* init_pop, const uint64_t* seeds, int maxiter, double tol, double atol,
+                     double* best_x, double* best_energy, int* generations);
+
+/* ---- fit and build in one call ------------------------------------------ */
+typedef struct sbo_fit_opts {
+  int32_t  P, maxiter;                 /* DE population (>= 4) and generation limit                          */
+  double   tol, atol;                  /* DE stop: std(E) <= atol + tol |mean(E)|                            */
+  uint64_t seed;                       /* output o searches with seed + o                                    */
+  int32_t  polish, polish_maxiter;     /* 1: projected BFGS from every output's DE best; <= 0: 10000 steps   */
+  double   polish_ftol, polish_gtol;   /* <= 0: float32 eps, 1e-8                                            */
+  double   lo[SBO_MAX_D + 2], hi[SBO_MAX_D + 2];   /* the box of the search and of the polish, [d+2] used    */
+} sbo_fit_opts;
+
+typedef struct sbo_fit_report {
+  double  de_nll[SBO_MAX_Q], nll[SBO_MAX_Q];        /* best NLL after the DE / after the polish (what the model uses) */
+  int32_t generations[SBO_MAX_Q], polish_status[SBO_MAX_Q] /* sbo_fit_status, -1 without a polish */, polish_evals[SBO_MAX_Q],
+          polished[SBO_MAX_Q];                      /* 1: the polished point was strictly lower and replaced the DE's  */
+  double  de_ms, polish_ms, build_ms, total_ms;     /* host clock around each phase                                   */
+  int32_t host_syncs, reserved;                     /* read-backs the fit waited for: one per convergence check + 1    */
+} sbo_fit_report;
+
+/* From normalised data to a resident, sweepable model (models/GP_Safe.py:194-245 without the host in the middle): the DE of
+ * sbo_fit_de_batch for all q outputs (output o with opts->seed + o, from init_pop[P, d+2]), with opts->polish one sbo_fit_local-style
+ * projected BFGS per output from its DE best on the same box -- kept only where its NLL is strictly lower --, then the model build of
+ * sbo_model_set_prior(..., hypopt_out, invK_list = NULL, mean_prior) (SBO_FACTOR_CHOL).  hypopt_out[d+2, q] is written in the layout
+ * sbo_model_set takes; report may be NULL.  No [n, n] matrix crosses the bus in either direction.  The fit runs in fp64 whatever
+ * dtype says; dtype tags the built model.  Status codes as sbo_fit_de / sbo_fit_local / sbo_model_set give them; an output whose
+ * whole final population has no finite NLL is SBO_E_INVALID.  A failure before the build leaves the resident model untouched; a
+ * failure of the build behaves as sbo_model_set's.  Deterministic; no collectives (every rank fits its replicated data). */
+int sbo_model_fit(sbo_ctx* ctx, int dtype, const char* kernel, int n, int d, int q, const double* X_mean, const double* X_std,
+                  const double* Y_mean, const double* Y_std, const double* X_norm, const double* Y_norm, const double* mean_prior,
+                  const sbo_fit_opts* opts, const double* init_pop, double* hypopt_out, sbo_fit_report* report);
+
 /* ---- local refinement of an acquisition optimum off the grid ------------ */
 /* per-seed outcome of sbo_refine */
 enum sbo_refine_status {

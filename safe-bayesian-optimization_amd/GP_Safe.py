@@ -5,7 +5,8 @@ Same method names, argument meaning and error behaviour as the reference ``GP`` 
 arithmetic runs: the posterior (``GP_inference``) is evaluated by the HIP kernels behind the C ABI, batched
 when the caller passes many points.  Model fitting (normalisation, hyper-parameter search) is host NumPy/SciPy by
 default; with ``fit_on_device = True`` the differential-evolution search evaluates its whole population per
-generation with the batched device objective ``sbo_nll_batch``.
+generation with the batched device objective ``sbo_nll_batch``; ``"de"`` runs the whole search
+on the device, and ``"model"`` the search of every output side by side, the polish and the model build (``sbo_model_fit``).
 
 Differences that are deliberate and documented:
   * no JAX: ``key`` arguments are ``numpy.random.Generator`` objects (or seeds); the reference's threefry
@@ -22,6 +23,37 @@ from scipy.optimize import differential_evolution
 from .engine import SweepEngine
 
 FLOAT32_EPS = float(np.finfo(np.float32).eps)
+
+
+class LazyInvK:
+    """``invKopt`` of a model the device fitted and built itself (``fit_on_device = "model"``): a sequence of q matrices
+    inv(K_i + (sn2_i + float32 eps) I), each formed from ``hypopt`` on its first read and kept -- a loop that never reads one never
+    pays its O(n^3).  ``materialised`` is True once every element exists; ``SweepEngine.set_model`` uploads such a dataset with
+    ``use_invK=False`` until then."""
+
+    def __init__(self, compute, q):
+        self._compute = compute      # i -> [n, n]
+        self._items = [None] * q
+
+    @property
+    def materialised(self):
+        return all(a is not None for a in self._items)
+
+    def __len__(self):
+        return len(self._items)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self._items)))]
+        if self._items[i] is None:
+            self._items[i] = self._compute(range(len(self._items))[i])
+        return self._items[i]
+
+    def __setitem__(self, i, value):
+        self._items[i] = value
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self._items)))
 
 
 class GP:
@@ -42,7 +74,8 @@ class GP:
         self.fixed_hyper = None
         self.de_options = {}         # forwarded to scipy DE (e.g. {"seed": 0, "maxiter": 50})
         self.fit_on_device = False   # True: DE evaluates whole populations with the batched device NLL (sbo_nll_batch);
-                                     # "de": the whole DE search runs on the device (sbo_fit_de), polish on the host
+                                     # "de": the whole DE search runs on the device (sbo_fit_de), polish on the host;
+                                     # "model": search, polish and model build on the device in one call (sbo_model_fit)
         self.var_out = True
 
     # ---- engine plumbing -----------------------------------------------------------------------------------
@@ -126,6 +159,8 @@ class GP:
         then invK = inv(K + (sn2 + float32 eps) I)."""
         d = self.nx_dim
         bounds = np.array([[-1.5, 1.5]] * (d + 1) + [[self.noise_lower_bound, -2.0]])
+        if self.fit_on_device == "model" and self.fixed_hyper is None:
+            return self._fit_model_on_device(X_norm, Y_norm, bounds)
         hypopt = np.zeros((d + 2, self.ny_dim))
         invKopt = []
         for i in range(self.ny_dim):
@@ -161,18 +196,45 @@ class GP:
                 res = differential_evolution(self.negative_loglikelihood, args=(X_norm, Y_norm[:, i:i + 1]), bounds=bounds,
                                              **self.de_options)
                 hypopt[:, i] = res.x
-            ell = np.exp(2.0 * hypopt[:d, i])
-            sf2 = np.exp(2.0 * hypopt[d, i])
-            sn2 = np.exp(2.0 * hypopt[d + 1, i]) + FLOAT32_EPS
-            K = self.Cov_mat(self.kernel, X_norm, X_norm, ell, sf2) + sn2 * np.eye(self.n_point)
-            invKopt.append(np.linalg.inv(K))
+            invKopt.append(self._invK(X_norm, hypopt, i))
         return hypopt, invKopt
+
+    def _invK(self, X_norm, hypopt, i):
+        """inv(K_i + (sn2_i + float32 eps) I) of output i (models/GP_Safe.py:226-232)."""
+        d = X_norm.shape[1]
+        ell = np.exp(2.0 * hypopt[:d, i])
+        sf2 = np.exp(2.0 * hypopt[d, i])
+        sn2 = np.exp(2.0 * hypopt[d + 1, i]) + FLOAT32_EPS
+        K = self.Cov_mat(self.kernel, X_norm, X_norm, ell, sf2) + sn2 * np.eye(X_norm.shape[0])
+        return np.linalg.inv(K)
+
+    def _fit_model_on_device(self, X_norm, Y_norm, bounds):
+        """``fit_on_device = "model"``: one ``sbo_model_fit`` call -- the DE of every output side by side, the polish and the model
+        build on the device -- with the population, seeds and ``de_options`` keys of the "de" mode.  The device model is then
+        current (``_device_model_fitted`` makes the caller mark it so); ``invKopt`` is formed on the host only if somebody reads it."""
+        from scipy.stats import qmc
+        d = self.nx_dim
+        opts = dict(self.de_options)
+        seed = int(opts.get("seed", 0) or 0)
+        P = int(opts.get("popsize", 15)) * (d + 2)
+        pop = qmc.scale(qmc.LatinHypercube(d + 2, seed=seed).random(P), bounds[:, 0], bounds[:, 1])
+        ds = {"X_mean": self.X_mean, "X_std": self.X_std, "Y_mean": self.Y_mean, "Y_std": self.Y_std, "X_norm": X_norm, "Y_norm": Y_norm}
+        self.fit_report = self.engine.model_fit(ds, bounds, pop, seed=seed, maxiter=int(opts.get("maxiter", 1000)),
+                                                tol=float(opts.get("tol", 0.01)), atol=float(opts.get("atol", 0.0)),
+                                                polish=bool(opts.get("polish", True)), dtype=self.dtype, kernel=self.kernel,
+                                                mean_prior=self._mean_prior(ds))
+        hypopt = self.fit_report["hypopt"]
+        self._device_model_fitted = True
+        return hypopt, LazyInvK(lambda i: self._invK(X_norm, hypopt, i), self.ny_dim)
 
     def update_inference_dataset(self):
         ds = self.inference_datasets
         ds["X_mean"], ds["X_std"], ds["Y_mean"], ds["Y_std"] = self.X_mean, self.X_std, self.Y_mean, self.Y_std
         ds["X_norm"], ds["Y_norm"], ds["invKopt"], ds["hypopt"] = self.X_norm, self.Y_norm, self.invKopt, self.hypopt
         self._model_version += 1
+        if self.__dict__.pop("_device_model_fitted", False):
+            self._uploaded_version = self._model_version   # sbo_model_fit built this very model on the device: no upload
+            self._cand_token = None
 
     # ---- initialisation / update (models/GP_Safe.py:251-304) ---------------------------------------------------
     def GP_initialization(self, X, Y, kernel, multi_hyper, var_out=True):

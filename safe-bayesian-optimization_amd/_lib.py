@@ -86,6 +86,19 @@ class RefineResult(C.Structure):
                 ("converged", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FitOpts(C.Structure):
+    _fields_ = [("P", C.c_int32), ("maxiter", C.c_int32), ("tol", C.c_double), ("atol", C.c_double), ("seed", C.c_uint64),
+                ("polish", C.c_int32), ("polish_maxiter", C.c_int32), ("polish_ftol", C.c_double), ("polish_gtol", C.c_double),
+                ("lo", C.c_double * (SBO_MAX_D + 2)), ("hi", C.c_double * (SBO_MAX_D + 2))]
+
+
+class FitReport(C.Structure):
+    _fields_ = [("de_nll", C.c_double * SBO_MAX_Q), ("nll", C.c_double * SBO_MAX_Q), ("generations", C.c_int32 * SBO_MAX_Q),
+                ("polish_status", C.c_int32 * SBO_MAX_Q), ("polish_evals", C.c_int32 * SBO_MAX_Q), ("polished", C.c_int32 * SBO_MAX_Q),
+                ("de_ms", C.c_double), ("polish_ms", C.c_double), ("build_ms", C.c_double), ("total_ms", C.c_double),
+                ("host_syncs", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Profile(C.Structure):
     _fields_ = [
         ("posterior_ms", C.c_double), ("classify_ms", C.c_double), ("expander_ms", C.c_double),
@@ -144,6 +157,10 @@ SYMBOLS = [
     ("sbo_nll_grad_batch", C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
     ("sbo_fit_local", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_double, C.c_double, _P, _P,
                                 _P, _P, _P, _P, _P, _P]),
+    ("sbo_fit_de_batch", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_double, C.c_double, _P, _P,
+                                   _P]),
+    ("sbo_model_fit", C.c_int, [_P, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.POINTER(FitOpts), _P, _P,
+                                C.POINTER(FitReport)]),
     ("sbo_refine", C.c_int, [_P, C.POINTER(RefineOpts), C.c_int64, _P, _P, _P, _P, C.POINTER(RefineResult)]),
     ("sbo_plant_wo", C.c_int, [_P, C.c_int64, _P, _P]),
     ("sbo_profile_get", C.c_int, [_P, C.POINTER(Profile)]),

@@ -511,6 +511,64 @@ int sbo_model_set_prior(sbo_ctx* c, int dtype, const char* kernel, int n, int d,
   return model_set_impl(c, dtype, kernel, n, d, q, X_mean, X_std, Y_mean, Y_std, X_norm, Y_norm, hypopt, invK_list, mean_prior);
 }
 
+// From (X_norm, Y_norm) to a resident model without the host in the middle: the DE of every output side by
+// side, a polish from every output's best, then the build of sbo_model_set_prior(..., hypopt_out, NULL, mean_prior).  Everything that
+// can fail before the build is checked before the resident model is touched.
+int sbo_model_fit(sbo_ctx* c, int dtype, const char* kernel, int n, int d, int q, const double* X_mean, const double* X_std,
+                  const double* Y_mean, const double* Y_std, const double* X_norm, const double* Y_norm, const double* mean_prior,
+                  const sbo_fit_opts* opts, const double* init_pop, double* hypopt_out, sbo_fit_report* report) {
+  using clk = std::chrono::steady_clock;
+  const auto t0 = clk::now();
+  if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
+  if (!kernel || strcmp(kernel, "RBF") != 0)      // models/GP_Safe.py:159-162
+    return fail(SBO_E_INVALID, std::string("ERROR no kernel with name ") + (kernel ? kernel : "(null)"));
+  if (dtype != SBO_F64 && dtype != SBO_F32) return fail(SBO_E_INVALID, "dtype must be SBO_F64 or SBO_F32");
+  if (n < 1 || n > SBO_MAX_N) return fail(SBO_E_INVALID, "n out of range [1, SBO_MAX_N]");
+  if (d < 1 || d > SBO_MAX_D) return fail(SBO_E_INVALID, "d out of range [1, SBO_MAX_D]");
+  if (q < 1 || q > SBO_MAX_Q) return fail(SBO_E_INVALID, "q out of range [1, SBO_MAX_Q]");
+  if (!X_mean || !X_std || !Y_mean || !Y_std || !X_norm || !Y_norm) return fail(SBO_E_INVALID, "NULL model array");
+  if (!opts || !init_pop || !hypopt_out) return fail(SBO_E_INVALID, "NULL argument");
+  if (opts->P < 4 || opts->maxiter < 0) return fail(SBO_E_INVALID, "P or maxiter out of range");
+  const int D = d + 2;
+  for (int a = 0; a < D; ++a)
+    if (!(opts->lo[a] <= opts->hi[a])) return fail(SBO_E_INVALID, "bounds need lo <= hi");
+  if (mean_prior)
+    for (int o = 0; o < q; ++o)
+      if (!std::isfinite(mean_prior[o])) return fail(SBO_E_INVALID, "mean_prior must be finite");
+  uint64_t seeds[SBO_MAX_Q];
+  for (int o = 0; o < q; ++o) seeds[o] = opts->seed + (uint64_t)o;
+  const double f32eps = (double)std::numeric_limits<float>::epsilon();
+  FitBatchResult r;
+  int rc = fit_batch(c, n, d, q, X_norm, Y_norm, opts->P, opts->lo, opts->hi, init_pop, seeds, opts->maxiter, opts->tol, opts->atol,
+                     opts->polish ? 1 : 0, opts->polish_maxiter > 0 ? opts->polish_maxiter : 10000,
+                     opts->polish_ftol > 0.0 ? opts->polish_ftol : f32eps, opts->polish_gtol > 0.0 ? opts->polish_gtol : 1e-8, r);
+  if (rc) return rc;
+  for (int o = 0; o < q; ++o)
+    if (!std::isfinite(r.nll[o])) return fail(SBO_E_INVALID, "the fit of output " + std::to_string(o) + " found no member with a finite likelihood");
+  for (int o = 0; o < q; ++o)
+    for (int a = 0; a < D; ++a) hypopt_out[(size_t)a * q + o] = r.x[o][a];
+  const auto t1 = clk::now();
+  rc = model_set_impl(c, dtype, kernel, n, d, q, X_mean, X_std, Y_mean, Y_std, X_norm, Y_norm, hypopt_out, nullptr, mean_prior);
+  const auto t2 = clk::now();
+  if (report) {
+    memset(report, 0, sizeof(*report));
+    for (int o = 0; o < q; ++o) {
+      report->de_nll[o] = r.de_nll[o];
+      report->nll[o] = r.nll[o];
+      report->generations[o] = r.generations[o];
+      report->polish_status[o] = r.polish_status[o];
+      report->polish_evals[o] = r.polish_evals[o];
+      report->polished[o] = r.polished[o];
+    }
+    report->de_ms = r.de_ms;
+    report->polish_ms = r.polish_ms;
+    report->build_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    report->total_ms = std::chrono::duration<double, std::milli>(t2 - t0).count();
+    report->host_syncs = r.host_syncs;
+  }
+  return rc;
+}
+
 // one more observation under frozen hyper-parameters and normalisation, O(n^2) on the
 // device instead of a refit (the reference always refits and renormalises, models/GP_Safe.py:283-304 -- this is an
 // opt-in fast path, not its behaviour).

@@ -9,6 +9,7 @@
 // that every inner loop walks contiguous memory; the right-hand side y rides along as an extra column, so the forward
 // solve costs no extra synchronisation.  Matrices live in an HBM workspace (L2-resident at the reference's sizes).
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <vector>
 #include "device_common.hpp"
@@ -106,6 +107,17 @@ __global__ __launch_bounds__(1024) void k_nll_batch(int n, int d, const double* 
   if (threadIdx.x == 0) out[p] = v;
 }
 
+// The same for q outputs at once (sbo_fit_de_batch): grid (P, q), member p of output o on hyper[o][p], column o of yT and its own
+// n x n slice of the workspace.
+__global__ __launch_bounds__(1024) void k_nll_batch_q(int n, int d, int P, const double* __restrict__ X, const double* __restrict__ yT,
+                                                      const double* __restrict__ hyper, double* __restrict__ work,
+                                                      double* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const size_t m = (size_t)blockIdx.y * P + blockIdx.x;
+  const double v = nll_member(n, d, X, yT + (size_t)blockIdx.y * n, hyper + m * (d + 2), work + m * n * n, reinterpret_cast<double*>(smem));
+  if (threadIdx.x == 0) out[m] = v;
+}
+
 // ---- differential evolution on the device --------------------------------------------------------------------------
 // One generation of SciPy's default strategy as the reference calls it (models/GP_Safe.py:224: best1bin, dithered
 // mutation, recombination 0.7) with deferred updating: workgroup i builds the trial vector of member i from the current
@@ -121,14 +133,13 @@ __device__ __forceinline__ double u01(unsigned long long seed, unsigned gen, uns
   return (double)(k >> 11) * (1.0 / 9007199254740992.0);
 }
 
-__global__ __launch_bounds__(1024) void k_de_step(int n, int d, const double* __restrict__ X, const double* __restrict__ y, int P,
-                                                  const double* __restrict__ pop, const double* __restrict__ energy,
-                                                  double* __restrict__ pop_next, double* __restrict__ energy_next,
-                                                  const double* __restrict__ lo, const double* __restrict__ hi, double F, double CR,
-                                                  unsigned long long seed, unsigned gen, double* __restrict__ work) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ double trial[SBO_MAX_D + 2];
-  const int i = blockIdx.x, D = d + 2;
+// Member i of one population: trial vector (thread 0, into `trial`), its NLL on the workspace U, selection into the next generation.
+__device__ __forceinline__ void de_member(int n, int d, const double* __restrict__ X, const double* __restrict__ y, int P, int i,
+                                          const double* __restrict__ pop, const double* __restrict__ energy, double* __restrict__ pop_next,
+                                          double* __restrict__ energy_next, const double* __restrict__ lo, const double* __restrict__ hi,
+                                          double F, double CR, unsigned long long seed, unsigned gen, double* __restrict__ U,
+                                          double* smem_d, double* trial) {
+  const int D = d + 2;
   if (threadIdx.x == 0) {
     int best = 0;                                    // best of the current generation (lowest index on ties)
     for (int p = 1; p < P; ++p)
@@ -151,12 +162,76 @@ __global__ __launch_bounds__(1024) void k_de_step(int n, int d, const double* __
     }
   }
   __syncthreads();
-  const double e = nll_member(n, d, X, y, trial, work + (size_t)i * n * n, reinterpret_cast<double*>(smem));
+  const double e = nll_member(n, d, X, y, trial, U, smem_d);
   if (threadIdx.x == 0) {
     const bool take = e <= energy[i];                // scipy: "if energy <= self.population_energies[candidate]"
     for (int a = 0; a < D; ++a) pop_next[(size_t)i * D + a] = take ? trial[a] : pop[(size_t)i * D + a];
     energy_next[i] = take ? e : energy[i];
   }
+}
+
+__global__ __launch_bounds__(1024) void k_de_step(int n, int d, const double* __restrict__ X, const double* __restrict__ y, int P,
+                                                  const double* __restrict__ pop, const double* __restrict__ energy,
+                                                  double* __restrict__ pop_next, double* __restrict__ energy_next,
+                                                  const double* __restrict__ lo, const double* __restrict__ hi, double F, double CR,
+                                                  unsigned long long seed, unsigned gen, double* __restrict__ work) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ double trial[SBO_MAX_D + 2];
+  const int i = blockIdx.x;
+  de_member(n, d, X, y, P, i, pop, energy, pop_next, energy_next, lo, hi, F, CR, seed, gen, work + (size_t)i * n * n,
+            reinterpret_cast<double*>(smem), trial);
+}
+
+// One generation of q searches side by side (sbo_fit_de_batch): grid (P, q), workgroup (i, o) is member i of output o's population
+// [o][P][d + 2], with that output's seed and dithered F.  An output whose search has stopped (active[o] == 0) is left as it is: its
+// workgroups return at once and its population stays in the buffer its last generation wrote.
+struct DeTable {
+  double F[SBO_MAX_Q];
+  unsigned long long seed[SBO_MAX_Q];
+  int active[SBO_MAX_Q];
+};
+
+__global__ __launch_bounds__(1024) void k_de_step_q(int n, int d, const double* __restrict__ X, const double* __restrict__ yT, int P,
+                                                    const double* __restrict__ pop, const double* __restrict__ energy,
+                                                    double* __restrict__ pop_next, double* __restrict__ energy_next,
+                                                    const double* __restrict__ lo, const double* __restrict__ hi, DeTable tab, double CR,
+                                                    unsigned gen, double* __restrict__ work) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ double trial[SBO_MAX_D + 2];
+  const int i = blockIdx.x, o = blockIdx.y, D = d + 2;
+  if (!tab.active[o]) return;
+  const size_t po = (size_t)o * P;
+  de_member(n, d, X, yT + (size_t)o * n, P, i, pop + po * D, energy + po, pop_next + po * D, energy_next + po, lo, hi, tab.F[o], CR,
+            tab.seed[o], gen, work + (po + i) * n * n, reinterpret_cast<double*>(smem), trial);
+}
+
+// The best member of every output's final population (lowest energy, lowest index on ties), read from the buffer that output
+// stopped in (bit o of `parity`): best_x[q][d + 2], best_e[q].
+__global__ void k_de_best(int q, int P, int D, const double* __restrict__ pop0, const double* __restrict__ pop1,
+                          const double* __restrict__ en0, const double* __restrict__ en1, unsigned parity, double* __restrict__ best_x,
+                          double* __restrict__ best_e) {
+  const int o = blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= q) return;
+  const double* pop = ((parity >> o) & 1u ? pop1 : pop0) + (size_t)o * P * D;
+  const double* en = ((parity >> o) & 1u ? en1 : en0) + (size_t)o * P;
+  int best = 0;
+  for (int p = 1; p < P; ++p)
+    if (en[p] < en[best]) best = p;
+  for (int a = 0; a < D; ++a) best_x[(size_t)o * D + a] = pop[(size_t)best * D + a];
+  best_e[o] = en[best];
+}
+
+// What the model is built from: the polished point of output o where its NLL is strictly lower than the DE's best, the DE's best
+// otherwise (always, without a polish: loc_f == nullptr).
+__global__ void k_fit_pick(int q, int D, const double* __restrict__ de_x, const double* __restrict__ de_e, const double* __restrict__ loc_x,
+                           const double* __restrict__ loc_f, double* __restrict__ x_out, double* __restrict__ f_out,
+                           int* __restrict__ polished) {
+  const int o = blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= q) return;
+  const bool take = loc_f && loc_f[o] < de_e[o];
+  for (int a = 0; a < D; ++a) x_out[(size_t)o * D + a] = take ? loc_x[(size_t)o * D + a] : de_x[(size_t)o * D + a];
+  f_out[o] = take ? loc_f[o] : de_e[o];
+  polished[o] = take ? 1 : 0;
 }
 
 }  // namespace sbo
@@ -508,8 +583,9 @@ __device__ __noinline__ bool fit_advance(FitState& S, int D, double ft, const do
   return fit_new_iteration(S, D, trial, maxiter, gtol);
 }
 
+// starts: [P][d + 2] shared by the outputs (starts_per_output == 0) or [q][P][d + 2] (starts_per_output == P).
 __global__ __launch_bounds__(1024) void k_fit_local(int n, int d, int P, const double* __restrict__ X, const double* __restrict__ yT,
-                                                    const double* __restrict__ starts, const double* __restrict__ lo,
+                                                    const double* __restrict__ starts, int starts_per_output, const double* __restrict__ lo,
                                                     const double* __restrict__ hi, int maxiter, double ftol, double gtol,
                                                     double* __restrict__ work, double* __restrict__ h_out, double* __restrict__ f_out,
                                                     double* __restrict__ pg_out, int* __restrict__ it_out, int* __restrict__ ev_out,
@@ -523,7 +599,7 @@ __global__ __launch_bounds__(1024) void k_fit_local(int n, int d, int P, const d
     for (int a = 0; a < D; ++a) {
       S.lo[a] = lo[a];
       S.hi[a] = hi[a];
-      trial[a] = clip_to(starts[(size_t)s * D + a], lo[a], hi[a]);   // SLSQP clips x0 into the bounds
+      trial[a] = clip_to(starts[((size_t)o * starts_per_output + s) * D + a], lo[a], hi[a]);   // SLSQP clips x0 into the bounds
     }
     fit_reset_h(S, D);
     S.phase = FIT_PH_START;
@@ -622,7 +698,7 @@ extern "C" int sbo_fit_local(sbo_ctx* c, int n, int d, int q, const double* X_no
   SBO_HIP(hipMemcpyAsync(dhi, hi, sizeof(double) * D, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fit_local), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(k_fit_local, dim3((unsigned)M), dim3(n >= 96 ? 1024 : 256), lds, c->stream, n, d, P, (const double*)dX,
-                     (const double*)dy, (const double*)dst, (const double*)dlo, (const double*)dhi, maxiter, ftol, gtol,
+                     (const double*)dy, (const double*)dst, 0, (const double*)dlo, (const double*)dhi, maxiter, ftol, gtol,
                      (double*)c->fitwork.p, dh, df, dpg, dit, dev, dstat);
   SBO_HIP(hipGetLastError());
   std::vector<double> hh(M * D), hf(M), hpg(M);
@@ -645,5 +721,169 @@ extern "C" int sbo_fit_local(sbo_ctx* c, int n, int d, int q, const double* X_no
   if (iters_out) std::copy(hit.begin(), hit.begin() + M, iters_out);
   if (evals_out) std::copy(hit.begin() + M, hit.begin() + 2 * M, evals_out);
   if (status_out) std::copy(hit.begin() + 2 * M, hit.end(), status_out);
+  return SBO_OK;
+}
+
+// ---- all outputs side by side: batched DE, per-output polish --------------------------------------------
+// The device side of sbo_fit_de_batch and sbo_model_fit.  The DE of output o is sbo_fit_de's for column o with seeds[o], launch for
+// launch: the same nll_member on the same workgroup size, the same draws, the same F sequence and the same convergence test on
+// the same cadence, so the result is the same bits.  One read-back of the q P energies per check is the only host wait of the
+// search.  The polish (polish != 0) is one k_fit_local launch with one start per output, the DE's best as k_de_best left it in
+// device memory; k_fit_pick keeps it where it is strictly lower.  One more read-back returns everything.
+namespace sbo {
+
+int fit_batch(sbo_ctx* c, int n, int d, int q, const double* X_norm, const double* Y_norm, int P, const double* lo, const double* hi,
+              const double* init_pop, const uint64_t* seeds, int maxiter, double tol, double atol, int polish, int polish_maxiter,
+              double ftol, double gtol, FitBatchResult& out) {
+  using clk = std::chrono::steady_clock;
+  const auto t0 = clk::now();
+  SBO_HIP(hipSetDevice(c->device));
+  const int D = d + 2;
+  const size_t lds = sizeof(double) * ((size_t)n * d + 2 * (size_t)n);
+  const size_t lds_g = nll_grad_lds(n, d);
+  if ((polish ? lds_g : lds) > 150 * 1024) return fail(SBO_E_UNSUPPORTED, "n * d too large for the fit kernel's LDS staging");
+  const size_t M = (size_t)q * P;
+  int rc;
+  // X | yT | pop[2] | energy[2] | lo | hi | final x, nll, DE best x, nll (read back as one block) | polish x, f, pgnorm |
+  // polish iters, evals, status, polished (ints)
+  const size_t res_elems = 2 * ((size_t)q * D + q);
+  const size_t in_elems = (size_t)n * d + (size_t)q * n + 2 * M * D + 2 * M + 2 * (size_t)D + res_elems + (size_t)q * D + 2 * (size_t)q + 2 * (size_t)q;
+  if ((rc = ensure(c->fitbuf, sizeof(double) * in_elems))) return rc;
+  if ((rc = ensure(c->fitwork, sizeof(double) * M * n * n))) return rc;
+  std::vector<double> yT((size_t)q * n);               // one contiguous column per output
+  for (int i = 0; i < n; ++i)
+    for (int o = 0; o < q; ++o) yT[(size_t)o * n + i] = Y_norm[(size_t)i * q + o];
+  double* dX = (double*)c->fitbuf.p;
+  double* dy = dX + (size_t)n * d;
+  double* dpop[2] = {dy + (size_t)q * n, dy + (size_t)q * n + M * D};
+  double* den[2] = {dpop[1] + M * D, dpop[1] + M * D + M};
+  double* dlo = den[1] + M;
+  double* dhi = dlo + D;
+  double* dfin_x = dhi + D;
+  double* dfin_f = dfin_x + (size_t)q * D;
+  double* dde_x = dfin_f + q;
+  double* dde_f = dde_x + (size_t)q * D;
+  double* dloc_x = dde_f + q;
+  double* dloc_f = dloc_x + (size_t)q * D;
+  double* dloc_pg = dloc_f + q;
+  int* dit = reinterpret_cast<int*>(dloc_pg + q);
+  int* dev = dit + q;
+  int* dstat = dev + q;
+  int* dpolished = dstat + q;
+  SBO_HIP(hipMemcpyAsync(dX, X_norm, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemcpyAsync(dy, yT.data(), sizeof(double) * (size_t)q * n, hipMemcpyHostToDevice, c->stream));
+  for (int o = 0; o < q; ++o)                          // every output starts from the caller's population
+    SBO_HIP(hipMemcpyAsync(dpop[0] + (size_t)o * P * D, init_pop, sizeof(double) * (size_t)P * D, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemcpyAsync(dlo, lo, sizeof(double) * D, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemcpyAsync(dhi, hi, sizeof(double) * D, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_nll_batch_q), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_de_step_q), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const int threads = n >= 96 ? 1024 : 256;
+  const dim3 grid(P, q);
+  hipLaunchKernelGGL(k_nll_batch_q, grid, dim3(threads), lds, c->stream, n, d, P, (const double*)dX, (const double*)dy,
+                     (const double*)dpop[0], (double*)c->fitwork.p, den[0]);
+  std::vector<double> he(M);
+  DeTable tab;
+  unsigned long long fstate[SBO_MAX_Q];
+  int n_active = 0;
+  unsigned parity = 0;                                 // bit o: the buffer output o's final population is in
+  out.host_syncs = 0;
+  for (int o = 0; o < SBO_MAX_Q; ++o) {
+    tab.F[o] = 0.0;
+    tab.seed[o] = o < q ? seeds[o] : 0;
+    tab.active[o] = o < q && maxiter > 0;
+    fstate[o] = mix64_host(tab.seed[o]);
+    if (o < q) out.generations[o] = maxiter > 0 ? maxiter : 0;
+    n_active += tab.active[o];
+  }
+  int cur = 0;
+  for (int gen = 0; gen < maxiter && n_active; ++gen) {
+    for (int o = 0; o < q; ++o) {
+      if (!tab.active[o]) continue;
+      fstate[o] = mix64_host(fstate[o]);
+      tab.F[o] = 0.5 + 0.5 * ((double)(fstate[o] >> 11) * (1.0 / 9007199254740992.0));
+    }
+    hipLaunchKernelGGL(k_de_step_q, grid, dim3(threads), lds, c->stream, n, d, (const double*)dX, (const double*)dy, P,
+                       (const double*)dpop[cur], (const double*)den[cur], dpop[cur ^ 1], den[cur ^ 1], (const double*)dlo,
+                       (const double*)dhi, tab, 0.7, (unsigned)gen, (double*)c->fitwork.p);
+    cur ^= 1;
+    for (int o = 0; o < q; ++o)
+      if (tab.active[o]) parity = (parity & ~(1u << o)) | ((unsigned)cur << o);
+    if ((gen & 7) == 7 || gen + 1 == maxiter) {
+      SBO_HIP(hipMemcpyAsync(he.data(), den[cur], sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
+      SBO_HIP(hipStreamSynchronize(c->stream));
+      ++out.host_syncs;
+      for (int o = 0; o < q; ++o) {
+        if (!tab.active[o]) continue;
+        const double* e = he.data() + (size_t)o * P;
+        double mean = 0, var = 0;
+        bool finite = true;
+        for (int p = 0; p < P; ++p) { mean += e[p]; finite = finite && std::isfinite(e[p]); }
+        mean /= P;
+        for (int p = 0; p < P; ++p) var += (e[p] - mean) * (e[p] - mean);
+        if (finite && std::sqrt(var / P) <= atol + tol * std::fabs(mean)) {
+          tab.active[o] = 0;
+          --n_active;
+          out.generations[o] = gen + 1;
+        }
+      }
+    }
+  }
+  SBO_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_de_best, dim3(1), dim3(64), 0, c->stream, q, P, D, (const double*)dpop[0], (const double*)dpop[1],
+                     (const double*)den[0], (const double*)den[1], parity, dde_x, dde_f);
+  const auto t1 = clk::now();                          // (the search's last check has drained the stream)
+  if (polish) {
+    SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fit_local), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g));
+    hipLaunchKernelGGL(k_fit_local, dim3(q), dim3(threads), lds_g, c->stream, n, d, 1, (const double*)dX, (const double*)dy,
+                       (const double*)dde_x, 1, (const double*)dlo, (const double*)dhi, polish_maxiter, ftol, gtol,
+                       (double*)c->fitwork.p, dloc_x, dloc_f, dloc_pg, dit, dev, dstat);
+  }
+  hipLaunchKernelGGL(k_fit_pick, dim3(1), dim3(64), 0, c->stream, q, D, (const double*)dde_x, (const double*)dde_f,
+                     (const double*)dloc_x, polish ? (const double*)dloc_f : (const double*)nullptr, dfin_x, dfin_f, dpolished);
+  SBO_HIP(hipGetLastError());
+  std::vector<double> hres(res_elems);
+  std::vector<int> hint(4 * (size_t)q);
+  SBO_HIP(hipMemcpyAsync(hres.data(), dfin_x, sizeof(double) * res_elems, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipMemcpyAsync(hint.data(), dit, sizeof(int) * 4 * (size_t)q, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipStreamSynchronize(c->stream));
+  ++out.host_syncs;
+  const double* hfin_f = hres.data() + (size_t)q * D;
+  const double* hde_x = hfin_f + q;
+  const double* hde_f = hde_x + (size_t)q * D;
+  for (int o = 0; o < q; ++o) {
+    for (int a = 0; a < D; ++a) {
+      out.x[o][a] = hres[(size_t)o * D + a];
+      out.de_x[o][a] = hde_x[(size_t)o * D + a];
+    }
+    out.nll[o] = hfin_f[o];
+    out.de_nll[o] = hde_f[o];
+    out.polish_evals[o] = polish ? hint[(size_t)q + o] : 0;
+    out.polish_status[o] = polish ? hint[2 * (size_t)q + o] : -1;
+    out.polished[o] = hint[3 * (size_t)q + o];
+  }
+  const auto t2 = clk::now();
+  out.de_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+  out.polish_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+  return SBO_OK;
+}
+
+}  // namespace sbo
+
+extern "C" int sbo_fit_de_batch(sbo_ctx* c, int n, int d, int q, const double* X_norm, const double* Y_norm, int P, const double* lo,
+                                const double* hi, const double* init_pop, const uint64_t* seeds, int maxiter, double tol, double atol,
+                                double* best_x, double* best_energy, int* generations) {
+  if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
+  if (n < 1 || n > SBO_MAX_N || d < 1 || d > SBO_MAX_D || q < 1 || q > SBO_MAX_Q || P < 4 || maxiter < 0)
+    return fail(SBO_E_INVALID, "n, d, q, P or maxiter out of range");
+  if (!X_norm || !Y_norm || !lo || !hi || !init_pop || !seeds || !best_x || !best_energy) return fail(SBO_E_INVALID, "NULL argument");
+  FitBatchResult r;
+  const int rc = fit_batch(c, n, d, q, X_norm, Y_norm, P, lo, hi, init_pop, seeds, maxiter, tol, atol, 0, 0, 0.0, 0.0, r);
+  if (rc) return rc;
+  for (int o = 0; o < q; ++o) {
+    for (int a = 0; a < d + 2; ++a) best_x[(size_t)o * (d + 2) + a] = r.de_x[o][a];
+    best_energy[o] = r.de_nll[o];
+    if (generations) generations[o] = r.generations[o];
+  }
   return SBO_OK;
 }

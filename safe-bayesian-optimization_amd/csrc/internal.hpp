@@ -436,6 +436,17 @@ int launch_posterior(sbo_ctx* c, const PostRequest& req, PostOutcome& out);
 int launch_bound(sbo_ctx* c, double b, int index, int kind, void* dev_out);
 int model_build(sbo_ctx* c, const double* const* host_invK, const double* X_norm, const double* Y_norm);
 int model_prep(sbo_ctx* c, const double* X_norm);
+// fit.hip: the DE of every output side by side and, with polish != 0, a projected BFGS from every output's DE best; x / nll are
+// what a model is built from (the polished point where it is strictly lower).  Arguments are the caller's to check.
+struct FitBatchResult {
+  double x[kMaxQ][kMaxD + 2], de_x[kMaxQ][kMaxD + 2], nll[kMaxQ], de_nll[kMaxQ];
+  int generations[kMaxQ], polish_status[kMaxQ], polish_evals[kMaxQ], polished[kMaxQ];
+  int host_syncs;                 // read-backs the host waited for: one per convergence check and the final one
+  double de_ms, polish_ms;        // host clock: upload + search up to its last check | polish + result read-back
+};
+int fit_batch(sbo_ctx* c, int n, int d, int q, const double* X_norm, const double* Y_norm, int P, const double* lo, const double* hi,
+              const double* init_pop, const uint64_t* seeds, int maxiter, double tol, double atol, int polish, int polish_maxiter,
+              double ftol, double gtol, FitBatchResult& out);
 int model_factor_enqueue(sbo_ctx* c);
 int model_pack_invk(sbo_ctx* c);         // images of the caller's invK for the K1b tables, when the grid arrived after the model   // the deferred factor chain of a caller's invK, behind everything on the critical path
 int model_append_check(sbo_ctx* c, const std::vector<double>& kvec /*[q][n]*/, const double* kappa, const double* rho);

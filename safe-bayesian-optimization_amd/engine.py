@@ -85,6 +85,8 @@ class SweepEngine:
         K + (sn2 + float32 eps) I itself (Cholesky, contraction with L^-1).  ``mean_prior`` [q] (normalised units) replaces
         GP_Safe's prior mean (0 for the objective, -2 Y_mean / Y_std for the constraints); models/GP_Robust.py uses zeros."""
         self.tag, self.np_dtype = _DTYPES[dtype]
+        if use_invK and getattr(ds.get("invKopt"), "materialised", True) is False:
+            use_invK = False         # a lazy invKopt nobody has read (GP_Safe.LazyInvK): the library factors K itself
         X_norm = _f64(ds["X_norm"])
         Y_norm = _f64(ds["Y_norm"])
         if X_norm.ndim != 2 or Y_norm.ndim != 2 or X_norm.shape[0] != Y_norm.shape[0]:
@@ -120,6 +122,53 @@ class SweepEngine:
         else:
             L.check(self._lib.sbo_model_set(*args, None))
         self.n, self.d, self.q = n, d, q
+
+    def model_fit(self, ds: dict, bounds, init_pop, seed: int = 0, maxiter: int = 1000, tol: float = 0.01, atol: float = 0.0,
+                  polish: bool = True, polish_maxiter: int = 10000, polish_ftol: float = FLOAT32_EPS, polish_gtol: float = 1e-8,
+                  dtype="f64", kernel: str = "RBF", mean_prior=None) -> dict:
+        """Fit and build in one call (``sbo_model_fit``): ``ds`` holds the normalisation and the normalised data (``X_mean``,
+        ``X_std``, ``Y_mean``, ``Y_std``, ``X_norm``, ``Y_norm`` -- no ``hypopt``, no ``invKopt``).  The DE of every output runs side
+        by side on the device (output o with ``seed + o`` from ``init_pop`` [P, d+2] in the box ``bounds`` [d+2, 2]), a projected
+        BFGS polishes every output's best, and the model is built as ``set_model(..., use_invK=False)`` builds it.  Returns
+        ``hypopt`` [d+2, q] and the fields of ``sbo_fit_report`` (per-output arrays cut to q)."""
+        tag, np_dtype = _DTYPES[dtype]
+        X_norm = _f64(ds["X_norm"])
+        Y_norm = _f64(ds["Y_norm"])
+        if X_norm.ndim != 2 or Y_norm.ndim != 2 or X_norm.shape[0] != Y_norm.shape[0]:
+            raise ValueError("X_norm / Y_norm must be [n, d] and [n, q]")
+        n, d = X_norm.shape
+        q, D = Y_norm.shape[1], d + 2
+        arrs = [_f64(ds[k]) for k in ("X_mean", "X_std", "Y_mean", "Y_std")]
+        if arrs[0].shape != (d,) or arrs[1].shape != (d,) or arrs[2].shape != (q,) or arrs[3].shape != (q,):
+            raise ValueError("X_mean/X_std must be [d], Y_mean/Y_std must be [q]")
+        B = _f64(bounds)
+        pop = _f64(init_pop)
+        if d > L.SBO_MAX_D or q > L.SBO_MAX_Q or B.shape != (D, 2) or pop.ndim != 2 or pop.shape[1] != D:
+            raise ValueError("bounds [d+2, 2], init_pop [P, d+2], d <= SBO_MAX_D, q <= SBO_MAX_Q")
+        mp = None
+        if mean_prior is not None:
+            mp = _f64(mean_prior).reshape(-1)
+            if mp.shape != (q,):
+                raise ValueError("mean_prior must be [q]")
+        opts = L.FitOpts(P=pop.shape[0], maxiter=int(maxiter), tol=float(tol), atol=float(atol), seed=int(seed) & (2 ** 64 - 1),
+                         polish=1 if polish else 0, polish_maxiter=int(polish_maxiter), polish_ftol=float(polish_ftol),
+                         polish_gtol=float(polish_gtol))
+        for a in range(D):
+            opts.lo[a], opts.hi[a] = B[a, 0], B[a, 1]
+        hyp = np.empty((D, q), dtype=np.float64)
+        rep = L.FitReport()
+        L.check(self._lib.sbo_model_fit(self._ctx, tag, kernel.encode(), n, d, q, _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]),
+                                        _ptr(arrs[3]), _ptr(X_norm), _ptr(Y_norm), _ptr(mp), C.byref(opts), _ptr(pop), _ptr(hyp),
+                                        C.byref(rep)))
+        self.tag, self.np_dtype = tag, np_dtype
+        self.n, self.d, self.q = n, d, q
+        out = {"hypopt": hyp}
+        for name, _ in L.FitReport._fields_:
+            if name == "reserved":
+                continue
+            v = getattr(rep, name)
+            out[name] = np.array(v[:q]) if hasattr(v, "__len__") else v
+        return out
 
     def append_sample(self, x_norm_new, y_norm_new):
         """One more observation under frozen hyper-parameters and normalisation: O(n^2) on the
@@ -371,6 +420,29 @@ class SweepEngine:
         L.check(self._lib.sbo_fit_de(self._ctx, X.shape[0], X.shape[1], _ptr(X), _ptr(yv), pop.shape[0], _ptr(lo), _ptr(hi), _ptr(pop),
                                      int(seed), int(maxiter), float(tol), float(atol), _ptr(best), C.byref(energy), C.byref(gens)))
         return best, float(energy.value), int(gens.value)
+
+    def fit_de_batch(self, X_norm, Y_norm, bounds, init_pop, seeds, maxiter: int = 1000, tol: float = 0.01, atol: float = 0.0):
+        """``fit_de`` for every column of Y_norm[n, q] side by side (``sbo_fit_de_batch``): one launch per generation for all
+        outputs, output o searched with ``seeds[o]`` from the shared ``init_pop``.  Returns (best_x [q, d+2], energies [q],
+        generations [q]); row o is bit for bit ``fit_de(X_norm, Y_norm[:, o], ..., seed=seeds[o])``."""
+        X = _f64(X_norm)
+        Y = _f64(Y_norm)
+        if Y.ndim == 1:
+            Y = Y[:, None].copy()
+        B = _f64(bounds)
+        pop = _f64(init_pop)
+        if X.ndim != 2 or Y.ndim != 2 or Y.shape[0] != X.shape[0]:
+            raise ValueError("X_norm [n, d], Y_norm [n, q]")
+        n, d = X.shape
+        q, D = Y.shape[1], d + 2
+        sd = np.ascontiguousarray(np.array([int(s) & (2 ** 64 - 1) for s in np.atleast_1d(seeds).tolist()], dtype=np.uint64))
+        if B.shape != (D, 2) or pop.ndim != 2 or pop.shape[1] != D or sd.shape != (q,):
+            raise ValueError("bounds [d+2, 2], init_pop [P, d+2], seeds [q]")
+        lo, hi = _f64(B[:, 0]), _f64(B[:, 1])
+        best, energy, gens = np.empty((q, D)), np.empty(q), np.empty(q, dtype=np.int32)
+        L.check(self._lib.sbo_fit_de_batch(self._ctx, n, d, q, _ptr(X), _ptr(Y), pop.shape[0], _ptr(lo), _ptr(hi), _ptr(pop), _ptr(sd),
+                                           int(maxiter), float(tol), float(atol), _ptr(best), _ptr(energy), _ptr(gens)))
+        return best, energy, gens
 
     def nll_grad_batch(self, X_norm, y, hypers):
         """``negative_loglikelihood`` and its analytic gradient (models/GP_Classic.py:219, ``grad(NLL)``) for a population:
