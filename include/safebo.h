@@ -474,7 +474,7 @@ int sbo_profile_get(sbo_ctx* ctx, sbo_profile* out);
  *   "k1_sched"         1: lean-2 sweeps on that path launch the constraint's and the objective's GEMM posterior over lists of the tiles they
  *                      evaluate, built per sweep (tiles left out are written by the lists' kernels); 0: one workgroup per tile (A/B checker)
  *   "col_overlap"      1: on that path the expander chain (distance transform, verdicts) runs on a second stream beside the objective's
- *                      posterior launch; 0: every kernel on the main stream
+ *                      posterior launch and the M part of the minimiser; 0: every kernel on the main stream
  *   "set_fuse"         1: 2-D grids of one rank share launches between independent set-phase kernels; 0: one launch per kernel
  *   "set_lanes"        1: constraints of a one-rank sweep alternate between two streams; 0: one after the other
  *   "exact_lazy"       1: one-constraint sweeps launch the exhaustive recheck only when in-band verdicts were listed; 2: always that late path (test); 0: eager

@@ -369,6 +369,7 @@ int interp_setup(sbo_ctx* c) {
   ip.used = false;
   ip.serial = c->model_serial;
   ip.ops = GemmOps();
+  c->bl.bt_ready = false;    // (this plan lays its tables into bl_P1A / bl_T4f / bl_cheb / bl_BtA: K1b's stage-1 images do not survive it)
   GemmOps& g = ip.ops;
   const ModelConst& mc = c->mc;
   const CandSpec& cs = c->cs;

@@ -1158,7 +1158,15 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
       hipLaunchKernelGGL((k_bstage1<S1>), grid, dim3(256), 0, c->stream, (const double*)c->bl_P1A.p, g.sP1A, (const double*)c->bl_T4f.p,
                          g.sT4f, g.KB1, g.nrb, g.KB0, g.BtA, g.sBt1, (const int*)g.eff);
   };
-  if (!interp) stage1();
+  // K1b: once per plan -- P1A, T4f and the counts are the plan's, so a resident model swept again would rebuild the same images
+  // (BilinearPlan::bt_ready states who may write them).  K1i: every launch (its images belong to a model's single first sweep, and
+  // they take the place of K1b's in bl_BtA).
+  const bool run_stage1 = interp || !c->bl.bt_ready;
+  if (interp) c->bl.bt_ready = false;
+  if (!interp && run_stage1) {
+    stage1();
+    c->bl.bt_ready = true;
+  }
   // stage 2 (fused): variance, mean, Lipschitz keys.  64 x 128 tiles (k_bpost<1>, three workgroups per CU): with the Chebyshev
   // core the variance phase is ~12 k-steps and no longer dominates, and the third workgroup per CU is worth more than the
   // B-fragment reuse of a 128 x 128 tile (r03: config B 0.204 -> 0.189 ms per sweep, H 0.547 -> 0.543)
@@ -1302,9 +1310,10 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
     // run to stay on the device -- a read-back per plan is a launch the host-bound plan does not need)
     c->last_k1_flops = (double)q * 2.0 * 1024.0 * 4.0 * (4.0 * (double)g.nrb * g.KB0 * g.KB0 + tiles2 * g.KB0 * 4);
   } else {
-    // flops issued on the matrix cores: stage 1 + the four phases of stage 2 (KS0 + 3 KSm k-steps: the axis-0 gradient phase
+    const double s1 = run_stage1 ? 1.0 : 0.0;
+    // flops issued on the matrix cores: stage 1 (when this launch ran it) + the four phases of stage 2 (KS0 + 3 KSm k-steps: the axis-0 gradient phase
     // runs on the mean phase's sums; 16 x 16 x 4 steps, 2 flops per multiply-add)
-    c->last_k1_flops = (double)q * 2.0 * 1024.0 * (4.0 * (double)g.nrb * g.KB0 * g.KB1 + tiles2 * (g.KS0 + 3 * g.KSm));
+    c->last_k1_flops = (double)q * 2.0 * 1024.0 * (s1 * 4.0 * (double)g.nrb * g.KB0 * g.KB1 + tiles2 * (g.KS0 + 3 * g.KSm));
     // Chebyshev core: the counts the kernels actually run to (k_cheb_trunc; copied to the pinned block when the plan was built --
     // they have arrived long before a sweep's result is read: a plan build is followed by the sweep's own synchronisation
     // before anyone asks for the profile).  Until then the upper bound above stands.
@@ -1315,7 +1324,7 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
       const int ks = he[4 * o], kb0 = he[4 * o + 1], kb1 = he[4 * o + 2];
       if (ks < 1 || ks > g.KS0 || kb0 < 1 || kb0 > g.KB0 || kb1 < 1 || kb1 > g.KB1) { ok = false; break; }
       // (the gradient phases run on the few tiles that can hold the maximum: not counted)
-      f += 2.0 * 1024.0 * (4.0 * (double)g.nrb * kb0 * kb1 + tiles2 * (ks + (g.gtmax ? 1 : 3) * g.KSm));
+      f += 2.0 * 1024.0 * (s1 * 4.0 * (double)g.nrb * kb0 * kb1 + tiles2 * (ks + (g.gtmax ? 1 : 3) * g.KSm));
     }
     if (ok) c->last_k1_flops = f;
   }

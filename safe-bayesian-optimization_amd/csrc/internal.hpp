@@ -130,6 +130,12 @@ struct BilinearPlan {
   double setup_ms = 0.0;
   GemmOps ops;           // (eff: per-output counts; band_ready: guard.hip, guard_band_bilinear)
   bool encl_ready = false;   // bl_encl holds the enclosures of the constraint's mean / var per 8 x 8 cell (k_bl_enclose, r06)
+  // bl_BtA holds stage 1's images of THIS plan (k_bstage1 has been enqueued on its operands): launch_posterior_gemm runs stage 1 for
+  // the plan's first launch only.  INVARIANT: stage 1 reads bl_P1A, bl_T4f and the counts `ops.eff` (in bl_cheb) and writes bl_BtA;
+  // all four are written by the two plan builders and by nothing else -- bilinear_setup (k_cheb_tab<0>, k_cheb_t4f, k_cheb_trunc)
+  // and interp_setup, which lays K1i's own tables into the same buffers -- and only those two resize them.  Both clear the flag, and
+  // so does a K1i launch (its stage 1 overwrites bl_BtA).  Whoever adds a writer of one of the four must clear it as well.
+  bool bt_ready = false;
 };
 
 // What one posterior launch is asked to do (posterior_enqueue).  A default request is a plain posterior run: every value and
@@ -346,7 +352,8 @@ struct sbo_ctx {
   sbo::DevBuf col_cimg, col_cbmin;           // the same on the 8 x 8 cells
   long long col_ckey = 0;                    // the grid the padding of col_cbmin was laid out for
   sbo::DevBuf col_fin;                       // the objective's scalars, the finals' tickets and intermediate rows (4 KB)
-  hipEvent_t ev_col[2]{};      // fork (the constraint's posterior launch has finished) / join (the expander chain on stream3 has)
+  hipEvent_t ev_col[3]{};      // fork (the constraint's posterior launch has finished) / join (the expander chain on stream3 has) /
+                               // the chain's first kernel, which clears the M words, has finished (carried by k_col_a: the minimiser's M part waits for it)
   hipEvent_t ev_grad[4]{};     // K1i's deferred tail: fork (plan: the series are in place) / stage 1 has run / the keys are merged / the band is written
   bool grad_pending = false;   // a deferred gradient launch is in flight on stream3: whoever reads the Lipschitz partials elsewhere waits for ev_grad[2]
   int grad_defer = 1;          // option: 0 = the gate stays in front of the posterior launch (r04)

@@ -383,9 +383,15 @@ typedef double d2c_t __attribute__((ext_vector_type(2)));
 typedef unsigned long long u2c_t __attribute__((ext_vector_type(2)));
 
 // ---- minimiser: M = {g in S : lcb_0 <= u*} (models/SafeOpt.py:62), arg-max var_0 over M, |M|; and, from the finished G words,
-// |G_1| and arg-max var_0 over G_1 (G_1 is a subset of S: its var_0 is already in registers) ------------------------------------------
+// |G_1| and arg-max var_0 over G_1 ----------------------------------------------------------------------------------------------------
 // lcb_0 against u* is decided from the single-precision bounds where they settle it -- the exact bound (IEEE square root) only inside
 // their margin.
+// Two launches of one body over the same units.  The M part (PART 0) needs the objective's posterior launch only -- u*, the variance
+// key, the row masks and olmin are complete behind k_bpost<1, 2> -- and the M words cleared by k_col_a: it runs on the main stream
+// while the expander chain is still at work on stream3.  It reads nothing the chain writes (SweepScalars, Lmax, the G words: its
+// scalars go to ColScal2), and of the slot block only fields the objective's launch completed.  The G part (PART 1) reads the finished
+// G words, so it follows the join: |G_1|, the arg-max of var_0 over G_1 (var_0 of the rows with a G bit alone), and the objective's
+// Lipschitz key out of the slot block (K1i's deferred gradient launch merges into kSlotL0 on stream3: complete behind the join only).
 struct ColMinJob {
   ColGeom gm;
   const unsigned long long* slots;
@@ -402,6 +408,7 @@ struct ColMinJob {
   Best* gpartial;           // rows of the arg-max over G_1
   const GuardBand* gb;
 };
+template <int PART>
 __global__ __launch_bounds__(256) void k_col_min(const ColMinJob j) {
   unsigned long long ukey, vkey;
   col_merge2_body(j.slots, ukey, vkey);
@@ -414,8 +421,11 @@ __global__ __launch_bounds__(256) void k_col_min(const ColMinJob j) {
     du0 = j.gb->dm[0] + (any ? j.b * gb_dsqrt(vm, j.gb->dv[0]) : 0.0);
   }
   if (blockIdx.x == 0 && threadIdx.x < 64) {
-    const unsigned long long l0 = col_slot_reduce(j.slots, kSlotL0);
-    if (threadIdx.x == 0) { j.Lmax[0] = l0; j.sc2->ustar_key = ukey; j.sc2->vmin0_key = vkey; j.sc2->gb_du0 = du0; }
+    const unsigned long long l0 = PART == 1 ? col_slot_reduce(j.slots, kSlotL0) : 0ull;
+    if (threadIdx.x == 0) {
+      if (PART == 0) { j.sc2->ustar_key = ukey; j.sc2->vmin0_key = vkey; j.sc2->gb_du0 = du0; }
+      else j.Lmax[0] = l0;
+    }
   }
   const ColGeom& gm = j.gm;
   const double ustar = ord_val(ukey), b = j.b;
@@ -434,15 +444,17 @@ __global__ __launch_bounds__(256) void k_col_min(const ColMinJob j) {
   uint8_t* Mb = reinterpret_cast<uint8_t*>(j.Mw);
   for (long long u = wave; u < nunits && anyS; u += nwaves) {
     const ColUnit x = col_unit(gm, um, u, lane);
-    const u2c_t sw = *reinterpret_cast<const u2c_t*>(j.Sw + x.w0), gw = *reinterpret_cast<const u2c_t*>(j.Gw + x.w0);
+    // (each part loads the words it decides from: S for M, G for G_1 -- a subset of S)
+    const u2c_t sw = PART == 0 ? *reinterpret_cast<const u2c_t*>(j.Sw + x.w0) : u2c_t{0ull, 0ull};
+    const u2c_t gw = PART == 1 ? *reinterpret_cast<const u2c_t*>(j.Gw + x.w0) : u2c_t{0ull, 0ull};
     const unsigned int sb[2] = {(unsigned int)(sw[0] >> (8 * x.oct)) & 0xffu, (unsigned int)(sw[1] >> (8 * x.oct)) & 0xffu};
     const unsigned int gbt[2] = {(unsigned int)(gw[0] >> (8 * x.oct)) & 0xffu, (unsigned int)(gw[1] >> (8 * x.oct)) & 0xffu};
     unsigned int mb[2] = {0u, 0u}, und[2] = {0u, 0u};
     // The tile's range first: lcb_0 >= lmin on all of its safe candidates, so a tile with lmin > u* (+ the guard's margin) holds no
     // member of M and nothing near it -- M is a thin set (80 of the 515 tiles with a safe candidate on config H) --, and such a
-    // tile only takes part through its members of G_1: var_0 of those rows alone.
-    const unsigned long long lk = j.olmin[x.tile];
-    const bool mposs = lk != ~0ull && !(ord_val(lk) > ustar + mg);
+    // tile only takes part through its members of G_1: var_0 of those rows alone (the G part, which takes every tile that way).
+    const unsigned long long lk = PART == 0 ? j.olmin[x.tile] : ~0ull;
+    const bool mposs = PART == 0 && lk != ~0ull && !(ord_val(lk) > ustar + mg);
     const unsigned int any8 = mposs ? (sb[0] | sb[1]) : (gbt[0] | gbt[1]);
     if (__ballot(any8 != 0u) != 0ull) {
       d2c_t mu[8], va[8];
@@ -458,24 +470,27 @@ __global__ __launch_bounds__(256) void k_col_min(const ColMinJob j) {
       for (int k = 0; k < 8; ++k) {
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-          const bool on = mposs && ((sb[e] >> k) & 1u);
           const double v = va[k][e];
-          const F32Bound fb = f32_bound(mu[k][e], v, bf);                 // lcb_0 within fb.del of fb.u
-          const bool sureM = fb.ok && fb.u + fb.del < ulo_f, sureN = fb.ok && fb.u - fb.del > uhi_f;
-          const bool mm = on && sureM;
-          und[e] |= (on && !sureM && !sureN) ? (1u << k) : 0u;
-          mb[e] |= mm ? (1u << k) : 0u;
           const unsigned int g = g32 + (unsigned int)(k * gm.W + e);
-          if (__ballot(mm) != 0ull) {                                    // (M is a thin set: most steps have no member in the wave)
-            cM += mm;
-            if (e2on) take_max<true>(mm, v, g, bvM, bgM, e2M);
-            else take_max<false>(mm, v, g, bvM, bgM, e2M);
-          }
-          const bool gg = (gbt[e] >> k) & 1u;
-          if (__ballot(gg) != 0ull) {
-            cG += gg;
-            if (e2on) take_max<true>(gg, v, g, bvG, bgG, e2G);
-            else take_max<false>(gg, v, g, bvG, bgG, e2G);
+          if (PART == 0) {
+            const bool on = mposs && ((sb[e] >> k) & 1u);
+            const F32Bound fb = f32_bound(mu[k][e], v, bf);               // lcb_0 within fb.del of fb.u
+            const bool sureM = fb.ok && fb.u + fb.del < ulo_f, sureN = fb.ok && fb.u - fb.del > uhi_f;
+            const bool mm = on && sureM;
+            und[e] |= (on && !sureM && !sureN) ? (1u << k) : 0u;
+            mb[e] |= mm ? (1u << k) : 0u;
+            if (__ballot(mm) != 0ull) {                                  // (M is a thin set: most steps have no member in the wave)
+              cM += mm;
+              if (e2on) take_max<true>(mm, v, g, bvM, bgM, e2M);
+              else take_max<false>(mm, v, g, bvM, bgM, e2M);
+            }
+          } else {
+            const bool gg = (gbt[e] >> k) & 1u;
+            if (__ballot(gg) != 0ull) {
+              cG += gg;
+              if (e2on) take_max<true>(gg, v, g, bvG, bgG, e2G);
+              else take_max<false>(gg, v, g, bvG, bgG, e2G);
+            }
           }
         }
       }
@@ -501,25 +516,30 @@ __global__ __launch_bounds__(256) void k_col_min(const ColMinJob j) {
         else take_max<false>(mm, v, (unsigned int)g, bvM, bgM, e2M);
       }
     }
-    Mb[8 * x.w0 + x.oct] = (uint8_t)mb[0];
-    Mb[8 * (x.w0 + 1) + x.oct] = (uint8_t)mb[1];
+    if (PART == 0) {
+      Mb[8 * x.w0 + x.oct] = (uint8_t)mb[0];
+      Mb[8 * (x.w0 + 1) + x.oct] = (uint8_t)mb[1];
+    }
   }
-  Best best = best_from(bvM, bgM, e2M), bestG = best_from(bvG, bgG, e2G);
-  best = block_best_uni<true>(best, dv0);
-  cM = block_sum_ll(cM);
-  cB = block_sum_ll(cB);
-  if (threadIdx.x == 0) {
-    j.partial[blockIdx.x] = best;
-    ((long long*)(j.partial + gridDim.x))[blockIdx.x] = cM;
-    ((long long*)(j.partial + gridDim.x))[gridDim.x + blockIdx.x] = cB;
-  }
-  __syncthreads();
-  bestG = block_best_uni<true>(bestG, dv0);
-  cG = block_sum_ll(cG);
-  if (threadIdx.x == 0) {
-    j.gpartial[blockIdx.x] = bestG;
-    ((long long*)(j.gpartial + gridDim.x))[blockIdx.x] = cG;
-    ((long long*)(j.gpartial + gridDim.x))[gridDim.x + blockIdx.x] = 0;
+  if (PART == 0) {
+    Best best = best_from(bvM, bgM, e2M);
+    best = block_best_uni<true>(best, dv0);
+    cM = block_sum_ll(cM);
+    cB = block_sum_ll(cB);
+    if (threadIdx.x == 0) {
+      j.partial[blockIdx.x] = best;
+      ((long long*)(j.partial + gridDim.x))[blockIdx.x] = cM;
+      ((long long*)(j.partial + gridDim.x))[gridDim.x + blockIdx.x] = cB;
+    }
+  } else {
+    Best bestG = best_from(bvG, bgG, e2G);
+    bestG = block_best_uni<true>(bestG, dv0);
+    cG = block_sum_ll(cG);
+    if (threadIdx.x == 0) {
+      j.gpartial[blockIdx.x] = bestG;
+      ((long long*)(j.gpartial + gridDim.x))[blockIdx.x] = cG;
+      ((long long*)(j.gpartial + gridDim.x))[gridDim.x + blockIdx.x] = 0;
+    }
   }
 }
 
@@ -1001,8 +1021,9 @@ static void col_expand(sbo_ctx* c, const DevBuf& words, uint8_t* out) {
 // and Lipschitz keys of the constraint --, so it runs on the high-priority stream3 behind the constraint's k_bpost launch (fork event
 // carried by that launch) WHILE the objective's k_bpost launch runs on the main stream: k_col_a, k_col_cs, k_col_decide, k_col_scan are
 // latency-bound kernels whose waiting the matrix kernel fills.  The OBJECTIVE chain follows its own launch on the main stream: u*
-// merged by every workgroup of k_col_min, M and its arg-max; the main stream then waits for the chain's join event and k_col_finals
-// merges both.  What the set phase adds to K1 is the minimiser, the join and the finals.
+// merged by every workgroup of k_col_min<0>, M and its arg-max, beside the chain's verdict kernels; the main stream then waits for the
+// chain's join event, k_col_min<1> takes the arg-max over the finished G_1 and k_col_finals merges both.  What the set phase adds to
+// K1 is the join, the G part and the finals.
 static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const PostOutcome& post, SweepScalars& h, unsigned long long* Lk) {
   const long long n = c->cs.n_local;
   const int q = c->mc.q;                 // == 2
@@ -1078,9 +1099,31 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const PostOutcome&
   mg.b = o->b;
   const int ncoarse = gm.CNB;
   const int nfine = (int)std::max<long long>(1, std::min<long long>(((long long)gm.NS * (gm.W / 64) + 3) / 4, (long long)c->n_cu * 5));
-  hipLaunchKernelGGL(k_col_a, dim3((unsigned)(1 + ncoarse + nfine)), dim3(256), 0, es, gm, cb, mg, ncoarse, (unsigned short*)c->col_cimg.p,
-                     (unsigned short*)c->col_cbmin.p, (unsigned short*)c->col_img.p, (unsigned short*)c->col_bmin.p, (unsigned long long*)c->cbM.p, (unsigned long long*)c->cbG.p);
+  // (overlapped: the launch carries ev_col[2] as its stop event -- it clears the M words the minimiser's M part fills on the main stream)
+  hipExtLaunchKernelGGL(k_col_a, dim3((unsigned)(1 + ncoarse + nfine)), dim3(256), 0, es, nullptr, overlap ? c->ev_col[2] : nullptr, 0, gm, cb, mg, ncoarse,
+                        (unsigned short*)c->col_cimg.p, (unsigned short*)c->col_cbmin.p, (unsigned short*)c->col_img.p, (unsigned short*)c->col_bmin.p,
+                        (unsigned long long*)c->cbM.p, (unsigned long long*)c->cbG.p);
   c->usum_dirty = false;
+  // ---- objective chain, M part: behind the objective's posterior launch on the main stream and behind k_col_a, beside the rest of the
+  // expander chain (one stream: in order between k_col_a and k_col_decide)
+  ColMinJob j;
+  memset(&j, 0, sizeof(j));
+  j.gm = gm;
+  j.slots = cb.slots;
+  j.Lmax = (unsigned long long*)c->Lmax.p;
+  j.sc2 = sc2;
+  j.olmin = (const unsigned long long*)c->cpart.p + (size_t)1 * c->cpart_cap + post.fuse_rows / 2;
+  j.Sw = cb.Sw;
+  j.mean0 = (const double*)c->mean.p;
+  j.var0 = (const double*)c->var.p;
+  j.b = o->b;
+  j.Mw = (unsigned long long*)c->cbM.p;
+  j.Gw = (const unsigned long long*)c->cbG.p;
+  j.partial = reg0;
+  j.gpartial = reg1;
+  j.gb = gb_of(c);
+  if (overlap) SBO_HIP(hipStreamWaitEvent(xs, c->ev_col[2], 0));
+  hipLaunchKernelGGL(k_col_min<0>, dim3((unsigned)nb), dim3(256), 0, xs, j);
   ColVerdict cv;
   memset(&cv, 0, sizeof(cv));
   cv.mean_c = (const double*)c->mean.p + (size_t)n;
@@ -1097,11 +1140,10 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const PostOutcome&
     cv.rx.gb_l = c->gb_slow ? -1 : lidx;
   }
   // (the verdict kernels do not read var_0 -- overlapped, the objective's launch may still be writing it: the arg-max over G_1 is the
-  // second job of k_col_min)
+  // job of k_col_min<1>, behind the join)
   // (grids sized to be resident at once: the waves loop over the units of the tiles with a safe candidate)
   const int ndw = std::max(1, c->n_cu * 4);
   const unsigned long long* rows = (const unsigned long long*)c->cpart.p;        // the posterior's partial rows: constraint tiles, then objective tiles
-  const int ntiles = post.fuse_rows / 2;
   hipLaunchKernelGGL(k_col_decide, dim3((unsigned)ndw), dim3(256), 0, es, gm, (const unsigned long long*)cb.Sw, (const unsigned long long*)cb.slots,
                      rows, rows + (size_t)(kRowRmax + 1) * c->cpart_cap, (const unsigned short*)c->col_cimg.p, (const unsigned short*)c->col_cbmin.p,
                      2.0 * gm.delta + 2.0 * kCoarse * hmax, cb.Usum, (const unsigned short*)c->col_img.p, cv, sc, (unsigned long long*)c->cbG.p, (long long*)ln.scanlist.p);
@@ -1113,25 +1155,9 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const PostOutcome&
     SBO_HIP(hipStreamWaitEvent(xs, c->ev_col[1], 0));
   }
 
-  // ---- objective chain (overlapped: its kernel takes the arg-max over G_1 along, so it follows the join)
-  ColMinJob j;
-  memset(&j, 0, sizeof(j));
-  j.gm = gm;
-  j.slots = cb.slots;
-  j.Lmax = (unsigned long long*)c->Lmax.p;
-  j.sc2 = sc2;
-  j.olmin = rows + (size_t)1 * c->cpart_cap + ntiles;
-  j.Sw = cb.Sw;
-  j.mean0 = (const double*)c->mean.p;
-  j.var0 = (const double*)c->var.p;
-  j.b = o->b;
-  j.Mw = (unsigned long long*)c->cbM.p;
-  j.Gw = (const unsigned long long*)c->cbG.p;
-  j.partial = reg0;
-  j.gpartial = reg1;
-  j.gb = gb_of(c);
+  // ---- objective chain, G part: the arg-max over G_1 reads the chain's G words, so it follows the join
   const int nbg = nb;
-  hipLaunchKernelGGL(k_col_min, dim3((unsigned)nb), dim3(256), 0, xs, j);
+  hipLaunchKernelGGL(k_col_min<1>, dim3((unsigned)nbg), dim3(256), 0, xs, j);
   hipExtLaunchKernelGGL(k_col_finals, dim3(nb > 2048 ? kColFinParts : 1, 2), dim3(256), 0, xs, nullptr, c->ev[4], 0, (const Best*)reg0, nb, (const Best*)reg1,
                         nbg, sc, (const ColScal2*)sc2, fin, tickets, c->h_back, (const unsigned long long*)c->Lmax.p, gb_of(c) ? 1 : 0, cb.slots);
   c->slots_clean = true;
