@@ -239,8 +239,7 @@ struct sbo_ctx {
   // Guard band of the approximating posteriors K1b / K1t (device_common.hpp: GuardBand; guard.hip)
   int guard_band = 1;              // option: 1 count + re-evaluate exactly when the count is non-zero; 0 off; 2 re-evaluate on every sweep (test)
   bool gb_active = false;          // the posterior in mean / var came from an approximating kernel; `gb` holds (or will hold, in stream order) its band
-  bool gb_off = false;             // a recheck's inner sweep on fully refined values: no band
-  bool gb_slow = false;            // the re-evaluation path of the SafeOpt sweep is running (Lipschitz keys exact, lists in use)
+                                   // (a fact about the resident arrays, kept between calls; what a running set phase makes of it: SetView in sets.hip)
   sbo::DevBuf gb;                  // GuardBand of the resident posterior
   long long guard_first = 0;       // decisions the first pass of the running sweep left open
   // Standing audit of the band (r05): behind every K1b / K1i posterior launch of a sweep a rotating sample of the candidates is
@@ -291,7 +290,8 @@ struct sbo_ctx {
   // the fork and after the join, every sweep of a model with one constraint and every sweep on several ranks uses it alone.  With
   // two or more constraints on one rank the chains are independent, so every other constraint goes to lane 1: stream2, its own
   // scratch, and a snapshot of the scalar block that k_classify_final writes (the chains only write its recheck / scan counters;
-  // the finals merge them).  The chain's functions take the lane as a parameter (sets.hip); no field here changes to select one.
+  // the finals merge them).  The chain's functions take the lane as a parameter (sets.hip); no field here changes to select one --
+  // nor to say which posterior arrays, band or refinement lists a set phase works on: a recheck hands those down the same way (SetView).
   struct SetLane {
     hipStream_t stream = nullptr;  // not owned: sbo_ctx::stream (lane 0) / stream2 (lane 1), set where those are created (api.hip)
     sbo::DevBuf dist2, dist2b;     // double [n_local] distance-transform scratch (x2 for ping-pong)
@@ -377,7 +377,6 @@ struct sbo_ctx {
   long long halo_guess[SBO_MAX_Q] = {-1, -1, -1, -1, -1, -1, -1, -1};
   int halo_spec = 1;
   int halo_reruns = 0;            // set phases of the current sweep call discarded for a short window (global decision)
-  bool in_halo_rerun = false;
   bool c1_pending = false;                // the read-back of h_c1 has been enqueued (event ev[5]) but not yet waited for
   void* h_stage = nullptr;                // pinned staging of the K1b table build's single upload
   size_t h_stage_bytes = 0;
@@ -403,10 +402,9 @@ struct sbo_ctx {
   sbo_ctx* shadow = nullptr;
   bool is_shadow = false;
   int fp64_recheck = 1;
-  sbo::DevBuf rc_mean, rc_var;   // double [q][n_local]: the fp32 posterior widened, flagged entries replaced by fp64 values
+  sbo::DevBuf rc_mean, rc_var;   // double [q][n_local]: the fp32 posterior widened, flagged entries replaced by fp64 values (what the recheck's set phases read)
   sbo::DevBuf rc_list;           // flagged candidate indices (long long) + counters (64-byte head)
   sbo::DevBuf rc_refined;        // uint8 [n_local]: this candidate's entries of rc_mean / rc_var are fp64 values
-  bool rc_active = false;        // the running set phase works on a partly refined fp32 posterior (verdicts carry bands)
   // robust sweep (robust.hip): per-control arrays of the last one, the mask of robust-safe controls, the split partials
   sbo::DevBuf rob, rob_mask, rob_part;
   long long rob_nc = 0;
@@ -425,6 +423,12 @@ struct sbo_ctx {
 namespace sbo {
 // the sweeps take their multi-rank path (pack, collective, unpack, host merge): more than one rank, or the self-test
 inline bool multi_rank(const sbo_ctx* c) { return c->world > 1 || c->comm_selftest; }
+// the guard band of the resident posterior of an fp64 model (device_common.hpp: GuardBand), when an approximating kernel (K1b / K1i / K1t)
+// wrote it and option guard_band is on; nullptr: the values are the exact kernels'
+struct GuardBand;
+inline const GuardBand* resident_band(const sbo_ctx* c) {
+  return (c->gb_active && c->guard_band && c->gb.p) ? (const GuardBand*)c->gb.p : nullptr;
+}
 int fail(int code, const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
 int ensure(DevBuf& b, size_t bytes);

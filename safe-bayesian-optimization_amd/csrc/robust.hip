@@ -368,10 +368,6 @@ int robust_phase(sbo_ctx* c, const sbo_sweep_opts* o, int kind, long long nc, co
   return SBO_OK;
 }
 
-inline const GuardBand* robust_gb(const sbo_ctx* c) {   // (as gb_of in sets.hip)
-  return (c->gb_active && !c->gb_off && c->guard_band && c->dtype == SBO_F64 && c->gb.p) ? (const GuardBand*)c->gb.p : nullptr;
-}
-
 int sweep_robust(sbo_ctx* c, const sbo_sweep_opts* o, int nca, int kind, sbo_robust_result* res) {
   const CandSpec& cs = c->cs;
   long long nc = 1, nd = 1;
@@ -388,7 +384,7 @@ int sweep_robust(sbo_ctx* c, const sbo_sweep_opts* o, int nca, int kind, sbo_rob
   if (!reuse && (rc = posterior_enqueue(c, PostRequest{}, &out))) return rc;
   SBO_HIP(k1_stop(c, out));
   if (!reuse && (rc = guard_audit_enqueue(c, out))) return rc;
-  const GuardBand* gb = robust_gb(c);
+  const GuardBand* gb = resident_band(c);      // (fp64 models only: sbo_sweep_robust)
   const int k1_first = c->last_k1;
   PhaseOut P{};
   if ((rc = robust_phase(c, o, kind, nc, gb, P))) return rc;

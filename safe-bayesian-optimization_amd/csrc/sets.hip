@@ -1119,10 +1119,46 @@ static bool whole_planes(const sbo_ctx* c, long long* plane_out = nullptr) {
 
 static bool lanes_on(const sbo_ctx* c) { return c->set_lanes && !multi_rank(c) && c->mc.q >= 3 && c->cs.n_local > 0 && c->stream2; }
 
-// the guard band in force for the running sweep: the posterior in the mean / var buffers came from an approximating kernel
-// (K1b / K1t) -- nullptr for the exact kernels and for fp32 models (whose own recheck covers them)
-static const GuardBand* gb_of(const sbo_ctx* c) {
-  return (c->gb_active && !c->gb_off && c->guard_band && c->dtype == SBO_F64 && c->gb.p) ? (const GuardBand*)c->gb.p : nullptr;
+// ---- what a set phase looks at ---------------------------------------------------------------------------------------------
+// Built by whoever starts the set phase and handed down next to the lane: a plain sweep looks at the resident posterior of the
+// context, a recheck (sets_recheck.inc.hpp) at its refined fp64 values.  No field of sbo_ctx changes to say which.
+struct RcBand {                          // half-widths of the values a recheck has not refined, per output (rc_bands)
+  double dm[kMaxQ], dv[kMaxQ];
+};
+enum class SetBand {
+  plan,        // the band of the resident approximating posterior (resident_band), values and Lipschitz keys alike
+  values,      // ... in force for unrefined values only: the Lipschitz keys have been recomputed exactly (RcExp::gb_l = -1)
+  none         // every value that enters a decision is exact
+};
+struct SetView {
+  // the posterior, SoA [q][n_local] of the sweep's T (the buffers, not their pointers: the sweep's own posterior launch may still size them)
+  const DevBuf* mean;
+  const DevBuf* var;
+  bool given = false;                    // the posterior is in place: no launch, hence no audit and no column path
+  SetBand band = SetBand::plan;
+  // SafeOpt recheck: entries without a `refined` flag carry the band `rc_band`, and a verdict it cannot settle defers its candidate to
+  // `rc_list` (length in *rc_count) instead of deciding it.  refined == nullptr: nothing is deferred
+  const uint8_t* refined = nullptr;
+  const RcBand* rc_band = nullptr;
+  long long* rc_list = nullptr;
+  unsigned long long* rc_count = nullptr;
+  bool halo_rerun = false;               // second pass of a sweep whose speculative halo was short: its record goes on counting
+  explicit SetView(const sbo_ctx* c) : mean(&c->mean), var(&c->var) {}
+  SetView(const DevBuf& m, const DevBuf& v, SetBand bd) : mean(&m), var(&v), given(true), band(bd) {}
+};
+
+// the guard band in force for a set phase in T -- nullptr for the exact kernels, for fp32 sweeps (whose own recheck covers them)
+// and where the view says that no band is left
+template <typename T>
+static const GuardBand* gb_of(const sbo_ctx* c, const SetView& v) {
+  return (std::is_same<T, double>::value && v.band != SetBand::none) ? resident_band(c) : nullptr;
+}
+// ... as the verdict kernels are told: judged against the band of constraint cidx and of the Lipschitz key lidx
+template <typename T>
+static void rx_band(const sbo_ctx* c, const SetView& v, int cidx, int lidx, RcExp& rx) {
+  if (!gb_of<T>(c, v)) return;
+  rx.gb_c = cidx;
+  rx.gb_l = v.band == SetBand::values ? -1 : lidx;
 }
 static void launch_final(sbo_ctx* c, FinalJob* fj) {
   if (!fj || !fj->pending) return;
@@ -1136,7 +1172,7 @@ static void launch_final(sbo_ctx* c, FinalJob* fj) {
 // the classification's partials is handed back instead of launched (SafeOpt on one rank: it rides in the expander's first
 // launch, which reads the U mask only)
 template <typename T>
-static int sweep_common_front(sbo_ctx* c, const sbo_sweep_opts* o, const PostOutcome& post, FinalJob* defer = nullptr) {
+static int sweep_common_front(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, const PostOutcome& post, FinalJob* defer = nullptr) {
   const long long n = c->cs.n_local;
   const int q = c->mc.q;
   int rc;
@@ -1148,7 +1184,7 @@ static int sweep_common_front(sbo_ctx* c, const sbo_sweep_opts* o, const PostOut
   fj.pending = true;
   fj.q = q;
   fj.sc = sc;
-  fj.gb = gb_of(c);
+  fj.gb = gb_of<T>(c, v);
   fj.b = o->b;
   if (lanes_on(c)) {
     if ((rc = ensure(c->lane[1].scal, 4096))) return rc;
@@ -1169,10 +1205,10 @@ static int sweep_common_front(sbo_ctx* c, const sbo_sweep_opts* o, const PostOut
     unsigned long long* rows = (unsigned long long*)c->cpart.p;
     if (q > 2) {
       const PlaneAnd pa{(const uint8_t*)c->fuseS.p, (const uint8_t*)c->fuseU.p, n, q - 1, (uint8_t*)c->maskU.p};
-      hipLaunchKernelGGL(k_classify_and<T>, dim3((unsigned)nob), dim3(256), 0, c->stream, (const T*)c->mean.p, (const T*)c->var.p, n, (T)o->b, pa,
+      hipLaunchKernelGGL(k_classify_and<T>, dim3((unsigned)nob), dim3(256), 0, c->stream, (const T*)v.mean->p, (const T*)v.var->p, n, (T)o->b, pa,
                          (uint8_t*)c->maskS.p, rows + post.fuse_rows, c->cpart_cap);
     } else
-    hipLaunchKernelGGL(k_classify_obj<T>, dim3((unsigned)nob), dim3(256), 0, c->stream, (const T*)c->mean.p, (const T*)c->var.p, n, (T)o->b,
+    hipLaunchKernelGGL(k_classify_obj<T>, dim3((unsigned)nob), dim3(256), 0, c->stream, (const T*)v.mean->p, (const T*)v.var->p, n, (T)o->b,
                        (const uint8_t*)c->maskS.p, rows + post.fuse_rows, c->cpart_cap);
     fj.part = (const unsigned long long*)rows;
     fj.nparts = post.fuse_rows + nob;
@@ -1186,8 +1222,8 @@ static int sweep_common_front(sbo_ctx* c, const sbo_sweep_opts* o, const PostOut
   if ((rc = ensure(c->cpart, sizeof(unsigned long long) * kClassifyRow * (size_t)ncb))) return rc;
   c->cpart_cap = (int)(c->cpart.bytes / (sizeof(unsigned long long) * kClassifyRow));
   if (n > 0)
-    hipLaunchKernelGGL((k_classify<T>), dim3((unsigned)ncb), dim3(256), 0, c->stream, (const T*)c->mean.p, (const T*)c->var.p, n, q,
-                       (T)o->b, (uint8_t*)c->maskS.p, (uint8_t*)c->maskU.p, (unsigned long long*)c->cpart.p, c->cpart_cap, gb_of(c));
+    hipLaunchKernelGGL((k_classify<T>), dim3((unsigned)ncb), dim3(256), 0, c->stream, (const T*)v.mean->p, (const T*)v.var->p, n, q,
+                       (T)o->b, (uint8_t*)c->maskS.p, (uint8_t*)c->maskU.p, (unsigned long long*)c->cpart.p, c->cpart_cap, gb_of<T>(c, v));
   fj.part = (const unsigned long long*)c->cpart.p;
   fj.nparts = n > 0 ? ncb : 0;
   fj.pcap = c->cpart_cap;
@@ -1199,11 +1235,11 @@ static int sweep_common_front(sbo_ctx* c, const sbo_sweep_opts* o, const PostOut
 }
 
 template <typename T, int D>
-static int launch_exact(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, int cidx, int lidx, uint8_t* G) {
+static int launch_exact(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, const SetView& v, int cidx, int lidx, uint8_t* G) {
   const long long n = c->cs.n_local;
   SweepScalars* sc = (SweepScalars*)ln.scal.p;
-  const T* mean_c = (const T*)c->mean.p + (size_t)cidx * n;
-  const T* var_c = (const T*)c->var.p + (size_t)cidx * n;
+  const T* mean_c = (const T*)v.mean->p + (size_t)cidx * n;
+  const T* var_c = (const T*)v.var->p + (size_t)cidx * n;
   CandSpec csU = c->cs;          // the witness set: every candidate that can matter (ranks > 1: the transform's window)
   const uint8_t* Uall = (const uint8_t*)c->maskU.p;
   if (multi_rank(c)) {
@@ -1213,10 +1249,7 @@ static int launch_exact(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
   }
   RcExp rx;
   memset(&rx, 0, sizeof(rx));
-  if (gb_of(c) && !c->rc_active) {        // (fast path of an approximating posterior: the listed candidates' verdicts are judged against its band)
-    rx.gb_c = cidx;
-    rx.gb_l = c->gb_slow ? -1 : lidx;
-  }
+  if (!v.refined) rx_band<T>(c, v, cidx, lidx, rx);   // (fast path of an approximating posterior: the listed candidates' verdicts are judged against its band)
   hipLaunchKernelGGL((k_expander_exact<T, D>), dim3(1024), dim3(256), 0, ln.stream, c->cs, csU, mean_c, var_c, (T)o->b,
                      Uall, (const unsigned long long*)c->Lmax.p, lidx, sc,
                      (const long long*)ln.amb.p, G, rx);
@@ -1225,11 +1258,11 @@ static int launch_exact(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
 }
 
 template <typename T>
-static int launch_exact_d(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, int cidx, int lidx, uint8_t* G) {
+static int launch_exact_d(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, const SetView& v, int cidx, int lidx, uint8_t* G) {
   switch (c->mc.dpad) {
-    case 2: return launch_exact<T, 2>(c, ln, o, cidx, lidx, G);
-    case 4: return launch_exact<T, 4>(c, ln, o, cidx, lidx, G);
-    case 8: return launch_exact<T, 8>(c, ln, o, cidx, lidx, G);
+    case 2: return launch_exact<T, 2>(c, ln, o, v, cidx, lidx, G);
+    case 4: return launch_exact<T, 4>(c, ln, o, v, cidx, lidx, G);
+    case 8: return launch_exact<T, 8>(c, ln, o, v, cidx, lidx, G);
   }
   return fail(SBO_E_UNSUPPORTED, "unsupported padded dimension");
 }
@@ -1441,7 +1474,7 @@ static int list_index_tree(sbo_ctx* c, sbo_ctx::SetLane& ln, int D, IdxTree* t) 
 // G_c of an explicit list on the index: boxes of this sweep's U members, then the walk (in-band verdicts of a guard band go to
 // amb, for k_expander_exact behind it)
 template <typename T, int D>
-static int list_index_expander(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, int cidx, int lidx, uint8_t* G) {
+static int list_index_expander(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, const SetView& v, int cidx, int lidx, uint8_t* G) {
   if (!c->lx.valid) return fail(SBO_E_INVALID, "list index not built for this sweep");
   const long long n = c->cs.n_local;
   IdxTree t;
@@ -1453,12 +1486,9 @@ static int list_index_expander(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep
     hipLaunchKernelGGL((k_idx_parents<D>), dim3((unsigned)((t.cnt[lev] + 3) / 4)), dim3(256), 0, ln.stream, t, lev);
   RcExp rx;                                  // (as launch_exact: the guard band of an approximating posterior's fast path)
   memset(&rx, 0, sizeof(rx));
-  if (gb_of(c) && !c->rc_active) {
-    rx.gb_c = cidx;
-    rx.gb_l = c->gb_slow ? -1 : lidx;
-  }
-  const T* mean_c = (const T*)c->mean.p + (size_t)cidx * n;
-  const T* var_c = (const T*)c->var.p + (size_t)cidx * n;
+  if (!v.refined) rx_band<T>(c, v, cidx, lidx, rx);
+  const T* mean_c = (const T*)v.mean->p + (size_t)cidx * n;
+  const T* var_c = (const T*)v.var->p + (size_t)cidx * n;
   const unsigned nb = (unsigned)std::min<long long>((n + 3) / 4, (long long)c->n_cu * 16);
   hipLaunchKernelGGL((k_idx_expander<T, D>), dim3(nb), dim3(256), 0, ln.stream, t, mean_c, var_c, (T)o->b, (const uint8_t*)c->maskS.p,
                      (const unsigned long long*)c->Lmax.p, lidx, (SweepScalars*)ln.scal.p, G, (long long*)ln.amb.p, rx);
@@ -1467,11 +1497,11 @@ static int list_index_expander(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep
   return SBO_OK;
 }
 template <typename T>
-static int list_index_expander_d(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, int cidx, int lidx, uint8_t* G) {
+static int list_index_expander_d(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, const SetView& v, int cidx, int lidx, uint8_t* G) {
   switch (idx_dpad(c->cs.d)) {
-    case 2: return list_index_expander<T, 2>(c, ln, o, cidx, lidx, G);
-    case 4: return list_index_expander<T, 4>(c, ln, o, cidx, lidx, G);
-    default: return list_index_expander<T, 8>(c, ln, o, cidx, lidx, G);
+    case 2: return list_index_expander<T, 2>(c, ln, o, v, cidx, lidx, G);
+    case 4: return list_index_expander<T, 4>(c, ln, o, v, cidx, lidx, G);
+    default: return list_index_expander<T, 8>(c, ln, o, v, cidx, lidx, G);
   }
 }
 
@@ -1483,26 +1513,27 @@ struct MinimizerJob {
   FinalJob fin;                 // the classification's merge, when it too waits for the expander's first launch
 };
 template <typename T>
-static void launch_minimizer(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, MinimizerJob* mj) {
+static void launch_minimizer(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, const SetView& v, MinimizerJob* mj) {
   if (mj) launch_final(c, &mj->fin);
   if (!mj || !mj->pending) return;
   mj->pending = false;
-  hipLaunchKernelGGL((k_minimizer<T>), dim3(mj->nb), dim3(256), 0, ln.stream, (const T*)c->mean.p, (const T*)c->var.p, c->cs.n_local,
+  hipLaunchKernelGGL((k_minimizer<T>), dim3(mj->nb), dim3(256), 0, ln.stream, (const T*)v.mean->p, (const T*)v.var->p, c->cs.n_local,
                      (long long)c->cs.first, (T)o->b, (const uint8_t*)c->maskS.p, (uint8_t*)c->maskM.p, (SweepScalars*)ln.scal.p,
-                     mj->partial, gb_of(c));
+                     mj->partial, gb_of<T>(c, v));
 }
 
 // `lazy_exact`: the exhaustive recheck of in-band candidates (k_expander_exact) is NOT launched -- the caller looks at the
 // sweep's n_amb afterwards and runs it (and everything behind it) only when something was listed, which is rare
 template <typename T>
-static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, int cidx, uint8_t* G, MinimizerJob* mj = nullptr, bool lazy_exact = false) {
+static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, const SetView& v, int cidx, uint8_t* G, MinimizerJob* mj = nullptr,
+                        bool lazy_exact = false) {
   const long long n = c->cs.n_local;
-  if (n == 0) { launch_minimizer<T>(c, ln, o, mj); return SBO_OK; }
+  if (n == 0) { launch_minimizer<T>(c, ln, o, v, mj); return SBO_OK; }
   const int q = c->mc.q;
   const int lidx = o->reference_quirk_L_index ? q - 1 : cidx;   // models/SafeOpt.py:110 (loop-leaked i)
   SweepScalars* sc = (SweepScalars*)ln.scal.p;
-  const T* mean_c = (const T*)c->mean.p + (size_t)cidx * n;
-  const T* var_c = (const T*)c->var.p + (size_t)cidx * n;
+  const T* mean_c = (const T*)v.mean->p + (size_t)cidx * n;
+  const T* var_c = (const T*)v.var->p + (size_t)cidx * n;
   const int nb = reduce_blocks(c);
   int rc;
   if ((rc = ensure(ln.amb, sizeof(long long) * (size_t)n))) return rc;
@@ -1621,15 +1652,15 @@ static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
       if (mj && mj->pending) {
         mj->pending = false;
         j.nb = mj->nb;
-        j.mean0 = (const T*)c->mean.p;
-        j.var0 = (const T*)c->var.p;
+        j.mean0 = (const T*)v.mean->p;
+        j.var0 = (const T*)v.var->p;
         j.n = n;
         j.first = (long long)c->cs.first;
         j.b = (T)o->b;
         j.S = (const uint8_t*)c->maskS.p;
         j.M = (uint8_t*)c->maskM.p;
         j.partial = mj->partial;
-        j.gb = gb_of(c);
+        j.gb = gb_of<T>(c, v);
       }
       if (want_bmin) {
         const int nblocks = (last_cnt_ + blk_ - 1) / blk_;
@@ -1647,7 +1678,7 @@ static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
       else hipLaunchKernelGGL((k_set_mid<T, false>), dim3((unsigned)(j.ns + j.nb + j.nm)), dim3(256), 0, ln.stream, j);
       cg.Dc = dc1;
     } else {
-      launch_minimizer<T>(c, ln, o, mj);
+      launch_minimizer<T>(c, ln, o, v, mj);
       launch_edt_axis0(c, ln, Uall, nlines, count0, c->cs.step[0], din);
       for (int a = 1; a < d - 1; ++a) {
         hipLaunchKernelGGL(k_edt_scan, dim3((unsigned)std::min<long long>((nt + 255) / 256, 1 << 20)), dim3(256), 0, ln.stream,
@@ -1698,20 +1729,16 @@ static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
       }
       const long long len0 = d >= 2 ? count0 : n;               // positions per line / local lines
       const long long nl = n / len0;
-      RcExp rx;                                                  // fp32 model with fp64 recheck: unrefined entries carry a band
+      RcExp rx;
       memset(&rx, 0, sizeof(rx));
-      if (c->rc_active) {
-        rx.refined = (const uint8_t*)c->rc_refined.p;
-        const double ys = std::max(1.0, c->mc.Y_std[cidx]);
-        rx.dm = 1e-4 * ys;
-        rx.dv = 1e-4 * ys * ys;
-        rx.list = (long long*)((char*)c->rc_list.p + kRcList);
-        rx.count = (unsigned long long*)((char*)c->rc_list.p + kRcCount2);
+      if (v.refined) {                                           // a recheck's pass: unrefined entries carry a band, open verdicts are deferred
+        rx.refined = v.refined;
+        rx.dm = v.rc_band->dm[cidx];
+        rx.dv = v.rc_band->dv[cidx];
+        rx.list = v.rc_list;
+        rx.count = v.rc_count;
       }
-      if (gb_of(c)) {                                            // guard band of an approximating fp64 posterior (fast path: no list)
-        rx.gb_c = cidx;
-        rx.gb_l = c->gb_slow ? -1 : lidx;                        // (the slow path has recomputed the Lipschitz keys exactly)
-      }
+      rx_band<T>(c, v, cidx, lidx, rx);                          // guard band of an approximating fp64 posterior (fast path: no list)
       const dim3 dgrid((unsigned)((len0 + 255) / 256), (unsigned)std::min<long long>((nl + kDecideLines - 1) / kDecideLines, 65535));
 #define SBO_DECIDE(LIST)                                                                                                            \
   hipLaunchKernelGGL((k_edt_decide<T, LIST>), dgrid, dim3(256), 0, ln.stream, (const double*)din, nl, (int)len0, goff / len0, goff, \
@@ -1754,11 +1781,11 @@ static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
     }
   } else {
     // explicit candidate lists, and grid ranges that are not whole hyper-planes: exhaustive evaluation
-    launch_minimizer<T>(c, ln, o, mj);
+    launch_minimizer<T>(c, ln, o, v, mj);
     if (list_index_on(c)) {
       // (explicit lists on the spatial index: the same verdicts with the pairs that cannot matter left out)
-      if ((rc = list_index_expander_d<T>(c, ln, o, cidx, lidx, G))) return rc;
-      return launch_exact_d<T>(c, ln, o, cidx, lidx, G);
+      if ((rc = list_index_expander_d<T>(c, ln, o, v, cidx, lidx, G))) return rc;
+      return launch_exact_d<T>(c, ln, o, v, cidx, lidx, G);
     }
     // (quadratic: every safe candidate against every U point, like the reference's vmap -- fine for the lists a campaign
     // uses, seconds at the cap)
@@ -1771,7 +1798,7 @@ static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
   }
   SBO_HIP(hipGetLastError());
   if (lazy_exact && plane_aligned) return SBO_OK;
-  return launch_exact_d<T>(c, ln, o, cidx, lidx, G);
+  return launch_exact_d<T>(c, ln, o, v, cidx, lidx, G);
 }
 
 static void coords_of(const sbo_ctx* c, long long gidx, double* x) {
@@ -1958,7 +1985,6 @@ static void sweep_times(sbo_ctx* c) {
   c->prof.comm_ms = cms;
 }
 static void sweep_comm_reset(sbo_ctx* c) {
-  if (c->in_halo_rerun) return;                // (the counters of the discarded pass stay in the sweep's record)
   c->halo_reruns = 0;
   c->host_syncs = 0;
   c->comm_bytes = 0;
@@ -1967,43 +1993,89 @@ static void sweep_comm_reset(sbo_ctx* c) {
   c->comm_host_ms = 0.0;
 }
 
-#include "sets_colpath.inc.hpp"
+enum SweepKind { kSafeOpt = 1, kGoose = 2, kTr = 3 };   // (sbo_ctx::last_sweep)
 
+// What the three sweeps open with: start event, posterior request, masks, K1 -- unless the view brings the posterior or the caller's
+// resident one serves (*reuse) --, its stop event and the standing audit.  SafeOpt and GoOSE also start the sweep's comm record
+// (a halo rerun goes on with the discarded pass's) and prepare the list index.
 template <typename T>
-static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_result* res) {
+static int sweep_open(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, SweepKind kind, bool* reuse_out, PostOutcome& post) {
   const long long n = c->cs.n_local;
   const int q = c->mc.q;
   int rc;
-  sweep_comm_reset(c);
+  if (kind != kTr && !v.halo_rerun) sweep_comm_reset(c);
   SBO_HIP(hipEventRecord(c->ev[0], c->stream));
-  if ((rc = list_index_prepare(c))) return rc;          // (explicit lists on the spatial index: its sorted order, once per list)
-  // (a posterior a lean sweep launched lacks the objective's Lipschitz key: a full sweep does not reuse it)
-  const bool reuse = o->posterior_ready && c->posterior_valid && (o->lean || !c->post_l0_missing);
+  if (kind != kTr && (rc = list_index_prepare(c))) return rc;   // (explicit lists on the spatial index: its sorted order, once per list)
+  // (a posterior a lean sweep launched lacks the objective's Lipschitz key: GoOSE reports L_0, and a full SafeOpt sweep does not reuse it)
+  const bool l0_ok = kind == kTr || !c->post_l0_missing || (kind == kSafeOpt && o->lean);
+  const bool reuse = v.given || (o->posterior_ready && c->posterior_valid && l0_ok);
   PostRequest req = sweep_request(c, o->b, !reuse);
-  // column path (sets_colpath.inc.hpp): a fresh posterior of a one-constraint fp64 model on one rank may deliver the classification
-  // as column words (the GEMM posterior decides whether its launch qualifies: PostOutcome::col_active)
-  req.col = !reuse && std::is_same<T, double>::value && q == 2 && !multi_rank(c) && !c->rc_active && c->result_mirror && n > 0;
-  const int lean = o->lean;
-  req.col_lean = req.col ? (lean >= 2 ? 2 : (lean ? 1 : 0)) : 0;
-  req.sweep_lean = (lean && q >= 2 && !reuse) ? 1 : 0;
+  if (kind == kSafeOpt) {
+    // column path (sets_colpath.inc.hpp): a fresh posterior of a one-constraint fp64 model on one rank may deliver the classification
+    // as column words (the GEMM posterior decides whether its launch qualifies: PostOutcome::col_active)
+    req.col = !reuse && std::is_same<T, double>::value && q == 2 && !multi_rank(c) && c->result_mirror && n > 0;
+    req.col_lean = req.col ? (o->lean >= 2 ? 2 : (o->lean ? 1 : 0)) : 0;
+    req.sweep_lean = (o->lean && q >= 2 && !reuse) ? 1 : 0;
+  }
   if ((rc = sweep_masks(c, req))) return rc;
-  PostOutcome post;
   if (!reuse && (rc = posterior_enqueue(c, req, &post))) return rc;
   SBO_HIP(k1_stop(c, post));
-  if (!reuse && !c->rc_active && (rc = guard_audit_enqueue(c, post))) return rc;
+  if (!reuse && (rc = guard_audit_enqueue(c, post))) return rc;
+  *reuse_out = reuse;
+  return SBO_OK;
+}
+
+// ... and close with, once the end event (ev[4]; the trust-region sweep: ev[2]) has been waited for: the profile
+static int sweep_profile(sbo_ctx* c, SweepKind kind, bool reuse) {
+  const long long n = c->cs.n_local;
+  const int end = kind == kTr ? 2 : 4;
+  int rc;
+  float t01 = 0, t12 = 0, t23 = 0, t34 = 0, t0e = 0;
+  SBO_HIP(hipEventElapsedTime(&t01, c->ev[0], c->ev[1]));
+  if (c->phase_events || kind == kTr) SBO_HIP(hipEventElapsedTime(&t12, c->ev[1], c->ev[2]));
+  if (c->phase_events && kind != kTr) {
+    SBO_HIP(hipEventElapsedTime(&t23, c->ev[2], c->ev[3]));
+    SBO_HIP(hipEventElapsedTime(&t34, c->ev[3], c->ev[4]));
+  }
+  SBO_HIP(hipEventElapsedTime(&t0e, c->ev[0], c->ev[end]));
+  memset(&c->prof, 0, sizeof(c->prof));
+  if (kind != kTr && (rc = list_index_profile(c))) return rc;
+  c->prof.posterior_ms = t01;
+  c->prof.classify_ms = t12;
+  c->prof.expander_ms = t23;
+  c->prof.argreduce_ms = t34;
+  c->prof.total_ms = t0e;
+  c->prof.candidates = n;
+  c->prof.posterior_launches = (!reuse && n > 0) ? 1 : 0;
+  const double nn = c->mc.n, dd = c->mc.d;
+  c->prof.posterior_flops = reuse ? 0.0 : c->mc.q * (nn * nn + (2 * dd + 10) * nn) * (double)n;
+  if (kind != kTr) sweep_times(c);
+  return SBO_OK;
+}
+
+#include "sets_colpath.inc.hpp"
+
+template <typename T>
+static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, sbo_safeopt_result* res) {
+  const long long n = c->cs.n_local;
+  const int q = c->mc.q;
+  int rc;
+  bool reuse;
+  PostOutcome post;
+  if ((rc = sweep_open<T>(c, o, v, kSafeOpt, &reuse, post))) return rc;
   SweepScalars h;
   unsigned long long Lk[kMaxQ];
   const bool colpath = post.col_active;
   if (colpath) {
     // (a lean sweep left the objective's mean / var unwritten where no later stage reads them: whoever wants the posterior re-runs K1)
     if (post.col_lean) c->posterior_valid = false;
-    if ((rc = col_set_phase(c, o, post, h, Lk))) return rc;
+    if ((rc = col_set_phase(c, o, v, post, h, Lk))) return rc;
   } else {
   MinimizerJob mj;
   const int nb = reduce_blocks(c);
   // one constraint on one rank: the exhaustive recheck of in-band candidates (almost never any) is launched only when the
   // result block says that something was listed -- one launch (~5 us) less on the common path
-  const bool lazy_exact = c->exact_lazy && q == 2 && !multi_rank(c) && !c->rc_active && c->result_mirror && n > 0 &&
+  const bool lazy_exact = c->exact_lazy && q == 2 && !multi_rank(c) && !v.refined && c->result_mirror && n > 0 &&
                           whole_planes(c);      // (grids: lists decide every expander exhaustively)
   // partials of the q arg-max reductions side by side: merged by one launch at the end (k_safeopt_finals)
   const size_t pstride = partial_stride(nb);
@@ -2012,36 +2084,36 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
   const bool lanes = lanes_on(c);
   {
     const bool defer = q >= 2 && !multi_rank(c) && c->set_fuse && n > 0 && !lanes;   // (lanes fork right behind the merge)
-    if ((rc = sweep_common_front<T>(c, o, post, defer ? &mj.fin : nullptr))) return rc;
+    if ((rc = sweep_common_front<T>(c, o, v, post, defer ? &mj.fin : nullptr))) return rc;
     if ((rc = sweep_exchange_front<T>(c, o, true))) return rc;
     // (single rank: the minimiser rides in the first constraint's k_set_mid; with ranks > 1 it is queued here, ahead of the
     // host's wait for the C1 keys)
     mj.pending = n > 0;
     mj.nb = nb;
     mj.partial = (Best*)pbase;
-    if (q < 2 || multi_rank(c)) launch_minimizer<T>(c, c->lane[0], o, &mj);
+    if (q < 2 || multi_rank(c)) launch_minimizer<T>(c, c->lane[0], o, v, &mj);
     if (c->phase_events) SBO_HIP(hipEventRecord(c->ev[2], c->stream));
     if (lanes && (rc = lanes_fork(c))) return rc;
     for (int cc = 1; cc < q; ++cc) {
       uint8_t* G = (uint8_t*)c->maskG.p + (size_t)(cc - 1) * n;
       const bool side = lanes && ((cc - 1) & 1);                 // constraints alternate between the two lanes
-      if ((rc = expander_set<T>(c, c->lane[side], o, cc, G, side ? nullptr : &mj, lazy_exact))) return rc;
+      if ((rc = expander_set<T>(c, c->lane[side], o, v, cc, G, side ? nullptr : &mj, lazy_exact))) return rc;
     }
-    launch_minimizer<T>(c, c->lane[0], o, &mj);
+    launch_minimizer<T>(c, c->lane[0], o, v, &mj);
     if (lanes && (rc = lanes_join(c))) return rc;
   }
   SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
   if (c->phase_events) SBO_HIP(hipEventRecord(c->ev[3], c->stream));
   if (n > 0 && q > 1) {
     hipLaunchKernelGGL((k_arg_masked_multi<T, true, ValArray<T>>), dim3((unsigned)nb, (unsigned)(q - 1)), dim3(256), 0, c->stream,
-                       ValArray<T>{(const T*)c->var.p, 0.0}, (const uint8_t*)nullptr, (const uint8_t*)c->maskG.p, n, (long long)c->cs.first, pbase,
-                       pstride, 1, gb_of(c));
+                       ValArray<T>{(const T*)v.var->p, 0.0}, (const uint8_t*)nullptr, (const uint8_t*)c->maskG.p, n, (long long)c->cs.first, pbase,
+                       pstride, 1, gb_of<T>(c, v));
   }
   const bool mirrored = !multi_rank(c) && c->result_mirror;
   hipExtLaunchKernelGGL(k_sweep_finals<true>, dim3((unsigned)q), dim3(256), 0, c->stream, nullptr, mirrored ? c->ev[4] : nullptr, 0,
                         (const unsigned char*)pbase, pstride, n > 0 ? nb : 0, sc,
                         lanes ? (const SweepScalars*)c->lane[1].scal.p : (const SweepScalars*)nullptr,
-                        mirrored ? c->h_back : (unsigned char*)nullptr, (const unsigned long long*)c->Lmax.p, gb_of(c) ? 1 : 0);
+                        mirrored ? c->h_back : (unsigned char*)nullptr, (const unsigned long long*)c->Lmax.p, gb_of<T>(c, v) ? 1 : 0);
   SBO_HIP(hipGetLastError());
   bool is_max[kArgSlots];
   for (int t = 0; t < kArgSlots; ++t) is_max[t] = true;
@@ -2049,14 +2121,14 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
   if (lazy_exact && (h.n_amb > 0 || c->exact_lazy == 2)) {      // (2: always, the test of this path)
     // in-band candidates after all: their exhaustive recheck, then the expanders' arg-max and the finals once more
     const int lidx = o->reference_quirk_L_index ? q - 1 : 1;
-    if ((rc = launch_exact_d<T>(c, c->lane[0], o, 1, lidx, (uint8_t*)c->maskG.p))) return rc;
+    if ((rc = launch_exact_d<T>(c, c->lane[0], o, v, 1, lidx, (uint8_t*)c->maskG.p))) return rc;
     hipLaunchKernelGGL((k_arg_masked_multi<T, true, ValArray<T>>), dim3((unsigned)nb, 1u), dim3(256), 0, c->stream,
-                       ValArray<T>{(const T*)c->var.p, 0.0}, (const uint8_t*)nullptr, (const uint8_t*)c->maskG.p, n, (long long)c->cs.first, pbase,
-                       pstride, 1, gb_of(c));
+                       ValArray<T>{(const T*)v.var->p, 0.0}, (const uint8_t*)nullptr, (const uint8_t*)c->maskG.p, n, (long long)c->cs.first, pbase,
+                       pstride, 1, gb_of<T>(c, v));
     hipLaunchKernelGGL(k_sweep_clear_slot, dim3(1), dim3(1), 0, c->stream, sc, 1);
     hipExtLaunchKernelGGL(k_sweep_finals<true>, dim3((unsigned)q), dim3(256), 0, c->stream, nullptr, c->ev[4], 0,
                           (const unsigned char*)pbase, pstride, nb, sc, (const SweepScalars*)nullptr, c->h_back,
-                          (const unsigned long long*)c->Lmax.p, gb_of(c) ? 1 : 0);
+                          (const unsigned long long*)c->Lmax.p, gb_of<T>(c, v) ? 1 : 0);
     SBO_HIP(hipGetLastError());
     if ((rc = sweep_exchange_back(c, h, is_max, Lk, c->ev[4], true))) return rc;
   }
@@ -2068,10 +2140,9 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
       sbo_sweep_opts o2 = *o;
       o2.posterior_ready = 1;
       ++c->halo_reruns;
-      c->in_halo_rerun = true;
-      const int rr = sweep_safeopt_t<T>(c, &o2, res);
-      c->in_halo_rerun = false;
-      return rr;
+      SetView v2 = v;
+      v2.halo_rerun = true;
+      return sweep_safeopt_t<T>(c, &o2, v2, res);
     }
     halo_learn(c, h, Lk, o->reference_quirk_L_index);
   }
@@ -2080,26 +2151,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
   c->last_sweep = 1;
   if (getenv("SBO_DEBUG_SCAN")) fprintf(stderr, "[safebo] open candidates scanned (last constraint) %lld, exact rechecks %lld\n", h.n_scan, h.n_amb_total);
 
-  float t01 = 0, t12 = 0, t23 = 0, t34 = 0, t04 = 0;
-  SBO_HIP(hipEventElapsedTime(&t01, c->ev[0], c->ev[1]));
-  if (c->phase_events) {
-    SBO_HIP(hipEventElapsedTime(&t12, c->ev[1], c->ev[2]));
-    SBO_HIP(hipEventElapsedTime(&t23, c->ev[2], c->ev[3]));
-    SBO_HIP(hipEventElapsedTime(&t34, c->ev[3], c->ev[4]));
-  }
-  SBO_HIP(hipEventElapsedTime(&t04, c->ev[0], c->ev[4]));
-  memset(&c->prof, 0, sizeof(c->prof));
-  if ((rc = list_index_profile(c))) return rc;
-  c->prof.posterior_ms = t01;
-  c->prof.classify_ms = t12;
-  c->prof.expander_ms = t23;
-  c->prof.argreduce_ms = t34;
-  c->prof.total_ms = t04;
-  c->prof.candidates = n;
-  c->prof.posterior_launches = (!reuse && n > 0) ? 1 : 0;
-  const double nn = c->mc.n, dd = c->mc.d;
-  c->prof.posterior_flops = reuse ? 0.0 : q * (nn * nn + (2 * dd + 10) * nn) * (double)n;
-  sweep_times(c);
+  if ((rc = sweep_profile(c, kSafeOpt, reuse))) return rc;
   c->prof.set_path = colpath ? 1 : 0;
   c->prof.k1_tiles_skipped = colpath ? h.tiles_skipped : 0;
 
@@ -2141,7 +2193,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
     coords_of(c, res->expander_index, res->expander_x);
   }
   res->choose_minimizer = res->minimizer_std > res->expander_std;   // test/test_SafeOpt.py:153
-  if (gb_of(c)) {
+  if (gb_of<T>(c, v)) {
     // the choices among the reductions' winners are decisions too: which constraint's expander is kept (largest var_0), and
     // minimiser against expander (std_min > std_exp) -- var_0 is known to +- arg_d
     long long near = 0;
@@ -2158,18 +2210,18 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeopt_resu
 }
 
 template <typename T>
-static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_result* res);
+static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, sbo_goose_result* res);
 template <typename T>
-static int sweep_tr_t(sbo_ctx* c, const sbo_sweep_opts* o, const double* x0, double r, sbo_tr_result* res);
+static int sweep_tr_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, const double* x0, double r, sbo_tr_result* res);
 #include "sets_recheck.inc.hpp"
 
 template <typename T, int D>
-static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, int cidx, const uint8_t* src, uint8_t* O) {
+static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, const SetView& v, int cidx, const uint8_t* src, uint8_t* O) {
   const long long n = c->cs.n_local;
   const int q = c->mc.q;
   const int lidx = o->reference_quirk_L_index ? q - 1 : cidx;   // models/GoOSE.py:100 (loop-leaked i)
-  const T* mean_c = (const T*)c->mean.p + (size_t)cidx * n;
-  const T* var_c = (const T*)c->var.p + (size_t)cidx * n;
+  const T* mean_c = (const T*)v.mean->p + (size_t)cidx * n;
+  const T* var_c = (const T*)v.var->p + (size_t)cidx * n;
   int rc;
   long long maxlocal = n;
   for (int r = 0; r < c->world && multi_rank(c); ++r) maxlocal = std::max(maxlocal, c->first_of[r + 1] - c->first_of[r]);
@@ -2364,7 +2416,7 @@ static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o,
     }
     hipLaunchKernelGGL((k_goose_exact<T, D>), dim3(1024), dim3(256), 0, ln.stream, c->cs, css, W,
                        (const unsigned long long*)c->Lmax.p, lidx, sc, cidx, (const long long*)ln.amb.p, O,
-                       (gb_of(c) && !c->rc_active && !c->gb_slow) ? 1 : 0);
+                       (gb_of<T>(c, v) && !v.refined && v.band == SetBand::plan) ? 1 : 0);
     SBO_HIP(hipGetLastError());
     return SBO_OK;
   }
@@ -2406,11 +2458,11 @@ static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o,
 }
 
 template <typename T>
-static int goose_sets_d(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, int cidx, const uint8_t* src, uint8_t* O) {
+static int goose_sets_d(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, const SetView& v, int cidx, const uint8_t* src, uint8_t* O) {
   switch (c->mc.dpad) {
-    case 2: return goose_sets<T, 2>(c, ln, o, cidx, src, O);
-    case 4: return goose_sets<T, 4>(c, ln, o, cidx, src, O);
-    case 8: return goose_sets<T, 8>(c, ln, o, cidx, src, O);
+    case 2: return goose_sets<T, 2>(c, ln, o, v, cidx, src, O);
+    case 4: return goose_sets<T, 4>(c, ln, o, v, cidx, src, O);
+    case 8: return goose_sets<T, 8>(c, ln, o, v, cidx, src, O);
   }
   return fail(SBO_E_UNSUPPORTED, "unsupported padded dimension");
 }
@@ -2440,24 +2492,17 @@ static void launch_argmin_dist(sbo_ctx* c, const double* dev_target, int nb) {
 // as for SafeOpt, one all-gather of the source weights per constraint, C3 for the arg-min slots and a second C3 for
 // the explore step (every rank derives the same target from the merged slots).
 template <typename T>
-static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_result* res) {
+static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, sbo_goose_result* res) {
   const long long n = c->cs.n_local;
   const int q = c->mc.q;
   int rc;
-  sweep_comm_reset(c);
-  SBO_HIP(hipEventRecord(c->ev[0], c->stream));
-  if ((rc = list_index_prepare(c))) return rc;          // (explicit lists on the spatial index: its sorted order, once per list)
-  const bool reuse = o->posterior_ready && c->posterior_valid && !c->post_l0_missing;    // (GoOSE reports L_0: not from a lean launch)
-  const PostRequest req = sweep_request(c, o->b, !reuse);
-  if ((rc = sweep_masks(c, req))) return rc;
+  bool reuse;
   PostOutcome post;
-  if (!reuse && (rc = posterior_enqueue(c, req, &post))) return rc;
-  SBO_HIP(k1_stop(c, post));
-  if (!reuse && !c->rc_active && (rc = guard_audit_enqueue(c, post))) return rc;
+  if ((rc = sweep_open<T>(c, o, v, kGoose, &reuse, post))) return rc;
   const int nb = reduce_blocks(c);
   const bool lanes = lanes_on(c);
   {
-    if ((rc = sweep_common_front<T>(c, o, post, nullptr))) return rc;
+    if ((rc = sweep_common_front<T>(c, o, v, post, nullptr))) return rc;
     if ((rc = sweep_exchange_front<T>(c, o, true))) return rc;
     if ((rc = ensure(c->maskO, (size_t)std::max<long long>(n, 1) * std::max(1, q - 1)))) return rc;
     if (c->phase_events) SBO_HIP(hipEventRecord(c->ev[2], c->stream));
@@ -2473,10 +2518,10 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_result* 
       const bool can_expand = n <= (1ll << 17) || whole_planes(c);   // (larger lists: S_t is the source set)
       const uint8_t* src = (const uint8_t*)c->maskS.p;
       if (can_expand) {
-        if ((rc = expander_set<T>(c, ln, o, cc, G))) return rc;
+        if ((rc = expander_set<T>(c, ln, o, v, cc, G))) return rc;
         src = G;
       }
-      if ((rc = goose_sets_d<T>(c, ln, o, cc, src, O))) return rc;
+      if ((rc = goose_sets_d<T>(c, ln, o, v, cc, src, O))) return rc;
     }
     if (lanes && (rc = lanes_join(c))) return rc;
   }
@@ -2484,13 +2529,13 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_result* 
   if (c->phase_events) SBO_HIP(hipEventRecord(c->ev[3], c->stream));
   // arg-min of lcb_0 over S_t and over every O_c: the bound is computed for the masked candidates only; one launch, the q
   // reductions side by side
-  const ValLcb<T> lcb0{(const T*)c->mean.p, (const T*)c->var.p, (T)o->b, 0.0, 0.0};
+  const ValLcb<T> lcb0{(const T*)v.mean->p, (const T*)v.var->p, (T)o->b, 0.0, 0.0};
   const size_t pstride = partial_stride(nb);     // q regions of partials, one merge launch
   if ((rc = ensure(c->partial, pstride * (size_t)q))) return rc;
   unsigned char* pbase = (unsigned char*)c->partial.p;
   if (n > 0)
     hipLaunchKernelGGL((k_arg_masked_multi<T, false, ValLcb<T>>), dim3((unsigned)nb, (unsigned)q), dim3(256), 0, c->stream, lcb0,
-                       (const uint8_t*)c->maskS.p, (const uint8_t*)c->maskO.p, n, (long long)c->cs.first, pbase, pstride, 0, gb_of(c));
+                       (const uint8_t*)c->maskS.p, (const uint8_t*)c->maskO.p, n, (long long)c->cs.first, pbase, pstride, 0, gb_of<T>(c, v));
   SweepScalars h;
   bool is_max[kArgSlots];
   for (int t = 0; t < kArgSlots; ++t) is_max[t] = false;
@@ -2499,7 +2544,7 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_result* 
   const bool fused_explore = !multi_rank(c) && q > 1;
   double* dev_t = (double*)c->lane[0].scal.p + 256;
   // (one rank: the finals and the target choice in one launch, the last merge writes the host's block itself)
-  const int gbon = gb_of(c) ? 1 : 0;
+  const int gbon = gb_of<T>(c, v) ? 1 : 0;
   const bool short_tail = fused_explore && c->result_mirror && (c->mc.dpad == 2 || c->mc.dpad == 4 || c->mc.dpad == 8);
   const SweepScalars* l1 = lanes ? (const SweepScalars*)c->lane[1].scal.p : (const SweepScalars*)nullptr;
   if (short_tail) {
@@ -2537,10 +2582,9 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_result* 
       sbo_sweep_opts o2 = *o;
       o2.posterior_ready = 1;
       ++c->halo_reruns;
-      c->in_halo_rerun = true;
-      const int rr = sweep_goose_t<T>(c, &o2, res);
-      c->in_halo_rerun = false;
-      return rr;
+      SetView v2 = v;
+      v2.halo_rerun = true;
+      return sweep_goose_t<T>(c, &o2, v2, res);
     }
     halo_learn(c, h, Lk, o->reference_quirk_L_index);
   }
@@ -2575,7 +2619,7 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_result* 
   res->target_best_c = best_c;
   res->target_lcb = best_c ? best_lcb : INFINITY;
   res->choose_safe_min = best_c ? (res->safe_min_lcb <= res->target_lcb) : 1;   // test/test_GoOSE.py:158
-  if (gb_of(c) && best_c) {
+  if (gb_of<T>(c, v) && best_c) {
     // choices among the winners (the short tail judged the targets' one on the device): which constraint's target, and safe
     // minimum against target (min_safe_lcb <= target_lcb) -- lcb_0 is known to +- arg_d
     long long near = 0;
@@ -2610,43 +2654,18 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_result* 
     SBO_HIP(hipEventRecord(c->ev[4], c->stream));
     SBO_HIP(hipEventSynchronize(c->ev[4]));
   }
-  float t01 = 0, t12 = 0, t23 = 0, t34 = 0, t04 = 0;
-  SBO_HIP(hipEventElapsedTime(&t01, c->ev[0], c->ev[1]));
-  if (c->phase_events) {
-    SBO_HIP(hipEventElapsedTime(&t12, c->ev[1], c->ev[2]));
-    SBO_HIP(hipEventElapsedTime(&t23, c->ev[2], c->ev[3]));
-    SBO_HIP(hipEventElapsedTime(&t34, c->ev[3], c->ev[4]));
-  }
-  SBO_HIP(hipEventElapsedTime(&t04, c->ev[0], c->ev[4]));
-  memset(&c->prof, 0, sizeof(c->prof));
-  if ((rc = list_index_profile(c))) return rc;
-  c->prof.posterior_ms = t01;
-  c->prof.classify_ms = t12;
-  c->prof.expander_ms = t23;
-  c->prof.argreduce_ms = t34;
-  c->prof.total_ms = t04;
-  c->prof.candidates = n;
-  c->prof.posterior_launches = (!reuse && n > 0) ? 1 : 0;
-  const double nn = c->mc.n, dd = c->mc.d;
-  c->prof.posterior_flops = reuse ? 0.0 : q * (nn * nn + (2 * dd + 10) * nn) * (double)n;
-  sweep_times(c);
-  return SBO_OK;
+  return sweep_profile(c, kGoose, reuse);
 }
 
 // Trust-region acquisition (models/GP_TR.py:43-51): argmin lcb_0 over S and the ball
 template <typename T>
-static int sweep_tr_t(sbo_ctx* c, const sbo_sweep_opts* o, const double* x0, double r, sbo_tr_result* res) {
+static int sweep_tr_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, const double* x0, double r, sbo_tr_result* res) {
   const long long n = c->cs.n_local;
   int rc;
-  SBO_HIP(hipEventRecord(c->ev[0], c->stream));
-  const bool reuse = o->posterior_ready && c->posterior_valid;
-  const PostRequest req = sweep_request(c, o->b, !reuse);
-  if ((rc = sweep_masks(c, req))) return rc;
+  bool reuse;
   PostOutcome post;
-  if (!reuse && (rc = posterior_enqueue(c, req, &post))) return rc;
-  SBO_HIP(k1_stop(c, post));
-  if (!reuse && !c->rc_active && (rc = guard_audit_enqueue(c, post))) return rc;
-  if ((rc = sweep_common_front<T>(c, o, post))) return rc;
+  if ((rc = sweep_open<T>(c, o, v, kTr, &reuse, post))) return rc;
+  if ((rc = sweep_common_front<T>(c, o, v, post))) return rc;
   SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
   const int nb = reduce_blocks(c);
   double* dev_x0 = (double*)c->lane[0].scal.p + 256;
@@ -2658,10 +2677,10 @@ static int sweep_tr_t(sbo_ctx* c, const sbo_sweep_opts* o, const double* x0, dou
       default: hipLaunchKernelGGL((k_ball_mask<8>), dim3(nb), dim3(256), 0, c->stream, c->cs, n, (const uint8_t*)c->maskS.p, (const double*)dev_x0, r, (uint8_t*)c->maskM.p); break;
     }
     hipLaunchKernelGGL((k_arg_masked<T, false, ValLcb<T>>), dim3(nb), dim3(256), 0, c->stream,
-                       ValLcb<T>{(const T*)c->mean.p, (const T*)c->var.p, (T)o->b, 0.0, 0.0}, (const uint8_t*)c->maskM.p, n,
-                       (long long)c->cs.first, (Best*)c->partial.p, gb_of(c));
+                       ValLcb<T>{(const T*)v.mean->p, (const T*)v.var->p, (T)o->b, 0.0, 0.0}, (const uint8_t*)c->maskM.p, n,
+                       (long long)c->cs.first, (Best*)c->partial.p, gb_of<T>(c, v));
   }
-  hipLaunchKernelGGL((k_arg_final<false>), dim3(1), dim3(256), 0, c->stream, (const Best*)c->partial.p, n > 0 ? nb : 0, sc, 0, &sc->count_M, gb_of(c) ? 1 : 0);
+  hipLaunchKernelGGL((k_arg_final<false>), dim3(1), dim3(256), 0, c->stream, (const Best*)c->partial.p, n > 0 ? nb : 0, sc, 0, &sc->count_M, gb_of<T>(c, v) ? 1 : 0);
   SBO_HIP(hipGetLastError());
   SweepScalars h;
   bool is_max[kArgSlots];
@@ -2674,18 +2693,7 @@ static int sweep_tr_t(sbo_ctx* c, const sbo_sweep_opts* o, const double* x0, dou
   SBO_HIP(hipEventSynchronize(c->ev[2]));
   c->masks_valid = true;
   c->last_sweep = 3;
-  float t01 = 0, t12 = 0, t02 = 0;
-  SBO_HIP(hipEventElapsedTime(&t01, c->ev[0], c->ev[1]));
-  SBO_HIP(hipEventElapsedTime(&t12, c->ev[1], c->ev[2]));
-  SBO_HIP(hipEventElapsedTime(&t02, c->ev[0], c->ev[2]));
-  memset(&c->prof, 0, sizeof(c->prof));
-  c->prof.posterior_ms = t01;
-  c->prof.classify_ms = t12;
-  c->prof.total_ms = t02;
-  c->prof.candidates = n;
-  c->prof.posterior_launches = (!reuse && n > 0) ? 1 : 0;
-  const double nn = c->mc.n, dd = c->mc.d;
-  c->prof.posterior_flops = reuse ? 0.0 : c->mc.q * (nn * nn + (2 * dd + 10) * nn) * (double)n;
+  if ((rc = sweep_profile(c, kTr, reuse))) return rc;
   memset(res, 0, sizeof(*res));
   res->guard_band = h.n_guard;
   c->guard_first = h.n_guard;
@@ -2733,6 +2741,38 @@ int robust_argmin(sbo_ctx* c, const double* f, const double* fb, const uint8_t* 
   return SBO_OK;
 }
 
+// ---- what the three sweep entry points share -----------------------------------------------------------------------------
+// the argument checks (`result`: nullptr when any pointer argument of the call is; `r`: the trust region's radius, or nullptr)
+static int sweep_args(sbo_ctx* c, const sbo_sweep_opts* opts, const void* result, const double* r) {
+  if (!c || !opts || !result) return fail(SBO_E_INVALID, "NULL argument");
+  if (!c->has_model) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
+  if (!c->has_cand) return fail(SBO_E_NO_CANDIDATES, "no candidates resident");
+  if (c->cs.d != c->mc.d) return fail(SBO_E_INVALID, "ERROR W and X_norm dimension should be same");
+  if (r && !(*r >= 0.0)) return fail(SBO_E_INVALID, "trust-region radius must be >= 0");
+  if (!(opts->b >= 0.0) || !std::isfinite(opts->b)) return fail(SBO_E_INVALID, "confidence multiplier b must be finite and >= 0");
+  SBO_HIP(hipSetDevice(c->device));
+  return SBO_OK;
+}
+// fp32 models with an fp64 twin: the recheck; every other: the plain sweep in the model's precision (`plain` / `recheck` take a
+// float or a double to say which), and behind an approximating fp64 posterior (K1b / K1i / K1t) whose band left decisions of that
+// pass open, the guard recheck: re-evaluate exactly, decide again
+template <typename Res, typename Plain, typename Recheck>
+static int sweep_dispatch(sbo_ctx* c, Res* result, bool drain, Plain plain, Recheck recheck) {
+  const auto done = [](int rc) { return rc == SBO_OK || rc == SBO_E_EMPTY_SAFE_SET; };
+  const bool f64 = c->dtype == SBO_F64;
+  c->guard_first = 0;
+  int rc;
+  if (!f64 && c->fp64_recheck && c->shadow && c->shadow->has_model) rc = recheck(0.0f);
+  else rc = f64 ? plain(0.0) : plain(0.0f);
+  if (done(rc) && f64 && resident_band(c) && (c->guard_first > 0 || c->guard_band == 2)) {
+    const long long first = c->guard_first;
+    rc = recheck(0.0);
+    if (done(rc)) result->guard_band = first;
+  }
+  if (drain && !done(rc)) drain_streams(c);   // (kernels of the failed call may still sit on the side streams)
+  return rc;
+}
+
 }  // namespace sbo
 
 using namespace sbo;
@@ -2740,68 +2780,27 @@ using namespace sbo;
 extern "C" {
 
 int sbo_sweep_safeopt(sbo_ctx* c, const sbo_sweep_opts* opts, sbo_safeopt_result* result) {
-  if (!c || !opts || !result) return fail(SBO_E_INVALID, "NULL argument");
-  if (!c->has_model) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
-  if (!c->has_cand) return fail(SBO_E_NO_CANDIDATES, "no candidates resident");
-  if (c->cs.d != c->mc.d) return fail(SBO_E_INVALID, "ERROR W and X_norm dimension should be same");
-  SBO_HIP(hipSetDevice(c->device));
-  if (!(opts->b >= 0.0) || !std::isfinite(opts->b)) return fail(SBO_E_INVALID, "confidence multiplier b must be finite and >= 0");
-  int rc;
-  c->guard_first = 0;
-  if (c->dtype == SBO_F32 && c->fp64_recheck && c->shadow && c->shadow->has_model)
-    rc = sweep_safeopt_recheck<float>(c, opts, result);
-  else
-    rc = c->dtype == SBO_F64 ? sweep_safeopt_t<double>(c, opts, result) : sweep_safeopt_t<float>(c, opts, result);
-  // an approximating posterior (K1b / K1t) whose band left decisions of that pass open: re-evaluate exactly, decide again
-  if ((rc == SBO_OK || rc == SBO_E_EMPTY_SAFE_SET) && c->dtype == SBO_F64 && gb_of(c) && (c->guard_first > 0 || c->guard_band == 2)) {
-    const long long first = c->guard_first;
-    rc = sweep_safeopt_recheck<double>(c, opts, result);
-    if (rc == SBO_OK || rc == SBO_E_EMPTY_SAFE_SET) result->guard_band = first;
-  }
-  if (rc != SBO_OK && rc != SBO_E_EMPTY_SAFE_SET) drain_streams(c);   // (kernels of the failed call may still sit on the side streams)
-  return rc;
+  const int rc = sweep_args(c, opts, result, nullptr);
+  if (rc) return rc;
+  return sweep_dispatch(
+      c, result, true, [&](auto t) { return sweep_safeopt_t<decltype(t)>(c, opts, SetView(c), result); },
+      [&](auto t) { return sweep_safeopt_recheck<decltype(t)>(c, opts, result); });
 }
 
 int sbo_sweep_goose(sbo_ctx* c, const sbo_sweep_opts* opts, sbo_goose_result* result) {
-  if (!c || !opts || !result) return fail(SBO_E_INVALID, "NULL argument");
-  if (!c->has_model) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
-  if (!c->has_cand) return fail(SBO_E_NO_CANDIDATES, "no candidates resident");
-  if (c->cs.d != c->mc.d) return fail(SBO_E_INVALID, "ERROR W and X_norm dimension should be same");
-  SBO_HIP(hipSetDevice(c->device));
-  if (!(opts->b >= 0.0) || !std::isfinite(opts->b)) return fail(SBO_E_INVALID, "confidence multiplier b must be finite and >= 0");
-  int rc;
-  c->guard_first = 0;
-  if (c->dtype == SBO_F32 && c->fp64_recheck && c->shadow && c->shadow->has_model)
-    rc = sweep_goose_recheck<float>(c, opts, result);
-  else
-    rc = c->dtype == SBO_F64 ? sweep_goose_t<double>(c, opts, result) : sweep_goose_t<float>(c, opts, result);
-  if ((rc == SBO_OK || rc == SBO_E_EMPTY_SAFE_SET) && c->dtype == SBO_F64 && gb_of(c) && (c->guard_first > 0 || c->guard_band == 2)) {
-    const long long first = c->guard_first;
-    rc = sweep_goose_recheck<double>(c, opts, result);
-    if (rc == SBO_OK || rc == SBO_E_EMPTY_SAFE_SET) result->guard_band = first;
-  }
-  if (rc != SBO_OK && rc != SBO_E_EMPTY_SAFE_SET) drain_streams(c);
-  return rc;
+  const int rc = sweep_args(c, opts, result, nullptr);
+  if (rc) return rc;
+  return sweep_dispatch(
+      c, result, true, [&](auto t) { return sweep_goose_t<decltype(t)>(c, opts, SetView(c), result); },
+      [&](auto t) { return sweep_goose_recheck<decltype(t)>(c, opts, result); });
 }
 
 int sbo_sweep_tr(sbo_ctx* c, const sbo_sweep_opts* opts, const double* x_0, double r, sbo_tr_result* result) {
-  if (!c || !opts || !x_0 || !result) return fail(SBO_E_INVALID, "NULL argument");
-  if (!c->has_model) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
-  if (!c->has_cand) return fail(SBO_E_NO_CANDIDATES, "no candidates resident");
-  if (c->cs.d != c->mc.d) return fail(SBO_E_INVALID, "ERROR W and X_norm dimension should be same");
-  if (!(r >= 0.0)) return fail(SBO_E_INVALID, "trust-region radius must be >= 0");
-  if (!(opts->b >= 0.0) || !std::isfinite(opts->b)) return fail(SBO_E_INVALID, "confidence multiplier b must be finite and >= 0");
-  SBO_HIP(hipSetDevice(c->device));
-  c->guard_first = 0;
-  if (c->dtype == SBO_F32 && c->fp64_recheck && c->shadow && c->shadow->has_model)
-    return sweep_tr_recheck<float>(c, opts, x_0, r, result);
-  int rc = c->dtype == SBO_F64 ? sweep_tr_t<double>(c, opts, x_0, r, result) : sweep_tr_t<float>(c, opts, x_0, r, result);
-  if (rc == SBO_OK && c->dtype == SBO_F64 && gb_of(c) && (c->guard_first > 0 || c->guard_band == 2)) {
-    const long long first = c->guard_first;
-    rc = sweep_tr_recheck<double>(c, opts, x_0, r, result);
-    if (rc == SBO_OK) result->guard_band = first;
-  }
-  return rc;
+  const int rc = sweep_args(c, opts, x_0 ? result : nullptr, &r);
+  if (rc) return rc;
+  return sweep_dispatch(
+      c, result, false, [&](auto t) { return sweep_tr_t<decltype(t)>(c, opts, SetView(c), x_0, r, result); },
+      [&](auto t) { return sweep_tr_recheck<decltype(t)>(c, opts, x_0, r, result); });
 }
 
 // explore_safeset(target) with a caller's own target (models/GoOSE.py:116-119): argmin over the safe set S_t of the last sweep of

@@ -1024,7 +1024,7 @@ static void col_expand(sbo_ctx* c, const DevBuf& words, uint8_t* out) {
 // merged by every workgroup of k_col_min<0>, M and its arg-max, beside the chain's verdict kernels; the main stream then waits for the
 // chain's join event, k_col_min<1> takes the arg-max over the finished G_1 and k_col_finals merges both.  What the set phase adds to
 // K1 is the join, the G part and the finals.
-static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const PostOutcome& post, SweepScalars& h, unsigned long long* Lk) {
+static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, const PostOutcome& post, SweepScalars& h, unsigned long long* Lk) {
   const long long n = c->cs.n_local;
   const int q = c->mc.q;                 // == 2
   int rc;
@@ -1095,7 +1095,7 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const PostOutcome&
   mg.slots = cb.slots;
   mg.sc = sc;
   mg.Lmax = (unsigned long long*)c->Lmax.p;
-  mg.gb = gb_of(c);
+  mg.gb = gb_of<double>(c, v);
   mg.b = o->b;
   const int ncoarse = gm.CNB;
   const int nfine = (int)std::max<long long>(1, std::min<long long>(((long long)gm.NS * (gm.W / 64) + 3) / 4, (long long)c->n_cu * 5));
@@ -1114,31 +1114,28 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const PostOutcome&
   j.sc2 = sc2;
   j.olmin = (const unsigned long long*)c->cpart.p + (size_t)1 * c->cpart_cap + post.fuse_rows / 2;
   j.Sw = cb.Sw;
-  j.mean0 = (const double*)c->mean.p;
-  j.var0 = (const double*)c->var.p;
+  j.mean0 = (const double*)v.mean->p;
+  j.var0 = (const double*)v.var->p;
   j.b = o->b;
   j.Mw = (unsigned long long*)c->cbM.p;
   j.Gw = (const unsigned long long*)c->cbG.p;
   j.partial = reg0;
   j.gpartial = reg1;
-  j.gb = gb_of(c);
+  j.gb = gb_of<double>(c, v);
   if (overlap) SBO_HIP(hipStreamWaitEvent(xs, c->ev_col[2], 0));
   hipLaunchKernelGGL(k_col_min<0>, dim3((unsigned)nb), dim3(256), 0, xs, j);
   ColVerdict cv;
   memset(&cv, 0, sizeof(cv));
-  cv.mean_c = (const double*)c->mean.p + (size_t)n;
-  cv.var_c = (const double*)c->var.p + (size_t)n;
-  cv.var0 = (const double*)c->var.p;
+  cv.mean_c = (const double*)v.mean->p + (size_t)n;
+  cv.var_c = (const double*)v.var->p + (size_t)n;
+  cv.var0 = (const double*)v.var->p;
   cv.b = o->b;
   cv.Lkeys = (const unsigned long long*)c->Lmax.p;
   cv.lidx = lidx;
   double xscale = 0.0;
   for (int a = 0; a < 2; ++a) xscale = std::max(xscale, std::max(std::fabs(c->cs.lo[a]), std::fabs(c->cs.hi[a])));
   cv.xscale = xscale;
-  if (gb_of(c)) {
-    cv.rx.gb_c = 1;
-    cv.rx.gb_l = c->gb_slow ? -1 : lidx;
-  }
+  rx_band<double>(c, v, 1, lidx, cv.rx);
   // (the verdict kernels do not read var_0 -- overlapped, the objective's launch may still be writing it: the arg-max over G_1 is the
   // job of k_col_min<1>, behind the join)
   // (grids sized to be resident at once: the waves loop over the units of the tiles with a safe candidate)
@@ -1159,7 +1156,7 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const PostOutcome&
   const int nbg = nb;
   hipLaunchKernelGGL(k_col_min<1>, dim3((unsigned)nbg), dim3(256), 0, xs, j);
   hipExtLaunchKernelGGL(k_col_finals, dim3(nb > 2048 ? kColFinParts : 1, 2), dim3(256), 0, xs, nullptr, c->ev[4], 0, (const Best*)reg0, nb, (const Best*)reg1,
-                        nbg, sc, (const ColScal2*)sc2, fin, tickets, c->h_back, (const unsigned long long*)c->Lmax.p, gb_of(c) ? 1 : 0, cb.slots);
+                        nbg, sc, (const ColScal2*)sc2, fin, tickets, c->h_back, (const unsigned long long*)c->Lmax.p, gb_of<double>(c, v) ? 1 : 0, cb.slots);
   c->slots_clean = true;
   SBO_HIP(hipGetLastError());
   bool is_max[kArgSlots];
@@ -1172,13 +1169,13 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const PostOutcome&
     // masks, then the expanders' arg-max and the finals once more (slot 0 is where that merge expects it)
     col_expand(c, c->cbU, (uint8_t*)c->maskU.p);
     col_expand(c, c->cbG, (uint8_t*)c->maskG.p);
-    if ((rc = launch_exact_d<double>(c, ln, o, 1, lidx, (uint8_t*)c->maskG.p))) return rc;
+    if ((rc = launch_exact_d<double>(c, ln, o, v, 1, lidx, (uint8_t*)c->maskG.p))) return rc;
     hipLaunchKernelGGL((k_arg_masked_multi<double, true, ValArray<double>>), dim3((unsigned)nb, 1u), dim3(256), 0, c->stream,
-                       ValArray<double>{(const double*)c->var.p, 0.0}, (const uint8_t*)nullptr, (const uint8_t*)c->maskG.p, n, (long long)c->cs.first, pbase,
-                       pstride, 1, gb_of(c));
+                       ValArray<double>{(const double*)v.var->p, 0.0}, (const uint8_t*)nullptr, (const uint8_t*)c->maskG.p, n, (long long)c->cs.first, pbase,
+                       pstride, 1, gb_of<double>(c, v));
     hipLaunchKernelGGL(k_sweep_clear_slot, dim3(1), dim3(1), 0, c->stream, sc, 1);
     hipExtLaunchKernelGGL(k_sweep_finals<true>, dim3(2), dim3(256), 0, c->stream, nullptr, c->ev[4], 0, (const unsigned char*)pbase, pstride, nb, sc,
-                          (const SweepScalars*)nullptr, c->h_back, (const unsigned long long*)c->Lmax.p, gb_of(c) ? 1 : 0);
+                          (const SweepScalars*)nullptr, c->h_back, (const unsigned long long*)c->Lmax.p, gb_of<double>(c, v) ? 1 : 0);
     SBO_HIP(hipGetLastError());
     if ((rc = sweep_exchange_back(c, h, is_max, Lk, c->ev[4], true))) return rc;
     c->col_G_bytes = true;

@@ -23,9 +23,6 @@
 // values replace the approximate ones IN PLACE, the Lipschitz keys are recomputed exactly, and the set phase runs again.
 #pragma once
 
-struct RcBand {
-  double dm[kMaxQ], dv[kMaxQ];
-};
 struct RcScal {                         // head of rc_list (256 bytes): this struct, the deferral counter at byte 32, G keys at 64
   unsigned long long ulo_key, uhi_key, vmax_key;
   long long count;
@@ -322,7 +319,7 @@ static int rc_lipschitz64(sbo_ctx* c, const sbo_ctx* s) {
   return SBO_OK;
 }
 
-// the bands of the intervals: the fp32 contract (1e-4 normalised), or the plan's guard band read back from the device
+// the bands of the intervals (and of SetView::rc_band): the fp32 contract (1e-4 normalised), or the plan's guard band read back from the device
 static int rc_bands(sbo_ctx* c, bool guard, RcBand& bd) {
   memset(&bd, 0, sizeof(bd));
   const int q = c->mc.q;
@@ -353,7 +350,7 @@ static int sweep_safeopt_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeop
   const long long n = c->cs.n_local;
   const int q = c->mc.q;
   int rc;
-  if (!kGuard && n == 0 && !multi_rank(c)) return sweep_safeopt_t<float>(c, o, res);
+  if (!kGuard && n == 0 && !multi_rank(c)) return sweep_safeopt_t<float>(c, o, SetView(c), res);
   SBO_HIP(hipEventRecord(c->ev_join[0], c->stream));
   // (guard: the posterior is resident -- unless the first pass was a lean sweep, which left part of it unwritten: K1 once more, in full)
   const bool reuse = (kGuard && c->posterior_valid) || (o->posterior_ready && c->posterior_valid && (o->lean || !c->post_l0_missing));
@@ -405,40 +402,22 @@ static int sweep_safeopt_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeop
   if (q > 1 && (rc = rc_lipschitz64(c, kGuard ? c : c->shadow))) return rc;
   SBO_HIP(hipEventRecord(c->ev_join[2], c->stream));
   // the set phase in fp64 arithmetic on the refined posterior (fp32: the widened copy -- the fp32 arrays stay what
-  // sbo_posterior_get returns); repeated while verdicts are deferred
-  const DevBuf keep_m = c->mean, keep_v = c->var;
-  const int keep_dtype = c->dtype;
-  const bool keep_valid = c->posterior_valid;
-  sbo_sweep_opts o2 = *o;
-  o2.posterior_ready = 1;
-  float set_extra = 0.0f;
+  // sbo_posterior_get returns; guard: the band stays in force for unrefined entries, L is exact now); repeated while verdicts are deferred
+  SetView view(kGuard ? c->mean : c->rc_mean, kGuard ? c->var : c->rc_var, kGuard ? SetBand::values : SetBand::plan);
+  if (q > 1) {
+    view.refined = (const uint8_t*)c->rc_refined.p;
+    view.rc_band = &bd;
+    view.rc_list = list;
+    view.rc_count = count2;
+  }
   int passes = 0;
   for (;; ++passes) {
     SBO_HIP(hipMemsetAsync(count2, 0, 8 + sizeof(unsigned long long) * kMaxQ + 24, c->stream));     // deferral counter + G keys
-    if (!kGuard) {
-      c->mean = c->rc_mean;
-      c->var = c->rc_var;
-    }
-    c->dtype = SBO_F64;
-    c->posterior_valid = true;
-    c->rc_active = q > 1;
-    c->gb_slow = kGuard;                   // (guard: the band stays in force for unrefined entries; L is exact now)
-    rc = sweep_safeopt_t<double>(c, &o2, res);
-    c->rc_active = false;
-    c->gb_slow = false;
-    if (!kGuard) {
-      c->rc_mean = c->mean;
-      c->rc_var = c->var;
-      c->mean = keep_m;
-      c->var = keep_v;
-    }
-    c->dtype = keep_dtype;
-    c->posterior_valid = keep_valid || !reuse;
+    rc = sweep_safeopt_t<double>(c, o, view, res);
     if (rc != SBO_OK || q == 1) break;
-    if (passes > 0) set_extra += (float)c->prof.total_ms;
     // Expander's arg-max over every G_c must not hinge on an unrefined variance
     const uint8_t* G = (const uint8_t*)c->maskG.p;
-    const double* var0 = kGuard ? (const double*)c->var.p : (const double*)c->rc_var.p;
+    const double* var0 = (const double*)view.var->p;
     hipLaunchKernelGGL(k_rc_gmax, dim3(nbk, (unsigned)(q - 1)), dim3(256), 0, c->stream, G, var0, (const uint8_t*)c->rc_refined.p, n, bd.dv[0],
                        gkeys);
     if ((rc = comm_allreduce_max_u64(c, gkeys, q - 1))) return rc;        // (the expanders' arg-max is over all ranks)
@@ -483,7 +462,6 @@ static int sweep_safeopt_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeop
     const double nn = c->mc.n, dd = c->mc.d;
     c->prof.posterior_flops = reuse ? 0.0 : q * (nn * nn + (2 * dd + 10) * nn) * (double)n;
   }
-  (void)set_extra;
   return rc;
 }
 
@@ -541,33 +519,11 @@ __global__ void k_rc_ball(const CandSpec cs, long long n, const double* __restri
   }
 }
 
-struct RcView {                        // the context looks at the refined fp64 posterior while the scope lives: the widened copy
-  sbo_ctx* c;                          // of an fp32 posterior, or (guard) the fp64 posterior itself, refined in place
-  bool guard;
-  DevBuf keep_m, keep_v;
-  int keep_dtype;
-  bool keep_valid;
-  RcView(sbo_ctx* c_, bool guard_) : c(c_), guard(guard_), keep_m(c_->mean), keep_v(c_->var), keep_dtype(c_->dtype), keep_valid(c_->posterior_valid) {
-    if (!guard) {
-      c->mean = c->rc_mean;
-      c->var = c->rc_var;
-    }
-    c->dtype = SBO_F64;
-    c->posterior_valid = true;
-    c->gb_off = true;                  // (every value that enters a decision is exact by now: no band)
-  }
-  ~RcView() {
-    if (!guard) {
-      c->rc_mean = c->mean;
-      c->rc_var = c->var;
-      c->mean = keep_m;
-      c->var = keep_v;
-    }
-    c->dtype = keep_dtype;
-    c->posterior_valid = keep_valid;
-    c->gb_off = false;
-  }
-};
+// what the GoOSE / trust-region rechecks hand their set phase: the widened copy of an fp32 posterior, or (guard) the fp64 posterior
+// itself, refined in place; every value that enters a decision is exact by then: no band
+static SetView rc_exact_view(const sbo_ctx* c, bool guard) {
+  return SetView(guard ? c->mean : c->rc_mean, guard ? c->var : c->rc_var, SetBand::none);
+}
 
 // front end shared by the GoOSE / trust-region rechecks: posterior, (fp32) widened copy, first refinement list (q > 1: every
 // possibly-safe or undecided candidate), fp64 Lipschitz keys.  Leaves the list buffers ready for further rounds.
@@ -654,7 +610,7 @@ static int sweep_goose_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_re
   constexpr bool kGuard = std::is_same<TP, double>::value;
   const long long n = c->cs.n_local;
   const int q = c->mc.q;
-  if (n == 0) return kGuard ? sweep_goose_t<double>(c, o, res) : sweep_goose_t<float>(c, o, res);
+  if (n == 0) return kGuard ? sweep_goose_t<double>(c, o, SetView(c), res) : sweep_goose_t<float>(c, o, SetView(c), res);
   int rc;
   SBO_HIP(hipEventRecord(c->ev_join[0], c->stream));
   const bool reuse = kGuard || (o->posterior_ready && c->posterior_valid);
@@ -662,23 +618,19 @@ static int sweep_goose_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_re
   long long total = 0, more = 0;
   if ((rc = rc_front_all<TP>(c, o, bd, &total))) return rc;
   SBO_HIP(hipEventRecord(c->ev_join[1], c->stream));
+  const SetView view = rc_exact_view(c, kGuard);
   sbo_sweep_opts o2 = *o;
-  o2.posterior_ready = 1;
   o2.want_masks = 1;
   int passes = 0;
   if (q == 1) {
     // arg-min lcb_0 over every candidate: its contenders, then one fp64 set phase
     if ((rc = rc_argmin_contenders(c, o, bd, nullptr, 0, &more, kGuard))) return rc;
     total += more;
-    RcView view(c, kGuard);
-    rc = sweep_goose_t<double>(c, &o2, res);
+    rc = sweep_goose_t<double>(c, &o2, view, res);
     passes = 1;
   } else {
     for (int pass = 0; pass < 3; ++pass) {
-      {
-        RcView view(c, kGuard);
-        rc = sweep_goose_t<double>(c, &o2, res);
-      }
+      rc = sweep_goose_t<double>(c, &o2, view, res);
       ++passes;
       if (rc != SBO_OK) break;
       // the target: arg-min lcb_0 over the union of the optimistic sets (members are unsafe candidates, so far unrefined values)
@@ -694,7 +646,6 @@ static int sweep_goose_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_re
     res->guard_passes = passes;
     c->prof.guard_ms = t01;
   } else {
-    c->posterior_valid = c->posterior_valid || !reuse;
     c->prof.fp64_rechecks = total;
     c->prof.posterior_launches = reuse ? 0 : 1;
     c->prof.recheck_ms = t01;
@@ -707,14 +658,11 @@ static int sweep_tr_recheck(sbo_ctx* c, const sbo_sweep_opts* o, const double* x
   constexpr bool kGuard = std::is_same<TP, double>::value;
   const long long n = c->cs.n_local;
   const int q = c->mc.q;
-  if (n == 0) return kGuard ? sweep_tr_t<double>(c, o, x0, r, res) : sweep_tr_t<float>(c, o, x0, r, res);
+  if (n == 0) return kGuard ? sweep_tr_t<double>(c, o, SetView(c), x0, r, res) : sweep_tr_t<float>(c, o, SetView(c), x0, r, res);
   int rc;
-  const bool reuse = kGuard || (o->posterior_ready && c->posterior_valid);
   RcBand bd;
   long long total = 0, more = 0;
   if ((rc = rc_front_all<TP>(c, o, bd, &total))) return rc;
-  sbo_sweep_opts o2 = *o;
-  o2.posterior_ready = 1;
   if (q == 1) {
     // arg-min lcb_0 over the ball: the ball as a mask (exact geometry), then the contenders inside it
     if ((rc = ensure(c->maskM, (size_t)n))) return rc;
@@ -729,15 +677,11 @@ static int sweep_tr_recheck(sbo_ctx* c, const sbo_sweep_opts* o, const double* x
     if ((rc = rc_argmin_contenders(c, o, bd, (const uint8_t*)c->maskM.p, 1, &more, kGuard))) return rc;
     total += more;
   }
-  {
-    RcView view(c, kGuard);
-    rc = sweep_tr_t<double>(c, &o2, x0, r, res);
-  }
+  rc = sweep_tr_t<double>(c, o, rc_exact_view(c, kGuard), x0, r, res);
   if (kGuard) {
     res->guard_rechecks = total;
     res->guard_passes = 1;
   } else {
-    c->posterior_valid = c->posterior_valid || !reuse;
     c->prof.fp64_rechecks = total;
   }
   return rc;
