@@ -444,6 +444,54 @@ typedef struct sbo_refine_result {
 int sbo_refine(sbo_ctx* ctx, const sbo_refine_opts* opts, int64_t n_seeds, const double* seeds, double* x_out, double* value_out,
                int32_t* status_out, sbo_refine_result* result);
 
+/* ---- the set-valued steps refined off the grid ----------------------------- */
+/* objective kind of sbo_refine_sets beside SBO_MEAN .. SBO_VAR: the squared distance ||x - target||^2, minimised (the value
+ * reported is the Euclidean distance) */
+#define SBO_REFINE_DIST 4
+
+typedef struct sbo_refine_sets_opts {
+  double   b;                      /* confidence multiplier, as sbo_sweep_opts.b                                                 */
+  int32_t  pair;                   /* 0: the variable is one point x; 1: a pair (x, x'), which needs 2 d <= SBO_MAX_D            */
+  int32_t  objective;              /* output index o in [0, q) (unused by SBO_REFINE_DIST)                                       */
+  int32_t  kind;                   /* SBO_MEAN / SBO_UCB / SBO_LCB / SBO_VAR of output o, or SBO_REFINE_DIST                     */
+  int32_t  objective_point;        /* 0: the bound is taken at x; 1: at x' (pair mode)                                           */
+  int32_t  maximize;               /* 0: minimise, 1: maximise (SBO_REFINE_DIST: 0)                                              */
+  uint32_t safe_mask;              /* bit c (1 <= c < q): lcb_c(x) >= 0                                                          */
+  uint32_t unsafe_mask;            /* bit c (1 <= c < q): lcb_c(x') <= 0 -- x' in the sweeps' U when every constraint is set; pair mode */
+  int32_t  use_level;              /* 1: also lcb_{level_output}(x) <= level (M_t: output 0, level u*)                           */
+  int32_t  level_output;
+  int32_t  use_link;               /* 1: also ucb_{link_output}(x) - L ||x - x' + 1e-8||_2 >= 0 (1e-8 added per component); pair mode */
+  int32_t  link_output;            /* a constraint output in [1, q)                                                              */
+  int32_t  use_ball;               /* 1: also ||x - x_0||_2 <= r, as sbo_refine_opts                                             */
+  int32_t  max_eval;               /* as sbo_refine_opts; a pair costs two evaluations, and the count is in evaluations of one point */
+  int32_t  reserved;
+  double   level, L;               /* finite; L >= 0 is the caller's Lipschitz constant (the one the sweep used: sbo_*_result.L)  */
+  double   lo[SBO_MAX_D], hi[SBO_MAX_D];   /* box of x and of x'                                                              */
+  double   x_0[SBO_MAX_D], r;
+  double   target[SBO_MAX_D];      /* SBO_REFINE_DIST: the point t                                                               */
+  double   tol;                    /* as sbo_refine_opts                                                                         */
+} sbo_refine_sets_opts;
+
+typedef struct sbo_refine_sets_result {
+  int64_t best;                    /* as sbo_refine_result                                                                       */
+  double  best_x[SBO_MAX_D], best_xp[SBO_MAX_D], best_value;   /* best_xp: x' of the best pair (zeros in single mode)            */
+  int64_t evaluations;             /* posterior + gradient evaluations of one point, summed over seeds                           */
+  int32_t converged;
+  int32_t reserved;
+} sbo_refine_sets_result;
+
+/* sbo_refine's solver on the problems of the set-valued steps (models/SafeOpt.py:53-124, models/GoOSE.py:80-119): each seed
+ * seeds[n_seeds][d] -- in pair mode with its partner seeds_p[n_seeds][d] -- moves to a local optimum of the objective over
+ * {x (and x') in the box; lcb_c(x) >= 0, c in safe_mask; lcb_c(x') <= 0, c in unsafe_mask; lcb_o(x) <= level; the link; the ball}.
+ * The exact check is sbo_refine's: seeds and iterates are evaluated by the list evaluator (both points of a pair) and every term is
+ * judged there with the sweeps' closed predicates; a returned x (pair) satisfies every term and its exact objective is no worse
+ * than its seed's, the seed itself at worst.  A seed that fails a term is SBO_REFINE_INFEASIBLE_SEED, a feasible seed with a term of
+ * exactly zero slack SBO_REFINE_ON_BOUNDARY; both come back unchanged.  x_out[n_seeds][d], xp_out[n_seeds][d] (pair mode),
+ * value_out[n_seeds] and status_out[n_seeds] may be NULL; seeds_p is read in pair mode only.  Pair mode with 2 d > SBO_MAX_D:
+ * SBO_E_UNSUPPORTED.  Otherwise as sbo_refine: deterministic, fp64 models only, no collectives, nothing resident is touched. */
+int sbo_refine_sets(sbo_ctx* ctx, const sbo_refine_sets_opts* opts, int64_t n_seeds, const double* seeds, const double* seeds_p,
+                    double* x_out, double* xp_out, double* value_out, int32_t* status_out, sbo_refine_sets_result* result);
+
 /* ---- plant evaluation ------------------------------------------ */
 /* The reference's William-Otto reactor (problems/WilliamOttoReactor_Problem.py:19-93), noise-free, for n input rows
  * u[n, 2] = (Fb, Tr): out[n, 3] = (get_objective, get_constraint1, get_constraint2), each the steady state of the six
@@ -488,7 +536,7 @@ int sbo_profile_get(sbo_ctx* ctx, sbo_profile* out);
  *   "guard_audit_scale_ppm" test hook: the audit compares against the band x value / 1e6 (default 1000000); setting it clears the counts
  *   "guard_audit_every" one sweep in this many carries an audit (default 16; the first sweep after setting it does).  An audit shares
  *                      the card with the sweep it follows (~35 us of config H's set phase at 1024 samples, n = 512): 1 audits every sweep
- *   "refine_lds"       1 (default): sbo_refine stages the used outputs' triangles of M in LDS when they fit 144 KiB; 0: it always streams
+ *   "refine_lds"       1 (default): sbo_refine / sbo_refine_sets stage the used outputs' triangles of M in LDS when they fit 144 KiB; 0: it always streams
  *                      M's rows from L2 (the tier of larger models; results are bit-identical either way)
  *   "list_index"       explicit candidate lists: expander sets (SafeOpt, GoOSE's source filter) and GoOSE's coverage search on a spatial
  *                      index of the list (Morton order, boxes of the U members; verdicts identical to the exhaustive ones).  -1 (default):

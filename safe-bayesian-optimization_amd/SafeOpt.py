@@ -134,9 +134,20 @@ class BO(GP):
             return fallback
         return out["best_x"], out["best_value"]
 
-    def Minimizer(self):
+    def Minimizer(self, refine=None):
+        """argmax over M_t of var_0 -> (x, std).  ``refine`` (default: the constructor's): the level of M_t is the refined u* of
+        ``minimize_obj_ucb(refine=True)``, and the grid's minimiser and that call's arg-min (lcb_0 <= u* holds there by
+        construction) are refined off the grid on max var_0 s.t. lcb_c >= 0, lcb_0 <= u* (models/SafeOpt.py:53-66); the grid's
+        answer when neither seed is usable."""
         res = self.sweep()
-        return res["minimizer_x"], res["minimizer_std"]
+        if not self._refining(refine):
+            return res["minimizer_x"], res["minimizer_std"]
+        x_u, u_star = self.minimize_obj_ucb(refine=True)
+        out = self.engine.refine_sets(self.b, np.stack([res["minimizer_x"], np.asarray(x_u, dtype=np.float64)]), objective=0, kind="var",
+                                      maximize=True, level=(0, u_star), lo=self.bound[:, 0], hi=self.bound[:, 1])
+        if out["best"] < 0:
+            return res["minimizer_x"], res["minimizer_std"]
+        return out["best_x"], float(np.sqrt(out["best_value"]))
 
     def infnorm_mean_grad(self, x, i):
         """max_a |d MEAN_i / d x_a| at one point (analytic form of jax.grad(self.mean), models/SafeOpt.py:68-71)."""
@@ -162,9 +173,65 @@ class BO(GP):
         d = self.nx_dim
         return self.ucb(x[:d], i) - max_infnorm_mean_grad * np.linalg.norm(x[:d] - x[d:] + 1e-8)
 
-    def Expander(self):
+    def Expander(self, refine=None):
+        """The most uncertain expander over the constraints -> (x, std).  ``refine`` (default: the constructor's): for every
+        constraint with a non-empty G_c the pair (its grid expander, the U candidate nearest to it under the shifted norm) is
+        refined off the grid on max var_0(x) s.t. x in S, x' in U and the link with the sweep's L (models/SafeOpt.py:90-124);
+        a constraint whose pair is not usable keeps its grid value.  ``expander_witness`` holds (x', c, L) of the answer, or None
+        when the answer is a grid value."""
         res = self.sweep()
-        return res["expander_x"], res["expander_std"]
+        if not self._refining(refine):
+            return res["expander_x"], res["expander_std"]
+        self.expander_witness = None
+        best_x, best_std = res["expander_x"], res["expander_std"]
+        if not (res["expander_index_c"] >= 0).any():
+            return best_x, best_std
+        if 2 * self.nx_dim > 8:
+            raise ValueError("refining a pair needs d <= 4")
+        res = self.sweep(want_masks=True)
+        pts, U = self._all_points(), self.engine.mask("U")
+        best_x, best_std, first = res["expander_x"], -np.inf, True
+        for c in range(1, self.n_fun):
+            g = int(res["expander_index_c"][c - 1])
+            if g < 0:
+                continue
+            xg, std_c, wit = pts[g], float(res["expander_std_c"][c - 1]), None
+            Lc = self._sweep_L(res, c)
+            h = self._nearest_in_mask(pts, U, xg)
+            out = self.engine.refine_sets(self.b, xg, pts[h], objective=0, kind="var", maximize=True, link=(c, Lc),
+                                          lo=self.bound[:, 0], hi=self.bound[:, 1], max_eval=self._pair_max_eval)
+            if out["best"] >= 0:
+                xg, std_c, wit = out["best_x"], float(np.sqrt(out["best_value"])), (out["best_xp"], c, Lc)
+            if first or std_c > best_std:          # (first on ties, models/SafeOpt.py:119-122)
+                best_x, best_std, self.expander_witness, first = xg, std_c, wit, False
+        return best_x, best_std
+
+    _pair_max_eval = 1600     # evaluations of one point per refined pair (a pair costs two, and has twice the variables)
+
+    def _sweep_L(self, res, c):
+        """The Lipschitz constant the sweep used for constraint c (models/SafeOpt.py:110: the loop-leaked index under the quirk)."""
+        return float(res["L"][self.n_fun - 1 if self.reference_quirk_L_index else c])
+
+    def _all_points(self):
+        """Every candidate [N, d] in the sweep's flat order (axis 0 fastest on a grid)."""
+        if self.candidates is not None:
+            return self.candidates.astype(np.float64)
+        axes = []
+        for a, cnt in enumerate(self.grid):
+            lo, hi = self.bound[a]
+            ax = lo + np.arange(cnt) * ((hi - lo) / (cnt - 1) if cnt > 1 else 0.0)
+            if cnt > 1:
+                ax[-1] = hi
+            axes.append(ax)
+        mesh = np.meshgrid(*axes[::-1], indexing="ij")
+        return np.stack([m.reshape(-1) for m in mesh[::-1]], axis=1)
+
+    @staticmethod
+    def _nearest_in_mask(pts, mask, x, flip=False):
+        """Index of the member of ``mask`` nearest to x under ||x - x_h + 1e-8|| (``flip``: ||x_h - x + 1e-8||); first on ties."""
+        idx = np.nonzero(mask)[0]
+        diff = (pts[idx] - x if flip else x - pts[idx]) + 1e-8
+        return int(idx[np.argmin(np.sqrt(np.sum(diff * diff, axis=1)))])
 
     # ---- helpers ----------------------------------------------------------------------------------------------------
     def _grid_point(self, g: int):

@@ -29,6 +29,7 @@ SBO_E_COMM = -7
 SBO_E_UNSUPPORTED = -8
 
 SBO_FIT_FTOL, SBO_FIT_GTOL, SBO_FIT_MAXITER, SBO_FIT_LINESEARCH, SBO_FIT_NOT_PD = 0, 1, 2, 3, 4
+SBO_REFINE_DIST = 4      # objective kind of sbo_refine_sets: the distance to a target point
 SBO_REFINE_CONVERGED, SBO_REFINE_MAX_EVAL, SBO_REFINE_NO_PROGRESS, SBO_REFINE_INFEASIBLE_SEED, SBO_REFINE_ON_BOUNDARY = 0, 1, 2, 3, 4
 
 
@@ -84,6 +85,20 @@ class RefineOpts(C.Structure):
 class RefineResult(C.Structure):
     _fields_ = [("best", C.c_int64), ("best_x", C.c_double * SBO_MAX_D), ("best_value", C.c_double), ("evaluations", C.c_int64),
                 ("converged", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RefineSetsOpts(C.Structure):
+    _fields_ = [("b", C.c_double), ("pair", C.c_int32), ("objective", C.c_int32), ("kind", C.c_int32), ("objective_point", C.c_int32),
+                ("maximize", C.c_int32), ("safe_mask", C.c_uint32), ("unsafe_mask", C.c_uint32), ("use_level", C.c_int32),
+                ("level_output", C.c_int32), ("use_link", C.c_int32), ("link_output", C.c_int32), ("use_ball", C.c_int32),
+                ("max_eval", C.c_int32), ("reserved", C.c_int32), ("level", C.c_double), ("L", C.c_double),
+                ("lo", C.c_double * SBO_MAX_D), ("hi", C.c_double * SBO_MAX_D), ("x_0", C.c_double * SBO_MAX_D), ("r", C.c_double),
+                ("target", C.c_double * SBO_MAX_D), ("tol", C.c_double)]
+
+
+class RefineSetsResult(C.Structure):
+    _fields_ = [("best", C.c_int64), ("best_x", C.c_double * SBO_MAX_D), ("best_xp", C.c_double * SBO_MAX_D), ("best_value", C.c_double),
+                ("evaluations", C.c_int64), ("converged", C.c_int32), ("reserved", C.c_int32)]
 
 
 class FitOpts(C.Structure):
@@ -162,6 +177,7 @@ SYMBOLS = [
     ("sbo_model_fit", C.c_int, [_P, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.POINTER(FitOpts), _P, _P,
                                 C.POINTER(FitReport)]),
     ("sbo_refine", C.c_int, [_P, C.POINTER(RefineOpts), C.c_int64, _P, _P, _P, _P, C.POINTER(RefineResult)]),
+    ("sbo_refine_sets", C.c_int, [_P, C.POINTER(RefineSetsOpts), C.c_int64, _P, _P, _P, _P, _P, _P, C.POINTER(RefineSetsResult)]),
     ("sbo_plant_wo", C.c_int, [_P, C.c_int64, _P, _P]),
     ("sbo_profile_get", C.c_int, [_P, C.POINTER(Profile)]),
     ("sbo_set_option", C.c_int, [_P, C.c_char_p, C.c_int64]),

@@ -6,6 +6,10 @@
 // lcb_c >= 0 and the trust-region ball by the barrier), the whole iteration inside one launch as k_fit_local does (fit.hip).  The
 // candidates it returns are then re-evaluated by the library's exact list evaluator (launch_posterior_on_list, the values
 // sbo_bounds gives at those points) and accepted only when they pass the sweep's S predicate there and are no worse than the seed.
+//
+// sbo_refine_sets runs the same solver on the set-valued steps (SafeOpt's M_t / G_t, GoOSE's target and explore_safeset): the
+// variables are one point x or a pair z = (x, x'), and the barrier also carries a level term (level - lcb_o(x) >= 0), U-membership
+// of x' (lcb_c(x') <= 0) and the Lipschitz link ucb_c(x) - L ||x - x' + 1e-8|| >= 0.  A pair is evaluated in one pass over M's rows.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -26,15 +30,22 @@ constexpr size_t kRefLdsM = 144 * 1024;          // LDS tier: the used outputs' 
 struct RefineArgs {
   ModelConst mc;
   int nu;                    // distinct outputs evaluated (objective first)
-  int obj_slot;              // (always 0)
-  int con_slots;             // bit u: slot u is a constraint (lcb >= 0)
+  int obj_slot;              // (always 0; unused by SBO_REFINE_DIST)
+  int con_slots;             // bit u: slot u is a constraint (lcb >= 0 at x)
   int kind, maximize, use_ball, max_eval, f_cap, a_ld, pad;
   int outs[kMaxQ];           // slot -> output index
   double b, tol, r;
-  double lo[kMaxD], hi[kMaxD], x0[kMaxD];
+  double lo[kMaxD], hi[kMaxD], x0[kMaxD];   // lo / hi: the box of every solver variable (pair: the point's box twice)
+  // sbo_refine_sets (sbo_refine: np = 1, nz = d, no further term)
+  int np, nz;                // points per variable vector (1: x, 2: x and x') and solver variables np * d
+  int obj_point;             // the point the objective is taken at
+  int unsafe_slots;          // bit u: lcb of slot u <= 0 at x'
+  int level_slot, link_slot; // -1, or the slot of the level term (lcb <= level at x) / of the link (ucb at x)
+  double level, L, dscale;   // dscale: SBO_REFINE_DIST's normalisation (the box diagonal squared)
+  double tgt[kMaxD];         // SBO_REFINE_DIST: the point t of ||x - t||^2
 };
 
-// one evaluation: per used slot the un-normalised mean / var and their gradients
+// one evaluation of one point: per used slot the un-normalised mean / var and their gradients
 struct RefEval {
   double m[kMaxQ], v[kMaxQ], gm[kMaxQ][kMaxD], gv[kMaxQ][kMaxD];
   int clamp[kMaxQ];
@@ -71,17 +82,22 @@ __device__ __forceinline__ void ref_block_sum(const double* v, int cnt, double (
   __syncthreads();
 }
 
-// mean / var and their gradients at x (LDS) for every used output.  M rows: LDS packed triangles (kLds) or Fplain (stride f_cap).
-template <bool kLds>
+// mean / var and their gradients at the kP points of x (LDS, point p at x + p d) for every used output -> E[p].  M rows: LDS
+// packed triangles (kLds) or Fplain (stride f_cap); every element of M is read once per pass and serves the kP points (kv / uv
+// [kP][n], red [kP][2 (kMaxD + 1)], uup [kP][kRefWaves]).  Each point's sums run in the order of a one-point evaluation.
+template <bool kLds, int kP>
 __device__ void ref_eval(const RefineArgs& A, const double* x, const double* F, const double* Ml, const double* alpha,
-                         const double* Xn, double* kv, double* uv, double (*part)[kMaxD + 1], double* red, double* uup, RefEval& E) {
+                         const double* Xn, double* kv, double* uv, double (*part)[kMaxD + 1], double* red, double* uup, RefEval* E) {
   const ModelConst& mc = A.mc;
   const int n = mc.n, d = mc.d, dp = mc.dpad;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6, bd = blockDim.x;
   const size_t tri = (size_t)n * (n + 1) / 2;
-  double xn[kMaxD];
+  constexpr int kRed = 2 * (kMaxD + 1);
+  double xn[kP][kMaxD];
 #pragma unroll
-  for (int a = 0; a < kMaxD; ++a) xn[a] = a < d ? (x[a] - mc.X_mean[a]) / mc.X_std[a] : 0.0;
+  for (int p = 0; p < kP; ++p)
+#pragma unroll
+    for (int a = 0; a < kMaxD; ++a) xn[p][a] = a < d ? (x[p * d + a] - mc.X_mean[a]) / mc.X_std[a] : 0.0;
   for (int u = 0; u < A.nu; ++u) {
     const int o = A.outs[u];
     const double* Mo = kLds ? Ml + (size_t)u * tri : F + (size_t)o * A.f_cap * A.f_cap;
@@ -91,97 +107,160 @@ __device__ void ref_eval(const RefineArgs& A, const double* x, const double* F, 
 #pragma unroll
     for (int a = 0; a < kMaxD; ++a) ie[a] = mc.inv_ell[o][a];
     // k_j, k . alpha and its gradient
-    double acc[kMaxD + 1];
+    double acc[kP][kMaxD + 1];
 #pragma unroll
-    for (int a = 0; a < kMaxD + 1; ++a) acc[a] = 0.0;
+    for (int p = 0; p < kP; ++p)
+#pragma unroll
+      for (int a = 0; a < kMaxD + 1; ++a) acc[p][a] = 0.0;
     for (int j = tid; j < n; j += bd) {
-      double diff[kMaxD], dist = 0.0;
 #pragma unroll
-      for (int a = 0; a < kMaxD; ++a) {
-        diff[a] = a < d ? Xn[(size_t)j * dp + a] - xn[a] : 0.0;
-        if (a < d) dist += diff[a] * diff[a] * ie[a];
+      for (int p = 0; p < kP; ++p) {
+        double diff[kMaxD], dist = 0.0;
+#pragma unroll
+        for (int a = 0; a < kMaxD; ++a) {
+          diff[a] = a < d ? Xn[(size_t)j * dp + a] - xn[p][a] : 0.0;
+          if (a < d) dist += diff[a] * diff[a] * ie[a];
+        }
+        const double kj = sf2 * exp(-0.5 * dist);
+        kv[p * n + j] = kj;
+        const double ak = al[j] * kj;
+        acc[p][0] += ak;
+#pragma unroll
+        for (int a = 0; a < kMaxD; ++a)
+          if (a < d) acc[p][1 + a] += ak * diff[a] * ie[a];
       }
-      const double kj = sf2 * exp(-0.5 * dist);
-      kv[j] = kj;
-      const double ak = al[j] * kj;
-      acc[0] += ak;
-#pragma unroll
-      for (int a = 0; a < kMaxD; ++a)
-        if (a < d) acc[1 + a] += ak * diff[a] * ie[a];
     }
-    ref_block_sum(acc, d + 1, part, red);         // (its barriers also publish kv)
+#pragma unroll
+    for (int p = 0; p < kP; ++p) ref_block_sum(acc[p], d + 1, part, red + p * kRed);   // (its barriers also publish kv)
     // u = M k (one wave per row, rows in order), u . u
-    double uu = 0.0;
+    double uu[kP];
+#pragma unroll
+    for (int p = 0; p < kP; ++p) uu[p] = 0.0;
     for (int i = wave; i < n; i += nw) {
       const double* row = Mo + (kLds ? (size_t)i * (i + 1) / 2 : (size_t)i * A.f_cap);
-      double s = 0.0;
-      for (int j = lane; j <= i; j += 64) s += row[j] * kv[j];
-      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-      if (lane == 0) {
-        uv[i] = s;
-        uu += s * s;
+      double s[kP];
+#pragma unroll
+      for (int p = 0; p < kP; ++p) s[p] = 0.0;
+      for (int j = lane; j <= i; j += 64) {
+        const double mij = row[j];
+#pragma unroll
+        for (int p = 0; p < kP; ++p) s[p] += mij * kv[p * n + j];
+      }
+#pragma unroll
+      for (int p = 0; p < kP; ++p) {
+        for (int off = 32; off > 0; off >>= 1) s[p] += __shfl_xor(s[p], off);
+        if (lane == 0) {
+          uv[p * n + i] = s[p];
+          uu[p] += s[p] * s[p];
+        }
       }
     }
-    if (lane == 0) uup[wave] = uu;
+    if (lane == 0)
+#pragma unroll
+      for (int p = 0; p < kP; ++p) uup[p * kRefWaves + wave] = uu[p];
     __syncthreads();
     // w = M^T u, and sum_j w_j dk_j / dx
-    double gacc[kMaxD + 1];
+    double gacc[kP][kMaxD + 1];
 #pragma unroll
-    for (int a = 0; a < kMaxD + 1; ++a) gacc[a] = 0.0;
+    for (int p = 0; p < kP; ++p)
+#pragma unroll
+      for (int a = 0; a < kMaxD + 1; ++a) gacc[p][a] = 0.0;
     for (int j0 = 0; j0 < n; j0 += bd) {
       const int j = j0 + tid;
       const int jw = j0 + (wave << 6);              // the wave's first column: rows above it hold nothing for the wave
-      double w = 0.0;
-      for (int i = jw; i < n; ++i)
-        if (i >= j && j < n) w += Mo[(kLds ? (size_t)i * (i + 1) / 2 : (size_t)i * A.f_cap) + j] * uv[i];
-      if (j < n) {
-        const double wk = w * kv[j];
+      double w[kP];
 #pragma unroll
-        for (int a = 0; a < kMaxD; ++a)
-          if (a < d) gacc[a] += wk * (Xn[(size_t)j * dp + a] - xn[a]) * ie[a];
+      for (int p = 0; p < kP; ++p) w[p] = 0.0;
+      for (int i = jw; i < n; ++i)
+        if (i >= j && j < n) {
+          const double mij = Mo[(kLds ? (size_t)i * (i + 1) / 2 : (size_t)i * A.f_cap) + j];
+#pragma unroll
+          for (int p = 0; p < kP; ++p) w[p] += mij * uv[p * n + i];
+        }
+      if (j < n) {
+#pragma unroll
+        for (int p = 0; p < kP; ++p) {
+          const double wk = w[p] * kv[p * n + j];
+#pragma unroll
+          for (int a = 0; a < kMaxD; ++a)
+            if (a < d) gacc[p][a] += wk * (Xn[(size_t)j * dp + a] - xn[p][a]) * ie[a];
+        }
       }
     }
-    ref_block_sum(gacc, d, part, red + kMaxD + 1);
+#pragma unroll
+    for (int p = 0; p < kP; ++p) ref_block_sum(gacc[p], d, part, red + p * kRed + kMaxD + 1);
     if (tid == 0) {
-      double s = 0.0;
-      for (int w = 0; w < nw; ++w) s += uup[w];
-      const double ys = mc.Y_std[o], vn = sf2 - s;
-      E.m[u] = ys * (mc.mp[o] + red[0]) + mc.Y_mean[o];
-      E.v[u] = ys * ys * (vn > 0.0 ? vn : 0.0);
-      E.clamp[u] = !(vn > 0.0);
-      for (int a = 0; a < d; ++a) {
-        E.gm[u][a] = ys * red[1 + a] / mc.X_std[a];
-        E.gv[u][a] = -2.0 * ys * ys * red[kMaxD + 1 + a] / mc.X_std[a];
+      for (int p = 0; p < kP; ++p) {
+        const double* rd = red + p * kRed;
+        double s = 0.0;
+        for (int w = 0; w < nw; ++w) s += uup[p * kRefWaves + w];
+        const double ys = mc.Y_std[o], vn = sf2 - s;
+        E[p].m[u] = ys * (mc.mp[o] + rd[0]) + mc.Y_mean[o];
+        E[p].v[u] = ys * ys * (vn > 0.0 ? vn : 0.0);
+        E[p].clamp[u] = !(vn > 0.0);
+        for (int a = 0; a < d; ++a) {
+          E[p].gm[u][a] = ys * rd[1 + a] / mc.X_std[a];
+          E[p].gv[u][a] = -2.0 * ys * ys * rd[kMaxD + 1 + a] / mc.X_std[a];
+        }
       }
     }
     __syncthreads();                                // (kv / uv are rewritten for the next output)
   }
 }
 
-// objective part (fo, go; obj = sign-adjusted objective) and barrier sum (B, gB) at x from an evaluation; false: the trial is rejected
-__device__ bool ref_terms(const RefineArgs& A, const RefEval& E, const double* x, double& fo, double* go, double& B, double* gB, double& obj) {
-  const int d = A.mc.d;
-  const double b = A.b;
-  double f, gf[kMaxD];
-  const int u0 = A.obj_slot;
-  if (A.kind == SBO_MEAN || ((A.kind == SBO_UCB || A.kind == SBO_LCB) && b == 0.0)) {
-    f = E.m[u0];
-    for (int a = 0; a < d; ++a) gf[a] = E.gm[u0][a];
-  } else if (A.kind == SBO_VAR) {
-    if (E.clamp[u0]) return false;
-    f = E.v[u0];
-    for (int a = 0; a < d; ++a) gf[a] = E.gv[u0][a];
-  } else {
-    if (E.clamp[u0] || !(E.v[u0] > 0.0)) return false;
-    const double sd = sqrt(E.v[u0]), sg = A.kind == SBO_UCB ? 1.0 : -1.0;
-    f = E.m[u0] + sg * b * sd;
-    for (int a = 0; a < d; ++a) gf[a] = E.gm[u0][a] + sg * b * E.gv[u0][a] / (2.0 * sd);
+// lcb (sgn = -1) or ucb (+1) of slot u at an evaluation, with its gradient; false where the variance gives none
+__device__ bool ref_conf(const RefEval& E, int u, double b, double sgn, int d, double& g, double* gg) {
+  g = E.m[u];
+  for (int a = 0; a < d; ++a) gg[a] = E.gm[u][a];
+  if (b != 0.0) {
+    if (E.clamp[u] || !(E.v[u] > 0.0)) return false;
+    const double sd = sqrt(E.v[u]);
+    g = E.m[u] + sgn * b * sd;
+    for (int a = 0; a < d; ++a) gg[a] += sgn * b * E.gv[u][a] / (2.0 * sd);
   }
-  const double sg = A.maximize ? -1.0 : 1.0, ys = A.mc.Y_std[A.outs[u0]];
+  return true;
+}
+
+// objective part (fo, go; obj = sign-adjusted objective) and barrier sum (B, gB) at x (pair: x, x') from the evaluation of its
+// points; false: the trial is rejected
+__device__ bool ref_terms(const RefineArgs& A, const RefEval* Ev, const double* x, double& fo, double* go, double& B, double* gB, double& obj) {
+  const int d = A.mc.d, nz = A.nz;
+  const double b = A.b;
+  const RefEval& E = Ev[0];                               // (the evaluation at x)
+  double f, gf[kMaxD], ys;
+  for (int a = 0; a < nz; ++a) gf[a] = 0.0;
+  if (A.kind == SBO_REFINE_DIST) {
+    f = 0.0;
+    for (int a = 0; a < d; ++a) {
+      const double df = x[a] - A.tgt[a];
+      f += df * df;
+      gf[a] = 2.0 * df;
+    }
+    ys = A.dscale;
+  } else {
+    const RefEval& Eo = Ev[A.obj_point];
+    double* gp = gf + A.obj_point * d;
+    const int u0 = A.obj_slot;
+    if (A.kind == SBO_MEAN || ((A.kind == SBO_UCB || A.kind == SBO_LCB) && b == 0.0)) {
+      f = Eo.m[u0];
+      for (int a = 0; a < d; ++a) gp[a] = Eo.gm[u0][a];
+    } else if (A.kind == SBO_VAR) {
+      if (Eo.clamp[u0]) return false;
+      f = Eo.v[u0];
+      for (int a = 0; a < d; ++a) gp[a] = Eo.gv[u0][a];
+    } else {
+      if (Eo.clamp[u0] || !(Eo.v[u0] > 0.0)) return false;
+      const double sd = sqrt(Eo.v[u0]), sg = A.kind == SBO_UCB ? 1.0 : -1.0;
+      f = Eo.m[u0] + sg * b * sd;
+      for (int a = 0; a < d; ++a) gp[a] = Eo.gm[u0][a] + sg * b * Eo.gv[u0][a] / (2.0 * sd);
+    }
+    ys = A.mc.Y_std[A.outs[u0]];
+  }
+  const double sg = A.maximize ? -1.0 : 1.0;
   obj = sg * f;
   fo = obj / ys;
   bool ok = isfinite(fo);
-  for (int a = 0; a < d; ++a) {
+  for (int a = 0; a < nz; ++a) {
     go[a] = sg * gf[a] / ys;
     gB[a] = 0.0;
     ok = ok && isfinite(go[a]);
@@ -209,14 +288,47 @@ __device__ bool ref_terms(const RefineArgs& A, const RefEval& E, const double* x
     B -= log(h / (A.r * A.r));
     for (int a = 0; a < d; ++a) gB[a] += 2.0 * (x[a] - A.x0[a]) / h;
   }
+  if (A.level_slot >= 0) {                                // level - lcb(x) > 0
+    double l, gl[kMaxD];
+    if (!ref_conf(E, A.level_slot, b, -1.0, d, l, gl)) return false;
+    const double gc = A.level - l;
+    if (!(gc > 0.0)) return false;
+    B -= log(gc / A.mc.Y_std[A.outs[A.level_slot]]);
+    for (int a = 0; a < d; ++a) gB[a] += gl[a] / gc;
+  }
+  for (int u = 0; u < A.nu; ++u) {                        // x' in U: -lcb_c(x') > 0
+    if (!((A.unsafe_slots >> u) & 1)) continue;
+    double l, gl[kMaxD];
+    if (!ref_conf(Ev[1], u, b, -1.0, d, l, gl)) return false;
+    const double gc = -l;
+    if (!(gc > 0.0)) return false;
+    B -= log(gc / A.mc.Y_std[A.outs[u]]);
+    for (int a = 0; a < d; ++a) gB[d + a] += gl[a] / gc;
+  }
+  if (A.link_slot >= 0) {                                 // ucb_c(x) - L ||x - x' + 1e-8|| > 0
+    double uc, gu[kMaxD], df[kMaxD], ss = 0.0;
+    if (!ref_conf(E, A.link_slot, b, 1.0, d, uc, gu)) return false;
+    for (int a = 0; a < d; ++a) {
+      df[a] = x[a] - x[d + a] + 1e-8;
+      ss += df[a] * df[a];
+    }
+    const double nrm = sqrt(ss), gc = uc - A.L * nrm;
+    if (!(gc > 0.0)) return false;
+    B -= log(gc / A.mc.Y_std[A.outs[A.link_slot]]);
+    for (int a = 0; a < d; ++a) {
+      const double gn = nrm > 0.0 ? A.L * df[a] / nrm : 0.0;
+      gB[a] -= (gu[a] - gn) / gc;
+      gB[d + a] -= gn / gc;
+    }
+  }
   ok = ok && isfinite(B);
-  for (int a = 0; a < d; ++a) ok = ok && isfinite(gB[a]);
+  for (int a = 0; a < nz; ++a) ok = ok && isfinite(gB[a]);
   return ok;
 }
 
 __device__ double ref_pgnorm(const RefState& S, const RefineArgs& A) {
   double pg = 0.0;
-  for (int a = 0; a < A.mc.d; ++a)
+  for (int a = 0; a < A.nz; ++a)
     if (S.span[a] > 0.0) pg = fmax(pg, fabs(ref_clip(S.x[a] - S.D2[a] * S.g[a], A.lo[a], A.hi[a]) - S.x[a]) / S.span[a]);
   return pg;
 }
@@ -229,7 +341,7 @@ __device__ void ref_reset_h(RefState& S, int d) {
 
 // Next search direction at the accepted point (lowering the barrier weight between stages): true with the first trial in `trial`
 __device__ bool ref_new_iteration(RefState& S, const RefineArgs& A, double* trial) {
-  const int d = A.mc.d;
+  const int d = A.nz;                 // (the solver's variables)
   for (;;) {
     S.f = S.fo + S.mu * S.B;
     for (int a = 0; a < d; ++a) S.g[a] = S.go[a] + S.mu * S.gB[a];
@@ -272,9 +384,9 @@ __device__ bool ref_stage_end(RefState& S, const RefineArgs& A, double* trial) {
 }
 
 // consume the evaluation of `trial`; true when `trial` holds the next point to evaluate
-__device__ __noinline__ bool ref_advance(RefState& S, const RefineArgs& A, const RefEval& E, double* trial) {
-  const int d = A.mc.d;
-  ++S.nev;
+__device__ __noinline__ bool ref_advance(RefState& S, const RefineArgs& A, const RefEval* E, double* trial) {
+  const int d = A.nz;                 // (the solver's variables)
+  S.nev += A.np;                      // (one posterior + gradient evaluation per point)
   double fo, go[kMaxD], B, gB[kMaxD], obj;
   const bool ok = ref_terms(A, E, trial, fo, go, B, gB, obj);
   if (S.phase == REF_PH_START) {
@@ -354,12 +466,13 @@ __device__ __forceinline__ double ref_bound(double m, double v, double b, int ki
   return kind == SBO_UCB ? add_rn(m, sd) : sub_rn(m, sd);
 }
 
-// the sweep's S predicate at x under exact values (mean / var [q][ld] at column g): 0 infeasible, 1 feasible, 2 feasible on a
-// barrier's boundary (some lcb_c == 0, or the ball's sphere)
+// every term of the problem at x (pair: x, x') under exact values (mean / var [q][ld], the first point at column g, x' behind it),
+// judged with the sweeps' closed predicates: 0 infeasible, 1 feasible, 2 feasible on a barrier's boundary (some lcb_c == 0, the
+// ball's sphere, lcb == level, or a link of exactly 0)
 __device__ int ref_feasible(const RefineArgs& A, const double* x, const double* m, const double* v, long long ld, long long g) {
   const int d = A.mc.d;
   bool edge = false;
-  for (int a = 0; a < d; ++a)
+  for (int a = 0; a < A.nz; ++a)
     if (!(x[a] >= A.lo[a] && x[a] <= A.hi[a])) return 0;          // (NaN / inf included)
   if (A.use_ball) {
     double ss = 0.0;
@@ -378,27 +491,67 @@ __device__ int ref_feasible(const RefineArgs& A, const double* x, const double* 
     if (!(l >= 0.0)) return 0;
     edge = edge || l == 0.0;
   }
+  if (A.level_slot >= 0) {                                         // (the sweep's M: lcb_0 <= u*)
+    const int o = A.outs[A.level_slot];
+    const double l = ref_bound(m[(size_t)o * ld + g], v[(size_t)o * ld + g], A.b, SBO_LCB);
+    if (!(l <= A.level)) return 0;
+    edge = edge || l == A.level;
+  }
+  for (int u = 0; u < A.nu; ++u) {                                 // (the sweep's U: every lcb_c <= 0)
+    if (!((A.unsafe_slots >> u) & 1)) continue;
+    const int o = A.outs[u];
+    const double l = ref_bound(m[(size_t)o * ld + g + 1], v[(size_t)o * ld + g + 1], A.b, SBO_LCB);
+    if (!(l <= 0.0)) return 0;
+    edge = edge || l == 0.0;
+  }
+  if (A.link_slot >= 0) {                                          // (lipschitz_pair's expression, sets_expander.inc.hpp)
+    const int o = A.outs[A.link_slot];
+    const double ucb = ref_bound(m[(size_t)o * ld + g], v[(size_t)o * ld + g], A.b, SBO_UCB);
+    double ss = 0.0;
+    for (int a = 0; a < d; ++a) {
+      const double df = add_rn(sub_rn(x[a], x[d + a]), 1e-8);
+      ss = (a == 0) ? mul_rn(df, df) : add_rn(ss, mul_rn(df, df));
+    }
+    const double val = sub_rn(ucb, mul_rn(A.L, sqrt_rn(ss)));
+    if (!(val >= 0.0)) return 0;
+    edge = edge || val == 0.0;
+  }
   return edge ? 2 : 1;
 }
 
-template <bool kLds>
+// the exact objective at x: the bound of the objective's output at its point, or the Euclidean distance to the target
+__device__ double ref_objective(const RefineArgs& A, const double* x, const double* m, const double* v, long long ld, long long g) {
+  if (A.kind == SBO_REFINE_DIST) {
+    double ss = 0.0;
+    for (int a = 0; a < A.mc.d; ++a) {
+      const double df = sub_rn(x[a], A.tgt[a]);
+      ss = (a == 0) ? mul_rn(df, df) : add_rn(ss, mul_rn(df, df));
+    }
+    return sqrt_rn(ss);
+  }
+  const int o = A.outs[A.obj_slot];
+  return ref_bound(m[(size_t)o * ld + g + A.obj_point], v[(size_t)o * ld + g + A.obj_point], A.b, A.kind);
+}
+
+// seeds / cand hold nz values per entry; m0 / v0 are [q][kP S] (seed s: columns kP s ..)
+template <bool kLds, int kP>
 __global__ __launch_bounds__(1024) void k_refine(const RefineArgs* __restrict__ Ap, const double* __restrict__ F, const double* __restrict__ alpha,
                                                  const double* __restrict__ Xn, const double* __restrict__ seeds,
                                                  const double* __restrict__ m0, const double* __restrict__ v0, long long S,
                                                  double* __restrict__ cand, int* __restrict__ st_out, int* __restrict__ nev_out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ RefState R;
-  __shared__ RefEval E;
-  __shared__ double trial[kMaxD], red[2 * (kMaxD + 1)], uup[kRefWaves];
+  __shared__ RefEval E[kP];
+  __shared__ double trial[kMaxD], red[kP * 2 * (kMaxD + 1)], uup[kP * kRefWaves];
   __shared__ double part[kRefWaves][kMaxD + 1];
   __shared__ int go;
   const RefineArgs& A = *Ap;                        // (in global memory: a kernarg copy indexed by output would go to scratch)
   const ModelConst& mc = A.mc;
-  const int n = mc.n, d = mc.d;
+  const int n = mc.n, d = mc.d, nz = A.nz;
   const long long s = blockIdx.x;
-  double* kv = reinterpret_cast<double*>(smem);
-  double* uv = kv + n;
-  double* Ml = uv + n;
+  double* kv = reinterpret_cast<double*>(smem);     // [kP][n]
+  double* uv = kv + kP * n;                         // [kP][n]
+  double* Ml = uv + kP * n;
   if (kLds) {                                       // the used outputs' triangles of M, packed row after row
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const size_t tri = (size_t)n * (n + 1) / 2;
@@ -409,31 +562,32 @@ __global__ __launch_bounds__(1024) void k_refine(const RefineArgs* __restrict__ 
     }
   }
   if (threadIdx.x == 0) {
-    for (int a = 0; a < d; ++a) {
-      trial[a] = seeds[s * d + a];
+    for (int a = 0; a < nz; ++a) {
+      trial[a] = seeds[s * nz + a];
       R.x[a] = R.xb[a] = trial[a];
       const double w = A.hi[a] - A.lo[a];
-      R.span[a] = A.use_ball ? fmin(w, 2.0 * A.r) : w;
+      R.span[a] = (A.use_ball && a < d) ? fmin(w, 2.0 * A.r) : w;
       R.D2[a] = R.span[a] * R.span[a];
     }
-    const int fe = ref_feasible(A, trial, m0, v0, S, s);
+    const int fe = ref_feasible(A, trial, m0, v0, kP * S, kP * s);
     R.nev = 0;
     R.status = fe == 0 ? SBO_REFINE_INFEASIBLE_SEED : fe == 2 ? SBO_REFINE_ON_BOUNDARY : -1;
-    R.nbar = __popc((unsigned)A.con_slots) + (A.use_ball ? 1 : 0);
+    R.nbar = __popc((unsigned)A.con_slots) + (A.use_ball ? 1 : 0) + __popc((unsigned)A.unsafe_slots) + (A.level_slot >= 0 ? 1 : 0) +
+             (A.link_slot >= 0 ? 1 : 0);
     R.phase = REF_PH_START;
-    ref_reset_h(R, d);
+    ref_reset_h(R, nz);
     go = R.status < 0;
   }
   __syncthreads();
   while (go) {
-    ref_eval<kLds>(A, trial, F, Ml, alpha, Xn, kv, uv, part, red, uup, E);
+    ref_eval<kLds, kP>(A, trial, F, Ml, alpha, Xn, kv, uv, part, red, uup, E);
     if (threadIdx.x == 0) go = ref_advance(R, A, E, trial);
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    for (int a = 0; a < d; ++a) {
-      cand[(2 * s) * d + a] = R.x[a];
-      cand[(2 * s + 1) * d + a] = R.xb[a];
+    for (int a = 0; a < nz; ++a) {
+      cand[(2 * s) * nz + a] = R.x[a];
+      cand[(2 * s + 1) * nz + a] = R.xb[a];
     }
     st_out[s] = R.status;
     nev_out[s] = R.nev;
@@ -441,16 +595,16 @@ __global__ __launch_bounds__(1024) void k_refine(const RefineArgs* __restrict__ 
 }
 
 // acceptance under exact values: the final iterate or the best-objective iterate when feasible there and no worse than the seed
-// (the better of the two, ties to the final iterate), else the seed
+// (the better of the two, ties to the final iterate), else the seed.  m0 / v0 [q][np S], m1 / v1 [q][2 np S]
 __global__ void k_refine_accept(const RefineArgs* __restrict__ Ap, long long S, const double* __restrict__ seeds, const double* __restrict__ m0,
                                 const double* __restrict__ v0, const double* __restrict__ cand, const double* __restrict__ m1,
                                 const double* __restrict__ v1, int* __restrict__ st, double* __restrict__ x_out,
                                 double* __restrict__ val_out) {
   const RefineArgs& A = *Ap;
-  const int d = A.mc.d, o = A.outs[A.obj_slot];
+  const int nz = A.nz, np = A.np;
   const double sg = A.maximize ? -1.0 : 1.0;
   for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < S; s += (long long)gridDim.x * blockDim.x) {
-    const double fs = ref_bound(m0[(size_t)o * S + s], v0[(size_t)o * S + s], A.b, A.kind);
+    const double fs = ref_objective(A, seeds + s * nz, m0, v0, np * S, np * s);
     int status = st[s];
     int pick = -1;                                   // -1 seed, 0 final iterate, 1 best iterate
     double fv = fs;
@@ -458,18 +612,122 @@ __global__ void k_refine_accept(const RefineArgs* __restrict__ Ap, long long S, 
       double best = 0.0;
       for (int k = 0; k < 2; ++k) {
         const long long g = 2 * s + k;
-        if (!ref_feasible(A, cand + g * d, m1, v1, 2 * S, g)) continue;
-        const double f = ref_bound(m1[(size_t)o * 2 * S + g], v1[(size_t)o * 2 * S + g], A.b, A.kind);
+        if (!ref_feasible(A, cand + g * nz, m1, v1, 2 * np * S, np * g)) continue;
+        const double f = ref_objective(A, cand + g * nz, m1, v1, 2 * np * S, np * g);
         if (!(sg * f <= sg * fs)) continue;
         if (pick < 0 || sg * f < best) { pick = k; best = sg * f; fv = f; }
       }
       if (pick < 0) status = SBO_REFINE_NO_PROGRESS;
     }
-    const double* xs = pick < 0 ? seeds + s * d : cand + (2 * s + pick) * d;
-    for (int a = 0; a < d; ++a) x_out[s * d + a] = xs[a];
+    const double* xs = pick < 0 ? seeds + s * nz : cand + (2 * s + pick) * nz;
+    for (int a = 0; a < nz; ++a) x_out[s * nz + a] = xs[a];
     val_out[s] = fv;
     st[s] = status;
   }
+}
+
+template <bool kLds, int kP>
+static int refine_launch(sbo_ctx* c, size_t lds, int threads, long long S, const RefineArgs* dA, const double* dseed, const double* m0,
+                         const double* v0, double* cand, int* dst, int* dnev) {
+  SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_refine<kLds, kP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((k_refine<kLds, kP>), dim3((unsigned)S), dim3(threads), lds, c->stream, dA, (const double*)c->Fplain.p,
+                     (const double*)c->alpha64.p, (const double*)c->Xn.p, dseed, m0, v0, S, cand, dst, dnev);
+  SBO_HIP(hipGetLastError());
+  return SBO_OK;
+}
+
+// what sbo_refine and sbo_refine_sets share once their arguments are checked and A describes the problem (outs, slots, terms, box):
+// the exact values at the seeds, the solver launch, the exact check.  hz [S][nz], hv [S], hs [2 S] (status, then evaluations)
+static int refine_run(sbo_ctx* c, RefineArgs& A, int max_eval, double tol, long long S, const double* seeds, std::vector<double>& hz,
+                      std::vector<double>& hv, std::vector<int>& hs) {
+  const ModelConst& mc = c->mc;
+  const int q = mc.q, np = A.np, nz = A.nz;
+  SBO_HIP(hipSetDevice(c->device));
+  int rc;
+  if ((rc = factor_sync(c))) return rc;             // (Fplain may still be in the making: the deferred factor chain)
+  A.mc = mc;
+  // one launch holds a CU for max_eval evaluations of O(n^2) each: the ceiling keeps a call near a few seconds at n = 2048
+  const int eval_cap = (int)std::min<double>(kRefMaxEval, std::max<double>(kRefDefaultEval, 4e9 / ((double)mc.n * mc.n)));
+  A.max_eval = max_eval > 0 ? std::min(max_eval, eval_cap) : kRefDefaultEval;
+  A.f_cap = c->f_cap;
+  A.a_ld = c->a_ld;
+  A.tol = tol > 0.0 ? tol : kRefDefaultTol;
+  // scratch: the arguments | seeds [S][nz] | mean0 var0 [q][np S] | cand [2 S][nz] | mean1 var1 [q][2 np S] | x_out [S][nz] | val [S] |
+  // status, evaluations [S]
+  const size_t P = (size_t)np * S;
+  const size_t ael = (sizeof(RefineArgs) + 255) / 256 * 32;
+  const size_t el = ael + (size_t)S * nz + 2 * (size_t)q * P + 2 * (size_t)S * nz + 4 * (size_t)q * P + (size_t)S * nz + S + S;
+  if ((rc = ensure(c->refbuf, sizeof(double) * el))) return rc;
+  RefineArgs* dA = (RefineArgs*)c->refbuf.p;
+  double* dseed = (double*)c->refbuf.p + ael;
+  double* m0 = dseed + (size_t)S * nz;
+  double* v0 = m0 + (size_t)q * P;
+  double* cand = v0 + (size_t)q * P;
+  double* m1 = cand + 2 * (size_t)S * nz;
+  double* v1 = m1 + 2 * (size_t)q * P;
+  double* dx = v1 + 2 * (size_t)q * P;
+  double* dval = dx + (size_t)S * nz;
+  int* dst = reinterpret_cast<int*>(dval + S);
+  int* dnev = dst + S;
+  SBO_HIP(hipMemcpyAsync(dA, &A, sizeof(RefineArgs), hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemcpyAsync(dseed, seeds, sizeof(double) * (size_t)S * nz, hipMemcpyHostToDevice, c->stream));
+  if ((rc = launch_posterior_on_list(c, dseed, (long long)P, m0, v0))) return rc;   // (a pair's points are consecutive rows of d)
+  const int n = mc.n;
+  const size_t tri_bytes = sizeof(double) * (size_t)A.nu * n * (n + 1) / 2;
+  const size_t kvuv = sizeof(double) * 2 * (size_t)n;                              // k and u = M k of one point
+  const bool lds_tier = c->refine_lds && tri_bytes + (np - 1) * kvuv <= kRefLdsM;  // (the second point's vectors count against M's budget)
+  const size_t lds = np * kvuv + (lds_tier ? tri_bytes : 0);
+  const int threads = n > 256 ? 1024 : 256;
+  if (S > 0x7fffffffLL) return fail(SBO_E_UNSUPPORTED, "too many seeds for one launch");
+  if (np == 1)
+    rc = lds_tier ? refine_launch<true, 1>(c, lds, threads, S, dA, dseed, m0, v0, cand, dst, dnev)
+                  : refine_launch<false, 1>(c, lds, threads, S, dA, dseed, m0, v0, cand, dst, dnev);
+  else
+    rc = lds_tier ? refine_launch<true, 2>(c, lds, threads, S, dA, dseed, m0, v0, cand, dst, dnev)
+                  : refine_launch<false, 2>(c, lds, threads, S, dA, dseed, m0, v0, cand, dst, dnev);
+  if (rc) return rc;
+  if ((rc = launch_posterior_on_list(c, cand, 2 * (long long)P, m1, v1))) return rc;
+  hipLaunchKernelGGL(k_refine_accept, dim3((unsigned)std::min<long long>((S + 255) / 256, 1024)), dim3(256), 0, c->stream, (const RefineArgs*)dA, S,
+                     (const double*)dseed, (const double*)m0, (const double*)v0, (const double*)cand, (const double*)m1,
+                     (const double*)v1, dst, dx, dval);
+  SBO_HIP(hipGetLastError());
+  hz.resize((size_t)S * nz);
+  hv.resize(S);
+  hs.resize(2 * (size_t)S);
+  SBO_HIP(hipMemcpyAsync(hz.data(), dx, sizeof(double) * (size_t)S * nz, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipMemcpyAsync(hv.data(), dval, sizeof(double) * S, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipMemcpyAsync(hs.data(), dst, sizeof(int) * 2 * (size_t)S, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipStreamSynchronize(c->stream));
+  return SBO_OK;
+}
+
+// the seed whose returned point is best (ties: the lowest index; infeasible seeds and NaN values never), -1 if none
+static long long refine_best(const std::vector<double>& hv, const std::vector<int>& hs, long long S, bool maximize, int64_t* evaluations,
+                             int32_t* converged) {
+  long long best = -1;
+  const double sg = maximize ? -1.0 : 1.0;
+  for (long long s = 0; s < S; ++s) {
+    *evaluations += hs[S + s];
+    if (hs[s] == SBO_REFINE_CONVERGED) ++*converged;
+    if (hs[s] == SBO_REFINE_INFEASIBLE_SEED || std::isnan(hv[s])) continue;
+    if (best < 0 || sg * hv[s] < sg * hv[best]) best = s;
+  }
+  return best;
+}
+
+// the checks sbo_refine_opts and sbo_refine_sets_opts share; nullptr when they pass
+static const char* refine_check_common(int d, double b, double tol, const double* lo, const double* hi, int use_ball, double r, const double* x_0) {
+  if (!(b >= 0.0) || !std::isfinite(b)) return "confidence multiplier b must be finite and >= 0";
+  if (std::isnan(tol)) return "tol is NaN";
+  for (int a = 0; a < d; ++a)
+    if (!std::isfinite(lo[a]) || !std::isfinite(hi[a]) || !(lo[a] <= hi[a])) return "box needs finite lo <= hi";
+  if (use_ball != 0 && use_ball != 1) return "use_ball must be 0 or 1";
+  if (use_ball) {
+    if (!(r > 0.0) || !std::isfinite(r)) return "ball radius must be finite and > 0";
+    for (int a = 0; a < d; ++a)
+      if (!std::isfinite(x_0[a])) return "ball centre must be finite";
+  }
+  return nullptr;
 }
 
 }  // namespace sbo
@@ -490,22 +748,12 @@ extern "C" int sbo_refine(sbo_ctx* c, const sbo_refine_opts* opts, int64_t n_see
   if (opts->maximize != 0 && opts->maximize != 1) return fail(SBO_E_INVALID, "maximize must be 0 or 1");
   if ((opts->constraint_mask & 1u) || (q < 32 && (opts->constraint_mask >> q) != 0))
     return fail(SBO_E_INVALID, "constraint_mask: bit 0 must be clear and no bit may reach q");
-  if (!(opts->b >= 0.0) || !std::isfinite(opts->b)) return fail(SBO_E_INVALID, "confidence multiplier b must be finite and >= 0");
-  if (std::isnan(opts->tol)) return fail(SBO_E_INVALID, "tol is NaN");
-  for (int a = 0; a < d; ++a)
-    if (!std::isfinite(opts->lo[a]) || !std::isfinite(opts->hi[a]) || !(opts->lo[a] <= opts->hi[a]))
-      return fail(SBO_E_INVALID, "box needs finite lo <= hi");
-  if (opts->use_ball != 0 && opts->use_ball != 1) return fail(SBO_E_INVALID, "use_ball must be 0 or 1");
-  if (opts->use_ball) {
-    if (!(opts->r > 0.0) || !std::isfinite(opts->r)) return fail(SBO_E_INVALID, "ball radius must be finite and > 0");
-    for (int a = 0; a < d; ++a)
-      if (!std::isfinite(opts->x_0[a])) return fail(SBO_E_INVALID, "ball centre must be finite");
-  }
-  SBO_HIP(hipSetDevice(c->device));
-  int rc;
-  if ((rc = factor_sync(c))) return rc;             // (Fplain may still be in the making: the deferred factor chain)
+  if (const char* why = refine_check_common(d, opts->b, opts->tol, opts->lo, opts->hi, opts->use_ball, opts->r, opts->x_0))
+    return fail(SBO_E_INVALID, why);
   RefineArgs A{};
-  A.mc = mc;
+  A.np = 1;
+  A.nz = d;
+  A.level_slot = A.link_slot = -1;
   A.outs[0] = opts->objective;
   A.nu = 1;
   for (int o = 1; o < q; ++o) {
@@ -518,13 +766,7 @@ extern "C" int sbo_refine(sbo_ctx* c, const sbo_refine_opts* opts, int64_t n_see
   A.kind = opts->kind;
   A.maximize = opts->maximize;
   A.use_ball = opts->use_ball;
-  // one launch holds a CU for max_eval evaluations of O(n^2) each: the ceiling keeps a call near a few seconds at n = 2048
-  const int eval_cap = (int)std::min<double>(kRefMaxEval, std::max<double>(kRefDefaultEval, 4e9 / ((double)mc.n * mc.n)));
-  A.max_eval = opts->max_eval > 0 ? std::min(opts->max_eval, eval_cap) : kRefDefaultEval;
-  A.f_cap = c->f_cap;
-  A.a_ld = c->a_ld;
   A.b = opts->b;
-  A.tol = opts->tol > 0.0 ? opts->tol : kRefDefaultTol;
   A.r = opts->use_ball ? opts->r : 0.0;
   for (int a = 0; a < d; ++a) {
     A.lo[a] = opts->lo[a];
@@ -532,69 +774,122 @@ extern "C" int sbo_refine(sbo_ctx* c, const sbo_refine_opts* opts, int64_t n_see
     A.x0[a] = opts->use_ball ? opts->x_0[a] : 0.0;
   }
   const long long S = n_seeds;
-  // scratch: the arguments | seeds | mean0 var0 [q][S] | cand [2 S][d] | mean1 var1 [q][2 S] | x_out [S][d] | val [S] | status, evaluations [S]
-  const size_t ael = (sizeof(RefineArgs) + 255) / 256 * 32;
-  const size_t el = ael + (size_t)S * d + 2 * (size_t)q * S + 2 * (size_t)S * d + 4 * (size_t)q * S + (size_t)S * d + S + S;
-  if ((rc = ensure(c->refbuf, sizeof(double) * el))) return rc;
-  RefineArgs* dA = (RefineArgs*)c->refbuf.p;
-  double* dseed = (double*)c->refbuf.p + ael;
-  double* m0 = dseed + (size_t)S * d;
-  double* v0 = m0 + (size_t)q * S;
-  double* cand = v0 + (size_t)q * S;
-  double* m1 = cand + 2 * (size_t)S * d;
-  double* v1 = m1 + 2 * (size_t)q * S;
-  double* dx = v1 + 2 * (size_t)q * S;
-  double* dval = dx + (size_t)S * d;
-  int* dst = reinterpret_cast<int*>(dval + S);
-  int* dnev = dst + S;
-  SBO_HIP(hipMemcpyAsync(dA, &A, sizeof(RefineArgs), hipMemcpyHostToDevice, c->stream));
-  SBO_HIP(hipMemcpyAsync(dseed, seeds, sizeof(double) * (size_t)S * d, hipMemcpyHostToDevice, c->stream));
-  if ((rc = launch_posterior_on_list(c, dseed, S, m0, v0))) return rc;
-  const int n = mc.n;
-  const size_t tri_bytes = sizeof(double) * (size_t)A.nu * n * (n + 1) / 2;
-  const bool lds_tier = c->refine_lds && tri_bytes <= kRefLdsM;
-  const size_t lds = sizeof(double) * 2 * (size_t)n + (lds_tier ? tri_bytes : 0);
-  const int threads = n > 256 ? 1024 : 256;
-  if (S > 0x7fffffffLL) return fail(SBO_E_UNSUPPORTED, "too many seeds for one launch");
-  if (lds_tier) {
-    SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_refine<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_refine<true>, dim3((unsigned)S), dim3(threads), lds, c->stream, (const RefineArgs*)dA, (const double*)c->Fplain.p,
-                       (const double*)c->alpha64.p, (const double*)c->Xn.p, (const double*)dseed, (const double*)m0,
-                       (const double*)v0, S, cand, dst, dnev);
-  } else {
-    SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_refine<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_refine<false>, dim3((unsigned)S), dim3(threads), lds, c->stream, (const RefineArgs*)dA, (const double*)c->Fplain.p,
-                       (const double*)c->alpha64.p, (const double*)c->Xn.p, (const double*)dseed, (const double*)m0,
-                       (const double*)v0, S, cand, dst, dnev);
-  }
-  SBO_HIP(hipGetLastError());
-  if ((rc = launch_posterior_on_list(c, cand, 2 * S, m1, v1))) return rc;
-  hipLaunchKernelGGL(k_refine_accept, dim3((unsigned)std::min<long long>((S + 255) / 256, 1024)), dim3(256), 0, c->stream, (const RefineArgs*)dA, S,
-                     (const double*)dseed, (const double*)m0, (const double*)v0, (const double*)cand, (const double*)m1,
-                     (const double*)v1, dst, dx, dval);
-  SBO_HIP(hipGetLastError());
-  std::vector<double> hx((size_t)S * d), hv(S);
-  std::vector<int> hs(2 * (size_t)S);
-  SBO_HIP(hipMemcpyAsync(hx.data(), dx, sizeof(double) * (size_t)S * d, hipMemcpyDeviceToHost, c->stream));
-  SBO_HIP(hipMemcpyAsync(hv.data(), dval, sizeof(double) * S, hipMemcpyDeviceToHost, c->stream));
-  SBO_HIP(hipMemcpyAsync(hs.data(), dst, sizeof(int) * 2 * (size_t)S, hipMemcpyDeviceToHost, c->stream));
-  SBO_HIP(hipStreamSynchronize(c->stream));
+  std::vector<double> hx, hv;
+  std::vector<int> hs;
+  int rc;
+  if ((rc = refine_run(c, A, opts->max_eval, opts->tol, S, seeds, hx, hv, hs))) return rc;
   sbo_refine_result res{};
-  res.best = -1;
-  res.best_value = NAN;
-  const double sg = opts->maximize ? -1.0 : 1.0;
-  for (long long s = 0; s < S; ++s) {
-    res.evaluations += hs[S + s];
-    if (hs[s] == SBO_REFINE_CONVERGED) ++res.converged;
-    if (hs[s] == SBO_REFINE_INFEASIBLE_SEED || std::isnan(hv[s])) continue;
-    if (res.best < 0 || sg * hv[s] < sg * res.best_value) {           // (ties: the lowest index)
-      res.best = s;
-      res.best_value = hv[s];
-    }
-  }
+  res.best = refine_best(hv, hs, S, opts->maximize != 0, &res.evaluations, &res.converged);
+  res.best_value = res.best >= 0 ? hv[res.best] : NAN;
   for (int a = 0; a < SBO_MAX_D; ++a) res.best_x[a] = (res.best >= 0 && a < d) ? hx[(size_t)res.best * d + a] : 0.0;
   *result = res;
   if (x_out) std::copy(hx.begin(), hx.end(), x_out);
+  if (value_out) std::copy(hv.begin(), hv.end(), value_out);
+  if (status_out)
+    for (long long s = 0; s < S; ++s) status_out[s] = hs[s];
+  return SBO_OK;
+}
+
+// slot of output o in A.outs, appended when new
+static int refine_slot(RefineArgs& A, int o) {
+  for (int u = 0; u < A.nu; ++u)
+    if (A.outs[u] == o) return u;
+  A.outs[A.nu] = o;
+  return A.nu++;
+}
+
+extern "C" int sbo_refine_sets(sbo_ctx* c, const sbo_refine_sets_opts* opts, int64_t n_seeds, const double* seeds, const double* seeds_p,
+                               double* x_out, double* xp_out, double* value_out, int32_t* status_out, sbo_refine_sets_result* result) {
+  if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
+  if (!opts || !seeds || !result) return fail(SBO_E_INVALID, "NULL argument");
+  if (!c->has_model) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
+  if (c->dtype != SBO_F64) return fail(SBO_E_UNSUPPORTED, "sbo_refine_sets needs an fp64 model");
+  const ModelConst& mc = c->mc;
+  const int d = mc.d, q = mc.q;
+  if (opts->pair != 0 && opts->pair != 1) return fail(SBO_E_INVALID, "pair must be 0 or 1");
+  const bool pair = opts->pair != 0;
+  if (pair && 2 * d > SBO_MAX_D) return fail(SBO_E_UNSUPPORTED, "sbo_refine_sets: pair mode needs 2 d <= SBO_MAX_D (d <= 4)");
+  if (pair && !seeds_p) return fail(SBO_E_INVALID, "pair mode needs seeds_p");
+  if (n_seeds < 1 || n_seeds > (1LL << 24)) return fail(SBO_E_INVALID, "n_seeds out of range");
+  const bool dist = opts->kind == SBO_REFINE_DIST;
+  if (!dist && (opts->kind < SBO_MEAN || opts->kind > SBO_VAR)) return fail(SBO_E_INVALID, "bad objective kind");
+  if (!dist && (opts->objective < 0 || opts->objective >= q)) return fail(SBO_E_INVALID, "objective output out of range");
+  if (opts->maximize != 0 && opts->maximize != 1) return fail(SBO_E_INVALID, "maximize must be 0 or 1");
+  if (dist && opts->maximize) return fail(SBO_E_INVALID, "the distance objective is minimised only");
+  if (opts->objective_point != 0 && !(opts->objective_point == 1 && pair && !dist))
+    return fail(SBO_E_INVALID, "objective_point: 0 (x), or 1 (x') for a bound in pair mode");
+  if ((opts->safe_mask & 1u) || (q < 32 && (opts->safe_mask >> q) != 0))
+    return fail(SBO_E_INVALID, "safe_mask: bit 0 must be clear and no bit may reach q");
+  if ((opts->unsafe_mask & 1u) || (q < 32 && (opts->unsafe_mask >> q) != 0))
+    return fail(SBO_E_INVALID, "unsafe_mask: bit 0 must be clear and no bit may reach q");
+  if (opts->unsafe_mask && !pair) return fail(SBO_E_INVALID, "unsafe_mask constrains x': pair mode only");
+  if (opts->use_level != 0 && opts->use_level != 1) return fail(SBO_E_INVALID, "use_level must be 0 or 1");
+  if (opts->use_level && (opts->level_output < 0 || opts->level_output >= q || !std::isfinite(opts->level)))
+    return fail(SBO_E_INVALID, "the level term needs an output in [0, q) and a finite level");
+  if (opts->use_link != 0 && opts->use_link != 1) return fail(SBO_E_INVALID, "use_link must be 0 or 1");
+  if (opts->use_link && !pair) return fail(SBO_E_INVALID, "the link joins x and x': pair mode only");
+  if (opts->use_link && (opts->link_output < 1 || opts->link_output >= q || !(opts->L >= 0.0) || !std::isfinite(opts->L)))
+    return fail(SBO_E_INVALID, "the link needs a constraint output in [1, q) and a finite L >= 0");
+  if (const char* why = refine_check_common(d, opts->b, opts->tol, opts->lo, opts->hi, opts->use_ball, opts->r, opts->x_0))
+    return fail(SBO_E_INVALID, why);
+  if (dist)
+    for (int a = 0; a < d; ++a)
+      if (!std::isfinite(opts->target[a])) return fail(SBO_E_INVALID, "the distance objective needs a finite target");
+  RefineArgs A{};
+  A.np = pair ? 2 : 1;
+  A.nz = A.np * d;
+  A.kind = opts->kind;
+  A.maximize = opts->maximize;
+  A.obj_point = opts->objective_point;
+  A.obj_slot = 0;
+  if (!dist) refine_slot(A, opts->objective);         // (objective first, as sbo_refine lays the slots out)
+  for (int o = 1; o < q; ++o)
+    if ((opts->safe_mask >> o) & 1u) A.con_slots |= 1 << refine_slot(A, o);
+  for (int o = 1; o < q; ++o)
+    if ((opts->unsafe_mask >> o) & 1u) A.unsafe_slots |= 1 << refine_slot(A, o);
+  A.level_slot = opts->use_level ? refine_slot(A, opts->level_output) : -1;
+  A.link_slot = opts->use_link ? refine_slot(A, opts->link_output) : -1;
+  A.level = opts->use_level ? opts->level : 0.0;
+  A.L = opts->use_link ? opts->L : 0.0;
+  A.use_ball = opts->use_ball;
+  A.b = opts->b;
+  A.r = opts->use_ball ? opts->r : 0.0;
+  A.dscale = 0.0;
+  for (int a = 0; a < d; ++a) {
+    for (int p = 0; p < A.np; ++p) {
+      A.lo[p * d + a] = opts->lo[a];
+      A.hi[p * d + a] = opts->hi[a];
+    }
+    A.x0[a] = opts->use_ball ? opts->x_0[a] : 0.0;
+    A.tgt[a] = dist ? opts->target[a] : 0.0;
+    A.dscale += (opts->hi[a] - opts->lo[a]) * (opts->hi[a] - opts->lo[a]);
+  }
+  if (!(A.dscale > 0.0)) A.dscale = 1.0;
+  const long long S = n_seeds;
+  std::vector<double> hseed((size_t)S * A.nz);          // [S][np][d]
+  for (long long s = 0; s < S; ++s)
+    for (int a = 0; a < d; ++a) {
+      hseed[(size_t)s * A.nz + a] = seeds[(size_t)s * d + a];
+      if (pair) hseed[(size_t)s * A.nz + d + a] = seeds_p[(size_t)s * d + a];
+    }
+  std::vector<double> hz, hv;
+  std::vector<int> hs;
+  int rc;
+  if ((rc = refine_run(c, A, opts->max_eval, opts->tol, S, hseed.data(), hz, hv, hs))) return rc;
+  sbo_refine_sets_result res{};
+  res.best = refine_best(hv, hs, S, opts->maximize != 0, &res.evaluations, &res.converged);
+  res.best_value = res.best >= 0 ? hv[res.best] : NAN;
+  for (int a = 0; a < SBO_MAX_D; ++a) {
+    const bool on = res.best >= 0 && a < d;
+    res.best_x[a] = on ? hz[(size_t)res.best * A.nz + a] : 0.0;
+    res.best_xp[a] = (on && pair) ? hz[(size_t)res.best * A.nz + d + a] : 0.0;
+  }
+  *result = res;
+  for (long long s = 0; s < S; ++s)
+    for (int a = 0; a < d; ++a) {
+      if (x_out) x_out[(size_t)s * d + a] = hz[(size_t)s * A.nz + a];
+      if (xp_out && pair) xp_out[(size_t)s * d + a] = hz[(size_t)s * A.nz + d + a];
+    }
   if (value_out) std::copy(hv.begin(), hv.end(), value_out);
   if (status_out)
     for (long long s = 0; s < S; ++s) status_out[s] = hs[s];

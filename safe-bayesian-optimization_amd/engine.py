@@ -388,6 +388,98 @@ class SweepEngine:
         return {"x": x, "value": val, "status": st, "best": int(res.best), "best_x": np.array(res.best_x[:d]),
                 "best_value": float(res.best_value), "evaluations": int(res.evaluations), "converged": int(res.converged)}
 
+    def refine_sets(self, b: float, seeds, seeds_p=None, *, objective: int = 0, kind: str = "lcb", at: str = "x", maximize: bool = False,
+                    safe=None, unsafe=None, level=None, link=None, target=None, lo, hi, x_0=None, r=None,
+                    max_eval: int | None = None, tol: float | None = None) -> dict:
+        """``refine`` for the set-valued steps (``sbo_refine_sets``).  With ``seeds_p`` [S, d] the variable is
+        the pair (x, x') from (``seeds``, ``seeds_p``) -- d <= 4 --, else the point x.  Objective: ``kind`` of output ``objective``
+        at x or (``at="xp"``) at x', or ``kind="dist"``: the distance from x to ``target`` [d], minimised.  Terms: lcb_c(x) >= 0 for c
+        in ``safe`` (None = every constraint, [] = none); lcb_c(x') <= 0 for c in ``unsafe`` (pair mode: None = every constraint;
+        single mode: none); ``level=(o, value)``: lcb_o(x) <= value; ``link=(c, L)``: ucb_c(x) - L ||x - x' + 1e-8|| >= 0; the box
+        (both points) and the ball (x).  Returns what ``refine`` returns -- ``evaluations`` counts each point of a pair -- and in
+        pair mode ``xp`` [S, d] and ``best_xp``."""
+        kinds = {"mean": L.SBO_MEAN, "ucb": L.SBO_UCB, "lcb": L.SBO_LCB, "var": L.SBO_VAR, "dist": L.SBO_REFINE_DIST}
+        if kind not in kinds:
+            raise ValueError("kind must be 'mean', 'ucb', 'lcb', 'var' or 'dist'")
+        if at not in ("x", "xp"):
+            raise ValueError("at must be 'x' or 'xp'")
+        d = self.d
+        pair = seeds_p is not None
+
+        def seed_array(s):
+            s = _f64(s)
+            if s.ndim == 1:
+                s = s.reshape(1, -1)
+            if d < 1 or s.ndim != 2 or s.shape[1] != d:
+                raise ValueError("seeds must be [S, d] for the model's d")
+            return np.ascontiguousarray(s)
+
+        def mask_of(cs):
+            m = 0
+            for c in cs:
+                c = int(c)
+                if c < 0 or c >= 32:
+                    raise ValueError("constraint index out of range")
+                m |= 1 << c
+            return m
+
+        S = seed_array(seeds)
+        Sp = seed_array(seeds_p) if pair else None
+        if pair and Sp.shape != S.shape:
+            raise ValueError("seeds and seeds_p must have the same shape")
+        opts = L.RefineSetsOpts()
+        opts.b = float(b)
+        opts.pair = int(pair)
+        opts.objective = int(objective)
+        opts.kind = kinds[kind]
+        opts.objective_point = int(at == "xp")
+        opts.maximize = int(bool(maximize))
+        opts.safe_mask = mask_of(range(1, self.q) if safe is None else safe)
+        opts.unsafe_mask = mask_of((range(1, self.q) if pair else ()) if unsafe is None else unsafe)
+        if level is not None:
+            opts.use_level, opts.level_output, opts.level = 1, int(level[0]), float(level[1])
+        if link is not None:
+            opts.use_link, opts.link_output, opts.L = 1, int(link[0]), float(link[1])
+        lo, hi = _f64(lo).reshape(-1), _f64(hi).reshape(-1)
+        if lo.shape != (d,) or hi.shape != (d,):
+            raise ValueError("lo and hi must have shape [d]")
+        for a in range(d):
+            opts.lo[a], opts.hi[a] = lo[a], hi[a]
+        if (x_0 is None) != (r is None):
+            raise ValueError("the ball needs both x_0 and r")
+        if x_0 is not None:
+            x0 = _f64(x_0).reshape(-1)
+            if x0.shape != (d,):
+                raise ValueError("x_0 must have shape [d]")
+            opts.use_ball = 1
+            for a in range(d):
+                opts.x_0[a] = x0[a]
+            opts.r = float(r)
+        if (kind == "dist") != (target is not None):
+            raise ValueError("kind='dist' and target go together")
+        if target is not None:
+            t = _f64(target).reshape(-1)
+            if t.shape != (d,):
+                raise ValueError("target must have shape [d]")
+            for a in range(d):
+                opts.target[a] = t[a]
+        opts.max_eval = int(max_eval) if max_eval is not None else 0
+        opts.tol = float(tol) if tol is not None else 0.0
+        n = S.shape[0]
+        x = np.empty((n, d))
+        xp = np.empty((n, d)) if pair else None
+        val = np.empty(n)
+        st = np.empty(n, dtype=np.int32)
+        res = L.RefineSetsResult()
+        L.check(self._lib.sbo_refine_sets(self._ctx, C.byref(opts), n, _ptr(S), _ptr(Sp) if pair else None, _ptr(x),
+                                          _ptr(xp) if pair else None, _ptr(val), _ptr(st), C.byref(res)))
+        out = {"x": x, "value": val, "status": st, "best": int(res.best), "best_x": np.array(res.best_x[:d]),
+               "best_value": float(res.best_value), "evaluations": int(res.evaluations), "converged": int(res.converged)}
+        if pair:
+            out["xp"] = xp
+            out["best_xp"] = np.array(res.best_xp[:d])
+        return out
+
     def mask(self, which: str, c: int = 0) -> np.ndarray:
         w = {"S": L.SBO_MASK_S, "U": L.SBO_MASK_U, "M": L.SBO_MASK_M, "G": L.SBO_MASK_G, "O": L.SBO_MASK_O}[which]
         out = np.empty(self.n_local, dtype=np.uint8)
