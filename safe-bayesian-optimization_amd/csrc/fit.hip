@@ -13,6 +13,7 @@
 #include <cmath>
 #include <vector>
 #include "device_common.hpp"
+#include "pbfgs.hpp"
 
 namespace sbo {
 
@@ -467,118 +468,55 @@ __global__ __launch_bounds__(1024) void k_nll_grad_batch(int n, int d, const dou
 }
 
 // ---- projected BFGS on the box, one workgroup per (output, start) ------------------------------------------------------------
-// Thread 0 runs the (d + 2)-dimensional algebra on LDS state; the whole workgroup evaluates NLL + gradient at thread 0's trial
-// point.  See DESIGN.md section 10 for the contract.
+// Thread 0 runs the (d + 2)-dimensional algebra on LDS state -- the shared core of pbfgs.hpp in the unit metric --; the whole
+// workgroup evaluates NLL + gradient at thread 0's trial point.  See DESIGN.md section 10 for the contract.
 struct FitState {
-  double x[kFitD], g[kFitD], p[kFitD], lo[kFitD], hi[kFitD], H[kFitD * kFitD];
-  double f, t;
-  int phase, iter, nev, halvings, status, h_identity;
+  PbfgsState<kFitD> s;
+  double lo[kFitD], hi[kFitD];
+  double f;
+  int phase, iter, nev, status;
 };
 enum { FIT_PH_START = 0, FIT_PH_SEARCH = 1 };
 
-__device__ __forceinline__ double clip_to(double v, double lo, double hi) { return v < lo ? lo : v > hi ? hi : v; }
+__device__ const double kFitUnit[kFitD] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
 
-__device__ double fit_pgnorm(const FitState& S, int D) {
-  double pg = 0.0;
-  for (int a = 0; a < D; ++a) pg = fmax(pg, fabs(clip_to(S.x[a] - S.g[a], S.lo[a], S.hi[a]) - S.x[a]));
-  return pg;
-}
-
-__device__ void fit_reset_h(FitState& S, int D) {
-  for (int a = 0; a < D * D; ++a) S.H[a] = 0.0;
-  for (int a = 0; a < D; ++a) S.H[a * D + a] = 1.0;
-  S.h_identity = 1;
-}
+// the box of the hyper-parameters in the unit metric; a steepest-descent step moves at most one unit of log scale
+__device__ __forceinline__ PbfgsBox fit_box(const FitState& S) { return {S.lo, S.hi, kFitUnit, kFitUnit, 1.0}; }
 
 // Start a new iteration at the accepted point: true with the first trial of the line search in `trial`, false when done.
 __device__ bool fit_new_iteration(FitState& S, int D, double* trial, int maxiter, double gtol) {
-  if (fit_pgnorm(S, D) <= gtol) { S.status = SBO_FIT_GTOL; return false; }
+  const PbfgsBox bx = fit_box(S);
+  if (pbfgs_pgnorm(S.s, bx, D) <= gtol) { S.status = SBO_FIT_GTOL; return false; }
   if (S.iter >= maxiter) { S.status = SBO_FIT_MAXITER; return false; }
-  bool fr[kFitD];
-  for (int a = 0; a < D; ++a)         // held: at a bound with the gradient pointing out of the box
-    fr[a] = !((S.x[a] <= S.lo[a] && S.g[a] > 0.0) || (S.x[a] >= S.hi[a] && S.g[a] < 0.0));
-  double gp = 0.0;
-  for (int a = 0; a < D; ++a) {
-    double s = 0.0;
-    if (fr[a])
-      for (int b = 0; b < D; ++b)
-        if (fr[b]) s += S.H[a * D + b] * S.g[b];
-    S.p[a] = -s;
-    gp += S.g[a] * S.p[a];
-  }
-  if (!(gp < 0.0)) {                  // not a descent direction: restart from steepest descent
-    fit_reset_h(S, D);
-    for (int a = 0; a < D; ++a) S.p[a] = fr[a] ? -S.g[a] : 0.0;
-  }
-  double pn = 0.0;
-  for (int a = 0; a < D; ++a) pn = fmax(pn, fabs(S.p[a]));
-  S.t = S.h_identity ? fmin(1.0, 1.0 / pn) : 1.0;   // a steepest-descent step moves at most one unit of log scale
-  S.halvings = 0;
+  pbfgs_direction(S.s, bx, D, trial);
   S.phase = FIT_PH_SEARCH;
-  for (int a = 0; a < D; ++a) trial[a] = clip_to(S.x[a] + S.t * S.p[a], S.lo[a], S.hi[a]);
   return true;
 }
 
 // Consume the evaluation (ft, tg) of `trial`; true when `trial` holds the next point to evaluate.
 __device__ __noinline__ bool fit_advance(FitState& S, int D, double ft, const double* tg, double* trial, int maxiter, double ftol, double gtol) {
   ++S.nev;
-  bool ok = ft < INFINITY;
+  bool ok = ft < INFINITY;            // (a trial without a factor, or with a non-finite gradient, is refused)
   for (int a = 0; a < D; ++a) ok = ok && isfinite(tg[a]);
   if (S.phase == FIT_PH_START) {
-    for (int a = 0; a < D; ++a) { S.x[a] = trial[a]; S.g[a] = tg[a]; }
+    for (int a = 0; a < D; ++a) { S.s.x[a] = trial[a]; S.s.g[a] = tg[a]; }
     S.f = ft;
     if (!ok) { S.status = SBO_FIT_NOT_PD; return false; }
     return fit_new_iteration(S, D, trial, maxiter, gtol);
   }
-  double dec = 0.0;
-  bool moved = false;
-  for (int a = 0; a < D; ++a) {
-    dec += S.g[a] * (trial[a] - S.x[a]);
-    moved = moved || trial[a] != S.x[a];
-  }
-  if (ok && moved && ft <= S.f + 1e-4 * dec) {                       // Armijo along the projection arc
-    double s[kFitD], yv[kFitD], sy = 0.0, ss = 0.0, yy = 0.0;
-    for (int a = 0; a < D; ++a) {
-      s[a] = trial[a] - S.x[a];
-      yv[a] = tg[a] - S.g[a];
-      sy += s[a] * yv[a];
-      ss += s[a] * s[a];
-      yy += yv[a] * yv[a];
-      S.x[a] = trial[a];
-      S.g[a] = tg[a];
-    }
+  const PbfgsBox bx = fit_box(S);
+  bool moved;
+  if (pbfgs_armijo(S.s, D, trial, ok, ft, S.f, moved)) {
+    pbfgs_update(S.s, bx, D, trial, tg);
     const double fprev = S.f;
     S.f = ft;
     ++S.iter;
-    if (sy > 1e-10 * sqrt(ss * yy)) {                                // BFGS update of the inverse Hessian, skipped unless s^T y > 0
-      if (S.h_identity) {
-        const double scale = sy / yy;
-        for (int a = 0; a < D; ++a) S.H[a * D + a] = scale;
-        S.h_identity = 0;
-      }
-      double Hy[kFitD], yHy = 0.0;
-      for (int a = 0; a < D; ++a) {
-        double v = 0.0;
-        for (int b = 0; b < D; ++b) v += S.H[a * D + b] * yv[b];
-        Hy[a] = v;
-        yHy += yv[a] * v;
-      }
-      const double rho = 1.0 / sy;
-      const double c = rho * rho * yHy + rho;
-      for (int a = 0; a < D; ++a)
-        for (int b = 0; b < D; ++b) S.H[a * D + b] += c * s[a] * s[b] - rho * (Hy[a] * s[b] + s[a] * Hy[b]);
-    }
     if (fabs(fprev - S.f) < ftol) { S.status = SBO_FIT_FTOL; return false; }
     return fit_new_iteration(S, D, trial, maxiter, gtol);
   }
-  if (moved && S.halvings < 60) {                                    // backtrack
-    ++S.halvings;
-    S.t *= 0.5;
-    for (int a = 0; a < D; ++a) trial[a] = clip_to(S.x[a] + S.t * S.p[a], S.lo[a], S.hi[a]);
-    return true;
-  }
-  if (S.h_identity) { S.status = SBO_FIT_LINESEARCH; return false; }
-  fit_reset_h(S, D);                                                 // the quasi-Newton direction failed: one steepest-descent try
+  if (pbfgs_backtrack(S.s, bx, D, moved, trial)) return true;
+  if (S.s.h_identity) { S.status = SBO_FIT_LINESEARCH; return false; }
+  pbfgs_reset_h(S.s, bx, D);                                         // the quasi-Newton direction failed: one steepest-descent try
   ++S.iter;
   return fit_new_iteration(S, D, trial, maxiter, gtol);
 }
@@ -601,7 +539,7 @@ __global__ __launch_bounds__(1024) void k_fit_local(int n, int d, int P, const d
       S.hi[a] = hi[a];
       trial[a] = clip_to(starts[((size_t)o * starts_per_output + s) * D + a], lo[a], hi[a]);   // SLSQP clips x0 into the bounds
     }
-    fit_reset_h(S, D);
+    pbfgs_reset_h(S.s, fit_box(S), D);
     S.phase = FIT_PH_START;
     S.iter = S.nev = 0;
     S.status = -1;
@@ -616,9 +554,9 @@ __global__ __launch_bounds__(1024) void k_fit_local(int n, int d, int P, const d
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    for (int a = 0; a < D; ++a) h_out[(size_t)m * D + a] = S.x[a];
+    for (int a = 0; a < D; ++a) h_out[(size_t)m * D + a] = S.s.x[a];
     f_out[m] = S.f;
-    pg_out[m] = S.status == SBO_FIT_NOT_PD ? NAN : fit_pgnorm(S, D);
+    pg_out[m] = S.status == SBO_FIT_NOT_PD ? NAN : pbfgs_pgnorm(S.s, fit_box(S), D);
     it_out[m] = S.iter;
     ev_out[m] = S.nev;
     st_out[m] = S.status;

@@ -3,7 +3,8 @@
 // The sweeps restate every continuous acquisition of the reference (SciPy DE in models/SafeOpt.py:47-51, models/GoOSE.py:63-67,
 // models/GP_TR.py:43-51; SLSQP multistarts in models/BayesRTOjax.py:17-85) as an arg-min over candidates.  This file polishes such
 // a winner: one workgroup per seed runs a projected BFGS on a log-barrier function of the exact fp64 posterior (box by projection,
-// lcb_c >= 0 and the trust-region ball by the barrier), the whole iteration inside one launch as k_fit_local does (fit.hip).  The
+// lcb_c >= 0 and the trust-region ball by the barrier), the whole iteration inside one launch.  The projected BFGS is the core
+// k_fit_local runs (pbfgs.hpp), here in the metric of the box spans; the barrier stages and the evaluation budget are this file's.  The
 // candidates it returns are then re-evaluated by the library's exact list evaluator (launch_posterior_on_list, the values
 // sbo_bounds gives at those points) and accepted only when they pass the sweep's S predicate there and are no worse than the seed.
 //
@@ -15,6 +16,7 @@
 #include <vector>
 #include "internal.hpp"
 #include "device_common.hpp"
+#include "pbfgs.hpp"
 
 namespace sbo {
 
@@ -52,14 +54,17 @@ struct RefEval {
 };
 
 struct RefState {
-  double x[kMaxD], g[kMaxD], p[kMaxD], H[kMaxD * kMaxD], D2[kMaxD], span[kMaxD], xb[kMaxD];
+  PbfgsState<kMaxD> s;                    // the shared core's state (pbfgs.hpp); s.g = go + mu gB
+  double D2[kMaxD], span[kMaxD], xb[kMaxD];   // the metric span^2, the (ball-limited) box widths, the best-objective iterate
   double fo, B, go[kMaxD], gB[kMaxD];     // objective part and barrier sum at x, with gradients
-  double f, mu, t, obj, objb;             // f = fo + mu B; obj / objb: sign-adjusted objective at x / at xb
-  int phase, nev, halvings, status, h_identity, nbar;
+  double f, mu, obj, objb;                // f = fo + mu B; obj / objb: sign-adjusted objective at x / at xb
+  int phase, nev, status, nbar;
 };
 enum { REF_PH_START = 0, REF_PH_SEARCH = 1 };
 
-__device__ __forceinline__ double ref_clip(double v, double lo, double hi) { return v < lo ? lo : v > hi ? hi : v; }
+// the box of the solver's variables in the metric of its spans; a steepest-descent step moves at most a tenth of the
+// (ball-limited) box
+__device__ __forceinline__ PbfgsBox ref_box(const RefState& S, const RefineArgs& A) { return {A.lo, A.hi, S.D2, S.span, 0.1}; }
 
 // sums of cnt per-thread values over the workgroup: butterfly within a wave, then the waves in order (thread 0) -> out[]
 __device__ __forceinline__ void ref_block_sum(const double* v, int cnt, double (*part)[kMaxD + 1], double* out) {
@@ -268,14 +273,8 @@ __device__ bool ref_terms(const RefineArgs& A, const RefEval* Ev, const double* 
   B = 0.0;
   for (int u = 0; u < A.nu; ++u) {
     if (!((A.con_slots >> u) & 1)) continue;
-    double gc = E.m[u], ggc[kMaxD];
-    for (int a = 0; a < d; ++a) ggc[a] = E.gm[u][a];
-    if (b != 0.0) {
-      if (E.clamp[u] || !(E.v[u] > 0.0)) return false;
-      const double sd = sqrt(E.v[u]);
-      gc = E.m[u] - b * sd;
-      for (int a = 0; a < d; ++a) ggc[a] -= b * E.gv[u][a] / (2.0 * sd);
-    }
+    double gc, ggc[kMaxD];
+    if (!ref_conf(E, u, b, -1.0, d, gc, ggc)) return false;
     if (!(gc > 0.0)) return false;
     B -= log(gc / A.mc.Y_std[A.outs[u]]);
     for (int a = 0; a < d; ++a) gB[a] -= ggc[a] / gc;
@@ -326,53 +325,20 @@ __device__ bool ref_terms(const RefineArgs& A, const RefEval* Ev, const double* 
   return ok;
 }
 
-__device__ double ref_pgnorm(const RefState& S, const RefineArgs& A) {
-  double pg = 0.0;
-  for (int a = 0; a < A.nz; ++a)
-    if (S.span[a] > 0.0) pg = fmax(pg, fabs(ref_clip(S.x[a] - S.D2[a] * S.g[a], A.lo[a], A.hi[a]) - S.x[a]) / S.span[a]);
-  return pg;
-}
-
-__device__ void ref_reset_h(RefState& S, int d) {
-  for (int a = 0; a < d * d; ++a) S.H[a] = 0.0;
-  for (int a = 0; a < d; ++a) S.H[a * d + a] = S.D2[a];
-  S.h_identity = 1;
-}
-
 // Next search direction at the accepted point (lowering the barrier weight between stages): true with the first trial in `trial`
 __device__ bool ref_new_iteration(RefState& S, const RefineArgs& A, double* trial) {
   const int d = A.nz;                 // (the solver's variables)
+  const PbfgsBox bx = ref_box(S, A);
   for (;;) {
     S.f = S.fo + S.mu * S.B;
-    for (int a = 0; a < d; ++a) S.g[a] = S.go[a] + S.mu * S.gB[a];
+    for (int a = 0; a < d; ++a) S.s.g[a] = S.go[a] + S.mu * S.gB[a];
     const double stol = S.mu > kRefMuFloor ? fmax(A.tol, S.mu) : A.tol;
-    if (ref_pgnorm(S, A) > stol) break;
+    if (pbfgs_pgnorm(S.s, bx, d) > stol) break;
     if (S.mu <= kRefMuFloor) { S.status = SBO_REFINE_CONVERGED; return false; }
     S.mu = fmax(kRefMuFloor, S.mu * kRefMuStep);
   }
-  bool fr[kMaxD];
-  for (int a = 0; a < d; ++a)         // held: at a face with the gradient pointing out of the box (or a degenerate axis)
-    fr[a] = S.span[a] > 0.0 && !((S.x[a] <= A.lo[a] && S.g[a] > 0.0) || (S.x[a] >= A.hi[a] && S.g[a] < 0.0));
-  double gp = 0.0;
-  for (int a = 0; a < d; ++a) {
-    double s = 0.0;
-    if (fr[a])
-      for (int c = 0; c < d; ++c)
-        if (fr[c]) s += S.H[a * d + c] * S.g[c];
-    S.p[a] = -s;
-    gp += S.g[a] * S.p[a];
-  }
-  if (!(gp < 0.0)) {                  // not a descent direction: restart from (scaled) steepest descent
-    ref_reset_h(S, d);
-    for (int a = 0; a < d; ++a) S.p[a] = fr[a] ? -S.D2[a] * S.g[a] : 0.0;
-  }
-  double pn = 0.0;
-  for (int a = 0; a < d; ++a)
-    if (S.span[a] > 0.0) pn = fmax(pn, fabs(S.p[a]) / S.span[a]);
-  S.t = S.h_identity ? fmin(1.0, 0.1 / pn) : 1.0;   // a steepest-descent step moves at most a tenth of the (ball-limited) box
-  S.halvings = 0;
+  pbfgs_direction(S.s, bx, d, trial);
   S.phase = REF_PH_SEARCH;
-  for (int a = 0; a < d; ++a) trial[a] = ref_clip(S.x[a] + S.t * S.p[a], A.lo[a], A.hi[a]);
   return true;
 }
 
@@ -397,64 +363,29 @@ __device__ __noinline__ bool ref_advance(RefState& S, const RefineArgs& A, const
     if (S.nev >= A.max_eval) { S.status = SBO_REFINE_MAX_EVAL; return false; }
     return ref_new_iteration(S, A, trial);
   }
-  const double ft = fo + S.mu * B;
-  double dec = 0.0;
-  bool moved = false;
-  for (int a = 0; a < d; ++a) {
-    dec += S.g[a] * (trial[a] - S.x[a]);
-    moved = moved || trial[a] != S.x[a];
-  }
-  if (ok && moved && ft <= S.f + 1e-4 * dec) {                        // Armijo along the projection arc
-    double s[kMaxD], yv[kMaxD], sy = 0.0, ss = 0.0, yy = 0.0;
+  const PbfgsBox bx = ref_box(S, A);
+  bool moved;
+  if (pbfgs_armijo(S.s, d, trial, ok, fo + S.mu * B, S.f, moved)) {
     for (int a = 0; a < d; ++a) {
-      s[a] = trial[a] - S.x[a];
-      yv[a] = (go[a] + S.mu * gB[a]) - S.g[a];
-      sy += s[a] * yv[a];
-      ss += s[a] * s[a];
-      yy += yv[a] * yv[a];
-      S.x[a] = trial[a];
       S.go[a] = go[a];
       S.gB[a] = gB[a];
+      go[a] += S.mu * gB[a];          // (from here on the barrier function's gradient at this stage's weight)
     }
+    pbfgs_update(S.s, bx, d, trial, go);
     const double fprev = S.f;
     S.fo = fo; S.B = B; S.obj = obj;
     if (obj < S.objb) {
       S.objb = obj;
-      for (int a = 0; a < d; ++a) S.xb[a] = S.x[a];
-    }
-    if (sy > 1e-10 * sqrt(ss * yy)) {                                 // BFGS update of the inverse Hessian, skipped unless s^T y > 0
-      if (S.h_identity) {
-        double yDy = 0.0;
-        for (int a = 0; a < d; ++a) yDy += yv[a] * S.D2[a] * yv[a];
-        const double scale = sy / yDy;
-        for (int a = 0; a < d; ++a) S.H[a * d + a] = scale * S.D2[a];
-        S.h_identity = 0;
-      }
-      double Hy[kMaxD], yHy = 0.0;
-      for (int a = 0; a < d; ++a) {
-        double v = 0.0;
-        for (int c = 0; c < d; ++c) v += S.H[a * d + c] * yv[c];
-        Hy[a] = v;
-        yHy += yv[a] * v;
-      }
-      const double rho = 1.0 / sy;
-      const double cc = rho * rho * yHy + rho;
-      for (int a = 0; a < d; ++a)
-        for (int c = 0; c < d; ++c) S.H[a * d + c] += cc * s[a] * s[c] - rho * (Hy[a] * s[c] + s[a] * Hy[c]);
+      for (int a = 0; a < d; ++a) S.xb[a] = S.s.x[a];
     }
     if (S.nev >= A.max_eval) { S.status = SBO_REFINE_MAX_EVAL; return false; }
     if (fabs(fprev - (S.fo + S.mu * S.B)) <= 1e-15 * (1.0 + fabs(fprev))) return ref_stage_end(S, A, trial);
-    return ref_new_iteration(S, A, trial);
+    return ref_new_iteration(S, A, trial);   // (recomputes s.g from go and gB: the same expression, or a lower weight's)
   }
   if (S.nev >= A.max_eval) { S.status = SBO_REFINE_MAX_EVAL; return false; }
-  if (moved && S.halvings < 60) {                                    // backtrack
-    ++S.halvings;
-    S.t *= 0.5;
-    for (int a = 0; a < d; ++a) trial[a] = ref_clip(S.x[a] + S.t * S.p[a], A.lo[a], A.hi[a]);
-    return true;
-  }
-  if (S.h_identity) return ref_stage_end(S, A, trial);
-  ref_reset_h(S, d);                                                 // the quasi-Newton direction failed: one steepest-descent try
+  if (pbfgs_backtrack(S.s, bx, d, moved, trial)) return true;
+  if (S.s.h_identity) return ref_stage_end(S, A, trial);
+  pbfgs_reset_h(S.s, bx, d);                                         // the quasi-Newton direction failed: one steepest-descent try
   return ref_new_iteration(S, A, trial);
 }
 
@@ -564,7 +495,7 @@ __global__ __launch_bounds__(1024) void k_refine(const RefineArgs* __restrict__ 
   if (threadIdx.x == 0) {
     for (int a = 0; a < nz; ++a) {
       trial[a] = seeds[s * nz + a];
-      R.x[a] = R.xb[a] = trial[a];
+      R.s.x[a] = R.xb[a] = trial[a];
       const double w = A.hi[a] - A.lo[a];
       R.span[a] = (A.use_ball && a < d) ? fmin(w, 2.0 * A.r) : w;
       R.D2[a] = R.span[a] * R.span[a];
@@ -575,7 +506,7 @@ __global__ __launch_bounds__(1024) void k_refine(const RefineArgs* __restrict__ 
     R.nbar = __popc((unsigned)A.con_slots) + (A.use_ball ? 1 : 0) + __popc((unsigned)A.unsafe_slots) + (A.level_slot >= 0 ? 1 : 0) +
              (A.link_slot >= 0 ? 1 : 0);
     R.phase = REF_PH_START;
-    ref_reset_h(R, nz);
+    pbfgs_reset_h(R.s, ref_box(R, A), nz);
     go = R.status < 0;
   }
   __syncthreads();
@@ -586,7 +517,7 @@ __global__ __launch_bounds__(1024) void k_refine(const RefineArgs* __restrict__ 
   }
   if (threadIdx.x == 0) {
     for (int a = 0; a < nz; ++a) {
-      cand[(2 * s) * nz + a] = R.x[a];
+      cand[(2 * s) * nz + a] = R.s.x[a];
       cand[(2 * s + 1) * nz + a] = R.xb[a];
     }
     st_out[s] = R.status;
@@ -701,95 +632,6 @@ static int refine_run(sbo_ctx* c, RefineArgs& A, int max_eval, double tol, long 
   return SBO_OK;
 }
 
-// the seed whose returned point is best (ties: the lowest index; infeasible seeds and NaN values never), -1 if none
-static long long refine_best(const std::vector<double>& hv, const std::vector<int>& hs, long long S, bool maximize, int64_t* evaluations,
-                             int32_t* converged) {
-  long long best = -1;
-  const double sg = maximize ? -1.0 : 1.0;
-  for (long long s = 0; s < S; ++s) {
-    *evaluations += hs[S + s];
-    if (hs[s] == SBO_REFINE_CONVERGED) ++*converged;
-    if (hs[s] == SBO_REFINE_INFEASIBLE_SEED || std::isnan(hv[s])) continue;
-    if (best < 0 || sg * hv[s] < sg * hv[best]) best = s;
-  }
-  return best;
-}
-
-// the checks sbo_refine_opts and sbo_refine_sets_opts share; nullptr when they pass
-static const char* refine_check_common(int d, double b, double tol, const double* lo, const double* hi, int use_ball, double r, const double* x_0) {
-  if (!(b >= 0.0) || !std::isfinite(b)) return "confidence multiplier b must be finite and >= 0";
-  if (std::isnan(tol)) return "tol is NaN";
-  for (int a = 0; a < d; ++a)
-    if (!std::isfinite(lo[a]) || !std::isfinite(hi[a]) || !(lo[a] <= hi[a])) return "box needs finite lo <= hi";
-  if (use_ball != 0 && use_ball != 1) return "use_ball must be 0 or 1";
-  if (use_ball) {
-    if (!(r > 0.0) || !std::isfinite(r)) return "ball radius must be finite and > 0";
-    for (int a = 0; a < d; ++a)
-      if (!std::isfinite(x_0[a])) return "ball centre must be finite";
-  }
-  return nullptr;
-}
-
-}  // namespace sbo
-
-using namespace sbo;
-
-extern "C" int sbo_refine(sbo_ctx* c, const sbo_refine_opts* opts, int64_t n_seeds, const double* seeds, double* x_out,
-                          double* value_out, int32_t* status_out, sbo_refine_result* result) {
-  if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
-  if (!opts || !seeds || !result) return fail(SBO_E_INVALID, "NULL argument");
-  if (!c->has_model) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
-  if (c->dtype != SBO_F64) return fail(SBO_E_UNSUPPORTED, "sbo_refine needs an fp64 model");
-  const ModelConst& mc = c->mc;
-  const int d = mc.d, q = mc.q;
-  if (n_seeds < 1 || n_seeds > (1LL << 24)) return fail(SBO_E_INVALID, "n_seeds out of range");
-  if (opts->objective < 0 || opts->objective >= q) return fail(SBO_E_INVALID, "objective output out of range");
-  if (opts->kind < SBO_MEAN || opts->kind > SBO_VAR) return fail(SBO_E_INVALID, "bad bound kind");
-  if (opts->maximize != 0 && opts->maximize != 1) return fail(SBO_E_INVALID, "maximize must be 0 or 1");
-  if ((opts->constraint_mask & 1u) || (q < 32 && (opts->constraint_mask >> q) != 0))
-    return fail(SBO_E_INVALID, "constraint_mask: bit 0 must be clear and no bit may reach q");
-  if (const char* why = refine_check_common(d, opts->b, opts->tol, opts->lo, opts->hi, opts->use_ball, opts->r, opts->x_0))
-    return fail(SBO_E_INVALID, why);
-  RefineArgs A{};
-  A.np = 1;
-  A.nz = d;
-  A.level_slot = A.link_slot = -1;
-  A.outs[0] = opts->objective;
-  A.nu = 1;
-  for (int o = 1; o < q; ++o) {
-    if (!((opts->constraint_mask >> o) & 1u)) continue;
-    if (o == opts->objective) { A.con_slots |= 1; continue; }
-    A.con_slots |= 1 << A.nu;
-    A.outs[A.nu++] = o;
-  }
-  A.obj_slot = 0;
-  A.kind = opts->kind;
-  A.maximize = opts->maximize;
-  A.use_ball = opts->use_ball;
-  A.b = opts->b;
-  A.r = opts->use_ball ? opts->r : 0.0;
-  for (int a = 0; a < d; ++a) {
-    A.lo[a] = opts->lo[a];
-    A.hi[a] = opts->hi[a];
-    A.x0[a] = opts->use_ball ? opts->x_0[a] : 0.0;
-  }
-  const long long S = n_seeds;
-  std::vector<double> hx, hv;
-  std::vector<int> hs;
-  int rc;
-  if ((rc = refine_run(c, A, opts->max_eval, opts->tol, S, seeds, hx, hv, hs))) return rc;
-  sbo_refine_result res{};
-  res.best = refine_best(hv, hs, S, opts->maximize != 0, &res.evaluations, &res.converged);
-  res.best_value = res.best >= 0 ? hv[res.best] : NAN;
-  for (int a = 0; a < SBO_MAX_D; ++a) res.best_x[a] = (res.best >= 0 && a < d) ? hx[(size_t)res.best * d + a] : 0.0;
-  *result = res;
-  if (x_out) std::copy(hx.begin(), hx.end(), x_out);
-  if (value_out) std::copy(hv.begin(), hv.end(), value_out);
-  if (status_out)
-    for (long long s = 0; s < S; ++s) status_out[s] = hs[s];
-  return SBO_OK;
-}
-
 // slot of output o in A.outs, appended when new
 static int refine_slot(RefineArgs& A, int o) {
   for (int u = 0; u < A.nu; ++u)
@@ -798,12 +640,11 @@ static int refine_slot(RefineArgs& A, int o) {
   return A.nu++;
 }
 
-extern "C" int sbo_refine_sets(sbo_ctx* c, const sbo_refine_sets_opts* opts, int64_t n_seeds, const double* seeds, const double* seeds_p,
-                               double* x_out, double* xp_out, double* value_out, int32_t* status_out, sbo_refine_sets_result* result) {
-  if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
-  if (!opts || !seeds || !result) return fail(SBO_E_INVALID, "NULL argument");
-  if (!c->has_model) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
-  if (c->dtype != SBO_F64) return fail(SBO_E_UNSUPPORTED, "sbo_refine_sets needs an fp64 model");
+// The one problem path of sbo_refine_sets and sbo_refine (its single-point case), behind their own NULL / model / dtype checks:
+// checks the options, lays the outputs out in slots (objective first, then ascending outputs), fills RefineArgs, packs the seeds
+// [S][np][d], runs the solver and the exact check (refine_run) and picks the best seed.
+static int refine_problem(sbo_ctx* c, const sbo_refine_sets_opts* opts, int64_t n_seeds, const double* seeds, const double* seeds_p,
+                          double* x_out, double* xp_out, double* value_out, int32_t* status_out, sbo_refine_sets_result* result) {
   const ModelConst& mc = c->mc;
   const int d = mc.d, q = mc.q;
   if (opts->pair != 0 && opts->pair != 1) return fail(SBO_E_INVALID, "pair must be 0 or 1");
@@ -830,11 +671,17 @@ extern "C" int sbo_refine_sets(sbo_ctx* c, const sbo_refine_sets_opts* opts, int
   if (opts->use_link && !pair) return fail(SBO_E_INVALID, "the link joins x and x': pair mode only");
   if (opts->use_link && (opts->link_output < 1 || opts->link_output >= q || !(opts->L >= 0.0) || !std::isfinite(opts->L)))
     return fail(SBO_E_INVALID, "the link needs a constraint output in [1, q) and a finite L >= 0");
-  if (const char* why = refine_check_common(d, opts->b, opts->tol, opts->lo, opts->hi, opts->use_ball, opts->r, opts->x_0))
-    return fail(SBO_E_INVALID, why);
-  if (dist)
-    for (int a = 0; a < d; ++a)
-      if (!std::isfinite(opts->target[a])) return fail(SBO_E_INVALID, "the distance objective needs a finite target");
+  if (!(opts->b >= 0.0) || !std::isfinite(opts->b)) return fail(SBO_E_INVALID, "confidence multiplier b must be finite and >= 0");
+  if (std::isnan(opts->tol)) return fail(SBO_E_INVALID, "tol is NaN");
+  for (int a = 0; a < d; ++a)
+    if (!std::isfinite(opts->lo[a]) || !std::isfinite(opts->hi[a]) || !(opts->lo[a] <= opts->hi[a]))
+      return fail(SBO_E_INVALID, "box needs finite lo <= hi");
+  if (opts->use_ball != 0 && opts->use_ball != 1) return fail(SBO_E_INVALID, "use_ball must be 0 or 1");
+  if (opts->use_ball && (!(opts->r > 0.0) || !std::isfinite(opts->r))) return fail(SBO_E_INVALID, "ball radius must be finite and > 0");
+  for (int a = 0; a < d; ++a) {
+    if (opts->use_ball && !std::isfinite(opts->x_0[a])) return fail(SBO_E_INVALID, "ball centre must be finite");
+    if (dist && !std::isfinite(opts->target[a])) return fail(SBO_E_INVALID, "the distance objective needs a finite target");
+  }
   RefineArgs A{};
   A.np = pair ? 2 : 1;
   A.nz = A.np * d;
@@ -842,7 +689,7 @@ extern "C" int sbo_refine_sets(sbo_ctx* c, const sbo_refine_sets_opts* opts, int
   A.maximize = opts->maximize;
   A.obj_point = opts->objective_point;
   A.obj_slot = 0;
-  if (!dist) refine_slot(A, opts->objective);         // (objective first, as sbo_refine lays the slots out)
+  if (!dist) refine_slot(A, opts->objective);         // (objective first; a constraint that is the objective shares slot 0)
   for (int o = 1; o < q; ++o)
     if ((opts->safe_mask >> o) & 1u) A.con_slots |= 1 << refine_slot(A, o);
   for (int o = 1; o < q; ++o)
@@ -876,8 +723,16 @@ extern "C" int sbo_refine_sets(sbo_ctx* c, const sbo_refine_sets_opts* opts, int
   std::vector<int> hs;
   int rc;
   if ((rc = refine_run(c, A, opts->max_eval, opts->tol, S, hseed.data(), hz, hv, hs))) return rc;
+  // the seed whose returned point is best (ties: the lowest index; infeasible seeds and NaN values never), -1 if none
   sbo_refine_sets_result res{};
-  res.best = refine_best(hv, hs, S, opts->maximize != 0, &res.evaluations, &res.converged);
+  res.best = -1;
+  const double sg = opts->maximize ? -1.0 : 1.0;
+  for (long long s = 0; s < S; ++s) {
+    res.evaluations += hs[S + s];
+    if (hs[s] == SBO_REFINE_CONVERGED) ++res.converged;
+    if (hs[s] == SBO_REFINE_INFEASIBLE_SEED || std::isnan(hv[s])) continue;
+    if (res.best < 0 || sg * hv[s] < sg * hv[res.best]) res.best = s;
+  }
   res.best_value = res.best >= 0 ? hv[res.best] : NAN;
   for (int a = 0; a < SBO_MAX_D; ++a) {
     const bool on = res.best >= 0 && a < d;
@@ -894,4 +749,59 @@ extern "C" int sbo_refine_sets(sbo_ctx* c, const sbo_refine_sets_opts* opts, int
   if (status_out)
     for (long long s = 0; s < S; ++s) status_out[s] = hs[s];
   return SBO_OK;
+}
+
+}  // namespace sbo
+
+using namespace sbo;
+
+// the single-point case of the set problem: no level, no link, no unsafe_mask, and the constraints as its safe_mask
+extern "C" int sbo_refine(sbo_ctx* c, const sbo_refine_opts* opts, int64_t n_seeds, const double* seeds, double* x_out,
+                          double* value_out, int32_t* status_out, sbo_refine_result* result) {
+  if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
+  if (!opts || !seeds || !result) return fail(SBO_E_INVALID, "NULL argument");
+  if (!c->has_model) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
+  if (c->dtype != SBO_F64) return fail(SBO_E_UNSUPPORTED, "sbo_refine needs an fp64 model");
+  const int q = c->mc.q;
+  if (n_seeds < 1 || n_seeds > (1LL << 24)) return fail(SBO_E_INVALID, "n_seeds out of range");
+  if (opts->objective < 0 || opts->objective >= q) return fail(SBO_E_INVALID, "objective output out of range");
+  if (opts->kind < SBO_MEAN || opts->kind > SBO_VAR) return fail(SBO_E_INVALID, "bad bound kind");
+  if (opts->maximize != 0 && opts->maximize != 1) return fail(SBO_E_INVALID, "maximize must be 0 or 1");
+  if ((opts->constraint_mask & 1u) || (q < 32 && (opts->constraint_mask >> q) != 0))
+    return fail(SBO_E_INVALID, "constraint_mask: bit 0 must be clear and no bit may reach q");
+  sbo_refine_sets_opts so{};
+  so.b = opts->b;
+  so.objective = opts->objective;
+  so.kind = opts->kind;
+  so.maximize = opts->maximize;
+  so.safe_mask = opts->constraint_mask;
+  so.use_ball = opts->use_ball;
+  so.max_eval = opts->max_eval;
+  so.r = opts->r;
+  so.tol = opts->tol;
+  for (int a = 0; a < SBO_MAX_D; ++a) {
+    so.lo[a] = opts->lo[a];
+    so.hi[a] = opts->hi[a];
+    so.x_0[a] = opts->x_0[a];
+  }
+  sbo_refine_sets_result sr{};
+  const int rc = refine_problem(c, &so, n_seeds, seeds, nullptr, x_out, nullptr, value_out, status_out, &sr);
+  if (rc) return rc;
+  sbo_refine_result res{};
+  res.best = sr.best;
+  res.best_value = sr.best_value;
+  res.evaluations = sr.evaluations;
+  res.converged = sr.converged;
+  std::copy(sr.best_x, sr.best_x + SBO_MAX_D, res.best_x);
+  *result = res;
+  return SBO_OK;
+}
+
+extern "C" int sbo_refine_sets(sbo_ctx* c, const sbo_refine_sets_opts* opts, int64_t n_seeds, const double* seeds, const double* seeds_p,
+                               double* x_out, double* xp_out, double* value_out, int32_t* status_out, sbo_refine_sets_result* result) {
+  if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
+  if (!opts || !seeds || !result) return fail(SBO_E_INVALID, "NULL argument");
+  if (!c->has_model) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
+  if (c->dtype != SBO_F64) return fail(SBO_E_UNSUPPORTED, "sbo_refine_sets needs an fp64 model");
+  return refine_problem(c, opts, n_seeds, seeds, seeds_p, x_out, xp_out, value_out, status_out, result);
 }

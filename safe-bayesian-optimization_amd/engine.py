@@ -342,26 +342,38 @@ class SweepEngine:
         k = {"mean": L.SBO_MEAN, "ucb": L.SBO_UCB, "lcb": L.SBO_LCB, "var": L.SBO_VAR}.get(kind)
         if k is None:
             raise ValueError("kind must be 'mean', 'ucb', 'lcb' or 'var'")
-        d = self.d
-        S = _f64(seeds)
-        if S.ndim == 1:
-            S = S.reshape(1, -1)
-        if d < 1 or S.ndim != 2 or S.shape[1] != d:
-            raise ValueError("seeds must be [S, d] for the model's d")
-        S = np.ascontiguousarray(S)
-        opts = L.RefineOpts()
-        opts.b = float(b)
+        opts, res = L.RefineOpts(), L.RefineResult()
         opts.objective = int(objective)
         opts.kind = k
         opts.maximize = int(bool(maximize))
-        cons = range(1, self.q) if constraints is None else constraints
-        mask = 0
-        for c in cons:
-            c = int(c)
-            if c < 0 or c >= 32:
-                raise ValueError("constraint index out of range")
-            mask |= 1 << c
-        opts.constraint_mask = mask
+        masks = {"constraint_mask": range(1, self.q) if constraints is None else constraints}
+        return self._refine_call(lambda n, S, Sp, x, xp, val, st: self._lib.sbo_refine(self._ctx, C.byref(opts), n, S, x, val, st, C.byref(res)),
+                                 opts, res, b, seeds, None, masks, lo, hi, x_0, r, max_eval, tol)
+
+    def _refine_call(self, call, opts, res, b, seeds, seeds_p, masks, lo, hi, x_0, r, max_eval, tol) -> dict:
+        """What ``refine`` and ``refine_sets`` share: the seed arrays, ``masks`` (field of ``opts`` -> output indices), the box, the
+        ball, ``max_eval`` and ``tol`` into ``opts``; ``call(n, seeds, seeds_p, x, xp, value, status)``; the result dict."""
+        d = self.d
+        pair = seeds_p is not None
+        S = []
+        for s in (seeds, seeds_p) if pair else (seeds,):
+            s = _f64(s)
+            if s.ndim == 1:
+                s = s.reshape(1, -1)
+            if d < 1 or s.ndim != 2 or s.shape[1] != d:
+                raise ValueError("seeds must be [S, d] for the model's d")
+            S.append(np.ascontiguousarray(s))
+        if pair and S[1].shape != S[0].shape:
+            raise ValueError("seeds and seeds_p must have the same shape")
+        opts.b = float(b)
+        for field, cs in masks.items():
+            m = 0
+            for c in cs:
+                c = int(c)
+                if c < 0 or c >= 32:
+                    raise ValueError("constraint index out of range")
+                m |= 1 << c
+            setattr(opts, field, m)
         lo, hi = _f64(lo).reshape(-1), _f64(hi).reshape(-1)
         if lo.shape != (d,) or hi.shape != (d,):
             raise ValueError("lo and hi must have shape [d]")
@@ -379,14 +391,18 @@ class SweepEngine:
             opts.r = float(r)
         opts.max_eval = int(max_eval) if max_eval is not None else 0
         opts.tol = float(tol) if tol is not None else 0.0
-        n = S.shape[0]
+        n = S[0].shape[0]
         x = np.empty((n, d))
+        xp = np.empty((n, d)) if pair else None
         val = np.empty(n)
         st = np.empty(n, dtype=np.int32)
-        res = L.RefineResult()
-        L.check(self._lib.sbo_refine(self._ctx, C.byref(opts), n, _ptr(S), _ptr(x), _ptr(val), _ptr(st), C.byref(res)))
-        return {"x": x, "value": val, "status": st, "best": int(res.best), "best_x": np.array(res.best_x[:d]),
-                "best_value": float(res.best_value), "evaluations": int(res.evaluations), "converged": int(res.converged)}
+        L.check(call(n, _ptr(S[0]), _ptr(S[1]) if pair else None, _ptr(x), _ptr(xp) if pair else None, _ptr(val), _ptr(st)))
+        out = {"x": x, "value": val, "status": st, "best": int(res.best), "best_x": np.array(res.best_x[:d]),
+               "best_value": float(res.best_value), "evaluations": int(res.evaluations), "converged": int(res.converged)}
+        if pair:
+            out["xp"] = xp
+            out["best_xp"] = np.array(res.best_xp[:d])
+        return out
 
     def refine_sets(self, b: float, seeds, seeds_p=None, *, objective: int = 0, kind: str = "lcb", at: str = "x", maximize: bool = False,
                     safe=None, unsafe=None, level=None, link=None, target=None, lo, hi, x_0=None, r=None,
@@ -403,82 +419,31 @@ class SweepEngine:
             raise ValueError("kind must be 'mean', 'ucb', 'lcb', 'var' or 'dist'")
         if at not in ("x", "xp"):
             raise ValueError("at must be 'x' or 'xp'")
+        if (kind == "dist") != (target is not None):
+            raise ValueError("kind='dist' and target go together")
         d = self.d
         pair = seeds_p is not None
-
-        def seed_array(s):
-            s = _f64(s)
-            if s.ndim == 1:
-                s = s.reshape(1, -1)
-            if d < 1 or s.ndim != 2 or s.shape[1] != d:
-                raise ValueError("seeds must be [S, d] for the model's d")
-            return np.ascontiguousarray(s)
-
-        def mask_of(cs):
-            m = 0
-            for c in cs:
-                c = int(c)
-                if c < 0 or c >= 32:
-                    raise ValueError("constraint index out of range")
-                m |= 1 << c
-            return m
-
-        S = seed_array(seeds)
-        Sp = seed_array(seeds_p) if pair else None
-        if pair and Sp.shape != S.shape:
-            raise ValueError("seeds and seeds_p must have the same shape")
-        opts = L.RefineSetsOpts()
-        opts.b = float(b)
+        opts, res = L.RefineSetsOpts(), L.RefineSetsResult()
         opts.pair = int(pair)
         opts.objective = int(objective)
         opts.kind = kinds[kind]
         opts.objective_point = int(at == "xp")
         opts.maximize = int(bool(maximize))
-        opts.safe_mask = mask_of(range(1, self.q) if safe is None else safe)
-        opts.unsafe_mask = mask_of((range(1, self.q) if pair else ()) if unsafe is None else unsafe)
         if level is not None:
             opts.use_level, opts.level_output, opts.level = 1, int(level[0]), float(level[1])
         if link is not None:
             opts.use_link, opts.link_output, opts.L = 1, int(link[0]), float(link[1])
-        lo, hi = _f64(lo).reshape(-1), _f64(hi).reshape(-1)
-        if lo.shape != (d,) or hi.shape != (d,):
-            raise ValueError("lo and hi must have shape [d]")
-        for a in range(d):
-            opts.lo[a], opts.hi[a] = lo[a], hi[a]
-        if (x_0 is None) != (r is None):
-            raise ValueError("the ball needs both x_0 and r")
-        if x_0 is not None:
-            x0 = _f64(x_0).reshape(-1)
-            if x0.shape != (d,):
-                raise ValueError("x_0 must have shape [d]")
-            opts.use_ball = 1
-            for a in range(d):
-                opts.x_0[a] = x0[a]
-            opts.r = float(r)
-        if (kind == "dist") != (target is not None):
-            raise ValueError("kind='dist' and target go together")
         if target is not None:
             t = _f64(target).reshape(-1)
             if t.shape != (d,):
                 raise ValueError("target must have shape [d]")
             for a in range(d):
                 opts.target[a] = t[a]
-        opts.max_eval = int(max_eval) if max_eval is not None else 0
-        opts.tol = float(tol) if tol is not None else 0.0
-        n = S.shape[0]
-        x = np.empty((n, d))
-        xp = np.empty((n, d)) if pair else None
-        val = np.empty(n)
-        st = np.empty(n, dtype=np.int32)
-        res = L.RefineSetsResult()
-        L.check(self._lib.sbo_refine_sets(self._ctx, C.byref(opts), n, _ptr(S), _ptr(Sp) if pair else None, _ptr(x),
-                                          _ptr(xp) if pair else None, _ptr(val), _ptr(st), C.byref(res)))
-        out = {"x": x, "value": val, "status": st, "best": int(res.best), "best_x": np.array(res.best_x[:d]),
-               "best_value": float(res.best_value), "evaluations": int(res.evaluations), "converged": int(res.converged)}
-        if pair:
-            out["xp"] = xp
-            out["best_xp"] = np.array(res.best_xp[:d])
-        return out
+        masks = {"safe_mask": range(1, self.q) if safe is None else safe,
+                 "unsafe_mask": (range(1, self.q) if pair else ()) if unsafe is None else unsafe}
+        return self._refine_call(lambda n, S, Sp, x, xp, val, st: self._lib.sbo_refine_sets(self._ctx, C.byref(opts), n, S, Sp, x, xp, val, st,
+                                                                                            C.byref(res)),
+                                 opts, res, b, seeds, seeds_p, masks, lo, hi, x_0, r, max_eval, tol)
 
     def mask(self, which: str, c: int = 0) -> np.ndarray:
         w = {"S": L.SBO_MASK_S, "U": L.SBO_MASK_U, "M": L.SBO_MASK_M, "G": L.SBO_MASK_G, "O": L.SBO_MASK_O}[which]

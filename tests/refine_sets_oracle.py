@@ -1,7 +1,7 @@
-"""NumPy / SciPy reference for sbo_refine_sets -- test infrastructure only.
+"""NumPy / SciPy reference for sbo_refine and sbo_refine_sets -- test infrastructure only.
 
-The four set-valued steps as continuous problems on z = x (single mode) or z = (x, x') (pair mode), built on
-refine_oracle.bound_grad:
+sbo_refine's problem (a bound of one output s.t. lcb_c(x) >= 0, the box and the trust-region ball) and the four set-valued steps
+as continuous problems on z = x (single mode) or z = (x, x') (pair mode), built on refine_oracle.bound_grad:
 
     M_t      max var_0(x)    s.t. lcb_c(x) >= 0, lcb_0(x) <= u*                                   models/SafeOpt.py:53-66
     G_t      max var_0(x)    s.t. lcb_c(x) >= 0, lcb_c(x') <= 0, ucb_i(x) - L ||x - x' + 1e-8|| >= 0      :90-124
@@ -13,7 +13,7 @@ terms():         every inequality term g_i(z) >= 0 with its analytic Jacobian;
 objective():     the minimised function (sign-adjusted) with its gradient, and value(): what the device reports;
 feasible():      the exact predicate checker (closed predicates, box included) and the smallest slack;
 slsqp():         SciPy SLSQP from a seed;  make_feasible(): bisection back to the feasible seed for pairs too;
-kkt_residual():  refine_oracle.kkt_residual extended with the level, U and link gradients;
+kkt_residual():  stationarity residual at a point, multipliers of the (nearly) active terms and box faces by NNLS;
 grid_case():     the grid sweep of a fixture and the seeds the host classes take from it.
 """
 import os
@@ -29,12 +29,14 @@ GRIDS = {"benoit_n20_50x50": [50, 50], "benoit_n128_64x48": [64, 48], "wo3_n64_4
 
 
 def problem(ds, b, lo, hi, kind, objective=0, at="x", maximize=False, safe=None, unsafe=None, level=None, link=None, target=None,
-            pair=False):
+            pair=False, ball=None):
+    """``ball``: (x_0, r) of the term r^2 - ||x - x_0||^2 >= 0."""
     q = ds["Y_norm"].shape[1]
     return {"ds": ds, "b": float(b), "lo": np.asarray(lo, float), "hi": np.asarray(hi, float), "kind": kind, "objective": objective,
             "at": at, "maximize": maximize, "safe": list(range(1, q)) if safe is None else list(safe),
             "unsafe": (list(range(1, q)) if pair else []) if unsafe is None else list(unsafe), "level": level, "link": link,
-            "target": None if target is None else np.asarray(target, float), "pair": pair, "d": len(lo)}
+            "target": None if target is None else np.asarray(target, float), "pair": pair, "d": len(lo),
+            "ball": None if ball is None else (np.asarray(ball[0], float), float(ball[1]))}
 
 
 def split(P, z):
@@ -45,8 +47,9 @@ def split(P, z):
 
 def engine_args(P):
     """Keyword arguments of SweepEngine.refine_sets for the problem."""
+    x_0, r = P["ball"] if P["ball"] is not None else (None, None)
     return dict(objective=P["objective"], kind=P["kind"], at=P["at"], maximize=P["maximize"], safe=P["safe"], unsafe=P["unsafe"],
-                level=P["level"], link=P["link"], target=P["target"], lo=P["lo"], hi=P["hi"])
+                level=P["level"], link=P["link"], target=P["target"], lo=P["lo"], hi=P["hi"], x_0=x_0, r=r)
 
 
 def shifted(x, xp):
@@ -55,7 +58,7 @@ def shifted(x, xp):
 
 
 def terms(P, z):
-    """[(name, g, jac [len z])] with g >= 0 feasible: safe, level, unsafe, link (no box)."""
+    """[(name, g, jac [len z])] with g >= 0 feasible: safe, ball, level, unsafe, link (no box)."""
     x, xp = split(P, z)
     d, nz, ds, b = P["d"], len(z), P["ds"], P["b"]
     out = []
@@ -64,6 +67,11 @@ def terms(P, z):
         j = np.zeros(nz)
         j[:d] = gg
         out.append((f"safe{c}", g, j))
+    if P["ball"] is not None:
+        x_0, r = P["ball"]
+        j = np.zeros(nz)
+        j[:d] = -2.0 * (x - x_0)
+        out.append(("ball", r * r - np.sum((x - x_0) ** 2), j))
     if P["level"] is not None:
         o, lv = P["level"]
         g, gg = ro.bound_grad(x, ds, b, o, "lcb")
@@ -157,7 +165,7 @@ def make_feasible(P, z, seed, steps=80):
 
 def kkt_residual(P, z, active=1e-6):
     """||grad f - sum lambda_i grad g_i||_inf / (1 + ||grad f||_inf), lambda >= 0 by NNLS over the terms within ``active``
-    (relative) of their bound and the box faces z sits on -- refine_oracle.kkt_residual with the level, U and link gradients."""
+    (relative: of Y_std_c + ||grad g||, the ball of r^2) of their bound and the box faces z sits on.  f is the minimised function."""
     from scipy.optimize import nnls
     z = np.asarray(z, dtype=np.float64)
     _, gf = objective(P, z)
@@ -166,8 +174,12 @@ def kkt_residual(P, z, active=1e-6):
     G = []
     ystd = np.abs(P["ds"]["Y_std"])
     for name, g, j in terms(P, z):
-        c = P["level"][0] if name == "level" else P["link"][0] if name == "link" else int("".join(ch for ch in name if ch.isdigit()))
-        if g <= active * (ystd[c] + np.linalg.norm(j)):
+        if name == "ball":
+            near = active * P["ball"][1] * P["ball"][1]
+        else:
+            c = P["level"][0] if name == "level" else P["link"][0] if name == "link" else int("".join(ch for ch in name if ch.isdigit()))
+            near = active * (ystd[c] + np.linalg.norm(j))
+        if g <= near:
             G.append(j)
     lo, hi = box(P)
     span = hi - lo

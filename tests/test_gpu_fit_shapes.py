@@ -217,17 +217,30 @@ def test_device_de_with_infinite_energies_equals_its_twin(engine, maxiter):
 
 
 # ---------------------------------------------------------------------------------------------- fit_local at new shapes
-@pytest.mark.parametrize("d", [1, 5, 8])
-@pytest.mark.parametrize("n", [95, 96, 97])
-def test_fit_local_many_outputs_across_the_workgroup_switch(engine, n, d):
-    """q = SBO_MAX_Q outputs x 33 starts = 264 workgroups (more than the CUs): the per-start contract of every (output, start)."""
+def many_outputs_problem(n, d):
+    """(X, Y [n, SBO_MAX_Q], box, 33 starts, maxiter) of test_fit_local_many_outputs_across_the_workgroup_switch."""
     q, P, maxiter = _lib.SBO_MAX_Q, 33, 12
     X, _ = _data(n, d, 400 + n + d)
     rng = np.random.default_rng(n * d)
     Y = np.column_stack([np.sin(X @ rng.uniform(0.2, 1.0, d) + o) for o in range(q)])
     Y = (Y - Y.mean(0)) / Y.std(0)
     B = np.array([[-2.0, 2.0]] * (d + 1) + [[-8.0, -2.0]])
-    starts = rng.uniform(B[:, 0], B[:, 1], size=(P, d + 2))
+    return X, Y, B, rng.uniform(B[:, 0], B[:, 1], size=(P, d + 2)), maxiter
+
+
+def slsqp_problem(n, d):
+    """(X, y, box, 3 starts) of test_fit_local_reaches_slsqp_at_new_shapes."""
+    X, y = _data(n, d, 900 + n + d)
+    B = np.array([[-2.0, 2.0]] * (d + 1) + [[-8.0, -2.0]])
+    return X, y, B, np.random.default_rng(d).uniform(B[:, 0], B[:, 1], size=(3, d + 2))
+
+
+@pytest.mark.parametrize("d", [1, 5, 8])
+@pytest.mark.parametrize("n", [95, 96, 97])
+def test_fit_local_many_outputs_across_the_workgroup_switch(engine, n, d):
+    """q = SBO_MAX_Q outputs x 33 starts = 264 workgroups (more than the CUs): the per-start contract of every (output, start)."""
+    X, Y, B, starts, maxiter = many_outputs_problem(n, d)
+    q, P = Y.shape[1], len(starts)
     t0 = time.perf_counter()
     res = engine.fit_local(X, Y, B, starts, maxiter=maxiter)
     print(f"fit_local n={n} d={d} q={q} P={P} maxiter={maxiter}: {time.perf_counter() - t0:.2f} s")
@@ -237,9 +250,7 @@ def test_fit_local_many_outputs_across_the_workgroup_switch(engine, n, d):
 @pytest.mark.parametrize("n,d", [(97, 1), (96, 5), (95, 8)])
 def test_fit_local_reaches_slsqp_at_new_shapes(engine, n, d):
     """From the same few starts the device fit is no worse than SciPy SLSQP with the analytic gradient."""
-    X, y = _data(n, d, 900 + n + d)
-    B = np.array([[-2.0, 2.0]] * (d + 1) + [[-8.0, -2.0]])
-    starts = np.random.default_rng(d).uniform(B[:, 0], B[:, 1], size=(3, d + 2))
+    X, y, B, starts = slsqp_problem(n, d)
     t0 = time.perf_counter()
     res = engine.fit_local(X, y[:, None], B, starts)
     print(f"fit_local n={n} d={d} P=3 to convergence: {time.perf_counter() - t0:.2f} s")

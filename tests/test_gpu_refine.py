@@ -12,6 +12,7 @@ from safebo_amd import BayesRTOjax, GoOSE, GP_TR, SafeOpt, _lib, synthetic
 from safebo_amd.BayesRTOjax import DataStorage
 
 import refine_oracle as ro
+import refine_sets_oracle as rs
 
 pytestmark = pytest.mark.gpu
 
@@ -49,7 +50,7 @@ def test_rosen4_refines_the_32_grid_winner_to_the_continuous_optimum(engine):
     assert bnd[(1, "lcb")][0] >= 0.0
     assert bnd[(0, "lcb")][0] == v
     assert out["best"] == 0 and np.array_equal(out["best_x"], x) and out["best_value"] == v
-    assert ro.kkt_residual(x, ds, b, lo=lo, hi=hi) <= 1e-5
+    assert rs.kkt_residual(rs.problem(ds, b, lo, hi, "lcb", safe=[1]), x) <= 1e-5
 
 
 def test_benoit_trust_region_refines_and_unsticks_small_radii(engine):
@@ -86,11 +87,12 @@ def test_each_kind_is_feasible_no_worse_than_its_seed_and_than_slsqp(engine, nam
     assert sg * v <= sg * bnd[(0, kind)][0]
     bnd = _bounds_at(engine, x, b)
     assert bnd[(1, "lcb")][0] >= 0.0 and bnd[(0, kind)][0] == v
-    xs, _ = ro.slsqp(ds, b, seed, 0, kind, maximize, lo=lo, hi=hi)
-    xs = ro.make_feasible(xs, seed, ds, b)                 # (SLSQP ends a hair outside the safe set on boundary optima)
+    P = rs.problem(ds, b, lo, hi, kind, maximize=maximize, safe=[1])
+    xs, _ = rs.slsqp(P, seed)
+    xs = rs.make_feasible(P, xs, seed)                     # (SLSQP ends a hair outside the safe set on boundary optima)
     fs = ro.bound_grad(xs, ds, b, 0, kind)[0]
     assert sg * v <= sg * fs + 1e-8 * (1.0 + abs(fs)), (v, fs)
-    assert ro.kkt_residual(x, ds, b, 0, kind, maximize, lo=lo, hi=hi) <= 1e-4
+    assert rs.kkt_residual(P, x) <= 1e-4
 
 
 def test_seed_batch_statuses_best_and_determinism(engine):
@@ -134,7 +136,7 @@ def test_box_only_and_held_faces(engine):
     seeds = lo + rng.uniform(0.2, 0.8, size=(6, 2)) * (hi - lo)
     out = engine.refine(b, seeds, 0, "mean", constraints=[], lo=lo, hi=hi, max_eval=2000)
     for x in out["x"]:
-        assert ro.kkt_residual(x, ds, b, 0, "mean", constraints=(), lo=lo, hi=hi) <= 1e-6
+        assert rs.kkt_residual(rs.problem(ds, b, lo, hi, "mean", safe=[]), x) <= 1e-6
     # a seed on a box face where the function keeps improving outward keeps that coordinate exactly (maximised mean: the faces
     # stay active) -- and no returned point leaves a face whose gradient still points out of the box
     held = 0

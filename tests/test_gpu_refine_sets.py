@@ -286,9 +286,9 @@ def test_a_call_between_two_sweeps_leaves_masks_results_and_audit_alone(engine):
     assert all(np.array_equal(masks[k], masks2[k]) for k in masks) and np.array_equal(G, G2)
 
 
-@pytest.mark.parametrize("n0", [16, 300])
-def test_refine_sets_follows_appended_samples(engine, n0):
-    """test_refine_follows_appended_samples for a pair: f_cap / a_ld strides in both tiers, against the same dataset set afresh."""
+def appended_pair_problem(n0):
+    """test_refine_sets_follows_appended_samples' inputs: the first n0 rows as a dataset, the whole (n0 + 5 rows in its
+    normalisation), those rows normalised, the pair problem on the whole, its seed and the posterior variance at the seed."""
     d, k, b = 2, 5, 2.0
     full = _synthetic(n0 + k, d, 5)
     X = full["X_norm"] * full["X_std"] + full["X_mean"]
@@ -303,7 +303,14 @@ def test_refine_sets_follows_appended_samples(engine, n0):
     assert m[0, 1] - b * np.sqrt(v[0, 1]) > 0 and m[1, 1] - b * np.sqrt(v[1, 1]) < 0
     L = 0.5 * (m[0, 1] + b * np.sqrt(v[0, 1])) / oracle.shifted_norm(x, xp)
     P = rs.problem(app, b, lo, hi, "var", maximize=True, link=(1, L), pair=True)
-    seed = np.concatenate([x, xp])
+    return ds0, app, Xn, Yn, P, np.concatenate([x, xp]), v
+
+
+@pytest.mark.parametrize("n0", [16, 300])
+def test_refine_sets_follows_appended_samples(engine, n0):
+    """test_refine_follows_appended_samples for a pair: f_cap / a_ld strides in both tiers, against the same dataset set afresh."""
+    ds0, app, Xn, Yn, P, seed, v = appended_pair_problem(n0)
+    k = len(Xn) - n0
     engine.set_model(app)
     fresh = _run(engine, P, seed)
     engine.set_model(ds0)

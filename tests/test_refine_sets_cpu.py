@@ -94,3 +94,35 @@ def test_refine_sets_struct_layout_matches_the_header(tmp_path):
     O, R = _lib.RefineSetsOpts, _lib.RefineSetsResult
     assert got == ([C.sizeof(O), C.sizeof(R), _lib.SBO_REFINE_DIST] + [getattr(O, f).offset for f in fields_o]
                    + [getattr(R, f).offset for f in fields_r])
+
+
+@pytest.mark.parametrize("r", [0.3, 0.002])
+def test_ball_term_of_the_trust_region_problem(r):
+    """sbo_refine's trust-region case (test_benoit_trust_region_refines_and_unsticks_small_radii: x_0 = point 44786 of the 400 x 400
+    grid) through the shared functions: the ball's Jacobian against central differences (a quadratic: exact up to rounding), the
+    feasible yardstick from SLSQP's answer and from a point outside the ball, and stationarity of that answer -- with the ball's
+    multiplier where the ball binds, which at r = 0.002 it must (the unconstrained step from x_0 is longer than 0.0015)."""
+    import oracle
+    ds, b, lo, hi = rs.load("benoit_n20_50x50")
+    x0 = oracle.grid_points(lo, hi, [400, 400], first=44786, n=1)[0]
+    P = rs.problem(ds, b, lo, hi, "lcb", safe=[1], ball=(x0, r))
+    assert [t[0] for t in rs.terms(P, x0)] == ["safe1", "ball"] and rs.terms(P, x0)[1][1] == r * r
+    z = x0 + np.array([0.3, -0.4]) * r
+    h = 1e-3 * r
+    for a in range(2):
+        e = np.zeros(2)
+        e[a] = h
+        fd = (rs.terms(P, z + e)[1][1] - rs.terms(P, z - e)[1][1]) / (2 * h)
+        assert abs(fd - rs.terms(P, z)[1][2][a]) <= 1e-6 * r
+    far = x0 + np.array([0.8, -0.5]) * 2 * r
+    assert not rs.feasible(P, far)[0]
+    back = rs.make_feasible(P, far, x0)
+    assert rs.feasible(P, back)[0] and np.linalg.norm(back - x0) <= r
+    xs, _ = rs.slsqp(P, x0)
+    xs = rs.make_feasible(P, xs, x0)
+    assert rs.feasible(P, xs)[0] and rs.value(P, xs) < rs.value(P, x0)
+    print(f"r {r}: |xs - x0| {np.linalg.norm(xs - x0):.6g}, ball slack / r^2 {rs.terms(P, xs)[1][1] / r ** 2:.3g}, kkt {rs.kkt_residual(P, xs):.3g}")
+    assert rs.kkt_residual(P, xs) <= 1e-6
+    if r == 0.002:
+        assert np.linalg.norm(xs - x0) > 0.0015
+        assert 0.0 <= rs.terms(P, xs)[1][1] <= 1e-6 * r * r       # (inside kkt_residual's active band: its gradient is a column)
