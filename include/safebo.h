@@ -225,6 +225,10 @@ typedef struct sbo_profile {
    * constraints.  GoOSE's coverage search on the sorted order does not count pairs.                                                */
   double list_index_build_ms;
   int64_t list_index_leaf_pairs, list_index_nodes_skipped;
+  /* Band of the last sweep of a dtype SBO_F32 model (option "fp64_recheck"): the half-widths, per output and in un-normalised units,
+   * within which that sweep took the fp32 mean / variance to lie of the fp64 values -- max(1e-4 normalised, 16 x the largest deviation the
+   * fp64 twin measured at the probe candidates of this (model, candidate set)).  Zero for fp64 models and with the recheck off.    */
+  double fp32_band_dm[SBO_MAX_Q], fp32_band_dv[SBO_MAX_Q];
 } sbo_profile;
 
 /* ---- library / context ------------------------------------------------------------------- */
@@ -531,7 +535,9 @@ int sbo_profile_get(sbo_ctx* ctx, sbo_profile* out);
  *   "halo_spec"        1: ranks > 1 size their transform windows from the previous sweep's keys (device-checked); 0: wait for this sweep's
  *   "comm_events"      1: an event pair around every collective (sbo_profile.comm_ms)
  *   "comm_selftest"    1: a one-rank communicator still sends C1 / C2 / C3 through RCCL (results must not change)
- *   "fp64_recheck"     1: fp32 models re-evaluate in fp64 every candidate their 1e-4 contract cannot decide; 0: masks of the fp32 posterior
+ *   "fp64_recheck"     1: fp32 models re-evaluate in fp64 every candidate that the band of their posterior cannot decide -- measured per (model,
+ *                      candidate set) by the fp64 twin at 256 probe candidates, never under 1e-4 normalised (sbo_profile.fp32_band_dm / _dv);
+ *                      0: masks of the fp32 posterior
  *   "guard_audit"      samples per audited sweep of the standing audit of the guard band (sbo_profile.guard_audit_*; default 1024); 0: off
  *   "guard_audit_scale_ppm" test hook: the audit compares against the band x value / 1e6 (default 1000000); setting it clears the counts
  *   "guard_audit_every" one sweep in this many carries an audit (default 16; the first sweep after setting it does).  An audit shares

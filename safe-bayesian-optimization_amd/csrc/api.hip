@@ -212,7 +212,7 @@ int sbo_shutdown(sbo_ctx* c) {
   }
   sbo_comm_destroy_internal(c);
   for (DevBuf* b : {&c->Fpk, &c->As, &c->sqA, &c->alpha, &c->Xn, &c->pts, &c->mean, &c->var, &c->maskS,
-                    &c->maskU, &c->maskM, &c->maskG, &c->maskO, &c->fitbuf, &c->fitwork, &c->refbuf, &c->partial, &c->bl_P0f, &c->bl_P1A, &c->bl_T4f, &c->bl_BtA, &c->bl_SBf, &c->bl_VA, &c->bl_small, &c->bl_work, &c->bl_cheb, &c->bl_basis, &c->mwork, &c->appendbuf, &c->rc_mean, &c->rc_var, &c->rc_list, &c->rc_refined, &c->Fplain, &c->alpha64, &c->cpart, &c->invk_img, &c->bl_lpart, &c->bl_grad, &c->Wfull, &c->Uwin, &c->ubits, &c->gather, &c->xch, &c->shard_first, &c->E0f, &c->Er, &c->AXg, &c->tn_pts, &c->tn_vals, &c->tn_work, &c->tn_W0t, &c->tn_W1t, &c->tn_probe, &c->tn_scr, &c->tn_tail, &c->fuseS, &c->fuseU, &c->tn_gather, &c->bi_params, &c->gb, &c->gb_pts, &c->gb_vals, &c->gb_probe, &c->gb_part, &c->list_scr, &c->cbS, &c->cbU, &c->cbM, &c->cbG, &c->cbUsum, &c->col_img, &c->col_bmin, &c->col_fin, &c->col_slots, &c->col_cimg, &c->col_cbmin, &c->audit_pts, &c->audit_val, &c->audit_part, &c->audit_cnt, &c->bl_encl, &c->bl_sched, &c->lx.box, &c->lx.keys, &c->lx.vals, &c->lx.hist, &c->lx.xs, &c->lx.stats})
+                    &c->maskU, &c->maskM, &c->maskG, &c->maskO, &c->fitbuf, &c->fitwork, &c->refbuf, &c->partial, &c->bl_P0f, &c->bl_P1A, &c->bl_T4f, &c->bl_BtA, &c->bl_SBf, &c->bl_VA, &c->bl_small, &c->bl_work, &c->bl_cheb, &c->bl_basis, &c->mwork, &c->appendbuf, &c->rc_mean, &c->rc_var, &c->rc_list, &c->rc_refined, &c->rc_probe, &c->Fplain, &c->alpha64, &c->cpart, &c->invk_img, &c->bl_lpart, &c->bl_grad, &c->Wfull, &c->Uwin, &c->ubits, &c->gather, &c->xch, &c->shard_first, &c->E0f, &c->Er, &c->AXg, &c->tn_pts, &c->tn_vals, &c->tn_work, &c->tn_W0t, &c->tn_W1t, &c->tn_probe, &c->tn_scr, &c->tn_tail, &c->fuseS, &c->fuseU, &c->tn_gather, &c->bi_params, &c->gb, &c->gb_pts, &c->gb_vals, &c->gb_probe, &c->gb_part, &c->list_scr, &c->cbS, &c->cbU, &c->cbM, &c->cbG, &c->cbUsum, &c->col_img, &c->col_bmin, &c->col_fin, &c->col_slots, &c->col_cimg, &c->col_cbmin, &c->audit_pts, &c->audit_val, &c->audit_part, &c->audit_cnt, &c->bl_encl, &c->bl_sched, &c->lx.box, &c->lx.keys, &c->lx.vals, &c->lx.hist, &c->lx.xs, &c->lx.stats})
     release(*b);
   for (auto& ln : c->lane)
     for (DevBuf* b : ln.bufs()) release(*b);
@@ -406,6 +406,7 @@ int sbo_set_option(sbo_ctx* c, const char* key, int64_t value) {
     if (value < 0 || value > 2) return fail(SBO_E_INVALID, "posterior_path must be 0 (auto), 1 (generic) or 2 (generic, chunked)");
     c->posterior_path = (int)value;
     c->posterior_valid = false;
+    c->rc_band_valid = false;              // (another kernel sums in another order: an fp32 model's band is measured again)
     return SBO_OK;
   }
   return fail(SBO_E_INVALID, std::string("unknown option ") + key);

@@ -405,6 +405,12 @@ struct sbo_ctx {
   sbo::DevBuf rc_mean, rc_var;   // double [q][n_local]: the fp32 posterior widened, flagged entries replaced by fp64 values (what the recheck's set phases read)
   sbo::DevBuf rc_list;           // flagged candidate indices (long long) + counters (64-byte head)
   sbo::DevBuf rc_refined;        // uint8 [n_local]: this candidate's entries of rc_mean / rc_var are fp64 values
+  // the band of the resident fp32 posterior (sets_recheck.inc.hpp: rc_bands): max(1e-4 normalised, 16 x the largest |fp32 - fp64 twin| over
+  // the probe candidates), measured when an fp32 sweep first meets this (model, candidate set); dropped by plans_invalidate
+  sbo::DevBuf rc_probe;          // probe indices (long long [kRcProbes]) behind 2 kMaxQ deviation keys
+  bool rc_band_valid = false;
+  double rc_band_dm[sbo::kMaxQ] = {}, rc_band_dv[sbo::kMaxQ] = {};
+  long long rc_probe_round = 0;  // rotates the probe set of the standing audit
   // robust sweep (robust.hip): per-control arrays of the last one, the mask of robust-safe controls, the split partials
   sbo::DevBuf rob, rob_mask, rob_part;
   long long rob_nc = 0;
@@ -475,6 +481,7 @@ inline void plans_invalidate(sbo_ctx* c) {
   c->bl.valid = false;
   c->bi.valid = false;
   c->posterior_valid = false;
+  c->rc_band_valid = false;
 }
 bool tensor_applicable(const sbo_ctx* c);
 int launch_posterior_tensor(sbo_ctx* c, const PostRequest& req, bool* declined);

@@ -2,9 +2,11 @@
 // inside namespace sbo; not a standalone header).
 //
 // SURVEY.md section 7, hard part 2: `lcb >= 0` flips for candidates whose bound lies inside the rounding band of the fp32
-// posterior.  The fp32 kernels keep mean / var within 1e-4 (normalised units) of the fp64 values -- their contract, checked by
-// the parity tests at <= 1e-5 --, so every decision is first taken with INTERVALS: a candidate's bounds are known to
-// +- (dm, dv), u* to [u_lo, u_hi], the largest variance over M from below.  Candidates whose intervals cannot decide
+// posterior.  How wide that band is depends on the model (1e-6 normalised at cond(K) ~ 1e3, beyond 1e-3 at the noise floor of the
+// reference's fit), so it is MEASURED per (model, candidate set) by the fp64 twin at probe candidates (rc_bands below: never under
+// 1e-4 normalised, 16 x the largest deviation seen; sbo_profile.fp32_band_dm / fp32_band_dv), and every decision is first taken with
+// INTERVALS: a candidate's bounds are known to +- (dm, dv), u* to [u_lo, u_hi], the largest variance over M from below.  Candidates
+// whose intervals cannot decide
 //   (iv) the sign of a constraint's lcb                          (S, U)
 //   (i)  whether they attain u* = min_S ucb_0                    (u*)
 //   (ii) lcb_0 <= u*                                             (M)
@@ -251,10 +253,10 @@ __global__ __launch_bounds__(256) void k_rc_gdefer(const uint8_t* __restrict__ G
     if (Gc[g] && !refined[g] && var0[g] + dv0 >= vlo) list[atomicAdd(count, 1ull)] = g;
 }
 
-// re-evaluate list[0..nf) exactly and put the values in place.  fp32 models: the fp64 twin's generic kernel, into the widened
+// re-evaluate list[0..nf) exactly and put the values in place (`scatter`; without it an fp32 model's twin keeps them).  fp32 models: the fp64 twin's generic kernel, into the widened
 // copy rc_mean / rc_var; guard band of an approximating fp64 posterior (`guard`): the exact evaluator of the same model
 // (guard.hip: guard_exact_list), into the posterior buffers themselves.
-static int rc_refine(sbo_ctx* c, const long long* list, long long nf, bool guard = false) {
+static int rc_refine(sbo_ctx* c, const long long* list, long long nf, bool guard = false, bool scatter = true) {
   sbo_ctx* s = guard ? c : c->shadow;
   const long long n = c->cs.n_local;
   const int q = c->mc.q, d = c->cs.d;
@@ -294,6 +296,7 @@ static int rc_refine(sbo_ctx* c, const long long* list, long long nf, bool guard
   if ((rc = ensure(s->var, sizeof(double) * (size_t)nf * q))) return rc;
   PostOutcome none;
   if ((rc = launch_posterior(s, PostRequest{}, none))) return rc;
+  if (!scatter) return SBO_OK;             // (rc_probe: the twin's values stay in its own buffers, [q][nf])
   hipLaunchKernelGGL(k_rc_scatter, dim3(nbf), dim3(256), 0, c->stream, list, nf, q, n, (const double*)s->mean.p, (const double*)s->var.p,
                      (double*)c->rc_mean.p, (double*)c->rc_var.p, (uint8_t*)c->rc_refined.p);
   SBO_HIP(hipGetLastError());
@@ -319,10 +322,87 @@ static int rc_lipschitz64(sbo_ctx* c, const sbo_ctx* s) {
   return SBO_OK;
 }
 
-// the bands of the intervals (and of SetView::rc_band): the fp32 contract (1e-4 normalised), or the plan's guard band read back from the device
+// ---- the band of an fp32 posterior: measured, not assumed ------------------------------------------------------------------------
+// How far the fp32 kernels are from the fp64 values depends on the model: 1e-6 (normalised) at cond(K) ~ 1e3, beyond 1e-3 at the noise
+// floor of the reference's fit (log sigma_n = -5, cond(K) 1e6 .. 1e8; profiles/fp32_band_checks.md).  So, in the idiom of guard.hip, the
+// first fp32 sweep of a (model, candidate set) has the fp64 twin evaluate kRcProbes candidates through the compacted-list path of
+// rc_refine and the band becomes max(1e-4 normalised, 16 x the largest deviation) per output, for mean and variance separately; it is
+// kept until the model, the candidates or the posterior kernel change (plans_invalidate).  Ranks > 1 merge intervals through the
+// collectives, so they all take the largest band of any rank.  The standing audit (sbo_profile.guard_audit_*) samples later sweeps of
+// the same pair at other candidates and counts an output whose deviation there exceeds the band in force.
+constexpr int kRcProbes = 256;
+constexpr double kRcBandFloor = 1e-4, kRcBandFactor = 16.0;
+
+// keys[o] / keys[kMaxQ + o]: largest |fp32 - twin| of output o's mean / variance over the probes (one block; non-negative doubles
+// order as their bit patterns; a NaN counts as infinite: everything is rechecked then)
+__global__ __launch_bounds__(256) void k_rc_probe_dev(const float* __restrict__ m32, const float* __restrict__ v32, long long n,
+                                                      const long long* __restrict__ list, int P, int q, const double* __restrict__ m64,
+                                                      const double* __restrict__ v64, unsigned long long* __restrict__ keys) {
+  const int k = threadIdx.x;
+  for (int o = 0; o < q; ++o) {
+    double dm = 0.0, dv = 0.0;
+    if (k < P) {
+      const long long g = list[k];
+      dm = fabs((double)m32[(size_t)o * n + g] - m64[(size_t)o * P + k]);
+      dv = fabs((double)v32[(size_t)o * n + g] - v64[(size_t)o * P + k]);
+      if (!(dm == dm)) dm = kInfD;
+      if (!(dv == dv)) dv = kInfD;
+    }
+    const unsigned long long km = block_ext_u64<true>((unsigned long long)__double_as_longlong(dm));
+    const unsigned long long kv = block_ext_u64<true>((unsigned long long)__double_as_longlong(dv));
+    if (threadIdx.x == 0) {
+      keys[o] = km;
+      keys[kMaxQ + o] = kv;
+    }
+    __syncthreads();
+  }
+}
+
+// the resident fp32 posterior against the fp64 twin at min(n, kRcProbes) candidates: largest deviation per output (un-normalised), and
+// how many candidates were compared.  `round` picks the probe set: a golden-ratio sequence over the index range (no stride a grid axis
+// could alias with), round 0 with the first and the last candidate in it.
+static int rc_probe(sbo_ctx* c, long long round, double* dev_m, double* dev_v, int* probes) {
+  const long long n = c->cs.n_local;
+  const int q = c->mc.q;
+  const int P = (int)std::min<long long>(n, kRcProbes);
+  int rc;
+  for (int o = 0; o < kMaxQ; ++o) dev_m[o] = dev_v[o] = 0.0;
+  *probes = P;
+  if ((rc = ensure(c->rc_probe, sizeof(unsigned long long) * 2 * kMaxQ + sizeof(long long) * kRcProbes))) return rc;
+  if (P <= 0) return SBO_OK;
+  unsigned long long* keys = (unsigned long long*)c->rc_probe.p;
+  long long* list = (long long*)(keys + 2 * kMaxQ);
+  long long h[kRcProbes];
+  for (int k = 0; k < P; ++k) {
+    const double t = (double)(round * P + k + 1) * 0.6180339887498949;
+    h[k] = std::min<long long>(n - 1, (long long)((t - std::floor(t)) * (double)n));
+  }
+  if (round == 0) {
+    h[0] = 0;
+    h[P - 1] = n - 1;
+  }
+  SBO_HIP(hipMemcpyAsync(list, h, sizeof(long long) * P, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipStreamSynchronize(c->stream));                      // (`h` is on this frame)
+  if ((rc = rc_refine(c, list, P, false, false))) return rc;
+  hipLaunchKernelGGL(k_rc_probe_dev, dim3(1), dim3(256), 0, c->stream, (const float*)c->mean.p, (const float*)c->var.p, n, (const long long*)list, P, q,
+                     (const double*)c->shadow->mean.p, (const double*)c->shadow->var.p, keys);
+  SBO_HIP(hipGetLastError());
+  double hk[2 * kMaxQ];
+  SBO_HIP(hipMemcpyAsync(hk, keys, sizeof(hk), hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipStreamSynchronize(c->stream));
+  for (int o = 0; o < q; ++o) {
+    dev_m[o] = hk[o];
+    dev_v[o] = hk[kMaxQ + o];
+  }
+  return SBO_OK;
+}
+
+// the bands of the intervals (and of SetView::rc_band): of an fp32 model the measured band above, else the plan's guard band read back
+// from the device
 static int rc_bands(sbo_ctx* c, bool guard, RcBand& bd) {
   memset(&bd, 0, sizeof(bd));
   const int q = c->mc.q;
+  int rc;
   if (guard) {
     GuardBand hb;
     SBO_HIP(hipMemcpyAsync(&hb, c->gb.p, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
@@ -334,12 +414,53 @@ static int rc_bands(sbo_ctx* c, bool guard, RcBand& bd) {
     }
     return SBO_OK;
   }
+  double dev_m[kMaxQ], dev_v[kMaxQ];
+  int probes = 0;
+  if (!c->rc_band_valid) {
+    if ((rc = rc_probe(c, 0, dev_m, dev_v, &probes))) return rc;
+    double hk[2 * kMaxQ] = {};
+    for (int i = 0; i < q; ++i) {
+      const double ys = std::max(1.0, c->mc.Y_std[i]);
+      hk[i] = std::max(kRcBandFloor * ys, kRcBandFactor * dev_m[i]);
+      hk[kMaxQ + i] = std::max(kRcBandFloor * ys * ys, kRcBandFactor * dev_v[i]);
+    }
+    if (multi_rank(c)) {                  // (one band for all ranks: the largest)
+      unsigned long long* keys = (unsigned long long*)c->rc_probe.p;
+      SBO_HIP(hipMemcpyAsync(keys, hk, sizeof(hk), hipMemcpyHostToDevice, c->stream));
+      SBO_HIP(hipStreamSynchronize(c->stream));
+      if ((rc = comm_allreduce_max_u64(c, keys, 2 * kMaxQ))) return rc;
+      SBO_HIP(hipMemcpyAsync(hk, keys, sizeof(hk), hipMemcpyDeviceToHost, c->stream));
+      SBO_HIP(hipStreamSynchronize(c->stream));
+    }
+    for (int i = 0; i < q; ++i) {
+      c->rc_band_dm[i] = hk[i];
+      c->rc_band_dv[i] = hk[kMaxQ + i];
+    }
+    c->rc_band_valid = true;
+    c->rc_probe_round = 0;
+  } else if (c->guard_audit > 0 && c->audit_tick++ % std::max(1, c->guard_audit_every) == 0) {
+    // the standing audit: another probe set against the band in force
+    if ((rc = rc_probe(c, ++c->rc_probe_round, dev_m, dev_v, &probes))) return rc;
+    for (int i = 0; i < q && probes > 0; ++i) {
+      const double wm = dev_m[i] / (c->rc_band_dm[i] * c->audit_scale), wv = dev_v[i] / (c->rc_band_dv[i] * c->audit_scale);
+      c->audit_samples += 2 * probes;
+      c->audit_violations += (wm > 1.0 ? 1 : 0) + (wv > 1.0 ? 1 : 0);
+      c->audit_worst = std::max(c->audit_worst, std::max(wm, wv));
+    }
+  }
   for (int i = 0; i < q; ++i) {
-    const double ys = std::max(1.0, c->mc.Y_std[i]);
-    bd.dm[i] = 1e-4 * ys;
-    bd.dv[i] = 1e-4 * ys * ys;
+    bd.dm[i] = c->rc_band_dm[i];
+    bd.dv[i] = c->rc_band_dv[i];
   }
   return SBO_OK;
+}
+
+// the band an fp32 sweep ran with, for sbo_profile (the set phase inside the recheck rewrites the profile: called behind it)
+static void rc_profile_band(sbo_ctx* c, const RcBand& bd) {
+  for (int i = 0; i < c->mc.q; ++i) {
+    c->prof.fp32_band_dm[i] = bd.dm[i];
+    c->prof.fp32_band_dv[i] = bd.dv[i];
+  }
 }
 
 // TP = float: an fp32 model (posterior in fp32, the fp64 twin re-evaluates); TP = double: the guard band of an approximating fp64
@@ -458,6 +579,7 @@ static int sweep_safeopt_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeop
     c->prof.recheck_ms = t12;
     c->prof.total_ms = t04;
     c->prof.fp64_rechecks = total;
+    rc_profile_band(c, bd);
     c->prof.posterior_launches = reuse ? 0 : 1;
     const double nn = c->mc.n, dd = c->mc.d;
     c->prof.posterior_flops = reuse ? 0.0 : q * (nn * nn + (2 * dd + 10) * nn) * (double)n;
@@ -647,6 +769,7 @@ static int sweep_goose_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_re
     c->prof.guard_ms = t01;
   } else {
     c->prof.fp64_rechecks = total;
+    rc_profile_band(c, bd);
     c->prof.posterior_launches = reuse ? 0 : 1;
     c->prof.recheck_ms = t01;
   }
@@ -683,6 +806,7 @@ static int sweep_tr_recheck(sbo_ctx* c, const sbo_sweep_opts* o, const double* x
     res->guard_passes = 1;
   } else {
     c->prof.fp64_rechecks = total;
+    rc_profile_band(c, bd);
   }
   return rc;
 }

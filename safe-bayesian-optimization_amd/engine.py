@@ -560,8 +560,7 @@ class SweepEngine:
 
     @staticmethod
     def profile_dict(p) -> dict:
-        return {name: (list(getattr(p, name)) if name.startswith("guard_") and not name.startswith("guard_audit") and name != "guard_ms" else getattr(p, name))
-                for name, _ in L.Profile._fields_}
+        return {name: (list(getattr(p, name)) if issubclass(tp, C.Array) else getattr(p, name)) for name, tp in L.Profile._fields_}
 
     def profile(self) -> dict:
         return self.profile_dict(self.profile_struct())

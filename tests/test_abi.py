@@ -46,6 +46,24 @@ def test_version_and_struct_layout(tmp_path):
     assert C.sizeof(_lib.SweepOpts) == 24
 
 
+def test_profile_ends_with_the_fp32_band(tmp_path):
+    """The band of the last fp32 sweep is the tail of sbo_profile: two arrays of SBO_MAX_Q doubles at the offsets the C compiler gives them,
+    nothing behind them, and profile_dict hands them out as lists."""
+    src = tmp_path / "tail.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "safebo.h"\nint main(void) { printf("%zu %zu %zu %d\\n", '
+                   'offsetof(sbo_profile, fp32_band_dm), offsetof(sbo_profile, fp32_band_dv), sizeof(sbo_profile), SBO_MAX_Q); return 0; }\n')
+    exe = tmp_path / "tail"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    off_dm, off_dv, size, max_q = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    assert max_q == _lib.SBO_MAX_Q
+    assert (_lib.Profile.fp32_band_dm.offset, _lib.Profile.fp32_band_dv.offset, C.sizeof(_lib.Profile)) == (off_dm, off_dv, size)
+    assert [name for name, _ in _lib.Profile._fields_][-2:] == ["fp32_band_dm", "fp32_band_dv"]
+    assert off_dv + 8 * max_q == size and off_dv - off_dm == 8 * max_q
+    d = safebo_amd.SweepEngine.profile_dict(_lib.Profile())
+    assert d["fp32_band_dm"] == [0.0] * max_q and d["fp32_band_dv"] == [0.0] * max_q and d["guard_dm"] == [0.0] * max_q
+    assert d["fp64_rechecks"] == 0 and d["guard_ms"] == 0.0
+
+
 def test_null_arguments_are_invalid_not_crashes():
     lib = _lib.load()
     assert lib.sbo_init(0, None) == _lib.SBO_E_INVALID
