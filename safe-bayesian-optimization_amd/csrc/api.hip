@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <chrono>
 #include "internal.hpp"
 #include "device_common.hpp"
@@ -23,9 +24,7 @@ int hip_fail(hipError_t e, const char* what) {
 int ensure(DevBuf& b, size_t bytes) {
   if (bytes == 0) bytes = 16;
   if (b.bytes >= bytes) return SBO_OK;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
+  b.reset();
   hipError_t e = hipMalloc(&b.p, bytes);
   if (e != hipSuccess) {
     g_err = std::string("hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e);
@@ -76,11 +75,7 @@ int factor_sync(sbo_ctx* c) {
   return SBO_OK;
 }
 
-void release(DevBuf& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-}
+void release(DevBuf& b) { b.reset(); }
 
 int launch_soa_to_aos(sbo_ctx* c, const void* soa, void* aos);
 
@@ -111,65 +106,72 @@ int sbo_init(int device_id, sbo_ctx** out) {
     return fail(SBO_E_HIP, "no HIP device available: libsafebo has no CPU fallback");
   if (device_id < 0 || device_id >= n) return fail(SBO_E_INVALID, "device_id out of range");
   SBO_HIP(hipSetDevice(device_id));
-  sbo_ctx* c = new sbo_ctx();
+  std::unique_ptr<sbo_ctx> guard(new sbo_ctx());   // (a failure exit below deletes it: the holders destroy what has been created by then)
+  sbo_ctx* c = guard.get();
+  sbo_ctx::Owned& own = c->own;
   c->device = device_id;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) c->n_cu = prop.multiProcessorCount;
-  e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking);
+  e = hipStreamCreateWithFlags(&own.stream.s, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&own.stream2.s, hipStreamNonBlocking);
   if (e == hipSuccess) {
     // the chain stream of an overlapped sweep carries many short kernels next to one long GEMM launch: highest priority,
     // so that its workgroups are placed ahead of the GEMM's when both queues have work
     int least = 0, greatest = 0;
     if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = greatest = 0;
-    e = hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, greatest);
-    if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->stream_audit, hipStreamNonBlocking, least);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream4, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_factor, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_w, hipEventDisableTiming);
-    for (auto& ev : c->ev_grad)
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    for (auto& ev : c->ev_col)
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    for (auto& ev : c->ev_audit)
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    e = hipStreamCreateWithPriority(&own.stream3.s, hipStreamNonBlocking, greatest);
+    if (e == hipSuccess) e = hipStreamCreateWithPriority(&own.stream_audit.s, hipStreamNonBlocking, least);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&own.stream4.s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&own.ev_factor.e, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&own.ev_w.e, hipEventDisableTiming);
+    for (auto& ev : own.ev_grad)
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&ev.e, hipEventDisableTiming);
+    for (auto& ev : own.ev_col)
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&ev.e, hipEventDisableTiming);
+    for (auto& ev : own.ev_audit)
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&ev.e, hipEventDisableTiming);
   }
-  if (e != hipSuccess) { delete c; return hip_fail(e, "hipStreamCreate"); }
-  for (auto& ev : c->ev) {
-    e = hipEventCreate(&ev);
-    if (e != hipSuccess) { delete c; return hip_fail(e, "hipEventCreate"); }
+  if (e != hipSuccess) return hip_fail(e, "hipStreamCreate");
+  for (auto& ev : own.ev) {
+    e = hipEventCreate(&ev.e);
+    if (e != hipSuccess) return hip_fail(e, "hipEventCreate");
   }
-  for (auto& ev : c->ev_join) {
-    e = hipEventCreate(&ev);
-    if (e != hipSuccess) { delete c; return hip_fail(e, "hipEventCreate"); }
+  for (auto& ev : own.ev_join) {
+    e = hipEventCreate(&ev.e);
+    if (e != hipSuccess) return hip_fail(e, "hipEventCreate");
   }
-  if (hipHostMalloc((void**)&c->h_c1, sizeof(unsigned long long) * (1 + 2 * kMaxQ), hipHostMallocDefault) != hipSuccess) {
-    delete c;
-    return fail(SBO_E_HIP, "hipHostMalloc");
-  }
-  if (hipHostMalloc((void**)&c->h_back, 8192, hipHostMallocDefault) != hipSuccess) {
-    delete c;
-    return fail(SBO_E_HIP, "hipHostMalloc");
-  }
+  if (hipHostMalloc(&own.h_c1.p, sizeof(unsigned long long) * (1 + 2 * kMaxQ), hipHostMallocDefault) != hipSuccess) return fail(SBO_E_HIP, "hipHostMalloc");
+  if (hipHostMalloc(&own.h_back.p, 8192, hipHostMallocDefault) != hipSuccess) return fail(SBO_E_HIP, "hipHostMalloc");
+  // the handles the code uses (the twin gets copies of some: shadow_ensure)
+  c->stream = own.stream.s, c->stream2 = own.stream2.s, c->stream3 = own.stream3.s, c->stream_audit = own.stream_audit.s, c->stream4 = own.stream4.s;
+  c->ev_factor = own.ev_factor.e, c->ev_w = own.ev_w.e;
+  for (int i = 0; i < 8; ++i) c->ev[i] = own.ev[i].e;
+  for (int i = 0; i < SBO_MAX_Q; ++i) c->ev_join[i] = own.ev_join[i].e;
+  for (int i = 0; i < 3; ++i) c->col.ev[i] = own.ev_col[i].e;
+  for (int i = 0; i < 4; ++i) c->ev_grad[i] = own.ev_grad[i].e;
+  for (int i = 0; i < 2; ++i) c->audit.ev[i] = own.ev_audit[i].e;
+  c->dist.h_c1 = (unsigned long long*)own.h_c1.p;
+  c->h_back = (unsigned char*)own.h_back.p;
   // the sweep's scalar block and, 3 KB further, the Lipschitz keys: one allocation, so one read-back covers both
   // (layout of the 4 KB: SweepScalars at 0, the explore target / trust-region centre at 2048, the keys at 3072, a
   // collective's scratch word at 4000)
   c->lane[0].stream = c->stream;
   c->lane[1].stream = c->stream2;
   int rc = ensure(c->lane[0].scal, 4096);
-  if (rc) { delete c; return rc; }
-  c->Lmax.p = (char*)c->lane[0].scal.p + 3072;   // (a view: not in the release list)
-  c->Lmax.bytes = 512;
-  *out = c;
+  if (rc) return rc;
+  c->Lmax = (unsigned long long*)((char*)c->lane[0].scal.p + 3072);
+  *out = guard.release();
   return SBO_OK;
 }
 
 int sbo_comm_destroy_internal(sbo_ctx* ctx);
 
-// fp64 twin of an fp32 model: a context of its own (model arrays, candidate list, posterior buffers) on the owner's streams
+// fp64 twin of an fp32 model: a context of its own (model arrays, candidate list, posterior buffers) on the owner's streams.  It
+// borrows the handles; its `own` stays empty, so deleting it frees its buffers and its h_stage and nothing of the owner's
 static int shadow_ensure(sbo_ctx* c) {
-  if (c->shadow) return SBO_OK;
-  sbo_ctx* s = new sbo_ctx();
+  if (c->recheck.shadow) return SBO_OK;
+  std::unique_ptr<sbo_ctx> guard(new sbo_ctx());
+  sbo_ctx* s = guard.get();
   s->is_shadow = true;
   s->device = c->device;
   s->n_cu = c->n_cu;
@@ -179,18 +181,17 @@ static int shadow_ensure(sbo_ctx* c) {
   s->stream4 = c->stream4;
   s->ev_factor = c->ev_factor;
   s->ev_w = c->ev_w;
-  s->chol_async = 0;
+  s->opt.chol_async = 0;
   for (int i = 0; i < 8; ++i) s->ev[i] = c->ev[i];
   s->h_back = c->h_back;
-  s->fp64_recheck = 0;
-  s->bilinear = 0;
+  s->opt.fp64_recheck = 0;
+  s->opt.bilinear = 0;
   s->lane[0].stream = c->stream;
   s->lane[1].stream = c->stream2;
   int rc = ensure(s->lane[0].scal, 4096);
-  if (rc) { delete s; return rc; }
-  s->Lmax.p = (char*)s->lane[0].scal.p + 3072;
-  s->Lmax.bytes = 512;
-  c->shadow = s;
+  if (rc) return rc;
+  s->Lmax = (unsigned long long*)((char*)s->lane[0].scal.p + 3072);
+  c->recheck.shadow = guard.release();
   return SBO_OK;
 }
 
@@ -198,51 +199,9 @@ int sbo_shutdown(sbo_ctx* c) {
   if (!c) return SBO_OK;
   (void)hipSetDevice(c->device);
   guard_audit_harvest(c, true);
-  (void)hipStreamSynchronize(c->stream);
-  if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-  if (c->stream3) (void)hipStreamSynchronize(c->stream3);
-  if (c->stream4) (void)hipStreamSynchronize(c->stream4);
-  if (c->shadow) {
-    sbo_ctx* s = c->shadow;
-    for (DevBuf* b : {&s->Fpk, &s->As, &s->sqA, &s->alpha, &s->Xn, &s->pts, &s->mean, &s->var, &s->lane[0].scal, &s->mwork, &s->appendbuf, &s->Fplain, &s->alpha64})
-      release(*b);
-    if (s->h_stage) (void)hipHostFree(s->h_stage);
-    delete s;
-    c->shadow = nullptr;
-  }
+  drain_streams(c);
   sbo_comm_destroy_internal(c);
-  for (DevBuf* b : {&c->Fpk, &c->As, &c->sqA, &c->alpha, &c->Xn, &c->pts, &c->mean, &c->var, &c->maskS,
-                    &c->maskU, &c->maskM, &c->maskG, &c->maskO, &c->fitbuf, &c->fitwork, &c->refbuf, &c->partial, &c->bl_P0f, &c->bl_P1A, &c->bl_T4f, &c->bl_BtA, &c->bl_SBf, &c->bl_VA, &c->bl_small, &c->bl_work, &c->bl_cheb, &c->bl_basis, &c->mwork, &c->appendbuf, &c->rc_mean, &c->rc_var, &c->rc_list, &c->rc_refined, &c->rc_probe, &c->Fplain, &c->alpha64, &c->cpart, &c->invk_img, &c->bl_lpart, &c->bl_grad, &c->Wfull, &c->Uwin, &c->ubits, &c->gather, &c->xch, &c->shard_first, &c->E0f, &c->Er, &c->AXg, &c->tn_pts, &c->tn_vals, &c->tn_work, &c->tn_W0t, &c->tn_W1t, &c->tn_probe, &c->tn_scr, &c->tn_tail, &c->fuseS, &c->fuseU, &c->tn_gather, &c->bi_params, &c->gb, &c->gb_pts, &c->gb_vals, &c->gb_probe, &c->gb_part, &c->list_scr, &c->cbS, &c->cbU, &c->cbM, &c->cbG, &c->cbUsum, &c->col_img, &c->col_bmin, &c->col_fin, &c->col_slots, &c->col_cimg, &c->col_cbmin, &c->audit_pts, &c->audit_val, &c->audit_part, &c->audit_cnt, &c->bl_encl, &c->bl_sched, &c->lx.box, &c->lx.keys, &c->lx.vals, &c->lx.hist, &c->lx.xs, &c->lx.stats})
-    release(*b);
-  for (auto& ln : c->lane)
-    for (DevBuf* b : ln.bufs()) release(*b);
-  for (auto& b : c->tn_W) release(b);
-  for (DevBuf* b : {&c->rob, &c->rob_mask, &c->rob_part}) release(*b);
-  for (auto& ev : c->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  for (auto& ev : c->ev_join)
-    if (ev) (void)hipEventDestroy(ev);
-  for (auto& ev : c->ev_col)
-    if (ev) (void)hipEventDestroy(ev);
-  for (hipEvent_t ev : {c->lx.ev0, c->lx.ev1})
-    if (ev) (void)hipEventDestroy(ev);
-  for (auto& ev : c->ev_grad)
-    if (ev) (void)hipEventDestroy(ev);
-  for (auto& ev : c->ev_audit)
-    if (ev) (void)hipEventDestroy(ev);
-  if (c->h_c1) (void)hipHostFree(c->h_c1);
-  if (c->h_back) (void)hipHostFree(c->h_back);
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
-  if (c->ev_factor) (void)hipEventDestroy(c->ev_factor);
-  if (c->ev_w) (void)hipEventDestroy(c->ev_w);
-  if (c->h_bi_params) (void)hipHostFree(c->h_bi_params);
-  if (c->ev_bi_params) (void)hipEventDestroy((hipEvent_t)c->ev_bi_params);
-  if (c->stream4) (void)hipStreamDestroy(c->stream4);
-  if (c->stream_audit) (void)hipStreamDestroy(c->stream_audit);
-  if (c->stream3) (void)hipStreamDestroy(c->stream3);
-  if (c->stream2) (void)hipStreamDestroy(c->stream2);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;   // the twin first (Recheck), then every buffer, pinned block, event and stream (internal.hpp: the holders)
   return SBO_OK;
 }
 
@@ -257,160 +216,113 @@ int sbo_synchronize(sbo_ctx* c) {
   return SBO_OK;
 }
 
+}  // extern "C"
+
+// One row per option, one macro per way of taking the value: its bounds, what it makes stale (internal.hpp: option_changed), its hook
+namespace {
+enum OptTake {
+  kTakeBool,     // value ? 1 : 0
+  kTakeInt,      // as given
+  kTakeClamp,    // as given; outside lo .. hi the default `fallback`
+  kTakeScaled    // double: value x scale
+};
+using Options = sbo_ctx::Options;
+struct OptRow {
+  const char* name;
+  int Options::* ifield;
+  double Options::* dfield;
+  OptTake take;
+  const char* reject;       // not nullptr: a value outside lo .. hi fails with this message
+  int64_t lo, hi;
+  int fallback;
+  double scale;
+  OptEffect effect;
+  int (*hook)(sbo_ctx*, int64_t);   // runs on an accepted value, before it is stored
+};
+int hook_halo(sbo_ctx* c, int64_t) { for (auto& g : c->dist.halo_guess) g = -1; return SBO_OK; }
+int hook_tensor_guess(sbo_ctx* c, int64_t) { c->tn.bump = 0; return SBO_OK; }
+int hook_audit(sbo_ctx* c, int64_t) { guard_audit_harvest(c, true); return SBO_OK; }
+// (test hook: the audit compares against the band times value / 1e6 -- with a band a thousand times too narrow it MUST count
+// violations, which is how the suite shows that it compares real values; setting it clears the counts)
+int hook_audit_scale(sbo_ctx* c, int64_t) {
+  guard_audit_harvest(c, true);
+  c->audit.samples = c->audit.violations = c->audit.skipped = 0;
+  c->audit.worst = 0.0;
+  return SBO_OK;
+}
+int hook_audit_every(sbo_ctx* c, int64_t) { c->audit.tick = 0; return SBO_OK; }
+int hook_selftest(sbo_ctx* c, int64_t value) {
+  if (value && !c->dist.comm && !c->dist.relay_allreduce)
+    return fail(SBO_E_INVALID, "comm_selftest needs a communicator: call sbo_comm_init(ctx, 1, 0, id) with a unique id first");
+  return SBO_OK;
+}
+#define OPT_BOOL(name, effect, hook) {#name, &Options::name, nullptr, kTakeBool, nullptr, 0, 0, 0, 0.0, effect, hook}
+#define OPT_RANGE(name, lo, hi, msg, effect, hook) {#name, &Options::name, nullptr, kTakeInt, msg, lo, hi, 0, 0.0, effect, hook}
+#define OPT_CLAMP(name, lo, hi, fallback, effect, hook) {#name, &Options::name, nullptr, kTakeClamp, nullptr, lo, hi, fallback, 0.0, effect, hook}
+#define OPT_RAW(name, effect, hook) {#name, &Options::name, nullptr, kTakeInt, nullptr, 0, 0, 0, 0.0, effect, hook}
+#define OPT_SCALED(key, field, scale, lo, hi, msg, effect, hook) {key, nullptr, &Options::field, kTakeScaled, msg, lo, hi, 0, scale, effect, hook}
+const OptRow kOptions[] = {
+    OPT_BOOL(halo_spec, kOptNothing, hook_halo),
+    OPT_BOOL(comm_events, kOptNothing, nullptr),
+    OPT_SCALED("cheb_tol_e17", cheb_tol, 1e-17, 0, 0, nullptr, kOptPlans, nullptr),
+    OPT_RANGE(tensor_guess_pct, 10, 400, "tensor_guess_pct must be within 10 .. 400", kOptTensor, hook_tensor_guess),
+    OPT_BOOL(tensor_cheb, kOptTensor, nullptr),
+    OPT_CLAMP(exact_lazy, 0, 2, 1, kOptNothing, nullptr),   // 2: the late-recheck path runs on every sweep (test)
+    OPT_BOOL(chol_async, kOptNothing, nullptr),
+    OPT_RANGE(bilinear, 0, 2, "bilinear must be 0 (off), 1 (on; a model's first sweep by node interpolation) or 2 (on, K1b's plan from the first sweep)", kOptPlans, nullptr),
+    OPT_BOOL(phase_events, kOptNothing, nullptr),
+    // 0: off; 8 / 16 / 32 / 64: lanes per listed candidate (anything else: the default, 16)
+    OPT_RAW(scan_waves, kOptNothing, nullptr),
+    OPT_BOOL(set_lanes, kOptNothing, nullptr),
+    OPT_BOOL(result_mirror, kOptNothing, nullptr),
+    OPT_BOOL(set_fuse, kOptNothing, nullptr),
+    OPT_RANGE(col_path, 0, 2, "col_path must be 0 (never), 1 (auto) or 2 (whenever the grid's shape allows)", kOptNothing, nullptr),
+    OPT_RANGE(guard_audit, 0, 1 << 20, "guard_audit: samples per sweep, 0 (off) .. 1048576", kOptNothing, hook_audit),
+    OPT_SCALED("guard_audit_scale_ppm", audit_scale, 1e-6, 1, 1000000000, "guard_audit_scale_ppm: 1 .. 1e9", kOptNothing, hook_audit_scale),
+    OPT_RANGE(guard_audit_every, 1, 1 << 20, "guard_audit_every: 1 .. 1048576 sweeps", kOptNothing, hook_audit_every),
+    OPT_RANGE(grad_defer, 0, 3, "grad_defer must be 0 .. 3", kOptInterp, nullptr),
+    OPT_BOOL(k1_sched, kOptNothing, nullptr),
+    OPT_BOOL(col_overlap, kOptNothing, nullptr),
+    OPT_BOOL(scan_blocks, kOptNothing, nullptr),
+    OPT_RANGE(fuse_classify, -1, 1, "fuse_classify must be -1 (auto), 0 or 1", kOptNothing, nullptr),
+    OPT_BOOL(goose_pairs, kOptNothing, nullptr),
+    OPT_RANGE(guard_band, 0, 2, "guard_band must be 0 (off), 1 (on) or 2 (re-evaluate on every sweep)", kOptPlansBand, nullptr),
+    OPT_BOOL(fp64_recheck, kOptNothing, nullptr),       // (takes effect at the next sbo_model_set: the fp64 twin is built there)
+    OPT_BOOL(comm_selftest, kOptNothing, hook_selftest),
+    OPT_RANGE(refine_lds, 0, 1, "refine_lds must be 0 (stream M) or 1 (LDS when it fits)", kOptNothing, nullptr),
+    OPT_RANGE(list_index, -1, 1, "list_index must be -1 (auto), 0 (never) or 1 (always)", kOptNothing, nullptr),
+    OPT_RANGE(posterior_path, 0, 2, "posterior_path must be 0 (auto), 1 (generic) or 2 (generic, chunked)", kOptPosterior, nullptr),
+};
+#undef OPT_BOOL
+#undef OPT_RANGE
+#undef OPT_CLAMP
+#undef OPT_RAW
+#undef OPT_SCALED
+}  // namespace
+
 int sbo_set_option(sbo_ctx* c, const char* key, int64_t value) {
   if (!c || !key) return fail(SBO_E_INVALID, "ctx/key is NULL");
-  if (!strcmp(key, "halo_spec")) {
-    c->halo_spec = value ? 1 : 0;
-    for (auto& g : c->halo_guess) g = -1;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "comm_events")) {
-    c->comm_events = value ? 1 : 0;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "cheb_tol_e17")) {
-    c->cheb_tol = (double)value * 1e-17;
-    plans_invalidate(c);
-    return SBO_OK;
-  }
-  if (!strcmp(key, "tensor_guess_pct")) {
-    if (value < 10 || value > 400) return fail(SBO_E_INVALID, "tensor_guess_pct must be within 10 .. 400");
-    c->tensor_guess_pct = (int)value;
-    c->tn_valid = false;
-    c->tn_bump = 0;
-    c->posterior_valid = false;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "tensor_cheb")) {
-    c->tensor_cheb = value ? 1 : 0;
-    c->tn_valid = false;
-    c->posterior_valid = false;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "exact_lazy")) {
-    c->exact_lazy = value < 0 || value > 2 ? 1 : (int)value;      // 2: the late-recheck path runs on every sweep (test)
-    return SBO_OK;
-  }
-  if (!strcmp(key, "chol_async")) {
-    c->chol_async = value ? 1 : 0;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "bilinear")) {
-    if (value < 0 || value > 2) return fail(SBO_E_INVALID, "bilinear must be 0 (off), 1 (on; a model's first sweep by node interpolation) or 2 (on, K1b's plan from the first sweep)");
-    c->bilinear = (int)value;
-    plans_invalidate(c);
-    return SBO_OK;
-  }
-  if (!strcmp(key, "phase_events")) {
-    c->phase_events = value ? 1 : 0;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "scan_waves")) {
-    c->scan_waves = (int)value;   // 0: off; 8 / 16 / 32 / 64: lanes per listed candidate (anything else: the default, 16)
-    return SBO_OK;
-  }
-  if (!strcmp(key, "set_lanes")) {
-    c->set_lanes = value ? 1 : 0;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "result_mirror")) {
-    c->result_mirror = value ? 1 : 0;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "set_fuse")) {
-    c->set_fuse = value ? 1 : 0;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "col_path")) {
-    if (value < 0 || value > 2) return fail(SBO_E_INVALID, "col_path must be 0 (never), 1 (auto) or 2 (whenever the grid's shape allows)");
-    c->col_path = (int)value;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "guard_audit")) {
-    if (value < 0 || value > (1 << 20)) return fail(SBO_E_INVALID, "guard_audit: samples per sweep, 0 (off) .. 1048576");
-    guard_audit_harvest(c, true);
-    c->guard_audit = (int)value;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "guard_audit_scale_ppm")) {
-    // (test hook: the audit compares against the band times value / 1e6 -- with a band a thousand times too narrow it MUST count
-    // violations, which is how the suite shows that it compares real values; setting it clears the counts)
-    if (value < 1 || value > 1000000000) return fail(SBO_E_INVALID, "guard_audit_scale_ppm: 1 .. 1e9");
-    guard_audit_harvest(c, true);
-    c->audit_scale = (double)value * 1e-6;
-    c->audit_samples = c->audit_violations = c->audit_skipped = 0;
-    c->audit_worst = 0.0;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "guard_audit_every")) {
-    if (value < 1 || value > (1 << 20)) return fail(SBO_E_INVALID, "guard_audit_every: 1 .. 1048576 sweeps");
-    c->guard_audit_every = (int)value;
-    c->audit_tick = 0;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "grad_defer")) {
-    if (value < 0 || value > 3) return fail(SBO_E_INVALID, "grad_defer must be 0 .. 3");
-    c->grad_defer = (int)value;
-    c->bi.valid = false;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "k1_sched")) {
-    c->k1_sched = value ? 1 : 0;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "col_overlap")) {
-    c->col_overlap = value ? 1 : 0;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "scan_blocks")) {
-    c->scan_blocks = value ? 1 : 0;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "fuse_classify")) {
-    if (value < -1 || value > 1) return fail(SBO_E_INVALID, "fuse_classify must be -1 (auto), 0 or 1");
-    c->fuse_classify = (int)value;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "goose_pairs")) {
-    c->goose_pairs = value ? 1 : 0;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "guard_band")) {
-    if (value < 0 || value > 2) return fail(SBO_E_INVALID, "guard_band must be 0 (off), 1 (on) or 2 (re-evaluate on every sweep)");
-    c->guard_band = (int)value;
-    plans_invalidate(c);                    // (plans measure their band when they are built)
-    c->tn_valid = false;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "fp64_recheck")) {
-    c->fp64_recheck = value ? 1 : 0;       // (takes effect at the next sbo_model_set: the fp64 twin is built there)
-    return SBO_OK;
-  }
-  if (!strcmp(key, "comm_selftest")) {
-    if (value && !c->comm && !c->relay_allreduce)
-      return fail(SBO_E_INVALID, "comm_selftest needs a communicator: call sbo_comm_init(ctx, 1, 0, id) with a unique id first");
-    c->comm_selftest = value ? 1 : 0;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "refine_lds")) {
-    if (value < 0 || value > 1) return fail(SBO_E_INVALID, "refine_lds must be 0 (stream M) or 1 (LDS when it fits)");
-    c->refine_lds = (int)value;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "list_index")) {
-    if (value < -1 || value > 1) return fail(SBO_E_INVALID, "list_index must be -1 (auto), 0 (never) or 1 (always)");
-    c->list_index = (int)value;
-    return SBO_OK;
-  }
-  if (!strcmp(key, "posterior_path")) {
-    if (value < 0 || value > 2) return fail(SBO_E_INVALID, "posterior_path must be 0 (auto), 1 (generic) or 2 (generic, chunked)");
-    c->posterior_path = (int)value;
-    c->posterior_valid = false;
-    c->rc_band_valid = false;              // (another kernel sums in another order: an fp32 model's band is measured again)
+  for (const OptRow& r : kOptions) {
+    if (strcmp(key, r.name)) continue;
+    const bool inside = value >= r.lo && value <= r.hi;
+    if (r.reject && !inside) return fail(SBO_E_INVALID, r.reject);
+    if (r.hook) {
+      const int rc = r.hook(c, value);
+      if (rc) return rc;
+    }
+    switch (r.take) {
+      case kTakeBool: c->opt.*r.ifield = value ? 1 : 0; break;
+      case kTakeInt: c->opt.*r.ifield = (int)value; break;
+      case kTakeClamp: c->opt.*r.ifield = inside ? (int)value : r.fallback; break;
+      case kTakeScaled: c->opt.*r.dfield = (double)value * r.scale; break;
+    }
+    option_changed(c, r.effect);
     return SBO_OK;
   }
   return fail(SBO_E_INVALID, std::string("unknown option ") + key);
 }
+
+extern "C" {
 
 static int model_set_impl(sbo_ctx* c, int dtype, const char* kernel, int n, int d, int q, const double* X_mean,
                           const double* X_std, const double* Y_mean, const double* Y_std, const double* X_norm,
@@ -428,9 +340,7 @@ static int model_set_impl(sbo_ctx* c, int dtype, const char* kernel, int n, int 
     return fail(SBO_E_INVALID, "NULL model array");
   SBO_HIP(hipSetDevice(c->device));
   c->has_model = false;
-  c->posterior_valid = false;
-  c->masks_valid = false;
-  c->rob_valid = false;
+  model_changed(c);
   ModelConst& mc = c->mc;
   memset(&mc, 0, sizeof(mc));
   mc.n = n; mc.d = d; mc.q = q;
@@ -454,7 +364,6 @@ static int model_set_impl(sbo_ctx* c, int dtype, const char* kernel, int n, int 
     }
   }
   c->dtype = dtype;
-  plans_invalidate(c);
   ++c->model_serial;
   // derived arrays (As, sqA, Xn, rhs), factorisation, alpha and the fragment images of the factor: on the device (model.hip)
   int rc = model_build(c, invK, X_norm, Y_norm);
@@ -465,14 +374,14 @@ static int model_set_impl(sbo_ctx* c, int dtype, const char* kernel, int n, int 
   if (!c->is_shadow && interp_applicable(c)) {
     if ((rc = interp_setup(c))) return rc;
   } else if (!c->is_shadow && bilinear_applicable(c) && (rc = bilinear_setup(c))) return rc;
-  if (dtype == SBO_F32 && c->fp64_recheck && !c->is_shadow) {
+  if (dtype == SBO_F32 && c->opt.fp64_recheck && !c->is_shadow) {
     // the fp64 twin: same constants, double arrays and factor images (built from the same inputs)
     if ((rc = shadow_ensure(c))) return rc;
-    sbo_ctx* s = c->shadow;
+    sbo_ctx* s = c->recheck.shadow;
     s->mc = c->mc;
     s->dtype = SBO_F64;
     s->has_model = false;
-    s->posterior_valid = false;
+    model_changed(s);
     s->h_Xnorm = c->h_Xnorm;
     ++s->model_serial;
     if ((rc = model_build(s, invK, X_norm, Y_norm))) return rc;
@@ -607,10 +516,8 @@ int sbo_model_append(sbo_ctx* c, const double* x_norm_new, const double* y_norm_
   // every output's update is computed and checked before anything is written: a refused append leaves the model as it was
   int rc = model_append_check(c, kvec, kappa, rho);
   if (rc) return rc;
-  if (c->shadow && c->shadow->has_model && (rc = sbo_model_append(c->shadow, x_norm_new, y_norm_new))) return rc;
+  if (c->recheck.shadow && c->recheck.shadow->has_model && (rc = sbo_model_append(c->recheck.shadow, x_norm_new, y_norm_new))) return rc;
   if ((rc = model_append_commit(c))) return rc;
-  c->invk_img_valid = false;                                    // (the images of the caller's invK do not follow an append)
-  c->invk_w_valid = false;
   // the derived arrays with the new row (device), then the re-pack of the factor images
   c->h_Xnorm.insert(c->h_Xnorm.end(), x_norm_new, x_norm_new + d);
   mc.n = n + 1;
@@ -618,9 +525,7 @@ int sbo_model_append(sbo_ctx* c, const double* x_norm_new, const double* y_norm_
   if ((rc = model_prep(c, c->h_Xnorm.data()))) return rc;
   if ((rc = model_repack(c))) return rc;
   ++c->model_serial;
-  c->masks_valid = false;
-  c->rob_valid = false;
-  plans_invalidate(c);
+  model_changed(c);
   return SBO_OK;
 }
 
@@ -650,18 +555,13 @@ int sbo_candidates_points(sbo_ctx* c, const void* points, int points_dtype, int6
   memset(&c->cs, 0, sizeof(c->cs));
   c->cs.kind = 0; c->cs.d = d; c->cs.pts_dtype = points_dtype; c->cs.pts = c->pts.p;
   c->cs.n_local = n_local; c->cs.first = first;
-  c->grid_total = n_local;
-  c->lx.valid = false;
-  c->sharded = false;
+  c->dist.grid_total = n_local;
   c->has_cand = true;
-  c->rob_valid = false;
-  plans_invalidate(c);
-  c->masks_valid = false;
+  candidates_changed(c, kCandPoints);
   return SBO_OK;
 }
 
-int sbo_candidates_grid(sbo_ctx* c, int d, const double* lo, const double* hi, const int64_t* count, int64_t first,
-                        int64_t n_local) {
+static int grid_set(sbo_ctx* c, int d, const double* lo, const double* hi, const int64_t* count, int64_t first, int64_t n_local, CandKind kind) {
   if (c) guard_audit_harvest(c, true);
   if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
   if (d < 1 || d > SBO_MAX_D || !lo || !hi || !count) return fail(SBO_E_INVALID, "bad grid description");
@@ -680,14 +580,15 @@ int sbo_candidates_grid(sbo_ctx* c, int d, const double* lo, const double* hi, c
     c->cs.step[a] = count[a] > 1 ? (hi[a] - lo[a]) / (double)(count[a] - 1) : 0.0;
   }
   for (int a = d; a < kMaxD; ++a) c->cs.count[a] = 1;
-  c->grid_total = (long long)total;
-  for (auto& g : c->halo_guess) g = -1;
-  c->sharded = false;
+  c->dist.grid_total = (long long)total;
   c->has_cand = true;
-  c->rob_valid = false;
-  plans_invalidate(c);
-  c->masks_valid = false;
+  candidates_changed(c, kind);
   return SBO_OK;
+}
+
+int sbo_candidates_grid(sbo_ctx* c, int d, const double* lo, const double* hi, const int64_t* count, int64_t first,
+                        int64_t n_local) {
+  return grid_set(c, d, lo, hi, count, first, n_local, kCandGrid);
 }
 
 int sbo_candidates_grid_sharded(sbo_ctx* c, int d, const double* lo, const double* hi, const int64_t* count,
@@ -701,15 +602,14 @@ int sbo_candidates_grid_sharded(sbo_ctx* c, int d, const double* lo, const doubl
   }
   if (count[d - 1] < 1) return fail(SBO_E_INVALID, "grid count must be >= 1");
   const long long planes = count[d - 1];
-  const int W = c->world, r = c->rank;
+  const int W = c->dist.world, r = c->dist.rank;
   std::vector<long long> first_of(W + 1);
   for (int i = 0; i <= W; ++i) first_of[i] = (planes * i / W) * stride;
-  int rc = sbo_candidates_grid(c, d, lo, hi, count, first_of[r], first_of[r + 1] - first_of[r]);
+  int rc = grid_set(c, d, lo, hi, count, first_of[r], first_of[r + 1] - first_of[r], kCandGridSharded);
   if (rc) return rc;
-  c->first_of = first_of;
-  c->sharded = true;
-  if ((rc = ensure(c->shard_first, sizeof(long long) * (W + 1)))) return rc;
-  SBO_HIP(hipMemcpy(c->shard_first.p, first_of.data(), sizeof(long long) * (W + 1), hipMemcpyHostToDevice));
+  c->dist.first_of = first_of;
+  if ((rc = ensure(c->dist.shard_first, sizeof(long long) * (W + 1)))) return rc;
+  SBO_HIP(hipMemcpy(c->dist.shard_first.p, first_of.data(), sizeof(long long) * (W + 1), hipMemcpyHostToDevice));
   if (first_out) *first_out = first_of[r];
   if (n_local_out) *n_local_out = first_of[r + 1] - first_of[r];
   return SBO_OK;
@@ -735,7 +635,7 @@ int sbo::posterior_enqueue(sbo_ctx* c, const PostRequest& req, PostOutcome* out)
   guard_audit_harvest(c, false);
   if ((rc = alloc_workspace(c))) return rc;
   // (a standing audit of the last sweep may not have taken its sample of mean / var yet: it is a few microseconds of work on its stream)
-  if (c->audit_pending) SBO_HIP(hipStreamWaitEvent(c->stream, c->ev_audit[0], 0));
+  if (c->audit.pending) SBO_HIP(hipStreamWaitEvent(c->stream, c->audit.ev[0], 0));
   if (c->cs.n_local > 0 && (rc = launch_posterior(c, req, *out))) return rc;
   c->posterior_valid = true;
   c->post_l0_missing = req.sweep_lean != 0;
@@ -782,12 +682,11 @@ int sbo_posterior_get(sbo_ctx* c, void* mean_out, void* var_out) {
     void* dst = which ? var_out : mean_out;
     if (!dst) continue;
     rc = launch_soa_to_aos(c, which ? c->var.p : c->mean.p, tmp.p);
-    if (rc) { release(tmp); return rc; }
+    if (rc) return rc;
     hipError_t e = hipMemcpyAsync(dst, tmp.p, bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { release(tmp); return hip_fail(e, "copy posterior to host"); }
+    if (e != hipSuccess) return hip_fail(e, "copy posterior to host");
   }
-  release(tmp);
   return SBO_OK;
 }
 
@@ -809,7 +708,6 @@ int sbo_bounds(sbo_ctx* c, double b, int index, int kind, void* out) {
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) rc = hip_fail(e, "copy bounds to host");
   }
-  release(tmp);
   return rc;
 }
 
@@ -820,39 +718,39 @@ int sbo_profile_get(sbo_ctx* c, sbo_profile* out) {
   out->posterior_executed_flops = c->prof.posterior_launches ? c->last_k1_flops : 0.0;
   out->posterior_setup_ms = c->bl.setup_ms;
   guard_audit_harvest(c, false);
-  out->guard_audit_samples = c->audit_samples;
-  out->guard_audit_violations = c->audit_violations;
-  out->guard_audit_worst = c->audit_worst;
-  out->guard_audit_skipped = c->audit_skipped;
+  out->guard_audit_samples = c->audit.samples;
+  out->guard_audit_violations = c->audit.violations;
+  out->guard_audit_worst = c->audit.worst;
+  out->guard_audit_skipped = c->audit.skipped;
   // the guard band of the posterior that is resident (K1b measures it on the device: a small read-back, off the hot path)
   for (int o = 0; o < SBO_MAX_Q; ++o)
     out->guard_dm[o] = out->guard_dv[o] = out->guard_rl[o] = out->guard_analytic_dm[o] = out->guard_analytic_dv[o] = out->guard_probe_dm[o] = out->guard_probe_dv[o] = 0.0;
-  if (c->gb_active && c->guard_band && c->gb.p && c->posterior_valid) {
-    if (!c->gb_host_valid) {               // (once per plan: the profile is read after every sweep of a timing loop)
+  if (c->gb.active && c->opt.guard_band && c->gb.buf.p && c->posterior_valid) {
+    if (!c->gb.host_valid) {               // (once per plan: the profile is read after every sweep of a timing loop)
       GuardBand hb;
-      if (c->gb_mirrored) {
+      if (c->gb.mirrored) {
         // (the plan's band kernel wrote a copy into the pinned block; the sweep whose posterior is valid has synchronised since)
         memcpy(&hb, c->h_back + kGbMirrorOffset, sizeof(hb));
       } else {
         SBO_HIP(hipSetDevice(c->device));
-        SBO_HIP(hipMemcpyAsync(&hb, c->gb.p, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
+        SBO_HIP(hipMemcpyAsync(&hb, c->gb.buf.p, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
         SBO_HIP(hipStreamSynchronize(c->stream));
       }
       for (int o = 0; o < SBO_MAX_Q; ++o) {
-        c->gb_host[o] = hb.dm[o]; c->gb_host[SBO_MAX_Q + o] = hb.dv[o]; c->gb_host[2 * SBO_MAX_Q + o] = hb.rl[o];
-        c->gb_host[3 * SBO_MAX_Q + o] = hb.an_m[o]; c->gb_host[4 * SBO_MAX_Q + o] = hb.an_v[o];
-        c->gb_host[5 * SBO_MAX_Q + o] = hb.pr_m[o]; c->gb_host[6 * SBO_MAX_Q + o] = hb.pr_v[o];
+        c->gb.host[o] = hb.dm[o]; c->gb.host[SBO_MAX_Q + o] = hb.dv[o]; c->gb.host[2 * SBO_MAX_Q + o] = hb.rl[o];
+        c->gb.host[3 * SBO_MAX_Q + o] = hb.an_m[o]; c->gb.host[4 * SBO_MAX_Q + o] = hb.an_v[o];
+        c->gb.host[5 * SBO_MAX_Q + o] = hb.pr_m[o]; c->gb.host[6 * SBO_MAX_Q + o] = hb.pr_v[o];
       }
-      c->gb_host_valid = true;
+      c->gb.host_valid = true;
     }
     for (int o = 0; o < c->mc.q; ++o) {
-      out->guard_dm[o] = c->gb_host[o];
-      out->guard_dv[o] = c->gb_host[SBO_MAX_Q + o];
-      out->guard_rl[o] = c->gb_host[2 * SBO_MAX_Q + o];
-      out->guard_analytic_dm[o] = c->gb_host[3 * SBO_MAX_Q + o];
-      out->guard_analytic_dv[o] = c->gb_host[4 * SBO_MAX_Q + o];
-      out->guard_probe_dm[o] = c->gb_host[5 * SBO_MAX_Q + o];
-      out->guard_probe_dv[o] = c->gb_host[6 * SBO_MAX_Q + o];
+      out->guard_dm[o] = c->gb.host[o];
+      out->guard_dv[o] = c->gb.host[SBO_MAX_Q + o];
+      out->guard_rl[o] = c->gb.host[2 * SBO_MAX_Q + o];
+      out->guard_analytic_dm[o] = c->gb.host[3 * SBO_MAX_Q + o];
+      out->guard_analytic_dv[o] = c->gb.host[4 * SBO_MAX_Q + o];
+      out->guard_probe_dm[o] = c->gb.host[5 * SBO_MAX_Q + o];
+      out->guard_probe_dv[o] = c->gb.host[6 * SBO_MAX_Q + o];
     }
   }
   return SBO_OK;

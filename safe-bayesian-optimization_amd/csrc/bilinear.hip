@@ -1463,18 +1463,18 @@ static double axis_position(const sbo_ctx* c, int a, long long i) {
 
 bool bilinear_applicable(const sbo_ctx* c) {
   const CandSpec& cs = c->cs;
-  if (!c->bilinear || c->dtype != SBO_F64 || !c->has_cand || cs.kind != 1 || cs.d != 2 || c->mc.d != 2) return false;
+  if (!c->opt.bilinear || c->dtype != SBO_F64 || !c->has_cand || cs.kind != 1 || cs.d != 2 || c->mc.d != 2) return false;
   const long long cnt0 = cs.count[0];
-  if ((cs.n_local <= 0 && !(c->sharded && c->world > 1)) || cs.first % cnt0 != 0 || cs.n_local % cnt0 != 0) return false;
+  if ((cs.n_local <= 0 && !(c->dist.sharded && c->dist.world > 1)) || cs.first % cnt0 != 0 || cs.n_local % cnt0 != 0) return false;
   // the bases pay off (and the interpolation interval is meaningful) only on real grids
   // (ranks > 1: ONE decision for all of them -- the recheck behind an approximating posterior contains collectives, so a rank that
   // took the exact kernel K1g for its 15-line shard would return while its 16-line neighbours wait for it there.  The shard sizes
   // are known to every rank: the smallest one decides.)
   long long min_lines = cs.n_local / cnt0;
-  if (c->sharded && c->first_of.size() == (size_t)c->world + 1)
-    for (int r = 0; r < c->world; ++r) min_lines = std::min(min_lines, (c->first_of[r + 1] - c->first_of[r]) / cnt0);
+  if (c->dist.sharded && c->dist.first_of.size() == (size_t)c->dist.world + 1)
+    for (int r = 0; r < c->dist.world; ++r) min_lines = std::min(min_lines, (c->dist.first_of[r + 1] - c->dist.first_of[r]) / cnt0);
   // (a caller's matrix whose factor is deferred: the band's reference runs on the matrix itself and must fit its LDS budget)
-  if (c->mc.factor == SBO_FACTOR_INVK && c->chol_async && c->mc.npad > kGuardRefMaxNpad) return false;
+  if (c->mc.factor == SBO_FACTOR_INVK && c->opt.chol_async && c->mc.npad > kGuardRefMaxNpad) return false;
   return cnt0 >= 64 && cs.count[1] >= 64 && min_lines >= 16 && c->alpha64.p != nullptr && c->f_cap >= c->mc.n;
 }
 
@@ -1533,9 +1533,9 @@ int bilinear_basis_enqueue(sbo_ctx* c, hipStream_t st, bool force_big) {
     // n <= 128: 256 threads, samples / residual rows in LDS (degree <= 64 assumed: a larger one fails over to the big form)
     const bool small = !force_big && n <= kBasisResLds / 64;
     const size_t dyn = sizeof(double) * (kBasisQLds + (small ? kBasisResLds : 0));
-    long long* dbg = nullptr;
+    DevBuf dbgbuf;
     const bool phases = getenv("SBO_BL_TIMING") != nullptr;
-    if (phases && hipMalloc(&dbg, sizeof(long long) * 81) != hipSuccess) dbg = nullptr;
+    long long* dbg = phases && ensure(dbgbuf, sizeof(long long) * 81) == SBO_OK ? (long long*)dbgbuf.p : nullptr;
     // front end on the whole chip: degree per job, then its coefficient rows into the jobs' workspaces
     int* rcjob = (int*)(base + L.rcjob);
     SBO_HIP(hipMemsetAsync(rcjob, 0, sizeof(double) * 5 * q, st));          // (the degrees and, behind them, the truncation figures)
@@ -1565,7 +1565,6 @@ int bilinear_basis_enqueue(sbo_ctx* c, hipStream_t st, bool force_big) {
         for (int i = 1; i < (int)h[80]; ++i) fprintf(stderr, " %.1f", (double)(h[i] - h[i - 1]) / 100.0);
         fprintf(stderr, "\n");
       }
-      (void)hipFree(dbg);
     }
   }
   SBO_HIP(hipMemcpyAsync(c->h_back + 4096, base + L.info, sizeof(int) * 8 * q, hipMemcpyDeviceToHost, st));
@@ -1722,8 +1721,8 @@ int bilinear_setup(sbo_ctx* c) {
   // fragments (k = observation) and as images of C^T, then G = C^T C.  With a CALLER's invK (sbo_ctx::invk_img, r03): W =
   // invK Z with the matrix as given -- the contraction the reference itself performs, models/GP_Safe.py:341-343, no
   // factorisation of an ill-conditioned inverse in between --, then G^T = W^T Z; k_bl_t4f symmetrises what rounding leaves.
-  if (mc.factor == SBO_FACTOR_INVK && c->chol_async && !c->invk_img_valid && c->invk_w_valid && (rc = model_pack_invk(c))) return rc;
-  const bool direct = mc.factor == SBO_FACTOR_INVK && c->chol_async && c->invk_img_valid;
+  if (mc.factor == SBO_FACTOR_INVK && c->opt.chol_async && !c->invk_img_valid && c->invk_w_valid && (rc = model_pack_invk(c))) return rc;
+  const bool direct = mc.factor == SBO_FACTOR_INVK && c->opt.chol_async && c->invk_img_valid;
   auto x_head = [&]() -> int {
   if (!direct && (rc = factor_sync(c))) return rc;
   if (direct) {
@@ -1786,7 +1785,7 @@ int bilinear_setup(sbo_ctx* c) {
     }
   }
   // guard band of this plan (guard.hip): the exact evaluator at the probe points runs here, beside the core's GEMM chain
-  const bool band = c->guard_band && !c->is_shadow;
+  const bool band = c->opt.guard_band && !c->is_shadow;
   double *gref_m = nullptr, *gref_v = nullptr;
   if (band && (rc = guard_probe_reference(c, zs, &gref_m, &gref_v))) return rc;
   // (and the exact gradient components there: the scale the analytic band of the Lipschitz keys is taken relative to)
@@ -1816,7 +1815,7 @@ int bilinear_setup(sbo_ctx* c) {
                        nPC1, (const double*)T4p, nT4p, KBp1, nrbD1, KBp0, Yt, nYt, (double*)nullptr, 0ll);
     hipLaunchKernelGGL((k_bgemm<4, 0, 2>), dim3((unsigned)((ncsD0 + 3) / 4), (unsigned)((nrbD1 + 3) / 4), uq), dim3(256), 0, xs, (const double*)Yt,
                        nYt, (const double*)PC0, nPC0, KBp0, nrbD1, ncsD0, Chat, nCh, (double*)nullptr, (long long)D0m);
-    hipLaunchKernelGGL(k_cheb_trunc, dim3(uq), dim3(1024), 0, xs, dm, (const double*)Chat, c->cheb_tol, eff);
+    hipLaunchKernelGGL(k_cheb_trunc, dim3(uq), dim3(1024), 0, xs, dm, (const double*)Chat, c->opt.cheb_tol, eff);
     hipLaunchKernelGGL(k_cheb_t4f, blocks(g.sT4f, uq), dim3(256), 0, xs, dm, (const double*)Chat, g.sT4f, (double*)c->bl_T4f.p);
     // (the counts also travel to the host, unwaited: the profile's flop count reads them after the next sweep's own sync)
     SBO_HIP(hipMemcpyAsync(c->h_back + 5376, eff, sizeof(int) * 4 * q, hipMemcpyDeviceToHost, xs));

@@ -354,10 +354,10 @@ __global__ __launch_bounds__(256) void k_gb_band_i(const InterpParams* __restric
 }
 
 bool interp_applicable(const sbo_ctx* c) {
-  if (c->bilinear != 1 || c->is_shadow || !bilinear_applicable(c)) return false;
+  if (c->opt.bilinear != 1 || c->is_shadow || !bilinear_applicable(c)) return false;
   // (the node values come from the reference formula on the caller's matrix: the packed images sbo_model_set made of it)
   // (a grid that arrived after the model: the images are packed on demand from the upload that still sits in the build workspace)
-  return c->mc.factor == SBO_FACTOR_INVK && c->chol_async && (c->invk_img_valid || c->invk_w_valid) && c->mc.npad % 16 == 0 &&
+  return c->mc.factor == SBO_FACTOR_INVK && c->opt.chol_async && (c->invk_img_valid || c->invk_w_valid) && c->mc.npad % 16 == 0 &&
          c->dtype == SBO_F64;
 }
 
@@ -433,22 +433,22 @@ int interp_setup(sbo_ctx* c) {
   const unsigned uq = (unsigned)q;
   auto blocks = [&](size_t total, unsigned y) { return dim3((unsigned)std::min<size_t>((total + 255) / 256, 1u << 16), y); };
   hipStream_t xs = c->stream, ys = c->stream2 ? c->stream2 : c->stream, zs = (ys != xs && c->stream3) ? c->stream3 : ys;
-  const bool band = c->guard_band != 0;
+  const bool band = c->opt.guard_band != 0;
   // buffers of the gate and of the probes
   const int ntx = (ncs0 + 7) / 8, nty = (nrb + 3) / 4;
   const size_t nt = (size_t)ntx * nty, head = (size_t)q * 2 * nt + 4 * (size_t)q;
   const size_t nS0 = (size_t)q * Dn * cnt0, nVb = (size_t)q * 3 * Dn * nlines;
   if ((rc = ensure(c->bl_grad, sizeof(double) * (head + nS0 + nVb)))) return rc;
-  if ((rc = ensure(c->gb_pts, sizeof(double) * ((size_t)QP * kGbProbes + 2 * (size_t)kGbProbes + 2 * (size_t)q * kGbProbes)))) return rc;
+  if ((rc = ensure(c->gb.pts, sizeof(double) * ((size_t)QP * kGbProbes + 2 * (size_t)kGbProbes + 2 * (size_t)q * kGbProbes)))) return rc;
   if ((rc = ensure(c->bi_params, sizeof(InterpParams)))) return rc;
-  if (!c->h_bi_params && hipHostMalloc(&c->h_bi_params, sizeof(InterpParams), hipHostMallocDefault) != hipSuccess)
+  if (!c->h_bi_params.p && hipHostMalloc(&c->h_bi_params.p, sizeof(InterpParams), hipHostMallocDefault) != hipSuccess)
     return fail(SBO_E_NOMEM, "pinned staging of the plan's parameters");
   double* gt = (double*)c->bl_grad.p;
   double* slack = gt + (size_t)q * 2 * nt;
   unsigned long long* gkey = (unsigned long long*)(slack + 2 * q);
   double* S0i = (double*)(gkey + 2 * q);
   double* Vbi = S0i + nS0;
-  double* raw = (double*)c->gb_pts.p;
+  double* raw = (double*)c->gb.pts.p;
   double* ppts = raw + (size_t)QP * kGbProbes;
   double* pgrad = ppts + 2 * (size_t)kGbProbes;
   // ---- what changes with the model: one block, read by the plan's kernels from device memory
@@ -465,21 +465,17 @@ int interp_setup(sbo_ctx* c) {
   g.gkey = gate ? gkey : nullptr;
   // (the previous plan's copy of the block has normally run long ago -- a sweep has synchronised since --, but two model changes in
   // a row must not let the first plan's copy read the second model's block)
-  if (c->ev_bi_params) SBO_HIP(hipEventSynchronize((hipEvent_t)c->ev_bi_params));
-  else {
-    hipEvent_t ev;
-    SBO_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    c->ev_bi_params = ev;
-  }
-  memcpy(c->h_bi_params, &hp, sizeof(hp));
-  const bool defer = gate && c->grad_defer && zs != xs && zs != ys;
+  if (c->ev_bi_params.e) SBO_HIP(hipEventSynchronize(c->ev_bi_params.e));
+  else SBO_HIP(hipEventCreateWithFlags(&c->ev_bi_params.e, hipEventDisableTiming));
+  memcpy(c->h_bi_params.p, &hp, sizeof(hp));
+  const bool defer = gate && c->opt.grad_defer && zs != xs && zs != ys;
   ip.grad_deferred = defer;
   // (no gate at all -- the deferred launch runs both gradient phases on every tile -- where the grid is small enough for the gate's
   // three launches to cost more than the phases they save: A/B r05, config B 0.419 -> 0.398 ms per iteration, config H 0.870 -> 0.920.
   // grad_defer = 2: always; 3: never)
-  const bool nogate = defer && (c->grad_defer == 2 || (c->grad_defer == 1 && (long long)ntx * nty * q <= 4ll * c->n_cu));
+  const bool nogate = defer && (c->opt.grad_defer == 2 || (c->opt.grad_defer == 1 && (long long)ntx * nty * q <= 4ll * c->n_cu));
   if (nogate) { g.gtmax = nullptr; g.gkey = nullptr; }
-  SBO_HIP(hipMemcpyAsync(c->bi_params.p, c->h_bi_params, sizeof(InterpParams), hipMemcpyHostToDevice, xs));
+  SBO_HIP(hipMemcpyAsync(c->bi_params.p, c->h_bi_params.p, sizeof(InterpParams), hipMemcpyHostToDevice, xs));
   if (ys != xs) {
     SBO_HIP(hipEventRecord(c->ev[7], xs));               // (the model's arrays and the block are in place at this point of the main stream)
     SBO_HIP(hipStreamWaitEvent(ys, c->ev[7], 0));
@@ -509,8 +505,8 @@ int interp_setup(sbo_ctx* c) {
   }
   // (deferred tail, r05: the fork of the gate's and the band's side chains rides on this kernel as its stop event -- a record of its own
   // would be a bubble in the chain)
-  if (defer) hipExtLaunchKernelGGL(k_cheb_trunc, dim3((unsigned)QP), dim3(1024), 0, xs, nullptr, c->ev_grad[0], 0, dm, (const double*)Chat, c->cheb_tol, eff);
-  else hipLaunchKernelGGL(k_cheb_trunc, dim3((unsigned)QP), dim3(1024), 0, xs, dm, (const double*)Chat, c->cheb_tol, eff);
+  if (defer) hipExtLaunchKernelGGL(k_cheb_trunc, dim3((unsigned)QP), dim3(1024), 0, xs, nullptr, c->ev_grad[0], 0, dm, (const double*)Chat, c->opt.cheb_tol, eff);
+  else hipLaunchKernelGGL(k_cheb_trunc, dim3((unsigned)QP), dim3(1024), 0, xs, dm, (const double*)Chat, c->opt.cheb_tol, eff);
   hipLaunchKernelGGL(k_cheb_t4f, blocks(g.sT4f, (unsigned)QP), dim3(256), 0, xs, dm, (const double*)Chat, g.sT4f, (double*)c->bl_T4f.p);
   // ... and which tiles of k_bpost can hold the largest gradient component (the gate of K1b's gradient phases, fed from the series.
   // A/B r04: without the gate -- 80 us of plan kernels against 45 us of gradient phases on every tile -- the iteration times are the
@@ -547,14 +543,14 @@ int interp_setup(sbo_ctx* c) {
     hipLaunchKernelGGL(k_gb_probe_series, dim3((unsigned)((kGbProbes + 3) / 4), (unsigned)QP), dim3(256), 0, bs, cs, dP, (const double*)Chat,
                        (const int*)eff, (const double*)dxn0, (const double*)dxn1, raw);
     hipLaunchKernelGGL(k_gb_band_i, dim3(1), dim3(256), 0, bs, dP, (const double*)raw, (const double*)gref_m, (const double*)gref_v,
-                       (const double*)pgrad, reinterpret_cast<const double*>(eff + 4 * QP), (const double*)c->alpha64.p, c->a_ld, (GuardBand*)c->gb.p,
+                       (const double*)pgrad, reinterpret_cast<const double*>(eff + 4 * QP), (const double*)c->alpha64.p, c->a_ld, (GuardBand*)c->gb.buf.p,
                        (GuardBand*)(c->h_back + kGbMirrorOffset));
-    c->gb_mirrored = true;
+    c->gb.mirrored = true;
     if (defer) SBO_HIP(hipEventRecord(c->ev_grad[3], bs));
   }
   SBO_HIP(hipGetLastError());
-  SBO_HIP(hipEventRecord((hipEvent_t)c->ev_bi_params, xs));
-  if (band) c->gb_host_valid = false;
+  SBO_HIP(hipEventRecord(c->ev_bi_params.e, xs));
+  if (band) c->gb.host_valid = false;
   g.eff = eff;
   g.band_ready = band;
   ip.usable = true;

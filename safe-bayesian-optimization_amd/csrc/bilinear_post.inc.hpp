@@ -1101,37 +1101,37 @@ __global__ __launch_bounds__(256) void k_lmax_reduce(const double* __restrict__ 
 // Column path (r05): can this launch deliver the classification as column words?  One constraint, fp64 grid of whole 64 x 128
 // tiles (every workgroup's tile inside the grid), at most 64 segments (Usum is one word per column); the sweep asked for it.
 static bool col_words_ok(const sbo_ctx* c, const PostRequest& req, long long cnt0, long long nlines) {
-  if (!req.col || !c->col_path) return false;
+  if (!req.col || !c->opt.col_path) return false;
   const bool shape = c->mc.q == 2 && c->cs.kind == 1 && c->cs.d == 2 && c->cs.first == 0 && cnt0 % 128 == 0 && nlines % 64 == 0 &&
-                     nlines / 64 <= 64 && nlines >= 64 && cnt0 >= 128 && cnt0 <= 4096 && c->world == 1 && !c->comm_selftest;
+                     nlines / 64 <= 64 && nlines >= 64 && cnt0 >= 128 && cnt0 <= 4096 && c->dist.world == 1 && !c->opt.comm_selftest;
   // (auto: from four tiles per CU and output on -- config H.  Below that the two launches per sweep cost more than the column
   // kernels save: config B, 512 tiles per output, 0.171 ms against 0.162 with the byte masks.  Option col_path = 2: whenever the shape fits.)
   const long long tiles = (cnt0 / 128) * (nlines / 64);
-  return shape && (c->col_path == 2 || tiles >= 4ll * c->n_cu);
+  return shape && (c->opt.col_path == 2 || tiles >= 4ll * c->n_cu);
 }
 static int col_words_prepare(sbo_ctx* c, long long cnt0, long long nlines, ColBits* cb) {
   const size_t words = (size_t)(nlines / 64) * (size_t)cnt0;
   int rc;
-  if ((rc = ensure(c->cbS, 8 * words)) || (rc = ensure(c->cbU, 8 * words)) || (rc = ensure(c->cbM, 8 * words)) || (rc = ensure(c->cbG, 8 * words))) return rc;
-  const bool fresh = c->cbUsum.bytes < 8 * (size_t)cnt0;
-  if ((rc = ensure(c->cbUsum, 8 * (size_t)cnt0))) return rc;
-  if (fresh || c->usum_dirty) SBO_HIP(hipMemsetAsync(c->cbUsum.p, 0, c->cbUsum.bytes, c->stream));
-  c->usum_dirty = true;       // (until the column path's second kernel has cleared it again)
+  if ((rc = ensure(c->col.S, 8 * words)) || (rc = ensure(c->col.U, 8 * words)) || (rc = ensure(c->col.M, 8 * words)) || (rc = ensure(c->col.G, 8 * words))) return rc;
+  const bool fresh = c->col.Usum.bytes < 8 * (size_t)cnt0;
+  if ((rc = ensure(c->col.Usum, 8 * (size_t)cnt0))) return rc;
+  if (fresh || c->col.usum_dirty) SBO_HIP(hipMemsetAsync(c->col.Usum.p, 0, c->col.Usum.bytes, c->stream));
+  c->col.usum_dirty = true;       // (until the column path's second kernel has cleared it again)
   const size_t sbytes = sizeof(unsigned long long) * kColSlotFields * kColSlots;
-  if (c->col_slots.bytes < sbytes) c->slots_clean = false;
-  if ((rc = ensure(c->col_slots, sbytes))) return rc;
-  if (!c->slots_clean) {
+  if (c->col.slots.bytes < sbytes) c->col.slots_clean = false;
+  if ((rc = ensure(c->col.slots, sbytes))) return rc;
+  if (!c->col.slots_clean) {
     unsigned long long init[kColSlotFields * kColSlots];
     for (int f = 0; f < kColSlotFields; ++f)
       for (int k = 0; k < kColSlots; ++k) init[f * kColSlots + k] = col_slot_is_min(f) ? ~0ull : 0ull;
-    SBO_HIP(hipMemcpyAsync(c->col_slots.p, init, sbytes, hipMemcpyHostToDevice, c->stream));
+    SBO_HIP(hipMemcpyAsync(c->col.slots.p, init, sbytes, hipMemcpyHostToDevice, c->stream));
     SBO_HIP(hipStreamSynchronize(c->stream));           // (first use, or after a failed sweep: `init` is on this stack)
   }
-  c->slots_clean = false;     // (until the sweep's finals have reset the block)
-  cb->Sw = (unsigned long long*)c->cbS.p;
-  cb->Uw = (unsigned long long*)c->cbU.p;
-  cb->Usum = (unsigned long long*)c->cbUsum.p;
-  cb->slots = (unsigned long long*)c->col_slots.p;
+  c->col.slots_clean = false;     // (until the sweep's finals have reset the block)
+  cb->Sw = (unsigned long long*)c->col.S.p;
+  cb->Uw = (unsigned long long*)c->col.U.p;
+  cb->Usum = (unsigned long long*)c->col.Usum.p;
+  cb->slots = (unsigned long long*)c->col.slots.p;
   return SBO_OK;
 }
 
@@ -1223,7 +1223,7 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
     }
     // r07: lean 2 -- the objective's launch over the tiles with a safe candidate, and, once the enclosures decide skips, the
     // constraint's over the tiles that need a workgroup (k_bl_sched_tiles1 and on).  [class bytes][list 1][list 2]
-    if (c->k1_sched && req.col_lean >= 2) {
+    if (c->opt.k1_sched && req.col_lean >= 2) {
       if ((rc = ensure(c->bl_sched, ((ntiles + 15) & ~(size_t)15) + 2 * sizeof(unsigned int) * (ntiles + 1)))) return rc;
       sched_cls = (uint8_t*)c->bl_sched.p;
       sched_l1 = (unsigned int*)(sched_cls + ((ntiles + 15) & ~(size_t)15));
@@ -1234,7 +1234,7 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
   if (interp) stage1();
   if (defer && g.band_ready) SBO_HIP(hipStreamWaitEvent(c->stream, c->ev_grad[3], 0));     // (the band: written on Y beside stage 1)
   // (the fused classification counts its sign tests inside the plan's guard band)
-  const GuardBand* gb_fused = (c->guard_band && !c->is_shadow && g.band_ready && c->gb.p) ? (const GuardBand*)c->gb.p : nullptr;
+  const GuardBand* gb_fused = (c->opt.guard_band && !c->is_shadow && g.band_ready && c->gb.buf.p) ? (const GuardBand*)c->gb.buf.p : nullptr;
   for (auto k : {k_bpost<1, 0>, k_bpost<1, 1>, k_bpost<1, 2>})
     SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   double* const lrows = (double*)c->bl_lpart.p;
@@ -1276,7 +1276,7 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
     px.tgy = (int)gy;
     const dim3 grid = px.tlist ? dim3(gx * gy) : dim3(gx, gy, (unsigned)(colw ? 1 : q));
     hipExtLaunchKernelGGL(kpost, grid, dim3(256), lds, c->stream, nullptr,
-                          (req.lmax_defer && last) ? c->ev[1] : ((colw && part == 0) ? c->ev_col[0] : nullptr), 0,
+                          (req.lmax_defer && last) ? c->ev[1] : ((colw && part == 0) ? c->col.ev[0] : nullptr), 0,
                           mc, cs, g.BtA, g.sBtA, g.P0f, g.sP0f, g.VA, g.sVA, g.SBf, g.sSBf, g.KB0, g.KS0, g.KBm, g.KSm, g.KBm2, g.nrb, g.ncs0,
                           nlines, (double*)c->mean.p, (double*)c->var.p, defer ? lrows + (size_t)rows_out * q : lrows,
                           (const double*)c->bl_small.p /* xn0 */, fuse ? (uint8_t*)(q > 2 ? c->fuseS.p : c->maskS.p) : (uint8_t*)nullptr,
@@ -1300,10 +1300,10 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
     out.lmax_per_out = (int)rows_out;
   } else {
     hipExtLaunchKernelGGL(k_lmax_reduce, dim3((unsigned)q), dim3(256), 0, c->stream, nullptr, c->ev[1], 0, (const double*)lrows,
-                          (int)rows_out, (unsigned long long*)c->Lmax.p);
+                          (int)rows_out, c->Lmax);
   }
   out.stop_attached = true;
-  c->gb_active = c->guard_band && !c->is_shadow && g.band_ready;     // (the band came with the plan)
+  c->gb.active = c->opt.guard_band && !c->is_shadow && g.band_ready;     // (the band came with the plan)
   const double tiles2 = (double)g.nrb * g.ncs0;
   if (interp) {
     // flops issued: stage 1 of four coefficient sets per output + four full phases of stage 2 (an upper bound: the counts the kernels

@@ -23,30 +23,30 @@ struct CommScope {
   int slot = -1;
   std::chrono::steady_clock::time_point t0;
   CommScope(sbo_ctx* c_, size_t bytes) : c(c_) {
-    c->comm_bytes += (long long)bytes;
-    ++c->comm_calls;
+    c->dist.comm_bytes += (long long)bytes;
+    ++c->dist.comm_calls;
     t0 = std::chrono::steady_clock::now();
-    if (c->comm_events && c->comm && c->comm_nev + 2 <= 16) {
-      slot = c->comm_nev;
-      c->comm_nev += 2;
+    if (c->opt.comm_events && c->dist.comm && c->dist.comm_nev + 2 <= 16) {
+      slot = c->dist.comm_nev;
+      c->dist.comm_nev += 2;
       for (int k = 0; k < 2; ++k)
-        if (!c->comm_ev[slot + k] && hipEventCreate(&c->comm_ev[slot + k]) != hipSuccess) slot = -1;
-      if (slot >= 0) (void)hipEventRecord(c->comm_ev[slot], c->stream);
+        if (!c->dist.comm_ev[slot + k].e && hipEventCreate(&c->dist.comm_ev[slot + k].e) != hipSuccess) slot = -1;
+      if (slot >= 0) (void)hipEventRecord(c->dist.comm_ev[slot].e, c->stream);
     }
   }
   ~CommScope() {
-    if (slot >= 0) (void)hipEventRecord(c->comm_ev[slot + 1], c->stream);
-    if (!c->comm) c->comm_host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (slot >= 0) (void)hipEventRecord(c->dist.comm_ev[slot + 1].e, c->stream);
+    if (!c->dist.comm) c->dist.comm_host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
 };
 
 // host-staged collective for the rehearsal transport
 static int relay_reduce(sbo_ctx* c, void* dev, size_t count, int elem, int op) {
-  if (!c->relay_allreduce) return fail(SBO_E_COMM, "no transport: neither an RCCL communicator nor relay callbacks are installed");
+  if (!c->dist.relay_allreduce) return fail(SBO_E_COMM, "no transport: neither an RCCL communicator nor relay callbacks are installed");
   std::vector<unsigned char> h(count * 8);
   SBO_HIP(hipMemcpyAsync(h.data(), dev, h.size(), hipMemcpyDeviceToHost, c->stream));
   SBO_HIP(hipStreamSynchronize(c->stream));
-  if (c->relay_allreduce(c->relay_user, h.data(), (int64_t)count, elem, op) != 0)
+  if (c->dist.relay_allreduce(c->dist.relay_user, h.data(), (int64_t)count, elem, op) != 0)
     return fail(SBO_E_COMM, "relay all-reduce callback failed");
   SBO_HIP(hipMemcpyAsync(dev, h.data(), h.size(), hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipStreamSynchronize(c->stream));
@@ -57,39 +57,39 @@ static int relay_reduce(sbo_ctx* c, void* dev, size_t count, int elem, int op) {
 int comm_allreduce_max_u64(sbo_ctx* c, unsigned long long* dev, int count) {
   if (!multi_rank(c)) return SBO_OK;
   CommScope cs_(c, sizeof(unsigned long long) * (size_t)count);
-  if (!c->comm) return relay_reduce(c, dev, count, 0, 1);
-  SBO_NCCL(ncclAllReduce(dev, dev, count, ncclUint64, ncclMax, (ncclComm_t)c->comm, c->stream));
+  if (!c->dist.comm) return relay_reduce(c, dev, count, 0, 1);
+  SBO_NCCL(ncclAllReduce(dev, dev, count, ncclUint64, ncclMax, (ncclComm_t)c->dist.comm, c->stream));
   return SBO_OK;
 }
 int comm_allreduce_min_u64(sbo_ctx* c, unsigned long long* dev, int count) {
   if (!multi_rank(c)) return SBO_OK;
   CommScope cs_(c, sizeof(unsigned long long) * (size_t)count);
-  if (!c->comm) return relay_reduce(c, dev, count, 0, 2);
-  SBO_NCCL(ncclAllReduce(dev, dev, count, ncclUint64, ncclMin, (ncclComm_t)c->comm, c->stream));
+  if (!c->dist.comm) return relay_reduce(c, dev, count, 0, 2);
+  SBO_NCCL(ncclAllReduce(dev, dev, count, ncclUint64, ncclMin, (ncclComm_t)c->dist.comm, c->stream));
   return SBO_OK;
 }
 int comm_allreduce_sum_f64(sbo_ctx* c, double* dev, int count) {
   if (!multi_rank(c)) return SBO_OK;
   CommScope cs_(c, sizeof(double) * (size_t)count);
-  if (!c->comm) return relay_reduce(c, dev, count, 1, 0);
-  SBO_NCCL(ncclAllReduce(dev, dev, count, ncclDouble, ncclSum, (ncclComm_t)c->comm, c->stream));
+  if (!c->dist.comm) return relay_reduce(c, dev, count, 1, 0);
+  SBO_NCCL(ncclAllReduce(dev, dev, count, ncclDouble, ncclSum, (ncclComm_t)c->dist.comm, c->stream));
   return SBO_OK;
 }
 int comm_allgather_bytes(sbo_ctx* c, const void* send, void* recv, size_t bytes_per_rank) {
   if (!multi_rank(c)) return SBO_OK;
   CommScope cs_(c, bytes_per_rank);
-  if (!c->comm) {
-    if (!c->relay_allgather) return fail(SBO_E_COMM, "no transport: neither an RCCL communicator nor relay callbacks are installed");
-    std::vector<unsigned char> hs(bytes_per_rank), hr(bytes_per_rank * c->world);
+  if (!c->dist.comm) {
+    if (!c->dist.relay_allgather) return fail(SBO_E_COMM, "no transport: neither an RCCL communicator nor relay callbacks are installed");
+    std::vector<unsigned char> hs(bytes_per_rank), hr(bytes_per_rank * c->dist.world);
     SBO_HIP(hipMemcpyAsync(hs.data(), send, hs.size(), hipMemcpyDeviceToHost, c->stream));
     SBO_HIP(hipStreamSynchronize(c->stream));
-    if (c->relay_allgather(c->relay_user, hs.data(), hr.data(), (int64_t)bytes_per_rank) != 0)
+    if (c->dist.relay_allgather(c->dist.relay_user, hs.data(), hr.data(), (int64_t)bytes_per_rank) != 0)
       return fail(SBO_E_COMM, "relay all-gather callback failed");
     SBO_HIP(hipMemcpyAsync(recv, hr.data(), hr.size(), hipMemcpyHostToDevice, c->stream));
     SBO_HIP(hipStreamSynchronize(c->stream));
     return SBO_OK;
   }
-  SBO_NCCL(ncclAllGather(send, recv, bytes_per_rank, ncclUint8, (ncclComm_t)c->comm, c->stream));
+  SBO_NCCL(ncclAllGather(send, recv, bytes_per_rank, ncclUint8, (ncclComm_t)c->dist.comm, c->stream));
   return SBO_OK;
 }
 }  // namespace sbo
@@ -111,12 +111,12 @@ int sbo_comm_unique_id(void* id_out) {
 int sbo_comm_init(sbo_ctx* c, int world_size, int rank, const void* id) {
   if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
   if (world_size < 1 || rank < 0 || rank >= world_size) return fail(SBO_E_INVALID, "bad world_size / rank");
-  if (c->comm) return fail(SBO_E_INVALID, "communicator already initialised");
+  if (c->dist.comm) return fail(SBO_E_INVALID, "communicator already initialised");
   // A one-rank world needs no communicator: the collectives are identities and are skipped.  With an id it still gets a
   // real one (option "comm_selftest" then sends C1 / C2 / C3 through RCCL anyway: the one-GPU test of the RCCL calls).
   if (world_size == 1 && !id) {
-    c->world = 1;
-    c->rank = 0;
+    c->dist.world = 1;
+    c->dist.rank = 0;
     return SBO_OK;
   }
   if (!id) return fail(SBO_E_INVALID, "id is NULL");
@@ -132,9 +132,9 @@ int sbo_comm_init(sbo_ctx* c, int world_size, int rank, const void* id) {
   ncclComm_t comm;
   SBO_NCCL(ncclCommInitRank(&comm, world_size, uid, rank));
   // world / rank change only once the communicator exists: a failed init leaves the context single-rank and usable
-  c->comm = comm;
-  c->world = world_size;
-  c->rank = rank;
+  c->dist.comm = comm;
+  c->dist.world = world_size;
+  c->dist.rank = rank;
   return SBO_OK;
 }
 
@@ -143,15 +143,15 @@ int sbo_comm_init_relay(sbo_ctx* c, int world_size, int rank, sbo_relay_allreduc
   if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
   if (world_size < 1 || rank < 0 || rank >= world_size) return fail(SBO_E_INVALID, "bad world_size / rank");
   if (world_size > 1 && (!allreduce || !allgather)) return fail(SBO_E_INVALID, "relay callbacks are NULL");
-  if (c->comm) {   // switching transports: drop the RCCL communicator
-    ncclCommDestroy((ncclComm_t)c->comm);
-    c->comm = nullptr;
+  if (c->dist.comm) {   // switching transports: drop the RCCL communicator
+    ncclCommDestroy((ncclComm_t)c->dist.comm);
+    c->dist.comm = nullptr;
   }
-  c->world = world_size;
-  c->rank = rank;
-  c->relay_allreduce = allreduce;
-  c->relay_allgather = allgather;
-  c->relay_user = user;
+  c->dist.world = world_size;
+  c->dist.rank = rank;
+  c->dist.relay_allreduce = allreduce;
+  c->dist.relay_allgather = allgather;
+  c->dist.relay_user = user;
   return SBO_OK;
 }
 
@@ -166,12 +166,9 @@ int sbo_comm_barrier(sbo_ctx* c) {
 }
 
 int sbo_comm_destroy_internal(sbo_ctx* c) {
-  if (c)
-    for (auto& ev : c->comm_ev)
-      if (ev) { (void)hipEventDestroy(ev); ev = nullptr; }
-  if (c && c->comm) {
-    ncclCommDestroy((ncclComm_t)c->comm);
-    c->comm = nullptr;
+  if (c && c->dist.comm) {
+    ncclCommDestroy((ncclComm_t)c->dist.comm);
+    c->dist.comm = nullptr;
   }
   return SBO_OK;
 }

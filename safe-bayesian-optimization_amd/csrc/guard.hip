@@ -335,7 +335,7 @@ __global__ __launch_bounds__(256) void k_gb_band(const ModelConst mc, const doub
 // ---- host ----------------------------------------------------------------------------------------------------------------
 // can the reference formula run with the caller's matrix (no factor needed)?
 static bool ref_direct(const sbo_ctx* c) {
-  return c->mc.factor == SBO_FACTOR_INVK && c->chol_async && c->invk_w_valid && c->invk_plain != nullptr && c->dtype == SBO_F64 && !c->is_shadow &&
+  return c->mc.factor == SBO_FACTOR_INVK && c->opt.chol_async && c->invk_w_valid && c->invk_plain != nullptr && c->dtype == SBO_F64 && !c->is_shadow &&
          c->mc.npad <= kGuardRefMaxNpad;
 }
 
@@ -352,7 +352,7 @@ static int launch_ref(sbo_ctx* c, hipStream_t st, const double* pts, long long N
   const int ccols = ((nblk + chunks - 1) / chunks) * 64;
   chunks = (mc.n + ccols - 1) / ccols;
   int rc;
-  DevBuf& pb = part_buf ? *part_buf : c->gb_part;
+  DevBuf& pb = part_buf ? *part_buf : c->gb.part;
   if ((rc = ensure(pb, sizeof(double) * 2 * (size_t)chunks * q * (size_t)N))) return rc;
   const size_t lds = sizeof(double) * ((size_t)kRefPer * mc.npad + 256 * kRefPer);
   auto kern = k_ref_list<D>;
@@ -394,9 +394,9 @@ int guard_exact_grad_list(sbo_ctx* c, const double* pts, long long N, double* gr
 // a band the host knows (K1t's probe), or all-zero (nullptr arguments)
 int guard_band_host(sbo_ctx* c, const double* dm, const double* dv, const double* rl, const double* parts) {
   int rc;
-  if ((rc = ensure(c->gb, sizeof(GuardBand)))) return rc;
-  c->gb_host_valid = false;
-  c->gb_mirrored = false;
+  if ((rc = ensure(c->gb.buf, sizeof(GuardBand)))) return rc;
+  c->gb.host_valid = false;
+  c->gb.mirrored = false;
   GuardBand hb;
   memset(&hb, 0, sizeof(hb));
   for (int o = 0; o < c->mc.q && dm; ++o) {
@@ -404,12 +404,12 @@ int guard_band_host(sbo_ctx* c, const double* dm, const double* dv, const double
     if (parts) { hb.an_m[o] = parts[o]; hb.an_v[o] = parts[kMaxQ + o]; hb.pr_m[o] = parts[2 * kMaxQ + o]; hb.pr_v[o] = parts[3 * kMaxQ + o]; }
   }
   // (pageable source: the runtime stages it before the call returns)
-  SBO_HIP(hipMemcpyAsync(c->gb.p, &hb, sizeof(hb), hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemcpyAsync(c->gb.buf.p, &hb, sizeof(hb), hipMemcpyHostToDevice, c->stream));
   for (int o = 0; o < SBO_MAX_Q; ++o) {
-    c->gb_host[o] = hb.dm[o]; c->gb_host[SBO_MAX_Q + o] = hb.dv[o]; c->gb_host[2 * SBO_MAX_Q + o] = hb.rl[o];
-    c->gb_host[3 * SBO_MAX_Q + o] = hb.an_m[o]; c->gb_host[4 * SBO_MAX_Q + o] = hb.an_v[o]; c->gb_host[5 * SBO_MAX_Q + o] = hb.pr_m[o]; c->gb_host[6 * SBO_MAX_Q + o] = hb.pr_v[o];
+    c->gb.host[o] = hb.dm[o]; c->gb.host[SBO_MAX_Q + o] = hb.dv[o]; c->gb.host[2 * SBO_MAX_Q + o] = hb.rl[o];
+    c->gb.host[3 * SBO_MAX_Q + o] = hb.an_m[o]; c->gb.host[4 * SBO_MAX_Q + o] = hb.an_v[o]; c->gb.host[5 * SBO_MAX_Q + o] = hb.pr_m[o]; c->gb.host[6 * SBO_MAX_Q + o] = hb.pr_v[o];
   }
-  c->gb_host_valid = true;
+  c->gb.host_valid = true;
   return SBO_OK;
 }
 
@@ -421,11 +421,11 @@ int guard_probe_reference(sbo_ctx* c, hipStream_t side, double** ref_m, double**
   const int q = c->mc.q;
   const long long nlines = c->cs.n_local / c->cs.count[0];
   int rc;
-  if ((rc = ensure(c->gb, sizeof(GuardBand)))) return rc;
-  c->gb_host_valid = false;
+  if ((rc = ensure(c->gb.buf, sizeof(GuardBand)))) return rc;
+  c->gb.host_valid = false;
   // (ref_m | ref_v | the plan's own values pm | pv | the probe list [P][2] | exact gradient components [q][2][P])
-  if ((rc = ensure(c->gb_probe, sizeof(double) * (6 * (size_t)q + 2) * kGbProbes))) return rc;
-  *ref_m = (double*)c->gb_probe.p;
+  if ((rc = ensure(c->gb.probe, sizeof(double) * (6 * (size_t)q + 2) * kGbProbes))) return rc;
+  *ref_m = (double*)c->gb.probe.p;
   *ref_v = *ref_m + (size_t)q * kGbProbes;
   if (ref_direct(c)) return launch_ref<2>(c, side, nullptr, kGbProbes, nlines, *ref_m, *ref_v, mcp);
   // (library Cholesky, or a caller's invK without chol_async: the factor is there, the generic kernel takes the probe list --
@@ -444,9 +444,9 @@ int guard_probe_gradients(sbo_ctx* c, hipStream_t st, double* ppts, double* grad
   return SBO_OK;
 }
 int guard_band_from_probes(sbo_ctx* c, const double* pm, const double* pv, const double* ref_m, const double* ref_v, const double* tail, const GbAnalytic& an) {
-  hipLaunchKernelGGL(k_gb_band, dim3(1), dim3(256), 0, c->stream, c->mc, pm, pv, ref_m, ref_v, tail, an, (GuardBand*)c->gb.p,
+  hipLaunchKernelGGL(k_gb_band, dim3(1), dim3(256), 0, c->stream, c->mc, pm, pv, ref_m, ref_v, tail, an, (GuardBand*)c->gb.buf.p,
                      (GuardBand*)(c->h_back + kGbMirrorOffset));
-  c->gb_mirrored = true;
+  c->gb.mirrored = true;
   SBO_HIP(hipGetLastError());
   return SBO_OK;
 }
@@ -533,35 +533,35 @@ __global__ __launch_bounds__(256) void k_audit_compare(int P, int q, int o_first
 }
 
 void guard_audit_harvest(sbo_ctx* c, bool wait) {
-  if (!c->audit_pending) return;
-  if (wait) (void)hipEventSynchronize(c->ev_audit[1]);
-  else if (hipEventQuery(c->ev_audit[1]) != hipSuccess) return;
+  if (!c->audit.pending) return;
+  if (wait) (void)hipEventSynchronize(c->audit.ev[1]);
+  else if (hipEventQuery(c->audit.ev[1]) != hipSuccess) return;
   const unsigned long long* hc = (const unsigned long long*)(c->h_back + 7168);
-  c->audit_violations += (long long)hc[0];
-  c->audit_samples += (long long)hc[1];
-  c->audit_skipped += (long long)hc[3];
+  c->audit.violations += (long long)hc[0];
+  c->audit.samples += (long long)hc[1];
+  c->audit.skipped += (long long)hc[3];
   double w;
   memcpy(&w, &hc[2], 8);
-  c->audit_worst = std::max(c->audit_worst, w);
-  c->audit_pending = false;
+  c->audit.worst = std::max(c->audit.worst, w);
+  c->audit.pending = false;
 }
 
 int guard_audit_enqueue(sbo_ctx* c, const PostOutcome& out) {
   const int first_output = out.col_lean ? 1 : 0;      // (a lean column-path launch left the objective's values incomplete)
-  if (c->guard_audit <= 0 || !c->gb_active || !c->guard_band || !c->gb.p || c->is_shadow || !(c->last_k1 == 4 || c->last_k1 == 6) || !ref_direct(c) || c->mc.dpad != 2 ||
+  if (c->opt.guard_audit <= 0 || !c->gb.active || !c->opt.guard_band || !c->gb.buf.p || c->is_shadow || !(c->last_k1 == 4 || c->last_k1 == 6) || !ref_direct(c) || c->mc.dpad != 2 ||
       c->cs.n_local <= 0 || !c->stream_audit || first_output >= c->mc.q)
     return SBO_OK;
   // (the audit shares the card with the sweep it follows -- ~35 us of a config-H sweep's set phase for 1024 samples at n = 512 --, so
   // one sweep in guard_audit_every carries one)
-  if (c->audit_tick++ % std::max(1, c->guard_audit_every)) return SBO_OK;
+  if (c->audit.tick++ % std::max(1, c->opt.guard_audit_every)) return SBO_OK;
   guard_audit_harvest(c, false);
-  if (c->audit_pending) return SBO_OK;                 // (the previous audit is still running: this sweep's is skipped, none queues up)
-  const int P = c->guard_audit, q = c->mc.q;
+  if (c->audit.pending) return SBO_OK;                 // (the previous audit is still running: this sweep's is skipped, none queues up)
+  const int P = c->opt.guard_audit, q = c->mc.q;
   int rc;
-  if ((rc = ensure(c->audit_pts, sizeof(double) * (size_t)P * 2)) || (rc = ensure(c->audit_val, sizeof(double) * (size_t)P * (q * 4 + 5) + sizeof(GuardBand))) ||
-      (rc = ensure(c->audit_cnt, 64)))
+  if ((rc = ensure(c->audit.pts, sizeof(double) * (size_t)P * 2)) || (rc = ensure(c->audit.val, sizeof(double) * (size_t)P * (q * 4 + 5) + sizeof(GuardBand))) ||
+      (rc = ensure(c->audit.cnt, 64)))
     return rc;
-  double* apx = (double*)c->audit_val.p;
+  double* apx = (double*)c->audit.val.p;
   double* ref_m = apx + (size_t)2 * q * P;
   double* ref_v = ref_m + (size_t)q * P;
   double* aenc = ref_v + (size_t)q * P;
@@ -580,22 +580,22 @@ int guard_audit_enqueue(sbo_ctx* c, const PostOutcome& out) {
   // the sample is taken behind the posterior (its stop event ev[1] -- no record of its own on the main stream: that would be a bubble
   // in the sweep) ...
   SBO_HIP(hipStreamWaitEvent(st, c->ev[1], 0));
-  SBO_HIP(hipMemsetAsync(c->audit_cnt.p, 0, 64, st));
+  SBO_HIP(hipMemsetAsync(c->audit.cnt.p, 0, 64, st));
   const unsigned long long stride = 1000003ull;
-  hipLaunchKernelGGL(k_audit_pick<2>, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, c->cs, P, c->audit_offset, stride, q, (const double*)c->mean.p,
-                     (const double*)c->var.p, (double*)c->audit_pts.p, apx, encl ? (const double*)c->bl_encl.p : (const double*)nullptr,
+  hipLaunchKernelGGL(k_audit_pick<2>, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, c->cs, P, c->audit.offset, stride, q, (const double*)c->mean.p,
+                     (const double*)c->var.p, (double*)c->audit.pts.p, apx, encl ? (const double*)c->bl_encl.p : (const double*)nullptr,
                      skips ? (const uint8_t*)c->bl_encl.p + sizeof(double) * 4 * 128 * ntiles : (const uint8_t*)nullptr, (int)(cnt0 / 128), aenc,
-                     (const GuardBand*)c->gb.p, gb_snap);
-  c->audit_offset += (unsigned long long)P * stride + 17ull;
+                     (const GuardBand*)c->gb.buf.p, gb_snap);
+  c->audit.offset += (unsigned long long)P * stride + 17ull;
   // ... and before anything overwrites mean / var or the band again (the next posterior launch waits for this event)
-  SBO_HIP(hipEventRecord(c->ev_audit[0], st));
-  if ((rc = launch_ref<2>(c, st, (const double*)c->audit_pts.p, P, 0, ref_m, ref_v, nullptr, &c->audit_part))) return rc;
+  SBO_HIP(hipEventRecord(c->audit.ev[0], st));
+  if ((rc = launch_ref<2>(c, st, (const double*)c->audit.pts.p, P, 0, ref_m, ref_v, nullptr, &c->audit.part))) return rc;
   hipLaunchKernelGGL(k_audit_compare, dim3(8), dim3(256), 0, st, P, q, first_output, (const double*)apx, (const double*)ref_m, (const double*)ref_v,
-                     (const GuardBand*)gb_snap, (unsigned long long*)c->audit_cnt.p, c->audit_scale, encl ? (const double*)aenc : (const double*)nullptr);
-  SBO_HIP(hipMemcpyAsync(c->h_back + 7168, c->audit_cnt.p, 32, hipMemcpyDeviceToHost, st));
-  SBO_HIP(hipEventRecord(c->ev_audit[1], st));
+                     (const GuardBand*)gb_snap, (unsigned long long*)c->audit.cnt.p, c->opt.audit_scale, encl ? (const double*)aenc : (const double*)nullptr);
+  SBO_HIP(hipMemcpyAsync(c->h_back + 7168, c->audit.cnt.p, 32, hipMemcpyDeviceToHost, st));
+  SBO_HIP(hipEventRecord(c->audit.ev[1], st));
   SBO_HIP(hipGetLastError());
-  c->audit_pending = true;
+  c->audit.pending = true;
   return SBO_OK;
 }
 

@@ -41,9 +41,39 @@ struct CandSpec {
   long long count[kMaxD];
 };
 
+// The four kinds of device resource a context holds, each freed by its holder's destructor and nowhere else.  Move-only (a copy
+// would free twice); what merely points into another's memory is a plain pointer, not one of these.
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(DevBuf&& o) noexcept {      // (the one move: sbo_model_append swaps a grown factor in)
+    if (this != &o) { reset(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  void reset() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+};
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(const Event&) = delete;
+  ~Event() { if (e) (void)hipEventDestroy(e); }
+};
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  ~Stream() { if (s) (void)hipStreamDestroy(s); }
+};
+struct Pinned {
+  void* p = nullptr;
+  size_t bytes = 0;
+  Pinned() = default;
+  Pinned(const Pinned&) = delete;
+  ~Pinned() { reset(); }
+  void reset() { if (p) (void)hipHostFree(p); p = nullptr; bytes = 0; }
 };
 
 // Spatial index of an explicit candidate list (sets_index.inc.hpp): Morton order of the points, built at the first sweep that
@@ -59,7 +89,7 @@ struct ListIndex {
   DevBuf keys, vals, hist;       // radix sort: keys / values twice (ping-pong), per-tile digit counts
   DevBuf xs;                     // sorted coordinates, fp64 [n][d]
   DevBuf stats;                  // walk counters of the running sweep: leaf pairs, nodes skipped
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  Event ev0, ev1;
 };
 
 // Column-word form of the masks of a 2-D grid (r05): word [s][i] holds the bits of column i (axis 0) for the 64 rows
@@ -154,7 +184,7 @@ struct PostRequest {
 // What the launch reports back (filled by the launcher: all zero unless a GEMM posterior ran)
 struct PostOutcome {
   bool col_active = false;     // the launch delivered the classification as column words (col_set_phase runs)
-  bool col_forked = false;     // ... and the constraint's launch carried ev_col[0]
+  bool col_forked = false;     // ... and the constraint's launch carried ColPath::ev[0]
   int col_lean = 0;            // ... at this lean level (non-zero: the objective's mean / var are incomplete)
   int fuse_rows = 0;           // > 0: the kernel wrote S / U and that many partial rows at the head of cpart
   bool lmax_pending = false;   // the Lipschitz partials (lmax_per_out rows per output in bl_lpart) wait for the sweep to merge them
@@ -173,9 +203,147 @@ struct InterpPlan {
                                               // gradient phases, a launch of those alone follows the gate there (launch_posterior_gemm)
 };
 
+// K1t (tensor.hip): fp64 grids of three / four axes by Chebyshev interpolation from exact node values.  The plan keys itself on
+// (model, first, nlocal, count, lo, hi): a new model or new candidates need not drop it, an option it is built with must
+struct TensorPlan {
+  DevBuf pts, vals, work, W0t, W1t, probe, scr;
+  DevBuf gather;     // ranks > 1: this rank's slab of the node tensors | every rank's (all-gather)
+  DevBuf W[SBO_MAX_D];
+  size_t work_half = 0;
+  double flops = 0.0;           // multiply-add flops of the last interpolation pass
+  bool valid = false, usable = false;     // plan decided for (model, grid below) / it passed its accuracy probe
+  unsigned long long model = 0;
+  long long first = 0, nlocal = 0, count[4] = {0, 0, 0, 0};
+  double lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
+  int level[4] = {0, 0, 0, 0};
+  int dn[4] = {0, 0, 0, 0};     // node counts of the plan in use
+  DevBuf tail;             // [2 q][d] keys of the node tensors' coefficient tails per axis (k_t_fiber_tail)
+  double band[7 * SBO_MAX_Q] = {0};   // the plan's guard band (dm | dv | rl | analytic dm | dv | probe dm | dv per output)
+  int bump = 0;                 // ladder steps added to the first guess on this grid (a previous model's plan needed its second attempt)
+  bool lean_probe = false;      // the plan's probe left out output 0's gradient (decided by a lean sweep): a full sweep probes it again
+  void invalidate() { valid = false; }
+};
+
+// Guard band of the approximating posteriors K1b / K1t (device_common.hpp: GuardBand; guard.hip), as far as it belongs to the
+// resident posterior
+struct ResidentBand {
+  bool active = false;          // the posterior in mean / var came from an approximating kernel; `buf` holds (or will hold, in stream order) its band
+                                // (a fact about the resident arrays, kept between calls; what a running set phase makes of it: SetView in sets.hip)
+  DevBuf buf;                   // GuardBand of the resident posterior
+  long long first = 0;          // decisions the first pass of the running sweep left open
+  bool mirrored = false;        // the plan's band kernel also wrote the block to pinned host memory (h_back + kGbMirrorOffset): valid once a sweep has synchronised
+  bool host_valid = false;      // `host` mirrors `buf` (read back on demand by sbo_profile_get; dropped when a plan writes the block)
+  double host[7 * SBO_MAX_Q] = {0};   // dm | dv | rl | analytic dm | dv | largest probe deviation dm | dv
+  DevBuf pts, vals;             // re-evaluation: coordinates and exact values of the listed candidates
+  DevBuf part;                  // k_ref_list: per-column-chunk partial sums
+  DevBuf probe;                 // K1b: probe indices / coordinates / reference values of the running plan
+  unsigned long long plan_model = 0;   // K1b: the model whose band `buf` holds (0: none)
+  long long plan_first = -1, plan_n = -1;
+};
+
+// Standing audit of the band (r05): behind every K1b / K1i posterior launch of a sweep a rotating sample of the candidates is
+// re-evaluated with the reference formula on stream2 -- off the critical path -- and compared with what the posterior kernel
+// stored: a deviation beyond the band is a VIOLATION of the claim the sweeps' exactness rests on (counted, reported in sbo_profile)
+struct Audit {
+  long long tick = 0;
+  DevBuf pts, val, part, cnt;
+  hipEvent_t ev[2]{};           // the sample has been taken (mean / var may be overwritten) / the audit has finished
+  bool pending = false;
+  unsigned long long offset = 0;
+  long long samples = 0, violations = 0;
+  long long skipped = 0;        // of samples: constraint samples on tiles a lean sweep left unevaluated (checked against the enclosure)
+  double worst = 0.0;           // largest deviation seen, in units of the band
+};
+
+// Column path (r05, sets_colpath.inc.hpp): a one-rank SafeOpt sweep of a one-constraint model on a 2-D grid of whole
+// 64 x 128 tiles asks (PostRequest::col) for the classification as column words; the GEMM posterior then runs one launch per
+// output -- constraint first: S / U words, |S| per tile; objective second: u* and min var_0 over S from its own epilogue --
+// and says so (PostOutcome::col_active).  The words stay resident for sbo_masks_get (masks_bits: expanded to bytes on demand).
+struct ColPath {
+  bool slots_clean = false;// the slot block holds its neutral elements (the finals of the last column sweep reset it)
+  bool usum_dirty = false; // Usum holds bits of an earlier launch (cleared by the column path's second kernel; by a memset after a failure)
+  DevBuf S, U, M, G, Usum;           // column words [H / 64][W]; Usum [W]
+  DevBuf slots;                      // ColBits::slots
+  DevBuf img, bmin;                  // column distance image u16 [H][W], block minima u16 [H][W / 32]
+  DevBuf cimg, cbmin;                // the same on the 8 x 8 cells
+  long long ckey = 0;                // the grid the padding of cbmin was laid out for
+  DevBuf fin;                        // the objective's scalars, the finals' tickets and intermediate rows (4 KB)
+  hipEvent_t ev[3]{};      // fork (the constraint's posterior launch has finished) / join (the expander chain on stream3 has) /
+                           // the chain's first kernel, which clears the M words, has finished (carried by k_col_a: the minimiser's M part waits for it)
+  bool masks_bits = false;     // the masks of the last sweep live in the column words (byte buffers stale)
+  bool G_bytes = false;        // ... except G, which the exhaustive recheck finished in byte form
+};
+
+// Several ranks: the communicator or the rehearsal transport, the buffers of the collectives, the sharding of the grid
+struct MultiRank {
+  void* comm = nullptr;  // ncclComm_t
+  int world = 1, rank = 0;
+  // rehearsal transport (tests on a 1-GPU box): collectives staged through host callbacks instead of RCCL
+  sbo_relay_allreduce_fn relay_allreduce = nullptr;
+  sbo_relay_allgather_fn relay_allgather = nullptr;
+  void* relay_user = nullptr;
+  long long comm_bytes = 0;   // collectives of the running sweep: bytes handed over (send side), calls, and -- option comm_events --
+  int comm_calls = 0;         // an event pair per call (comm_ev, created on first use) whose elapsed times sbo_profile.comm_ms sums
+  int comm_nev = 0;
+  double comm_host_ms = 0.0;  // (relay transport: wall clock of the staged collectives)
+  Event comm_ev[16];
+  DevBuf Wfull;   // GoOSE: source weights of the whole grid (all-gathered), T [grid_total]
+  DevBuf Uwin;    // U mask of the expander transform's window (own planes + halo), uint8
+  long long uwin_first = 0, uwin_n = 0;   // flat range the window covers
+  DevBuf ubits;                      // own U bits (gather_words words) followed by every rank's (all-gathered)
+  long long gather_words = 0;        // words per rank in ubits
+  DevBuf gather;  // all-gather receive buffer [world][max_local]
+  DevBuf xch;     // small exchange buffers (C1 keys, C3 rows)
+  DevBuf shard_first;  // device copy of first_of[]
+  long long grid_total = 0; // candidates in the whole grid (all ranks)
+  bool sharded = false;     // candidates were set with the canonical plane sharding
+  std::vector<long long> first_of;   // [world + 1] flat offsets of the rank shards
+  unsigned long long* h_c1 = nullptr;     // pinned host copy of the C1 keys (global u*, L, radius) of the running sweep
+  bool c1_pending = false;                // the read-back of h_c1 has been enqueued (event ev[5]) but not yet waited for
+  // Speculative halo (ranks > 1, option halo_spec): the host sizes the transform window of constraint c from the keys of the
+  // PREVIOUS sweep (with a margin) instead of waiting for this sweep's; the device checks the guess against the keys it
+  // gathered (SweepScalars::halo_short) and a short guess reruns the set phase the waiting way.  -1: no guess yet.
+  long long halo_guess[SBO_MAX_Q] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  int halo_reruns = 0;            // set phases of the current sweep call discarded for a short window (global decision)
+};
+
+// fp32 models: an fp64 twin of the model (same arrays, double images) that re-evaluates the candidates the fp32 bounds
+// cannot decide (option fp64_recheck); it borrows its owner's streams, events and h_back and holds explicit lists only
+struct Recheck {
+  sbo_ctx* shadow = nullptr;
+  DevBuf mean, var;         // double [q][n_local]: the fp32 posterior widened, flagged entries replaced by fp64 values (what the recheck's set phases read)
+  DevBuf list;              // flagged candidate indices (long long) + counters (64-byte head)
+  DevBuf refined;           // uint8 [n_local]: this candidate's entries of mean / var are fp64 values
+  // the band of the resident fp32 posterior (sets_recheck.inc.hpp: rc_bands): max(1e-4 normalised, 16 x the largest |fp32 - fp64 twin| over
+  // the probe candidates), measured when an fp32 sweep first meets this (model, candidate set); dropped by plans_invalidate
+  DevBuf probe;             // probe indices (long long [kRcProbes]) behind 2 kMaxQ deviation keys
+  bool band_valid = false;
+  double band_dm[kMaxQ] = {}, band_dv[kMaxQ] = {};
+  long long probe_round = 0;  // rotates the probe set of the standing audit
+  void invalidate() { band_valid = false; }
+  ~Recheck();               // deletes the twin (defined below sbo_ctx)
+};
+
+// robust sweep (robust.hip): per-control arrays of the last one, the mask of robust-safe controls, the split partials
+struct Robust {
+  DevBuf vals, mask, part;
+  long long nc = 0;
+  int q = 0;
+  bool valid = false;   // sbo_robust_get may read `vals` (cleared by a model or candidate change)
+  void invalidate() { valid = false; }
+};
+
 }  // namespace sbo
 
 struct sbo_ctx {
+  // What sbo_init created, and it alone fills: the fp64 twin (Recheck::shadow) borrows the raw handles below and its `own` stays empty.
+  // Declared first, so destroyed last: its pinned blocks, events, streams, after every buffer further down.  (The owners a plan or the twin
+  // holds itself -- h_stage, h_bi_params, ev_bi_params, lx.ev0 / ev1, dist.comm_ev[] -- go among the buffers; every stream outlives them.)
+  struct Owned {
+    sbo::Stream stream, stream2, stream3, stream_audit, stream4;
+    sbo::Event ev_factor, ev_w, ev[8], ev_join[SBO_MAX_Q], ev_col[3], ev_grad[4], ev_audit[2];
+    sbo::Pinned h_c1, h_back;
+  } own;
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;   // side stream: the K1b axis bases of a new model run next to its factorisation
@@ -183,6 +351,38 @@ struct sbo_ctx {
   hipStream_t stream4 = nullptr;   // the deferred factorisation of a caller's invK (chol_async): off the critical path of a model change
   hipStream_t stream3 = nullptr;   // spare high-priority stream (drained with the others)
   int n_cu = 256;
+  // What sbo_set_option steers (api.hip: one table row per key -- how the value is taken, its bounds, what it makes stale)
+  struct Options {
+    int chol_async = 1;
+    int exact_lazy = 1;      // one-constraint SafeOpt sweeps on one rank: k_expander_exact only when the result block reports in-band candidates
+    double cheb_tol = 4e-15; // ... relative size below which trailing coefficients are not run (option cheb_tol_e17, in units of 1e-17)
+    int tensor_cheb = 1;             // 0 = always K1g
+    int tensor_guess_pct = 100;      // (test hook): scales the first guess of the node counts; a short guess exercises the probe's second attempt
+    int guard_band = 1;              // 1 count + re-evaluate exactly when the count is non-zero; 0 off; 2 re-evaluate on every sweep (test)
+    int guard_audit = 1024;          // samples per audited sweep, 0 = off
+    int guard_audit_every = 16;      // one sweep in this many is audited (the context's first one is)
+    double audit_scale = 1.0;        // guard_audit_scale_ppm (tests): the audit compares against band x this -- a way to see it fire
+    int set_lanes = 1;       // 0: all constraints on the main stream, one after the other
+    int refine_lds = 1;   // (A/B checker): 1 sbo_refine stages M in LDS when it fits, 0 it always streams M's rows
+    int list_index = -1;  // -1 the index for explicit lists above the exhaustive cap only, 0 never, 1 always
+    int k1_sched = 1;             // 1 = K1b's two lean-2 column-path launches take their tiles from per-sweep lists; 0: one workgroup per tile
+    int comm_events = 0;     // an event pair per collective (MultiRank::comm_ev) whose elapsed times sbo_profile.comm_ms sums
+    int col_path = 1;        // 0 = never
+    int col_overlap = 1;     // 1 = the expander chain runs on stream3 beside the objective's posterior launch; 0: one stream
+    int grad_defer = 1;          // 0 = K1i's gate stays in front of the posterior launch (r04)
+    int halo_spec = 1;       // speculative halo (MultiRank::halo_guess)
+    int scan_waves = 1;      // 1: candidates the coarse bounds leave open are scanned one wave each (0: by their own thread)
+    int scan_blocks = 1;     // 0: step-by-step last-axis scans (A/B against the blocked form)
+    int result_mirror = 1;   // SafeOpt sweeps on one rank: the last kernel writes the results into the pinned host block itself (0: a copy behind it)
+    int set_fuse = 1;        // 2-D grids: independent set-phase kernels share launches (k_edt_axis0_pair, k_set_mid); 0: one launch each
+    int fuse_classify = -1;  // one-constraint sweeps on the K1b path take their S / U bytes from the posterior kernel's mean epilogue: 1 always, 0 never, -1 (default) when the launch has at least four workgroups per CU (r03, sqrt-free sign tests: config H -40 us, config B +-0)
+    int goose_pairs = 0;     // 1: GoOSE coverage by pruned pair evaluation on grids too (A/B against the transform)
+    int phase_events = 0;    // 1: events between the set phases too (classify / expander / arg-reduce times in sbo_profile)
+    int bilinear = 1;        // 1: fp64 2-D grids run the posterior as two GEMMs in a reduced basis when the bases qualify (K1b)
+    int posterior_path = 0;  // 0 auto (separable tables on aligned grids), 1 force the generic exp() kernel
+    int fp64_recheck = 1;    // fp32 models get an fp64 twin (Recheck::shadow); takes effect at the next sbo_model_set
+    int comm_selftest = 0; // 1: a one-rank world still sends C1 / C2 / C3 through its communicator (test of the RCCL calls on one GPU)
+  } opt;
   // model
   bool has_model = false;
   int dtype = SBO_F64;
@@ -210,67 +410,38 @@ struct sbo_ctx {
   sbo::DevBuf invk_img;            // [q][npad / 16][npad / 16][256] A images of the full invK (fp64)
   bool invk_img_valid = false;
   bool invk_w_valid = false;       // the uploaded invK of the current model is still in the build workspace (images can be packed later)
+  const double* invk_plain = nullptr;     // the caller's invK as uploaded, [q][n][n] (valid while invk_w_valid)
   bool factor_todo = false;        // the chain has not been enqueued yet (sbo_model_set does that last: model_factor_enqueue)
   bool factor_pending = false;     // the factor chain of the current model is (possibly) still running; ev_factor marks its end
   hipEvent_t ev_factor = nullptr, ev_w = nullptr;
-  int chol_async = 1;
-  int exact_lazy = 1;      // one-constraint SafeOpt sweeps on one rank: k_expander_exact only when the result block reports in-band candidates
-  double cheb_tol = 4e-15; // ... relative size below which trailing coefficients are not run (option cheb_tol_e17, in units of 1e-17)
+  unsigned long long model_serial = 0;   // bumped by every sbo_model_set / sbo_model_append
+  // K1b (bilinear.hip): the plan, its tables, and what its builders and launches keep between calls
   sbo::BilinearPlan bl;
   sbo::DevBuf bl_P0f, bl_P1A, bl_T4f, bl_BtA, bl_SBf, bl_VA, bl_small, bl_work, bl_cheb;
-  // K1t (tensor.hip): fp64 grids of three / four axes by Chebyshev interpolation from exact node values
-  int tensor_cheb = 1;             // option: 0 = always K1g
-  int tensor_guess_pct = 100;      // option (test hook): scales the first guess of the node counts; a short guess exercises the probe's second attempt
-  sbo::DevBuf tn_pts, tn_vals, tn_work, tn_W0t, tn_W1t, tn_probe, tn_scr;
-  sbo::DevBuf tn_gather;     // ranks > 1: this rank's slab of the node tensors | every rank's (all-gather)
-  sbo::DevBuf tn_W[SBO_MAX_D];
-  size_t tn_work_half = 0;
-  double tn_flops = 0.0;           // multiply-add flops of the last interpolation pass
-  bool tn_valid = false, tn_usable = false;     // plan decided for (tn_model, grid below) / it passed its accuracy probe
-  unsigned long long tn_model = 0;
-  long long tn_first = 0, tn_nlocal = 0, tn_count[4] = {0, 0, 0, 0};
-  double tn_lo[4] = {0, 0, 0, 0}, tn_hi[4] = {0, 0, 0, 0};
-  int tn_level[4] = {0, 0, 0, 0};
-  int tn_dn[4] = {0, 0, 0, 0};     // node counts of the plan in use
-  sbo::DevBuf tn_tail;             // K1t: [2 q][d] keys of the node tensors' coefficient tails per axis (k_t_fiber_tail)
-  double tn_band[7 * SBO_MAX_Q] = {0};   // the plan's guard band (dm | dv | rl | analytic dm | dv | probe dm | dv per output)
-  int tn_bump = 0;                 // ladder steps added to the first guess on this grid (a previous model's plan needed its second attempt)
-  bool tn_lean_probe = false;      // the plan's probe left out output 0's gradient (decided by a lean sweep): a full sweep probes it again
-  // Guard band of the approximating posteriors K1b / K1t (device_common.hpp: GuardBand; guard.hip)
-  int guard_band = 1;              // option: 1 count + re-evaluate exactly when the count is non-zero; 0 off; 2 re-evaluate on every sweep (test)
-  bool gb_active = false;          // the posterior in mean / var came from an approximating kernel; `gb` holds (or will hold, in stream order) its band
-                                   // (a fact about the resident arrays, kept between calls; what a running set phase makes of it: SetView in sets.hip)
-  sbo::DevBuf gb;                  // GuardBand of the resident posterior
-  long long guard_first = 0;       // decisions the first pass of the running sweep left open
-  // Standing audit of the band (r05): behind every K1b / K1i posterior launch of a sweep a rotating sample of the candidates is
-  // re-evaluated with the reference formula on stream2 -- off the critical path -- and compared with what the posterior kernel
-  // stored: a deviation beyond the band is a VIOLATION of the claim the sweeps' exactness rests on (counted, reported in sbo_profile)
-  int guard_audit = 1024;          // option: samples per audited sweep, 0 = off
-  int guard_audit_every = 16;      // option: one sweep in this many is audited (the context's first one is)
-  long long audit_tick = 0;
-  double audit_scale = 1.0;        // option guard_audit_scale_ppm (tests): the audit compares against band x this -- a way to see it fire
-  sbo::DevBuf audit_pts, audit_val, audit_part, audit_cnt;
-  hipEvent_t ev_audit[2]{};        // the sample has been taken (mean / var may be overwritten) / the audit has finished
-  bool audit_pending = false;
-  unsigned long long audit_offset = 0;
-  long long audit_samples = 0, audit_violations = 0;
-  long long audit_skipped = 0;     // of audit_samples: constraint samples on tiles a lean sweep left unevaluated (checked against the enclosure)
-  double audit_worst = 0.0;        // largest deviation seen, in units of the band
-  bool gb_mirrored = false;        // the plan's band kernel also wrote the block to pinned host memory (h_back + kGbMirrorOffset): valid once a sweep has synchronised
-  bool gb_host_valid = false;      // gb_host mirrors `gb` (read back on demand by sbo_profile_get; dropped when a plan writes the block)
-  double gb_host[7 * SBO_MAX_Q] = {0};   // dm | dv | rl | analytic dm | dv | largest probe deviation dm | dv
-  sbo::DevBuf gb_pts, gb_vals;     // re-evaluation: coordinates and exact values of the listed candidates
-  sbo::DevBuf gb_part;             // k_ref_list: per-column-chunk partial sums
-  sbo::DevBuf gb_probe;            // K1b: probe indices / coordinates / reference values of the running plan
-  sbo::DevBuf list_scr;            // key scratch of launch_posterior_on_list
-  unsigned long long gb_plan_model = 0;   // K1b: the model whose band `gb` holds (0: none)
-  long long gb_plan_first = -1, gb_plan_n = -1;
-  const double* invk_plain = nullptr;     // the caller's invK as uploaded, [q][n][n] (valid while invk_w_valid)
   sbo::DevBuf bl_basis;            // K1b: the 2 q axis bases (U, Chebyshev series, ranks) and the workspace of their kernel
   bool bl_basis_ok = false;        // bases enqueued for (bl_basis_serial, bl_basis_ab); their (ok, r, rc) records land at h_back + 4096
   unsigned long long bl_basis_serial = 0;
   double bl_basis_ab[4] = {0, 0, 0, 0};
-  unsigned long long model_serial = 0;   // bumped by every sbo_model_set / sbo_model_append
+  sbo::DevBuf bl_grad;  // K1b: which tiles run the gradient phases (per plan)
+  sbo::DevBuf bl_lpart; // K1b: per-wave Lipschitz partials of k_bpost
+  sbo::DevBuf bl_encl;  // K1b column path: per-cell enclosures of the constraint's posterior (per plan) + a skip byte per tile (per sweep)
+  sbo::DevBuf bl_sched;         // K1b column path, lean 2 (r07): per-tile classes + the tile lists of the constraint's and the objective's launch
+  sbo::Pinned h_stage;          // pinned staging of the K1b table build's single upload (the twin has one of its own)
+  // what the last posterior launch leaves for the standing audit (guard.hip), cleared by every enqueue of a posterior (api.hip):
+  bool k1_skip_armed = false;   // it could leave constraint tiles unevaluated: bl_encl's skip bytes are its record
+  bool k1_encl_check = false;   // a K1b column-path launch on a plan whose enclosures were recorded: what it stored lies inside them
+  size_t k1_encl_tiles = 0;     // tiles of the grid bl_encl was laid out for (the skip bytes sit behind 4 x 128 doubles per tile)
+  // K1i plan (first sweep of a model)
+  sbo::InterpPlan bi;
+  sbo::DevBuf bi_params; // ... its per-model parameter block (device; the plan's kernels read it by pointer) and its pinned staging
+  sbo::Pinned h_bi_params;
+  sbo::Event ev_bi_params;   // the plan's copy of the block (and everything before it on the main stream) has run
+  hipEvent_t ev_grad[4]{};     // K1i's deferred tail: fork (plan: the series are in place) / stage 1 has run / the keys are merged / the band is written
+  bool grad_pending = false;   // a deferred gradient launch is in flight on stream3: whoever reads the Lipschitz partials elsewhere waits for ev_grad[2]
+  sbo::TensorPlan tn;   // K1t plan (fp64 grids of three / four axes)
+  sbo::ResidentBand gb;
+  sbo::Audit audit;
+  sbo::DevBuf list_scr;            // key scratch of launch_posterior_on_list
   // candidates
   bool has_cand = false;
   sbo::CandSpec cs{};
@@ -281,7 +452,7 @@ struct sbo_ctx {
   bool post_l0_missing = false;  // the resident posterior came from a lean sweep's launch: L_0 (Lmax[0]) was not computed
   int last_k1 = 0;               // kernel family of the last posterior launch (sbo_profile.posterior_kernel)
   double last_k1_flops = 0.0;    // matrix-core flops it issued
-  sbo::DevBuf Lmax;    // [kMaxQ] uint64 keys: max ||grad MEAN_i||_inf over the candidates
+  unsigned long long* Lmax = nullptr;   // [kMaxQ] keys: max ||grad MEAN_i||_inf over the candidates -- a view: lane[0].scal + 3072
   // set workspace
   sbo::DevBuf maskS, maskU, maskM, maskG, maskO;   // uint8 [n_local] (G/O: [(q-1)][n_local])
   sbo::DevBuf fitbuf, fitwork;   // hyper-parameter objective: inputs/outputs and the P x n x n factor workspace
@@ -307,133 +478,37 @@ struct sbo_ctx {
     // the explore target / trust-region centre (+ 2048) and a collective's scratch word (+ 4000) are views into it
     sbo::DevBuf scal;
     bool amb_clean = false;        // the recheck / scan counters of `scal` are still zero (no k_reset_amb needed)
-    // every buffer above, for sbo_shutdown: a new one is added here and nowhere else
-    std::vector<sbo::DevBuf*> bufs() { return {&dist2, &dist2b, &coarse, &blockmin, &blockmax, &scanlist, &amb, &gw, &runmeta, &lxtree, &scal}; }
   } lane[2];
-  int set_lanes = 1;       // 0: all constraints on the main stream, one after the other
   sbo::DevBuf partial; // arg-reduce per-block partials
   sbo::ListIndex lx;    // spatial index of an explicit list (sets_index.inc.hpp); a sweep's hierarchy on it: SetLane::lxtree
-  int refine_lds = 1;   // option (A/B checker): 1 sbo_refine stages M in LDS when it fits, 0 it always streams M's rows
-  int list_index = -1;  // option: -1 the index for explicit lists above the exhaustive cap only, 0 never, 1 always
-  sbo::InterpPlan bi;   // K1i plan (first sweep of a model)
-  sbo::DevBuf bi_params; // ... its per-model parameter block (device; the plan's kernels read it by pointer) and its pinned staging
-  void* h_bi_params = nullptr;
-  void* ev_bi_params = nullptr;   // hipEvent_t: the plan's copy of the block (and everything before it on the main stream) has run
-  sbo::DevBuf bl_grad;  // K1b: which tiles run the gradient phases (per plan)
-  sbo::DevBuf bl_lpart; // K1b: per-wave Lipschitz partials of k_bpost
-  sbo::DevBuf bl_encl;  // K1b column path: per-cell enclosures of the constraint's posterior (per plan) + a skip byte per tile (per sweep)
-  // what the last posterior launch leaves for the standing audit (guard.hip), cleared by every enqueue of a posterior (api.hip):
-  bool k1_skip_armed = false;   // it could leave constraint tiles unevaluated: bl_encl's skip bytes are its record
-  bool k1_encl_check = false;   // a K1b column-path launch on a plan whose enclosures were recorded: what it stored lies inside them
-  size_t k1_encl_tiles = 0;     // tiles of the grid bl_encl was laid out for (the skip bytes sit behind 4 x 128 doubles per tile)
-  sbo::DevBuf bl_sched;         // K1b column path, lean 2 (r07): per-tile classes + the tile lists of the constraint's and the objective's launch
-  int k1_sched = 1;             // option: 1 = those two launches take their tiles from per-sweep lists (lean 2); 0: one workgroup per tile
   sbo::DevBuf cpart;   // per-workgroup partials of k_classify, field-major [kClassifyRow][cpart_cap]
   int cpart_cap = 0;   // row capacity the last writer of cpart laid its rows out with
-  long long comm_bytes = 0;   // collectives of the running sweep: bytes handed over (send side), calls, and -- option comm_events --
-  int comm_calls = 0;         // an event pair per call (comm_ev, created on first use) whose elapsed times sbo_profile.comm_ms sums
-  int comm_events = 0;
-  int comm_nev = 0;
-  double comm_host_ms = 0.0;  // (relay transport: wall clock of the staged collectives)
-  hipEvent_t comm_ev[16]{};
   int host_syncs = 0;  // host waits on the device inside the running sweep call (sbo_profile.host_syncs)
   sbo::DevBuf fuseS, fuseU;   // [(q - 1)][N] byte planes of a fused classification of several constraints (r05)
-  // Column path (r05, sets_colpath.inc.hpp): a one-rank SafeOpt sweep of a one-constraint model on a 2-D grid of whole
-  // 64 x 128 tiles asks (PostRequest::col) for the classification as column words; the GEMM posterior then runs one launch per
-  // output -- constraint first: S / U words, |S| per tile; objective second: u* and min var_0 over S from its own epilogue --
-  // and says so (PostOutcome::col_active).  The words stay resident for sbo_masks_get (masks_bits: expanded to bytes on demand).
-  bool slots_clean = false;// the slot block holds its neutral elements (the finals of the last column sweep reset it)
-  bool usum_dirty = false; // Usum holds bits of an earlier launch (cleared by the column path's second kernel; by a memset after a failure)
-  int col_path = 1;        // option: 0 = never
-  int col_overlap = 1;     // option: 1 = the expander chain runs on stream3 beside the objective's posterior launch; 0: one stream
-  sbo::DevBuf cbS, cbU, cbM, cbG, cbUsum;    // column words [H / 64][W]; Usum [W]
-  sbo::DevBuf col_slots;                     // ColBits::slots
-  sbo::DevBuf col_img, col_bmin;             // column distance image u16 [H][W], block minima u16 [H][W / 32]
-  sbo::DevBuf col_cimg, col_cbmin;           // the same on the 8 x 8 cells
-  long long col_ckey = 0;                    // the grid the padding of col_cbmin was laid out for
-  sbo::DevBuf col_fin;                       // the objective's scalars, the finals' tickets and intermediate rows (4 KB)
-  hipEvent_t ev_col[3]{};      // fork (the constraint's posterior launch has finished) / join (the expander chain on stream3 has) /
-                               // the chain's first kernel, which clears the M words, has finished (carried by k_col_a: the minimiser's M part waits for it)
-  hipEvent_t ev_grad[4]{};     // K1i's deferred tail: fork (plan: the series are in place) / stage 1 has run / the keys are merged / the band is written
-  bool grad_pending = false;   // a deferred gradient launch is in flight on stream3: whoever reads the Lipschitz partials elsewhere waits for ev_grad[2]
-  int grad_defer = 1;          // option: 0 = the gate stays in front of the posterior launch (r04)
-  bool masks_bits = false;     // the masks of the last sweep live in the column words (byte buffers stale)
-  bool col_G_bytes = false;    // ... except G, which the exhaustive recheck finished in byte form
-  sbo::DevBuf Wfull;   // multi-rank GoOSE: source weights of the whole grid (all-gathered), T [grid_total]
-  sbo::DevBuf Uwin;    // multi-rank: U mask of the expander transform's window (own planes + halo), uint8
-  long long uwin_first = 0, uwin_n = 0;   // flat range the window covers
-  sbo::DevBuf ubits;                      // multi-rank: own U bits (gather_words words) followed by every rank's (all-gathered)
-  long long gather_words = 0;             // words per rank in ubits
-  sbo::DevBuf gather;  // multi-rank: all-gather receive buffer [world][max_local]
-  sbo::DevBuf xch;     // multi-rank: small exchange buffers (C1 keys, C3 rows)
-  sbo::DevBuf shard_first;  // device copy of first_of[]
-  long long grid_total = 0; // candidates in the whole grid (all ranks)
-  bool sharded = false;     // candidates were set with the canonical plane sharding
-  std::vector<long long> first_of;   // [world + 1] flat offsets of the rank shards
-  unsigned long long* h_c1 = nullptr;     // pinned host copy of the C1 keys (global u*, L, radius) of the running sweep
-  // Speculative halo (ranks > 1, option halo_spec): the host sizes the transform window of constraint c from the keys of the
-  // PREVIOUS sweep (with a margin) instead of waiting for this sweep's; the device checks the guess against the keys it
-  // gathered (SweepScalars::halo_short) and a short guess reruns the set phase the waiting way.  -1: no guess yet.
-  long long halo_guess[SBO_MAX_Q] = {-1, -1, -1, -1, -1, -1, -1, -1};
-  int halo_spec = 1;
-  int halo_reruns = 0;            // set phases of the current sweep call discarded for a short window (global decision)
-  bool c1_pending = false;                // the read-back of h_c1 has been enqueued (event ev[5]) but not yet waited for
-  void* h_stage = nullptr;                // pinned staging of the K1b table build's single upload
-  size_t h_stage_bytes = 0;
+  sbo::ColPath col;
+  sbo::MultiRank dist;
   unsigned char* h_back = nullptr;        // pinned host landing area of the end-of-sweep read-back (scalars + Lipschitz keys)
   int last_sweep = 0;  // 1 safeopt, 2 goose (what the masks hold)
   bool masks_valid = false;
   // profile
   sbo_profile prof{};
   hipEvent_t ev[8]{};
-  hipEvent_t ev_join[SBO_MAX_Q]{};   // phase marks of the fp32 recheck
-  // options
-  int scan_waves = 1;      // 1: candidates the coarse bounds leave open are scanned one wave each (0: by their own thread)
-  int scan_blocks = 1;     // 0: step-by-step last-axis scans (A/B against the blocked form)
-  int result_mirror = 1;   // SafeOpt sweeps on one rank: the last kernel writes the results into the pinned host block itself (0: a copy behind it)
-  int set_fuse = 1;        // 2-D grids: independent set-phase kernels share launches (k_edt_axis0_pair, k_set_mid); 0: one launch each
-  int fuse_classify = -1;  // one-constraint sweeps on the K1b path take their S / U bytes from the posterior kernel's mean epilogue: 1 always, 0 never, -1 (default) when the launch has at least four workgroups per CU (r03, sqrt-free sign tests: config H -40 us, config B +-0)
-  int goose_pairs = 0;     // 1: GoOSE coverage by pruned pair evaluation on grids too (A/B against the transform)
-  int phase_events = 0;    // 1: events between the set phases too (classify / expander / arg-reduce times in sbo_profile)
-  int bilinear = 1;        // 1: fp64 2-D grids run the posterior as two GEMMs in a reduced basis when the bases qualify (K1b)
-  int posterior_path = 0;  // 0 auto (separable tables on aligned grids), 1 force the generic exp() kernel
-  // fp32 models: an fp64 twin of the model (same arrays, double images) that re-evaluates the candidates the fp32 bounds
-  // cannot decide (option fp64_recheck); it shares this context's streams and pinned areas and holds explicit lists only
-  sbo_ctx* shadow = nullptr;
-  bool is_shadow = false;
-  int fp64_recheck = 1;
-  sbo::DevBuf rc_mean, rc_var;   // double [q][n_local]: the fp32 posterior widened, flagged entries replaced by fp64 values (what the recheck's set phases read)
-  sbo::DevBuf rc_list;           // flagged candidate indices (long long) + counters (64-byte head)
-  sbo::DevBuf rc_refined;        // uint8 [n_local]: this candidate's entries of rc_mean / rc_var are fp64 values
-  // the band of the resident fp32 posterior (sets_recheck.inc.hpp: rc_bands): max(1e-4 normalised, 16 x the largest |fp32 - fp64 twin| over
-  // the probe candidates), measured when an fp32 sweep first meets this (model, candidate set); dropped by plans_invalidate
-  sbo::DevBuf rc_probe;          // probe indices (long long [kRcProbes]) behind 2 kMaxQ deviation keys
-  bool rc_band_valid = false;
-  double rc_band_dm[sbo::kMaxQ] = {}, rc_band_dv[sbo::kMaxQ] = {};
-  long long rc_probe_round = 0;  // rotates the probe set of the standing audit
-  // robust sweep (robust.hip): per-control arrays of the last one, the mask of robust-safe controls, the split partials
-  sbo::DevBuf rob, rob_mask, rob_part;
-  long long rob_nc = 0;
-  int rob_q = 0;
-  bool rob_valid = false;   // sbo_robust_get may read `rob` (cleared by a model or candidate change)
-  // comm
-  void* comm = nullptr;  // ncclComm_t
-  int world = 1, rank = 0;
-  int comm_selftest = 0; // 1: a one-rank world still sends C1 / C2 / C3 through its communicator (test of the RCCL calls on one GPU)
-  // rehearsal transport (tests on a 1-GPU box): collectives staged through host callbacks instead of RCCL
-  sbo_relay_allreduce_fn relay_allreduce = nullptr;
-  sbo_relay_allgather_fn relay_allgather = nullptr;
-  void* relay_user = nullptr;
+  hipEvent_t ev_join[SBO_MAX_Q]{};   // phase marks of the fp32 recheck; fork / join marks of the plan builders and of the lanes
+  bool is_shadow = false;   // this context is the fp64 twin of an fp32 model's (Recheck::shadow of its owner)
+  sbo::Recheck recheck;
+  sbo::Robust rob;
 };
+
+inline sbo::Recheck::~Recheck() { delete shadow; }
 
 namespace sbo {
 // the sweeps take their multi-rank path (pack, collective, unpack, host merge): more than one rank, or the self-test
-inline bool multi_rank(const sbo_ctx* c) { return c->world > 1 || c->comm_selftest; }
+inline bool multi_rank(const sbo_ctx* c) { return c->dist.world > 1 || c->opt.comm_selftest; }
 // the guard band of the resident posterior of an fp64 model (device_common.hpp: GuardBand), when an approximating kernel (K1b / K1i / K1t)
 // wrote it and option guard_band is on; nullptr: the values are the exact kernels'
 struct GuardBand;
 inline const GuardBand* resident_band(const sbo_ctx* c) {
-  return (c->gb_active && c->guard_band && c->gb.p) ? (const GuardBand*)c->gb.p : nullptr;
+  return (c->gb.active && c->opt.guard_band && c->gb.buf.p) ? (const GuardBand*)c->gb.buf.p : nullptr;
 }
 int fail(int code, const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
@@ -476,12 +551,49 @@ int interp_setup(sbo_ctx* c);
 int guard_probe_gradients(sbo_ctx* c, hipStream_t st, double* ppts, double* grad_out, const sbo::ModelConst* mcp = nullptr);
 int bilinear_setup(sbo_ctx* c);
 int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostOutcome& out);   // on the operands of K1i's plan (interp) or of K1b's
-// both GEMM-posterior plans (and the posterior) out of date: a new model, new candidates, or an option the plans are built with
+// What a change makes stale.  Every entry point and every option handler (api.hip) calls exactly one of the three functions below
+// and writes no validity flag itself; where the cases differ, the reason stands here.
+// Both GEMM-posterior plans, the posterior and the fp32 band: a new model, new candidates, or an option the plans are built with.
+// (Not K1t's plan: it keys itself on the model's serial and the grid, tensor_applicable compares them.)
 inline void plans_invalidate(sbo_ctx* c) {
   c->bl.valid = false;
   c->bi.valid = false;
   c->posterior_valid = false;
-  c->rc_band_valid = false;
+  c->recheck.invalidate();
+}
+// sbo_model_set (before it touches the resident model) and sbo_model_append (once the new row is in place: a refused or failed append
+// leaves everything as it was).  The factor and invK flags are the model builder's own (model.hip: model_build, model_append_commit).
+inline void model_changed(sbo_ctx* c) {
+  c->masks_valid = false;
+  c->rob.invalidate();
+  plans_invalidate(c);
+}
+enum CandKind { kCandPoints, kCandGrid, kCandGridSharded };
+inline void candidates_changed(sbo_ctx* c, CandKind kind) {
+  if (kind == kCandPoints) c->lx.valid = false;          // (a grid leaves the index of the last list alone: only a list reads it, and every list drops it)
+  else for (auto& g : c->dist.halo_guess) g = -1;        // (points: the halo guess is a property of grids)
+  c->dist.sharded = kind == kCandGridSharded;
+  c->rob.invalidate();
+  plans_invalidate(c);
+  c->masks_valid = false;
+}
+enum OptEffect {
+  kOptNothing,     // read where it is used
+  kOptPlans,       // the GEMM plans are built with it
+  kOptPlansBand,   // guard_band: every plan measures its band when it is built -- K1t's too, which no model or grid change needs to drop
+  kOptTensor,      // K1t's plan and the posterior it may have written
+  kOptInterp,      // grad_defer: K1i's plan is laid out for it; K1b's is not, and a resident posterior stays what it is
+  kOptPosterior    // posterior_path: another exact kernel sums in another order -- the posterior and an fp32 model's band, but no plan
+};
+inline void option_changed(sbo_ctx* c, OptEffect effect) {
+  switch (effect) {
+    case kOptNothing: break;
+    case kOptPlans: plans_invalidate(c); break;
+    case kOptPlansBand: plans_invalidate(c); c->tn.invalidate(); break;
+    case kOptTensor: c->tn.invalidate(); c->posterior_valid = false; break;
+    case kOptInterp: c->bi.valid = false; break;
+    case kOptPosterior: c->posterior_valid = false; c->recheck.invalidate(); break;
+  }
 }
 bool tensor_applicable(const sbo_ctx* c);
 int launch_posterior_tensor(sbo_ctx* c, const PostRequest& req, bool* declined);
@@ -493,7 +605,7 @@ int launch_posterior_on_list(sbo_ctx* c, const double* pts, long long N, double*
 // enqueued behind the first posterior launch of a plan); a host-known band (K1t) or "none" (exact kernels)
 int guard_exact_list(sbo_ctx* c, const double* pts, long long N, double* mean_out, double* var_out);
 int guard_exact_grad_list(sbo_ctx* c, const double* pts, long long N, double* grad_out /* [q][d][N] */);
-int guard_probe_reference(sbo_ctx* c, hipStream_t side, double** ref_m, double** ref_v, const sbo::ModelConst* mcp = nullptr);       // -> gb_probe: [q][P] each; K1b's own values follow at + 2 q P
+int guard_probe_reference(sbo_ctx* c, hipStream_t side, double** ref_m, double** ref_v, const sbo::ModelConst* mcp = nullptr);       // -> gb.probe: [q][P] each; K1b's own values follow at + 2 q P
 // what K1b's band kernel needs to carry the axis bases' truncation through the posterior formula (guard.hip: k_gb_band)
 struct GbAnalytic {
   const double* axis_eps;   // [2 q][2]: largest of the last four Chebyshev coefficients of the axis factors | sqrt(rc) x largest residual row norm of the basis

@@ -604,13 +604,11 @@ static int model_work(sbo_ctx* c, bool with_W, ModelWork& w) {
   return SBO_OK;
 }
 static int stage_ensure(sbo_ctx* c, size_t bytes) {
-  if (c->h_stage_bytes >= bytes) return SBO_OK;
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
-  c->h_stage = nullptr;
-  c->h_stage_bytes = 0;
+  if (c->h_stage.bytes >= bytes) return SBO_OK;
+  c->h_stage.reset();
   const size_t want = bytes + bytes / 2 + 4096;
-  if (hipHostMalloc(&c->h_stage, want, hipHostMallocDefault) != hipSuccess) return fail(SBO_E_HIP, "hipHostMalloc (model staging)");
-  c->h_stage_bytes = want;
+  if (hipHostMalloc(&c->h_stage.p, want, hipHostMallocDefault) != hipSuccess) return fail(SBO_E_HIP, "hipHostMalloc (model staging)");
+  c->h_stage.bytes = want;
   return SBO_OK;
 }
 template <typename T>
@@ -619,7 +617,7 @@ static int model_prep_t(sbo_ctx* c, const double* X_norm, const double* Y_norm, 
   const size_t n = mc.n, q = mc.q, npad = mc.npad;
   int rc;
   if ((rc = stage_ensure(c, sizeof(double) * (n * mc.d + n * q + 2 * q)))) return rc;
-  double* hs = (double*)c->h_stage;
+  double* hs = (double*)c->h_stage.p;
   std::memcpy(hs, X_norm, sizeof(double) * n * mc.d);
   if (Y_norm) std::memcpy(hs + n * mc.d, Y_norm, sizeof(double) * n * q);
   SBO_HIP(hipMemcpyAsync(w.XY, hs, sizeof(double) * (n * mc.d + (Y_norm ? n * q : 0)), hipMemcpyHostToDevice, c->stream));
@@ -714,7 +712,7 @@ static int model_build_t(sbo_ctx* c, const double* const* host_invK /* q matrice
   bool eager_basis = false;
   // (r04) a caller's invK on a K1b-capable grid: the model's first sweep runs on interpolated node values (K1i, bilinear.hip), which
   // needs no bases -- they are made when the model is swept a second time
-  const bool interp_first = bilinear_applicable(c) && c->bilinear == 1 && host_invK != nullptr && n >= kBlockedFrom && c->chol_async &&
+  const bool interp_first = bilinear_applicable(c) && c->opt.bilinear == 1 && host_invK != nullptr && n >= kBlockedFrom && c->opt.chol_async &&
                             !c->is_shadow && c->stream4 && std::is_same<T, double>::value && c->mc.npad % 16 == 0;
   if (bilinear_applicable(c) && !interp_first) {
     // the bases need X_norm only: next to the factorisation, on the second stream -- and ahead of the upload of invK
@@ -739,7 +737,7 @@ static int model_build_t(sbo_ctx* c, const double* const* host_invK /* q matrice
   // not even enqueued here (the host needs ~0.1 ms for them): the next sweep does that while it waits for its own result
   // (model_factor_enqueue), a consumer of the factor before that enqueues and waits (factor_sync), and a model replaced
   // before anyone asked never factors at all.
-  const bool deferred = mode == 0 && n >= kBlockedFrom && c->chol_async && !c->is_shadow && (eager_basis || interp_first) && c->stream4 &&
+  const bool deferred = mode == 0 && n >= kBlockedFrom && c->opt.chol_async && !c->is_shadow && (eager_basis || interp_first) && c->stream4 &&
                         std::is_same<T, double>::value;
   const size_t ntri = (size_t)nb * (nb + 1) / 2;
   c->fpk_stride = ntri * 4 * 64;
@@ -843,7 +841,7 @@ int model_append_check(sbo_ctx* c, const std::vector<double>& kvec, const double
     if (n + 1 > cap) return fail(SBO_E_UNSUPPORTED, "model is at its capacity: rebuild it with sbo_model_set");
     DevBuf F2, a2;
     if ((rc = ensure(F2, sizeof(double) * (size_t)q * cap * cap))) return rc;
-    if ((rc = ensure(a2, sizeof(double) * (size_t)q * cap))) { release(F2); return rc; }
+    if ((rc = ensure(a2, sizeof(double) * (size_t)q * cap))) return rc;
     hipError_t e = hipMemsetAsync(F2.p, 0, sizeof(double) * (size_t)q * cap * cap, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(a2.p, 0, sizeof(double) * (size_t)q * cap, c->stream);
     for (int o = 0; o < q && e == hipSuccess; ++o) {
@@ -854,11 +852,9 @@ int model_append_check(sbo_ctx* c, const std::vector<double>& kvec, const double
                            hipMemcpyDeviceToDevice, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { release(F2); release(a2); return hip_fail(e, "growing the resident factor"); }
-    release(c->Fplain);
-    release(c->alpha64);
-    c->Fplain = F2;
-    c->alpha64 = a2;
+    if (e != hipSuccess) return hip_fail(e, "growing the resident factor");
+    c->Fplain = std::move(F2);
+    c->alpha64 = std::move(a2);
     c->f_cap = cap;
     c->a_ld = cap;
   }
@@ -893,6 +889,8 @@ int model_append_commit(sbo_ctx* c) {
   hipLaunchKernelGGL(k_model_append_commit, dim3(q), dim3(1024), 0, c->stream, n, cap, (double*)c->Fplain.p, (double*)c->alpha64.p,
                      (const double*)drho, (const double*)dscratch, (const double*)dsk);
   SBO_HIP(hipGetLastError());
+  c->invk_img_valid = false;                                    // (the images of the caller's invK do not follow an append)
+  c->invk_w_valid = false;
   return SBO_OK;
 }
 

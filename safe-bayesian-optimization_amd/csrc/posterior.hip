@@ -949,7 +949,7 @@ static int launch_posterior_grid(sbo_ctx* c, const PostTarget& t) {
 // the separable path needs whole axis-0 lines in the shard
 static bool grid_path_ok(const sbo_ctx* c) {
   const CandSpec& cs = c->cs;
-  if (c->posterior_path != 0) return false;
+  if (c->opt.posterior_path != 0) return false;
   if (cs.kind != 1 || cs.n_local <= 0) return false;
   const long long cnt0 = cs.count[0];
   return cs.first % cnt0 == 0 && cs.n_local % cnt0 == 0;
@@ -959,16 +959,16 @@ static bool grid_path_ok(const sbo_ctx* c) {
 // chunked kernel beyond that (and on request: posterior_path 2)
 static bool generic_chunked(const sbo_ctx* c) {
   const size_t tile_bytes = (c->dtype == SBO_F64 ? 8u : 4u) * (size_t)c->mc.npad * 64;
-  return c->posterior_path == 2 || tile_bytes > 64 * 1024;
+  return c->opt.posterior_path == 2 || tile_bytes > 64 * 1024;
 }
 static int launch_generic(sbo_ctx* c, const PostTarget& t);   // (defined below launch_posterior: the code object keeps its kernel order)
 
 int launch_posterior(sbo_ctx* c, const PostRequest& req, PostOutcome& out) {
-  c->gb_active = false;                    // (the approximating paths K1b / K1t switch their guard band on themselves)
+  c->gb.active = false;                    // (the approximating paths K1b / K1t switch their guard band on themselves)
   c->k1_skip_armed = c->k1_encl_check = false;   // (so does the K1b column path its records for the audit, guard.hip)
   // block-triangular contraction as issued: npad (npad + 16) / 2 multiply-adds per candidate and output
   const double tri_flops = (double)c->mc.q * c->mc.npad * (c->mc.npad + 16.0) * (double)c->cs.n_local;
-  const PostTarget t{c->cs, c->mean.p, c->var.p, (unsigned long long*)c->Lmax.p};
+  const PostTarget t{c->cs, c->mean.p, c->var.p, c->Lmax};
   if (grid_path_ok(c)) {
     // fp64 2-D grids: two GEMMs in a reduced basis (K1b) when the axis bases qualify, else the separable tables (K1g)
     if (!req.exact && bilinear_applicable(c)) {
@@ -1037,7 +1037,7 @@ int launch_posterior_on_axes(sbo_ctx* c, int d, const long long* count, const do
 }
 
 // the exact posterior of the generic kernel on an explicit fp64 list, into caller-given arrays.  The resident posterior and its
-// records (last_k1, last_k1_flops, gb_active: they describe what mean / var hold) are not touched.
+// records (last_k1, last_k1_flops, gb.active: they describe what mean / var hold) are not touched.
 int launch_posterior_on_list(sbo_ctx* c, const double* pts, long long N, double* mean_out, double* var_out) {
   if (c->dtype != SBO_F64) return fail(SBO_E_UNSUPPORTED, "internal: exact lists are an fp64 path");
   int rc;

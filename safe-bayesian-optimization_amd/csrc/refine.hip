@@ -606,7 +606,7 @@ static int refine_run(sbo_ctx* c, RefineArgs& A, int max_eval, double tol, long 
   const int n = mc.n;
   const size_t tri_bytes = sizeof(double) * (size_t)A.nu * n * (n + 1) / 2;
   const size_t kvuv = sizeof(double) * 2 * (size_t)n;                              // k and u = M k of one point
-  const bool lds_tier = c->refine_lds && tri_bytes + (np - 1) * kvuv <= kRefLdsM;  // (the second point's vectors count against M's budget)
+  const bool lds_tier = c->opt.refine_lds && tri_bytes + (np - 1) * kvuv <= kRefLdsM;  // (the second point's vectors count against M's budget)
   const size_t lds = np * kvuv + (lds_tier ? tri_bytes : 0);
   const int threads = n > 256 ? 1024 : 256;
   if (S > 0x7fffffffLL) return fail(SBO_E_UNSUPPORTED, "too many seeds for one launch");

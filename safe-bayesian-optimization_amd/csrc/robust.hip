@@ -223,11 +223,11 @@ int rob_layout(sbo_ctx* c, long long nc, RobLayout& L) {
   const size_t nA = (size_t)nc;
   // local f | fsec | argd | fb | g | gbd;  ranks > 1: global f | fb | g | gbd and the key arrays (2 x (2 + qc) Nc);  the scalars; the rows
   const size_t words = nA * (4 + 2 * (size_t)qc) + (mr ? nA * (2 + 2 * (size_t)qc) + 2 * nA * (2 + (size_t)qc) : 0) + 64 +
-                       (size_t)kRowFields * (c->world + 1);
+                       (size_t)kRowFields * (c->dist.world + 1);
   int rc;
-  if ((rc = ensure(c->rob, words * 8))) return rc;
-  if ((rc = ensure(c->rob_mask, nA + 8))) return rc;
-  double* p = (double*)c->rob.p;
+  if ((rc = ensure(c->rob.vals, words * 8))) return rc;
+  if ((rc = ensure(c->rob.mask, nA + 8))) return rc;
+  double* p = (double*)c->rob.vals.p;
   L.nc = nc;
   L.qc = qc;
   L.floc = p; p += nA;
@@ -291,8 +291,8 @@ int robust_phase(sbo_ctx* c, const sbo_sweep_opts* o, int kind, long long nc, co
       hipLaunchKernelGGL(k_robust_reduce, dim3(bx, 1), dim3(kRobBlock), 0, c->stream, a);
     } else {
       const size_t per = (size_t)nc * (4 + 2 * (size_t)qc);
-      if ((rc = ensure(c->rob_part, per * (size_t)sp * 8))) return rc;
-      double* p = (double*)c->rob_part.p;
+      if ((rc = ensure(c->rob.part, per * (size_t)sp * 8))) return rc;
+      double* p = (double*)c->rob.part.p;
       a.f = p; p += (size_t)sp * nc;
       a.fsec = p; p += (size_t)sp * nc;
       a.argd = (long long*)p; p += (size_t)sp * nc;
@@ -316,14 +316,14 @@ int robust_phase(sbo_ctx* c, const sbo_sweep_opts* o, int kind, long long nc, co
     if (qc > 0 && (rc = comm_allreduce_min_u64(c, L.kmin, (int)(nc * qc)))) return rc;
     hipLaunchKernelGGL(k_robust_unkeys, dim3(bx), dim3(kRobBlock), 0, c->stream, L.kmax, L.kmin, nc, qc, L.fG, L.fbG, L.gG, L.gbG);
   }
-  if (nc > 0) hipLaunchKernelGGL(k_robust_safe, dim3(bx), dim3(kRobBlock), 0, c->stream, L.gG, L.gbG, nc, qc, (uint8_t*)c->rob_mask.p, L.open);
+  if (nc > 0) hipLaunchKernelGGL(k_robust_safe, dim3(bx), dim3(kRobBlock), 0, c->stream, L.gG, L.gbG, nc, qc, (uint8_t*)c->rob.mask.p, L.open);
   SBO_HIP(hipGetLastError());
   long long* a4 = (long long*)(L.open + 1);
-  if ((rc = robust_argmin(c, L.fG, L.fbG, (const uint8_t*)c->rob_mask.p, nc, gb != nullptr, a4))) return rc;
+  if ((rc = robust_argmin(c, L.fG, L.fbG, (const uint8_t*)c->rob.mask.p, nc, gb != nullptr, a4))) return rc;
   // the winner's worst disturbance: every rank's first plane of the maximum and runner-up value, merged on the host
   hipLaunchKernelGGL(k_robust_row, dim3(1), dim3(1), 0, c->stream, (const long long*)a4, L.fG, L.floc, L.fsec, L.argd, L.fbG, L.row);
   SBO_HIP(hipGetLastError());
-  const int nrows = multi_rank(c) ? c->world : 1;
+  const int nrows = multi_rank(c) ? c->dist.world : 1;
   const double* rows = L.row;
   if (multi_rank(c)) {
     if ((rc = comm_allgather_bytes(c, L.row, L.rows, sizeof(double) * kRowFields))) return rc;
@@ -391,7 +391,7 @@ int sweep_robust(sbo_ctx* c, const sbo_sweep_opts* o, int nca, int kind, sbo_rob
   const long long first_open = P.open + P.worst_open;
   // an approximating posterior whose band left a decision open (or option guard_band 2): the exact kernel on the whole grid, decide again.
   // The ranks decide together -- the re-evaluation contains collectives.
-  unsigned long long want[2] = {(unsigned long long)(gb && (first_open > 0 || c->guard_band == 2) ? 1 : 0), 0};
+  unsigned long long want[2] = {(unsigned long long)(gb && (first_open > 0 || c->opt.guard_band == 2) ? 1 : 0), 0};
   if (multi_rank(c)) {
     RobLayout L;
     if ((rc = rob_layout(c, nc, L))) return rc;
@@ -458,9 +458,9 @@ int sweep_robust(sbo_ctx* c, const sbo_sweep_opts* o, int nca, int kind, sbo_rob
       else res->worst_d[a - nca] = x;
     }
   }
-  c->rob_nc = nc;
-  c->rob_q = c->mc.q;
-  c->rob_valid = true;
+  c->rob.nc = nc;
+  c->rob.q = c->mc.q;
+  c->rob.valid = true;
   return SBO_OK;
 }
 
@@ -483,8 +483,8 @@ int sbo_sweep_robust(sbo_ctx* c, const sbo_sweep_opts* opts, int n_control_axes,
   if (!(opts->b >= 0.0) || !std::isfinite(opts->b)) return fail(SBO_E_INVALID, "confidence multiplier b must be finite and >= 0");
   if (c->dtype != SBO_F64) return fail(SBO_E_UNSUPPORTED, "the robust sweep runs fp64 models only");
   SBO_HIP(hipSetDevice(c->device));
-  c->guard_first = 0;
-  c->rob_valid = false;
+  c->gb.first = 0;
+  c->rob.valid = false;
   const int rc = sweep_robust(c, opts, n_control_axes, kind, result);
   if (rc != SBO_OK) drain_streams(c);
   return rc;
@@ -492,14 +492,14 @@ int sbo_sweep_robust(sbo_ctx* c, const sbo_sweep_opts* opts, int n_control_axes,
 
 int sbo_robust_get(sbo_ctx* c, double* f_out, double* g_out) {
   if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
-  if (!c->rob_valid) return fail(SBO_E_INVALID, "no robust sweep has run on the resident model and candidates");
+  if (!c->rob.valid) return fail(SBO_E_INVALID, "no robust sweep has run on the resident model and candidates");
   SBO_HIP(hipSetDevice(c->device));
   RobLayout L;
-  const int rc = rob_layout(c, c->rob_nc, L);   // (the buffer is already that size: no reallocation)
+  const int rc = rob_layout(c, c->rob.nc, L);   // (the buffer is already that size: no reallocation)
   if (rc) return rc;
-  const size_t nc = (size_t)c->rob_nc;
+  const size_t nc = (size_t)c->rob.nc;
   if (f_out && nc) SBO_HIP(hipMemcpyAsync(f_out, L.fG, nc * 8, hipMemcpyDeviceToHost, c->stream));
-  if (g_out && nc && c->rob_q > 1) SBO_HIP(hipMemcpyAsync(g_out, L.gG, nc * (c->rob_q - 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  if (g_out && nc && c->rob.q > 1) SBO_HIP(hipMemcpyAsync(g_out, L.gG, nc * (c->rob.q - 1) * 8, hipMemcpyDeviceToHost, c->stream));
   SBO_HIP(hipStreamSynchronize(c->stream));
   return SBO_OK;
 }

@@ -1081,7 +1081,7 @@ static int reduce_blocks(const sbo_ctx* c) {
 // leaves its Lipschitz partials for the sweep (every sweep merges them in its k_classify_final)
 static PostRequest sweep_request(const sbo_ctx* c, double b, bool may_fuse) {
   PostRequest req;
-  req.fuse = (may_fuse && c->mc.q >= 2) ? (c->fuse_classify < 0 ? 2 : c->fuse_classify) : 0;
+  req.fuse = (may_fuse && c->mc.q >= 2) ? (c->opt.fuse_classify < 0 ? 2 : c->opt.fuse_classify) : 0;
   req.fuse_b = b;
   req.lmax_defer = may_fuse;
   return req;
@@ -1093,14 +1093,14 @@ static int sweep_masks(sbo_ctx* c, const PostRequest& req) {
   const int q = c->mc.q;
   int rc;
   long long npad_shard = n;                  // ranks > 1: the U mask is all-gathered with the largest shard's size
-  for (size_t r = 0; r + 1 < c->first_of.size() && multi_rank(c) && c->sharded; ++r)
-    npad_shard = std::max(npad_shard, c->first_of[r + 1] - c->first_of[r]);
+  for (size_t r = 0; r + 1 < c->dist.first_of.size() && multi_rank(c) && c->dist.sharded; ++r)
+    npad_shard = std::max(npad_shard, c->dist.first_of[r + 1] - c->dist.first_of[r]);
   if ((rc = ensure(c->maskS, (size_t)n))) return rc;
   if ((rc = ensure(c->maskU, (size_t)npad_shard))) return rc;
   if ((rc = ensure(c->maskM, (size_t)n))) return rc;
   if ((rc = ensure(c->maskG, (size_t)n * std::max(1, q - 1)))) return rc;
-  c->masks_bits = false;
-  c->col_G_bytes = false;
+  c->col.masks_bits = false;
+  c->col.G_bytes = false;
   if (req.fuse && q > 2) {            // (one S / U byte plane per constraint: bilinear.hip, k_classify_and)
     if ((rc = ensure(c->fuseS, (size_t)n * (q - 1))) || (rc = ensure(c->fuseU, (size_t)n * (q - 1)))) return rc;
   }
@@ -1117,7 +1117,7 @@ static bool whole_planes(const sbo_ctx* c, long long* plane_out = nullptr) {
   return c->cs.kind == 1 && c->cs.first % plane == 0 && c->cs.n_local % plane == 0;
 }
 
-static bool lanes_on(const sbo_ctx* c) { return c->set_lanes && !multi_rank(c) && c->mc.q >= 3 && c->cs.n_local > 0 && c->stream2; }
+static bool lanes_on(const sbo_ctx* c) { return c->opt.set_lanes && !multi_rank(c) && c->mc.q >= 3 && c->cs.n_local > 0 && c->stream2; }
 
 // ---- what a set phase looks at ---------------------------------------------------------------------------------------------
 // Built by whoever starts the set phase and handed down next to the lane: a plain sweep looks at the resident posterior of the
@@ -1193,7 +1193,7 @@ static int sweep_common_front(sbo_ctx* c, const sbo_sweep_opts* o, const SetView
   if (post.lmax_pending) {
     fj.Lpart = (const double*)c->bl_lpart.p;
     fj.per_out = post.lmax_per_out;
-    fj.Lmax = (unsigned long long*)c->Lmax.p;
+    fj.Lmax = c->Lmax;
   }
   // four workgroups per CU measured best (2: 24.6 us, 4: 21.5, 8: 27.1 on config B's 4 M candidates; on config C's 1 M: 1024 /
   // 512 / 256 workgroups 0.1455 / 0.1463 / 0.1530 ms per sweep -- fewer is not better there either)
@@ -1243,15 +1243,15 @@ static int launch_exact(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
   CandSpec csU = c->cs;          // the witness set: every candidate that can matter (ranks > 1: the transform's window)
   const uint8_t* Uall = (const uint8_t*)c->maskU.p;
   if (multi_rank(c)) {
-    csU.first = c->uwin_first;
-    csU.n_local = c->uwin_n;
-    Uall = (const uint8_t*)c->Uwin.p;
+    csU.first = c->dist.uwin_first;
+    csU.n_local = c->dist.uwin_n;
+    Uall = (const uint8_t*)c->dist.Uwin.p;
   }
   RcExp rx;
   memset(&rx, 0, sizeof(rx));
   if (!v.refined) rx_band<T>(c, v, cidx, lidx, rx);   // (fast path of an approximating posterior: the listed candidates' verdicts are judged against its band)
   hipLaunchKernelGGL((k_expander_exact<T, D>), dim3(1024), dim3(256), 0, ln.stream, c->cs, csU, mean_c, var_c, (T)o->b,
-                     Uall, (const unsigned long long*)c->Lmax.p, lidx, sc,
+                     Uall, c->Lmax, lidx, sc,
                      (const long long*)ln.amb.p, G, rx);
   SBO_HIP(hipGetLastError());
   return SBO_OK;
@@ -1290,12 +1290,12 @@ __global__ void k_halo_check(SweepScalars* sc, const unsigned long long* Lkeys, 
 // the window's halo for constraint cidx: the guess from the previous sweep (checked on the device), or the keys of this one
 // (the host waits for their read-back)
 static int halo_for(sbo_ctx* c, sbo_ctx::SetLane& ln, int cidx, int lidx, double hl, long long planes_total, long long* H_out) {
-  if (c->halo_spec && c->halo_guess[cidx] >= 0) {
-    long long H = std::min(planes_total, c->halo_guess[cidx]);
+  if (c->opt.halo_spec && c->dist.halo_guess[cidx] >= 0) {
+    long long H = std::min(planes_total, c->dist.halo_guess[cidx]);
     // (test hook: this rank alone guesses one plane -- tests/test_gpu_parity.py: the rerun must be every rank's decision)
     static const bool test_short = getenv("SBO_TEST_HALO_SHORT") != nullptr;
     if (test_short) H = std::min<long long>(H, 1);
-    hipLaunchKernelGGL(k_halo_check, dim3(1), dim3(1), 0, ln.stream, (SweepScalars*)ln.scal.p, (const unsigned long long*)c->Lmax.p, lidx, cidx,
+    hipLaunchKernelGGL(k_halo_check, dim3(1), dim3(1), 0, ln.stream, (SweepScalars*)ln.scal.p, c->Lmax, lidx, cidx,
                        hl, H, planes_total);
     *H_out = H;
     return SBO_OK;
@@ -1303,8 +1303,8 @@ static int halo_for(sbo_ctx* c, sbo_ctx::SetLane& ln, int cidx, int lidx, double
   int rc;
   if ((rc = sweep_exchange_wait(c))) return rc;
   double L, rmax = 0.0;
-  memcpy(&L, &c->h_c1[1 + lidx], 8);
-  if (c->h_c1[1 + kMaxQ + cidx]) rmax = ord_val(c->h_c1[1 + kMaxQ + cidx]);
+  memcpy(&L, &c->dist.h_c1[1 + lidx], 8);
+  if (c->dist.h_c1[1 + kMaxQ + cidx]) rmax = ord_val(c->dist.h_c1[1 + kMaxQ + cidx]);
   *H_out = halo_planes(L, rmax, hl, planes_total);
   return SBO_OK;
 }
@@ -1320,7 +1320,7 @@ static void halo_learn(sbo_ctx* c, const SweepScalars& h, const unsigned long lo
     memcpy(&L, &Lk[lidx], 8);
     const double rmax = h.rmax_key[cc] ? ord_val(h.rmax_key[cc]) : 0.0;
     const long long H = halo_planes(L, rmax, hl, planes_total);
-    c->halo_guess[cc] = H >= planes_total ? planes_total : std::min(planes_total, H + H / 4 + 2);
+    c->dist.halo_guess[cc] = H >= planes_total ? planes_total : std::min(planes_total, H + H / 4 + 2);
   }
 }
 
@@ -1354,8 +1354,8 @@ constexpr long long kListExpanderMax = 1ll << 21;     // explicit lists: largest
 // ---- spatial index of explicit lists (sets_index.inc.hpp) ----------------------------------------------------------------
 // option list_index: -1 (default) only where the exhaustive expander sets refuse the list (above kListExpanderMax), 1 always, 0 never
 static bool list_index_on(const sbo_ctx* c) {
-  if (c->cs.kind != 0 || multi_rank(c) || c->cs.n_local <= 0 || c->list_index == 0) return false;
-  return c->list_index == 1 || c->cs.n_local > kListExpanderMax;
+  if (c->cs.kind != 0 || multi_rank(c) || c->cs.n_local <= 0 || c->opt.list_index == 0) return false;
+  return c->opt.list_index == 1 || c->cs.n_local > kListExpanderMax;
 }
 static int idx_dpad(int d) { return d <= 2 ? 2 : (d <= 4 ? 4 : 8); }
 
@@ -1402,9 +1402,9 @@ static int list_index_prepare(sbo_ctx* c) {
   if ((rc = ensure(x.vals, 2 * sizeof(unsigned) * (size_t)n))) return rc;
   if ((rc = ensure(x.hist, sizeof(unsigned) * ((size_t)256 * ntiles + 256)))) return rc;
   if ((rc = ensure(x.xs, sizeof(double) * (size_t)n * c->cs.d))) return rc;
-  if (!x.ev0) SBO_HIP(hipEventCreate(&x.ev0));
-  if (!x.ev1) SBO_HIP(hipEventCreate(&x.ev1));
-  SBO_HIP(hipEventRecord(x.ev0, c->stream));
+  if (!x.ev0.e) SBO_HIP(hipEventCreate(&x.ev0.e));
+  if (!x.ev1.e) SBO_HIP(hipEventCreate(&x.ev1.e));
+  SBO_HIP(hipEventRecord(x.ev0.e, c->stream));
   unsigned long long* k0 = (unsigned long long*)x.keys.p;
   unsigned* v0 = (unsigned*)x.vals.p;
   switch (idx_dpad(c->cs.d)) {
@@ -1413,7 +1413,7 @@ static int list_index_prepare(sbo_ctx* c) {
     default: list_index_sort_d<8>(c, k0, v0, k0 + n, v0 + n, ntiles); break;
   }
   SBO_HIP(hipGetLastError());
-  SBO_HIP(hipEventRecord(x.ev1, c->stream));
+  SBO_HIP(hipEventRecord(x.ev1.e, c->stream));
   x.valid = true;
   x.built_now = true;
   x.n = n;
@@ -1428,7 +1428,7 @@ static int list_index_profile(sbo_ctx* c) {
   c->prof.list_index_leaf_pairs = c->prof.list_index_nodes_skipped = 0;
   if (x.built_now) {
     float ms = 0.f;
-    SBO_HIP(hipEventElapsedTime(&ms, x.ev0, x.ev1));
+    SBO_HIP(hipEventElapsedTime(&ms, x.ev0.e, x.ev1.e));
     c->prof.list_index_build_ms = ms;
   }
   if (x.ran) {
@@ -1491,7 +1491,7 @@ static int list_index_expander(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep
   const T* var_c = (const T*)v.var->p + (size_t)cidx * n;
   const unsigned nb = (unsigned)std::min<long long>((n + 3) / 4, (long long)c->n_cu * 16);
   hipLaunchKernelGGL((k_idx_expander<T, D>), dim3(nb), dim3(256), 0, ln.stream, t, mean_c, var_c, (T)o->b, (const uint8_t*)c->maskS.p,
-                     (const unsigned long long*)c->Lmax.p, lidx, (SweepScalars*)ln.scal.p, G, (long long*)ln.amb.p, rx);
+                     c->Lmax, lidx, (SweepScalars*)ln.scal.p, G, (long long*)ln.amb.p, rx);
   SBO_HIP(hipGetLastError());
   c->lx.ran = true;
   return SBO_OK;
@@ -1562,13 +1562,13 @@ static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
     const uint8_t* Uall = (const uint8_t*)c->maskU.p;
     if (multi_rank(c)) {
       // bytes of the window only, out of the all-gathered bit words (the gather itself was queued ahead of the host's wait)
-      if ((rc = ensure(c->Uwin, (size_t)nt))) return rc;
-      const unsigned long long* recvw = (const unsigned long long*)c->ubits.p + c->gather_words + kC1Head;   // (past the own block and a head)
+      if ((rc = ensure(c->dist.Uwin, (size_t)nt))) return rc;
+      const unsigned long long* recvw = (const unsigned long long*)c->dist.ubits.p + c->dist.gather_words + kC1Head;   // (past the own block and a head)
       hipLaunchKernelGGL(k_unpack_shards, dim3((unsigned)std::min<long long>((nt + 255) / 256, 1 << 16)), dim3(256), 0, ln.stream, recvw,
-                         c->gather_words, c->world, (const long long*)c->shard_first.p, p0 * plane, nt, (uint8_t*)c->Uwin.p);
-      c->uwin_first = p0 * plane;
-      c->uwin_n = nt;
-      Uall = (const uint8_t*)c->Uwin.p;
+                         c->dist.gather_words, c->dist.world, (const long long*)c->dist.shard_first.p, p0 * plane, nt, (uint8_t*)c->dist.Uwin.p);
+      c->dist.uwin_first = p0 * plane;
+      c->dist.uwin_n = nt;
+      Uall = (const uint8_t*)c->dist.Uwin.p;
     }
     if ((rc = ensure(ln.dist2, sizeof(double) * (size_t)nt))) return rc;
     if (d > 2 && (rc = ensure(ln.dist2b, sizeof(double) * (size_t)nt))) return rc;
@@ -1606,9 +1606,9 @@ static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
     const double cap_extra = 2.0 * cg.delta + 2.0 * kCoarse * hmax;
     const int last_cnt_ = d >= 2 ? (int)wplanes : 1;
     const int blk_ = last_cnt_ >= 8192 ? 64 : 32;
-    const bool want_bmin = d >= 2 && last_cnt_ >= 4 * blk_ && c->scan_blocks;
+    const bool want_bmin = d >= 2 && last_cnt_ >= 4 * blk_ && c->opt.scan_blocks;
     // 2-D grids: the two axis-0 passes share a launch, and so do the coarse last-axis scan, the minimiser and the block minima
-    const bool paired = d == 2 && coarse_ok && c->set_fuse && count0 <= kAxis0Max && count0 >= 128 && cc0 >= 128;
+    const bool paired = d == 2 && coarse_ok && c->opt.set_fuse && count0 <= kAxis0Max && count0 >= 128 && cc0 >= 128;
     bool bmin_done = false, u16 = false;
     double* din = (double*)ln.dist2.p;
     double* dout = (double*)ln.dist2b.p;
@@ -1628,7 +1628,7 @@ static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
       // the fine image as 16-bit step counts (0xffff: no U point on the line) -- only when its readers are the block minima
       // and the list scan, which decode it: without the list (short last axis, options scan_blocks / scan_waves = 0) the
       // verdict kernel scans the image itself and expects squared distances as doubles
-      u16 = count0 < 65535 && want_bmin && blk_ <= 64 && c->scan_waves;
+      u16 = count0 < 65535 && want_bmin && blk_ <= 64 && c->opt.scan_waves;
       if (u16)
         hipLaunchKernelGGL(k_edt_axis0_pair<true>, dim3((unsigned)(nfine + ncoarse + (fin.pending ? 1 : 0))), dim3(256), 0, ln.stream, Uall,
                            nlines, count0, c->cs.step[0], din, nfine, ncoarse, clines, cc0, c->cs.step[0] * kCoarse, dc0, cg, fin, wave_lines);
@@ -1638,7 +1638,7 @@ static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
       MidJobs<T> j;
       memset(&j, 0, sizeof(j));
       j.sc = sc;
-      j.Lkeys = (const unsigned long long*)c->Lmax.p;
+      j.Lkeys = c->Lmax;
       j.ns = (int)std::min<long long>((nc + 255) / 256, 1 << 16);
       j.dc_in = dc0;
       j.dc_out = dc1;
@@ -1683,7 +1683,7 @@ static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
       for (int a = 1; a < d - 1; ++a) {
         hipLaunchKernelGGL(k_edt_scan, dim3((unsigned)std::min<long long>((nt + 255) / 256, 1 << 20)), dim3(256), 0, ln.stream,
                            (const double*)din, dout, nt, stride, (int)c->cs.count[a], c->cs.step[a],
-                           (const SweepScalars*)sc, cidx, (const unsigned long long*)c->Lmax.p, lidx, 0, 0.0);
+                           (const SweepScalars*)sc, cidx, c->Lmax, lidx, 0, 0.0);
         std::swap(din, dout);
         stride *= c->cs.count[a];
       }
@@ -1701,7 +1701,7 @@ static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
         for (int a = 1; a < d; ++a) {
           hipLaunchKernelGGL(k_edt_scan, dim3((unsigned)std::min<long long>((nc + 255) / 256, 1 << 16)), dim3(256), 0, ln.stream,
                              (const double*)dc0, dc1, nc, cstride, (int)cg.ccount[a], c->cs.step[a] * kCoarse, (const SweepScalars*)sc,
-                             cidx, (const unsigned long long*)c->Lmax.p, lidx, 0, cap_extra);
+                             cidx, c->Lmax, lidx, 0, cap_extra);
           std::swap(dc0, dc1);
           cstride *= cg.ccount[a];
         }
@@ -1723,7 +1723,7 @@ static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
         bmin = (const double*)ln.blockmin.p;
       }
       long long* slist = nullptr;
-      if (bmin && blk <= 64 && c->scan_waves) {
+      if (bmin && blk <= 64 && c->opt.scan_waves) {
         if ((rc = ensure(ln.scanlist, 2 * sizeof(long long) * (size_t)n))) return rc;   // (candidate, ucb) pairs
         slist = (long long*)ln.scanlist.p;
       }
@@ -1743,14 +1743,14 @@ static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
 #define SBO_DECIDE(LIST)                                                                                                            \
   hipLaunchKernelGGL((k_edt_decide<T, LIST>), dgrid, dim3(256), 0, ln.stream, (const double*)din, nl, (int)len0, goff / len0, goff, \
                      d >= 2 ? stride : 1, last_cnt, last_h, d, xscale, mean_c, var_c, (T)o->b, (const uint8_t*)c->maskS.p,          \
-                     (const unsigned long long*)c->Lmax.p, lidx, sc, G, (long long*)ln.amb.p, cg, bmin, blk, slist, rx)
+                     c->Lmax, lidx, sc, G, (long long*)ln.amb.p, cg, bmin, blk, slist, rx)
       // (grids whose lines are whole 8-byte mask words: eight candidates per lane, see k_edt_decide8)
       const bool wide = slist && len0 % 8 == 0 && d >= 2 && cg.enabled && ((uintptr_t)G & 7) == 0 &&
                         ((uintptr_t)c->maskS.p & 7) == 0;
       if (wide) {
         const dim3 g8((unsigned)((len0 / 8 + 255) / 256), (unsigned)std::min<long long>(nl, 65535));
         hipLaunchKernelGGL((k_edt_decide8<T>), g8, dim3(256), 0, ln.stream, nl, (int)len0, goff / len0, goff, d, xscale, mean_c, var_c, (T)o->b,
-                           (const uint8_t*)c->maskS.p, (const unsigned long long*)c->Lmax.p, lidx, sc, G, cg, slist, rx);
+                           (const uint8_t*)c->maskS.p, c->Lmax, lidx, sc, G, cg, slist, rx);
       } else if (slist) SBO_DECIDE(true);
       else SBO_DECIDE(false);
 #undef SBO_DECIDE
@@ -1759,16 +1759,16 @@ static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
       if (slist) {
         // lanes per listed candidate: 16 by default (more candidates in flight beat shorter rounds: 53 k open candidates
         // of config B take 19 us with 16 lanes, 32 us with 32), never more than a wave, 64 for 64-step blocks on request
-        const int gl = c->scan_waves == 8 || c->scan_waves == 32 || c->scan_waves == 64 ? c->scan_waves : 16;
+        const int gl = c->opt.scan_waves == 8 || c->opt.scan_waves == 32 || c->opt.scan_waves == 64 ? c->opt.scan_waves : 16;
 #define SBO_SCAN_LIST(GL)                                                                                                       \
   if (u16)                                                                                                                      \
     hipLaunchKernelGGL((k_edt_scan_list<T, GL, DistU16>), dim3(scan_wgs), dim3(256), 0, ln.stream,                              \
                        DistU16{reinterpret_cast<const unsigned short*>(din), c->cs.step[0]}, goff, stride, last_cnt,            \
-                       last_h, d, xscale, mean_c, var_c, (T)o->b, (const unsigned long long*)c->Lmax.p, lidx, sc, G,            \
+                       last_h, d, xscale, mean_c, var_c, (T)o->b, c->Lmax, lidx, sc, G,            \
                        (long long*)ln.amb.p, bmin, blk, (const long long*)slist, rx);                                           \
   else                                                                                                                          \
   hipLaunchKernelGGL((k_edt_scan_list<T, GL, DistF64>), dim3(scan_wgs), dim3(256), 0, ln.stream, DistF64{(const double*)din, 0.0}, goff, stride, last_cnt, \
-                     last_h, d, xscale, mean_c, var_c, (T)o->b, (const unsigned long long*)c->Lmax.p, lidx, sc, G,              \
+                     last_h, d, xscale, mean_c, var_c, (T)o->b, c->Lmax, lidx, sc, G,              \
                      (long long*)ln.amb.p, bmin, blk, (const long long*)slist, rx)
         switch (gl) {
           case 8: SBO_SCAN_LIST(8); break;
@@ -1833,48 +1833,48 @@ static int sweep_exchange_front(sbo_ctx* c, const sbo_sweep_opts* o, bool need_U
   SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
   if (!multi_rank(c)) return SBO_OK;   // (the radius keys, max over S of ucb_c, come out of k_classify)
   int rc;
-  if (!c->sharded && q > 1 && need_U)
+  if (!c->dist.sharded && q > 1 && need_U)
     return fail(SBO_E_INVALID, "multi-rank sweeps with constraints need sbo_candidates_grid_sharded");
-  if ((rc = ensure(c->xch, sizeof(double) * (size_t)(c->world * kC3Row + 64)))) return rc;
-  unsigned long long* kb = (unsigned long long*)c->xch.p;
+  if ((rc = ensure(c->dist.xch, sizeof(double) * (size_t)(c->dist.world * kC3Row + 64)))) return rc;
+  unsigned long long* kb = (unsigned long long*)c->dist.xch.p;
   if (need_U && q > 1) {
     // C1 + C2 in ONE all-gather: every rank sends [its keys (kC1Head words) | its U mask as bits (one ballot word per 64
     // candidates: 8x fewer bytes on the links than the byte mask)]; the keys are then max-reduced over the gathered heads by
     // a small kernel on every rank -- one collective latency per sweep less than an all-reduce followed by an all-gather.
     long long maxlocal = 0;
-    for (int r = 0; r < c->world; ++r) maxlocal = std::max(maxlocal, c->first_of[r + 1] - c->first_of[r]);
+    for (int r = 0; r < c->dist.world; ++r) maxlocal = std::max(maxlocal, c->dist.first_of[r + 1] - c->dist.first_of[r]);
     const long long words = (maxlocal + 63) / 64, stride = kC1Head + words;
     // (their own buffer: the words are read again per constraint, after GoOSE's weight exchanges have used `gather`)
-    if ((rc = ensure(c->ubits, sizeof(unsigned long long) * (size_t)stride * (c->world + 1)))) return rc;
-    c->gather_words = stride;
-    unsigned long long* sendw = (unsigned long long*)c->ubits.p;
+    if ((rc = ensure(c->dist.ubits, sizeof(unsigned long long) * (size_t)stride * (c->dist.world + 1)))) return rc;
+    c->dist.gather_words = stride;
+    unsigned long long* sendw = (unsigned long long*)c->dist.ubits.p;
     unsigned long long* recvw = sendw + stride;
-    hipLaunchKernelGGL(k_pack_c1, dim3(1), dim3(64), 0, c->stream, (const SweepScalars*)sc, (const unsigned long long*)c->Lmax.p, sendw);
+    hipLaunchKernelGGL(k_pack_c1, dim3(1), dim3(64), 0, c->stream, (const SweepScalars*)sc, c->Lmax, sendw);
     hipLaunchKernelGGL(k_pack_bits, dim3((unsigned)std::min<long long>((words + 3) / 4, 1 << 16)), dim3(256), 0, c->stream,
                        (const uint8_t*)c->maskU.p, c->cs.n_local, words, sendw + kC1Head);
     if ((rc = comm_allgather_bytes(c, sendw, recvw, sizeof(unsigned long long) * (size_t)stride))) return rc;
-    hipLaunchKernelGGL(k_unpack_c1_gathered, dim3(1), dim3(64), 0, c->stream, sc, (unsigned long long*)c->Lmax.p,
-                       (const unsigned long long*)recvw, stride, c->world, kb);
+    hipLaunchKernelGGL(k_unpack_c1_gathered, dim3(1), dim3(64), 0, c->stream, sc, c->Lmax,
+                       (const unsigned long long*)recvw, stride, c->dist.world, kb);
     // (the bits are expanded to bytes per constraint, window only: expander_set)
   } else {
-    hipLaunchKernelGGL(k_pack_c1, dim3(1), dim3(64), 0, c->stream, (const SweepScalars*)sc, (const unsigned long long*)c->Lmax.p, kb);
+    hipLaunchKernelGGL(k_pack_c1, dim3(1), dim3(64), 0, c->stream, (const SweepScalars*)sc, c->Lmax, kb);
     if ((rc = comm_allreduce_max_u64(c, kb, kC1Words))) return rc;
-    hipLaunchKernelGGL(k_unpack_c1, dim3(1), dim3(64), 0, c->stream, sc, (unsigned long long*)c->Lmax.p, (const unsigned long long*)kb);
+    hipLaunchKernelGGL(k_unpack_c1, dim3(1), dim3(64), 0, c->stream, sc, c->Lmax, (const unsigned long long*)kb);
   }
   // the host needs the global L and radius keys to size the halo of the expander transform: the read-back goes to
   // pinned memory and is waited for only where the window is computed (sweep_exchange_wait), so the minimiser kernels are
   // already queued behind it and the GPU does not idle through the round trip
-  SBO_HIP(hipMemcpyAsync(c->h_c1, kb, sizeof(unsigned long long) * (1 + 2 * kMaxQ), hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipMemcpyAsync(c->dist.h_c1, kb, sizeof(unsigned long long) * (1 + 2 * kMaxQ), hipMemcpyDeviceToHost, c->stream));
   SBO_HIP(hipEventRecord(c->ev[5], c->stream));
-  c->c1_pending = true;
+  c->dist.c1_pending = true;
   SBO_HIP(hipGetLastError());
   return SBO_OK;
 }
 
 static int sweep_exchange_wait(sbo_ctx* c) {
-  if (c->c1_pending) {
+  if (c->dist.c1_pending) {
     SBO_HIP(hipEventSynchronize(c->ev[5]));
-    c->c1_pending = false;
+    c->dist.c1_pending = false;
     ++c->host_syncs;
   }
   return SBO_OK;
@@ -1907,20 +1907,20 @@ static int sweep_exchange_back(sbo_ctx* c, SweepScalars& h, const bool* slot_is_
     if (Lk) memcpy(Lk, Lk_pinned, sizeof(unsigned long long) * kMaxQ);
     // decisions the guard band of an approximating posterior leaves open: the classification's and the verdict kernels' count
     // plus what the final reductions found in their slots
-    if (getenv("SBO_DEBUG_GUARD") && c->gb_active) {
+    if (getenv("SBO_DEBUG_GUARD") && c->gb.active) {
       fprintf(stderr, "[guard] device count %lld (classification %lld), slots:", h.n_guard, h.n_guard_cls);
       for (int t = 0; t < kArgSlots; ++t) fprintf(stderr, " %lld", h.guard_slot[t]);
       fprintf(stderr, "\n");
     }
-    if (c->gb_active) for (int t = 0; t < kArgSlots; ++t) h.n_guard += h.guard_slot[t];
+    if (c->gb.active) for (int t = 0; t < kArgSlots; ++t) h.n_guard += h.guard_slot[t];
     else h.n_guard = 0;
     return SBO_OK;
   }
-  double* buf = (double*)c->xch.p + 64;
-  hipLaunchKernelGGL(k_pack_c3, dim3(1), dim3(256), 0, c->stream, (const SweepScalars*)sc, buf, c->world, c->rank);
+  double* buf = (double*)c->dist.xch.p + 64;
+  hipLaunchKernelGGL(k_pack_c3, dim3(1), dim3(256), 0, c->stream, (const SweepScalars*)sc, buf, c->dist.world, c->dist.rank);
   int rc;
-  if ((rc = comm_allreduce_sum_f64(c, buf, c->world * kC3Row))) return rc;
-  std::vector<double> rows((size_t)c->world * kC3Row);
+  if ((rc = comm_allreduce_sum_f64(c, buf, c->dist.world * kC3Row))) return rc;
+  std::vector<double> rows((size_t)c->dist.world * kC3Row);
   SBO_HIP(hipMemcpyAsync(c->h_back, sc, kBack, hipMemcpyDeviceToHost, c->stream));
   SBO_HIP(hipMemcpyAsync(rows.data(), buf, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, c->stream));
   if (done_ev) SBO_HIP(hipEventRecord(done_ev, c->stream));
@@ -1929,13 +1929,13 @@ static int sweep_exchange_back(sbo_ctx* c, SweepScalars& h, const bool* slot_is_
   memset(&h, 0, sizeof(h));
   memcpy(&h, c->h_back, kScalHost);
   if (Lk) memcpy(Lk, Lk_pinned, sizeof(unsigned long long) * kMaxQ);
-  c->c1_pending = false;                       // (the whole stream has drained)
+  c->dist.c1_pending = false;                       // (the whole stream has drained)
   h.count_S = h.count_U = h.count_M = h.n_amb_total = h.n_guard = 0;
   h.halo_short = 0;                            // GLOBAL: a rank that alone reran its set phase would leave the others in a collective
   for (int t = 0; t < kMaxQ; ++t) h.count_set[t] = 0;
   Best merged[kArgSlots];
   for (int t = 0; t < kArgSlots; ++t) merged[t] = slot_is_max[t] ? best_none<true>() : best_none<false>();
-  for (int r = 0; r < c->world; ++r) {
+  for (int r = 0; r < c->dist.world; ++r) {
     const double* row = &rows[(size_t)r * kC3Row];
     for (int t = 0; t < kArgSlots; ++t) {
       const long long idx = (long long)row[kArgSlots + t];
@@ -1952,20 +1952,20 @@ static int sweep_exchange_back(sbo_ctx* c, SweepScalars& h, const bool* slot_is_
     h.halo_short += (long long)row[kC3Halo];
   }
   static const bool dbg_guard = getenv("SBO_DEBUG_GUARD") != nullptr;
-  if (dbg_guard && c->gb_active) {
-    for (int r = 0; r < c->world; ++r) fprintf(stderr, "[guard] rank %d row: counted %g\n", r, rows[(size_t)r * kC3Row + kC3Counts + 4]);
+  if (dbg_guard && c->gb.active) {
+    for (int r = 0; r < c->dist.world; ++r) fprintf(stderr, "[guard] rank %d row: counted %g\n", r, rows[(size_t)r * kC3Row + kC3Counts + 4]);
   }
   for (int t = 0; t < kArgSlots; ++t) {
     h.arg_val[t] = merged[t].i >= 0 ? merged[t].v : 0.0;
     h.arg_idx[t] = merged[t].i;
     h.arg_d[t] = merged[t].d;
-    const bool near = c->gb_active && (slot_is_max[t] ? arg_near<true>(merged[t]) : arg_near<false>(merged[t]));
+    const bool near = c->gb.active && (slot_is_max[t] ? arg_near<true>(merged[t]) : arg_near<false>(merged[t]));
     if (dbg_guard && near)
       fprintf(stderr, "[guard] slot %d near after the merge: v %.17g i %lld d %.3g e1 %.17g e2 %.17g ei %lld\n", t, merged[t].v, merged[t].i, merged[t].d,
               merged[t].e1, merged[t].e2, merged[t].ei);
     if (near) ++h.n_guard;
   }
-  if (!c->gb_active) h.n_guard = 0;
+  if (!c->gb.active) h.n_guard = 0;
   return SBO_OK;
 }
 
@@ -1974,23 +1974,23 @@ static void sweep_times(sbo_ctx* c) {
   (void)hipEventElapsedTime(&te, c->ev[1], c->ev[4]);
   c->prof.set_phase_ms = te;
   c->prof.host_syncs = c->host_syncs;
-  c->prof.comm_bytes = c->comm_bytes;
-  c->prof.comm_calls = c->comm_calls;
-  c->prof.halo_reruns = c->halo_reruns;
-  double cms = c->comm_host_ms;
-  for (int k = 0; k + 1 < c->comm_nev; k += 2) {
+  c->prof.comm_bytes = c->dist.comm_bytes;
+  c->prof.comm_calls = c->dist.comm_calls;
+  c->prof.halo_reruns = c->dist.halo_reruns;
+  double cms = c->dist.comm_host_ms;
+  for (int k = 0; k + 1 < c->dist.comm_nev; k += 2) {
     float t = 0;
-    if (hipEventElapsedTime(&t, c->comm_ev[k], c->comm_ev[k + 1]) == hipSuccess) cms += t;
+    if (hipEventElapsedTime(&t, c->dist.comm_ev[k].e, c->dist.comm_ev[k + 1].e) == hipSuccess) cms += t;
   }
   c->prof.comm_ms = cms;
 }
 static void sweep_comm_reset(sbo_ctx* c) {
-  c->halo_reruns = 0;
+  c->dist.halo_reruns = 0;
   c->host_syncs = 0;
-  c->comm_bytes = 0;
-  c->comm_calls = 0;
-  c->comm_nev = 0;
-  c->comm_host_ms = 0.0;
+  c->dist.comm_bytes = 0;
+  c->dist.comm_calls = 0;
+  c->dist.comm_nev = 0;
+  c->dist.comm_host_ms = 0.0;
 }
 
 enum SweepKind { kSafeOpt = 1, kGoose = 2, kTr = 3 };   // (sbo_ctx::last_sweep)
@@ -2013,7 +2013,7 @@ static int sweep_open(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, Swe
   if (kind == kSafeOpt) {
     // column path (sets_colpath.inc.hpp): a fresh posterior of a one-constraint fp64 model on one rank may deliver the classification
     // as column words (the GEMM posterior decides whether its launch qualifies: PostOutcome::col_active)
-    req.col = !reuse && std::is_same<T, double>::value && q == 2 && !multi_rank(c) && c->result_mirror && n > 0;
+    req.col = !reuse && std::is_same<T, double>::value && q == 2 && !multi_rank(c) && c->opt.result_mirror && n > 0;
     req.col_lean = req.col ? (o->lean >= 2 ? 2 : (o->lean ? 1 : 0)) : 0;
     req.sweep_lean = (o->lean && q >= 2 && !reuse) ? 1 : 0;
   }
@@ -2032,8 +2032,8 @@ static int sweep_profile(sbo_ctx* c, SweepKind kind, bool reuse) {
   int rc;
   float t01 = 0, t12 = 0, t23 = 0, t34 = 0, t0e = 0;
   SBO_HIP(hipEventElapsedTime(&t01, c->ev[0], c->ev[1]));
-  if (c->phase_events || kind == kTr) SBO_HIP(hipEventElapsedTime(&t12, c->ev[1], c->ev[2]));
-  if (c->phase_events && kind != kTr) {
+  if (c->opt.phase_events || kind == kTr) SBO_HIP(hipEventElapsedTime(&t12, c->ev[1], c->ev[2]));
+  if (c->opt.phase_events && kind != kTr) {
     SBO_HIP(hipEventElapsedTime(&t23, c->ev[2], c->ev[3]));
     SBO_HIP(hipEventElapsedTime(&t34, c->ev[3], c->ev[4]));
   }
@@ -2075,7 +2075,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v
   const int nb = reduce_blocks(c);
   // one constraint on one rank: the exhaustive recheck of in-band candidates (almost never any) is launched only when the
   // result block says that something was listed -- one launch (~5 us) less on the common path
-  const bool lazy_exact = c->exact_lazy && q == 2 && !multi_rank(c) && !v.refined && c->result_mirror && n > 0 &&
+  const bool lazy_exact = c->opt.exact_lazy && q == 2 && !multi_rank(c) && !v.refined && c->opt.result_mirror && n > 0 &&
                           whole_planes(c);      // (grids: lists decide every expander exhaustively)
   // partials of the q arg-max reductions side by side: merged by one launch at the end (k_safeopt_finals)
   const size_t pstride = partial_stride(nb);
@@ -2083,7 +2083,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v
   unsigned char* pbase = (unsigned char*)c->partial.p;
   const bool lanes = lanes_on(c);
   {
-    const bool defer = q >= 2 && !multi_rank(c) && c->set_fuse && n > 0 && !lanes;   // (lanes fork right behind the merge)
+    const bool defer = q >= 2 && !multi_rank(c) && c->opt.set_fuse && n > 0 && !lanes;   // (lanes fork right behind the merge)
     if ((rc = sweep_common_front<T>(c, o, v, post, defer ? &mj.fin : nullptr))) return rc;
     if ((rc = sweep_exchange_front<T>(c, o, true))) return rc;
     // (single rank: the minimiser rides in the first constraint's k_set_mid; with ranks > 1 it is queued here, ahead of the
@@ -2092,7 +2092,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v
     mj.nb = nb;
     mj.partial = (Best*)pbase;
     if (q < 2 || multi_rank(c)) launch_minimizer<T>(c, c->lane[0], o, v, &mj);
-    if (c->phase_events) SBO_HIP(hipEventRecord(c->ev[2], c->stream));
+    if (c->opt.phase_events) SBO_HIP(hipEventRecord(c->ev[2], c->stream));
     if (lanes && (rc = lanes_fork(c))) return rc;
     for (int cc = 1; cc < q; ++cc) {
       uint8_t* G = (uint8_t*)c->maskG.p + (size_t)(cc - 1) * n;
@@ -2103,22 +2103,22 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v
     if (lanes && (rc = lanes_join(c))) return rc;
   }
   SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
-  if (c->phase_events) SBO_HIP(hipEventRecord(c->ev[3], c->stream));
+  if (c->opt.phase_events) SBO_HIP(hipEventRecord(c->ev[3], c->stream));
   if (n > 0 && q > 1) {
     hipLaunchKernelGGL((k_arg_masked_multi<T, true, ValArray<T>>), dim3((unsigned)nb, (unsigned)(q - 1)), dim3(256), 0, c->stream,
                        ValArray<T>{(const T*)v.var->p, 0.0}, (const uint8_t*)nullptr, (const uint8_t*)c->maskG.p, n, (long long)c->cs.first, pbase,
                        pstride, 1, gb_of<T>(c, v));
   }
-  const bool mirrored = !multi_rank(c) && c->result_mirror;
+  const bool mirrored = !multi_rank(c) && c->opt.result_mirror;
   hipExtLaunchKernelGGL(k_sweep_finals<true>, dim3((unsigned)q), dim3(256), 0, c->stream, nullptr, mirrored ? c->ev[4] : nullptr, 0,
                         (const unsigned char*)pbase, pstride, n > 0 ? nb : 0, sc,
                         lanes ? (const SweepScalars*)c->lane[1].scal.p : (const SweepScalars*)nullptr,
-                        mirrored ? c->h_back : (unsigned char*)nullptr, (const unsigned long long*)c->Lmax.p, gb_of<T>(c, v) ? 1 : 0);
+                        mirrored ? c->h_back : (unsigned char*)nullptr, c->Lmax, gb_of<T>(c, v) ? 1 : 0);
   SBO_HIP(hipGetLastError());
   bool is_max[kArgSlots];
   for (int t = 0; t < kArgSlots; ++t) is_max[t] = true;
   if ((rc = sweep_exchange_back(c, h, is_max, Lk, c->ev[4], mirrored))) return rc;
-  if (lazy_exact && (h.n_amb > 0 || c->exact_lazy == 2)) {      // (2: always, the test of this path)
+  if (lazy_exact && (h.n_amb > 0 || c->opt.exact_lazy == 2)) {      // (2: always, the test of this path)
     // in-band candidates after all: their exhaustive recheck, then the expanders' arg-max and the finals once more
     const int lidx = o->reference_quirk_L_index ? q - 1 : 1;
     if ((rc = launch_exact_d<T>(c, c->lane[0], o, v, 1, lidx, (uint8_t*)c->maskG.p))) return rc;
@@ -2128,7 +2128,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v
     hipLaunchKernelGGL(k_sweep_clear_slot, dim3(1), dim3(1), 0, c->stream, sc, 1);
     hipExtLaunchKernelGGL(k_sweep_finals<true>, dim3((unsigned)q), dim3(256), 0, c->stream, nullptr, c->ev[4], 0,
                           (const unsigned char*)pbase, pstride, nb, sc, (const SweepScalars*)nullptr, c->h_back,
-                          (const unsigned long long*)c->Lmax.p, gb_of<T>(c, v) ? 1 : 0);
+                          c->Lmax, gb_of<T>(c, v) ? 1 : 0);
     SBO_HIP(hipGetLastError());
     if ((rc = sweep_exchange_back(c, h, is_max, Lk, c->ev[4], true))) return rc;
   }
@@ -2136,10 +2136,10 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v
     if (h.halo_short) {
       // a speculative window was too narrow for this sweep's radii (every rank sees the same keys and the same guess): the set
       // phase again, this time waiting for the keys
-      for (auto& g : c->halo_guess) g = -1;
+      for (auto& g : c->dist.halo_guess) g = -1;
       sbo_sweep_opts o2 = *o;
       o2.posterior_ready = 1;
-      ++c->halo_reruns;
+      ++c->dist.halo_reruns;
       SetView v2 = v;
       v2.halo_rerun = true;
       return sweep_safeopt_t<T>(c, &o2, v2, res);
@@ -2161,7 +2161,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v
   res->count_M = h.count_M;
   res->n_exact_rechecks = h.n_amb_total;
   res->guard_band = h.n_guard;
-  c->guard_first = h.n_guard;
+  c->gb.first = h.n_guard;
   for (int i = 0; i < q; ++i) memcpy(&res->L[i], &Lk[i], 8);
   // (a lean sweep does not report the objective's key: no sweep of the reference reads it -- models/SafeOpt.py:110, GoOSE.py:100 --
   // and K1t / K1i leave its gradient quantities out; zero whichever kernel ran)
@@ -2204,7 +2204,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v
     if (best_c && h.arg_idx[0] >= 0 && h.arg_idx[0] != h.arg_idx[best_c] &&
         std::fabs(h.arg_val[0] - h.arg_val[best_c]) <= h.arg_d[0] + h.arg_d[best_c]) ++near;
     res->guard_band += near;
-    c->guard_first += near;
+    c->gb.first += near;
   }
   return SBO_OK;
 }
@@ -2224,7 +2224,7 @@ static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o,
   const T* var_c = (const T*)v.var->p + (size_t)cidx * n;
   int rc;
   long long maxlocal = n;
-  for (int r = 0; r < c->world && multi_rank(c); ++r) maxlocal = std::max(maxlocal, c->first_of[r + 1] - c->first_of[r]);
+  for (int r = 0; r < c->dist.world && multi_rank(c); ++r) maxlocal = std::max(maxlocal, c->dist.first_of[r + 1] - c->dist.first_of[r]);
   if ((rc = ensure(ln.gw, sizeof(T) * (size_t)std::max<long long>(maxlocal, 1)))) return rc;
   if (n > 0)
     hipLaunchKernelGGL((k_goose_weights<T>), dim3(reduce_blocks(c)), dim3(256), 0, ln.stream, mean_c, var_c, n, (T)o->b, src,
@@ -2251,32 +2251,32 @@ static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o,
     win_p0 = p0;
     win_p1 = p1;
     long long min_planes = planes_total;
-    for (int r = 0; r < c->world; ++r) min_planes = std::min(min_planes, (c->first_of[r + 1] - c->first_of[r]) / plane);
+    for (int r = 0; r < c->dist.world; ++r) min_planes = std::min(min_planes, (c->dist.first_of[r + 1] - c->dist.first_of[r]) / plane);
     if (getenv("SBO_DEBUG_COMM"))
-      fprintf(stderr, "[rank %d] GoOSE sources c=%d: halo %lld planes, smallest shard %lld planes -> %s\n", c->rank, cidx, H, min_planes,
-              (c->sharded && H <= min_planes) ? "slab exchange" : "full all-gather");
-    if (c->sharded && H <= min_planes) {
+      fprintf(stderr, "[rank %d] GoOSE sources c=%d: halo %lld planes, smallest shard %lld planes -> %s\n", c->dist.rank, cidx, H, min_planes,
+              (c->dist.sharded && H <= min_planes) ? "slab exchange" : "full all-gather");
+    if (c->dist.sharded && H <= min_planes) {
       // the halo fits inside the neighbours: every rank contributes only its first and last H planes (2 H plane values
       // instead of its whole shard), and the window is assembled from the previous rank's top slab, the own shard and
       // the next rank's bottom slab
       const size_t slab = (size_t)H * plane;
-      if ((rc = ensure(c->gather, sizeof(T) * slab * 2 * (c->world + 1)))) return rc;
-      if ((rc = ensure(c->Wfull, sizeof(T) * (size_t)(p1 - p0) * plane))) return rc;
-      T* send = (T*)c->gather.p;
+      if ((rc = ensure(c->dist.gather, sizeof(T) * slab * 2 * (c->dist.world + 1)))) return rc;
+      if ((rc = ensure(c->dist.Wfull, sizeof(T) * (size_t)(p1 - p0) * plane))) return rc;
+      T* send = (T*)c->dist.gather.p;
       T* recv = send + 2 * slab;
       SBO_HIP(hipMemcpyAsync(send, ln.gw.p, sizeof(T) * slab, hipMemcpyDeviceToDevice, ln.stream));
       SBO_HIP(hipMemcpyAsync(send + slab, (const T*)ln.gw.p + (size_t)n - slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, ln.stream));
       if ((rc = comm_allgather_bytes(c, send, recv, sizeof(T) * slab * 2))) return rc;
-      T* win = (T*)c->Wfull.p;
+      T* win = (T*)c->dist.Wfull.p;
       size_t at = 0;
       if (own0 > p0) {       // previous rank's top slab (p0 = own0 - H exactly, since H <= its planes)
-        SBO_HIP(hipMemcpyAsync(win, recv + (size_t)(c->rank - 1) * 2 * slab + slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, ln.stream));
+        SBO_HIP(hipMemcpyAsync(win, recv + (size_t)(c->dist.rank - 1) * 2 * slab + slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, ln.stream));
         at = slab;
       }
       SBO_HIP(hipMemcpyAsync(win + at, ln.gw.p, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, ln.stream));
       at += (size_t)n;
       if (p1 > own1)
-        SBO_HIP(hipMemcpyAsync(win + at, recv + (size_t)(c->rank + 1) * 2 * slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, ln.stream));
+        SBO_HIP(hipMemcpyAsync(win + at, recv + (size_t)(c->dist.rank + 1) * 2 * slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, ln.stream));
       css.first = p0 * plane;
       css.n_local = (p1 - p0) * plane;
       W = (const T*)win;
@@ -2285,15 +2285,15 @@ static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o,
       run_hi = (css.n_local + kRun - 1) / kRun;
     } else {
       // wide halo: all-gather the whole weight shards
-      if ((rc = ensure(c->gather, sizeof(T) * (size_t)maxlocal * c->world))) return rc;
-      if ((rc = ensure(c->Wfull, sizeof(T) * (size_t)c->grid_total))) return rc;
-      if ((rc = comm_allgather_bytes(c, ln.gw.p, c->gather.p, sizeof(T) * (size_t)maxlocal))) return rc;
-      hipLaunchKernelGGL(k_compact_shards<T>, dim3((unsigned)std::min<long long>((c->grid_total + 255) / 256, 1 << 16)), dim3(256), 0,
-                         ln.stream, (const T*)c->gather.p, maxlocal, c->world, (const long long*)c->shard_first.p, c->grid_total,
-                         (T*)c->Wfull.p);
+      if ((rc = ensure(c->dist.gather, sizeof(T) * (size_t)maxlocal * c->dist.world))) return rc;
+      if ((rc = ensure(c->dist.Wfull, sizeof(T) * (size_t)c->dist.grid_total))) return rc;
+      if ((rc = comm_allgather_bytes(c, ln.gw.p, c->dist.gather.p, sizeof(T) * (size_t)maxlocal))) return rc;
+      hipLaunchKernelGGL(k_compact_shards<T>, dim3((unsigned)std::min<long long>((c->dist.grid_total + 255) / 256, 1 << 16)), dim3(256), 0,
+                         ln.stream, (const T*)c->dist.gather.p, maxlocal, c->dist.world, (const long long*)c->dist.shard_first.p, c->dist.grid_total,
+                         (T*)c->dist.Wfull.p);
       css.first = 0;
-      css.n_local = c->grid_total;
-      W = (const T*)c->Wfull.p;
+      css.n_local = c->dist.grid_total;
+      W = (const T*)c->dist.Wfull.p;
       run_lo = p0 * plane / kRun;
       run_hi = (p1 * plane + kRun - 1) / kRun;
     }
@@ -2301,7 +2301,7 @@ static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o,
   if (n == 0) return SBO_OK;           // (an empty shard still took part in the all-gather)
   long long plane1;
   const bool plane_aligned = whole_planes(c, &plane1);
-  if (plane_aligned && !c->goose_pairs) {
+  if (plane_aligned && !c->opt.goose_pairs) {
     // grids: power-distance transform of the source weights over the window, verdict by sign, exact recheck in the band
     const int d = c->cs.d;
     SweepScalars* sc = (SweepScalars*)ln.scal.p;
@@ -2338,12 +2338,12 @@ static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o,
       double* hi0 = lo1 + nc;
       double* hi1 = hi0 + nc;
       hipLaunchKernelGGL((k_pdt_cell_min<T>), dim3((unsigned)std::min<long long>((nc * 8 + 255) / 256, 1 << 18)), dim3(256), 0, ln.stream, Wwin, cg, nc,
-                         (const unsigned long long*)c->Lmax.p, lidx, lo0, hi0);
+                         c->Lmax, lidx, lo0, hi0);
       long long cstride = 1;
       for (int a = 0; a < d; ++a) {
         hipLaunchKernelGGL(k_pdt_coarse_scan, dim3((unsigned)std::min<long long>((2 * nc * 8 + 255) / 256, 1 << 18)), dim3(256), 0, ln.stream, (const double*)lo0, lo1, (const double*)hi0,
                            hi1, nc, cstride, (int)cg.ccount[a], c->cs.step[a], (const SweepScalars*)sc, cidx,
-                           (const unsigned long long*)c->Lmax.p, lidx, d, xscale);
+                           c->Lmax, lidx, d, xscale);
         std::swap(lo0, lo1);
         std::swap(hi0, hi1);
         cstride *= cg.ccount[a];
@@ -2353,16 +2353,16 @@ static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o,
     }
     const T* wbmax = nullptr;
     const int blk0 = 32;
-    if (c->scan_blocks && count0 >= 16 * blk0 && count0 <= 8192 && nt / count0 >= 1024) {
+    if (c->opt.scan_blocks && count0 >= 16 * blk0 && count0 <= 8192 && nt / count0 >= 1024) {
       // one workgroup per line, the line in LDS (pays once there are enough lines to fill the chip: from 1024 lines on --
       // config C's 1024 x 1024 grid of the Williams-Otto plant: 33 -> 19 us per constraint against the thread-per-position kernel)
       const size_t lds = sizeof(double) * ((size_t)count0 + (count0 + kAnchor - 1) / kAnchor) + sizeof(int) * 2 * ((size_t)(count0 + kAnchor - 1) / kAnchor + 2);
       SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pdt_axis0_lds<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       hipLaunchKernelGGL((k_pdt_axis0_lds<T>), dim3((unsigned)std::min<long long>(nt / count0, 1 << 16)), dim3(256), lds, ln.stream, Wwin,
-                         nt / count0, count0, c->cs.step[0], (const SweepScalars*)sc, cidx, (const unsigned long long*)c->Lmax.p, lidx, d,
+                         nt / count0, count0, c->cs.step[0], (const SweepScalars*)sc, cidx, c->Lmax, lidx, d,
                          xscale, cg, pc_lo, blk0, (double*)ln.dist2.p);
     } else {
-      if (c->scan_blocks && count0 >= 16 * blk0) {
+      if (c->opt.scan_blocks && count0 >= 16 * blk0) {
         const long long nbw = (nt / count0) * ((count0 + blk0 - 1) / blk0);
         if ((rc = ensure(ln.blockmax, sizeof(T) * (size_t)nbw))) return rc;
         hipLaunchKernelGGL((k_block_max_w<T>), dim3((unsigned)std::min<long long>((nbw + 255) / 256, 1 << 20)), dim3(256), 0, ln.stream,
@@ -2370,7 +2370,7 @@ static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o,
         wbmax = (const T*)ln.blockmax.p;
       }
       hipLaunchKernelGGL((k_pdt_axis0<T>), dim3(gridn), dim3(256), 0, ln.stream, Wwin, nt, count0, c->cs.step[0],
-                         (const SweepScalars*)sc, cidx, (const unsigned long long*)c->Lmax.p, lidx, d, xscale, cg, pc_lo, wbmax,
+                         (const SweepScalars*)sc, cidx, c->Lmax, lidx, d, xscale, cg, pc_lo, wbmax,
                          blk0, (double*)ln.dist2.p);
     }
     double* pin = (double*)ln.dist2.p;
@@ -2379,7 +2379,7 @@ static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o,
     for (int a = 1; a < d - 1; ++a) {
       hipLaunchKernelGGL(k_pdt_scan, dim3(gridn), dim3(256), 0, ln.stream, (const double*)pin, pout, nt, stride,
                          (int)c->cs.count[a], c->cs.step[a], (const SweepScalars*)sc, cidx,
-                         (const unsigned long long*)c->Lmax.p, lidx, d, xscale);
+                         c->Lmax, lidx, d, xscale);
       std::swap(pin, pout);
       stride *= c->cs.count[a];
     }
@@ -2387,7 +2387,7 @@ static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o,
     const double last_h = d >= 2 ? c->cs.step[d - 1] : 0.0;
     const double* bmin = nullptr;
     const int blk = last_cnt >= 8192 ? 64 : 32;
-    if (d >= 2 && last_cnt >= 4 * blk && c->scan_blocks) {
+    if (d >= 2 && last_cnt >= 4 * blk && c->opt.scan_blocks) {
       const long long nb_ = (long long)((last_cnt + blk - 1) / blk) * stride;
       if ((rc = ensure(ln.blockmin, sizeof(double) * (size_t)nb_))) return rc;
       hipLaunchKernelGGL(k_block_min, dim3((unsigned)std::min<long long>((stride + 63) / 64 * ((last_cnt + blk - 1) / blk), 1 << 20)), dim3(256), 0, ln.stream,
@@ -2396,26 +2396,26 @@ static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o,
     }
     const long long len0 = d >= 2 ? count0 : n, nl = n / len0;    // positions per line / local lines
     long long* slist = nullptr;                    // open points of the verdict: listed and scanned by groups of lanes
-    if (bmin && blk <= 64 && c->scan_waves) {
+    if (bmin && blk <= 64 && c->opt.scan_waves) {
       if ((rc = ensure(ln.scanlist, sizeof(long long) * (size_t)n))) return rc;
       slist = (long long*)ln.scanlist.p;
     }
     hipLaunchKernelGGL(k_pdt_decide, dim3((unsigned)((len0 + 255) / 256), (unsigned)std::min<long long>((nl + kDecideLines - 1) / kDecideLines, 65535)),
                        dim3(256), 0, ln.stream, (const double*)pin, nl, (int)len0, goff / len0, goff, d >= 2 ? stride : 1, last_cnt, last_h, d,
-                       xscale, (const uint8_t*)c->maskU.p, (const unsigned long long*)c->Lmax.p, lidx, sc, cidx, O, (long long*)ln.amb.p, cg,
+                       xscale, (const uint8_t*)c->maskU.p, c->Lmax, lidx, sc, cidx, O, (long long*)ln.amb.p, cg,
                        pc_lo, pc_hi, bmin, blk, slist);
     if (slist) {
-      if (c->scan_waves == 32 || c->scan_waves == 64)
+      if (c->opt.scan_waves == 32 || c->opt.scan_waves == 64)
         hipLaunchKernelGGL((k_pdt_scan_list<32>), dim3(2048), dim3(256), 0, ln.stream, (const double*)pin, goff, stride, last_cnt, last_h, d,
-                           xscale, (const unsigned long long*)c->Lmax.p, lidx, sc, cidx, O, (long long*)ln.amb.p, bmin, blk,
+                           xscale, c->Lmax, lidx, sc, cidx, O, (long long*)ln.amb.p, bmin, blk,
                            (const long long*)slist);
       else
         hipLaunchKernelGGL((k_pdt_scan_list<16>), dim3(2048), dim3(256), 0, ln.stream, (const double*)pin, goff, stride, last_cnt, last_h, d,
-                           xscale, (const unsigned long long*)c->Lmax.p, lidx, sc, cidx, O, (long long*)ln.amb.p, bmin, blk,
+                           xscale, c->Lmax, lidx, sc, cidx, O, (long long*)ln.amb.p, bmin, blk,
                            (const long long*)slist);
     }
     hipLaunchKernelGGL((k_goose_exact<T, D>), dim3(1024), dim3(256), 0, ln.stream, c->cs, css, W,
-                       (const unsigned long long*)c->Lmax.p, lidx, sc, cidx, (const long long*)ln.amb.p, O,
+                       c->Lmax, lidx, sc, cidx, (const long long*)ln.amb.p, O,
                        (gb_of<T>(c, v) && !v.refined && v.band == SetBand::plan) ? 1 : 0);
     SBO_HIP(hipGetLastError());
     return SBO_OK;
@@ -2440,18 +2440,18 @@ static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o,
     csx.pts = c->lx.xs.p;
     csx.pts_dtype = SBO_F64;
     hipLaunchKernelGGL((k_goose_run_meta<T, D>), dim3((unsigned)nsrc_runs), dim3(256), 0, ln.stream, csx, (const T*)Ws,
-                       (const unsigned long long*)c->Lmax.p, lidx, 0ll, (RunMeta*)ln.runmeta.p);
+                       c->Lmax, lidx, 0ll, (RunMeta*)ln.runmeta.p);
     hipLaunchKernelGGL((k_goose_optimistic<T, D>), dim3((unsigned)((n + kRun - 1) / kRun)), dim3(256), 0, ln.stream, csx, csx, (const T*)Ws,
-                       (const uint8_t*)Us, (const unsigned long long*)c->Lmax.p, lidx, (const RunMeta*)ln.runmeta.p, 0ll,
+                       (const uint8_t*)Us, c->Lmax, lidx, (const RunMeta*)ln.runmeta.p, 0ll,
                        (int)nsrc_runs, Os);
     hipLaunchKernelGGL(k_idx_scatter_u8, dim3(gb), dim3(256), 0, ln.stream, (const uint8_t*)Os, perm, n, O);
     SBO_HIP(hipGetLastError());
     return SBO_OK;
   }
   hipLaunchKernelGGL((k_goose_run_meta<T, D>), dim3((unsigned)nsrc_runs), dim3(256), 0, ln.stream, css, W,
-                     (const unsigned long long*)c->Lmax.p, lidx, run_lo, (RunMeta*)ln.runmeta.p);
+                     c->Lmax, lidx, run_lo, (RunMeta*)ln.runmeta.p);
   hipLaunchKernelGGL((k_goose_optimistic<T, D>), dim3((unsigned)((n + kRun - 1) / kRun)), dim3(256), 0, ln.stream, c->cs, css, W,
-                     (const uint8_t*)c->maskU.p, (const unsigned long long*)c->Lmax.p, lidx, (const RunMeta*)ln.runmeta.p,
+                     (const uint8_t*)c->maskU.p, c->Lmax, lidx, (const RunMeta*)ln.runmeta.p,
                      run_lo, (int)nsrc_runs, O);
   SBO_HIP(hipGetLastError());
   return SBO_OK;
@@ -2505,7 +2505,7 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
     if ((rc = sweep_common_front<T>(c, o, v, post, nullptr))) return rc;
     if ((rc = sweep_exchange_front<T>(c, o, true))) return rc;
     if ((rc = ensure(c->maskO, (size_t)std::max<long long>(n, 1) * std::max(1, q - 1)))) return rc;
-    if (c->phase_events) SBO_HIP(hipEventRecord(c->ev[2], c->stream));
+    if (c->opt.phase_events) SBO_HIP(hipEventRecord(c->ev[2], c->stream));
     // Only expanders can cover an unsafe point: "g covers h" is the predicate that puts g into G_c.  So G_c is built
     // first (distance transform, cheap) and serves as the source set of the coverage search instead of all of S_t.
     if ((rc = ensure(c->maskG, (size_t)std::max<long long>(n, 1) * std::max(1, q - 1)))) return rc;
@@ -2526,7 +2526,7 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
     if (lanes && (rc = lanes_join(c))) return rc;
   }
   SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
-  if (c->phase_events) SBO_HIP(hipEventRecord(c->ev[3], c->stream));
+  if (c->opt.phase_events) SBO_HIP(hipEventRecord(c->ev[3], c->stream));
   // arg-min of lcb_0 over S_t and over every O_c: the bound is computed for the masked candidates only; one launch, the q
   // reductions side by side
   const ValLcb<T> lcb0{(const T*)v.mean->p, (const T*)v.var->p, (T)o->b, 0.0, 0.0};
@@ -2545,7 +2545,7 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   double* dev_t = (double*)c->lane[0].scal.p + 256;
   // (one rank: the finals and the target choice in one launch, the last merge writes the host's block itself)
   const int gbon = gb_of<T>(c, v) ? 1 : 0;
-  const bool short_tail = fused_explore && c->result_mirror && (c->mc.dpad == 2 || c->mc.dpad == 4 || c->mc.dpad == 8);
+  const bool short_tail = fused_explore && c->opt.result_mirror && (c->mc.dpad == 2 || c->mc.dpad == 4 || c->mc.dpad == 8);
   const SweepScalars* l1 = lanes ? (const SweepScalars*)c->lane[1].scal.p : (const SweepScalars*)nullptr;
   if (short_tail) {
     switch (c->mc.dpad) {
@@ -2555,7 +2555,7 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
     }
     if (n > 0) launch_argmin_dist<T>(c, dev_t, nb);
     hipExtLaunchKernelGGL(k_arg_final_mirror, dim3(1), dim3(256), 0, c->stream, nullptr, c->ev[4], 0, (const Best*)c->partial.p, n > 0 ? nb : 0, sc,
-                          kArgSlots - 1, c->h_back, (const unsigned long long*)c->Lmax.p, 0);
+                          kArgSlots - 1, c->h_back, c->Lmax, 0);
     SBO_HIP(hipGetLastError());
   } else {
     hipLaunchKernelGGL(k_sweep_finals<false>, dim3((unsigned)q), dim3(256), 0, c->stream, (const unsigned char*)pbase, pstride,
@@ -2578,10 +2578,10 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   if ((rc = sweep_exchange_back(c, h, is_max, Lk, short_tail ? c->ev[4] : nullptr, short_tail))) return rc;
   if (multi_rank(c)) {
     if (h.halo_short) {                     // (see sweep_safeopt_t)
-      for (auto& g : c->halo_guess) g = -1;
+      for (auto& g : c->dist.halo_guess) g = -1;
       sbo_sweep_opts o2 = *o;
       o2.posterior_ready = 1;
-      ++c->halo_reruns;
+      ++c->dist.halo_reruns;
       SetView v2 = v;
       v2.halo_rerun = true;
       return sweep_goose_t<T>(c, &o2, v2, res);
@@ -2596,7 +2596,7 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   res->count_U = h.count_U;
   res->n_exact_rechecks = h.n_amb_total;
   res->guard_band = h.n_guard;
-  c->guard_first = h.n_guard;
+  c->gb.first = h.n_guard;
   for (int i = 0; i < q; ++i) memcpy(&res->L[i], &Lk[i], 8);
   res->safe_min_index = res->target_index = res->explore_index = -1;
   for (int cc = 1; cc < q; ++cc) res->target_index_c[cc - 1] = -1;
@@ -2628,7 +2628,7 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
           !(h.arg_val[cc] - h.arg_d[cc] > h.arg_val[best_c] + h.arg_d[best_c])) ++near;
     if (h.arg_idx[0] >= 0 && std::fabs(h.arg_val[0] - h.arg_val[best_c]) <= h.arg_d[0] + h.arg_d[best_c]) ++near;
     res->guard_band += near;
-    c->guard_first += near;
+    c->gb.first += near;
   }
   if (best_c) {
     res->target_index = res->target_index_c[best_c - 1];
@@ -2686,7 +2686,7 @@ static int sweep_tr_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, con
   bool is_max[kArgSlots];
   for (int t = 0; t < kArgSlots; ++t) is_max[t] = false;
   if (multi_rank(c)) {
-    if ((rc = ensure(c->xch, sizeof(double) * (size_t)(c->world * kC3Row + 64)))) return rc;
+    if ((rc = ensure(c->dist.xch, sizeof(double) * (size_t)(c->dist.world * kC3Row + 64)))) return rc;
   }
   if ((rc = sweep_exchange_back(c, h, is_max))) return rc;
   SBO_HIP(hipEventRecord(c->ev[2], c->stream));
@@ -2696,7 +2696,7 @@ static int sweep_tr_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, con
   if ((rc = sweep_profile(c, kTr, reuse))) return rc;
   memset(res, 0, sizeof(*res));
   res->guard_band = h.n_guard;
-  c->guard_first = h.n_guard;
+  c->gb.first = h.n_guard;
   res->count_S = h.count_S;
   res->count_T = h.count_M;
   res->index = h.arg_idx[0];
@@ -2760,12 +2760,12 @@ template <typename Res, typename Plain, typename Recheck>
 static int sweep_dispatch(sbo_ctx* c, Res* result, bool drain, Plain plain, Recheck recheck) {
   const auto done = [](int rc) { return rc == SBO_OK || rc == SBO_E_EMPTY_SAFE_SET; };
   const bool f64 = c->dtype == SBO_F64;
-  c->guard_first = 0;
+  c->gb.first = 0;
   int rc;
-  if (!f64 && c->fp64_recheck && c->shadow && c->shadow->has_model) rc = recheck(0.0f);
+  if (!f64 && c->opt.fp64_recheck && c->recheck.shadow && c->recheck.shadow->has_model) rc = recheck(0.0f);
   else rc = f64 ? plain(0.0) : plain(0.0f);
-  if (done(rc) && f64 && resident_band(c) && (c->guard_first > 0 || c->guard_band == 2)) {
-    const long long first = c->guard_first;
+  if (done(rc) && f64 && resident_band(c) && (c->gb.first > 0 || c->opt.guard_band == 2)) {
+    const long long first = c->gb.first;
     rc = recheck(0.0);
     if (done(rc)) result->guard_band = first;
   }
@@ -2815,7 +2815,7 @@ int sbo_explore_safeset(sbo_ctx* c, const double* target, int64_t* index_out, do
   if ((rc = ensure(c->lane[0].scal, sizeof(SweepScalars)))) return rc;
   const int nb = reduce_blocks(c);
   if ((rc = ensure(c->partial, partial_stride(nb)))) return rc;
-  if (c->masks_bits && n > 0) col_expand(c, c->cbS, (uint8_t*)c->maskS.p);
+  if (c->col.masks_bits && n > 0) col_expand(c, c->col.S, (uint8_t*)c->maskS.p);
   SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
   double* dev_t = (double*)c->lane[0].scal.p + 256;
   double t8[SBO_MAX_D] = {0};
@@ -2831,7 +2831,7 @@ int sbo_explore_safeset(sbo_ctx* c, const double* target, int64_t* index_out, do
   SweepScalars h;
   bool is_max[kArgSlots];
   for (int t = 0; t < kArgSlots; ++t) is_max[t] = false;
-  if (multi_rank(c) && (rc = ensure(c->xch, sizeof(double) * (size_t)(c->world * kC3Row + 64)))) return rc;
+  if (multi_rank(c) && (rc = ensure(c->dist.xch, sizeof(double) * (size_t)(c->dist.world * kC3Row + 64)))) return rc;
   if ((rc = sweep_exchange_back(c, h, is_max))) return rc;
   *index_out = h.arg_idx[kArgSlots - 1];
   if (x_out) coords_of(c, h.arg_idx[kArgSlots - 1], x_out);
@@ -2842,13 +2842,13 @@ int sbo_masks_get(sbo_ctx* c, int which, int cidx, uint8_t* out) {
   if (!c || !out) return fail(SBO_E_INVALID, "NULL argument");
   if (!c->masks_valid) return fail(SBO_E_INVALID, "no sweep has produced masks on these candidates");
   const long long n = c->cs.n_local;
-  if (c->masks_bits && n > 0) {
+  if (c->col.masks_bits && n > 0) {
     // the last sweep ran on column words (sets_colpath.inc.hpp): the byte form of the mask asked for is made here
     SBO_HIP(hipSetDevice(c->device));
-    if (which == SBO_MASK_S) col_expand(c, c->cbS, (uint8_t*)c->maskS.p);
-    else if (which == SBO_MASK_U) col_expand(c, c->cbU, (uint8_t*)c->maskU.p);
-    else if (which == SBO_MASK_M) col_expand(c, c->cbM, (uint8_t*)c->maskM.p);
-    else if (which == SBO_MASK_G && cidx == 1 && !c->col_G_bytes) col_expand(c, c->cbG, (uint8_t*)c->maskG.p);
+    if (which == SBO_MASK_S) col_expand(c, c->col.S, (uint8_t*)c->maskS.p);
+    else if (which == SBO_MASK_U) col_expand(c, c->col.U, (uint8_t*)c->maskU.p);
+    else if (which == SBO_MASK_M) col_expand(c, c->col.M, (uint8_t*)c->maskM.p);
+    else if (which == SBO_MASK_G && cidx == 1 && !c->col.G_bytes) col_expand(c, c->col.G, (uint8_t*)c->maskG.p);
     SBO_HIP(hipGetLastError());
   }
   const void* src = nullptr;

@@ -1051,14 +1051,14 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   SweepScalars* sc = (SweepScalars*)ln.scal.p;
   // (their own small block: the objective's scalars, the finals' tickets and intermediate rows)
   static_assert(128 + 2 * kColFinParts * sizeof(ColFinRow) <= 4096, "column path scalar block");
-  const bool fresh_fin = c->col_fin.bytes < 4096;
-  if ((rc = ensure(c->col_fin, 4096))) return rc;
-  ColScal2* sc2 = (ColScal2*)c->col_fin.p;
-  unsigned long long* tickets = (unsigned long long*)((char*)c->col_fin.p + 64);
-  ColFinRow* fin = (ColFinRow*)((char*)c->col_fin.p + 128);
-  const bool overlap = c->col_overlap && c->stream3 && post.col_forked;
+  const bool fresh_fin = c->col.fin.bytes < 4096;
+  if ((rc = ensure(c->col.fin, 4096))) return rc;
+  ColScal2* sc2 = (ColScal2*)c->col.fin.p;
+  unsigned long long* tickets = (unsigned long long*)((char*)c->col.fin.p + 64);
+  ColFinRow* fin = (ColFinRow*)((char*)c->col.fin.p + 128);
+  const bool overlap = c->opt.col_overlap && c->stream3 && post.col_forked;
   hipStream_t xs = c->stream, es = overlap ? c->stream3 : c->stream;      // objective chain / expander chain
-  if (fresh_fin) SBO_HIP(hipMemsetAsync(c->col_fin.p, 0, 4096, es));       // (tickets: the last workgroup of a slot resets its own)
+  if (fresh_fin) SBO_HIP(hipMemsetAsync(c->col.fin.p, 0, 4096, es));       // (tickets: the last workgroup of a slot resets its own)
   const int nb = reduce_blocks(c);
   // partial regions: slot 0 (the minimiser, nb rows) in the layout of the byte-mask path -- its late exhaustive recheck merges
   // slots 0 / 1 from there --, the rows of the arg-max over G_1 (nb) behind both
@@ -1071,22 +1071,22 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   Best* reg1 = (Best*)(pbase + 2 * pstride);
   if ((rc = ensure(ln.amb, sizeof(long long) * (size_t)n))) return rc;
   if ((rc = ensure(ln.scanlist, 2 * sizeof(long long) * (size_t)n))) return rc;
-  if ((rc = ensure(c->col_img, sizeof(unsigned short) * (size_t)n + 64))) return rc;
-  if ((rc = ensure(c->col_bmin, sizeof(unsigned short) * (size_t)gm.H * gm.NBp + 64))) return rc;
+  if ((rc = ensure(c->col.img, sizeof(unsigned short) * (size_t)n + 64))) return rc;
+  if ((rc = ensure(c->col.bmin, sizeof(unsigned short) * (size_t)gm.H * gm.NBp + 64))) return rc;
   // coarse column image / block minima (rows padded to whole 64-row coarse segments; block-minimum entries beyond the row stay 0xffff)
   const int crows = ((gm.CH + 63) / 64) * 64;
   const size_t cimg_bytes = sizeof(unsigned short) * (size_t)crows * gm.CWp + 64, cbmin_bytes = sizeof(unsigned short) * (size_t)crows * gm.CNBp + 64;
-  const bool fresh_c = c->col_cbmin.bytes < cbmin_bytes || c->col_ckey != ((long long)gm.W << 32 | gm.H);
-  if ((rc = ensure(c->col_cimg, cimg_bytes)) || (rc = ensure(c->col_cbmin, cbmin_bytes))) return rc;
+  const bool fresh_c = c->col.cbmin.bytes < cbmin_bytes || c->col.ckey != ((long long)gm.W << 32 | gm.H);
+  if ((rc = ensure(c->col.cimg, cimg_bytes)) || (rc = ensure(c->col.cbmin, cbmin_bytes))) return rc;
   if (fresh_c) {
-    SBO_HIP(hipMemsetAsync(c->col_cbmin.p, 0xff, c->col_cbmin.bytes, es));
-    c->col_ckey = (long long)gm.W << 32 | gm.H;
+    SBO_HIP(hipMemsetAsync(c->col.cbmin.p, 0xff, c->col.cbmin.bytes, es));
+    c->col.ckey = (long long)gm.W << 32 | gm.H;
   }
-  ColBits cb{(unsigned long long*)c->cbS.p, (unsigned long long*)c->cbU.p, (unsigned long long*)c->cbUsum.p, (unsigned long long*)c->col_slots.p};
+  ColBits cb{(unsigned long long*)c->col.S.p, (unsigned long long*)c->col.U.p, (unsigned long long*)c->col.Usum.p, (unsigned long long*)c->col.slots.p};
   // (the Lipschitz keys come out of the slot block: the posterior's partial rows are not merged)
 
   // ---- expander chain
-  if (overlap) SBO_HIP(hipStreamWaitEvent(es, c->ev_col[0], 0));
+  if (overlap) SBO_HIP(hipStreamWaitEvent(es, c->col.ev[0], 0));
   // (K1i's deferred gradient launch merges the Lipschitz keys into the slot block on stream3: in stream order ahead of this chain when
   // the chain runs there, an event otherwise)
   if (c->grad_pending && es != c->stream3) SBO_HIP(hipStreamWaitEvent(es, c->ev_grad[2], 0));
@@ -1094,35 +1094,35 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   ColMergeJob mg;
   mg.slots = cb.slots;
   mg.sc = sc;
-  mg.Lmax = (unsigned long long*)c->Lmax.p;
+  mg.Lmax = c->Lmax;
   mg.gb = gb_of<double>(c, v);
   mg.b = o->b;
   const int ncoarse = gm.CNB;
   const int nfine = (int)std::max<long long>(1, std::min<long long>(((long long)gm.NS * (gm.W / 64) + 3) / 4, (long long)c->n_cu * 5));
-  // (overlapped: the launch carries ev_col[2] as its stop event -- it clears the M words the minimiser's M part fills on the main stream)
-  hipExtLaunchKernelGGL(k_col_a, dim3((unsigned)(1 + ncoarse + nfine)), dim3(256), 0, es, nullptr, overlap ? c->ev_col[2] : nullptr, 0, gm, cb, mg, ncoarse,
-                        (unsigned short*)c->col_cimg.p, (unsigned short*)c->col_cbmin.p, (unsigned short*)c->col_img.p, (unsigned short*)c->col_bmin.p,
-                        (unsigned long long*)c->cbM.p, (unsigned long long*)c->cbG.p);
-  c->usum_dirty = false;
+  // (overlapped: the launch carries col.ev[2] as its stop event -- it clears the M words the minimiser's M part fills on the main stream)
+  hipExtLaunchKernelGGL(k_col_a, dim3((unsigned)(1 + ncoarse + nfine)), dim3(256), 0, es, nullptr, overlap ? c->col.ev[2] : nullptr, 0, gm, cb, mg, ncoarse,
+                        (unsigned short*)c->col.cimg.p, (unsigned short*)c->col.cbmin.p, (unsigned short*)c->col.img.p, (unsigned short*)c->col.bmin.p,
+                        (unsigned long long*)c->col.M.p, (unsigned long long*)c->col.G.p);
+  c->col.usum_dirty = false;
   // ---- objective chain, M part: behind the objective's posterior launch on the main stream and behind k_col_a, beside the rest of the
   // expander chain (one stream: in order between k_col_a and k_col_decide)
   ColMinJob j;
   memset(&j, 0, sizeof(j));
   j.gm = gm;
   j.slots = cb.slots;
-  j.Lmax = (unsigned long long*)c->Lmax.p;
+  j.Lmax = c->Lmax;
   j.sc2 = sc2;
   j.olmin = (const unsigned long long*)c->cpart.p + (size_t)1 * c->cpart_cap + post.fuse_rows / 2;
   j.Sw = cb.Sw;
   j.mean0 = (const double*)v.mean->p;
   j.var0 = (const double*)v.var->p;
   j.b = o->b;
-  j.Mw = (unsigned long long*)c->cbM.p;
-  j.Gw = (const unsigned long long*)c->cbG.p;
+  j.Mw = (unsigned long long*)c->col.M.p;
+  j.Gw = (const unsigned long long*)c->col.G.p;
   j.partial = reg0;
   j.gpartial = reg1;
   j.gb = gb_of<double>(c, v);
-  if (overlap) SBO_HIP(hipStreamWaitEvent(xs, c->ev_col[2], 0));
+  if (overlap) SBO_HIP(hipStreamWaitEvent(xs, c->col.ev[2], 0));
   hipLaunchKernelGGL(k_col_min<0>, dim3((unsigned)nb), dim3(256), 0, xs, j);
   ColVerdict cv;
   memset(&cv, 0, sizeof(cv));
@@ -1130,7 +1130,7 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   cv.var_c = (const double*)v.var->p + (size_t)n;
   cv.var0 = (const double*)v.var->p;
   cv.b = o->b;
-  cv.Lkeys = (const unsigned long long*)c->Lmax.p;
+  cv.Lkeys = c->Lmax;
   cv.lidx = lidx;
   double xscale = 0.0;
   for (int a = 0; a < 2; ++a) xscale = std::max(xscale, std::max(std::fabs(c->cs.lo[a]), std::fabs(c->cs.hi[a])));
@@ -1142,43 +1142,43 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   const int ndw = std::max(1, c->n_cu * 4);
   const unsigned long long* rows = (const unsigned long long*)c->cpart.p;        // the posterior's partial rows: constraint tiles, then objective tiles
   hipLaunchKernelGGL(k_col_decide, dim3((unsigned)ndw), dim3(256), 0, es, gm, (const unsigned long long*)cb.Sw, (const unsigned long long*)cb.slots,
-                     rows, rows + (size_t)(kRowRmax + 1) * c->cpart_cap, (const unsigned short*)c->col_cimg.p, (const unsigned short*)c->col_cbmin.p,
-                     2.0 * gm.delta + 2.0 * kCoarse * hmax, cb.Usum, (const unsigned short*)c->col_img.p, cv, sc, (unsigned long long*)c->cbG.p, (long long*)ln.scanlist.p);
-  hipLaunchKernelGGL(k_col_scan, dim3((unsigned)nsc), dim3(256), 0, es, gm, (const unsigned short*)c->col_img.p, (const unsigned short*)c->col_bmin.p,
-                     cv, sc, (unsigned long long*)c->cbG.p, (long long*)ln.amb.p, (const long long*)ln.scanlist.p);
+                     rows, rows + (size_t)(kRowRmax + 1) * c->cpart_cap, (const unsigned short*)c->col.cimg.p, (const unsigned short*)c->col.cbmin.p,
+                     2.0 * gm.delta + 2.0 * kCoarse * hmax, cb.Usum, (const unsigned short*)c->col.img.p, cv, sc, (unsigned long long*)c->col.G.p, (long long*)ln.scanlist.p);
+  hipLaunchKernelGGL(k_col_scan, dim3((unsigned)nsc), dim3(256), 0, es, gm, (const unsigned short*)c->col.img.p, (const unsigned short*)c->col.bmin.p,
+                     cv, sc, (unsigned long long*)c->col.G.p, (long long*)ln.amb.p, (const long long*)ln.scanlist.p);
   ln.amb_clean = false;
   if (overlap) {
-    SBO_HIP(hipEventRecord(c->ev_col[1], es));
-    SBO_HIP(hipStreamWaitEvent(xs, c->ev_col[1], 0));
+    SBO_HIP(hipEventRecord(c->col.ev[1], es));
+    SBO_HIP(hipStreamWaitEvent(xs, c->col.ev[1], 0));
   }
 
   // ---- objective chain, G part: the arg-max over G_1 reads the chain's G words, so it follows the join
   const int nbg = nb;
   hipLaunchKernelGGL(k_col_min<1>, dim3((unsigned)nbg), dim3(256), 0, xs, j);
   hipExtLaunchKernelGGL(k_col_finals, dim3(nb > 2048 ? kColFinParts : 1, 2), dim3(256), 0, xs, nullptr, c->ev[4], 0, (const Best*)reg0, nb, (const Best*)reg1,
-                        nbg, sc, (const ColScal2*)sc2, fin, tickets, c->h_back, (const unsigned long long*)c->Lmax.p, gb_of<double>(c, v) ? 1 : 0, cb.slots);
-  c->slots_clean = true;
+                        nbg, sc, (const ColScal2*)sc2, fin, tickets, c->h_back, c->Lmax, gb_of<double>(c, v) ? 1 : 0, cb.slots);
+  c->col.slots_clean = true;
   SBO_HIP(hipGetLastError());
   bool is_max[kArgSlots];
   for (int t = 0; t < kArgSlots; ++t) is_max[t] = true;
   if ((rc = sweep_exchange_back(c, h, is_max, Lk, c->ev[4], true))) return rc;
-  c->masks_bits = true;
-  c->col_G_bytes = false;
-  if (h.n_amb > 0 || c->exact_lazy == 2) {       // (2: always, the test of this path)
+  c->col.masks_bits = true;
+  c->col.G_bytes = false;
+  if (h.n_amb > 0 || c->opt.exact_lazy == 2) {       // (2: always, the test of this path)
     // verdicts inside the reference's "+1e-8" band after all: the exhaustive recheck of the byte-mask path on the expanded U / G
     // masks, then the expanders' arg-max and the finals once more (slot 0 is where that merge expects it)
-    col_expand(c, c->cbU, (uint8_t*)c->maskU.p);
-    col_expand(c, c->cbG, (uint8_t*)c->maskG.p);
+    col_expand(c, c->col.U, (uint8_t*)c->maskU.p);
+    col_expand(c, c->col.G, (uint8_t*)c->maskG.p);
     if ((rc = launch_exact_d<double>(c, ln, o, v, 1, lidx, (uint8_t*)c->maskG.p))) return rc;
     hipLaunchKernelGGL((k_arg_masked_multi<double, true, ValArray<double>>), dim3((unsigned)nb, 1u), dim3(256), 0, c->stream,
                        ValArray<double>{(const double*)v.var->p, 0.0}, (const uint8_t*)nullptr, (const uint8_t*)c->maskG.p, n, (long long)c->cs.first, pbase,
                        pstride, 1, gb_of<double>(c, v));
     hipLaunchKernelGGL(k_sweep_clear_slot, dim3(1), dim3(1), 0, c->stream, sc, 1);
     hipExtLaunchKernelGGL(k_sweep_finals<true>, dim3(2), dim3(256), 0, c->stream, nullptr, c->ev[4], 0, (const unsigned char*)pbase, pstride, nb, sc,
-                          (const SweepScalars*)nullptr, c->h_back, (const unsigned long long*)c->Lmax.p, gb_of<double>(c, v) ? 1 : 0);
+                          (const SweepScalars*)nullptr, c->h_back, c->Lmax, gb_of<double>(c, v) ? 1 : 0);
     SBO_HIP(hipGetLastError());
     if ((rc = sweep_exchange_back(c, h, is_max, Lk, c->ev[4], true))) return rc;
-    c->col_G_bytes = true;
+    c->col.G_bytes = true;
   }
   return SBO_OK;
 }

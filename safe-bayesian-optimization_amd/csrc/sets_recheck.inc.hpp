@@ -25,7 +25,7 @@
 // values replace the approximate ones IN PLACE, the Lipschitz keys are recomputed exactly, and the set phase runs again.
 #pragma once
 
-struct RcScal {                         // head of rc_list (256 bytes): this struct, the deferral counter at byte 32, G keys at 64
+struct RcScal {                         // head of Recheck::list (256 bytes): this struct, the deferral counter at byte 32, G keys at 64
   unsigned long long ulo_key, uhi_key, vmax_key;
   long long count;
 };
@@ -254,15 +254,15 @@ __global__ __launch_bounds__(256) void k_rc_gdefer(const uint8_t* __restrict__ G
 }
 
 // re-evaluate list[0..nf) exactly and put the values in place (`scatter`; without it an fp32 model's twin keeps them).  fp32 models: the fp64 twin's generic kernel, into the widened
-// copy rc_mean / rc_var; guard band of an approximating fp64 posterior (`guard`): the exact evaluator of the same model
+// copy recheck.mean / recheck.var; guard band of an approximating fp64 posterior (`guard`): the exact evaluator of the same model
 // (guard.hip: guard_exact_list), into the posterior buffers themselves.
 static int rc_refine(sbo_ctx* c, const long long* list, long long nf, bool guard = false, bool scatter = true) {
-  sbo_ctx* s = guard ? c : c->shadow;
+  sbo_ctx* s = guard ? c : c->recheck.shadow;
   const long long n = c->cs.n_local;
   const int q = c->mc.q, d = c->cs.d;
   int rc;
   if (nf <= 0) return SBO_OK;
-  DevBuf& pbuf = guard ? c->gb_pts : s->pts;
+  DevBuf& pbuf = guard ? c->gb.pts : s->pts;
   if ((rc = ensure(pbuf, sizeof(double) * (size_t)nf * d))) return rc;
   const unsigned nbf = (unsigned)std::max<long long>(1, std::min<long long>((nf + 255) / 256, 4096));
   switch (c->mc.dpad) {
@@ -271,14 +271,14 @@ static int rc_refine(sbo_ctx* c, const long long* list, long long nf, bool guard
     default: hipLaunchKernelGGL(k_rc_gather<8>, dim3(nbf), dim3(256), 0, c->stream, c->cs, list, nf, (double*)pbuf.p); break;
   }
   if (guard) {
-    if ((rc = ensure(c->gb_vals, sizeof(double) * 2 * (size_t)nf * q))) return rc;
-    double* em = (double*)c->gb_vals.p;
+    if ((rc = ensure(c->gb.vals, sizeof(double) * 2 * (size_t)nf * q))) return rc;
+    double* em = (double*)c->gb.vals.p;
     double* ev = em + (size_t)nf * q;
     if ((rc = guard_exact_list(c, (const double*)pbuf.p, nf, em, ev))) return rc;
     // (the standing audit takes its sample of what the posterior kernel stored before the exact values replace it)
-    if (c->audit_pending) SBO_HIP(hipStreamWaitEvent(c->stream, c->ev_audit[0], 0));
+    if (c->audit.pending) SBO_HIP(hipStreamWaitEvent(c->stream, c->audit.ev[0], 0));
     hipLaunchKernelGGL(k_rc_scatter, dim3(nbf), dim3(256), 0, c->stream, list, nf, q, n, (const double*)em, (const double*)ev,
-                       (double*)c->mean.p, (double*)c->var.p, (uint8_t*)c->rc_refined.p);
+                       (double*)c->mean.p, (double*)c->var.p, (uint8_t*)c->recheck.refined.p);
     SBO_HIP(hipGetLastError());
     return SBO_OK;
   }
@@ -289,16 +289,16 @@ static int rc_refine(sbo_ctx* c, const long long* list, long long nf, bool guard
   s->cs.pts = s->pts.p;
   s->cs.n_local = nf;
   s->cs.first = 0;
-  s->grid_total = nf;
+  s->dist.grid_total = nf;
   s->has_cand = true;
-  s->posterior_path = 0;
+  s->opt.posterior_path = 0;
   if ((rc = ensure(s->mean, sizeof(double) * (size_t)nf * q))) return rc;
   if ((rc = ensure(s->var, sizeof(double) * (size_t)nf * q))) return rc;
   PostOutcome none;
   if ((rc = launch_posterior(s, PostRequest{}, none))) return rc;
   if (!scatter) return SBO_OK;             // (rc_probe: the twin's values stay in its own buffers, [q][nf])
   hipLaunchKernelGGL(k_rc_scatter, dim3(nbf), dim3(256), 0, c->stream, list, nf, q, n, (const double*)s->mean.p, (const double*)s->var.p,
-                     (double*)c->rc_mean.p, (double*)c->rc_var.p, (uint8_t*)c->rc_refined.p);
+                     (double*)c->recheck.mean.p, (double*)c->recheck.var.p, (uint8_t*)c->recheck.refined.p);
   SBO_HIP(hipGetLastError());
   return SBO_OK;
 }
@@ -307,11 +307,11 @@ static int rc_refine(sbo_ctx* c, const long long* list, long long nf, bool guard
 // candidates of `c`
 static int rc_lipschitz64(sbo_ctx* c, const sbo_ctx* s) {
   const long long n = c->cs.n_local;
-  SBO_HIP(hipMemsetAsync(c->Lmax.p, 0, sizeof(unsigned long long) * kMaxQ, c->stream));
+  SBO_HIP(hipMemsetAsync(c->Lmax, 0, sizeof(unsigned long long) * kMaxQ, c->stream));
   const unsigned nbg = (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)c->n_cu * 8));
 #define SBO_GRAD(DD)                                                                                                              \
   hipLaunchKernelGGL(k_rc_grad64<DD>, dim3(nbg), dim3(256), 0, c->stream, s->mc, c->cs, (const double*)s->As.p, (const double*)s->sqA.p, \
-                     (const double*)s->alpha.p, (const double*)s->Xn.p, (unsigned long long*)c->Lmax.p)
+                     (const double*)s->alpha.p, (const double*)s->Xn.p, c->Lmax)
   switch (c->mc.dpad) {
     case 2: SBO_GRAD(2); break;
     case 4: SBO_GRAD(4); break;
@@ -368,9 +368,9 @@ static int rc_probe(sbo_ctx* c, long long round, double* dev_m, double* dev_v, i
   int rc;
   for (int o = 0; o < kMaxQ; ++o) dev_m[o] = dev_v[o] = 0.0;
   *probes = P;
-  if ((rc = ensure(c->rc_probe, sizeof(unsigned long long) * 2 * kMaxQ + sizeof(long long) * kRcProbes))) return rc;
+  if ((rc = ensure(c->recheck.probe, sizeof(unsigned long long) * 2 * kMaxQ + sizeof(long long) * kRcProbes))) return rc;
   if (P <= 0) return SBO_OK;
-  unsigned long long* keys = (unsigned long long*)c->rc_probe.p;
+  unsigned long long* keys = (unsigned long long*)c->recheck.probe.p;
   long long* list = (long long*)(keys + 2 * kMaxQ);
   long long h[kRcProbes];
   for (int k = 0; k < P; ++k) {
@@ -385,7 +385,7 @@ static int rc_probe(sbo_ctx* c, long long round, double* dev_m, double* dev_v, i
   SBO_HIP(hipStreamSynchronize(c->stream));                      // (`h` is on this frame)
   if ((rc = rc_refine(c, list, P, false, false))) return rc;
   hipLaunchKernelGGL(k_rc_probe_dev, dim3(1), dim3(256), 0, c->stream, (const float*)c->mean.p, (const float*)c->var.p, n, (const long long*)list, P, q,
-                     (const double*)c->shadow->mean.p, (const double*)c->shadow->var.p, keys);
+                     (const double*)c->recheck.shadow->mean.p, (const double*)c->recheck.shadow->var.p, keys);
   SBO_HIP(hipGetLastError());
   double hk[2 * kMaxQ];
   SBO_HIP(hipMemcpyAsync(hk, keys, sizeof(hk), hipMemcpyDeviceToHost, c->stream));
@@ -405,7 +405,7 @@ static int rc_bands(sbo_ctx* c, bool guard, RcBand& bd) {
   int rc;
   if (guard) {
     GuardBand hb;
-    SBO_HIP(hipMemcpyAsync(&hb, c->gb.p, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
+    SBO_HIP(hipMemcpyAsync(&hb, c->gb.buf.p, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
     SBO_HIP(hipStreamSynchronize(c->stream));
     for (int i = 0; i < q; ++i) {
       if (!(hb.dm[i] >= 0.0) || !(hb.dv[i] >= 0.0)) return fail(SBO_E_HIP, "internal: guard band is not finite");
@@ -416,7 +416,7 @@ static int rc_bands(sbo_ctx* c, bool guard, RcBand& bd) {
   }
   double dev_m[kMaxQ], dev_v[kMaxQ];
   int probes = 0;
-  if (!c->rc_band_valid) {
+  if (!c->recheck.band_valid) {
     if ((rc = rc_probe(c, 0, dev_m, dev_v, &probes))) return rc;
     double hk[2 * kMaxQ] = {};
     for (int i = 0; i < q; ++i) {
@@ -425,7 +425,7 @@ static int rc_bands(sbo_ctx* c, bool guard, RcBand& bd) {
       hk[kMaxQ + i] = std::max(kRcBandFloor * ys * ys, kRcBandFactor * dev_v[i]);
     }
     if (multi_rank(c)) {                  // (one band for all ranks: the largest)
-      unsigned long long* keys = (unsigned long long*)c->rc_probe.p;
+      unsigned long long* keys = (unsigned long long*)c->recheck.probe.p;
       SBO_HIP(hipMemcpyAsync(keys, hk, sizeof(hk), hipMemcpyHostToDevice, c->stream));
       SBO_HIP(hipStreamSynchronize(c->stream));
       if ((rc = comm_allreduce_max_u64(c, keys, 2 * kMaxQ))) return rc;
@@ -433,24 +433,24 @@ static int rc_bands(sbo_ctx* c, bool guard, RcBand& bd) {
       SBO_HIP(hipStreamSynchronize(c->stream));
     }
     for (int i = 0; i < q; ++i) {
-      c->rc_band_dm[i] = hk[i];
-      c->rc_band_dv[i] = hk[kMaxQ + i];
+      c->recheck.band_dm[i] = hk[i];
+      c->recheck.band_dv[i] = hk[kMaxQ + i];
     }
-    c->rc_band_valid = true;
-    c->rc_probe_round = 0;
-  } else if (c->guard_audit > 0 && c->audit_tick++ % std::max(1, c->guard_audit_every) == 0) {
+    c->recheck.band_valid = true;
+    c->recheck.probe_round = 0;
+  } else if (c->opt.guard_audit > 0 && c->audit.tick++ % std::max(1, c->opt.guard_audit_every) == 0) {
     // the standing audit: another probe set against the band in force
-    if ((rc = rc_probe(c, ++c->rc_probe_round, dev_m, dev_v, &probes))) return rc;
+    if ((rc = rc_probe(c, ++c->recheck.probe_round, dev_m, dev_v, &probes))) return rc;
     for (int i = 0; i < q && probes > 0; ++i) {
-      const double wm = dev_m[i] / (c->rc_band_dm[i] * c->audit_scale), wv = dev_v[i] / (c->rc_band_dv[i] * c->audit_scale);
-      c->audit_samples += 2 * probes;
-      c->audit_violations += (wm > 1.0 ? 1 : 0) + (wv > 1.0 ? 1 : 0);
-      c->audit_worst = std::max(c->audit_worst, std::max(wm, wv));
+      const double wm = dev_m[i] / (c->recheck.band_dm[i] * c->opt.audit_scale), wv = dev_v[i] / (c->recheck.band_dv[i] * c->opt.audit_scale);
+      c->audit.samples += 2 * probes;
+      c->audit.violations += (wm > 1.0 ? 1 : 0) + (wv > 1.0 ? 1 : 0);
+      c->audit.worst = std::max(c->audit.worst, std::max(wm, wv));
     }
   }
   for (int i = 0; i < q; ++i) {
-    bd.dm[i] = c->rc_band_dm[i];
-    bd.dv[i] = c->rc_band_dv[i];
+    bd.dm[i] = c->recheck.band_dm[i];
+    bd.dv[i] = c->recheck.band_dv[i];
   }
   return SBO_OK;
 }
@@ -482,20 +482,20 @@ static int sweep_safeopt_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeop
   // (one pass can list a candidate once per constraint in the verdict kernels and once more per constraint in k_rc_gdefer;
   // the first list -- k_rc_flag -- holds every candidate at most once)
   const size_t list_cap = (size_t)std::max<long long>(n, 1) * (size_t)(2 * std::max(1, q - 1) + 1);
-  if ((rc = ensure(c->rc_list, kRcList + sizeof(long long) * list_cap))) return rc;
+  if ((rc = ensure(c->recheck.list, kRcList + sizeof(long long) * list_cap))) return rc;
   if (!kGuard) {
-    if ((rc = ensure(c->rc_mean, sizeof(double) * (size_t)q * std::max<long long>(n, 1)))) return rc;
-    if ((rc = ensure(c->rc_var, sizeof(double) * (size_t)q * std::max<long long>(n, 1)))) return rc;
+    if ((rc = ensure(c->recheck.mean, sizeof(double) * (size_t)q * std::max<long long>(n, 1)))) return rc;
+    if ((rc = ensure(c->recheck.var, sizeof(double) * (size_t)q * std::max<long long>(n, 1)))) return rc;
   }
-  if ((rc = ensure(c->rc_refined, (size_t)std::max<long long>(n, 1)))) return rc;
-  RcScal* sc = (RcScal*)c->rc_list.p;
-  unsigned long long* count2 = (unsigned long long*)((char*)c->rc_list.p + kRcCount2);
-  unsigned long long* gkeys = (unsigned long long*)((char*)c->rc_list.p + kRcGKeys);
-  long long* list = (long long*)((char*)c->rc_list.p + kRcList);
-  SBO_HIP(hipMemsetAsync(c->rc_list.p, 0, kRcList, c->stream));
+  if ((rc = ensure(c->recheck.refined, (size_t)std::max<long long>(n, 1)))) return rc;
+  RcScal* sc = (RcScal*)c->recheck.list.p;
+  unsigned long long* count2 = (unsigned long long*)((char*)c->recheck.list.p + kRcCount2);
+  unsigned long long* gkeys = (unsigned long long*)((char*)c->recheck.list.p + kRcGKeys);
+  long long* list = (long long*)((char*)c->recheck.list.p + kRcList);
+  SBO_HIP(hipMemsetAsync(c->recheck.list.p, 0, kRcList, c->stream));
   const RcScal init{~0ull, ~0ull, 0ull, 0};
   SBO_HIP(hipMemcpyAsync(sc, &init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  SBO_HIP(hipMemsetAsync(c->rc_refined.p, 0, (size_t)std::max<long long>(n, 1), c->stream));
+  SBO_HIP(hipMemsetAsync(c->recheck.refined.p, 0, (size_t)std::max<long long>(n, 1), c->stream));
   const TP* m32 = (const TP*)c->mean.p;
   const TP* v32 = (const TP*)c->var.p;
   const unsigned nbk = (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)c->n_cu * 4));
@@ -512,7 +512,7 @@ static int sweep_safeopt_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeop
   hipLaunchKernelGGL(k_rc_flag<TP>, dim3(nbk), dim3(256), 0, c->stream, m32, v32, n, q, o->b, bd, sc, list, grid_expander ? 0 : 1);
   if (!kGuard)
     hipLaunchKernelGGL(k_rc_widen, dim3(nbk), dim3(256), 0, c->stream, (const float*)c->mean.p, (const float*)c->var.p, (long long)q * n,
-                       (double*)c->rc_mean.p, (double*)c->rc_var.p);
+                       (double*)c->recheck.mean.p, (double*)c->recheck.var.p);
   SBO_HIP(hipGetLastError());
   unsigned char* hb = c->h_back + 5120;                             // pinned landing area of the list lengths
   SBO_HIP(hipMemcpyAsync(hb, sc, 64, hipMemcpyDeviceToHost, c->stream));
@@ -520,13 +520,13 @@ static int sweep_safeopt_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeop
   long long total = ((const RcScal*)hb)->count;
   if ((rc = rc_refine(c, list, total, kGuard))) return rc;
   // Lipschitz keys in fp64 (the fp32 posterior kernel left fp32-accurate ones, an approximating one its own band)
-  if (q > 1 && (rc = rc_lipschitz64(c, kGuard ? c : c->shadow))) return rc;
+  if (q > 1 && (rc = rc_lipschitz64(c, kGuard ? c : c->recheck.shadow))) return rc;
   SBO_HIP(hipEventRecord(c->ev_join[2], c->stream));
   // the set phase in fp64 arithmetic on the refined posterior (fp32: the widened copy -- the fp32 arrays stay what
   // sbo_posterior_get returns; guard: the band stays in force for unrefined entries, L is exact now); repeated while verdicts are deferred
-  SetView view(kGuard ? c->mean : c->rc_mean, kGuard ? c->var : c->rc_var, kGuard ? SetBand::values : SetBand::plan);
+  SetView view(kGuard ? c->mean : c->recheck.mean, kGuard ? c->var : c->recheck.var, kGuard ? SetBand::values : SetBand::plan);
   if (q > 1) {
-    view.refined = (const uint8_t*)c->rc_refined.p;
+    view.refined = (const uint8_t*)c->recheck.refined.p;
     view.rc_band = &bd;
     view.rc_list = list;
     view.rc_count = count2;
@@ -539,18 +539,18 @@ static int sweep_safeopt_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeop
     // Expander's arg-max over every G_c must not hinge on an unrefined variance
     const uint8_t* G = (const uint8_t*)c->maskG.p;
     const double* var0 = (const double*)view.var->p;
-    hipLaunchKernelGGL(k_rc_gmax, dim3(nbk, (unsigned)(q - 1)), dim3(256), 0, c->stream, G, var0, (const uint8_t*)c->rc_refined.p, n, bd.dv[0],
+    hipLaunchKernelGGL(k_rc_gmax, dim3(nbk, (unsigned)(q - 1)), dim3(256), 0, c->stream, G, var0, (const uint8_t*)c->recheck.refined.p, n, bd.dv[0],
                        gkeys);
     if ((rc = comm_allreduce_max_u64(c, gkeys, q - 1))) return rc;        // (the expanders' arg-max is over all ranks)
-    hipLaunchKernelGGL(k_rc_gdefer, dim3(nbk, (unsigned)(q - 1)), dim3(256), 0, c->stream, G, var0, (const uint8_t*)c->rc_refined.p, n,
+    hipLaunchKernelGGL(k_rc_gdefer, dim3(nbk, (unsigned)(q - 1)), dim3(256), 0, c->stream, G, var0, (const uint8_t*)c->recheck.refined.p, n,
                        bd.dv[0], (const unsigned long long*)gkeys, list, count2);
     SBO_HIP(hipGetLastError());
-    SBO_HIP(hipMemcpyAsync(hb, c->rc_list.p, 64, hipMemcpyDeviceToHost, c->stream));
+    SBO_HIP(hipMemcpyAsync(hb, c->recheck.list.p, 64, hipMemcpyDeviceToHost, c->stream));
     SBO_HIP(hipStreamSynchronize(c->stream));
     const long long nd = (long long)*(const unsigned long long*)(hb + kRcCount2);
     // (ranks > 1: every rank runs the set phase the same number of times -- its collectives are inside --, so "nothing deferred"
     // is a global statement: the largest count over the ranks)
-    unsigned long long* dcount = (unsigned long long*)((char*)c->rc_list.p + kRcCount2 + 8);   // scratch word behind the counter
+    unsigned long long* dcount = (unsigned long long*)((char*)c->recheck.list.p + kRcCount2 + 8);   // scratch word behind the counter
     long long nd_all = nd;
     if (multi_rank(c)) {
       SBO_HIP(hipMemcpyAsync(dcount, hb + kRcCount2, 8, hipMemcpyHostToDevice, c->stream));
@@ -644,7 +644,7 @@ __global__ void k_rc_ball(const CandSpec cs, long long n, const double* __restri
 // what the GoOSE / trust-region rechecks hand their set phase: the widened copy of an fp32 posterior, or (guard) the fp64 posterior
 // itself, refined in place; every value that enters a decision is exact by then: no band
 static SetView rc_exact_view(const sbo_ctx* c, bool guard) {
-  return SetView(guard ? c->mean : c->rc_mean, guard ? c->var : c->rc_var, SetBand::none);
+  return SetView(guard ? c->mean : c->recheck.mean, guard ? c->var : c->recheck.var, SetBand::none);
 }
 
 // front end shared by the GoOSE / trust-region rechecks: posterior, (fp32) widened copy, first refinement list (q > 1: every
@@ -658,18 +658,18 @@ static int rc_front_all(sbo_ctx* c, const sbo_sweep_opts* o, RcBand& bd, long lo
   const bool reuse = kGuard || (o->posterior_ready && c->posterior_valid);
   if (!reuse && (rc = posterior_enqueue(c, PostRequest{}, nullptr))) return rc;
   if ((rc = rc_bands(c, kGuard, bd))) return rc;
-  if ((rc = ensure(c->rc_list, kRcList + sizeof(long long) * (size_t)std::max<long long>(n, 1) * 2))) return rc;
+  if ((rc = ensure(c->recheck.list, kRcList + sizeof(long long) * (size_t)std::max<long long>(n, 1) * 2))) return rc;
   if (!kGuard) {
-    if ((rc = ensure(c->rc_mean, sizeof(double) * (size_t)q * std::max<long long>(n, 1)))) return rc;
-    if ((rc = ensure(c->rc_var, sizeof(double) * (size_t)q * std::max<long long>(n, 1)))) return rc;
+    if ((rc = ensure(c->recheck.mean, sizeof(double) * (size_t)q * std::max<long long>(n, 1)))) return rc;
+    if ((rc = ensure(c->recheck.var, sizeof(double) * (size_t)q * std::max<long long>(n, 1)))) return rc;
   }
-  if ((rc = ensure(c->rc_refined, (size_t)std::max<long long>(n, 1)))) return rc;
-  RcScal* sc = (RcScal*)c->rc_list.p;
-  long long* list = (long long*)((char*)c->rc_list.p + kRcList);
-  SBO_HIP(hipMemsetAsync(c->rc_list.p, 0, kRcList, c->stream));
+  if ((rc = ensure(c->recheck.refined, (size_t)std::max<long long>(n, 1)))) return rc;
+  RcScal* sc = (RcScal*)c->recheck.list.p;
+  long long* list = (long long*)((char*)c->recheck.list.p + kRcList);
+  SBO_HIP(hipMemsetAsync(c->recheck.list.p, 0, kRcList, c->stream));
   const RcScal init{~0ull, ~0ull, 0ull, 0};
   SBO_HIP(hipMemcpyAsync(sc, &init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  SBO_HIP(hipMemsetAsync(c->rc_refined.p, 0, (size_t)std::max<long long>(n, 1), c->stream));
+  SBO_HIP(hipMemsetAsync(c->recheck.refined.p, 0, (size_t)std::max<long long>(n, 1), c->stream));
   const TP* m32 = (const TP*)c->mean.p;
   const TP* v32 = (const TP*)c->var.p;
   const unsigned nbk = (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)c->n_cu * 4));
@@ -680,14 +680,14 @@ static int rc_front_all(sbo_ctx* c, const sbo_sweep_opts* o, RcBand& bd, long lo
   }
   if (!kGuard)
     hipLaunchKernelGGL(k_rc_widen, dim3(nbk), dim3(256), 0, c->stream, (const float*)c->mean.p, (const float*)c->var.p, (long long)q * n,
-                       (double*)c->rc_mean.p, (double*)c->rc_var.p);
+                       (double*)c->recheck.mean.p, (double*)c->recheck.var.p);
   SBO_HIP(hipGetLastError());
   unsigned char* hb = c->h_back + 5120;
   SBO_HIP(hipMemcpyAsync(hb, sc, 64, hipMemcpyDeviceToHost, c->stream));
   SBO_HIP(hipStreamSynchronize(c->stream));
   *total = ((const RcScal*)hb)->count;
   if ((rc = rc_refine(c, list, *total, kGuard))) return rc;
-  if (q > 1 && (rc = rc_lipschitz64(c, kGuard ? c : c->shadow))) return rc;
+  if (q > 1 && (rc = rc_lipschitz64(c, kGuard ? c : c->recheck.shadow))) return rc;
   return SBO_OK;
 }
 
@@ -697,26 +697,26 @@ static int rc_argmin_contenders(sbo_ctx* c, const sbo_sweep_opts* o, const RcBan
                                 bool guard) {
   const long long n = c->cs.n_local;
   int rc;
-  unsigned long long* key = (unsigned long long*)((char*)c->rc_list.p + kRcCount2 + 8);
-  unsigned long long* count2 = (unsigned long long*)((char*)c->rc_list.p + kRcCount2);
-  long long* list = (long long*)((char*)c->rc_list.p + kRcList);
+  unsigned long long* key = (unsigned long long*)((char*)c->recheck.list.p + kRcCount2 + 8);
+  unsigned long long* count2 = (unsigned long long*)((char*)c->recheck.list.p + kRcCount2);
+  long long* list = (long long*)((char*)c->recheck.list.p + kRcList);
   const unsigned long long init[2] = {0ull, ~0ull};
   SBO_HIP(hipMemcpyAsync(count2, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
   const unsigned nbk = (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)c->n_cu * 4));
-  const double* m0 = guard ? (const double*)c->mean.p : (const double*)c->rc_mean.p;
-  const double* v0 = guard ? (const double*)c->var.p : (const double*)c->rc_var.p;
-  hipLaunchKernelGGL(k_rc_lmin, dim3(nbk), dim3(256), 0, c->stream, m0, v0, (const uint8_t*)c->rc_refined.p, mask, nmask, n, o->b, bd.dm[0], bd.dv[0], key);
+  const double* m0 = guard ? (const double*)c->mean.p : (const double*)c->recheck.mean.p;
+  const double* v0 = guard ? (const double*)c->var.p : (const double*)c->recheck.var.p;
+  hipLaunchKernelGGL(k_rc_lmin, dim3(nbk), dim3(256), 0, c->stream, m0, v0, (const uint8_t*)c->recheck.refined.p, mask, nmask, n, o->b, bd.dm[0], bd.dv[0], key);
   if ((rc = comm_allreduce_min_u64(c, key, 1))) return rc;             // (ranks > 1: the arg-min is over all ranks)
-  hipLaunchKernelGGL(k_rc_lflag, dim3(nbk), dim3(256), 0, c->stream, m0, v0, (const uint8_t*)c->rc_refined.p, mask, nmask, n, o->b, bd.dm[0], bd.dv[0],
+  hipLaunchKernelGGL(k_rc_lflag, dim3(nbk), dim3(256), 0, c->stream, m0, v0, (const uint8_t*)c->recheck.refined.p, mask, nmask, n, o->b, bd.dm[0], bd.dv[0],
                      (const unsigned long long*)key, list, count2);
   SBO_HIP(hipGetLastError());
   unsigned char* hb = c->h_back + 5120;
-  SBO_HIP(hipMemcpyAsync(hb, c->rc_list.p, 64, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipMemcpyAsync(hb, c->recheck.list.p, 64, hipMemcpyDeviceToHost, c->stream));
   SBO_HIP(hipStreamSynchronize(c->stream));
   const long long mine = (long long)*(const unsigned long long*)(hb + kRcCount2);
   *found = mine;
   if (multi_rank(c)) {                   // every rank goes round the same number of times: the largest count decides
-    unsigned long long* dcount = (unsigned long long*)((char*)c->rc_list.p + kRcCount2 + 16);
+    unsigned long long* dcount = (unsigned long long*)((char*)c->recheck.list.p + kRcCount2 + 16);
     SBO_HIP(hipMemcpyAsync(dcount, hb + kRcCount2, 8, hipMemcpyHostToDevice, c->stream));
     if ((rc = comm_allreduce_max_u64(c, dcount, 1))) return rc;
     SBO_HIP(hipMemcpyAsync(hb + 56, dcount, 8, hipMemcpyDeviceToHost, c->stream));

@@ -467,7 +467,7 @@ static int ladder_size(int a) { return a < 2 ? 4 : 7; }
 static int ladder_at(int a, int lv) { return a < 2 ? kLadder01[std::min(lv, 3)] : kLadderN[std::min(lv, 6)]; }
 
 bool tensor_applicable(const sbo_ctx* c) {
-  if (!c->tensor_cheb || c->is_shadow || c->dtype != SBO_F64 || c->cs.kind != 1) return false;
+  if (!c->opt.tensor_cheb || c->is_shadow || c->dtype != SBO_F64 || c->cs.kind != 1) return false;
   const int d = c->cs.d;
   if (d < 3 || d > kTMaxD) return false;
   long long plane = 1;
@@ -475,7 +475,7 @@ bool tensor_applicable(const sbo_ctx* c) {
   if (c->cs.n_local <= 0 || c->cs.first % plane != 0 || c->cs.n_local % plane != 0) return false;
   for (int a = 0; a < d; ++a)
     if (c->cs.count[a] < 64) return false;
-  return c->grid_total >= (1ll << 22);
+  return c->dist.grid_total >= (1ll << 22);
 }
 
 template <int DM>
@@ -503,8 +503,8 @@ static int launch_final(sbo_ctx* c, const double* in, size_t stride_q, const Ten
   SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const long long units = planes * (nq - gskip) * ((td.cnt[0] + 127) / 128);
   const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(units, (long long)c->n_cu));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, c->stream, in, stride_q, (const double*)c->tn_W0t.p, (const double*)c->tn_W1t.p, td.cnt[0],
-                     td.cnt[1], planes, td.q, td.d, nq, (double*)c->mean.p, (double*)c->var.p, (size_t)c->cs.n_local, (unsigned long long*)c->Lmax.p, gskip);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, c->stream, in, stride_q, (const double*)c->tn.W0t.p, (const double*)c->tn.W1t.p, td.cnt[0],
+                     td.cnt[1], planes, td.q, td.d, nq, (double*)c->mean.p, (double*)c->var.p, (size_t)c->cs.n_local, c->Lmax, gskip);
   SBO_HIP(hipGetLastError());
   return SBO_OK;
 }
@@ -515,23 +515,23 @@ static int interpolate(sbo_ctx* c, const TensorDims& td, const double* nodes, lo
   const int d = td.d;
   int rc;
   const int gskip = (sweep_lean && td.q >= 2) ? d : 0;      // (a lean sweep: nobody reads L_0)
-  // axes d-1 .. 2 on the small tensors (ping-pong in tn_work), then the planes
+  // axes d-1 .. 2 on the small tensors (ping-pong in tn.work), then the planes
   const double* cur = nodes;
   size_t cur_stride = (size_t)Nn;
   long long pre = 1;
   for (int a = 0; a < d - 1; ++a) pre *= td.Dn[a];          // product of the node counts below the axis being contracted
   long long post = 1;
-  double* bufA = (double*)c->tn_work.p;
-  double* bufB = bufA + c->tn_work_half;
+  double* bufA = (double*)c->tn.work.p;
+  double* bufB = bufA + c->tn.work_half;
   bool toA = true;
   for (int a = d - 1; a >= 2; --a) {
     const long long nx = td.cnt[a];
     double* dst = toA ? bufA : bufB;
     const size_t dst_stride = (size_t)pre * nx * post;
     if ((rc = mode_dispatch(c->stream, td.Dn[a] <= 32 ? 32 : (td.Dn[a] <= 48 ? 48 : (td.Dn[a] <= 64 ? 64 : 96)), cur, cur_stride, dst, dst_stride,
-                            (const double*)c->tn_W[a].p, pre, td.Dn[a], nx, post, nq, a == d - 1 ? td.Dn[0] : 0, 2 * td.q, gskip)))
+                            (const double*)c->tn.W[a].p, pre, td.Dn[a], nx, post, nq, a == d - 1 ? td.Dn[0] : 0, 2 * td.q, gskip)))
       return rc;
-    c->tn_flops += 2.0 * (double)pre * td.Dn[a] * (double)nx * (double)post * (nq - gskip);
+    c->tn.flops += 2.0 * (double)pre * td.Dn[a] * (double)nx * (double)post * (nq - gskip);
     cur = dst;
     cur_stride = dst_stride;
     post *= nx;
@@ -541,8 +541,8 @@ static int interpolate(sbo_ctx* c, const TensorDims& td, const double* nodes, lo
   // now cur = [DM][DM][planes = post] per quantity
   *cur_out = cur;
   *stride_out = cur_stride;
-  c->tn_flops += 2.0 * (double)post * (nq - gskip) * ((double)td.cnt[0] * td.Dn[0] * td.Dn[1] + (double)td.cnt[0] * td.cnt[1] * td.Dn[1]);
-  SBO_HIP(hipMemsetAsync(c->Lmax.p, 0, sizeof(unsigned long long) * kMaxQ, c->stream));
+  c->tn.flops += 2.0 * (double)post * (nq - gskip) * ((double)td.cnt[0] * td.Dn[0] * td.Dn[1] + (double)td.cnt[0] * td.cnt[1] * td.Dn[1]);
+  SBO_HIP(hipMemsetAsync(c->Lmax, 0, sizeof(unsigned long long) * kMaxQ, c->stream));
   switch (td.Dn[0]) {
     case 32: return launch_final<32, 8>(c, cur, cur_stride, td, post, nq, gskip);
     case 48: return launch_final<48, 8>(c, cur, cur_stride, td, post, nq, gskip);
@@ -572,39 +572,39 @@ int launch_posterior_tensor(sbo_ctx* c, const PostRequest& req, bool* declined) 
   }
   td.first_last = cs.first / plane;
   // plan: degrees per axis, decided once per (model, grid) with an accuracy probe
-  const bool same_grid = c->tn_valid && c->tn_model == c->model_serial && c->tn_first == cs.first && c->tn_nlocal == cs.n_local &&
-                         !memcmp(c->tn_count, cs.count, sizeof(long long) * kTMaxD) && !memcmp(c->tn_lo, cs.lo, sizeof(double) * kTMaxD) &&
-                         !memcmp(c->tn_hi, cs.hi, sizeof(double) * kTMaxD);
+  const bool same_grid = c->tn.valid && c->tn.model == c->model_serial && c->tn.first == cs.first && c->tn.nlocal == cs.n_local &&
+                         !memcmp(c->tn.count, cs.count, sizeof(long long) * kTMaxD) && !memcmp(c->tn.lo, cs.lo, sizeof(double) * kTMaxD) &&
+                         !memcmp(c->tn.hi, cs.hi, sizeof(double) * kTMaxD);
   // same candidates as the last plan's, whatever the model
-  const bool same_box = c->tn_valid && c->tn_first == cs.first && c->tn_nlocal == cs.n_local && !memcmp(c->tn_count, cs.count, sizeof(long long) * kTMaxD) &&
-                        !memcmp(c->tn_lo, cs.lo, sizeof(double) * kTMaxD) && !memcmp(c->tn_hi, cs.hi, sizeof(double) * kTMaxD);
-  if (!same_box) c->tn_bump = 0;
+  const bool same_box = c->tn.valid && c->tn.first == cs.first && c->tn.nlocal == cs.n_local && !memcmp(c->tn.count, cs.count, sizeof(long long) * kTMaxD) &&
+                        !memcmp(c->tn.lo, cs.lo, sizeof(double) * kTMaxD) && !memcmp(c->tn.hi, cs.hi, sizeof(double) * kTMaxD);
+  if (!same_box) c->tn.bump = 0;
   // a plan a lean sweep decided never probed output 0's gradient (its band has no measured part for L_0): the first full sweep on it
   // keeps its degrees and runs the probe once more, so the band is what a full sweep deciding the plan would have measured
-  const bool reprobe = same_grid && c->tn_usable && c->tn_lean_probe && !(req.sweep_lean && q >= 2);
+  const bool reprobe = same_grid && c->tn.usable && c->tn.lean_probe && !(req.sweep_lean && q >= 2);
   const bool probe = !same_grid || reprobe;
   int level0[kTMaxD], base0[kTMaxD] = {0, 0, 0, 0};
   if (same_grid) {
-    if (!c->tn_usable) return SBO_OK;
-    for (int a = 0; a < d; ++a) level0[a] = c->tn_level[a];
+    if (!c->tn.usable) return SBO_OK;
+    for (int a = 0; a < d; ++a) level0[a] = c->tn.level[a];
   } else {
     // first guess from the shortest length scale of the axis: degree ~ 7.6 x (normalised interval / ell); the probe below corrects a short guess
     for (int a = 0; a < d; ++a) {
       double tmax = 0.0;
       for (int o = 0; o < q; ++o) tmax = std::max(tmax, 2.0 * td.half[a] / mc.X_std[a] * std::sqrt(mc.inv_ell[o][a]));
       // (the further axes' ladder is finer and their guess tighter: 40 nodes measured 1e-13 where this rule gives 39.4)
-      const double want = (a < 2 ? 7.6 : 6.9) * tmax * (0.01 * c->tensor_guess_pct);     // (option: a test hook for the second attempt)
+      const double want = (a < 2 ? 7.6 : 6.9) * tmax * (0.01 * c->opt.tensor_guess_pct);     // (option: a test hook for the second attempt)
       int lv = 0;
       while (lv < ladder_size(a) - 1 && ladder_at(a, lv) < want) ++lv;
       base0[a] = lv;
-      level0[a] = lv + (same_box ? c->tn_bump : 0);     // (the previous model on this grid needed the second attempt: start there)
+      level0[a] = lv + (same_box ? c->tn.bump : 0);     // (the previous model on this grid needed the second attempt: start there)
     }
   }
   for (int attempt = 0; attempt < (same_grid ? 1 : 2); ++attempt) {
     long long Nn = 1;
     bool ok_dims = true;
     for (int a = 0; a < d; ++a) {
-      td.Dn[a] = same_grid ? c->tn_dn[a] : ladder_at(a, level0[a] + attempt);
+      td.Dn[a] = same_grid ? c->tn.dn[a] : ladder_at(a, level0[a] + attempt);
       // (steps beyond the first guess: the first two axes stay within what k_t_final takes -- the error may well sit on the others)
       if (!same_grid && a < 2 && td.Dn[a] > 64 && ladder_at(a, base0[a]) <= 64) td.Dn[a] = 64;
     }
@@ -617,11 +617,11 @@ int launch_posterior_tensor(sbo_ctx* c, const PostRequest& req, bool* declined) 
     if (!ok_dims || Nn > (1ll << 24)) break;
     // buffers: node list, node values (mean, var: q each; gradient: q d), interpolation matrices, ping-pong work
     const int nqg = q * d;
-    if ((rc = ensure(c->tn_pts, sizeof(double) * 8 * 128))) return rc;       // the node positions of the axes (+ a rank's slab of them)
+    if ((rc = ensure(c->tn.pts, sizeof(double) * 8 * 128))) return rc;       // the node positions of the axes (+ a rank's slab of them)
     // (the two large buffers: running out of memory for them is a reason to decline -- K1g needs neither --, not to fail the sweep.
     // With ranks > 1 it IS an error: the plan is one decision of all ranks, and a rank that left for K1g alone would leave the others
     // in the all-gather of the node slabs -- ADVICE r04)
-    if ((rc = ensure(c->tn_vals, sizeof(double) * (size_t)Nn * (2 * q + nqg)))) { if (rc == SBO_E_NOMEM && !multi_rank(c)) break; return rc; }
+    if ((rc = ensure(c->tn.vals, sizeof(double) * (size_t)Nn * (2 * q + nqg)))) { if (rc == SBO_E_NOMEM && !multi_rank(c)) break; return rc; }
     size_t half_elems = 0;
     {
       long long pre = 1, post = 1;
@@ -632,22 +632,22 @@ int launch_posterior_tensor(sbo_ctx* c, const PostRequest& req, bool* declined) 
         pre /= td.Dn[a - 1];
       }
     }
-    c->tn_work_half = half_elems;
-    if ((rc = ensure(c->tn_work, sizeof(double) * 2 * std::max<size_t>(half_elems, 16)))) { if (rc == SBO_E_NOMEM && !multi_rank(c)) break; return rc; }
+    c->tn.work_half = half_elems;
+    if ((rc = ensure(c->tn.work, sizeof(double) * 2 * std::max<size_t>(half_elems, 16)))) { if (rc == SBO_E_NOMEM && !multi_rank(c)) break; return rc; }
     for (int a = 0; a < d; ++a)
-      if ((rc = ensure(c->tn_W[a], sizeof(double) * (size_t)td.cnt[a] * td.Dn[a]))) return rc;
-    if ((rc = ensure(c->tn_W0t, sizeof(double) * (size_t)td.cnt[0] * td.Dn[0]))) return rc;
-    if ((rc = ensure(c->tn_W1t, sizeof(double) * (size_t)td.cnt[1] * td.Dn[1]))) return rc;
-    if ((rc = ensure(c->tn_scr, 512))) return rc;
-    hipLaunchKernelGGL(k_t_axes, dim3(1), dim3(128), 0, c->stream, td, (double*)c->tn_pts.p);
+      if ((rc = ensure(c->tn.W[a], sizeof(double) * (size_t)td.cnt[a] * td.Dn[a]))) return rc;
+    if ((rc = ensure(c->tn.W0t, sizeof(double) * (size_t)td.cnt[0] * td.Dn[0]))) return rc;
+    if ((rc = ensure(c->tn.W1t, sizeof(double) * (size_t)td.cnt[1] * td.Dn[1]))) return rc;
+    if ((rc = ensure(c->tn.scr, 512))) return rc;
+    hipLaunchKernelGGL(k_t_axes, dim3(1), dim3(128), 0, c->stream, td, (double*)c->tn.pts.p);
     for (int a = 0; a < d; ++a)
       hipLaunchKernelGGL(k_t_wmat, dim3((unsigned)std::min<long long>((td.cnt[a] * td.Dn[a] + 255) / 256, 4096)), dim3(256), 0, c->stream, td, cs, a,
-                         td.cnt[a], a == d - 1 ? td.first_last : 0ll, (double*)c->tn_W[a].p, a == 0 ? (double*)c->tn_W0t.p : (a == 1 ? (double*)c->tn_W1t.p : (double*)nullptr));
+                         td.cnt[a], a == d - 1 ? td.first_last : 0ll, (double*)c->tn.W[a].p, a == 0 ? (double*)c->tn.W0t.p : (a == 1 ? (double*)c->tn.W1t.p : (double*)nullptr));
     // exact values at the nodes
-    double* nmean = (double*)c->tn_vals.p;
+    double* nmean = (double*)c->tn.vals.p;
     double* nvar = nmean + (size_t)q * Nn;
     double* ngrad = nvar + (size_t)q * Nn;
-    const int W = c->world;
+    const int W = c->dist.world;
     if (W > 1 && td.Dn[d - 1] >= W) {
       // (r04) every rank used to evaluate ALL the nodes -- 3.2 of config D's 13.8 ms that no number of GPUs made shorter.  A slab
       // of the last axis' node planes per rank, one all-gather of the slabs (12 quantities x 3.7 M nodes x 8 B = 354 MB in all
@@ -656,15 +656,15 @@ int launch_posterior_tensor(sbo_ctx* c, const PostRequest& req, bool* declined) 
       long long pre_all = 1;
       for (int a = 0; a < d - 1; ++a) pre_all *= td.Dn[a];
       const long long Nl = pre_all * per;
-      if ((rc = ensure(c->tn_gather, sizeof(double) * (size_t)nq_all * (size_t)Nl * (size_t)(W + 1)))) { if (rc == SBO_E_NOMEM && !multi_rank(c)) break; return rc; }
-      double* slab = (double*)c->tn_gather.p;
+      if ((rc = ensure(c->tn.gather, sizeof(double) * (size_t)nq_all * (size_t)Nl * (size_t)(W + 1)))) { if (rc == SBO_E_NOMEM && !multi_rank(c)) break; return rc; }
+      double* slab = (double*)c->tn.gather.p;
       double* gathered = slab + (size_t)nq_all * Nl;
-      double* axl = (double*)c->tn_pts.p + 4 * 128;
-      hipLaunchKernelGGL(k_t_axes_slab, dim3(1), dim3(128), 0, c->stream, td, (const double*)c->tn_pts.p, c->rank * per, per, axl);
+      double* axl = (double*)c->tn.pts.p + 4 * 128;
+      hipLaunchKernelGGL(k_t_axes_slab, dim3(1), dim3(128), 0, c->stream, td, (const double*)c->tn.pts.p, c->dist.rank * per, per, axl);
       long long cnt[kTMaxD];
       for (int a = 0; a < d; ++a) cnt[a] = a == d - 1 ? per : td.Dn[a];
       if ((rc = launch_posterior_on_axes(c, d, cnt, (const double*)axl, slab, slab + (size_t)q * Nl, slab + (size_t)2 * q * Nl,
-                                         (unsigned long long*)c->tn_scr.p)))
+                                         (unsigned long long*)c->tn.scr.p)))
         return rc;
       if ((rc = comm_allgather_bytes(c, slab, gathered, sizeof(double) * (size_t)nq_all * Nl))) return rc;
       hipLaunchKernelGGL(k_t_unslab, dim3((unsigned)std::min<long long>((Nn * nq_all + 255) / 256, 1 << 16)), dim3(256), 0, c->stream,
@@ -672,17 +672,17 @@ int launch_posterior_tensor(sbo_ctx* c, const PostRequest& req, bool* declined) 
     } else {
       long long cnt[kTMaxD];
       for (int a = 0; a < d; ++a) cnt[a] = td.Dn[a];
-      if ((rc = launch_posterior_on_axes(c, d, cnt, (const double*)c->tn_pts.p, nmean, nvar, ngrad, (unsigned long long*)c->tn_scr.p))) return rc;
+      if ((rc = launch_posterior_on_axes(c, d, cnt, (const double*)c->tn.pts.p, nmean, nvar, ngrad, (unsigned long long*)c->tn.scr.p))) return rc;
     }
     // (the coefficient tails of the node tensors of mean and variance along every axis: the analytic part of the plan's band, below)
     if (probe) {
-      if ((rc = ensure(c->tn_tail, sizeof(unsigned long long) * 2 * kMaxQ * kTMaxD))) return rc;
-      SBO_HIP(hipMemsetAsync(c->tn_tail.p, 0, sizeof(unsigned long long) * 2 * kMaxQ * kTMaxD, c->stream));
+      if ((rc = ensure(c->tn.tail, sizeof(unsigned long long) * 2 * kMaxQ * kTMaxD))) return rc;
+      SBO_HIP(hipMemsetAsync(c->tn.tail.p, 0, sizeof(unsigned long long) * 2 * kMaxQ * kTMaxD, c->stream));
       hipLaunchKernelGGL(k_t_fiber_tail, dim3(kTFibers, (unsigned)d, (unsigned)(2 * q)), dim3(64), 0, c->stream, td, (const double*)nmean, Nn,
-                         0x9e3779b97f4a7c15ull ^ (unsigned long long)c->model_serial, (unsigned long long*)c->tn_tail.p);
+                         0x9e3779b97f4a7c15ull ^ (unsigned long long)c->model_serial, (unsigned long long*)c->tn.tail.p);
     }
     // interpolation: mean, variance (clipped at zero), gradient components -> Lipschitz keys max_a max_x |d MEAN_o / d x_a|
-    c->tn_flops = 0.0;
+    c->tn.flops = 0.0;
     const double* cur = nullptr;
     size_t cur_stride = 0;
     if ((rc = interpolate(c, td, nmean, Nn, 2 * q + nqg, req.sweep_lean, &cur, &cur_stride))) return rc;
@@ -707,8 +707,8 @@ int launch_posterior_tensor(sbo_ctx* c, const PostRequest& req, bool* declined) 
       }
       // probe buffers: indices | points | exact mean, var | interpolated mean, var | exact gradient, interpolated gradient [q d] | keys
       const size_t pbytes = sizeof(long long) * kTProbes + sizeof(double) * ((size_t)kTProbes * (d + 4 * q + 2 * nqg) + kMaxQ);
-      if ((rc = ensure(c->tn_probe, pbytes))) return rc;
-      long long* didx = (long long*)c->tn_probe.p;
+      if ((rc = ensure(c->tn.probe, pbytes))) return rc;
+      long long* didx = (long long*)c->tn.probe.p;
       double* ppts = (double*)(didx + kTProbes);
       double* pexm = ppts + (size_t)kTProbes * d;          // exact mean [q][np], exact var, interpolated mean, interpolated var
       double* pexv = pexm + (size_t)q * kTProbes;
@@ -724,13 +724,13 @@ int launch_posterior_tensor(sbo_ctx* c, const PostRequest& req, bool* declined) 
       hipLaunchKernelGGL(k_t_pick, dim3(8, q), dim3(256), 0, c->stream, (const double*)c->mean.p, (size_t)cs.n_local, (const long long*)didx, kTProbes, pinm);
       hipLaunchKernelGGL(k_t_pick, dim3(8, q), dim3(256), 0, c->stream, (const double*)c->var.p, (size_t)cs.n_local, (const long long*)didx, kTProbes, pinv);
       hipLaunchKernelGGL(k_t_probe_core, dim3((unsigned)(((long long)kTProbes * nqg * 64 + 255) / 256)), dim3(256), 0, c->stream, cur, cur_stride,
-                         td.Dn[0], (const double*)c->tn_W[0].p, (const double*)c->tn_W[1].p, td.cnt[0], td.cnt[1], (const long long*)didx, kTProbes,
+                         td.Dn[0], (const double*)c->tn.W[0].p, (const double*)c->tn.W[1].p, td.cnt[0], td.cnt[1], (const long long*)didx, kTProbes,
                          2 * q, nqg, ping);
-      SBO_HIP(hipMemcpyAsync(pkeys, c->Lmax.p, sizeof(double) * kMaxQ, hipMemcpyDeviceToDevice, c->stream));
+      SBO_HIP(hipMemcpyAsync(pkeys, c->Lmax, sizeof(double) * kMaxQ, hipMemcpyDeviceToDevice, c->stream));
       std::vector<double> h((size_t)(4 * q + 2 * nqg) * kTProbes + kMaxQ);
       double tails[2 * kMaxQ * kTMaxD];
       SBO_HIP(hipMemcpyAsync(h.data(), pexm, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
-      SBO_HIP(hipMemcpyAsync(tails, c->tn_tail.p, sizeof(tails), hipMemcpyDeviceToHost, c->stream));
+      SBO_HIP(hipMemcpyAsync(tails, c->tn.tail.p, sizeof(tails), hipMemcpyDeviceToHost, c->stream));
       SBO_HIP(hipStreamSynchronize(c->stream));
       // deviations per output (un-normalised: the band's units) and the probe error in normalised units (the plan's gate);
       // a value that is not finite fails the gate (NaN compares false)
@@ -791,49 +791,49 @@ int launch_posterior_tensor(sbo_ctx* c, const PostRequest& req, bool* declined) 
         // (REPORTED, not added: with the Lebesgue products of a tensor interpolant the estimate is ~1e3 x the deviations seen at the 2048
         // probes and on whole-grid comparisons with K1g -- 7e-9 against 1e-12 in the variance of a 64^3 grid --, and as a band it would send
         // about a fifth of config D's sweeps into a second pass of their 5.7 ms set phase.  K1t's band stays MEASURED: sbo_profile shows both)
-        c->tn_band[o] = safety * em[o] + 64.0 * eps * std::max(am[o], std::fabs(mc.Y_mean[o]) + mc.Y_std[o]);
-        c->tn_band[kMaxQ + o] = safety * ev[o] + 64.0 * eps * std::max(av[o], mc.sf2[o] * mc.Y_std[o] * mc.Y_std[o]);
-        c->tn_band[2 * kMaxQ + o] = (Lo > 0.0 ? safety * eg[o] / Lo : 0.0) + 1e-13;
-        c->tn_band[3 * kMaxQ + o] = an[0];
-        c->tn_band[4 * kMaxQ + o] = an[1];
-        c->tn_band[5 * kMaxQ + o] = em[o];
-        c->tn_band[6 * kMaxQ + o] = ev[o];
+        c->tn.band[o] = safety * em[o] + 64.0 * eps * std::max(am[o], std::fabs(mc.Y_mean[o]) + mc.Y_std[o]);
+        c->tn.band[kMaxQ + o] = safety * ev[o] + 64.0 * eps * std::max(av[o], mc.sf2[o] * mc.Y_std[o] * mc.Y_std[o]);
+        c->tn.band[2 * kMaxQ + o] = (Lo > 0.0 ? safety * eg[o] / Lo : 0.0) + 1e-13;
+        c->tn.band[3 * kMaxQ + o] = an[0];
+        c->tn.band[4 * kMaxQ + o] = an[1];
+        c->tn.band[5 * kMaxQ + o] = em[o];
+        c->tn.band[6 * kMaxQ + o] = ev[o];
       }
-      c->tn_valid = true;
-      c->tn_model = c->model_serial;
-      c->tn_first = cs.first;
-      c->tn_nlocal = cs.n_local;
-      memcpy(c->tn_count, cs.count, sizeof(long long) * kTMaxD);
-      memcpy(c->tn_lo, cs.lo, sizeof(double) * kTMaxD);
-      memcpy(c->tn_hi, cs.hi, sizeof(double) * kTMaxD);
+      c->tn.valid = true;
+      c->tn.model = c->model_serial;
+      c->tn.first = cs.first;
+      c->tn.nlocal = cs.n_local;
+      memcpy(c->tn.count, cs.count, sizeof(long long) * kTMaxD);
+      memcpy(c->tn.lo, cs.lo, sizeof(double) * kTMaxD);
+      memcpy(c->tn.hi, cs.hi, sizeof(double) * kTMaxD);
       for (int a = 0; a < d; ++a) {
-        c->tn_level[a] = std::min(ladder_size(a) - 1, level0[a] + attempt);
-        c->tn_dn[a] = td.Dn[a];
+        c->tn.level[a] = std::min(ladder_size(a) - 1, level0[a] + attempt);
+        c->tn.dn[a] = td.Dn[a];
       }
-      c->tn_usable = ok_all != 0ull;
-      c->tn_lean_probe = req.sweep_lean && q >= 2;
-      if (!c->tn_usable) continue;           // one step up the ladder, or give up
-      if (attempt > 0) c->tn_bump = std::min(2, c->tn_bump + 1);
+      c->tn.usable = ok_all != 0ull;
+      c->tn.lean_probe = req.sweep_lean && q >= 2;
+      if (!c->tn.usable) continue;           // one step up the ladder, or give up
+      if (attempt > 0) c->tn.bump = std::min(2, c->tn.bump + 1);
     }
     *declined = false;
     c->last_k1 = 5;
-    if (c->guard_band) {
-      if ((rc = guard_band_host(c, c->tn_band, c->tn_band + kMaxQ, c->tn_band + 2 * kMaxQ, c->tn_band + 3 * kMaxQ))) return rc;   // (whoever used the block last)
-      c->gb_active = true;
+    if (c->opt.guard_band) {
+      if ((rc = guard_band_host(c, c->tn.band, c->tn.band + kMaxQ, c->tn.band + 2 * kMaxQ, c->tn.band + 3 * kMaxQ))) return rc;   // (whoever used the block last)
+      c->gb.active = true;
     }
     // flops issued: node posterior (block-triangular contraction) + interpolation sums
-    c->last_k1_flops = (double)q * mc.npad * (mc.npad + 16.0) * (double)Nn / (double)((c->world > 1 && td.Dn[d - 1] >= c->world) ? c->world : 1) +
-                       c->tn_flops;
+    c->last_k1_flops = (double)q * mc.npad * (mc.npad + 16.0) * (double)Nn / (double)((c->dist.world > 1 && td.Dn[d - 1] >= c->dist.world) ? c->dist.world : 1) +
+                       c->tn.flops;
     return SBO_OK;
   }
-  c->tn_valid = true;
-  c->tn_usable = false;
-  c->tn_model = c->model_serial;
-  c->tn_first = cs.first;
-  c->tn_nlocal = cs.n_local;
-  memcpy(c->tn_count, cs.count, sizeof(long long) * kTMaxD);
-  memcpy(c->tn_lo, cs.lo, sizeof(double) * kTMaxD);
-  memcpy(c->tn_hi, cs.hi, sizeof(double) * kTMaxD);
+  c->tn.valid = true;
+  c->tn.usable = false;
+  c->tn.model = c->model_serial;
+  c->tn.first = cs.first;
+  c->tn.nlocal = cs.n_local;
+  memcpy(c->tn.count, cs.count, sizeof(long long) * kTMaxD);
+  memcpy(c->tn.lo, cs.lo, sizeof(double) * kTMaxD);
+  memcpy(c->tn.hi, cs.hi, sizeof(double) * kTMaxD);
   return SBO_OK;
 }
 
