@@ -101,8 +101,8 @@ typedef struct sbo_safeopt_result {
   double  minimizer_x[SBO_MAX_D];
   double  minimizer_std;
   /* Expander(): per constraint argmax_{G_c} var_0, most uncertain kept   models/SafeOpt.py:90-124         */
-  int64_t expander_index_c[SBO_MAX_Q];   /* [c-1], -1 when G_c is empty                                   */
-  double  expander_std_c[SBO_MAX_Q];
+  int64_t expander_index_c[SBO_MAX_Q];   /* [c-1], -1 when G_c is empty; -1 past entry q-2 as well         */
+  double  expander_std_c[SBO_MAX_Q];     /* [c-1], 0 when G_c is empty; 0 past entry q-2 (count_G too)     */
   int32_t expander_best_c;               /* constraint index of the kept expander, 0 when none            */
   int64_t expander_index;
   double  expander_x[SBO_MAX_D];
@@ -128,8 +128,9 @@ typedef struct sbo_goose_result {
   int64_t safe_min_index;                /* argmin_{S_t} lcb_0            models/GoOSE.py:63-67            */
   double  safe_min_x[SBO_MAX_D];
   double  safe_min_lcb;
-  int64_t target_index_c[SBO_MAX_Q];     /* per constraint argmin_{O_c} lcb_0, -1 when empty   :82-112    */
-  double  target_lcb_c[SBO_MAX_Q];
+  int64_t target_index_c[SBO_MAX_Q];     /* per constraint argmin_{O_c} lcb_0, -1 when empty   :82-112;
+                                            -1 past entry q-2 as well                                      */
+  double  target_lcb_c[SBO_MAX_Q];       /* [c-1], +inf when O_c is empty; 0 past entry q-2 (count_O too) */
   int32_t target_best_c;
   int64_t target_index;
   double  target_x[SBO_MAX_D];

@@ -2168,7 +2168,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v
   if (o->lean && q >= 2) res->L[0] = 0.0;
   res->minimizer_index = -1;
   res->expander_index = -1;
-  for (int cc = 1; cc < q; ++cc) res->expander_index_c[cc - 1] = -1;
+  for (int cc = 1; cc <= kMaxQ; ++cc) res->expander_index_c[cc - 1] = -1;   // (entries past q - 1 too: no such constraint)
   if (h.count_S == 0) return fail(SBO_E_EMPTY_SAFE_SET, "safe set S_t is empty on this candidate set");
   res->u_star = ord_val(h.ustar_key);
   res->minimizer_index = h.arg_idx[0];
@@ -2599,7 +2599,7 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   c->gb.first = h.n_guard;
   for (int i = 0; i < q; ++i) memcpy(&res->L[i], &Lk[i], 8);
   res->safe_min_index = res->target_index = res->explore_index = -1;
-  for (int cc = 1; cc < q; ++cc) res->target_index_c[cc - 1] = -1;
+  for (int cc = 1; cc <= kMaxQ; ++cc) res->target_index_c[cc - 1] = -1;     // (entries past q - 1 too: no such constraint)
   if (h.count_S == 0) return fail(SBO_E_EMPTY_SAFE_SET, "safe set S_t is empty on this candidate set");
   res->safe_min_index = h.arg_idx[0];
   res->safe_min_lcb = h.arg_val[0];

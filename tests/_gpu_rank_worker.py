@@ -13,6 +13,19 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 
 
+def _config(cfg_name, n):
+    """A BASELINE.json config, or "mc:<q>": the fan model of tests/many_constraints.py with q - 1 constraints (case "q<q>")."""
+    if cfg_name.startswith("mc:"):
+        import many_constraints
+        q = int(cfg_name[3:])
+        k = many_constraints.CASES[f"q{q}"]
+        assert n == k["n"]
+        lo, hi = many_constraints.box(k["d"])
+        return {"ds": many_constraints.model(f"q{q}"), "bound": np.stack([lo, hi], axis=1), "q": q}
+    from safebo_amd import synthetic
+    return synthetic.make_config(cfg_name, n=n)
+
+
 def main():
     rank, world, port, out_path, cfg_name, n, count, b = (int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4],
                                                           sys.argv[5], int(sys.argv[6]), json.loads(sys.argv[7]), json.loads(sys.argv[8]))
@@ -35,7 +48,7 @@ def main():
         lo, hi, _ = tie_cases.mirror_grid(grid)
         cfg = {"ds": tie_cases.mirror_model(q=int(q), n=n), "bound": np.stack([lo, hi], axis=1), "q": int(q)}
     else:
-        cfg = synthetic.make_config(cfg_name, n=n)
+        cfg = _config(cfg_name, n)
     eng = safebo_amd.SweepEngine(0)
     distributed.join(eng, dist, relay=True)
     if tie:
@@ -87,7 +100,7 @@ def sequence(rank, world, port, out_path, cfg_name, n, count, bs):
     from safebo_amd import synthetic, distributed
 
     dist = distributed.init_from_env()
-    cfg = synthetic.make_config(cfg_name, n=n)
+    cfg = _config(cfg_name, n)
     eng = safebo_amd.SweepEngine(0)
     distributed.join(eng, dist, relay=True)
     eng.set_grid_sharded(cfg["bound"][:, 0], cfg["bound"][:, 1], count)
