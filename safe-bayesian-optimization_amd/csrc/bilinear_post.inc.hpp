@@ -605,65 +605,116 @@ __global__ __launch_bounds__(128) void k_bl_enclose(const double* __restrict__ m
 // need a workgroup -- a 1-D grid, workgroup i takes entry i and exits at once past the list -- so the evaluated tiles are dispatched
 // first and fit the CUs in one round.  What a left-out tile produced is written here, bit for bit what its workgroup wrote.
 //
-// The constraint's tiles, one wave each (before the constraint's launch): the skip decision of k_bpost (encl_unsafe on every cell of
-// the tile, at this sweep's b and band) and the gradient gate's decision for output 1.  cls: 0 = skipped, no gradient phase (written
-// here: S = 0 and U = all ones words, its Lipschitz row, its partial row of the classification -- |U| = 8192, no keys; Usum and the
-// slot block in k_bl_sched_list1); 1 = evaluated with gradient phases, 2 = skipped but runs gradient phases, 3 = evaluated.  The skip
-// byte of every tile for the audit (guard.hip).
-__global__ __launch_bounds__(256) void k_bl_sched_tiles1(const ModelConst mc, const double* __restrict__ encl, int ntiles, int tgx, int tgy,
+// The constraint's tiles, one wave each, kSchedWaves to a workgroup (before the constraint's launch): the skip decision of k_bpost (encl_unsafe on every cell of
+// the tile, at this sweep's b and band) and the gradient gate's decision for output 1.  Class 0 = skipped, no gradient phase: no
+// workgroup; written here is what its workgroup wrote -- S = 0 and U = all ones words, its bit of Usum in its 128 columns, its
+// Lipschitz row, its partial row of the classification (|U| = 8192, no keys) and its scalars in the slot block (|U|, the Lipschitz
+// key, the skip count).  1 = evaluated with gradient phases, 2 = skipped but runs gradient phases, 3 = evaluated: these go into the
+// list.  The skip byte of every tile for the audit (guard.hip).
+//
+// The list has two ends: classes 1 and 2 -- the tiles with gradient phases, the longest -- fill the front upwards, class 3 fills the
+// back downwards, each end behind a counter bumped by one atomic per listed tile; bit 31 of an entry marks class 2.  One pair of
+// counters took config H's 738 returning atomics on two addresses: the kernel ran 13.8 us against the 7.1 us it takes without a
+// list (profiles/sched_head_H_timeline.txt, variant A; B and C for the figures below).  So the list is kTlistShards lists of that form (PostExtra::tlist): of every kTlistShards consecutive tiles each goes to
+// another shard -- rotated by three from one such block to the next, so that a band of unsafe tile columns does not leave the same
+// shards short: shards of unequal length put workgroups that exit at once between the launch's real ones, which cost k_bpost<1, 1>
+// 6 us when whole classifier workgroups shared a shard --, a shard has room for its share of the tiles (cap), and workgroup i of the
+// launch takes entry i / kTlistShards of shard i mod kTlistShards -- front entries upwards, then the back entries from the last one
+// down (k_bpost) --, so the long tiles are still dispatched first.  The order inside an end is whatever the atomics give, and no result depends on it: a tile's words, partial row,
+// Lipschitz row and slot (tile mod kColSlots) depend on the tile alone, and every merge into the slot block and into Usum is an
+// integer add, an OR, or a min / max of ordered keys.
+// The counters are zero when this kernel starts: k_bl_sched_list2, which follows the constraint's launch in every sweep that runs
+// this kernel, resets them once the list is dead (ColPath::sched_clean).  Usum is zero as well (col_words_prepare, k_col_decide), as
+// the launch over the whole tile grid needs it; the listed tiles OR their bits in behind.
+// The slot block: one atomic per scalar and tile -- config H's 3900 on the twelve cache lines of three fields -- took 4 of the kernel's
+// 10.5 us; the kSchedWaves tiles of a workgroup are merged in LDS first and join one slot (sums and a maximum: the slot does not
+// change them).  The 128 ORs per tile into Usum cost nothing measurable (they spread over 4096 words).
+constexpr int kSchedWaves = 8;
+__global__ __launch_bounds__(64 * kSchedWaves) void k_bl_sched_tiles1(const ModelConst mc, const double* __restrict__ encl, int ntiles, int tgx, int tgy,
                                                          unsigned int cnt0, double bconf, const GuardBand* __restrict__ gb,
                                                          const double* __restrict__ gtmax, const unsigned long long* __restrict__ gkey, int q,
-                                                         uint8_t* __restrict__ skip, uint8_t* __restrict__ cls, unsigned long long* __restrict__ Sw,
-                                                         unsigned long long* __restrict__ Uw, double* __restrict__ Lpart,
+                                                         uint8_t* __restrict__ skip, unsigned int* __restrict__ list, int cap, unsigned long long* __restrict__ Sw,
+                                                         unsigned long long* __restrict__ Uw, unsigned long long* __restrict__ Usum,
+                                                         unsigned long long* __restrict__ slots, double* __restrict__ Lpart,
                                                          unsigned long long* __restrict__ cpart, int pcap) {
-  const int lane = threadIdx.x & 63, tile = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-  if (tile >= ntiles) return;
-  const double bb = bconf * bconf;
-  const bool gb_on = gb != nullptr;
-  const LcbBand lb = gb_on ? lcb_band(bb, gb->dm[1], gb->dv[1]) : LcbBand{0.0, 0.0};
-  bool ok = true;
+  __shared__ unsigned long long sh_key[kSchedWaves];      // per wave: the Lipschitz key of a class-0 tile (0: none)
+  __shared__ unsigned int sh_cnt[kSchedWaves];            // ... bit 0: a class-0 tile, bit 1: a skipped tile (class 0 or 2)
+  const int lane = threadIdx.x & 63, wave = (int)(threadIdx.x >> 6), tile = (int)blockIdx.x * kSchedWaves + wave;
+  unsigned long long my_key = 0ull;
+  unsigned int my_cnt = 0u;
+  if (tile < ntiles) {                                    // (a whole wave or none of it)
+    const double bb = bconf * bconf;
+    const bool gb_on = gb != nullptr;
+    const LcbBand lb = gb_on ? lcb_band(bb, gb->dm[1], gb->dv[1]) : LcbBand{0.0, 0.0};
+    bool ok = true;
 #pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const double4 e = reinterpret_cast<const double4*>(encl)[(size_t)tile * 128 + h * 64 + lane];
-    ok = ok && encl_unsafe(e.x, e.y, e.z, e.w, bconf, bb, gb_on, lb);
-  }
-  const bool dec = __ballot(!ok) == 0ull;
-  // (k_bpost's gate, output 1, and the largest coarse sample it folds in)
-  bool run2 = true, run3 = true;
-  double gfold = 0.0;
-  if (gtmax) {
-    const size_t nt = (size_t)ntiles;
-    const double* slack = gtmax + (size_t)q * 2 * nt;
-    const double ystd = mc.Y_std[1];
-    const double cg0 = ystd * mc.inv_ell[1][0] * mc.X_rstd[0], cg1 = ystd * mc.inv_ell[1][1] * mc.X_rstd[1];
-    const double t0 = gtmax[(size_t)2 * nt + tile], t1 = gtmax[(size_t)3 * nt + tile];
-    const double G0 = __longlong_as_double((long long)gkey[2]), G1 = __longlong_as_double((long long)gkey[3]);
-    run2 = !(t0 + slack[2] < G0 * (1.0 - 1e-12));
-    run3 = !(t1 + slack[3] < G1 * (1.0 - 1e-12));
-    gfold = fmax(fabs(cg0 * t0), fabs(cg1 * t1));
-  }
-  const bool grad = run2 || run3;
-  const unsigned int k = dec ? (grad ? 2u : 0u) : (grad ? 1u : 3u);
-  if (lane == 0) {
-    skip[tile] = dec ? 1 : 0;
-    cls[tile] = (uint8_t)k;
-  }
-  if (k != 0u) return;
-  const int bx = tile % tgx, by = tile / tgx;
-  const size_t w0 = (size_t)by * cnt0 + (size_t)bx * 128;
+    for (int h = 0; h < 2; ++h) {
+      const double4 e = reinterpret_cast<const double4*>(encl)[(size_t)tile * 128 + h * 64 + lane];
+      ok = ok && encl_unsafe(e.x, e.y, e.z, e.w, bconf, bb, gb_on, lb);
+    }
+    const bool dec = __ballot(!ok) == 0ull;
+    // (k_bpost's gate, output 1, and the largest coarse sample it folds in)
+    bool run2 = true, run3 = true;
+    double gfold = 0.0;
+    if (gtmax) {
+      const size_t nt = (size_t)ntiles;
+      const double* slack = gtmax + (size_t)q * 2 * nt;
+      const double ystd = mc.Y_std[1];
+      const double cg0 = ystd * mc.inv_ell[1][0] * mc.X_rstd[0], cg1 = ystd * mc.inv_ell[1][1] * mc.X_rstd[1];
+      const double t0 = gtmax[(size_t)2 * nt + tile], t1 = gtmax[(size_t)3 * nt + tile];
+      const double G0 = __longlong_as_double((long long)gkey[2]), G1 = __longlong_as_double((long long)gkey[3]);
+      run2 = !(t0 + slack[2] < G0 * (1.0 - 1e-12));
+      run3 = !(t1 + slack[3] < G1 * (1.0 - 1e-12));
+      gfold = fmax(fabs(cg0 * t0), fabs(cg1 * t1));
+    }
+    const bool grad = run2 || run3;
+    const unsigned int k = dec ? (grad ? 2u : 0u) : (grad ? 1u : 3u);
+    if (lane == 0) skip[tile] = dec ? 1 : 0;
+    my_cnt = k == 0u ? 3u : (k == 2u ? 2u : 0u);
+    if (k != 0u) {
+      if (lane == 0) {
+        // (p < cap whenever the counters started from zero; the test keeps a store inside the shard whatever they held)
+        const unsigned int sh = ((unsigned int)tile + 3u * ((unsigned int)tile >> kTlistShift)) & (kTlistShards - 1);
+        const unsigned int p = atomicAdd(&list[sh * kTlistHead + (k == 3u ? 1 : 0)], 1u);
+        if (p < (unsigned int)cap)
+          list[kTlistShards * kTlistHead + sh * cap + (k == 3u ? (unsigned int)(cap - 1) - p : p)] = (unsigned int)tile | (k == 2u ? 0x80000000u : 0u);
+      }
+    } else {
+      const int bx = tile % tgx, by = tile / tgx;
+      const size_t w0 = (size_t)by * cnt0 + (size_t)bx * 128;
 #pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    Sw[w0 + h * 64 + lane] = 0ull;
-    Uw[w0 + h * 64 + lane] = ~0ull;
+      for (int h = 0; h < 2; ++h) {
+        Sw[w0 + h * 64 + lane] = 0ull;
+        Uw[w0 + h * 64 + lane] = ~0ull;
+        atomicOr(&Usum[(size_t)bx * 128 + h * 64 + lane], 1ull << by);      // (no return value: the wave does not wait for it)
+      }
+      const double lrow = fmax(0.0, gfold);
+      my_key = (unsigned long long)__double_as_longlong(lrow);               // (the key in post_partials' encoding)
+      if (lane == 0) Lpart[((size_t)tgy + by) * tgx + bx] = lrow;
+      // (post_partials' row of a tile with every candidate in U: no safe candidate, no decision in the band, no keys)
+      if (lane < kFuseRow) {
+        unsigned long long v = 0ull;
+        if (lane == 0) v = ~0ull;
+        else if (lane == 2) v = 64ull * 128ull;
+        else if (lane >= kFuseVmin && lane < kFuseRmax) v = ~0ull;
+        cpart[(size_t)lane * pcap + tile] = v;
+      }
+    }
   }
-  if (lane == 0) Lpart[((size_t)tgy + by) * tgx + bx] = fmax(0.0, gfold);
-  // (post_partials' row of a tile with every candidate in U: no safe candidate, no decision in the band, no keys)
-  if (lane < kFuseRow) {
-    unsigned long long v = 0ull;
-    if (lane == 0) v = ~0ull;
-    else if (lane == 2) v = 64ull * 128ull;
-    else if (lane >= kFuseVmin && lane < kFuseRmax) v = ~0ull;
-    cpart[(size_t)lane * pcap + tile] = v;
+  if (lane == 0) { sh_key[wave] = my_key; sh_cnt[wave] = my_cnt; }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    unsigned long long key = 0ull, n0 = 0ull, nskip = 0ull;
+#pragma unroll
+    for (int w = 0; w < kSchedWaves; ++w) {
+      key = sh_key[w] > key ? sh_key[w] : key;
+      n0 += sh_cnt[w] & 1u;
+      nskip += sh_cnt[w] >> 1;
+    }
+    const int slot = (int)(blockIdx.x & (kColSlots - 1));
+    if (threadIdx.x == 0 && n0) atomicAdd(&slots[(size_t)kSlotU * kColSlots + slot], 64ull * 128ull * n0);
+    if (threadIdx.x == 1 && n0) atomicMax(&slots[(size_t)kSlotL1 * kColSlots + slot], key);
+    if (threadIdx.x == 2 && nskip) atomicAdd(&slots[(size_t)kSlotSkip * kColSlots + slot], nskip);
   }
 }
 
@@ -696,61 +747,13 @@ __device__ __forceinline__ unsigned int sched_rank3(int k, unsigned int (&base)[
   return r;
 }
 
-// The constraint's list (one workgroup, behind k_bl_sched_tiles1): classes 1, 2, 3 in that order -- the tiles with gradient phases,
-// the longest, first --, tile order within a class.  The skipped tiles' shares of the set phase's inputs: Usum (bit by of every
-// column of tile (bx, by) without a workgroup; plain stores -- the launch's own tiles OR theirs in behind), |U|, the skip count and
-// the Lipschitz key into slot 0 (sums and a maximum: the slot a tile joins does not change them).
-__global__ __launch_bounds__(1024) void k_bl_sched_list1(const uint8_t* __restrict__ cls, int ntiles, int tgx, const double* __restrict__ Lpart1,
-                                                         unsigned int* __restrict__ list, unsigned long long* __restrict__ Usum,
-                                                         unsigned long long* __restrict__ slots) {
-  __shared__ unsigned int sh[3 * 16];
-  __shared__ unsigned long long umask[64];
-  __shared__ unsigned long long lmax;
-  __shared__ unsigned int nlight;
-  const int t = threadIdx.x;
-  if (t < 64) umask[t] = 0ull;
-  if (t == 0) { lmax = 0ull; nlight = 0u; }
-  __syncthreads();
-  // (two passes: the counts per class first, so that classes 2 and 3 start behind every tile of the classes before them)
-  unsigned int cnt[3] = {0u, 0u, 0u};
-  for (int r = 0; r * 1024 < ntiles; ++r) {
-    const int i = r * 1024 + t;
-    (void)sched_rank3(i < ntiles ? (int)cls[i] - 1 : -1, cnt, sh);
-  }
-  unsigned int base[3] = {0u, cnt[0], cnt[0] + cnt[1]};
-  unsigned int nl = 0u;
-  unsigned long long gm = 0ull;
-  for (int r = 0; r * 1024 < ntiles; ++r) {
-    const int i = r * 1024 + t;
-    const int k = i < ntiles ? (int)cls[i] - 1 : -1;
-    const unsigned int p = sched_rank3(k, base, sh);
-    if (k >= 0) list[1 + p] = (unsigned int)i | (k == 1 ? 0x80000000u : 0u);
-    if (i < ntiles && k < 0) {
-      ++nl;
-      atomicOr(&umask[i % tgx], 1ull << (i / tgx));
-      const unsigned long long g = (unsigned long long)__double_as_longlong(Lpart1[i]);
-      gm = g > gm ? g : gm;
-    }
-  }
-  if (nl) { atomicAdd(&nlight, nl); atomicMax(&lmax, gm); }
-  if (t == 0) list[0] = cnt[0] + cnt[1] + cnt[2];
-  __syncthreads();
-  for (int c = t; c < tgx * 128; c += 1024) Usum[c] = umask[c >> 7];
-  if (t == 0) {
-    const unsigned long long nskip = (unsigned long long)nlight + cnt[1];
-    if (nlight) {
-      atomicAdd(&slots[(size_t)kSlotU * kColSlots], 64ull * 128ull * nlight);
-      atomicMax(&slots[(size_t)kSlotL1 * kColSlots], lmax);
-    }
-    if (nskip) atomicAdd(&slots[(size_t)kSlotSkip * kColSlots], nskip);
-  }
-}
-
 // The objective's list (one workgroup, behind the constraint's launch): the tiles that hold a safe candidate (field 1 of the
 // constraint's partial rows), in tile order.  The others' objective rows as their workgroups wrote them in a lean-2 sweep (no safe
-// candidate, no gradient phase): no u* key, no range of lcb_0, no variance key, Lipschitz row 0.
+// candidate, no gradient phase): no u* key, no range of lcb_0, no variance key, Lipschitz row 0.  One shard, one end: [1] = 0.
+// It also resets the counters of the constraint's list (`head1`), which is dead by now -- the constraint's launch, its only reader,
+// has finished on this stream --, for the next sweep's k_bl_sched_tiles1.
 __global__ __launch_bounds__(1024) void k_bl_sched_list2(unsigned long long* __restrict__ cpart, int pcap, int ntiles, unsigned int* __restrict__ list,
-                                                         double* __restrict__ Lpart0) {
+                                                         double* __restrict__ Lpart0, unsigned int* __restrict__ head1) {
   __shared__ unsigned int sh[3 * 16];
   const int t = threadIdx.x;
   const unsigned long long* nS = cpart + (size_t)1 * pcap;
@@ -761,7 +764,7 @@ __global__ __launch_bounds__(1024) void k_bl_sched_list2(unsigned long long* __r
     const bool in = i < ntiles, has = in && nS[i] != 0ull;
     const unsigned int p = sched_rank3(has ? 0 : -1, base, sh);
     if (has) {
-      list[1 + p] = (unsigned int)i;
+      list[kTlistHead + p] = (unsigned int)i;
     } else if (in) {
       Lpart0[i] = 0.0;
 #pragma unroll
@@ -769,7 +772,11 @@ __global__ __launch_bounds__(1024) void k_bl_sched_list2(unsigned long long* __r
         orow[(size_t)lane * pcap + i] = (lane <= 1 || (lane >= kFuseVmin && lane < kFuseRmax)) ? ~0ull : 0ull;
     }
   }
-  if (t == 0) list[0] = base[0];
+  if (t == 0) {
+    list[0] = base[0];
+    list[1] = 0u;
+  }
+  if (t < kTlistShards) head1[t * kTlistHead] = head1[t * kTlistHead + 1] = 0u;
 }
 
 // RB: row blocks per wave.  2 = the 128 x 128 tile above; 1 = a 64 x 128 tile for grids whose 128 x 128 tiles would leave
@@ -800,13 +807,17 @@ __global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelCon
   const bool listed = ROLE != 0 && px.tlist != nullptr;
   unsigned int ent = 0u;
   if (listed) {
-    if (blockIdx.x >= px.tlist[0]) {
+    // (shard i mod 2^tshift, entry i >> tshift of it: the front entries upwards, then the back entries from the last one down --
+    // k_bl_sched_tiles1)
+    const unsigned int sh = blockIdx.x & ((1u << px.tshift) - 1u), at = blockIdx.x >> px.tshift;
+    const unsigned int nfront = px.tlist[sh * kTlistHead], nback = px.tlist[sh * kTlistHead + 1];
+    if (at >= nfront + nback) {
 #ifdef SBO_PHASE_CLOCKS
       if (threadIdx.x == 0) { const unsigned long long t_ = wall_clock64(); wg_trace_row(o, t_, t_, t_, 0xffffffu, 3u); }
 #endif
       return;                                   // (past the list: the tile was written by the list's kernels)
     }
-    ent = px.tlist[1 + blockIdx.x];
+    ent = px.tlist[(kTlistHead << px.tshift) + sh * (unsigned int)px.tcap + (at < nfront ? at : (unsigned int)px.tcap - 1u - (at - nfront))];
   }
   const unsigned int tgx = listed ? (unsigned int)px.tgx : gridDim.x, tgy = listed ? (unsigned int)px.tgy : gridDim.y;
   const unsigned int bx = listed ? (ent & 0xffffffu) % tgx : blockIdx.x, by = listed ? (ent & 0xffffffu) / tgx : blockIdx.y;
@@ -1203,8 +1214,8 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
   }
   bool record_encl = false;
   double* encl = nullptr;
-  uint8_t* sched_cls = nullptr;
   unsigned int *sched_l1 = nullptr, *sched_l2 = nullptr;
+  int sched_cap1 = 0;
   if (colw && !interp) {
     // r06: the constraint's enclosures per 8 x 8 cell (per plan) and a skip byte per tile (per sweep); a lean-2 sweep hands them to
     // the constraint's launch once the plan's first launch has recorded them
@@ -1222,14 +1233,22 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
       c->k1_skip_armed = true;
     }
     // r07: lean 2 -- the objective's launch over the tiles with a safe candidate, and, once the enclosures decide skips, the
-    // constraint's over the tiles that need a workgroup (k_bl_sched_tiles1 and on).  [class bytes][list 1][list 2]
+    // constraint's over the tiles that need a workgroup (k_bl_sched_tiles1 and on).  [list 1: kTlistShards shards][list 2: one],
+    // PostExtra::tlist: the constraint's counters stay at the head of the buffer whatever the grid
     if (c->opt.k1_sched && req.col_lean >= 2) {
-      if ((rc = ensure(c->bl_sched, ((ntiles + 15) & ~(size_t)15) + 2 * sizeof(unsigned int) * (ntiles + 1)))) return rc;
-      sched_cls = (uint8_t*)c->bl_sched.p;
-      sched_l1 = (unsigned int*)(sched_cls + ((ntiles + 15) & ~(size_t)15));
-      sched_l2 = sched_l1 + ntiles + 1;
+      // (of every kTlistShards consecutive tiles a shard gets one)
+      sched_cap1 = (int)((ntiles + kTlistShards - 1) / kTlistShards);
+      const size_t words1 = (size_t)kTlistShards * (kTlistHead + (size_t)sched_cap1);
+      const void* had = c->bl_sched.p;
+      if ((rc = ensure(c->bl_sched, sizeof(unsigned int) * (words1 + kTlistHead + ntiles)))) return rc;
+      if (c->bl_sched.p != had) c->col.sched_clean = false;
+      sched_l1 = (unsigned int*)c->bl_sched.p;
+      sched_l2 = sched_l1 + words1;
     }
   }
+  // (the flag is set again by col_set_phase, once a sweep whose k_bl_sched_list2 reset the counters has come through)
+  const bool sched_zero = c->col.sched_clean;
+  if (colw) c->col.sched_clean = false;
   // (K1i: stage 1 behind col_words_prepare -- the gradient launch, which follows it on another stream, merges into the slot block)
   if (interp) stage1();
   if (defer && g.band_ready) SBO_HIP(hipStreamWaitEvent(c->stream, c->ev_grad[3], 0));     // (the band: written on Y beside stage 1)
@@ -1257,24 +1276,29 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
     px.o0 = colw ? 1 - part : 0;
     const bool last = !colw || part == 1;
     auto kpost = !colw ? k_bpost<1, 0> : (part == 0 ? k_bpost<1, 1> : k_bpost<1, 2>);
-    // r07: the tile lists (k_bl_sched_tiles1 / _list1 / _list2), built on this stream right in front of the launch that reads them
+    // r07: the tile lists (k_bl_sched_tiles1 / k_bl_sched_list2), built on this stream right in front of the launch that reads them
     px.tlist = nullptr;
     if (sched_l1 && part == 0 && px.encl) {
-      hipLaunchKernelGGL(k_bl_sched_tiles1, dim3((gx * gy + 3) / 4), dim3(256), 0, c->stream, mc, (const double*)px.encl, (int)(gx * gy), (int)gx,
-                         (int)gy, (unsigned int)cnt0, req.fuse_b, gb_fused, g.gtmax, g.gkey, q, px.skip, sched_cls, px.cb.Sw, px.cb.Uw,
-                         lrows, (unsigned long long*)c->cpart.p, c->cpart_cap);
-      hipLaunchKernelGGL(k_bl_sched_list1, dim3(1), dim3(1024), 0, c->stream, (const uint8_t*)sched_cls, (int)(gx * gy), (int)gx,
-                         (const double*)lrows + (size_t)rows_out, sched_l1, px.cb.Usum, px.cb.slots);
+      // (the list's counters: zero from the last sweep's k_bl_sched_list2 -- a fill only for a new buffer or after a sweep that failed)
+      if (!sched_zero) SBO_HIP(hipMemsetAsync(sched_l1, 0, sizeof(unsigned int) * kTlistShards * kTlistHead, c->stream));
+      hipLaunchKernelGGL(k_bl_sched_tiles1, dim3((gx * gy + kSchedWaves - 1) / kSchedWaves), dim3(64 * kSchedWaves), 0, c->stream, mc, (const double*)px.encl, (int)(gx * gy), (int)gx,
+                         (int)gy, (unsigned int)cnt0, req.fuse_b, gb_fused, g.gtmax, g.gkey, q, px.skip, sched_l1, sched_cap1, px.cb.Sw, px.cb.Uw,
+                         px.cb.Usum, px.cb.slots, lrows, (unsigned long long*)c->cpart.p, c->cpart_cap);
       px.tlist = sched_l1;
+      px.tshift = kTlistShift;
+      px.tcap = sched_cap1;
     }
     if (sched_l2 && part == 1) {
       hipLaunchKernelGGL(k_bl_sched_list2, dim3(1), dim3(1024), 0, c->stream, (unsigned long long*)c->cpart.p, c->cpart_cap, (int)(gx * gy), sched_l2,
-                         lrows);
+                         lrows, sched_l1);
       px.tlist = sched_l2;
+      px.tshift = 0;
+      px.tcap = (int)(gx * gy);
+      out.col_sched = true;
     }
     px.tgx = (int)gx;
     px.tgy = (int)gy;
-    const dim3 grid = px.tlist ? dim3(gx * gy) : dim3(gx, gy, (unsigned)(colw ? 1 : q));
+    const dim3 grid = px.tlist ? dim3((unsigned)px.tcap << px.tshift) : dim3(gx, gy, (unsigned)(colw ? 1 : q));
     hipExtLaunchKernelGGL(kpost, grid, dim3(256), lds, c->stream, nullptr,
                           (req.lmax_defer && last) ? c->ev[1] : ((colw && part == 0) ? c->col.ev[0] : nullptr), 0,
                           mc, cs, g.BtA, g.sBtA, g.P0f, g.sP0f, g.VA, g.sVA, g.SBf, g.sSBf, g.KB0, g.KS0, g.KBm, g.KSm, g.KBm2, g.nrb, g.ncs0,

@@ -112,6 +112,7 @@ enum ColSlotField { kSlotUmin = 0 /* min key of ucb_0 over S */, kSlotS, kSlotU,
                     kSlotRowMask /* word s: bit t set iff tile t of tile row s holds a safe candidate */,
                     kSlotSkip /* count: constraint tiles its enclosure proved unsafe, left unevaluated (r06) */, kColSlotFields };
 __host__ __device__ inline bool col_slot_is_min(int f) { return f == kSlotUmin || f == kSlotVmin0 || f == kSlotVmin1; }
+constexpr int kTlistShift = 5, kTlistShards = 1 << kTlistShift, kTlistHead = 32;     // PostExtra::tlist (the constraint's list; the objective's has one shard)
 // what a k_bpost launch is told beyond its operands (r05: one launch per output on the column path)
 struct PostExtra {
   int o0;        // first output of this launch (blockIdx.z counts from it)
@@ -124,10 +125,14 @@ struct PostExtra {
   // (k_bl_enclose), and one byte per tile that says whether the tile was left unevaluated; nullptr: every tile is evaluated
   const double* encl;
   uint8_t* skip;
-  // lean >= 2, k1_sched (r07): nullptr, or the tile list of this launch -- [0] = entries, then one entry per workgroup of a 1-D grid:
-  // the tile (by * tgx + bx) in bits 0..23, bit 31 = a constraint tile the list's kernel proved unsafe that still runs the gradient
-  // phases.  Workgroup i takes entry i, and exits at once when i >= [0].  Tiles not in the list were written by the list's kernels.
+  // lean >= 2, k1_sched (r07): nullptr, or the tile list of this launch, 2^tshift shards: a head of kTlistHead words per shard -- [0] =
+  // entries at the front, [1] = entries at the back, the rest unused: a shard's counters have a cache line to themselves --, then room for
+  // tcap entries per shard: the tile (by * tgx + bx) in bits 0..23, bit 31 = a constraint tile the list's kernel proved unsafe that still
+  // runs the gradient phases.  Workgroup i of a 1-D grid of tcap << tshift takes entry i >> tshift of shard i mod 2^tshift -- the front
+  // entries upwards, then the back entries from the last one down -- and exits at once past both.  Tiles not in the list were written by
+  // the list's kernels.
   const unsigned int* tlist;
+  int tshift, tcap;
   int tgx, tgy;  // the tile grid (tiles per row, tile rows) behind the list
 };
 
@@ -186,6 +191,7 @@ struct PostOutcome {
   bool col_active = false;     // the launch delivered the classification as column words (col_set_phase runs)
   bool col_forked = false;     // ... and the constraint's launch carried ColPath::ev[0]
   int col_lean = 0;            // ... at this lean level (non-zero: the objective's mean / var are incomplete)
+  bool col_sched = false;      // ... and k_bl_sched_list2 ran behind the constraint's launch: the counters of the constraint's tile list are zero again
   int fuse_rows = 0;           // > 0: the kernel wrote S / U and that many partial rows at the head of cpart
   bool lmax_pending = false;   // the Lipschitz partials (lmax_per_out rows per output in bl_lpart) wait for the sweep to merge them
   int lmax_per_out = 0;
@@ -262,6 +268,8 @@ struct Audit {
 struct ColPath {
   bool slots_clean = false;// the slot block holds its neutral elements (the finals of the last column sweep reset it)
   bool usum_dirty = false; // Usum holds bits of an earlier launch (cleared by the column path's second kernel; by a memset after a failure)
+  bool sched_clean = false;// the counters of the constraint's tile list at the head of bl_sched are zero (k_bl_sched_list2 of the last column sweep reset them and that sweep
+                           // came through; clear for a new buffer, after a sweep that failed or ran no lists: a memset in front of k_bl_sched_tiles1)
   DevBuf S, U, M, G, Usum;           // column words [H / 64][W]; Usum [W]
   DevBuf slots;                      // ColBits::slots
   DevBuf img, bmin;                  // column distance image u16 [H][W], block minima u16 [H][W / 32]
@@ -425,7 +433,7 @@ struct sbo_ctx {
   sbo::DevBuf bl_grad;  // K1b: which tiles run the gradient phases (per plan)
   sbo::DevBuf bl_lpart; // K1b: per-wave Lipschitz partials of k_bpost
   sbo::DevBuf bl_encl;  // K1b column path: per-cell enclosures of the constraint's posterior (per plan) + a skip byte per tile (per sweep)
-  sbo::DevBuf bl_sched;         // K1b column path, lean 2 (r07): per-tile classes + the tile lists of the constraint's and the objective's launch
+  sbo::DevBuf bl_sched;         // K1b column path, lean 2 (r07): the tile lists of the constraint's and the objective's launch (PostExtra::tlist)
   sbo::Pinned h_stage;          // pinned staging of the K1b table build's single upload (the twin has one of its own)
   // what the last posterior launch leaves for the standing audit (guard.hip), cleared by every enqueue of a posterior (api.hip):
   bool k1_skip_armed = false;   // it could leave constraint tiles unevaluated: bl_encl's skip bytes are its record

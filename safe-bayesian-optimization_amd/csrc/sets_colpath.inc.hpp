@@ -1180,5 +1180,6 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
     if ((rc = sweep_exchange_back(c, h, is_max, Lk, c->ev[4], true))) return rc;
     c->col.G_bytes = true;
   }
+  c->col.sched_clean = post.col_sched;
   return SBO_OK;
 }
