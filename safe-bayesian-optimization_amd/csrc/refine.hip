@@ -91,6 +91,17 @@ __device__ __forceinline__ void ref_block_sum(const double* v, int cnt, double (
   __syncthreads();
 }
 
+// the LDS tier's copy of M: the used outputs' lower triangles out of Fplain, packed row after row (one wave per row) -> Ml
+__device__ __forceinline__ void ref_load_M(const RefineArgs& A, const double* F, double* Ml) {
+  const int n = A.mc.n, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const size_t tri = (size_t)n * (n + 1) / 2;
+  for (int u = 0; u < A.nu; ++u) {
+    const double* Fo = F + (size_t)A.outs[u] * A.f_cap * A.f_cap;
+    for (int i = wave; i < n; i += nw)
+      for (int j = lane; j <= i; j += 64) Ml[u * tri + (size_t)i * (i + 1) / 2 + j] = Fo[(size_t)i * A.f_cap + j];
+  }
+}
+
 // mean / var and their gradients at the kP points of x (LDS, point p at x + p d) for every used output -> E[p].  M rows: LDS
 // packed triangles (kLds) or Fplain (stride f_cap); every element of M is read once per pass and serves the kP points (kv / uv
 // [kP][n], red [kP][2 (kMaxD + 1)], uup [kP][kRefWaves]).  Each point's sums run in the order of a one-point evaluation.
@@ -353,12 +364,12 @@ __device__ bool ref_stage_end(RefState& S, const RefineArgs& A, double* trial) {
   return ref_new_iteration(S, A, trial);
 }
 
-// consume the evaluation of `trial`; true when `trial` holds the next point to evaluate
-__device__ __noinline__ bool ref_advance(RefState& S, const RefineArgs& A, const RefEval* E, double* trial) {
+// The one barrier step: consume the problem's terms at `trial` (ok: usable; go is overwritten), which cost nev point evaluations; true
+// when `trial` holds the next point to evaluate
+__device__ __forceinline__ bool ref_step(RefState& S, const RefineArgs& A, bool ok, double fo, double* go, double B, const double* gB, double obj,
+                                         int nev, double* trial) {
   const int d = A.nz;                 // (the solver's variables)
-  S.nev += A.np;                      // (one posterior + gradient evaluation per point)
-  double fo, go[kMaxD], B, gB[kMaxD], obj;
-  const bool ok = ref_terms(A, E, trial, fo, go, B, gB, obj);
+  S.nev += nev;
   if (S.phase == REF_PH_START) {
     if (!ok) { S.status = SBO_REFINE_NO_PROGRESS; return false; }   // the solver's own arithmetic cannot start at the seed
     S.fo = fo; S.B = B; S.obj = S.objb = obj;
@@ -391,6 +402,13 @@ __device__ __noinline__ bool ref_advance(RefState& S, const RefineArgs& A, const
   if (S.s.h_identity) return ref_stage_end(S, A, trial);
   pbfgs_reset_h(S.s, bx, d);                                         // the quasi-Newton direction failed: one steepest-descent try
   return ref_new_iteration(S, A, trial);
+}
+
+// consume the evaluation of `trial` (one posterior + gradient evaluation per point); true when `trial` holds the next point to evaluate
+__device__ __noinline__ bool ref_advance(RefState& S, const RefineArgs& A, const RefEval* E, double* trial) {
+  double fo, go[kMaxD], B, gB[kMaxD], obj;
+  const bool ok = ref_terms(A, E, trial, fo, go, B, gB, obj);
+  return ref_step(S, A, ok, fo, go, B, gB, obj, A.np, trial);
 }
 
 // the exact bound of models/SafeOpt.py:34-45 as k_bound computes it (posterior.hip)
@@ -487,15 +505,7 @@ __global__ __launch_bounds__(1024) void k_refine(const RefineArgs* __restrict__ 
   double* kv = reinterpret_cast<double*>(smem);     // [kP][n]
   double* uv = kv + kP * n;                         // [kP][n]
   double* Ml = uv + kP * n;
-  if (kLds) {                                       // the used outputs' triangles of M, packed row after row
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const size_t tri = (size_t)n * (n + 1) / 2;
-    for (int u = 0; u < A.nu; ++u) {
-      const double* Fo = F + (size_t)A.outs[u] * A.f_cap * A.f_cap;
-      for (int i = wave; i < n; i += nw)
-        for (int j = lane; j <= i; j += 64) Ml[u * tri + (size_t)i * (i + 1) / 2 + j] = Fo[(size_t)i * A.f_cap + j];
-    }
-  }
+  if (kLds) ref_load_M(A, F, Ml);
   if (threadIdx.x == 0) {
     for (int a = 0; a < nz; ++a) {
       trial[a] = seeds[s * nz + a];
@@ -561,6 +571,51 @@ __global__ void k_refine_accept(const RefineArgs* __restrict__ Ap, long long S, 
   }
 }
 
+// the ceiling of max_eval: one launch holds a CU for max_eval evaluations of O(n^2) each, which keeps a call near a few seconds at n = 2048
+static int refine_eval_cap(int n) { return (int)std::min<double>(kRefMaxEval, std::max<double>(kRefDefaultEval, 4e9 / ((double)n * n))); }
+static int refine_threads(int n) { return n > 256 ? 1024 : 256; }
+
+// The dynamic LDS of a launch that evaluates `pts` points per pass over `tris` outputs' triangles of M: the points' k and u = M k, and
+// M itself (tier) when it fits kRefLdsM beside the vectors of every point but the first and `extra` bytes
+static size_t refine_lds_bytes(const sbo_ctx* c, int tris, int pts, size_t extra, bool& tier) {
+  const int n = c->mc.n;
+  const size_t tri_bytes = sizeof(double) * (size_t)tris * n * (n + 1) / 2, kvuv = sizeof(double) * 2 * (size_t)n;
+  tier = c->opt.refine_lds && tri_bytes + (pts - 1) * kvuv + extra <= kRefLdsM;
+  return pts * kvuv + (tier ? tri_bytes : 0);
+}
+
+// the model's constants and leading dimensions, and the tolerance (<= 0: the default), of a problem on c's model
+static void refine_fill(const sbo_ctx* c, double tol, RefineArgs& A) {
+  A.mc = c->mc;
+  A.f_cap = c->f_cap;
+  A.a_ld = c->a_ld;
+  A.tol = tol > 0.0 ? tol : kRefDefaultTol;
+}
+
+// the checks every refine entry point makes: of b and tol, and of the box of the d axes
+static int refine_check(double b, double tol) {
+  if (!(b >= 0.0) || !std::isfinite(b)) return fail(SBO_E_INVALID, "confidence multiplier b must be finite and >= 0");
+  if (std::isnan(tol)) return fail(SBO_E_INVALID, "tol is NaN");
+  return SBO_OK;
+}
+static int refine_check_box(const double* lo, const double* hi, int d) {
+  for (int a = 0; a < d; ++a)
+    if (!std::isfinite(lo[a]) || !std::isfinite(hi[a]) || !(lo[a] <= hi[a])) return fail(SBO_E_INVALID, "box needs finite lo <= hi");
+  return SBO_OK;
+}
+
+// Hands out consecutive blocks of one buffer, each at a multiple of `align` bytes.  A layout is one sequence of take() calls, run
+// once on a null base for the size and once on the buffer for the pointers.
+struct Carve {
+  unsigned char* base;
+  size_t off = 0;
+  template <class T> void take(T*& p, size_t count, size_t align = alignof(T)) {
+    off = (off + align - 1) / align * align;
+    p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += sizeof(T) * count;
+  }
+};
+
 template <bool kLds, int kP>
 static int refine_launch(sbo_ctx* c, size_t lds, int threads, long long S, const RefineArgs* dA, const double* dseed, const double* m0,
                          const double* v0, double* cand, int* dst, int* dnev) {
@@ -580,39 +635,32 @@ static int refine_run(sbo_ctx* c, RefineArgs& A, int max_eval, double tol, long 
   SBO_HIP(hipSetDevice(c->device));
   int rc;
   if ((rc = factor_sync(c))) return rc;             // (Fplain may still be in the making: the deferred factor chain)
-  A.mc = mc;
-  // one launch holds a CU for max_eval evaluations of O(n^2) each: the ceiling keeps a call near a few seconds at n = 2048
-  const int eval_cap = (int)std::min<double>(kRefMaxEval, std::max<double>(kRefDefaultEval, 4e9 / ((double)mc.n * mc.n)));
-  A.max_eval = max_eval > 0 ? std::min(max_eval, eval_cap) : kRefDefaultEval;
-  A.f_cap = c->f_cap;
-  A.a_ld = c->a_ld;
-  A.tol = tol > 0.0 ? tol : kRefDefaultTol;
+  refine_fill(c, tol, A);
+  A.max_eval = max_eval > 0 ? std::min(max_eval, refine_eval_cap(mc.n)) : kRefDefaultEval;
   // scratch: the arguments | seeds [S][nz] | mean0 var0 [q][np S] | cand [2 S][nz] | mean1 var1 [q][2 np S] | x_out [S][nz] | val [S] |
   // status, evaluations [S]
   const size_t P = (size_t)np * S;
-  const size_t ael = (sizeof(RefineArgs) + 255) / 256 * 32;
-  const size_t el = ael + (size_t)S * nz + 2 * (size_t)q * P + 2 * (size_t)S * nz + 4 * (size_t)q * P + (size_t)S * nz + S + S;
-  if ((rc = ensure(c->refbuf, sizeof(double) * el))) return rc;
-  RefineArgs* dA = (RefineArgs*)c->refbuf.p;
-  double* dseed = (double*)c->refbuf.p + ael;
-  double* m0 = dseed + (size_t)S * nz;
-  double* v0 = m0 + (size_t)q * P;
-  double* cand = v0 + (size_t)q * P;
-  double* m1 = cand + 2 * (size_t)S * nz;
-  double* v1 = m1 + 2 * (size_t)q * P;
-  double* dx = v1 + 2 * (size_t)q * P;
-  double* dval = dx + (size_t)S * nz;
-  int* dst = reinterpret_cast<int*>(dval + S);
-  int* dnev = dst + S;
+  RefineArgs* dA;
+  double *dseed, *m0, *v0, *cand, *m1, *v1, *dx, *dval;
+  int *dst, *dnev;
+  auto layout = [&](Carve cv) {
+    cv.take(dA, 1, 256);
+    cv.take(dseed, (size_t)S * nz, 256);
+    cv.take(m0, q * P); cv.take(v0, q * P);
+    cv.take(cand, 2 * (size_t)S * nz);
+    cv.take(m1, 2 * q * P); cv.take(v1, 2 * q * P);
+    cv.take(dx, (size_t)S * nz); cv.take(dval, S);
+    cv.take(dst, S); cv.take(dnev, S);
+    return cv.off;
+  };
+  if ((rc = ensure(c->refbuf, layout({nullptr})))) return rc;
+  layout({(unsigned char*)c->refbuf.p});
   SBO_HIP(hipMemcpyAsync(dA, &A, sizeof(RefineArgs), hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(dseed, seeds, sizeof(double) * (size_t)S * nz, hipMemcpyHostToDevice, c->stream));
   if ((rc = launch_posterior_on_list(c, dseed, (long long)P, m0, v0))) return rc;   // (a pair's points are consecutive rows of d)
-  const int n = mc.n;
-  const size_t tri_bytes = sizeof(double) * (size_t)A.nu * n * (n + 1) / 2;
-  const size_t kvuv = sizeof(double) * 2 * (size_t)n;                              // k and u = M k of one point
-  const bool lds_tier = c->opt.refine_lds && tri_bytes + (np - 1) * kvuv <= kRefLdsM;  // (the second point's vectors count against M's budget)
-  const size_t lds = np * kvuv + (lds_tier ? tri_bytes : 0);
-  const int threads = n > 256 ? 1024 : 256;
+  bool lds_tier;
+  const size_t lds = refine_lds_bytes(c, A.nu, np, 0, lds_tier);
+  const int threads = refine_threads(mc.n);
   if (S > 0x7fffffffLL) return fail(SBO_E_UNSUPPORTED, "too many seeds for one launch");
   if (np == 1)
     rc = lds_tier ? refine_launch<true, 1>(c, lds, threads, S, dA, dseed, m0, v0, cand, dst, dnev)
@@ -675,11 +723,8 @@ static int refine_problem(sbo_ctx* c, const sbo_refine_sets_opts* opts, int64_t 
   if (opts->use_link && !pair) return fail(SBO_E_INVALID, "the link joins x and x': pair mode only");
   if (opts->use_link && (opts->link_output < 1 || opts->link_output >= q || !(opts->L >= 0.0) || !std::isfinite(opts->L)))
     return fail(SBO_E_INVALID, "the link needs a constraint output in [1, q) and a finite L >= 0");
-  if (!(opts->b >= 0.0) || !std::isfinite(opts->b)) return fail(SBO_E_INVALID, "confidence multiplier b must be finite and >= 0");
-  if (std::isnan(opts->tol)) return fail(SBO_E_INVALID, "tol is NaN");
-  for (int a = 0; a < d; ++a)
-    if (!std::isfinite(opts->lo[a]) || !std::isfinite(opts->hi[a]) || !(opts->lo[a] <= opts->hi[a]))
-      return fail(SBO_E_INVALID, "box needs finite lo <= hi");
+  int rc;
+  if ((rc = refine_check(opts->b, opts->tol)) || (rc = refine_check_box(opts->lo, opts->hi, d))) return rc;
   if (opts->use_ball != 0 && opts->use_ball != 1) return fail(SBO_E_INVALID, "use_ball must be 0 or 1");
   if (opts->use_ball && (!(opts->r > 0.0) || !std::isfinite(opts->r))) return fail(SBO_E_INVALID, "ball radius must be finite and > 0");
   for (int a = 0; a < d; ++a) {
@@ -725,7 +770,6 @@ static int refine_problem(sbo_ctx* c, const sbo_refine_sets_opts* opts, int64_t 
     }
   std::vector<double> hz, hv;
   std::vector<int> hs;
-  int rc;
   if ((rc = refine_run(c, A, opts->max_eval, opts->tol, S, hseed.data(), hz, hv, hs))) return rc;
   // the seed whose returned point is best (ties: the lowest index; infeasible seeds and NaN values never), -1 if none
   sbo_refine_sets_result res{};
@@ -790,15 +834,8 @@ struct RobScen {
 
 __device__ void rob_store(const RobustArgs& R, const RefEval& E, int k, RobScen& Sc) {
   const int d = R.A.mc.d, q = R.A.mc.q;
-  double g, gg[kMaxD];
-  bool ok = ref_conf(E, 0, R.bobj, R.sobj, d, g, gg);
-  Sc.f[k] = g;
-  for (int a = 0; a < R.nxc; ++a) Sc.gf[k][a] = gg[a];
-  for (int c = 1; c < q; ++c) {
-    ok = ref_conf(E, c, R.A.b, -1.0, d, g, gg) && ok;
-    Sc.l[k][c] = g;
-    for (int a = 0; a < R.nxc; ++a) Sc.gl[k][c][a] = gg[a];
-  }
+  bool ok = ref_conf(E, 0, R.bobj, R.sobj, d, Sc.f[k], Sc.gf[k]);   // (gradients land in place: the entries past nxc are not read)
+  for (int c = 1; c < q; ++c) ok = ref_conf(E, c, R.A.b, -1.0, d, Sc.l[k][c], Sc.gl[k][c]) && ok;
   Sc.ok[k] = ok;
 }
 
@@ -829,14 +866,14 @@ __device__ bool rob_terms(const RobustArgs& R, const RobScen& Sc, int K, const d
   return ok;
 }
 
-// ref_advance on the epigraph problem: the same stages, metric, first step, Armijo and rejection of unusable trials; the function is
-// rob_terms on the scenarios' evaluation at `trial`.  The first evaluation of a step only places t above the largest bound_0.
+// ref_advance on the epigraph problem: the function is rob_terms on the scenarios' evaluation at `trial`, the step ref_step with t as
+// the objective (so its best-iterate tracking runs here too; xb is not read).  The first evaluation of a step only places t above
+// the largest bound_0: refused outside t's box or where a scenario's evaluation is unusable, which ref_step ends as an unusable start.
 __device__ __noinline__ bool rob_advance(RefState& S, const RobustArgs& R, const RobScen& Sc, int K, double* trial) {
   const RefineArgs& A = R.A;
-  const int nz = A.nz, nxc = R.nxc;
-  S.nev += K;
+  const int nxc = R.nxc;
+  bool ok = true;
   if (S.phase == REF_PH_START) {
-    bool ok = true;
     double fmax = -INFINITY;
     for (int k = 0; k < K; ++k) {
       ok = ok && Sc.ok[k];
@@ -845,75 +882,68 @@ __device__ __noinline__ bool rob_advance(RefState& S, const RobustArgs& R, const
     const double t = fmax + kRefMu0 * A.mc.Y_std[0];
     ok = ok && t >= A.lo[nxc] && t <= A.hi[nxc];
     trial[nxc] = S.s.x[nxc] = t;
-    double fo, go[kMaxD], B, gB[kMaxD];
-    ok = ok && rob_terms(R, Sc, K, trial, fo, go, B, gB);
-    if (!ok) { S.status = SBO_REFINE_NO_PROGRESS; return false; }   // this point is not strictly inside every scenario's terms
-    S.fo = fo; S.B = B; S.obj = S.objb = t;
-    for (int a = 0; a < nz; ++a) { S.go[a] = go[a]; S.gB[a] = gB[a]; S.xb[a] = S.s.x[a]; }
-    S.mu = kRefMu0;
-    if (S.nev >= A.max_eval) { S.status = SBO_REFINE_MAX_EVAL; return false; }
-    return ref_new_iteration(S, A, trial);
   }
-  double fo, go[kMaxD], B, gB[kMaxD];
-  const bool ok = rob_terms(R, Sc, K, trial, fo, go, B, gB);
-  const PbfgsBox bx = ref_box(S, A);
-  bool moved;
-  if (pbfgs_armijo(S.s, nz, trial, ok, fo + S.mu * B, S.f, moved)) {
-    for (int a = 0; a < nz; ++a) {
-      S.go[a] = go[a];
-      S.gB[a] = gB[a];
-      go[a] += S.mu * gB[a];
-    }
-    pbfgs_update(S.s, bx, nz, trial, go);
-    const double fprev = S.f;
-    S.fo = fo; S.B = B; S.obj = trial[nxc];
-    if (S.nev >= A.max_eval) { S.status = SBO_REFINE_MAX_EVAL; return false; }
-    if (fabs(fprev - (S.fo + S.mu * S.B)) <= 1e-15 * (1.0 + fabs(fprev))) return ref_stage_end(S, A, trial);
-    return ref_new_iteration(S, A, trial);
+  double fo = 0.0, go[kMaxD], B = 0.0, gB[kMaxD];
+  ok = ok && rob_terms(R, Sc, K, trial, fo, go, B, gB);
+  return ref_step(S, A, ok, fo, go, B, gB, trial[nxc], K, trial);
+}
+
+// the outer step's evaluation workspace (LDS): the joint points of a pass, ref_eval's sums and results, the scenarios' terms
+struct RobWork {
+  RefEval E[2];
+  RobScen Sc;
+  double pts[2 * kMaxD], red[2 * 2 * (kMaxD + 1)], uup[2 * kRefWaves], part[kRefWaves][kMaxD + 1];
+};
+
+// bound_0 and every lcb_c at the K joint points (xc, d_k), xc = trial's first nxc entries -> W.Sc: two points per pass over M
+// (ref_eval<kLds, 2>), an odd last one alone, in scenario order
+template <bool kLds>
+__device__ __forceinline__ void rob_eval_scenarios(const RobustArgs& RA, const RobustCtl* ctl, int K, const double* trial, const double* F,
+                                                const double* Ml, const double* alpha, const double* Xn, double* kv, double* uv, RobWork& W) {
+  const RefineArgs& A = RA.A;
+  const int d = A.mc.d, nxc = RA.nxc, nd = RA.nd;
+  for (int k0 = 0; k0 < K; k0 += 2) {
+    const int np = K - k0 >= 2 ? 2 : 1;
+    if (threadIdx.x == 0)
+      for (int p = 0; p < np; ++p) {
+        for (int a = 0; a < nxc; ++a) W.pts[p * d + a] = trial[a];
+        for (int a = 0; a < nd; ++a) W.pts[p * d + nxc + a] = ctl->scen[k0 + p][a];
+      }
+    __syncthreads();
+    if (np == 2) ref_eval<kLds, 2>(A, W.pts, F, Ml, alpha, Xn, kv, uv, W.part, W.red, W.uup, W.E);
+    else ref_eval<kLds, 1>(A, W.pts, F, Ml, alpha, Xn, kv, uv, W.part, W.red, W.uup, W.E);
+    if (threadIdx.x == 0)
+      for (int p = 0; p < np; ++p) rob_store(RA, W.E[p], k0 + p, W.Sc);
+    __syncthreads();
   }
-  if (S.nev >= A.max_eval) { S.status = SBO_REFINE_MAX_EVAL; return false; }
-  if (pbfgs_backtrack(S.s, bx, nz, moved, trial)) return true;
-  if (S.s.h_identity) return ref_stage_end(S, A, trial);
-  pbfgs_reset_h(S.s, bx, nz);
-  return ref_new_iteration(S, A, trial);
 }
 
 // The outer step: one workgroup minimises t over z = (xc, t) on the barrier function of the scenarios, from the current outer
-// solution when that is strictly inside every scenario's terms, else from the seed.  The K joint points (xc, d_k) are evaluated two
-// per pass over M (ref_eval<kLds, 2>), an odd last one alone.
+// solution when that is strictly inside every scenario's terms, else from the seed.
 template <bool kLds>
 __global__ __launch_bounds__(1024) void k_refine_robust(const RobustArgs* __restrict__ Rp, const double* __restrict__ F,
                                                         const double* __restrict__ alpha, const double* __restrict__ Xn,
                                                         RobustCtl* __restrict__ ctl) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ RefState R;
-  __shared__ RefEval E[2];
-  __shared__ RobScen Sc;
-  __shared__ double trial[kMaxD], pts[2 * kMaxD], red[2 * 2 * (kMaxD + 1)], uup[2 * kRefWaves];
-  __shared__ double part[kRefWaves][kMaxD + 1];
+  __shared__ RobWork W;
+  __shared__ double trial[kMaxD];
   __shared__ int go, attempt;
   const RobustArgs& RA = *Rp;
   const RefineArgs& A = RA.A;
   if (ctl->added == 0 || ctl->stop >= 0) return;    // (the separation ended the call: uniform over the workgroup)
-  const int n = A.mc.n, d = A.mc.d, nz = A.nz, nxc = RA.nxc, nd = RA.nd, K = ctl->K;
+  const int n = A.mc.n, nz = A.nz, nxc = RA.nxc, K = ctl->K;
   double* kv = reinterpret_cast<double*>(smem);     // [2][n]
   double* uv = kv + 2 * n;                          // [2][n]
   double* Ml = uv + 2 * n;
-  if (kLds) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const size_t tri = (size_t)n * (n + 1) / 2;
-    for (int u = 0; u < A.nu; ++u) {
-      const double* Fo = F + (size_t)A.outs[u] * A.f_cap * A.f_cap;
-      for (int i = wave; i < n; i += nw)
-        for (int j = lane; j <= i; j += 64) Ml[u * tri + (size_t)i * (i + 1) / 2 + j] = Fo[(size_t)i * A.f_cap + j];
-    }
-  }
+  if (kLds) ref_load_M(A, F, Ml);
   if (threadIdx.x == 0) {
     for (int a = 0; a < nz; ++a) {
       R.span[a] = A.hi[a] - A.lo[a];
       R.D2[a] = R.span[a] * R.span[a];
     }
     R.nev = 0;
+    R.nbar = K * A.mc.q;                            // (every scenario's terms; > 0, so the first stage's weight is kRefMu0)
     attempt = 0;
   }
   __syncthreads();
@@ -928,21 +958,8 @@ __global__ __launch_bounds__(1024) void k_refine_robust(const RobustArgs* __rest
     }
     __syncthreads();
     while (go) {
-      for (int k0 = 0; k0 < K; k0 += 2) {
-        const int np = K - k0 >= 2 ? 2 : 1;
-        if (threadIdx.x == 0)
-          for (int p = 0; p < np; ++p) {
-            for (int a = 0; a < nxc; ++a) pts[p * d + a] = trial[a];
-            for (int a = 0; a < nd; ++a) pts[p * d + nxc + a] = ctl->scen[k0 + p][a];
-          }
-        __syncthreads();
-        if (np == 2) ref_eval<kLds, 2>(A, pts, F, Ml, alpha, Xn, kv, uv, part, red, uup, E);
-        else ref_eval<kLds, 1>(A, pts, F, Ml, alpha, Xn, kv, uv, part, red, uup, E);
-        if (threadIdx.x == 0)
-          for (int p = 0; p < np; ++p) rob_store(RA, E[p], k0 + p, Sc);
-        __syncthreads();
-      }
-      if (threadIdx.x == 0) go = rob_advance(R, RA, Sc, K, trial);
+      rob_eval_scenarios<kLds>(RA, ctl, K, trial, F, Ml, alpha, Xn, kv, uv, W);
+      if (threadIdx.x == 0) go = rob_advance(R, RA, W.Sc, K, trial);
       __syncthreads();
     }
     const bool retry = R.status == SBO_REFINE_NO_PROGRESS && R.phase == REF_PH_START && attempt == 0;
@@ -956,28 +973,15 @@ __global__ __launch_bounds__(1024) void k_refine_robust(const RobustArgs* __rest
     if (threadIdx.x == 0)
       for (int a = 0; a < nz; ++a) trial[a] = R.s.x[a];
     __syncthreads();
-    for (int k0 = 0; k0 < K; k0 += 2) {
-      const int np = K - k0 >= 2 ? 2 : 1;
-      if (threadIdx.x == 0)
-        for (int p = 0; p < np; ++p) {
-          for (int a = 0; a < nxc; ++a) pts[p * d + a] = trial[a];
-          for (int a = 0; a < nd; ++a) pts[p * d + nxc + a] = ctl->scen[k0 + p][a];
-        }
-      __syncthreads();
-      if (np == 2) ref_eval<kLds, 2>(A, pts, F, Ml, alpha, Xn, kv, uv, part, red, uup, E);
-      else ref_eval<kLds, 1>(A, pts, F, Ml, alpha, Xn, kv, uv, part, red, uup, E);
-      if (threadIdx.x == 0)
-        for (int p = 0; p < np; ++p) rob_store(RA, E[p], k0 + p, Sc);
-      __syncthreads();
-    }
+    rob_eval_scenarios<kLds>(RA, ctl, K, trial, F, Ml, alpha, Xn, kv, uv, W);
   }
   if (threadIdx.x == 0) {
     if (started) {
       for (int a = 0; a < nz; ++a) ctl->z[a] = R.s.x[a];
       for (int k = 0; k < K; ++k) {
-        double s = (R.s.x[nxc] - Sc.f[k]) / A.mc.Y_std[0];
-        for (int c = 1; c < A.mc.q; ++c) s = fmin(s, Sc.l[k][c] / A.mc.Y_std[c]);
-        ctl->slack[k] = Sc.ok[k] ? s : 0.0;
+        double s = (R.s.x[nxc] - W.Sc.f[k]) / A.mc.Y_std[0];
+        for (int c = 1; c < A.mc.q; ++c) s = fmin(s, W.Sc.l[k][c] / A.mc.Y_std[c]);
+        ctl->slack[k] = W.Sc.ok[k] ? s : 0.0;
       }
       R.nev += K;
     }
@@ -1140,12 +1144,10 @@ static int refine_robust(sbo_ctx* c, const sbo_refine_robust_opts* opts, const d
   if (nxc + 1 > kMaxD) return fail(SBO_E_UNSUPPORTED, "sbo_refine_robust: the solver's variables (xc, t) need n_control_axes + 1 <= SBO_MAX_D");
   const int nd = d - nxc;
   if (opts->kind != SBO_MEAN && opts->kind != SBO_UCB && opts->kind != SBO_LCB) return fail(SBO_E_INVALID, "kind must be SBO_MEAN, SBO_UCB or SBO_LCB");
-  if (!(opts->b >= 0.0) || !std::isfinite(opts->b)) return fail(SBO_E_INVALID, "confidence multiplier b must be finite and >= 0");
-  if (std::isnan(opts->tol)) return fail(SBO_E_INVALID, "tol is NaN");
+  int rc;
+  if ((rc = refine_check(opts->b, opts->tol))) return rc;
   if (opts->max_scenarios > kRobMaxScen) return fail(SBO_E_INVALID, "max_scenarios is at most SBO_ROBUST_MAX_SCEN");
-  for (int a = 0; a < d; ++a)
-    if (!std::isfinite(opts->lo[a]) || !std::isfinite(opts->hi[a]) || !(opts->lo[a] <= opts->hi[a]))
-      return fail(SBO_E_INVALID, "box needs finite lo <= hi");
+  if ((rc = refine_check_box(opts->lo, opts->hi, d))) return rc;
   long long Nd = 1;
   for (int a = 0; a < nd; ++a) {
     if (opts->count_d[a] < 1 || opts->count_d[a] > (1LL << 24)) return fail(SBO_E_INVALID, "count_d needs at least one point per disturbance axis");
@@ -1155,22 +1157,17 @@ static int refine_robust(sbo_ctx* c, const sbo_refine_robust_opts* opts, const d
   for (int a = 0; a < nxc; ++a)
     if (!std::isfinite(xc_seed[a])) return fail(SBO_E_INVALID, "the seed must be finite");
   SBO_HIP(hipSetDevice(c->device));
-  int rc;
   if ((rc = factor_sync(c))) return rc;
   const int max_rounds = opts->max_rounds > 0 ? opts->max_rounds : kRobDefaultRounds;
-  const int eval_cap = (int)std::min<double>(kRefMaxEval, std::max<double>(kRefDefaultEval, 4e9 / ((double)n * n)));
+  const int eval_cap = refine_eval_cap(n);
   const int max_eval = opts->max_eval > 0 ? std::min(opts->max_eval, eval_cap) : eval_cap;
-  const double tol = opts->tol > 0.0 ? opts->tol : kRefDefaultTol;
 
   RobustArgs R{};
-  R.A.mc = mc;
+  refine_fill(c, opts->tol, R.A);
   R.A.nu = q;
   for (int u = 0; u < q; ++u) R.A.outs[u] = u;
   R.A.kind = opts->kind;
   R.A.b = opts->b;
-  R.A.tol = tol;
-  R.A.f_cap = c->f_cap;
-  R.A.a_ld = c->a_ld;
   R.A.np = 1;
   R.A.nz = nxc + 1;
   R.A.level_slot = R.A.link_slot = -1;
@@ -1180,7 +1177,7 @@ static int refine_robust(sbo_ctx* c, const sbo_refine_robust_opts* opts, const d
   R.max_scen = opts->max_scenarios > 0 ? opts->max_scenarios : kRobMaxScen;
   R.bobj = opts->kind == SBO_MEAN ? 0.0 : opts->b;
   R.sobj = opts->kind == SBO_LCB ? -1.0 : 1.0;
-  R.sep_tol = tol;
+  R.sep_tol = R.A.tol;
   bool seed_in_box = true;
   for (int a = 0; a < nxc; ++a) {
     R.A.lo[a] = opts->lo[a];
@@ -1211,32 +1208,32 @@ static int refine_robust(sbo_ctx* c, const sbo_refine_robust_opts* opts, const d
   // scratch: (q + 1) argument blocks | control | final | list [2 NC][d] | mean var [q][2 NC] | seeds [q][d] | sval [q] | cand [2 q][d] |
   // mean1 var1 [q][2 q] | polish status, evaluations [q]
   const long long NC = Nd + kRobMaxScen;
-  const size_t ael = (std::max(sizeof(RobustArgs), sizeof(RefineArgs)) + 255) / 256 * 32;
-  const size_t cel = (sizeof(RobustCtl) + 255) / 256 * 32, fel = (sizeof(RobustFinal) + 255) / 256 * 32;
-  const size_t el = (size_t)(q + 1) * ael + cel + fel + 2 * (size_t)NC * d + 4 * (size_t)q * NC + (size_t)q * d + q + 2 * (size_t)q * d +
-                    4 * (size_t)q * q + 2 * q + 32;
-  if ((rc = ensure(c->refbuf, sizeof(double) * el))) return rc;
-  double* base = (double*)c->refbuf.p;
-  RobustArgs* dR = (RobustArgs*)base;
-  RobustCtl* dctl = (RobustCtl*)(base + (size_t)(q + 1) * ael);
-  RobustFinal* dfin = (RobustFinal*)((double*)dctl + cel);
-  double* dlist = (double*)dfin + fel;
-  double* mL = dlist + 2 * (size_t)NC * d;
-  double* vL = mL + 2 * (size_t)q * NC;
-  double* dseed = vL + 2 * (size_t)q * NC;
-  double* dsval = dseed + (size_t)q * d;
-  double* dcand = dsval + q;
-  double* m1 = dcand + 2 * (size_t)q * d;
-  double* v1 = m1 + 2 * (size_t)q * q;
-  int* dst = reinterpret_cast<int*>(v1 + 2 * (size_t)q * q);
-  int* dnev = dst + q;
+  const size_t asz = (std::max(sizeof(RobustArgs), sizeof(RefineArgs)) + 255) / 256 * 256;   // (the stride of the argument blocks)
+  unsigned char* dargs;
+  RobustCtl* dctl;
+  RobustFinal* dfin;
+  double *dlist, *mL, *vL, *dseed, *dsval, *dcand, *m1, *v1;
+  int *dst, *dnev;
+  auto layout = [&](Carve cv) {
+    cv.take(dargs, (size_t)(q + 1) * asz, 256);
+    cv.take(dctl, 1, 256);
+    cv.take(dfin, 1, 256);
+    cv.take(dlist, 2 * (size_t)NC * d, 256);
+    cv.take(mL, 2 * (size_t)q * NC); cv.take(vL, 2 * (size_t)q * NC);
+    cv.take(dseed, (size_t)q * d); cv.take(dsval, q);
+    cv.take(dcand, 2 * (size_t)q * d);
+    cv.take(m1, 2 * (size_t)q * q); cv.take(v1, 2 * (size_t)q * q);
+    cv.take(dst, q); cv.take(dnev, q);
+    return cv.off;
+  };
+  if ((rc = ensure(c->refbuf, layout({nullptr})))) return rc;
+  layout({(unsigned char*)c->refbuf.p});
+  RobustArgs* dR = (RobustArgs*)dargs;
 
-  const size_t tri1 = sizeof(double) * (size_t)n * (n + 1) / 2, kvuv = sizeof(double) * 2 * (size_t)n;
-  const bool lds_polish = c->opt.refine_lds && tri1 <= kRefLdsM;
-  const size_t lds_p = kvuv + (lds_polish ? tri1 : 0);
-  const bool lds_outer = c->opt.refine_lds && q * tri1 + kvuv + 8192 <= kRefLdsM;   // (two points' vectors, as a pair of k_refine, and the scenarios' terms)
-  const size_t lds_o = 2 * kvuv + (lds_outer ? q * tri1 : 0);
-  const int threads = n > 256 ? 1024 : 256;
+  bool lds_polish, lds_outer;
+  const size_t lds_p = refine_lds_bytes(c, 1, 1, 0, lds_polish);
+  const size_t lds_o = refine_lds_bytes(c, q, 2, 8192, lds_outer);   // (two points' vectors, as a pair of k_refine; 8192: the scenarios' terms)
+  const int threads = refine_threads(n);
 
   RobustCtl hctl{};
   for (int a = 0; a < nxc; ++a) hctl.z[a] = xc_seed[a];
@@ -1260,16 +1257,13 @@ static int refine_robust(sbo_ctx* c, const sbo_refine_robust_opts* opts, const d
     for (int u = 0; u < q; ++u) {                    // output u's polish over d: the control axes held by a box of width zero
       RefineArgs& P = hP[u];
       P = RefineArgs{};
-      P.mc = mc;
+      refine_fill(c, opts->tol, P);
       P.nu = 1;
       P.outs[0] = u;
       P.kind = u == 0 ? opts->kind : SBO_LCB;
       P.maximize = u == 0;
       P.max_eval = kRobPolishEval;
-      P.f_cap = c->f_cap;
-      P.a_ld = c->a_ld;
       P.b = opts->b;
-      P.tol = tol;
       P.np = 1;
       P.nz = d;
       P.level_slot = P.link_slot = -1;
@@ -1277,7 +1271,7 @@ static int refine_robust(sbo_ctx* c, const sbo_refine_robust_opts* opts, const d
         P.lo[a] = a < nxc ? hctl.z[a] : opts->lo[a];
         P.hi[a] = a < nxc ? hctl.z[a] : opts->hi[a];
       }
-      SBO_HIP(hipMemcpyAsync((double*)dR + (size_t)(u + 1) * ael, &P, sizeof(RefineArgs), hipMemcpyHostToDevice, c->stream));
+      SBO_HIP(hipMemcpyAsync(dargs + (size_t)(u + 1) * asz, &P, sizeof(RefineArgs), hipMemcpyHostToDevice, c->stream));
     }
     SBO_HIP(hipMemcpyAsync(dR, &R, sizeof(RobustArgs), hipMemcpyHostToDevice, c->stream));
     if ((rc = launch_posterior_on_list(c, dlist, Nd, mL, vL))) return rc;
@@ -1285,7 +1279,7 @@ static int refine_robust(sbo_ctx* c, const sbo_refine_robust_opts* opts, const d
                        (const double*)vL, Nd, dseed, dsval);
     SBO_HIP(hipGetLastError());
     for (int u = 0; u < q; ++u) {
-      const RefineArgs* dP = (const RefineArgs*)((double*)dR + (size_t)(u + 1) * ael);
+      const RefineArgs* dP = (const RefineArgs*)(dargs + (size_t)(u + 1) * asz);
       rc = lds_polish ? refine_launch<true, 1>(c, lds_p, threads, 1, dP, dseed + (size_t)u * d, mL, vL, dcand + 2 * (size_t)u * d, dst + u, dnev + u)
                       : refine_launch<false, 1>(c, lds_p, threads, 1, dP, dseed + (size_t)u * d, mL, vL, dcand + 2 * (size_t)u * d, dst + u, dnev + u);
       if (rc) return rc;
