@@ -287,6 +287,17 @@ int sbo_model_set_prior(sbo_ctx* ctx, int dtype, const char* kernel, int n, int 
  * everything a posterior or a sweep reads are unchanged. */
 int sbo_model_append(sbo_ctx* ctx, const double* x_norm_new, const double* y_norm_new);
 
+/* Its counterpart: observation `index` (0-based, in the order of X_norm as set and appended) leaves the resident model.  The
+ * hyper-parameters, the normalisation constants and the prior mean stay frozen, the remaining observations keep their order
+ * (row i > index becomes row i - 1) and n becomes n - 1; the lower factor and alpha are updated in O(n^2) on the device
+ *  and no [n, n] matrix crosses the bus.  Every later call -- posterior, sweeps, refinement, an append,
+ * another removal -- sees the (n - 1)-row model; a sliding window of recent data is a removal of index 0 followed by an
+ * append.  Not the reference's behaviour either (it refits).  Fails with SBO_E_INVALID for an index outside [0, n) or for
+ * n == 1 (a model holds at least one observation) and with SBO_E_NO_MODEL without a model; on any error the model is as
+ * before the call.  Multi-rank: the model is replicated, every rank makes the same call, nothing is communicated (as for
+ * sbo_model_append). */
+int sbo_model_remove(sbo_ctx* ctx, int index);
+
 /* explicit list: points[N, d] of doubles (dtype SBO_F64) or floats (SBO_F32); first_index = global flat
  * index of points[0] (shard offset). */
 int sbo_candidates_points(sbo_ctx* ctx, const void* points, int points_dtype, int64_t n_local, int d,

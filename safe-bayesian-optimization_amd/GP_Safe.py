@@ -247,11 +247,20 @@ class GP:
         self.hypopt, self.invKopt = self.determine_hyperparameters(self.X_norm, self.Y_norm)
         self.update_inference_dataset()
 
-    def add_sample(self, x_new, y_new, incremental: bool = False):
+    def add_sample(self, x_new, y_new, incremental: bool = False, window: int | None = None):
         """Reference behaviour (models/GP_Safe.py:283-304): re-normalise, refit, rebuild.  ``incremental=True`` is the
         opt-in fast path of SURVEY.md 8(f) rank 2: normalisation constants and hyper-parameters stay frozen and the device
         model gains one row in O(n^2) (``sbo_model_append``); the Python-side ``inference_datasets`` follows with the
-        bordered inverse, also O(n^2)."""
+        bordered inverse, also O(n^2).  ``window=W`` (with ``incremental=True`` only) keeps a sliding window of the W most
+        recent observations: a model that already holds W of them loses its oldest (``remove_sample(0)``) before the new one
+        is appended, so n never exceeds W and a model at ``SBO_MAX_N`` keeps running."""
+        if window is not None:
+            if not incremental:
+                raise ValueError("window needs incremental=True (the default path refits on all data)")
+            if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1:
+                raise ValueError("window must be an integer >= 1")
+            while self.n_point >= window:
+                self.remove_sample(0)
         self.X = np.vstack([self.X, np.asarray(x_new, dtype=np.float64)])
         self.Y = np.vstack([self.Y, np.asarray(y_new, dtype=np.float64)])
         self.n_point = self.X.shape[0]
@@ -280,6 +289,38 @@ class GP:
         self.X_norm, self.Y_norm = self.data_normalization()
         self.hypopt, self.invKopt = self.determine_hyperparameters(self.X_norm, self.Y_norm)
         self.update_inference_dataset()
+
+    def remove_sample(self, index: int):
+        """The mirror of ``add_sample(..., incremental=True)``: observation ``index`` leaves the model under the frozen
+        normalisation constants and hyper-parameters, O(n^2) on the device (``sbo_model_remove``).  The Python-side
+        ``inference_datasets`` follows: with the old inverse split into A (without row and column ``index``), b (that column
+        without its diagonal entry) and c (the diagonal entry), the inverse of K without the observation is A - b b^T / c."""
+        n = self.n_point
+        if isinstance(index, bool) or not isinstance(index, (int, np.integer)) or not 0 <= index < n:
+            raise ValueError(f"index {index!r} out of range [0, {n})")
+        if n == 1:
+            raise ValueError("a model holds at least one observation")
+        index = int(index)
+        self._sync_model()
+        self.engine.remove_sample(index)
+        keep = np.arange(n) != index
+        X_norm = self.X_norm[keep]
+        lazy = isinstance(self.invKopt, LazyInvK)
+        if lazy:                                  # what nobody has read stays unformed, now over the remaining rows
+            hypopt, old = self.hypopt, self.invKopt
+            self.invKopt = LazyInvK(lambda i: self._invK(X_norm, hypopt, i), self.ny_dim)
+        for i in range(self.ny_dim):
+            if lazy and old._items[i] is None:
+                continue
+            P = old._items[i] if lazy else self.invKopt[i]
+            b = P[keep, index]
+            self.invKopt[i] = P[np.ix_(keep, keep)] - np.outer(b, b) / P[index, index]
+        self.X, self.Y = self.X[keep], self.Y[keep]
+        self.X_norm, self.Y_norm = X_norm, self.Y_norm[keep]
+        self.n_point = n - 1
+        self.update_inference_dataset()              # bumps _model_version: the cached sweeps of SafeOpt / GoOSE.BO are stale
+        self._uploaded_version = self._model_version  # ... but the device model is already current: no re-upload
+        self._cand_token = None
 
     # ---- inference (models/GP_Safe.py:310-352) -----------------------------------------------------------------
     def GP_inference(self, x, inference_dataset=None):

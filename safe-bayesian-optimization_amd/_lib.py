@@ -167,6 +167,7 @@ SYMBOLS = [
     ("sbo_model_set_list", C.c_int, [_P, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("sbo_model_set_prior", C.c_int, [_P, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("sbo_model_append", C.c_int, [_P, _P, _P]),
+    ("sbo_model_remove", C.c_int, [_P, C.c_int]),
     ("sbo_candidates_points", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int64]),
     ("sbo_candidates_grid", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, C.c_int64]),
     ("sbo_candidates_grid_sharded", C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

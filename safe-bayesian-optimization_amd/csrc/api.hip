@@ -529,6 +529,35 @@ int sbo_model_append(sbo_ctx* c, const double* x_norm_new, const double* y_norm_
   return SBO_OK;
 }
 
+// The counterpart of sbo_model_append: observation `index` leaves the resident model under the same frozen
+// hyper-parameters and normalisation, O(n^2) on the device; the rows behind it move up by one.
+int sbo_model_remove(sbo_ctx* c, int index) {
+  if (c) guard_audit_harvest(c, true);
+  if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
+  if (!c->has_model || !c->Fplain.p) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
+  ModelConst& mc = c->mc;
+  const int n = mc.n, d = mc.d;
+  if (index < 0 || index >= n) return fail(SBO_E_INVALID, "index out of range [0, n)");
+  if (n == 1) return fail(SBO_E_INVALID, "a model holds at least one observation");
+  SBO_HIP(hipSetDevice(c->device));
+  { const int rcf = factor_sync(c); if (rcf) return rcf; }     // (the update works on the resident factor)
+  int rc;
+  // (the fp64 twin of an fp32 model follows; a twin left behind by an earlier fp32 model is not this model's)
+  if (c->dtype == SBO_F32 && c->recheck.shadow && c->recheck.shadow->has_model && c->recheck.shadow->mc.n == n &&
+      (rc = sbo_model_remove(c->recheck.shadow, index)))
+    return rc;
+  if ((rc = model_remove(c, index))) return rc;
+  // the derived arrays without the row (device), then the re-pack of the factor images
+  c->h_Xnorm.erase(c->h_Xnorm.begin() + (size_t)index * d, c->h_Xnorm.begin() + (size_t)(index + 1) * d);
+  mc.n = n - 1;
+  mc.npad = (mc.n + 15) / 16 * 16;
+  if ((rc = model_prep(c, c->h_Xnorm.data()))) return rc;
+  if ((rc = model_repack(c))) return rc;
+  ++c->model_serial;
+  model_changed(c);
+  return SBO_OK;
+}
+
 static int alloc_workspace(sbo_ctx* c) {
   const size_t es = c->dtype == SBO_F64 ? 8 : 4;
   const size_t n = (size_t)std::max<long long>(c->cs.n_local, 1);

@@ -411,6 +411,8 @@ struct sbo_ctx {
   int a_ld = 0;                  // stride of alpha64: npad after a build, f_cap after an append
   sbo::DevBuf mwork;             // model build workspace (uploads, fp64 copies of the derived arrays, the factorisation's scratch)
   sbo::DevBuf appendbuf;         // sbo_model_append's uploads and scratch (apart from mwork: a refused append leaves the uploaded invK in place)
+  sbo::DevBuf Fspare, aspare;    // sbo_model_remove writes the factor / alpha without the row here ([q][f_cap][f_cap], [q][a_ld]), then swaps them in
+  sbo::DevBuf removebuf;         // sbo_model_remove's per-row coefficients [q][3 f_cap + 1]
   // Caller's invK on a K1b-capable grid (option chol_async): the GEMM posterior's tables contract with invK itself -- packed
   // here as full matrix-core images, exactly the matrix of models/GP_Safe.py:341-343 -- so the reverse Cholesky factor M (needed
   // by the O(n^2) kernels K1g / K1 / K1c and by sbo_model_append only) is built on stream4 while the caller goes on; whoever
@@ -422,7 +424,7 @@ struct sbo_ctx {
   bool factor_todo = false;        // the chain has not been enqueued yet (sbo_model_set does that last: model_factor_enqueue)
   bool factor_pending = false;     // the factor chain of the current model is (possibly) still running; ev_factor marks its end
   hipEvent_t ev_factor = nullptr, ev_w = nullptr;
-  unsigned long long model_serial = 0;   // bumped by every sbo_model_set / sbo_model_append
+  unsigned long long model_serial = 0;   // bumped by every sbo_model_set / sbo_model_append / sbo_model_remove
   // K1b (bilinear.hip): the plan, its tables, and what its builders and launches keep between calls
   sbo::BilinearPlan bl;
   sbo::DevBuf bl_P0f, bl_P1A, bl_T4f, bl_BtA, bl_SBf, bl_VA, bl_small, bl_work, bl_cheb;
@@ -551,6 +553,7 @@ int model_factor_enqueue(sbo_ctx* c);
 int model_pack_invk(sbo_ctx* c);         // images of the caller's invK for the K1b tables, when the grid arrived after the model   // the deferred factor chain of a caller's invK, behind everything on the critical path
 int model_append_check(sbo_ctx* c, const std::vector<double>& kvec /*[q][n]*/, const double* kappa, const double* rho);
 int model_append_commit(sbo_ctx* c);   // (after model_append_check succeeded; mc.n still the old n)
+int model_remove(sbo_ctx* c, int index);   // the factor and alpha without observation `index` (mc.n still the old n); enqueued, not waited for
 int model_repack(sbo_ctx* c);
 bool bilinear_applicable(const sbo_ctx* c);
 int bilinear_basis_enqueue(sbo_ctx* c, hipStream_t st, bool force_big);

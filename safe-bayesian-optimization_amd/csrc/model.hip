@@ -549,6 +549,101 @@ __global__ __launch_bounds__(1024) void k_model_append_commit(int n, int ld, dou
   for (int j = n + 1 + tid; j < ld; j += blockDim.x) M[(size_t)n * ld + j] = 0.0;
 }
 
+// One observation less.  With m = column j of M (zero above row j, m[j] > 0), M~ = M without column j,
+// r_i = sqrt(sum_{t=j..i} m[t]^2) and the running sum W_i = sum_{t=j..i} m[t] row_t(M~), the Givens rotations that turn m into
+// r_{n-1} e_j leave rows 0 .. j-1 of M~ as they are and give, for i = j+1 .. n-1,
+//   new row i-1 = (r_{i-1} / r_i) row_i(M~) - (m[i] / (r_i r_{i-1})) W_{i-1};
+// the rotated row j is dropped.  N^T N is the Schur complement invK_-j-j - p p^T / P_jj with p = M~^T m = W_{n-1} and
+// P_jj = r_{n-1}^2, the exact inverse of K without row and column j, and alpha' = alpha_-j - p alpha_j / P_jj.  Two launches:
+//   k_model_remove_coef: one workgroup per output reads column j once and writes what every strip needs per row -- m[i],
+//                        a[i] = r_{i-1} / r_i, b[i] = m[i] / (r_i r_{i-1}) -- and alpha_j / P_jj (IEEE sqrt and division);
+//   k_model_remove     : one wave per strip of kRemoveStrip new columns and output, lanes along the columns (the row-major
+//                        factor is read and written coalesced), down the rows with W in a register.
+// New column c comes from old column c (c < j) or c + 1 and new row i - 1 from old row i, so the result goes to a second, zeroed
+// buffer (no strip reads what another writes); nothing above the diagonal of the old factor is read (a build leaves scratch there).
+constexpr int kRemoveStrip = 64;
+__global__ __launch_bounds__(256) void k_model_remove_coef(int n, int ld, int a_ld, int j, const double* __restrict__ F,
+                                                           const double* __restrict__ alpha, double* __restrict__ coef) {
+  __shared__ double mv[SBO_MAX_N], sq[SBO_MAX_N];
+  __shared__ double part[256];
+  const int o = blockIdx.x, tid = threadIdx.x, len = n - j;
+  const double* M = F + (size_t)o * ld * ld;
+  double* cm = coef + (size_t)o * (3 * (size_t)ld + 1);
+  double* ca = cm + ld;
+  double* cb = ca + ld;
+  for (int k = tid; k < len; k += 256) {
+    const double v = M[(size_t)(j + k) * ld + j];
+    cm[j + k] = v;
+    mv[k] = v;
+    sq[k] = v * v;
+  }
+  __syncthreads();
+  // inclusive prefix sums of m^2: a contiguous chunk per thread, the chunks before it summed in order
+  const int chunk = (len + 255) / 256, k0 = tid * chunk, k1 = min(len, k0 + chunk);
+  double s = 0.0;
+  for (int k = k0; k < k1; ++k) s += sq[k];
+  part[tid] = s;
+  __syncthreads();
+  double acc = 0.0;
+  for (int t = 0; t < tid; ++t) acc += part[t];
+  for (int k = k0; k < k1; ++k) {
+    const double prev = acc;
+    acc += sq[k];
+    if (k > 0) {
+      const double r = sqrt(acc), rp = sqrt(prev);
+      ca[j + k] = rp / r;
+      cb[j + k] = mv[k] / (r * rp);
+    }
+    if (k == len - 1) cb[ld + 0] = alpha[(size_t)o * a_ld + j] / acc;       // alpha_j / P_jj
+  }
+}
+__global__ __launch_bounds__(64) void k_model_remove(int n, int ld, int a_ld, int j, const double* __restrict__ F,
+                                                     const double* __restrict__ alpha, const double* __restrict__ coef,
+                                                     double* __restrict__ F2, double* __restrict__ alpha2) {
+  constexpr int kU = 8;                      // rows in flight per wave
+  const int o = blockIdx.y, c0 = blockIdx.x * kRemoveStrip, cn = c0 + (int)threadIdx.x;
+  const bool active = cn < n - 1;
+  const int co = cn < j ? cn : cn + 1;       // the old column of new column cn
+  const double* M = F + (size_t)o * ld * ld;
+  double* N = F2 + (size_t)o * ld * ld;
+  const double* cm = coef + (size_t)o * (3 * (size_t)ld + 1);
+  const double* ca = cm + ld;
+  const double* cb = ca + ld;
+  // rows above j: as they were (their columns lie left of j)
+  for (int i0 = c0; i0 < j; i0 += kU) {
+    double x[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int i = i0 + u;
+      x[u] = (active && i < j && cn <= i) ? M[(size_t)i * ld + cn] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int i = i0 + u;
+      if (active && i < j && cn <= i) N[(size_t)i * ld + cn] = x[u];
+    }
+  }
+  // rows j .. n-1 (a strip right of j starts at its own diagonal: the rows above hold nothing of its columns)
+  double W = 0.0;
+  for (int i0 = max(j, c0); i0 < n; i0 += kU) {
+    double x[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int i = i0 + u;
+      x[u] = (active && i < n && co <= i) ? M[(size_t)i * ld + co] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int i = i0 + u;
+      if (i < n) {
+        if (i > j && active && cn <= i - 1) N[(size_t)(i - 1) * ld + cn] = ca[i] * x[u] - cb[i] * W;
+        W += cm[i] * x[u];
+      }
+    }
+  }
+  if (active) alpha2[(size_t)o * a_ld + cn] = alpha[(size_t)o * a_ld + co] - W * cb[ld];
+}
+
 // Derived model arrays from the uploaded X_norm [n][d] / Y_norm [n][q] (models/GP_Safe.py:112-116, 331-342):
 //   As[o][j][a] = X_norm[j][a] ell_a^-1/2, sqA[o][j] = sum_a As^2 (model dtype for the K1 kernels, fp64 for the build),
 //   Xn[j][a] (model dtype, for the mean gradient), rhs[o][j] = Y_norm[j][o] - mp_o (fp64, only with Y_norm).
@@ -890,6 +985,33 @@ int model_append_commit(sbo_ctx* c) {
                      (const double*)drho, (const double*)dscratch, (const double*)dsk);
   SBO_HIP(hipGetLastError());
   c->invk_img_valid = false;                                    // (the images of the caller's invK do not follow an append)
+  c->invk_w_valid = false;
+  return SBO_OK;
+}
+
+// The factor and alpha without observation j, written into the spare pair (same leading dimensions, zeroed first: the padding
+// and everything right of the diagonal stay zero) and swapped in once every launch has been accepted -- until then nothing of
+// the model has changed.  The outgoing pair is the next call's spare.
+int model_remove(sbo_ctx* c, int j) {
+  const int n = c->mc.n, q = c->mc.q, cap = c->f_cap, a_ld = c->a_ld;
+  const size_t fbytes = sizeof(double) * (size_t)q * cap * cap, abytes = sizeof(double) * (size_t)q * a_ld;
+  int rc;
+  if ((rc = ensure(c->Fspare, fbytes))) return rc;
+  if ((rc = ensure(c->aspare, abytes))) return rc;
+  if ((rc = ensure(c->removebuf, sizeof(double) * (size_t)q * (3 * (size_t)cap + 1)))) return rc;
+  SBO_HIP(hipMemsetAsync(c->Fspare.p, 0, fbytes, c->stream));
+  SBO_HIP(hipMemsetAsync(c->aspare.p, 0, abytes, c->stream));
+  hipLaunchKernelGGL(k_model_remove_coef, dim3(q), dim3(256), 0, c->stream, n, cap, a_ld, j, (const double*)c->Fplain.p,
+                     (const double*)c->alpha64.p, (double*)c->removebuf.p);
+  hipLaunchKernelGGL(k_model_remove, dim3((unsigned)((n - 1 + kRemoveStrip - 1) / kRemoveStrip), q), dim3(64), 0, c->stream, n, cap, a_ld, j,
+                     (const double*)c->Fplain.p, (const double*)c->alpha64.p, (const double*)c->removebuf.p, (double*)c->Fspare.p,
+                     (double*)c->aspare.p);
+  SBO_HIP(hipGetLastError());
+  std::swap(c->Fplain.p, c->Fspare.p);
+  std::swap(c->Fplain.bytes, c->Fspare.bytes);
+  std::swap(c->alpha64.p, c->aspare.p);
+  std::swap(c->alpha64.bytes, c->aspare.bytes);
+  c->invk_img_valid = false;                                    // (the images of the caller's invK do not follow a removal)
   c->invk_w_valid = false;
   return SBO_OK;
 }

@@ -181,6 +181,17 @@ class SweepEngine:
         L.check(self._lib.sbo_model_append(self._ctx, _ptr(x), _ptr(y)))
         self.n += 1
 
+    def remove_sample(self, index: int):
+        """The counterpart of ``append_sample`` (``sbo_model_remove``): observation ``index`` (0-based, in the order of ``X_norm``
+        as set and appended) leaves the resident model under the same frozen constants, O(n^2) on the device; the rows behind
+        it move up by one.  A model keeps at least one observation."""
+        if isinstance(index, bool) or not isinstance(index, (int, np.integer)):
+            raise ValueError("index must be an integer")
+        if self.n and not 0 <= index < self.n:          # (without a model the library answers: SBO_E_NO_MODEL)
+            raise ValueError(f"index {int(index)} out of range [0, {self.n})")
+        L.check(self._lib.sbo_model_remove(self._ctx, int(index)))
+        self.n -= 1
+
     # ---- candidates --------------------------------------------------------------------------
     def set_points(self, points, first: int = 0):
         pts = np.asarray(points)
