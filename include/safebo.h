@@ -298,6 +298,32 @@ int sbo_model_append(sbo_ctx* ctx, const double* x_norm_new, const double* y_nor
  * sbo_model_append). */
 int sbo_model_remove(sbo_ctx* ctx, int index);
 
+/* Leave-one-out diagnostics of the resident model: is the frozen model still calibrated on its own data,
+ * and which observation fits worst?  With P = invK, the prediction of observation i from all the others has the residual
+ * e_i = y_i - mu_-i = alpha_i / P_ii and the variance v_i = 1 / P_ii (noise included); P_ii is a column sum of squares of the
+ * resident lower factor M (M^T M = invK), so one pass over the triangle on the device gives every e_i and v_i in O(n^2) and
+ * O(n q) bytes come back -- no [n, n] matrix is formed or crosses the bus.  Everything is in normalised units and fp64 whatever
+ * the model dtype.  resid_out / var_out: [n][q] as in sbo_posterior_get, rows in the order of X_norm as set, appended and
+ * removed; each of the three outputs may be NULL.  `outside` counts |z_i| > b, the test every safe set rests on
+ * (|y - mean| <= b sqrt(var)).  The reference's NLL form (models/GP_Safe.py:169-192) is r^T alpha + logdet with
+ * r = Y_norm - mean prior: since alpha_i = e_i / v_i, a caller forms it from these outputs and its own Y_norm (the library keeps
+ * no copy of Y_norm).  The call is read-only: model, plans, caches, guard band and options are as before, and a posterior or
+ * sweep after it equals one before it bit for bit; two calls on the same model return the same bits.  It waits for a deferred
+ * factorisation first, so a caller's invK that is not positive definite gives SBO_E_INVALID here as elsewhere.  SBO_E_INVALID
+ * also for a NULL ctx and for b not finite or < 0; SBO_E_NO_MODEL without a model.  Multi-rank: the model is replicated, any
+ * rank may call, nothing is communicated. */
+typedef struct sbo_model_loo_result {
+  int32_t n, q;
+  double  logdet[SBO_MAX_Q];    /* log det(K_o + sn2_o I) = -2 sum_i log M_o[i][i]                          */
+  double  lpd[SBO_MAX_Q];       /* sum_i log N(y_i | mu_-i, v_i) = -1/2 sum_i (log(2 pi v_i) + e_i^2 / v_i) */
+  double  z_max[SBO_MAX_Q];     /* max_i |z_i|,  z_i = e_i / sqrt(v_i) = alpha_i / sqrt(P_ii)               */
+  int32_t z_argmax[SBO_MAX_Q];  /* its index; ties -> lowest index                                          */
+  int32_t outside[SBO_MAX_Q];   /* #{ i : |z_i| > b }                                                       */
+} sbo_model_loo_result;
+
+int sbo_model_loo(sbo_ctx* ctx, double b, double* resid_out /* [n][q] or NULL */, double* var_out /* [n][q] or NULL */,
+                  sbo_model_loo_result* result /* or NULL */);
+
 /* explicit list: points[N, d] of doubles (dtype SBO_F64) or floats (SBO_F32); first_index = global flat
  * index of points[0] (shard offset). */
 int sbo_candidates_points(sbo_ctx* ctx, const void* points, int points_dtype, int64_t n_local, int d,

@@ -247,13 +247,21 @@ class GP:
         self.hypopt, self.invKopt = self.determine_hyperparameters(self.X_norm, self.Y_norm)
         self.update_inference_dataset()
 
-    def add_sample(self, x_new, y_new, incremental: bool = False, window: int | None = None):
+    def add_sample(self, x_new, y_new, incremental: bool = False, window: int | None = None, refit_when=None):
         """Reference behaviour (models/GP_Safe.py:283-304): re-normalise, refit, rebuild.  ``incremental=True`` is the
         opt-in fast path of SURVEY.md 8(f) rank 2: normalisation constants and hyper-parameters stay frozen and the device
         model gains one row in O(n^2) (``sbo_model_append``); the Python-side ``inference_datasets`` follows with the
         bordered inverse, also O(n^2).  ``window=W`` (with ``incremental=True`` only) keeps a sliding window of the W most
         recent observations: a model that already holds W of them loses its oldest (``remove_sample(0)``) before the new one
-        is appended, so n never exceeds W and a model at ``SBO_MAX_N`` keeps running."""
+        is appended, so n never exceeds W and a model at ``SBO_MAX_N`` keeps running.  ``refit_when=fn`` (with ``incremental=True``
+        only) asks whether the frozen constants still describe the data: after the update ``fn(self.loo())`` is called, and if it
+        returns true the model is refitted on the data it now holds by exactly the default path (re-normalise, refit, rebuild).
+        The policy is the caller's; the library fixes no threshold."""
+        if refit_when is not None:
+            if not incremental:
+                raise ValueError("refit_when needs incremental=True (the default path refits on every sample)")
+            if not callable(refit_when):
+                raise ValueError("refit_when must be callable: it receives the dict of loo()")
         if window is not None:
             if not incremental:
                 raise ValueError("window needs incremental=True (the default path refits on all data)")
@@ -285,7 +293,8 @@ class GP:
             self.update_inference_dataset()              # bumps _model_version: the cached sweeps of SafeOpt / GoOSE.BO are stale
             self._uploaded_version = self._model_version  # ... but the device model is already current: no re-upload
             self._cand_token = None
-            return
+            if refit_when is None or not refit_when(self.loo()):
+                return
         self.X_norm, self.Y_norm = self.data_normalization()
         self.hypopt, self.invKopt = self.determine_hyperparameters(self.X_norm, self.Y_norm)
         self.update_inference_dataset()
@@ -321,6 +330,21 @@ class GP:
         self.update_inference_dataset()              # bumps _model_version: the cached sweeps of SafeOpt / GoOSE.BO are stale
         self._uploaded_version = self._model_version  # ... but the device model is already current: no re-upload
         self._cand_token = None
+
+    def loo(self, b=None):
+        """Leave-one-out diagnostics of the model as it stands (``sbo_model_loo``: one O(n^2) pass over the device model's factor,
+        nothing is changed).  Physical units: ``mean`` [n, q] = Y - resid Y_std, the prediction of every observation from all the
+        others, and ``var`` [n, q] = var Y_std^2 (noise included).  ``z`` [n, q] and the per-output summaries ``logdet``, ``lpd``,
+        ``z_max``, ``z_argmax``, ``outside`` (= #{|z_i| > b}) and ``nll`` (the fit objective's form at the frozen hyper-parameters)
+        are the engine's, in normalised units.  ``b`` defaults to the instance's ``b`` where the class has one, else 3.0."""
+        if b is None:
+            b = getattr(self, "b", 3.0)
+        self._sync_model()
+        d = self.engine.model_loo(b, self.Y_norm)
+        out = {"mean": self.Y - d["resid"] * self.Y_std, "var": d["var"] * self.Y_std ** 2}
+        for k in ("z", "logdet", "lpd", "z_max", "z_argmax", "outside", "nll"):
+            out[k] = d[k]
+        return out
 
     # ---- inference (models/GP_Safe.py:310-352) -----------------------------------------------------------------
     def GP_inference(self, x, inference_dataset=None):

@@ -127,6 +127,11 @@ class FitReport(C.Structure):
                 ("host_syncs", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ModelLooResult(C.Structure):
+    _fields_ = [("n", C.c_int32), ("q", C.c_int32), ("logdet", C.c_double * SBO_MAX_Q), ("lpd", C.c_double * SBO_MAX_Q),
+                ("z_max", C.c_double * SBO_MAX_Q), ("z_argmax", C.c_int32 * SBO_MAX_Q), ("outside", C.c_int32 * SBO_MAX_Q)]
+
+
 class Profile(C.Structure):
     _fields_ = [
         ("posterior_ms", C.c_double), ("classify_ms", C.c_double), ("expander_ms", C.c_double),
@@ -168,6 +173,7 @@ SYMBOLS = [
     ("sbo_model_set_prior", C.c_int, [_P, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("sbo_model_append", C.c_int, [_P, _P, _P]),
     ("sbo_model_remove", C.c_int, [_P, C.c_int]),
+    ("sbo_model_loo", C.c_int, [_P, C.c_double, _P, _P, C.POINTER(ModelLooResult)]),
     ("sbo_candidates_points", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int64]),
     ("sbo_candidates_grid", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, C.c_int64]),
     ("sbo_candidates_grid_sharded", C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -558,6 +558,36 @@ int sbo_model_remove(sbo_ctx* c, int index) {
   return SBO_OK;
 }
 
+// Leave-one-out diagnostics of the resident model: read-only, O(n^2) on the device, O(n q) bytes back.
+int sbo_model_loo(sbo_ctx* c, double b, double* resid_out, double* var_out, sbo_model_loo_result* result) {
+  if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
+  if (!std::isfinite(b) || b < 0.0) return fail(SBO_E_INVALID, "b must be finite and >= 0");
+  if (!c->has_model || !c->Fplain.p) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
+  SBO_HIP(hipSetDevice(c->device));
+  { const int rcf = factor_sync(c); if (rcf) return rcf; }     // (the sums run over the resident factor)
+  const int n = c->mc.n, q = c->mc.q;
+  const unsigned char* h = nullptr;
+  const int rc = model_loo(c, b, resid_out || var_out, &h);
+  if (rc) return rc;
+  const size_t head = sizeof(LooSummary) * kMaxQ, nq = sizeof(double) * (size_t)n * q;
+  if (resid_out) std::memcpy(resid_out, h + head, nq);
+  if (var_out) std::memcpy(var_out, h + head + nq, nq);
+  if (result) {
+    std::memset(result, 0, sizeof(*result));
+    result->n = n;
+    result->q = q;
+    const LooSummary* s = (const LooSummary*)h;
+    for (int o = 0; o < q; ++o) {
+      result->logdet[o] = s[o].logdet;
+      result->lpd[o] = s[o].lpd;
+      result->z_max[o] = s[o].z_max;
+      result->z_argmax[o] = s[o].z_argmax;
+      result->outside[o] = s[o].outside;
+    }
+  }
+  return SBO_OK;
+}
+
 static int alloc_workspace(sbo_ctx* c) {
   const size_t es = c->dtype == SBO_F64 ? 8 : 4;
   const size_t n = (size_t)std::max<long long>(c->cs.n_local, 1);

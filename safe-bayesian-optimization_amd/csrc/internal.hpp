@@ -341,6 +341,17 @@ struct Robust {
   void invalidate() { valid = false; }
 };
 
+// sbo_model_loo (model.hip): what one call leaves per output, and the buffers every call reuses
+struct LooSummary {
+  double logdet, lpd, z_max;
+  int z_argmax, outside;
+};
+struct Loo {
+  DevBuf part;     // [q][ceil(f_cap / kLooRows)][f_cap] partial column sums of squares of the factor, one row per chunk of rows
+  DevBuf out;      // LooSummary[kMaxQ] | resid [n][q] | var [n][q]
+  Pinned h_out;    // ... and where the one copy of a call lands
+};
+
 }  // namespace sbo
 
 struct sbo_ctx {
@@ -413,6 +424,7 @@ struct sbo_ctx {
   sbo::DevBuf appendbuf;         // sbo_model_append's uploads and scratch (apart from mwork: a refused append leaves the uploaded invK in place)
   sbo::DevBuf Fspare, aspare;    // sbo_model_remove writes the factor / alpha without the row here ([q][f_cap][f_cap], [q][a_ld]), then swaps them in
   sbo::DevBuf removebuf;         // sbo_model_remove's per-row coefficients [q][3 f_cap + 1]
+  sbo::Loo loo;                  // sbo_model_loo's scratch and landing area (the call reads the model and writes nothing else)
   // Caller's invK on a K1b-capable grid (option chol_async): the GEMM posterior's tables contract with invK itself -- packed
   // here as full matrix-core images, exactly the matrix of models/GP_Safe.py:341-343 -- so the reverse Cholesky factor M (needed
   // by the O(n^2) kernels K1g / K1 / K1c and by sbo_model_append only) is built on stream4 while the caller goes on; whoever
@@ -554,6 +566,9 @@ int model_pack_invk(sbo_ctx* c);         // images of the caller's invK for the 
 int model_append_check(sbo_ctx* c, const std::vector<double>& kvec /*[q][n]*/, const double* kappa, const double* rho);
 int model_append_commit(sbo_ctx* c);   // (after model_append_check succeeded; mc.n still the old n)
 int model_remove(sbo_ctx* c, int index);   // the factor and alpha without observation `index` (mc.n still the old n); enqueued, not waited for
+// leave-one-out diagnostics of the resident factor / alpha; waited for: *host then points at LooSummary[kMaxQ] | resid [n][q] | var [n][q]
+// (the arrays only with `arrays`)
+int model_loo(sbo_ctx* c, double b, bool arrays, const unsigned char** host);
 int model_repack(sbo_ctx* c);
 bool bilinear_applicable(const sbo_ctx* c);
 int bilinear_basis_enqueue(sbo_ctx* c, hipStream_t st, bool force_big);

@@ -644,6 +644,94 @@ __global__ __launch_bounds__(64) void k_model_remove(int n, int ld, int a_ld, in
   if (active) alpha2[(size_t)o * a_ld + cn] = alpha[(size_t)o * a_ld + co] - W * cb[ld];
 }
 
+// Leave-one-out diagnostics of the resident model.  With P = invK = M^T M the leave-one-out prediction of
+// observation i has the residual e_i = y_i - mu_-i = alpha_i / P_ii and the variance v_i = 1 / P_ii (noise included), and
+// P_ii = sum_{t >= i} M[t][i]^2 is a column sum of squares of the lower factor; log det(K + sn2 I) = -2 sum_i log M[i][i].
+// Read-only, two launches:
+//   k_model_loo_colsq : one wave per strip of kLooStrip columns, chunk of kLooRows rows and output, lanes along the columns (a row
+//                       segment is one coalesced load, kU rows in flight), the running sum in a register, rows in ascending order;
+//                       the partial sum of chunk k goes to part[o][k][column].  Nothing above the diagonal is read (a build leaves
+//                       scratch there) and no row >= n (a grown factor has ld > n).  A chunk that lies above the strip's diagonal
+//                       block has no rows: its wave leaves at once and its partials are never read.
+//   k_model_loo_finish: one workgroup per output adds the partials of a column in chunk order (from the chunk that holds the
+//                       diagonal on), forms e, v, z = e / sqrt(v) (IEEE division and sqrt) and reduces logdet, lpd, max |z| with
+//                       its lowest index and #{|z| > b} in LDS.
+// No atomics and one summation order: the same model gives the same bits whatever was called before.
+constexpr int kLooStrip = 64;
+constexpr int kLooRows = 64;
+__global__ __launch_bounds__(64) void k_model_loo_colsq(int n, int ld, int chunks, const double* __restrict__ F, double* __restrict__ part) {
+  constexpr int kU = 16;                     // rows in flight per wave
+  const int o = blockIdx.z, k = blockIdx.y, c0 = blockIdx.x * kLooStrip, cn = c0 + (int)threadIdx.x;
+  const int r0 = max(k * kLooRows, c0), r1 = min(n, (k + 1) * kLooRows);
+  if (r1 <= r0) return;
+  const double* M = F + (size_t)o * ld * ld;
+  double s = 0.0;
+  for (int i0 = r0; i0 < r1; i0 += kU) {
+    double x[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int i = i0 + u;
+      x[u] = (i < r1 && cn <= i) ? M[(size_t)i * ld + cn] : 0.0;      // (cn <= i < n: inside the triangle)
+    }
+#pragma unroll
+    for (int u = 0; u < kU; ++u) s += x[u] * x[u];
+  }
+  if (cn < n) part[((size_t)o * chunks + k) * ld + cn] = s;
+}
+__global__ __launch_bounds__(1024) void k_model_loo_finish(int n, int q, int ld, int a_ld, int chunks, double b, const double* __restrict__ F,
+                                                           const double* __restrict__ alpha, const double* __restrict__ part,
+                                                           double* __restrict__ resid /* [n][q] or nullptr */,
+                                                           double* __restrict__ var /* [n][q] or nullptr */, LooSummary* __restrict__ sum) {
+  __shared__ double s_ld[1024], s_lp[1024], s_z[1024];
+  __shared__ int s_i[1024], s_c[1024];
+  constexpr int kU = 8;
+  const int o = blockIdx.x, tid = threadIdx.x;
+  const double* M = F + (size_t)o * ld * ld;
+  double ldsum = 0.0, lpsum = 0.0, zm = -1.0;
+  int zi = 0x7fffffff, cnt = 0;
+  for (int i = tid; i < n; i += 1024) {
+    double P = 0.0;
+    for (int k0 = i / kLooRows; k0 < chunks; k0 += kU) {      // (chunk order; kU partials in flight, the missing ones add +0)
+      double x[kU];
+#pragma unroll
+      for (int u = 0; u < kU; ++u) x[u] = k0 + u < chunks ? part[((size_t)o * chunks + k0 + u) * ld + i] : 0.0;
+#pragma unroll
+      for (int u = 0; u < kU; ++u) P += x[u];
+    }
+    const double a = alpha[(size_t)o * a_ld + i];
+    const double v = 1.0 / P, e = a / P;
+    const double az = fabs(e / sqrt(v));
+    if (resid) resid[(size_t)i * q + o] = e;
+    if (var) var[(size_t)i * q + o] = v;
+    ldsum += log(M[(size_t)i * ld + i]);
+    lpsum += log(6.283185307179586476925 * v) + e * e / v;
+    if (az > zm) { zm = az; zi = i; }        // (ascending i: the lowest index of a tie stays)
+    cnt += az > b ? 1 : 0;
+  }
+  s_ld[tid] = ldsum, s_lp[tid] = lpsum, s_z[tid] = zm, s_i[tid] = zi, s_c[tid] = cnt;
+  __syncthreads();
+  for (int w = 512; w > 0; w >>= 1) {
+    if (tid < w) {
+      s_ld[tid] += s_ld[tid + w];
+      s_lp[tid] += s_lp[tid + w];
+      s_c[tid] += s_c[tid + w];
+      const double z2 = s_z[tid + w];
+      const int i2 = s_i[tid + w];
+      if (z2 > s_z[tid] || (z2 == s_z[tid] && i2 < s_i[tid])) { s_z[tid] = z2; s_i[tid] = i2; }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    LooSummary r;
+    r.logdet = -2.0 * s_ld[0];
+    r.lpd = -0.5 * s_lp[0];
+    r.z_max = s_z[0];
+    r.z_argmax = s_i[0];
+    r.outside = s_c[0];
+    sum[o] = r;
+  }
+}
+
 // Derived model arrays from the uploaded X_norm [n][d] / Y_norm [n][q] (models/GP_Safe.py:112-116, 331-342):
 //   As[o][j][a] = X_norm[j][a] ell_a^-1/2, sqA[o][j] = sum_a As^2 (model dtype for the K1 kernels, fp64 for the build),
 //   Xn[j][a] (model dtype, for the mean gradient), rhs[o][j] = Y_norm[j][o] - mp_o (fp64, only with Y_norm).
@@ -1013,6 +1101,35 @@ int model_remove(sbo_ctx* c, int j) {
   std::swap(c->alpha64.bytes, c->aspare.bytes);
   c->invk_img_valid = false;                                    // (the images of the caller's invK do not follow a removal)
   c->invk_w_valid = false;
+  return SBO_OK;
+}
+
+// sbo_model_loo's device side: the two launches, one copy into the pinned landing area, one wait.  Nothing of the model, the plans
+// or the caches is written; the scratch is kept for the next call (a grown factor grows it).
+int model_loo(sbo_ctx* c, double b, bool arrays, const unsigned char** host) {
+  const int n = c->mc.n, q = c->mc.q, cap = c->f_cap, a_ld = c->a_ld;
+  const int chunks = (n + kLooRows - 1) / kLooRows, strips = (n + kLooStrip - 1) / kLooStrip;
+  const size_t head = sizeof(LooSummary) * kMaxQ, nq = sizeof(double) * (size_t)n * q;
+  const size_t bytes = head + (arrays ? 2 * nq : 0);
+  int rc;
+  if ((rc = ensure(c->loo.part, sizeof(double) * (size_t)q * ((cap + kLooRows - 1) / kLooRows) * cap))) return rc;
+  if ((rc = ensure(c->loo.out, head + 2 * sizeof(double) * (size_t)cap * q))) return rc;
+  if (c->loo.h_out.bytes < bytes) {
+    c->loo.h_out.reset();
+    const size_t want = head + 2 * sizeof(double) * (size_t)cap * q;
+    if (hipHostMalloc(&c->loo.h_out.p, want, hipHostMallocDefault) != hipSuccess) return fail(SBO_E_HIP, "hipHostMalloc (leave-one-out results)");
+    c->loo.h_out.bytes = want;
+  }
+  unsigned char* dout = (unsigned char*)c->loo.out.p;
+  hipLaunchKernelGGL(k_model_loo_colsq, dim3((unsigned)strips, (unsigned)chunks, (unsigned)q), dim3(64), 0, c->stream, n, cap, chunks,
+                     (const double*)c->Fplain.p, (double*)c->loo.part.p);
+  hipLaunchKernelGGL(k_model_loo_finish, dim3(q), dim3(1024), 0, c->stream, n, q, cap, a_ld, chunks, b, (const double*)c->Fplain.p,
+                     (const double*)c->alpha64.p, (const double*)c->loo.part.p, arrays ? (double*)(dout + head) : (double*)nullptr,
+                     arrays ? (double*)(dout + head + nq) : (double*)nullptr, (LooSummary*)dout);
+  SBO_HIP(hipGetLastError());
+  SBO_HIP(hipMemcpyAsync(c->loo.h_out.p, dout, bytes, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(stream_wait(c, c->stream));
+  *host = (const unsigned char*)c->loo.h_out.p;
   return SBO_OK;
 }
 

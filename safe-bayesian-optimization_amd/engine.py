@@ -122,6 +122,7 @@ class SweepEngine:
         else:
             L.check(self._lib.sbo_model_set(*args, None))
         self.n, self.d, self.q = n, d, q
+        self._prior = self._prior_mean(arrs[2], arrs[3], mean_prior)
 
     def model_fit(self, ds: dict, bounds, init_pop, seed: int = 0, maxiter: int = 1000, tol: float = 0.01, atol: float = 0.0,
                   polish: bool = True, polish_maxiter: int = 10000, polish_ftol: float = FLOAT32_EPS, polish_gtol: float = 1e-8,
@@ -162,6 +163,7 @@ class SweepEngine:
                                         C.byref(rep)))
         self.tag, self.np_dtype = tag, np_dtype
         self.n, self.d, self.q = n, d, q
+        self._prior = self._prior_mean(arrs[2], arrs[3], mp)
         out = {"hypopt": hyp}
         for name, _ in L.FitReport._fields_:
             if name == "reserved":
@@ -169,6 +171,15 @@ class SweepEngine:
             v = getattr(rep, name)
             out[name] = np.array(v[:q]) if hasattr(v, "__len__") else v
         return out
+
+    @staticmethod
+    def _prior_mean(Y_mean, Y_std, mean_prior):
+        """The prior mean of the resident model in normalised units (models/GP_Safe.py:331-332, or the caller's)."""
+        if mean_prior is not None:
+            return _f64(mean_prior).reshape(-1).copy()
+        mp = -2.0 * Y_mean / Y_std
+        mp[0] = 0.0
+        return mp
 
     def append_sample(self, x_norm_new, y_norm_new):
         """One more observation under frozen hyper-parameters and normalisation: O(n^2) on the
@@ -191,6 +202,29 @@ class SweepEngine:
             raise ValueError(f"index {int(index)} out of range [0, {self.n})")
         L.check(self._lib.sbo_model_remove(self._ctx, int(index)))
         self.n -= 1
+
+    def model_loo(self, b: float = 3.0, Y_norm=None) -> dict:
+        """Leave-one-out diagnostics of the resident model (``sbo_model_loo``), normalised units, fp64 whatever the model dtype:
+        ``resid`` [n, q] = y_i - mu_-i, ``var`` [n, q] (noise included), ``z`` [n, q] = resid / sqrt(var), and per output ``logdet``
+        = log det(K + sn2 I), ``lpd`` = sum_i log N(y_i | mu_-i, v_i), ``z_max`` = max |z| with its index ``z_argmax`` (the lowest of a
+        tie) and ``outside`` = #{|z_i| > b}.  One O(n^2) pass over the resident factor on the device; the model is not changed.
+        With ``Y_norm`` [n, q] (the rows the model holds; the library keeps no copy) it adds the reference's NLL form
+        ``nll`` [q] = sum_i r_i e_i / v_i + logdet with r = Y_norm - prior mean (models/GP_Safe.py:169-192 without its jitter)."""
+        b = float(b)
+        n, q = self.n, self.q
+        resid = np.empty((n, q), dtype=np.float64)
+        var = np.empty((n, q), dtype=np.float64)
+        res = L.ModelLooResult()
+        L.check(self._lib.sbo_model_loo(self._ctx, b, _ptr(resid), _ptr(var), C.byref(res)))
+        out = {"resid": resid, "var": var, "z": resid / np.sqrt(var), "logdet": np.array(res.logdet[:q]), "lpd": np.array(res.lpd[:q]),
+               "z_max": np.array(res.z_max[:q]), "z_argmax": np.array(res.z_argmax[:q], dtype=np.int64),
+               "outside": np.array(res.outside[:q], dtype=np.int64)}
+        if Y_norm is not None:
+            Y = _f64(Y_norm)
+            if Y.shape != (n, q):
+                raise ValueError("Y_norm must be [n, q]")
+            out["nll"] = np.sum((Y - self._prior) * resid / var, axis=0) + out["logdet"]
+        return out
 
     # ---- candidates --------------------------------------------------------------------------
     def set_points(self, points, first: int = 0):
