@@ -112,6 +112,10 @@ int sbo_init(int device_id, sbo_ctx** out) {
   c->device = device_id;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) c->n_cu = prop.multiProcessorCount;
+  {
+    const int rc = col_decide_resident(&c->decide_wg_per_cu);
+    if (rc) return rc;
+  }
   e = hipStreamCreateWithFlags(&own.stream.s, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&own.stream2.s, hipStreamNonBlocking);
   if (e == hipSuccess) {
@@ -175,6 +179,7 @@ static int shadow_ensure(sbo_ctx* c) {
   s->is_shadow = true;
   s->device = c->device;
   s->n_cu = c->n_cu;
+  s->decide_wg_per_cu = c->decide_wg_per_cu;
   s->stream = c->stream;
   s->stream2 = c->stream2;
   s->stream3 = c->stream3;
@@ -283,6 +288,7 @@ const OptRow kOptions[] = {
     OPT_RANGE(grad_defer, 0, 3, "grad_defer must be 0 .. 3", kOptInterp, nullptr),
     OPT_BOOL(k1_sched, kOptNothing, nullptr),
     OPT_BOOL(col_overlap, kOptNothing, nullptr),
+    OPT_RANGE(col_queue, 64, 128, "col_queue must be within 64 .. 128 (the default)", kOptNothing, nullptr),
     OPT_BOOL(scan_blocks, kOptNothing, nullptr),
     OPT_RANGE(fuse_classify, -1, 1, "fuse_classify must be -1 (auto), 0 or 1", kOptNothing, nullptr),
     OPT_BOOL(goose_pairs, kOptNothing, nullptr),

@@ -370,6 +370,7 @@ struct sbo_ctx {
   hipStream_t stream4 = nullptr;   // the deferred factorisation of a caller's invK (chol_async): off the critical path of a model change
   hipStream_t stream3 = nullptr;   // spare high-priority stream (drained with the others)
   int n_cu = 256;
+  int decide_wg_per_cu = 1;        // workgroups of k_col_decide a CU holds at once (the occupancy query of sbo_init): sizes its persistent grid
   // What sbo_set_option steers (api.hip: one table row per key -- how the value is taken, its bounds, what it makes stale)
   struct Options {
     int chol_async = 1;
@@ -388,6 +389,7 @@ struct sbo_ctx {
     int comm_events = 0;     // an event pair per collective (MultiRank::comm_ev) whose elapsed times sbo_profile.comm_ms sums
     int col_path = 1;        // 0 = never
     int col_overlap = 1;     // 1 = the expander chain runs on stream3 beside the objective's posterior launch; 0: one stream
+    int col_queue = 128;     // open candidates a wave of k_col_decide queues in LDS before it flushes them to the scan list: 64 .. 128 (64: a flush before every append, the test of that path)
     int grad_defer = 1;          // 0 = K1i's gate stays in front of the posterior launch (r04)
     int halo_spec = 1;       // speculative halo (MultiRank::halo_guess)
     int scan_waves = 1;      // 1: candidates the coarse bounds leave open are scanned one wave each (0: by their own thread)
@@ -538,6 +540,7 @@ int ensure(DevBuf& b, size_t bytes);
 hipError_t stream_wait(const sbo_ctx* c, hipStream_t st);   // hipStreamSynchronize, polling first (option spin_wait)
 void release(DevBuf& b);
 void drain_streams(sbo_ctx* c);
+int col_decide_resident(int* wg_per_cu);   // sets.hip: the runtime's occupancy of k_col_decide, workgroups per CU
 int factor_sync(sbo_ctx* c);      // wait for a deferred factorisation (sbo_ctx::factor_pending); SBO_E_INVALID when invK was not positive definite   // after a failed call: wait for whatever it left on the main and side streams
 
 // the posterior inside a sweep, without synchronisation or timing (api.hip); `out` (nullptr: not wanted) is reset first

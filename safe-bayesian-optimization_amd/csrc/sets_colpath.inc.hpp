@@ -337,16 +337,23 @@ __device__ __forceinline__ Best best_from(double bv, unsigned int bg, double e2)
 // 54 MB of mean / var at 2.4 TB/s).  No list: row s of the slot block's kSlotRowMask holds the bits of its tiles with a safe
 // candidate; a wave keeps the rows' unit counts and their prefix sums in its lanes (lane = tile row) and finds a unit's place with a
 // ballot and three broadcasts.
+// The verdict kernel (k_col_decide) walks HALF-WIDTH units (HALVES = 2): (tile, octet, 64-column half), ONE column per lane, in the
+// order (tile row, octet, tile column, half) -- the two halves of a tile's octet go to consecutive waves, so the runs of adjacent
+// pieces of the same eight rows stay as long as they were.  A lane then holds 8 + 8 doubles of mean / var instead of 16 + 16 and one
+// column's bits, and the unit is one round of the coarse search: a wave of the kernel fits beside the objective's posterior launch
+// (DESIGN 3.2).  Its loads are 512 bytes per row and instruction; measured on config H that cost nothing (the kernel's length is its
+// dependent steps, not its loads).  The minimiser keeps the full-width units (HALVES = 1).
 struct ColUnitMap {
   unsigned int mask;        // lane s: tiles of tile row s with a safe candidate
-  int cnt, pre;             // 8 popc(mask); units of the rows before s
+  int cnt, pre;             // 8 HALVES popc(mask); units of the rows before s
   long long total;
 };
+template <int HALVES>
 __device__ __forceinline__ ColUnitMap col_unit_map(const unsigned long long* __restrict__ slots, int NS) {
   const int lane = threadIdx.x & 63;
   ColUnitMap um;
   um.mask = lane < NS ? (unsigned int)slots[(size_t)kSlotRowMask * kColSlots + lane] : 0u;
-  um.cnt = 8 * __popc(um.mask);
+  um.cnt = 8 * HALVES * __popc(um.mask);
   int inc = um.cnt;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o); if (lane >= o) inc += t; }
@@ -355,18 +362,25 @@ __device__ __forceinline__ ColUnitMap col_unit_map(const unsigned long long* __r
   return um;
 }
 struct ColUnit {
-  int s, c, oct;            // segment, the lane's first column (even), octet of the segment
+  int s, c, oct;            // segment, the lane's first column (full width: even, c + 1 is the lane's too), octet of the segment
   int tile;                 // row-major index of the posterior tile (a row of the classification's partials)
-  size_t w0;                // index of the column word of c (c + 1: the next word)
+  int c0;                   // the unit's first column
+  size_t w0;                // index of the column word of c (full width: c + 1 is the next word)
   size_t g0;                // candidate (first row of the octet, column c)
 };
+// (Everything but `c` and the lane's share of w0 / g0 is the same in all lanes, and the readlane / readfirstlane forms say so to the
+// compiler: the unit's place is worked out on the scalar unit, and a kernel that forms its addresses as "uniform row + lane" loads
+// through a scalar base and a 32-bit lane offset instead of holding a 64-bit address per row.)
+template <int HALVES>
 __device__ __forceinline__ ColUnit col_unit(const ColGeom& gm, const ColUnitMap& um, long long u, int lane) {
   // tile row: the last one whose prefix does not exceed u (rows without units share their successor's prefix: skipped by cnt > 0)
   const unsigned long long at = __ballot(um.cnt > 0 && (long long)um.pre <= u);
   const int s = 63 - __clzll((long long)at);
-  const unsigned int mask = (unsigned int)__shfl((int)um.mask, s);
-  const int pc = __shfl(um.cnt, s) >> 3, local = (int)(u - __shfl(um.pre, s));
-  const int oct = local / pc, t = local - oct * pc;
+  const unsigned int mask = (unsigned int)__builtin_amdgcn_readlane((int)um.mask, s);
+  const int pc = __builtin_amdgcn_readlane(um.cnt, s) >> 3;                           // pc: units of one octet of the row
+  const int local = __builtin_amdgcn_readfirstlane((int)u) - __builtin_amdgcn_readlane(um.pre, s);
+  const int oct = local / pc, rem = local - oct * pc;
+  const int t = HALVES == 2 ? rem >> 1 : rem, half = HALVES == 2 ? rem & 1 : 0;
   // tile column: the t-th set bit of the row's mask
   const unsigned long long hit = __ballot(lane < 32 && ((mask >> lane) & 1u) && __popc(mask & ((1u << lane) - 1u)) == t);
   const int tc = (int)__ffsll((long long)hit) - 1;
@@ -374,7 +388,8 @@ __device__ __forceinline__ ColUnit col_unit(const ColGeom& gm, const ColUnitMap&
   x.oct = oct;
   x.s = s;
   x.tile = s * gm.gxt + tc;
-  x.c = tc * 128 + 2 * lane;
+  x.c0 = tc * 128 + 64 * half;
+  x.c = x.c0 + (HALVES == 2 ? lane : 2 * lane);
   x.w0 = (size_t)x.s * gm.W + x.c;
   x.g0 = ((size_t)(64 * x.s + 8 * x.oct)) * gm.W + x.c;
   return x;
@@ -412,7 +427,7 @@ template <int PART>
 __global__ __launch_bounds__(256) void k_col_min(const ColMinJob j) {
   unsigned long long ukey, vkey;
   col_merge2_body(j.slots, ukey, vkey);
-  const ColUnitMap um = col_unit_map(j.slots, j.gm.NS);
+  const ColUnitMap um = col_unit_map<1>(j.slots, j.gm.NS);
   const long long nunits = um.total;
   double du0 = 0.0;
   if (j.gb) {
@@ -443,7 +458,7 @@ __global__ __launch_bounds__(256) void k_col_min(const ColMinJob j) {
   const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
   uint8_t* Mb = reinterpret_cast<uint8_t*>(j.Mw);
   for (long long u = wave; u < nunits && anyS; u += nwaves) {
-    const ColUnit x = col_unit(gm, um, u, lane);
+    const ColUnit x = col_unit<1>(gm, um, u, lane);
     // (each part loads the words it decides from: S for M, G for G_1 -- a subset of S)
     const u2c_t sw = PART == 0 ? *reinterpret_cast<const u2c_t*>(j.Sw + x.w0) : u2c_t{0ull, 0ull};
     const u2c_t gw = PART == 1 ? *reinterpret_cast<const u2c_t*>(j.Gw + x.w0) : u2c_t{0ull, 0ull};
@@ -596,7 +611,10 @@ __device__ __forceinline__ double col_row_search(const unsigned short* __restric
     gap = gap > 0 ? gap : 0;
     const float x = h1f * (float)bm[e], y = h0f * (float)gap;
     float v = (x * x + y * y) * (1.0f - 1.0e-6f);
-    if (!live || gap > gapmax || bb >= NB) v = 3.0e38f;
+    // (a block that is not to be searched -- beyond the cap, or past the end of the row -- gets +inf, not a large finite number: while
+    // no U point has been found the running minimum is +inf itself, and "bound < minimum" would send the group into blocks past the
+    // row's end, which on rows of fewer than 8 BPL blocks are the NEXT rows of the image: U points that are not there)
+    if (!live || gap > gapmax || bb >= NB) v = __builtin_inff();
     lb[e] = v;
     if (v < lbl) { lbl = v; bl = bb; }
   }
@@ -674,27 +692,32 @@ struct ColVerdict {
   double xscale;
   RcExp rx;
 };
-constexpr int kColQueue = 512;                  // open candidates a WAVE collects in LDS before it takes list slots with one atomic
+// Open candidates a WAVE collects in LDS before it takes list slots with one atomic.  A wave walks one or two half-width units on
+// config H (64 x 8 candidates each) and a unit leaves a few dozen open at most: 128 entries, 8 KB per workgroup (the 512 of the
+// full-width form were 32 KB, which alone kept a second workgroup off a CU that holds two of k_bpost's).  `qcap` (option col_queue,
+// 64 .. kColQueue) is the capacity in use: a wave flushes before an append that could overflow it (qcnt > qcap - 64), so at 64 every
+// append is preceded by a flush -- the test of that path.
+constexpr int kColQueue = 128;
 __global__ __launch_bounds__(256) void k_col_decide(const ColGeom gm, const unsigned long long* __restrict__ Sw, const unsigned long long* __restrict__ slots,
                                                     const unsigned long long* __restrict__ tumin /* per constraint tile: key of the lower end
                                                     of ucb_1 over its safe candidates */, const unsigned long long* __restrict__ tumax /* of the
                                                     upper end (the tile's radius key) */, const unsigned short* __restrict__ cimg, const unsigned short* __restrict__ cbmin,
                                                     double cap_extra, unsigned long long* __restrict__ Usum,
                                                     const unsigned short* __restrict__ img /* the fine column image */, const ColVerdict cv,
-                                                    SweepScalars* sc, unsigned long long* __restrict__ Gw, long long* __restrict__ scanlist) {
+                                                    SweepScalars* sc, unsigned long long* __restrict__ Gw, long long* __restrict__ scanlist, int qcap) {
   __shared__ long long qg[4][kColQueue];
   __shared__ double qu[4][kColQueue];
   const double L = __longlong_as_double((long long)cv.Lkeys[cv.lidx]);
   const bool on_all = sc->count_U > 0 && sc->count_S > 0;
-  const ColUnitMap um = col_unit_map(slots, gm.NS);
+  const ColUnitMap um = col_unit_map<2>(slots, gm.NS);
   const long long nunits = on_all ? um.total : 0;
   const RcBandK bk = rc_band(cv.rx, sc);
   const double eps_abs = 1.01e-8 * sqrt(2.0) + 1e-14 * cv.xscale + 1e-13;
   const double delta = gm.delta;
   const double b = cv.b;
   const float bfp = (float)b;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const long long wave = (long long)blockIdx.x * 4 + wv, nwaves = (long long)gridDim.x * 4;
   uint8_t* Gb = reinterpret_cast<uint8_t*>(Gw);
   // (Usum cleared for the next sweep's posterior: its readers ran in the launch before)
   for (int i = (int)blockIdx.x * 256 + threadIdx.x; i < gm.W; i += (int)gridDim.x * 256) Usum[i] = 0ull;
@@ -718,31 +741,30 @@ __global__ __launch_bounds__(256) void k_col_decide(const ColGeom gm, const unsi
     qcnt = 0;
   };
   for (long long u = wave; u < nunits; u += nwaves) {
-    const ColUnit x = col_unit(gm, um, u, lane);
-    const u2c_t sw = *reinterpret_cast<const u2c_t*>(Sw + x.w0);
-    const unsigned int sb[2] = {(unsigned int)(sw[0] >> (8 * x.oct)) & 0xffu, (unsigned int)(sw[1] >> (8 * x.oct)) & 0xffu};
-    unsigned int gbits[2] = {0u, 0u};
-    const unsigned int any8 = sb[0] | sb[1];
-    if (__ballot(any8 != 0u) != 0ull) {
+    const ColUnit x = col_unit<2>(gm, um, u, lane);
+    // (the unit's words, bytes and rows from bases that are the same in all lanes, the lane as a 32-bit offset)
+    const size_t wu = (size_t)x.s * gm.W + x.c0;
+    uint8_t* Gu = Gb + 8 * wu + x.oct;
+    const unsigned int sb = (unsigned int)((Sw + wu)[lane] >> (8 * x.oct)) & 0xffu;
+    unsigned int gbits = 0u;
+    if (__ballot(sb != 0u) != 0ull) {
       const int row0 = 64 * x.s + 8 * x.oct;
-      // The coarse distances of the unit's sixteen cells (the octet is one coarse row, the lane's two columns lie in cell lane >> 2):
-      // eight lanes search a cell, two rounds; a lane then picks up its own cell's value.
+      // The coarse distances of the unit's eight cells (the octet is one coarse row, the lane's column lies in cell lane >> 3): eight
+      // lanes search a cell, one round, and the cell a lane has searched is its own (the search leaves its minimum in all eight).
       double dc2;
       {
-        const int cj = row0 >> 3, ci0 = (x.c - 2 * lane) >> 3, l8 = lane & 7, sub = lane >> 3;
+        const int cj = row0 >> 3, ci0 = x.c0 >> 3, l8 = lane & 7, sub = lane >> 3;
         const unsigned short* rowi = cimg + (size_t)cj * gm.CWp;
         const unsigned short* rowb = cbmin + (size_t)cj * gm.CNBp;
-        const double d0 = col_row_search<2>(rowi, rowb, gm.CNB, ci0 + sub, h0c, h1c, inv_h0c, capC, -1.0, true, l8, sub);
-        const double d1 = col_row_search<2>(rowi, rowb, gm.CNB, ci0 + 8 + sub, h0c, h1c, inv_h0c, capC, -1.0, true, l8, sub);
-        const int m = lane >> 2;
-        const double v0 = __shfl(d0, 8 * (m & 7)), v1 = __shfl(d1, 8 * (m & 7));
-        dc2 = (m >> 3) ? v1 : v0;
+        dc2 = col_row_search<2>(rowi, rowb, gm.CNB, ci0 + sub, h0c, h1c, inv_h0c, capC, -1.0, true, l8, sub);
       }
       // The whole unit at once where that settles it: ucb_1 of every safe candidate of the tile lies in [ulo, uhi] (the posterior's
-      // epilogue kept both ends), the coarse distances of the unit's sixteen cells in [dmin, dmax] -- if the candidate with the
+      // epilogue kept both ends), the coarse distances of the unit's eight cells in [dmin, dmax] -- if the candidate with the
       // SMALLEST bound at the LARGEST distance is within its radius for sure, all are (G = S on the unit, no candidate is read), and
       // likewise none is when the largest bound at the smallest distance is beyond it.  Only the units the boundary of G_1 crosses
-      // read mean / var (a third of the 515 tiles with a safe candidate on config H).
+      // read mean / var (a third of the 515 tiles with a safe candidate on config H).  (A half-width unit's own cells: an interval
+      // inside the one the tile's sixteen cells gave, so it settles every unit that one settled; and a unit it settles holds no
+      // candidate the tests below would have left open -- they use the candidate's own bound and cell, which lie inside both.)
       if (L > 0) {
         double dmx = dc2, dmn = dc2;
 #pragma unroll
@@ -760,24 +782,22 @@ __global__ __launch_bounds__(256) void k_col_decide(const ColGeom gm, const unsi
           const double dhi = dCx * (1.0 + 1e-9) + delta, dlo = fmax(0.0, dCn * (1.0 - 1e-9) - delta);
           const double tolu = 1e-12 * (amax + du + L * dhi);
           if (ulo - du - L * (dhi + eps_abs + 1e-11 * dhi) > tolu) {             // every safe candidate of the unit is in G_1
-            Gb[8 * x.w0 + x.oct] = (uint8_t)sb[0];
-            Gb[8 * (x.w0 + 1) + x.oct] = (uint8_t)sb[1];
+            Gu[8 * lane] = (uint8_t)sb;
             continue;
           }
           if (uhi + du - L * (dlo - eps_abs - 1e-11 * dlo) < -tolu) {           // none is
-            Gb[8 * x.w0 + x.oct] = 0;
-            Gb[8 * (x.w0 + 1) + x.oct] = 0;
+            Gu[8 * lane] = 0;
             continue;
           }
         }
       }
-      d2c_t mu[8], va[8];
+      double mu[8], va[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        const bool on = (any8 >> k) & 1u;
-        const size_t g = x.g0 + (size_t)k * gm.W;
-        mu[k] = on ? *reinterpret_cast<const d2c_t*>(cv.mean_c + g) : d2c_t{0.0, 0.0};
-        va[k] = on ? *reinterpret_cast<const d2c_t*>(cv.var_c + g) : d2c_t{0.0, 0.0};
+        const bool on = (sb >> k) & 1u;
+        const size_t gr = (size_t)(row0 + k) * gm.W + x.c0;
+        mu[k] = on ? (cv.mean_c + gr)[lane] : 0.0;
+        va[k] = on ? (cv.var_c + gr)[lane] : 0.0;
       }
       const double dC = sqrt(dc2);
       const double dhi = dC * (1.0 + 1e-9) + delta, dlo = fmax(0.0, dC * (1.0 - 1e-9) - delta);
@@ -788,32 +808,30 @@ __global__ __launch_bounds__(256) void k_col_decide(const ColGeom gm, const unsi
       // settle (`und`) takes the fp64 path below: the coarse sandwich on the exact bound, as k_edt_decide8.
       const float Lhi_f = __double2float_ru(Lhi), Llo_f = __double2float_rd(Llo);
       const float du_f = cv.rx.gb_c > 0 ? __double2float_ru(bk.du) : 0.0f, rl_f = cv.rx.gb_c > 0 ? __double2float_ru(bk.rl) : 0.0f;
-      unsigned int und[2] = {0u, 0u};
+      unsigned int und = 0u;
       if (L > 0) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            const bool on = (sb[e] >> k) & 1u;
-            const F32Bound fb = f32_bound(mu[k][e], va[k][e], bfp);
-            const float dumax = fmaf(rl_f, fb.amax, du_f) * 1.000001f;
-            const float tol = 1.0e-6f * (fb.amax + dumax + Lhi_f);
-            const bool in = fb.ok && (fb.u - fb.del - dumax - Lhi_f) > tol, out = fb.ok && (fb.u + fb.del + dumax - Llo_f) < -tol;
-            gbits[e] |= (on && in) ? (1u << k) : 0u;
-            und[e] |= (on && !in && !out) ? (1u << k) : 0u;
-          }
+          const bool on = (sb >> k) & 1u;
+          const F32Bound fb = f32_bound(mu[k], va[k], bfp);
+          const float dumax = fmaf(rl_f, fb.amax, du_f) * 1.000001f;
+          const float tol = 1.0e-6f * (fb.amax + dumax + Lhi_f);
+          const bool in = fb.ok && (fb.u - fb.del - dumax - Lhi_f) > tol, out = fb.ok && (fb.u + fb.del + dumax - Llo_f) < -tol;
+          gbits |= (on && in) ? (1u << k) : 0u;
+          und |= (on && !in && !out) ? (1u << k) : 0u;
         }
       } else {
-        und[0] = sb[0];
-        und[1] = sb[1];
+        und = sb;
       }
-      while (__ballot((und[0] | und[1]) != 0u) != 0ull) {
-        const bool act = (und[0] | und[1]) != 0u;
-        const int e = und[0] ? 0 : 1;
-        const int k = act ? (int)(__ffs((int)und[e]) - 1) : 0;
-        if (act) und[e] &= und[e] - 1u;
-        const long long g = (long long)(x.g0 + (size_t)k * gm.W + e);
-        const double m = act ? cv.mean_c[g] : 0.0, v = act ? cv.var_c[g] : 0.0;     // (second read of a value this wave has just loaded)
+      // Row by row, the lanes with an open candidate in that row: mean / var come out of the registers of the batch above (a second
+      // load per step -- each lane its own next row -- put a memory round trip into every one of up to eight dependent steps, and
+      // those steps were the length of the kernel: DESIGN 6).
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const bool act = (und >> k) & 1u;
+        if (__ballot(act) == 0ull) continue;
+        const long long g = (long long)(x.g0 + (size_t)k * gm.W);
+        const double m = mu[k], v = va[k];
         bool open = false, in = false;
         double ucb = 0.0;
         if (act) {
@@ -837,21 +855,20 @@ __global__ __launch_bounds__(256) void k_col_decide(const ColGeom gm, const unsi
             }
           }
         }
-        gbits[e] |= in ? (1u << k) : 0u;
+        gbits |= in ? (1u << k) : 0u;
         const unsigned long long om = __ballot(open);
         if (om) {
-          if (qcnt > kColQueue - 64) flush();
+          if (qcnt > qcap - 64) flush();
           if (open) {
             const int slot = qcnt + __popcll(om & ((1ull << lane) - 1ull));
-            qg[wv][slot] = ((long long)(row0 + k) << 32) | (long long)(x.c + e);          // (row, column): the list kernel needs no division
+            qg[wv][slot] = ((long long)(row0 + k) << 32) | (long long)x.c;                // (row, column): the list kernel needs no division
             qu[wv][slot] = ucb;
           }
           qcnt += __popcll(om);
         }
       }
     }
-    Gb[8 * x.w0 + x.oct] = (uint8_t)gbits[0];
-    Gb[8 * (x.w0 + 1) + x.oct] = (uint8_t)gbits[1];
+    Gu[8 * lane] = (uint8_t)gbits;
   }
   flush();
 }
@@ -1024,6 +1041,10 @@ static void col_expand(sbo_ctx* c, const DevBuf& words, uint8_t* out) {
 // merged by every workgroup of k_col_min<0>, M and its arg-max, beside the chain's verdict kernels; the main stream then waits for the
 // chain's join event, k_col_min<1> takes the arg-max over the finished G_1 and k_col_finals merges both.  What the set phase adds to
 // K1 is the join, the G part and the finals.
+int col_decide_resident(int* wg_per_cu) {
+  SBO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(wg_per_cu, k_col_decide, 256, 0));
+  return SBO_OK;
+}
 static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, const PostOutcome& post, SweepScalars& h, unsigned long long* Lk) {
   const long long n = c->cs.n_local;
   const int q = c->mc.q;                 // == 2
@@ -1138,12 +1159,16 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   rx_band<double>(c, v, 1, lidx, cv.rx);
   // (the verdict kernels do not read var_0 -- overlapped, the objective's launch may still be writing it: the arg-max over G_1 is the
   // job of k_col_min<1>, behind the join)
-  // (grids sized to be resident at once: the waves loop over the units of the tiles with a safe candidate)
-  const int ndw = std::max(1, c->n_cu * 4);
+  // (the grid is sized to be resident at once -- decide_wg_per_cu is what the runtime's occupancy query reports for k_col_decide's
+  // registers and LDS on an otherwise empty CU (col_decide_resident, asked once at sbo_init) -- and the waves loop over the half-width
+  // units of the tiles with a safe candidate; no more workgroups than would give every wave a unit if every tile had one)
+  const long long units_max = 16ll * gm.NS * gm.gxt;
+  const int ndw = (int)std::max<long long>(1, std::min<long long>((long long)c->n_cu * std::max(1, c->decide_wg_per_cu), (units_max + 3) / 4));
+  const int qcap = std::min(kColQueue, std::max(64, c->opt.col_queue));
   const unsigned long long* rows = (const unsigned long long*)c->cpart.p;        // the posterior's partial rows: constraint tiles, then objective tiles
   hipLaunchKernelGGL(k_col_decide, dim3((unsigned)ndw), dim3(256), 0, es, gm, (const unsigned long long*)cb.Sw, (const unsigned long long*)cb.slots,
                      rows, rows + (size_t)(kRowRmax + 1) * c->cpart_cap, (const unsigned short*)c->col.cimg.p, (const unsigned short*)c->col.cbmin.p,
-                     2.0 * gm.delta + 2.0 * kCoarse * hmax, cb.Usum, (const unsigned short*)c->col.img.p, cv, sc, (unsigned long long*)c->col.G.p, (long long*)ln.scanlist.p);
+                     2.0 * gm.delta + 2.0 * kCoarse * hmax, cb.Usum, (const unsigned short*)c->col.img.p, cv, sc, (unsigned long long*)c->col.G.p, (long long*)ln.scanlist.p, qcap);
   hipLaunchKernelGGL(k_col_scan, dim3((unsigned)nsc), dim3(256), 0, es, gm, (const unsigned short*)c->col.img.p, (const unsigned short*)c->col.bmin.p,
                      cv, sc, (unsigned long long*)c->col.G.p, (long long*)ln.amb.p, (const long long*)ln.scanlist.p);
   ln.amb_clean = false;
