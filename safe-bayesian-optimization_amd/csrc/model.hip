@@ -8,8 +8,8 @@
 //                invK: reverse both index orders, factor J invK J = U~^T U~ (U~ upper), M = J U~ J.
 //   invK absent: K from the expanded distance (models/GP_Safe.py:119), K = U^T U, M = L^-1 = U^-T by row-wise
 //                substitution, alpha = M^T (M rhs).
-// The factor is then packed into the matrix-core fragment images every K1 kernel reads (Fpk).  Small models (n < 256)
-// run in one workgroup per output; larger ones use the blocked multi-workgroup form below (n = 512: 1.4 ms, n = 2048:
+// The factor is then packed into the matrix-core fragment images every K1 kernel reads (Fpk).  Small models (n < kBlockedFrom =
+// 96) run in one workgroup per output; from there on the blocked multi-workgroup form below is used (n = 512: 1.4 ms, n = 2048:
 // 9 ms per model, against ~95 ms / seconds of host Cholesky).
 #include <cmath>
 #include <cstring>
