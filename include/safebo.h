@@ -87,7 +87,11 @@ typedef struct sbo_sweep_opts {
                                       models/SafeOpt.py:47-66); 2: it need not even evaluate them there (the result is the same), nor
                                       the constraint on the posterior tiles whose enclosure (per plan, from its first full evaluation)
                                       proves every candidate unsafe at this b and outside the guard band (sbo_profile.k1_tiles_skipped;
-                                      one-constraint column path, from the plan's second sweep on).  A lean
+                                      one-constraint column path, from the plan's second sweep on), nor -- option "k1_skip_safe" -- on
+                                      the tiles it proves safe throughout (k1_tiles_skipped_safe): there the set phase reads what the
+                                      plan's first full evaluation stored, so any other writer of the resident posterior (another
+                                      posterior kernel, sbo_posterior_run, a model / grid / option change) makes the next sweep of the
+                                      plan evaluate and record everything again.  A lean
                                       SafeOpt sweep of a model with constraints reports L[0] = 0: the objective's Lipschitz key is read by
                                       no sweep of the reference (its expanders use the constraints' keys, models/SafeOpt.py:110,
                                       models/GoOSE.py:100), and the interpolating posteriors then leave its gradient fields out.
@@ -217,8 +221,12 @@ typedef struct sbo_profile {
   /* r06: posterior tiles (64 x 128 candidates) of the constraint that the last sweep left unevaluated -- a lean 2 sweep on the column
    * path (set_path 1) whose plan's per-cell enclosures of mean / var prove every candidate of the tile unsafe and outside the band.  */
   int64_t k1_tiles_skipped;
-  /* of guard_audit_samples: samples on such tiles, where the audit checks the reference values against the tile's enclosure (widened
-   * by the band) instead of the stored ones.  Cumulative, as guard_audit_samples.                                                    */
+  /* ... and those it left unevaluated because the enclosures prove every candidate of the tile SAFE and outside the band (option
+   * "k1_skip_safe"): every S bit, no U bit, the stored mean / var of the plan's recording sweep stand for the tile's values.          */
+  int64_t k1_tiles_skipped_safe;
+  /* of guard_audit_samples: samples on tiles of either kind, where the audit checks the reference values against the tile's enclosure
+   * (widened by the band) instead of the stored ones -- on a proved-safe tile also the stored values, which must lie inside the
+   * enclosure bit for bit.  Cumulative, as guard_audit_samples.                                                                      */
   int64_t guard_audit_skipped;
   /* Spatial index of an explicit list (option "list_index"; zero when the last sweep did not use it): device time of building its
    * sorted order (Morton keys, radix sort, sorted copy of the points) when the last sweep built it, 0 when it reused it; the
@@ -612,6 +620,8 @@ int sbo_profile_get(sbo_ctx* ctx, sbo_profile* out);
  *                      launches -- behind the gate on large grids, on every tile without a gate on small ones; 2: always without, 3: always with
  *   "k1_sched"         1: lean-2 sweeps on that path launch the constraint's and the objective's GEMM posterior over lists of the tiles they
  *                      evaluate, built per sweep (tiles left out are written by the lists' kernels); 0: one workgroup per tile (A/B checker)
+ *   "k1_skip_safe"     1: lean-2 sweeps on that path also leave unevaluated the constraint tiles the plan's enclosures prove safe at this
+ *                      sweep's b (sbo_profile.k1_tiles_skipped_safe); 0: only the tiles proved unsafe (A/B checker)
  *   "col_overlap"      1: on that path the expander chain (distance transform, verdicts) runs on a second stream beside the objective's
  *                      posterior launch and the M part of the minimiser; 0: every kernel on the main stream
  *   "set_fuse"         1: 2-D grids of one rank share launches between independent set-phase kernels; 0: one launch per kernel

@@ -287,6 +287,7 @@ const OptRow kOptions[] = {
     OPT_RANGE(guard_audit_every, 1, 1 << 20, "guard_audit_every: 1 .. 1048576 sweeps", kOptNothing, hook_audit_every),
     OPT_RANGE(grad_defer, 0, 3, "grad_defer must be 0 .. 3", kOptInterp, nullptr),
     OPT_BOOL(k1_sched, kOptNothing, nullptr),
+    OPT_BOOL(k1_skip_safe, kOptNothing, nullptr),       // (read per sweep: the decision is taken at every sweep's b and band)
     OPT_BOOL(col_overlap, kOptNothing, nullptr),
     OPT_RANGE(col_queue, 64, 128, "col_queue must be within 64 .. 128 (the default)", kOptNothing, nullptr),
     OPT_BOOL(scan_blocks, kOptNothing, nullptr),
@@ -598,8 +599,10 @@ static int alloc_workspace(sbo_ctx* c) {
   const size_t es = c->dtype == SBO_F64 ? 8 : 4;
   const size_t n = (size_t)std::max<long long>(c->cs.n_local, 1);
   int rc;
+  const void *had_m = c->mean.p, *had_v = c->var.p;
   if ((rc = ensure(c->mean, es * n * c->mc.q))) return rc;
   if ((rc = ensure(c->var, es * n * c->mc.q))) return rc;
+  if (c->mean.p != had_m || c->var.p != had_v) post_regions_written(c);     // (new buffers hold nothing of the plan's)
   return SBO_OK;
 }
 

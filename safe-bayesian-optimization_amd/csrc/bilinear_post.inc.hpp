@@ -158,6 +158,52 @@ __device__ __forceinline__ bool encl_unsafe(double mlo, double mhi, double vlo, 
   const bool pdom = mhi < 0.0 && (Pmin - Qh) - mg * (Pmin + Qh) > rhs * (1.0 + mg);
   return qdom || pdom;
 }
+// The mirror of encl_unsafe: does post_classify_row leave EVERY (m, v) of the box with ge = 1, le = 0, outside the undecided branch and
+// -- with a band in force -- outside the band test?  Then every candidate of a tile whose cells all pass is in S and none in U, at this
+// sweep's b and band, whatever the tile's values are inside their enclosures.  The predicate is the epilogue's arithmetic at the corner
+// (m_lo, v_hi): m > 0 throughout, so m * m is increasing in m and bb * v in v under rounding to nearest, and so are their products
+// with c.  For a point of the box P = m * m lies in [Pl, Ph] and Q = bb * v in [0, Qh]: `ok` holds (bconf >= 0, v >= v_lo >= 0), `neg`
+// does not (m >= m_lo > 0), `rng` holds (P <= Ph < huge, Q <= Qh < huge), P >= Pl > tiny, and P >= Pl >= Qh * c >= Q * c: ge = 1.  le is
+// then false (neg is, and its other branch asks for !ge), so the point is not undecided either.  The band test counts a point unless
+// |P - Q| > fma(|m|, c1, c0): here P - Q >= Pl - Qh and the right side is at most its value at m_hi, tested with the same relative
+// margin of 2^-40 on the operands as encl_unsafe.  NaN anywhere: not decided.
+__device__ __forceinline__ bool encl_safe(double mlo, double mhi, double vlo, double vhi, double bconf, double bb, bool gb_on, const LcbBand& lb) {
+  constexpr double c = 1.0 + 0x1p-48, tiny = 1e-250, huge = 1e300, mg = 0x1p-40;
+  if (!(bconf >= 0.0 && vlo >= 0.0 && vlo <= vhi && mlo <= mhi && mlo > 0.0)) return false;          // (NaN: false)
+  const double Pl = mlo * mlo, Ph = mhi * mhi, Qh = bb * vhi;
+  if (!(Ph < huge && Qh < huge && Pl > tiny && Pl >= Qh * c)) return false;
+  if (!gb_on) return true;
+  const double rhs = fma(mhi, lb.c1, lb.c0);
+  if (!(mhi < 1e150 && rhs < huge)) return false;
+  return (Pl - Qh) - mg * (Pl + Qh) > rhs * (1.0 + mg);
+}
+// What a proved-safe tile hands the set phase in place of its candidates' own values, from one cell's enclosure (min / max over the
+// tile's 128 cells by the caller).  vlo: the cell's smallest stored variance -- S is the whole tile and the enclosure holds the minimum
+// of the stored values, so the variance key is EXACT.  up / lo: bounds of ucb_1 = fl(m + fl(b fl(sqrt v))) over the cell, by the
+// arithmetic post_classify_row bounds a candidate's with (one single-precision root, 2^-20 slack, widened by 2^-50): every step of
+// ucb_1 is monotone in m and v, so its values on the cell lie between those at (m_lo, v_lo) and (m_hi, v_hi).
+// The radius key is therefore an UPPER BOUND of max ucb_1 over the tile, not the maximum itself.  Its readers on the column path, each of
+// which takes it as a cap or an interval end and nothing else:
+//   * k_col_decide, capC = rmax / L (+ slack): distances beyond it are "beyond every radius"; a larger cap examines more entries and
+//     declares fewer cells beyond, never a cell within a true radius beyond;
+//   * k_col_decide, the whole-unit tests on [tumin, tumax] (fields 0 and kFuseRmax + 1 of the tile's partial row): a wider interval
+//     settles fewer units wholesale, the rest take the per-candidate path on their own values and reach the same verdicts;
+//   * the late exhaustive recheck (launch_exact_d -> edt_scan_body and the goose / expander kernels' rmax / L): the same cap;
+//   * the host: halo_learn / halo_for (sets.hip), multi-rank only -- the column path runs on one rank --, again rmax / L as a halo width.
+// Nobody compares it for equality, reports it, or takes an arg-max from it.
+struct EnclKeys { double vlo, up, lo; };
+__device__ __forceinline__ EnclKeys encl_keys(double mlo, double mhi, double vlo, double vhi, double bconf) {
+  const float sfh = __builtin_amdgcn_sqrtf((float)vhi), sfl = __builtin_amdgcn_sqrtf((float)vlo);
+  const double s_up = (double)sfh * (1.0 + 0x1p-20) + 1e-18;
+  double s_lo = (double)sfl * (1.0 - 0x1p-20) - 1e-18;
+  s_lo = s_lo > 0.0 ? s_lo : 0.0;
+  const double xu = mhi + bconf * s_up, xl = mlo + bconf * (sfl < 3.0e38f ? s_lo : 0.0);
+  EnclKeys k;
+  k.vlo = vlo;
+  k.up = sfh < 3.0e38f ? xu + (xu < 0 ? -xu : xu) * 0x1p-50 : 1e300;
+  k.lo = xl - (xl < 0 ? -xl : xl) * 0x1p-50;
+  return k;
+}
 // role 2: a safe candidate of the objective -- u* = min over S of ucb_0 (models/SafeOpt.py:47-51), the exact bound only when the
 // cheap lower bound could beat the thread's running minimum (as k_classify's objective pass), and the smallest var_0 over S
 __device__ __forceinline__ void post_objective(PostCtx& cx, bool set, double m, double v) {
@@ -579,6 +625,10 @@ __device__ __forceinline__ void wg_trace_row(int o, unsigned long long t0, unsig
 // changes their operands, k-steps or k-order between sweeps of one plan (a per-sweep truncation, another tile shape, a different
 // accumulation order) must clear BilinearPlan::encl_ready.  The standing audit checks it where it samples an evaluated tile: the stored
 // values must lie inside the recorded enclosure bit for bit (guard.hip: k_audit_compare).
+// SECOND INVARIANT (k1_skip_safe): a tile proved safe is not evaluated, and the set phase reads its STORED mean / var -- so the
+// constraint's regions of sbo_ctx::mean / var must hold the plan's bits on every tile, not only be enclosed by what was recorded.  Who
+// may write them, and who drops the flags: BilinearPlan::encl_ready / vals_ready (internal.hpp).  The audit checks a sample on such a
+// tile both ways.
 __global__ __launch_bounds__(128) void k_bl_enclose(const double* __restrict__ mean, const double* __restrict__ var, long long cnt0,
                                                     double* __restrict__ encl) {
   const int cell = threadIdx.x, cr = cell >> 4, cc = cell & 15;
@@ -611,6 +661,12 @@ __global__ __launch_bounds__(128) void k_bl_enclose(const double* __restrict__ m
 // Lipschitz row, its partial row of the classification (|U| = 8192, no keys) and its scalars in the slot block (|U|, the Lipschitz
 // key, the skip count).  1 = evaluated with gradient phases, 2 = skipped but runs gradient phases, 3 = evaluated: these go into the
 // list.  The skip byte of every tile for the audit (guard.hip).
+// Option k1_skip_safe adds the mirror image: a tile whose every cell encl_safe proves SAFE at this b and band.  Class 4 = proved safe, no
+// gradient phase: no workgroup; written here is what its workgroup wrote -- S = all ones and U = 0 words, no bit of Usum, its bit of
+// the tile row's mask, its Lipschitz row, its partial row (|S| = 8192, the keys of encl_keys) and its scalars (|S|, the variance,
+// radius and Lipschitz keys, the count of such tiles).  Class 5 = proved safe but runs gradient phases: listed at the front like
+// class 2, bit 30 of its entry set.  The tile's mean / var stay what the plan's recording launch stored, and the set phase READS them
+// (k_col_decide, on the units it cannot settle wholesale): BilinearPlan::encl_ready says who may write those regions.
 //
 // The list has two ends: classes 1 and 2 -- the tiles with gradient phases, the longest -- fill the front upwards, class 3 fills the
 // back downwards, each end behind a counter bumped by one atomic per listed tile; bit 31 of an entry marks class 2.  One pair of
@@ -636,23 +692,33 @@ __global__ __launch_bounds__(64 * kSchedWaves) void k_bl_sched_tiles1(const Mode
                                                          uint8_t* __restrict__ skip, unsigned int* __restrict__ list, int cap, unsigned long long* __restrict__ Sw,
                                                          unsigned long long* __restrict__ Uw, unsigned long long* __restrict__ Usum,
                                                          unsigned long long* __restrict__ slots, double* __restrict__ Lpart,
-                                                         unsigned long long* __restrict__ cpart, int pcap) {
-  __shared__ unsigned long long sh_key[kSchedWaves];      // per wave: the Lipschitz key of a class-0 tile (0: none)
-  __shared__ unsigned int sh_cnt[kSchedWaves];            // ... bit 0: a class-0 tile, bit 1: a skipped tile (class 0 or 2)
+                                                         unsigned long long* __restrict__ cpart, int pcap, int skip_safe /* option k1_skip_safe */) {
+  __shared__ unsigned long long sh_key[kSchedWaves];     // per wave: the Lipschitz key of a class-0 / class-4 tile (0: none)
+  __shared__ unsigned int sh_cnt[kSchedWaves];            // ... bit 0: a class-0 tile, bit 1: a tile proved unsafe (class 0 or 2), bit 2: a class-4 tile, bit 3: a tile proved safe (class 4 or 5)
+  __shared__ unsigned long long sh_vmin[kSchedWaves], sh_rmax[kSchedWaves];   // ... a class-4 tile's variance / radius key (~0 / 0: none)
   const int lane = threadIdx.x & 63, wave = (int)(threadIdx.x >> 6), tile = (int)blockIdx.x * kSchedWaves + wave;
-  unsigned long long my_key = 0ull;
+  unsigned long long my_key = 0ull, my_vmin = ~0ull, my_rmax = 0ull;
   unsigned int my_cnt = 0u;
   if (tile < ntiles) {                                    // (a whole wave or none of it)
     const double bb = bconf * bconf;
     const bool gb_on = gb != nullptr;
     const LcbBand lb = gb_on ? lcb_band(bb, gb->dm[1], gb->dv[1]) : LcbBand{0.0, 0.0};
-    bool ok = true;
+    bool ok = true, oks = skip_safe != 0;
+    double kv = 1e300, ku = -1.0, kl = 1e300;             // (the tile's keys, should it be proved safe: encl_keys)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const double4 e = reinterpret_cast<const double4*>(encl)[(size_t)tile * 128 + h * 64 + lane];
       ok = ok && encl_unsafe(e.x, e.y, e.z, e.w, bconf, bb, gb_on, lb);
+      oks = oks && encl_safe(e.x, e.y, e.z, e.w, bconf, bb, gb_on, lb);
+      if (oks) {
+        const EnclKeys ek = encl_keys(e.x, e.y, e.z, e.w, bconf);
+        kv = ek.vlo < kv ? ek.vlo : kv;
+        ku = ek.up > ku ? ek.up : ku;
+        kl = ek.lo < kl ? ek.lo : kl;
+      }
     }
     const bool dec = __ballot(!ok) == 0ull;
+    const bool sdec = !dec && __ballot(!oks) == 0ull;       // (proved safe: classes 4 / 5)
     // (k_bpost's gate, output 1, and the largest coarse sample it folds in)
     bool run2 = true, run3 = true;
     double gfold = 0.0;
@@ -668,16 +734,51 @@ __global__ __launch_bounds__(64 * kSchedWaves) void k_bl_sched_tiles1(const Mode
       gfold = fmax(fabs(cg0 * t0), fabs(cg1 * t1));
     }
     const bool grad = run2 || run3;
-    const unsigned int k = dec ? (grad ? 2u : 0u) : (grad ? 1u : 3u);
-    if (lane == 0) skip[tile] = dec ? 1 : 0;
-    my_cnt = k == 0u ? 3u : (k == 2u ? 2u : 0u);
-    if (k != 0u) {
+    // (4 = proved safe, no gradient phase: no workgroup, written below; 5 = proved safe but runs gradient phases: listed like class 2)
+    const unsigned int k = dec ? (grad ? 2u : 0u) : (sdec ? (grad ? 5u : 4u) : (grad ? 1u : 3u));
+    if (lane == 0) skip[tile] = dec ? kSkipUnsafe : (sdec ? kSkipSafe : 0);
+    my_cnt = k == 0u ? 3u : (k == 2u ? 2u : (k == 4u ? 12u : (k == 5u ? 8u : 0u)));
+    if (k != 0u && k != 4u) {
       if (lane == 0) {
         // (p < cap whenever the counters started from zero; the test keeps a store inside the shard whatever they held)
         const unsigned int sh = ((unsigned int)tile + 3u * ((unsigned int)tile >> kTlistShift)) & (kTlistShards - 1);
         const unsigned int p = atomicAdd(&list[sh * kTlistHead + (k == 3u ? 1 : 0)], 1u);
         if (p < (unsigned int)cap)
-          list[kTlistShards * kTlistHead + sh * cap + (k == 3u ? (unsigned int)(cap - 1) - p : p)] = (unsigned int)tile | (k == 2u ? 0x80000000u : 0u);
+          list[kTlistShards * kTlistHead + sh * cap + (k == 3u ? (unsigned int)(cap - 1) - p : p)] =
+              (unsigned int)tile | (k == 2u ? kTlistUnsafe : (k == 5u ? kTlistSafe : 0u));
+      }
+    } else if (k == 4u) {
+      // what the tile's workgroup wrote (k_bpost, csafe): every S bit, no U bit -- so no bit of Usum --, its Lipschitz row, its partial
+      // row (|S| = 8192, the lower end of ucb_1, the variance and radius keys of encl_keys) and, below, its scalars in the slot block
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(kv, off), ou = __shfl_xor(ku, off), ol = __shfl_xor(kl, off);
+        kv = ov < kv ? ov : kv;
+        ku = ou > ku ? ou : ku;
+        kl = ol < kl ? ol : kl;
+      }
+      const int bx = tile % tgx, by = tile / tgx;
+      const size_t w0 = (size_t)by * cnt0 + (size_t)bx * 128;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        Sw[w0 + h * 64 + lane] = ~0ull;
+        Uw[w0 + h * 64 + lane] = 0ull;
+      }
+      const double lrow = fmax(0.0, gfold);
+      my_key = (unsigned long long)__double_as_longlong(lrow);
+      my_vmin = kv < 1e300 ? ord_key(kv) : ~0ull;
+      my_rmax = ku >= 0.0 ? ord_key(ku) : 0ull;
+      if (lane == 0) {
+        Lpart[((size_t)tgy + by) * tgx + bx] = lrow;
+        atomicOr(&slots[(size_t)kSlotRowMask * kColSlots + by], 1ull << bx);      // (no return value)
+      }
+      if (lane < kFuseRow) {                                // (post_partials' row, fuse && slots)
+        unsigned long long v = 0ull;
+        if (lane == 0) v = kl < 1e300 ? ord_key(kl) : ~0ull;
+        else if (lane == 1) v = 64ull * 128ull;
+        else if (lane >= kFuseVmin && lane < kFuseRmax) v = lane == kFuseVmin + 1 ? my_vmin : ~0ull;
+        else if (lane == kFuseRmax + 1) v = my_rmax;
+        cpart[(size_t)lane * pcap + tile] = v;
       }
     } else {
       const int bx = tile % tgx, by = tile / tgx;
@@ -701,20 +802,28 @@ __global__ __launch_bounds__(64 * kSchedWaves) void k_bl_sched_tiles1(const Mode
       }
     }
   }
-  if (lane == 0) { sh_key[wave] = my_key; sh_cnt[wave] = my_cnt; }
+  if (lane == 0) { sh_key[wave] = my_key; sh_cnt[wave] = my_cnt; sh_vmin[wave] = my_vmin; sh_rmax[wave] = my_rmax; }
   __syncthreads();
-  if (threadIdx.x < 3) {
-    unsigned long long key = 0ull, n0 = 0ull, nskip = 0ull;
+  if (threadIdx.x < 7) {
+    unsigned long long key = 0ull, n0 = 0ull, nskip = 0ull, n4 = 0ull, nsafe = 0ull, vmin = ~0ull, rmax = 0ull;
 #pragma unroll
     for (int w = 0; w < kSchedWaves; ++w) {
       key = sh_key[w] > key ? sh_key[w] : key;
       n0 += sh_cnt[w] & 1u;
-      nskip += sh_cnt[w] >> 1;
+      nskip += (sh_cnt[w] >> 1) & 1u;
+      n4 += (sh_cnt[w] >> 2) & 1u;
+      nsafe += (sh_cnt[w] >> 3) & 1u;
+      vmin = sh_vmin[w] < vmin ? sh_vmin[w] : vmin;
+      rmax = sh_rmax[w] > rmax ? sh_rmax[w] : rmax;
     }
     const int slot = (int)(blockIdx.x & (kColSlots - 1));
     if (threadIdx.x == 0 && n0) atomicAdd(&slots[(size_t)kSlotU * kColSlots + slot], 64ull * 128ull * n0);
-    if (threadIdx.x == 1 && n0) atomicMax(&slots[(size_t)kSlotL1 * kColSlots + slot], key);
+    if (threadIdx.x == 1 && (n0 || n4)) atomicMax(&slots[(size_t)kSlotL1 * kColSlots + slot], key);
     if (threadIdx.x == 2 && nskip) atomicAdd(&slots[(size_t)kSlotSkip * kColSlots + slot], nskip);
+    if (threadIdx.x == 3 && n4) atomicAdd(&slots[(size_t)kSlotS * kColSlots + slot], 64ull * 128ull * n4);
+    if (threadIdx.x == 4 && nsafe) atomicAdd(&slots[(size_t)kSlotSkipSafe * kColSlots + slot], nsafe);
+    if (threadIdx.x == 5 && vmin != ~0ull) atomicMin(&slots[(size_t)kSlotVmin1 * kColSlots + slot], vmin);
+    if (threadIdx.x == 6 && rmax != 0ull) atomicMax(&slots[(size_t)kSlotRmax1 * kColSlots + slot], rmax);
   }
 }
 
@@ -913,19 +1022,28 @@ __global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelCon
   // var: the set phase reads the constraint's posterior on tiles with a safe candidate only (G within S), and the audit checks a
   // sample that lands here against the enclosure instead (guard.hip).
   // (r07, a listed launch: the list's kernel took the decision, wrote the skip byte and counted the tile; its entry carries it)
-  bool cskip = false;
+  // k1_skip_safe, the mirror image: a tile whose every cell the enclosure proves SAFE at this b and band (encl_safe) is not evaluated
+  // either -- every S bit, no U bit, |S| = 8192, the keys of encl_keys (the variance key exact, the ends of ucb_1 as bounds), its
+  // gradient phases as the gate says.  Unlike an unsafe tile's, its mean / var ARE read by this sweep (k_col_decide, on the units it
+  // cannot settle wholesale): they are what the plan's recording launch stored, which is what this launch would store again
+  // (BilinearPlan::encl_ready: nobody else writes those regions while the flag stands).
+  bool cskip = false, csafe = false;
   if (ROLE == 1 && cbits && px.lean >= 2 && px.encl != nullptr) {
     if (listed) {
-      cskip = (ent >> 31) != 0u;
+      cskip = (ent & kTlistUnsafe) != 0u;
+      csafe = (ent & kTlistSafe) != 0u;
     } else {
-      bool dec = true;
+      bool dec = true, sdec = px.skip_safe != 0;
       if (cx.tid < 128) {
         const double4 e = reinterpret_cast<const double4*>(px.encl)[ctile * 128 + cx.tid];
         dec = encl_unsafe(e.x, e.y, e.z, e.w, cx.bconf, cx.bb, cx.gb_on, cx.lband);
+        sdec = sdec && encl_safe(e.x, e.y, e.z, e.w, cx.bconf, cx.bb, cx.gb_on, cx.lband);
       }
       cskip = __syncthreads_and(dec ? 1 : 0) != 0;
-      if (cx.tid == 0) px.skip[ctile] = cskip ? 1 : 0;
+      csafe = __syncthreads_and(sdec ? 1 : 0) != 0 && !cskip;
+      if (cx.tid == 0) px.skip[ctile] = cskip ? kSkipUnsafe : (csafe ? kSkipSafe : 0);
       if (cskip && cx.tid == 0) atomicAdd(&px.cb.slots[(size_t)kSlotSkip * kColSlots + (ctile & (kColSlots - 1))], 1ull);
+      if (csafe && cx.tid == 0) atomicAdd(&px.cb.slots[(size_t)kSlotSkipSafe * kColSlots + (ctile & (kColSlots - 1))], 1ull);
     }
     if (cskip) {
       cx.role = 0;
@@ -933,8 +1051,21 @@ __global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelCon
       cx.cU = 64 * 128 / 256;               // (every candidate in U, spread over the threads: the partials sum to 8192)
       for (int i = cx.tid; i < 4 * 128; i += 256) cx.lds_bits[i] = 0xffff0000u;      // (S pieces 0, U pieces all ones)
     }
+    if (csafe) {
+      cx.role = 0;
+      cx.skip_store = true;
+      cx.cS = 64 * 128 / 256;               // (every candidate in S)
+      for (int i = cx.tid; i < 4 * 128; i += 256) cx.lds_bits[i] = 0x0000ffffu;      // (S pieces all ones, U pieces 0)
+      if (cx.tid < 128) {                   // (a cell per thread; post_partials takes the minima / the maximum over the workgroup)
+        const double4 e = reinterpret_cast<const double4*>(px.encl)[ctile * 128 + cx.tid];
+        const EnclKeys ek = encl_keys(e.x, e.y, e.z, e.w, cx.bconf);
+        cx.vminS = ek.vlo;
+        cx.rmax = ek.up;
+        cx.xmin = ek.lo;
+      }
+    }
   }
-  const bool skip_tile = (ROLE == 2 && obits && tile_nS == 0ull && px.lean >= 2) || cskip;
+  const bool skip_tile = (ROLE == 2 && obits && tile_nS == 0ull && px.lean >= 2) || cskip || csafe;
   if (!skip_tile)
     post_phase<0, RB, ROLE>(cx, BtA + (size_t)o * sBtA, P0f + (size_t)o * sP0f, KB0, eff ? eff[4 * o * es] : KS0, vo, sf2, ystd * ystd, 0.0, gmax, acc, xn0, pre,
                             VAo, SBo, KBm);
@@ -993,7 +1124,7 @@ __global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelCon
     g_phase_clk[clk_row_ & (kPhaseClkRows - 1)][4] += (unsigned long long)((run2 ? 1 : 0) + (run3 ? 1 : 0));
     g_phase_clk[clk_row_ & (kPhaseClkRows - 1)][5] += 1ull;
     if (ROLE != 0)
-      wg_trace_row(o, clk_in_, clk_part_, clk_, (unsigned int)ctile, skip_tile ? ((!cskip || !(run2 || run3)) ? 1u : 2u) : 0u);
+      wg_trace_row(o, clk_in_, clk_part_, clk_, (unsigned int)ctile, skip_tile ? ((!(cskip || csafe) || !(run2 || run3)) ? 1u : 2u) : 0u);
   }
 #endif
 }
@@ -1212,6 +1343,8 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
     out.col_lean = req.col_lean;
     fuse = false;                      // (no byte masks: the words are the classification)
   }
+  // (K1b's byte-mask launch stores the plan's values through another epilogue: not relied on -- BilinearPlan::encl_ready)
+  if (!interp && !colw) post_regions_written(c);
   bool record_encl = false;
   double* encl = nullptr;
   unsigned int *sched_l1 = nullptr, *sched_l2 = nullptr;
@@ -1230,6 +1363,7 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
     if (!record_encl && req.col_lean >= 2) {
       px.encl = encl;
       px.skip = (uint8_t*)c->bl_encl.p + ebytes;
+      px.skip_safe = (c->opt.k1_skip_safe && c->bl.vals_ready) ? 1 : 0;     // (a proved-safe tile's stored values are read: internal.hpp)
       c->k1_skip_armed = true;
     }
     // r07: lean 2 -- the objective's launch over the tiles with a safe candidate, and, once the enclosures decide skips, the
@@ -1283,7 +1417,7 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
       if (!sched_zero) SBO_HIP(hipMemsetAsync(sched_l1, 0, sizeof(unsigned int) * kTlistShards * kTlistHead, c->stream));
       hipLaunchKernelGGL(k_bl_sched_tiles1, dim3((gx * gy + kSchedWaves - 1) / kSchedWaves), dim3(64 * kSchedWaves), 0, c->stream, mc, (const double*)px.encl, (int)(gx * gy), (int)gx,
                          (int)gy, (unsigned int)cnt0, req.fuse_b, gb_fused, g.gtmax, g.gkey, q, px.skip, sched_l1, sched_cap1, px.cb.Sw, px.cb.Uw,
-                         px.cb.Usum, px.cb.slots, lrows, (unsigned long long*)c->cpart.p, c->cpart_cap);
+                         px.cb.Usum, px.cb.slots, lrows, (unsigned long long*)c->cpart.p, c->cpart_cap, px.skip_safe);
       px.tlist = sched_l1;
       px.tshift = kTlistShift;
       px.tcap = sched_cap1;
@@ -1312,6 +1446,8 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
                          (const double*)c->var.p + (size_t)cs.n_local, cnt0, encl);
       c->bl.encl_ready = true;
     }
+    // (a constraint's launch without a skip list evaluated and stored every tile: the stored values are the plan's again)
+    if (colw && part == 0 && !interp && c->bl.encl_ready && !px.encl) c->bl.vals_ready = true;
   }
   // (whoever merges the Lipschitz rows on this stream -- the reduction below, a sweep's first small kernel -- waits for the gradient launch;
   // the column path reads the keys from the slot block on stream3 itself, in stream order behind that launch: sets_colpath.inc.hpp)

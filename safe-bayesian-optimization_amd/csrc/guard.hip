@@ -462,7 +462,7 @@ __global__ __launch_bounds__(256) void k_audit_pick(const CandSpec cs, int P, un
                                                     (bilinear.hip: k_bl_enclose) of the K1b column-path launch that just ran */,
                                                     const uint8_t* __restrict__ skip /* nullptr, or its skip bytes (a lean-2 launch) */,
                                                     int gx /* 64 x 128 tiles per tile row */,
-                                                    double* __restrict__ aenc /* [5][P]: 1 on a skipped tile, 2 on an evaluated one; m_lo, m_hi, v_lo, v_hi */,
+                                                    double* __restrict__ aenc /* [5][P]: 1 on a tile skipped as unsafe, 2 on an evaluated one, 3 on a tile skipped as safe; m_lo, m_hi, v_lo, v_hi */,
                                                     const GuardBand* __restrict__ gb, GuardBand* __restrict__ gb_snap) {
   const long long N = cs.n_local;
   // (the band this sweep's values rest on: the next sweep may rebuild its plan -- and rewrite gb -- while the comparison still waits)
@@ -482,7 +482,8 @@ __global__ __launch_bounds__(256) void k_audit_pick(const CandSpec cs, int P, un
       // (column path: line g / count0, column g % count0; tile (line / 64, column / 128), cell ((line % 64) / 8, (column % 128) / 8))
       const long long cnt0 = cs.count[0], line = g / cnt0, col = g % cnt0;
       const size_t tile = (size_t)(line >> 6) * (size_t)gx + (size_t)(col >> 7);
-      aenc[k] = (skip && skip[tile] != 0) ? 1.0 : 2.0;
+      const uint8_t sk = skip ? skip[tile] : (uint8_t)0;
+      aenc[k] = sk == kSkipUnsafe ? 1.0 : (sk == kSkipSafe ? 3.0 : 2.0);
       const double* e = encl + (tile * 128 + (size_t)(((line & 63) >> 3) * 16 + ((col & 127) >> 3))) * 4;
       for (int j = 0; j < 4; ++j) aenc[(size_t)(1 + j) * P + k] = e[j];
     }
@@ -490,7 +491,10 @@ __global__ __launch_bounds__(256) void k_audit_pick(const CandSpec cs, int P, un
 }
 // cnt: [0] violations, [1] samples (value pairs compared), [2] bit pattern of the largest deviation in units of the band, [3] samples on
 // constraint tiles the sweep left unevaluated: there the claim is the skip's -- the exact values lie in the tile's enclosure of what the
-// posterior kernel computes, widened by the band --, and the deviation is the distance from that interval
+// posterior kernel computes, widened by the band --, and the deviation is the distance from that interval.  A tile left unevaluated as
+// proved SAFE (k1_skip_safe) is checked both ways: the reference values against the enclosure widened by the band, as above, AND the
+// stored values -- which the sweep did read: they must be what the plan's recording launch stored -- inside the enclosure bit for bit,
+// which is what notices a buffer somebody else wrote (BilinearPlan::vals_ready).
 __global__ __launch_bounds__(256) void k_audit_compare(int P, int q, int o_first, const double* __restrict__ apx, const double* __restrict__ ref_m,
                                                        const double* __restrict__ ref_v, const GuardBand* __restrict__ gb,
                                                        unsigned long long* __restrict__ cnt, double scale /* 1, or the test hook's factor on the band */,
@@ -501,10 +505,10 @@ __global__ __launch_bounds__(256) void k_audit_compare(int P, int q, int o_first
     const int o = o_first + e / P, k = e % P;
     double dm = fabs(apx[(size_t)o * P + k] - ref_m[(size_t)o * P + k]), dv = fabs(apx[(size_t)(q + o) * P + k] - ref_v[(size_t)o * P + k]);
     // (an evaluated constraint tile of a launch with enclosures: what it stored lies inside them, bit for bit -- NaN counts)
-    const bool drift = aenc && o == 1 && aenc[k] == 2.0 &&
+    const bool drift = aenc && o == 1 && (aenc[k] == 2.0 || aenc[k] == 3.0) &&
                        !(apx[(size_t)o * P + k] >= aenc[(size_t)1 * P + k] && apx[(size_t)o * P + k] <= aenc[(size_t)2 * P + k] &&
                          apx[(size_t)(q + o) * P + k] >= aenc[(size_t)3 * P + k] && apx[(size_t)(q + o) * P + k] <= aenc[(size_t)4 * P + k]);
-    if (aenc && o == 1 && aenc[k] == 1.0) {
+    if (aenc && o == 1 && (aenc[k] == 1.0 || aenc[k] == 3.0)) {
       const double rm = ref_m[(size_t)o * P + k], rv = ref_v[(size_t)o * P + k];
       dm = fmax(fmax(aenc[(size_t)1 * P + k] - rm, rm - aenc[(size_t)2 * P + k]), 0.0);
       dv = fmax(fmax(aenc[(size_t)3 * P + k] - rv, rv - aenc[(size_t)4 * P + k]), 0.0);

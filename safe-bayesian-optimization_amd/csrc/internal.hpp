@@ -110,8 +110,11 @@ constexpr int kColSlots = 64;
 enum ColSlotField { kSlotUmin = 0 /* min key of ucb_0 over S */, kSlotS, kSlotU, kSlotB /* counts */, kSlotVmin0, kSlotVmin1 /* min keys */,
                     kSlotRmax1 /* max key */, kSlotL0, kSlotL1 /* max of the gradient norms' bit patterns */,
                     kSlotRowMask /* word s: bit t set iff tile t of tile row s holds a safe candidate */,
-                    kSlotSkip /* count: constraint tiles its enclosure proved unsafe, left unevaluated (r06) */, kColSlotFields };
+                    kSlotSkip /* count: constraint tiles its enclosure proved unsafe, left unevaluated (r06) */,
+                    kSlotSkipSafe /* count: constraint tiles its enclosure proved safe, left unevaluated (option k1_skip_safe) */, kColSlotFields };
 __host__ __device__ inline bool col_slot_is_min(int f) { return f == kSlotUmin || f == kSlotVmin0 || f == kSlotVmin1; }
+constexpr unsigned int kTlistUnsafe = 0x80000000u, kTlistSafe = 0x40000000u;          // flag bits of a tile-list entry (the tile: ent & 0xffffff)
+constexpr unsigned char kSkipUnsafe = 1, kSkipSafe = 2;                                  // a tile's skip byte (bl_encl, behind the enclosures): 0 = evaluated
 constexpr int kTlistShift = 5, kTlistShards = 1 << kTlistShift, kTlistHead = 32;     // PostExtra::tlist (the constraint's list; the objective's has one shard)
 // what a k_bpost launch is told beyond its operands (r05: one launch per output on the column path)
 struct PostExtra {
@@ -125,10 +128,11 @@ struct PostExtra {
   // (k_bl_enclose), and one byte per tile that says whether the tile was left unevaluated; nullptr: every tile is evaluated
   const double* encl;
   uint8_t* skip;
+  int skip_safe; // option k1_skip_safe: tiles the enclosures prove SAFE are left unevaluated as well (skip byte kSkipSafe)
   // lean >= 2, k1_sched (r07): nullptr, or the tile list of this launch, 2^tshift shards: a head of kTlistHead words per shard -- [0] =
   // entries at the front, [1] = entries at the back, the rest unused: a shard's counters have a cache line to themselves --, then room for
   // tcap entries per shard: the tile (by * tgx + bx) in bits 0..23, bit 31 = a constraint tile the list's kernel proved unsafe that still
-  // runs the gradient phases.  Workgroup i of a 1-D grid of tcap << tshift takes entry i >> tshift of shard i mod 2^tshift -- the front
+  // runs the gradient phases, bit 30 = one it proved safe that does.  Workgroup i of a 1-D grid of tcap << tshift takes entry i >> tshift of shard i mod 2^tshift -- the front
   // entries upwards, then the back entries from the last one down -- and exits at once past both.  Tiles not in the list were written by
   // the list's kernels.
   const unsigned int* tlist;
@@ -164,7 +168,23 @@ struct BilinearPlan {
   int r0[kMaxQ] = {0}, r1[kMaxQ] = {0};
   double setup_ms = 0.0;
   GemmOps ops;           // (eff: per-output counts; band_ready: guard.hip, guard_band_bilinear)
-  bool encl_ready = false;   // bl_encl holds the enclosures of the constraint's mean / var per 8 x 8 cell (k_bl_enclose, r06)
+  // bl_encl holds the enclosures of the constraint's mean / var per 8 x 8 cell (k_bl_enclose, r06), recorded from a launch of this plan
+  // that stored every tile, AND no posterior launch of another kind has written sbo_ctx::mean / var since.
+  // vals_ready: on top of that, the constraint's regions of sbo_ctx::mean / var hold ON EVERY TILE the bits this plan's k_bpost computes
+  // (a lean-2 sweep leaves the tiles it proves safe unevaluated, and k_col_decide reads their stored values: option k1_skip_safe).
+  // WHO MAY WRITE THOSE REGIONS while the flags stand: K1b's column-path launches of this plan, nothing else.
+  //   * Every posterior launch on the context passes through launch_posterior (posterior.hip), which drops both flags for every other
+  //     family -- K1g, K1i, K1t, the generic kernels, an fp32 model's launches, whoever asked (a sweep, sbo_posterior_run, the guard) --;
+  //     launch_posterior_gemm drops them for a K1b launch that is not on the column path (another epilogue: not relied on).
+  //   * A new plan starts without them (bilinear_setup: a new model, new candidates, an option the plans are built with, among them
+  //     `bilinear` itself), and so does a reallocation of mean / var (alloc_workspace).
+  //   * The guard's recheck scatters exact values over the plan's at the candidates it lists (rc_refine): it drops vals_ready alone --
+  //     nobody reads the stored values of a tile proved UNSAFE, so r06's skip stands --, and the next K1b column-path launch that
+  //     evaluates and stores every tile (the recording one, or a lean-0 / lean-1 sweep) sets it again.
+  // With encl_ready down the next K1b column-path launch evaluates and stores every tile and records the enclosures again, as after a
+  // plan rebuild.  Whoever adds a writer of sbo_ctx::mean / var must call post_regions_written (or post_values_patched).
+  bool encl_ready = false;
+  bool vals_ready = false;
   // bl_BtA holds stage 1's images of THIS plan (k_bstage1 has been enqueued on its operands): launch_posterior_gemm runs stage 1 for
   // the plan's first launch only.  INVARIANT: stage 1 reads bl_P1A, bl_T4f and the counts `ops.eff` (in bl_cheb) and writes bl_BtA;
   // all four are written by the two plan builders and by nothing else -- bilinear_setup (k_cheb_tab<0>, k_cheb_t4f, k_cheb_trunc)
@@ -386,6 +406,7 @@ struct sbo_ctx {
     int refine_lds = 1;   // (A/B checker): 1 sbo_refine stages M in LDS when it fits, 0 it always streams M's rows
     int list_index = -1;  // -1 the index for explicit lists above the exhaustive cap only, 0 never, 1 always
     int k1_sched = 1;             // 1 = K1b's two lean-2 column-path launches take their tiles from per-sweep lists; 0: one workgroup per tile
+    int k1_skip_safe = 1;         // 1 = a lean-2 column-path sweep leaves the constraint tiles its enclosures prove SAFE unevaluated too; 0: the unsafe ones only
     int comm_events = 0;     // an event pair per collective (MultiRank::comm_ev) whose elapsed times sbo_profile.comm_ms sums
     int col_path = 1;        // 0 = never
     int col_overlap = 1;     // 1 = the expander chain runs on stream3 beside the objective's posterior launch; 0: one stream
@@ -584,6 +605,11 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
 // and writes no validity flag itself; where the cases differ, the reason stands here.
 // Both GEMM-posterior plans, the posterior and the fp32 band: a new model, new candidates, or an option the plans are built with.
 // (Not K1t's plan: it keys itself on the model's serial and the grid, tensor_applicable compares them.)
+// Somebody other than a K1b column-path launch of the resident plan writes (or is about to write) sbo_ctx::mean / var: the stored
+// values of the constraint are no longer the plan's on every tile (BilinearPlan::encl_ready).
+inline void post_regions_written(sbo_ctx* c) { c->bl.encl_ready = c->bl.vals_ready = false; }
+// ... single candidates of it are overwritten with other values (the guard's exact recheck): see BilinearPlan::vals_ready
+inline void post_values_patched(sbo_ctx* c) { c->bl.vals_ready = false; }
 inline void plans_invalidate(sbo_ctx* c) {
   c->bl.valid = false;
   c->bi.valid = false;

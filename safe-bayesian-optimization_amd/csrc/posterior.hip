@@ -966,6 +966,12 @@ static int launch_generic(sbo_ctx* c, const PostTarget& t);   // (defined below 
 int launch_posterior(sbo_ctx* c, const PostRequest& req, PostOutcome& out) {
   c->gb.active = false;                    // (the approximating paths K1b / K1t switch their guard band on themselves)
   c->k1_skip_armed = c->k1_encl_check = false;   // (so does the K1b column path its records for the audit, guard.hip)
+  // Whatever family runs below writes mean / var of this context.  Only a K1b launch of the plan that is resident NOW leaves the
+  // constraint's stored values what that plan computes (BilinearPlan::encl_ready, internal.hpp): every other family -- K1i, K1g, K1t,
+  // the generic kernels, an fp32 model's -- drops the flag here, in the one place the family is chosen, and a plan built below starts
+  // without it.
+  const bool encl_kept = c->bl.valid && c->bl.encl_ready, vals_kept = encl_kept && c->bl.vals_ready;
+  post_regions_written(c);
   // block-triangular contraction as issued: npad (npad + 16) / 2 multiply-adds per candidate and output
   const double tri_flops = (double)c->mc.q * c->mc.npad * (c->mc.npad + 16.0) * (double)c->cs.n_local;
   const PostTarget t{c->cs, c->mean.p, c->var.p, c->Lmax};
@@ -985,6 +991,8 @@ int launch_posterior(sbo_ctx* c, const PostRequest& req, PostOutcome& out) {
       if (!c->bl.valid && (rc = bilinear_setup(c))) return rc;
       if (c->bl.usable) {
         c->last_k1 = 4;
+        c->bl.encl_ready = encl_kept;                        // (the same plan as when the enclosures were recorded: bilinear_setup did not run)
+        c->bl.vals_ready = vals_kept;
         return launch_posterior_gemm(c, false, req, out);    // (writes the Lipschitz keys itself)
       }
     }

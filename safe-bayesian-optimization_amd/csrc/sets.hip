@@ -51,6 +51,7 @@ struct SweepScalars {
   long long n_guard;
   long long guard_slot[kArgSlots];
   long long tiles_skipped;                 // column path, lean 2: constraint tiles of the posterior left unevaluated (r06: kSlotSkip)
+  long long tiles_skipped_safe;            // ... and those left unevaluated as proved safe (kSlotSkipSafe)
   // ---- device only ----
   unsigned long long ticket;               // workgroups of k_goose_finals that have finished their slot (zeroed with the block)
   long long n_guard_cls;                   // the classification's share of n_guard, the value it starts from
@@ -2154,6 +2155,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v
   if ((rc = sweep_profile(c, kSafeOpt, reuse))) return rc;
   c->prof.set_path = colpath ? 1 : 0;
   c->prof.k1_tiles_skipped = colpath ? h.tiles_skipped : 0;
+  c->prof.k1_tiles_skipped_safe = colpath ? h.tiles_skipped_safe : 0;
 
   memset(res, 0, sizeof(*res));
   res->count_S = h.count_S;

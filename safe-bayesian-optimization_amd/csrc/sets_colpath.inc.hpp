@@ -201,7 +201,7 @@ __device__ __forceinline__ void col_coarse_job(int blk, const ColGeom gm, const 
 // one wave reduces a field of the slot block (internal.hpp: ColSlotField): a load per lane, six shuffle steps; valid in every lane
 __device__ __forceinline__ unsigned long long col_slot_reduce(const unsigned long long* __restrict__ slots, int field) {
   unsigned long long v = slots[(size_t)field * kColSlots + (threadIdx.x & 63)];
-  const bool is_min = col_slot_is_min(field), is_sum = field == kSlotS || field == kSlotU || field == kSlotB || field == kSlotSkip;
+  const bool is_min = col_slot_is_min(field), is_sum = field == kSlotS || field == kSlotU || field == kSlotB || field == kSlotSkip || field == kSlotSkipSafe;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const unsigned long long y = __shfl_xor(v, o);
@@ -217,10 +217,11 @@ __device__ __forceinline__ void col_merge1_body(const unsigned long long* __rest
   if (threadIdx.x < 64) {
     const unsigned long long cS = col_slot_reduce(slots, kSlotS), cU = col_slot_reduce(slots, kSlotU), cB = col_slot_reduce(slots, kSlotB);
     const unsigned long long vmin = col_slot_reduce(slots, kSlotVmin1), rmax = col_slot_reduce(slots, kSlotRmax1), l1 = col_slot_reduce(slots, kSlotL1);
-    const unsigned long long nskip = col_slot_reduce(slots, kSlotSkip);
+    const unsigned long long nskip = col_slot_reduce(slots, kSlotSkip), nsafe = col_slot_reduce(slots, kSlotSkipSafe);
     if (threadIdx.x == 0) {
       Lmax[1] = l1;
       sc->tiles_skipped = (long long)nskip;
+      sc->tiles_skipped_safe = (long long)nsafe;
       sc->ustar_key = ~0ull;                       // (the objective's half: k_col_min, into its own block)
       sc->count_S = (long long)cS;
       sc->count_U = (long long)cU;
@@ -765,6 +766,12 @@ __global__ __launch_bounds__(256) void k_col_decide(const ColGeom gm, const unsi
       // read mean / var (a third of the 515 tiles with a safe candidate on config H).  (A half-width unit's own cells: an interval
       // inside the one the tile's sixteen cells gave, so it settles every unit that one settled; and a unit it settles holds no
       // candidate the tests below would have left open -- they use the candidate's own bound and cell, which lie inside both.)
+      // (k1_skip_safe: a tile the posterior left unevaluated as proved safe hands over [ulo, uhi] from its cells' enclosures --
+      // bilinear_post.inc.hpp: encl_keys --, an interval AROUND the one its candidates' own bounds would have given.  The argument is
+      // the same one step further out: the wider interval settles no unit the narrower one would not have settled the same way -- both
+      // tests are monotone in ulo and uhi --, and a unit it leaves open takes the per-candidate path below on the tile's stored mean /
+      // var, the plan's values (BilinearPlan::vals_ready), with every candidate's verdict taken from its own bound and cell.  The
+      // same holds for capC above: rmax is then an upper bound of the largest ucb_1, and a larger cap only examines more entries.)
       if (L > 0) {
         double dmx = dc2, dmn = dc2;
 #pragma unroll
@@ -1011,6 +1018,7 @@ __global__ __launch_bounds__(256) void k_col_finals(const Best* __restrict__ reg
       hm->n_scan = sc->n_scan;
       hm->n_guard = sc->n_guard;
       hm->tiles_skipped = sc->tiles_skipped;
+      hm->tiles_skipped_safe = sc->tiles_skipped_safe;
       for (int t = 0; t < kMaxQ; ++t) {
         hm->rmax_key[t] = sc->rmax_key[t];
         reinterpret_cast<unsigned long long*>(mirror + 3072)[t] = Lkeys[t];

@@ -277,6 +277,7 @@ static int rc_refine(sbo_ctx* c, const long long* list, long long nf, bool guard
     if ((rc = guard_exact_list(c, (const double*)pbuf.p, nf, em, ev))) return rc;
     // (the standing audit takes its sample of what the posterior kernel stored before the exact values replace it)
     if (c->audit.pending) SBO_HIP(hipStreamWaitEvent(c->stream, c->audit.ev[0], 0));
+    post_values_patched(c);                 // (exact values replace the plan's at the listed candidates: internal.hpp, BilinearPlan::vals_ready)
     hipLaunchKernelGGL(k_rc_scatter, dim3(nbf), dim3(256), 0, c->stream, list, nf, q, n, (const double*)em, (const double*)ev,
                        (double*)c->mean.p, (double*)c->var.p, (uint8_t*)c->recheck.refined.p);
     SBO_HIP(hipGetLastError());

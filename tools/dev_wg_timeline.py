@@ -97,7 +97,7 @@ def main():
     prof = eng.profile()
     assert fn(ptr, ROWS, 0) == 0
     out = open(args.out, "w") if args.out else sys.stdout
-    print(f"config {args.config}, lean 2, k1_sched {args.sched}: k1_tiles_skipped {prof['k1_tiles_skipped']}, count_S {res['count_S']}, "
+    print(f"config {args.config}, lean 2, k1_sched {args.sched}: k1_tiles_skipped {prof['k1_tiles_skipped']}, k1_tiles_skipped_safe {prof['k1_tiles_skipped_safe']}, count_S {res['count_S']}, "
           f"posterior_ms {prof['posterior_ms']:.4f} (diagnostic build: a clock read and a barrier at each phase boundary)", file=out)
     report("constraint launch k_bpost<1,1>", decode(buf[1]), out)
     report("objective launch k_bpost<1,2>", decode(buf[0]), out)
