@@ -591,6 +591,52 @@ typedef struct sbo_refine_robust_result {
 int sbo_refine_robust(sbo_ctx* ctx, const sbo_refine_robust_opts* opts, const double* xc_seed, double* scenarios_out,
                       sbo_refine_robust_result* result);
 
+/* ---- the mean's gradient at a list, and its bound maximised over the box ---- */
+/* d MEAN_o / d x_a = Y_std_o sum_j alpha_oj k_j (X_ja - xn_a) / ell_a / X_std_a (DESIGN.md section 12's formula, on the resident fp64
+ * alpha and X_norm) at points[n_points][d]: grad_out[n_points][q][d], infnorm_out[n_points][q] = max_a |.|; either may be NULL, not
+ * both.  The value at a point does not depend on n_points or on the point's place in the list, bit for bit: every sum runs over the
+ * observations in their order, whatever the launch shape, and two calls return the same bits.  Waits first for a deferred
+ * factorisation (one that fails: SBO_E_INVALID).  Reads the model only: candidates, posterior, masks, plans, guard band, audit
+ * counters and options are untouched, and a sweep behind the call equals one before it bit for bit.  No collectives (the model is
+ * replicated: any rank may call).  fp64 models only (SBO_F32: SBO_E_UNSUPPORTED); n_points < 1: SBO_E_INVALID. */
+int sbo_mean_grad(sbo_ctx* ctx, int64_t n_points, const double* points, double* grad_out, double* infnorm_out);
+
+typedef struct sbo_lipschitz_opts {
+  uint32_t output_mask;            /* bit o (o < q): bound output o; 0: every output                                              */
+  int32_t  top;                    /* seeds refined per (output, axis, sign); <= 0: 4; at most 16                                 */
+  int32_t  max_eval;               /* evaluations (value + Hessian row) per problem; <= 0: 200; at most 2000                      */
+  int32_t  reserved;
+  double   tol;                    /* projected-gradient inf-norm in span units of the objective scaled by the output's L_seed;
+                                      <= 0: 1e-9                                                                                  */
+  double   lo[SBO_MAX_D], hi[SBO_MAX_D];   /* the box (finite, lo <= hi; an axis of span 0 is held)                               */
+} sbo_lipschitz_opts;
+
+typedef struct sbo_lipschitz_result {
+  double  L[SBO_MAX_Q];            /* the bound found; 0 for outputs not asked for                                                */
+  double  L_seed[SBO_MAX_Q];       /* max over the usable seeds, before any refinement                                            */
+  double  x[SBO_MAX_Q][SBO_MAX_D]; /* where L[o] is attained                                                                      */
+  int32_t axis[SBO_MAX_Q], sign[SBO_MAX_Q];   /* L[o] = sign * dMEAN_o/dx_axis at x[o]; sign is +1 or -1                          */
+  int64_t seeds_used, evaluations; /* seeds inside the box; evaluations summed over the problems                                  */
+  int32_t problems, converged;     /* solver problems run / ended at tol                                                          */
+} sbo_lipschitz_result;
+
+/* L[o] ~ max over the box of ||grad MEAN_o||_inf (models/SafeOpt.py:79-83, models/GoOSE.py:74-78: maximize_infnorm_mean_grad, there by
+ * SciPy DE) as a multistart local search from seeds[n_seeds][d].  Seeds that are non-finite or outside the box are skipped, not
+ * clipped (none left: SBO_E_INVALID).  Stage 1 evaluates every usable seed with sbo_mean_grad's kernel and keeps, for each asked
+ * output o, axis a of span > 0 and sign s, the `top` seeds of largest s g_a (ties: the lowest seed index).  Stage 2 runs one solver
+ * problem per kept seed, all in one launch and one workgroup each: maximise s g_a(x) over the box by a projected BFGS in the metric of
+ * the spans on F = -s g_a / L_seed[o], with row a of the mean's Hessian as its gradient (max_x ||grad||_inf = max_{a,s} max_x s g_a(x),
+ * and every inner problem is smooth); it stops at tol, at max_eval, when an accepted step changes F by no more than rounding, or when a
+ * line search fails with H reset.  Exact check: the final iterate of
+ * every problem is evaluated again by stage 1's kernel, and L[o] is the largest |g_a| over the usable seeds and those final points, all
+ * axes (ties: the lowest axis, then sign +, then seeds before iterates, then the lowest index).  Hence L[o] >= L_seed[o] always, lo <=
+ * x[o] <= hi, and L[o] is bit for bit the infnorm_out sbo_mean_grad gives at x[o].  L is a lower bound of the supremum, attained inside
+ * the box -- as the reference's DE gives one; it is NOT a certificate: a basin no seed reaches is missed.  Deterministic; one host wait.
+ * Otherwise as sbo_mean_grad: waits for a deferred factorisation, reads the model only, no collectives, fp64 models only.
+ * SBO_E_INVALID: n_seeds < 1, top > 16, max_eval > 2000, a box that is not finite with lo <= hi, output_mask bits at or above q. */
+int sbo_lipschitz(sbo_ctx* ctx, const sbo_lipschitz_opts* opts, int64_t n_seeds, const double* seeds /* [n_seeds][d] */,
+                  sbo_lipschitz_result* result);
+
 /* ---- plant evaluation ------------------------------------------ */
 /* The reference's William-Otto reactor (problems/WilliamOttoReactor_Problem.py:19-93), noise-free, for n input rows
  * u[n, 2] = (Fb, Tr): out[n, 3] = (get_objective, get_constraint1, get_constraint2), each the steady state of the six
@@ -641,6 +687,8 @@ int sbo_profile_get(sbo_ctx* ctx, sbo_profile* out);
  *                      the card with the sweep it follows (~35 us of config H's set phase at 1024 samples, n = 512): 1 audits every sweep
  *   "refine_lds"       1 (default): sbo_refine / sbo_refine_sets / sbo_refine_robust stage the used outputs' triangles of M in LDS when they fit 144 KiB; 0: it always streams
  *                      M's rows from L2 (the tier of larger models; results are bit-identical either way)
+ *   "lipschitz_lds"    1 (default): sbo_lipschitz's solver stages X_norm and its output's alpha in LDS when they fit 144 KiB; 0: it always streams
+ *                      them from L2 (results are bit-identical either way)
  *   "list_index"       explicit candidate lists: expander sets (SafeOpt, GoOSE's source filter) and GoOSE's coverage search on a spatial
  *                      index of the list (Morton order, boxes of the U members; verdicts identical to the exhaustive ones).  -1 (default):
  *                      only for lists above 2097152 candidates, where the exhaustive expander sets are refused; 1: at any size (A/B checker);

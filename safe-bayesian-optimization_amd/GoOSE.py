@@ -17,10 +17,10 @@ from .SafeOpt import BO as _SafeOptBO
 class BO(_SafeOptBO):
     def __init__(self, plant_system, bound, b, grid=None, device: int = 0, dtype: str = "f64",
                  reference_quirk_L_index: bool = True, seed: int = 42, candidates=None, list_index: int | None = None,
-                 refine: bool = False):
+                 refine: bool = False, lipschitz: str = "grid"):
         _SafeOptBO.__init__(self, plant_system, bound, b, grid=grid, device=device, dtype=dtype,
                             reference_quirk_L_index=reference_quirk_L_index, seed=seed, candidates=candidates,
-                            list_index=list_index, refine=refine)
+                            list_index=list_index, refine=refine, lipschitz=lipschitz)
         self._goose_cache = None
 
     def goose_sweep(self, want_masks: bool = False) -> dict:

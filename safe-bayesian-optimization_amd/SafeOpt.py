@@ -23,8 +23,14 @@ from .GP_Safe import GP
 class BO(GP):
     def __init__(self, plant_system, bound, b, grid=None, device: int = 0, dtype: str = "f64",
                  reference_quirk_L_index: bool = True, seed: int = 42, candidates=None, list_index: int | None = None,
-                 refine: bool = False):
+                 refine: bool = False, lipschitz: str = "grid"):
         GP.__init__(self, plant_system, device=device, dtype=dtype, seed=seed)
+        if lipschitz not in ("grid", "box"):
+            raise ValueError("lipschitz must be 'grid' or 'box'")
+        # "grid": L_i is the sweep's, the maximum over the candidates.  "box": the larger of that and SweepEngine.lipschitz over
+        # ``bound`` -- a multistart lower bound of the box maximum; the sweeps' own L does not change
+        self.lipschitz = lipschitz
+        self._box_L_cache = None      # (model_version, L [q])
         self.refine = bool(refine)    # acquisitions polish the sweep's winner off the grid (SweepEngine.refine)
         self.bound = np.asarray(bound, dtype=np.float64)
         self.b = b
@@ -163,9 +169,36 @@ class BO(GP):
         grad = ds["Y_std"][i] * ((ds["X_norm"] - xn).T @ w) / ell / ds["X_std"]
         return float(np.max(np.abs(grad)))
 
-    def maximize_infnorm_mean_grad(self, i):
-        """L_i = max over the candidate grid of ||grad MEAN_i||_inf (the reference maximises over the box with DE)."""
-        return float(self.sweep()["L"][i])
+    def mean_grad(self, points):
+        """d MEAN_o / d x_a at ``points`` [N, d] (or one point [d]) -> [N, q, d], on the device (SweepEngine.mean_grad)."""
+        self._sync_model()
+        return self.engine.mean_grad(points)
+
+    def maximize_infnorm_mean_grad(self, i, lipschitz=None):
+        """L_i = max over the candidate grid of ||grad MEAN_i||_inf (the reference maximises over the box with DE).  ``lipschitz``
+        (default: the constructor's) "box": the larger of that -- where the sweep computed it -- and the box maximum found by
+        ``SweepEngine.lipschitz`` over ``bound`` from its default seeds (cached until the model changes)."""
+        res = self.sweep()
+        if not self._box_lipschitz(lipschitz):
+            return float(res["L"][i])
+        return self._max_L(res, i)
+
+    def _box_lipschitz(self, lipschitz=None):
+        mode = self.lipschitz if lipschitz is None else lipschitz
+        if mode not in ("grid", "box"):
+            raise ValueError("lipschitz must be 'grid' or 'box'")
+        return mode == "box"
+
+    def _box_L(self):
+        """``SweepEngine.lipschitz`` over ``bound`` for every output, once per model version."""
+        if self._box_L_cache is None or self._box_L_cache[0] != self._model_version:
+            self._sync_model()
+            self._box_L_cache = (self._model_version, self.engine.lipschitz(self.bound[:, 0], self.bound[:, 1])["L"])
+        return self._box_L_cache[1]
+
+    def _max_L(self, res, i):
+        """max(the sweep's L_i, the box L_i).  (A lean sweep leaves L_0 = 0: the maximum is then the box value.)"""
+        return float(max(res["L"][i], self._box_L()[i]))
 
     def Lipschitz_continuity_constraint(self, x, i, max_infnorm_mean_grad):
         """x = [x, x'] stacked: ucb_i(x) - L ||x - x' + 1e-8|| (models/SafeOpt.py:85-88)."""
@@ -209,8 +242,10 @@ class BO(GP):
     _pair_max_eval = 1600     # evaluations of one point per refined pair (a pair costs two, and has twice the variables)
 
     def _sweep_L(self, res, c):
-        """The Lipschitz constant the sweep used for constraint c (models/SafeOpt.py:110: the loop-leaked index under the quirk)."""
-        return float(res["L"][self.n_fun - 1 if self.reference_quirk_L_index else c])
+        """The Lipschitz constant the sweep used for constraint c (models/SafeOpt.py:110: the loop-leaked index under the quirk);
+        with ``lipschitz="box"`` the larger of it and the box value of the same index."""
+        i = self.n_fun - 1 if self.reference_quirk_L_index else c
+        return self._max_L(res, i) if self._box_lipschitz() else float(res["L"][i])
 
     def _all_points(self):
         """Every candidate [N, d] in the sweep's flat order (axis 0 fastest on a grid)."""

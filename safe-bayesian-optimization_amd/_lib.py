@@ -114,6 +114,17 @@ class RefineRobustResult(C.Structure):
                 ("worst_d", C.c_double * SBO_MAX_D), ("g_min", C.c_double * SBO_MAX_Q), ("gap", C.c_double)]
 
 
+class LipschitzOpts(C.Structure):
+    _fields_ = [("output_mask", C.c_uint32), ("top", C.c_int32), ("max_eval", C.c_int32), ("reserved", C.c_int32), ("tol", C.c_double),
+                ("lo", C.c_double * SBO_MAX_D), ("hi", C.c_double * SBO_MAX_D)]
+
+
+class LipschitzResult(C.Structure):
+    _fields_ = [("L", C.c_double * SBO_MAX_Q), ("L_seed", C.c_double * SBO_MAX_Q), ("x", (C.c_double * SBO_MAX_D) * SBO_MAX_Q),
+                ("axis", C.c_int32 * SBO_MAX_Q), ("sign", C.c_int32 * SBO_MAX_Q), ("seeds_used", C.c_int64), ("evaluations", C.c_int64),
+                ("problems", C.c_int32), ("converged", C.c_int32)]
+
+
 class FitOpts(C.Structure):
     _fields_ = [("P", C.c_int32), ("maxiter", C.c_int32), ("tol", C.c_double), ("atol", C.c_double), ("seed", C.c_uint64),
                 ("polish", C.c_int32), ("polish_maxiter", C.c_int32), ("polish_ftol", C.c_double), ("polish_gtol", C.c_double),
@@ -200,6 +211,8 @@ SYMBOLS = [
     ("sbo_refine", C.c_int, [_P, C.POINTER(RefineOpts), C.c_int64, _P, _P, _P, _P, C.POINTER(RefineResult)]),
     ("sbo_refine_sets", C.c_int, [_P, C.POINTER(RefineSetsOpts), C.c_int64, _P, _P, _P, _P, _P, _P, C.POINTER(RefineSetsResult)]),
     ("sbo_refine_robust", C.c_int, [_P, C.POINTER(RefineRobustOpts), _P, _P, C.POINTER(RefineRobustResult)]),
+    ("sbo_mean_grad", C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    ("sbo_lipschitz", C.c_int, [_P, C.POINTER(LipschitzOpts), C.c_int64, _P, C.POINTER(LipschitzResult)]),
     ("sbo_plant_wo", C.c_int, [_P, C.c_int64, _P, _P]),
     ("sbo_profile_get", C.c_int, [_P, C.POINTER(Profile)]),
     ("sbo_set_option", C.c_int, [_P, C.c_char_p, C.c_int64]),

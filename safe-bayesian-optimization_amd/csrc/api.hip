@@ -297,6 +297,7 @@ const OptRow kOptions[] = {
     OPT_BOOL(fp64_recheck, kOptNothing, nullptr),       // (takes effect at the next sbo_model_set: the fp64 twin is built there)
     OPT_BOOL(comm_selftest, kOptNothing, hook_selftest),
     OPT_RANGE(refine_lds, 0, 1, "refine_lds must be 0 (stream M) or 1 (LDS when it fits)", kOptNothing, nullptr),
+    OPT_RANGE(lipschitz_lds, 0, 1, "lipschitz_lds must be 0 (stream X_norm and alpha) or 1 (LDS when they fit)", kOptNothing, nullptr),
     OPT_RANGE(list_index, -1, 1, "list_index must be -1 (auto), 0 (never) or 1 (always)", kOptNothing, nullptr),
     OPT_RANGE(posterior_path, 0, 2, "posterior_path must be 0 (auto), 1 (generic) or 2 (generic, chunked)", kOptPosterior, nullptr),
 };

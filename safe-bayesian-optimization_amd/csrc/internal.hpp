@@ -404,6 +404,7 @@ struct sbo_ctx {
     double audit_scale = 1.0;        // guard_audit_scale_ppm (tests): the audit compares against band x this -- a way to see it fire
     int set_lanes = 1;       // 0: all constraints on the main stream, one after the other
     int refine_lds = 1;   // (A/B checker): 1 sbo_refine stages M in LDS when it fits, 0 it always streams M's rows
+    int lipschitz_lds = 1;  // (A/B checker): 1 sbo_lipschitz stages X_norm and the output's alpha in LDS when they fit, 0 it always streams them
     int list_index = -1;  // -1 the index for explicit lists above the exhaustive cap only, 0 never, 1 always
     int k1_sched = 1;             // 1 = K1b's two lean-2 column-path launches take their tiles from per-sweep lists; 0: one workgroup per tile
     int k1_skip_safe = 1;         // 1 = a lean-2 column-path sweep leaves the constraint tiles its enclosures prove SAFE unevaluated too; 0: the unsafe ones only
@@ -502,6 +503,7 @@ struct sbo_ctx {
   sbo::DevBuf maskS, maskU, maskM, maskG, maskO;   // uint8 [n_local] (G/O: [(q-1)][n_local])
   sbo::DevBuf fitbuf, fitwork;   // hyper-parameter objective: inputs/outputs and the P x n x n factor workspace
   sbo::DevBuf refbuf;            // sbo_refine: seeds, candidates, their exact values and the results (refine.hip)
+  sbo::DevBuf lipbuf;            // sbo_mean_grad / sbo_lipschitz: points, gradients, picks and the result block (lipschitz.hip)
   // What one per-constraint chain of the set phase enqueues on and scribbles in.  Lane 0 is the main stream's: everything before
   // the fork and after the join, every sweep of a model with one constraint and every sweep on several ranks uses it alone.  With
   // two or more constraints on one rank the chains are independent, so every other constraint goes to lane 1: stream2, its own

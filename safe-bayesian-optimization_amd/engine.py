@@ -39,6 +39,7 @@ class SweepEngine:
         self.n_local = 0
         self.first = 0
         self.world, self.rank = 1, 0
+        self._obs = None       # (X_norm, X_mean, X_std) of the resident model: the observations among lipschitz's default seeds
 
     # ---- lifetime ---------------------------------------------------------------------------
     def close(self):
@@ -123,6 +124,7 @@ class SweepEngine:
             L.check(self._lib.sbo_model_set(*args, None))
         self.n, self.d, self.q = n, d, q
         self._prior = self._prior_mean(arrs[2], arrs[3], mean_prior)
+        self._obs = (X_norm.copy(), arrs[0].copy(), arrs[1].copy())
 
     def model_fit(self, ds: dict, bounds, init_pop, seed: int = 0, maxiter: int = 1000, tol: float = 0.01, atol: float = 0.0,
                   polish: bool = True, polish_maxiter: int = 10000, polish_ftol: float = FLOAT32_EPS, polish_gtol: float = 1e-8,
@@ -164,6 +166,7 @@ class SweepEngine:
         self.tag, self.np_dtype = tag, np_dtype
         self.n, self.d, self.q = n, d, q
         self._prior = self._prior_mean(arrs[2], arrs[3], mp)
+        self._obs = (X_norm.copy(), arrs[0].copy(), arrs[1].copy())
         out = {"hypopt": hyp}
         for name, _ in L.FitReport._fields_:
             if name == "reserved":
@@ -191,6 +194,7 @@ class SweepEngine:
             raise ValueError("x_norm_new must be [d] and y_norm_new [q]")
         L.check(self._lib.sbo_model_append(self._ctx, _ptr(x), _ptr(y)))
         self.n += 1
+        self._obs = (np.vstack([self._obs[0], x]),) + self._obs[1:]
 
     def remove_sample(self, index: int):
         """The counterpart of ``append_sample`` (``sbo_model_remove``): observation ``index`` (0-based, in the order of ``X_norm``
@@ -202,6 +206,7 @@ class SweepEngine:
             raise ValueError(f"index {int(index)} out of range [0, {self.n})")
         L.check(self._lib.sbo_model_remove(self._ctx, int(index)))
         self.n -= 1
+        self._obs = (np.delete(self._obs[0], int(index), axis=0),) + self._obs[1:]
 
     def model_loo(self, b: float = 3.0, Y_norm=None) -> dict:
         """Leave-one-out diagnostics of the resident model (``sbo_model_loo``), normalised units, fp64 whatever the model dtype:
@@ -529,6 +534,81 @@ class SweepEngine:
         return {"status": int(res.status), "xc": np.array(res.xc[:nxc]), "value": float(res.value), "seed_value": float(res.seed_value),
                 "worst_d": np.array(res.worst_d[:nd]), "g_min": np.array(res.g_min[1:self.q]), "scenarios": scen[:K, :nd].copy(),
                 "rounds": int(res.rounds), "evaluations": int(res.evaluations), "gap": float(res.gap)}
+
+    def mean_grad(self, points, infnorm: bool = False):
+        """d MEAN_o / d x_a at ``points`` [N, d] (``sbo_mean_grad``): grad [N, q, d], the analytic form of
+        ``jax.grad(self.mean)`` (models/SafeOpt.py:68-71).  ``infnorm=True``: also max_a |.| as [N, q].  The value at a point does not
+        depend on the list it stands in, bit for bit.  fp64 models; nothing resident is touched."""
+        pts = _f64(points)
+        if pts.ndim == 1:
+            pts = pts.reshape(1, -1)
+        if self.d < 1 or pts.ndim != 2 or pts.shape[1] != self.d:
+            raise ValueError("points must be [N, d] for the model's d")
+        N = pts.shape[0]
+        grad = np.empty((N, self.q, self.d))
+        inf = np.empty((N, self.q)) if infnorm else None
+        L.check(self._lib.sbo_mean_grad(self._ctx, N, _ptr(pts), _ptr(grad), _ptr(inf)))
+        return (grad, inf) if infnorm else grad
+
+    def lipschitz_seeds(self, lo, hi) -> np.ndarray:
+        """The default seeds of ``lipschitz``: a tensor grid over the box of min(33, max(2, floor(4096^(1/d)))) points per axis -- the
+        points of ``sbo_candidates_grid``, axis 0 the fastest --, then the observations (X_norm X_std + X_mean) clipped to the box."""
+        lo, hi = _f64(lo).reshape(-1), _f64(hi).reshape(-1)
+        d = self.d
+        if lo.shape != (d,) or hi.shape != (d,):
+            raise ValueError("lo and hi must have shape [d]")
+        m = 2
+        while m < 33 and (m + 1) ** d <= 4096:
+            m += 1
+        axes = []
+        for a in range(d):
+            ax = lo[a] + np.arange(m) * ((hi[a] - lo[a]) / (m - 1))
+            ax[-1] = hi[a]
+            axes.append(ax)
+        mesh = np.meshgrid(*axes[::-1], indexing="ij")
+        grid = np.stack([g.reshape(-1) for g in mesh[::-1]], axis=1)
+        if self._obs is None:
+            raise ValueError("the default seeds need a model")
+        X_norm, X_mean, X_std = self._obs
+        return np.ascontiguousarray(np.vstack([grid, np.clip(X_norm * X_std + X_mean, lo, hi)]))
+
+    def lipschitz(self, lo, hi, seeds=None, outputs=None, top: int | None = None, max_eval: int | None = None,
+                  tol: float | None = None) -> dict:
+        """max over the box [lo, hi] of ||grad MEAN_o||_inf by a multistart local search on the device (``sbo_lipschitz``, DESIGN.md
+        section 16) -- the reference's ``maximize_infnorm_mean_grad`` (models/SafeOpt.py:79-83), there by DE.  ``seeds`` [S, d] (None:
+        ``lipschitz_seeds(lo, hi)``); seeds outside the box are skipped.  ``outputs``: the outputs to bound (None: all).  Returns
+        ``L`` [q] (0 for outputs not asked for), ``L_seed`` [q] (the largest value at a seed), ``x`` [q, d] where L is attained,
+        ``axis`` and ``sign`` [q] (L = sign * d MEAN_o / d x_axis at x), ``seeds_used``, ``evaluations``, ``problems``, ``converged``.
+        L >= L_seed, and L is bit for bit ``mean_grad(x[o], infnorm=True)``'s value: a lower bound of the supremum that is attained
+        in the box, not a certificate.  Nothing resident is touched."""
+        lo, hi = _f64(lo).reshape(-1), _f64(hi).reshape(-1)
+        d, q = self.d, self.q
+        if lo.shape != (d,) or hi.shape != (d,):
+            raise ValueError("lo and hi must have shape [d]")
+        S = self.lipschitz_seeds(lo, hi) if seeds is None else _f64(seeds)
+        if S.ndim == 1:
+            S = S.reshape(1, -1)
+        if d < 1 or S.ndim != 2 or S.shape[1] != d:
+            raise ValueError("seeds must be [S, d] for the model's d")
+        opts, res = L.LipschitzOpts(), L.LipschitzResult()
+        if outputs is not None:
+            for o in outputs:
+                o = int(o)
+                if o < 0 or o >= 32:
+                    raise ValueError("output index out of range")
+                opts.output_mask |= 1 << o
+            if not opts.output_mask:
+                raise ValueError("outputs must name at least one output")
+        opts.top = int(top) if top is not None else 0
+        opts.max_eval = int(max_eval) if max_eval is not None else 0
+        opts.tol = float(tol) if tol is not None else 0.0
+        for a in range(d):
+            opts.lo[a], opts.hi[a] = lo[a], hi[a]
+        L.check(self._lib.sbo_lipschitz(self._ctx, C.byref(opts), S.shape[0], _ptr(S), C.byref(res)))
+        return {"L": np.array(res.L[:q]), "L_seed": np.array(res.L_seed[:q]), "x": np.array([list(res.x[o][:d]) for o in range(q)]),
+                "axis": np.array(res.axis[:q], dtype=np.int64), "sign": np.array(res.sign[:q], dtype=np.int64),
+                "seeds_used": int(res.seeds_used), "evaluations": int(res.evaluations), "problems": int(res.problems),
+                "converged": int(res.converged)}
 
     def mask(self, which: str, c: int = 0) -> np.ndarray:
         w = {"S": L.SBO_MASK_S, "U": L.SBO_MASK_U, "M": L.SBO_MASK_M, "G": L.SBO_MASK_G, "O": L.SBO_MASK_O}[which]
