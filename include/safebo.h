@@ -637,6 +637,42 @@ typedef struct sbo_lipschitz_result {
 int sbo_lipschitz(sbo_ctx* ctx, const sbo_lipschitz_opts* opts, int64_t n_seeds, const double* seeds /* [n_seeds][d] */,
                   sbo_lipschitz_result* result);
 
+/* ---- a greedy batch of k points under hallucinated observations (GP-BUCB) ---- */
+#define SBO_MAX_BATCH 64
+typedef struct sbo_batch_opts {
+  int32_t output;      /* whose variance is maximised, 0 .. q-1                                                                    */
+  int32_t k;           /* picks wanted, 1 .. SBO_MAX_BATCH                                                                          */
+  int32_t n_pending;   /* points conditioned on first and never picked; n_pending + k <= SBO_MAX_BATCH                              */
+  int32_t reserved;
+  double  min_std;     /* stop before a pick whose conditional std (un-normalised) is < min_std; >= 0, finite                       */
+} sbo_batch_opts;
+
+typedef struct sbo_batch_result {
+  int32_t n_selected, reserved;
+  int64_t index[SBO_MAX_BATCH];   /* into pool, in pick order; -1 past n_selected                                                  */
+  double  std[SBO_MAX_BATCH];     /* sqrt of the conditional variance the pick had when picked, times Y_std[output]                */
+} sbo_batch_result;
+
+/* Pick j of the batch is the arg-max over pool[m][d] (raw coordinates, as for sbo_mean_grad and sbo_candidates_points) of the
+ * posterior variance of `output` conditioned on the data, on pending[n_pending][d] (raw coordinates; in their order, first) and on
+ * picks 0 .. j-1 -- possible before any of them is measured, because a GP's posterior variance does not depend on the observed values.
+ * fp64 on the resident fp64 factor whatever the model dtype, as sbo_model_loo.  With the resident lower factor M (M^T M =
+ * inv(K + sn2 I)): v_0(x) = sf2 - ||M k_x||^2, k_x with the expanded distance of the reference (GP_Safe.py:119); v is not clipped
+ * inside the recursion.  Conditioning on a point z is the step sbo_model_append would take for it: with c(x) the current posterior
+ * covariance of x and z and s = v(z) + sn2 (kappa = sf2 + sn2 on the diagonal of the new row), v(x) <- v(x) - c(x)^2 / s.  Ties go
+ * to the lowest index; a pool point may be picked again (with noise its variance stays positive).  std[j] = sqrt(max(0, v)) Y_std[output];
+ * var_out[m] (may be NULL) is the pool's variance after the last conditioning -- every pick made is conditioned on --: max(0, v) Y_std^2.
+ * The value computed for a pool point does not depend on m or on the point's place in the list, bit for bit: every sum over the
+ * observations and the earlier picks runs in index order, two identical pool rows hold identical bits (the lower index wins), and two
+ * calls return the same bits.  Waits first for a deferred factorisation (one that fails: SBO_E_INVALID).  Reads the model only -- the
+ * growing factor is a scratch copy --: candidates, posterior, masks, plans, guard band, audit counters and options are untouched, and a
+ * sweep behind the call equals one before it bit for bit.  One host wait.  No collectives (the model is replicated: any rank may call).
+ * SBO_E_INVALID: a NULL ctx, opts, pool or result; m < 1 (or > 2^28); output outside [0, q); k < 1; n_pending < 0, or > 0 with a NULL
+ * pending; k + n_pending > SBO_MAX_BATCH; a non-finite coordinate; min_std negative or non-finite; a conditioning step with s <= 0.
+ * SBO_E_NO_MODEL without a model.  On any error the result is zeroed, its indices -1. */
+int sbo_batch_select(sbo_ctx* ctx, const sbo_batch_opts* opts, int64_t m, const double* pool /* [m][d] */,
+                     const double* pending /* [n_pending][d] or NULL */, double* var_out /* [m] or NULL */, sbo_batch_result* result);
+
 /* ---- plant evaluation ------------------------------------------ */
 /* The reference's William-Otto reactor (problems/WilliamOttoReactor_Problem.py:19-93), noise-free, for n input rows
  * u[n, 2] = (Fb, Tr): out[n, 3] = (get_objective, get_constraint1, get_constraint2), each the steady state of the six

@@ -239,7 +239,29 @@ class BO(GP):
                 best_x, best_std, self.expander_witness, first = xg, std_c, wit, False
         return best_x, best_std
 
-    _pair_max_eval = 1600     # evaluations of one point per refined pair (a pair costs two, and has twice the variables)
+    def Batch(self, k, pending=None, min_std=0.01):
+        """``k`` points to evaluate side by side -> (X [j, d], std [j]), j <= k: the greedy batch of ``SweepEngine.batch_select``
+        (GP-BUCB, "hallucinated observations") over the candidates of M u G_1 u .. u G_{q-1} of the current model.  Pick j has the
+        largest std of the objective conditioned on the data, on ``pending`` [P, d] (points whose experiments are still running) and
+        on the picks before it; the batch ends before a pick whose std is below ``min_std`` (default: the stopping threshold of the
+        reference's loop, test/test_SafeOpt.py:178).  With k = 1 and nothing pending the std is max(minimizer std, expander std)
+        of ``sweep()``.  The sets are those of the current model: they are NOT re-derived between the picks, which is the GP-BUCB
+        rule.  Ties go to the lowest flat index of the candidates, whereas the reference's loop prefers the expander on a tie.
+        This is not reference behaviour: the reference proposes one point per iteration."""
+        from .engine import SweepEngine
+        d = self.bound.shape[0]
+        _, k, _, pend, min_std = SweepEngine.batch_arguments(d, self.n_fun, np.zeros((1, d)), k, 0, pending, min_std)
+        self.sweep(want_masks=True)
+        member = self.engine.mask("M")
+        for c in range(1, self.n_fun):
+            member = member | self.engine.mask("G", c)
+        pool = self._all_points()[np.nonzero(member)[0]]          # (ascending flat index)
+        if pool.shape[0] == 0:
+            return np.empty((0, d)), np.empty(0)
+        out = self.engine.batch_select(pool, k, 0, pend, min_std)
+        return out["x"], out["std"]
+
+    _pair_max_eval = 1600    # evaluations of one point per refined pair (a pair costs two, and has twice the variables)
 
     def _sweep_L(self, res, c):
         """The Lipschitz constant the sweep used for constraint c (models/SafeOpt.py:110: the loop-leaked index under the quirk);

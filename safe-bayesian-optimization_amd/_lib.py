@@ -14,6 +14,7 @@ SBO_MAX_Q = 8
 SBO_MAX_N = 2048
 SBO_COMM_ID_BYTES = 128
 SBO_ROBUST_MAX_SCEN = 8
+SBO_MAX_BATCH = 64
 
 SBO_F64, SBO_F32 = 0, 1
 SBO_MEAN, SBO_UCB, SBO_LCB, SBO_VAR = 0, 1, 2, 3
@@ -143,6 +144,15 @@ class ModelLooResult(C.Structure):
                 ("z_max", C.c_double * SBO_MAX_Q), ("z_argmax", C.c_int32 * SBO_MAX_Q), ("outside", C.c_int32 * SBO_MAX_Q)]
 
 
+class BatchOpts(C.Structure):
+    _fields_ = [("output", C.c_int32), ("k", C.c_int32), ("n_pending", C.c_int32), ("reserved", C.c_int32), ("min_std", C.c_double)]
+
+
+class BatchResult(C.Structure):
+    _fields_ = [("n_selected", C.c_int32), ("reserved", C.c_int32), ("index", C.c_int64 * SBO_MAX_BATCH),
+                ("std", C.c_double * SBO_MAX_BATCH)]
+
+
 class Profile(C.Structure):
     _fields_ = [
         ("posterior_ms", C.c_double), ("classify_ms", C.c_double), ("expander_ms", C.c_double),
@@ -213,6 +223,7 @@ SYMBOLS = [
     ("sbo_refine_robust", C.c_int, [_P, C.POINTER(RefineRobustOpts), _P, _P, C.POINTER(RefineRobustResult)]),
     ("sbo_mean_grad", C.c_int, [_P, C.c_int64, _P, _P, _P]),
     ("sbo_lipschitz", C.c_int, [_P, C.POINTER(LipschitzOpts), C.c_int64, _P, C.POINTER(LipschitzResult)]),
+    ("sbo_batch_select", C.c_int, [_P, C.POINTER(BatchOpts), C.c_int64, _P, _P, _P, C.POINTER(BatchResult)]),
     ("sbo_plant_wo", C.c_int, [_P, C.c_int64, _P, _P]),
     ("sbo_profile_get", C.c_int, [_P, C.POINTER(Profile)]),
     ("sbo_set_option", C.c_int, [_P, C.c_char_p, C.c_int64]),

@@ -610,6 +610,60 @@ class SweepEngine:
                 "seeds_used": int(res.seeds_used), "evaluations": int(res.evaluations), "problems": int(res.problems),
                 "converged": int(res.converged)}
 
+    @staticmethod
+    def batch_arguments(d: int, q: int, points, k, output=0, pending=None, min_std=0.0):
+        """The checks of ``batch_select`` that need no device: (points [m, d], k, output, pending [P, d] or None, min_std), or
+        ValueError.  ``d`` / ``q`` < 1 (no model yet): the width of ``points`` and the range of ``output`` are the library's to check."""
+        pts = _f64(points)
+        if pts.ndim == 1:
+            pts = pts.reshape(1, -1)
+        if pts.ndim != 2 or pts.shape[0] < 1 or pts.shape[1] < 1 or (d >= 1 and pts.shape[1] != d):
+            raise ValueError("points must be [m, d] for the model's d, m >= 1")
+        for name, val in (("k", k), ("output", output)):
+            if isinstance(val, bool) or not isinstance(val, (int, np.integer)):
+                raise ValueError(f"{name} must be an integer")
+        if not 1 <= k <= L.SBO_MAX_BATCH:
+            raise ValueError(f"k must be in [1, {L.SBO_MAX_BATCH}]")
+        if output < 0 or (q >= 1 and output >= q):
+            raise ValueError("output out of range [0, q)")
+        pend = None
+        if pending is not None:
+            pend = _f64(pending)
+            if pend.ndim == 1:
+                pend = pend.reshape(1, -1)
+            if pend.ndim != 2 or pend.shape[1] != pts.shape[1]:
+                raise ValueError("pending must be [P, d]")
+            if pend.shape[0] == 0:
+                pend = None
+            elif k + pend.shape[0] > L.SBO_MAX_BATCH:
+                raise ValueError(f"k + len(pending) must be at most {L.SBO_MAX_BATCH}")
+        min_std = float(min_std)
+        if not np.isfinite(min_std) or min_std < 0.0:
+            raise ValueError("min_std must be finite and >= 0")
+        if not np.all(np.isfinite(pts)) or (pend is not None and not np.all(np.isfinite(pend))):
+            raise ValueError("points and pending must be finite")
+        return pts, int(k), int(output), pend, min_std
+
+    def batch_select(self, points, k: int, output: int = 0, pending=None, min_std: float = 0.0, return_var: bool = False) -> dict:
+        """A greedy batch of ``k`` rows of ``points`` [m, d] under hallucinated observations (``sbo_batch_select``, DESIGN.md section
+        17; the GP-BUCB rule): pick j maximises the posterior variance of ``output`` conditioned on the data, on ``pending`` [P, d]
+        (points whose experiments are still running: conditioned on first, never picked) and on picks 0 .. j-1 -- a GP's variance
+        does not depend on the observed values, so nothing has to be measured in between.  Ties go to the lowest index, a row may
+        be picked again, and the batch ends before a pick whose std is below ``min_std``.  Returns ``index`` [j] into ``points``,
+        ``x`` [j, d], ``std`` [j] (un-normalised, at the time of the pick) and, with ``return_var``, ``var`` [m]: the variance of
+        every row after the last pick has been conditioned on.  fp64 whatever the model dtype; the value of a row does not depend
+        on the list it stands in, bit for bit; nothing resident is touched."""
+        pts, k, output, pend, min_std = self.batch_arguments(self.d, self.q, points, k, output, pending, min_std)
+        opts, res = L.BatchOpts(output, k, 0 if pend is None else pend.shape[0], 0, min_std), L.BatchResult()
+        var = np.empty(pts.shape[0]) if return_var else None
+        L.check(self._lib.sbo_batch_select(self._ctx, C.byref(opts), pts.shape[0], _ptr(pts), _ptr(pend), _ptr(var), C.byref(res)))
+        j = int(res.n_selected)
+        index = np.array(res.index[:j], dtype=np.int64)
+        out = {"index": index, "x": pts[index].reshape(j, pts.shape[1]), "std": np.array(res.std[:j], dtype=np.float64)}
+        if return_var:
+            out["var"] = var
+        return out
+
     def mask(self, which: str, c: int = 0) -> np.ndarray:
         w = {"S": L.SBO_MASK_S, "U": L.SBO_MASK_U, "M": L.SBO_MASK_M, "G": L.SBO_MASK_G, "O": L.SBO_MASK_O}[which]
         out = np.empty(self.n_local, dtype=np.uint8)
