@@ -13,6 +13,7 @@ from safebo_amd.BayesRTOjax import DataStorage
 
 import refine_oracle as ro
 import refine_sets_oracle as rs
+from refine_shapes import _synthetic
 
 pytestmark = pytest.mark.gpu
 
@@ -155,13 +156,6 @@ def test_box_only_and_held_faces(engine):
                     else:
                         assert not (sign * -gx[a] > 1e-9 * (1 + np.abs(gx).max())), (a, face, x, gx)
     assert held > 0
-
-
-def _synthetic(n, d, seed):
-    rng = np.random.default_rng(seed)
-    X = rng.uniform(-1, 1, size=(n, d))
-    Y = np.stack([np.sum(X ** 2, axis=1) + 0.3 * np.sin(3 * X[:, 0]), 0.8 - np.sum(np.abs(X), axis=1) / d], axis=1)
-    return synthetic.make_dataset(X, Y, synthetic.default_hypopt(d, 2))
 
 
 @pytest.mark.parametrize("n,d", [(4, 2), (20, 2), (128, 2), (128, 4), (512, 2), (2048, 4)])
