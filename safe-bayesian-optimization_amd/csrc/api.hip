@@ -75,6 +75,17 @@ int factor_sync(sbo_ctx* c) {
   return SBO_OK;
 }
 
+int model_reader_check(const sbo_ctx* c, const char* who, bool need_f64) {
+  if (!c->has_model) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
+  if (need_f64 && c->dtype != SBO_F64) return fail(SBO_E_UNSUPPORTED, std::string(who) + " needs an fp64 model");
+  return SBO_OK;
+}
+int model_reader_begin(sbo_ctx* c, const char* who, bool need_f64) {
+  if (const int rc = model_reader_check(c, who, need_f64)) return rc;
+  SBO_HIP(hipSetDevice(c->device));
+  return factor_sync(c);
+}
+
 void release(DevBuf& b) { b.reset(); }
 
 int launch_soa_to_aos(sbo_ctx* c, const void* soa, void* aos);
@@ -570,9 +581,8 @@ int sbo_model_remove(sbo_ctx* c, int index) {
 int sbo_model_loo(sbo_ctx* c, double b, double* resid_out, double* var_out, sbo_model_loo_result* result) {
   if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
   if (!std::isfinite(b) || b < 0.0) return fail(SBO_E_INVALID, "b must be finite and >= 0");
-  if (!c->has_model || !c->Fplain.p) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
-  SBO_HIP(hipSetDevice(c->device));
-  { const int rcf = factor_sync(c); if (rcf) return rcf; }     // (the sums run over the resident factor)
+  if (!c->Fplain.p) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
+  if (const int rcb = model_reader_begin(c, "sbo_model_loo", false)) return rcb;     // (the sums run over the resident factor)
   const int n = c->mc.n, q = c->mc.q;
   const unsigned char* h = nullptr;
   const int rc = model_loo(c, b, resid_out || var_out, &h);

@@ -27,7 +27,6 @@ constexpr int kBatV0Threads = 1024;              // k_batch_v0: P points x 1024 
 constexpr int kBatV0Rows = 4;                    // ... rows of M per row lane and step
 constexpr size_t kBatV0Lds = 128 * 1024;         // ... its K(X, tile) image [n][P]: P = 32 up to n = 512, 16 up to 1024, 8 up to SBO_MAX_N
 constexpr int kBatMaxAug = SBO_MAX_N + SBO_MAX_BATCH;
-constexpr long long kBatNone = 0x7fffffffffffffffLL;
 
 struct BatchArgs {                               // by value (kernarg segment)
   int n, d, ld;                                  // observations of the model, input dimension, leading dimension n + n_pending + k of the scratch factor
@@ -60,30 +59,6 @@ __device__ __forceinline__ double bat_k(double sf2, const double* a, double asq,
 #pragma unroll
   for (int t = 0; t < D; ++t) dot += a[t] * b[t];
   return sf2 * exp(-0.5 * ((-2.0 * dot + asq) + bsq));
-}
-
-// (value, index) under the order "larger value first, then lower index"; kBatNone: no entry.  Selects on scalars.
-__device__ __forceinline__ void bat_take(double& bv, long long& bi, double v, long long i) {
-  const bool better = i != kBatNone && (bi == kBatNone || v > bv || (v == bv && i < bi));
-  bv = better ? v : bv;
-  bi = better ? i : bi;
-}
-// the best entry of the workgroup -> thread 0 (sv / si: one slot per wave)
-__device__ __forceinline__ void bat_block_best(double& bv, long long& bi, double* sv, long long* si) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double ov = __shfl_xor(bv, off);
-    const long long oi = __shfl_xor(bi, off);
-    bat_take(bv, bi, ov, oi);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
-  if (lane == 0) {
-    sv[wave] = bv;
-    si[wave] = bi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int w = 1; w < waves; ++w) bat_take(bv, bi, sv[w], si[w]);
 }
 
 // ---- the observations in scaled coordinates: As [ld][D] (rows >= n: filled as points are conditioned on), sq [ld] -----------------
@@ -237,7 +212,7 @@ __global__ __launch_bounds__(kBatThreads) void k_batch_pass(const BatchArgs A, i
                                                             double* __restrict__ partv, long long* __restrict__ parti) {
   __shared__ double sA[kBatChunk * D], sS[kBatChunk], sU[kBatChunk];
   __shared__ double sv[kBatThreads / 64];
-  __shared__ long long si[kBatThreads / 64];
+  __shared__ long long sk[kBatThreads / 64];
   if (st->stop || st->bad) return;                      // (the same for the whole grid)
   const int tid = threadIdx.x;
   const bool update = na >= 0;
@@ -247,7 +222,7 @@ __global__ __launch_bounds__(kBatThreads) void k_batch_pass(const BatchArgs A, i
   for (int t = 0; t < D; ++t) z[t] = update ? As[(size_t)na * D + t] : 0.0;
   if (update) zsq = sq[na];
   double bv = 0.0;
-  long long bi = kBatNone;
+  long long bi = kArgNone;                              // (value, index): arg_take's order, ties to the lowest index
   for (long long base = (long long)blockIdx.x * kBatThreads; base < m; base += (long long)gridDim.x * kBatThreads) {
     const long long i = base + tid;
     const bool on = i < m;
@@ -274,9 +249,9 @@ __global__ __launch_bounds__(kBatThreads) void k_batch_pass(const BatchArgs A, i
         v[i] = vn;
       }
     }
-    bat_take(bv, bi, vn, (on && vn == vn) ? i : kBatNone);   // (i ascends: the first of equals stays; a NaN is never taken)
+    arg_take(bv, bi, vn, (on && vn == vn) ? i : kArgNone);   // (a NaN is never taken)
   }
-  bat_block_best(bv, bi, sv, si);
+  arg_block_best(bv, bi, sv, sk);
   if (tid == 0) {
     partv[blockIdx.x] = bv;
     parti[blockIdx.x] = bi;
@@ -287,14 +262,14 @@ __global__ __launch_bounds__(kBatThreads) void k_batch_pass(const BatchArgs A, i
 __global__ __launch_bounds__(kBatThreads) void k_batch_finish(const BatchArgs A, int j, int nb, const double* __restrict__ partv,
                                                               const long long* __restrict__ parti, BatchState* __restrict__ st) {
   __shared__ double sv[kBatThreads / 64];
-  __shared__ long long si[kBatThreads / 64];
+  __shared__ long long sk[kBatThreads / 64];
   if (st->stop || st->bad) return;
   double bv = 0.0;
-  long long bi = kBatNone;
-  for (int k = threadIdx.x; k < nb; k += kBatThreads) bat_take(bv, bi, partv[k], parti[k]);
-  bat_block_best(bv, bi, sv, si);
+  long long bi = kArgNone;                              // (value, index): arg_take's order, ties to the lowest index
+  for (int k = threadIdx.x; k < nb; k += kBatThreads) arg_take(bv, bi, partv[k], parti[k]);
+  arg_block_best(bv, bi, sv, sk);
   if (threadIdx.x == 0) {
-    if (bi == kBatNone) {
+    if (bi == kArgNone) {
       st->bad = 1;
       return;
     }
@@ -316,16 +291,6 @@ __global__ __launch_bounds__(256) void k_batch_var(double ys2, long long m, doub
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-struct BatCarve {
-  unsigned char* base;
-  size_t off = 0;
-  template <class T> void take(T*& p, size_t count, size_t align = 256) {
-    off = (off + align - 1) / align * align;
-    p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += sizeof(T) * count;
-  }
-};
-
 struct BatBufs {
   double *Xn, *As, *sq, *M, *pool, *pend, *v, *u, *partv;
   long long* parti;
@@ -395,7 +360,9 @@ extern "C" int sbo_batch_select(sbo_ctx* c, const sbo_batch_opts* opts, int64_t 
     return fail(SBO_E_INVALID, "k >= 1, n_pending >= 0 and k + n_pending <= SBO_MAX_BATCH are required");
   if (opts->n_pending > 0 && !pending) return fail(SBO_E_INVALID, "pending is NULL");
   if (!std::isfinite(opts->min_std) || opts->min_std < 0.0) return fail(SBO_E_INVALID, "min_std must be finite and >= 0");
-  if (!c->has_model || !c->Fplain.p) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
+  int rc;
+  if (!c->Fplain.p) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
+  if ((rc = model_reader_check(c, "sbo_batch_select", false))) return rc;        // (d and q, which the checks below need)
   const ModelConst& mc = c->mc;
   const int n = mc.n, d = mc.d, o = opts->output, k = opts->k, np = opts->n_pending;
   if (o < 0 || o >= mc.q) return fail(SBO_E_INVALID, "output out of range [0, q)");
@@ -403,9 +370,7 @@ extern "C" int sbo_batch_select(sbo_ctx* c, const sbo_batch_opts* opts, int64_t 
     if (!std::isfinite(pool[t])) return fail(SBO_E_INVALID, "pool holds a non-finite coordinate");
   for (size_t t = 0; t < (size_t)np * d; ++t)
     if (!std::isfinite(pending[t])) return fail(SBO_E_INVALID, "pending holds a non-finite coordinate");
-  SBO_HIP(hipSetDevice(c->device));
-  int rc;
-  if ((rc = factor_sync(c))) return rc;                 // (the scratch factor starts as a copy of the resident one)
+  if ((rc = model_reader_begin(c, "sbo_batch_select", false))) return rc;        // (the scratch factor starts as a copy of the resident one)
   BatchArgs A{};
   A.n = n;
   A.d = d;
@@ -421,10 +386,10 @@ extern "C" int sbo_batch_select(sbo_ctx* c, const sbo_batch_opts* opts, int64_t 
   A.min_std = opts->min_std;
   // scratch: X_norm [n][d] | scaled observations [ld][dpad] and their squares [ld] | the factor [ld][ld] | pool [m][d] | pending |
   // v [m] | u [ld] | the partials | the state block
-  const int D = mc.dpad <= 2 ? 2 : mc.dpad <= 4 ? 4 : 8;
+  const int D = mc.dpad;
   const size_t ld = (size_t)A.ld, nbmax = 8192;
   BatBufs B;
-  auto layout = [&](BatCarve cv) {
+  auto layout = [&](Carve cv) {
     cv.take(B.Xn, (size_t)n * d);
     cv.take(B.As, ld * D);
     cv.take(B.sq, ld);
@@ -438,8 +403,7 @@ extern "C" int sbo_batch_select(sbo_ctx* c, const sbo_batch_opts* opts, int64_t 
     cv.take(B.st, 1);
     return cv.off;
   };
-  if ((rc = ensure(c->batchbuf, layout({nullptr})))) return rc;
-  layout({(unsigned char*)c->batchbuf.p});
+  if ((rc = carve(c->batchbuf, layout, 256))) return rc;
   hipStream_t st = c->stream;
   BatchState init{};
   batch_clear(&init.res);
@@ -449,11 +413,7 @@ extern "C" int sbo_batch_select(sbo_ctx* c, const sbo_batch_opts* opts, int64_t 
   if (np) SBO_HIP(hipMemcpyAsync(B.pend, pending, sizeof(double) * (size_t)np * d, hipMemcpyHostToDevice, st));
   SBO_HIP(hipMemcpy2DAsync(B.M, sizeof(double) * ld, (const double*)c->Fplain.p + (size_t)o * c->f_cap * c->f_cap, sizeof(double) * c->f_cap,
                            sizeof(double) * n, n, hipMemcpyDeviceToDevice, st));
-  switch (D) {
-    case 2: rc = batch_enqueue<2>(c, A, B, m, k, np, var_out != nullptr); break;
-    case 4: rc = batch_enqueue<4>(c, A, B, m, k, np, var_out != nullptr); break;
-    default: rc = batch_enqueue<8>(c, A, B, m, k, np, var_out != nullptr); break;
-  }
+  rc = with_dpad(D, [&](auto DD) { return batch_enqueue<DD()>(c, A, B, m, k, np, var_out != nullptr); });
   if (rc) {
     (void)hipStreamSynchronize(st);                     // (nothing of the call may still read the caller's arrays)
     return rc;

@@ -256,6 +256,68 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
+// Sums of cnt <= kMaxD + 1 per-thread values over the workgroup: butterfly within a wave, then the waves in order (thread 0)
+// -> out[].  part: [blockDim.x / 64][kMaxD + 1].
+__device__ __forceinline__ void block_sum_cols(const double* v, int cnt, double (*part)[kMaxD + 1], double* out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+#pragma unroll
+  for (int k = 0; k < kMaxD + 1; ++k) {
+    if (k < cnt) {
+      double s = v[k];
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+      if (lane == 0) part[wave][k] = s;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int k = 0; k < cnt; ++k) {
+      double s = 0.0;
+      for (int w = 0; w < nw; ++w) s += part[w][k];
+      out[k] = s;
+    }
+  __syncthreads();
+}
+
+// The running best of (value, key) pairs -- a double and a signed 64-bit key -- under the total order "larger value first, then smaller key"; key kArgNone: no entry (a
+// caller passes it for what must never win: a NaN, a masked element).  The order is total, so the winner does not depend on how a
+// reduction is associated.  An arg-min negates the value; whatever else decides a tie is folded into the key.  The update is two
+// selects on plain scalars: written as a comparator with early returns it lost the update of the value.
+constexpr long long kArgNone = 0x7fffffffffffffffLL;
+__device__ __forceinline__ void arg_take(double& bv, long long& bk, double v, long long k) {
+  const bool better = k != kArgNone && (bk == kArgNone || v > bv || (v == bv && k < bk));
+  bv = better ? v : bv;
+  bk = better ? k : bk;
+}
+// the best entry of the workgroup -> thread 0: butterfly within a wave, then the waves in order (sv / sk: one slot per wave)
+__device__ __forceinline__ void arg_block_best(double& bv, long long& bk, double* sv, long long* sk) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double ov = __shfl_xor(bv, off);
+    const long long ok = __shfl_xor(bk, off);
+    arg_take(bv, bk, ov, ok);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+  if (lane == 0) {
+    sv[wave] = bv;
+    sk[wave] = bk;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < waves; ++w) arg_take(bv, bk, sv[w], sk[w]);
+}
+// ... -> every thread; the slots are free again when it returns
+__device__ __forceinline__ void arg_block_best_all(double& bv, long long& bk, double* sv, long long* sk) {
+  arg_block_best(bv, bk, sv, sk);
+  if (threadIdx.x == 0) {
+    sv[0] = bv;
+    sk[0] = bk;
+  }
+  __syncthreads();
+  bv = sv[0];
+  bk = sk[0];
+  __syncthreads();
+}
+
 // Lipschitz key of output o from K1b's per-wave partials: Lmax[o] = max (values >= 0, so the bit pattern orders them);
 // one workgroup of 256 threads, `sh`: four doubles of LDS
 __device__ __forceinline__ void lmax_reduce_body(int o, double* sh, const double* __restrict__ Lpart, int per_out,

@@ -255,13 +255,14 @@ extern "C" int sbo_nll_batch(sbo_ctx* c, int n, int d, const double* X_norm, con
   const size_t lds = sizeof(double) * ((size_t)n * d + 2 * (size_t)n);
   if (lds > 150 * 1024) return fail(SBO_E_UNSUPPORTED, "n * d too large for the fit kernel's LDS staging");
   int rc;
-  const size_t in_bytes = sizeof(double) * ((size_t)n * d + n + (size_t)P * (d + 2) + P);
-  if ((rc = ensure(c->fitbuf, in_bytes))) return rc;
+  double *dX, *dy, *dh, *dout;
+  auto layout = [&](Carve cv) {
+    cv.take(dX, (size_t)n * d); cv.take(dy, n);
+    cv.take(dh, (size_t)P * (d + 2)); cv.take(dout, P);
+    return cv.off;
+  };
+  if ((rc = carve(c->fitbuf, layout))) return rc;
   if ((rc = ensure(c->fitwork, sizeof(double) * (size_t)P * n * n))) return rc;
-  double* dX = (double*)c->fitbuf.p;
-  double* dy = dX + (size_t)n * d;
-  double* dh = dy + n;
-  double* dout = dh + (size_t)P * (d + 2);
   SBO_HIP(hipMemcpyAsync(dX, X_norm, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(dh, hyper, sizeof(double) * (size_t)P * (d + 2), hipMemcpyHostToDevice, c->stream));
@@ -291,15 +292,16 @@ extern "C" int sbo_fit_de(sbo_ctx* c, int n, int d, const double* X_norm, const 
   const size_t lds = sizeof(double) * ((size_t)n * d + 2 * (size_t)n);
   if (lds > 150 * 1024) return fail(SBO_E_UNSUPPORTED, "n * d too large for the fit kernel's LDS staging");
   int rc;
-  const size_t in_elems = (size_t)n * d + n + 2 * (size_t)P * D + 2 * (size_t)P + 2 * (size_t)D;
-  if ((rc = ensure(c->fitbuf, sizeof(double) * in_elems))) return rc;
+  double *dX, *dy, *dpop[2], *den[2], *dlo, *dhi;
+  auto layout = [&](Carve cv) {
+    cv.take(dX, (size_t)n * d); cv.take(dy, n);
+    cv.take(dpop[0], (size_t)P * D); cv.take(dpop[1], (size_t)P * D);
+    cv.take(den[0], P); cv.take(den[1], P);
+    cv.take(dlo, D); cv.take(dhi, D);
+    return cv.off;
+  };
+  if ((rc = carve(c->fitbuf, layout))) return rc;
   if ((rc = ensure(c->fitwork, sizeof(double) * (size_t)P * n * n))) return rc;
-  double* dX = (double*)c->fitbuf.p;
-  double* dy = dX + (size_t)n * d;
-  double* dpop[2] = {dy + n, dy + n + (size_t)P * D};
-  double* den[2] = {dpop[1] + (size_t)P * D, dpop[1] + (size_t)P * D + P};
-  double* dlo = den[1] + P;
-  double* dhi = dlo + D;
   SBO_HIP(hipMemcpyAsync(dX, X_norm, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(dpop[0], init_pop, sizeof(double) * (size_t)P * D, hipMemcpyHostToDevice, c->stream));
@@ -575,14 +577,14 @@ extern "C" int sbo_nll_grad_batch(sbo_ctx* c, int n, int d, const double* X_norm
   const size_t lds = nll_grad_lds(n, d);
   if (lds > 150 * 1024) return fail(SBO_E_UNSUPPORTED, "n * d too large for the fit kernel's LDS staging");
   int rc;
-  const size_t in_elems = (size_t)n * d + n + 2 * (size_t)P * D + P;
-  if ((rc = ensure(c->fitbuf, sizeof(double) * in_elems))) return rc;
+  double *dX, *dy, *dh, *dg, *dout;
+  auto layout = [&](Carve cv) {
+    cv.take(dX, (size_t)n * d); cv.take(dy, n);
+    cv.take(dh, (size_t)P * D); cv.take(dg, (size_t)P * D); cv.take(dout, P);
+    return cv.off;
+  };
+  if ((rc = carve(c->fitbuf, layout))) return rc;
   if ((rc = ensure(c->fitwork, sizeof(double) * (size_t)P * n * n))) return rc;
-  double* dX = (double*)c->fitbuf.p;
-  double* dy = dX + (size_t)n * d;
-  double* dh = dy + n;
-  double* dg = dh + (size_t)P * D;
-  double* dout = dg + (size_t)P * D;
   SBO_HIP(hipMemcpyAsync(dX, X_norm, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(dh, hyper, sizeof(double) * (size_t)P * D, hipMemcpyHostToDevice, c->stream));
@@ -612,23 +614,20 @@ extern "C" int sbo_fit_local(sbo_ctx* c, int n, int d, int q, const double* X_no
   if (lds > 150 * 1024) return fail(SBO_E_UNSUPPORTED, "n * d too large for the fit kernel's LDS staging");
   const size_t M = (size_t)q * P;
   int rc;
-  const size_t in_elems = (size_t)n * d + (size_t)q * n + (size_t)P * D + 2 * (size_t)D + M * D + 2 * M + 3 * M;
-  if ((rc = ensure(c->fitbuf, sizeof(double) * in_elems))) return rc;
+  double *dX, *dy, *dst, *dlo, *dhi, *dh, *df, *dpg;
+  int *dit, *dev, *dstat;                              // (read back as one block of 3 M)
+  auto layout = [&](Carve cv) {
+    cv.take(dX, (size_t)n * d); cv.take(dy, (size_t)q * n);
+    cv.take(dst, (size_t)P * D); cv.take(dlo, D); cv.take(dhi, D);
+    cv.take(dh, M * D); cv.take(df, M); cv.take(dpg, M);
+    cv.take(dit, M); cv.take(dev, M); cv.take(dstat, M);
+    return cv.off;
+  };
+  if ((rc = carve(c->fitbuf, layout))) return rc;
   if ((rc = ensure(c->fitwork, sizeof(double) * M * n * n))) return rc;
   std::vector<double> yT((size_t)q * n);               // one contiguous column per output
   for (int i = 0; i < n; ++i)
     for (int o = 0; o < q; ++o) yT[(size_t)o * n + i] = Y_norm[(size_t)i * q + o];
-  double* dX = (double*)c->fitbuf.p;
-  double* dy = dX + (size_t)n * d;
-  double* dst = dy + (size_t)q * n;
-  double* dlo = dst + (size_t)P * D;
-  double* dhi = dlo + D;
-  double* dh = dhi + D;
-  double* df = dh + M * D;
-  double* dpg = df + M;
-  int* dit = reinterpret_cast<int*>(dpg + M);
-  int* dev = dit + M;
-  int* dstat = dev + M;
   SBO_HIP(hipMemcpyAsync(dX, X_norm, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(dy, yT.data(), sizeof(double) * (size_t)q * n, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(dst, starts, sizeof(double) * (size_t)P * D, hipMemcpyHostToDevice, c->stream));
@@ -684,30 +683,24 @@ int fit_batch(sbo_ctx* c, int n, int d, int q, const double* X_norm, const doubl
   int rc;
   // X | yT | pop[2] | energy[2] | lo | hi | final x, nll, DE best x, nll (read back as one block) | polish x, f, pgnorm |
   // polish iters, evals, status, polished (ints)
-  const size_t res_elems = 2 * ((size_t)q * D + q);
-  const size_t in_elems = (size_t)n * d + (size_t)q * n + 2 * M * D + 2 * M + 2 * (size_t)D + res_elems + (size_t)q * D + 2 * (size_t)q + 2 * (size_t)q;
-  if ((rc = ensure(c->fitbuf, sizeof(double) * in_elems))) return rc;
+  double *dX, *dy, *dpop[2], *den[2], *dlo, *dhi, *dfin_x, *dfin_f, *dde_x, *dde_f, *dloc_x, *dloc_f, *dloc_pg;
+  int *dit, *dev, *dstat, *dpolished;                  // (read back as one block of 4 q)
+  auto layout = [&](Carve cv) {
+    cv.take(dX, (size_t)n * d); cv.take(dy, (size_t)q * n);
+    cv.take(dpop[0], M * D); cv.take(dpop[1], M * D);
+    cv.take(den[0], M); cv.take(den[1], M);
+    cv.take(dlo, D); cv.take(dhi, D);
+    cv.take(dfin_x, (size_t)q * D); cv.take(dfin_f, q); cv.take(dde_x, (size_t)q * D); cv.take(dde_f, q);
+    cv.take(dloc_x, (size_t)q * D); cv.take(dloc_f, q); cv.take(dloc_pg, q);
+    cv.take(dit, q); cv.take(dev, q); cv.take(dstat, q); cv.take(dpolished, q);
+    return cv.off;
+  };
+  if ((rc = carve(c->fitbuf, layout))) return rc;
+  const size_t res_elems = (size_t)(dloc_x - dfin_x);  // final x, nll, DE best x, nll
   if ((rc = ensure(c->fitwork, sizeof(double) * M * n * n))) return rc;
   std::vector<double> yT((size_t)q * n);               // one contiguous column per output
   for (int i = 0; i < n; ++i)
     for (int o = 0; o < q; ++o) yT[(size_t)o * n + i] = Y_norm[(size_t)i * q + o];
-  double* dX = (double*)c->fitbuf.p;
-  double* dy = dX + (size_t)n * d;
-  double* dpop[2] = {dy + (size_t)q * n, dy + (size_t)q * n + M * D};
-  double* den[2] = {dpop[1] + M * D, dpop[1] + M * D + M};
-  double* dlo = den[1] + M;
-  double* dhi = dlo + D;
-  double* dfin_x = dhi + D;
-  double* dfin_f = dfin_x + (size_t)q * D;
-  double* dde_x = dfin_f + q;
-  double* dde_f = dde_x + (size_t)q * D;
-  double* dloc_x = dde_f + q;
-  double* dloc_f = dloc_x + (size_t)q * D;
-  double* dloc_pg = dloc_f + q;
-  int* dit = reinterpret_cast<int*>(dloc_pg + q);
-  int* dev = dit + q;
-  int* dstat = dev + q;
-  int* dpolished = dstat + q;
   SBO_HIP(hipMemcpyAsync(dX, X_norm, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(dy, yT.data(), sizeof(double) * (size_t)q * n, hipMemcpyHostToDevice, c->stream));
   for (int o = 0; o < q; ++o)                          // every output starts from the caller's population

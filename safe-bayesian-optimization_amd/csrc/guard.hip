@@ -368,13 +368,8 @@ static int launch_ref(sbo_ctx* c, hipStream_t st, const double* pts, long long N
 
 int guard_exact_list(sbo_ctx* c, const double* pts, long long N, double* mean_out, double* var_out) {
   if (N <= 0) return SBO_OK;
-  if ((c->last_k1 == 4 || c->last_k1 == 6) && ref_direct(c)) {
-    switch (c->mc.dpad) {
-      case 2: return launch_ref<2>(c, c->stream, pts, N, 0, mean_out, var_out);
-      case 4: return launch_ref<4>(c, c->stream, pts, N, 0, mean_out, var_out);
-      default: return launch_ref<8>(c, c->stream, pts, N, 0, mean_out, var_out);
-    }
-  }
+  if ((c->last_k1 == 4 || c->last_k1 == 6) && ref_direct(c))
+    return with_dpad(c->mc.dpad, [&](auto D) { return launch_ref<D()>(c, c->stream, pts, N, 0, mean_out, var_out); });
   return launch_posterior_on_list(c, pts, N, mean_out, var_out);
 }
 
@@ -382,11 +377,10 @@ int guard_exact_grad_list(sbo_ctx* c, const double* pts, long long N, double* gr
   if (N <= 0) return SBO_OK;
   if (c->dtype != SBO_F64) return fail(SBO_E_UNSUPPORTED, "internal: gradient list is an fp64 path");
   const unsigned nb = (unsigned)std::max<long long>(1, std::min<long long>((N + 255) / 256, 4096));
-  switch (c->mc.dpad) {
-    case 2: hipLaunchKernelGGL(k_grad_list<2>, dim3(nb), dim3(256), 0, c->stream, c->mc, pts, N, (const double*)c->As.p, (const double*)c->sqA.p, (const double*)c->alpha.p, (const double*)c->Xn.p, grad_out); break;
-    case 4: hipLaunchKernelGGL(k_grad_list<4>, dim3(nb), dim3(256), 0, c->stream, c->mc, pts, N, (const double*)c->As.p, (const double*)c->sqA.p, (const double*)c->alpha.p, (const double*)c->Xn.p, grad_out); break;
-    default: hipLaunchKernelGGL(k_grad_list<8>, dim3(nb), dim3(256), 0, c->stream, c->mc, pts, N, (const double*)c->As.p, (const double*)c->sqA.p, (const double*)c->alpha.p, (const double*)c->Xn.p, grad_out); break;
-  }
+  with_dpad(c->mc.dpad, [&](auto D) {
+    hipLaunchKernelGGL(k_grad_list<D()>, dim3(nb), dim3(256), 0, c->stream, c->mc, pts, N, (const double*)c->As.p, (const double*)c->sqA.p,
+                       (const double*)c->alpha.p, (const double*)c->Xn.p, grad_out);
+  });
   SBO_HIP(hipGetLastError());
   return SBO_OK;
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/safebo.h"
 
@@ -566,6 +567,43 @@ void release(DevBuf& b);
 void drain_streams(sbo_ctx* c);
 int col_decide_resident(int* wg_per_cu);   // sets.hip: the runtime's occupancy of k_col_decide, workgroups per CU
 int factor_sync(sbo_ctx* c);      // wait for a deferred factorisation (sbo_ctx::factor_pending); SBO_E_INVALID when invK was not positive definite   // after a failed call: wait for whatever it left on the main and side streams
+
+// What the calls that only read the resident model do once their arguments are checked (sbo_refine*, sbo_mean_grad, sbo_lipschitz,
+// sbo_batch_select, sbo_model_loo): no model -> SBO_E_NO_MODEL, `need_f64` and an fp32 model -> SBO_E_UNSUPPORTED ("<who> needs an
+// fp64 model"), then the device is selected and a deferred factor chain waited for (which also delivers the verdict on a caller's invK).
+// model_reader_check is the first half alone, for a call that needs d and q to check its arguments before it waits.
+int model_reader_check(const sbo_ctx* c, const char* who, bool need_f64);
+int model_reader_begin(sbo_ctx* c, const char* who, bool need_f64);
+
+// Hands out consecutive blocks of one buffer, each at a multiple of `align` bytes.  A layout is one sequence of take() calls, run
+// once on a null base for the size and once on the buffer for the pointers.  `floor`: the least alignment of every block.
+struct Carve {
+  unsigned char* base;
+  size_t off = 0, floor = 1;
+  template <class T> void take(T*& p, size_t count, size_t align = alignof(T)) {
+    align = align > floor ? align : floor;
+    off = (off + align - 1) / align * align;
+    p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += sizeof(T) * count;
+  }
+};
+// the two passes of `layout` (Carve -> the offset it ends at) over a buffer that grows to hold it
+template <class F> int carve(DevBuf& buf, F&& layout, size_t floor = 1) {
+  const size_t bytes = layout(Carve{nullptr, 0, floor});
+  if (int rc = ensure(buf, bytes)) return rc;
+  if (layout(Carve{(unsigned char*)buf.p, 0, floor}) != bytes) return fail(SBO_E_INVALID, "a scratch layout changed between its two passes");
+  return SBO_OK;
+}
+
+// f(std::integral_constant<int, D>{}) for the padded input dimension D = 2, 4 or 8 (ModelConst::dpad): a launch line is written once,
+// as a generic lambda `[&](auto D) { ... k<D()> ... }`
+template <class F> auto with_dpad(int dpad, F&& f) {
+  switch (dpad) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
 
 // the posterior inside a sweep, without synchronisation or timing (api.hip); `out` (nullptr: not wanted) is reset first
 int posterior_enqueue(sbo_ctx* c, const PostRequest& req, PostOutcome* out);

@@ -114,15 +114,12 @@ __global__ void k_lip_flag(const LipArgs* __restrict__ Ap, const double* __restr
 
 // ---- the `top` seeds of largest s g_a per (output, axis, sign), ties to the lowest seed -> pick[((o d + a) 2 + sg) top + t] -------
 // One workgroup per (o, a, sg); round t takes the best seed behind round t - 1's in the order (value descending, index ascending).
-// (Both arg-max scans below keep their running best with selects on plain scalars: a comparator with early returns over a struct of
-// (value, axis, sign, entry) came out of the compiler without the update of the value.)
-constexpr long long kLipNone = 0x7fffffffffffffffLL;
+// (The arg-max is arg_take / arg_block_best_all of device_common.hpp, the seed as the key: selects on plain scalars -- a comparator
+// with early returns over a struct of (value, axis, sign, entry) came out of the compiler without the update of the value.)
 __global__ __launch_bounds__(kLipThreads) void k_lip_top(const LipArgs* __restrict__ Ap, const double* __restrict__ grad,
                                                          const int* __restrict__ use, int* __restrict__ pick) {
-  __shared__ double sv[kLipThreads];
-  __shared__ long long si[kLipThreads];
-  __shared__ double pv;
-  __shared__ long long pi;
+  __shared__ double sv[kLipWaves];
+  __shared__ long long sk[kLipWaves];
   const LipArgs& A = *Ap;
   const int d = A.mc.d, q = A.mc.q, tid = threadIdx.x;
   const int sg = blockIdx.x & 1, a = (blockIdx.x >> 1) % d, o = (blockIdx.x >> 1) / d;
@@ -130,90 +127,59 @@ __global__ __launch_bounds__(kLipThreads) void k_lip_top(const LipArgs* __restri
   const bool asked = ((A.mask >> o) & 1) && A.hi[a] - A.lo[a] > 0.0;
   const double sgn = sg ? -1.0 : 1.0;
   bool more = asked;
+  double lastv = 0.0;                                 // the pick of the round before
+  long long lasti = -1;
   for (int t = 0; t < A.top; ++t) {
     if (!more) {                                      // (the same for the whole workgroup)
       if (tid == 0) out[t] = -1;
       continue;
     }
     double bv = 0.0;
-    long long bi = kLipNone;
-    const double lastv = t ? pv : 0.0;
-    const long long lasti = t ? pi : -1;
+    long long bk = kArgNone;
     for (long long s = tid; s < A.nS; s += kLipThreads) {
       const double v = sgn * grad[((size_t)s * q + o) * d + a];
       const bool open = use[s] != 0 && v == v && (t == 0 || v < lastv || (v == lastv && s > lasti));
-      const bool better = open && (bi == kLipNone || v > bv);   // (s ascends: the first of equals stays)
-      bv = better ? v : bv;
-      bi = better ? s : bi;
+      arg_take(bv, bk, v, open ? s : kArgNone);
     }
-    sv[tid] = bv;
-    si[tid] = bi;
-    __syncthreads();
-    if (tid == 0) {
-      double v = 0.0;
-      long long i = kLipNone;
-      for (int k = 0; k < kLipThreads; ++k) {
-        const bool better = si[k] != kLipNone && (i == kLipNone || sv[k] > v || (sv[k] == v && si[k] < i));
-        v = better ? sv[k] : v;
-        i = better ? si[k] : i;
-      }
-      pv = v;
-      pi = i;
-      out[t] = i == kLipNone ? -1 : (int)i;
-    }
-    __syncthreads();
-    more = pi != kLipNone;
+    arg_block_best_all(bv, bk, sv, sk);
+    more = bk != kArgNone;
+    if (tid == 0) out[t] = more ? (int)bk : -1;
+    lastv = bv;
+    lasti = bk;
   }
 }
 
 // ---- largest |g_a| of output o over the usable entries [0, E), all axes: ties to the lowest axis, then sign +, then the lowest entry
 // (seeds stand before the iterates).  The order behind the value is one key: (2 axis + (sign < 0)) << 40 | entry ----------------------
 struct LipBest {
-  double v;                  // -1: none
-  unsigned long long key;
+  double v;
+  long long key;             // kArgNone: none
 };
-__device__ __forceinline__ int lip_key_axis(unsigned long long key) { return (int)(key >> 41); }
-__device__ __forceinline__ int lip_key_neg(unsigned long long key) { return (int)((key >> 40) & 1); }
-__device__ __forceinline__ long long lip_key_entry(unsigned long long key) { return (long long)(key & ((1ull << 40) - 1)); }
-__device__ LipBest lip_argmax(const LipArgs& A, int o, long long E, const double* grad, const int* use, double* sv,
-                              unsigned long long* sk) {
-  const int d = A.mc.d, q = A.mc.q, tid = threadIdx.x;
-  double bv = -1.0;
-  unsigned long long bk = ~0ull;
-  for (long long e = tid; e < E; e += kLipThreads) {
+__device__ __forceinline__ int lip_key_axis(long long key) { return (int)(key >> 41); }
+__device__ __forceinline__ int lip_key_neg(long long key) { return (int)((key >> 40) & 1); }
+__device__ __forceinline__ long long lip_key_entry(long long key) { return key & ((1LL << 40) - 1); }
+__device__ LipBest lip_argmax(const LipArgs& A, int o, long long E, const double* grad, const int* use, double* sv, long long* sk) {
+  const int d = A.mc.d, q = A.mc.q;
+  double bv = 0.0;
+  long long bk = kArgNone;
+  for (long long e = threadIdx.x; e < E; e += kLipThreads) {
     const bool on = use[e] != 0;
     for (int a = 0; a < d; ++a) {
       const double g = grad[((size_t)e * q + o) * d + a];
-      const double v = fabs(g);                       // (a NaN fails both comparisons)
-      const unsigned long long key = ((unsigned long long)(2 * a + (g < 0.0 ? 1 : 0)) << 40) | (unsigned long long)e;
-      const bool better = on && (v > bv || (v == bv && key < bk));
-      bv = better ? v : bv;
-      bk = better ? key : bk;
+      const double v = fabs(g);
+      const long long key = ((long long)(2 * a + (g < 0.0 ? 1 : 0)) << 40) | e;
+      arg_take(bv, bk, v, (on && v == v) ? key : kArgNone);      // (a NaN is never taken)
     }
   }
-  sv[tid] = bv;
-  sk[tid] = bk;
-  __syncthreads();
-  if (tid == 0) {
-    for (int k = 1; k < kLipThreads; ++k) {
-      const bool better = sv[k] > bv || (sv[k] == bv && sk[k] < bk);
-      bv = better ? sv[k] : bv;
-      bk = better ? sk[k] : bk;
-    }
-    sv[0] = bv;
-    sk[0] = bk;
-  }
-  __syncthreads();
-  const LipBest b{sv[0], sk[0]};
-  __syncthreads();
-  return b;
+  arg_block_best_all(bv, bk, sv, sk);
+  return LipBest{bv, bk};
 }
 
 // one workgroup per output: L_seed over the seeds
 __global__ __launch_bounds__(kLipThreads) void k_lip_seedmax(const LipArgs* __restrict__ Ap, const double* __restrict__ grad,
                                                              const int* __restrict__ use, double* __restrict__ Lseed) {
-  __shared__ double sv[kLipThreads];
-  __shared__ unsigned long long sk[kLipThreads];
+  __shared__ double sv[kLipWaves];
+  __shared__ long long sk[kLipWaves];
   const LipArgs& A = *Ap;
   const int o = blockIdx.x;
   if (!((A.mask >> o) & 1)) {
@@ -221,7 +187,7 @@ __global__ __launch_bounds__(kLipThreads) void k_lip_seedmax(const LipArgs* __re
     return;
   }
   const LipBest b = lip_argmax(A, o, A.nS, grad, use, sv, sk);
-  if (threadIdx.x == 0) Lseed[o] = b.v >= 0.0 ? b.v : 0.0;
+  if (threadIdx.x == 0) Lseed[o] = b.key != kArgNone ? b.v : 0.0;
 }
 
 // one workgroup per output: the result over seeds and final iterates; workgroup 0 also sums the solver's counters
@@ -230,8 +196,8 @@ __global__ __launch_bounds__(kLipThreads) void k_lip_final(const LipArgs* __rest
                                                            const double* __restrict__ Lseed, const int* __restrict__ nev,
                                                            const int* __restrict__ conv, const unsigned long long* __restrict__ count,
                                                            sbo_lipschitz_result* __restrict__ res) {
-  __shared__ double sv[kLipThreads];
-  __shared__ unsigned long long sk[kLipThreads];
+  __shared__ double sv[kLipWaves];
+  __shared__ long long sk[kLipWaves];
   const LipArgs& A = *Ap;
   const int o = blockIdx.x, d = A.mc.d;
   if (o == 0 && threadIdx.x == 0) {
@@ -252,7 +218,7 @@ __global__ __launch_bounds__(kLipThreads) void k_lip_final(const LipArgs* __rest
   const LipBest b = lip_argmax(A, o, A.nS + A.nP, grad, use, sv, sk);
   if (threadIdx.x == 0) {
     res->L_seed[o] = Lseed[o];
-    if (b.v >= 0.0) {
+    if (b.key != kArgNone) {
       res->L[o] = b.v;
       res->axis[o] = lip_key_axis(b.key);
       res->sign[o] = lip_key_neg(b.key) ? -1 : 1;
@@ -262,27 +228,6 @@ __global__ __launch_bounds__(kLipThreads) void k_lip_final(const LipArgs* __rest
 }
 
 // ---- stage 2: maximise s g_a over the box from one seed --------------------------------------------------------------------------
-// sums of cnt per-thread values over the workgroup: butterfly within a wave, then the waves in order (thread 0) -> out[]
-__device__ __forceinline__ void lip_block_sum(const double* v, int cnt, double (*part)[kMaxD + 1], double* out) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kMaxD + 1; ++k) {
-    if (k < cnt) {
-      double s = v[k];
-      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-      if (lane == 0) part[wave][k] = s;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int k = 0; k < cnt; ++k) {
-      double s = 0.0;
-      for (int w = 0; w < kLipWaves; ++w) s += part[w][k];
-      out[k] = s;
-    }
-  __syncthreads();
-}
-
 struct LipState {
   PbfgsState<kMaxD> s;
   double D2[kMaxD], span[kMaxD];
@@ -333,7 +278,7 @@ __device__ __noinline__ bool lip_advance(LipState& S, const LipArgs& A, double F
 }
 
 // One workgroup per problem p = ((o d + a) 2 + sg) top + t, from seed pick[p] (-1: no problem).  F = -s g_a / L_seed[o]; an
-// evaluation is d + 1 workgroup sums over the observations (lane-serial partials, lip_block_sum).  kLds: X_norm and alpha_o are
+// evaluation is d + 1 workgroup sums over the observations (lane-serial partials, block_sum_cols).  kLds: X_norm and alpha_o are
 // staged in LDS first; the arithmetic is the same either way.  The final iterate goes to pts[nS + p], its usability to use[nS + p].
 template <bool kLds>
 __global__ __launch_bounds__(kLipThreads) void k_lipschitz(const LipArgs* __restrict__ Ap, const double* __restrict__ alpha,
@@ -409,7 +354,7 @@ __global__ __launch_bounds__(kLipThreads) void k_lipschitz(const LipArgs* __rest
       for (int b = 0; b < kMaxD; ++b)
         if (b < d) acc[1 + b] += ak * (da * diff[b] * ie[b] - (b == ax ? 1.0 : 0.0));
     }
-    lip_block_sum(acc, d + 1, part, red);
+    block_sum_cols(acc, d + 1, part, red);
     if (tid == 0) {
       const double Ca = mc.Y_std[o] * mc.inv_ell[o][ax] / mc.X_std[ax];
       double gF[kMaxD];
@@ -427,38 +372,15 @@ __global__ __launch_bounds__(kLipThreads) void k_lipschitz(const LipArgs* __rest
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-struct LipCarve {
-  unsigned char* base;
-  size_t off = 0;
-  template <class T> void take(T*& p, size_t count, size_t align = 256) {
-    off = (off + align - 1) / align * align;
-    p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += sizeof(T) * count;
-  }
-};
-
 static int lip_launch_grad(sbo_ctx* c, const LipArgs* dA, const double* pts, long long N, double* grad, double* inf) {
   if (N <= 0) return SBO_OK;
   const unsigned nb = (unsigned)std::min<long long>((N + kLipThreads - 1) / kLipThreads, 8192);
   const double *al = (const double*)c->alpha64.p, *Xn = (const double*)c->Xn.p;
-  switch (c->mc.dpad) {
-    case 2: hipLaunchKernelGGL(k_mean_grad<2>, dim3(nb), dim3(kLipThreads), 0, c->stream, dA, al, Xn, pts, N, grad, inf); break;
-    case 4: hipLaunchKernelGGL(k_mean_grad<4>, dim3(nb), dim3(kLipThreads), 0, c->stream, dA, al, Xn, pts, N, grad, inf); break;
-    default: hipLaunchKernelGGL(k_mean_grad<8>, dim3(nb), dim3(kLipThreads), 0, c->stream, dA, al, Xn, pts, N, grad, inf); break;
-  }
+  with_dpad(c->mc.dpad, [&](auto D) {
+    hipLaunchKernelGGL(k_mean_grad<D()>, dim3(nb), dim3(kLipThreads), 0, c->stream, dA, al, Xn, pts, N, grad, inf);
+  });
   SBO_HIP(hipGetLastError());
   return SBO_OK;
-}
-
-// the model both entry points need; once their arguments are checked they wait for its arrays (lip_wait)
-static int lip_model(const sbo_ctx* c, const char* who) {
-  if (!c->has_model) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
-  if (c->dtype != SBO_F64) return fail(SBO_E_UNSUPPORTED, std::string(who) + " needs an fp64 model");
-  return SBO_OK;
-}
-static int lip_wait(sbo_ctx* c) {
-  SBO_HIP(hipSetDevice(c->device));
-  return factor_sync(c);                              // (a deferred factor chain also delivers the verdict on a caller's invK)
 }
 
 template <bool kLds>
@@ -480,7 +402,7 @@ extern "C" int sbo_mean_grad(sbo_ctx* c, int64_t n_points, const double* points,
   if (!points || (!grad_out && !infnorm_out)) return fail(SBO_E_INVALID, "NULL argument");
   if (n_points < 1 || n_points > (1LL << 28)) return fail(SBO_E_INVALID, "n_points out of range");
   int rc;
-  if ((rc = lip_model(c, "sbo_mean_grad")) || (rc = lip_wait(c))) return rc;
+  if ((rc = model_reader_begin(c, "sbo_mean_grad", true))) return rc;
   const int d = c->mc.d, q = c->mc.q;
   const size_t N = (size_t)n_points;
   LipArgs A{};
@@ -488,15 +410,14 @@ extern "C" int sbo_mean_grad(sbo_ctx* c, int64_t n_points, const double* points,
   A.a_ld = c->a_ld;
   LipArgs* dA;
   double *dpts, *dgrad, *dinf;
-  auto layout = [&](LipCarve cv) {
+  auto layout = [&](Carve cv) {
     cv.take(dA, 1);
     cv.take(dpts, N * d);
     cv.take(dgrad, grad_out ? N * q * d : 0);
     cv.take(dinf, infnorm_out ? N * q : 0);
     return cv.off;
   };
-  if ((rc = ensure(c->lipbuf, layout({nullptr})))) return rc;
-  layout({(unsigned char*)c->lipbuf.p});
+  if ((rc = carve(c->lipbuf, layout, 256))) return rc;
   SBO_HIP(hipMemcpyAsync(dA, &A, sizeof(A), hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(dpts, points, sizeof(double) * N * d, hipMemcpyHostToDevice, c->stream));
   if ((rc = lip_launch_grad(c, dA, dpts, n_points, grad_out ? dgrad : nullptr, infnorm_out ? dinf : nullptr))) return rc;
@@ -511,7 +432,7 @@ extern "C" int sbo_lipschitz(sbo_ctx* c, const sbo_lipschitz_opts* opts, int64_t
   if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
   if (!opts || !seeds || !result) return fail(SBO_E_INVALID, "NULL argument");
   int rc;
-  if ((rc = lip_model(c, "sbo_lipschitz"))) return rc;
+  if ((rc = model_reader_check(c, "sbo_lipschitz", true))) return rc;   // (d and q, which the checks below need)
   const int d = c->mc.d, q = c->mc.q;
   if (n_seeds < 1 || n_seeds > (1LL << 24)) return fail(SBO_E_INVALID, "n_seeds out of range");
   if (opts->top > kLipMaxTop) return fail(SBO_E_INVALID, "top must be at most 16");
@@ -521,7 +442,7 @@ extern "C" int sbo_lipschitz(sbo_ctx* c, const sbo_lipschitz_opts* opts, int64_t
   for (int a = 0; a < d; ++a)
     if (!std::isfinite(opts->lo[a]) || !std::isfinite(opts->hi[a]) || !(opts->lo[a] <= opts->hi[a]))
       return fail(SBO_E_INVALID, "box needs finite lo <= hi");
-  if ((rc = lip_wait(c))) return rc;
+  if ((rc = model_reader_begin(c, "sbo_lipschitz", true))) return rc;
   LipArgs A{};
   A.mc = c->mc;
   A.a_ld = c->a_ld;
@@ -543,7 +464,7 @@ extern "C" int sbo_lipschitz(sbo_ctx* c, const sbo_lipschitz_opts* opts, int64_t
   int *duse, *dpick, *dnev, *dconv;
   unsigned long long* dcount;
   sbo_lipschitz_result* dres;
-  auto layout = [&](LipCarve cv) {
+  auto layout = [&](Carve cv) {
     cv.take(dA, 1);
     cv.take(dpts, E * d);
     cv.take(dgrad, E * q * d);
@@ -556,8 +477,7 @@ extern "C" int sbo_lipschitz(sbo_ctx* c, const sbo_lipschitz_opts* opts, int64_t
     cv.take(dres, 1);
     return cv.off;
   };
-  if ((rc = ensure(c->lipbuf, layout({nullptr})))) return rc;
-  layout({(unsigned char*)c->lipbuf.p});
+  if ((rc = carve(c->lipbuf, layout, 256))) return rc;
   hipStream_t st = c->stream;
   SBO_HIP(hipMemcpyAsync(dA, &A, sizeof(A), hipMemcpyHostToDevice, st));
   SBO_HIP(hipMemcpyAsync(dpts, seeds, sizeof(double) * (size_t)A.nS * d, hipMemcpyHostToDevice, st));

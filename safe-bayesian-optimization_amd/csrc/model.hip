@@ -772,19 +772,12 @@ static int model_work(sbo_ctx* c, bool with_W, ModelWork& w) {
   const size_t n = mc.n, q = mc.q, npad = mc.npad, nn = n * n;
   const size_t nXY = n * mc.d + n * q, nAs = q * npad * mc.dpad, nsq = q * npad, nrhs = q * n;
   const size_t ndiag = q * ((n + kPB - 1) / kPB) * (kPB * kPB);
-  const size_t total = nXY + nAs + nsq + nrhs + 2 * q + (with_W ? q * nn : 0) + q * nn + ndiag + q + 8;
-  int rc = ensure(c->mwork, sizeof(double) * total);
-  if (rc) return rc;
-  w.XY = (double*)c->mwork.p;
-  w.As64 = w.XY + nXY;
-  w.sq64 = w.As64 + nAs;
-  w.rhs = w.sq64 + nsq;
-  w.sfsn = w.rhs + nrhs;
-  w.W = w.sfsn + 2 * q;
-  w.work = w.W + (with_W ? q * nn : 0);
-  w.Dg = w.work + q * nn;
-  w.bad = (int*)(w.Dg + ndiag);
-  return SBO_OK;
+  return carve(c->mwork, [&](Carve cv) {
+    cv.take(w.XY, nXY); cv.take(w.As64, nAs); cv.take(w.sq64, nsq); cv.take(w.rhs, nrhs);
+    cv.take(w.sfsn, 2 * q); cv.take(w.W, with_W ? q * nn : 0); cv.take(w.work, q * nn); cv.take(w.Dg, ndiag);
+    cv.take(w.bad, q);
+    return cv.off;
+  });
 }
 static int stage_ensure(sbo_ctx* c, size_t bytes) {
   if (c->h_stage.bytes >= bytes) return SBO_OK;
@@ -1012,6 +1005,18 @@ static int model_repack_t(sbo_ctx* c) {
 }
 int model_repack(sbo_ctx* c) { return c->dtype == SBO_F64 ? model_repack_t<double>(c) : model_repack_t<float>(c); }
 
+// c->appendbuf: kvec [q][n] | kappa [q] | rho [q] | scratch [q][2 cap] | (s, k.alpha) [q][2] | bad [q]
+struct AppendWork {
+  double *k, *kappa, *rho, *scratch, *sk;
+  int* bad;
+};
+static size_t append_layout(Carve cv, int n, int q, int cap, AppendWork& w) {
+  cv.take(w.k, (size_t)q * n); cv.take(w.kappa, q); cv.take(w.rho, q);
+  cv.take(w.scratch, 2 * (size_t)q * cap); cv.take(w.sk, 2 * (size_t)q);
+  cv.take(w.bad, q);
+  return cv.off;
+}
+
 // kvec [q][n] cross-covariances of the new point, kappa[q] = sf2 + sn2, rho[q] = y_norm_new - mp.  model_append_check
 // computes the update of row n into c->appendbuf and fails with SBO_E_INVALID when an output's s <= 0; nothing of the model
 // changes (growing the factor's capacity copies it and keeps its values).  model_append_commit then writes the update.
@@ -1042,23 +1047,17 @@ int model_append_check(sbo_ctx* c, const std::vector<double>& kvec, const double
     c->a_ld = cap;
   }
   const int cap = c->f_cap;
-  // appendbuf (doubles): kvec [q][n] | kappa [q] | rho [q] | scratch [q][2 cap] | (s, k.alpha) [q][2] | bad [q] (ints)
-  if ((rc = ensure(c->appendbuf, sizeof(double) * ((size_t)q * n + 4 * (size_t)q + 2 * (size_t)q * cap) + sizeof(int) * q))) return rc;
-  double* dk = (double*)c->appendbuf.p;
-  double* dkappa = dk + (size_t)q * n;
-  double* drho = dkappa + q;
-  double* dscratch = drho + q;
-  double* dsk = dscratch + 2 * (size_t)q * cap;
-  int* dbad = (int*)(dsk + 2 * (size_t)q);
-  SBO_HIP(hipMemcpyAsync(dk, kvec.data(), sizeof(double) * (size_t)q * n, hipMemcpyHostToDevice, c->stream));
-  SBO_HIP(hipMemcpyAsync(dkappa, kappa, sizeof(double) * q, hipMemcpyHostToDevice, c->stream));
-  SBO_HIP(hipMemcpyAsync(drho, rho, sizeof(double) * q, hipMemcpyHostToDevice, c->stream));
-  SBO_HIP(hipMemsetAsync(dbad, 0, sizeof(int) * q, c->stream));
+  AppendWork w;
+  if ((rc = carve(c->appendbuf, [&](Carve cv) { return append_layout(cv, n, q, cap, w); }))) return rc;
+  SBO_HIP(hipMemcpyAsync(w.k, kvec.data(), sizeof(double) * (size_t)q * n, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemcpyAsync(w.kappa, kappa, sizeof(double) * q, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemcpyAsync(w.rho, rho, sizeof(double) * q, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemsetAsync(w.bad, 0, sizeof(int) * q, c->stream));
   hipLaunchKernelGGL(k_model_append, dim3(q), dim3(1024), 0, c->stream, n, cap, (const double*)c->Fplain.p, (const double*)c->alpha64.p,
-                     (const double*)dk, (const double*)dkappa, dscratch, dsk, dbad);
+                     (const double*)w.k, (const double*)w.kappa, w.scratch, w.sk, w.bad);
   SBO_HIP(hipGetLastError());
   std::vector<int> hbad(q, 0);
-  SBO_HIP(hipMemcpyAsync(hbad.data(), dbad, sizeof(int) * q, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipMemcpyAsync(hbad.data(), w.bad, sizeof(int) * q, hipMemcpyDeviceToHost, c->stream));
   SBO_HIP(hipStreamSynchronize(c->stream));
   for (int o = 0; o < q; ++o)
     if (hbad[o]) return fail(SBO_E_INVALID, "appended observation makes K singular (duplicate point without noise?)");
@@ -1066,11 +1065,10 @@ int model_append_check(sbo_ctx* c, const std::vector<double>& kvec, const double
 }
 int model_append_commit(sbo_ctx* c) {
   const int n = c->mc.n, q = c->mc.q, cap = c->f_cap;
-  double* drho = (double*)c->appendbuf.p + (size_t)q * n + q;
-  double* dscratch = drho + q;
-  double* dsk = dscratch + 2 * (size_t)q * cap;
+  AppendWork w;                                                  // (as model_append_check laid it out)
+  append_layout(Carve{(unsigned char*)c->appendbuf.p}, n, q, cap, w);
   hipLaunchKernelGGL(k_model_append_commit, dim3(q), dim3(1024), 0, c->stream, n, cap, (double*)c->Fplain.p, (double*)c->alpha64.p,
-                     (const double*)drho, (const double*)dscratch, (const double*)dsk);
+                     (const double*)w.rho, (const double*)w.scratch, (const double*)w.sk);
   SBO_HIP(hipGetLastError());
   c->invk_img_valid = false;                                    // (the images of the caller's invK do not follow an append)
   c->invk_w_valid = false;

@@ -835,12 +835,7 @@ static int launch_posterior_t(sbo_ctx* c, const PostTarget& t) {
 
 template <typename T, int S>
 static int launch_posterior_d(sbo_ctx* c, const PostTarget& t) {
-  switch (c->mc.dpad) {
-    case 2: return launch_posterior_t<T, S, 2>(c, t);
-    case 4: return launch_posterior_t<T, S, 4>(c, t);
-    case 8: return launch_posterior_t<T, S, 8>(c, t);
-  }
-  return fail(SBO_E_UNSUPPORTED, "unsupported padded dimension");
+  return with_dpad(c->mc.dpad, [&](auto D) { return launch_posterior_t<T, S, D()>(c, t); });
 }
 
 template <typename T, int D>
@@ -861,12 +856,7 @@ static int launch_posterior_chunked_t(sbo_ctx* c, const PostTarget& t) {
 
 template <typename T>
 static int launch_posterior_chunked(sbo_ctx* c, const PostTarget& t) {
-  switch (c->mc.dpad) {
-    case 2: return launch_posterior_chunked_t<T, 2>(c, t);
-    case 4: return launch_posterior_chunked_t<T, 4>(c, t);
-    case 8: return launch_posterior_chunked_t<T, 8>(c, t);
-  }
-  return fail(SBO_E_UNSUPPORTED, "unsupported padded dimension");
+  return with_dpad(c->mc.dpad, [&](auto D) { return launch_posterior_chunked_t<T, D()>(c, t); });
 }
 
 template <typename T>
@@ -938,12 +928,7 @@ static int launch_posterior_grid_t(sbo_ctx* c, const PostTarget& t) {
 
 template <typename T>
 static int launch_posterior_grid(sbo_ctx* c, const PostTarget& t) {
-  switch (c->mc.dpad) {
-    case 2: return launch_posterior_grid_t<T, 2>(c, t);
-    case 4: return launch_posterior_grid_t<T, 4>(c, t);
-    case 8: return launch_posterior_grid_t<T, 8>(c, t);
-  }
-  return fail(SBO_E_UNSUPPORTED, "unsupported padded dimension");
+  return with_dpad(c->mc.dpad, [&](auto D) { return launch_posterior_grid_t<T, D()>(c, t); });
 }
 
 // the separable path needs whole axis-0 lines in the shard

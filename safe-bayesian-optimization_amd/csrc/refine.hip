@@ -70,27 +70,6 @@ enum { REF_PH_START = 0, REF_PH_SEARCH = 1 };
 // (ball-limited) box
 __device__ __forceinline__ PbfgsBox ref_box(const RefState& S, const RefineArgs& A) { return {A.lo, A.hi, S.D2, S.span, 0.1}; }
 
-// sums of cnt per-thread values over the workgroup: butterfly within a wave, then the waves in order (thread 0) -> out[]
-__device__ __forceinline__ void ref_block_sum(const double* v, int cnt, double (*part)[kMaxD + 1], double* out) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kMaxD + 1; ++k) {
-    if (k < cnt) {
-      double s = v[k];
-      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-      if (lane == 0) part[wave][k] = s;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int k = 0; k < cnt; ++k) {
-      double s = 0.0;
-      for (int w = 0; w < nw; ++w) s += part[w][k];
-      out[k] = s;
-    }
-  __syncthreads();
-}
-
 // the LDS tier's copy of M: the used outputs' lower triangles out of Fplain, packed row after row (one wave per row) -> Ml
 __device__ __forceinline__ void ref_load_M(const RefineArgs& A, const double* F, double* Ml) {
   const int n = A.mc.n, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -151,7 +130,7 @@ __device__ void ref_eval(const RefineArgs& A, const double* x, const double* F, 
       }
     }
 #pragma unroll
-    for (int p = 0; p < kP; ++p) ref_block_sum(acc[p], d + 1, part, red + p * kRed);   // (its barriers also publish kv)
+    for (int p = 0; p < kP; ++p) block_sum_cols(acc[p], d + 1, part, red + p * kRed);   // (its barriers also publish kv)
     // u = M k (one wave per row, rows in order), u . u
     double uu[kP];
 #pragma unroll
@@ -208,7 +187,7 @@ __device__ void ref_eval(const RefineArgs& A, const double* x, const double* F, 
       }
     }
 #pragma unroll
-    for (int p = 0; p < kP; ++p) ref_block_sum(gacc[p], d, part, red + p * kRed + kMaxD + 1);
+    for (int p = 0; p < kP; ++p) block_sum_cols(gacc[p], d, part, red + p * kRed + kMaxD + 1);
     if (tid == 0) {
       for (int p = 0; p < kP; ++p) {
         const double* rd = red + p * kRed;
@@ -604,18 +583,6 @@ static int refine_check_box(const double* lo, const double* hi, int d) {
   return SBO_OK;
 }
 
-// Hands out consecutive blocks of one buffer, each at a multiple of `align` bytes.  A layout is one sequence of take() calls, run
-// once on a null base for the size and once on the buffer for the pointers.
-struct Carve {
-  unsigned char* base;
-  size_t off = 0;
-  template <class T> void take(T*& p, size_t count, size_t align = alignof(T)) {
-    off = (off + align - 1) / align * align;
-    p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += sizeof(T) * count;
-  }
-};
-
 template <bool kLds, int kP>
 static int refine_launch(sbo_ctx* c, size_t lds, int threads, long long S, const RefineArgs* dA, const double* dseed, const double* m0,
                          const double* v0, double* cand, int* dst, int* dnev) {
@@ -632,9 +599,8 @@ static int refine_run(sbo_ctx* c, RefineArgs& A, int max_eval, double tol, long 
                       std::vector<double>& hv, std::vector<int>& hs) {
   const ModelConst& mc = c->mc;
   const int q = mc.q, np = A.np, nz = A.nz;
-  SBO_HIP(hipSetDevice(c->device));
   int rc;
-  if ((rc = factor_sync(c))) return rc;             // (Fplain may still be in the making: the deferred factor chain)
+  if ((rc = model_reader_begin(c, "sbo_refine", true))) return rc;   // (Fplain may still be in the making: the deferred factor chain)
   refine_fill(c, tol, A);
   A.max_eval = max_eval > 0 ? std::min(max_eval, refine_eval_cap(mc.n)) : kRefDefaultEval;
   // scratch: the arguments | seeds [S][nz] | mean0 var0 [q][np S] | cand [2 S][nz] | mean1 var1 [q][2 np S] | x_out [S][nz] | val [S] |
@@ -653,8 +619,7 @@ static int refine_run(sbo_ctx* c, RefineArgs& A, int max_eval, double tol, long 
     cv.take(dst, S); cv.take(dnev, S);
     return cv.off;
   };
-  if ((rc = ensure(c->refbuf, layout({nullptr})))) return rc;
-  layout({(unsigned char*)c->refbuf.p});
+  if ((rc = carve(c->refbuf, layout))) return rc;
   SBO_HIP(hipMemcpyAsync(dA, &A, sizeof(RefineArgs), hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(dseed, seeds, sizeof(double) * (size_t)S * nz, hipMemcpyHostToDevice, c->stream));
   if ((rc = launch_posterior_on_list(c, dseed, (long long)P, m0, v0))) return rc;   // (a pair's points are consecutive rows of d)
@@ -990,46 +955,34 @@ __global__ __launch_bounds__(1024) void k_refine_robust(const RobustArgs* __rest
   }
 }
 
-// (value, index) of the larger value (or the smaller), ties and equal values to the lower index; NaN never wins
-__device__ __forceinline__ void rob_better(bool want_max, double v, long long i, double& bv, long long& bi) {
-  if (i < 0 || isnan(v)) return;
-  if (bi < 0 || (want_max ? v > bv : v < bv) || (v == bv && i < bi)) { bv = v; bi = i; }
-}
-
-// arg-max (arg-min) over i < N of `kind` of (m[i], v[i]) by the workgroup (256 threads): every thread returns the result
-__device__ void rob_argext(const double* m, const double* v, long long N, double b, int kind, bool want_max, double* sv, long long* si,
-                           double& val, long long& idx) {
+// arg-max (arg-min: of the negated value, which is exact) over i < N of `kind` of (m[i], v[i]) by the workgroup, ties to the lower
+// index, a NaN never wins: every thread returns the result (nothing qualified: val = 0, idx = -1).  sv / sk: one slot per wave
+__device__ void rob_argext(const double* m, const double* v, long long N, double b, int kind, bool want_max, double* sv,
+                           long long* sk, double& val, long long& idx) {
   double bv = 0.0;
-  long long bi = -1;
-  for (long long i = threadIdx.x; i < N; i += blockDim.x) rob_better(want_max, ref_bound(m[i], v[i], b, kind), i, bv, bi);
-  sv[threadIdx.x] = bv;
-  si[threadIdx.x] = bi;
-  __syncthreads();
-  for (int o = blockDim.x >> 1; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      rob_better(want_max, sv[threadIdx.x + o], si[threadIdx.x + o], bv, bi);
-      sv[threadIdx.x] = bv;
-      si[threadIdx.x] = bi;
-    }
-    __syncthreads();
+  long long bk = kArgNone;
+  for (long long i = threadIdx.x; i < N; i += blockDim.x) {
+    const double f = ref_bound(m[i], v[i], b, kind);
+    arg_take(bv, bk, want_max ? f : -f, isnan(f) ? kArgNone : i);
   }
-  val = sv[0];
-  idx = si[0];
-  __syncthreads();
+  arg_block_best_all(bv, bk, sv, sk);
+  const bool none = bk == kArgNone;
+  val = none ? 0.0 : (want_max ? bv : -bv);
+  idx = none ? -1 : bk;
 }
 
 // the separation's grid seeds: output 0's arg-max of the objective's bound and every constraint's arg-min of its lcb over the list
 // pts [N][d] (values m / v [q][N]) -> seeds [q][d], their values sval [q]
 __global__ __launch_bounds__(256) void k_rob_pick(const RobustArgs* __restrict__ Rp, const double* __restrict__ pts, const double* __restrict__ m,
                                                   const double* __restrict__ v, long long N, double* __restrict__ seeds, double* __restrict__ sval) {
-  __shared__ double sv[256];
-  __shared__ long long si[256];
+  __shared__ double sv[256 / 64];
+  __shared__ long long sk[256 / 64];
   const RobustArgs& R = *Rp;
   const int d = R.A.mc.d, q = R.A.mc.q;
   for (int u = 0; u < q; ++u) {
     double val;
     long long idx;
-    rob_argext(m + (size_t)u * N, v + (size_t)u * N, N, R.A.b, u == 0 ? R.kind : SBO_LCB, u == 0, sv, si, val, idx);
+    rob_argext(m + (size_t)u * N, v + (size_t)u * N, N, R.A.b, u == 0 ? R.kind : SBO_LCB, u == 0, sv, sk, val, idx);
     if (threadIdx.x == 0) {
       if (idx < 0) idx = 0;                          // (no finite value on the list: the first point)
       for (int a = 0; a < d; ++a) seeds[u * d + a] = pts[idx * d + a];
@@ -1105,8 +1058,8 @@ struct RobustFinal {
 // the exact check: lists {seed} x C and {xc} x C of NC points each, values m / v [q][2 NC]
 __global__ __launch_bounds__(256) void k_rob_final(const RobustArgs* __restrict__ Rp, const double* __restrict__ m, const double* __restrict__ v,
                                                    long long NC, RobustFinal* __restrict__ out) {
-  __shared__ double sv[256];
-  __shared__ long long si[256];
+  __shared__ double sv[256 / 64];
+  __shared__ long long sk[256 / 64];
   const RobustArgs& R = *Rp;
   const int q = R.A.mc.q;
   for (int w = 0; w < 2; ++w)
@@ -1114,7 +1067,7 @@ __global__ __launch_bounds__(256) void k_rob_final(const RobustArgs* __restrict_
       double val;
       long long idx;
       const size_t off = (size_t)u * 2 * NC + (size_t)w * NC;
-      rob_argext(m + off, v + off, NC, R.A.b, u == 0 ? R.kind : SBO_LCB, u == 0, sv, si, val, idx);
+      rob_argext(m + off, v + off, NC, R.A.b, u == 0 ? R.kind : SBO_LCB, u == 0, sv, sk, val, idx);
       if (threadIdx.x == 0) {
         if (u == 0) {
           out->value[w] = idx >= 0 ? val : NAN;
@@ -1156,8 +1109,7 @@ static int refine_robust(sbo_ctx* c, const sbo_refine_robust_opts* opts, const d
   }
   for (int a = 0; a < nxc; ++a)
     if (!std::isfinite(xc_seed[a])) return fail(SBO_E_INVALID, "the seed must be finite");
-  SBO_HIP(hipSetDevice(c->device));
-  if ((rc = factor_sync(c))) return rc;
+  if ((rc = model_reader_begin(c, "sbo_refine_robust", true))) return rc;
   const int max_rounds = opts->max_rounds > 0 ? opts->max_rounds : kRobDefaultRounds;
   const int eval_cap = refine_eval_cap(n);
   const int max_eval = opts->max_eval > 0 ? std::min(opts->max_eval, eval_cap) : eval_cap;
@@ -1226,8 +1178,7 @@ static int refine_robust(sbo_ctx* c, const sbo_refine_robust_opts* opts, const d
     cv.take(dst, q); cv.take(dnev, q);
     return cv.off;
   };
-  if ((rc = ensure(c->refbuf, layout({nullptr})))) return rc;
-  layout({(unsigned char*)c->refbuf.p});
+  if ((rc = carve(c->refbuf, layout))) return rc;
   RobustArgs* dR = (RobustArgs*)dargs;
 
   bool lds_polish, lds_outer;
@@ -1361,8 +1312,7 @@ extern "C" int sbo_refine_robust(sbo_ctx* c, const sbo_refine_robust_opts* opts,
                                  sbo_refine_robust_result* result) {
   if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
   if (!opts || !xc_seed || !result) return fail(SBO_E_INVALID, "NULL argument");
-  if (!c->has_model) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
-  if (c->dtype != SBO_F64) return fail(SBO_E_UNSUPPORTED, "sbo_refine_robust needs an fp64 model");
+  if (const int rcm = model_reader_check(c, "sbo_refine_robust", true)) return rcm;
   return refine_robust(c, opts, xc_seed, scenarios_out, result);
 }
 
@@ -1371,8 +1321,7 @@ extern "C" int sbo_refine(sbo_ctx* c, const sbo_refine_opts* opts, int64_t n_see
                           double* value_out, int32_t* status_out, sbo_refine_result* result) {
   if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
   if (!opts || !seeds || !result) return fail(SBO_E_INVALID, "NULL argument");
-  if (!c->has_model) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
-  if (c->dtype != SBO_F64) return fail(SBO_E_UNSUPPORTED, "sbo_refine needs an fp64 model");
+  if (const int rcm = model_reader_check(c, "sbo_refine", true)) return rcm;
   const int q = c->mc.q;
   if (n_seeds < 1 || n_seeds > (1LL << 24)) return fail(SBO_E_INVALID, "n_seeds out of range");
   if (opts->objective < 0 || opts->objective >= q) return fail(SBO_E_INVALID, "objective output out of range");
@@ -1412,7 +1361,6 @@ extern "C" int sbo_refine_sets(sbo_ctx* c, const sbo_refine_sets_opts* opts, int
                                double* x_out, double* xp_out, double* value_out, int32_t* status_out, sbo_refine_sets_result* result) {
   if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
   if (!opts || !seeds || !result) return fail(SBO_E_INVALID, "NULL argument");
-  if (!c->has_model) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
-  if (c->dtype != SBO_F64) return fail(SBO_E_UNSUPPORTED, "sbo_refine_sets needs an fp64 model");
+  if (const int rcm = model_reader_check(c, "sbo_refine_sets", true)) return rcm;
   return refine_problem(c, opts, n_seeds, seeds, seeds_p, x_out, xp_out, value_out, status_out, result);
 }

@@ -222,34 +222,26 @@ int rob_layout(sbo_ctx* c, long long nc, RobLayout& L) {
   const bool mr = multi_rank(c);
   const size_t nA = (size_t)nc;
   // local f | fsec | argd | fb | g | gbd;  ranks > 1: global f | fb | g | gbd and the key arrays (2 x (2 + qc) Nc);  the scalars; the rows
-  const size_t words = nA * (4 + 2 * (size_t)qc) + (mr ? nA * (2 + 2 * (size_t)qc) + 2 * nA * (2 + (size_t)qc) : 0) + 64 +
-                       (size_t)kRowFields * (c->dist.world + 1);
   int rc;
-  if ((rc = ensure(c->rob.vals, words * 8))) return rc;
+  if ((rc = carve(c->rob.vals, [&](Carve cv) {
+        cv.take(L.floc, nA); cv.take(L.fsec, nA); cv.take(L.argd, nA); cv.take(L.fb, nA);
+        cv.take(L.g, nA * qc); cv.take(L.gbd, nA * qc);
+        if (mr) {
+          cv.take(L.fG, nA); cv.take(L.fbG, nA);
+          cv.take(L.gG, nA * qc); cv.take(L.gbG, nA * qc);
+          cv.take(L.kmax, nA * (2 + qc)); cv.take(L.kmin, nA * (2 + qc));   // (kmin: qc x Nc used)
+        }
+        cv.take(L.open, 64); cv.take(L.row, kRowFields); cv.take(L.rows, (size_t)kRowFields * c->dist.world);
+        return cv.off;
+      })))
+    return rc;
   if ((rc = ensure(c->rob.mask, nA + 8))) return rc;
-  double* p = (double*)c->rob.vals.p;
   L.nc = nc;
   L.qc = qc;
-  L.floc = p; p += nA;
-  L.fsec = p; p += nA;
-  L.argd = (long long*)p; p += nA;
-  L.fb = p; p += nA;
-  L.g = p; p += nA * qc;
-  L.gbd = p; p += nA * qc;
-  if (mr) {
-    L.fG = p; p += nA;
-    L.fbG = p; p += nA;
-    L.gG = p; p += nA * qc;
-    L.gbG = p; p += nA * qc;
-    L.kmax = (unsigned long long*)p; p += nA * (2 + qc);
-    L.kmin = (unsigned long long*)p; p += nA * (2 + qc);   // (qc x Nc used)
-  } else {
+  if (!mr) {
     L.fG = L.floc; L.fbG = L.fb; L.gG = L.g; L.gbG = L.gbd;
     L.kmax = L.kmin = nullptr;
   }
-  L.open = (unsigned long long*)p; p += 64;
-  L.row = p; p += kRowFields;
-  L.rows = p;
   return SBO_OK;
 }
 
@@ -290,15 +282,13 @@ int robust_phase(sbo_ctx* c, const sbo_sweep_opts* o, int kind, long long nc, co
       a.f = L.floc; a.fsec = L.fsec; a.argd = L.argd; a.fb = L.fb; a.g = L.g; a.gbd = L.gbd;
       hipLaunchKernelGGL(k_robust_reduce, dim3(bx, 1), dim3(kRobBlock), 0, c->stream, a);
     } else {
-      const size_t per = (size_t)nc * (4 + 2 * (size_t)qc);
-      if ((rc = ensure(c->rob.part, per * (size_t)sp * 8))) return rc;
-      double* p = (double*)c->rob.part.p;
-      a.f = p; p += (size_t)sp * nc;
-      a.fsec = p; p += (size_t)sp * nc;
-      a.argd = (long long*)p; p += (size_t)sp * nc;
-      a.fb = p; p += (size_t)sp * nc;
-      a.g = p; p += (size_t)sp * nc * qc;
-      a.gbd = p;
+      const size_t per = (size_t)sp * nc;                // (one array of a split's partials)
+      if ((rc = carve(c->rob.part, [&](Carve cv) {
+            cv.take(a.f, per); cv.take(a.fsec, per); cv.take(a.argd, per); cv.take(a.fb, per);
+            cv.take(a.g, per * qc); cv.take(a.gbd, per * qc);
+            return cv.off;
+          })))
+        return rc;
       hipLaunchKernelGGL(k_robust_reduce, dim3(bx, (unsigned)sp), dim3(kRobBlock), 0, c->stream, a);
       hipLaunchKernelGGL(k_robust_combine, dim3(bx), dim3(kRobBlock), 0, c->stream, a, sp, L.floc, L.fsec, L.argd, L.fb, L.g, L.gbd);
     }

@@ -1260,12 +1260,7 @@ static int launch_exact(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* 
 
 template <typename T>
 static int launch_exact_d(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, const SetView& v, int cidx, int lidx, uint8_t* G) {
-  switch (c->mc.dpad) {
-    case 2: return launch_exact<T, 2>(c, ln, o, v, cidx, lidx, G);
-    case 4: return launch_exact<T, 4>(c, ln, o, v, cidx, lidx, G);
-    case 8: return launch_exact<T, 8>(c, ln, o, v, cidx, lidx, G);
-  }
-  return fail(SBO_E_UNSUPPORTED, "unsupported padded dimension");
+  return with_dpad(c->mc.dpad, [&](auto D) { return launch_exact<T, D()>(c, ln, o, v, cidx, lidx, G); });
 }
 
 static int sweep_exchange_wait(sbo_ctx* c);
@@ -1408,11 +1403,7 @@ static int list_index_prepare(sbo_ctx* c) {
   SBO_HIP(hipEventRecord(x.ev0.e, c->stream));
   unsigned long long* k0 = (unsigned long long*)x.keys.p;
   unsigned* v0 = (unsigned*)x.vals.p;
-  switch (idx_dpad(c->cs.d)) {
-    case 2: list_index_sort_d<2>(c, k0, v0, k0 + n, v0 + n, ntiles); break;
-    case 4: list_index_sort_d<4>(c, k0, v0, k0 + n, v0 + n, ntiles); break;
-    default: list_index_sort_d<8>(c, k0, v0, k0 + n, v0 + n, ntiles); break;
-  }
+  with_dpad(idx_dpad(c->cs.d), [&](auto D) { list_index_sort_d<D()>(c, k0, v0, k0 + n, v0 + n, ntiles); });
   SBO_HIP(hipGetLastError());
   SBO_HIP(hipEventRecord(x.ev1.e, c->stream));
   x.valid = true;
@@ -1499,11 +1490,7 @@ static int list_index_expander(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep
 }
 template <typename T>
 static int list_index_expander_d(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, const SetView& v, int cidx, int lidx, uint8_t* G) {
-  switch (idx_dpad(c->cs.d)) {
-    case 2: return list_index_expander<T, 2>(c, ln, o, v, cidx, lidx, G);
-    case 4: return list_index_expander<T, 4>(c, ln, o, v, cidx, lidx, G);
-    default: return list_index_expander<T, 8>(c, ln, o, v, cidx, lidx, G);
-  }
+  return with_dpad(idx_dpad(c->cs.d), [&](auto D) { return list_index_expander<T, D()>(c, ln, o, v, cidx, lidx, G); });
 }
 
 // the minimiser launch of a SafeOpt sweep, held back so that the first constraint's expander can take it into k_set_mid
@@ -2461,12 +2448,7 @@ static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o,
 
 template <typename T>
 static int goose_sets_d(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, const SetView& v, int cidx, const uint8_t* src, uint8_t* O) {
-  switch (c->mc.dpad) {
-    case 2: return goose_sets<T, 2>(c, ln, o, v, cidx, src, O);
-    case 4: return goose_sets<T, 4>(c, ln, o, v, cidx, src, O);
-    case 8: return goose_sets<T, 8>(c, ln, o, v, cidx, src, O);
-  }
-  return fail(SBO_E_UNSUPPORTED, "unsupported padded dimension");
+  return with_dpad(c->mc.dpad, [&](auto D) { return goose_sets<T, D()>(c, ln, o, v, cidx, src, O); });
 }
 
 // arg-min over S_t of the distance to the target (explore_safeset, models/GoOSE.py:116-119) -> partials for k_arg_final
@@ -2474,20 +2456,10 @@ template <typename T>
 static void launch_argmin_dist(sbo_ctx* c, const double* dev_target, int nb) {
   const long long n = c->cs.n_local;
   const uint8_t* S = (const uint8_t*)c->maskS.p;
-  switch (c->mc.dpad) {
-    case 2:
-      hipLaunchKernelGGL((k_arg_masked<T, false, ValDist<T, 2>>), dim3(nb), dim3(256), 0, c->stream, ValDist<T, 2>{c->cs, dev_target}, S, n,
-                         (long long)c->cs.first, (Best*)c->partial.p, (const GuardBand*)nullptr);
-      break;
-    case 4:
-      hipLaunchKernelGGL((k_arg_masked<T, false, ValDist<T, 4>>), dim3(nb), dim3(256), 0, c->stream, ValDist<T, 4>{c->cs, dev_target}, S, n,
-                         (long long)c->cs.first, (Best*)c->partial.p, (const GuardBand*)nullptr);
-      break;
-    default:
-      hipLaunchKernelGGL((k_arg_masked<T, false, ValDist<T, 8>>), dim3(nb), dim3(256), 0, c->stream, ValDist<T, 8>{c->cs, dev_target}, S, n,
-                         (long long)c->cs.first, (Best*)c->partial.p, (const GuardBand*)nullptr);
-      break;
-  }
+  with_dpad(c->mc.dpad, [&](auto D) {
+    hipLaunchKernelGGL((k_arg_masked<T, false, ValDist<T, D()>>), dim3(nb), dim3(256), 0, c->stream, ValDist<T, D()>{c->cs, dev_target}, S, n,
+                       (long long)c->cs.first, (Best*)c->partial.p, (const GuardBand*)nullptr);
+  });
 }
 
 // GoOSE iteration (models/GoOSE.py:63-119, test/test_GoOSE.py:151-162) on the resident candidates.  Ranks > 1: C1 + C2
@@ -2550,11 +2522,10 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   const bool short_tail = fused_explore && c->opt.result_mirror && (c->mc.dpad == 2 || c->mc.dpad == 4 || c->mc.dpad == 8);
   const SweepScalars* l1 = lanes ? (const SweepScalars*)c->lane[1].scal.p : (const SweepScalars*)nullptr;
   if (short_tail) {
-    switch (c->mc.dpad) {
-      case 2: hipLaunchKernelGGL((k_goose_finals<2>), dim3((unsigned)q), dim3(256), 0, c->stream, (const unsigned char*)pbase, pstride, n > 0 ? nb : 0, q, sc, l1, c->cs, dev_t, gbon); break;
-      case 4: hipLaunchKernelGGL((k_goose_finals<4>), dim3((unsigned)q), dim3(256), 0, c->stream, (const unsigned char*)pbase, pstride, n > 0 ? nb : 0, q, sc, l1, c->cs, dev_t, gbon); break;
-      default: hipLaunchKernelGGL((k_goose_finals<8>), dim3((unsigned)q), dim3(256), 0, c->stream, (const unsigned char*)pbase, pstride, n > 0 ? nb : 0, q, sc, l1, c->cs, dev_t, gbon); break;
-    }
+    with_dpad(c->mc.dpad, [&](auto D) {
+      hipLaunchKernelGGL((k_goose_finals<D()>), dim3((unsigned)q), dim3(256), 0, c->stream, (const unsigned char*)pbase, pstride,
+                         n > 0 ? nb : 0, q, sc, l1, c->cs, dev_t, gbon);
+    });
     if (n > 0) launch_argmin_dist<T>(c, dev_t, nb);
     hipExtLaunchKernelGGL(k_arg_final_mirror, dim3(1), dim3(256), 0, c->stream, nullptr, c->ev[4], 0, (const Best*)c->partial.p, n > 0 ? nb : 0, sc,
                           kArgSlots - 1, c->h_back, c->Lmax, 0);
@@ -2564,11 +2535,9 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
                        n > 0 ? nb : 0, sc, l1, (unsigned char*)nullptr, (const unsigned long long*)nullptr, gbon);
     SBO_HIP(hipGetLastError());
     if (fused_explore) {
-      switch (c->mc.dpad) {
-        case 2: hipLaunchKernelGGL((k_pick_target<2>), dim3(1), dim3(1), 0, c->stream, c->cs, (const SweepScalars*)sc, q, dev_t); break;
-        case 4: hipLaunchKernelGGL((k_pick_target<4>), dim3(1), dim3(1), 0, c->stream, c->cs, (const SweepScalars*)sc, q, dev_t); break;
-        default: hipLaunchKernelGGL((k_pick_target<8>), dim3(1), dim3(1), 0, c->stream, c->cs, (const SweepScalars*)sc, q, dev_t); break;
-      }
+      with_dpad(c->mc.dpad, [&](auto D) {
+        hipLaunchKernelGGL((k_pick_target<D()>), dim3(1), dim3(1), 0, c->stream, c->cs, (const SweepScalars*)sc, q, dev_t);
+      });
       if (n > 0) {
         launch_argmin_dist<T>(c, dev_t, nb);
       }
@@ -2673,11 +2642,10 @@ static int sweep_tr_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, con
   double* dev_x0 = (double*)c->lane[0].scal.p + 256;
   SBO_HIP(hipMemcpyAsync(dev_x0, x0, sizeof(double) * c->cs.d, hipMemcpyHostToDevice, c->stream));
   if (n > 0) {
-    switch (c->mc.dpad) {
-      case 2: hipLaunchKernelGGL((k_ball_mask<2>), dim3(nb), dim3(256), 0, c->stream, c->cs, n, (const uint8_t*)c->maskS.p, (const double*)dev_x0, r, (uint8_t*)c->maskM.p); break;
-      case 4: hipLaunchKernelGGL((k_ball_mask<4>), dim3(nb), dim3(256), 0, c->stream, c->cs, n, (const uint8_t*)c->maskS.p, (const double*)dev_x0, r, (uint8_t*)c->maskM.p); break;
-      default: hipLaunchKernelGGL((k_ball_mask<8>), dim3(nb), dim3(256), 0, c->stream, c->cs, n, (const uint8_t*)c->maskS.p, (const double*)dev_x0, r, (uint8_t*)c->maskM.p); break;
-    }
+    with_dpad(c->mc.dpad, [&](auto D) {
+      hipLaunchKernelGGL((k_ball_mask<D()>), dim3(nb), dim3(256), 0, c->stream, c->cs, n, (const uint8_t*)c->maskS.p, (const double*)dev_x0, r,
+                         (uint8_t*)c->maskM.p);
+    });
     hipLaunchKernelGGL((k_arg_masked<T, false, ValLcb<T>>), dim3(nb), dim3(256), 0, c->stream,
                        ValLcb<T>{(const T*)v.mean->p, (const T*)v.var->p, (T)o->b, 0.0, 0.0}, (const uint8_t*)c->maskM.p, n,
                        (long long)c->cs.first, (Best*)c->partial.p, gb_of<T>(c, v));

@@ -265,11 +265,9 @@ static int rc_refine(sbo_ctx* c, const long long* list, long long nf, bool guard
   DevBuf& pbuf = guard ? c->gb.pts : s->pts;
   if ((rc = ensure(pbuf, sizeof(double) * (size_t)nf * d))) return rc;
   const unsigned nbf = (unsigned)std::max<long long>(1, std::min<long long>((nf + 255) / 256, 4096));
-  switch (c->mc.dpad) {
-    case 2: hipLaunchKernelGGL(k_rc_gather<2>, dim3(nbf), dim3(256), 0, c->stream, c->cs, list, nf, (double*)pbuf.p); break;
-    case 4: hipLaunchKernelGGL(k_rc_gather<4>, dim3(nbf), dim3(256), 0, c->stream, c->cs, list, nf, (double*)pbuf.p); break;
-    default: hipLaunchKernelGGL(k_rc_gather<8>, dim3(nbf), dim3(256), 0, c->stream, c->cs, list, nf, (double*)pbuf.p); break;
-  }
+  with_dpad(c->mc.dpad, [&](auto D) {
+    hipLaunchKernelGGL(k_rc_gather<D()>, dim3(nbf), dim3(256), 0, c->stream, c->cs, list, nf, (double*)pbuf.p);
+  });
   if (guard) {
     if ((rc = ensure(c->gb.vals, sizeof(double) * 2 * (size_t)nf * q))) return rc;
     double* em = (double*)c->gb.vals.p;
@@ -310,15 +308,10 @@ static int rc_lipschitz64(sbo_ctx* c, const sbo_ctx* s) {
   const long long n = c->cs.n_local;
   SBO_HIP(hipMemsetAsync(c->Lmax, 0, sizeof(unsigned long long) * kMaxQ, c->stream));
   const unsigned nbg = (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)c->n_cu * 8));
-#define SBO_GRAD(DD)                                                                                                              \
-  hipLaunchKernelGGL(k_rc_grad64<DD>, dim3(nbg), dim3(256), 0, c->stream, s->mc, c->cs, (const double*)s->As.p, (const double*)s->sqA.p, \
-                     (const double*)s->alpha.p, (const double*)s->Xn.p, c->Lmax)
-  switch (c->mc.dpad) {
-    case 2: SBO_GRAD(2); break;
-    case 4: SBO_GRAD(4); break;
-    default: SBO_GRAD(8); break;
-  }
-#undef SBO_GRAD
+  with_dpad(c->mc.dpad, [&](auto D) {
+    hipLaunchKernelGGL(k_rc_grad64<D()>, dim3(nbg), dim3(256), 0, c->stream, s->mc, c->cs, (const double*)s->As.p, (const double*)s->sqA.p,
+                       (const double*)s->alpha.p, (const double*)s->Xn.p, c->Lmax);
+  });
   SBO_HIP(hipGetLastError());
   return SBO_OK;
 }
@@ -793,11 +786,9 @@ static int sweep_tr_recheck(sbo_ctx* c, const sbo_sweep_opts* o, const double* x
     double* dev_x0 = (double*)c->lane[0].scal.p + 256;
     SBO_HIP(hipMemcpyAsync(dev_x0, x0, sizeof(double) * c->cs.d, hipMemcpyHostToDevice, c->stream));
     const unsigned nbk = (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)c->n_cu * 4));
-    switch (c->mc.dpad) {
-      case 2: hipLaunchKernelGGL((k_rc_ball<2>), dim3(nbk), dim3(256), 0, c->stream, c->cs, n, (const double*)dev_x0, r, (uint8_t*)c->maskM.p); break;
-      case 4: hipLaunchKernelGGL((k_rc_ball<4>), dim3(nbk), dim3(256), 0, c->stream, c->cs, n, (const double*)dev_x0, r, (uint8_t*)c->maskM.p); break;
-      default: hipLaunchKernelGGL((k_rc_ball<8>), dim3(nbk), dim3(256), 0, c->stream, c->cs, n, (const double*)dev_x0, r, (uint8_t*)c->maskM.p); break;
-    }
+    with_dpad(c->mc.dpad, [&](auto D) {
+      hipLaunchKernelGGL((k_rc_ball<D()>), dim3(nbk), dim3(256), 0, c->stream, c->cs, n, (const double*)dev_x0, r, (uint8_t*)c->maskM.p);
+    });
     if ((rc = rc_argmin_contenders(c, o, bd, (const uint8_t*)c->maskM.p, 1, &more, kGuard))) return rc;
     total += more;
   }
