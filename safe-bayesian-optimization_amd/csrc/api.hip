@@ -66,9 +66,8 @@ int factor_sync(sbo_ctx* c) {
   if (!c->factor_pending) return SBO_OK;
   SBO_HIP(hipEventSynchronize(c->ev_factor));
   c->factor_pending = false;
-  const int* hbad = (const int*)(c->h_back + 4864);
   for (int o = 0; o < c->mc.q; ++o)
-    if (hbad[o]) {
+    if (c->h_back->factor_bad[o]) {
       c->has_model = false;
       return fail(SBO_E_INVALID, "invK is not positive definite (its factor was needed by this call)");
     }
@@ -156,7 +155,7 @@ int sbo_init(int device_id, sbo_ctx** out) {
     if (e != hipSuccess) return hip_fail(e, "hipEventCreate");
   }
   if (hipHostMalloc(&own.h_c1.p, sizeof(unsigned long long) * (1 + 2 * kMaxQ), hipHostMallocDefault) != hipSuccess) return fail(SBO_E_HIP, "hipHostMalloc");
-  if (hipHostMalloc(&own.h_back.p, 8192, hipHostMallocDefault) != hipSuccess) return fail(SBO_E_HIP, "hipHostMalloc");
+  if (hipHostMalloc(&own.h_back.p, sizeof(PinnedBack), hipHostMallocDefault) != hipSuccess) return fail(SBO_E_HIP, "hipHostMalloc");
   // the handles the code uses (the twin gets copies of some: shadow_ensure)
   c->stream = own.stream.s, c->stream2 = own.stream2.s, c->stream3 = own.stream3.s, c->stream_audit = own.stream_audit.s, c->stream4 = own.stream4.s;
   c->ev_factor = own.ev_factor.e, c->ev_w = own.ev_w.e;
@@ -166,15 +165,13 @@ int sbo_init(int device_id, sbo_ctx** out) {
   for (int i = 0; i < 4; ++i) c->ev_grad[i] = own.ev_grad[i].e;
   for (int i = 0; i < 2; ++i) c->audit.ev[i] = own.ev_audit[i].e;
   c->dist.h_c1 = (unsigned long long*)own.h_c1.p;
-  c->h_back = (unsigned char*)own.h_back.p;
-  // the sweep's scalar block and, 3 KB further, the Lipschitz keys: one allocation, so one read-back covers both
-  // (layout of the 4 KB: SweepScalars at 0, the explore target / trust-region centre at 2048, the keys at 3072, a
-  // collective's scratch word at 4000)
+  c->h_back = (PinnedBack*)own.h_back.p;
+  // the sweep's scalar block with the Lipschitz keys in it (internal.hpp: ScalBlock)
   c->lane[0].stream = c->stream;
   c->lane[1].stream = c->stream2;
-  int rc = ensure(c->lane[0].scal, 4096);
+  int rc = ensure(c->lane[0].scal, sizeof(ScalBlock));
   if (rc) return rc;
-  c->Lmax = (unsigned long long*)((char*)c->lane[0].scal.p + 3072);
+  c->Lmax = scal_block(c)->lip_keys;
   *out = guard.release();
   return SBO_OK;
 }
@@ -204,9 +201,9 @@ static int shadow_ensure(sbo_ctx* c) {
   s->opt.bilinear = 0;
   s->lane[0].stream = c->stream;
   s->lane[1].stream = c->stream2;
-  int rc = ensure(s->lane[0].scal, 4096);
+  int rc = ensure(s->lane[0].scal, sizeof(ScalBlock));
   if (rc) return rc;
-  s->Lmax = (unsigned long long*)((char*)s->lane[0].scal.p + 3072);
+  s->Lmax = scal_block(s)->lip_keys;
   c->recheck.shadow = guard.release();
   return SBO_OK;
 }
@@ -809,7 +806,7 @@ int sbo_profile_get(sbo_ctx* c, sbo_profile* out) {
       GuardBand hb;
       if (c->gb.mirrored) {
         // (the plan's band kernel wrote a copy into the pinned block; the sweep whose posterior is valid has synchronised since)
-        memcpy(&hb, c->h_back + kGbMirrorOffset, sizeof(hb));
+        memcpy(&hb, c->h_back->guard_band, sizeof(hb));
       } else {
         SBO_HIP(hipSetDevice(c->device));
         SBO_HIP(hipMemcpyAsync(&hb, c->gb.buf.p, sizeof(hb), hipMemcpyDeviceToHost, c->stream));

@@ -1567,7 +1567,7 @@ int bilinear_basis_enqueue(sbo_ctx* c, hipStream_t st, bool force_big) {
       }
     }
   }
-  SBO_HIP(hipMemcpyAsync(c->h_back + 4096, base + L.info, sizeof(int) * 8 * q, hipMemcpyDeviceToHost, st));
+  SBO_HIP(hipMemcpyAsync(c->h_back->basis_info, base + L.info, sizeof(int) * 8 * q, hipMemcpyDeviceToHost, st));
   for (int t = 0; t < 4; ++t) c->bl_basis_ab[t] = ab[t];
   c->bl_basis_serial = c->model_serial;
   c->bl_basis_ok = true;       // (enqueued: valid once `st` has drained)
@@ -1609,7 +1609,7 @@ int bilinear_setup(sbo_ctx* c) {
     if (!c->bl_basis_ok) return SBO_OK;
     SBO_HIP(hipStreamSynchronize(c->stream));
   }
-  const int* inf = (const int*)(c->h_back + 4096);
+  const int* inf = c->h_back->basis_info;
   for (int t = 0; t < 2 * q; ++t)
     if (inf[4 * t] == 2) {                 // the small form of the basis kernel needs more LDS than it has: the big form
       if ((rc = bilinear_basis_enqueue(c, c->stream, true))) return rc;
@@ -1818,7 +1818,7 @@ int bilinear_setup(sbo_ctx* c) {
     hipLaunchKernelGGL(k_cheb_trunc, dim3(uq), dim3(1024), 0, xs, dm, (const double*)Chat, c->opt.cheb_tol, eff);
     hipLaunchKernelGGL(k_cheb_t4f, blocks(g.sT4f, uq), dim3(256), 0, xs, dm, (const double*)Chat, g.sT4f, (double*)c->bl_T4f.p);
     // (the counts also travel to the host, unwaited: the profile's flop count reads them after the next sweep's own sync)
-    SBO_HIP(hipMemcpyAsync(c->h_back + 5376, eff, sizeof(int) * 4 * q, hipMemcpyDeviceToHost, xs));
+    SBO_HIP(hipMemcpyAsync(c->h_back->tile_eff, eff, sizeof(int) * 4 * q, hipMemcpyDeviceToHost, xs));
     g.eff = eff;
   }
   if (ys != xs) SBO_HIP(hipStreamWaitEvent(xs, c->ev_join[3], 0));

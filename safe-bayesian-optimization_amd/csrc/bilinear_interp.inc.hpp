@@ -544,7 +544,7 @@ int interp_setup(sbo_ctx* c) {
                        (const int*)eff, (const double*)dxn0, (const double*)dxn1, raw);
     hipLaunchKernelGGL(k_gb_band_i, dim3(1), dim3(256), 0, bs, dP, (const double*)raw, (const double*)gref_m, (const double*)gref_v,
                        (const double*)pgrad, reinterpret_cast<const double*>(eff + 4 * QP), (const double*)c->alpha64.p, c->a_ld, (GuardBand*)c->gb.buf.p,
-                       (GuardBand*)(c->h_back + kGbMirrorOffset));
+                       (GuardBand*)c->h_back->guard_band);
     c->gb.mirrored = true;
     if (defer) SBO_HIP(hipEventRecord(c->ev_grad[3], bs));
   }

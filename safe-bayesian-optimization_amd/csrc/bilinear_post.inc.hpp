@@ -1477,7 +1477,7 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
     // Chebyshev core: the counts the kernels actually run to (k_cheb_trunc; copied to the pinned block when the plan was built --
     // they have arrived long before a sweep's result is read: a plan build is followed by the sweep's own synchronisation
     // before anyone asks for the profile).  Until then the upper bound above stands.
-    const int* he = (const int*)(c->h_back + 5376);
+    const int* he = c->h_back->tile_eff;
     double f = 0.0;
     bool ok = true;
     for (int o = 0; o < q; ++o) {

@@ -158,7 +158,7 @@ int sbo_comm_init_relay(sbo_ctx* c, int world_size, int rank, sbo_relay_allreduc
 int sbo_comm_barrier(sbo_ctx* c) {
   if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
   if (multi_rank(c)) {
-    int rc = comm_allreduce_sum_f64(c, (double*)c->lane[0].scal.p + 500, 1);
+    int rc = comm_allreduce_sum_f64(c, &scal_block(c)->comm_word, 1);
     if (rc) return rc;
   }
   SBO_HIP(hipStreamSynchronize(c->stream));

@@ -131,6 +131,7 @@ struct GuardBand {
   double dm[kMaxQ], dv[kMaxQ], rl[kMaxQ];
   double an_m[kMaxQ], an_v[kMaxQ], pr_m[kMaxQ], pr_v[kMaxQ];
 };
+static_assert(sizeof(GuardBand) <= sizeof(PinnedBack::guard_band), "the band kernels write the block into PinnedBack::guard_band");
 constexpr double kGbSafety = 16.0;
 // worst-case rounding of the reference formula's sums in any order (un-normalised units): n eps sum_j |alpha_j k_j| <= n eps sf2 ||alpha||_1
 // and 2 n eps |k|^T |A| |k| <= 2 n eps ||k||_2^2 || |A| ||_2 <= 2 n eps (n sf2^2) (sqrt(n) / sn2)

@@ -439,7 +439,7 @@ int guard_probe_gradients(sbo_ctx* c, hipStream_t st, double* ppts, double* grad
 }
 int guard_band_from_probes(sbo_ctx* c, const double* pm, const double* pv, const double* ref_m, const double* ref_v, const double* tail, const GbAnalytic& an) {
   hipLaunchKernelGGL(k_gb_band, dim3(1), dim3(256), 0, c->stream, c->mc, pm, pv, ref_m, ref_v, tail, an, (GuardBand*)c->gb.buf.p,
-                     (GuardBand*)(c->h_back + kGbMirrorOffset));
+                     (GuardBand*)c->h_back->guard_band);
   c->gb.mirrored = true;
   SBO_HIP(hipGetLastError());
   return SBO_OK;
@@ -534,7 +534,7 @@ void guard_audit_harvest(sbo_ctx* c, bool wait) {
   if (!c->audit.pending) return;
   if (wait) (void)hipEventSynchronize(c->audit.ev[1]);
   else if (hipEventQuery(c->audit.ev[1]) != hipSuccess) return;
-  const unsigned long long* hc = (const unsigned long long*)(c->h_back + 7168);
+  const unsigned long long* hc = c->h_back->audit;
   c->audit.violations += (long long)hc[0];
   c->audit.samples += (long long)hc[1];
   c->audit.skipped += (long long)hc[3];
@@ -590,7 +590,7 @@ int guard_audit_enqueue(sbo_ctx* c, const PostOutcome& out) {
   if ((rc = launch_ref<2>(c, st, (const double*)c->audit.pts.p, P, 0, ref_m, ref_v, nullptr, &c->audit.part))) return rc;
   hipLaunchKernelGGL(k_audit_compare, dim3(8), dim3(256), 0, st, P, q, first_output, (const double*)apx, (const double*)ref_m, (const double*)ref_v,
                      (const GuardBand*)gb_snap, (unsigned long long*)c->audit.cnt.p, c->opt.audit_scale, encl ? (const double*)aenc : (const double*)nullptr);
-  SBO_HIP(hipMemcpyAsync(c->h_back + 7168, c->audit.cnt.p, 32, hipMemcpyDeviceToHost, st));
+  SBO_HIP(hipMemcpyAsync(c->h_back->audit, c->audit.cnt.p, sizeof(c->h_back->audit), hipMemcpyDeviceToHost, st));
   SBO_HIP(hipEventRecord(c->audit.ev[1], st));
   SBO_HIP(hipGetLastError());
   c->audit.pending = true;

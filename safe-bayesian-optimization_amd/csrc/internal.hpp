@@ -1,6 +1,7 @@
 // internal.hpp -- shared declarations of libsafebo.so (host side + kernel argument blocks).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <string>
 #include <type_traits>
@@ -15,7 +16,52 @@ namespace sbo {
 constexpr int kGuardRefMaxNpad = 1008;
 constexpr int kMaxD = SBO_MAX_D;
 constexpr int kMaxQ = SBO_MAX_Q;
-constexpr int kGbMirrorOffset = 7680;   // pinned landing block h_back: [0, 4096) end-of-sweep read-back | 4096 plan records | 7168 audit counts | 7680 guard band
+
+// ---- The three small shared blocks, each laid out once.  A member is a region at a fixed offset with room for its largest writer (its pad:
+// the region's size less the member's); the asserts fail the build when a region moves, overlaps the next one or is too small.  SweepScalars
+// and GuardBand are defined later (sets.hip, device_common.hpp): their regions are bytes here, the assert on their size stands at the type.
+// Recheck::list (sets_recheck.inc.hpp) = RcHead, then the list of flagged candidates.  A recheck reads back the part in front of gkeys.
+struct RcScal {
+  unsigned long long ulo_key, uhi_key, vmax_key;   // interval of u*, lower end of the largest variance over M
+  long long count;                                 // length of the first list (k_rc_flag)
+};
+struct RcHead {
+  RcScal sc;
+  unsigned long long deferred;       // candidates a set phase deferred (RcExp, k_rc_gdefer) / contenders of an arg-min (k_rc_lflag)
+  unsigned long long lmin_key;       // rc_argmin_contenders: min over the mask of the upper end of lcb_0
+  unsigned long long all_ranks;      // rc_count_all: the largest `deferred` over the ranks (the collective's word)
+  unsigned long long all_ranks_back; // ... and where that word lands in the pinned copy (on the device: unused)
+  unsigned long long gkeys[kMaxQ];   // k_rc_gmax: per constraint, max over G_c of the lower end of var_0
+  unsigned char pad[192 - sizeof(gkeys)];
+};
+static_assert(offsetof(RcHead, deferred) == 32 && offsetof(RcHead, lmin_key) == 40 && offsetof(RcHead, all_ranks) == 48 &&
+              offsetof(RcHead, all_ranks_back) == 56 && offsetof(RcHead, gkeys) == 64 && sizeof(RcHead) == 256, "RcHead");
+// The 4 KB device scalar block of lane 0 (SetLane::scal): one allocation, so that one read-back covers the scalars and the keys.
+struct ScalBlock {
+  unsigned char scalars[2048];                                                         // SweepScalars (sets.hip)
+  double point[kMaxD]; unsigned char pad0[1024 - sizeof(point)];                       // the explore target / trust-region centre
+  unsigned long long lip_keys[kMaxQ]; unsigned char pad1[928 - sizeof(lip_keys)];      // sbo_ctx::Lmax
+  double comm_word; unsigned char pad2[96 - sizeof(comm_word)];                        // sbo_comm_barrier's all-reduce word
+};
+static_assert(offsetof(ScalBlock, point) == 2048 && offsetof(ScalBlock, lip_keys) == 3072 && offsetof(ScalBlock, comm_word) == 4000 &&
+              sizeof(ScalBlock) == 4096, "ScalBlock");
+// The 8 KB pinned landing block sbo_ctx::h_back: where the small device-to-host copies of a call land, and what the last kernel of a
+// sweep or a plan's band kernel writes itself (`mirror`).  Its head is the image of ScalBlock's, up to the end of lip_keys.
+struct PinnedBack {
+  unsigned char scalars[2048], pad0[1024];                                             // SweepScalars (its first kScalHost bytes are read)
+  unsigned long long lip_keys[kMaxQ]; unsigned char pad1[1024 - sizeof(lip_keys)];     // k_sweep_finals, k_arg_final_mirror, k_col_finals write
+  int basis_info[8 * kMaxQ]; unsigned char pad2[512 - sizeof(basis_info)];             // K1b: 4 ints per axis basis (bilinear.hip)
+  int build_bad[kMaxQ]; unsigned char pad3[256 - sizeof(build_bad)];                   // the model build's verdict per output (model.hip)
+  int factor_bad[kMaxQ]; unsigned char pad4[256 - sizeof(factor_bad)];                 // the deferred factor chain's (factor_sync reads)
+  RcHead rc;                                                                           // a recheck's counters (sets_recheck.inc.hpp)
+  int tile_eff[4 * kMaxQ]; unsigned char pad5[1792 - sizeof(tile_eff)];                // K1b: the counts its kernels run to (k_cheb_trunc)
+  unsigned long long audit[4]; unsigned char pad6[512 - sizeof(audit)];                // the standing audit's counters (guard.hip)
+  unsigned char guard_band[512];                                                       // GuardBand, written by the plan's band kernel
+};
+static_assert(offsetof(PinnedBack, lip_keys) == offsetof(ScalBlock, lip_keys) && offsetof(PinnedBack, basis_info) == 4096 &&
+              offsetof(PinnedBack, build_bad) == 4608 && offsetof(PinnedBack, factor_bad) == 4864 && offsetof(PinnedBack, rc) == 5120 &&
+              offsetof(PinnedBack, tile_eff) == 5376 && offsetof(PinnedBack, audit) == 7168 && offsetof(PinnedBack, guard_band) == 7680 &&
+              sizeof(PinnedBack) == 8192, "PinnedBack");
 
 // Model constants handed to kernels by value (kernarg segment).  Everything is kept in double; the
 // fp32 kernels round on use.  Rows a1/a4 of SURVEY.md section 8 (models/GP_Safe.py:236-245, 326-347).
@@ -258,7 +304,7 @@ struct ResidentBand {
                                 // (a fact about the resident arrays, kept between calls; what a running set phase makes of it: SetView in sets.hip)
   DevBuf buf;                   // GuardBand of the resident posterior
   long long first = 0;          // decisions the first pass of the running sweep left open
-  bool mirrored = false;        // the plan's band kernel also wrote the block to pinned host memory (h_back + kGbMirrorOffset): valid once a sweep has synchronised
+  bool mirrored = false;        // the plan's band kernel also wrote the block to pinned host memory (PinnedBack::guard_band): valid once a sweep has synchronised
   bool host_valid = false;      // `host` mirrors `buf` (read back on demand by sbo_profile_get; dropped when a plan writes the block)
   double host[7 * SBO_MAX_Q] = {0};   // dm | dv | rl | analytic dm | dv | largest probe deviation dm | dv
   DevBuf pts, vals;             // re-evaluation: coordinates and exact values of the listed candidates
@@ -341,7 +387,7 @@ struct MultiRank {
 struct Recheck {
   sbo_ctx* shadow = nullptr;
   DevBuf mean, var;         // double [q][n_local]: the fp32 posterior widened, flagged entries replaced by fp64 values (what the recheck's set phases read)
-  DevBuf list;              // flagged candidate indices (long long) + counters (64-byte head)
+  DevBuf list;              // RcHead, then the flagged candidate indices (long long)
   DevBuf refined;           // uint8 [n_local]: this candidate's entries of mean / var are fp64 values
   // the band of the resident fp32 posterior (sets_recheck.inc.hpp: rc_bands): max(1e-4 normalised, 16 x the largest |fp32 - fp64 twin| over
   // the probe candidates), measured when an fp32 sweep first meets this (model, candidate set); dropped by plans_invalidate
@@ -466,7 +512,7 @@ struct sbo_ctx {
   sbo::BilinearPlan bl;
   sbo::DevBuf bl_P0f, bl_P1A, bl_T4f, bl_BtA, bl_SBf, bl_VA, bl_small, bl_work, bl_cheb;
   sbo::DevBuf bl_basis;            // K1b: the 2 q axis bases (U, Chebyshev series, ranks) and the workspace of their kernel
-  bool bl_basis_ok = false;        // bases enqueued for (bl_basis_serial, bl_basis_ab); their (ok, r, rc) records land at h_back + 4096
+  bool bl_basis_ok = false;        // bases enqueued for (bl_basis_serial, bl_basis_ab); their (ok, r, rc) records land in PinnedBack::basis_info
   unsigned long long bl_basis_serial = 0;
   double bl_basis_ab[4] = {0, 0, 0, 0};
   sbo::DevBuf bl_grad;  // K1b: which tiles run the gradient phases (per plan)
@@ -499,7 +545,7 @@ struct sbo_ctx {
   bool post_l0_missing = false;  // the resident posterior came from a lean sweep's launch: L_0 (Lmax[0]) was not computed
   int last_k1 = 0;               // kernel family of the last posterior launch (sbo_profile.posterior_kernel)
   double last_k1_flops = 0.0;    // matrix-core flops it issued
-  unsigned long long* Lmax = nullptr;   // [kMaxQ] keys: max ||grad MEAN_i||_inf over the candidates -- a view: lane[0].scal + 3072
+  unsigned long long* Lmax = nullptr;   // [kMaxQ] keys: max ||grad MEAN_i||_inf over the candidates -- a view: ScalBlock::lip_keys of lane[0].scal
   // set workspace
   sbo::DevBuf maskS, maskU, maskM, maskG, maskO;   // uint8 [n_local] (G/O: [(q-1)][n_local])
   sbo::DevBuf fitbuf, fitwork;   // hyper-parameter objective: inputs/outputs and the P x n x n factor workspace
@@ -523,8 +569,8 @@ struct sbo_ctx {
     sbo::DevBuf gw;                // GoOSE: source weights (ucb_c on sources, -inf elsewhere), T [max shard]
     sbo::DevBuf runmeta;           // GoOSE: per-run bounding boxes / radii of the coverage search
     sbo::DevBuf lxtree;            // list index: this sweep's boxes of U members / sorted U mask, or GoOSE's sorted weights and masks
-    // small device scalar block (keys, counters, arg-reduce results), 4 KB.  Lane 0's is THE block of the sweep: Lmax (+ 3072),
-    // the explore target / trust-region centre (+ 2048) and a collective's scratch word (+ 4000) are views into it
+    // small device scalar block (keys, counters, arg-reduce results), 4 KB.  Lane 0's is THE block of the sweep, laid out as a
+    // ScalBlock (scal_block below); lane 1's holds a snapshot of its SweepScalars alone
     sbo::DevBuf scal;
     bool amb_clean = false;        // the recheck / scan counters of `scal` are still zero (no k_reset_amb needed)
   } lane[2];
@@ -536,7 +582,7 @@ struct sbo_ctx {
   sbo::DevBuf fuseS, fuseU;   // [(q - 1)][N] byte planes of a fused classification of several constraints (r05)
   sbo::ColPath col;
   sbo::MultiRank dist;
-  unsigned char* h_back = nullptr;        // pinned host landing area of the end-of-sweep read-back (scalars + Lipschitz keys)
+  sbo::PinnedBack* h_back = nullptr;      // pinned host landing block (the twin borrows its owner's)
   int last_sweep = 0;  // 1 safeopt, 2 goose (what the masks hold)
   bool masks_valid = false;
   // profile
@@ -553,6 +599,7 @@ inline sbo::Recheck::~Recheck() { delete shadow; }
 namespace sbo {
 // the sweeps take their multi-rank path (pack, collective, unpack, host merge): more than one rank, or the self-test
 inline bool multi_rank(const sbo_ctx* c) { return c->dist.world > 1 || c->opt.comm_selftest; }
+inline ScalBlock* scal_block(const sbo_ctx* c) { return (ScalBlock*)c->lane[0].scal.p; }
 // the guard band of the resident posterior of an fp64 model (device_common.hpp: GuardBand), when an approximating kernel (K1b / K1i / K1t)
 // wrote it and option guard_band is on; nullptr: the values are the exact kernels'
 struct GuardBand;

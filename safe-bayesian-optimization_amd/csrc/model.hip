@@ -943,7 +943,7 @@ static int model_build_t(sbo_ctx* c, const double* const* host_invK /* q matrice
   if ((rc = factor_chain_enqueue<T>(c, w, mode, c->stream))) return rc;
   hipLaunchKernelGGL((k_cast_alpha<T>), dim3(16), dim3(256), 0, c->stream, (const double*)dalpha, npad, n, q, npad, (T*)c->alpha.p);
   SBO_HIP(hipGetLastError());
-  int* hbad = (int*)(c->h_back + 4608);
+  int* hbad = c->h_back->build_bad;
   SBO_HIP(hipMemcpyAsync(hbad, w.bad, sizeof(int) * q, hipMemcpyDeviceToHost, c->stream));
   SBO_HIP(stream_wait(c, c->stream));
   if (eager_basis) SBO_HIP(stream_wait(c, c->stream2));
@@ -979,7 +979,7 @@ int model_factor_enqueue(sbo_ctx* c) {
   if (rc) return rc;
   SBO_HIP(hipStreamWaitEvent(c->stream4, c->ev_w, 0));
   if ((rc = factor_chain_enqueue<double>(c, w, 0, c->stream4))) return rc;
-  SBO_HIP(hipMemcpyAsync(c->h_back + 4864, w.bad, sizeof(int) * c->mc.q, hipMemcpyDeviceToHost, c->stream4));
+  SBO_HIP(hipMemcpyAsync(c->h_back->factor_bad, w.bad, sizeof(int) * c->mc.q, hipMemcpyDeviceToHost, c->stream4));
   SBO_HIP(hipEventRecord(c->ev_factor, c->stream4));
   c->factor_pending = true;
   return SBO_OK;

@@ -63,6 +63,7 @@ struct SweepScalars {
   long long arg_ei[kArgSlots];             //   candidate (ranks > 1: merged by the host from the C3 rows)
 };
 constexpr size_t kScalHost = offsetof(SweepScalars, ticket);
+static_assert(sizeof(SweepScalars) <= sizeof(ScalBlock::scalars) && sizeof(SweepScalars) <= sizeof(PinnedBack::scalars), "SweepScalars fits its region of the scalar block and of the pinned block");
 
 // Result of a masked arg-reduction over values known to +- d.  (v, i): the winner, ties -> lowest flat index; d: its band;
 // e1 / e2: the two most extreme FAR ends over all candidates (v + d for an arg-max: how high could it be; v - d for an
@@ -907,8 +908,8 @@ __global__ __launch_bounds__(256) void k_sweep_finals(const unsigned char* __res
     sc->n_amb_total += lane1->n_amb_total;
     sc->n_guard += lane1->n_guard - lane1->n_guard_cls;      // (the lane's block started as a snapshot: its own additions only)
   }
-  // `mirror`: the results go straight to the pinned host block the read-back would have filled (SweepScalars at 0, the
-  // Lipschitz keys at 3072) -- every workgroup its own slot, workgroup 0 the fields earlier kernels finished --, and the
+  // `mirror`: the results go straight to the pinned host block the read-back would have filled (PinnedBack: scalars,
+  // lip_keys) -- every workgroup its own slot, workgroup 0 the fields earlier kernels finished --, and the
   // sweep's end event rides on this launch: no copy kernel and no barrier packet behind the last kernel.
   SweepScalars* hm = reinterpret_cast<SweepScalars*>(mirror);
   if (mirror && blockIdx.x == 0) {
@@ -923,7 +924,7 @@ __global__ __launch_bounds__(256) void k_sweep_finals(const unsigned char* __res
     }
     if (threadIdx.x < kMaxQ) {
       hm->rmax_key[threadIdx.x] = sc->rmax_key[threadIdx.x];
-      reinterpret_cast<unsigned long long*>(mirror + 3072)[threadIdx.x] = Lkeys[threadIdx.x];
+      reinterpret_cast<unsigned long long*>(mirror + offsetof(PinnedBack, lip_keys))[threadIdx.x] = Lkeys[threadIdx.x];
     }
     if (threadIdx.x >= 64 && threadIdx.x < 64 + kArgSlots && (int)threadIdx.x - 64 >= (int)gridDim.x) hm->guard_slot[threadIdx.x - 64] = 0;
   }
@@ -1069,14 +1070,16 @@ __global__ __launch_bounds__(256) void k_arg_final_mirror(const Best* __restrict
   const unsigned long long* from = reinterpret_cast<const unsigned long long*>(sc);
   unsigned long long* to = reinterpret_cast<unsigned long long*>(mirror);
   for (unsigned i = threadIdx.x; i < kScalHost / 8; i += blockDim.x) to[i] = from[i];     // (the host's part of the block)
-  if (threadIdx.x < kMaxQ) reinterpret_cast<unsigned long long*>(mirror + 3072)[threadIdx.x] = Lkeys[threadIdx.x];
+  if (threadIdx.x < kMaxQ) reinterpret_cast<unsigned long long*>(mirror + offsetof(PinnedBack, lip_keys))[threadIdx.x] = Lkeys[threadIdx.x];
 }
 
 // ---- host orchestration -------------------------------------------------------------------------------
-static int reduce_blocks(const sbo_ctx* c) {
-  const long long n = c->cs.n_local;
-  return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)c->n_cu * 4));   // (per-block reduction tails cost more than extra grid-stride turns: x4 measured best)
+// workgroups of 256 threads for a grid-stride pass over n items: one per 256 items, at most per_cu per CU, at least one
+static int grid_blocks(const sbo_ctx* c, long long n, int per_cu) {
+  return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)c->n_cu * per_cu));
 }
+// ... over the local candidates (per-block reduction tails cost more than extra grid-stride turns: x4 measured best)
+static int reduce_blocks(const sbo_ctx* c) { return grid_blocks(c, c->cs.n_local, 4); }
 
 // what a sweep asks of its posterior launch: K1b may classify in its mean epilogue at the sweep's confidence multiplier `b`, and
 // leaves its Lipschitz partials for the sweep (every sweep merges them in its k_classify_final)
@@ -1318,6 +1321,16 @@ static void halo_learn(sbo_ctx* c, const SweepScalars& h, const unsigned long lo
     const long long H = halo_planes(L, rmax, hl, planes_total);
     c->dist.halo_guess[cc] = H >= planes_total ? planes_total : std::min(planes_total, H + H / 4 + 2);
   }
+}
+// ranks > 1, behind the exchange of a SafeOpt / GoOSE set phase: a speculative window that was too narrow for this sweep's radii (every
+// rank sees the same keys and the same guess) -> true: the caller runs its set phase again with `o` and `v`, which now make it wait for the keys
+static bool halo_rerun(sbo_ctx* c, const SweepScalars& h, const unsigned long long* Lk, sbo_sweep_opts& o, SetView& v) {
+  if (!h.halo_short) { halo_learn(c, h, Lk, o.reference_quirk_L_index); return false; }
+  for (auto& g : c->dist.halo_guess) g = -1;
+  o.posterior_ready = 1;
+  ++c->dist.halo_reruns;
+  v.halo_rerun = true;
+  return true;
 }
 
 // G_c for constraint cidx (1..q-1) into G[n]
@@ -1872,12 +1885,9 @@ static int sweep_exchange_wait(sbo_ctx* c) {
 static int sweep_exchange_back(sbo_ctx* c, SweepScalars& h, const bool* slot_is_max, unsigned long long* Lk = nullptr,
                                hipEvent_t done_ev = nullptr, bool mirrored = false /* the last kernel wrote h_back and carries done_ev */) {
   SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
-  // (the Lipschitz keys ride in the same read-back: one synchronisation per sweep)
+  // (the Lipschitz keys ride in the same read-back -- ScalBlock; PinnedBack's head is its image --: one synchronisation per sweep)
   // (pinned landing area: pageable destinations are staged by the runtime, ~20 us per copy)
-  // (the Lipschitz keys live 3 KB into the same allocation: sbo_create)
-  static_assert(sizeof(SweepScalars) <= 2048 && sizeof(unsigned long long) * kMaxQ <= 512, "read-back area");
-  constexpr size_t kBack = 3072 + sizeof(unsigned long long) * kMaxQ;
-  const unsigned long long* Lk_pinned = (const unsigned long long*)(c->h_back + 3072);
+  constexpr size_t kBack = offsetof(ScalBlock, lip_keys) + sizeof(ScalBlock::lip_keys);
   if (!multi_rank(c)) {
     if (!mirrored) {
       SBO_HIP(hipMemcpyAsync(c->h_back, sc, kBack, hipMemcpyDeviceToHost, c->stream));
@@ -1891,8 +1901,8 @@ static int sweep_exchange_back(sbo_ctx* c, SweepScalars& h, const bool* slot_is_
     SBO_HIP(stream_wait(c, c->stream));
     ++c->host_syncs;
     memset(&h, 0, sizeof(h));
-    memcpy(&h, c->h_back, kScalHost);
-    if (Lk) memcpy(Lk, Lk_pinned, sizeof(unsigned long long) * kMaxQ);
+    memcpy(&h, c->h_back->scalars, kScalHost);
+    if (Lk) memcpy(Lk, c->h_back->lip_keys, sizeof(unsigned long long) * kMaxQ);
     // decisions the guard band of an approximating posterior leaves open: the classification's and the verdict kernels' count
     // plus what the final reductions found in their slots
     if (getenv("SBO_DEBUG_GUARD") && c->gb.active) {
@@ -1915,8 +1925,8 @@ static int sweep_exchange_back(sbo_ctx* c, SweepScalars& h, const bool* slot_is_
   SBO_HIP(stream_wait(c, c->stream));
   ++c->host_syncs;
   memset(&h, 0, sizeof(h));
-  memcpy(&h, c->h_back, kScalHost);
-  if (Lk) memcpy(Lk, Lk_pinned, sizeof(unsigned long long) * kMaxQ);
+  memcpy(&h, c->h_back->scalars, kScalHost);
+  if (Lk) memcpy(Lk, c->h_back->lip_keys, sizeof(unsigned long long) * kMaxQ);
   c->dist.c1_pending = false;                       // (the whole stream has drained)
   h.count_S = h.count_U = h.count_M = h.n_amb_total = h.n_guard = 0;
   h.halo_short = 0;                            // GLOBAL: a rank that alone reran its set phase would leave the others in a collective
@@ -2101,7 +2111,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v
   hipExtLaunchKernelGGL(k_sweep_finals<true>, dim3((unsigned)q), dim3(256), 0, c->stream, nullptr, mirrored ? c->ev[4] : nullptr, 0,
                         (const unsigned char*)pbase, pstride, n > 0 ? nb : 0, sc,
                         lanes ? (const SweepScalars*)c->lane[1].scal.p : (const SweepScalars*)nullptr,
-                        mirrored ? c->h_back : (unsigned char*)nullptr, c->Lmax, gb_of<T>(c, v) ? 1 : 0);
+                        mirrored ? (unsigned char*)c->h_back : (unsigned char*)nullptr, c->Lmax, gb_of<T>(c, v) ? 1 : 0);
   SBO_HIP(hipGetLastError());
   bool is_max[kArgSlots];
   for (int t = 0; t < kArgSlots; ++t) is_max[t] = true;
@@ -2115,24 +2125,15 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v
                        pstride, 1, gb_of<T>(c, v));
     hipLaunchKernelGGL(k_sweep_clear_slot, dim3(1), dim3(1), 0, c->stream, sc, 1);
     hipExtLaunchKernelGGL(k_sweep_finals<true>, dim3((unsigned)q), dim3(256), 0, c->stream, nullptr, c->ev[4], 0,
-                          (const unsigned char*)pbase, pstride, nb, sc, (const SweepScalars*)nullptr, c->h_back,
+                          (const unsigned char*)pbase, pstride, nb, sc, (const SweepScalars*)nullptr, (unsigned char*)c->h_back,
                           c->Lmax, gb_of<T>(c, v) ? 1 : 0);
     SBO_HIP(hipGetLastError());
     if ((rc = sweep_exchange_back(c, h, is_max, Lk, c->ev[4], true))) return rc;
   }
   if (multi_rank(c)) {
-    if (h.halo_short) {
-      // a speculative window was too narrow for this sweep's radii (every rank sees the same keys and the same guess): the set
-      // phase again, this time waiting for the keys
-      for (auto& g : c->dist.halo_guess) g = -1;
-      sbo_sweep_opts o2 = *o;
-      o2.posterior_ready = 1;
-      ++c->dist.halo_reruns;
-      SetView v2 = v;
-      v2.halo_rerun = true;
-      return sweep_safeopt_t<T>(c, &o2, v2, res);
-    }
-    halo_learn(c, h, Lk, o->reference_quirk_L_index);
+    sbo_sweep_opts o2 = *o;
+    SetView v2 = v;
+    if (halo_rerun(c, h, Lk, o2, v2)) return sweep_safeopt_t<T>(c, &o2, v2, res);
   }
   }      // (byte-mask path)
   c->masks_valid = true;
@@ -2516,7 +2517,7 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   // Single rank: the explore step (target choice, distances, arg-min over S) is enqueued before the read-back, one host
   // round trip per sweep; ranks > 1 need the merged target slots first and take a second one below.
   const bool fused_explore = !multi_rank(c) && q > 1;
-  double* dev_t = (double*)c->lane[0].scal.p + 256;
+  double* dev_t = scal_block(c)->point;
   // (one rank: the finals and the target choice in one launch, the last merge writes the host's block itself)
   const int gbon = gb_of<T>(c, v) ? 1 : 0;
   const bool short_tail = fused_explore && c->opt.result_mirror && (c->mc.dpad == 2 || c->mc.dpad == 4 || c->mc.dpad == 8);
@@ -2528,7 +2529,7 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
     });
     if (n > 0) launch_argmin_dist<T>(c, dev_t, nb);
     hipExtLaunchKernelGGL(k_arg_final_mirror, dim3(1), dim3(256), 0, c->stream, nullptr, c->ev[4], 0, (const Best*)c->partial.p, n > 0 ? nb : 0, sc,
-                          kArgSlots - 1, c->h_back, c->Lmax, 0);
+                          kArgSlots - 1, (unsigned char*)c->h_back, c->Lmax, 0);
     SBO_HIP(hipGetLastError());
   } else {
     hipLaunchKernelGGL(k_sweep_finals<false>, dim3((unsigned)q), dim3(256), 0, c->stream, (const unsigned char*)pbase, pstride,
@@ -2548,16 +2549,9 @@ static int sweep_goose_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   unsigned long long Lk[kMaxQ];
   if ((rc = sweep_exchange_back(c, h, is_max, Lk, short_tail ? c->ev[4] : nullptr, short_tail))) return rc;
   if (multi_rank(c)) {
-    if (h.halo_short) {                     // (see sweep_safeopt_t)
-      for (auto& g : c->dist.halo_guess) g = -1;
-      sbo_sweep_opts o2 = *o;
-      o2.posterior_ready = 1;
-      ++c->dist.halo_reruns;
-      SetView v2 = v;
-      v2.halo_rerun = true;
-      return sweep_goose_t<T>(c, &o2, v2, res);
-    }
-    halo_learn(c, h, Lk, o->reference_quirk_L_index);
+    sbo_sweep_opts o2 = *o;
+    SetView v2 = v;
+    if (halo_rerun(c, h, Lk, o2, v2)) return sweep_goose_t<T>(c, &o2, v2, res);
   }
   c->masks_valid = true;
   c->last_sweep = 2;
@@ -2639,7 +2633,7 @@ static int sweep_tr_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, con
   if ((rc = sweep_common_front<T>(c, o, v, post))) return rc;
   SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
   const int nb = reduce_blocks(c);
-  double* dev_x0 = (double*)c->lane[0].scal.p + 256;
+  double* dev_x0 = scal_block(c)->point;
   SBO_HIP(hipMemcpyAsync(dev_x0, x0, sizeof(double) * c->cs.d, hipMemcpyHostToDevice, c->stream));
   if (n > 0) {
     with_dpad(c->mc.dpad, [&](auto D) {
@@ -2697,7 +2691,7 @@ __global__ void k_robust_out(const SweepScalars* sc, long long* out4) {
 int robust_argmin(sbo_ctx* c, const double* f, const double* fb, const uint8_t* mask, long long Nc, bool gb_on, long long* out4) {
   int rc;
   if ((rc = ensure(c->lane[0].scal, sizeof(SweepScalars)))) return rc;
-  const int nb = (int)std::max<long long>(1, std::min<long long>((Nc + 255) / 256, (long long)c->n_cu * 4));
+  const int nb = grid_blocks(c, Nc, 4);
   if ((rc = ensure(c->partial, partial_stride(nb)))) return rc;
   SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
   SBO_HIP(hipMemsetAsync(sc, 0, sizeof(SweepScalars), c->stream));
@@ -2787,7 +2781,7 @@ int sbo_explore_safeset(sbo_ctx* c, const double* target, int64_t* index_out, do
   if ((rc = ensure(c->partial, partial_stride(nb)))) return rc;
   if (c->col.masks_bits && n > 0) col_expand(c, c->col.S, (uint8_t*)c->maskS.p);
   SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
-  double* dev_t = (double*)c->lane[0].scal.p + 256;
+  double* dev_t = scal_block(c)->point;
   double t8[SBO_MAX_D] = {0};
   for (int a = 0; a < c->cs.d; ++a) t8[a] = target[a];
   SBO_HIP(hipMemcpyAsync(dev_t, t8, sizeof(t8), hipMemcpyHostToDevice, c->stream));

@@ -1021,7 +1021,7 @@ __global__ __launch_bounds__(256) void k_col_finals(const Best* __restrict__ reg
       hm->tiles_skipped_safe = sc->tiles_skipped_safe;
       for (int t = 0; t < kMaxQ; ++t) {
         hm->rmax_key[t] = sc->rmax_key[t];
-        reinterpret_cast<unsigned long long*>(mirror + 3072)[t] = Lkeys[t];
+        reinterpret_cast<unsigned long long*>(mirror + offsetof(PinnedBack, lip_keys))[t] = Lkeys[t];
       }
     }
   }
@@ -1189,7 +1189,7 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   const int nbg = nb;
   hipLaunchKernelGGL(k_col_min<1>, dim3((unsigned)nbg), dim3(256), 0, xs, j);
   hipExtLaunchKernelGGL(k_col_finals, dim3(nb > 2048 ? kColFinParts : 1, 2), dim3(256), 0, xs, nullptr, c->ev[4], 0, (const Best*)reg0, nb, (const Best*)reg1,
-                        nbg, sc, (const ColScal2*)sc2, fin, tickets, c->h_back, c->Lmax, gb_of<double>(c, v) ? 1 : 0, cb.slots);
+                        nbg, sc, (const ColScal2*)sc2, fin, tickets, (unsigned char*)c->h_back, c->Lmax, gb_of<double>(c, v) ? 1 : 0, cb.slots);
   c->col.slots_clean = true;
   SBO_HIP(hipGetLastError());
   bool is_max[kArgSlots];
@@ -1208,7 +1208,7 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
                        pstride, 1, gb_of<double>(c, v));
     hipLaunchKernelGGL(k_sweep_clear_slot, dim3(1), dim3(1), 0, c->stream, sc, 1);
     hipExtLaunchKernelGGL(k_sweep_finals<true>, dim3(2), dim3(256), 0, c->stream, nullptr, c->ev[4], 0, (const unsigned char*)pbase, pstride, nb, sc,
-                          (const SweepScalars*)nullptr, c->h_back, c->Lmax, gb_of<double>(c, v) ? 1 : 0);
+                          (const SweepScalars*)nullptr, (unsigned char*)c->h_back, c->Lmax, gb_of<double>(c, v) ? 1 : 0);
     SBO_HIP(hipGetLastError());
     if ((rc = sweep_exchange_back(c, h, is_max, Lk, c->ev[4], true))) return rc;
     c->col.G_bytes = true;

@@ -595,7 +595,7 @@ __device__ __forceinline__ bool lipschitz_pair(const double (&xg)[D], const doub
 // fp32 models with fp64 recheck (sets_recheck.inc.hpp): the verdict kernels see a posterior whose UNREFINED entries are
 // fp32 values, good to +- (dm, dv).  For those the ucb is an interval of half-width du; a verdict the interval cannot
 // settle sends the candidate to the refinement list instead of deciding it.  refined == nullptr: every value is exact.
-constexpr size_t kRcCount2 = 32, kRcGKeys = 64, kRcList = 256;   // layout of Recheck::list: counters, G keys, the list
+// (The list and its counter: Recheck::list, laid out as internal.hpp's RcHead.)
 // The guard band of an approximating fp64 posterior (device_common.hpp: GuardBand) rides on the same mechanism: gb_c >= 1 names
 // the constraint whose band SweepScalars::gb_du[gb_c] (one bound for every candidate of S) and relative Lipschitz band gb_rl
 // apply to entries that are not `refined`; on the fast path there is no list and an unsettled verdict is only counted

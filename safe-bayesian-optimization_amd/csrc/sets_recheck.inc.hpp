@@ -25,11 +25,6 @@
 // values replace the approximate ones IN PLACE, the Lipschitz keys are recomputed exactly, and the set phase runs again.
 #pragma once
 
-struct RcScal {                         // head of Recheck::list (256 bytes): this struct, the deferral counter at byte 32, G keys at 64
-  unsigned long long ulo_key, uhi_key, vmax_key;
-  long long count;
-};
-
 __device__ __forceinline__ void rc_interval(double m, double v, double b, double dm, double dv, double& lcb_lo, double& lcb_hi, double& ucb_lo,
                                             double& ucb_hi) {
   const double md = (double)m, vd = (double)v;
@@ -305,9 +300,8 @@ static int rc_refine(sbo_ctx* c, const long long* list, long long nf, bool guard
 // Lipschitz keys in fp64 from the double arrays of `s` (the twin of an fp32 model, or the fp64 model itself) over the
 // candidates of `c`
 static int rc_lipschitz64(sbo_ctx* c, const sbo_ctx* s) {
-  const long long n = c->cs.n_local;
   SBO_HIP(hipMemsetAsync(c->Lmax, 0, sizeof(unsigned long long) * kMaxQ, c->stream));
-  const unsigned nbg = (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)c->n_cu * 8));
+  const unsigned nbg = (unsigned)grid_blocks(c, c->cs.n_local, 8);
   with_dpad(c->mc.dpad, [&](auto D) {
     hipLaunchKernelGGL(k_rc_grad64<D()>, dim3(nbg), dim3(256), 0, c->stream, s->mc, c->cs, (const double*)s->As.p, (const double*)s->sqA.p,
                        (const double*)s->alpha.p, (const double*)s->Xn.p, c->Lmax);
@@ -449,12 +443,87 @@ static int rc_bands(sbo_ctx* c, bool guard, RcBand& bd) {
   return SBO_OK;
 }
 
-// the band an fp32 sweep ran with, for sbo_profile (the set phase inside the recheck rewrites the profile: called behind it)
-static void rc_profile_band(sbo_ctx* c, const RcBand& bd) {
+// what a recheck re-evaluated: the guard's count and passes go into the result, an fp32 sweep's count and the band it ran with into
+// sbo_profile (the set phase inside the recheck rewrites the profile: called behind it)
+template <class R>
+static void rc_report(sbo_ctx* c, bool guard, R* res, long long total, int passes, const RcBand& bd) {
+  if (guard) { res->guard_rechecks = total; res->guard_passes = passes; return; }
+  c->prof.fp64_rechecks = total;
   for (int i = 0; i < c->mc.q; ++i) {
     c->prof.fp32_band_dm[i] = bd.dm[i];
     c->prof.fp32_band_dv[i] = bd.dv[i];
   }
+}
+
+// The front of every recheck: posterior, bands, (fp32) the widened copy, the first refinement list re-evaluated, fp64 Lipschitz keys;
+// leaves the head and the list of Recheck::list ready for further rounds.  What the SafeOpt and the GoOSE / trust-region rechecks do differently:
+//   reuse      no K1 launch, the resident posterior serves; the callers' rules differ, each is stated where it is evaluated
+//   list_cap   entries of Recheck::list behind its head: what the caller's later rounds can append at most
+//   flag_mode  k_rc_flag's all_possibly_safe -- 0: the undecided and the contenders of u*, M, the minimiser; 1: every possibly-safe candidate
+//              too; 2: the undecided and the possibly safe alone --, < 0: no flag pass.  The interval passes k_rc_ustar / k_rc_vmax (with
+//              their collectives) run in front of modes 0 and 1, which decide u*, M and the minimiser from them; no other mode reads them
+//   marks      ev_join[0] in front of the posterior and ev_join[1] behind it (the SafeOpt recheck's profile)
+template <typename TP>
+static int rc_front(sbo_ctx* c, const sbo_sweep_opts* o, bool reuse, size_t list_cap, int flag_mode, bool marks, RcBand& bd, long long* total) {
+  constexpr bool kGuard = std::is_same<TP, double>::value;
+  const long long n = c->cs.n_local, n1 = std::max<long long>(n, 1);
+  const int q = c->mc.q;
+  int rc;
+  if (marks) SBO_HIP(hipEventRecord(c->ev_join[0], c->stream));
+  if (!reuse && (rc = posterior_enqueue(c, PostRequest{}, nullptr))) return rc;
+  if (marks) SBO_HIP(hipEventRecord(c->ev_join[1], c->stream));
+  if ((rc = rc_bands(c, kGuard, bd))) return rc;
+  if ((rc = ensure(c->recheck.list, sizeof(RcHead) + sizeof(long long) * list_cap))) return rc;
+  if (!kGuard) {
+    if ((rc = ensure(c->recheck.mean, sizeof(double) * (size_t)q * n1))) return rc;
+    if ((rc = ensure(c->recheck.var, sizeof(double) * (size_t)q * n1))) return rc;
+  }
+  if ((rc = ensure(c->recheck.refined, (size_t)n1))) return rc;
+  RcHead* head = (RcHead*)c->recheck.list.p;
+  RcScal* sc = &head->sc;
+  long long* list = (long long*)(head + 1);
+  SBO_HIP(hipMemsetAsync(head, 0, sizeof(RcHead), c->stream));
+  const RcScal init{~0ull, ~0ull, 0ull, 0};
+  SBO_HIP(hipMemcpyAsync(sc, &init, sizeof(init), hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemsetAsync(c->recheck.refined.p, 0, (size_t)n1, c->stream));
+  const TP *m32 = (const TP*)c->mean.p, *v32 = (const TP*)c->var.p;
+  const unsigned nbk = (unsigned)reduce_blocks(c);
+  if (flag_mode == 0 || flag_mode == 1) {
+    hipLaunchKernelGGL(k_rc_ustar<TP>, dim3(nbk), dim3(256), 0, c->stream, m32, v32, n, q, o->b, bd, sc);
+    // (ranks > 1: the interval of u* and the variance guard are global quantities -- three keys through the collectives)
+    if ((rc = comm_allreduce_min_u64(c, &sc->ulo_key, 2))) return rc;
+    hipLaunchKernelGGL(k_rc_vmax<TP>, dim3(nbk), dim3(256), 0, c->stream, m32, v32, n, q, o->b, bd, sc);
+    if ((rc = comm_allreduce_max_u64(c, &sc->vmax_key, 1))) return rc;
+  }
+  if (flag_mode >= 0) hipLaunchKernelGGL(k_rc_flag<TP>, dim3(nbk), dim3(256), 0, c->stream, m32, v32, n, q, o->b, bd, sc, list, flag_mode);
+  if (!kGuard)
+    hipLaunchKernelGGL(k_rc_widen, dim3(nbk), dim3(256), 0, c->stream, (const float*)c->mean.p, (const float*)c->var.p, (long long)q * n,
+                       (double*)c->recheck.mean.p, (double*)c->recheck.var.p);
+  SBO_HIP(hipGetLastError());
+  SBO_HIP(hipMemcpyAsync(&c->h_back->rc, head, offsetof(RcHead, gkeys), hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipStreamSynchronize(c->stream));
+  *total = c->h_back->rc.sc.count;
+  if ((rc = rc_refine(c, list, *total, kGuard))) return rc;
+  // Lipschitz keys in fp64 (the fp32 posterior kernel left fp32-accurate ones, an approximating one its own band)
+  if (q > 1 && (rc = rc_lipschitz64(c, kGuard ? c : c->recheck.shadow))) return rc;
+  return SBO_OK;
+}
+
+// The counter of a later round (RcHead::deferred) read back: *mine.  Ranks > 1: every rank goes round the same number of times --
+// the collectives of a set phase are inside it --, so "nothing left" is a global statement: *all is the largest count over the ranks.
+static int rc_count_all(sbo_ctx* c, long long* mine, long long* all) {
+  RcHead* head = (RcHead*)c->recheck.list.p;
+  RcHead& back = c->h_back->rc;
+  SBO_HIP(hipMemcpyAsync(&back, head, offsetof(RcHead, gkeys), hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipStreamSynchronize(c->stream));
+  *mine = *all = (long long)back.deferred;
+  if (!multi_rank(c)) return SBO_OK;
+  SBO_HIP(hipMemcpyAsync(&head->all_ranks, &back.deferred, sizeof(back.deferred), hipMemcpyHostToDevice, c->stream));
+  if (int rc = comm_allreduce_max_u64(c, &head->all_ranks, 1)) return rc;
+  SBO_HIP(hipMemcpyAsync(&back.all_ranks_back, &head->all_ranks, sizeof(back.all_ranks_back), hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipStreamSynchronize(c->stream));
+  *all = (long long)back.all_ranks_back;
+  return SBO_OK;
 }
 
 // TP = float: an fp32 model (posterior in fp32, the fp64 twin re-evaluates); TP = double: the guard band of an approximating fp64
@@ -466,56 +535,22 @@ static int sweep_safeopt_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeop
   const int q = c->mc.q;
   int rc;
   if (!kGuard && n == 0 && !multi_rank(c)) return sweep_safeopt_t<float>(c, o, SetView(c), res);
-  SBO_HIP(hipEventRecord(c->ev_join[0], c->stream));
-  // (guard: the posterior is resident -- unless the first pass was a lean sweep, which left part of it unwritten: K1 once more, in full)
+  // Reuse -- guard: the fast pass of this call left the posterior resident, unless it was a lean sweep, which leaves part of it
+  // unwritten and so not valid: K1 once more, in full.  fp32: the caller vouches for the resident posterior, and it must hold every
+  // Lipschitz key this sweep reports: one a lean launch left out (post_l0_missing: L_0) serves a lean sweep alone, which reports L_0 = 0.
   const bool reuse = (kGuard && c->posterior_valid) || (o->posterior_ready && c->posterior_valid && (o->lean || !c->post_l0_missing));
-  if (!reuse && (rc = posterior_enqueue(c, PostRequest{}, nullptr))) return rc;
-  SBO_HIP(hipEventRecord(c->ev_join[1], c->stream));
-  RcBand bd;
-  if ((rc = rc_bands(c, kGuard, bd))) return rc;
   // (one pass can list a candidate once per constraint in the verdict kernels and once more per constraint in k_rc_gdefer;
   // the first list -- k_rc_flag -- holds every candidate at most once)
   const size_t list_cap = (size_t)std::max<long long>(n, 1) * (size_t)(2 * std::max(1, q - 1) + 1);
-  if ((rc = ensure(c->recheck.list, kRcList + sizeof(long long) * list_cap))) return rc;
-  if (!kGuard) {
-    if ((rc = ensure(c->recheck.mean, sizeof(double) * (size_t)q * std::max<long long>(n, 1)))) return rc;
-    if ((rc = ensure(c->recheck.var, sizeof(double) * (size_t)q * std::max<long long>(n, 1)))) return rc;
-  }
-  if ((rc = ensure(c->recheck.refined, (size_t)std::max<long long>(n, 1)))) return rc;
-  RcScal* sc = (RcScal*)c->recheck.list.p;
-  unsigned long long* count2 = (unsigned long long*)((char*)c->recheck.list.p + kRcCount2);
-  unsigned long long* gkeys = (unsigned long long*)((char*)c->recheck.list.p + kRcGKeys);
-  long long* list = (long long*)((char*)c->recheck.list.p + kRcList);
-  SBO_HIP(hipMemsetAsync(c->recheck.list.p, 0, kRcList, c->stream));
-  const RcScal init{~0ull, ~0ull, 0ull, 0};
-  SBO_HIP(hipMemcpyAsync(sc, &init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  SBO_HIP(hipMemsetAsync(c->recheck.refined.p, 0, (size_t)std::max<long long>(n, 1), c->stream));
-  const TP* m32 = (const TP*)c->mean.p;
-  const TP* v32 = (const TP*)c->var.p;
-  const unsigned nbk = (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)c->n_cu * 4));
-  // candidate sets without a grid to transform decide their expanders by exhaustive pair evaluation on the ucb of every
-  // safe candidate: there all possibly-safe candidates are re-evaluated
-  long long plane = 1;
-  for (int a = 0; a < c->cs.d - 1; ++a) plane *= c->cs.count[a];
-  const bool grid_expander = c->cs.kind == 1 && c->cs.first % plane == 0 && n % plane == 0;
-  hipLaunchKernelGGL(k_rc_ustar<TP>, dim3(nbk), dim3(256), 0, c->stream, m32, v32, n, q, o->b, bd, sc);
-  // (ranks > 1: the interval of u* and the variance guard are global quantities -- three keys through the collectives)
-  if ((rc = comm_allreduce_min_u64(c, &sc->ulo_key, 2))) return rc;
-  hipLaunchKernelGGL(k_rc_vmax<TP>, dim3(nbk), dim3(256), 0, c->stream, m32, v32, n, q, o->b, bd, sc);
-  if ((rc = comm_allreduce_max_u64(c, &sc->vmax_key, 1))) return rc;
-  hipLaunchKernelGGL(k_rc_flag<TP>, dim3(nbk), dim3(256), 0, c->stream, m32, v32, n, q, o->b, bd, sc, list, grid_expander ? 0 : 1);
-  if (!kGuard)
-    hipLaunchKernelGGL(k_rc_widen, dim3(nbk), dim3(256), 0, c->stream, (const float*)c->mean.p, (const float*)c->var.p, (long long)q * n,
-                       (double*)c->recheck.mean.p, (double*)c->recheck.var.p);
-  SBO_HIP(hipGetLastError());
-  unsigned char* hb = c->h_back + 5120;                             // pinned landing area of the list lengths
-  SBO_HIP(hipMemcpyAsync(hb, sc, 64, hipMemcpyDeviceToHost, c->stream));
-  SBO_HIP(hipStreamSynchronize(c->stream));
-  long long total = ((const RcScal*)hb)->count;
-  if ((rc = rc_refine(c, list, total, kGuard))) return rc;
-  // Lipschitz keys in fp64 (the fp32 posterior kernel left fp32-accurate ones, an approximating one its own band)
-  if (q > 1 && (rc = rc_lipschitz64(c, kGuard ? c : c->recheck.shadow))) return rc;
+  RcBand bd;
+  long long total = 0;
+  // (flag mode 1: candidate sets without a grid to transform decide their expanders by exhaustive pair evaluation on the ucb of every
+  // safe candidate, so there all possibly-safe candidates are re-evaluated)
+  if ((rc = rc_front<TP>(c, o, reuse, list_cap, whole_planes(c) ? 0 : 1, true, bd, &total))) return rc;
   SBO_HIP(hipEventRecord(c->ev_join[2], c->stream));
+  RcHead* head = (RcHead*)c->recheck.list.p;
+  long long* list = (long long*)(head + 1);
+  const unsigned nbk = (unsigned)reduce_blocks(c);
   // the set phase in fp64 arithmetic on the refined posterior (fp32: the widened copy -- the fp32 arrays stay what
   // sbo_posterior_get returns; guard: the band stays in force for unrefined entries, L is exact now); repeated while verdicts are deferred
   SetView view(kGuard ? c->mean : c->recheck.mean, kGuard ? c->var : c->recheck.var, kGuard ? SetBand::values : SetBand::plan);
@@ -523,36 +558,24 @@ static int sweep_safeopt_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeop
     view.refined = (const uint8_t*)c->recheck.refined.p;
     view.rc_band = &bd;
     view.rc_list = list;
-    view.rc_count = count2;
+    view.rc_count = &head->deferred;
   }
   int passes = 0;
   for (;; ++passes) {
-    SBO_HIP(hipMemsetAsync(count2, 0, 8 + sizeof(unsigned long long) * kMaxQ + 24, c->stream));     // deferral counter + G keys
+    SBO_HIP(hipMemsetAsync(&head->deferred, 0, offsetof(RcHead, pad) - offsetof(RcHead, deferred), c->stream));   // the deferral counter .. the G keys
     rc = sweep_safeopt_t<double>(c, o, view, res);
     if (rc != SBO_OK || q == 1) break;
     // Expander's arg-max over every G_c must not hinge on an unrefined variance
     const uint8_t* G = (const uint8_t*)c->maskG.p;
     const double* var0 = (const double*)view.var->p;
     hipLaunchKernelGGL(k_rc_gmax, dim3(nbk, (unsigned)(q - 1)), dim3(256), 0, c->stream, G, var0, (const uint8_t*)c->recheck.refined.p, n, bd.dv[0],
-                       gkeys);
-    if ((rc = comm_allreduce_max_u64(c, gkeys, q - 1))) return rc;        // (the expanders' arg-max is over all ranks)
+                       head->gkeys);
+    if ((rc = comm_allreduce_max_u64(c, head->gkeys, q - 1))) return rc;        // (the expanders' arg-max is over all ranks)
     hipLaunchKernelGGL(k_rc_gdefer, dim3(nbk, (unsigned)(q - 1)), dim3(256), 0, c->stream, G, var0, (const uint8_t*)c->recheck.refined.p, n,
-                       bd.dv[0], (const unsigned long long*)gkeys, list, count2);
+                       bd.dv[0], (const unsigned long long*)head->gkeys, list, &head->deferred);
     SBO_HIP(hipGetLastError());
-    SBO_HIP(hipMemcpyAsync(hb, c->recheck.list.p, 64, hipMemcpyDeviceToHost, c->stream));
-    SBO_HIP(hipStreamSynchronize(c->stream));
-    const long long nd = (long long)*(const unsigned long long*)(hb + kRcCount2);
-    // (ranks > 1: every rank runs the set phase the same number of times -- its collectives are inside --, so "nothing deferred"
-    // is a global statement: the largest count over the ranks)
-    unsigned long long* dcount = (unsigned long long*)((char*)c->recheck.list.p + kRcCount2 + 8);   // scratch word behind the counter
-    long long nd_all = nd;
-    if (multi_rank(c)) {
-      SBO_HIP(hipMemcpyAsync(dcount, hb + kRcCount2, 8, hipMemcpyHostToDevice, c->stream));
-      if ((rc = comm_allreduce_max_u64(c, dcount, 1))) return rc;
-      SBO_HIP(hipMemcpyAsync(hb + 56, dcount, 8, hipMemcpyDeviceToHost, c->stream));
-      SBO_HIP(hipStreamSynchronize(c->stream));
-      nd_all = (long long)*(const unsigned long long*)(hb + 56);
-    }
+    long long nd, nd_all;
+    if ((rc = rc_count_all(c, &nd, &nd_all))) return rc;
     if (nd_all == 0) break;
     if ((size_t)nd > list_cap) return fail(SBO_E_HIP, "internal: refinement list overflow");
     // (every candidate is refined at most once, so the passes end; six without an end would be a defect, not a slow case)
@@ -564,16 +587,12 @@ static int sweep_safeopt_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_safeop
   (void)hipEventElapsedTime(&t01, c->ev_join[0], c->ev_join[1]);
   (void)hipEventElapsedTime(&t12, c->ev_join[1], c->ev_join[2]);
   (void)hipEventElapsedTime(&t04, c->ev_join[0], c->ev[4]);
-  if (kGuard) {
-    c->prof.guard_ms = t04;
-    res->guard_rechecks = total;
-    res->guard_passes = passes + 1;
-  } else {
+  rc_report(c, kGuard, res, total, passes + 1, bd);
+  if (kGuard) c->prof.guard_ms = t04;
+  if (!kGuard) {
     c->prof.posterior_ms = t01;
     c->prof.recheck_ms = t12;
     c->prof.total_ms = t04;
-    c->prof.fp64_rechecks = total;
-    rc_profile_band(c, bd);
     c->prof.posterior_launches = reuse ? 0 : 1;
     const double nn = c->mc.n, dd = c->mc.d;
     c->prof.posterior_flops = reuse ? 0.0 : q * (nn * nn + (2 * dd + 10) * nn) * (double)n;
@@ -641,48 +660,14 @@ static SetView rc_exact_view(const sbo_ctx* c, bool guard) {
   return SetView(guard ? c->mean : c->recheck.mean, guard ? c->var : c->recheck.var, SetBand::none);
 }
 
-// front end shared by the GoOSE / trust-region rechecks: posterior, (fp32) widened copy, first refinement list (q > 1: every
-// possibly-safe or undecided candidate), fp64 Lipschitz keys.  Leaves the list buffers ready for further rounds.
+// The front as the GoOSE / trust-region rechecks run it.  q > 1: every possibly-safe or undecided candidate goes on the first list, no
+// intervals (the contenders of the arg-mins come afterwards, rc_argmin_contenders: once more at most n entries); q = 1: nothing to flag.
+// Reuse -- guard: the fast pass of this call left the posterior resident, and these sweeps have no lean form that could have left part of
+// it unwritten.  fp32: the caller vouches for it; post_l0_missing does not matter: no decision of these sweeps reads the objective's key.
 template <typename TP>
 static int rc_front_all(sbo_ctx* c, const sbo_sweep_opts* o, RcBand& bd, long long* total) {
-  constexpr bool kGuard = std::is_same<TP, double>::value;
-  const long long n = c->cs.n_local;
-  const int q = c->mc.q;
-  int rc;
-  const bool reuse = kGuard || (o->posterior_ready && c->posterior_valid);
-  if (!reuse && (rc = posterior_enqueue(c, PostRequest{}, nullptr))) return rc;
-  if ((rc = rc_bands(c, kGuard, bd))) return rc;
-  if ((rc = ensure(c->recheck.list, kRcList + sizeof(long long) * (size_t)std::max<long long>(n, 1) * 2))) return rc;
-  if (!kGuard) {
-    if ((rc = ensure(c->recheck.mean, sizeof(double) * (size_t)q * std::max<long long>(n, 1)))) return rc;
-    if ((rc = ensure(c->recheck.var, sizeof(double) * (size_t)q * std::max<long long>(n, 1)))) return rc;
-  }
-  if ((rc = ensure(c->recheck.refined, (size_t)std::max<long long>(n, 1)))) return rc;
-  RcScal* sc = (RcScal*)c->recheck.list.p;
-  long long* list = (long long*)((char*)c->recheck.list.p + kRcList);
-  SBO_HIP(hipMemsetAsync(c->recheck.list.p, 0, kRcList, c->stream));
-  const RcScal init{~0ull, ~0ull, 0ull, 0};
-  SBO_HIP(hipMemcpyAsync(sc, &init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  SBO_HIP(hipMemsetAsync(c->recheck.refined.p, 0, (size_t)std::max<long long>(n, 1), c->stream));
-  const TP* m32 = (const TP*)c->mean.p;
-  const TP* v32 = (const TP*)c->var.p;
-  const unsigned nbk = (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)c->n_cu * 4));
-  *total = 0;
-  if (q > 1) {
-    // (ulo / uhi / vmax stay at their initial values: only the "undecided or possibly safe" rule of the flag pass fires)
-    hipLaunchKernelGGL(k_rc_flag<TP>, dim3(nbk), dim3(256), 0, c->stream, m32, v32, n, q, o->b, bd, sc, list, 2);
-  }
-  if (!kGuard)
-    hipLaunchKernelGGL(k_rc_widen, dim3(nbk), dim3(256), 0, c->stream, (const float*)c->mean.p, (const float*)c->var.p, (long long)q * n,
-                       (double*)c->recheck.mean.p, (double*)c->recheck.var.p);
-  SBO_HIP(hipGetLastError());
-  unsigned char* hb = c->h_back + 5120;
-  SBO_HIP(hipMemcpyAsync(hb, sc, 64, hipMemcpyDeviceToHost, c->stream));
-  SBO_HIP(hipStreamSynchronize(c->stream));
-  *total = ((const RcScal*)hb)->count;
-  if ((rc = rc_refine(c, list, *total, kGuard))) return rc;
-  if (q > 1 && (rc = rc_lipschitz64(c, kGuard ? c : c->recheck.shadow))) return rc;
-  return SBO_OK;
+  const bool reuse = std::is_same<TP, double>::value || (o->posterior_ready && c->posterior_valid);
+  return rc_front<TP>(c, o, reuse, (size_t)std::max<long long>(c->cs.n_local, 1) * 2, c->mc.q > 1 ? 2 : -1, false, bd, total);
 }
 
 // contenders of arg-min lcb_0 over `mask` (nmask stacked byte masks, nullptr: every candidate): re-evaluated exactly; returns
@@ -691,32 +676,21 @@ static int rc_argmin_contenders(sbo_ctx* c, const sbo_sweep_opts* o, const RcBan
                                 bool guard) {
   const long long n = c->cs.n_local;
   int rc;
-  unsigned long long* key = (unsigned long long*)((char*)c->recheck.list.p + kRcCount2 + 8);
-  unsigned long long* count2 = (unsigned long long*)((char*)c->recheck.list.p + kRcCount2);
-  long long* list = (long long*)((char*)c->recheck.list.p + kRcList);
-  const unsigned long long init[2] = {0ull, ~0ull};
-  SBO_HIP(hipMemcpyAsync(count2, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  const unsigned nbk = (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)c->n_cu * 4));
+  RcHead* head = (RcHead*)c->recheck.list.p;
+  unsigned long long* key = &head->lmin_key;
+  long long* list = (long long*)(head + 1);
+  const unsigned long long init[2] = {0ull, ~0ull};                    // deferred, lmin_key
+  SBO_HIP(hipMemcpyAsync(&head->deferred, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
+  const unsigned nbk = (unsigned)reduce_blocks(c);
   const double* m0 = guard ? (const double*)c->mean.p : (const double*)c->recheck.mean.p;
   const double* v0 = guard ? (const double*)c->var.p : (const double*)c->recheck.var.p;
   hipLaunchKernelGGL(k_rc_lmin, dim3(nbk), dim3(256), 0, c->stream, m0, v0, (const uint8_t*)c->recheck.refined.p, mask, nmask, n, o->b, bd.dm[0], bd.dv[0], key);
   if ((rc = comm_allreduce_min_u64(c, key, 1))) return rc;             // (ranks > 1: the arg-min is over all ranks)
   hipLaunchKernelGGL(k_rc_lflag, dim3(nbk), dim3(256), 0, c->stream, m0, v0, (const uint8_t*)c->recheck.refined.p, mask, nmask, n, o->b, bd.dm[0], bd.dv[0],
-                     (const unsigned long long*)key, list, count2);
+                     (const unsigned long long*)key, list, &head->deferred);
   SBO_HIP(hipGetLastError());
-  unsigned char* hb = c->h_back + 5120;
-  SBO_HIP(hipMemcpyAsync(hb, c->recheck.list.p, 64, hipMemcpyDeviceToHost, c->stream));
-  SBO_HIP(hipStreamSynchronize(c->stream));
-  const long long mine = (long long)*(const unsigned long long*)(hb + kRcCount2);
-  *found = mine;
-  if (multi_rank(c)) {                   // every rank goes round the same number of times: the largest count decides
-    unsigned long long* dcount = (unsigned long long*)((char*)c->recheck.list.p + kRcCount2 + 16);
-    SBO_HIP(hipMemcpyAsync(dcount, hb + kRcCount2, 8, hipMemcpyHostToDevice, c->stream));
-    if ((rc = comm_allreduce_max_u64(c, dcount, 1))) return rc;
-    SBO_HIP(hipMemcpyAsync(hb + 56, dcount, 8, hipMemcpyDeviceToHost, c->stream));
-    SBO_HIP(hipStreamSynchronize(c->stream));
-    *found = (long long)*(const unsigned long long*)(hb + 56);
-  }
+  long long mine;
+  if ((rc = rc_count_all(c, &mine, found))) return rc;
   if ((rc = rc_refine(c, list, mine, guard))) return rc;
   return SBO_OK;
 }
@@ -757,16 +731,9 @@ static int sweep_goose_recheck(sbo_ctx* c, const sbo_sweep_opts* o, sbo_goose_re
   }
   float t01 = 0;
   (void)hipEventElapsedTime(&t01, c->ev_join[0], c->ev_join[1]);
-  if (kGuard) {
-    res->guard_rechecks = total;
-    res->guard_passes = passes;
-    c->prof.guard_ms = t01;
-  } else {
-    c->prof.fp64_rechecks = total;
-    rc_profile_band(c, bd);
-    c->prof.posterior_launches = reuse ? 0 : 1;
-    c->prof.recheck_ms = t01;
-  }
+  rc_report(c, kGuard, res, total, passes, bd);
+  (kGuard ? c->prof.guard_ms : c->prof.recheck_ms) = t01;
+  if (!kGuard) c->prof.posterior_launches = reuse ? 0 : 1;
   return rc;
 }
 
@@ -783,22 +750,15 @@ static int sweep_tr_recheck(sbo_ctx* c, const sbo_sweep_opts* o, const double* x
   if (q == 1) {
     // arg-min lcb_0 over the ball: the ball as a mask (exact geometry), then the contenders inside it
     if ((rc = ensure(c->maskM, (size_t)n))) return rc;
-    double* dev_x0 = (double*)c->lane[0].scal.p + 256;
+    double* dev_x0 = scal_block(c)->point;
     SBO_HIP(hipMemcpyAsync(dev_x0, x0, sizeof(double) * c->cs.d, hipMemcpyHostToDevice, c->stream));
-    const unsigned nbk = (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)c->n_cu * 4));
     with_dpad(c->mc.dpad, [&](auto D) {
-      hipLaunchKernelGGL((k_rc_ball<D()>), dim3(nbk), dim3(256), 0, c->stream, c->cs, n, (const double*)dev_x0, r, (uint8_t*)c->maskM.p);
+      hipLaunchKernelGGL((k_rc_ball<D()>), dim3((unsigned)reduce_blocks(c)), dim3(256), 0, c->stream, c->cs, n, (const double*)dev_x0, r, (uint8_t*)c->maskM.p);
     });
     if ((rc = rc_argmin_contenders(c, o, bd, (const uint8_t*)c->maskM.p, 1, &more, kGuard))) return rc;
     total += more;
   }
   rc = sweep_tr_t<double>(c, o, rc_exact_view(c, kGuard), x0, r, res);
-  if (kGuard) {
-    res->guard_rechecks = total;
-    res->guard_passes = 1;
-  } else {
-    c->prof.fp64_rechecks = total;
-    rc_profile_band(c, bd);
-  }
+  rc_report(c, kGuard, res, total, 1, bd);
   return rc;
 }
