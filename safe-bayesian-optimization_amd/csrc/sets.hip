@@ -1523,283 +1523,328 @@ static void launch_minimizer(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_o
                      mj->partial, gb_of<T>(c, v));
 }
 
-// `lazy_exact`: the exhaustive recheck of in-band candidates (k_expander_exact) is NOT launched -- the caller looks at the
-// sweep's n_amb afterwards and runs it (and everything behind it) only when something was listed, which is rare
+// ---- one constraint's set phase as steps over one window: expander_set here, goose_sets further down ----------------------
+// INVARIANT of every step (the functions from here to expander_set, and goose_* in front of goose_sets): for every input the same
+// kernels with the same template arguments, grids, block sizes, dynamic LDS and argument values are enqueued on the same streams
+// in the same order as when the two drivers were one function each, and every ensure, hipMemcpyAsync, comm_allgather_bytes and
+// hipFuncSetAttribute keeps its place among them.  Error returns keep their codes and texts.  tests/test_gpu_set_steps_pins.py
+// holds the results, the recheck counts and the host's waits of every branch to that; profiles/set_steps_checks.md has the launches.
+
+// f(std::true_type{} / std::false_type{}), f(std::integral_constant<int, 8 | 16 | 32 | 64>{}): like with_dpad, a launch is written once
+template <class F> auto with_bool(bool on, F&& f) { return on ? f(std::true_type{}) : f(std::false_type{}); }
+template <class F> auto with_lanes(int gl, F&& f) {
+  if (gl == 8) return f(std::integral_constant<int, 8>{});
+  if (gl == 32) return f(std::integral_constant<int, 32>{});
+  if (gl == 64) return f(std::integral_constant<int, 64>{});
+  return f(std::integral_constant<int, 16>{});
+}
+
+// what every step of a constraint reads: the driver's arguments and what follows from them alone
+template <typename T>
+struct SetCall {
+  sbo_ctx* c;
+  sbo_ctx::SetLane& ln;
+  const sbo_sweep_opts* o;
+  const SetView& v;
+  int cidx, lidx;                  // the constraint, and whose Lipschitz key it is judged with
+  SweepScalars* sc;
+  const T *mean_c, *var_c;         // the constraint's rows of the posterior
+};
+
+// Window of a constraint's transform: this rank's hyper-planes of the slowest axis plus, with ranks > 1, a halo of ceil(cap / h)
+// planes on either side (cap = largest radius that can matter, from the keys of collective C1).  Witnesses (expanders) and sources
+// (GoOSE) further away cannot change a verdict, so the window is exact.
+struct SetWindow {
+  int d;
+  long long plane, planes_total;   // candidates per step of the slowest axis; its steps (one rank: those of the local range)
+  long long own0, own1, halo;      // the rank's own planes [own0, own1); planes added on either side (one rank: none)
+  long long w0, w1, wplanes, nt;   // the window [w0, w1) and its candidates
+  long long goff;                  // own candidates start here inside the window
+  int count0; long long nlines;    // positions per axis-0 line (d == 1: the window is one line) and lines of the window
+  int last_cnt; double last_h;     // steps of the last axis inside the window (d == 1: none to scan) and their width
+  long long len0, nl;              // positions per line / local lines
+  double xscale;                   // largest coordinate magnitude (the scale of the verdicts' rounding margins)
+  int blk; bool want_bmin;         // last-axis steps per block minimum, which pay from four blocks on (option scan_blocks)
+};
+// Makes the constraint's one call of halo_for, which may block the host (sweep_exchange_wait): whatever a driver enqueues in front
+// of this call is ahead of that wait.  own1 rounds up where the transforms' own statement (own0 + n / plane) rounds down: the two
+// agree on whole planes (first and n multiples of plane), the only ranges that are transformed; a ragged shard goes to GoOSE's
+// pair path, whose source runs must reach over its last, partial plane.
+static int set_window(sbo_ctx* c, sbo_ctx::SetLane& ln, int cidx, int lidx, SetWindow& w) {
+  const long long n = c->cs.n_local;
+  const int d = w.d = c->cs.d;
+  whole_planes(c, &w.plane);
+  w.planes_total = multi_rank(c) ? c->cs.count[d - 1] : n / w.plane;
+  w.w0 = w.own0 = c->cs.first / w.plane;
+  w.w1 = w.own1 = (c->cs.first + n + w.plane - 1) / w.plane;
+  w.halo = 0;
+  if (multi_rank(c)) {
+    int rc;
+    if ((rc = halo_for(c, ln, cidx, lidx, c->cs.step[d - 1], w.planes_total, &w.halo))) return rc;
+    w.w0 = std::max(0ll, w.own0 - w.halo);
+    w.w1 = std::min(w.planes_total, w.own1 + w.halo);
+  }
+  w.wplanes = w.w1 - w.w0, w.nt = w.wplanes * w.plane, w.goff = (w.own0 - w.w0) * w.plane;
+  w.count0 = d >= 2 ? (int)c->cs.count[0] : (int)w.nt, w.nlines = w.count0 ? w.nt / w.count0 : 0;
+  w.last_cnt = d >= 2 ? (int)w.wplanes : 1, w.last_h = d >= 2 ? c->cs.step[d - 1] : 0.0;
+  w.len0 = d >= 2 ? w.count0 : n, w.nl = w.len0 ? n / w.len0 : 0;
+  w.xscale = 0.0;
+  for (int a = 0; a < d; ++a) w.xscale = std::max(w.xscale, std::max(std::fabs(c->cs.lo[a]), std::fabs(c->cs.hi[a])));
+  w.blk = w.last_cnt >= 8192 ? 64 : 32;
+  w.want_bmin = d >= 2 && w.last_cnt >= 4 * w.blk && c->opt.scan_blocks;
+  return SBO_OK;
+}
+// cells of kCoarse steps per axis over the window -> their number; cg.enabled: coarse bounds pay (a tiny transform of its own lets
+// most candidates decide without the per-candidate scan)
+static long long coarse_grid(const sbo_ctx* c, const SetWindow& w, CoarseGrid& cg) {
+  memset(&cg, 0, sizeof(cg));
+  cg.d = w.d;
+  cg.enabled = w.d >= 2 && w.nt >= (1ll << 16);
+  long long nc = 1;
+  for (int a = 0; a < w.d; ++a) {
+    cg.count[a] = a == w.d - 1 ? w.wplanes : c->cs.count[a];
+    cg.ccount[a] = (cg.count[a] + kCoarse - 1) / kCoarse;
+    nc *= cg.ccount[a];
+    if (cg.count[a] < 4 * kCoarse) cg.enabled = 0;
+  }
+  return nc;
+}
+// workgroups of the block minima of an image with `stride` last-axis columns: k_block_min's grid, k_set_mid's share
+static int block_min_wgs(const SetWindow& w, long long stride) { return (int)std::min<long long>((stride + 63) / 64 * ((w.last_cnt + w.blk - 1) / w.blk), 1 << 20); }
+// ln.blockmin: minima of `din` over blocks of w.blk steps of the last axis; launch == false: the caller's k_set_mid computes them
+static int block_minima(sbo_ctx::SetLane& ln, const SetWindow& w, const double* din, long long stride, bool launch) {
+  int rc;
+  if ((rc = ensure(ln.blockmin, sizeof(double) * (size_t)((w.last_cnt + w.blk - 1) / w.blk) * (size_t)stride))) return rc;
+  if (launch)
+    hipLaunchKernelGGL(k_block_min, dim3((unsigned)block_min_wgs(w, stride)), dim3(256), 0, ln.stream, din, stride, w.last_cnt, w.blk, (double*)ln.blockmin.p);
+  return SBO_OK;
+}
+// the list of the candidates a verdict kernel leaves open, `per` entries each, scanned by groups of lanes against the block minima
+// `bmin` -- nullptr without them, and with option scan_waves = 0 (the verdict kernel then scans by itself)
+static int scan_list(const sbo_ctx* c, sbo_ctx::SetLane& ln, const SetWindow& w, const double* bmin, int per, long long** slist) {
+  *slist = nullptr;
+  if (!bmin || w.blk > 64 || !c->opt.scan_waves) return SBO_OK;
+  int rc;
+  if ((rc = ensure(ln.scanlist, per * sizeof(long long) * (size_t)c->cs.n_local))) return rc;
+  *slist = (long long*)ln.scanlist.p;
+  return SBO_OK;
+}
+
+// -- expander_set's steps
+struct ExpCoarse {
+  long long nc, clines; int cc0;   // cells, their axis-0 lines, cells per line
+  double *dc0, *dc1;               // the coarse transform's two images
+  uint8_t* Uc;                     // the cells' mask, where no kernel forms it from the fine one
+  double cap_extra;                // what a coarse scan's cap adds to the largest radius
+};
+static int exp_coarse(const sbo_ctx* c, sbo_ctx::SetLane& ln, const SetWindow& w, CoarseGrid& cg, ExpCoarse& k) {
+  k = ExpCoarse{};
+  k.nc = coarse_grid(c, w, cg), k.cc0 = (int)cg.ccount[0], k.clines = k.nc / k.cc0;
+  double h2 = 0.0, hmax = 0.0;
+  for (int a = 0; a < w.d; ++a) h2 += c->cs.step[a] * c->cs.step[a], hmax = std::max(hmax, c->cs.step[a]);
+  if (cg.enabled) {
+    int rc;
+    cg.delta = (kCoarse - 1) * std::sqrt(h2) * (1.0 + 1e-9);
+    if ((rc = ensure(ln.coarse, ((size_t)k.nc * (1 + 2 * sizeof(double)) + 64 + 255) / 256 * 256))) return rc;
+    k.dc0 = (double*)ln.coarse.p, k.dc1 = k.dc0 + k.nc, k.Uc = (uint8_t*)(k.dc1 + k.nc);
+  }
+  k.cap_extra = 2.0 * cg.delta + 2.0 * kCoarse * hmax;
+  return SBO_OK;
+}
+// what a transform hands to the verdict (and sets cg.Dc, the coarse image)
+struct ExpImage {
+  double* din; long long stride;   // the fine image and its last-axis stride
+  bool u16;                        // din holds 16-bit step counts (DistU16), not squared distances as doubles
+  bool bmin_done;                  // its block minima are in ln.blockmin already
+};
+// 2-D grids: the two axis-0 passes share a launch (k_edt_axis0_pair, with the classification's merge where it waits in `mj`), and so
+// do the coarse last-axis scan, the minimiser (where it waits in `mj`) and the block minima (k_set_mid)
+template <typename T>
+static int exp_transform_paired(const SetCall<T>& a, const SetWindow& w, CoarseGrid& cg, const ExpCoarse& k, const uint8_t* U, MinimizerJob* mj,
+                                ExpImage& im) {
+  sbo_ctx* c = a.c;
+  const int count0 = w.count0;
+  im = ExpImage{(double*)a.ln.dist2.p, count0, false, false};
+  // fine lines of whole words, up to 4096 positions: a wave per line
+  const int wave_lines = ((count0 & 63) == 0 && count0 <= 4096 && w.nlines < (1ll << 22)) ? 1 : 0;
+  const int ncoarse = (int)std::min<long long>(k.clines, 1 << 20);
+  // (wave form: four workgroups of 39 KB LDS fit a CU; no more fine workgroups than are resident beside the coarse ones)
+  const int nfine = wave_lines ? (int)std::min<long long>((w.nlines + 3) / 4, std::max<long long>(c->n_cu, 4ll * c->n_cu - ncoarse - 1))
+                               : (int)std::min<long long>(w.nlines, 1 << 20);
+  FinalJob fin;
+  if (mj && mj->fin.pending) fin = mj->fin, mj->fin.pending = false;
+  // the fine image as 16-bit step counts (0xffff: no U point on the line) -- only when its readers are the block minima
+  // and the list scan, which decode it: without the list (short last axis, options scan_blocks / scan_waves = 0) the
+  // verdict kernel scans the image itself and expects squared distances as doubles
+  im.u16 = count0 < 65535 && w.want_bmin && w.blk <= 64 && c->opt.scan_waves;
+  with_bool(im.u16, [&](auto U16) {
+    hipLaunchKernelGGL(k_edt_axis0_pair<U16()>, dim3((unsigned)(nfine + ncoarse + (fin.pending ? 1 : 0))), dim3(256), 0, a.ln.stream, U,
+                       w.nlines, count0, c->cs.step[0], im.din, nfine, ncoarse, k.clines, k.cc0, c->cs.step[0] * kCoarse, k.dc0, cg, fin, wave_lines);
+  });
+  MidJobs<T> j;
+  memset(&j, 0, sizeof(j));
+  j.sc = a.sc, j.Lkeys = c->Lmax, j.cidx = a.cidx, j.lidx = a.lidx, j.h0 = c->cs.step[0];
+  // its three jobs.  The coarse last-axis scan:
+  j.ns = (int)std::min<long long>((k.nc + 255) / 256, 1 << 16);
+  j.dc_in = k.dc0, j.dc_out = k.dc1, j.nc = k.nc, j.cstride = k.cc0, j.ccnt = (int)cg.ccount[1], j.hc = c->cs.step[1] * kCoarse, j.cap_extra = k.cap_extra;
+  if (mj && mj->pending) {           // the minimiser:
+    mj->pending = false;
+    j.nb = mj->nb, j.mean0 = (const T*)a.v.mean->p, j.var0 = (const T*)a.v.var->p, j.n = c->cs.n_local, j.first = (long long)c->cs.first, j.b = (T)a.o->b;
+    j.S = (const uint8_t*)c->maskS.p, j.M = (uint8_t*)c->maskM.p, j.partial = mj->partial, j.gb = gb_of<T>(c, a.v);
+  }
+  if (w.want_bmin) {                 // the block minima:
+    int rc;
+    if ((rc = block_minima(a.ln, w, im.din, im.stride, false))) return rc;
+    j.nm = block_min_wgs(w, im.stride), j.din = im.din, j.stride = im.stride, j.cnt = w.last_cnt, j.blk = w.blk, j.bmin = (double*)a.ln.blockmin.p;
+    im.bmin_done = true;
+  }
+  with_bool(im.u16, [&](auto U16) { hipLaunchKernelGGL((k_set_mid<T, U16()>), dim3((unsigned)(j.ns + j.nb + j.nm)), dim3(256), 0, a.ln.stream, j); });
+  cg.Dc = k.dc1;
+  return SBO_OK;
+}
+// every other grid: the minimiser (where it waits in `mj`), axis 0, the middle axes, then the coarse transform by itself
+template <typename T>
+static void exp_transform_plain(const SetCall<T>& a, const SetWindow& w, CoarseGrid& cg, const ExpCoarse& k, const uint8_t* U, MinimizerJob* mj,
+                                ExpImage& im) {
+  sbo_ctx* c = a.c;
+  im = ExpImage{(double*)a.ln.dist2.p, w.count0, false, false};
+  double* dout = (double*)a.ln.dist2b.p;
+  launch_minimizer<T>(c, a.ln, a.o, a.v, mj);
+  launch_edt_axis0(c, a.ln, U, w.nlines, w.count0, c->cs.step[0], im.din);
+  for (int ax = 1; ax < w.d - 1; ++ax) {
+    hipLaunchKernelGGL(k_edt_scan, dim3((unsigned)std::min<long long>((w.nt + 255) / 256, 1 << 20)), dim3(256), 0, a.ln.stream, (const double*)im.din, dout,
+                       w.nt, im.stride, (int)c->cs.count[ax], c->cs.step[ax], (const SweepScalars*)a.sc, a.cidx, c->Lmax, a.lidx, 0, 0.0);
+    std::swap(im.din, dout), im.stride *= c->cs.count[ax];
+  }
+  if (!cg.enabled) return;
+  double *dc0 = k.dc0, *dc1 = k.dc1;
+  if (k.cc0 <= kAxis0Max && k.cc0 >= 128) {
+    // the coarse axis-0 pass forms the cells' bits from the fine mask itself
+    hipLaunchKernelGGL(k_edt_axis0_wg<true>, dim3((unsigned)std::min<long long>(k.clines, 1 << 20)), dim3(256), 0, a.ln.stream, U,
+                       k.clines, k.cc0, c->cs.step[0] * kCoarse, dc0, cg);
+  } else {
+    hipLaunchKernelGGL(k_coarsen_mask, dim3((unsigned)std::min<long long>((k.nc + 255) / 256, 1 << 16)), dim3(256), 0, a.ln.stream, U, cg, k.nc, k.Uc);
+    launch_edt_axis0(c, a.ln, (const uint8_t*)k.Uc, k.clines, k.cc0, c->cs.step[0] * kCoarse, dc0);
+  }
+  long long cstride = k.cc0;
+  for (int ax = 1; ax < w.d; ++ax) {
+    hipLaunchKernelGGL(k_edt_scan, dim3((unsigned)std::min<long long>((k.nc + 255) / 256, 1 << 16)), dim3(256), 0, a.ln.stream, (const double*)dc0, dc1,
+                       k.nc, cstride, (int)cg.ccount[ax], c->cs.step[ax] * kCoarse, (const SweepScalars*)a.sc, a.cidx, c->Lmax, a.lidx, 0, k.cap_extra);
+    std::swap(dc0, dc1), cstride *= cg.ccount[ax];
+  }
+  cg.Dc = dc0;
+}
+// verdict by the coarse bounds and the fine image; what it leaves open goes to `slist` (and from there to the list scan) or, without
+// a list, is scanned by the verdict kernel itself; what stays in the band goes to ln.amb, for the exact recheck
+template <typename T>
+static void exp_verdict(const SetCall<T>& a, const SetWindow& w, const CoarseGrid& cg, const ExpImage& im, const double* bmin, long long* slist,
+                        uint8_t* G) {
+  sbo_ctx* c = a.c;
+  const long long n = c->cs.n_local, len0 = w.len0, nl = w.nl;
+  const int d = w.d;
+  const uint8_t* S = (const uint8_t*)c->maskS.p;
+  long long* amb = (long long*)a.ln.amb.p;
+  const T b = (T)a.o->b;
+  RcExp rx;
+  memset(&rx, 0, sizeof(rx));
+  if (a.v.refined)                                             // a recheck's pass: unrefined entries carry a band, open verdicts are deferred
+    rx.refined = a.v.refined, rx.dm = a.v.rc_band->dm[a.cidx], rx.dv = a.v.rc_band->dv[a.cidx], rx.list = a.v.rc_list, rx.count = a.v.rc_count;
+  rx_band<T>(c, a.v, a.cidx, a.lidx, rx);                      // guard band of an approximating fp64 posterior (fast path: no list)
+  // (grids whose lines are whole 8-byte mask words: eight candidates per lane, see k_edt_decide8)
+  const bool wide = slist && len0 % 8 == 0 && d >= 2 && cg.enabled && ((uintptr_t)G & 7) == 0 && ((uintptr_t)S & 7) == 0;
+  if (wide) {
+    const dim3 g8((unsigned)((len0 / 8 + 255) / 256), (unsigned)std::min<long long>(nl, 65535));
+    hipLaunchKernelGGL((k_edt_decide8<T>), g8, dim3(256), 0, a.ln.stream, nl, (int)len0, w.goff / len0, w.goff, d, w.xscale, a.mean_c, a.var_c, b,
+                       S, c->Lmax, a.lidx, a.sc, G, cg, slist, rx);
+  } else {
+    const dim3 dgrid((unsigned)((len0 + 255) / 256), (unsigned)std::min<long long>((nl + kDecideLines - 1) / kDecideLines, 65535));
+    with_bool(slist != nullptr, [&](auto LIST) {
+      hipLaunchKernelGGL((k_edt_decide<T, LIST()>), dgrid, dim3(256), 0, a.ln.stream, (const double*)im.din, nl, (int)len0, w.goff / len0, w.goff,
+                         d >= 2 ? im.stride : 1, w.last_cnt, w.last_h, d, w.xscale, a.mean_c, a.var_c, b, S, c->Lmax, a.lidx, a.sc, G, amb, cg,
+                         bmin, w.blk, slist, rx);
+    });
+  }
+  if (!slist) return;
+  // (workgroups of the list scan: 2048 on config B's 4 M candidates, 4096 on H's 16 M -- -8 us there)
+  const int scan_wgs = (int)std::min<long long>(4096, std::max<long long>(1024, n / 2048));
+  // lanes per listed candidate: 16 by default (more candidates in flight beat shorter rounds: 53 k open candidates
+  // of config B take 19 us with 16 lanes, 32 us with 32), never more than a wave, 64 for 64-step blocks on request
+  with_lanes(c->opt.scan_waves, [&](auto GL) {
+    with_bool(im.u16, [&](auto U16) {
+      using Dist = std::conditional_t<U16(), DistU16, DistF64>;
+      const Dist img{reinterpret_cast<decltype(Dist::p)>(im.din), U16() ? c->cs.step[0] : 0.0};
+      hipLaunchKernelGGL((k_edt_scan_list<T, GL(), Dist>), dim3(scan_wgs), dim3(256), 0, a.ln.stream, img, w.goff, im.stride, w.last_cnt, w.last_h,
+                         d, w.xscale, a.mean_c, a.var_c, b, c->Lmax, a.lidx, a.sc, G, amb, bmin, w.blk, (const long long*)slist, rx);
+    });
+  });
+}
+// explicit candidate lists, and grid ranges that are not whole hyper-planes: exhaustive evaluation, on the spatial index (the same
+// verdicts with the pairs that cannot matter left out) or quadratic (every safe candidate against every U point, like the
+// reference's vmap -- fine for the lists a campaign uses, seconds at the cap)
+template <typename T>
+static int exp_on_list(const SetCall<T>& a, uint8_t* G, MinimizerJob* mj) {
+  sbo_ctx* c = a.c;
+  const long long n = c->cs.n_local;
+  int rc;
+  launch_minimizer<T>(c, a.ln, a.o, a.v, mj);
+  if (list_index_on(c)) {
+    if ((rc = list_index_expander_d<T>(c, a.ln, a.o, a.v, a.cidx, a.lidx, G))) return rc;
+  } else {
+    if (n > kListExpanderMax) return fail(SBO_E_UNSUPPORTED, "expander sets need a grid of whole hyper-planes, or at most 2097152 candidates (exhaustive)");
+    if (multi_rank(c)) return fail(SBO_E_UNSUPPORTED, "expander sets on explicit candidate lists are single-rank");
+    hipLaunchKernelGGL(k_list_safe, dim3(reduce_blocks(c)), dim3(256), 0, a.ln.stream, (const uint8_t*)c->maskS.p, n, a.sc, G, (long long*)a.ln.amb.p);
+    SBO_HIP(hipGetLastError());
+  }
+  return launch_exact_d<T>(c, a.ln, a.o, a.v, a.cidx, a.lidx, G);
+}
+
+// G_c of constraint cidx.  `mj`: the minimiser and the classification's merge where they wait for this constraint's first launches; each
+// branch takes them at a point of its own (paired: inside its two launches; otherwise launch_minimizer, in front of the transform or of
+// the list kernels).  `lazy_exact`: the exhaustive recheck of in-band candidates (k_expander_exact) is NOT launched -- the caller looks
+// at the sweep's n_amb afterwards and runs it (and everything behind it) only when something was listed, which is rare
 template <typename T>
 static int expander_set(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, const SetView& v, int cidx, uint8_t* G, MinimizerJob* mj = nullptr,
                         bool lazy_exact = false) {
   const long long n = c->cs.n_local;
   if (n == 0) { launch_minimizer<T>(c, ln, o, v, mj); return SBO_OK; }
-  const int q = c->mc.q;
-  const int lidx = o->reference_quirk_L_index ? q - 1 : cidx;   // models/SafeOpt.py:110 (loop-leaked i)
-  SweepScalars* sc = (SweepScalars*)ln.scal.p;
-  const T* mean_c = (const T*)v.mean->p + (size_t)cidx * n;
-  const T* var_c = (const T*)v.var->p + (size_t)cidx * n;
-  const int nb = reduce_blocks(c);
+  const int lidx = o->reference_quirk_L_index ? c->mc.q - 1 : cidx;   // models/SafeOpt.py:110 (loop-leaked i)
+  const SetCall<T> a{c, ln, o, v, cidx, lidx, (SweepScalars*)ln.scal.p, (const T*)v.mean->p + (size_t)cidx * n, (const T*)v.var->p + (size_t)cidx * n};
   int rc;
   if ((rc = ensure(ln.amb, sizeof(long long) * (size_t)n))) return rc;
-  if (!ln.amb_clean) hipLaunchKernelGGL(k_reset_amb, dim3(1), dim3(1), 0, ln.stream, sc);   // (k_classify_final left the counters at zero)
+  if (!ln.amb_clean) hipLaunchKernelGGL(k_reset_amb, dim3(1), dim3(1), 0, ln.stream, a.sc);   // (k_classify_final left the counters at zero)
   ln.amb_clean = false;
-  long long plane;                           // candidates per step of the slowest axis
-  const bool plane_aligned = whole_planes(c, &plane);
-  if (plane_aligned) {
-    const int d = c->cs.d;
-    // Window of the transform: this rank's hyper-planes of the slowest axis plus, with ranks > 1, a halo of
-    // ceil(cap / h) planes on either side taken from the all-gathered U mask (cap = largest radius that can matter,
-    // from the keys of collective C1).  Witnesses further away cannot change a verdict, so the window is exact.
-    const long long planes_total = multi_rank(c) ? c->cs.count[d - 1] : n / plane;
-    long long p0 = multi_rank(c) ? c->cs.first / plane : 0, p1 = p0 + n / plane;
-    const long long own0 = p0;
-    if (multi_rank(c)) {
-      const double hl = d >= 2 ? c->cs.step[d - 1] : c->cs.step[0];
-      long long H;
-      if ((rc = halo_for(c, ln, cidx, lidx, hl, planes_total, &H))) return rc;
-      p0 = std::max(0ll, p0 - H);
-      p1 = std::min(planes_total, p1 + H);
-    }
-    const long long wplanes = p1 - p0;
-    const long long nt = wplanes * plane;
-    const long long goff = (own0 - p0) * plane;                 // own candidates start here inside the window
-    const uint8_t* Uall = (const uint8_t*)c->maskU.p;
-    if (multi_rank(c)) {
-      // bytes of the window only, out of the all-gathered bit words (the gather itself was queued ahead of the host's wait)
-      if ((rc = ensure(c->dist.Uwin, (size_t)nt))) return rc;
-      const unsigned long long* recvw = (const unsigned long long*)c->dist.ubits.p + c->dist.gather_words + kC1Head;   // (past the own block and a head)
-      hipLaunchKernelGGL(k_unpack_shards, dim3((unsigned)std::min<long long>((nt + 255) / 256, 1 << 16)), dim3(256), 0, ln.stream, recvw,
-                         c->dist.gather_words, c->dist.world, (const long long*)c->dist.shard_first.p, p0 * plane, nt, (uint8_t*)c->dist.Uwin.p);
-      c->dist.uwin_first = p0 * plane;
-      c->dist.uwin_n = nt;
-      Uall = (const uint8_t*)c->dist.Uwin.p;
-    }
-    if ((rc = ensure(ln.dist2, sizeof(double) * (size_t)nt))) return rc;
-    if (d > 2 && (rc = ensure(ln.dist2b, sizeof(double) * (size_t)nt))) return rc;
-    const int count0 = d >= 2 ? (int)c->cs.count[0] : (int)nt;  // d == 1: the window is one line
-    const long long nlines = nt / count0;
-    // coarse transform of the window (tiny): lets most candidates decide without the per-candidate scan
-    CoarseGrid cg;
-    memset(&cg, 0, sizeof(cg));
-    cg.d = d;
-    bool coarse_ok = d >= 2 && nt >= (1ll << 16);
-    long long nc = 1;
-    double h2 = 0.0, hmax = 0.0;
-    for (int a = 0; a < d; ++a) {
-      cg.count[a] = a == d - 1 ? wplanes : c->cs.count[a];
-      cg.ccount[a] = (cg.count[a] + kCoarse - 1) / kCoarse;
-      nc *= cg.ccount[a];
-      h2 += c->cs.step[a] * c->cs.step[a];
-      hmax = std::max(hmax, c->cs.step[a]);
-      if (cg.count[a] < 4 * kCoarse) coarse_ok = false;
-    }
-    double* dc0 = nullptr;
-    double* dc1 = nullptr;
-    uint8_t* Uc = nullptr;
-    const int cc0 = (int)cg.ccount[0];
-    const long long clines = nc / cc0;
-    if (coarse_ok) {
-      cg.enabled = 1;
-      cg.delta = (kCoarse - 1) * std::sqrt(h2) * (1.0 + 1e-9);
-      const size_t cbytes = ((size_t)nc * (1 + 2 * sizeof(double)) + 64 + 255) / 256 * 256;
-      if ((rc = ensure(ln.coarse, cbytes))) return rc;
-      dc0 = (double*)ln.coarse.p;
-      dc1 = dc0 + nc;
-      Uc = (uint8_t*)(dc1 + nc);
-    }
-    const double cap_extra = 2.0 * cg.delta + 2.0 * kCoarse * hmax;
-    const int last_cnt_ = d >= 2 ? (int)wplanes : 1;
-    const int blk_ = last_cnt_ >= 8192 ? 64 : 32;
-    const bool want_bmin = d >= 2 && last_cnt_ >= 4 * blk_ && c->opt.scan_blocks;
-    // 2-D grids: the two axis-0 passes share a launch, and so do the coarse last-axis scan, the minimiser and the block minima
-    const bool paired = d == 2 && coarse_ok && c->opt.set_fuse && count0 <= kAxis0Max && count0 >= 128 && cc0 >= 128;
-    bool bmin_done = false, u16 = false;
-    double* din = (double*)ln.dist2.p;
-    double* dout = (double*)ln.dist2b.p;
-    long long stride = count0;
-    if (paired) {
-      // fine lines of whole words, up to 4096 positions: a wave per line
-      const int wave_lines = ((count0 & 63) == 0 && count0 <= 4096 && nlines < (1ll << 22)) ? 1 : 0;
-      const int ncoarse = (int)std::min<long long>(clines, 1 << 20);
-      // (wave form: four workgroups of 39 KB LDS fit a CU; no more fine workgroups than are resident beside the coarse ones)
-      const int nfine = wave_lines ? (int)std::min<long long>((nlines + 3) / 4, std::max<long long>(c->n_cu, 4ll * c->n_cu - ncoarse - 1))
-                                   : (int)std::min<long long>(nlines, 1 << 20);
-      FinalJob fin;
-      if (mj && mj->fin.pending) {
-        fin = mj->fin;
-        mj->fin.pending = false;
-      }
-      // the fine image as 16-bit step counts (0xffff: no U point on the line) -- only when its readers are the block minima
-      // and the list scan, which decode it: without the list (short last axis, options scan_blocks / scan_waves = 0) the
-      // verdict kernel scans the image itself and expects squared distances as doubles
-      u16 = count0 < 65535 && want_bmin && blk_ <= 64 && c->opt.scan_waves;
-      if (u16)
-        hipLaunchKernelGGL(k_edt_axis0_pair<true>, dim3((unsigned)(nfine + ncoarse + (fin.pending ? 1 : 0))), dim3(256), 0, ln.stream, Uall,
-                           nlines, count0, c->cs.step[0], din, nfine, ncoarse, clines, cc0, c->cs.step[0] * kCoarse, dc0, cg, fin, wave_lines);
-      else
-        hipLaunchKernelGGL(k_edt_axis0_pair<false>, dim3((unsigned)(nfine + ncoarse + (fin.pending ? 1 : 0))), dim3(256), 0, ln.stream, Uall,
-                           nlines, count0, c->cs.step[0], din, nfine, ncoarse, clines, cc0, c->cs.step[0] * kCoarse, dc0, cg, fin, wave_lines);
-      MidJobs<T> j;
-      memset(&j, 0, sizeof(j));
-      j.sc = sc;
-      j.Lkeys = c->Lmax;
-      j.ns = (int)std::min<long long>((nc + 255) / 256, 1 << 16);
-      j.dc_in = dc0;
-      j.dc_out = dc1;
-      j.nc = nc;
-      j.cstride = cc0;
-      j.ccnt = (int)cg.ccount[1];
-      j.hc = c->cs.step[1] * kCoarse;
-      j.cidx = cidx;
-      j.lidx = lidx;
-      j.cap_extra = cap_extra;
-      if (mj && mj->pending) {
-        mj->pending = false;
-        j.nb = mj->nb;
-        j.mean0 = (const T*)v.mean->p;
-        j.var0 = (const T*)v.var->p;
-        j.n = n;
-        j.first = (long long)c->cs.first;
-        j.b = (T)o->b;
-        j.S = (const uint8_t*)c->maskS.p;
-        j.M = (uint8_t*)c->maskM.p;
-        j.partial = mj->partial;
-        j.gb = gb_of<T>(c, v);
-      }
-      if (want_bmin) {
-        const int nblocks = (last_cnt_ + blk_ - 1) / blk_;
-        if ((rc = ensure(ln.blockmin, sizeof(double) * (size_t)nblocks * (size_t)stride))) return rc;
-        j.nm = (int)std::min<long long>((stride + 63) / 64 * nblocks, 1 << 20);
-        j.din = din;
-        j.stride = stride;
-        j.cnt = last_cnt_;
-        j.blk = blk_;
-        j.bmin = (double*)ln.blockmin.p;
-        bmin_done = true;
-      }
-      j.h0 = c->cs.step[0];
-      if (u16) hipLaunchKernelGGL((k_set_mid<T, true>), dim3((unsigned)(j.ns + j.nb + j.nm)), dim3(256), 0, ln.stream, j);
-      else hipLaunchKernelGGL((k_set_mid<T, false>), dim3((unsigned)(j.ns + j.nb + j.nm)), dim3(256), 0, ln.stream, j);
-      cg.Dc = dc1;
-    } else {
-      launch_minimizer<T>(c, ln, o, v, mj);
-      launch_edt_axis0(c, ln, Uall, nlines, count0, c->cs.step[0], din);
-      for (int a = 1; a < d - 1; ++a) {
-        hipLaunchKernelGGL(k_edt_scan, dim3((unsigned)std::min<long long>((nt + 255) / 256, 1 << 20)), dim3(256), 0, ln.stream,
-                           (const double*)din, dout, nt, stride, (int)c->cs.count[a], c->cs.step[a],
-                           (const SweepScalars*)sc, cidx, c->Lmax, lidx, 0, 0.0);
-        std::swap(din, dout);
-        stride *= c->cs.count[a];
-      }
-      if (coarse_ok) {
-        if (cc0 <= kAxis0Max && cc0 >= 128) {
-          // the coarse axis-0 pass forms the cells' bits from the fine mask itself
-          hipLaunchKernelGGL(k_edt_axis0_wg<true>, dim3((unsigned)std::min<long long>(clines, 1 << 20)), dim3(256), 0, ln.stream, Uall,
-                             clines, cc0, c->cs.step[0] * kCoarse, dc0, cg);
-        } else {
-          hipLaunchKernelGGL(k_coarsen_mask, dim3((unsigned)std::min<long long>((nc + 255) / 256, 1 << 16)), dim3(256), 0, ln.stream,
-                             Uall, cg, nc, Uc);
-          launch_edt_axis0(c, ln, (const uint8_t*)Uc, clines, cc0, c->cs.step[0] * kCoarse, dc0);
-        }
-        long long cstride = cc0;
-        for (int a = 1; a < d; ++a) {
-          hipLaunchKernelGGL(k_edt_scan, dim3((unsigned)std::min<long long>((nc + 255) / 256, 1 << 16)), dim3(256), 0, ln.stream,
-                             (const double*)dc0, dc1, nc, cstride, (int)cg.ccount[a], c->cs.step[a] * kCoarse, (const SweepScalars*)sc,
-                             cidx, c->Lmax, lidx, 0, cap_extra);
-          std::swap(dc0, dc1);
-          cstride *= cg.ccount[a];
-        }
-        cg.Dc = dc0;
-      }
-    }
-    double xscale = 0.0;
-    for (int a = 0; a < d; ++a) xscale = std::max(xscale, std::max(std::fabs(c->cs.lo[a]), std::fabs(c->cs.hi[a])));
-    const int last_cnt = d >= 2 ? (int)wplanes : 1;
-    const double last_h = d >= 2 ? c->cs.step[d - 1] : 0.0;
-    {
-      const double* bmin = bmin_done ? (const double*)ln.blockmin.p : nullptr;
-      const int blk = blk_;
-      if (!bmin_done && want_bmin) {
-        const long long nb_ = (long long)((last_cnt + blk - 1) / blk) * stride;
-        if ((rc = ensure(ln.blockmin, sizeof(double) * (size_t)nb_))) return rc;
-        hipLaunchKernelGGL(k_block_min, dim3((unsigned)std::min<long long>((stride + 63) / 64 * ((last_cnt + blk - 1) / blk), 1 << 20)), dim3(256), 0, ln.stream,
-                           (const double*)din, stride, last_cnt, blk, (double*)ln.blockmin.p);
-        bmin = (const double*)ln.blockmin.p;
-      }
-      long long* slist = nullptr;
-      if (bmin && blk <= 64 && c->opt.scan_waves) {
-        if ((rc = ensure(ln.scanlist, 2 * sizeof(long long) * (size_t)n))) return rc;   // (candidate, ucb) pairs
-        slist = (long long*)ln.scanlist.p;
-      }
-      const long long len0 = d >= 2 ? count0 : n;               // positions per line / local lines
-      const long long nl = n / len0;
-      RcExp rx;
-      memset(&rx, 0, sizeof(rx));
-      if (v.refined) {                                           // a recheck's pass: unrefined entries carry a band, open verdicts are deferred
-        rx.refined = v.refined;
-        rx.dm = v.rc_band->dm[cidx];
-        rx.dv = v.rc_band->dv[cidx];
-        rx.list = v.rc_list;
-        rx.count = v.rc_count;
-      }
-      rx_band<T>(c, v, cidx, lidx, rx);                          // guard band of an approximating fp64 posterior (fast path: no list)
-      const dim3 dgrid((unsigned)((len0 + 255) / 256), (unsigned)std::min<long long>((nl + kDecideLines - 1) / kDecideLines, 65535));
-#define SBO_DECIDE(LIST)                                                                                                            \
-  hipLaunchKernelGGL((k_edt_decide<T, LIST>), dgrid, dim3(256), 0, ln.stream, (const double*)din, nl, (int)len0, goff / len0, goff, \
-                     d >= 2 ? stride : 1, last_cnt, last_h, d, xscale, mean_c, var_c, (T)o->b, (const uint8_t*)c->maskS.p,          \
-                     c->Lmax, lidx, sc, G, (long long*)ln.amb.p, cg, bmin, blk, slist, rx)
-      // (grids whose lines are whole 8-byte mask words: eight candidates per lane, see k_edt_decide8)
-      const bool wide = slist && len0 % 8 == 0 && d >= 2 && cg.enabled && ((uintptr_t)G & 7) == 0 &&
-                        ((uintptr_t)c->maskS.p & 7) == 0;
-      if (wide) {
-        const dim3 g8((unsigned)((len0 / 8 + 255) / 256), (unsigned)std::min<long long>(nl, 65535));
-        hipLaunchKernelGGL((k_edt_decide8<T>), g8, dim3(256), 0, ln.stream, nl, (int)len0, goff / len0, goff, d, xscale, mean_c, var_c, (T)o->b,
-                           (const uint8_t*)c->maskS.p, c->Lmax, lidx, sc, G, cg, slist, rx);
-      } else if (slist) SBO_DECIDE(true);
-      else SBO_DECIDE(false);
-#undef SBO_DECIDE
-      // (workgroups of the list scan: 2048 on config B's 4 M candidates, 4096 on H's 16 M -- -8 us there)
-      const int scan_wgs = (int)std::min<long long>(4096, std::max<long long>(1024, n / 2048));
-      if (slist) {
-        // lanes per listed candidate: 16 by default (more candidates in flight beat shorter rounds: 53 k open candidates
-        // of config B take 19 us with 16 lanes, 32 us with 32), never more than a wave, 64 for 64-step blocks on request
-        const int gl = c->opt.scan_waves == 8 || c->opt.scan_waves == 32 || c->opt.scan_waves == 64 ? c->opt.scan_waves : 16;
-#define SBO_SCAN_LIST(GL)                                                                                                       \
-  if (u16)                                                                                                                      \
-    hipLaunchKernelGGL((k_edt_scan_list<T, GL, DistU16>), dim3(scan_wgs), dim3(256), 0, ln.stream,                              \
-                       DistU16{reinterpret_cast<const unsigned short*>(din), c->cs.step[0]}, goff, stride, last_cnt,            \
-                       last_h, d, xscale, mean_c, var_c, (T)o->b, c->Lmax, lidx, sc, G,            \
-                       (long long*)ln.amb.p, bmin, blk, (const long long*)slist, rx);                                           \
-  else                                                                                                                          \
-  hipLaunchKernelGGL((k_edt_scan_list<T, GL, DistF64>), dim3(scan_wgs), dim3(256), 0, ln.stream, DistF64{(const double*)din, 0.0}, goff, stride, last_cnt, \
-                     last_h, d, xscale, mean_c, var_c, (T)o->b, c->Lmax, lidx, sc, G,              \
-                     (long long*)ln.amb.p, bmin, blk, (const long long*)slist, rx)
-        switch (gl) {
-          case 8: SBO_SCAN_LIST(8); break;
-          case 32: SBO_SCAN_LIST(32); break;
-          case 64: SBO_SCAN_LIST(64); break;
-          default: SBO_SCAN_LIST(16); break;
-        }
-#undef SBO_SCAN_LIST
-      }
-    }
-  } else {
-    // explicit candidate lists, and grid ranges that are not whole hyper-planes: exhaustive evaluation
-    launch_minimizer<T>(c, ln, o, v, mj);
-    if (list_index_on(c)) {
-      // (explicit lists on the spatial index: the same verdicts with the pairs that cannot matter left out)
-      if ((rc = list_index_expander_d<T>(c, ln, o, v, cidx, lidx, G))) return rc;
-      return launch_exact_d<T>(c, ln, o, v, cidx, lidx, G);
-    }
-    // (quadratic: every safe candidate against every U point, like the reference's vmap -- fine for the lists a campaign
-    // uses, seconds at the cap)
-    if (n > kListExpanderMax)
-      return fail(SBO_E_UNSUPPORTED, "expander sets need a grid of whole hyper-planes, or at most 2097152 candidates (exhaustive)");
-    if (multi_rank(c))
-      return fail(SBO_E_UNSUPPORTED, "expander sets on explicit candidate lists are single-rank");
-    hipLaunchKernelGGL(k_list_safe, dim3(nb), dim3(256), 0, ln.stream, (const uint8_t*)c->maskS.p, n, sc, G,
-                       (long long*)ln.amb.p);
+  if (!whole_planes(c)) return exp_on_list<T>(a, G, mj);
+  SetWindow w;
+  if ((rc = set_window(c, ln, cidx, lidx, w))) return rc;          // (ranks > 1: may wait for the keys, behind everything above)
+  const uint8_t* U = (const uint8_t*)c->maskU.p;
+  if (multi_rank(c)) {
+    // bytes of the window only, out of the all-gathered bit words (the gather itself was queued ahead of the host's wait)
+    if ((rc = ensure(c->dist.Uwin, (size_t)w.nt))) return rc;
+    const unsigned long long* recvw = (const unsigned long long*)c->dist.ubits.p + c->dist.gather_words + kC1Head;   // (past the own block and a head)
+    hipLaunchKernelGGL(k_unpack_shards, dim3((unsigned)std::min<long long>((w.nt + 255) / 256, 1 << 16)), dim3(256), 0, ln.stream, recvw,
+                       c->dist.gather_words, c->dist.world, (const long long*)c->dist.shard_first.p, w.w0 * w.plane, w.nt, (uint8_t*)c->dist.Uwin.p);
+    c->dist.uwin_first = w.w0 * w.plane, c->dist.uwin_n = w.nt;
+    U = (const uint8_t*)c->dist.Uwin.p;
   }
+  if ((rc = ensure(ln.dist2, sizeof(double) * (size_t)w.nt))) return rc;
+  if (w.d > 2 && (rc = ensure(ln.dist2b, sizeof(double) * (size_t)w.nt))) return rc;
+  CoarseGrid cg;
+  ExpCoarse k;
+  ExpImage im;
+  if ((rc = exp_coarse(c, ln, w, cg, k))) return rc;
+  if (w.d == 2 && cg.enabled && c->opt.set_fuse && w.count0 <= kAxis0Max && w.count0 >= 128 && k.cc0 >= 128) {
+    if ((rc = exp_transform_paired<T>(a, w, cg, k, U, mj, im))) return rc;
+  } else {
+    exp_transform_plain<T>(a, w, cg, k, U, mj, im);
+  }
+  if (w.want_bmin && !im.bmin_done && (rc = block_minima(ln, w, im.din, im.stride, true))) return rc;
+  const double* bmin = w.want_bmin ? (const double*)ln.blockmin.p : nullptr;
+  long long* slist;
+  if ((rc = scan_list(c, ln, w, bmin, 2, &slist))) return rc;         // (candidate, ucb) pairs
+  exp_verdict<T>(a, w, cg, im, bmin, slist, G);
   SBO_HIP(hipGetLastError());
-  if (lazy_exact && plane_aligned) return SBO_OK;
-  return launch_exact_d<T>(c, ln, o, v, cidx, lidx, G);
+  if (lazy_exact) return SBO_OK;
+  return launch_exact_d<T>(c, ln, o, v, cidx, a.lidx, G);
 }
 
 static void coords_of(const sbo_ctx* c, long long gidx, double* x) {
@@ -2205,246 +2250,195 @@ template <typename T>
 static int sweep_tr_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, const double* x0, double r, sbo_tr_result* res);
 #include "sets_recheck.inc.hpp"
 
+// -- goose_sets's steps (the INVARIANT in front of SetWindow holds for them).  The sources of a constraint: S_t's candidates with their
+// weights W -- the local ones, or with ranks > 1 those of the window, or of the whole grid with the window as a range of runs
+template <typename T>
+struct GooseSources {
+  CandSpec css; const T* W;     // the source candidates and their weights
+  long long run_lo, run_hi;     // the runs of kRun sources that can matter
+  bool w_is_window;             // ranks > 1, slab exchange: W holds exactly the window [w.w0, w.w1)
+};
+// Ranks > 1.  Sources of the other ranks that can reach this shard lie within w.halo hyper-planes of it (from the largest source
+// radius, keys of collective C1 -- exact, as for the expanders)
+template <typename T>
+static int goose_exchange(const SetCall<T>& a, const SetWindow& w, long long maxlocal, GooseSources<T>& s) {
+  sbo_ctx* c = a.c;
+  const long long n = c->cs.n_local, plane = w.plane, H = w.halo;
+  int rc;
+  long long min_planes = w.planes_total;
+  for (int r = 0; r < c->dist.world; ++r) min_planes = std::min(min_planes, (c->dist.first_of[r + 1] - c->dist.first_of[r]) / plane);
+  const bool slabs = c->dist.sharded && H <= min_planes;
+  if (getenv("SBO_DEBUG_COMM"))
+    fprintf(stderr, "[rank %d] GoOSE sources c=%d: halo %lld planes, smallest shard %lld planes -> %s\n", c->dist.rank, a.cidx, H, min_planes,
+            slabs ? "slab exchange" : "full all-gather");
+  if (slabs) {
+    // the halo fits inside the neighbours: every rank contributes only its first and last H planes (2 H plane values
+    // instead of its whole shard), and the window is assembled from the previous rank's top slab, the own shard and
+    // the next rank's bottom slab
+    const size_t slab = (size_t)H * plane;
+    if ((rc = ensure(c->dist.gather, sizeof(T) * slab * 2 * (c->dist.world + 1)))) return rc;
+    if ((rc = ensure(c->dist.Wfull, sizeof(T) * (size_t)w.nt))) return rc;
+    T *send = (T*)c->dist.gather.p, *recv = send + 2 * slab;
+    SBO_HIP(hipMemcpyAsync(send, a.ln.gw.p, sizeof(T) * slab, hipMemcpyDeviceToDevice, a.ln.stream));
+    SBO_HIP(hipMemcpyAsync(send + slab, (const T*)a.ln.gw.p + (size_t)n - slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, a.ln.stream));
+    if ((rc = comm_allgather_bytes(c, send, recv, sizeof(T) * slab * 2))) return rc;
+    T* win = (T*)c->dist.Wfull.p;
+    size_t at = 0;
+    if (w.own0 > w.w0) {       // previous rank's top slab (w0 = own0 - H exactly, since H <= its planes)
+      SBO_HIP(hipMemcpyAsync(win, recv + (size_t)(c->dist.rank - 1) * 2 * slab + slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, a.ln.stream));
+      at = slab;
+    }
+    SBO_HIP(hipMemcpyAsync(win + at, a.ln.gw.p, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, a.ln.stream));
+    at += (size_t)n;
+    if (w.w1 > w.own1)
+      SBO_HIP(hipMemcpyAsync(win + at, recv + (size_t)(c->dist.rank + 1) * 2 * slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, a.ln.stream));
+    s.css.first = w.w0 * plane, s.css.n_local = w.nt, s.W = (const T*)win, s.w_is_window = true;
+    s.run_lo = 0, s.run_hi = (s.css.n_local + kRun - 1) / kRun;
+  } else {
+    // wide halo: all-gather the whole weight shards
+    if ((rc = ensure(c->dist.gather, sizeof(T) * (size_t)maxlocal * c->dist.world))) return rc;
+    if ((rc = ensure(c->dist.Wfull, sizeof(T) * (size_t)c->dist.grid_total))) return rc;
+    if ((rc = comm_allgather_bytes(c, a.ln.gw.p, c->dist.gather.p, sizeof(T) * (size_t)maxlocal))) return rc;
+    hipLaunchKernelGGL(k_compact_shards<T>, dim3((unsigned)std::min<long long>((c->dist.grid_total + 255) / 256, 1 << 16)), dim3(256), 0,
+                       a.ln.stream, (const T*)c->dist.gather.p, maxlocal, c->dist.world, (const long long*)c->dist.shard_first.p, c->dist.grid_total,
+                       (T*)c->dist.Wfull.p);
+    s.css.first = 0, s.css.n_local = c->dist.grid_total, s.W = (const T*)c->dist.Wfull.p;
+    s.run_lo = w.w0 * plane / kRun, s.run_hi = (w.w1 * plane + kRun - 1) / kRun;
+  }
+  return SBO_OK;
+}
+// grids: power-distance transform of the source weights over the window, verdict by sign, exact recheck in the band
+template <typename T, int D>
+static int goose_transform(const SetCall<T>& a, const SetWindow& w, const GooseSources<T>& s, uint8_t* O) {
+  sbo_ctx* c = a.c;
+  sbo_ctx::SetLane& ln = a.ln;
+  const long long n = c->cs.n_local, nt = w.nt;
+  const int d = w.d;
+  int rc;
+  const T* Wwin = (multi_rank(c) && !s.w_is_window) ? s.W + w.w0 * w.plane : s.W;
+  if ((rc = ensure(ln.dist2, sizeof(double) * (size_t)nt))) return rc;
+  if (d > 2 && (rc = ensure(ln.dist2b, sizeof(double) * (size_t)nt))) return rc;
+  if ((rc = ensure(ln.amb, sizeof(long long) * (size_t)n))) return rc;
+  ln.amb_clean = false;                          // (k_goose_weights cleared the counters)
+  // coarse bounds of the window: decide most candidates (and skip their axis-0 scans) without touching the fine arrays
+  CoarseGrid cg;
+  const long long nc = coarse_grid(c, w, cg);
+  const double *pc_lo = nullptr, *pc_hi = nullptr;          // (the cells' bounds, where there is a coarse grid)
+  if (cg.enabled) {
+    if ((rc = ensure(ln.coarse, (size_t)nc * 5 * sizeof(double) + 64))) return rc;
+    double *lo0 = (double*)ln.coarse.p, *lo1 = lo0 + nc, *hi0 = lo1 + nc, *hi1 = hi0 + nc;
+    hipLaunchKernelGGL((k_pdt_cell_min<T>), dim3((unsigned)std::min<long long>((nc * 8 + 255) / 256, 1 << 18)), dim3(256), 0, ln.stream, Wwin, cg, nc, c->Lmax, a.lidx, lo0, hi0);
+    long long cstride = 1;
+    for (int ax = 0; ax < d; ++ax) {
+      hipLaunchKernelGGL(k_pdt_coarse_scan, dim3((unsigned)std::min<long long>((2 * nc * 8 + 255) / 256, 1 << 18)), dim3(256), 0, ln.stream, (const double*)lo0,
+                         lo1, (const double*)hi0, hi1, nc, cstride, (int)cg.ccount[ax], c->cs.step[ax], (const SweepScalars*)a.sc, a.cidx, c->Lmax, a.lidx, d, w.xscale);
+      std::swap(lo0, lo1), std::swap(hi0, hi1), cstride *= cg.ccount[ax];
+    }
+    pc_lo = lo0, pc_hi = hi0;
+  }
+  // axis 0 of the transform, into ln.dist2
+  const int count0 = w.count0, blk0 = 32;
+  double *pin = (double*)ln.dist2.p, *pout = (double*)ln.dist2b.p;
+  if (c->opt.scan_blocks && count0 >= 16 * blk0 && count0 <= 8192 && w.nlines >= 1024) {
+    // one workgroup per line, the line in LDS (pays once there are enough lines to fill the chip: from 1024 lines on --
+    // config C's 1024 x 1024 grid of the Williams-Otto plant: 33 -> 19 us per constraint against the thread-per-position kernel)
+    const size_t lds = sizeof(double) * ((size_t)count0 + (count0 + kAnchor - 1) / kAnchor) + sizeof(int) * 2 * ((size_t)(count0 + kAnchor - 1) / kAnchor + 2);
+    SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pdt_axis0_lds<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_pdt_axis0_lds<T>), dim3((unsigned)std::min<long long>(w.nlines, 1 << 16)), dim3(256), lds, ln.stream, Wwin, w.nlines, count0,
+                       c->cs.step[0], (const SweepScalars*)a.sc, a.cidx, c->Lmax, a.lidx, d, w.xscale, cg, pc_lo, blk0, pin);
+  } else {
+    const T* wbmax = nullptr;
+    if (c->opt.scan_blocks && count0 >= 16 * blk0) {
+      const long long nbw = w.nlines * ((count0 + blk0 - 1) / blk0);
+      if ((rc = ensure(ln.blockmax, sizeof(T) * (size_t)nbw))) return rc;
+      hipLaunchKernelGGL((k_block_max_w<T>), dim3((unsigned)std::min<long long>((nbw + 255) / 256, 1 << 20)), dim3(256), 0, ln.stream, Wwin, nt, count0, blk0, (T*)ln.blockmax.p);
+      wbmax = (const T*)ln.blockmax.p;
+    }
+    hipLaunchKernelGGL((k_pdt_axis0<T>), dim3((unsigned)std::min<long long>((nt + 255) / 256, 1 << 20)), dim3(256), 0, ln.stream, Wwin, nt, count0,
+                       c->cs.step[0], (const SweepScalars*)a.sc, a.cidx, c->Lmax, a.lidx, d, w.xscale, cg, pc_lo, wbmax, blk0, pin);
+  }
+  // the middle axes, the block minima of the last one, the verdict with its list scan, the exact recheck
+  long long stride = count0;
+  for (int ax = 1; ax < d - 1; ++ax) {
+    hipLaunchKernelGGL(k_pdt_scan, dim3((unsigned)std::min<long long>((nt + 255) / 256, 1 << 20)), dim3(256), 0, ln.stream, (const double*)pin, pout,
+                       nt, stride, (int)c->cs.count[ax], c->cs.step[ax], (const SweepScalars*)a.sc, a.cidx, c->Lmax, a.lidx, d, w.xscale);
+    std::swap(pin, pout), stride *= c->cs.count[ax];
+  }
+  if (w.want_bmin && (rc = block_minima(ln, w, pin, stride, true))) return rc;
+  const double* bmin = w.want_bmin ? (const double*)ln.blockmin.p : nullptr;
+  long long* slist;                              // open points of the verdict: listed and scanned by groups of lanes
+  if ((rc = scan_list(c, ln, w, bmin, 1, &slist))) return rc;
+  long long* amb = (long long*)ln.amb.p;
+  hipLaunchKernelGGL(k_pdt_decide, dim3((unsigned)((w.len0 + 255) / 256), (unsigned)std::min<long long>((w.nl + kDecideLines - 1) / kDecideLines, 65535)),
+                     dim3(256), 0, ln.stream, (const double*)pin, w.nl, (int)w.len0, w.goff / w.len0, w.goff, d >= 2 ? stride : 1, w.last_cnt,
+                     w.last_h, d, w.xscale, (const uint8_t*)c->maskU.p, c->Lmax, a.lidx, a.sc, a.cidx, O, amb, cg, pc_lo, pc_hi, bmin, w.blk, slist);
+  if (slist)
+    with_bool(c->opt.scan_waves == 32 || c->opt.scan_waves == 64, [&](auto WAVE) {      // (lanes per listed point: 32 on request, else 16)
+      hipLaunchKernelGGL((k_pdt_scan_list<WAVE() ? 32 : 16>), dim3(2048), dim3(256), 0, ln.stream, (const double*)pin, w.goff, stride, w.last_cnt,
+                         w.last_h, d, w.xscale, c->Lmax, a.lidx, a.sc, a.cidx, O, amb, bmin, w.blk, (const long long*)slist);
+    });
+  hipLaunchKernelGGL((k_goose_exact<T, D>), dim3(1024), dim3(256), 0, ln.stream, c->cs, s.css, s.W, c->Lmax, a.lidx, a.sc, a.cidx,
+                     (const long long*)amb, O, (gb_of<T>(c, a.v) && !a.v.refined && a.v.band == SetBand::plan) ? 1 : 0);
+  SBO_HIP(hipGetLastError());
+  return SBO_OK;
+}
+// explicit lists and ragged grid ranges: pruned exact pair evaluation over runs of kRun candidates.  `sorted`: sources and targets in
+// the spatial index's order -- the runs' boxes are compact, so the box test skips whole runs.  Coverage is a union of balls: the order
+// of the search cannot change a verdict, and O goes back to the caller's order
+template <typename T, int D>
+static int goose_pairs(const SetCall<T>& a, const GooseSources<T>& s, bool sorted, uint8_t* O) {
+  sbo_ctx* c = a.c;
+  sbo_ctx::SetLane& ln = a.ln;
+  const long long n = c->cs.n_local, nsrc_runs = s.run_hi - s.run_lo;
+  int rc;
+  if (nsrc_runs > 0x7fffffffll) return fail(SBO_E_UNSUPPORTED, "too many source runs");
+  if ((rc = ensure(ln.runmeta, sizeof(RunMeta) * (size_t)std::max<long long>(nsrc_runs, 1)))) return rc;
+  CandSpec cst = c->cs, css = s.css;              // targets and sources, their weights and U flags, the first source run, the verdicts
+  const T* W = s.W;
+  const uint8_t* U = (const uint8_t*)c->maskU.p;
+  long long run_lo = s.run_lo;
+  uint8_t* out = O;
+  const unsigned* perm = nullptr;
+  const unsigned gb = (unsigned)std::min<long long>((n + 255) / 256, (long long)c->n_cu * 16);
+  if (sorted) {
+    const size_t ub = ((size_t)n + 255) / 256 * 256;
+    if ((rc = ensure(ln.lxtree, 2 * ub + sizeof(T) * (size_t)n))) return rc;
+    uint8_t* Us = (uint8_t*)ln.lxtree.p;
+    T* Ws = (T*)(Us + 2 * ub);
+    perm = (const unsigned*)c->lx.vals.p + (size_t)c->lx.perm_half * n;
+    hipLaunchKernelGGL((k_idx_gather<T>), dim3(gb), dim3(256), 0, ln.stream, s.W, perm, n, Ws);
+    hipLaunchKernelGGL((k_idx_gather<uint8_t>), dim3(gb), dim3(256), 0, ln.stream, U, perm, n, Us);
+    cst.pts = c->lx.xs.p, cst.pts_dtype = SBO_F64;
+    css = cst, W = Ws, U = Us, run_lo = 0, out = Us + ub;
+  }
+  hipLaunchKernelGGL((k_goose_run_meta<T, D>), dim3((unsigned)nsrc_runs), dim3(256), 0, ln.stream, css, W, c->Lmax, a.lidx, run_lo, (RunMeta*)ln.runmeta.p);
+  hipLaunchKernelGGL((k_goose_optimistic<T, D>), dim3((unsigned)((n + kRun - 1) / kRun)), dim3(256), 0, ln.stream, cst, css, W, U, c->Lmax, a.lidx,
+                     (const RunMeta*)ln.runmeta.p, run_lo, (int)nsrc_runs, out);
+  if (sorted) hipLaunchKernelGGL(k_idx_scatter_u8, dim3(gb), dim3(256), 0, ln.stream, (const uint8_t*)out, perm, n, O);
+  SBO_HIP(hipGetLastError());
+  return SBO_OK;
+}
+
+// O_c of constraint cidx from the sources `src` (S_t)
 template <typename T, int D>
 static int goose_sets(sbo_ctx* c, sbo_ctx::SetLane& ln, const sbo_sweep_opts* o, const SetView& v, int cidx, const uint8_t* src, uint8_t* O) {
   const long long n = c->cs.n_local;
-  const int q = c->mc.q;
-  const int lidx = o->reference_quirk_L_index ? q - 1 : cidx;   // models/GoOSE.py:100 (loop-leaked i)
-  const T* mean_c = (const T*)v.mean->p + (size_t)cidx * n;
-  const T* var_c = (const T*)v.var->p + (size_t)cidx * n;
+  const int lidx = o->reference_quirk_L_index ? c->mc.q - 1 : cidx;   // models/GoOSE.py:100 (loop-leaked i)
+  const SetCall<T> a{c, ln, o, v, cidx, lidx, (SweepScalars*)ln.scal.p, (const T*)v.mean->p + (size_t)cidx * n, (const T*)v.var->p + (size_t)cidx * n};
   int rc;
   long long maxlocal = n;
   for (int r = 0; r < c->dist.world && multi_rank(c); ++r) maxlocal = std::max(maxlocal, c->dist.first_of[r + 1] - c->dist.first_of[r]);
   if ((rc = ensure(ln.gw, sizeof(T) * (size_t)std::max<long long>(maxlocal, 1)))) return rc;
   if (n > 0)
-    hipLaunchKernelGGL((k_goose_weights<T>), dim3(reduce_blocks(c)), dim3(256), 0, ln.stream, mean_c, var_c, n, (T)o->b, src,
-                       (T*)ln.gw.p, (SweepScalars*)ln.scal.p);
-  CandSpec css = c->cs;                 // the source candidates
-  const T* W = (const T*)ln.gw.p;
-  long long run_lo = 0, run_hi = (n + kRun - 1) / kRun;
-  long long win_p0 = 0, win_p1 = 0;     // ranks > 1: window of hyper-planes holding every source that can matter
-  bool w_is_window = false;             // ranks > 1, slab exchange: W holds exactly the window [win_p0, win_p1)
-  if (multi_rank(c)) {
-    // Sources of the other ranks that can reach this shard lie within H hyper-planes of it (H from the largest source
-    // radius, keys of collective C1 -- exact, as for the expanders).
-    const int d = c->cs.d;
-    long long plane = 1;
-    for (int a = 0; a < d - 1; ++a) plane *= c->cs.count[a];
-    const long long planes_total = c->cs.count[d - 1];
-    long long p0 = c->cs.first / plane, p1 = (c->cs.first + n + plane - 1) / plane;
-    const long long own0 = p0, own1 = p1;
-    const double hl = c->cs.step[d - 1];
-    long long H;
-    if ((rc = halo_for(c, ln, cidx, lidx, hl, planes_total, &H))) return rc;
-    p0 = std::max(0ll, p0 - H);
-    p1 = std::min(planes_total, p1 + H);
-    win_p0 = p0;
-    win_p1 = p1;
-    long long min_planes = planes_total;
-    for (int r = 0; r < c->dist.world; ++r) min_planes = std::min(min_planes, (c->dist.first_of[r + 1] - c->dist.first_of[r]) / plane);
-    if (getenv("SBO_DEBUG_COMM"))
-      fprintf(stderr, "[rank %d] GoOSE sources c=%d: halo %lld planes, smallest shard %lld planes -> %s\n", c->dist.rank, cidx, H, min_planes,
-              (c->dist.sharded && H <= min_planes) ? "slab exchange" : "full all-gather");
-    if (c->dist.sharded && H <= min_planes) {
-      // the halo fits inside the neighbours: every rank contributes only its first and last H planes (2 H plane values
-      // instead of its whole shard), and the window is assembled from the previous rank's top slab, the own shard and
-      // the next rank's bottom slab
-      const size_t slab = (size_t)H * plane;
-      if ((rc = ensure(c->dist.gather, sizeof(T) * slab * 2 * (c->dist.world + 1)))) return rc;
-      if ((rc = ensure(c->dist.Wfull, sizeof(T) * (size_t)(p1 - p0) * plane))) return rc;
-      T* send = (T*)c->dist.gather.p;
-      T* recv = send + 2 * slab;
-      SBO_HIP(hipMemcpyAsync(send, ln.gw.p, sizeof(T) * slab, hipMemcpyDeviceToDevice, ln.stream));
-      SBO_HIP(hipMemcpyAsync(send + slab, (const T*)ln.gw.p + (size_t)n - slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, ln.stream));
-      if ((rc = comm_allgather_bytes(c, send, recv, sizeof(T) * slab * 2))) return rc;
-      T* win = (T*)c->dist.Wfull.p;
-      size_t at = 0;
-      if (own0 > p0) {       // previous rank's top slab (p0 = own0 - H exactly, since H <= its planes)
-        SBO_HIP(hipMemcpyAsync(win, recv + (size_t)(c->dist.rank - 1) * 2 * slab + slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, ln.stream));
-        at = slab;
-      }
-      SBO_HIP(hipMemcpyAsync(win + at, ln.gw.p, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, ln.stream));
-      at += (size_t)n;
-      if (p1 > own1)
-        SBO_HIP(hipMemcpyAsync(win + at, recv + (size_t)(c->dist.rank + 1) * 2 * slab, sizeof(T) * slab, hipMemcpyDeviceToDevice, ln.stream));
-      css.first = p0 * plane;
-      css.n_local = (p1 - p0) * plane;
-      W = (const T*)win;
-      w_is_window = true;
-      run_lo = 0;
-      run_hi = (css.n_local + kRun - 1) / kRun;
-    } else {
-      // wide halo: all-gather the whole weight shards
-      if ((rc = ensure(c->dist.gather, sizeof(T) * (size_t)maxlocal * c->dist.world))) return rc;
-      if ((rc = ensure(c->dist.Wfull, sizeof(T) * (size_t)c->dist.grid_total))) return rc;
-      if ((rc = comm_allgather_bytes(c, ln.gw.p, c->dist.gather.p, sizeof(T) * (size_t)maxlocal))) return rc;
-      hipLaunchKernelGGL(k_compact_shards<T>, dim3((unsigned)std::min<long long>((c->dist.grid_total + 255) / 256, 1 << 16)), dim3(256), 0,
-                         ln.stream, (const T*)c->dist.gather.p, maxlocal, c->dist.world, (const long long*)c->dist.shard_first.p, c->dist.grid_total,
-                         (T*)c->dist.Wfull.p);
-      css.first = 0;
-      css.n_local = c->dist.grid_total;
-      W = (const T*)c->dist.Wfull.p;
-      run_lo = p0 * plane / kRun;
-      run_hi = (p1 * plane + kRun - 1) / kRun;
-    }
-  }
+    hipLaunchKernelGGL((k_goose_weights<T>), dim3(reduce_blocks(c)), dim3(256), 0, ln.stream, a.mean_c, a.var_c, n, (T)o->b, src, (T*)ln.gw.p, a.sc);
+  const bool transform = whole_planes(c) && !c->opt.goose_pairs;       // grids; lists, ragged ranges and option goose_pairs: pairs
+  SetWindow w;
+  if ((multi_rank(c) || transform) && (rc = set_window(c, ln, cidx, lidx, w))) return rc;   // (ranks > 1: may wait, behind the weights)
+  GooseSources<T> s{c->cs, (const T*)ln.gw.p, 0, (n + kRun - 1) / kRun, false};
+  if (multi_rank(c) && (rc = goose_exchange<T>(a, w, maxlocal, s))) return rc;
   if (n == 0) return SBO_OK;           // (an empty shard still took part in the all-gather)
-  long long plane1;
-  const bool plane_aligned = whole_planes(c, &plane1);
-  if (plane_aligned && !c->opt.goose_pairs) {
-    // grids: power-distance transform of the source weights over the window, verdict by sign, exact recheck in the band
-    const int d = c->cs.d;
-    SweepScalars* sc = (SweepScalars*)ln.scal.p;
-    const long long own0 = c->cs.first / plane1;
-    const long long w0 = multi_rank(c) ? win_p0 : own0, w1 = multi_rank(c) ? win_p1 : own0 + n / plane1;
-    const long long wplanes = w1 - w0, nt = wplanes * plane1, goff = (own0 - w0) * plane1;
-    const T* Wwin = (multi_rank(c) && !w_is_window) ? W + w0 * plane1 : W;
-    if ((rc = ensure(ln.dist2, sizeof(double) * (size_t)nt))) return rc;
-    if (d > 2 && (rc = ensure(ln.dist2b, sizeof(double) * (size_t)nt))) return rc;
-    if ((rc = ensure(ln.amb, sizeof(long long) * (size_t)n))) return rc;
-    double xscale = 0.0;
-    for (int a = 0; a < d; ++a) xscale = std::max(xscale, std::max(std::fabs(c->cs.lo[a]), std::fabs(c->cs.hi[a])));
-    const int count0 = d >= 2 ? (int)c->cs.count[0] : (int)nt;
-    const unsigned gridn = (unsigned)std::min<long long>((nt + 255) / 256, 1 << 20);
-    ln.amb_clean = false;                          // (k_goose_weights cleared the counters)
-    // coarse bounds of the window: decide most candidates (and skip their axis-0 scans) without touching the fine arrays
-    CoarseGrid cg;
-    memset(&cg, 0, sizeof(cg));
-    cg.d = d;
-    bool coarse_ok = d >= 2 && nt >= (1ll << 16);
-    long long nc = 1;
-    for (int a = 0; a < d; ++a) {
-      cg.count[a] = a == d - 1 ? wplanes : c->cs.count[a];
-      cg.ccount[a] = (cg.count[a] + kCoarse - 1) / kCoarse;
-      nc *= cg.ccount[a];
-      if (cg.count[a] < 4 * kCoarse) coarse_ok = false;
-    }
-    const double *pc_lo = nullptr, *pc_hi = nullptr;
-    if (coarse_ok) {
-      cg.enabled = 1;
-      if ((rc = ensure(ln.coarse, (size_t)nc * 5 * sizeof(double) + 64))) return rc;
-      double* lo0 = (double*)ln.coarse.p;
-      double* lo1 = lo0 + nc;
-      double* hi0 = lo1 + nc;
-      double* hi1 = hi0 + nc;
-      hipLaunchKernelGGL((k_pdt_cell_min<T>), dim3((unsigned)std::min<long long>((nc * 8 + 255) / 256, 1 << 18)), dim3(256), 0, ln.stream, Wwin, cg, nc,
-                         c->Lmax, lidx, lo0, hi0);
-      long long cstride = 1;
-      for (int a = 0; a < d; ++a) {
-        hipLaunchKernelGGL(k_pdt_coarse_scan, dim3((unsigned)std::min<long long>((2 * nc * 8 + 255) / 256, 1 << 18)), dim3(256), 0, ln.stream, (const double*)lo0, lo1, (const double*)hi0,
-                           hi1, nc, cstride, (int)cg.ccount[a], c->cs.step[a], (const SweepScalars*)sc, cidx,
-                           c->Lmax, lidx, d, xscale);
-        std::swap(lo0, lo1);
-        std::swap(hi0, hi1);
-        cstride *= cg.ccount[a];
-      }
-      pc_lo = lo0;
-      pc_hi = hi0;
-    }
-    const T* wbmax = nullptr;
-    const int blk0 = 32;
-    if (c->opt.scan_blocks && count0 >= 16 * blk0 && count0 <= 8192 && nt / count0 >= 1024) {
-      // one workgroup per line, the line in LDS (pays once there are enough lines to fill the chip: from 1024 lines on --
-      // config C's 1024 x 1024 grid of the Williams-Otto plant: 33 -> 19 us per constraint against the thread-per-position kernel)
-      const size_t lds = sizeof(double) * ((size_t)count0 + (count0 + kAnchor - 1) / kAnchor) + sizeof(int) * 2 * ((size_t)(count0 + kAnchor - 1) / kAnchor + 2);
-      SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pdt_axis0_lds<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL((k_pdt_axis0_lds<T>), dim3((unsigned)std::min<long long>(nt / count0, 1 << 16)), dim3(256), lds, ln.stream, Wwin,
-                         nt / count0, count0, c->cs.step[0], (const SweepScalars*)sc, cidx, c->Lmax, lidx, d,
-                         xscale, cg, pc_lo, blk0, (double*)ln.dist2.p);
-    } else {
-      if (c->opt.scan_blocks && count0 >= 16 * blk0) {
-        const long long nbw = (nt / count0) * ((count0 + blk0 - 1) / blk0);
-        if ((rc = ensure(ln.blockmax, sizeof(T) * (size_t)nbw))) return rc;
-        hipLaunchKernelGGL((k_block_max_w<T>), dim3((unsigned)std::min<long long>((nbw + 255) / 256, 1 << 20)), dim3(256), 0, ln.stream,
-                           Wwin, nt, count0, blk0, (T*)ln.blockmax.p);
-        wbmax = (const T*)ln.blockmax.p;
-      }
-      hipLaunchKernelGGL((k_pdt_axis0<T>), dim3(gridn), dim3(256), 0, ln.stream, Wwin, nt, count0, c->cs.step[0],
-                         (const SweepScalars*)sc, cidx, c->Lmax, lidx, d, xscale, cg, pc_lo, wbmax,
-                         blk0, (double*)ln.dist2.p);
-    }
-    double* pin = (double*)ln.dist2.p;
-    double* pout = (double*)ln.dist2b.p;
-    long long stride = count0;
-    for (int a = 1; a < d - 1; ++a) {
-      hipLaunchKernelGGL(k_pdt_scan, dim3(gridn), dim3(256), 0, ln.stream, (const double*)pin, pout, nt, stride,
-                         (int)c->cs.count[a], c->cs.step[a], (const SweepScalars*)sc, cidx,
-                         c->Lmax, lidx, d, xscale);
-      std::swap(pin, pout);
-      stride *= c->cs.count[a];
-    }
-    const int last_cnt = d >= 2 ? (int)wplanes : 1;
-    const double last_h = d >= 2 ? c->cs.step[d - 1] : 0.0;
-    const double* bmin = nullptr;
-    const int blk = last_cnt >= 8192 ? 64 : 32;
-    if (d >= 2 && last_cnt >= 4 * blk && c->opt.scan_blocks) {
-      const long long nb_ = (long long)((last_cnt + blk - 1) / blk) * stride;
-      if ((rc = ensure(ln.blockmin, sizeof(double) * (size_t)nb_))) return rc;
-      hipLaunchKernelGGL(k_block_min, dim3((unsigned)std::min<long long>((stride + 63) / 64 * ((last_cnt + blk - 1) / blk), 1 << 20)), dim3(256), 0, ln.stream,
-                         (const double*)pin, stride, last_cnt, blk, (double*)ln.blockmin.p);
-      bmin = (const double*)ln.blockmin.p;
-    }
-    const long long len0 = d >= 2 ? count0 : n, nl = n / len0;    // positions per line / local lines
-    long long* slist = nullptr;                    // open points of the verdict: listed and scanned by groups of lanes
-    if (bmin && blk <= 64 && c->opt.scan_waves) {
-      if ((rc = ensure(ln.scanlist, sizeof(long long) * (size_t)n))) return rc;
-      slist = (long long*)ln.scanlist.p;
-    }
-    hipLaunchKernelGGL(k_pdt_decide, dim3((unsigned)((len0 + 255) / 256), (unsigned)std::min<long long>((nl + kDecideLines - 1) / kDecideLines, 65535)),
-                       dim3(256), 0, ln.stream, (const double*)pin, nl, (int)len0, goff / len0, goff, d >= 2 ? stride : 1, last_cnt, last_h, d,
-                       xscale, (const uint8_t*)c->maskU.p, c->Lmax, lidx, sc, cidx, O, (long long*)ln.amb.p, cg,
-                       pc_lo, pc_hi, bmin, blk, slist);
-    if (slist) {
-      if (c->opt.scan_waves == 32 || c->opt.scan_waves == 64)
-        hipLaunchKernelGGL((k_pdt_scan_list<32>), dim3(2048), dim3(256), 0, ln.stream, (const double*)pin, goff, stride, last_cnt, last_h, d,
-                           xscale, c->Lmax, lidx, sc, cidx, O, (long long*)ln.amb.p, bmin, blk,
-                           (const long long*)slist);
-      else
-        hipLaunchKernelGGL((k_pdt_scan_list<16>), dim3(2048), dim3(256), 0, ln.stream, (const double*)pin, goff, stride, last_cnt, last_h, d,
-                           xscale, c->Lmax, lidx, sc, cidx, O, (long long*)ln.amb.p, bmin, blk,
-                           (const long long*)slist);
-    }
-    hipLaunchKernelGGL((k_goose_exact<T, D>), dim3(1024), dim3(256), 0, ln.stream, c->cs, css, W,
-                       c->Lmax, lidx, sc, cidx, (const long long*)ln.amb.p, O,
-                       (gb_of<T>(c, v) && !v.refined && v.band == SetBand::plan) ? 1 : 0);
-    SBO_HIP(hipGetLastError());
-    return SBO_OK;
-  }
-  // explicit lists and ragged grid ranges: pruned exact pair evaluation over runs of 256 candidates
-  const long long nsrc_runs = run_hi - run_lo;
-  if (nsrc_runs > 0x7fffffffll) return fail(SBO_E_UNSUPPORTED, "too many source runs");
-  if ((rc = ensure(ln.runmeta, sizeof(RunMeta) * (size_t)std::max<long long>(nsrc_runs, 1)))) return rc;
-  if (list_index_on(c) && c->lx.valid) {
-    // sources and targets in the index's sorted order: the runs' boxes are compact, so the box test skips whole runs.  Coverage
-    // is a union of balls: the order of the search cannot change a verdict, and O goes back to the caller's order.
-    const size_t ub = ((size_t)n + 255) / 256 * 256;
-    if ((rc = ensure(ln.lxtree, 2 * ub + sizeof(T) * (size_t)n))) return rc;
-    uint8_t* Us = (uint8_t*)ln.lxtree.p;
-    uint8_t* Os = Us + ub;
-    T* Ws = (T*)(Os + ub);
-    const unsigned* perm = (const unsigned*)c->lx.vals.p + (size_t)c->lx.perm_half * n;
-    const unsigned gb = (unsigned)std::min<long long>((n + 255) / 256, (long long)c->n_cu * 16);
-    hipLaunchKernelGGL((k_idx_gather<T>), dim3(gb), dim3(256), 0, ln.stream, W, perm, n, Ws);
-    hipLaunchKernelGGL((k_idx_gather<uint8_t>), dim3(gb), dim3(256), 0, ln.stream, (const uint8_t*)c->maskU.p, perm, n, Us);
-    CandSpec csx = c->cs;
-    csx.pts = c->lx.xs.p;
-    csx.pts_dtype = SBO_F64;
-    hipLaunchKernelGGL((k_goose_run_meta<T, D>), dim3((unsigned)nsrc_runs), dim3(256), 0, ln.stream, csx, (const T*)Ws,
-                       c->Lmax, lidx, 0ll, (RunMeta*)ln.runmeta.p);
-    hipLaunchKernelGGL((k_goose_optimistic<T, D>), dim3((unsigned)((n + kRun - 1) / kRun)), dim3(256), 0, ln.stream, csx, csx, (const T*)Ws,
-                       (const uint8_t*)Us, c->Lmax, lidx, (const RunMeta*)ln.runmeta.p, 0ll,
-                       (int)nsrc_runs, Os);
-    hipLaunchKernelGGL(k_idx_scatter_u8, dim3(gb), dim3(256), 0, ln.stream, (const uint8_t*)Os, perm, n, O);
-    SBO_HIP(hipGetLastError());
-    return SBO_OK;
-  }
-  hipLaunchKernelGGL((k_goose_run_meta<T, D>), dim3((unsigned)nsrc_runs), dim3(256), 0, ln.stream, css, W,
-                     c->Lmax, lidx, run_lo, (RunMeta*)ln.runmeta.p);
-  hipLaunchKernelGGL((k_goose_optimistic<T, D>), dim3((unsigned)((n + kRun - 1) / kRun)), dim3(256), 0, ln.stream, c->cs, css, W,
-                     (const uint8_t*)c->maskU.p, c->Lmax, lidx, (const RunMeta*)ln.runmeta.p,
-                     run_lo, (int)nsrc_runs, O);
-  SBO_HIP(hipGetLastError());
-  return SBO_OK;
+  if (transform) return goose_transform<T, D>(a, w, s, O);
+  return goose_pairs<T, D>(a, s, list_index_on(c) && c->lx.valid, O);
 }
 
 template <typename T>
