@@ -295,7 +295,22 @@ int sbo_model_set_prior(sbo_ctx* ctx, int dtype, const char* kernel, int n, int 
  * everything a posterior or a sweep reads are unchanged. */
 int sbo_model_append(sbo_ctx* ctx, const double* x_norm_new, const double* y_norm_new);
 
-/* Its counterpart: observation `index` (0-based, in the order of X_norm as set and appended) leaves the resident model.  The
+/* k observations in one block update: x_norm_new [k][d] and y_norm_new [k][q], normalised with the frozen
+ * constants of the last sbo_model_set, enter in call order as observations n .. n + k - 1 and n becomes n + k; every later call sees
+ * the larger model.  The result is the model k calls of sbo_model_append would leave (a lower factor with positive diagonal is
+ * unique), but the two triangular products run as (n x n) (n x k) block products over the whole chip, followed by one k x k Schur
+ * complement with its Cholesky, one verdict read-back, one re-pack of the factor images and one invalidation of the plans.  All
+ * or nothing: every output's update is computed and checked before anything of the model is written; on any error n, the factor,
+ * alpha and everything a posterior or a sweep reads are bit for bit as before (a grown capacity of the factor may stay).  Fails
+ * with SBO_E_INVALID for NULL pointers, k < 1, k > SBO_MAX_APPEND, a non-finite coordinate or output, or a Schur pivot that is not
+ * > 0 on some output (the message names the output and the row of the block); with SBO_E_UNSUPPORTED when n + k > SBO_MAX_N (no
+ * row is appended, not even a prefix); with SBO_E_NO_MODEL without a model.  Waits first for a deferred factorisation.
+ * Deterministic: the same model and the same rows give the same bits.  Multi-rank: the model is replicated, every rank makes the
+ * same call, nothing is communicated. */
+#define SBO_MAX_APPEND 64
+int sbo_model_append_batch(sbo_ctx* ctx, int k, const double* x_norm_new /* [k][d] */, const double* y_norm_new /* [k][q] */);
+
+/* The counterpart of sbo_model_append: observation `index` (0-based, in the order of X_norm as set and appended) leaves the resident model.  The
  * hyper-parameters, the normalisation constants and the prior mean stay frozen, the remaining observations keep their order
  * (row i > index becomes row i - 1) and n becomes n - 1; the lower factor and alpha are updated in O(n^2) on the device
  *  and no [n, n] matrix crosses the bus.  Every later call -- posterior, sweeps, refinement, an append,

@@ -299,6 +299,85 @@ class GP:
         self.hypopt, self.invKopt = self.determine_hyperparameters(self.X_norm, self.Y_norm)
         self.update_inference_dataset()
 
+    def add_samples(self, X_new, Y_new, incremental: bool = True, window: int | None = None, refit_when=None):
+        """k observations at once -- the other half of ``Batch``: ``X_new`` [k, d], ``Y_new`` [k, q] in physical units.
+        ``incremental=True`` (the default here) normalises them with the frozen constants and makes one ``append_samples`` call
+        (``sbo_model_append_batch``: one block update of the device model); the Python-side ``inference_datasets`` follows with the
+        block-bordered inverse per output, [[invK + U S^-1 U^T, -U S^-1], [-S^-1 U^T, S^-1]] with U = invK K(X, X_new) and
+        S = K(X_new, X_new) + sn2 I - K(X_new, X) U; an element of a ``LazyInvK`` nobody has read stays unformed, now over all rows.
+        More than ``SBO_MAX_APPEND`` rows are split into consecutive blocks here.  ``window=W`` (1 <= k < W) removes the
+        ``max(0, n + k - W)`` oldest observations (``remove_sample(0)``) before the append, so n never exceeds W.  ``refit_when`` is
+        asked once, after the block, as in ``add_sample``.  ``incremental=False`` stacks the rows and runs the default path once
+        (re-normalise, refit, rebuild) -- the reference, fed the same rows one by one, would have refitted k times."""
+        from ._lib import SBO_MAX_APPEND
+        X_new, Y_new = np.asarray(X_new, dtype=np.float64), np.asarray(Y_new, dtype=np.float64)
+        if X_new.ndim != 2 or Y_new.ndim != 2 or X_new.shape[1] != self.nx_dim or Y_new.shape[1] != self.ny_dim \
+                or X_new.shape[0] != Y_new.shape[0]:
+            raise ValueError("X_new must be [k, d] and Y_new [k, q]")
+        k = X_new.shape[0]
+        if k < 1:
+            raise ValueError("add_samples needs at least one row")
+        if not (np.all(np.isfinite(X_new)) and np.all(np.isfinite(Y_new))):
+            raise ValueError("X_new and Y_new must be finite")
+        if refit_when is not None:
+            if not incremental:
+                raise ValueError("refit_when needs incremental=True (the default path refits on the stacked data)")
+            if not callable(refit_when):
+                raise ValueError("refit_when must be callable: it receives the dict of loo()")
+        if window is not None:
+            if not incremental:
+                raise ValueError("window needs incremental=True (the default path refits on all data)")
+            if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1:
+                raise ValueError("window must be an integer >= 1")
+            if not k < window:
+                raise ValueError(f"a block of k = {k} rows needs window > k")
+            for _ in range(max(0, self.n_point + k - int(window))):
+                self.remove_sample(0)
+        if not incremental:
+            self.X, self.Y = np.vstack([self.X, X_new]), np.vstack([self.Y, Y_new])
+            self.n_point = self.X.shape[0]
+            self.X_norm, self.Y_norm = self.data_normalization()
+            self.hypopt, self.invKopt = self.determine_hyperparameters(self.X_norm, self.Y_norm)
+            self.update_inference_dataset()
+            return
+        self._sync_model()
+        d = self.nx_dim
+        for b0 in range(0, k, SBO_MAX_APPEND):
+            xn = (X_new[b0:b0 + SBO_MAX_APPEND] - self.X_mean) / self.X_std
+            yn = (Y_new[b0:b0 + SBO_MAX_APPEND] - self.Y_mean) / self.Y_std
+            self.engine.append_samples(xn, yn)
+            X_norm = np.vstack([self.X_norm, xn])
+            lazy = isinstance(self.invKopt, LazyInvK)
+            if lazy:                              # what nobody has read stays unformed, now over all rows
+                hypopt, old = self.hypopt, self.invKopt
+                self.invKopt = LazyInvK(lambda i, X_norm=X_norm, hypopt=hypopt: self._invK(X_norm, hypopt, i), self.ny_dim)
+            for i in range(self.ny_dim):
+                if lazy and old._items[i] is None:
+                    continue
+                P = old._items[i] if lazy else self.invKopt[i]
+                ell, sf2 = np.exp(2.0 * self.hypopt[:d, i]), np.exp(2.0 * self.hypopt[d, i])
+                sn2 = np.exp(2.0 * self.hypopt[d + 1, i]) + FLOAT32_EPS
+                B = self.Cov_mat(self.kernel, self.X_norm, xn, ell, sf2)
+                Z = self.Cov_mat(self.kernel, xn, xn, ell, sf2) + sn2 * np.eye(xn.shape[0])
+                U = P @ B
+                # (kept exactly symmetric: an asymmetry of P would enter the border through U = P B and grow from block to block)
+                Sinv = np.linalg.inv(Z - B.T @ U)
+                Sinv = 0.5 * (Sinv + Sinv.T)
+                USinv = U @ Sinv
+                top = P + USinv @ U.T
+                self.invKopt[i] = np.block([[0.5 * (top + top.T), -USinv], [-USinv.T, Sinv]])
+            self.X = np.vstack([self.X, X_new[b0:b0 + SBO_MAX_APPEND]])
+            self.Y = np.vstack([self.Y, Y_new[b0:b0 + SBO_MAX_APPEND]])
+            self.X_norm, self.Y_norm = X_norm, np.vstack([self.Y_norm, yn])
+            self.n_point = self.X.shape[0]
+        self.update_inference_dataset()              # bumps _model_version: the cached sweeps of SafeOpt / GoOSE.BO are stale
+        self._uploaded_version = self._model_version  # ... but the device model is already current: no re-upload
+        self._cand_token = None
+        if refit_when is not None and refit_when(self.loo()):
+            self.X_norm, self.Y_norm = self.data_normalization()
+            self.hypopt, self.invKopt = self.determine_hyperparameters(self.X_norm, self.Y_norm)
+            self.update_inference_dataset()
+
     def remove_sample(self, index: int):
         """The mirror of ``add_sample(..., incremental=True)``: observation ``index`` leaves the model under the frozen
         normalisation constants and hyper-parameters, O(n^2) on the device (``sbo_model_remove``).  The Python-side

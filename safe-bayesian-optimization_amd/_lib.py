@@ -15,6 +15,7 @@ SBO_MAX_N = 2048
 SBO_COMM_ID_BYTES = 128
 SBO_ROBUST_MAX_SCEN = 8
 SBO_MAX_BATCH = 64
+SBO_MAX_APPEND = 64
 
 SBO_F64, SBO_F32 = 0, 1
 SBO_MEAN, SBO_UCB, SBO_LCB, SBO_VAR = 0, 1, 2, 3
@@ -193,6 +194,7 @@ SYMBOLS = [
     ("sbo_model_set_list", C.c_int, [_P, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("sbo_model_set_prior", C.c_int, [_P, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("sbo_model_append", C.c_int, [_P, _P, _P]),
+    ("sbo_model_append_batch", C.c_int, [_P, C.c_int, _P, _P]),
     ("sbo_model_remove", C.c_int, [_P, C.c_int]),
     ("sbo_model_loo", C.c_int, [_P, C.c_double, _P, _P, C.POINTER(ModelLooResult)]),
     ("sbo_candidates_points", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int64]),

@@ -545,6 +545,48 @@ int sbo_model_append(sbo_ctx* c, const double* x_norm_new, const double* y_norm_
   return SBO_OK;
 }
 
+// k observations in one block update: the sequence of sbo_model_append with the block kernels in the middle --
+// one verdict wait, one re-pack, one invalidation for the k rows.
+int sbo_model_append_batch(sbo_ctx* c, int k, const double* x_norm_new, const double* y_norm_new) {
+  if (c) guard_audit_harvest(c, true);
+  if (!c || !x_norm_new || !y_norm_new) return fail(SBO_E_INVALID, "NULL argument");
+  if (k < 1 || k > SBO_MAX_APPEND) return fail(SBO_E_INVALID, "k out of range [1, SBO_MAX_APPEND]");
+  if (!c->has_model || !c->Fplain.p) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
+  ModelConst& mc = c->mc;
+  const int n = mc.n, d = mc.d, q = mc.q;
+  for (size_t i = 0; i < (size_t)k * d; ++i)
+    if (!std::isfinite(x_norm_new[i])) return fail(SBO_E_INVALID, "x_norm_new must be finite");
+  for (size_t i = 0; i < (size_t)k * q; ++i)
+    if (!std::isfinite(y_norm_new[i])) return fail(SBO_E_INVALID, "y_norm_new must be finite");
+  if (n + k > SBO_MAX_N) return fail(SBO_E_UNSUPPORTED, "the block does not fit below SBO_MAX_N: rebuild the model with sbo_model_set");
+  SBO_HIP(hipSetDevice(c->device));
+  { const int rcf = factor_sync(c); if (rcf) return rcf; }     // (the update works on the resident factor)
+  // the observations the cross-covariances are formed from (device, k_append_cross) and the residuals of the new rows
+  std::vector<double> Xall(c->h_Xnorm.begin(), c->h_Xnorm.begin() + (size_t)n * d);
+  Xall.insert(Xall.end(), x_norm_new, x_norm_new + (size_t)k * d);
+  std::vector<double> rho((size_t)q * k);
+  for (int o = 0; o < q; ++o)
+    for (int r = 0; r < k; ++r) rho[(size_t)o * k + r] = y_norm_new[(size_t)r * q + o] - mc.mp[o];
+  // every output's update is computed and checked before anything is written: a refused block leaves the model as it was
+  int rc = model_append_block_check(c, k, Xall, rho);
+  if (rc) return rc;
+  // (the fp64 twin of an fp32 model makes the same call and must accept first; a twin left behind by an earlier fp32 model is not
+  // this model's, as in sbo_model_remove)
+  if (c->dtype == SBO_F32 && c->recheck.shadow && c->recheck.shadow->has_model && c->recheck.shadow->mc.n == n &&
+      (rc = sbo_model_append_batch(c->recheck.shadow, k, x_norm_new, y_norm_new)))
+    return rc;
+  if ((rc = model_append_block_commit(c, k))) return rc;
+  // the derived arrays with the new rows (device), then one re-pack of the factor images
+  c->h_Xnorm = std::move(Xall);
+  mc.n = n + k;
+  mc.npad = (mc.n + 15) / 16 * 16;
+  if ((rc = model_prep(c, c->h_Xnorm.data()))) return rc;
+  if ((rc = model_repack(c))) return rc;
+  ++c->model_serial;
+  model_changed(c);
+  return SBO_OK;
+}
+
 // The counterpart of sbo_model_append: observation `index` leaves the resident model under the same frozen
 // hyper-parameters and normalisation, O(n^2) on the device; the rows behind it move up by one.
 int sbo_model_remove(sbo_ctx* c, int index) {

@@ -677,6 +677,9 @@ int model_factor_enqueue(sbo_ctx* c);
 int model_pack_invk(sbo_ctx* c);         // images of the caller's invK for the K1b tables, when the grid arrived after the model   // the deferred factor chain of a caller's invK, behind everything on the critical path
 int model_append_check(sbo_ctx* c, const std::vector<double>& kvec /*[q][n]*/, const double* kappa, const double* rho);
 int model_append_commit(sbo_ctx* c);   // (after model_append_check succeeded; mc.n still the old n)
+// the block form: Xall [n + k][d] the model's observations followed by the k new rows, rho [q][k] = y_norm_new - mp
+int model_append_block_check(sbo_ctx* c, int k, const std::vector<double>& Xall, const std::vector<double>& rho);
+int model_append_block_commit(sbo_ctx* c, int k);   // (after model_append_block_check succeeded; mc.n still the old n)
 int model_remove(sbo_ctx* c, int index);   // the factor and alpha without observation `index` (mc.n still the old n); enqueued, not waited for
 // leave-one-out diagnostics of the resident factor / alpha; waited for: *host then points at LooSummary[kMaxQ] | resid [n][q] | var [n][q]
 // (the arrays only with `arrays`)

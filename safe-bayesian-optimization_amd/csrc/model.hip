@@ -549,6 +549,345 @@ __global__ __launch_bounds__(1024) void k_model_append_commit(int n, int ld, dou
   for (int j = n + 1 + tid; j < ld; j += blockDim.x) M[(size_t)n * ld + j] = 0.0;
 }
 
+// k observations in one block update.  With B = K(X, X_new) [n][k], Z = K(X_new, X_new) + sn2 I, rho = y_new - mp:
+//   T = M B,  U = M^T T (= invK B),  S = Z - B^T U,  g = B^T alpha,  S = R R^T,  G = R^-1,  w = G^T G (g - rho);
+//   rows n + r of M: -(G U^T)[r] | G[r][0..r] | 0;   alpha[0..n) += U w,  alpha[n..n+k) = -w
+// -- the factor k calls of k_model_append would leave (a lower factor with positive diagonal is unique), with the two triangular
+// products as block products over the whole chip.  The block's columns are padded to kp = a multiple of kAppColBlock; the padding
+// columns of B are zero and stay zero through T and U, so that no kernel needs a column guard.  Launches, fp64 throughout:
+//   k_append_cross : B [q][n][kp] (column c of the block contiguous: a wave reads <= 512 contiguous bytes per row) and Z [q][kp][kp]
+//                    from the fp64 observations with the expanded distance; Z[r][c] is formed once for r < c and mirrored;
+//   k_append_t     : T = M B.  A wave owns kAppRows rows of M, lanes along the block's columns: M[i][j] is wave-uniform, rows of B and T
+//                    are coalesced; the sum of (i, c) runs over j = 0 .. i in index order in one accumulator;
+//   k_append_u     : U = M^T T.  A wave owns a strip of 64 columns j of M (lanes along them: a row segment is one coalesced load, as
+//                    k_model_remove) and kAppColBlock columns of the block; T[i][c] is a broadcast read; the sum of (j, c) runs over
+//                    i = j .. n - 1 in index order in one accumulator;
+//   k_append_s     : S = Z - B^T U, a wave per kAppSRows rows of S, lanes along its columns, and g = B^T alpha in one more wave;
+//                    every sum over j = 0 .. n - 1 in index order in one accumulator;
+//   k_append_chol  : one workgroup per output: the lower Cholesky of S in LDS (IEEE sqrt and division; a pivot that is not > 0 flags
+//                    bad[o] = 1 + its row), G = R^-1, w;
+//   k_append_commit: once the host has seen every output accepted: the k new rows (lanes along the columns, coalesced writes; the sum
+//                    over c <= r of G[r][c] U[j][c] in index order), zeros right of the diagonal up to ld, alpha.
+// Nothing above the diagonal of the resident factor is read (a build leaves scratch there), no kernel but the last writes the factor
+// or alpha, no atomics, and no sum depends on the launch shape.
+constexpr int kAppRows = 4;          // k_append_t: rows of M per wave
+constexpr int kAppWaves = 4;         // ... waves per workgroup
+constexpr int kAppColBlock = 8;      // k_append_u: columns of the block per wave; the block's padded width is a multiple of it
+constexpr int kAppSRows = 4;         // k_append_s: rows of S per wave
+static_assert(SBO_MAX_APPEND == 64 && SBO_MAX_APPEND % kAppColBlock == 0 && kAppColBlock % kAppSRows == 0, "the block is one wave wide");
+
+template <int D>
+__global__ __launch_bounds__(256) void k_append_cross(const ModelConst mc, int n, int k, int kp, const double* __restrict__ Xall /* [n + k][d] */,
+                                                      double* __restrict__ B, double* __restrict__ Z) {
+  const int o = blockIdx.y, d = mc.d;
+  const double sf2 = mc.sf2[o], sn2 = mc.sn2[o];
+  double* Bo = B + (size_t)o * n * kp;
+  double* Zo = Z + (size_t)o * kp * kp;
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < (long long)(n + kp) * kp; idx += (long long)gridDim.x * blockDim.x) {
+    const int row = (int)(idx / kp), c = (int)(idx % kp);
+    const int r = row - n;                                   // row of Z (row >= n)
+    double v = 0.0;
+    if (c < k && r < k) {
+      // the older observation is `a` of the expanded distance, as in a row-by-row append
+      const int ia = r < 0 ? row : n + min(r, c), ib = r < 0 ? n + c : n + max(r, c);
+      if (r == c) {
+        v = sf2 + sn2;                                       // kappa, as sbo_model_append sets it
+      } else {
+        double dot = 0.0, asq = 0.0, bsq = 0.0;
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+          if (a < d) {
+            const double va = Xall[(size_t)ia * d + a] * mc.vinv[o][a], vb = Xall[(size_t)ib * d + a] * mc.vinv[o][a];
+            dot += va * vb;
+            asq += va * va;
+            bsq += vb * vb;
+          }
+        }
+        v = sf2 * exp(-0.5 * ((-2.0 * dot + asq) + bsq));
+      }
+    }
+    if (r < 0) Bo[(size_t)row * kp + c] = v;
+    else Zo[(size_t)r * kp + c] = v;
+  }
+}
+
+// Steps of kAppStep columns: the wave fetches the rows' segments M[i][j0 .. j0 + 63] (one coalesced load per row, zero right of a
+// row's diagonal; the next step's segments are requested before this step's arithmetic), every lane its 64 values of B, all in
+// flight at once; M[i][j] then reaches the multiply as a wave-uniform operand (readlane).  The terms right of the diagonal are +0
+// and leave the sum as it is.
+constexpr int kAppStep = 64;
+__global__ __launch_bounds__(64 * kAppWaves) void k_append_t(int n, int ld, int kp, const double* __restrict__ F, const double* __restrict__ B,
+                                                             double* __restrict__ T) {
+  const int o = blockIdx.y, lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int i0 = ((int)blockIdx.x * kAppWaves + wave) * kAppRows;
+  if (i0 >= n) return;
+  const int c = min(lane, kp - 1);                           // (lanes past the block's width repeat its last column and store nothing)
+  const double* M = F + (size_t)o * ld * ld;
+  const double* Bo = B + (size_t)o * n * kp + c;
+  const int ilast = min(i0 + kAppRows, n) - 1;
+  double acc[kAppRows], m[kAppRows], mnext[kAppRows];
+#pragma unroll
+  for (int u = 0; u < kAppRows; ++u) {
+    acc[u] = 0.0;
+    m[u] = (i0 + u < n && lane <= i0 + u) ? M[(size_t)(i0 + u) * ld + lane] : 0.0;
+  }
+  for (int j0 = 0; j0 <= ilast; j0 += kAppStep) {
+    double b[kAppStep];
+    const int jn = j0 + kAppStep + lane;
+#pragma unroll
+    for (int u = 0; u < kAppRows; ++u) mnext[u] = (i0 + u < n && jn <= i0 + u) ? M[(size_t)(i0 + u) * ld + jn] : 0.0;
+#pragma unroll
+    for (int t = 0; t < kAppStep; ++t) b[t] = Bo[(size_t)min(j0 + t, n - 1) * kp];      // (past the last row: any finite value, its factor is 0)
+#pragma unroll
+    for (int t = 0; t < kAppStep; ++t) {
+#pragma unroll
+      for (int u = 0; u < kAppRows; ++u) acc[u] = fma(readlane_f64(m[u], t), b[t], acc[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < kAppRows; ++u) m[u] = mnext[u];
+  }
+  if (lane < kp) {
+    double* To = T + (size_t)o * n * kp + lane;
+#pragma unroll
+    for (int u = 0; u < kAppRows; ++u)
+      if (i0 + u < n) To[(size_t)(i0 + u) * kp] = acc[u];
+  }
+}
+
+// Steps of kAppURows rows: every lane fetches its column's 128 values of M (coalesced row segments, zero above the diagonal) and two
+// rows of the step's [128][kAppColBlock] tile of T, all in flight at once -- the walk down a strip is bound by the latency of these
+// loads, so as many as the registers hold --; the tile goes through LDS, from where T[i][c] is a broadcast read.
+constexpr int kAppURows = 128;
+__global__ __launch_bounds__(64) void k_append_u(int n, int ld, int kp, const double* __restrict__ F, const double* __restrict__ T,
+                                                 double* __restrict__ U) {
+  static_assert(kAppURows == 2 * 64, "two rows of the tile per lane");
+  __shared__ __attribute__((aligned(32))) double sT[kAppURows][kAppColBlock];
+  const int o = blockIdx.z, c0 = (int)blockIdx.y * kAppColBlock, j0 = (int)blockIdx.x * 64, lane = threadIdx.x, j = j0 + lane;
+  const double* M = F + (size_t)o * ld * ld;
+  const double* To = T + (size_t)o * n * kp + c0;
+  double acc[kAppColBlock];
+#pragma unroll
+  for (int cc = 0; cc < kAppColBlock; ++cc) acc[cc] = 0.0;
+  for (int i0 = j0; i0 < n; i0 += kAppURows) {
+    double x[kAppURows];
+#pragma unroll
+    for (int u = 0; u < kAppURows; ++u) {
+      const int i = i0 + u;
+      x[u] = (i < n && j <= i) ? M[(size_t)i * ld + j] : 0.0;          // (j <= i < n: inside the triangle)
+    }
+    double tv[2][kAppColBlock];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+      for (int e = 0; e < kAppColBlock; ++e) tv[h][e] = i0 + 64 * h + lane < n ? To[(size_t)(i0 + 64 * h + lane) * kp + e] : 0.0;
+    }
+    __syncthreads();                                         // (the previous step's reads of the tile are done)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+      for (int e = 0; e < kAppColBlock; ++e) sT[64 * h + lane][e] = tv[h][e];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < kAppURows; ++u) {
+#pragma unroll
+      for (int cc = 0; cc < kAppColBlock; ++cc) acc[cc] = fma(x[u], sT[u][cc], acc[cc]);      // (rows above the lane's diagonal and past n add +0)
+    }
+  }
+  if (j < n) {
+    double* dst = U + ((size_t)o * n + j) * kp + c0;
+#pragma unroll
+    for (int cc = 0; cc < kAppColBlock; ++cc) dst[cc] = acc[cc];
+  }
+}
+
+// blockIdx.x < kp / kAppSRows: rows of S;  the last workgroup: g.  Steps of kAppStep rows j: every lane fetches its column's 64 values
+// of U and one row of the step's [64][kAppSRows] tile of B, all in flight at once; the tile goes through LDS, from where B[j][r] is a
+// broadcast read (g: alpha[j] by readlane).
+__global__ __launch_bounds__(64) void k_append_s(int n, int a_ld, int kp, const double* __restrict__ B, const double* __restrict__ U,
+                                                 const double* __restrict__ Z, const double* __restrict__ alpha, double* __restrict__ S,
+                                                 double* __restrict__ g) {
+  static_assert(kAppStep == 64, "one row of the tile per lane");
+  __shared__ __attribute__((aligned(32))) double sB[kAppStep][kAppSRows];
+  const int o = blockIdx.y, lane = threadIdx.x, c = min(lane, kp - 1);
+  const double* Bo = B + (size_t)o * n * kp;
+  if ((int)blockIdx.x == kp / kAppSRows) {
+    const double* al = alpha + (size_t)o * a_ld;
+    double s = 0.0;
+    for (int j0 = 0; j0 < n; j0 += kAppStep) {
+      double b[kAppStep];
+      const double av = j0 + lane < n ? al[j0 + lane] : 0.0;
+#pragma unroll
+      for (int t = 0; t < kAppStep; ++t) b[t] = Bo[(size_t)min(j0 + t, n - 1) * kp + c];
+#pragma unroll
+      for (int t = 0; t < kAppStep; ++t) s = fma(b[t], readlane_f64(av, t), s);
+    }
+    if (lane < kp) g[(size_t)o * kp + lane] = s;
+    return;
+  }
+  const int r0 = (int)blockIdx.x * kAppSRows;
+  const double* Uo = U + (size_t)o * n * kp + c;
+  double acc[kAppSRows];
+#pragma unroll
+  for (int u = 0; u < kAppSRows; ++u) acc[u] = 0.0;
+  for (int j0 = 0; j0 < n; j0 += kAppStep) {
+    double uv[kAppStep], bv[kAppSRows];
+#pragma unroll
+    for (int u = 0; u < kAppSRows; ++u) bv[u] = j0 + lane < n ? Bo[(size_t)(j0 + lane) * kp + r0 + u] : 0.0;
+#pragma unroll
+    for (int t = 0; t < kAppStep; ++t) uv[t] = Uo[(size_t)min(j0 + t, n - 1) * kp];      // (past the last row: its factor is 0)
+    __syncthreads();                                         // (the previous step's reads of the tile are done)
+#pragma unroll
+    for (int u = 0; u < kAppSRows; ++u) sB[lane][u] = bv[u];
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < kAppStep; ++t) {
+#pragma unroll
+      for (int u = 0; u < kAppSRows; ++u) acc[u] = fma(sB[t][u], uv[t], acc[u]);
+    }
+  }
+  if (lane < kp) {
+#pragma unroll
+    for (int u = 0; u < kAppSRows; ++u) S[((size_t)o * kp + r0 + u) * kp + lane] = Z[((size_t)o * kp + r0 + u) * kp + lane] - acc[u];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_append_chol(int k, int kp, const double* __restrict__ S, const double* __restrict__ g,
+                                                     const double* __restrict__ rho, double* __restrict__ G, double* __restrict__ w,
+                                                     int* __restrict__ bad) {
+  // A: below the diagonal R; above it, transposed, first the running sums and then the entries of G = R^-1 (A[c][r] <-> G[r][c],
+  // r > c); the diagonals of R and G in dg and ginv.  One array: two would not fit 64 KiB.
+  constexpr int K = SBO_MAX_APPEND;
+  __shared__ double A[K][K + 1];
+  __shared__ double dg[K], ginv[K], e[K], v[K];
+  __shared__ int sh_bad;
+  const int o = blockIdx.x, tid = threadIdx.x;
+  const double* So = S + (size_t)o * kp * kp;
+  if (tid == 0) sh_bad = 0;
+  for (int idx = tid; idx < K * K; idx += blockDim.x) {
+    const int r = idx / K, c = idx % K;
+    A[r][c] = (r < k && c <= r) ? So[(size_t)r * kp + c] : 0.0;      // (the lower triangle is the one that is factored)
+  }
+  __syncthreads();
+  // S = R R^T, right-looking: every element receives its updates in the order of the pivots
+  for (int jj = 0; jj < k; ++jj) {
+    const double piv = A[jj][jj];                            // (nobody writes the diagonal)
+    if (tid == 0 && !(piv > 0.0) && sh_bad == 0) sh_bad = 1 + jj;
+    const double rjj = sqrt(piv > 0.0 ? piv : 1.0);
+    if (tid > jj && tid < k) A[tid][jj] = A[tid][jj] / rjj;
+    if (tid == jj) dg[jj] = rjj;
+    __syncthreads();
+    {                                                        // column c = tid % K, rows r = tid / K + 4 s: operands first, then the stores
+      const int c = tid & (K - 1), rb = tid >> 6;
+      const double lc = A[c][jj];
+      double a[K / 4], lr[K / 4];
+#pragma unroll
+      for (int s = 0; s < K / 4; ++s) {
+        a[s] = A[rb + 4 * s][c];
+        lr[s] = A[rb + 4 * s][jj];
+      }
+#pragma unroll
+      for (int s = 0; s < K / 4; ++s) {
+        const int r = rb + 4 * s;
+        if (c > jj && c <= r && r < k) A[r][c] = a[s] - lr[s] * lc;
+      }
+    }
+    __syncthreads();
+  }
+  // G = R^-1, right-looking as well: G[t][c] = (delta_tc - sum_{t' < t} R[t][t'] G[t'][c]) / R[t][t], the sum of (r, c) growing by
+  // the term of t once row t of G is known -- in the order of t
+  for (int t = 0; t < k; ++t) {
+    if (tid < t) A[tid][t] = -A[tid][t] / dg[t];
+    if (tid == t) ginv[t] = 1.0 / dg[t];
+    __syncthreads();
+    {                                                        // row r = tid % K of R, columns c = tid / K + 4 s of G: operands first
+      const int r = tid & (K - 1), cb = tid >> 6;
+      const double rt = A[r][t], gt = ginv[t];
+      double a[K / 4], gc[K / 4];
+#pragma unroll
+      for (int s = 0; s < K / 4; ++s) {
+        a[s] = A[cb + 4 * s][r];
+        gc[s] = A[cb + 4 * s][t];
+      }
+#pragma unroll
+      for (int s = 0; s < K / 4; ++s) {
+        const int c = cb + 4 * s;
+        if (c <= t && r > t && r < k) A[c][r] = fma(rt, c == t ? gt : gc[s], a[s]);
+      }
+    }
+    __syncthreads();
+  }
+  if (tid < k) e[tid] = g[(size_t)o * kp + tid] - rho[(size_t)o * kp + tid];
+  __syncthreads();
+  if (tid < k) {                                             // v = G e
+    double s = 0.0;
+    for (int c = 0; c < tid; ++c) s = fma(A[c][tid], e[c], s);
+    v[tid] = fma(ginv[tid], e[tid], s);
+  }
+  __syncthreads();
+  if (tid < kp) {                                            // w = G^T v  (padding columns: 0)
+    double s = 0.0;
+    if (tid < k) {
+      s = ginv[tid] * v[tid];
+      for (int r = tid + 1; r < k; ++r) s = fma(A[tid][r], v[r], s);
+    }
+    w[(size_t)o * kp + tid] = s;
+  }
+  for (int idx = tid; idx < kp * kp; idx += blockDim.x) {
+    const int r = idx / kp, c = idx % kp;
+    G[(size_t)o * kp * kp + idx] = (r < k && c <= r) ? (c == r ? ginv[r] : A[c][r]) : 0.0;
+  }
+  if (tid == 0) bad[o] = sh_bad;
+}
+
+// A wave per 64 columns of the new rows.  Left of column n a lane keeps its row of U in registers and walks the rows of G (LDS,
+// broadcast reads; the entries right of G's diagonal and in the padding are zero and leave the sum as it is).
+__global__ __launch_bounds__(64) void k_append_commit(int n, int ld, int a_ld, int k, int kp, double* __restrict__ F, double* __restrict__ alpha,
+                                                      const double* __restrict__ U, const double* __restrict__ G, const double* __restrict__ w) {
+  constexpr int K = SBO_MAX_APPEND;
+  __shared__ double sG[K][K];
+  __shared__ double sw[K];
+  const int o = blockIdx.y, lane = threadIdx.x, j0 = (int)blockIdx.x * 64, j = j0 + lane;
+  double* M = F + (size_t)o * ld * ld;
+  if (j0 >= n + k) {                                         // right of the new diagonal block: zeros
+    if (j < ld)
+      for (int r = 0; r < k; ++r) M[(size_t)(n + r) * ld + j] = 0.0;
+    return;
+  }
+  for (int idx = lane; idx < K * K; idx += 64) {
+    const int r = idx / K, c = idx % K;
+    sG[r][c] = (r < kp && c < kp) ? G[((size_t)o * kp + r) * kp + c] : 0.0;
+  }
+  sw[lane] = lane < kp ? w[(size_t)o * kp + lane] : 0.0;
+  double u[K];
+#pragma unroll
+  for (int c = 0; c < K; ++c) u[c] = (j < n && c < kp) ? U[((size_t)o * n + j) * kp + c] : 0.0;
+  __syncthreads();
+  if (j >= ld) return;
+  for (int r = 0; r < k; ++r) {
+    double val = 0.0;
+    if (j < n) {
+      double s = 0.0;
+#pragma unroll
+      for (int c = 0; c < K; ++c) s = fma(sG[r][c], u[c], s);
+      val = -s;
+    } else if (j - n <= r) {
+      val = sG[r][j - n];
+    }
+    M[(size_t)(n + r) * ld + j] = val;                       // (right of the diagonal: 0)
+  }
+  double* al = alpha + (size_t)o * a_ld;
+  if (j < n) {
+    double s = 0.0;
+#pragma unroll
+    for (int c = 0; c < K; ++c) s = fma(u[c], sw[c], s);
+    al[j] += s;
+  } else if (j < n + k) {
+    al[j] = -sw[j - n];
+  }
+}
+
 // One observation less.  With m = column j of M (zero above row j, m[j] > 0), M~ = M without column j,
 // r_i = sqrt(sum_{t=j..i} m[t]^2) and the running sum W_i = sum_{t=j..i} m[t] row_t(M~), the Givens rotations that turn m into
 // r_{n-1} e_j leave rows 0 .. j-1 of M~ as they are and give, for i = j+1 .. n-1,
@@ -1017,35 +1356,43 @@ static size_t append_layout(Carve cv, int n, int q, int cap, AppendWork& w) {
   return cv.off;
 }
 
+// Room for `rows` more rows in the resident factor.  A freshly built model keeps its factor tight (leading dimension n): the first
+// append makes room for 256 more rows -- or for the whole block, if that is more --, a later one that does not fit grows it again.
+// The copy keeps every value; a call refused afterwards leaves the larger capacity behind.
+static int factor_reserve(sbo_ctx* c, int rows) {
+  const int n = c->mc.n, q = c->mc.q;
+  if (n + rows <= c->f_cap && c->a_ld == c->f_cap) return SBO_OK;
+  int rc;
+  const int cap = std::min(SBO_MAX_N, std::max((c->mc.npad + 256 + 127) / 128 * 128, (n + rows + 127) / 128 * 128));
+  if (n + rows > cap) return fail(SBO_E_UNSUPPORTED, "model is at its capacity: rebuild it with sbo_model_set");
+  DevBuf F2, a2;
+  if ((rc = ensure(F2, sizeof(double) * (size_t)q * cap * cap))) return rc;
+  if ((rc = ensure(a2, sizeof(double) * (size_t)q * cap))) return rc;
+  hipError_t e = hipMemsetAsync(F2.p, 0, sizeof(double) * (size_t)q * cap * cap, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(a2.p, 0, sizeof(double) * (size_t)q * cap, c->stream);
+  for (int o = 0; o < q && e == hipSuccess; ++o) {
+    e = hipMemcpy2DAsync((double*)F2.p + (size_t)o * cap * cap, sizeof(double) * cap, (const double*)c->Fplain.p + (size_t)o * c->f_cap * c->f_cap,
+                         sizeof(double) * c->f_cap, sizeof(double) * n, n, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync((double*)a2.p + (size_t)o * cap, (const double*)c->alpha64.p + (size_t)o * c->a_ld, sizeof(double) * n,
+                         hipMemcpyDeviceToDevice, c->stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return hip_fail(e, "growing the resident factor");
+  c->Fplain = std::move(F2);
+  c->alpha64 = std::move(a2);
+  c->f_cap = cap;
+  c->a_ld = cap;
+  return SBO_OK;
+}
+
 // kvec [q][n] cross-covariances of the new point, kappa[q] = sf2 + sn2, rho[q] = y_norm_new - mp.  model_append_check
 // computes the update of row n into c->appendbuf and fails with SBO_E_INVALID when an output's s <= 0; nothing of the model
 // changes (growing the factor's capacity copies it and keeps its values).  model_append_commit then writes the update.
 int model_append_check(sbo_ctx* c, const std::vector<double>& kvec, const double* kappa, const double* rho) {
   const int n = c->mc.n, q = c->mc.q;
   int rc;
-  if (n + 1 > c->f_cap || c->a_ld != c->f_cap) {
-    // a freshly built model keeps its factor tight (leading dimension n): make room for 256 more rows
-    const int cap = std::min(SBO_MAX_N, (c->mc.npad + 256 + 127) / 128 * 128);
-    if (n + 1 > cap) return fail(SBO_E_UNSUPPORTED, "model is at its capacity: rebuild it with sbo_model_set");
-    DevBuf F2, a2;
-    if ((rc = ensure(F2, sizeof(double) * (size_t)q * cap * cap))) return rc;
-    if ((rc = ensure(a2, sizeof(double) * (size_t)q * cap))) return rc;
-    hipError_t e = hipMemsetAsync(F2.p, 0, sizeof(double) * (size_t)q * cap * cap, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(a2.p, 0, sizeof(double) * (size_t)q * cap, c->stream);
-    for (int o = 0; o < q && e == hipSuccess; ++o) {
-      e = hipMemcpy2DAsync((double*)F2.p + (size_t)o * cap * cap, sizeof(double) * cap, (const double*)c->Fplain.p + (size_t)o * c->f_cap * c->f_cap,
-                           sizeof(double) * c->f_cap, sizeof(double) * n, n, hipMemcpyDeviceToDevice, c->stream);
-      if (e == hipSuccess)
-        e = hipMemcpyAsync((double*)a2.p + (size_t)o * cap, (const double*)c->alpha64.p + (size_t)o * c->a_ld, sizeof(double) * n,
-                           hipMemcpyDeviceToDevice, c->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return hip_fail(e, "growing the resident factor");
-    c->Fplain = std::move(F2);
-    c->alpha64 = std::move(a2);
-    c->f_cap = cap;
-    c->a_ld = cap;
-  }
+  if ((rc = factor_reserve(c, 1))) return rc;
   const int cap = c->f_cap;
   AppendWork w;
   if ((rc = carve(c->appendbuf, [&](Carve cv) { return append_layout(cv, n, q, cap, w); }))) return rc;
@@ -1069,6 +1416,78 @@ int model_append_commit(sbo_ctx* c) {
   append_layout(Carve{(unsigned char*)c->appendbuf.p}, n, q, cap, w);
   hipLaunchKernelGGL(k_model_append_commit, dim3(q), dim3(1024), 0, c->stream, n, cap, (double*)c->Fplain.p, (double*)c->alpha64.p,
                      (const double*)w.rho, (const double*)w.scratch, (const double*)w.sk);
+  SBO_HIP(hipGetLastError());
+  c->invk_img_valid = false;                                    // (the images of the caller's invK do not follow an append)
+  c->invk_w_valid = false;
+  return SBO_OK;
+}
+
+// c->appendbuf for a block of k rows (kp = k rounded up to kAppColBlock):
+//   Xall [n + k][d] | rho [q][kp] | B, T, U [q][n][kp] | Z, S, G [q][kp][kp] | g, w [q][kp] | bad [q]
+struct AppendBlockWork {
+  double *Xall, *rho, *B, *T, *U, *Z, *S, *G, *g, *w;
+  int* bad;
+};
+static size_t append_block_layout(Carve cv, int n, int d, int q, int k, int kp, AppendBlockWork& w) {
+  const size_t nk = (size_t)q * n * kp, kk = (size_t)q * kp * kp;
+  cv.take(w.Xall, (size_t)(n + k) * d); cv.take(w.rho, (size_t)q * kp);
+  cv.take(w.B, nk); cv.take(w.T, nk); cv.take(w.U, nk);
+  cv.take(w.Z, kk); cv.take(w.S, kk); cv.take(w.G, kk);
+  cv.take(w.g, (size_t)q * kp); cv.take(w.w, (size_t)q * kp);
+  cv.take(w.bad, q);
+  return cv.off;
+}
+static inline int append_block_kp(int k) { return (k + kAppColBlock - 1) / kAppColBlock * kAppColBlock; }
+
+// The block update of rows n .. n + k - 1 computed into c->appendbuf: Xall holds the observations of the model followed by the k new
+// rows (normalised, fp64), rho [q][k] = y_norm_new - mp.  One host wait, for the verdict: SBO_E_INVALID when a Schur pivot of some
+// output is not > 0.  Nothing of the model changes (growing the factor's capacity copies it and keeps its values);
+// model_append_block_commit then writes the update.
+int model_append_block_check(sbo_ctx* c, int k, const std::vector<double>& Xall, const std::vector<double>& rho) {
+  const ModelConst& mc = c->mc;
+  const int n = mc.n, d = mc.d, q = mc.q, kp = append_block_kp(k);
+  int rc;
+  if ((rc = factor_reserve(c, k))) return rc;
+  const int cap = c->f_cap;
+  AppendBlockWork w;
+  if ((rc = carve(c->appendbuf, [&](Carve cv) { return append_block_layout(cv, n, d, q, k, kp, w); }))) return rc;
+  std::vector<double> hrho((size_t)q * kp, 0.0);
+  for (int o = 0; o < q; ++o)
+    for (int r = 0; r < k; ++r) hrho[(size_t)o * kp + r] = rho[(size_t)o * k + r];
+  SBO_HIP(hipMemcpyAsync(w.Xall, Xall.data(), sizeof(double) * (size_t)(n + k) * d, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemcpyAsync(w.rho, hrho.data(), sizeof(double) * (size_t)q * kp, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemsetAsync(w.bad, 0, sizeof(int) * q, c->stream));
+  const double* dF = (const double*)c->Fplain.p;
+  const long long cells = (long long)(n + kp) * kp;
+  with_dpad(mc.dpad, [&](auto D) {
+    hipLaunchKernelGGL((k_append_cross<D()>), dim3((unsigned)std::min<long long>((cells + 255) / 256, 1024), q), dim3(256), 0, c->stream, mc, n, k,
+                       kp, (const double*)w.Xall, w.B, w.Z);
+  });
+  hipLaunchKernelGGL(k_append_t, dim3((unsigned)((n + kAppWaves * kAppRows - 1) / (kAppWaves * kAppRows)), q), dim3(64 * kAppWaves), 0, c->stream,
+                     n, cap, kp, dF, (const double*)w.B, w.T);
+  hipLaunchKernelGGL(k_append_u, dim3((unsigned)((n + 63) / 64), (unsigned)(kp / kAppColBlock), q), dim3(64), 0, c->stream, n, cap, kp, dF,
+                     (const double*)w.T, w.U);
+  hipLaunchKernelGGL(k_append_s, dim3((unsigned)(kp / kAppSRows + 1), q), dim3(64), 0, c->stream, n, c->a_ld, kp, (const double*)w.B,
+                     (const double*)w.U, (const double*)w.Z, (const double*)c->alpha64.p, w.S, w.g);
+  hipLaunchKernelGGL(k_append_chol, dim3(q), dim3(256), 0, c->stream, k, kp, (const double*)w.S, (const double*)w.g, (const double*)w.rho, w.G,
+                     w.w, w.bad);
+  SBO_HIP(hipGetLastError());
+  std::vector<int> hbad(q, 0);
+  SBO_HIP(hipMemcpyAsync(hbad.data(), w.bad, sizeof(int) * q, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipStreamSynchronize(c->stream));
+  for (int o = 0; o < q; ++o)
+    if (hbad[o])
+      return fail(SBO_E_INVALID, "appended block makes K singular: output " + std::to_string(o) + ", row " + std::to_string(hbad[o] - 1) +
+                                     " of the block has a Schur pivot that is not > 0 (duplicate point without noise?)");
+  return SBO_OK;
+}
+int model_append_block_commit(sbo_ctx* c, int k) {
+  const ModelConst& mc = c->mc;
+  const int n = mc.n, q = mc.q, cap = c->f_cap, kp = append_block_kp(k);
+  AppendBlockWork w;                                             // (as model_append_block_check laid it out)
+  append_block_layout(Carve{(unsigned char*)c->appendbuf.p}, n, mc.d, q, k, kp, w);
+  hipLaunchKernelGGL(k_append_commit, dim3((unsigned)((cap + 63) / 64), q), dim3(64), 0, c->stream, n, cap, c->a_ld, k, kp, (double*)c->Fplain.p,
+                     (double*)c->alpha64.p, (const double*)w.U, (const double*)w.G, (const double*)w.w);
   SBO_HIP(hipGetLastError());
   c->invk_img_valid = false;                                    // (the images of the caller's invK do not follow an append)
   c->invk_w_valid = false;

@@ -196,6 +196,25 @@ class SweepEngine:
         self.n += 1
         self._obs = (np.vstack([self._obs[0], x]),) + self._obs[1:]
 
+    def append_samples(self, X_norm_new, Y_norm_new):
+        """k observations in one block update (``sbo_model_append_batch``): ``X_norm_new`` [k, d] and
+        ``Y_norm_new`` [k, q], normalised with the constants of the last ``set_model``, enter in row order; the resident model is
+        the one k calls of ``append_sample`` would leave, with one verdict wait, one re-pack and one plan invalidation.  All or
+        nothing: a refused block (``ValueError``: a non-finite value, a Schur pivot that is not positive; ``SafeBOError`` with
+        ``SBO_E_UNSUPPORTED``: n + k > ``SBO_MAX_N``) leaves the model as it was.  1 <= k <= ``SBO_MAX_APPEND``."""
+        X = _f64(X_norm_new)
+        Y = _f64(Y_norm_new)
+        if X.ndim != 2 or Y.ndim != 2 or X.shape[1] != self.d or Y.shape[1] != self.q or X.shape[0] != Y.shape[0]:
+            raise ValueError("X_norm_new must be [k, d] and Y_norm_new [k, q]")
+        k = X.shape[0]
+        if not 1 <= k <= L.SBO_MAX_APPEND:
+            raise ValueError(f"k = {k} out of range [1, SBO_MAX_APPEND = {L.SBO_MAX_APPEND}]")
+        if not (np.all(np.isfinite(X)) and np.all(np.isfinite(Y))):
+            raise ValueError("X_norm_new and Y_norm_new must be finite")
+        L.check(self._lib.sbo_model_append_batch(self._ctx, k, _ptr(X), _ptr(Y)))
+        self.n += k
+        self._obs = (np.vstack([self._obs[0], X]),) + self._obs[1:]
+
     def remove_sample(self, index: int):
         """The counterpart of ``append_sample`` (``sbo_model_remove``): observation ``index`` (0-based, in the order of ``X_norm``
         as set and appended) leaves the resident model under the same frozen constants, O(n^2) on the device; the rows behind
