@@ -731,7 +731,8 @@ int sbo_profile_get(sbo_ctx* ctx, sbo_profile* out);
  *   "comm_selftest"    1: a one-rank communicator still sends C1 / C2 / C3 through RCCL (results must not change)
  *   "fp64_recheck"     1: fp32 models re-evaluate in fp64 every candidate that the band of their posterior cannot decide -- measured per (model,
  *                      candidate set) by the fp64 twin at 256 probe candidates, never under 1e-4 normalised (sbo_profile.fp32_band_dm / _dv);
- *                      0: masks of the fp32 posterior
+ *                      0: masks of the fp32 posterior.  Read by sbo_model_set, which builds the twin: a change takes effect at the next one.  A
+ *                      twin is its model's alone (it follows that model's appends and removals); once another model is set it takes no part
  *   "guard_audit"      samples per audited sweep of the standing audit of the guard band (sbo_profile.guard_audit_*; default 1024); 0: off
  *   "guard_audit_scale_ppm" test hook: the audit compares against the band x value / 1e6 (default 1000000); setting it clears the counts
  *   "guard_audit_every" one sweep in this many carries an audit (default 16; the first sweep after setting it does).  An audit shares

@@ -127,7 +127,10 @@ def cast_dataset(ds, dtype):
 
 
 def mean_prior(ds):
-    """models/GP_Safe.py:331-332 -- pessimistic constraint prior, zero for the objective."""
+    """models/GP_Safe.py:331-332 -- pessimistic constraint prior, zero for the objective.  A dataset may carry the caller's prior
+    of ``set_model(..., mean_prior=)`` under the key "mean_prior" ([q], normalised units), which then stands in its place."""
+    if ds.get("mean_prior") is not None:
+        return np.array(ds["mean_prior"], dtype=np.asarray(ds["Y_mean"]).dtype, copy=True)
     mp = (-2 * ds["Y_mean"]) / ds["Y_std"]
     mp = np.array(mp, copy=True)
     mp[0] = 0.0

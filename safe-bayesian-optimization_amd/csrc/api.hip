@@ -402,6 +402,7 @@ static int model_set_impl(sbo_ctx* c, int dtype, const char* kernel, int n, int 
     ++s->model_serial;
     if ((rc = model_build(s, invK, X_norm, Y_norm))) return rc;
     s->has_model = true;
+    c->recheck.serial = c->model_serial;
   }
   c->has_model = true;
   return SBO_OK;
@@ -532,7 +533,10 @@ int sbo_model_append(sbo_ctx* c, const double* x_norm_new, const double* y_norm_
   // every output's update is computed and checked before anything is written: a refused append leaves the model as it was
   int rc = model_append_check(c, kvec, kappa, rho);
   if (rc) return rc;
-  if (c->recheck.shadow && c->recheck.shadow->has_model && (rc = sbo_model_append(c->recheck.shadow, x_norm_new, y_norm_new))) return rc;
+  // (the fp64 twin of this model makes the same call and must accept first; a twin left behind by an earlier model takes no part)
+  const bool twin = twin_current(c);
+  if (twin && (rc = sbo_model_append(c->recheck.shadow, x_norm_new, y_norm_new))) return rc;
+  if (twin) c->recheck.serial = Recheck::kNoSerial;     // (ahead of its owner until the owner's update is complete)
   if ((rc = model_append_commit(c))) return rc;
   // the derived arrays with the new row (device), then the re-pack of the factor images
   c->h_Xnorm.insert(c->h_Xnorm.end(), x_norm_new, x_norm_new + d);
@@ -541,6 +545,7 @@ int sbo_model_append(sbo_ctx* c, const double* x_norm_new, const double* y_norm_
   if ((rc = model_prep(c, c->h_Xnorm.data()))) return rc;
   if ((rc = model_repack(c))) return rc;
   ++c->model_serial;
+  if (twin) c->recheck.serial = c->model_serial;
   model_changed(c);
   return SBO_OK;
 }
@@ -570,11 +575,10 @@ int sbo_model_append_batch(sbo_ctx* c, int k, const double* x_norm_new, const do
   // every output's update is computed and checked before anything is written: a refused block leaves the model as it was
   int rc = model_append_block_check(c, k, Xall, rho);
   if (rc) return rc;
-  // (the fp64 twin of an fp32 model makes the same call and must accept first; a twin left behind by an earlier fp32 model is not
-  // this model's, as in sbo_model_remove)
-  if (c->dtype == SBO_F32 && c->recheck.shadow && c->recheck.shadow->has_model && c->recheck.shadow->mc.n == n &&
-      (rc = sbo_model_append_batch(c->recheck.shadow, k, x_norm_new, y_norm_new)))
-    return rc;
+  // (the fp64 twin of this model makes the same call and must accept first; a twin left behind by an earlier model takes no part)
+  const bool twin = twin_current(c);
+  if (twin && (rc = sbo_model_append_batch(c->recheck.shadow, k, x_norm_new, y_norm_new))) return rc;
+  if (twin) c->recheck.serial = Recheck::kNoSerial;
   if ((rc = model_append_block_commit(c, k))) return rc;
   // the derived arrays with the new rows (device), then one re-pack of the factor images
   c->h_Xnorm = std::move(Xall);
@@ -583,6 +587,7 @@ int sbo_model_append_batch(sbo_ctx* c, int k, const double* x_norm_new, const do
   if ((rc = model_prep(c, c->h_Xnorm.data()))) return rc;
   if ((rc = model_repack(c))) return rc;
   ++c->model_serial;
+  if (twin) c->recheck.serial = c->model_serial;
   model_changed(c);
   return SBO_OK;
 }
@@ -600,10 +605,10 @@ int sbo_model_remove(sbo_ctx* c, int index) {
   SBO_HIP(hipSetDevice(c->device));
   { const int rcf = factor_sync(c); if (rcf) return rcf; }     // (the update works on the resident factor)
   int rc;
-  // (the fp64 twin of an fp32 model follows; a twin left behind by an earlier fp32 model is not this model's)
-  if (c->dtype == SBO_F32 && c->recheck.shadow && c->recheck.shadow->has_model && c->recheck.shadow->mc.n == n &&
-      (rc = sbo_model_remove(c->recheck.shadow, index)))
-    return rc;
+  // (the fp64 twin of this model follows; a twin left behind by an earlier model takes no part)
+  const bool twin = twin_current(c);
+  if (twin && (rc = sbo_model_remove(c->recheck.shadow, index))) return rc;
+  if (twin) c->recheck.serial = Recheck::kNoSerial;
   if ((rc = model_remove(c, index))) return rc;
   // the derived arrays without the row (device), then the re-pack of the factor images
   c->h_Xnorm.erase(c->h_Xnorm.begin() + (size_t)index * d, c->h_Xnorm.begin() + (size_t)(index + 1) * d);
@@ -612,6 +617,7 @@ int sbo_model_remove(sbo_ctx* c, int index) {
   if ((rc = model_prep(c, c->h_Xnorm.data()))) return rc;
   if ((rc = model_repack(c))) return rc;
   ++c->model_serial;
+  if (twin) c->recheck.serial = c->model_serial;
   model_changed(c);
   return SBO_OK;
 }

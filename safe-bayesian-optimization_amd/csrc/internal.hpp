@@ -386,6 +386,10 @@ struct MultiRank {
 // cannot decide (option fp64_recheck); it borrows its owner's streams, events and h_back and holds explicit lists only
 struct Recheck {
   sbo_ctx* shadow = nullptr;
+  // the owner's model_serial the twin holds the model of (twin_current below): written when sbo_model_set builds the twin, advanced when
+  // the twin has followed an accepted append, block append or removal; kNoSerial while it is ahead of its owner, inside such a call
+  static constexpr unsigned long long kNoSerial = ~0ull;
+  unsigned long long serial = kNoSerial;
   DevBuf mean, var;         // double [q][n_local]: the fp32 posterior widened, flagged entries replaced by fp64 values (what the recheck's set phases read)
   DevBuf list;              // RcHead, then the flagged candidate indices (long long)
   DevBuf refined;           // uint8 [n_local]: this candidate's entries of mean / var are fp64 values
@@ -599,6 +603,12 @@ inline sbo::Recheck::~Recheck() { delete shadow; }
 namespace sbo {
 // the sweeps take their multi-rank path (pack, collective, unpack, host merge): more than one rank, or the self-test
 inline bool multi_rank(const sbo_ctx* c) { return c->dist.world > 1 || c->opt.comm_selftest; }
+// the fp64 twin is the resident model's: an fp32 model, a twin with a model, built for (or brought along to) this model_serial.  A twin
+// left behind by an earlier model -- an fp64 model set since, or an fp32 one under fp64_recheck = 0 -- takes part in nothing: no sweep
+// rechecks against it, no append or removal reaches it
+inline bool twin_current(const sbo_ctx* c) {
+  return c->dtype == SBO_F32 && c->recheck.shadow && c->recheck.shadow->has_model && c->recheck.serial == c->model_serial;
+}
 inline ScalBlock* scal_block(const sbo_ctx* c) { return (ScalBlock*)c->lane[0].scal.p; }
 // the guard band of the resident posterior of an fp64 model (device_common.hpp: GuardBand), when an approximating kernel (K1b / K1i / K1t)
 // wrote it and option guard_band is on; nullptr: the values are the exact kernels'

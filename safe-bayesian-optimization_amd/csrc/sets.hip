@@ -2711,7 +2711,7 @@ static int sweep_args(sbo_ctx* c, const sbo_sweep_opts* opts, const void* result
   SBO_HIP(hipSetDevice(c->device));
   return SBO_OK;
 }
-// fp32 models with an fp64 twin: the recheck; every other: the plain sweep in the model's precision (`plain` / `recheck` take a
+// fp32 models whose fp64 twin is current (twin_current): the recheck; every other: the plain sweep in the model's precision (`plain` / `recheck` take a
 // float or a double to say which), and behind an approximating fp64 posterior (K1b / K1i / K1t) whose band left decisions of that
 // pass open, the guard recheck: re-evaluate exactly, decide again
 template <typename Res, typename Plain, typename Recheck>
@@ -2720,7 +2720,7 @@ static int sweep_dispatch(sbo_ctx* c, Res* result, bool drain, Plain plain, Rech
   const bool f64 = c->dtype == SBO_F64;
   c->gb.first = 0;
   int rc;
-  if (!f64 && c->opt.fp64_recheck && c->recheck.shadow && c->recheck.shadow->has_model) rc = recheck(0.0f);
+  if (twin_current(c)) rc = recheck(0.0f);
   else rc = f64 ? plain(0.0) : plain(0.0f);
   if (done(rc) && f64 && resident_band(c) && (c->gb.first > 0 || c->opt.guard_band == 2)) {
     const long long first = c->gb.first;

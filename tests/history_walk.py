@@ -5,11 +5,27 @@ The claim under test: whatever the engine did before, a sweep returns what a fre
 options.  A walk is a list of plain tuples (replayable from the seed alone, printed whole on a failure); the driver runs it on an
 engine and checks every step against NumPy references of the current state: the dataset (appends rebuilt with frozen normalisation,
 as tests/test_gpu_append.py::_extend does), the candidate set and the sweep's arguments.  Importing this module opens no GPU.
+
+Seeds 0 .. 7 are the walks of the first version, step for step (tests/test_history_walk_cpu.py pins their digests): set_model, single
+appends, the four sweeps, options and three reads.  Seeds 8 .. 15 add what has joined the ABI since: removals, block appends, the
+on-device fit and a caller's prior (model-changing steps, each under a resident K1i, K1b or K1g plan and followed by two sweeps), and
+the read-only calls -- model_loo, mean_grad, lipschitz, batch_select, the three refines, the likelihood kernels -- each checked
+against the oracle its own suite uses and followed by a sweep on ``posterior_ready``.  A new step never returns early: the generator
+establishes its precondition and the driver raises when it is missing.  ``Walk(None, ...)`` is the dry mode: no engine, references
+only, and per sweep the smallest margin of any decision (``Walk.margins``).
 """
 import numpy as np
 
+import batch_oracle
+import de_twin
+import model_append_batch as mb
+import model_loo
+import model_remove as mr
+import nll_grad_oracle
 import oracle
+import refine_sets_oracle as rso
 import robust_oracle
+import robust_refine_oracle
 from safebo_amd import synthetic
 
 # problems: (config, n) -- B and H (q = 2, Benoit), C (q = 3, the Williams-Otto shape), A (small n)
@@ -20,15 +36,29 @@ GRIDS = {"t128x64": [128, 64], "t256x64": [256, 64], "r130x70": [130, 70], "r96x
 SMALLER = {"t256x64": "r130x70", "r130x70": "r96x50", "t128x64": "r96x50", "r96x50": "r96x50"}
 LARGER = {"r96x50": "t256x64", "r130x70": "t256x64", "t128x64": "t256x64", "t256x64": "t256x64"}
 LISTS = {"l1000": 1000, "l2000": 2000}
-ALL_GRIDS = dict(GRIDS, t256x128=[256, 128])      # (+ the directed tests' grid)
+# a grid over a small box inside the safe set (_inside_box): every control is robust-safe there, so a robust sweep has a winner for
+# refine_robust to start from -- on the whole domain of these problems no control is safe against every disturbance
+INSIDE = {"i128x64": [128, 64]}
+ALL_GRIDS = dict(GRIDS, t256x128=[256, 128], **INSIDE)      # (+ the directed tests' grid)
 # option whitelist (value sets) and the defaults a walk restores
-OPTIONS = {"bilinear": (0, 1, 2), "col_path": (0, 1, 2), "fuse_classify": (-1, 0, 1), "posterior_path": (0, 1, 2), "k1_sched": (0, 1),
+OPTIONS_V1 = {"bilinear": (0, 1, 2), "col_path": (0, 1, 2), "fuse_classify": (-1, 0, 1), "posterior_path": (0, 1, 2), "k1_sched": (0, 1),
            "guard_band": (1, 2), "list_index": (-1, 0, 1), "exact_lazy": (1, 2), "tensor_cheb": (0, 1)}
-DEFAULTS = {"bilinear": 1, "col_path": 1, "fuse_classify": -1, "posterior_path": 0, "k1_sched": 1, "guard_band": 1, "list_index": -1,
+DEFAULTS_V1 = {"bilinear": 1, "col_path": 1, "fuse_classify": -1, "posterior_path": 0, "k1_sched": 1, "guard_band": 1, "list_index": -1,
             "exact_lazy": 1, "tensor_cheb": 1}
+# (seeds 8 ..: the options that have joined the column path and the set phase since)
+OPTIONS = dict(OPTIONS_V1, k1_skip_safe=(0, 1), col_overlap=(0, 1), set_fuse=(0, 1), set_lanes=(0, 1), grad_defer=(0, 1, 2, 3))
+DEFAULTS = dict(DEFAULTS_V1, k1_skip_safe=1, col_overlap=1, set_fuse=1, set_lanes=1, grad_defer=1)
 READY_KINDS = ("safeopt", "goose", "tr", "robust")
 REFUSALS = ("b_nan", "b_neg", "append_nonfinite", "grid_zero", "mask_g_after_goose", "robust_arrays_after_model")
-SEEDS = tuple(range(8))
+OLD_SEEDS = tuple(range(8))
+NEW_SEEDS = tuple(range(8, 16))
+SEEDS = OLD_SEEDS + NEW_SEEDS
+READ_ONLY = ("loo", "mean_grad", "lipschitz", "batch_select", "refine", "refine_sets", "refine_robust", "nll")
+MODEL_STEPS = ("remove", "append_block", "fit", "set_prior_zero")
+UNDER = ("K1i", "K1b", "K1g")
+RTOL_GRAD = 1e-9            # tests/test_gpu_lipschitz.py: RTOL, per output, of the largest |grad_o| over the step's points
+FIT_BOX = np.array([[-1.0, 0.5], [-1.0, 0.5], [-0.5, 0.5], [-2.5, -1.5]])     # (d = 2: a box of well-conditioned models)
+FIT_P, FIT_MAXITER, FIT_SEED = 8, 4, 77
 WALK_PROBLEMS = ("B", "H", "C", "A", "B", "C", "H", "B")
 SWEEPS = ("safeopt", "goose", "tr", "robust")
 
@@ -43,6 +73,7 @@ class _Gen:
         self.b = float(synthetic.CONFIGS[PROBLEMS[self.problem][0]]["b"])
         self.grid = None
         self.on_list = False
+        self.options = OPTIONS_V1
 
     def emit(self, *step):
         self.steps.append(tuple(step))
@@ -142,8 +173,8 @@ class _Gen:
 
     def seg_options(self):
         for _ in range(2):
-            key = str(self.rng.choice(list(OPTIONS)))
-            self.emit("option", key, int(self.rng.choice(OPTIONS[key])))
+            key = str(self.rng.choice(list(self.options)))
+            self.emit("option", key, int(self.rng.choice(self.options[key])))
             self.sweep()
 
     def seg_reads(self):
@@ -154,8 +185,173 @@ class _Gen:
         self.sweep(ready=True)
 
 
+class _Gen2(_Gen):
+    """Seeds 8 ..: the old segments plus one per step added since."""
+
+    def __init__(self, seed):
+        super().__init__(seed)
+        self.options = OPTIONS
+        self.touched = []
+
+    def emit(self, *step):
+        if step[0] == "option" and step[1] not in self.touched:
+            self.touched.append(step[1])
+        super().emit(*step)
+
+    def under(self, under, robust=False):
+        """A fresh fp64 model with the plan `under` resident (seg_append's way there); `robust`: the last sweep in front of the
+        step is a robust one, whose arrays the step has to drop."""
+        if under == "K1i":
+            self.to_grid("t256x128")
+        elif self.on_list or self.grid == "t256x128":
+            self.to_grid(self.grid if self.grid in GRIDS else "t128x64")
+        self.emit("option", "posterior_path", 0)
+        self.emit("option", "bilinear", 0 if under == "K1g" else 1)
+        self.model()
+        self.sweep("safeopt", ready=False, lean=0)
+        if under == "K1b":
+            self.sweep("safeopt", ready=False)
+        if robust:
+            assert under != "K1i"            # (K1i is the model's first sweep alone)
+            self.sweep("robust", ready=bool(self.rng.integers(2)))
+
+    def after(self, under):
+        self.sweep()
+        self.sweep()
+        if under == "K1g":
+            self.emit("option", "bilinear", 1)
+
+    def seg_remove(self, under, index_kind, robust=False):
+        self.under(under, robust)
+        self.emit("remove", index_kind, under)
+        self.after(under)
+
+    def seg_append_block(self, under, k, robust=False):
+        self.under(under, robust)
+        self.emit("append_block", k, under)
+        self.after(under)
+
+    def seg_fit(self, under, robust=False):
+        self.under(under, robust)
+        self.emit("fit", under)
+        self.after(under)
+
+    def seg_set_prior_zero(self):
+        if self.on_list:
+            self.to_grid()
+        self.model()
+        self.sweep("safeopt", ready=False, lean=0)
+        self.emit("set_prior_zero")
+        self.sweep()
+        self.sweep()
+        self.model()
+        self.sweep("safeopt", ready=False, lean=0)
+
+    def seg_remove_on_list(self):
+        self.emit("option", "list_index", 1)
+        self.on_list = True
+        self.emit("set_points", "l2000")
+        self.model()
+        self.sweep("safeopt", ready=False, lean=0)
+        self.emit("remove", "middle", "list")
+        self.sweep()
+        self.sweep()
+        self.emit("option", "list_index", -1)
+
+    def seg_new_options(self, *settings):
+        """The options added since the first version at the values the drawn ones of seg_options do not reach: each followed by a
+        lean-2 SafeOpt sweep (the column path's) and a random one, and left standing until the walk's end."""
+        if self.on_list or self.grid not in GRIDS:
+            self.to_grid(self.grid if self.grid in GRIDS else "t128x64")
+        for key, val in settings:
+            self.emit("option", key, val)
+            self.sweep("safeopt", ready=False, lean=2)
+            self.sweep()
+
+    def seg_read_only(self, step, kind):
+        """A sweep that leaves the step what it reads, the step, a sweep of `kind` on posterior_ready."""
+        if kind == "robust" and self.on_list:
+            self.to_grid(self.grid if self.grid in GRIDS else "t128x64")
+        if self.grid == "t256x128" and not self.on_list:
+            self.to_grid("r130x70")
+        back = self.grid
+        if step == "refine_robust":
+            self.to_grid("i128x64")
+            self.model()
+            self.sweep("robust", ready=False, b=self.b)
+        else:
+            self.sweep("safeopt" if step == "refine_sets" else str(self.rng.choice(["safeopt", "goose"])), ready=False, b=self.b, lean=0)
+        if step == "batch_select":
+            self.emit(step, 4)
+        else:
+            self.emit(step)
+        self.sweep(kind, ready=True, b=self.b, lean=0)
+        if step == "refine_robust":
+            self.to_grid(back if back in GRIDS else "t128x64")
+
+    def seg_dtype_round(self):
+        """The old round with an append, a block append and a removal while the model is fp32 with its twin, and one single append
+        after the last set_model(f64): the twin left behind is not that model's."""
+        if self.on_list or self.grid == "t256x128":
+            self.to_grid(self.grid if self.grid in GRIDS else "t128x64")
+        three = ["safeopt", "goose", "tr"]
+        self.model("f32")
+        self.sweep(str(self.rng.choice(three)), ready=False)
+        for step in (("append", 1, "f32"), ("append_block", 3, "f32"), ("remove", "middle", "f32")):
+            self.emit(*step)
+            self.sweep(str(self.rng.choice(three)), ready=bool(self.rng.integers(2)))
+        self.model("f64")
+        self.sweep(str(self.rng.choice(three)), ready=False)
+        self.model("f32")
+        self.sweep(str(self.rng.choice(three)), ready=False)
+        self.sweep(str(self.rng.choice(three)), ready=True)
+        self.model("f64")
+        self.emit("append", 1, "f64_after_f32")
+        self.sweep()
+        self.sweep(ready=True)
+
+
+# seeds 8 ..: (model-changing segments, old segments); every seed also gets four read-only segments (make_walk)
+NEW_PLAN = {
+    8: ([("remove", "K1b", "first"), ("append_block", "K1b", 3), ("dtype_round",)], [("b_change",), ("new_options", ("set_fuse", 0))]),
+    9: ([("remove", "K1g", "middle", True), ("append_block", "K1g", 17), ("set_prior_zero",)],
+        [("options",), ("reads",), ("new_options", ("k1_skip_safe", 0), ("set_lanes", 0))]),
+    10: ([("remove", "K1g", "last"), ("append_block", "K1g", 1)],
+         [("shrink_grow",), ("options",), ("refuse", "b_nan"), ("new_options", ("set_lanes", 0), ("set_fuse", 0))]),
+    11: ([("remove", "K1i", "first"), ("append_block", "K1i", 17), ("remove_on_list",)], [("options",), ("new_options", ("grad_defer", 0))]),
+    12: ([("append_block", "K1b", 17, True), ("remove", "K1b", "last"), ("fit", "K1b")],
+         [("list_round",), ("options",), ("new_options", ("k1_skip_safe", 0))]),
+    13: ([("append_block", "K1g", 3), ("set_prior_zero",), ("remove_on_list",)], [("options",), ("b_change",), ("new_options", ("set_lanes", 0))]),
+    14: ([("remove", "K1g", "last"), ("append_block", "K1g", 1), ("remove_on_list",)],
+         [("options",), ("shrink_grow",), ("new_options", ("col_overlap", 0), ("k1_skip_safe", 0))]),
+    15: ([("fit", "K1b", True), ("remove", "K1b", "middle"), ("append_block", "K1b", 1)],
+         [("options",), ("reads",), ("refuse", "mask_g_after_goose"), ("new_options", ("grad_defer", 2), ("set_fuse", 0))]),
+}
+# (every value of the five options that is not its default and the one a new_options segment of some seed sets)
+NEW_OPTION_VALUES = {("set_fuse", 0), ("set_lanes", 0), ("k1_skip_safe", 0), ("col_overlap", 0), ("grad_defer", 0), ("grad_defer", 2)}
+
+
+def _make_walk2(seed):
+    g = _Gen2(seed)
+    g.to_grid(str(g.rng.choice(["t128x64", "r130x70", "r96x50"])))     # (the NumPy references of the larger grids take seconds each)
+    g.model()
+    g.sweep("safeopt", ready=False, lean=0)
+    changing, old = NEW_PLAN[seed]
+    j0 = 4 * (seed - NEW_SEEDS[0])
+    reads = [("read_only", READ_ONLY[(j0 + j) % len(READ_ONLY)], READY_KINDS[(seed + j + (j0 + j) // len(READ_ONLY)) % len(READY_KINDS)]) for j in range(4)]
+    segs = list(changing) + list(old) + reads
+    for i in g.rng.permutation(len(segs)):
+        name, *args = segs[i]
+        getattr(g, "seg_" + name)(*args)
+    for key in g.touched:
+        g.emit("option", key, DEFAULTS[key])
+    return g.steps
+
+
 def make_walk(seed):
     """The step list of walk ``seed`` (deterministic: the seed is all a replay needs)."""
+    if seed >= NEW_SEEDS[0]:
+        return _make_walk2(seed)
     g = _Gen(seed)
     g.to_grid(str(g.rng.choice(list(GRIDS))))
     g.model()
@@ -169,7 +365,7 @@ def make_walk(seed):
     for i in g.rng.permutation(len(segs)):
         name, *args = segs[i]
         getattr(g, "seg_" + name)(*args)
-    for key, val in DEFAULTS.items():
+    for key, val in DEFAULTS_V1.items():
         g.emit("option", key, val)
     return g.steps
 
@@ -184,8 +380,14 @@ def transitions(steps):
     dtypes = []
     cands = []
     grid = None
+    pending = None               # a read-only step waiting for its posterior_ready sweep
     for i, s in enumerate(steps):
         kind = s[0]
+        if pending is not None:
+            ready = kind in SWEEPS and (s[2] if kind == "goose" else s[3])
+            assert ready, (i, s, "a read-only step is followed by a sweep on posterior_ready")
+            out.add(f"{pending}->{kind}_ready")
+            pending = None
         if kind in SWEEPS:
             ready = s[2] if kind == "goose" else s[3]
             if ready and last_sweep is not None and last_sweep[0] == "safeopt":
@@ -200,6 +402,34 @@ def transitions(steps):
             model_sweeps = 0
             last_sweep = None
             dtypes.append(s[2])
+        elif kind in READ_ONLY:
+            assert dtypes[-1] == "f64" and model_sweeps >= 1, (i, s)
+            assert kind != "refine_robust" or (last_sweep[0] == "robust" and not on_list), (i, s)
+            assert kind != "refine_sets" or last_sweep[0] == "safeopt", (i, s)
+            pending = kind
+        elif kind in MODEL_STEPS or (kind == "append" and s[2] not in UNDER):
+            under = s[-1] if kind != "set_prior_zero" else None
+            if last_sweep is not None and last_sweep[0] in ("safeopt", "goose"):
+                out.add("mask_refused_after_model_change")
+            if last_sweep is not None and last_sweep[0] == "robust":
+                out.add("robust_arrays_refused_after_" + kind)
+            if under in UNDER:
+                out.add(f"{kind}_under_{under}")
+                expect = "K1g" if opts["bilinear"] == 0 else ("K1i" if model_sweeps == 1 else "K1b")
+                assert not on_list and expect == under and dtypes[-1] == "f64", (i, s, model_sweeps, opts["bilinear"])
+            elif under == "list":
+                assert kind == "remove" and on_list and opts["list_index"] == 1, (i, s)
+                out.add("remove_on_list")
+            elif under == "f32":
+                assert dtypes[-1] == "f32", (i, s)
+                out.add("f32_" + kind)
+            elif under == "f64_after_f32":
+                assert kind == "append" and dtypes[-2:] == ["f32", "f64"] and model_sweeps == 0, (i, s)
+                out.add("append_after_f32_then_f64")
+            else:
+                assert kind == "set_prior_zero", (i, s)
+                model_sweeps = 0
+            last_sweep = None
         elif kind == "append":
             out.add("append_under_" + s[2])
             # (the generator's label agrees with the state it left: K1i after one sweep, K1b after two, K1g with bilinear 0)
@@ -207,6 +437,8 @@ def transitions(steps):
             assert not on_list and expect == s[2], (i, s, model_sweeps, opts["bilinear"])
         elif kind == "option":
             opts[s[1]] = s[2]
+            if (s[1], s[2]) in NEW_OPTION_VALUES:
+                out.add(f"option_{s[1]}_{s[2]}")
         elif kind == "set_grid":
             if grid is not None and not on_list:
                 a, b = np.prod(ALL_GRIDS[grid]), np.prod(ALL_GRIDS[s[1]])
@@ -223,12 +455,28 @@ def transitions(steps):
         out.add("list->grid->list")
     if any(dtypes[j:j + 3] == ["f32", "f64", "f32"] for j in range(len(dtypes))):
         out.add("f32->f64->f32")
+    assert pending is None, "a walk does not end on a read-only step"
     return out
 
 
 REQUIRED = ({f"lean{lv}->{k}_ready" for lv in (0, 1, 2) for k in READY_KINDS} |
             {"append_under_K1i", "append_under_K1b", "append_under_K1g", "refused->sweep", "grid_shrink", "grid_grow",
-             "list->grid->list", "f32->f64->f32", "b_change_between_ready"})
+             "list->grid->list", "f32->f64->f32", "b_change_between_ready"} |
+            {f"{k}_under_{u}" for k in ("remove", "append_block") for u in UNDER} |
+            {"fit_under_K1b", "remove_on_list", "f32_append", "f32_append_block", "f32_remove", "append_after_f32_then_f64",
+             "mask_refused_after_model_change", "robust_arrays_refused_after_remove", "robust_arrays_refused_after_append_block",
+             "robust_arrays_refused_after_fit"} |
+            {f"option_{k}_{v}" for k, v in NEW_OPTION_VALUES})
+
+
+def read_only_followers(seen):
+    """{read-only step: sweep kinds found behind it on posterior_ready} of a set of transition names."""
+    out = {k: set() for k in READ_ONLY}
+    for name in seen:
+        head, _, tail = name.partition("->")
+        if head in out and tail.endswith("_ready"):
+            out[head].add(tail[:-len("_ready")])
+    return out
 
 
 # ---- the driver (GPU) ------------------------------------------------------------------------------------------------------------
@@ -245,12 +493,31 @@ def _list_points(problem, name):
     return rng.uniform(bound[:, 0], bound[:, 1], size=(LISTS[name], bound.shape[0]))
 
 
+_INSIDE = {}
+
+
+def _inside_box(problem):
+    """(lo, hi): 2 % of the problem's domain around the coarse-grid candidate whose smallest constraint lcb is largest (the way of
+    tests/skip_safe_cases.py: grid)."""
+    if problem not in _INSIDE:
+        cfg = _problem(problem)
+        lo, hi = cfg["bound"][:, 0], cfg["bound"][:, 1]
+        coarse = oracle.grid_points(lo, hi, [64, 64])
+        mean, var = oracle.gp_inference(coarse, cfg["ds"])
+        lcb = (mean - float(cfg["b"]) * np.sqrt(var))[:, 1:].min(axis=1)
+        c, w = coarse[int(np.argmax(lcb))], 0.01 * (hi - lo)
+        _INSIDE[problem] = (np.maximum(lo, c - w), np.minimum(hi, c + w))
+    return _INSIDE[problem]
+
+
 def _nerr(got, ref, ystd, power):
     return float(np.max(np.abs(np.asarray(got, dtype=np.float64) - ref) / np.maximum(1.0, ystd) ** power)) if np.size(ref) else 0.0
 
 
 class Walk:
-    """Runs a step list on ``eng`` and checks every step.  ``record`` collects (step index, posterior_kernel, set_path)."""
+    """Runs a step list on ``eng`` and checks every step.  ``record`` collects (step index, posterior_kernel, set_path).  With
+    ``eng`` None (the dry mode) nothing runs: the references are computed and ``margins`` collects, per sweep, (step index, kind, the
+    smallest normalised distance of any S / U / M / G / O / T decision of the oracle from its threshold: _margin)."""
 
     def __init__(self, eng, seed, steps, problem=None):
         self.eng, self.seed, self.steps = eng, seed, steps
@@ -262,12 +529,21 @@ class Walk:
         self.cand = None
         self.pts = None
         self.last = None           # (kind, oracle result) of the last sweep that left masks
-        self.robust_ok = False
         self.cache = {}
         self.rng = np.random.default_rng(5000 + seed)
         self.walk_problem = problem or WALK_PROBLEMS[seed % len(WALK_PROBLEMS)]
         self.bound = _problem(self.walk_problem)["bound"]
+        self.box = (self.bound[:, 0], self.bound[:, 1])     # of the resident candidates: the domain, or an INSIDE grid's small box
         self.append_kernels = set()     # posterior kernel of the sweep before each append
+        self.remove_kernels, self.block_kernels = set(), set()      # ... before each removal / block append on a grid
+        self.dry = eng is None
+        self.robust_refusals = 0        # model-changing steps behind a robust sweep: robust_arrays() was asserted refused
+        self.margins = []
+        self.index = 0
+        self.masks = None               # what the engine's masks held behind the last sweep: {(name, c): array}
+        self.rob_kept = None              # robust_arrays() behind the last robust sweep
+        self.winner = None              # the last sweep's winner x [d], the seed of the refine steps
+        self.last_sweep = None          # the last sweep's step
 
     # references, cached on (dataset, candidates, arguments)
     def _ref(self, kind, *args):
@@ -290,6 +566,7 @@ class Walk:
 
     def run(self, start=0):
         for i, step in enumerate(self.steps[start:], start):
+            self.index = i
             try:
                 self.step(step)
             except Exception as e:                                 # noqa: BLE001
@@ -297,52 +574,166 @@ class Walk:
                 raise AssertionError(f"history walk seed {self.seed}, step {i}: {step!r}\n"
                                      f"replay: history_walk.make_walk({self.seed})[:{i + 1}] =\n{listing}\n"
                                      f"{type(e).__name__}: {e}") from e
-            prof = self.eng.profile()
-            self.record.append((i, step[0], int(prof["posterior_kernel"]), int(prof["set_path"])))
+            if not self.dry:
+                prof = self.eng.profile()
+                self.record.append((i, step[0], int(prof["posterior_kernel"]), int(prof["set_path"])))
         return self.record
+
+    def _changed(self):
+        """A candidate or model change: nothing the last sweep left is readable any more."""
+        self.last, self.masks, self.rob_kept, self.winner, self.last_sweep = None, None, None, None, None
+
+    def _model_changed(self):
+        """Behind a model-changing step: the masks are refused, and so are the robust arrays of an earlier robust sweep."""
+        if not self.dry:
+            self._raises(lambda: self.eng.mask("S"))
+            if self.rob_kept is not None:
+                self._raises(lambda: self.eng.robust_arrays())
+                self.robust_refusals += 1
+        self.ds_ver += 1
+        self._changed()
+
+    def _unchanged(self):
+        """Behind a read-only step: the masks of the last sweep are still readable, byte for byte; so are the robust arrays."""
+        if self.dry:
+            return
+        if self.masks is None and self.rob_kept is None:
+            raise RuntimeError("a read-only step stands behind a sweep that left masks or robust arrays")
+        for (k, c), m in (self.masks or {}).items():
+            assert np.array_equal(self.eng.mask(k, c), m), ("mask changed by a read-only call", k, c)
+        if self.rob_kept is not None:
+            f, g = self.eng.robust_arrays()
+            assert f.tobytes() == self.rob_kept[0].tobytes() and g.tobytes() == self.rob_kept[1].tobytes(), "robust arrays changed"
+
+    def _keep_masks(self, names):
+        self.masks = None if self.dry else {(k, c): self.eng.mask(k, c) for k, c in names}
+        self.rob_kept = None
+
+    def _reach_margin(self, ref, over_safe):
+        """Smallest |max over the other set of (ucb_c(g) - L_c ||x_g - x_h + 1e-8||)| / max(1, Y_std[c]): the distance of a G_c decision
+        (per g in S, the best h in U) or of an O_c decision (per h in U, the best g in S) from its threshold."""
+        gi, hi = np.nonzero(ref["S"])[0], np.nonzero(ref["U"])[0]
+        if gi.size == 0 or hi.size == 0:
+            return np.inf
+        ys, m = np.maximum(1.0, self.ds["Y_std"]), np.inf
+        rows, cols = (gi, hi) if over_safe else (hi, gi)
+        for s in range(0, rows.size, 1024):
+            idx = rows[s:s + 1024]
+            g, h = (idx[:, None], cols[None, :]) if over_safe else (cols[None, :], idx[:, None])
+            dist = oracle.shifted_norm(self.pts[g], self.pts[h])
+            for c in range(1, ref["ucb"].shape[1]):
+                best = np.max(ref["ucb"][g, c] - ref["L_used"][c] * dist, axis=1)
+                m = min(m, float(np.min(np.abs(best))) / ys[c])
+        return m
+
+    def _margin(self, kind, ref, x0=None, r=None):
+        """Dry mode: the smallest normalised distance of any decision of the oracle's sweep from its threshold -- S / U (|lcb_c|), M
+        (|lcb_0 - u*| over S), G_c / O_c (_reach_margin), and for the trust region T (| ||x - x_0|| - r | over S, relative to r)."""
+        if not self.dry:
+            return
+        ys = np.maximum(1.0, self.ds["Y_std"])
+        m = float(np.min(np.abs(ref["lcb"][:, 1:]) / ys[1:]))
+        if kind == "tr":
+            if ref["S"].any():
+                m = min(m, float(np.min(np.abs(np.sqrt(np.sum((self.pts[ref["S"]] - x0) ** 2, axis=1)) - r))) / r)
+        elif not ref["empty_safe_set"]:
+            if kind == "safeopt":
+                m = min(m, float(np.min(np.abs(ref["lcb"][ref["S"], 0] - ref["u_star"])) / ys[0]))
+            m = min(m, self._reach_margin(ref, kind == "safeopt"))
+        self.margins.append((self.index, kind, float(m)))
+
+    def _plant_rows(self, k):
+        bound = _problem(self.problem)["bound"]
+        x = self.rng.uniform(bound[:, 0], bound[:, 1], size=(k, bound.shape[0]))
+        y = (synthetic.williams_otto if self.problem == "C" else synthetic.benoit)(x)
+        return (x - self.ds["X_mean"]) / self.ds["X_std"], (y - self.ds["Y_mean"]) / self.ds["Y_std"]
+
+    def _kernel(self, under, into):
+        if not self.dry and under in UNDER:
+            into.add(int(self.eng.profile()["posterior_kernel"]))
 
     def step(self, s):
         eng, kind = self.eng, s[0]
         if kind == "set_grid":
-            bound = self.bound
-            eng.set_grid(bound[:, 0], bound[:, 1], ALL_GRIDS[s[1]])
+            self.box = _inside_box(self.walk_problem) if s[1] in INSIDE else (self.bound[:, 0], self.bound[:, 1])
+            if not self.dry:
+                eng.set_grid(self.box[0], self.box[1], ALL_GRIDS[s[1]])
             self.cand = ("grid", s[1])
-            self.pts = oracle.grid_points(bound[:, 0], bound[:, 1], ALL_GRIDS[s[1]])
-            self.last, self.robust_ok = None, False
+            self.pts = oracle.grid_points(self.box[0], self.box[1], ALL_GRIDS[s[1]])
+            self._changed()
         elif kind == "set_points":
             pts = _list_points(self.walk_problem, s[1])
-            eng.set_points(pts)
+            if not self.dry:
+                eng.set_points(pts)
             self.cand = ("list", s[1])
             self.pts = pts
-            self.last, self.robust_ok = None, False
+            self.box = (self.bound[:, 0], self.bound[:, 1])
+            self._changed()
         elif kind == "set_model":
             self.problem, self.dtype = s[1], s[2]
             cfg = _problem(s[1])
             self.ds = {k: (list(v) if k == "invKopt" else np.array(v)) for k, v in cfg["ds"].items()}
             self.ds_ver += 1
-            eng.set_model(self.ds, dtype=s[2], use_invK=s[2] == "f64")
-            self.last, self.robust_ok = None, False
+            if not self.dry:
+                eng.set_model(self.ds, dtype=s[2], use_invK=s[2] == "f64")
+            self._changed()
         elif kind == "append":
             n_new = s[1]
-            self.append_kernels.add(int(eng.profile()["posterior_kernel"]))
+            if not self.dry and s[2] in UNDER:
+                self.append_kernels.add(int(eng.profile()["posterior_kernel"]))
             bound = _problem(self.problem)["bound"]
             for _ in range(n_new):
                 x = self.rng.uniform(bound[:, 0], bound[:, 1])
                 y = (synthetic.williams_otto if self.problem == "C" else synthetic.benoit)(x[None])[0]
                 xn = (x - self.ds["X_mean"]) / self.ds["X_std"]
                 yn = (y - self.ds["Y_mean"]) / self.ds["Y_std"]
-                eng.append_sample(xn, yn)
+                if not self.dry:
+                    eng.append_sample(xn, yn)
                 out = dict(self.ds)
                 out["X_norm"] = np.vstack([self.ds["X_norm"], xn[None]])
                 out["Y_norm"] = np.vstack([self.ds["Y_norm"], yn[None]])
                 out["invKopt"] = oracle.build_invK(out["X_norm"], self.ds["hypopt"])
                 self.ds = out
                 self.ds_ver += 1
-            self.last, self.robust_ok = None, False
+            if s[2] in UNDER:
+                self._changed()
+            else:
+                self._model_changed()
+        elif kind == "remove":
+            n = self.ds["X_norm"].shape[0]
+            if n <= 8:
+                raise RuntimeError("a walk never takes a model below 8 rows")
+            j = {"first": 0, "middle": n // 2, "last": n - 1}[s[1]]
+            self._kernel(s[2], self.remove_kernels)
+            if not self.dry:
+                eng.remove_sample(j)
+            self.ds = mr.without(self.ds, j)
+            self._model_changed()
+        elif kind == "append_block":
+            xn, yn = self._plant_rows(s[1])
+            self._kernel(s[2], self.block_kernels)
+            if not self.dry:
+                eng.append_samples(xn, yn)
+            self.ds = mb.extended(self.ds, xn, yn)
+            self._model_changed()
+        elif kind == "fit":
+            self.fit()
+        elif kind == "set_prior_zero":
+            self.ds = dict(self.ds, mean_prior=np.zeros(self.ds["Y_norm"].shape[1]))
+            if not self.dry:
+                eng.set_model(self.ds, dtype="f64", use_invK=True, mean_prior=self.ds["mean_prior"])
+            self._model_changed()
+        elif kind in READ_ONLY:
+            if self.dtype != "f64" or self.last_sweep is None:
+                raise RuntimeError(f"{kind}: needs an fp64 model and a sweep before it")
+            getattr(self, "ro_" + kind)(*s[1:])
+            self._unchanged()
         elif kind == "option":
-            eng.set_option(s[1], s[2])
+            if not self.dry:
+                eng.set_option(s[1], s[2])
         elif kind == "refuse":
-            self.refuse(s[1])
+            if not self.dry:
+                self.refuse(s[1])
         elif kind == "safeopt":
             self.safeopt(*s[1:])
         elif kind == "goose":
@@ -352,14 +743,16 @@ class Walk:
         elif kind == "robust":
             self.robust(*s[1:])
         elif kind == "posterior":
-            self.check_posterior()
+            if not self.dry:
+                self.check_posterior()
         elif kind == "posterior_run":
-            eng.posterior_run()
-            self.check_posterior()
+            if not self.dry:
+                eng.posterior_run()
+                self.check_posterior()
         elif kind == "explore":
             lo, hi = self.pts.min(axis=0), self.pts.max(axis=0)
             t = lo + np.asarray(s[1]) * (hi - lo)
-            if self.last is None:
+            if self.last is None or self.dry:
                 return
             S = self.last[1]["S"]
             idx, x = eng.explore_safeset(t)
@@ -420,9 +813,15 @@ class Walk:
         ref = self._ref("safeopt", b, quirk)
         q = self.ds["Y_norm"].shape[1]
         call = lambda: self.eng.sweep_safeopt(b, quirk_L_index=quirk, want_masks=True, posterior_ready=ready, lean=lean)  # noqa: E731
+        self._margin("safeopt", ref)
+        self.last_sweep = ("safeopt", b, lean, ready, quirk)
         if ref["empty_safe_set"]:
-            self.last = None
-            return self._empty(ref, call)
+            self.last, self.masks, self.rob_kept, self.winner = None, None, None, None
+            return None if self.dry else self._empty(ref, call)
+        self.winner = self.pts[ref["minimizer_index"]]
+        if self.dry:
+            self.last = ("safeopt", ref)
+            return
         res = call()
         eng = self.eng
         for k in ("S", "U", "M"):
@@ -442,14 +841,21 @@ class Walk:
         else:
             assert np.allclose(res["L"], ref["L"], rtol=1e-9), ("L", res["L"], ref["L"])
         self.last = ("safeopt", ref)
+        self._keep_masks([("S", 0), ("U", 0), ("M", 0)] + [("G", c) for c in range(1, q)])
 
     def goose(self, b, ready):
         ref = self._ref("goose", b)
         q = self.ds["Y_norm"].shape[1]
         call = lambda: self.eng.sweep_goose(b, want_masks=True, posterior_ready=ready)  # noqa: E731
+        self._margin("goose", ref)
+        self.last_sweep = ("goose", b, ready)
         if ref["empty_safe_set"]:
-            self.last = None
-            return self._empty(ref, call)
+            self.last, self.masks, self.rob_kept, self.winner = None, None, None, None
+            return None if self.dry else self._empty(ref, call)
+        self.winner = self.pts[ref["safe_min_index"]]
+        if self.dry:
+            self.last = ("goose", ref)
+            return
         res = call()
         eng = self.eng
         for k in ("S", "U"):
@@ -464,19 +870,31 @@ class Walk:
         assert res["choose_safe_min"] == ref["choose_safe_min"]
         assert np.allclose(res["L"], ref["L"], rtol=1e-9), ("L", res["L"], ref["L"])
         self.last = ("goose", ref)
+        self._keep_masks([("S", 0), ("U", 0)] + [("O", c) for c in range(1, q)])
 
     def tr(self, b, r, ready):
         x0 = self.pts[len(self.pts) // 3]
         ref = self._ref("tr", b, tuple(x0), r)
         call = lambda: self.eng.sweep_tr(b, x0, r, posterior_ready=ready)  # noqa: E731
-        if ref["empty"] and not ref["S"].any():
-            return self._empty(ref, call)
+        self._margin("tr", ref, x0, r)
+        self.last_sweep = ("tr", b, r, ready)
+        # (an empty trust region, or an empty safe set, is no error of sbo_sweep_tr: index -1 -- include/safebo.h: sbo_tr_result)
+        self.winner = self.pts[ref["index"]] if not ref["empty"] else None
+        if self.dry:
+            return
         res = call()
+        self._keep_masks([("S", 0), ("M", 0)])
         assert res["count_S"] == ref["S"].sum() and res["count_T"] == ref["T"].sum(), ("counts", res["count_S"], res["count_T"])
         assert res["index"] == (ref["index"] if not ref["empty"] else -1), ("index", res["index"])
 
     def robust(self, b, kind, ready):
         ref = self._ref("robust", b, kind)
+        self.last_sweep = ("robust", b, kind, ready)
+        self.winner = self.pts[ref["index"]][:1] if ref["index"] >= 0 else None      # (axis 0 is the control, the fastest)
+        if self.dry:
+            g = ref["g"] / np.maximum(1.0, self.ds["Y_std"])[1:, None]
+            self.margins.append((self.index, "robust", float(np.min(np.abs(g))) if g.size else np.inf))
+            return
         res = self.eng.sweep_robust(b, 1, kind, posterior_ready=ready)
         assert res["index"] == ref["index"] and res["count_safe"] == ref["count_safe"], ("robust", res["index"], ref["index"])
         assert res["worst_d_index"] == ref["worst_d_index"]
@@ -485,3 +903,142 @@ class Walk:
         assert _nerr(f, ref["f"], self.ds["Y_std"][0], 1) < tol
         for c in range(g.shape[0]):
             assert _nerr(g[c], ref["g"][c], self.ds["Y_std"][c + 1], 1) < tol
+        self.masks, self.rob_kept = None, (f, g)
+
+    # ---- the steps added since the first version ------------------------------------------------------------------------------------
+    def fit(self):
+        """engine.model_fit on the current data (P = 8, four generations, no polish, a fixed seed); the reference is the oracle of the
+        returned hyper-parameters, built as use_invK=False builds it.  Dry: the host twin of the DE on the oracle's likelihood."""
+        ds = self.ds
+        d, q = ds["X_norm"].shape[1], ds["Y_norm"].shape[1]
+        if d != 2:
+            raise RuntimeError("the fit step's box is two-dimensional")
+        pop = np.random.default_rng(FIT_SEED).uniform(FIT_BOX[:, 0], FIT_BOX[:, 1], size=(FIT_P, d + 2))
+        if self.dry:
+            hyp = np.empty((d + 2, q))
+            for o in range(q):
+                nll = lambda P, o=o: np.array([oracle.negative_loglikelihood(h, ds["X_norm"], ds["Y_norm"][:, o]) for h in P])  # noqa: E731
+                hyp[:, o] = de_twin.fit_de(nll, FIT_BOX, pop, FIT_SEED + o, FIT_MAXITER, 0.0)[0]
+        else:
+            data = {k: ds[k] for k in ("X_mean", "X_std", "Y_mean", "Y_std", "X_norm", "Y_norm")}
+            out = self.eng.model_fit(data, FIT_BOX, pop, seed=FIT_SEED, maxiter=FIT_MAXITER, tol=0.0, polish=False)
+            hyp = out["hypopt"]
+            assert hyp.shape == (d + 2, q) and np.all(hyp >= FIT_BOX[:, :1]) and np.all(hyp <= FIT_BOX[:, 1:]), hyp
+        self.ds = dict(ds, hypopt=hyp, invKopt=oracle.build_invK(ds["X_norm"], hyp))
+        self.ds.pop("mean_prior", None)
+        self._model_changed()
+
+    def ro_loo(self):
+        if not self.dry:
+            model_loo.check_loo(self.eng, self.ds, model_loo.TOL64, f"walk {self.seed} step {self.index}")
+
+    def ro_mean_grad(self):
+        lo, hi = self.box
+        pts = self.rng.uniform(lo, hi, size=(257, len(lo)))
+        if self.dry:
+            return
+        got, inf = self.eng.mean_grad(pts, infnorm=True)
+        want = oracle.mean_grad(pts, self.ds)
+        for o in range(want.shape[1]):
+            scale, dev = np.max(np.abs(want[:, o, :])), np.max(np.abs(got[:, o, :] - want[:, o, :]))
+            assert dev <= RTOL_GRAD * scale, ("mean_grad", o, dev, scale)
+        assert np.array_equal(inf, np.max(np.abs(got), axis=2))
+
+    def ro_lipschitz(self):
+        if self.dry:
+            return
+        lo, hi = self.box
+        out = self.eng.lipschitz(lo, hi)
+        for o in range(self.ds["Y_norm"].shape[1]):
+            x = out["x"][o]
+            assert np.all(x >= lo) and np.all(x <= hi), ("lipschitz", o, x)
+            assert out["L"][o] >= out["L_seed"][o] > 0.0, ("lipschitz", o, out["L"][o], out["L_seed"][o])
+            _, inf = self.eng.mean_grad(x, infnorm=True)
+            assert out["L"][o].tobytes() == inf[0, o].tobytes(), ("lipschitz", o, out["L"][o], inf[0, o])
+
+    def ro_batch_select(self, k):
+        lo, hi = self.box
+        pool = self.rng.uniform(lo, hi, size=(500, len(lo)))
+        ref = batch_oracle.select_naive(self.ds, 0, pool, k)
+        if self.dry:
+            return
+        got = self.eng.batch_select(pool, k, 0, return_var=True)
+        assert len(got["index"]) == k, got["index"]
+        ys = float(self.ds["Y_std"][0])
+        for j in range(k):
+            # (picks are compared while the oracle's own arg-max is decided by more than GAP; behind a closer call the batches differ)
+            if not ref["gaps"][j] > batch_oracle.GAP:
+                break
+            assert got["index"][j] == ref["index"][j], ("batch_select", j, got["index"], ref["index"], ref["gaps"])
+            assert abs(got["std"][j] / ys - np.sqrt(max(0.0, ref["v_pick"][j]))) < batch_oracle.TOL64, ("batch_select std", j)
+        else:
+            assert np.max(np.abs(got["var"] / ys ** 2 - np.maximum(0.0, ref["v"]))) < batch_oracle.TOL64, "batch_select var"
+
+    def _refine_contract(self, P, out, seed):
+        """The contract of the refine calls: the oracle's posterior at the returned point satisfies every term, the reported value is
+        the oracle's bound there, and it is no worse than the seed's -- all within 1e-10 max(1, Y_std)."""
+        tol = 1e-10 * max(1.0, float(np.max(self.ds["Y_std"])))
+        x = out["x"][0]
+        assert out["best"] == 0 and np.all(x >= P["lo"]) and np.all(x <= P["hi"]), (out["best"], x)
+        for name, g, _ in rso.terms(P, x):
+            assert g >= -tol, ("refine term", name, g)
+        val, val0 = rso.value(P, x), rso.value(P, seed)
+        assert abs(out["value"][0] - val) <= tol, ("refine value", out["value"][0], val)
+        worse = (val0 - out["value"][0]) if P["maximize"] else (out["value"][0] - val0)
+        assert worse <= tol, ("refine: worse than its seed", out["value"][0], val0)
+
+    def _seed(self, what):
+        if self.winner is None or self.last_sweep[0] == "robust":
+            raise RuntimeError(f"{what}: the last sweep left no winner to start from")
+        return np.array(self.winner)
+
+    def ro_refine(self):
+        seed, b = self._seed("refine"), self.last_sweep[1]
+        lo, hi = self.box
+        P = rso.problem(self.ds, b, lo, hi, "lcb", objective=0)
+        if not self.dry:
+            self._refine_contract(P, self.eng.refine(b, seed, 0, "lcb", lo=lo, hi=hi), seed)
+
+    def ro_refine_sets(self):
+        """The M_t problem from the sweep's minimiser: max var_0 s.t. lcb_c >= 0 and lcb_0 <= u*."""
+        if self.last_sweep[0] != "safeopt" or self.last is None:
+            raise RuntimeError("refine_sets: the last sweep was no SafeOpt sweep with a safe set")
+        seed, b = self._seed("refine_sets"), self.last_sweep[1]
+        lo, hi = self.box
+        P = rso.problem(self.ds, b, lo, hi, "var", objective=0, maximize=True, level=(0, float(self.last[1]["u_star"])))
+        if not self.dry:
+            self._refine_contract(P, self.eng.refine_sets(b, seed, **rso.engine_args(P)), seed)
+
+    def ro_refine_robust(self):
+        if self.last_sweep[0] != "robust" or self.cand[0] != "grid" or self.winner is None:
+            raise RuntimeError("refine_robust: the last sweep was no robust sweep on a grid with a robust-safe control")
+        _, b, kind, _ = self.last_sweep
+        lo, hi = self.box
+        count_d = [17]
+        if self.dry:
+            return
+        out = self.eng.refine_robust(b, self.winner, 1, lo, hi, count_d, kind)
+        ds, mp = self.ds, oracle.mean_prior(self.ds)
+        tol = 1e-10 * max(1.0, float(np.max(ds["Y_std"])))
+        Cset = np.vstack((robust_refine_oracle.check_grid(lo, hi, 1, count_d), out["scenarios"]))
+        f, l = robust_refine_oracle.exact_on(out["xc"], Cset, ds, mp, b, kind)
+        f0, _ = robust_refine_oracle.exact_on(self.winner, Cset, ds, mp, b, kind)
+        assert lo[0] <= out["xc"][0] <= hi[0] and np.all(out["scenarios"] >= lo[1:]) and np.all(out["scenarios"] <= hi[1:])
+        assert abs(out["value"] - np.max(f)) <= tol and abs(out["seed_value"] - np.max(f0)) <= tol, (out["value"], np.max(f), out["seed_value"], np.max(f0))
+        assert np.max(np.abs(out["g_min"] - l[:, 1:].min(axis=0))) <= tol and np.all(l[:, 1:].min(axis=0) >= -tol), out["g_min"]
+        assert out["value"] <= out["seed_value"] + tol
+
+    def ro_nll(self):
+        """nll_batch with P = 8 and nll_grad_batch on the current rows, output 0, at the tolerances of tests/test_gpu_fit_shapes.py."""
+        X, y = self.ds["X_norm"], self.ds["Y_norm"][:, 0]
+        d = X.shape[1]
+        H = self.rng.uniform([-0.5] * d + [-0.5, -2.0], [0.5] * d + [0.5, -1.0], size=(8, d + 2))
+        if self.dry:
+            return
+        nll = self.eng.nll_batch(X, y, H)
+        nll2, grad = self.eng.nll_grad_batch(X, y, H)
+        assert np.array_equal(nll.view(np.uint64), nll2.view(np.uint64))
+        for p, h in enumerate(H):
+            ref, g = nll_grad_oracle.nll_grad(h, X, y)
+            assert abs(nll[p] - ref) <= 1e-9 * max(1.0, abs(ref)), ("nll", p, nll[p], ref)
+            assert np.all(np.abs(grad[p] - g) <= 1e-8 * nll_grad_oracle.grad_scale(h, X, y) + 1e-300), ("nll grad", p, grad[p], g)

@@ -11,91 +11,19 @@ L[1] is compared with lean 0's and the oracle's like every other case's."""
 import numpy as np
 import pytest
 
-import safebo_amd
 import skip_safe_cases as cases
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ("minimizer_index", "expander_index", "expander_best_c", "choose_minimizer", "count_S", "count_U", "count_M", "u_star",
-        "minimizer_std", "expander_std")
 CASES = [(cases.WHOLE, 1.0), (cases.WHOLE, 0.25), (cases.WHOLE, 3.0), (cases.INSIDE, None)]
+# (the sweep, comparison and start-up helpers are tests/skip_safe_cases.py's: tests/test_gpu_history.py uses them too)
+KEYS = cases.KEYS
+_masks, _sweep, _same, _check_oracle, _census, _skips = cases.masks, cases.sweep, cases.same, cases.check_oracle, cases.census_safe, cases.skips
+_colpath_options, _start, _fresh = cases.colpath_options, cases.start, cases.fresh
 
 
 def _b(b):
     return cases.config()["b"] if b is None else b
-
-
-def _masks(eng):
-    return {"S": eng.mask("S"), "U": eng.mask("U"), "M": eng.mask("M"), "G": eng.mask("G", 1)}
-
-
-def _sweep(eng, b, lean):
-    res = eng.sweep_safeopt(b, want_masks=True, lean=lean)
-    return res, _masks(eng)
-
-
-def _same(a, b):
-    (ra, ma), (rb, mb) = a, b
-    for k in KEYS:
-        assert ra[k] == rb[k], (k, ra[k], rb[k])
-    assert list(ra["count_G"]) == list(rb["count_G"]) and list(ra["expander_index_c"]) == list(rb["expander_index_c"])
-    assert ra["L"][1] == rb["L"][1]
-    for k in ma:
-        assert np.array_equal(ma[k], mb[k]), k
-
-
-def _check_oracle(res, masks, ref):
-    for k in ("S", "U", "M"):
-        assert np.array_equal(masks[k], ref[k]), k
-    assert np.array_equal(masks["G"], ref["G"][0])
-    assert res["minimizer_index"] == ref["minimizer_index"]
-    assert list(res["expander_index_c"]) == list(ref["expander_index"])
-    assert abs(res["u_star"] - ref["u_star"]) < 1e-10
-    assert (res["count_S"], res["count_U"], res["count_M"], res["count_G"][0]) == (ref["S"].sum(), ref["U"].sum(), ref["M"].sum(), ref["G"][0].sum())
-    assert np.allclose(res["L"][1:], ref["L"][1:], rtol=1e-9)
-    assert abs(res["minimizer_std"] - ref["minimizer_std"]) < 1e-10
-    if ref["expander_best"] > 0:
-        assert abs(res["expander_std"] - ref["expander_best_std"]) < 1e-10
-
-
-def _census(name, b):
-    """Tiles the CPU census proves safe.  (The device's count of tiles proved UNSAFE is not compared with the census, which leaves the
-    band test out and proves more -- tests/skip_safe_cases.py: encl_unsafe --; it is compared between option settings instead.)"""
-    return int(cases.census(name, b)["safe"].sum())
-
-
-def _skips(eng):
-    p = eng.profile()
-    return p["k1_tiles_skipped_safe"], p["k1_tiles_skipped"]
-
-
-def _colpath_options(eng):
-    eng.set_option("fuse_classify", 1)
-    eng.set_option("col_path", 2)
-
-
-def _start(eng, name, b):
-    """Grid and model of a case, the model's first sweep (K1i) and the plan's first K1b sweep, which evaluates every tile and records."""
-    lo, hi, count = cases.grid(name)
-    eng.set_grid(lo, hi, list(count))
-    eng.set_model(cases.config()["ds"], dtype="f64")
-    eng.sweep_safeopt(b, want_masks=True)
-    eng.sweep_safeopt(b, want_masks=True)
-    assert eng.profile()["posterior_kernel"] == 4 and _skips(eng) == (0, 0)
-
-
-_FRESH = {}
-
-
-def _fresh(name, b):
-    """What a fresh engine returns for the case at lean 0 on its K1b plan (nothing skipped): computed once per (grid, b)."""
-    if (name, b) not in _FRESH:
-        with safebo_amd.SweepEngine(0) as eng:
-            _colpath_options(eng)
-            _start(eng, name, b)
-            _FRESH[(name, b)] = _sweep(eng, b, 0)
-            assert eng.profile()["set_path"] == 1
-    return _FRESH[(name, b)]
 
 
 @pytest.fixture
