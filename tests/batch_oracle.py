@@ -109,10 +109,41 @@ def follow(ds, o, pool, picks, pending=None):
     return select_naive(ds, o, pool, len(picks), pending, 0.0, picks=picks)
 
 
+def variance_after(ds, o, pool, picks, pending=None):
+    """v [m] (normalised, not clipped) after conditioning on the pending points and on all of ``picks``, by the definition: one full
+    matrix over the data, the pending points and the picks, one inverse."""
+    ell, sf2, sn2 = params(ds, o)
+    P = normalise(ds, pool)
+    rows = [np.array(ds["X_norm"], dtype=np.float64)]
+    if pending is not None and len(pending):
+        rows.append(normalise(ds, pending))
+    rows.append(P[np.asarray(picks, dtype=np.int64)])
+    return _variance(np.vstack(rows), P, ell, sf2, sn2)
+
+
 # ---- the committed cases of tests/test_gpu_batch_select.py ---------------------------------------------------------------------------
-# (n, m, k, d, q, output, n_pending, use_invK, seed): every n in {1, 2, 63, 64, 65, 300}, m in {1, 63, 64, 65, 257, 5000} (the larger
-# ones give several workgroups in the arg-max), k in {1, 2, 8, 64} with k > m twice, d in {1, 2, 4, 8}, q = 3 with outputs 0 and 2,
-# n_pending in {0, 1, 5}, both factor sources -- each edge once, not the product.
+# (n, m, k, d, q, output, n_pending, use_invK, seed), each edge once, not the product.
+# The first eight: every n in {1, 2, 63, 64, 65, 300}, m in {1, 63, 64, 65, 257, 5000} (the larger ones give several workgroups in
+# the arg-max), k in {1, 2, 8, 64} with k > m twice, d in {1, 2, 4, 8}, q = 3 with outputs 0 and 2, n_pending in {0, 1, 5}, both
+# factor sources.  They all run in the first tier of k_batch_v0, in one LDS chunk of k_batch_pass and in one trip of every loop.
+# The cases from FIRST_LARGE on reach what lies beyond, by the constants of csrc/batch.hip (tests/test_batch_cpu.py reads them from
+# the source and holds this list to them):
+#   k_batch_v0      P = 32 points per workgroup up to n = 512, 16 up to 1024, 8 up to SBO_MAX_N = 2048, hence 1024 / P row lanes and
+#                   RB = kBatV0Rows (4) * 1024 / P = 128 | 256 | 512 rows per block; its LDS image n * P * 8 bytes is exactly 128 KiB at
+#                   n = 512, 1024 and 2048 -- n in {512, 513, 1024, 1025, 2048}, a top block of one row at 513 and 1025, m = 33 and
+#                   m = 257 no multiple of P, m = 16 one workgroup;
+#   k_batch_pass    LDS chunks of kBatChunk = 512 augmented observations: na = n + n_pending + j runs 508 .. 523 (the second chunk
+#                   starts at one row and grows) and starts at exactly 512; more than two chunks from n = 1025 up;
+#   k_batch_u       strides of kBatV0Threads = 1024 columns and 16 rows: na runs 1023 .. 1030, and up to kBatMaxAug - 1 = 2111 with
+#                   the leading dimension ld = 2112 its arrays are sized for;
+#   grid stride     k_batch_pass has at most 8192 workgroups of kBatThreads = 256: m = 2 097 152 + 513 gives 513 lanes a second
+#                   candidate of their own;
+#   padded lanes    d = 3 in dpad 4, d = 6 in dpad 8.
+# ``log_sn``: the noise of every output (-1 keeps the oracle sharp at these n, as in tests/test_gpu_model_loo.py); ``oracle``:
+# "incremental" where the naive walk (an inverse per step) would take too long; ``pool``: "planted", see planted_pool().
+FIRST_LARGE = 8
+M_TRIP = 8192 * 256                   # pool points of one trip of k_batch_pass's grid-stride loop
+PLANTED = (M_TRIP + 500, 17, M_TRIP - 1, M_TRIP)      # where the large-m pool holds its four far rows, in pick order
 CASES = [
     dict(n=1, m=1, k=2, d=2, q=2, output=0, n_pending=0, use_invK=True, seed=11),
     dict(n=2, m=63, k=8, d=1, q=2, output=1, n_pending=1, use_invK=False, seed=12),
@@ -122,7 +153,18 @@ CASES = [
     dict(n=300, m=5000, k=64, d=2, q=2, output=0, n_pending=0, use_invK=False, seed=16),
     dict(n=40, m=5000, k=8, d=2, q=2, output=1, n_pending=5, use_invK=True, seed=17),
     dict(n=20, m=8, k=64, d=2, q=2, output=0, n_pending=0, use_invK=True, seed=18),
+    dict(n=505, m=1000, k=16, d=2, q=2, output=0, n_pending=3, use_invK=True, seed=21, log_sn=-1.0),
+    dict(n=512, m=257, k=8, d=2, q=2, output=1, n_pending=0, use_invK=False, seed=22, log_sn=-1.0),
+    dict(n=513, m=33, k=2, d=2, q=2, output=0, n_pending=0, use_invK=True, seed=23, log_sn=-1.0),
+    dict(n=600, m=257, k=4, d=3, q=3, output=2, n_pending=1, use_invK=False, seed=24, log_sn=-1.0),
+    dict(n=1020, m=1000, k=8, d=2, q=2, output=0, n_pending=3, use_invK=False, seed=25, log_sn=-1.0),
+    dict(n=1024, m=16, k=1, d=2, q=2, output=1, n_pending=0, use_invK=True, seed=26, log_sn=-1.0),
+    dict(n=1025, m=257, k=8, d=2, q=2, output=0, n_pending=5, use_invK=True, seed=27, log_sn=-1.0),
+    dict(n=1100, m=257, k=4, d=6, q=3, output=2, n_pending=1, use_invK=True, seed=28, log_sn=-1.0),
+    dict(n=2048, m=300, k=59, d=2, q=2, output=1, n_pending=5, use_invK=False, seed=29, log_sn=-1.0, oracle="incremental"),
+    dict(n=8, m=M_TRIP + 513, k=4, d=2, q=2, output=0, n_pending=0, use_invK=True, seed=30, pool="planted"),
 ]
+assert len(CASES[:FIRST_LARGE]) == FIRST_LARGE and all("log_sn" not in c and "pool" not in c for c in CASES[:FIRST_LARGE])
 
 
 def case_id(c):
@@ -133,29 +175,56 @@ def make_case(c):
     """(ds, pool [m, d], pending [n_pending, d] or None) of a case.  d = q = 2: config B's data (seed 5) with the default
     hyper-parameters -- n < 3 takes the first rows of its 90-row set under that set's constants --; other shapes: uniform rows in
     [-1, 1]^d with smooth outputs, log_ell = 0.5 from d = 4 up (at the default -0.5 no two points of [-1, 1]^8 are correlated and
-    every variance is sf2 to rounding), output 2 with hyper-parameters of its own.  Pool and pending points: uniform in the box."""
+    every variance is sf2 to rounding), output 2 with hyper-parameters of its own.  A case's ``log_sn`` is the noise of every output
+    (default: -2, output 2 of q = 3: -1.5).  Pool and pending points: uniform in the box, but for ``pool="planted"``."""
     n, m, d, q = c["n"], c["m"], c["d"], c["q"]
     rng = np.random.default_rng(1000 + c["seed"])
+    log_sn = c.get("log_sn")
     if d == 2 and q == 2:
         cfg = synthetic.make_config("B", n=max(n, 90), seed=5)
         ds0, bound = cfg["ds"], np.asarray(cfg["bound"], dtype=np.float64)
+        if log_sn is not None:
+            ds0 = synthetic.make_dataset(cfg["X"], cfg["Y"], synthetic.default_hypopt(2, 2, log_sn=log_sn))
     else:
         bound = np.array([[-1.0, 1.0]] * d)
         X = rng.uniform(bound[:, 0], bound[:, 1], size=(max(n, 30), d))
         Y = np.column_stack([np.sin((o + 1.0) * X.sum(axis=1)) + 0.5 * np.cos(2.0 * X[:, 0] - o) for o in range(q)])
-        hyp = synthetic.default_hypopt(d, q, log_ell=-0.5 if d <= 2 else 0.5)
+        hyp = synthetic.default_hypopt(d, q, log_ell=-0.5 if d <= 2 else 0.5, **({} if log_sn is None else {"log_sn": log_sn}))
         if q > 2:
-            hyp[:, 2] = synthetic.default_hypopt(d, 1, log_ell=-0.3 if d <= 2 else 0.7, log_sf=0.2, log_sn=-1.5)[:, 0]
+            hyp[:, 2] = synthetic.default_hypopt(d, 1, log_ell=-0.3 if d <= 2 else 0.7, log_sf=0.2, log_sn=-1.5 if log_sn is None else log_sn)[:, 0]
         ds0 = synthetic.make_dataset(X, Y, hyp)
     ds = ds0 if ds0["X_norm"].shape[0] == n else mr.with_rows(ds0, ds0["X_norm"][:n], ds0["Y_norm"][:n])
+    if c.get("pool") == "planted":
+        return ds, planted_pool(ds, c["output"], bound, m, rng), None
     pool = rng.uniform(bound[:, 0], bound[:, 1], size=(m, d))
     pending = rng.uniform(bound[:, 0], bound[:, 1], size=(c["n_pending"], d)) if c["n_pending"] else None
     return ds, pool, pending
 
 
+def planted_pool(ds, o, bound, m, rng):
+    """A pool longer than one trip of k_batch_pass's grid-stride loop whose batch is known.  Two million uniform points would make
+    the top of the variance ranking dense, so every row is one of the observations (de-normalised) plus 0.02 N(0, 1) noise -- tiny
+    variances --, the rows from M_TRIP on are copies of rows 0, 1, .. (a lane meets the same point in its first and in its second
+    trip), and the four picks select_naive makes among 64 uniform box points are planted, in pick order, at PLANTED: on both sides of
+    the trip boundary, and one of them at a row whose copy then holds another point."""
+    n, d = ds["X_norm"].shape
+    assert m > M_TRIP and max(PLANTED) < m
+    obs = np.asarray(ds["X_norm"]) * ds["X_std"] + ds["X_mean"]
+    pool = obs[rng.integers(0, n, size=m)] + 0.02 * rng.standard_normal((m, d))
+    pool[M_TRIP:] = pool[:m - M_TRIP]
+    far = rng.uniform(bound[:, 0], bound[:, 1], size=(64, d))
+    far = far[select_naive(ds, o, far, len(PLANTED))["index"]]
+    assert len(far) == len(PLANTED)
+    pool[list(PLANTED)] = far
+    return pool
+
+
 @functools.lru_cache(maxsize=None)
 def reference(i):
-    """Case i and its naive selection, computed once per process: (ds, pool, pending, select_naive result)."""
+    """Case i and its reference selection, computed once per process: (ds, pool, pending, result) -- select_naive's, or
+    select_incremental's where the case says ``oracle="incremental"`` (tests/test_batch_cpu.py ties that one to the definition
+    through variance_after)."""
     c = CASES[i]
     ds, pool, pending = make_case(c)
-    return ds, pool, pending, select_naive(ds, c["output"], pool, c["k"], pending)
+    select = {"naive": select_naive, "incremental": select_incremental}[c.get("oracle", "naive")]
+    return ds, pool, pending, select(ds, c["output"], pool, c["k"], pending)

@@ -31,7 +31,8 @@ k_lipschitz, the scratch layout):
 
 batch_select (index, std, n_selected and var_out; the block arg-max over one and over several workgroups, the scratch layout,
 the dpad dispatch):
-  every entry of batch_oracle.CASES (n in 1 .. 300, m in 1 .. 5000, dpad 2, 4 and 8, pending points, k > m);
+  the first eight entries of batch_oracle.CASES, which are the ones that commit had (n in 1 .. 300, m in 1 .. 5000, dpad 2, 4 and
+  8, pending points, k > m; the later entries, n = 505 and up, are compared with the oracle in tests/test_gpu_batch_select.py);
   the duplicated pool of test_ties_permutations_embeddings_and_repeated_calls (every row twice: each pick is a tie between two
   workgroups' candidates).
 
@@ -111,7 +112,7 @@ def _lipschitz(engine):
 
 def _batch(engine):
     out = {}
-    for c in bo.CASES:
+    for c in bo.CASES[:bo.FIRST_LARGE]:                     # (the cases that existed when the fixture was recorded)
         ds, pool, pending = bo.make_case(c)
         engine.set_model(ds, use_invK=c["use_invK"])
         out["batch_" + bo.case_id(c)] = _batch_call(engine, pool, c["k"], c["output"], pending)
