@@ -243,9 +243,42 @@ class GP:
         self.ny_dim = self.Y.shape[1]
         self.multi_hyper = multi_hyper
         self.var_out = var_out
+        self._refit()
+
+    def _refit(self):
+        """The default path on the data the model holds: re-normalise, refit, rebuild (models/GP_Safe.py:283-304)."""
         self.X_norm, self.Y_norm = self.data_normalization()
         self.hypopt, self.invKopt = self.determine_hyperparameters(self.X_norm, self.Y_norm)
         self.update_inference_dataset()
+
+    def _device_followed(self):
+        """Behind an incremental update: the host state is complete again and the device model already holds it."""
+        self.update_inference_dataset()              # bumps _model_version: the cached sweeps of SafeOpt / GoOSE.BO are stale
+        self._uploaded_version = self._model_version  # ... but the device model is already current: no re-upload
+        self._cand_token = None
+
+    @staticmethod
+    def _check_incremental_args(incremental, window, refit_when, what):
+        """``window`` and ``refit_when`` of add_sample / add_samples; ``what``: how that method's default path refits."""
+        if refit_when is not None:
+            if not incremental:
+                raise ValueError(f"refit_when needs incremental=True (the default path refits {what})")
+            if not callable(refit_when):
+                raise ValueError("refit_when must be callable: it receives the dict of loo()")
+        if window is not None:
+            if not incremental:
+                raise ValueError("window needs incremental=True (the default path refits on all data)")
+            if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1:
+                raise ValueError("window must be an integer >= 1")
+
+    def _carry_lazy(self, X_norm):
+        """[(i, invKopt[i])] of the outputs whose inverse exists, for an update that carries them over to the rows ``X_norm``.  A
+        ``LazyInvK`` is replaced by one over those rows first: an element nobody has read stays unformed and is not in the list."""
+        if not isinstance(self.invKopt, LazyInvK):
+            return list(enumerate(self.invKopt))
+        hypopt, old = self.hypopt, self.invKopt
+        self.invKopt = LazyInvK(lambda i: self._invK(X_norm, hypopt, i), self.ny_dim)
+        return [(i, P) for i, P in enumerate(old._items) if P is not None]
 
     def add_sample(self, x_new, y_new, incremental: bool = False, window: int | None = None, refit_when=None):
         """Reference behaviour (models/GP_Safe.py:283-304): re-normalise, refit, rebuild.  ``incremental=True`` is the
@@ -257,16 +290,8 @@ class GP:
         only) asks whether the frozen constants still describe the data: after the update ``fn(self.loo())`` is called, and if it
         returns true the model is refitted on the data it now holds by exactly the default path (re-normalise, refit, rebuild).
         The policy is the caller's; the library fixes no threshold."""
-        if refit_when is not None:
-            if not incremental:
-                raise ValueError("refit_when needs incremental=True (the default path refits on every sample)")
-            if not callable(refit_when):
-                raise ValueError("refit_when must be callable: it receives the dict of loo()")
+        self._check_incremental_args(incremental, window, refit_when, "on every sample")
         if window is not None:
-            if not incremental:
-                raise ValueError("window needs incremental=True (the default path refits on all data)")
-            if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1:
-                raise ValueError("window must be an integer >= 1")
             while self.n_point >= window:
                 self.remove_sample(0)
         self.X = np.vstack([self.X, np.asarray(x_new, dtype=np.float64)])
@@ -290,14 +315,10 @@ class GP:
                                             [-u[None, :] / s, np.array([[1.0 / s]])]])
             self.X_norm = np.vstack([self.X_norm, xn])
             self.Y_norm = np.vstack([self.Y_norm, yn])
-            self.update_inference_dataset()              # bumps _model_version: the cached sweeps of SafeOpt / GoOSE.BO are stale
-            self._uploaded_version = self._model_version  # ... but the device model is already current: no re-upload
-            self._cand_token = None
+            self._device_followed()
             if refit_when is None or not refit_when(self.loo()):
                 return
-        self.X_norm, self.Y_norm = self.data_normalization()
-        self.hypopt, self.invKopt = self.determine_hyperparameters(self.X_norm, self.Y_norm)
-        self.update_inference_dataset()
+        self._refit()
 
     def add_samples(self, X_new, Y_new, incremental: bool = True, window: int | None = None, refit_when=None):
         """k observations at once -- the other half of ``Batch``: ``X_new`` [k, d], ``Y_new`` [k, q] in physical units.
@@ -319,16 +340,8 @@ class GP:
             raise ValueError("add_samples needs at least one row")
         if not (np.all(np.isfinite(X_new)) and np.all(np.isfinite(Y_new))):
             raise ValueError("X_new and Y_new must be finite")
-        if refit_when is not None:
-            if not incremental:
-                raise ValueError("refit_when needs incremental=True (the default path refits on the stacked data)")
-            if not callable(refit_when):
-                raise ValueError("refit_when must be callable: it receives the dict of loo()")
+        self._check_incremental_args(incremental, window, refit_when, "on the stacked data")
         if window is not None:
-            if not incremental:
-                raise ValueError("window needs incremental=True (the default path refits on all data)")
-            if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1:
-                raise ValueError("window must be an integer >= 1")
             if not k < window:
                 raise ValueError(f"a block of k = {k} rows needs window > k")
             for _ in range(max(0, self.n_point + k - int(window))):
@@ -336,9 +349,7 @@ class GP:
         if not incremental:
             self.X, self.Y = np.vstack([self.X, X_new]), np.vstack([self.Y, Y_new])
             self.n_point = self.X.shape[0]
-            self.X_norm, self.Y_norm = self.data_normalization()
-            self.hypopt, self.invKopt = self.determine_hyperparameters(self.X_norm, self.Y_norm)
-            self.update_inference_dataset()
+            self._refit()
             return
         self._sync_model()
         d = self.nx_dim
@@ -347,14 +358,7 @@ class GP:
             yn = (Y_new[b0:b0 + SBO_MAX_APPEND] - self.Y_mean) / self.Y_std
             self.engine.append_samples(xn, yn)
             X_norm = np.vstack([self.X_norm, xn])
-            lazy = isinstance(self.invKopt, LazyInvK)
-            if lazy:                              # what nobody has read stays unformed, now over all rows
-                hypopt, old = self.hypopt, self.invKopt
-                self.invKopt = LazyInvK(lambda i, X_norm=X_norm, hypopt=hypopt: self._invK(X_norm, hypopt, i), self.ny_dim)
-            for i in range(self.ny_dim):
-                if lazy and old._items[i] is None:
-                    continue
-                P = old._items[i] if lazy else self.invKopt[i]
+            for i, P in self._carry_lazy(X_norm):       # (what nobody has read stays unformed, now over all rows)
                 ell, sf2 = np.exp(2.0 * self.hypopt[:d, i]), np.exp(2.0 * self.hypopt[d, i])
                 sn2 = np.exp(2.0 * self.hypopt[d + 1, i]) + FLOAT32_EPS
                 B = self.Cov_mat(self.kernel, self.X_norm, xn, ell, sf2)
@@ -370,13 +374,9 @@ class GP:
             self.Y = np.vstack([self.Y, Y_new[b0:b0 + SBO_MAX_APPEND]])
             self.X_norm, self.Y_norm = X_norm, np.vstack([self.Y_norm, yn])
             self.n_point = self.X.shape[0]
-        self.update_inference_dataset()              # bumps _model_version: the cached sweeps of SafeOpt / GoOSE.BO are stale
-        self._uploaded_version = self._model_version  # ... but the device model is already current: no re-upload
-        self._cand_token = None
+        self._device_followed()
         if refit_when is not None and refit_when(self.loo()):
-            self.X_norm, self.Y_norm = self.data_normalization()
-            self.hypopt, self.invKopt = self.determine_hyperparameters(self.X_norm, self.Y_norm)
-            self.update_inference_dataset()
+            self._refit()
 
     def remove_sample(self, index: int):
         """The mirror of ``add_sample(..., incremental=True)``: observation ``index`` leaves the model under the frozen
@@ -393,22 +393,13 @@ class GP:
         self.engine.remove_sample(index)
         keep = np.arange(n) != index
         X_norm = self.X_norm[keep]
-        lazy = isinstance(self.invKopt, LazyInvK)
-        if lazy:                                  # what nobody has read stays unformed, now over the remaining rows
-            hypopt, old = self.hypopt, self.invKopt
-            self.invKopt = LazyInvK(lambda i: self._invK(X_norm, hypopt, i), self.ny_dim)
-        for i in range(self.ny_dim):
-            if lazy and old._items[i] is None:
-                continue
-            P = old._items[i] if lazy else self.invKopt[i]
+        for i, P in self._carry_lazy(X_norm):           # (what nobody has read stays unformed, now over the remaining rows)
             b = P[keep, index]
             self.invKopt[i] = P[np.ix_(keep, keep)] - np.outer(b, b) / P[index, index]
         self.X, self.Y = self.X[keep], self.Y[keep]
         self.X_norm, self.Y_norm = X_norm, self.Y_norm[keep]
         self.n_point = n - 1
-        self.update_inference_dataset()              # bumps _model_version: the cached sweeps of SafeOpt / GoOSE.BO are stale
-        self._uploaded_version = self._model_version  # ... but the device model is already current: no re-upload
-        self._cand_token = None
+        self._device_followed()
 
     def loo(self, b=None):
         """Leave-one-out diagnostics of the model as it stands (``sbo_model_loo``: one O(n^2) pass over the device model's factor,

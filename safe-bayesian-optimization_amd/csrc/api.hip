@@ -57,7 +57,7 @@ void drain_streams(sbo_ctx* c) {
 }
 
 // The reverse Cholesky factor of a caller's invK may still be in the making (sbo_ctx::factor_pending): every consumer of
-// Fpk / Fplain waits here first.  The positive-definiteness verdict arrives with it.
+// Fpk / the fp64 factor (sbo_ctx::factor) waits here first.  The positive-definiteness verdict arrives with it.
 int factor_sync(sbo_ctx* c) {
   if (c->factor_todo) {                   // (not even enqueued: a model change that failed half-way)
     const int rc = model_factor_enqueue(c);
@@ -496,137 +496,88 @@ int sbo_model_fit(sbo_ctx* c, int dtype, const char* kernel, int n, int d, int q
   return rc;
 }
 
+// What sbo_model_append, sbo_model_append_batch and sbo_model_remove ask of the resident model once their arguments are checked:
+// `rows` = +1 with block == false (one row, k_model_append), +k with block == true (the block kernels), -1 (row `index` leaves).
+struct ModelUpdateRequest { int rows; bool block; int index; const double *x_norm_new /* [rows][d] */, *y_norm_new /* [rows][q] */; };
+
+// The one sequence of a model update under frozen hyper-parameters and normalisation.  Every output's update is computed and checked
+// before anything is written: a refused update leaves the model as it was.  The fp64 twin of this model makes the same public call and
+// must accept before the owner commits (a twin left behind by an earlier model takes no part); until the owner is done it is not current.
+static int model_update_run(sbo_ctx* c, const ModelUpdateRequest& r) {
+  ModelConst& mc = c->mc;
+  const int d = mc.d;
+  SBO_HIP(hipSetDevice(c->device));
+  int rc;
+  if ((rc = factor_sync(c))) return rc;                    // (the update works on the resident factor)
+  ModelUpdate u;
+  if (r.rows < 0) u = model_update_staged(c, -1, r.index);
+  else if ((rc = r.block ? model_append_block_stage(c, r.rows, r.x_norm_new, r.y_norm_new, u) : model_append_stage(c, r.x_norm_new, r.y_norm_new, u)))
+    return rc;
+  const bool twin = twin_current(c);
+  if (twin) {
+    sbo_ctx* s = c->recheck.shadow;
+    rc = r.rows < 0 ? sbo_model_remove(s, r.index)
+                    : (r.block ? sbo_model_append_batch(s, r.rows, r.x_norm_new, r.y_norm_new) : sbo_model_append(s, r.x_norm_new, r.y_norm_new));
+    if (rc) return rc;
+    c->recheck.serial = Recheck::kNoSerial;
+  }
+  if ((rc = model_update_commit(c, u))) return rc;
+  // the derived arrays over the rows the model now holds (device), then one re-pack of the factor images
+  if (r.rows < 0) c->h_Xnorm.erase(c->h_Xnorm.begin() + (size_t)r.index * d, c->h_Xnorm.begin() + (size_t)(r.index + 1) * d);
+  else c->h_Xnorm.insert(c->h_Xnorm.end(), r.x_norm_new, r.x_norm_new + (size_t)r.rows * d);
+  mc.n += r.rows;
+  mc.npad = (mc.n + 15) / 16 * 16;
+  if ((rc = model_prep(c, c->h_Xnorm.data()))) return rc;
+  if ((rc = model_repack(c))) return rc;
+  ++c->model_serial;
+  if (twin) c->recheck.serial = c->model_serial;
+  model_changed(c);
+  return SBO_OK;
+}
+
 // one more observation under frozen hyper-parameters and normalisation, O(n^2) on the
 // device instead of a refit (the reference always refits and renormalises, models/GP_Safe.py:283-304 -- this is an
 // opt-in fast path, not its behaviour).
 int sbo_model_append(sbo_ctx* c, const double* x_norm_new, const double* y_norm_new) {
   if (c) guard_audit_harvest(c, true);
   if (!c || !x_norm_new || !y_norm_new) return fail(SBO_E_INVALID, "NULL argument");
-  if (!c->has_model || !c->Fplain.p) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
-  ModelConst& mc = c->mc;
-  const int n = mc.n, d = mc.d, q = mc.q;
-  for (int a = 0; a < d; ++a)
+  if (!c->has_model || !c->factor.present()) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
+  for (int a = 0; a < c->mc.d; ++a)
     if (!std::isfinite(x_norm_new[a])) return fail(SBO_E_INVALID, "x_norm_new must be finite");
-  for (int o = 0; o < q; ++o)
+  for (int o = 0; o < c->mc.q; ++o)
     if (!std::isfinite(y_norm_new[o])) return fail(SBO_E_INVALID, "y_norm_new must be finite");
-  if (n + 1 > SBO_MAX_N) return fail(SBO_E_UNSUPPORTED, "model is at its capacity: rebuild it with sbo_model_set");
-  SBO_HIP(hipSetDevice(c->device));
-  { const int rcf = factor_sync(c); if (rcf) return rcf; }     // (the update works on the resident factor)
-  // cross-covariances of the new point with the expanded distance of the reference (GP_Safe.py:115-119, 166)
-  std::vector<double> kvec((size_t)q * n);
-  double kappa[kMaxQ], rho[kMaxQ];
-  for (int o = 0; o < q; ++o) {
-    double bsq = 0.0, bvec[kMaxD];
-    for (int a = 0; a < d; ++a) { bvec[a] = x_norm_new[a] * mc.vinv[o][a]; bsq += bvec[a] * bvec[a]; }
-    for (int j = 0; j < n; ++j) {
-      double dot = 0.0, asq = 0.0;
-      for (int a = 0; a < d; ++a) {
-        const double v = c->h_Xnorm[(size_t)j * d + a] * mc.vinv[o][a];
-        dot += v * bvec[a];
-        asq += v * v;
-      }
-      kvec[(size_t)o * n + j] = mc.sf2[o] * std::exp(-0.5 * ((-2.0 * dot + asq) + bsq));
-    }
-    kappa[o] = mc.sf2[o] + mc.sn2[o];
-    rho[o] = y_norm_new[o] - mc.mp[o];
-  }
-  // every output's update is computed and checked before anything is written: a refused append leaves the model as it was
-  int rc = model_append_check(c, kvec, kappa, rho);
-  if (rc) return rc;
-  // (the fp64 twin of this model makes the same call and must accept first; a twin left behind by an earlier model takes no part)
-  const bool twin = twin_current(c);
-  if (twin && (rc = sbo_model_append(c->recheck.shadow, x_norm_new, y_norm_new))) return rc;
-  if (twin) c->recheck.serial = Recheck::kNoSerial;     // (ahead of its owner until the owner's update is complete)
-  if ((rc = model_append_commit(c))) return rc;
-  // the derived arrays with the new row (device), then the re-pack of the factor images
-  c->h_Xnorm.insert(c->h_Xnorm.end(), x_norm_new, x_norm_new + d);
-  mc.n = n + 1;
-  mc.npad = (mc.n + 15) / 16 * 16;
-  if ((rc = model_prep(c, c->h_Xnorm.data()))) return rc;
-  if ((rc = model_repack(c))) return rc;
-  ++c->model_serial;
-  if (twin) c->recheck.serial = c->model_serial;
-  model_changed(c);
-  return SBO_OK;
+  if (c->mc.n + 1 > SBO_MAX_N) return fail(SBO_E_UNSUPPORTED, "model is at its capacity: rebuild it with sbo_model_set");
+  return model_update_run(c, {1, false, -1, x_norm_new, y_norm_new});
 }
 
-// k observations in one block update: the sequence of sbo_model_append with the block kernels in the middle --
-// one verdict wait, one re-pack, one invalidation for the k rows.
+// k observations in one block update: one verdict wait, one re-pack, one invalidation for the k rows.
 int sbo_model_append_batch(sbo_ctx* c, int k, const double* x_norm_new, const double* y_norm_new) {
   if (c) guard_audit_harvest(c, true);
   if (!c || !x_norm_new || !y_norm_new) return fail(SBO_E_INVALID, "NULL argument");
   if (k < 1 || k > SBO_MAX_APPEND) return fail(SBO_E_INVALID, "k out of range [1, SBO_MAX_APPEND]");
-  if (!c->has_model || !c->Fplain.p) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
-  ModelConst& mc = c->mc;
-  const int n = mc.n, d = mc.d, q = mc.q;
-  for (size_t i = 0; i < (size_t)k * d; ++i)
+  if (!c->has_model || !c->factor.present()) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
+  for (size_t i = 0; i < (size_t)k * c->mc.d; ++i)
     if (!std::isfinite(x_norm_new[i])) return fail(SBO_E_INVALID, "x_norm_new must be finite");
-  for (size_t i = 0; i < (size_t)k * q; ++i)
+  for (size_t i = 0; i < (size_t)k * c->mc.q; ++i)
     if (!std::isfinite(y_norm_new[i])) return fail(SBO_E_INVALID, "y_norm_new must be finite");
-  if (n + k > SBO_MAX_N) return fail(SBO_E_UNSUPPORTED, "the block does not fit below SBO_MAX_N: rebuild the model with sbo_model_set");
-  SBO_HIP(hipSetDevice(c->device));
-  { const int rcf = factor_sync(c); if (rcf) return rcf; }     // (the update works on the resident factor)
-  // the observations the cross-covariances are formed from (device, k_append_cross) and the residuals of the new rows
-  std::vector<double> Xall(c->h_Xnorm.begin(), c->h_Xnorm.begin() + (size_t)n * d);
-  Xall.insert(Xall.end(), x_norm_new, x_norm_new + (size_t)k * d);
-  std::vector<double> rho((size_t)q * k);
-  for (int o = 0; o < q; ++o)
-    for (int r = 0; r < k; ++r) rho[(size_t)o * k + r] = y_norm_new[(size_t)r * q + o] - mc.mp[o];
-  // every output's update is computed and checked before anything is written: a refused block leaves the model as it was
-  int rc = model_append_block_check(c, k, Xall, rho);
-  if (rc) return rc;
-  // (the fp64 twin of this model makes the same call and must accept first; a twin left behind by an earlier model takes no part)
-  const bool twin = twin_current(c);
-  if (twin && (rc = sbo_model_append_batch(c->recheck.shadow, k, x_norm_new, y_norm_new))) return rc;
-  if (twin) c->recheck.serial = Recheck::kNoSerial;
-  if ((rc = model_append_block_commit(c, k))) return rc;
-  // the derived arrays with the new rows (device), then one re-pack of the factor images
-  c->h_Xnorm = std::move(Xall);
-  mc.n = n + k;
-  mc.npad = (mc.n + 15) / 16 * 16;
-  if ((rc = model_prep(c, c->h_Xnorm.data()))) return rc;
-  if ((rc = model_repack(c))) return rc;
-  ++c->model_serial;
-  if (twin) c->recheck.serial = c->model_serial;
-  model_changed(c);
-  return SBO_OK;
+  if (c->mc.n + k > SBO_MAX_N) return fail(SBO_E_UNSUPPORTED, "the block does not fit below SBO_MAX_N: rebuild the model with sbo_model_set");
+  return model_update_run(c, {k, true, -1, x_norm_new, y_norm_new});
 }
 
-// The counterpart of sbo_model_append: observation `index` leaves the resident model under the same frozen
-// hyper-parameters and normalisation, O(n^2) on the device; the rows behind it move up by one.
+// Observation `index` leaves the resident model, O(n^2) on the device; the rows behind it move up by one.
 int sbo_model_remove(sbo_ctx* c, int index) {
   if (c) guard_audit_harvest(c, true);
   if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
-  if (!c->has_model || !c->Fplain.p) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
-  ModelConst& mc = c->mc;
-  const int n = mc.n, d = mc.d;
-  if (index < 0 || index >= n) return fail(SBO_E_INVALID, "index out of range [0, n)");
-  if (n == 1) return fail(SBO_E_INVALID, "a model holds at least one observation");
-  SBO_HIP(hipSetDevice(c->device));
-  { const int rcf = factor_sync(c); if (rcf) return rcf; }     // (the update works on the resident factor)
-  int rc;
-  // (the fp64 twin of this model follows; a twin left behind by an earlier model takes no part)
-  const bool twin = twin_current(c);
-  if (twin && (rc = sbo_model_remove(c->recheck.shadow, index))) return rc;
-  if (twin) c->recheck.serial = Recheck::kNoSerial;
-  if ((rc = model_remove(c, index))) return rc;
-  // the derived arrays without the row (device), then the re-pack of the factor images
-  c->h_Xnorm.erase(c->h_Xnorm.begin() + (size_t)index * d, c->h_Xnorm.begin() + (size_t)(index + 1) * d);
-  mc.n = n - 1;
-  mc.npad = (mc.n + 15) / 16 * 16;
-  if ((rc = model_prep(c, c->h_Xnorm.data()))) return rc;
-  if ((rc = model_repack(c))) return rc;
-  ++c->model_serial;
-  if (twin) c->recheck.serial = c->model_serial;
-  model_changed(c);
-  return SBO_OK;
+  if (!c->has_model || !c->factor.present()) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
+  if (index < 0 || index >= c->mc.n) return fail(SBO_E_INVALID, "index out of range [0, n)");
+  if (c->mc.n == 1) return fail(SBO_E_INVALID, "a model holds at least one observation");
+  return model_update_run(c, {-1, false, index, nullptr, nullptr});
 }
 
 // Leave-one-out diagnostics of the resident model: read-only, O(n^2) on the device, O(n q) bytes back.
 int sbo_model_loo(sbo_ctx* c, double b, double* resid_out, double* var_out, sbo_model_loo_result* result) {
   if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
   if (!std::isfinite(b) || b < 0.0) return fail(SBO_E_INVALID, "b must be finite and >= 0");
-  if (!c->Fplain.p) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
   if (const int rcb = model_reader_begin(c, "sbo_model_loo", false)) return rcb;     // (the sums run over the resident factor)
   const int n = c->mc.n, q = c->mc.q;
   const unsigned char* h = nullptr;

@@ -361,7 +361,6 @@ extern "C" int sbo_batch_select(sbo_ctx* c, const sbo_batch_opts* opts, int64_t 
   if (opts->n_pending > 0 && !pending) return fail(SBO_E_INVALID, "pending is NULL");
   if (!std::isfinite(opts->min_std) || opts->min_std < 0.0) return fail(SBO_E_INVALID, "min_std must be finite and >= 0");
   int rc;
-  if (!c->Fplain.p) return fail(SBO_E_NO_MODEL, "sbo_model_set has not been called");
   if ((rc = model_reader_check(c, "sbo_batch_select", false))) return rc;        // (d and q, which the checks below need)
   const ModelConst& mc = c->mc;
   const int n = mc.n, d = mc.d, o = opts->output, k = opts->k, np = opts->n_pending;
@@ -411,7 +410,7 @@ extern "C" int sbo_batch_select(sbo_ctx* c, const sbo_batch_opts* opts, int64_t 
   SBO_HIP(hipMemcpyAsync(B.Xn, c->h_Xnorm.data(), sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, st));
   SBO_HIP(hipMemcpyAsync(B.pool, pool, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice, st));
   if (np) SBO_HIP(hipMemcpyAsync(B.pend, pending, sizeof(double) * (size_t)np * d, hipMemcpyHostToDevice, st));
-  SBO_HIP(hipMemcpy2DAsync(B.M, sizeof(double) * ld, (const double*)c->Fplain.p + (size_t)o * c->f_cap * c->f_cap, sizeof(double) * c->f_cap,
+  SBO_HIP(hipMemcpy2DAsync(B.M, sizeof(double) * ld, c->factor.F() + (size_t)o * c->factor.ld() * c->factor.ld(), sizeof(double) * c->factor.ld(),
                            sizeof(double) * n, n, hipMemcpyDeviceToDevice, st));
   rc = with_dpad(D, [&](auto DD) { return batch_enqueue<DD()>(c, A, B, m, k, np, var_out != nullptr); });
   if (rc) {

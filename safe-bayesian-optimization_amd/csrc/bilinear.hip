@@ -1475,7 +1475,7 @@ bool bilinear_applicable(const sbo_ctx* c) {
     for (int r = 0; r < c->dist.world; ++r) min_lines = std::min(min_lines, (c->dist.first_of[r + 1] - c->dist.first_of[r]) / cnt0);
   // (a caller's matrix whose factor is deferred: the band's reference runs on the matrix itself and must fit its LDS budget)
   if (c->mc.factor == SBO_FACTOR_INVK && c->opt.chol_async && c->mc.npad > kGuardRefMaxNpad) return false;
-  return cnt0 >= 64 && cs.count[1] >= 64 && min_lines >= 16 && c->alpha64.p != nullptr && c->f_cap >= c->mc.n;
+  return cnt0 >= 64 && cs.count[1] >= 64 && min_lines >= 16 && c->factor.present() && c->factor.ld() >= c->mc.n;
 }
 
 // layout of bl_basis (doubles): U [2q][kBlMaxR][n] | Vs [2q][kBlMaxR][kBlMaxRc] | sig [2q][kBlMaxR] | info (ints, 2q x 4, in
@@ -1748,8 +1748,8 @@ int bilinear_setup(sbo_ctx* c) {
   hipLaunchKernelGGL((k_cheb_tab<0>), dim3((unsigned)((nrb * 16 + 255) / 256)), dim3(256), 0, ys, dm, (const double*)dxn1, (double*)c->bl_P1A.p);
   // mean phases: Mb (forms of alpha, alpha Xn_0, alpha Xn_1) -> Vb = Mb S1 -> A images [V0 | V1;V0 | V1x], B fragments
   // [S0 | S0;-xn0 S0]
-  hipLaunchKernelGGL(k_bl_mb, blocks((size_t)3 * r0u * r1u * 64, uq), dim3(256), 0, ys, dm, dU, (const double*)c->alpha64.p,
-                     c->a_ld, (const double*)c->Xn.p, mc.dpad, dMb);
+  hipLaunchKernelGGL(k_bl_mb, blocks((size_t)3 * r0u * r1u * 64, uq), dim3(256), 0, ys, dm, dU, c->factor.alpha(),
+                     c->factor.a_ld(), (const double*)c->Xn.p, mc.dpad, dMb);
   hipLaunchKernelGGL(k_bl_vb, blocks((size_t)3 * r0u * nlines, uq), dim3(256), 0, ys, dm, (const double*)dMb, (const double*)dS1, dVb);
   hipLaunchKernelGGL(k_bl_va, blocks(g.sVA, uq), dim3(256), 0, ys, dm, (const double*)dVb, (const double*)dxn1, g.sVA,
                      (double*)c->bl_VA.p);
@@ -1834,8 +1834,8 @@ int bilinear_setup(sbo_ctx* c) {
     GbAnalytic an;
     memset(&an, 0, sizeof(an));
     an.axis_eps = bb + basis_layout(n, q).eps;
-    an.alpha = (const double*)c->alpha64.p;
-    an.a_ld = c->a_ld;
+    an.alpha = c->factor.alpha();
+    an.a_ld = c->factor.a_ld();
     an.n = n;
     for (int o = 0; o < q; ++o) { an.rc[o][0] = dm.rc0[o]; an.rc[o][1] = dm.rc1[o]; }
     an.Xn = (const double*)c->Xn.p;

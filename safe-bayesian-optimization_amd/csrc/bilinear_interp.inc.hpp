@@ -497,7 +497,7 @@ int interp_setup(sbo_ctx* c) {
   hipLaunchKernelGGL((k_bgemm<4, 0, 1>), dim3((unsigned)((ncsR + 3) / 4), (unsigned)((KBn + 3) / 4), uq), dim3(256), 0, xs,
                      (const double*)c->invk_img.p, (size_t)mc.npad * mc.npad, (const double*)Zf, nZf, KBn, KBn, ncsR, Cf, nZf, CtA, 0ll);
   hipLaunchKernelGGL(k_i_nodevals, dim3((unsigned)ncsR, uq), dim3(64), 0, xs, KBn, n, (const double*)Zf, (const double*)Cf, nZf,
-                     (const double*)c->alpha64.p, c->a_ld, ncols, V);
+                     c->factor.alpha(), c->factor.a_ld(), ncols, V);
   {
     const size_t lds = sizeof(double) * 3 * (size_t)Dn * (Dn + 1);
     SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_i_dct), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -543,7 +543,7 @@ int interp_setup(sbo_ctx* c) {
     hipLaunchKernelGGL(k_gb_probe_series, dim3((unsigned)((kGbProbes + 3) / 4), (unsigned)QP), dim3(256), 0, bs, cs, dP, (const double*)Chat,
                        (const int*)eff, (const double*)dxn0, (const double*)dxn1, raw);
     hipLaunchKernelGGL(k_gb_band_i, dim3(1), dim3(256), 0, bs, dP, (const double*)raw, (const double*)gref_m, (const double*)gref_v,
-                       (const double*)pgrad, reinterpret_cast<const double*>(eff + 4 * QP), (const double*)c->alpha64.p, c->a_ld, (GuardBand*)c->gb.buf.p,
+                       (const double*)pgrad, reinterpret_cast<const double*>(eff + 4 * QP), c->factor.alpha(), c->factor.a_ld(), (GuardBand*)c->gb.buf.p,
                        (GuardBand*)c->h_back->guard_band);
     c->gb.mirrored = true;
     if (defer) SBO_HIP(hipEventRecord(c->ev_grad[3], bs));

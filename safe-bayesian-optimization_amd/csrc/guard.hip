@@ -358,7 +358,7 @@ static int launch_ref(sbo_ctx* c, hipStream_t st, const double* pts, long long N
   auto kern = k_ref_list<D>;
   SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)groups, (unsigned)q, (unsigned)chunks), dim3(256), lds, st, mc, mcp, c->cs, pts, N, nlines,
-                     (const double*)c->As.p, (const double*)c->sqA.p, (const double*)c->alpha64.p, c->a_ld, c->invk_plain,
+                     (const double*)c->As.p, (const double*)c->sqA.p, c->factor.alpha(), c->factor.a_ld(), c->invk_plain,
                      (size_t)mc.n * mc.n, ccols, (double*)pb.p);
   hipLaunchKernelGGL(k_ref_finish, dim3((unsigned)std::max<long long>(1, std::min<long long>((N * q + 255) / 256, 1024))), dim3(256), 0, st,
                      mc, mcp, N, chunks, (const double*)pb.p, mean_out, var_out);

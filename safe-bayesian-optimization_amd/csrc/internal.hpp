@@ -418,9 +418,36 @@ struct LooSummary {
   int z_argmax, outside;
 };
 struct Loo {
-  DevBuf part;     // [q][ceil(f_cap / kLooRows)][f_cap] partial column sums of squares of the factor, one row per chunk of rows
+  DevBuf part;     // [q][ceil(ld / kLooRows)][ld] (ld: ResidentFactor::ld()) partial column sums of squares of the factor, one row per chunk of rows
   DevBuf out;      // LooSummary[kMaxQ] | resid [n][q] | var [n][q]
   Pinned h_out;    // ... and where the one copy of a call lands
+};
+
+// The resident fp64 factor of the model (model.hip): the lower factor M [q][ld][ld], row-major, with M^T M = invK, and alpha [q][a_ld]
+// -- what the K1b table build, the O(n^2) readers (refine, lipschitz, batch, guard, loo) and the three model updates work on.
+//   * Tight after a build: ld == n, a_ld == npad.  The first reserve() that has to grow it leaves a_ld == ld == the capacity (a
+//     multiple of 128, at most SBO_MAX_N), and so it stays until the next build.
+//   * Everything outside the n x n lower triangles and alpha's first n entries is zero: right of the diagonal in appended rows, and
+//     all of the padding (reserve() copies into zeroed buffers, the commit kernels write whole rows, a removal writes a zeroed spare).
+//   * The spare pair has the leading dimensions of the resident one.  A removal writes the factor without its row there and
+//     adopt_spare() swaps the pairs: the outgoing pair is the next removal's spare.
+// Readers take F() / alpha(); the mutable forms are for the kernels that build or commit an update.
+struct ResidentFactor {
+  const double *F() const { return (const double*)F_.p; }  const double *alpha() const { return (const double*)alpha_.p; }
+  double *F_mut() { return (double*)F_.p; }                double *alpha_mut() { return (double*)alpha_.p; }
+  double *spare_F() { return (double*)Fspare_.p; }         double *spare_alpha() { return (double*)aspare_.p; }
+  int ld() const { return ld_; }                           int a_ld() const { return a_ld_; }
+  bool present() const { return F_.p != nullptr && alpha_.p != nullptr; }
+  int build(int n, int npad, int q);            // tight buffers for a model build (contents: the builder's)
+  // Room for `rows` more rows.  A tight factor gets room for 256 more rows -- or for all of `rows`, if that is more --, a grown one that
+  // does not fit grows again.  The copy keeps every value and is waited for; a call refused afterwards leaves the larger capacity behind.
+  int reserve(sbo_ctx* c, int rows);
+  int spare_ensure_zeroed(sbo_ctx* c);          // the spare pair, zeroed on the main stream (enqueued)
+  void adopt_spare() { std::swap(F_.p, Fspare_.p); std::swap(F_.bytes, Fspare_.bytes); std::swap(alpha_.p, aspare_.p); std::swap(alpha_.bytes, aspare_.bytes); }
+
+ private:
+  DevBuf F_, alpha_, Fspare_, aspare_;
+  int ld_ = 0, a_ld_ = 0;
 };
 
 }  // namespace sbo
@@ -491,14 +518,10 @@ struct sbo_ctx {
   sbo::DevBuf AXg;     // grid path: alpha_j (1, Xn_j) rows in fragment-slot order [q][npad][1 + dpad]
   size_t fpk_stride = 0;  // elements per output in Fpk
   std::vector<double> h_Xnorm;   // host copies used by the exact-recheck / result decoding
-  sbo::DevBuf Fplain;            // [q][f_cap][f_cap] fp64 lower factor M, row-major (K1b table build, sbo_model_append)
-  sbo::DevBuf alpha64;           // [q][a_ld] fp64 alpha
-  int f_cap = 0;                 // leading dimension / capacity of Fplain: n after a build, n + 256.. once an append has grown it
-  int a_ld = 0;                  // stride of alpha64: npad after a build, f_cap after an append
+  sbo::ResidentFactor factor;    // the fp64 lower factor M and alpha, with the spare pair of a removal
   sbo::DevBuf mwork;             // model build workspace (uploads, fp64 copies of the derived arrays, the factorisation's scratch)
-  sbo::DevBuf appendbuf;         // sbo_model_append's uploads and scratch (apart from mwork: a refused append leaves the uploaded invK in place)
-  sbo::DevBuf Fspare, aspare;    // sbo_model_remove writes the factor / alpha without the row here ([q][f_cap][f_cap], [q][a_ld]), then swaps them in
-  sbo::DevBuf removebuf;         // sbo_model_remove's per-row coefficients [q][3 f_cap + 1]
+  sbo::DevBuf appendbuf;         // model_append_stage's / model_append_block_stage's uploads and scratch (apart from mwork: a refused append leaves the uploaded invK in place)
+  sbo::DevBuf removebuf;         // model_update_commit's per-row coefficients of a removal [q][3 factor.ld() + 1]
   sbo::Loo loo;                  // sbo_model_loo's scratch and landing area (the call reads the model and writes nothing else)
   // Caller's invK on a K1b-capable grid (option chol_async): the GEMM posterior's tables contract with invK itself -- packed
   // here as full matrix-core images, exactly the matrix of models/GP_Safe.py:341-343 -- so the reverse Cholesky factor M (needed
@@ -511,7 +534,7 @@ struct sbo_ctx {
   bool factor_todo = false;        // the chain has not been enqueued yet (sbo_model_set does that last: model_factor_enqueue)
   bool factor_pending = false;     // the factor chain of the current model is (possibly) still running; ev_factor marks its end
   hipEvent_t ev_factor = nullptr, ev_w = nullptr;
-  unsigned long long model_serial = 0;   // bumped by every sbo_model_set / sbo_model_append / sbo_model_remove
+  unsigned long long model_serial = 0;   // bumped by every sbo_model_set and by every accepted update (model_update_run: sbo_model_append, sbo_model_append_batch, sbo_model_remove)
   // K1b (bilinear.hip): the plan, its tables, and what its builders and launches keep between calls
   sbo::BilinearPlan bl;
   sbo::DevBuf bl_P0f, bl_P1A, bl_T4f, bl_BtA, bl_SBf, bl_VA, bl_small, bl_work, bl_cheb;
@@ -685,12 +708,24 @@ int fit_batch(sbo_ctx* c, int n, int d, int q, const double* X_norm, const doubl
               double ftol, double gtol, FitBatchResult& out);
 int model_factor_enqueue(sbo_ctx* c);
 int model_pack_invk(sbo_ctx* c);         // images of the caller's invK for the K1b tables, when the grid arrived after the model   // the deferred factor chain of a caller's invK, behind everything on the critical path
-int model_append_check(sbo_ctx* c, const std::vector<double>& kvec /*[q][n]*/, const double* kappa, const double* rho);
-int model_append_commit(sbo_ctx* c);   // (after model_append_check succeeded; mc.n still the old n)
-// the block form: Xall [n + k][d] the model's observations followed by the k new rows, rho [q][k] = y_norm_new - mp
-int model_append_block_check(sbo_ctx* c, int k, const std::vector<double>& Xall, const std::vector<double>& rho);
-int model_append_block_commit(sbo_ctx* c, int k);   // (after model_append_block_check succeeded; mc.n still the old n)
-int model_remove(sbo_ctx* c, int index);   // the factor and alpha without observation `index` (mc.n still the old n); enqueued, not waited for
+// An update of the resident model, staged: computed into scratch and accepted by the device, nothing of the model written yet (a grown
+// capacity keeps every value).  `rows`: +1 (one appended row), +k (a block), -1 (row `index` leaves).  The operands are what the commit
+// kernel of its kind reads (appendbuf, laid out once by the stage function); `serial` / `ld`: the model and factor it was staged against.
+struct ModelUpdate {
+  int rows = 0, index = -1, ld = 0;
+  unsigned long long serial = 0;
+  const double *rho = nullptr, *scratch = nullptr, *sk = nullptr;     // one row: k_model_append_commit
+  const double *U = nullptr, *G = nullptr, *w = nullptr;               // a block: k_append_commit
+};
+// One row (x_norm_new [d], y_norm_new [q]): the cross-covariances on the host, k_model_append, one wait for the verdict; SBO_E_INVALID
+// when an output's s <= 0.  A block (x_norm_new [k][d], y_norm_new [k][q]): the five block kernels, one wait;
+// SBO_E_INVALID when a Schur pivot is not > 0.  A removal cannot be refused on the device: its update is model_update_staged(c, -1, index).
+int model_append_stage(sbo_ctx* c, const double* x_norm_new, const double* y_norm_new, ModelUpdate& u);
+int model_append_block_stage(sbo_ctx* c, int k, const double* x_norm_new, const double* y_norm_new, ModelUpdate& u);
+ModelUpdate model_update_staged(const sbo_ctx* c, int rows, int index = -1);
+// Writes a staged update into the resident factor / alpha (enqueued, not waited for; mc.n still the old n) and drops the images of a
+// caller's invK, which follow no update.  SBO_E_INVALID when the model or its factor moved since the update was staged.
+int model_update_commit(sbo_ctx* c, const ModelUpdate& u);
 // leave-one-out diagnostics of the resident factor / alpha; waited for: *host then points at LooSummary[kMaxQ] | resid [n][q] | var [n][q]
 // (the arrays only with `arrays`)
 int model_loo(sbo_ctx* c, double b, bool arrays, const unsigned char** host);
@@ -717,8 +752,9 @@ inline void plans_invalidate(sbo_ctx* c) {
   c->posterior_valid = false;
   c->recheck.invalidate();
 }
-// sbo_model_set (before it touches the resident model) and sbo_model_append (once the new row is in place: a refused or failed append
-// leaves everything as it was).  The factor and invK flags are the model builder's own (model.hip: model_build, model_append_commit).
+// sbo_model_set (before it touches the resident model) and model_update_run (api.hip: the driver of sbo_model_append, sbo_model_append_batch
+// and sbo_model_remove, once the rows are in place: a refused or failed update leaves everything as it was).  The factor and invK flags are
+// the model builder's own (model.hip: model_build, model_update_commit).
 inline void model_changed(sbo_ctx* c) {
   c->masks_valid = false;
   c->rob.invalidate();

@@ -10,7 +10,7 @@
 // iterates go through k_mean_grad again, and the answer is the largest |g_a| over the usable seeds and those points: a value that
 // is attained, never an extrapolation of the solver's own arithmetic.
 //
-// Only alpha64 and X_norm are read: no n x n matrix, no variance, nothing resident is written.
+// Only the fp64 alpha and X_norm are read: no n x n matrix, no variance, nothing resident is written.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -375,7 +375,7 @@ __global__ __launch_bounds__(kLipThreads) void k_lipschitz(const LipArgs* __rest
 static int lip_launch_grad(sbo_ctx* c, const LipArgs* dA, const double* pts, long long N, double* grad, double* inf) {
   if (N <= 0) return SBO_OK;
   const unsigned nb = (unsigned)std::min<long long>((N + kLipThreads - 1) / kLipThreads, 8192);
-  const double *al = (const double*)c->alpha64.p, *Xn = (const double*)c->Xn.p;
+  const double *al = c->factor.alpha(), *Xn = (const double*)c->Xn.p;
   with_dpad(c->mc.dpad, [&](auto D) {
     hipLaunchKernelGGL(k_mean_grad<D()>, dim3(nb), dim3(kLipThreads), 0, c->stream, dA, al, Xn, pts, N, grad, inf);
   });
@@ -387,7 +387,7 @@ template <bool kLds>
 static int lip_launch_solver(sbo_ctx* c, size_t lds, long long P, const LipArgs* dA, double* pts, const int* pick, const double* Lseed,
                              int* use, int* nev, int* conv) {
   SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_lipschitz<kLds>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((k_lipschitz<kLds>), dim3((unsigned)P), dim3(kLipThreads), lds, c->stream, dA, (const double*)c->alpha64.p,
+  hipLaunchKernelGGL((k_lipschitz<kLds>), dim3((unsigned)P), dim3(kLipThreads), lds, c->stream, dA, c->factor.alpha(),
                      (const double*)c->Xn.p, pts, pick, Lseed, use, nev, conv);
   SBO_HIP(hipGetLastError());
   return SBO_OK;
@@ -407,7 +407,7 @@ extern "C" int sbo_mean_grad(sbo_ctx* c, int64_t n_points, const double* points,
   const size_t N = (size_t)n_points;
   LipArgs A{};
   A.mc = c->mc;
-  A.a_ld = c->a_ld;
+  A.a_ld = c->factor.a_ld();
   LipArgs* dA;
   double *dpts, *dgrad, *dinf;
   auto layout = [&](Carve cv) {
@@ -445,7 +445,7 @@ extern "C" int sbo_lipschitz(sbo_ctx* c, const sbo_lipschitz_opts* opts, int64_t
   if ((rc = model_reader_begin(c, "sbo_lipschitz", true))) return rc;
   LipArgs A{};
   A.mc = c->mc;
-  A.a_ld = c->a_ld;
+  A.a_ld = c->factor.a_ld();
   A.top = opts->top > 0 ? opts->top : kLipDefaultTop;
   A.max_eval = opts->max_eval > 0 ? opts->max_eval : kLipDefaultEval;
   A.mask = opts->output_mask ? (int)opts->output_mask : (1 << q) - 1;

@@ -1162,8 +1162,8 @@ static int factor_chain_enqueue(sbo_ctx* c, const ModelWork& w, int mode, hipStr
   const ModelConst& mc = c->mc;
   const int n = mc.n, npad = mc.npad, q = mc.q, nb = npad / 16;
   const size_t nn = (size_t)n * n;
-  double* dF = (double*)c->Fplain.p;
-  double* dalpha = (double*)c->alpha64.p;
+  double* dF = c->factor.F_mut();
+  double* dalpha = c->factor.alpha_mut();
   if (n >= kBlockedFrom) {
     // blocked multi-workgroup factorisation: the single-workgroup loop is bound by the latency of its own updates
     if (mode == 0) {
@@ -1200,7 +1200,7 @@ static int factor_chain_enqueue(sbo_ctx* c, const ModelWork& w, int mode, hipStr
 }
 
 // Device side of sbo_model_set.  host_invK may be NULL (the library factors K itself).  On success Fpk (dtype T), alpha
-// (dtype T), the derived arrays As / sqA / Xn and the fp64 factor / alpha (Fplain, alpha64: leading dimension n / npad
+// (dtype T), the derived arrays As / sqA / Xn and the fp64 factor / alpha (sbo_ctx::factor: leading dimension n / npad
 // until an append grows them) are in place.  One host synchronisation, at the end (the positive-definiteness verdict);
 // when a K1b-capable grid is resident the axis bases of the new model are built meanwhile on the second stream.
 template <typename T>
@@ -1218,11 +1218,8 @@ static int model_build_t(sbo_ctx* c, const double* const* host_invK /* q matrice
   c->factor_todo = false;
   ModelWork w;
   if ((rc = model_work(c, host_invK != nullptr, w))) return rc;
-  if ((rc = ensure(c->Fplain, sizeof(double) * (size_t)q * nn))) return rc;
-  if ((rc = ensure(c->alpha64, sizeof(double) * (size_t)q * npad))) return rc;
-  c->f_cap = n;
-  c->a_ld = npad;
-  double* dalpha = (double*)c->alpha64.p;
+  if ((rc = c->factor.build(n, npad, q))) return rc;
+  double* dalpha = c->factor.alpha_mut();
   if ((rc = model_prep_t<T>(c, X_norm, Y_norm, w))) return rc;
   bool eager_basis = false;
   // (r04) a caller's invK on a K1b-capable grid: the model's first sweep runs on interpolated node values (K1i, bilinear.hip), which
@@ -1328,16 +1325,16 @@ int model_factor_enqueue(sbo_ctx* c) {
 template <typename T>
 static int model_repack_t(sbo_ctx* c) {
   const ModelConst& mc = c->mc;
-  const int n = mc.n, npad = mc.npad, q = mc.q, nb = npad / 16, cap = c->f_cap;
+  const int n = mc.n, npad = mc.npad, q = mc.q, nb = npad / 16, cap = c->factor.ld();
   const size_t ntri = (size_t)nb * (nb + 1) / 2;
   int rc;
   c->fpk_stride = ntri * 4 * 64;
   if ((rc = ensure(c->Fpk, sizeof(T) * ((size_t)q * c->fpk_stride + 512)))) return rc;
   SBO_HIP(hipMemsetAsync(c->Fpk.p, 0, sizeof(T) * ((size_t)q * c->fpk_stride + 512), c->stream));
   hipLaunchKernelGGL((k_pack_factor<T>), dim3((unsigned)std::min<size_t>((ntri * 256 + 255) / 256, 4096), q), dim3(256), 0, c->stream,
-                     (const double*)c->Fplain.p, n, cap, (size_t)cap * cap, nb, c->fpk_stride, (T*)c->Fpk.p);
+                     c->factor.F(), n, cap, (size_t)cap * cap, nb, c->fpk_stride, (T*)c->Fpk.p);
   if ((rc = ensure(c->alpha, sizeof(T) * (size_t)q * npad))) return rc;
-  hipLaunchKernelGGL((k_cast_alpha<T>), dim3(16), dim3(256), 0, c->stream, (const double*)c->alpha64.p, c->a_ld, n, q, npad, (T*)c->alpha.p);
+  hipLaunchKernelGGL((k_cast_alpha<T>), dim3(16), dim3(256), 0, c->stream, c->factor.alpha(), c->factor.a_ld(), n, q, npad, (T*)c->alpha.p);
   SBO_HIP(hipGetLastError());
   SBO_HIP(hipStreamSynchronize(c->stream));
   return SBO_OK;
@@ -1356,12 +1353,15 @@ static size_t append_layout(Carve cv, int n, int q, int cap, AppendWork& w) {
   return cv.off;
 }
 
-// Room for `rows` more rows in the resident factor.  A freshly built model keeps its factor tight (leading dimension n): the first
-// append makes room for 256 more rows -- or for the whole block, if that is more --, a later one that does not fit grows it again.
-// The copy keeps every value; a call refused afterwards leaves the larger capacity behind.
-static int factor_reserve(sbo_ctx* c, int rows) {
+int ResidentFactor::build(int n, int npad, int q) {
+  ld_ = n, a_ld_ = npad;
+  if (const int rc = ensure(F_, sizeof(double) * (size_t)q * n * n)) return rc;
+  return ensure(alpha_, sizeof(double) * (size_t)q * npad);
+}
+
+int ResidentFactor::reserve(sbo_ctx* c, int rows) {
   const int n = c->mc.n, q = c->mc.q;
-  if (n + rows <= c->f_cap && c->a_ld == c->f_cap) return SBO_OK;
+  if (n + rows <= ld_ && a_ld_ == ld_) return SBO_OK;
   int rc;
   const int cap = std::min(SBO_MAX_N, std::max((c->mc.npad + 256 + 127) / 128 * 128, (n + rows + 127) / 128 * 128));
   if (n + rows > cap) return fail(SBO_E_UNSUPPORTED, "model is at its capacity: rebuild it with sbo_model_set");
@@ -1371,54 +1371,81 @@ static int factor_reserve(sbo_ctx* c, int rows) {
   hipError_t e = hipMemsetAsync(F2.p, 0, sizeof(double) * (size_t)q * cap * cap, c->stream);
   if (e == hipSuccess) e = hipMemsetAsync(a2.p, 0, sizeof(double) * (size_t)q * cap, c->stream);
   for (int o = 0; o < q && e == hipSuccess; ++o) {
-    e = hipMemcpy2DAsync((double*)F2.p + (size_t)o * cap * cap, sizeof(double) * cap, (const double*)c->Fplain.p + (size_t)o * c->f_cap * c->f_cap,
-                         sizeof(double) * c->f_cap, sizeof(double) * n, n, hipMemcpyDeviceToDevice, c->stream);
+    e = hipMemcpy2DAsync((double*)F2.p + (size_t)o * cap * cap, sizeof(double) * cap, F() + (size_t)o * ld_ * ld_, sizeof(double) * ld_,
+                         sizeof(double) * n, n, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess)
-      e = hipMemcpyAsync((double*)a2.p + (size_t)o * cap, (const double*)c->alpha64.p + (size_t)o * c->a_ld, sizeof(double) * n,
-                         hipMemcpyDeviceToDevice, c->stream);
+      e = hipMemcpyAsync((double*)a2.p + (size_t)o * cap, alpha() + (size_t)o * a_ld_, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return hip_fail(e, "growing the resident factor");
-  c->Fplain = std::move(F2);
-  c->alpha64 = std::move(a2);
-  c->f_cap = cap;
-  c->a_ld = cap;
+  F_ = std::move(F2);
+  alpha_ = std::move(a2);
+  ld_ = a_ld_ = cap;
   return SBO_OK;
 }
 
-// kvec [q][n] cross-covariances of the new point, kappa[q] = sf2 + sn2, rho[q] = y_norm_new - mp.  model_append_check
-// computes the update of row n into c->appendbuf and fails with SBO_E_INVALID when an output's s <= 0; nothing of the model
-// changes (growing the factor's capacity copies it and keeps its values).  model_append_commit then writes the update.
-int model_append_check(sbo_ctx* c, const std::vector<double>& kvec, const double* kappa, const double* rho) {
-  const int n = c->mc.n, q = c->mc.q;
+int ResidentFactor::spare_ensure_zeroed(sbo_ctx* c) {
+  const size_t fbytes = sizeof(double) * (size_t)c->mc.q * ld_ * ld_, abytes = sizeof(double) * (size_t)c->mc.q * a_ld_;
+  if (const int rc = ensure(Fspare_, fbytes)) return rc;
+  if (const int rc = ensure(aspare_, abytes)) return rc;
+  SBO_HIP(hipMemsetAsync(Fspare_.p, 0, fbytes, c->stream));
+  SBO_HIP(hipMemsetAsync(aspare_.p, 0, abytes, c->stream));
+  return SBO_OK;
+}
+
+// The verdict of a staged append (its one host wait): the first output whose flag in `dbad` [q] is set names the error, msg(o, flag).
+template <class Msg>
+static int append_verdict(sbo_ctx* c, const int* dbad, Msg&& msg) {
+  const int q = c->mc.q;
+  int hbad[kMaxQ] = {};
+  SBO_HIP(hipMemcpyAsync(hbad, dbad, sizeof(int) * q, hipMemcpyDeviceToHost, c->stream));
+  SBO_HIP(hipStreamSynchronize(c->stream));
+  for (int o = 0; o < q; ++o)
+    if (hbad[o]) return fail(SBO_E_INVALID, msg(o, hbad[o]));
+  return SBO_OK;
+}
+ModelUpdate model_update_staged(const sbo_ctx* c, int rows, int index) {
+  ModelUpdate u;
+  u.rows = rows, u.index = index, u.ld = c->factor.ld(), u.serial = c->model_serial;
+  return u;
+}
+
+int model_append_stage(sbo_ctx* c, const double* x_norm_new, const double* y_norm_new, ModelUpdate& u) {
+  const ModelConst& mc = c->mc;
+  const int n = mc.n, d = mc.d, q = mc.q;
+  // cross-covariances of the new point with the expanded distance of the reference (GP_Safe.py:115-119, 166)
+  std::vector<double> kvec((size_t)q * n);
+  double kappa[kMaxQ], rho[kMaxQ];
+  for (int o = 0; o < q; ++o) {
+    double bsq = 0.0, bvec[kMaxD];
+    for (int a = 0; a < d; ++a) { bvec[a] = x_norm_new[a] * mc.vinv[o][a]; bsq += bvec[a] * bvec[a]; }
+    for (int j = 0; j < n; ++j) {
+      double dot = 0.0, asq = 0.0;
+      for (int a = 0; a < d; ++a) {
+        const double v = c->h_Xnorm[(size_t)j * d + a] * mc.vinv[o][a];
+        dot += v * bvec[a];
+        asq += v * v;
+      }
+      kvec[(size_t)o * n + j] = mc.sf2[o] * std::exp(-0.5 * ((-2.0 * dot + asq) + bsq));
+    }
+    kappa[o] = mc.sf2[o] + mc.sn2[o];
+    rho[o] = y_norm_new[o] - mc.mp[o];
+  }
   int rc;
-  if ((rc = factor_reserve(c, 1))) return rc;
-  const int cap = c->f_cap;
+  if ((rc = c->factor.reserve(c, 1))) return rc;
+  const int cap = c->factor.ld();
   AppendWork w;
   if ((rc = carve(c->appendbuf, [&](Carve cv) { return append_layout(cv, n, q, cap, w); }))) return rc;
   SBO_HIP(hipMemcpyAsync(w.k, kvec.data(), sizeof(double) * (size_t)q * n, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(w.kappa, kappa, sizeof(double) * q, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(w.rho, rho, sizeof(double) * q, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemsetAsync(w.bad, 0, sizeof(int) * q, c->stream));
-  hipLaunchKernelGGL(k_model_append, dim3(q), dim3(1024), 0, c->stream, n, cap, (const double*)c->Fplain.p, (const double*)c->alpha64.p,
-                     (const double*)w.k, (const double*)w.kappa, w.scratch, w.sk, w.bad);
+  hipLaunchKernelGGL(k_model_append, dim3(q), dim3(1024), 0, c->stream, n, cap, c->factor.F(), c->factor.alpha(), (const double*)w.k,
+                     (const double*)w.kappa, w.scratch, w.sk, w.bad);
   SBO_HIP(hipGetLastError());
-  std::vector<int> hbad(q, 0);
-  SBO_HIP(hipMemcpyAsync(hbad.data(), w.bad, sizeof(int) * q, hipMemcpyDeviceToHost, c->stream));
-  SBO_HIP(hipStreamSynchronize(c->stream));
-  for (int o = 0; o < q; ++o)
-    if (hbad[o]) return fail(SBO_E_INVALID, "appended observation makes K singular (duplicate point without noise?)");
-  return SBO_OK;
-}
-int model_append_commit(sbo_ctx* c) {
-  const int n = c->mc.n, q = c->mc.q, cap = c->f_cap;
-  AppendWork w;                                                  // (as model_append_check laid it out)
-  append_layout(Carve{(unsigned char*)c->appendbuf.p}, n, q, cap, w);
-  hipLaunchKernelGGL(k_model_append_commit, dim3(q), dim3(1024), 0, c->stream, n, cap, (double*)c->Fplain.p, (double*)c->alpha64.p,
-                     (const double*)w.rho, (const double*)w.scratch, (const double*)w.sk);
-  SBO_HIP(hipGetLastError());
-  c->invk_img_valid = false;                                    // (the images of the caller's invK do not follow an append)
-  c->invk_w_valid = false;
+  if ((rc = append_verdict(c, w.bad, [](int, int) { return "appended observation makes K singular (duplicate point without noise?)"; }))) return rc;
+  u = model_update_staged(c, 1);
+  u.rho = w.rho; u.scratch = w.scratch; u.sk = w.sk;
   return SBO_OK;
 }
 
@@ -1439,25 +1466,23 @@ static size_t append_block_layout(Carve cv, int n, int d, int q, int k, int kp, 
 }
 static inline int append_block_kp(int k) { return (k + kAppColBlock - 1) / kAppColBlock * kAppColBlock; }
 
-// The block update of rows n .. n + k - 1 computed into c->appendbuf: Xall holds the observations of the model followed by the k new
-// rows (normalised, fp64), rho [q][k] = y_norm_new - mp.  One host wait, for the verdict: SBO_E_INVALID when a Schur pivot of some
-// output is not > 0.  Nothing of the model changes (growing the factor's capacity copies it and keeps its values);
-// model_append_block_commit then writes the update.
-int model_append_block_check(sbo_ctx* c, int k, const std::vector<double>& Xall, const std::vector<double>& rho) {
+// Rows n .. n + k - 1: Xall holds the model's observations followed by the k new rows (normalised, fp64), rho [q][kp] = y_norm_new - mp.
+int model_append_block_stage(sbo_ctx* c, int k, const double* x_norm_new, const double* y_norm_new, ModelUpdate& u) {
   const ModelConst& mc = c->mc;
   const int n = mc.n, d = mc.d, q = mc.q, kp = append_block_kp(k);
   int rc;
-  if ((rc = factor_reserve(c, k))) return rc;
-  const int cap = c->f_cap;
+  if ((rc = c->factor.reserve(c, k))) return rc;
+  const int cap = c->factor.ld();
   AppendBlockWork w;
   if ((rc = carve(c->appendbuf, [&](Carve cv) { return append_block_layout(cv, n, d, q, k, kp, w); }))) return rc;
   std::vector<double> hrho((size_t)q * kp, 0.0);
   for (int o = 0; o < q; ++o)
-    for (int r = 0; r < k; ++r) hrho[(size_t)o * kp + r] = rho[(size_t)o * k + r];
-  SBO_HIP(hipMemcpyAsync(w.Xall, Xall.data(), sizeof(double) * (size_t)(n + k) * d, hipMemcpyHostToDevice, c->stream));
+    for (int r = 0; r < k; ++r) hrho[(size_t)o * kp + r] = y_norm_new[(size_t)r * q + o] - mc.mp[o];
+  SBO_HIP(hipMemcpyAsync(w.Xall, c->h_Xnorm.data(), sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, c->stream));
+  SBO_HIP(hipMemcpyAsync(w.Xall + (size_t)n * d, x_norm_new, sizeof(double) * (size_t)k * d, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemcpyAsync(w.rho, hrho.data(), sizeof(double) * (size_t)q * kp, hipMemcpyHostToDevice, c->stream));
   SBO_HIP(hipMemsetAsync(w.bad, 0, sizeof(int) * q, c->stream));
-  const double* dF = (const double*)c->Fplain.p;
+  const double* dF = c->factor.F();
   const long long cells = (long long)(n + kp) * kp;
   with_dpad(mc.dpad, [&](auto D) {
     hipLaunchKernelGGL((k_append_cross<D()>), dim3((unsigned)std::min<long long>((cells + 255) / 256, 1024), q), dim3(256), 0, c->stream, mc, n, k,
@@ -1467,56 +1492,44 @@ int model_append_block_check(sbo_ctx* c, int k, const std::vector<double>& Xall,
                      n, cap, kp, dF, (const double*)w.B, w.T);
   hipLaunchKernelGGL(k_append_u, dim3((unsigned)((n + 63) / 64), (unsigned)(kp / kAppColBlock), q), dim3(64), 0, c->stream, n, cap, kp, dF,
                      (const double*)w.T, w.U);
-  hipLaunchKernelGGL(k_append_s, dim3((unsigned)(kp / kAppSRows + 1), q), dim3(64), 0, c->stream, n, c->a_ld, kp, (const double*)w.B,
-                     (const double*)w.U, (const double*)w.Z, (const double*)c->alpha64.p, w.S, w.g);
+  hipLaunchKernelGGL(k_append_s, dim3((unsigned)(kp / kAppSRows + 1), q), dim3(64), 0, c->stream, n, c->factor.a_ld(), kp, (const double*)w.B,
+                     (const double*)w.U, (const double*)w.Z, c->factor.alpha(), w.S, w.g);
   hipLaunchKernelGGL(k_append_chol, dim3(q), dim3(256), 0, c->stream, k, kp, (const double*)w.S, (const double*)w.g, (const double*)w.rho, w.G,
                      w.w, w.bad);
   SBO_HIP(hipGetLastError());
-  std::vector<int> hbad(q, 0);
-  SBO_HIP(hipMemcpyAsync(hbad.data(), w.bad, sizeof(int) * q, hipMemcpyDeviceToHost, c->stream));
-  SBO_HIP(hipStreamSynchronize(c->stream));
-  for (int o = 0; o < q; ++o)
-    if (hbad[o])
-      return fail(SBO_E_INVALID, "appended block makes K singular: output " + std::to_string(o) + ", row " + std::to_string(hbad[o] - 1) +
-                                     " of the block has a Schur pivot that is not > 0 (duplicate point without noise?)");
-  return SBO_OK;
-}
-int model_append_block_commit(sbo_ctx* c, int k) {
-  const ModelConst& mc = c->mc;
-  const int n = mc.n, q = mc.q, cap = c->f_cap, kp = append_block_kp(k);
-  AppendBlockWork w;                                             // (as model_append_block_check laid it out)
-  append_block_layout(Carve{(unsigned char*)c->appendbuf.p}, n, mc.d, q, k, kp, w);
-  hipLaunchKernelGGL(k_append_commit, dim3((unsigned)((cap + 63) / 64), q), dim3(64), 0, c->stream, n, cap, c->a_ld, k, kp, (double*)c->Fplain.p,
-                     (double*)c->alpha64.p, (const double*)w.U, (const double*)w.G, (const double*)w.w);
-  SBO_HIP(hipGetLastError());
-  c->invk_img_valid = false;                                    // (the images of the caller's invK do not follow an append)
-  c->invk_w_valid = false;
+  rc = append_verdict(c, w.bad, [](int o, int flag) {
+    return "appended block makes K singular: output " + std::to_string(o) + ", row " + std::to_string(flag - 1) +
+           " of the block has a Schur pivot that is not > 0 (duplicate point without noise?)";
+  });
+  if (rc) return rc;
+  u = model_update_staged(c, k);
+  u.U = w.U; u.G = w.G; u.w = w.w;
   return SBO_OK;
 }
 
-// The factor and alpha without observation j, written into the spare pair (same leading dimensions, zeroed first: the padding
-// and everything right of the diagonal stay zero) and swapped in once every launch has been accepted -- until then nothing of
-// the model has changed.  The outgoing pair is the next call's spare.
-int model_remove(sbo_ctx* c, int j) {
-  const int n = c->mc.n, q = c->mc.q, cap = c->f_cap, a_ld = c->a_ld;
-  const size_t fbytes = sizeof(double) * (size_t)q * cap * cap, abytes = sizeof(double) * (size_t)q * a_ld;
-  int rc;
-  if ((rc = ensure(c->Fspare, fbytes))) return rc;
-  if ((rc = ensure(c->aspare, abytes))) return rc;
-  if ((rc = ensure(c->removebuf, sizeof(double) * (size_t)q * (3 * (size_t)cap + 1)))) return rc;
-  SBO_HIP(hipMemsetAsync(c->Fspare.p, 0, fbytes, c->stream));
-  SBO_HIP(hipMemsetAsync(c->aspare.p, 0, abytes, c->stream));
-  hipLaunchKernelGGL(k_model_remove_coef, dim3(q), dim3(256), 0, c->stream, n, cap, a_ld, j, (const double*)c->Fplain.p,
-                     (const double*)c->alpha64.p, (double*)c->removebuf.p);
-  hipLaunchKernelGGL(k_model_remove, dim3((unsigned)((n - 1 + kRemoveStrip - 1) / kRemoveStrip), q), dim3(64), 0, c->stream, n, cap, a_ld, j,
-                     (const double*)c->Fplain.p, (const double*)c->alpha64.p, (const double*)c->removebuf.p, (double*)c->Fspare.p,
-                     (double*)c->aspare.p);
+// A removal writes the factor and alpha without observation `index` into the zeroed spare pair (the padding and everything right of the
+// diagonal stay zero), which is adopted once every launch has been accepted -- until then nothing of the model has changed.
+int model_update_commit(sbo_ctx* c, const ModelUpdate& u) {
+  ResidentFactor& f = c->factor;
+  if (u.serial != c->model_serial || u.ld != f.ld() || u.rows == 0)
+    return fail(SBO_E_INVALID, "internal: the model changed between the staging of an update and its commit");
+  const int n = c->mc.n, q = c->mc.q, cap = f.ld(), a_ld = f.a_ld();
+  if (u.rows < 0) {
+    if (const int rc = f.spare_ensure_zeroed(c)) return rc;
+    if (const int rc = ensure(c->removebuf, sizeof(double) * (size_t)q * (3 * (size_t)cap + 1))) return rc;
+    hipLaunchKernelGGL(k_model_remove_coef, dim3(q), dim3(256), 0, c->stream, n, cap, a_ld, u.index, f.F(), f.alpha(), (double*)c->removebuf.p);
+    hipLaunchKernelGGL(k_model_remove, dim3((unsigned)((n - 1 + kRemoveStrip - 1) / kRemoveStrip), q), dim3(64), 0, c->stream, n, cap, a_ld,
+                       u.index, f.F(), f.alpha(), (const double*)c->removebuf.p, f.spare_F(), f.spare_alpha());
+  } else if (u.U) {
+    const int k = u.rows, kp = append_block_kp(k);
+    hipLaunchKernelGGL(k_append_commit, dim3((unsigned)((cap + 63) / 64), q), dim3(64), 0, c->stream, n, cap, a_ld, k, kp, f.F_mut(), f.alpha_mut(),
+                       u.U, u.G, u.w);
+  } else {
+    hipLaunchKernelGGL(k_model_append_commit, dim3(q), dim3(1024), 0, c->stream, n, cap, f.F_mut(), f.alpha_mut(), u.rho, u.scratch, u.sk);
+  }
   SBO_HIP(hipGetLastError());
-  std::swap(c->Fplain.p, c->Fspare.p);
-  std::swap(c->Fplain.bytes, c->Fspare.bytes);
-  std::swap(c->alpha64.p, c->aspare.p);
-  std::swap(c->alpha64.bytes, c->aspare.bytes);
-  c->invk_img_valid = false;                                    // (the images of the caller's invK do not follow a removal)
+  if (u.rows < 0) f.adopt_spare();
+  c->invk_img_valid = false;                                   // (the images of the caller's invK follow no update)
   c->invk_w_valid = false;
   return SBO_OK;
 }
@@ -1524,7 +1537,7 @@ int model_remove(sbo_ctx* c, int j) {
 // sbo_model_loo's device side: the two launches, one copy into the pinned landing area, one wait.  Nothing of the model, the plans
 // or the caches is written; the scratch is kept for the next call (a grown factor grows it).
 int model_loo(sbo_ctx* c, double b, bool arrays, const unsigned char** host) {
-  const int n = c->mc.n, q = c->mc.q, cap = c->f_cap, a_ld = c->a_ld;
+  const int n = c->mc.n, q = c->mc.q, cap = c->factor.ld(), a_ld = c->factor.a_ld();
   const int chunks = (n + kLooRows - 1) / kLooRows, strips = (n + kLooStrip - 1) / kLooStrip;
   const size_t head = sizeof(LooSummary) * kMaxQ, nq = sizeof(double) * (size_t)n * q;
   const size_t bytes = head + (arrays ? 2 * nq : 0);
@@ -1539,9 +1552,9 @@ int model_loo(sbo_ctx* c, double b, bool arrays, const unsigned char** host) {
   }
   unsigned char* dout = (unsigned char*)c->loo.out.p;
   hipLaunchKernelGGL(k_model_loo_colsq, dim3((unsigned)strips, (unsigned)chunks, (unsigned)q), dim3(64), 0, c->stream, n, cap, chunks,
-                     (const double*)c->Fplain.p, (double*)c->loo.part.p);
-  hipLaunchKernelGGL(k_model_loo_finish, dim3(q), dim3(1024), 0, c->stream, n, q, cap, a_ld, chunks, b, (const double*)c->Fplain.p,
-                     (const double*)c->alpha64.p, (const double*)c->loo.part.p, arrays ? (double*)(dout + head) : (double*)nullptr,
+                     c->factor.F(), (double*)c->loo.part.p);
+  hipLaunchKernelGGL(k_model_loo_finish, dim3(q), dim3(1024), 0, c->stream, n, q, cap, a_ld, chunks, b, c->factor.F(),
+                     c->factor.alpha(), (const double*)c->loo.part.p, arrays ? (double*)(dout + head) : (double*)nullptr,
                      arrays ? (double*)(dout + head + nq) : (double*)nullptr, (LooSummary*)dout);
   SBO_HIP(hipGetLastError());
   SBO_HIP(hipMemcpyAsync(c->loo.h_out.p, dout, bytes, hipMemcpyDeviceToHost, c->stream));

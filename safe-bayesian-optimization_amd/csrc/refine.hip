@@ -70,7 +70,7 @@ enum { REF_PH_START = 0, REF_PH_SEARCH = 1 };
 // (ball-limited) box
 __device__ __forceinline__ PbfgsBox ref_box(const RefState& S, const RefineArgs& A) { return {A.lo, A.hi, S.D2, S.span, 0.1}; }
 
-// the LDS tier's copy of M: the used outputs' lower triangles out of Fplain, packed row after row (one wave per row) -> Ml
+// the LDS tier's copy of M: the used outputs' lower triangles out of the resident factor, packed row after row (one wave per row) -> Ml
 __device__ __forceinline__ void ref_load_M(const RefineArgs& A, const double* F, double* Ml) {
   const int n = A.mc.n, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   const size_t tri = (size_t)n * (n + 1) / 2;
@@ -82,7 +82,7 @@ __device__ __forceinline__ void ref_load_M(const RefineArgs& A, const double* F,
 }
 
 // mean / var and their gradients at the kP points of x (LDS, point p at x + p d) for every used output -> E[p].  M rows: LDS
-// packed triangles (kLds) or Fplain (stride f_cap); every element of M is read once per pass and serves the kP points (kv / uv
+// packed triangles (kLds) or the resident factor (stride f_cap); every element of M is read once per pass and serves the kP points (kv / uv
 // [kP][n], red [kP][2 (kMaxD + 1)], uup [kP][kRefWaves]).  Each point's sums run in the order of a one-point evaluation.
 template <bool kLds, int kP>
 __device__ void ref_eval(const RefineArgs& A, const double* x, const double* F, const double* Ml, const double* alpha,
@@ -566,8 +566,8 @@ static size_t refine_lds_bytes(const sbo_ctx* c, int tris, int pts, size_t extra
 // the model's constants and leading dimensions, and the tolerance (<= 0: the default), of a problem on c's model
 static void refine_fill(const sbo_ctx* c, double tol, RefineArgs& A) {
   A.mc = c->mc;
-  A.f_cap = c->f_cap;
-  A.a_ld = c->a_ld;
+  A.f_cap = c->factor.ld();
+  A.a_ld = c->factor.a_ld();
   A.tol = tol > 0.0 ? tol : kRefDefaultTol;
 }
 
@@ -587,8 +587,8 @@ template <bool kLds, int kP>
 static int refine_launch(sbo_ctx* c, size_t lds, int threads, long long S, const RefineArgs* dA, const double* dseed, const double* m0,
                          const double* v0, double* cand, int* dst, int* dnev) {
   SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_refine<kLds, kP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((k_refine<kLds, kP>), dim3((unsigned)S), dim3(threads), lds, c->stream, dA, (const double*)c->Fplain.p,
-                     (const double*)c->alpha64.p, (const double*)c->Xn.p, dseed, m0, v0, S, cand, dst, dnev);
+  hipLaunchKernelGGL((k_refine<kLds, kP>), dim3((unsigned)S), dim3(threads), lds, c->stream, dA, c->factor.F(),
+                     c->factor.alpha(), (const double*)c->Xn.p, dseed, m0, v0, S, cand, dst, dnev);
   SBO_HIP(hipGetLastError());
   return SBO_OK;
 }
@@ -600,7 +600,7 @@ static int refine_run(sbo_ctx* c, RefineArgs& A, int max_eval, double tol, long 
   const ModelConst& mc = c->mc;
   const int q = mc.q, np = A.np, nz = A.nz;
   int rc;
-  if ((rc = model_reader_begin(c, "sbo_refine", true))) return rc;   // (Fplain may still be in the making: the deferred factor chain)
+  if ((rc = model_reader_begin(c, "sbo_refine", true))) return rc;   // (the fp64 factor may still be in the making: the deferred factor chain)
   refine_fill(c, tol, A);
   A.max_eval = max_eval > 0 ? std::min(max_eval, refine_eval_cap(mc.n)) : kRefDefaultEval;
   // scratch: the arguments | seeds [S][nz] | mean0 var0 [q][np S] | cand [2 S][nz] | mean1 var1 [q][2 np S] | x_out [S][nz] | val [S] |
@@ -1082,8 +1082,8 @@ __global__ __launch_bounds__(256) void k_rob_final(const RobustArgs* __restrict_
 template <bool kLds>
 static int robust_outer_launch(sbo_ctx* c, size_t lds, int threads, const RobustArgs* dR, RobustCtl* ctl) {
   SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_refine_robust<kLds>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((k_refine_robust<kLds>), dim3(1), dim3(threads), lds, c->stream, dR, (const double*)c->Fplain.p,
-                     (const double*)c->alpha64.p, (const double*)c->Xn.p, ctl);
+  hipLaunchKernelGGL((k_refine_robust<kLds>), dim3(1), dim3(threads), lds, c->stream, dR, c->factor.F(),
+                     c->factor.alpha(), (const double*)c->Xn.p, ctl);
   SBO_HIP(hipGetLastError());
   return SBO_OK;
 }

@@ -193,8 +193,7 @@ class SweepEngine:
         if x.shape != (self.d,) or y.shape != (self.q,):
             raise ValueError("x_norm_new must be [d] and y_norm_new [q]")
         L.check(self._lib.sbo_model_append(self._ctx, _ptr(x), _ptr(y)))
-        self.n += 1
-        self._obs = (np.vstack([self._obs[0], x]),) + self._obs[1:]
+        self._rows_changed(1, np.vstack([self._obs[0], x]))
 
     def append_samples(self, X_norm_new, Y_norm_new):
         """k observations in one block update (``sbo_model_append_batch``): ``X_norm_new`` [k, d] and
@@ -212,8 +211,7 @@ class SweepEngine:
         if not (np.all(np.isfinite(X)) and np.all(np.isfinite(Y))):
             raise ValueError("X_norm_new and Y_norm_new must be finite")
         L.check(self._lib.sbo_model_append_batch(self._ctx, k, _ptr(X), _ptr(Y)))
-        self.n += k
-        self._obs = (np.vstack([self._obs[0], X]),) + self._obs[1:]
+        self._rows_changed(k, np.vstack([self._obs[0], X]))
 
     def remove_sample(self, index: int):
         """The counterpart of ``append_sample`` (``sbo_model_remove``): observation ``index`` (0-based, in the order of ``X_norm``
@@ -224,8 +222,12 @@ class SweepEngine:
         if self.n and not 0 <= index < self.n:          # (without a model the library answers: SBO_E_NO_MODEL)
             raise ValueError(f"index {int(index)} out of range [0, {self.n})")
         L.check(self._lib.sbo_model_remove(self._ctx, int(index)))
-        self.n -= 1
-        self._obs = (np.delete(self._obs[0], int(index), axis=0),) + self._obs[1:]
+        self._rows_changed(-1, np.delete(self._obs[0], int(index), axis=0))
+
+    def _rows_changed(self, dn, new_obs0):
+        """Behind an accepted append, block append or removal: the row count and the observations follow the resident model."""
+        self.n += dn
+        self._obs = (new_obs0,) + self._obs[1:]
 
     def model_loo(self, b: float = 3.0, Y_norm=None) -> dict:
         """Leave-one-out diagnostics of the resident model (``sbo_model_loo``), normalised units, fp64 whatever the model dtype:

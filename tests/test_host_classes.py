@@ -124,6 +124,111 @@ def test_infnorm_mean_grad_matches_oracle():
             assert m.infnorm_mean_grad(pts[p], i) == pytest.approx(want[p, i], rel=1e-10)
 
 
+# --------------------------------------------------------------------------------------- host state across the update helpers
+HOST_FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "model_updates", "host_classes_before_helpers.npz")
+
+
+class _Recorder:
+    """In the engine's place: records the calls; model_loo answers with zeros (the device side is not under test here)."""
+
+    def __init__(self):
+        self.calls = []
+
+    def append_sample(self, xn, yn):
+        self.calls.append(1)
+
+    def append_samples(self, xn, yn):
+        self.calls.append(100 + xn.shape[0])
+
+    def remove_sample(self, index):
+        self.calls.append(-1 - index)
+
+    def model_loo(self, b, Y_norm):
+        self.calls.append(0)
+        n, q = Y_norm.shape
+        z = np.zeros(q)
+        return {"resid": np.zeros((n, q)), "var": np.ones((n, q)), "z": np.zeros((n, q)), "logdet": z, "lpd": z, "z_max": z,
+                "z_argmax": z.astype(np.int64), "outside": z.astype(np.int64), "nll": z}
+
+
+def _new_rows(m, k):
+    X = np.array([1.4, -0.8]) + 0.25 * np.random.default_rng(5).uniform(-1, 1, size=(k, 2))
+    return X, np.array([m.calculate_plant_outputs(x) for x in X])
+
+
+HOST_UPDATES = {
+    "add_sample_default": lambda m, X, Y: m.add_sample(X[0], Y[0]),
+    "add_sample_incremental": lambda m, X, Y: m.add_sample(X[0], Y[0], incremental=True),
+    "add_sample_window": lambda m, X, Y: m.add_sample(X[0], Y[0], incremental=True, window=9),
+    "add_sample_refit_true": lambda m, X, Y: m.add_sample(X[0], Y[0], incremental=True, refit_when=lambda loo: True),
+    "add_sample_refit_false": lambda m, X, Y: m.add_sample(X[0], Y[0], incremental=True, refit_when=lambda loo: False),
+    "add_samples_incremental": lambda m, X, Y: m.add_samples(X, Y),
+    "add_samples_default": lambda m, X, Y: m.add_samples(X, Y, incremental=False),
+    "add_samples_window": lambda m, X, Y: m.add_samples(X, Y, window=11),
+    "add_samples_refit_true": lambda m, X, Y: m.add_samples(X, Y, refit_when=lambda loo: True),
+    "add_samples_refit_false": lambda m, X, Y: m.add_samples(X, Y, window=12, refit_when=lambda loo: False),
+    "remove_sample_first": lambda m, X, Y: m.remove_sample(0),
+    "remove_sample_middle": lambda m, X, Y: m.remove_sample(4),
+    "remove_then_add_samples": lambda m, X, Y: (m.remove_sample(9), m.add_samples(X, Y), m.add_sample(X[1], Y[1], incremental=True)),
+    "error_add_sample_refit_default": lambda m, X, Y: m.add_sample(X[0], Y[0], refit_when=lambda loo: True),
+    "error_add_sample_refit_callable": lambda m, X, Y: m.add_sample(X[0], Y[0], incremental=True, refit_when=3),
+    "error_add_sample_window_default": lambda m, X, Y: m.add_sample(X[0], Y[0], window=5),
+    "error_add_sample_window_zero": lambda m, X, Y: m.add_sample(X[0], Y[0], incremental=True, window=0),
+    "error_add_sample_window_bool": lambda m, X, Y: m.add_sample(X[0], Y[0], incremental=True, window=True),
+    "error_add_samples_shape": lambda m, X, Y: m.add_samples(X[:, :1], Y),
+    "error_add_samples_empty": lambda m, X, Y: m.add_samples(X[:0], Y[:0]),
+    "error_add_samples_finite": lambda m, X, Y: m.add_samples(X * np.inf, Y),
+    "error_add_samples_refit_default": lambda m, X, Y: m.add_samples(X, Y, incremental=False, refit_when=lambda loo: True),
+    "error_add_samples_refit_callable": lambda m, X, Y: m.add_samples(X, Y, refit_when="no"),
+    "error_add_samples_window_default": lambda m, X, Y: m.add_samples(X, Y, incremental=False, window=20),
+    "error_add_samples_window_float": lambda m, X, Y: m.add_samples(X, Y, window=2.5),
+    "error_add_samples_window_small": lambda m, X, Y: m.add_samples(X, Y, window=3),
+    "error_remove_sample_range": lambda m, X, Y: m.remove_sample(10),
+    "error_remove_sample_bool": lambda m, X, Y: m.remove_sample(True),
+}
+
+
+def host_update_state(name):
+    """What one update leaves on the host: a 10-row SafeOpt.BO model under fixed hyper-parameters and a fixed seed, the engine a stub."""
+    m = _init(SafeOpt.BO, n=10)
+    m._engine = _Recorder()
+    m._uploaded_version = m._model_version
+    X, Y = _new_rows(m, 3)
+    text = ""
+    try:
+        HOST_UPDATES[name](m, X, Y)
+    except ValueError as e:
+        text = str(e)
+    assert bool(text) == name.startswith("error_"), (name, text)
+    ds = m.inference_datasets
+    assert ds["X_norm"] is m.X_norm and ds["Y_norm"] is m.Y_norm and ds["invKopt"] is m.invKopt
+    return {"invKopt": np.stack([np.asarray(a) for a in ds["invKopt"]]), "X_norm": ds["X_norm"], "Y_norm": ds["Y_norm"], "X": m.X, "Y": m.Y,
+            "versions": np.array([m._model_version, m._uploaded_version, m.n_point]), "calls": np.array(m._engine.calls, dtype=np.int64),
+            "error": np.frombuffer(text.encode(), dtype=np.uint8)}
+
+
+def test_a_model_of_one_row_refuses_its_removal():
+    m = _init(SafeOpt.BO, n=10)
+    m._engine = _Recorder()
+    m._uploaded_version = m._model_version
+    for _ in range(9):
+        m.remove_sample(0)
+    with pytest.raises(ValueError, match="^a model holds at least one observation$"):
+        m.remove_sample(0)
+
+
+@pytest.mark.parametrize("name", list(HOST_UPDATES))
+def test_host_updates_leave_what_they_left_before_the_helpers(name):
+    """add_sample, add_samples and remove_sample -- incremental and not, with a window, with a refit_when that says yes and no -- leave
+    invKopt, X_norm, Y_norm, the versions, the engine's calls and every ValueError text byte for byte as the commit before
+    _check_incremental_args / _refit / _device_followed / _carry_lazy left them (tests/golden/model_updates/record.py --host)."""
+    z = np.load(HOST_FIXTURE)
+    got = host_update_state(name)
+    for k, a in got.items():
+        want = z[f"{name}/{k}"]
+        assert a.dtype == want.dtype and a.shape == want.shape and a.tobytes() == want.tobytes(), (name, k)
+
+
 # ------------------------------------------------------------------------------------------------------------ device
 @pytest.mark.gpu
 @pytest.mark.parametrize("cls", [SafeOpt.BO, GoOSE.BO])
