@@ -680,7 +680,7 @@ __global__ __launch_bounds__(128) void k_bl_enclose(const double* __restrict__ m
 // Lipschitz row and slot (tile mod kColSlots) depend on the tile alone, and every merge into the slot block and into Usum is an
 // integer add, an OR, or a min / max of ordered keys.
 // The counters are zero when this kernel starts: k_bl_sched_list2, which follows the constraint's launch in every sweep that runs
-// this kernel, resets them once the list is dead (ColPath::sched_clean).  Usum is zero as well (col_words_prepare, k_col_decide), as
+// this kernel, resets them once the list is dead (sbo_ctx::bl_sched, a ResetBuf).  Usum is zero as well (col_words_prepare, k_col_decide), as
 // the launch over the whole tile grid needs it; the listed tiles OR their bits in behind.
 // The slot block: one atomic per scalar and tile -- config H's 3900 on the twelve cache lines of three fields -- took 4 of the kernel's
 // 10.5 us; the kSchedWaves tiles of a workgroup are merged in LDS first and join one slot (sums and a maximum: the slot does not
@@ -1251,243 +1251,316 @@ static bool col_words_ok(const sbo_ctx* c, const PostRequest& req, long long cnt
   const long long tiles = (cnt0 / 128) * (nlines / 64);
   return shape && (c->opt.col_path == 2 || tiles >= 4ll * c->n_cu);
 }
+static_assert(kFuseRmax + 1 == kColRowRmax1, "ColPartRows::tumax is the radius key of constraint 1");
+
+// ---- launch_posterior_gemm: the GEMM posterior on the operands of a plan -- K1i's when `interp`, else K1b's: stage 1, the k_bpost launches
+// and the Lipschitz tail.  Only K1i has the deferred gradient launch (k_bgrad on stream3); only K1b the column path's enclosures and tile
+// lists (r06, r07).  A driver over the steps below, which hand each other a GemmLaunch; what is enqueued, with which arguments, on which
+// stream and in which order does not depend on how the steps are cut.
+struct GemmLaunch {
+  sbo_ctx* c;
+  bool interp;
+  const PostRequest& req;
+  PostOutcome& out;
+  const GemmOps& g;
+  int q;
+  long long cnt0, nlines;
+  bool defer;                 // K1i: the posterior launches write their -- empty -- Lipschitz rows behind the real ones, which the gradient launch fills
+  bool run_stage1;
+  unsigned gx = 0, gy = 0, rows_out = 0;      // the tile grid; partial rows per output: one per workgroup
+  size_t lds = 0, ntiles = 0;
+  bool fuse = false, colw = false;            // classification as S / U bytes | as column words (never both)
+  PostExtra px;
+  double* encl = nullptr;                     // column path, K1b: the plan's enclosures; this launch records them | a lean-2 launch uses them (px.encl)
+  bool record_encl = false;
+  unsigned int *sched_l1 = nullptr, *sched_l2 = nullptr;      // the tile lists of the constraint's launch (kTlistShards shards of sched_cap1) and the objective's
+  int sched_cap1 = 0;
+  const GuardBand* gb_fused = nullptr;        // the fused classification counts its sign tests inside the plan's guard band
+  double* lrows = nullptr;
+};
+
+// stage 1: Bt = P1^T T4qq^T, written as the packed A operand of stage 2 (three strips per workgroup measured best on
+// config B: 27.7 us against 28.8 with two and 31.3 with four; the per-wave k_bgemm<2, 0, 0> took 32.6)
+static void gemm_stage1(const GemmLaunch& L) {
+  constexpr int S1 = 3;
+  sbo_ctx* c = L.c;
+  const GemmOps& g = L.g;
+  const dim3 grid((unsigned)((g.KB0 + S1 - 1) / S1), (unsigned)((g.nrb + 3) / 4), (unsigned)(g.sets * L.q));
+  if (L.defer)
+    hipExtLaunchKernelGGL((k_bstage1<S1>), grid, dim3(256), 0, c->stream, nullptr, c->ev_grad[1], 0, (const double*)c->bl_P1A.p, g.sP1A,
+                          (const double*)c->bl_T4f.p, g.sT4f, g.KB1, g.nrb, g.KB0, g.BtA, g.sBt1, (const int*)g.eff);
+  else
+    hipLaunchKernelGGL((k_bstage1<S1>), grid, dim3(256), 0, c->stream, (const double*)c->bl_P1A.p, g.sP1A, (const double*)c->bl_T4f.p,
+                       g.sT4f, g.KB1, g.nrb, g.KB0, g.BtA, g.sBt1, (const int*)g.eff);
+}
+
+// stage 2 (fused): variance, mean, Lipschitz keys.  64 x 128 tiles (k_bpost<1>, three workgroups per CU): with the Chebyshev
+// core the variance phase is ~12 k-steps and no longer dominates, and the third workgroup per CU is worth more than the
+// B-fragment reuse of a 128 x 128 tile (r03: config B 0.204 -> 0.189 ms per sweep, H 0.547 -> 0.543)
+static int gemm_shape(GemmLaunch& L) {
+  L.gx = (unsigned)((L.g.ncs0 + 7) / 8);
+  L.gy = (unsigned)((L.g.nrb + 3) / 4);
+  L.rows_out = L.gx * L.gy;
+  L.ntiles = (size_t)L.gx * L.gy;
+  L.lds = sizeof(double) * 2 * 3072 + 2048;
+  return ensure(L.c->bl_lpart, sizeof(double) * (size_t)L.rows_out * L.q * (L.interp ? 2 : 1));
+}
+
+// What the launch classifies, and into what: S / U bytes (`fuse`), column words (`colw`) or nothing; the rows of cpart either form
+// writes, and the stride of the byte planes of several constraints.
+// A sweep may ask for the S / U bytes, |S|, |U| and the radius key straight from the mean epilogue of the constraint
+// (one-constraint models; the masks are allocated by the sweep before it enqueues the posterior)
+// (r03: with the sqrt-free sign tests the fused epilogue saves the separate pass 76 us on config H and costs the GEMM 36;
+// on config B, two workgroups per CU, the two cancel -- "auto" asks for at least four workgroups per CU)
+static int gemm_classify_plan(GemmLaunch& L) {
+  sbo_ctx* c = L.c;
+  const CandSpec& cs = c->cs;
+  const int q = L.q;
+  const bool fuse_wanted = L.req.fuse == 1 || (L.req.fuse == 2 && ((long long)L.gx * L.gy * q >= 4ll * c->n_cu || q > 2));   // (several constraints: the separate pass costs more than one constraint's)
+  L.fuse = fuse_wanted && q >= 2 && c->maskS.p && c->maskU.p && c->maskS.bytes >= (size_t)cs.n_local && c->maskU.bytes >= (size_t)cs.n_local &&
+           (q == 2 || (c->fuseS.bytes >= (size_t)cs.n_local * (q - 1) && c->fuseU.bytes >= (size_t)cs.n_local * (q - 1)));
+  L.colw = L.fuse && col_words_ok(c, L.req, L.cnt0, L.nlines);
+  memset(&L.px, 0, sizeof(L.px));
+  L.px.q = q;
+  if (!L.fuse) return SBO_OK;
+  L.out.fuse_rows = (int)L.rows_out * (L.colw ? 2 : (q - 1));
+  L.px.fstride = q > 2 ? (long long)cs.n_local : 0ll;
+  // (room behind the rows for the partials of the objective pass, see sweep_common_front)
+  if (int rc = ensure(c->cpart, sizeof(unsigned long long) * kFuseRow * ((size_t)L.out.fuse_rows + 4 * (size_t)c->n_cu + 64))) return rc;
+  c->cpart_cap = (int)(c->cpart.bytes / (sizeof(unsigned long long) * kFuseRow));
+  if (L.colw) L.out.col_rows = ColPartRows{(unsigned long long*)c->cpart.p, c->cpart_cap, (int)L.rows_out};
+  return SBO_OK;
+}
+
+// The word buffers, Usum and the slot block of a column-path launch.  The slot block's fill is a host array on this stack: the one
+// host wait of the path, on first use or after a sweep that failed.
 static int col_words_prepare(sbo_ctx* c, long long cnt0, long long nlines, ColBits* cb) {
   const size_t words = (size_t)(nlines / 64) * (size_t)cnt0;
   int rc;
   if ((rc = ensure(c->col.S, 8 * words)) || (rc = ensure(c->col.U, 8 * words)) || (rc = ensure(c->col.M, 8 * words)) || (rc = ensure(c->col.G, 8 * words))) return rc;
-  const bool fresh = c->col.Usum.bytes < 8 * (size_t)cnt0;
-  if ((rc = ensure(c->col.Usum, 8 * (size_t)cnt0))) return rc;
-  if (fresh || c->col.usum_dirty) SBO_HIP(hipMemsetAsync(c->col.Usum.p, 0, c->col.Usum.bytes, c->stream));
-  c->col.usum_dirty = true;       // (until the column path's second kernel has cleared it again)
+  DevBuf& usum = c->col.Usum.buf;
+  if ((rc = c->col.Usum.acquire(8 * (size_t)cnt0, [&]() -> int {
+        SBO_HIP(hipMemsetAsync(usum.p, 0, usum.bytes, c->stream));
+        return SBO_OK;
+      })))
+    return rc;
   const size_t sbytes = sizeof(unsigned long long) * kColSlotFields * kColSlots;
-  if (c->col.slots.bytes < sbytes) c->col.slots_clean = false;
-  if ((rc = ensure(c->col.slots, sbytes))) return rc;
-  if (!c->col.slots_clean) {
-    unsigned long long init[kColSlotFields * kColSlots];
-    for (int f = 0; f < kColSlotFields; ++f)
-      for (int k = 0; k < kColSlots; ++k) init[f * kColSlots + k] = col_slot_is_min(f) ? ~0ull : 0ull;
-    SBO_HIP(hipMemcpyAsync(c->col.slots.p, init, sbytes, hipMemcpyHostToDevice, c->stream));
-    SBO_HIP(hipStreamSynchronize(c->stream));           // (first use, or after a failed sweep: `init` is on this stack)
-  }
-  c->col.slots_clean = false;     // (until the sweep's finals have reset the block)
+  if ((rc = c->col.slots.acquire(sbytes, [&]() -> int {
+        unsigned long long init[kColSlotFields * kColSlots];
+        for (int f = 0; f < kColSlotFields; ++f)
+          for (int k = 0; k < kColSlots; ++k) init[f * kColSlots + k] = col_slot_is_min(f) ? ~0ull : 0ull;
+        SBO_HIP(hipMemcpyAsync(c->col.slots.buf.p, init, sbytes, hipMemcpyHostToDevice, c->stream));
+        SBO_HIP(hipStreamSynchronize(c->stream));           // (`init` is on this stack)
+        return SBO_OK;
+      })))
+    return rc;
   cb->Sw = (unsigned long long*)c->col.S.p;
   cb->Uw = (unsigned long long*)c->col.U.p;
-  cb->Usum = (unsigned long long*)c->col.Usum.p;
-  cb->slots = (unsigned long long*)c->col.slots.p;
+  cb->Usum = (unsigned long long*)usum.p;
+  cb->slots = (unsigned long long*)c->col.slots.buf.p;
   return SBO_OK;
 }
 
-// The GEMM posterior on the operands of a plan -- K1i's when `interp`, else K1b's: stage 1, the k_bpost launches and the Lipschitz tail.
-// Only K1i has the deferred gradient launch (k_bgrad on stream3); only K1b the column path's enclosures and tile lists (r06, r07).
-int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostOutcome& out) {
-  const GemmOps& g = interp ? c->bi.ops : c->bl.ops;
-  const ModelConst& mc = c->mc;
+// r06: the constraint's enclosures per 8 x 8 cell (per plan) and a skip byte per tile (per sweep); a lean-2 sweep hands them to
+// the constraint's launch once the plan's first launch has recorded them.  Leaves the audit its record of this launch (guard.hip).
+static int col_enclosures(GemmLaunch& L) {
+  sbo_ctx* c = L.c;
+  const size_t ebytes = sizeof(double) * 4 * 128 * L.ntiles;
+  const void* was = c->bl_encl.p;
+  if (int rc = ensure(c->bl_encl, ebytes + L.ntiles)) return rc;
+  if (c->bl_encl.p != was) c->bl.encl_ready = false;
+  L.encl = (double*)c->bl_encl.p;
+  L.record_encl = !c->bl.encl_ready;
+  c->k1_audit.encl_tiles = L.ntiles;
+  c->k1_audit.encl_check = !L.record_encl;
+  if (!L.record_encl && L.req.col_lean >= 2) {
+    L.px.encl = L.encl;
+    L.px.skip = (uint8_t*)c->bl_encl.p + ebytes;
+    L.px.skip_safe = (c->opt.k1_skip_safe && c->bl.vals_ready) ? 1 : 0;     // (a proved-safe tile's stored values are read: internal.hpp)
+    c->k1_audit.skip_armed = true;
+  }
+  return SBO_OK;
+}
+
+// r07: lean 2 -- the objective's launch over the tiles with a safe candidate, and, once the enclosures decide skips, the
+// constraint's over the tiles that need a workgroup (k_bl_sched_tiles1 and on).  [list 1: kTlistShards shards][list 2: one],
+// PostExtra::tlist: the constraint's counters stay at the head of the buffer whatever the grid.
+// The counters are zero from the last sweep's k_bl_sched_list2 -- a fill only for a new buffer, or after a sweep that failed or ran no
+// lists, and only in front of a k_bl_sched_tiles1 (a launch with enclosures to decide by: nothing else reads them).  Every column-path
+// launch takes the block in use; col_set_phase says when a sweep whose k_bl_sched_list2 reset the counters has come through.
+static int col_tile_lists(GemmLaunch& L) {
+  sbo_ctx* c = L.c;
+  if (L.interp || !c->opt.k1_sched || L.req.col_lean < 2) {
+    c->bl_sched.in_use();
+    return SBO_OK;
+  }
+  // (of every kTlistShards consecutive tiles a shard gets one)
+  L.sched_cap1 = (int)((L.ntiles + kTlistShards - 1) / kTlistShards);
+  const size_t words1 = (size_t)kTlistShards * (kTlistHead + (size_t)L.sched_cap1);
+  if (int rc = c->bl_sched.acquire(sizeof(unsigned int) * (words1 + kTlistHead + L.ntiles), [&]() -> int {
+        if (L.px.encl) SBO_HIP(hipMemsetAsync(c->bl_sched.buf.p, 0, sizeof(unsigned int) * kTlistShards * kTlistHead, c->stream));
+        return SBO_OK;
+      }))
+    return rc;
+  L.sched_l1 = (unsigned int*)c->bl_sched.buf.p;
+  L.sched_l2 = L.sched_l1 + words1;
+  return SBO_OK;
+}
+
+// K1i's deferred gradient launch: the gradient phases alone, behind the gate on stream3 and behind stage 1 (its images): one launch for all outputs
+static int gemm_grad_deferred(GemmLaunch& L) {
+  sbo_ctx* c = L.c;
+  const GemmOps& g = L.g;
+  hipStream_t gs = c->stream3;
+  SBO_HIP(hipStreamWaitEvent(gs, c->ev_grad[1], 0));
+  SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bgrad), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+  hipLaunchKernelGGL(k_bgrad, dim3((unsigned)std::min<long long>((long long)L.rows_out, 2ll * c->n_cu)), dim3(256), L.lds, gs, c->mc, c->cs, g.VA,
+                     g.sVA, g.P0f, g.KB0, g.nrb, g.ncs0, L.nlines, (int)L.gx, (int)L.gy, (const int*)g.eff, g.gtmax, g.gkey,
+                     (const double*)c->bl_small.p, L.q, L.lrows, L.colw ? L.px.cb.slots : (unsigned long long*)nullptr, (L.req.sweep_lean && L.q >= 2) ? 1 : 0);
+  SBO_HIP(hipEventRecord(c->ev_grad[2], gs));
+  c->grad_pending = true;
+  L.px.nograd = 1;
+  return SBO_OK;
+}
+
+// One k_bpost launch: all outputs (part 0 of 1), or on the column path the constraint's (part 0) and then the objective's (part 1), whose
+// tiles read the constraint's words and its counts of safe candidates per tile.  In front of it the kernel that builds its tile list (r07:
+// on this stream, right in front of the launch that reads the list), behind the constraint's the plan's enclosures where it records them.
+// The K1 stop event rides on the last launch (hipExtLaunchKernel): a separate hipEventRecord behind it is a barrier packet
+// the next kernel waits ~6 us for.  A sweep merges the Lipschitz partials in its own first small kernel (req.lmax_defer).
+static void gemm_post_part(GemmLaunch& L, int part) {
+  sbo_ctx* c = L.c;
+  const GemmOps& g = L.g;
   const CandSpec& cs = c->cs;
-  const int q = mc.q;
-  const long long cnt0 = cs.count[0], nlines = cs.n_local / cnt0;
+  const bool colw = L.colw, fuse = L.fuse;
+  const int q = L.q;
+  const ColPartRows& rows = L.out.col_rows;
+  PostExtra& px = L.px;
+  px.o0 = colw ? 1 - part : 0;
+  const bool last = !colw || part == 1;
+  const decltype(&k_bpost<1, 0>) kposts[3] = {k_bpost<1, 0>, k_bpost<1, 1>, k_bpost<1, 2>};
+  const auto kpost = kposts[colw ? 1 + part : 0];
+  px.tlist = nullptr;
+  if (L.sched_l1 && part == 0 && px.encl) {
+    hipLaunchKernelGGL(k_bl_sched_tiles1, dim3((L.gx * L.gy + kSchedWaves - 1) / kSchedWaves), dim3(64 * kSchedWaves), 0, c->stream, c->mc, (const double*)px.encl, (int)(L.gx * L.gy), (int)L.gx,
+                       (int)L.gy, (unsigned int)L.cnt0, L.req.fuse_b, L.gb_fused, g.gtmax, g.gkey, q, px.skip, L.sched_l1, L.sched_cap1, px.cb.Sw, px.cb.Uw,
+                       px.cb.Usum, px.cb.slots, L.lrows, rows.base, rows.cap, px.skip_safe);
+    px.tlist = L.sched_l1;
+    px.tshift = kTlistShift;
+    px.tcap = L.sched_cap1;
+  }
+  if (L.sched_l2 && part == 1) {
+    hipLaunchKernelGGL(k_bl_sched_list2, dim3(1), dim3(1024), 0, c->stream, rows.base, rows.cap, (int)(L.gx * L.gy), L.sched_l2,
+                       L.lrows, L.sched_l1);
+    px.tlist = L.sched_l2;
+    px.tshift = 0;
+    px.tcap = (int)(L.gx * L.gy);
+    L.out.col_sched = true;
+  }
+  px.tgx = (int)L.gx;
+  px.tgy = (int)L.gy;
+  const dim3 grid = px.tlist ? dim3((unsigned)px.tcap << px.tshift) : dim3(L.gx, L.gy, (unsigned)(colw ? 1 : q));
+  hipExtLaunchKernelGGL(kpost, grid, dim3(256), L.lds, c->stream, nullptr,
+                        (L.req.lmax_defer && last) ? c->ev[1] : ((colw && part == 0) ? c->col.ev[0] : nullptr), 0,
+                        c->mc, cs, g.BtA, g.sBtA, g.P0f, g.sP0f, g.VA, g.sVA, g.SBf, g.sSBf, g.KB0, g.KS0, g.KBm, g.KSm, g.KBm2, g.nrb, g.ncs0,
+                        L.nlines, (double*)c->mean.p, (double*)c->var.p, L.defer ? L.lrows + (size_t)L.rows_out * q : L.lrows,
+                        (const double*)c->bl_small.p /* xn0 */, fuse ? (uint8_t*)(q > 2 ? c->fuseS.p : c->maskS.p) : (uint8_t*)nullptr,
+                        fuse ? (uint8_t*)(q > 2 ? c->fuseU.p : c->maskU.p) : (uint8_t*)nullptr, L.req.fuse_b, (unsigned long long*)c->cpart.p,
+                        c->cpart_cap, L.gb_fused, (const int*)g.eff, g.gtmax, g.gkey, g.imode, px);
+  if (colw && part == 0 && L.record_encl) {
+    // (the plan's first constraint launch evaluated and stored every tile: its enclosures, ~270 MB read once per plan)
+    hipLaunchKernelGGL(k_bl_enclose, dim3(L.gx, L.gy), dim3(128), 0, c->stream, (const double*)c->mean.p + (size_t)cs.n_local,
+                       (const double*)c->var.p + (size_t)cs.n_local, L.cnt0, L.encl);
+    c->bl.encl_ready = true;
+  }
+  // (a constraint's launch without a skip list evaluated and stored every tile: the stored values are the plan's again)
+  if (colw && part == 0 && !L.interp && c->bl.encl_ready && !px.encl) c->bl.vals_ready = true;
+}
+
+// sbo_profile's flop figure of the launch
+static void gemm_flops(const GemmLaunch& L) {
+  sbo_ctx* c = L.c;
+  const GemmOps& g = L.g;
+  const int q = L.q;
+  const double tiles2 = (double)g.nrb * g.ncs0;
+  if (L.interp) {
+    // flops issued: stage 1 of four coefficient sets per output + four full phases of stage 2 (an upper bound: the counts the kernels
+    // run to stay on the device -- a read-back per plan is a launch the host-bound plan does not need)
+    c->last_k1_flops = (double)q * 2.0 * 1024.0 * 4.0 * (4.0 * (double)g.nrb * g.KB0 * g.KB0 + tiles2 * g.KB0 * 4);
+    return;
+  }
+  const double s1 = L.run_stage1 ? 1.0 : 0.0;
+  // flops issued on the matrix cores: stage 1 (when this launch ran it) + the four phases of stage 2 (KS0 + 3 KSm k-steps: the axis-0 gradient phase
+  // runs on the mean phase's sums; 16 x 16 x 4 steps, 2 flops per multiply-add)
+  c->last_k1_flops = (double)q * 2.0 * 1024.0 * (s1 * 4.0 * (double)g.nrb * g.KB0 * g.KB1 + tiles2 * (g.KS0 + 3 * g.KSm));
+  // Chebyshev core: the counts the kernels actually run to (k_cheb_trunc; copied to the pinned block when the plan was built --
+  // they have arrived long before a sweep's result is read: a plan build is followed by the sweep's own synchronisation
+  // before anyone asks for the profile).  Until then the upper bound above stands.
+  const int* he = c->h_back->tile_eff;
+  double f = 0.0;
+  for (int o = 0; o < q; ++o) {
+    const int ks = he[4 * o], kb0 = he[4 * o + 1], kb1 = he[4 * o + 2];
+    if (ks < 1 || ks > g.KS0 || kb0 < 1 || kb0 > g.KB0 || kb1 < 1 || kb1 > g.KB1) return;
+    // (the gradient phases run on the few tiles that can hold the maximum: not counted)
+    f += 2.0 * 1024.0 * (s1 * 4.0 * (double)g.nrb * kb0 * kb1 + tiles2 * (ks + (g.gtmax ? 1 : 3) * g.KSm));
+  }
+  c->last_k1_flops = f;
+}
+
+int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostOutcome& out) {
+  GemmLaunch L{c, interp, req, out, interp ? c->bi.ops : c->bl.ops, c->mc.q, c->cs.count[0], c->cs.n_local / c->cs.count[0]};
+  const GemmOps& g = L.g;
   if (interp) c->bi.used = true;
-  // (deferred gate: the posterior launches write their -- empty -- Lipschitz rows behind the real ones, which the gradient launch fills)
-  const bool defer = interp && c->bi.grad_deferred && c->stream3 != nullptr;
-  // stage 1: Bt = P1^T T4qq^T, written as the packed A operand of stage 2 (three strips per workgroup measured best on
-  // config B: 27.7 us against 28.8 with two and 31.3 with four; the per-wave k_bgemm<2, 0, 0> took 32.6)
-  constexpr int S1 = 3;
-  auto stage1 = [&]() {
-    const dim3 grid((unsigned)((g.KB0 + S1 - 1) / S1), (unsigned)((g.nrb + 3) / 4), (unsigned)(g.sets * q));
-    if (defer)
-      hipExtLaunchKernelGGL((k_bstage1<S1>), grid, dim3(256), 0, c->stream, nullptr, c->ev_grad[1], 0, (const double*)c->bl_P1A.p, g.sP1A,
-                            (const double*)c->bl_T4f.p, g.sT4f, g.KB1, g.nrb, g.KB0, g.BtA, g.sBt1, (const int*)g.eff);
-    else
-      hipLaunchKernelGGL((k_bstage1<S1>), grid, dim3(256), 0, c->stream, (const double*)c->bl_P1A.p, g.sP1A, (const double*)c->bl_T4f.p,
-                         g.sT4f, g.KB1, g.nrb, g.KB0, g.BtA, g.sBt1, (const int*)g.eff);
-  };
-  // K1b: once per plan -- P1A, T4f and the counts are the plan's, so a resident model swept again would rebuild the same images
+  L.defer = interp && c->bi.grad_deferred && c->stream3 != nullptr;
+  // K1b: stage 1 once per plan -- P1A, T4f and the counts are the plan's, so a resident model swept again would rebuild the same images
   // (BilinearPlan::bt_ready states who may write them).  K1i: every launch (its images belong to a model's single first sweep, and
   // they take the place of K1b's in bl_BtA).
-  const bool run_stage1 = interp || !c->bl.bt_ready;
+  L.run_stage1 = interp || !c->bl.bt_ready;
   if (interp) c->bl.bt_ready = false;
-  if (!interp && run_stage1) {
-    stage1();
+  if (!interp && L.run_stage1) {
+    gemm_stage1(L);
     c->bl.bt_ready = true;
   }
-  // stage 2 (fused): variance, mean, Lipschitz keys.  64 x 128 tiles (k_bpost<1>, three workgroups per CU): with the Chebyshev
-  // core the variance phase is ~12 k-steps and no longer dominates, and the third workgroup per CU is worth more than the
-  // B-fragment reuse of a 128 x 128 tile (r03: config B 0.204 -> 0.189 ms per sweep, H 0.547 -> 0.543)
-  const unsigned gx = (unsigned)((g.ncs0 + 7) / 8), gy = (unsigned)((g.nrb + 3) / 4);
-  const unsigned rows_out = gx * gy;                      // partial rows per output: one per workgroup
-  const size_t lds = sizeof(double) * 2 * 3072 + 2048;
   int rc;
-  if ((rc = ensure(c->bl_lpart, sizeof(double) * (size_t)rows_out * q * (interp ? 2 : 1)))) return rc;
-  // a sweep may ask for the S / U bytes, |S|, |U| and the radius key straight from the mean epilogue of the constraint
-  // (one-constraint models; the masks are allocated by the sweep before it enqueues the posterior)
-  // (r03: with the sqrt-free sign tests the fused epilogue saves the separate pass 76 us on config H and costs the GEMM 36;
-  // on config B, two workgroups per CU, the two cancel -- "auto" asks for at least four workgroups per CU)
-  const bool fuse_wanted = req.fuse == 1 || (req.fuse == 2 && ((long long)gx * gy * q >= 4ll * c->n_cu || q > 2));   // (several constraints: the separate pass costs more than one constraint's)
-  bool fuse = fuse_wanted && q >= 2 && c->maskS.p && c->maskU.p && c->maskS.bytes >= (size_t)cs.n_local && c->maskU.bytes >= (size_t)cs.n_local &&
-              (q == 2 || (c->fuseS.bytes >= (size_t)cs.n_local * (q - 1) && c->fuseU.bytes >= (size_t)cs.n_local * (q - 1)));
-  const bool colw = fuse && col_words_ok(c, req, cnt0, nlines);
-  PostExtra px;
-  memset(&px, 0, sizeof(px));
-  px.q = q;
-  if (fuse) {
-    out.fuse_rows = (int)rows_out * (colw ? 2 : (q - 1));
-    px.fstride = q > 2 ? (long long)cs.n_local : 0ll;
-    // (room behind the rows for the partials of the objective pass, see sweep_common_front)
-    if ((rc = ensure(c->cpart, sizeof(unsigned long long) * kFuseRow * ((size_t)out.fuse_rows + 4 * (size_t)c->n_cu + 64)))) return rc;
-    c->cpart_cap = (int)(c->cpart.bytes / (sizeof(unsigned long long) * kFuseRow));
-  }
-  if (colw) {
-    if ((rc = col_words_prepare(c, cnt0, nlines, &px.cb))) return rc;
-    px.lean = req.col_lean;
+  if ((rc = gemm_shape(L)) || (rc = gemm_classify_plan(L))) return rc;
+  if (L.colw) {
+    if ((rc = col_words_prepare(c, L.cnt0, L.nlines, &L.px.cb))) return rc;
+    L.px.lean = req.col_lean;
     out.col_active = true;
     out.col_forked = true;
     out.col_lean = req.col_lean;
-    fuse = false;                      // (no byte masks: the words are the classification)
+    L.fuse = false;                    // (no byte masks: the words are the classification)
+    if (!interp && (rc = col_enclosures(L))) return rc;
+    if ((rc = col_tile_lists(L))) return rc;
   }
   // (K1b's byte-mask launch stores the plan's values through another epilogue: not relied on -- BilinearPlan::encl_ready)
-  if (!interp && !colw) post_regions_written(c);
-  bool record_encl = false;
-  double* encl = nullptr;
-  unsigned int *sched_l1 = nullptr, *sched_l2 = nullptr;
-  int sched_cap1 = 0;
-  if (colw && !interp) {
-    // r06: the constraint's enclosures per 8 x 8 cell (per plan) and a skip byte per tile (per sweep); a lean-2 sweep hands them to
-    // the constraint's launch once the plan's first launch has recorded them
-    const size_t ntiles = (size_t)gx * gy, ebytes = sizeof(double) * 4 * 128 * ntiles;
-    const void* was = c->bl_encl.p;
-    if ((rc = ensure(c->bl_encl, ebytes + ntiles))) return rc;
-    if (c->bl_encl.p != was) c->bl.encl_ready = false;
-    encl = (double*)c->bl_encl.p;
-    record_encl = !c->bl.encl_ready;
-    c->k1_encl_tiles = ntiles;
-    c->k1_encl_check = !record_encl;
-    if (!record_encl && req.col_lean >= 2) {
-      px.encl = encl;
-      px.skip = (uint8_t*)c->bl_encl.p + ebytes;
-      px.skip_safe = (c->opt.k1_skip_safe && c->bl.vals_ready) ? 1 : 0;     // (a proved-safe tile's stored values are read: internal.hpp)
-      c->k1_skip_armed = true;
-    }
-    // r07: lean 2 -- the objective's launch over the tiles with a safe candidate, and, once the enclosures decide skips, the
-    // constraint's over the tiles that need a workgroup (k_bl_sched_tiles1 and on).  [list 1: kTlistShards shards][list 2: one],
-    // PostExtra::tlist: the constraint's counters stay at the head of the buffer whatever the grid
-    if (c->opt.k1_sched && req.col_lean >= 2) {
-      // (of every kTlistShards consecutive tiles a shard gets one)
-      sched_cap1 = (int)((ntiles + kTlistShards - 1) / kTlistShards);
-      const size_t words1 = (size_t)kTlistShards * (kTlistHead + (size_t)sched_cap1);
-      const void* had = c->bl_sched.p;
-      if ((rc = ensure(c->bl_sched, sizeof(unsigned int) * (words1 + kTlistHead + ntiles)))) return rc;
-      if (c->bl_sched.p != had) c->col.sched_clean = false;
-      sched_l1 = (unsigned int*)c->bl_sched.p;
-      sched_l2 = sched_l1 + words1;
-    }
-  }
-  // (the flag is set again by col_set_phase, once a sweep whose k_bl_sched_list2 reset the counters has come through)
-  const bool sched_zero = c->col.sched_clean;
-  if (colw) c->col.sched_clean = false;
+  if (!interp && !L.colw) post_regions_written(c);
   // (K1i: stage 1 behind col_words_prepare -- the gradient launch, which follows it on another stream, merges into the slot block)
-  if (interp) stage1();
-  if (defer && g.band_ready) SBO_HIP(hipStreamWaitEvent(c->stream, c->ev_grad[3], 0));     // (the band: written on Y beside stage 1)
-  // (the fused classification counts its sign tests inside the plan's guard band)
-  const GuardBand* gb_fused = (c->opt.guard_band && !c->is_shadow && g.band_ready && c->gb.buf.p) ? (const GuardBand*)c->gb.buf.p : nullptr;
+  if (interp) gemm_stage1(L);
+  if (L.defer && g.band_ready) SBO_HIP(hipStreamWaitEvent(c->stream, c->ev_grad[3], 0));     // (the band: written on Y beside stage 1)
+  L.gb_fused = (c->opt.guard_band && !c->is_shadow && g.band_ready && c->gb.buf.p) ? (const GuardBand*)c->gb.buf.p : nullptr;
   for (auto k : {k_bpost<1, 0>, k_bpost<1, 1>, k_bpost<1, 2>})
-    SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  double* const lrows = (double*)c->bl_lpart.p;
-  if (defer) {
-    // the gradient phases alone, behind the gate on stream3 and behind stage 1 (its images): one launch for all outputs
-    hipStream_t gs = c->stream3;
-    SBO_HIP(hipStreamWaitEvent(gs, c->ev_grad[1], 0));
-    SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bgrad), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_bgrad, dim3((unsigned)std::min<long long>((long long)rows_out, 2ll * c->n_cu)), dim3(256), lds, gs, mc, cs, g.VA,
-                       g.sVA, g.P0f, g.KB0, g.nrb, g.ncs0, nlines, (int)gx, (int)gy, (const int*)g.eff, g.gtmax, g.gkey,
-                       (const double*)c->bl_small.p, q, lrows, colw ? px.cb.slots : (unsigned long long*)nullptr, (req.sweep_lean && q >= 2) ? 1 : 0);
-    SBO_HIP(hipEventRecord(c->ev_grad[2], gs));
-    c->grad_pending = true;
-    px.nograd = 1;
-  }
-  // the K1 stop event rides on the last launch (hipExtLaunchKernel): a separate hipEventRecord behind it is a barrier packet
-  // the next kernel waits ~6 us for.  A sweep merges the Lipschitz partials in its own first small kernel (req.lmax_defer).
-  // (column path: the constraint's launch first -- the objective's tiles read its words and its counts of safe candidates per tile)
-  for (int part = 0; part < (colw ? 2 : 1); ++part) {
-    px.o0 = colw ? 1 - part : 0;
-    const bool last = !colw || part == 1;
-    auto kpost = !colw ? k_bpost<1, 0> : (part == 0 ? k_bpost<1, 1> : k_bpost<1, 2>);
-    // r07: the tile lists (k_bl_sched_tiles1 / k_bl_sched_list2), built on this stream right in front of the launch that reads them
-    px.tlist = nullptr;
-    if (sched_l1 && part == 0 && px.encl) {
-      // (the list's counters: zero from the last sweep's k_bl_sched_list2 -- a fill only for a new buffer or after a sweep that failed)
-      if (!sched_zero) SBO_HIP(hipMemsetAsync(sched_l1, 0, sizeof(unsigned int) * kTlistShards * kTlistHead, c->stream));
-      hipLaunchKernelGGL(k_bl_sched_tiles1, dim3((gx * gy + kSchedWaves - 1) / kSchedWaves), dim3(64 * kSchedWaves), 0, c->stream, mc, (const double*)px.encl, (int)(gx * gy), (int)gx,
-                         (int)gy, (unsigned int)cnt0, req.fuse_b, gb_fused, g.gtmax, g.gkey, q, px.skip, sched_l1, sched_cap1, px.cb.Sw, px.cb.Uw,
-                         px.cb.Usum, px.cb.slots, lrows, (unsigned long long*)c->cpart.p, c->cpart_cap, px.skip_safe);
-      px.tlist = sched_l1;
-      px.tshift = kTlistShift;
-      px.tcap = sched_cap1;
-    }
-    if (sched_l2 && part == 1) {
-      hipLaunchKernelGGL(k_bl_sched_list2, dim3(1), dim3(1024), 0, c->stream, (unsigned long long*)c->cpart.p, c->cpart_cap, (int)(gx * gy), sched_l2,
-                         lrows, sched_l1);
-      px.tlist = sched_l2;
-      px.tshift = 0;
-      px.tcap = (int)(gx * gy);
-      out.col_sched = true;
-    }
-    px.tgx = (int)gx;
-    px.tgy = (int)gy;
-    const dim3 grid = px.tlist ? dim3((unsigned)px.tcap << px.tshift) : dim3(gx, gy, (unsigned)(colw ? 1 : q));
-    hipExtLaunchKernelGGL(kpost, grid, dim3(256), lds, c->stream, nullptr,
-                          (req.lmax_defer && last) ? c->ev[1] : ((colw && part == 0) ? c->col.ev[0] : nullptr), 0,
-                          mc, cs, g.BtA, g.sBtA, g.P0f, g.sP0f, g.VA, g.sVA, g.SBf, g.sSBf, g.KB0, g.KS0, g.KBm, g.KSm, g.KBm2, g.nrb, g.ncs0,
-                          nlines, (double*)c->mean.p, (double*)c->var.p, defer ? lrows + (size_t)rows_out * q : lrows,
-                          (const double*)c->bl_small.p /* xn0 */, fuse ? (uint8_t*)(q > 2 ? c->fuseS.p : c->maskS.p) : (uint8_t*)nullptr,
-                          fuse ? (uint8_t*)(q > 2 ? c->fuseU.p : c->maskU.p) : (uint8_t*)nullptr, req.fuse_b, (unsigned long long*)c->cpart.p,
-                          c->cpart_cap, gb_fused, (const int*)g.eff, g.gtmax, g.gkey, g.imode, px);
-    if (colw && part == 0 && record_encl) {
-      // (the plan's first constraint launch evaluated and stored every tile: its enclosures, ~270 MB read once per plan)
-      hipLaunchKernelGGL(k_bl_enclose, dim3(gx, gy), dim3(128), 0, c->stream, (const double*)c->mean.p + (size_t)cs.n_local,
-                         (const double*)c->var.p + (size_t)cs.n_local, cnt0, encl);
-      c->bl.encl_ready = true;
-    }
-    // (a constraint's launch without a skip list evaluated and stored every tile: the stored values are the plan's again)
-    if (colw && part == 0 && !interp && c->bl.encl_ready && !px.encl) c->bl.vals_ready = true;
-  }
+    SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+  L.lrows = (double*)c->bl_lpart.p;
+  if (L.defer && (rc = gemm_grad_deferred(L))) return rc;
+  // (column path: the constraint's launch first)
+  for (int part = 0; part < (L.colw ? 2 : 1); ++part) gemm_post_part(L, part);
   // (whoever merges the Lipschitz rows on this stream -- the reduction below, a sweep's first small kernel -- waits for the gradient launch;
   // the column path reads the keys from the slot block on stream3 itself, in stream order behind that launch: sets_colpath.inc.hpp)
-  if (defer && !colw) {
+  if (L.defer && !L.colw) {
     SBO_HIP(hipStreamWaitEvent(c->stream, c->ev_grad[2], 0));
     c->grad_pending = false;
   }
   if (req.lmax_defer) {
     out.lmax_pending = true;
-    out.lmax_per_out = (int)rows_out;
+    out.lmax_per_out = (int)L.rows_out;
   } else {
-    hipExtLaunchKernelGGL(k_lmax_reduce, dim3((unsigned)q), dim3(256), 0, c->stream, nullptr, c->ev[1], 0, (const double*)lrows,
-                          (int)rows_out, c->Lmax);
+    hipExtLaunchKernelGGL(k_lmax_reduce, dim3((unsigned)L.q), dim3(256), 0, c->stream, nullptr, c->ev[1], 0, (const double*)L.lrows,
+                          (int)L.rows_out, c->Lmax);
   }
   out.stop_attached = true;
   c->gb.active = c->opt.guard_band && !c->is_shadow && g.band_ready;     // (the band came with the plan)
-  const double tiles2 = (double)g.nrb * g.ncs0;
-  if (interp) {
-    // flops issued: stage 1 of four coefficient sets per output + four full phases of stage 2 (an upper bound: the counts the kernels
-    // run to stay on the device -- a read-back per plan is a launch the host-bound plan does not need)
-    c->last_k1_flops = (double)q * 2.0 * 1024.0 * 4.0 * (4.0 * (double)g.nrb * g.KB0 * g.KB0 + tiles2 * g.KB0 * 4);
-  } else {
-    const double s1 = run_stage1 ? 1.0 : 0.0;
-    // flops issued on the matrix cores: stage 1 (when this launch ran it) + the four phases of stage 2 (KS0 + 3 KSm k-steps: the axis-0 gradient phase
-    // runs on the mean phase's sums; 16 x 16 x 4 steps, 2 flops per multiply-add)
-    c->last_k1_flops = (double)q * 2.0 * 1024.0 * (s1 * 4.0 * (double)g.nrb * g.KB0 * g.KB1 + tiles2 * (g.KS0 + 3 * g.KSm));
-    // Chebyshev core: the counts the kernels actually run to (k_cheb_trunc; copied to the pinned block when the plan was built --
-    // they have arrived long before a sweep's result is read: a plan build is followed by the sweep's own synchronisation
-    // before anyone asks for the profile).  Until then the upper bound above stands.
-    const int* he = c->h_back->tile_eff;
-    double f = 0.0;
-    bool ok = true;
-    for (int o = 0; o < q; ++o) {
-      const int ks = he[4 * o], kb0 = he[4 * o + 1], kb1 = he[4 * o + 2];
-      if (ks < 1 || ks > g.KS0 || kb0 < 1 || kb0 > g.KB0 || kb1 < 1 || kb1 > g.KB1) { ok = false; break; }
-      // (the gradient phases run on the few tiles that can hold the maximum: not counted)
-      f += 2.0 * 1024.0 * (s1 * 4.0 * (double)g.nrb * kb0 * kb1 + tiles2 * (ks + (g.gtmax ? 1 : 3) * g.KSm));
-    }
-    if (ok) c->last_k1_flops = f;
-  }
+  gemm_flops(L);
   SBO_HIP(hipGetLastError());
   return SBO_OK;
 }

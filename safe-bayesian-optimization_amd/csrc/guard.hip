@@ -571,9 +571,9 @@ int guard_audit_enqueue(sbo_ctx* c, const PostOutcome& out) {
   // sweep may overwrite either.  Only for the launch that just ran, on the layout bl_encl has for this grid.)
   const long long cnt0 = c->cs.count[0];
   const size_t ntiles = c->cs.kind == 1 && c->cs.d == 2 && cnt0 > 0 ? (size_t)(cnt0 / 128) * (size_t)(c->cs.n_local / cnt0 / 64) : 0;
-  const bool encl = c->k1_encl_check && c->last_k1 == 4 && c->bl.encl_ready && first_output <= 1 && ntiles > 0 && c->k1_encl_tiles == ntiles &&
+  const bool encl = c->k1_audit.encl_check && c->last_k1 == 4 && c->bl.encl_ready && first_output <= 1 && ntiles > 0 && c->k1_audit.encl_tiles == ntiles &&
                     c->bl_encl.bytes >= (sizeof(double) * 4 * 128 + 1) * ntiles;
-  const bool skips = encl && c->k1_skip_armed;
+  const bool skips = encl && c->k1_audit.skip_armed;
   hipStream_t st = c->stream_audit;
   // the sample is taken behind the posterior (its stop event ev[1] -- no record of its own on the main stream: that would be a bubble
   // in the sweep) ...

@@ -90,6 +90,8 @@ struct CandSpec {
 
 // The four kinds of device resource a context holds, each freed by its holder's destructor and nowhere else.  Move-only (a copy
 // would free twice); what merely points into another's memory is a plain pointer, not one of these.
+struct DevBuf;
+int ensure(DevBuf& b, size_t bytes);
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
@@ -101,6 +103,34 @@ struct DevBuf {
   }
   ~DevBuf() { reset(); }
   void reset() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+};
+// A device block that starts every sweep in a NEUTRAL state (zeros, or the neutral elements of its merges) without a fill per sweep:
+// the last kernel of a sweep that reads the block puts it back, and the host only remembers whether that has happened.
+//   * acquire(bytes, fill, key) is the one way to the block: it grows the buffer, runs `fill` (which enqueues, and may wait) when the
+//     buffer grew, when the block is not known to be neutral, or when it was laid out for another `key`, and marks the block in use.
+//     A new allocation is never taken for neutral.
+//   * reset_enqueued() says that the kernel that resets the block has been enqueued behind its last reader -- or, where the caller
+//     wants more, that the sweep it ran in has come through.  Which of the two a block uses is its owner's choice and stands at the
+//     member; nobody else raises the flag.
+//   * in_use() is for a sweep that may touch the block but runs none of its kernels' resets (no buffer is needed for it).
+//   * A sweep that fails between acquire() and reset_enqueued() leaves the block in use: the next acquire() fills it again.  A failure
+//     after reset_enqueued() leaves it neutral, which is right as long as what was enqueued runs (a failed call drains the streams).
+struct ResetBuf {
+  DevBuf buf;
+  template <class Fill> int acquire(size_t bytes, Fill&& fill, long long key = 0) {
+    const bool fresh = buf.bytes < bytes;
+    if (int rc = ensure(buf, bytes)) return rc;
+    const bool stale = fresh || !neutral_ || key != key_;
+    neutral_ = false;
+    key_ = key;
+    return stale ? fill() : SBO_OK;
+  }
+  void reset_enqueued() { neutral_ = true; }
+  void in_use() { neutral_ = false; }
+
+ private:
+  bool neutral_ = false;
+  long long key_ = 0;
 };
 struct Event {
   hipEvent_t e = nullptr;
@@ -253,6 +283,21 @@ struct PostRequest {
   bool exact = false;       // no approximating posterior (K1b, K1i, K1t): the exact kernels only
 };
 
+// The column path's rows in sbo_ctx::cpart: field-major with `cap` rows to a field (the capacity the launcher laid cpart out with,
+// sbo_ctx::cpart_cap), a row per tile -- the constraint's tiles first, then the objective's.  launch_posterior_gemm builds the view;
+// the list kernels' launch lines and col_set_phase read it.
+constexpr int kColRowRmax1 = 4 + kMaxQ + 1;    // the field of constraint 1's radius key (= kFuseRmax + 1 = kRowRmax + 1: asserted where those are defined)
+struct ColPartRows {
+  unsigned long long* base = nullptr;
+  int cap = 0;
+  int tiles = 0;                                   // constraint rows [0, tiles), objective rows [tiles, 2 tiles)
+  int count() const { return 2 * tiles; }
+  const unsigned long long* field(int f) const { return base + (size_t)f * cap; }
+  const unsigned long long* tumin() const { return field(0); }                  // per constraint tile: key of the lower end of ucb_1 over its safe candidates
+  const unsigned long long* tumax() const { return field(kColRowRmax1); }       // ... of the upper end (the tile's radius key)
+  const unsigned long long* olmin() const { return field(1) + tiles; }          // per objective tile: key of the smallest lower bound of lcb_0 over its safe candidates
+};
+
 // What the launch reports back (filled by the launcher: all zero unless a GEMM posterior ran)
 struct PostOutcome {
   bool col_active = false;     // the launch delivered the classification as column words (col_set_phase runs)
@@ -260,6 +305,7 @@ struct PostOutcome {
   int col_lean = 0;            // ... at this lean level (non-zero: the objective's mean / var are incomplete)
   bool col_sched = false;      // ... and k_bl_sched_list2 ran behind the constraint's launch: the counters of the constraint's tile list are zero again
   int fuse_rows = 0;           // > 0: the kernel wrote S / U and that many partial rows at the head of cpart
+  ColPartRows col_rows;        // col_active: those rows
   bool lmax_pending = false;   // the Lipschitz partials (lmax_per_out rows per output in bl_lpart) wait for the sweep to merge them
   int lmax_per_out = 0;
   bool stop_attached = false;  // the last kernel carries ev[1] as its stop event (no separate record, which costs a ~6 us bubble)
@@ -333,16 +379,15 @@ struct Audit {
 // output -- constraint first: S / U words, |S| per tile; objective second: u* and min var_0 over S from its own epilogue --
 // and says so (PostOutcome::col_active).  The words stay resident for sbo_masks_get (masks_bits: expanded to bytes on demand).
 struct ColPath {
-  bool slots_clean = false;// the slot block holds its neutral elements (the finals of the last column sweep reset it)
-  bool usum_dirty = false; // Usum holds bits of an earlier launch (cleared by the column path's second kernel; by a memset after a failure)
-  bool sched_clean = false;// the counters of the constraint's tile list at the head of bl_sched are zero (k_bl_sched_list2 of the last column sweep reset them and that sweep
-                           // came through; clear for a new buffer, after a sweep that failed or ran no lists: a memset in front of k_bl_sched_tiles1)
-  DevBuf S, U, M, G, Usum;           // column words [H / 64][W]; Usum [W]
-  DevBuf slots;                      // ColBits::slots
+  DevBuf S, U, M, G;                 // column words [H / 64][W]
+  // The blocks a sweep's last reader resets (ResetBuf).  Each flag but the tile lists' is raised when the resetting kernel is ENQUEUED;
+  // the lists' (sbo_ctx::bl_sched) only at the end of col_set_phase, once the sweep whose k_bl_sched_list2 reset them has come through.
+  ResetBuf Usum;                     // [W]: zero; k_col_decide clears it (raised behind k_col_a, the chain's first launch)
+  ResetBuf slots;                    // ColBits::slots: the neutral elements of its fields (a host array, copied and waited for); k_col_finals
   DevBuf img, bmin;                  // column distance image u16 [H][W], block minima u16 [H][W / 32]
-  DevBuf cimg, cbmin;                // the same on the 8 x 8 cells
-  long long ckey = 0;                // the grid the padding of cbmin was laid out for
-  DevBuf fin;                        // the objective's scalars, the finals' tickets and intermediate rows (4 KB)
+  DevBuf cimg;                       // the same on the 8 x 8 cells
+  ResetBuf cbmin;                    // ... 0xffff in the padding of its rows, keyed on the grid: k_col_a, its one writer, leaves the padding alone
+  ResetBuf fin;                      // the objective's scalars, the finals' tickets and intermediate rows (4 KB): zero; k_col_finals' last workgroup of a slot resets its ticket
   hipEvent_t ev[3]{};      // fork (the constraint's posterior launch has finished) / join (the expander chain on stream3 has) /
                            // the chain's first kernel, which clears the M words, has finished (carried by k_col_a: the minimiser's M part waits for it)
   bool masks_bits = false;     // the masks of the last sweep live in the column words (byte buffers stale)
@@ -545,12 +590,15 @@ struct sbo_ctx {
   sbo::DevBuf bl_grad;  // K1b: which tiles run the gradient phases (per plan)
   sbo::DevBuf bl_lpart; // K1b: per-wave Lipschitz partials of k_bpost
   sbo::DevBuf bl_encl;  // K1b column path: per-cell enclosures of the constraint's posterior (per plan) + a skip byte per tile (per sweep)
-  sbo::DevBuf bl_sched;         // K1b column path, lean 2 (r07): the tile lists of the constraint's and the objective's launch (PostExtra::tlist)
+  sbo::ResetBuf bl_sched;       // K1b column path, lean 2 (r07): the tile lists of the constraint's and the objective's launch (PostExtra::tlist); neutral: the
+                                // counters of the constraint's list, at the head, are zero (k_bl_sched_list2; raised by col_set_phase at its end)
   sbo::Pinned h_stage;          // pinned staging of the K1b table build's single upload (the twin has one of its own)
   // what the last posterior launch leaves for the standing audit (guard.hip), cleared by every enqueue of a posterior (api.hip):
-  bool k1_skip_armed = false;   // it could leave constraint tiles unevaluated: bl_encl's skip bytes are its record
-  bool k1_encl_check = false;   // a K1b column-path launch on a plan whose enclosures were recorded: what it stored lies inside them
-  size_t k1_encl_tiles = 0;     // tiles of the grid bl_encl was laid out for (the skip bytes sit behind 4 x 128 doubles per tile)
+  struct K1AuditRecord {
+    bool skip_armed = false;    // it could leave constraint tiles unevaluated: bl_encl's skip bytes are its record
+    bool encl_check = false;    // a K1b column-path launch on a plan whose enclosures were recorded: what it stored lies inside them
+    size_t encl_tiles = 0;      // tiles of the grid bl_encl was laid out for (the skip bytes sit behind 4 x 128 doubles per tile)
+  } k1_audit;                   // (filled by col_enclosures, read by guard_audit_enqueue)
   // K1i plan (first sweep of a model)
   sbo::InterpPlan bi;
   sbo::DevBuf bi_params; // ... its per-model parameter block (device; the plan's kernels read it by pointer) and its pinned staging

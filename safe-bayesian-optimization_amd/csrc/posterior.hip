@@ -950,7 +950,7 @@ static int launch_generic(sbo_ctx* c, const PostTarget& t);   // (defined below 
 
 int launch_posterior(sbo_ctx* c, const PostRequest& req, PostOutcome& out) {
   c->gb.active = false;                    // (the approximating paths K1b / K1t switch their guard band on themselves)
-  c->k1_skip_armed = c->k1_encl_check = false;   // (so does the K1b column path its records for the audit, guard.hip)
+  c->k1_audit = {};                        // (so does the K1b column path its record for the audit, guard.hip)
   // Whatever family runs below writes mean / var of this context.  Only a K1b launch of the plan that is resident NOW leaves the
   // constraint's stored values what that plan computes (BilinearPlan::encl_ready, internal.hpp): every other family -- K1i, K1g, K1t,
   // the generic kernels, an fp32 model's -- drops the flag here, in the one place the family is chosen, and a plan built below starts

@@ -2096,6 +2096,37 @@ static int sweep_profile(sbo_ctx* c, SweepKind kind, bool reuse) {
   return SBO_OK;
 }
 
+// Every arg slot of a SafeOpt sweep is an arg-max (sweep_exchange_back)
+struct AllMax {
+  bool v[kArgSlots];
+  AllMax() { for (bool& b : v) b = true; }
+};
+
+// The late exhaustive recheck of a one-constraint SafeOpt sweep (option exact_lazy): in-band candidates after all, so their exhaustive
+// recheck on the byte masks U / G_1, then the expanders' arg-max and the finals once more, and the result block read again.  Called by
+// the byte-mask path and by the column path (which expands its U and G words to bytes first); `nb`: rows of a partial slot.
+// `exact` is launch_exact_d<T>: the caller names it, where it always named it, so that the code object keeps its kernel order.
+using ExactRecheck = int (*)(sbo_ctx*, sbo_ctx::SetLane&, const sbo_sweep_opts*, const SetView&, int, int, uint8_t*);
+template <typename T>
+static int late_exact_pass(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, int nb, SweepScalars& h, unsigned long long* Lk, ExactRecheck exact) {
+  const int q = c->mc.q;
+  const long long n = c->cs.n_local;
+  const int lidx = o->reference_quirk_L_index ? q - 1 : 1;
+  unsigned char* pbase = (unsigned char*)c->partial.p;
+  const size_t pstride = partial_stride(nb);
+  SweepScalars* sc = (SweepScalars*)c->lane[0].scal.p;
+  if (int rc = exact(c, c->lane[0], o, v, 1, lidx, (uint8_t*)c->maskG.p)) return rc;
+  hipLaunchKernelGGL((k_arg_masked_multi<T, true, ValArray<T>>), dim3((unsigned)nb, 1u), dim3(256), 0, c->stream,
+                     ValArray<T>{(const T*)v.var->p, 0.0}, (const uint8_t*)nullptr, (const uint8_t*)c->maskG.p, n, (long long)c->cs.first, pbase,
+                     pstride, 1, gb_of<T>(c, v));
+  hipLaunchKernelGGL(k_sweep_clear_slot, dim3(1), dim3(1), 0, c->stream, sc, 1);
+  hipExtLaunchKernelGGL(k_sweep_finals<true>, dim3((unsigned)q), dim3(256), 0, c->stream, nullptr, c->ev[4], 0,
+                        (const unsigned char*)pbase, pstride, nb, sc, (const SweepScalars*)nullptr, (unsigned char*)c->h_back,
+                        c->Lmax, gb_of<T>(c, v) ? 1 : 0);
+  SBO_HIP(hipGetLastError());
+  return sweep_exchange_back(c, h, AllMax().v, Lk, c->ev[4], true);
+}
+
 #include "sets_colpath.inc.hpp"
 
 template <typename T>
@@ -2158,23 +2189,9 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v
                         lanes ? (const SweepScalars*)c->lane[1].scal.p : (const SweepScalars*)nullptr,
                         mirrored ? (unsigned char*)c->h_back : (unsigned char*)nullptr, c->Lmax, gb_of<T>(c, v) ? 1 : 0);
   SBO_HIP(hipGetLastError());
-  bool is_max[kArgSlots];
-  for (int t = 0; t < kArgSlots; ++t) is_max[t] = true;
-  if ((rc = sweep_exchange_back(c, h, is_max, Lk, c->ev[4], mirrored))) return rc;
-  if (lazy_exact && (h.n_amb > 0 || c->opt.exact_lazy == 2)) {      // (2: always, the test of this path)
-    // in-band candidates after all: their exhaustive recheck, then the expanders' arg-max and the finals once more
-    const int lidx = o->reference_quirk_L_index ? q - 1 : 1;
-    if ((rc = launch_exact_d<T>(c, c->lane[0], o, v, 1, lidx, (uint8_t*)c->maskG.p))) return rc;
-    hipLaunchKernelGGL((k_arg_masked_multi<T, true, ValArray<T>>), dim3((unsigned)nb, 1u), dim3(256), 0, c->stream,
-                       ValArray<T>{(const T*)v.var->p, 0.0}, (const uint8_t*)nullptr, (const uint8_t*)c->maskG.p, n, (long long)c->cs.first, pbase,
-                       pstride, 1, gb_of<T>(c, v));
-    hipLaunchKernelGGL(k_sweep_clear_slot, dim3(1), dim3(1), 0, c->stream, sc, 1);
-    hipExtLaunchKernelGGL(k_sweep_finals<true>, dim3((unsigned)q), dim3(256), 0, c->stream, nullptr, c->ev[4], 0,
-                          (const unsigned char*)pbase, pstride, nb, sc, (const SweepScalars*)nullptr, (unsigned char*)c->h_back,
-                          c->Lmax, gb_of<T>(c, v) ? 1 : 0);
-    SBO_HIP(hipGetLastError());
-    if ((rc = sweep_exchange_back(c, h, is_max, Lk, c->ev[4], true))) return rc;
-  }
+  if ((rc = sweep_exchange_back(c, h, AllMax().v, Lk, c->ev[4], mirrored))) return rc;
+  // (2: always, the test of this path)
+  if (lazy_exact && (h.n_amb > 0 || c->opt.exact_lazy == 2) && (rc = late_exact_pass<T>(c, o, v, nb, h, Lk, launch_exact_d<T>))) return rc;
   if (multi_rank(c)) {
     sbo_sweep_opts o2 = *o;
     SetView v2 = v;

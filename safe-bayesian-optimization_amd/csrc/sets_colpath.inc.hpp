@@ -1053,13 +1053,12 @@ int col_decide_resident(int* wg_per_cu) {
   SBO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(wg_per_cu, k_col_decide, 256, 0));
   return SBO_OK;
 }
-static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, const PostOutcome& post, SweepScalars& h, unsigned long long* Lk) {
-  const long long n = c->cs.n_local;
-  const int q = c->mc.q;                 // == 2
-  int rc;
+static_assert(kRowRmax + 1 == kColRowRmax1, "ColPartRows::tumax is the radius key of constraint 1");
+
+static ColGeom col_geometry(const CandSpec& cs) {
   ColGeom gm;
-  gm.W = (int)c->cs.count[0];
-  gm.H = (int)(n / gm.W);
+  gm.W = (int)cs.count[0];
+  gm.H = (int)(cs.n_local / gm.W);
   gm.NS = gm.H / 64;
   gm.NB = gm.W / 32;
   gm.NBp = (gm.NB + 7) & ~7;
@@ -1069,35 +1068,49 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   gm.CNB = (gm.CW + 31) / 32;
   gm.CNBp = 16;
   gm.CWp = gm.CNB * 32;
-  gm.h0 = c->cs.step[0];
-  gm.h1 = c->cs.step[1];
-  double h2 = 0.0, hmax = 0.0;
-  for (int a = 0; a < 2; ++a) { h2 += c->cs.step[a] * c->cs.step[a]; hmax = std::max(hmax, c->cs.step[a]); }
+  gm.h0 = cs.step[0];
+  gm.h1 = cs.step[1];
+  double h2 = 0.0;
+  for (int a = 0; a < 2; ++a) h2 += cs.step[a] * cs.step[a];
   gm.delta = (kCoarse - 1) * std::sqrt(h2) * (1.0 + 1e-9);
-  const int lidx = o->reference_quirk_L_index ? q - 1 : 1;     // models/SafeOpt.py:110 (loop-leaked i)
+  return gm;
+}
+
+// What the set phase works in, typed.  `es`: the stream of the expander chain, on which the blocks that need a fill get it.
+struct ColScratch {
+  SweepScalars* sc;
+  ColScal2* sc2;                      // (their own small block: the objective's scalars, the finals' tickets and intermediate rows)
+  unsigned long long* tickets;
+  ColFinRow* fin;
+  int nb;
+  Best *reg0, *reg1;                  // partial rows of the minimiser | of the arg-max over G_1
+  unsigned short *img, *bmin, *cimg, *cbmin;
+  unsigned long long *Mw, *Gw;
+  ColBits cb;
+};
+static int col_scratch(sbo_ctx* c, const ColGeom& gm, hipStream_t es, ColScratch& s) {
+  const long long n = c->cs.n_local;
   sbo_ctx::SetLane& ln = c->lane[0];     // (one constraint: the main lane's scalar block and lists, whichever stream the chains run on)
+  int rc;
   if ((rc = ensure(ln.scal, sizeof(SweepScalars)))) return rc;
-  SweepScalars* sc = (SweepScalars*)ln.scal.p;
-  // (their own small block: the objective's scalars, the finals' tickets and intermediate rows)
+  s.sc = (SweepScalars*)ln.scal.p;
   static_assert(128 + 2 * kColFinParts * sizeof(ColFinRow) <= 4096, "column path scalar block");
-  const bool fresh_fin = c->col.fin.bytes < 4096;
-  if ((rc = ensure(c->col.fin, 4096))) return rc;
-  ColScal2* sc2 = (ColScal2*)c->col.fin.p;
-  unsigned long long* tickets = (unsigned long long*)((char*)c->col.fin.p + 64);
-  ColFinRow* fin = (ColFinRow*)((char*)c->col.fin.p + 128);
-  const bool overlap = c->opt.col_overlap && c->stream3 && post.col_forked;
-  hipStream_t xs = c->stream, es = overlap ? c->stream3 : c->stream;      // objective chain / expander chain
-  if (fresh_fin) SBO_HIP(hipMemsetAsync(c->col.fin.p, 0, 4096, es));       // (tickets: the last workgroup of a slot resets its own)
-  const int nb = reduce_blocks(c);
+  DevBuf& fin = c->col.fin.buf;
+  if ((rc = c->col.fin.acquire(4096, [&]() -> int {
+        SBO_HIP(hipMemsetAsync(fin.p, 0, 4096, es));       // (tickets: the last workgroup of a slot resets its own)
+        return SBO_OK;
+      })))
+    return rc;
+  s.sc2 = (ColScal2*)fin.p;
+  s.tickets = (unsigned long long*)((char*)fin.p + 64);
+  s.fin = (ColFinRow*)((char*)fin.p + 128);
+  s.nb = reduce_blocks(c);
   // partial regions: slot 0 (the minimiser, nb rows) in the layout of the byte-mask path -- its late exhaustive recheck merges
   // slots 0 / 1 from there --, the rows of the arg-max over G_1 (nb) behind both
-  const size_t pstride = partial_stride(nb);
-  // (the list kernel: eight lanes per candidate, 32 candidates per workgroup and round)
-  const int nsc = (int)std::min<long long>(2048, std::max<long long>(256, n / 4096));
+  const size_t pstride = partial_stride(s.nb);
   if ((rc = ensure(c->partial, pstride * 3))) return rc;
-  unsigned char* pbase = (unsigned char*)c->partial.p;
-  Best* reg0 = (Best*)pbase;
-  Best* reg1 = (Best*)(pbase + 2 * pstride);
+  s.reg0 = (Best*)c->partial.p;
+  s.reg1 = (Best*)((unsigned char*)c->partial.p + 2 * pstride);
   if ((rc = ensure(ln.amb, sizeof(long long) * (size_t)n))) return rc;
   if ((rc = ensure(ln.scanlist, 2 * sizeof(long long) * (size_t)n))) return rc;
   if ((rc = ensure(c->col.img, sizeof(unsigned short) * (size_t)n + 64))) return rc;
@@ -1105,54 +1118,44 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   // coarse column image / block minima (rows padded to whole 64-row coarse segments; block-minimum entries beyond the row stay 0xffff)
   const int crows = ((gm.CH + 63) / 64) * 64;
   const size_t cimg_bytes = sizeof(unsigned short) * (size_t)crows * gm.CWp + 64, cbmin_bytes = sizeof(unsigned short) * (size_t)crows * gm.CNBp + 64;
-  const bool fresh_c = c->col.cbmin.bytes < cbmin_bytes || c->col.ckey != ((long long)gm.W << 32 | gm.H);
-  if ((rc = ensure(c->col.cimg, cimg_bytes)) || (rc = ensure(c->col.cbmin, cbmin_bytes))) return rc;
-  if (fresh_c) {
-    SBO_HIP(hipMemsetAsync(c->col.cbmin.p, 0xff, c->col.cbmin.bytes, es));
-    c->col.ckey = (long long)gm.W << 32 | gm.H;
-  }
-  ColBits cb{(unsigned long long*)c->col.S.p, (unsigned long long*)c->col.U.p, (unsigned long long*)c->col.Usum.p, (unsigned long long*)c->col.slots.p};
-  // (the Lipschitz keys come out of the slot block: the posterior's partial rows are not merged)
+  if ((rc = ensure(c->col.cimg, cimg_bytes))) return rc;
+  DevBuf& cbmin = c->col.cbmin.buf;
+  if ((rc = c->col.cbmin.acquire(cbmin_bytes, [&]() -> int {
+        SBO_HIP(hipMemsetAsync(cbmin.p, 0xff, cbmin.bytes, es));
+        return SBO_OK;
+      }, (long long)gm.W << 32 | gm.H)))
+    return rc;
+  s.img = (unsigned short*)c->col.img.p;
+  s.bmin = (unsigned short*)c->col.bmin.p;
+  s.cimg = (unsigned short*)c->col.cimg.p;
+  s.cbmin = (unsigned short*)cbmin.p;
+  s.Mw = (unsigned long long*)c->col.M.p;
+  s.Gw = (unsigned long long*)c->col.G.p;
+  s.cb = ColBits{(unsigned long long*)c->col.S.p, (unsigned long long*)c->col.U.p, (unsigned long long*)c->col.Usum.buf.p, (unsigned long long*)c->col.slots.buf.p};
+  return SBO_OK;
+}
 
-  // ---- expander chain
-  if (overlap) SBO_HIP(hipStreamWaitEvent(es, c->col.ev[0], 0));
-  // (K1i's deferred gradient launch merges the Lipschitz keys into the slot block on stream3: in stream order ahead of this chain when
-  // the chain runs there, an event otherwise)
-  if (c->grad_pending && es != c->stream3) SBO_HIP(hipStreamWaitEvent(es, c->ev_grad[2], 0));
-  c->grad_pending = false;
-  ColMergeJob mg;
-  mg.slots = cb.slots;
-  mg.sc = sc;
-  mg.Lmax = c->Lmax;
-  mg.gb = gb_of<double>(c, v);
-  mg.b = o->b;
-  const int ncoarse = gm.CNB;
-  const int nfine = (int)std::max<long long>(1, std::min<long long>(((long long)gm.NS * (gm.W / 64) + 3) / 4, (long long)c->n_cu * 5));
-  // (overlapped: the launch carries col.ev[2] as its stop event -- it clears the M words the minimiser's M part fills on the main stream)
-  hipExtLaunchKernelGGL(k_col_a, dim3((unsigned)(1 + ncoarse + nfine)), dim3(256), 0, es, nullptr, overlap ? c->col.ev[2] : nullptr, 0, gm, cb, mg, ncoarse,
-                        (unsigned short*)c->col.cimg.p, (unsigned short*)c->col.cbmin.p, (unsigned short*)c->col.img.p, (unsigned short*)c->col.bmin.p,
-                        (unsigned long long*)c->col.M.p, (unsigned long long*)c->col.G.p);
-  c->col.usum_dirty = false;
-  // ---- objective chain, M part: behind the objective's posterior launch on the main stream and behind k_col_a, beside the rest of the
-  // expander chain (one stream: in order between k_col_a and k_col_decide)
+static ColMinJob col_min_job(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, const PostOutcome& post, const ColGeom& gm, const ColScratch& s) {
   ColMinJob j;
   memset(&j, 0, sizeof(j));
   j.gm = gm;
-  j.slots = cb.slots;
+  j.slots = s.cb.slots;
   j.Lmax = c->Lmax;
-  j.sc2 = sc2;
-  j.olmin = (const unsigned long long*)c->cpart.p + (size_t)1 * c->cpart_cap + post.fuse_rows / 2;
-  j.Sw = cb.Sw;
+  j.sc2 = s.sc2;
+  j.olmin = post.col_rows.olmin();
+  j.Sw = s.cb.Sw;
   j.mean0 = (const double*)v.mean->p;
   j.var0 = (const double*)v.var->p;
   j.b = o->b;
-  j.Mw = (unsigned long long*)c->col.M.p;
-  j.Gw = (const unsigned long long*)c->col.G.p;
-  j.partial = reg0;
-  j.gpartial = reg1;
+  j.Mw = s.Mw;
+  j.Gw = s.Gw;
+  j.partial = s.reg0;
+  j.gpartial = s.reg1;
   j.gb = gb_of<double>(c, v);
-  if (overlap) SBO_HIP(hipStreamWaitEvent(xs, c->col.ev[2], 0));
-  hipLaunchKernelGGL(k_col_min<0>, dim3((unsigned)nb), dim3(256), 0, xs, j);
+  return j;
+}
+static ColVerdict col_verdict(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, int lidx) {
+  const long long n = c->cs.n_local;
   ColVerdict cv;
   memset(&cv, 0, sizeof(cv));
   cv.mean_c = (const double*)v.mean->p + (size_t)n;
@@ -1165,6 +1168,49 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   for (int a = 0; a < 2; ++a) xscale = std::max(xscale, std::max(std::fabs(c->cs.lo[a]), std::fabs(c->cs.hi[a])));
   cv.xscale = xscale;
   rx_band<double>(c, v, 1, lidx, cv.rx);
+  return cv;
+}
+
+// The minimiser's launches on the main stream: the M part (PART 0) behind the objective's posterior launch and behind k_col_a, beside the
+// rest of the expander chain (one stream: in order between k_col_a and k_col_decide); the G part (PART 1) behind the join -- the arg-max
+// over G_1 reads the chain's G words.
+template <int PART>
+static int col_min_part(sbo_ctx* c, bool overlap, const ColMinJob& j, int nb) {
+  // (overlapped: k_col_a carries col.ev[2] -- it clears the M words the M part fills)
+  if (PART == 0 && overlap) SBO_HIP(hipStreamWaitEvent(c->stream, c->col.ev[2], 0));
+  hipLaunchKernelGGL(k_col_min<PART>, dim3((unsigned)nb), dim3(256), 0, c->stream, j);
+  return SBO_OK;
+}
+
+// The expander chain on `es`: k_col_a, k_col_decide, k_col_scan.  `between`: what the main stream gets once k_col_a is enqueued (the
+// minimiser's M part).
+template <class Between>
+static int col_expander_chain(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, const PostOutcome& post, const ColGeom& gm, const ColScratch& s,
+                              hipStream_t es, bool overlap, int lidx, Between&& between) {
+  const long long n = c->cs.n_local;
+  sbo_ctx::SetLane& ln = c->lane[0];
+  int rc;
+  if (overlap) SBO_HIP(hipStreamWaitEvent(es, c->col.ev[0], 0));
+  // (K1i's deferred gradient launch merges the Lipschitz keys into the slot block on stream3: in stream order ahead of this chain when
+  // the chain runs there, an event otherwise)
+  if (c->grad_pending && es != c->stream3) SBO_HIP(hipStreamWaitEvent(es, c->ev_grad[2], 0));
+  c->grad_pending = false;
+  // (the Lipschitz keys come out of the slot block: the posterior's partial rows are not merged)
+  ColMergeJob mg;
+  mg.slots = s.cb.slots;
+  mg.sc = s.sc;
+  mg.Lmax = c->Lmax;
+  mg.gb = gb_of<double>(c, v);
+  mg.b = o->b;
+  const int ncoarse = gm.CNB;
+  const int nfine = (int)std::max<long long>(1, std::min<long long>(((long long)gm.NS * (gm.W / 64) + 3) / 4, (long long)c->n_cu * 5));
+  // (overlapped: the launch carries col.ev[2] as its stop event -- it clears the M words the minimiser's M part fills on the main stream)
+  hipExtLaunchKernelGGL(k_col_a, dim3((unsigned)(1 + ncoarse + nfine)), dim3(256), 0, es, nullptr, overlap ? c->col.ev[2] : nullptr, 0, gm, s.cb, mg, ncoarse,
+                        s.cimg, s.cbmin, s.img, s.bmin, s.Mw, s.Gw);
+  c->col.Usum.reset_enqueued();        // (k_col_decide, below, clears it)
+  c->col.cbmin.reset_enqueued();       // (its one writer has been enqueued: the padding stays what the fill made it)
+  if ((rc = between())) return rc;
+  const ColVerdict cv = col_verdict(c, o, v, lidx);
   // (the verdict kernels do not read var_0 -- overlapped, the objective's launch may still be writing it: the arg-max over G_1 is the
   // job of k_col_min<1>, behind the join)
   // (the grid is sized to be resident at once -- decide_wg_per_cu is what the runtime's occupancy query reports for k_col_decide's
@@ -1173,46 +1219,59 @@ static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, 
   const long long units_max = 16ll * gm.NS * gm.gxt;
   const int ndw = (int)std::max<long long>(1, std::min<long long>((long long)c->n_cu * std::max(1, c->decide_wg_per_cu), (units_max + 3) / 4));
   const int qcap = std::min(kColQueue, std::max(64, c->opt.col_queue));
-  const unsigned long long* rows = (const unsigned long long*)c->cpart.p;        // the posterior's partial rows: constraint tiles, then objective tiles
-  hipLaunchKernelGGL(k_col_decide, dim3((unsigned)ndw), dim3(256), 0, es, gm, (const unsigned long long*)cb.Sw, (const unsigned long long*)cb.slots,
-                     rows, rows + (size_t)(kRowRmax + 1) * c->cpart_cap, (const unsigned short*)c->col.cimg.p, (const unsigned short*)c->col.cbmin.p,
-                     2.0 * gm.delta + 2.0 * kCoarse * hmax, cb.Usum, (const unsigned short*)c->col.img.p, cv, sc, (unsigned long long*)c->col.G.p, (long long*)ln.scanlist.p, qcap);
-  hipLaunchKernelGGL(k_col_scan, dim3((unsigned)nsc), dim3(256), 0, es, gm, (const unsigned short*)c->col.img.p, (const unsigned short*)c->col.bmin.p,
-                     cv, sc, (unsigned long long*)c->col.G.p, (long long*)ln.amb.p, (const long long*)ln.scanlist.p);
+  // (the list kernel: eight lanes per candidate, 32 candidates per workgroup and round)
+  const int nsc = (int)std::min<long long>(2048, std::max<long long>(256, n / 4096));
+  const double hmax = std::max(c->cs.step[0], c->cs.step[1]);
+  hipLaunchKernelGGL(k_col_decide, dim3((unsigned)ndw), dim3(256), 0, es, gm, (const unsigned long long*)s.cb.Sw, (const unsigned long long*)s.cb.slots,
+                     post.col_rows.tumin(), post.col_rows.tumax(), (const unsigned short*)s.cimg, (const unsigned short*)s.cbmin,
+                     2.0 * gm.delta + 2.0 * kCoarse * hmax, s.cb.Usum, (const unsigned short*)s.img, cv, s.sc, s.Gw, (long long*)ln.scanlist.p, qcap);
+  hipLaunchKernelGGL(k_col_scan, dim3((unsigned)nsc), dim3(256), 0, es, gm, (const unsigned short*)s.img, (const unsigned short*)s.bmin,
+                     cv, s.sc, s.Gw, (long long*)ln.amb.p, (const long long*)ln.scanlist.p);
   ln.amb_clean = false;
   if (overlap) {
     SBO_HIP(hipEventRecord(c->col.ev[1], es));
-    SBO_HIP(hipStreamWaitEvent(xs, c->col.ev[1], 0));
+    SBO_HIP(hipStreamWaitEvent(c->stream, c->col.ev[1], 0));
   }
+  return SBO_OK;
+}
 
-  // ---- objective chain, G part: the arg-max over G_1 reads the chain's G words, so it follows the join
-  const int nbg = nb;
-  hipLaunchKernelGGL(k_col_min<1>, dim3((unsigned)nbg), dim3(256), 0, xs, j);
-  hipExtLaunchKernelGGL(k_col_finals, dim3(nb > 2048 ? kColFinParts : 1, 2), dim3(256), 0, xs, nullptr, c->ev[4], 0, (const Best*)reg0, nb, (const Best*)reg1,
-                        nbg, sc, (const ColScal2*)sc2, fin, tickets, (unsigned char*)c->h_back, c->Lmax, gb_of<double>(c, v) ? 1 : 0, cb.slots);
-  c->col.slots_clean = true;
+// k_col_finals merges both chains, resets the slot block and its tickets, and carries the sweep's stop event
+static int col_finals(sbo_ctx* c, const SetView& v, const ColScratch& s) {
+  hipExtLaunchKernelGGL(k_col_finals, dim3(s.nb > 2048 ? kColFinParts : 1, 2), dim3(256), 0, c->stream, nullptr, c->ev[4], 0, (const Best*)s.reg0, s.nb,
+                        (const Best*)s.reg1, s.nb, s.sc, (const ColScal2*)s.sc2, s.fin, s.tickets, (unsigned char*)c->h_back, c->Lmax,
+                        gb_of<double>(c, v) ? 1 : 0, s.cb.slots);
+  c->col.slots.reset_enqueued();
+  c->col.fin.reset_enqueued();
   SBO_HIP(hipGetLastError());
-  bool is_max[kArgSlots];
-  for (int t = 0; t < kArgSlots; ++t) is_max[t] = true;
-  if ((rc = sweep_exchange_back(c, h, is_max, Lk, c->ev[4], true))) return rc;
+  return SBO_OK;
+}
+
+static int col_set_phase(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v, const PostOutcome& post, SweepScalars& h, unsigned long long* Lk) {
+  const int q = c->mc.q;                 // == 2
+  const int lidx = o->reference_quirk_L_index ? q - 1 : 1;     // models/SafeOpt.py:110 (loop-leaked i)
+  const bool overlap = c->opt.col_overlap && c->stream3 && post.col_forked;
+  hipStream_t es = overlap ? c->stream3 : c->stream;      // the expander chain's stream (the objective chain: the main stream)
+  const ColGeom gm = col_geometry(c->cs);
+  ColScratch s;
+  int rc;
+  if ((rc = col_scratch(c, gm, es, s))) return rc;
+  const ColMinJob j = col_min_job(c, o, v, post, gm, s);
+  if ((rc = col_expander_chain(c, o, v, post, gm, s, es, overlap, lidx, [&] { return col_min_part<0>(c, overlap, j, s.nb); }))) return rc;
+  if ((rc = col_min_part<1>(c, overlap, j, s.nb)) || (rc = col_finals(c, v, s))) return rc;
+  if ((rc = sweep_exchange_back(c, h, AllMax().v, Lk, c->ev[4], true))) return rc;
   c->col.masks_bits = true;
   c->col.G_bytes = false;
   if (h.n_amb > 0 || c->opt.exact_lazy == 2) {       // (2: always, the test of this path)
     // verdicts inside the reference's "+1e-8" band after all: the exhaustive recheck of the byte-mask path on the expanded U / G
-    // masks, then the expanders' arg-max and the finals once more (slot 0 is where that merge expects it)
+    // masks (slot 0 of the partials is where its merge expects the minimiser's)
     col_expand(c, c->col.U, (uint8_t*)c->maskU.p);
     col_expand(c, c->col.G, (uint8_t*)c->maskG.p);
-    if ((rc = launch_exact_d<double>(c, ln, o, v, 1, lidx, (uint8_t*)c->maskG.p))) return rc;
-    hipLaunchKernelGGL((k_arg_masked_multi<double, true, ValArray<double>>), dim3((unsigned)nb, 1u), dim3(256), 0, c->stream,
-                       ValArray<double>{(const double*)v.var->p, 0.0}, (const uint8_t*)nullptr, (const uint8_t*)c->maskG.p, n, (long long)c->cs.first, pbase,
-                       pstride, 1, gb_of<double>(c, v));
-    hipLaunchKernelGGL(k_sweep_clear_slot, dim3(1), dim3(1), 0, c->stream, sc, 1);
-    hipExtLaunchKernelGGL(k_sweep_finals<true>, dim3(2), dim3(256), 0, c->stream, nullptr, c->ev[4], 0, (const unsigned char*)pbase, pstride, nb, sc,
-                          (const SweepScalars*)nullptr, (unsigned char*)c->h_back, c->Lmax, gb_of<double>(c, v) ? 1 : 0);
-    SBO_HIP(hipGetLastError());
-    if ((rc = sweep_exchange_back(c, h, is_max, Lk, c->ev[4], true))) return rc;
+    const ExactRecheck exact = launch_exact_d<double>;
+    if ((rc = late_exact_pass<double>(c, o, v, s.nb, h, Lk, exact))) return rc;
     c->col.G_bytes = true;
   }
-  c->col.sched_clean = post.col_sched;
+  // (the tile lists' counters: only now, once the sweep whose k_bl_sched_list2 reset them has come through -- the other blocks' flags
+  // went up when their resetting kernel was enqueued)
+  if (post.col_sched) c->bl_sched.reset_enqueued();
   return SBO_OK;
 }
