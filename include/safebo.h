@@ -688,6 +688,44 @@ typedef struct sbo_batch_result {
 int sbo_batch_select(sbo_ctx* ctx, const sbo_batch_opts* opts, int64_t m, const double* pool /* [m][d] */,
                      const double* pending /* [n_pending][d] or NULL */, double* var_out /* [m] or NULL */, sbo_batch_result* result);
 
+/* ---- expanders by hallucinated optimistic observations (the SafeOpt paper's G_t) ---- */
+#define SBO_EXPANDER_MAX_POINTS  65536            /* sources, and targets, of one call; longer target lists: several calls (counts add)      */
+#define SBO_EXPANDER_MAX_SCRATCH 4294967296ULL    /* bytes of the whitened vectors of one call: (ms + mt) * ldt * #constraints * 8, ldt = n
+                                                     rounded up to a multiple of 32                                                          */
+typedef struct sbo_expander_opts {
+  double   b;                 /* finite, >= 0                                                                                              */
+  uint32_t constraint_mask;   /* bit c (1 <= c < q): constraint c takes part; 0: every constraint 1 .. q-1; bit 0 or bits >= q: SBO_E_INVALID */
+  int32_t  reserved;
+} sbo_expander_opts;
+
+/* Source g of sources[ms][d] (raw coordinates, as for sbo_batch_select) is an expander when, were it measured at its optimistic value
+ * ucb_c(g) on every masked constraint c, the GP would certify some target of targets[mt][d]: count_out[g] > 0.  No Lipschitz constant
+ * enters (the rule the sweeps evaluate, SURVEY.md Appendix A, is the reference's and is untouched).  Normalised units, per masked c,
+ * with the resident lower factor M_c (M_c^T M_c = inv(K_c + sn2_c I)), t_p = M_c k_c(X, p) with the expanded distance of the reference
+ * (GP_Safe.py:115-119), mu_c(p) = mp_c + k_c(X, p) . alpha_c, taken as mp_c + t_p . (M_c (y_c - mp_c)) -- the call rests on the factor
+ * and the data, so an append and the removal of that row give back its bits --, and v_c(p) = sf2_c - ||t_p||^2 (not clipped):
+ *   s = v_c(g) + sn2_c              (kappa = sf2 + sn2 on the diagonal of the new row, as sbo_model_append)
+ *   cov = k_c(x, g) - t_x . t_g
+ *   mu' = mu_c(x) + cov b sqrt(max(0, v_c(g))) / s      (the observation at g is ucb_c(g): its residual is b sqrt(v))
+ *   v'  = v_c(x) - cov^2 / s
+ *   z_c(x | g) = mu' - b sqrt(max(0, v')) + Y_mean[c] / Y_std[c]     (>= 0 <=> the raw lcb of c at x, with g added, is >= 0)
+ *   Z(x | g) = min over the masked c of z_c(x | g)
+ * count_out[g] = #{x : Z(x | g) >= 0}; margin_out[g] (may be NULL) = max_x Z(x | g) and witness_out[g] (may be NULL) its target index,
+ * ties to the lowest index, a NaN never taken (none left: margin NaN, witness -1).  fp64 on the resident fp64 factor whatever the
+ * model dtype, as sbo_batch_select.  Stage 1 forms t, mu and v of every point (O((ms + mt) n^2)); stage 2 takes t_x . t_g of all pairs
+ * on the matrix cores in 64 x 64 tiles (O(ms mt n) per constraint) with the formulas above as its epilogue; no [ms][mt] array exists.
+ * The value of a pair does not depend on ms, mt or the points' places in their lists; per-source partials are combined in workgroup
+ * order, there are no atomics, and two calls return the same bits.  Waits first for a deferred factorisation (one that fails:
+ * SBO_E_INVALID).  Reads the model only: candidates, posterior, masks, plans, guard band, audit counters and options are untouched, and
+ * a sweep behind the call equals one before it bit for bit.  One host wait.  No collectives (the model is replicated: any rank may call).
+ * SBO_E_INVALID: a NULL ctx, opts, sources, targets or count_out; ms < 1 or mt < 1; b negative or non-finite; q < 2; a bad mask; a
+ * non-finite coordinate; s <= 0 on some source and masked constraint.  SBO_E_NO_MODEL without a model.  SBO_E_UNSUPPORTED: ms or mt above
+ * SBO_EXPANDER_MAX_POINTS, or whitened vectors above SBO_EXPANDER_MAX_SCRATCH.  On any error the outputs are cleared: counts 0, margins
+ * NaN, witnesses -1. */
+int sbo_expander_gain(sbo_ctx* ctx, const sbo_expander_opts* opts, int64_t ms, const double* sources /* [ms][d] */, int64_t mt,
+                      const double* targets /* [mt][d] */, int64_t* count_out /* [ms] */, double* margin_out /* [ms] or NULL */,
+                      int64_t* witness_out /* [ms] or NULL */);
+
 /* ---- plant evaluation ------------------------------------------ */
 /* The reference's William-Otto reactor (problems/WilliamOttoReactor_Problem.py:19-93), noise-free, for n input rows
  * u[n, 2] = (Fb, Tr): out[n, 3] = (get_objective, get_constraint1, get_constraint2), each the steady state of the six

@@ -23,10 +23,21 @@ from .GP_Safe import GP
 class BO(GP):
     def __init__(self, plant_system, bound, b, grid=None, device: int = 0, dtype: str = "f64",
                  reference_quirk_L_index: bool = True, seed: int = 42, candidates=None, list_index: int | None = None,
-                 refine: bool = False, lipschitz: str = "grid"):
+                 refine: bool = False, lipschitz: str = "grid", expanders: str = "lipschitz", expander_sources: int = 4096):
         GP.__init__(self, plant_system, device=device, dtype=dtype, seed=seed)
         if lipschitz not in ("grid", "box"):
             raise ValueError("lipschitz must be 'grid' or 'box'")
+        if expanders not in ("lipschitz", "hallucinated"):
+            raise ValueError("expanders must be 'lipschitz' or 'hallucinated'")
+        if isinstance(expander_sources, bool) or not isinstance(expander_sources, (int, np.integer)) or expander_sources < 1:
+            raise ValueError("expander_sources must be an integer >= 1")
+        if expanders == "hallucinated" and refine:
+            raise ValueError("refine=True needs expanders='lipschitz': the pair refinement is built on the Lipschitz link")
+        # "lipschitz": G_t is the sweep's, the reference's rule.  "hallucinated": Expander() decides by SweepEngine.expander_gain
+        #  among the ``expander_sources`` most uncertain safe candidates that could win the acquisition
+        self.expanders = expanders
+        self.expander_sources = int(expander_sources)
+        self.expander_witness = None
         # "grid": L_i is the sweep's, the maximum over the candidates.  "box": the larger of that and SweepEngine.lipschitz over
         # ``bound`` -- a multistart lower bound of the box maximum; the sweeps' own L does not change
         self.lipschitz = lipschitz
@@ -211,7 +222,11 @@ class BO(GP):
         constraint with a non-empty G_c the pair (its grid expander, the U candidate nearest to it under the shifted norm) is
         refined off the grid on max var_0(x) s.t. x in S, x' in U and the link with the sweep's L (models/SafeOpt.py:90-124);
         a constraint whose pair is not usable keeps its grid value.  ``expander_witness`` holds (x', c, L) of the answer, or None
-        when the answer is a grid value."""
+        when the answer is a grid value.  With ``expanders="hallucinated"`` see ``_expander_hallucinated``."""
+        if self.expanders == "hallucinated":
+            if self._refining(refine):
+                raise ValueError("refine=True needs expanders='lipschitz': the pair refinement is built on the Lipschitz link")
+            return self._expander_hallucinated()
         res = self.sweep()
         if not self._refining(refine):
             return res["expander_x"], res["expander_std"]
@@ -238,6 +253,35 @@ class BO(GP):
             if first or std_c > best_std:          # (first on ties, models/SafeOpt.py:119-122)
                 best_x, best_std, self.expander_witness, first = xg, std_c, wit, False
         return best_x, best_std
+
+    def _expander_hallucinated(self):
+        """``Expander()`` under ``expanders="hallucinated"``: the SafeOpt paper's G_t, which needs no Lipschitz constant -- a safe
+        candidate g is an expander when, were it measured at its optimistic value ucb_c(g), the GP would certify a candidate that
+        is not safe today (``SweepEngine.expander_gain``).  Sources: the members of S whose objective std exceeds the sweep's
+        minimiser std (no other source can win the acquisition), the ``expander_sources`` largest by std, ties to the lowest
+        flat index; targets: every candidate outside S.  Returns the source with count > 0 of largest objective std (ties: the
+        lowest flat index) and that std, and stores ``expander_witness = (x', None, None)``, x' the target it certifies best; with no such
+        source, what the sweep returns for an empty G and ``expander_witness = None``.  This is not reference behaviour: the
+        reference decides expanders by the Lipschitz rule."""
+        res = self.sweep(want_masks=True)
+        self.expander_witness = None
+        d = self.bound.shape[0]
+        empty = (np.zeros(d), 0.0)                                    # (the sweep's answer for an empty G: sbo_safeopt_result)
+        S = self.engine.mask("S")
+        std = np.sqrt(self.engine.bounds(self.b, 0, "var").astype(np.float64))
+        cand = np.nonzero(S & (std > res["minimizer_std"]))[0]
+        outside = np.nonzero(~S)[0]
+        if cand.size == 0 or outside.size == 0:
+            return empty
+        order = cand[np.argsort(-std[cand], kind="stable")][:self.expander_sources]      # (stable: ties keep the lower flat index first)
+        pts = self._all_points()
+        out = self.engine.expander_gain(pts[order], pts[outside], self.b, return_margin=True)
+        hit = np.nonzero(out["count"] > 0)[0]
+        if hit.size == 0:
+            return empty
+        g = int(hit[0])                                               # (``order`` descends by std)
+        self.expander_witness = (pts[outside[int(out["witness"][g])]], None, None)
+        return pts[order[g]], float(std[order[g]])
 
     def Batch(self, k, pending=None, min_std=0.01):
         """``k`` points to evaluate side by side -> (X [j, d], std [j]), j <= k: the greedy batch of ``SweepEngine.batch_select``

@@ -16,6 +16,8 @@ SBO_COMM_ID_BYTES = 128
 SBO_ROBUST_MAX_SCEN = 8
 SBO_MAX_BATCH = 64
 SBO_MAX_APPEND = 64
+SBO_EXPANDER_MAX_POINTS = 65536
+SBO_EXPANDER_MAX_SCRATCH = 1 << 32
 
 SBO_F64, SBO_F32 = 0, 1
 SBO_MEAN, SBO_UCB, SBO_LCB, SBO_VAR = 0, 1, 2, 3
@@ -154,6 +156,10 @@ class BatchResult(C.Structure):
                 ("std", C.c_double * SBO_MAX_BATCH)]
 
 
+class ExpanderOpts(C.Structure):
+    _fields_ = [("b", C.c_double), ("constraint_mask", C.c_uint32), ("reserved", C.c_int32)]
+
+
 class Profile(C.Structure):
     _fields_ = [
         ("posterior_ms", C.c_double), ("classify_ms", C.c_double), ("expander_ms", C.c_double),
@@ -226,6 +232,7 @@ SYMBOLS = [
     ("sbo_mean_grad", C.c_int, [_P, C.c_int64, _P, _P, _P]),
     ("sbo_lipschitz", C.c_int, [_P, C.POINTER(LipschitzOpts), C.c_int64, _P, C.POINTER(LipschitzResult)]),
     ("sbo_batch_select", C.c_int, [_P, C.POINTER(BatchOpts), C.c_int64, _P, _P, _P, C.POINTER(BatchResult)]),
+    ("sbo_expander_gain", C.c_int, [_P, C.POINTER(ExpanderOpts), C.c_int64, _P, C.c_int64, _P, _P, _P, _P]),
     ("sbo_plant_wo", C.c_int, [_P, C.c_int64, _P, _P]),
     ("sbo_profile_get", C.c_int, [_P, C.POINTER(Profile)]),
     ("sbo_set_option", C.c_int, [_P, C.c_char_p, C.c_int64]),

@@ -365,6 +365,7 @@ static int model_set_impl(sbo_ctx* c, int dtype, const char* kernel, int n, int 
   mc.factor = invK ? SBO_FACTOR_INVK : SBO_FACTOR_CHOL;
   for (int a = 0; a < kMaxD; ++a) { mc.X_mean[a] = a < d ? X_mean[a] : 0.0; mc.X_std[a] = a < d ? X_std[a] : 1.0; mc.X_rstd[a] = 1.0 / mc.X_std[a]; }
   c->h_Xnorm.assign(X_norm, X_norm + (size_t)n * d);
+  c->h_Ynorm.assign(Y_norm, Y_norm + (size_t)n * q);
   const double f32eps = (double)std::numeric_limits<float>::epsilon();
   for (int o = 0; o < q; ++o) {
     mc.Y_mean[o] = Y_mean[o];
@@ -399,6 +400,7 @@ static int model_set_impl(sbo_ctx* c, int dtype, const char* kernel, int n, int 
     s->has_model = false;
     model_changed(s);
     s->h_Xnorm = c->h_Xnorm;
+    s->h_Ynorm = c->h_Ynorm;
     ++s->model_serial;
     if ((rc = model_build(s, invK, X_norm, Y_norm))) return rc;
     s->has_model = true;
@@ -525,6 +527,8 @@ static int model_update_run(sbo_ctx* c, const ModelUpdateRequest& r) {
   // the derived arrays over the rows the model now holds (device), then one re-pack of the factor images
   if (r.rows < 0) c->h_Xnorm.erase(c->h_Xnorm.begin() + (size_t)r.index * d, c->h_Xnorm.begin() + (size_t)(r.index + 1) * d);
   else c->h_Xnorm.insert(c->h_Xnorm.end(), r.x_norm_new, r.x_norm_new + (size_t)r.rows * d);
+  if (r.rows < 0) c->h_Ynorm.erase(c->h_Ynorm.begin() + (size_t)r.index * mc.q, c->h_Ynorm.begin() + (size_t)(r.index + 1) * mc.q);
+  else c->h_Ynorm.insert(c->h_Ynorm.end(), r.y_norm_new, r.y_norm_new + (size_t)r.rows * mc.q);
   mc.n += r.rows;
   mc.npad = (mc.n + 15) / 16 * 16;
   if ((rc = model_prep(c, c->h_Xnorm.data()))) return rc;

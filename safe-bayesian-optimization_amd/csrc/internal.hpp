@@ -563,6 +563,7 @@ struct sbo_ctx {
   sbo::DevBuf AXg;     // grid path: alpha_j (1, Xn_j) rows in fragment-slot order [q][npad][1 + dpad]
   size_t fpk_stride = 0;  // elements per output in Fpk
   std::vector<double> h_Xnorm;   // host copies used by the exact-recheck / result decoding
+  std::vector<double> h_Ynorm;   // [n][q], kept in step with h_Xnorm: sbo_expander_gain whitens the residuals itself (expander.hip)
   sbo::ResidentFactor factor;    // the fp64 lower factor M and alpha, with the spare pair of a removal
   sbo::DevBuf mwork;             // model build workspace (uploads, fp64 copies of the derived arrays, the factorisation's scratch)
   sbo::DevBuf appendbuf;         // model_append_stage's / model_append_block_stage's uploads and scratch (apart from mwork: a refused append leaves the uploaded invK in place)
@@ -627,6 +628,7 @@ struct sbo_ctx {
   sbo::DevBuf refbuf;            // sbo_refine: seeds, candidates, their exact values and the results (refine.hip)
   sbo::DevBuf lipbuf;            // sbo_mean_grad / sbo_lipschitz: points, gradients, picks and the result block (lipschitz.hip)
   sbo::DevBuf batchbuf;          // sbo_batch_select: the scratch factor that grows with the picks, the pool, its variances and the state block (batch.hip)
+  sbo::DevBuf expbuf;            // sbo_expander_gain: the points, their whitened vectors and posteriors, the partials and the results (expander.hip)
   // What one per-constraint chain of the set phase enqueues on and scribbles in.  Lane 0 is the main stream's: everything before
   // the fork and after the join, every sweep of a model with one constraint and every sweep on several ranks uses it alone.  With
   // two or more constraints on one rank the chains are independent, so every other constraint goes to lane 1: stream2, its own

@@ -685,6 +685,86 @@ class SweepEngine:
             out["var"] = var
         return out
 
+    @staticmethod
+    def expander_arguments(d: int, q: int, sources, targets, b, constraints=None):
+        """The checks of ``expander_gain`` that need no device: (sources [ms, d], targets [mt, d], b, constraint mask), or
+        ValueError.  ``d`` / ``q`` < 1 (no model yet): the width of the lists and the range of ``constraints`` are the library's to
+        check."""
+        src, tgt = _f64(sources), _f64(targets)
+        if src.ndim == 1:
+            src = src.reshape(1, -1)
+        if tgt.ndim == 1:
+            tgt = tgt.reshape(1, -1)
+        if src.ndim != 2 or src.shape[0] < 1 or src.shape[1] < 1 or (d >= 1 and src.shape[1] != d):
+            raise ValueError("sources must be [ms, d] for the model's d, ms >= 1")
+        if tgt.ndim != 2 or tgt.shape[0] < 1 or tgt.shape[1] != src.shape[1]:
+            raise ValueError("targets must be [mt, d], mt >= 1")
+        if src.shape[0] > L.SBO_EXPANDER_MAX_POINTS:
+            raise ValueError(f"at most {L.SBO_EXPANDER_MAX_POINTS} sources per call")
+        if isinstance(b, bool) or not isinstance(b, (int, float, np.integer, np.floating)):
+            raise ValueError("b must be a number")
+        b = float(b)
+        if not np.isfinite(b) or b < 0.0:
+            raise ValueError("b must be finite and >= 0")
+        if q == 1:
+            raise ValueError("the model has no constraint (q >= 2 is required)")
+        mask = 0
+        if constraints is not None:
+            for c in constraints:
+                if isinstance(c, bool) or not isinstance(c, (int, np.integer)):
+                    raise ValueError("constraints must be integers")
+                if c < 1 or c >= 32 or (q >= 1 and c >= q):
+                    raise ValueError("constraint out of range [1, q)")
+                mask |= 1 << int(c)
+            if not mask:
+                raise ValueError("constraints must name at least one constraint")
+        if not np.all(np.isfinite(src)) or not np.all(np.isfinite(tgt)):
+            raise ValueError("sources and targets must be finite")
+        return src, tgt, b, mask
+
+    def _expander_call(self, opts, src, tgt, want_margin):
+        """One ``sbo_expander_gain``: (count, margin or None, witness or None) of ``src`` against ``tgt`` (within the caps)."""
+        ms = src.shape[0]
+        count = np.empty(ms, dtype=np.int64)
+        margin = np.empty(ms) if want_margin else None
+        witness = np.empty(ms, dtype=np.int64) if want_margin else None
+        L.check(self._lib.sbo_expander_gain(self._ctx, C.byref(opts), ms, _ptr(src), tgt.shape[0], _ptr(tgt), _ptr(count), _ptr(margin),
+                                            _ptr(witness)))
+        return count, margin, witness
+
+    def expander_gain(self, sources, targets, b, constraints=None, return_margin: bool = False) -> dict:
+        """Expanders by hallucinated optimistic observations (``sbo_expander_gain``; the G_t of the SafeOpt
+        paper, no Lipschitz constant): row g of ``sources`` [ms, d] is an expander when, were it measured at ``ucb_c(g)`` on every
+        constraint of ``constraints`` (None: all), the GP would certify some row of ``targets`` [mt, d] on all of them.  Returns
+        ``count`` [ms] (int64: the targets g would certify) and ``expander`` [ms] (count > 0); with ``return_margin`` also
+        ``margin`` [ms] (the largest Z(x | g) = min_c lcb'_c(x) / Y_std[c] over the targets) and ``witness`` [ms] (its row of
+        ``targets``, the lowest on a tie).  Target lists above the library's cap are passed in chunks: counts add, margins take the
+        maximum with the lowest row on a tie.  fp64 whatever the model dtype; nothing resident is touched."""
+        src, tgt, b, mask = self.expander_arguments(self.d, self.q, sources, targets, b, constraints)
+        opts = L.ExpanderOpts(b, mask, 0)
+        count = margin = witness = None
+        chunk = self._expander_chunk
+        if self.n >= 1 and self.q >= 2:  # (the whitened vectors of a call: (ms + mt) * ldt * #constraints * 8 bytes under the library's cap)
+            row = 8 * ((self.n + 31) // 32 * 32) * (bin(mask).count("1") if mask else self.q - 1)
+            chunk = min(chunk, L.SBO_EXPANDER_MAX_SCRATCH // row - src.shape[0])
+            if chunk < 1:
+                raise ValueError("too many sources for the scratch of one call at this n: pass them in parts")
+        for lo in range(0, tgt.shape[0], chunk):
+            c, m, w = self._expander_call(opts, src, np.ascontiguousarray(tgt[lo:lo + chunk]), return_margin)
+            if count is None:
+                count, margin, witness = c, m, (w if w is None else np.where(w >= 0, w + lo, -1))
+                continue
+            count = count + c
+            if return_margin:            # (chunks in ascending order: a later one wins only when strictly larger -- or the first with a value)
+                better = (w >= 0) & ((witness < 0) | (m > margin))
+                margin, witness = np.where(better, m, margin), np.where(better, w + lo, witness)
+        out = {"count": count, "expander": count > 0}
+        if return_margin:
+            out["margin"], out["witness"] = margin, witness
+        return out
+
+    _expander_chunk = L.SBO_EXPANDER_MAX_POINTS      # targets of one call
+
     def mask(self, which: str, c: int = 0) -> np.ndarray:
         w = {"S": L.SBO_MASK_S, "U": L.SBO_MASK_U, "M": L.SBO_MASK_M, "G": L.SBO_MASK_G, "O": L.SBO_MASK_O}[which]
         out = np.empty(self.n_local, dtype=np.uint8)
