@@ -726,6 +726,54 @@ int sbo_expander_gain(sbo_ctx* ctx, const sbo_expander_opts* opts, int64_t ms, c
                       const double* targets /* [mt][d] */, int64_t* count_out /* [ms] */, double* margin_out /* [ms] or NULL */,
                       int64_t* witness_out /* [ms] or NULL */);
 
+/* ---- posterior sample paths for Thompson sampling (pathwise conditioning) ---- */
+#define SBO_MAX_PATHS        64
+#define SBO_MAX_FEATURES     8192
+#define SBO_PATHS_MAX_POINTS 16777216          /* 2^24 points of one call; longer pools: several calls with the same draws               */
+#define SBO_PATHS_MAX_VALUES 4294967296ULL     /* bytes of values_out: m * n_paths * 8                                                    */
+typedef struct sbo_paths_opts {
+  int32_t output;      /* 0 .. q-1                                                       */
+  int32_t n_paths;     /* S, 1 .. SBO_MAX_PATHS                                          */
+  int32_t n_features;  /* F, 1 .. SBO_MAX_FEATURES                                       */
+  int32_t maximize;    /* 0: per path the arg-min over the points, 1: the arg-max        */
+} sbo_paths_opts;
+typedef struct sbo_paths_result {
+  int64_t index[SBO_MAX_PATHS];   /* into points; -1 past n_paths, and when every value of the path is NaN */
+  double  value[SBO_MAX_PATHS];   /* the path's value there, un-normalised; NaN where index is -1         */
+} sbo_paths_result;
+
+/* S joint draws from the posterior of one output, as functions, evaluated at points[m][d] (raw coordinates, as for sbo_batch_select),
+ * at O(F + n) per point and path (Matheron's rule: a random-feature draw from the prior plus a data-dependent update; Wilson et al.,
+ * "Efficiently sampling functions from Gaussian process posteriors", 2020).  The library draws nothing: omega [F][d], weights [S][F]
+ * and noise [S][n] are the caller's standard normal numbers, phase [F] is uniform on [0, 2 pi); the library applies the
+ * hyper-parameters, so the call is deterministic and the same draws in two calls are the same functions (a long pool can be chunked).
+ * Normalised units, output o, ell_a = exp(2 h_a), u(p)_a = xn(p)_a / sqrt(ell_a), k the reference's expanded distance
+ * (GP_Safe.py:115-119), sn2 as sbo_batch_select's s = v + sn2, M the resident lower factor (M^T M = inv(K + sn2 I)):
+ *   phi_f(p)   = sqrt(2 sf2 / F) cos(omega_f . u(p) + phase_f)
+ *   prior_s(p) = sum_f weights[s][f] phi_f(p)
+ *   r_s[j]     = (Y_norm[j][o] - mp) - prior_s(X_j) - sqrt(sn2) noise[s][j]
+ *   c_s        = M^T (M r_s)
+ *   f_s(p)     = mp + prior_s(p) + sum_j k(X_j, p) c_s[j]
+ *   value      = Y_mean[o] + Y_std[o] f_s(p)
+ * With weights = 0 and noise = 0, f_s is the posterior mean.  c_s rests on the factor and the data, not on the resident alpha: an
+ * append and the removal of that row give back the call's bits.  values_out [m][S] (may be NULL) receives every value; result->index[s]
+ * / value[s] the arg-min (maximize = 1: the arg-max) of path s over the points and the value there, ties to the lowest index, a NaN
+ * never taken.  One set of F features fixes the prior's kernel to within O(1 / sqrt(F)): the paths' variance differs from the
+ * posterior's by that much.  fp64 on the resident fp64 factor whatever the model dtype.  The value of (point, path) does not depend on
+ * m, on the point's place in the list or on the other paths: every sum over features and observations runs in an order fixed by (F, n)
+ * alone, two identical rows hold identical bits, per-path partials are combined in workgroup order, there are no atomics, and two calls
+ * return the same bits.  Waits first for a deferred factorisation (one that fails: SBO_E_INVALID).  Reads the model only: candidates,
+ * posterior, masks, plans, guard band, audit counters and options are untouched, and a sweep behind the call equals one before it bit
+ * for bit.  One host wait.  No collectives (the model is replicated: any rank may call).
+ * SBO_E_INVALID: a NULL ctx, opts, omega, phase, weights, noise, points or result; m < 1 or m > SBO_PATHS_MAX_POINTS; n_paths or
+ * n_features out of range; output outside [0, q); maximize not 0 or 1; a non-finite entry of the five input arrays.  SBO_E_NO_MODEL
+ * without a model.  SBO_E_UNSUPPORTED: values_out given and m * S * 8 > SBO_PATHS_MAX_VALUES.  On any error the result is cleared
+ * (indices -1, values NaN) and values_out is not written. */
+int sbo_sample_paths(sbo_ctx* ctx, const sbo_paths_opts* opts, const double* omega /* [F][d] */, const double* phase /* [F] */,
+                     const double* weights /* [S][F] */, const double* noise /* [S][n] */, int64_t m,
+                     const double* points /* [m][d], raw coordinates */, double* values_out /* [m][S] or NULL */,
+                     sbo_paths_result* result);
+
 /* ---- plant evaluation ------------------------------------------ */
 /* The reference's William-Otto reactor (problems/WilliamOttoReactor_Problem.py:19-93), noise-free, for n input rows
  * u[n, 2] = (Fb, Tr): out[n, 3] = (get_objective, get_constraint1, get_constraint2), each the steady state of the six

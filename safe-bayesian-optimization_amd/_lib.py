@@ -18,6 +18,10 @@ SBO_MAX_BATCH = 64
 SBO_MAX_APPEND = 64
 SBO_EXPANDER_MAX_POINTS = 65536
 SBO_EXPANDER_MAX_SCRATCH = 1 << 32
+SBO_MAX_PATHS = 64
+SBO_MAX_FEATURES = 8192
+SBO_PATHS_MAX_POINTS = 1 << 24
+SBO_PATHS_MAX_VALUES = 1 << 32
 
 SBO_F64, SBO_F32 = 0, 1
 SBO_MEAN, SBO_UCB, SBO_LCB, SBO_VAR = 0, 1, 2, 3
@@ -160,6 +164,14 @@ class ExpanderOpts(C.Structure):
     _fields_ = [("b", C.c_double), ("constraint_mask", C.c_uint32), ("reserved", C.c_int32)]
 
 
+class PathsOpts(C.Structure):
+    _fields_ = [("output", C.c_int32), ("n_paths", C.c_int32), ("n_features", C.c_int32), ("maximize", C.c_int32)]
+
+
+class PathsResult(C.Structure):
+    _fields_ = [("index", C.c_int64 * SBO_MAX_PATHS), ("value", C.c_double * SBO_MAX_PATHS)]
+
+
 class Profile(C.Structure):
     _fields_ = [
         ("posterior_ms", C.c_double), ("classify_ms", C.c_double), ("expander_ms", C.c_double),
@@ -233,6 +245,7 @@ SYMBOLS = [
     ("sbo_lipschitz", C.c_int, [_P, C.POINTER(LipschitzOpts), C.c_int64, _P, C.POINTER(LipschitzResult)]),
     ("sbo_batch_select", C.c_int, [_P, C.POINTER(BatchOpts), C.c_int64, _P, _P, _P, C.POINTER(BatchResult)]),
     ("sbo_expander_gain", C.c_int, [_P, C.POINTER(ExpanderOpts), C.c_int64, _P, C.c_int64, _P, _P, _P, _P]),
+    ("sbo_sample_paths", C.c_int, [_P, C.POINTER(PathsOpts), _P, _P, _P, _P, C.c_int64, _P, _P, C.POINTER(PathsResult)]),
     ("sbo_plant_wo", C.c_int, [_P, C.c_int64, _P, _P]),
     ("sbo_profile_get", C.c_int, [_P, C.POINTER(Profile)]),
     ("sbo_set_option", C.c_int, [_P, C.c_char_p, C.c_int64]),

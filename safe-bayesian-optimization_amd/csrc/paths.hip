@@ -1,0 +1,426 @@
+// paths.hip -- sbo_sample_paths: posterior sample paths by pathwise conditioning (Matheron's rule).
+//
+// A path is a function: a random-feature draw from the prior plus an update that depends on the data,
+//   f_s(p) = mp + sum_f B[f][s] cos(omega_f . u(p) + phase_f) + sum_j k(X_j, p) c_s[j],   B[f][s] = sqrt(2 sf2 / F) weights[s][f],
+//   c_s = M^T (M r_s),   r_s[j] = (y_j - mp) - prior_s(X_j) - sqrt(sn2) noise[s][j]   (M^T M = inv(K + sn2 I), the resident fp64 factor)
+// which is ONE matrix product per point tile: the A operand [point][F + n] is generated on the fly (cos features, then RBF columns),
+// the B operand [F + n][S] (scaled weights, then c) is small and lives in L2.
+//   k_path_prep    the observations in the output's scaled coordinates (as k_exp_prep) and their squares
+//   k_path_bw      the feature rows of B
+//   k_path_main    the hot path on the matrix cores: a workgroup owns kPathTile points x all Spad paths, wave w points 32 w .. + 31 as
+//                  2 x Spad / 16 accumulators of MM<double> (v_mfma_f64_4x4x4, four per step).  The K axis is the F features rounded up
+//                  to a slab, then the n observations rounded up to a slab; per slab of kPathKSlab columns every thread generates 16
+//                  elements of the A image (a column's value at a point is computed once and used by every path) and the [32][Spad]
+//                  slab of B is staged beside it.  Epilogue: un-normalise, store [m][S] where asked, a running arg-best per path.  A
+//                  bounded grid walks the tiles; one partial per (workgroup, path).
+//                  The prior at the data is THIS kernel with the observations as the points and no observation slabs: no second
+//                  feature evaluator exists that could round differently.
+//   k_path_solve   per path: r, w = M r (a wave per row, butterfly, as k_exp_w), c = M^T w (a thread per column, rows in order) into
+//                  the observation rows of B
+//   k_path_finish  the partials in workgroup order -> the result block
+// Every sum over features and observations runs in an order fixed by (F, n) alone, (value, index) reductions are arg_take's total
+// order, there are no atomics: the value of (point, path) does not depend on m, on the point's place or on the other paths, and two
+// calls return the same bits.  One read-back, one host wait; nothing resident is written.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include "internal.hpp"
+#include "device_common.hpp"
+
+namespace sbo {
+
+constexpr int kPathTile = 128;                   // points of one workgroup tile of k_path_main (4 waves x 32 points)
+constexpr int kPathThreads = 256;                // k_path_main
+constexpr int kPathKSlab = 32;                   // columns of the K axis (features, then observations) of one LDS slab
+constexpr int kPathGridTiles = 1024;             // workgroups k_path_main aims at: min(point tiles, kPathGridTiles); each walks its tiles
+constexpr int kPathFinishThreads = 1024;         // k_path_finish: SBO_MAX_PATHS paths x 16 parts of the workgroups
+constexpr int kPathBlk = 16 * kPathKSlab;        // doubles of one 16-row block of a slab image
+constexpr int kPathBlkA = kPathBlk + 16;         // ... and the distance between two blocks of the A image (the four blocks a wave writes at once land in two bank halves)
+static_assert(kPathTile == 128 && kPathThreads == 256 && kPathKSlab == 32, "k_path_main: 4 waves of 32 points, a thread generates 16 columns of one point per slab");
+static_assert(SBO_MAX_PATHS == 64, "k_path_main is instantiated for 16, 32 and 64 padded paths");
+
+struct PathArgs {                                // by value (kernarg segment)
+  int n, d, ld, q;                               // observations, input dimension, leading dimension of the resident factor, outputs
+  int F, S, Spad, o;                             // features, paths, paths rounded up to 16 | 32 | 64, the output
+  int KF, KN, maximize, pad;                     // F and n rounded up to kPathKSlab (KN = 0: no observation part)
+  long long m;                                   // points
+  double X_mean[kMaxD], X_std[kMaxD], vinv[kMaxD];
+  double sf2, sn2, mp, ymean, ystd, fscale;      // fscale = sqrt(2 sf2 / F)
+};
+
+struct PathBufs {
+  double *Xn, *Yn, *As, *sq, *om, *ph, *wt, *nz, *B, *prior, *pts, *vals, *pval;
+  long long* pidx;
+  sbo_paths_result* res;
+};
+
+// ---- the observations in the scaled coordinates of the output: As [n][D], sq [n] (k_exp_prep's arithmetic) ---------------------------
+template <int D>
+__global__ __launch_bounds__(256) void k_path_prep(const PathArgs A, const double* __restrict__ Xn /* [n][d] */, double* __restrict__ As,
+                                                   double* __restrict__ sq) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n) return;
+  double s = 0.0;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    const double v = a < A.d ? Xn[(size_t)i * A.d + a] * A.vinv[a] : 0.0;
+    As[(size_t)i * D + a] = v;
+    s += v * v;
+  }
+  sq[i] = s;
+}
+
+// ---- the feature rows of B: B [f][s] = fscale weights[s][f] (the buffer was zeroed: rows from F on and columns from S on stay zero) ---
+__global__ __launch_bounds__(256) void k_path_bw(const PathArgs A, const double* __restrict__ wt /* [S][F] */, double* __restrict__ B) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long long)A.F * A.S) return;
+  const int s = (int)(e / A.F), f = (int)(e - (long long)s * A.F);
+  B[(size_t)f * A.Spad + s] = A.fscale * wt[e];
+}
+
+// ---- the hot path -------------------------------------------------------------------------------------------------------------------
+// Thread t generates, per slab, columns 16 (t >> 7) .. + 15 of point t & 127 of the tile (the column is wave-uniform: its omega row or
+// observation is read once per wave).  LDS images of a slab, per block of 16 rows and k-step of 4 columns: the points in MM<double>'s
+// packed A order (a lane's four row groups contiguous: one 32-byte read), B as [k-slot][path] (lane l reads element l).  acc[a][c][t]
+// of lane l of wave w is (point 32 w + 16 a + 4 t + (l >> 4), path 16 c + (l & 15)), the D layout of the 4x4x4 form
+// (device_common.hpp).  Points past m generate zeros and are never stored or taken.
+// `pts` holds rows of d coordinates x with u = ((x - X_mean) / X_std) vinv: the raw points, or -- with X_mean = 0, X_std = 1, both exact
+// -- the normalised observations.  The value is ymean + ystd (mp + sum): the caller's units, or -- with 0, 1, 0, all exact -- the sum.
+template <int D, int SB>
+__global__ __launch_bounds__(kPathThreads, 2) void k_path_main(const PathArgs A, long long ntiles, const double* __restrict__ pts,
+                                                              const double* __restrict__ om /* [KF][D] */, const double* __restrict__ ph /* [KF] */,
+                                                              const double* __restrict__ As, const double* __restrict__ sq,
+                                                              const double* __restrict__ B /* [KF + KN][Spad] */, double* __restrict__ vals /* [m][S] or null */,
+                                                              double* __restrict__ pval, long long* __restrict__ pidx /* [grid][Spad] or null */) {
+  constexpr int SP = 16 * SB;
+  __shared__ __attribute__((aligned(32))) double sA[(kPathTile / 16) * kPathBlkA], sB[SB * kPathBlk];
+  __shared__ double rVal[4][SP];
+  __shared__ long long rIdx[4][SP];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int gp = tid & (kPathTile - 1), gk = (tid >> 7) * 16;       // generation: this thread's point of the tile and its first column of the slab
+  const int posA = (gp >> 4) * kPathBlkA + (gk >> 2) * 64 + (gp & 3) * 4 + ((gp & 15) >> 2);      // + (e >> 2) * 64 + (e & 3) * 16
+  const int n = A.n, F = A.F;
+  long long run_idx = kArgNone;                   // threads 0 .. SP - 1: path tid over this workgroup's tiles
+  double run_val = 0.0;
+  for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const long long p0 = tile * kPathTile;
+    const bool on = p0 + gp < A.m;
+    double u[D], usq = 0.0;
+    {
+      const double* x = pts + (size_t)(on ? p0 + gp : 0) * A.d;
+#pragma unroll
+      for (int a = 0; a < D; ++a) {
+        u[a] = (on && a < A.d) ? ((x[a] - A.X_mean[a]) / A.X_std[a]) * A.vinv[a] : 0.0;
+        usq += u[a] * u[a];
+      }
+    }
+    d4_t acc[2][SB];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int c = 0; c < SB; ++c) acc[a][c] = d4_t{0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < A.KF + A.KN; k0 += kPathKSlab) {
+      double g[16];
+      if (k0 < A.KF) {                              // features: cos(omega_f . u + phase_f)
+        const int f0 = __builtin_amdgcn_readfirstlane(k0 + gk);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int f = f0 + e;
+          double arg = 0.0;
+#pragma unroll
+          for (int a = 0; a < D; ++a) arg += om[(size_t)f * D + a] * u[a];
+          arg += ph[f];
+          g[e] = (on && f < F) ? cos(arg) : 0.0;
+        }
+      } else {                                      // observations: sf2 exp(-1/2 dist), the expanded distance of the reference (GP_Safe.py:119)
+        const int j0 = __builtin_amdgcn_readfirstlane(k0 - A.KF + gk);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int j = j0 + e, jj = j < n ? j : n - 1;
+          double dot = 0.0;
+#pragma unroll
+          for (int a = 0; a < D; ++a) dot += As[(size_t)jj * D + a] * u[a];
+          const double kv = A.sf2 * exp(-0.5 * ((-2.0 * dot + sq[jj]) + usq));
+          g[e] = (on && j < n) ? kv : 0.0;
+        }
+      }
+      double bv[SB * 2];                            // the slab of B: [32][Spad] row-major = 32 SP consecutive doubles
+#pragma unroll
+      for (int i = 0; i < SB * 2; ++i) bv[i] = B[(size_t)k0 * SP + i * kPathThreads + tid];
+      __syncthreads();                              // (the slab before this one has been read)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) sA[posA + (e >> 2) * 64 + (e & 3) * 16] = g[e];
+#pragma unroll
+      for (int i = 0; i < SB * 2; ++i) {
+        const int idx = i * kPathThreads + tid, k = idx / SP, s = idx - k * SP;
+        sB[(s >> 4) * kPathBlk + (k >> 2) * 64 + (k & 3) * 16 + (s & 15)] = bv[i];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int kk = 0; kk < kPathKSlab / 4; ++kk) {
+        d4_t fa[2];
+        double fb[SB];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) fa[a] = MM<double>::load_a(sA + (2 * w + a) * kPathBlkA, lane, kk);
+#pragma unroll
+        for (int c = 0; c < SB; ++c) fb[c] = sB[c * kPathBlk + kk * 64 + lane];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int c = 0; c < SB; ++c) acc[a][c] = MM<double>::mfma(fa[a], fb[c], acc[a][c]);
+      }
+    }
+    // epilogue: the values in the caller's units, and per path the arg-best over this tile's points
+#pragma unroll
+    for (int c = 0; c < SB; ++c) {
+      const int s = 16 * c + (lane & 15);
+      long long bk = kArgNone;
+      double bvv = 0.0;
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const long long p = p0 + 32 * w + 16 * a + 4 * t + (lane >> 4);
+          const double v = A.ymean + A.ystd * (A.mp + acc[a][c][t]);
+          const bool in = p < A.m && s < A.S;
+          if (vals && in) vals[(size_t)p * A.S + s] = v;
+          arg_take(bvv, bk, A.maximize ? v : -v, (in && v == v) ? p : kArgNone);      // (a NaN is never taken)
+        }
+#pragma unroll
+      for (int off = 16; off < 64; off <<= 1) {
+        const double ov = __shfl_xor(bvv, off);
+        const long long ok = __shfl_xor(bk, off);
+        arg_take(bvv, bk, ov, ok);
+      }
+      if (lane < 16) {
+        rVal[w][s] = bvv;
+        rIdx[w][s] = bk;
+      }
+    }
+    __syncthreads();
+    if (tid < SP)
+#pragma unroll
+      for (int ww = 0; ww < 4; ++ww) arg_take(run_val, run_idx, rVal[ww][tid], rIdx[ww][tid]);
+    // (the next tile's first barrier stands between these reads and its epilogue's writes)
+  }
+  if (pidx && tid < SP) {
+    pval[(size_t)blockIdx.x * SP + tid] = run_val;
+    pidx[(size_t)blockIdx.x * SP + tid] = run_idx;
+  }
+}
+
+// ---- per path: the residual, w = M r, c = M^T w -> B [KF + j][s] --------------------------------------------------------------------
+// One workgroup per path.  w: a wave per row, lanes along the row, butterfly (k_exp_w).  c: a thread per column, the rows i = j .. n - 1
+// in order (lanes read consecutive columns of a row).  Both orders depend on n alone.
+__global__ __launch_bounds__(1024) void k_path_solve(const PathArgs A, const double* __restrict__ Yn /* [n][q] */, const double* __restrict__ prior /* [n][S] */,
+                                                     const double* __restrict__ nz /* [S][n] */, const double* __restrict__ Fm, double* __restrict__ B) {
+  __shared__ double sr[SBO_MAX_N], sw[SBO_MAX_N];
+  const int n = A.n, ld = A.ld, s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const double* M = Fm + (size_t)A.o * ld * ld;
+  const double sn = sqrt(A.sn2);
+  for (int j = tid; j < n; j += 1024) sr[j] = ((Yn[(size_t)j * A.q + A.o] - A.mp) - prior[(size_t)j * A.S + s]) - sn * nz[(size_t)s * n + j];
+  __syncthreads();
+  for (int i = wave; i < n; i += 16) {
+    double t = 0.0;
+    for (int j = lane; j <= i; j += 64) t = fma(M[(size_t)i * ld + j], sr[j], t);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
+    if (lane == 0) sw[i] = t;
+  }
+  __syncthreads();
+  for (int j = tid; j < n; j += 1024) {
+    double t = 0.0;
+#pragma unroll 8
+    for (int i = j; i < n; ++i) t = fma(M[(size_t)i * ld + j], sw[i], t);
+    B[(size_t)(A.KF + j) * A.Spad + s] = t;
+  }
+}
+
+// ---- per path: the workgroups in order -> the result block --------------------------------------------------------------------------
+// One workgroup: thread (s, part) = (tid & 63, tid >> 6) takes workgroups part, part + 16, .. of path s, then thread s the 16 parts in
+// order (arg_take's order is total: the winner is that of the workgroups taken one by one).
+__global__ __launch_bounds__(kPathFinishThreads) void k_path_finish(const PathArgs A, int nwg, const double* __restrict__ pval,
+                                                                    const long long* __restrict__ pidx, sbo_paths_result* __restrict__ res) {
+  constexpr int kParts = kPathFinishThreads / SBO_MAX_PATHS;
+  __shared__ double sv[kParts][SBO_MAX_PATHS];
+  __shared__ long long sk[kParts][SBO_MAX_PATHS];
+  const int s = threadIdx.x & (SBO_MAX_PATHS - 1), part = threadIdx.x / SBO_MAX_PATHS;
+  long long bk = kArgNone;
+  double bv = 0.0;
+  if (s < A.S)
+    for (int g = part; g < nwg; g += kParts) arg_take(bv, bk, pval[(size_t)g * A.Spad + s], pidx[(size_t)g * A.Spad + s]);
+  sv[part][s] = bv;
+  sk[part][s] = bk;
+  __syncthreads();
+  if (part) return;
+  for (int p = 1; p < kParts; ++p) arg_take(bv, bk, sv[p][s], sk[p][s]);
+  res->index[s] = bk == kArgNone ? -1 : bk;
+  res->value[s] = bk == kArgNone ? __builtin_nan("") : (A.maximize ? bv : -bv);
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------------
+template <int D, int SB>
+static int paths_enqueue_sb(sbo_ctx* c, const PathArgs& A, const PathBufs& Bf, int nwg, long long ntiles) {
+  hipStream_t st = c->stream;
+  const int n = A.n;
+  hipLaunchKernelGGL((k_path_prep<D>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, (const double*)Bf.Xn, Bf.As, Bf.sq);
+  SBO_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_path_bw, dim3((unsigned)(((long long)A.F * A.S + 255) / 256)), dim3(256), 0, st, A, (const double*)Bf.wt, Bf.B);
+  SBO_HIP(hipGetLastError());
+  // the prior at the data: the observations as the points (already normalised: X_mean = 0, X_std = 1), no observation part, the bare sum
+  PathArgs P = A;
+  P.m = n;
+  P.KN = 0;
+  P.mp = 0.0;
+  P.ymean = 0.0;
+  P.ystd = 1.0;
+  for (int a = 0; a < kMaxD; ++a) {
+    P.X_mean[a] = 0.0;
+    P.X_std[a] = 1.0;
+  }
+  const long long ptiles = ((long long)n + kPathTile - 1) / kPathTile;
+  hipLaunchKernelGGL((k_path_main<D, SB>), dim3((unsigned)ptiles), dim3(kPathThreads), 0, st, P, ptiles, (const double*)Bf.Xn, (const double*)Bf.om,
+                     (const double*)Bf.ph, (const double*)Bf.As, (const double*)Bf.sq, (const double*)Bf.B, Bf.prior, (double*)nullptr,
+                     (long long*)nullptr);
+  SBO_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_path_solve, dim3((unsigned)A.S), dim3(1024), 0, st, A, (const double*)Bf.Yn, (const double*)Bf.prior, (const double*)Bf.nz,
+                     c->factor.F(), Bf.B);
+  SBO_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_path_main<D, SB>), dim3((unsigned)nwg), dim3(kPathThreads), 0, st, A, ntiles, (const double*)Bf.pts, (const double*)Bf.om,
+                     (const double*)Bf.ph, (const double*)Bf.As, (const double*)Bf.sq, (const double*)Bf.B, Bf.vals, Bf.pval, Bf.pidx);
+  SBO_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_path_finish, dim3(1), dim3(kPathFinishThreads), 0, st, A, nwg, (const double*)Bf.pval, (const long long*)Bf.pidx, Bf.res);
+  SBO_HIP(hipGetLastError());
+  return SBO_OK;
+}
+
+template <int D>
+static int paths_enqueue(sbo_ctx* c, const PathArgs& A, const PathBufs& Bf, int nwg, long long ntiles) {
+  switch (A.Spad) {                                // S = 1 does not pay for 64 paths
+    case 16: return paths_enqueue_sb<D, 1>(c, A, Bf, nwg, ntiles);
+    case 32: return paths_enqueue_sb<D, 2>(c, A, Bf, nwg, ntiles);
+    default: return paths_enqueue_sb<D, 4>(c, A, Bf, nwg, ntiles);
+  }
+}
+
+static void paths_clear(sbo_paths_result* r) {
+  if (!r) return;
+  for (int s = 0; s < SBO_MAX_PATHS; ++s) {
+    r->index[s] = -1;
+    r->value[s] = std::numeric_limits<double>::quiet_NaN();
+  }
+}
+
+static bool all_finite(const double* p, size_t count) {
+  for (size_t t = 0; t < count; ++t)
+    if (!std::isfinite(p[t])) return false;
+  return true;
+}
+
+}  // namespace sbo
+
+using namespace sbo;
+
+extern "C" int sbo_sample_paths(sbo_ctx* c, const sbo_paths_opts* opts, const double* omega, const double* phase, const double* weights,
+                                const double* noise, int64_t m, const double* points, double* values_out, sbo_paths_result* result) {
+  paths_clear(result);
+  if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
+  if (!opts || !omega || !phase || !weights || !noise || !points || !result) return fail(SBO_E_INVALID, "NULL argument");
+  if (m < 1 || m > SBO_PATHS_MAX_POINTS) return fail(SBO_E_INVALID, "1 <= m <= SBO_PATHS_MAX_POINTS is required");
+  if (opts->n_paths < 1 || opts->n_paths > SBO_MAX_PATHS) return fail(SBO_E_INVALID, "n_paths must be in [1, SBO_MAX_PATHS]");
+  if (opts->n_features < 1 || opts->n_features > SBO_MAX_FEATURES) return fail(SBO_E_INVALID, "n_features must be in [1, SBO_MAX_FEATURES]");
+  if (opts->maximize != 0 && opts->maximize != 1) return fail(SBO_E_INVALID, "maximize must be 0 or 1");
+  int rc;
+  if ((rc = model_reader_check(c, "sbo_sample_paths", false))) return rc;        // (d and q, which the checks below need)
+  const ModelConst& mc = c->mc;
+  const int n = mc.n, d = mc.d, q = mc.q, o = opts->output, S = opts->n_paths, F = opts->n_features;
+  if (o < 0 || o >= q) return fail(SBO_E_INVALID, "output out of range [0, q)");
+  if (values_out && (unsigned long long)m * (unsigned long long)S * sizeof(double) > SBO_PATHS_MAX_VALUES)
+    return fail(SBO_E_UNSUPPORTED, "sbo_sample_paths: values_out needs more than SBO_PATHS_MAX_VALUES bytes");
+  if (!all_finite(omega, (size_t)F * d) || !all_finite(phase, (size_t)F) || !all_finite(weights, (size_t)S * F) || !all_finite(noise, (size_t)S * n))
+    return fail(SBO_E_INVALID, "omega, phase, weights or noise holds a non-finite entry");
+  if (!all_finite(points, (size_t)m * d)) return fail(SBO_E_INVALID, "points holds a non-finite coordinate");
+  if ((rc = model_reader_begin(c, "sbo_sample_paths", false))) return rc;
+  PathArgs A{};
+  A.n = n;
+  A.d = d;
+  A.q = q;
+  A.ld = c->factor.ld();
+  A.F = F;
+  A.S = S;
+  A.Spad = S <= 16 ? 16 : S <= 32 ? 32 : 64;
+  A.o = o;
+  A.KF = (F + kPathKSlab - 1) / kPathKSlab * kPathKSlab;
+  A.KN = (n + kPathKSlab - 1) / kPathKSlab * kPathKSlab;
+  A.maximize = opts->maximize;
+  A.m = m;
+  for (int a = 0; a < kMaxD; ++a) {
+    A.X_mean[a] = a < d ? mc.X_mean[a] : 0.0;
+    A.X_std[a] = a < d ? mc.X_std[a] : 1.0;
+    A.vinv[a] = a < d ? mc.vinv[o][a] : 0.0;
+  }
+  A.sf2 = mc.sf2[o];
+  A.sn2 = mc.sn2[o];
+  A.mp = mc.mp[o];
+  A.ymean = mc.Y_mean[o];
+  A.ystd = mc.Y_std[o];
+  A.fscale = std::sqrt(2.0 * mc.sf2[o] / (double)F);
+  const long long ntiles = ((long long)m + kPathTile - 1) / kPathTile;
+  const int nwg = (int)std::min<long long>(ntiles, kPathGridTiles);
+  // scratch: X_norm [n][d] | Y_norm [n][q] | scaled observations [n][dpad], their squares | omega [KF][dpad], phase [KF] (zero rows behind
+  // F) | weights [S][F] | noise [S][n] | B [KF + KN][Spad] | the prior at the data [n][S] | the points | the values [m][S] where asked |
+  // the partials [nwg][Spad] | the result block
+  const int D = mc.dpad;
+  const size_t KF = (size_t)A.KF, Sp = (size_t)A.Spad;
+  PathBufs Bf;
+  auto layout = [&](Carve cv) {
+    cv.take(Bf.Xn, (size_t)n * d);
+    cv.take(Bf.Yn, (size_t)n * q);
+    cv.take(Bf.As, (size_t)n * D);
+    cv.take(Bf.sq, (size_t)n);
+    cv.take(Bf.om, KF * D);
+    cv.take(Bf.ph, KF);
+    cv.take(Bf.wt, (size_t)S * F);
+    cv.take(Bf.nz, (size_t)S * n);
+    cv.take(Bf.B, (KF + (size_t)A.KN) * Sp);
+    cv.take(Bf.prior, (size_t)n * S);
+    cv.take(Bf.pts, (size_t)m * d);
+    cv.take(Bf.vals, values_out ? (size_t)m * S : 0);
+    cv.take(Bf.pval, (size_t)nwg * Sp);
+    cv.take(Bf.pidx, (size_t)nwg * Sp);
+    cv.take(Bf.res, 1);
+    return cv.off;
+  };
+  if ((rc = carve(c->pathbuf, layout, 256))) return rc;
+  if (!values_out) Bf.vals = nullptr;
+  hipStream_t st = c->stream;
+  // omega in padded lanes [KF][dpad], zero behind d and behind F (the host block is read by the copy before the call returns: it is waited for)
+  std::vector<double> omp(KF * D, 0.0);
+  for (int f = 0; f < F; ++f)
+    for (int a = 0; a < d; ++a) omp[(size_t)f * D + a] = omega[(size_t)f * d + a];
+  SBO_HIP(hipMemsetAsync(Bf.ph, 0, sizeof(double) * KF, st));
+  SBO_HIP(hipMemsetAsync(Bf.B, 0, sizeof(double) * (KF + (size_t)A.KN) * Sp, st));
+  hipError_t e = hipMemcpyAsync(Bf.om, omp.data(), sizeof(double) * KF * D, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(Bf.ph, phase, sizeof(double) * (size_t)F, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(Bf.wt, weights, sizeof(double) * (size_t)S * F, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(Bf.nz, noise, sizeof(double) * (size_t)S * n, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(Bf.Xn, c->h_Xnorm.data(), sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(Bf.Yn, c->h_Ynorm.data(), sizeof(double) * (size_t)n * q, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(Bf.pts, points, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice, st);
+  rc = e == hipSuccess ? with_dpad(D, [&](auto DD) { return paths_enqueue<DD()>(c, A, Bf, nwg, ntiles); }) : SBO_OK;
+  if (e != hipSuccess || rc) {
+    (void)hipStreamSynchronize(st);                     // (nothing of the call may still read the caller's arrays or `omp`)
+    SBO_HIP(e);
+    return rc;
+  }
+  // the one read-back (every refusal of the contract lies above: from here on only the runtime itself can fail)
+  sbo_paths_result out;
+  e = hipMemcpyAsync(&out, Bf.res, sizeof(out), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && values_out) e = hipMemcpyAsync(values_out, Bf.vals, sizeof(double) * (size_t)m * S, hipMemcpyDeviceToHost, st);
+  const hipError_t ew = stream_wait(c, st);
+  SBO_HIP(e);
+  SBO_HIP(ew);
+  *result = out;
+  return SBO_OK;
+}

@@ -765,6 +765,111 @@ class SweepEngine:
 
     _expander_chunk = L.SBO_EXPANDER_MAX_POINTS      # targets of one call
 
+    @staticmethod
+    def path_draws(d: int, n: int, n_paths: int, features: int = 1024, seed=0):
+        """The randomness of ``sample_paths`` in unit scale, from ``np.random.default_rng(seed)`` in this order: ``omega`` [F, d]
+        standard normal, ``phase`` [F] uniform on [0, 2 pi), ``weights`` [S, F] and ``noise`` [S, n] standard normal."""
+        rng = np.random.default_rng(seed)
+        omega = rng.standard_normal((features, d))
+        phase = rng.uniform(0.0, 2.0 * np.pi, features)
+        weights = rng.standard_normal((n_paths, features))
+        noise = rng.standard_normal((n_paths, n))
+        return omega, phase, weights, noise
+
+    @staticmethod
+    def path_arguments(d: int, q: int, n: int, points, n_paths, output=0, features=1024, seed=0, maximize=False, draws=None):
+        """The checks of ``sample_paths`` that need no device: (points [m, d], n_paths, output, features, seed, maximize as 0 | 1,
+        draws as four contiguous float64 arrays or None), or ValueError.  With ``draws`` the number of features is that of its
+        ``omega``.  ``d`` / ``q`` / ``n`` < 1 (no model yet): what depends on them is the library's to check."""
+        pts = _f64(points)
+        if pts.ndim == 1:
+            pts = pts.reshape(1, -1)
+        if pts.ndim != 2 or pts.shape[0] < 1 or pts.shape[1] < 1 or (d >= 1 and pts.shape[1] != d):
+            raise ValueError("points must be [m, d] for the model's d, m >= 1")
+        for name, val in (("n_paths", n_paths), ("output", output), ("features", features), ("seed", seed)):
+            if isinstance(val, bool) or not isinstance(val, (int, np.integer)):
+                raise ValueError(f"{name} must be an integer")
+        if not 1 <= n_paths <= L.SBO_MAX_PATHS:
+            raise ValueError(f"n_paths must be in [1, {L.SBO_MAX_PATHS}]")
+        if output < 0 or (q >= 1 and output >= q):
+            raise ValueError("output out of range [0, q)")
+        if seed < 0:
+            raise ValueError("seed must be >= 0")
+        if not isinstance(maximize, (bool, np.bool_)) and not (isinstance(maximize, (int, np.integer)) and maximize in (0, 1)):
+            raise ValueError("maximize must be a bool")
+        if draws is not None:
+            if not isinstance(draws, (tuple, list)) or len(draws) != 4:
+                raise ValueError("draws must be (omega [F, d], phase [F], weights [S, F], noise [S, n])")
+            omega, phase, weights, noise = (np.ascontiguousarray(_f64(a)) for a in draws)
+            if omega.ndim != 2 or omega.shape[0] < 1 or omega.shape[1] != pts.shape[1]:
+                raise ValueError("omega must be [F, d], F >= 1")
+            features = omega.shape[0]
+            if phase.shape != (features,) or weights.shape != (n_paths, features):
+                raise ValueError("phase must be [F] and weights [n_paths, F]")
+            if noise.ndim != 2 or noise.shape[0] != n_paths or (n >= 1 and noise.shape[1] != n):
+                raise ValueError("noise must be [n_paths, n] for the model's n")
+            if not all(np.all(np.isfinite(a)) for a in (omega, phase, weights, noise)):
+                raise ValueError("draws must be finite")
+            draws = (omega, phase, weights, noise)
+        if not 1 <= features <= L.SBO_MAX_FEATURES:
+            raise ValueError(f"features must be in [1, {L.SBO_MAX_FEATURES}]")
+        if not np.all(np.isfinite(pts)):
+            raise ValueError("points must be finite")
+        return pts, int(n_paths), int(output), int(features), int(seed), int(bool(maximize)), draws
+
+    def _paths_call(self, opts, draws, pts, want_values):
+        """One ``sbo_sample_paths``: (index [S], value [S], values [m, S] or None) of ``pts`` (within the caps)."""
+        S = int(opts.n_paths)
+        res = L.PathsResult()
+        values = np.empty((pts.shape[0], S)) if want_values else None
+        omega, phase, weights, noise = draws
+        L.check(self._lib.sbo_sample_paths(self._ctx, C.byref(opts), _ptr(omega), _ptr(phase), _ptr(weights), _ptr(noise), pts.shape[0],
+                                           _ptr(pts), _ptr(values), C.byref(res)))
+        return np.array(res.index[:S], dtype=np.int64), np.array(res.value[:S], dtype=np.float64), values
+
+    def sample_paths(self, points, n_paths: int, output: int = 0, features: int = 1024, seed: int = 0, maximize: bool = False,
+                     draws=None, return_values: bool = False) -> dict:
+        """``n_paths`` joint draws from the posterior of ``output``, as functions, at ``points`` [m, d] (``sbo_sample_paths``,
+        DESIGN.md section 20; pathwise conditioning: a random-feature draw from the prior plus a data-dependent update, O(F + n)
+        per point and path).  The randomness is ``draws`` = (omega, phase, weights, noise) in unit scale, by default
+        ``path_draws(d, n, n_paths, features, seed)``; the same draws are the same functions in every call.  Returns ``index``
+        [S] (per path its arg-min over the points, ``maximize``: arg-max; the lowest row on a tie, -1 without a value), ``x`` [S, d]
+        (NaN rows where index is -1), ``value`` [S] (un-normalised) and, with ``return_values``, ``values`` [m, S].  Pools above
+        the library's caps are passed in chunks with the same draws and merged by (value, lowest row).  One set of features fixes
+        the prior's kernel to within O(1 / sqrt(F)): the paths' variance differs from the posterior's by that much.  fp64 whatever
+        the model dtype; nothing resident is touched.  This is not reference behaviour."""
+        pts, S, output, F, seed, maximize, draws = self.path_arguments(self.d, self.q, self.n, points, n_paths, output, features, seed,
+                                                                       maximize, draws)
+        if draws is None:
+            draws = tuple(np.ascontiguousarray(a) for a in self.path_draws(pts.shape[1], max(self.n, 0), S, F, seed))
+        opts = L.PathsOpts(output, S, F, maximize)
+        m = pts.shape[0]
+        chunk = self._paths_chunk
+        if return_values:
+            chunk = min(chunk, self._paths_values // (8 * S))
+        index = value = None
+        values = np.empty((m, S)) if return_values else None
+        for lo in range(0, m, chunk):
+            i, v, vals = self._paths_call(opts, draws, np.ascontiguousarray(pts[lo:lo + chunk]), return_values)
+            if return_values:
+                values[lo:lo + chunk] = vals
+            i = np.where(i >= 0, i + lo, -1)
+            if index is None:
+                index, value = i, v
+                continue
+            # (chunks in ascending order: a later one wins only when strictly better -- or the first with a value)
+            better = (i >= 0) & ((index < 0) | ((v > value) if maximize else (v < value)))
+            index, value = np.where(better, i, index), np.where(better, v, value)
+        x = np.full((S, pts.shape[1]), np.nan)
+        x[index >= 0] = pts[index[index >= 0]]
+        out = {"index": index, "x": x, "value": value}
+        if return_values:
+            out["values"] = values
+        return out
+
+    _paths_chunk = L.SBO_PATHS_MAX_POINTS            # points of one call
+    _paths_values = L.SBO_PATHS_MAX_VALUES           # bytes of values_out of one call
+
     def mask(self, which: str, c: int = 0) -> np.ndarray:
         w = {"S": L.SBO_MASK_S, "U": L.SBO_MASK_U, "M": L.SBO_MASK_M, "G": L.SBO_MASK_G, "O": L.SBO_MASK_O}[which]
         out = np.empty(self.n_local, dtype=np.uint8)
