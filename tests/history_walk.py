@@ -13,20 +13,29 @@ the read-only calls -- model_loo, mean_grad, lipschitz, batch_select, the three 
 against the oracle its own suite uses and followed by a sweep on ``posterior_ready``.  A new step never returns early: the generator
 establishes its precondition and the driver raises when it is missing.  ``Walk(None, ...)`` is the dry mode: no engine, references
 only, and per sweep the smallest margin of any decision (``Walk.margins``).
+
+Seeds 16 .. 23 (the third generation, _Gen3) add expander_gain and sample_paths -- each against the NumPy statement of its own suite
+(expander_oracle.gain_naive, paths_oracle.paths_solve) on the rows the walk holds, sharp by assertion, and repeated with the same
+arguments behind the posterior_ready sweep that follows it: the same bytes -- and three situations the earlier walks forbid: a
+read-only call directly behind a model change with no sweep in between (mask("S") is refused before the call and still refused after
+it), model_loo / batch_select / expander_gain / sample_paths on an fp32 model and behind its updates at their fp64 bars, and a caller's
+prior that is not zero.  Seeds 0 .. 15 are untouched by all of this: READ_ONLY stays the tuple _make_walk2 indexes.
 """
 import numpy as np
 
 import batch_oracle
 import de_twin
+import expander_oracle
 import model_append_batch as mb
 import model_loo
 import model_remove as mr
 import nll_grad_oracle
 import oracle
+import paths_oracle
 import refine_sets_oracle as rso
 import robust_oracle
 import robust_refine_oracle
-from safebo_amd import synthetic
+from safebo_amd import SweepEngine, synthetic
 
 # problems: (config, n) -- B and H (q = 2, Benoit), C (q = 3, the Williams-Otto shape), A (small n)
 PROBLEMS = {"A": ("A", 20), "B": ("B", 64), "H": ("H", 96), "C": ("C", 48)}
@@ -52,15 +61,33 @@ READY_KINDS = ("safeopt", "goose", "tr", "robust")
 REFUSALS = ("b_nan", "b_neg", "append_nonfinite", "grid_zero", "mask_g_after_goose", "robust_arrays_after_model")
 OLD_SEEDS = tuple(range(8))
 NEW_SEEDS = tuple(range(8, 16))
-SEEDS = OLD_SEEDS + NEW_SEEDS
-READ_ONLY = ("loo", "mean_grad", "lipschitz", "batch_select", "refine", "refine_sets", "refine_robust", "nll")
-MODEL_STEPS = ("remove", "append_block", "fit", "set_prior_zero")
+THIRD_SEEDS = tuple(range(16, 24))
+SEEDS = OLD_SEEDS + NEW_SEEDS + THIRD_SEEDS
+READ_ONLY = ("loo", "mean_grad", "lipschitz", "batch_select", "refine", "refine_sets", "refine_robust", "nll")     # (_make_walk2 indexes this)
+NEW_CALLS = ("expander_gain", "sample_paths")
+READ_ONLY3 = READ_ONLY + NEW_CALLS
+F32_READS = ("loo", "batch_select", "expander_gain", "sample_paths")      # fp64 data and factor "for every model dtype" 
+F64_ONLY = ("mean_grad", "lipschitz", "refine")                           # refused on an fp32 model
+MODEL_STEPS = ("remove", "append_block", "fit", "set_prior_zero", "set_prior")
+# the model-changing steps a read-only call stands directly behind (seeds 16 ..), as the driver and transitions() label them
+CHANGES = ("set_model_invK1", "set_model_invK0", "append", "remove_first", "remove_middle", "remove_last", "append_block_1",
+           "append_block_3", "append_block_17", "fit", "set_prior")
+F32_UPDATES = ("append", "append_block_3", "remove_middle")
+PRIOR = (0.3, -0.7, 0.4)        # set_prior: a caller's prior that is not zero, normalised units, cut to q
+EG_SOURCES, EG_TARGETS = 9, 257                  # expander_gain: off the 64 x 64 tile edges of csrc/expander.hip
+SP_POINTS, SP_PATHS, SP_FEATURES = 257, 17, 257  # sample_paths: off the 128-point tiles, the 16-path blocks and the 32-column slabs
+SHARP = 1e-8                    # the sharpness above which counts, witnesses and path indices are compared exactly (a condition on the inputs)
 UNDER = ("K1i", "K1b", "K1g")
 RTOL_GRAD = 1e-9            # tests/test_gpu_lipschitz.py: RTOL, per output, of the largest |grad_o| over the step's points
 FIT_BOX = np.array([[-1.0, 0.5], [-1.0, 0.5], [-0.5, 0.5], [-2.5, -1.5]])     # (d = 2: a box of well-conditioned models)
 FIT_P, FIT_MAXITER, FIT_SEED = 8, 4, 77
 WALK_PROBLEMS = ("B", "H", "C", "A", "B", "C", "H", "B")
+WALK3_PROBLEMS = ("B", "H", "C", "A", "B", "H", "C", "A")      # seeds 16 ..: the four problems, two seeds each
 SWEEPS = ("safeopt", "goose", "tr", "robust")
+
+
+def walk_problem(seed):
+    return WALK3_PROBLEMS[seed - THIRD_SEEDS[0]] if seed >= THIRD_SEEDS[0] else WALK_PROBLEMS[seed % len(WALK_PROBLEMS)]
 
 
 # ---- the generator (CPU only) ----------------------------------------------------------------------------------------------------
@@ -69,7 +96,7 @@ class _Gen:
         self.rng = np.random.default_rng(1000 + seed)
         self.seed = seed
         self.steps = []
-        self.problem = WALK_PROBLEMS[seed % len(WALK_PROBLEMS)]
+        self.problem = walk_problem(seed)
         self.b = float(synthetic.CONFIGS[PROBLEMS[self.problem][0]]["b"])
         self.grid = None
         self.on_list = False
@@ -348,8 +375,188 @@ def _make_walk2(seed):
     return g.steps
 
 
+class _Gen3(_Gen2):
+    """Seeds 16 ..: expander_gain and sample_paths among the read-only calls, read-only calls directly behind a model change, on an
+    fp32 model and behind a caller's prior.  The sweeps of these segments are named, not drawn: a SafeOpt or GoOSE sweep of a changed
+    model is a NumPy expander reference of its own."""
+
+    def __init__(self, seed):
+        super().__init__(seed)
+        self.paths = 0             # sample_paths steps so far: output q - 1 and 0 in turn, maximize alternates
+        self.turn = seed           # the sweep kinds behind direct calls, in turn
+
+    def plain_grid(self):
+        if self.on_list or self.grid not in GRIDS:
+            self.to_grid(self.grid if self.grid in GRIDS else "t128x64")
+
+    def call(self, name, under="", mask=0):
+        if name == "expander_gain":
+            self.emit(name, mask, under)
+        elif name == "sample_paths":
+            self.emit(name, "first" if self.paths % 2 else "last", (self.paths + self.seed) % 2 == 0, int(self.rng.integers(1 << 30)), under)
+            self.paths += 1
+        elif name == "batch_select":
+            self.emit(name, 4)
+        else:
+            self.emit(name)
+
+    def change(self, label):
+        if label.startswith("set_model_invK"):
+            self.emit("set_model", self.problem, "f64", label.endswith("1"))
+        elif label == "append":
+            self.emit("append", 1, "direct")
+        elif label.startswith("remove_"):
+            self.emit("remove", label[len("remove_"):], "direct")
+        elif label.startswith("append_block_"):
+            self.emit("append_block", int(label[len("append_block_"):]), "direct")
+        elif label == "fit":
+            self.emit("fit", "direct")
+        else:
+            assert label == "set_prior", label
+            self.emit("set_prior")
+
+    def next_kind(self):
+        self.turn += 1
+        return ("tr", "robust", "goose", "tr", "safeopt", "robust")[self.turn % 6]
+
+    def seg_single(self, name, ctx, kind):
+        """One of the two new calls with K1i, K1b or K1g resident, or on a list: behind a sweep, in front of a sweep of `kind` on
+        posterior_ready, and again behind that sweep."""
+        if ctx == "list":
+            self.emit("option", "list_index", int(self.rng.choice([-1, 0, 1])))
+            self.on_list = True
+            self.emit("set_points", str(self.rng.choice(list(LISTS))))
+            self.sweep(str(self.rng.choice(["safeopt", "goose"])), ready=False, b=self.b, lean=0)
+        else:
+            self.under(ctx)
+        self.call(name, under=ctx if ctx in UNDER else "")
+        self.sweep(kind, ready=True, b=self.b, lean=0)
+        self.emit("again", name)
+        if ctx == "K1g":
+            self.emit("option", "bilinear", 1)
+        if ctx == "list":
+            self.emit("option", "list_index", -1)
+
+    def seg_pair(self, first, kind):
+        """Both new calls, the second directly behind the first, between a sweep and a sweep of `kind` on posterior_ready; then both
+        again.  Problem C: expander_gain runs with a one-bit mask too."""
+        if kind == "robust":
+            self.plain_grid()
+        if self.grid == "t256x128" and not self.on_list:
+            self.to_grid("r130x70")
+        self.sweep(str(self.rng.choice(["safeopt", "goose"])), ready=False, b=self.b, lean=0)
+        for name in (first, NEW_CALLS[1 - NEW_CALLS.index(first)]):
+            self.call(name)
+            if name == "expander_gain" and self.problem == "C":
+                self.call(name, mask=int(self.rng.choice([2, 4])))
+        self.sweep(kind, ready=True, b=self.b, lean=0)
+        self.emit("again", NEW_CALLS[0])
+        self.emit("again", NEW_CALLS[1])
+
+    def seg_direct(self, *pairs):
+        """A fresh model and a sweep; then, per (change, call): the model-changing step, the read-only call directly behind it, a sweep.
+        The refine calls start from the winner of the sweep before the change, so they stand first, behind a set_model of the same model."""
+        self.plain_grid()
+        back, first = self.grid, pairs[0][1]
+        if first == "refine_robust":
+            self.to_grid("i128x64")
+            self.model()
+            self.sweep("robust", ready=False, b=self.b)
+        else:
+            self.model()
+            self.sweep("safeopt" if first in ("refine", "refine_sets") else str(self.rng.choice(["safeopt", "goose"])), ready=False, b=self.b, lean=0)
+        for label, name in pairs:
+            self.change(label)
+            self.call(name)
+            self.sweep(self.next_kind(), ready=bool(self.rng.integers(2)), b=self.b, lean=0)
+        if first == "refine_robust":
+            self.to_grid(back)
+        self.model()                                      # (the segments behind this one start from the problem's own model)
+        self.sweep("safeopt", ready=False, lean=0)
+
+    def seg_set_prior(self, first):
+        """A caller's prior that is not zero: both new calls (the first directly behind the change) and two sweeps, then the model back."""
+        self.plain_grid()
+        self.model()
+        self.sweep("safeopt", ready=False, lean=0)
+        self.change("set_prior")
+        self.call(first)
+        self.sweep(self.next_kind(), ready=bool(self.rng.integers(2)), b=self.b, lean=0)
+        self.call(NEW_CALLS[1 - NEW_CALLS.index(first)])
+        self.sweep(self.next_kind(), ready=True, b=self.b, lean=0)
+        self.model()
+        self.sweep("safeopt", ready=False, lean=0)
+
+    def seg_f32_reads(self, behind, tail):
+        """An fp32 model with its twin: the four calls that read fp64 data whatever the model's dtype, each between two sweeps; the
+        fp64-only calls refused; an append, a block append and a removal, each with one of `behind` directly behind it; then
+        set_model(f64), an append and `tail`: the twin left behind is not that model's."""
+        self.plain_grid()
+        three = ["safeopt", "goose", "tr"]
+        self.model("f32")
+        self.sweep(str(self.rng.choice(three)), ready=False, b=self.b, lean=0)
+        for name in F32_READS:
+            self.call(name)
+            self.sweep(str(self.rng.choice(three)), ready=True, b=self.b, lean=0)
+        self.emit("refuse", "f64_only_on_f32")
+        self.sweep(str(self.rng.choice(three)), ready=True, b=self.b, lean=0)
+        for step, name in zip((("append", 1, "f32"), ("append_block", 3, "f32"), ("remove", "middle", "f32")), behind):
+            self.emit(*step)
+            self.call(name)
+            self.sweep(str(self.rng.choice(["goose", "tr"])), ready=bool(self.rng.integers(2)), b=self.b)
+        self.model("f64")
+        self.emit("append", 1, "f64_after_f32")
+        self.call(tail)
+        self.sweep("tr", ready=bool(self.rng.integers(2)), b=self.b)
+
+
+# seeds 16 ..: per seed the segments of _Gen3 (and seg_read_only of _Gen2 for one of the eight older calls), in the order the seed shuffles
+THIRD_PLAN = {
+    16: [("single", "expander_gain", "K1b", "safeopt"), ("pair", "expander_gain", "goose"), ("read_only", "loo", "tr"),
+         ("direct", ("set_model_invK1", "refine"), ("append", "expander_gain"), ("remove_first", "sample_paths"),
+          ("append_block_1", "expander_gain"), ("fit", "sample_paths"))],
+    17: [("single", "sample_paths", "K1g", "goose"), ("pair", "sample_paths", "tr"), ("read_only", "mean_grad", "robust"),
+         ("direct", ("set_model_invK0", "refine_sets"), ("append", "sample_paths"), ("remove_middle", "expander_gain"),
+          ("append_block_3", "sample_paths"), ("fit", "expander_gain"))],
+    18: [("single", "expander_gain", "K1i", "tr"), ("pair", "expander_gain", "robust"), ("read_only", "lipschitz", "safeopt"),
+         ("direct", ("set_model_invK1", "expander_gain"), ("remove_last", "sample_paths"), ("append_block_17", "expander_gain"),
+          ("remove_middle", "loo"))],
+    19: [("single", "sample_paths", "K1i", "robust"), ("pair", "sample_paths", "safeopt"), ("read_only", "batch_select", "goose"),
+         ("direct", ("set_model_invK0", "sample_paths"), ("remove_first", "expander_gain"), ("append_block_1", "sample_paths"),
+          ("append_block_3", "mean_grad"))],
+    20: [("single", "expander_gain", "list", "goose"), ("pair", "expander_gain", "tr"), ("read_only", "refine", "robust"),
+         ("direct", ("set_model_invK1", "sample_paths"), ("remove_middle", "sample_paths"), ("append_block_3", "expander_gain"),
+          ("append_block_17", "lipschitz")),
+         ("f32_reads", ("loo", "expander_gain", "batch_select"), "sample_paths")],
+    21: [("single", "sample_paths", "list", "safeopt"), ("pair", "sample_paths", "goose"), ("read_only", "refine_sets", "tr"),
+         ("direct", ("set_model_invK0", "expander_gain"), ("remove_last", "expander_gain"), ("append_block_17", "sample_paths"),
+          ("append", "batch_select")),
+         ("f32_reads", ("sample_paths", "batch_select", "expander_gain"), "expander_gain")],
+    22: [("single", "expander_gain", "K1g", "robust"), ("pair", "expander_gain", "safeopt"), ("read_only", "refine_robust", "goose"),
+         ("direct", ("set_model_invK1", "refine_robust"), ("remove_first", "nll")), ("set_prior", "expander_gain")],
+    23: [("single", "sample_paths", "K1b", "tr"), ("pair", "sample_paths", "robust"), ("read_only", "nll", "safeopt"),
+         ("direct", ("remove_middle", "expander_gain"), ("append_block_17", "sample_paths")), ("set_prior", "sample_paths")],
+}
+
+
+def _make_walk3(seed):
+    g = _Gen3(seed)
+    g.to_grid(str(g.rng.choice(["t128x64", "r130x70", "r96x50"])))
+    g.model()
+    g.sweep("safeopt", ready=False, lean=0)
+    segs = THIRD_PLAN[seed]
+    for i in g.rng.permutation(len(segs)):
+        name, *args = segs[i]
+        getattr(g, "seg_" + name)(*args)
+    for key in g.touched:
+        g.emit("option", key, DEFAULTS[key])
+    return g.steps
+
+
 def make_walk(seed):
     """The step list of walk ``seed`` (deterministic: the seed is all a replay needs)."""
+    if seed >= THIRD_SEEDS[0]:
+        return _make_walk3(seed)
     if seed >= NEW_SEEDS[0]:
         return _make_walk2(seed)
     g = _Gen(seed)
@@ -370,8 +577,21 @@ def make_walk(seed):
     return g.steps
 
 
-def transitions(steps):
-    """Names of the required transitions a step list contains (what the CPU test asserts over the fixed seeds)."""
+def change_label(s):
+    """The name of a model-changing step as CHANGES has it (None: the step changes no model)."""
+    kind = s[0]
+    if kind == "set_model":
+        return "set_model_f32" if s[2] != "f64" else "set_model_invK%d" % int(s[3] if len(s) > 3 else True)
+    if kind == "remove":
+        return "remove_" + s[1]
+    if kind == "append_block":
+        return "append_block_%d" % s[1]
+    return kind if kind in ("append", "fit", "set_prior", "set_prior_zero") else None
+
+
+def transitions(steps, third=False):
+    """Names of the required transitions a step list contains (what the CPU test asserts over the fixed seeds).  ``third``: the walk
+    is one of seeds 16 .., where a read-only call may stand directly behind a model change and on an fp32 model."""
     out = set()
     last_sweep = None
     model_sweeps = 0
@@ -380,14 +600,30 @@ def transitions(steps):
     dtypes = []
     cands = []
     grid = None
-    pending = None               # a read-only step waiting for its posterior_ready sweep
+    pending = None               # a read-only step waiting for its sweep: (step name, directly behind a model change)
+    prev_change = None           # the label of the model-changing step directly in front of this step
+    stale_sweep = None           # the last sweep in front of that change
+    recent, swept = [], []       # the new calls since the last sweep; those a posterior_ready sweep has followed since
+    prior_seg = None             # behind set_prior, until the next set_model: [new calls, sweeps]
     for i, s in enumerate(steps):
         kind = s[0]
+        if kind == "again":
+            assert third and s[1] in swept, (i, s, "a repeated call stands behind the posterior_ready sweep that followed the first")
+            out.add("again_" + s[1])
+            continue
         if pending is not None:
-            ready = kind in SWEEPS and (s[2] if kind == "goose" else s[3])
-            assert ready, (i, s, "a read-only step is followed by a sweep on posterior_ready")
-            out.add(f"{pending}->{kind}_ready")
+            name, direct = pending
             pending = None
+            if third and kind in NEW_CALLS and name in NEW_CALLS and not direct:
+                out.add(f"{name}->{kind}")                  # the second of a pair stands directly behind the first
+            else:
+                ready = kind in SWEEPS and (s[2] if kind == "goose" else s[3])
+                assert ready or (direct and kind in SWEEPS), (i, s, "a read-only step is followed by a sweep (on posterior_ready unless "
+                                                                    "the step stood directly behind a model change)")
+                if not direct:
+                    out.add(f"{name}->{kind}_ready")
+        if kind not in SWEEPS:
+            swept = []
         if kind in SWEEPS:
             ready = s[2] if kind == "goose" else s[3]
             if ready and last_sweep is not None and last_sweep[0] == "safeopt":
@@ -398,17 +634,55 @@ def transitions(steps):
                 out.add("refused->sweep")
             last_sweep = s
             model_sweeps += 1
+            swept, recent = (recent if ready else []), []
+            if prior_seg is not None:
+                prior_seg[1] += 1
         elif kind == "set_model":
+            if prior_seg is not None and set(prior_seg[0]) == set(NEW_CALLS) and prior_seg[1] >= 2:
+                out.add("set_prior_segment")
+            prior_seg = None
+            stale_sweep = last_sweep
             model_sweeps = 0
             last_sweep = None
             dtypes.append(s[2])
-        elif kind in READ_ONLY:
-            assert dtypes[-1] == "f64" and model_sweeps >= 1, (i, s)
-            assert kind != "refine_robust" or (last_sweep[0] == "robust" and not on_list), (i, s)
-            assert kind != "refine_sets" or last_sweep[0] == "safeopt", (i, s)
-            pending = kind
+        elif kind in READ_ONLY3:
+            direct = prev_change is not None
+            f32 = dtypes[-1] != "f64"
+            if not third:
+                assert kind in READ_ONLY and not f32 and model_sweeps >= 1 and not direct, (i, s)
+            assert kind in F32_READS or not f32, (i, s)
+            assert direct == (last_sweep is None), (i, s, "a read-only step stands behind a sweep, or directly behind a model change")
+            before = stale_sweep if direct else last_sweep
+            assert kind != "refine_robust" or (before[0] == "robust" and not on_list), (i, s)
+            assert kind != "refine_sets" or before[0] == "safeopt", (i, s)
+            assert kind not in ("refine", "refine_sets", "refine_robust") or not direct or prev_change.startswith("set_model_invK"), (i, s)
+            if kind in NEW_CALLS:
+                if s[-1] in UNDER:
+                    expect = "K1g" if opts["bilinear"] == 0 else ("K1i" if model_sweeps == 1 else "K1b")
+                    assert not on_list and not direct and not f32 and expect == s[-1], (i, s, model_sweeps, opts["bilinear"])
+                    out.add(f"{kind}_under_{s[-1]}")
+                if on_list and not direct:
+                    out.add(kind + "_on_list")
+                if kind == "expander_gain" and s[1] != 0:
+                    out.add("expander_gain_one_bit")
+                if kind == "sample_paths":
+                    out.add("sample_paths_output_" + {"first": "0", "last": "last"}[s[1]])
+                    out.add("sample_paths_max" if s[2] else "sample_paths_min")
+                if not direct:
+                    recent.append(kind)
+                if prior_seg is not None:
+                    prior_seg[0].append(kind)
+            if direct:
+                out.add(f"direct:{'f32:' if f32 else ''}{prev_change}->{kind}")
+                if stale_sweep is not None and stale_sweep[0] == "robust":
+                    out.add("direct_read_robust_refused")
+                if steps[i - 1][-1] == "f64_after_f32":
+                    out.add("append_after_f32_then_f64->" + kind)
+            elif f32:
+                out.add("f32_read_" + kind)
+            pending = (kind, direct)
         elif kind in MODEL_STEPS or (kind == "append" and s[2] not in UNDER):
-            under = s[-1] if kind != "set_prior_zero" else None
+            under = s[-1] if kind not in ("set_prior_zero", "set_prior") else None
             if last_sweep is not None and last_sweep[0] in ("safeopt", "goose"):
                 out.add("mask_refused_after_model_change")
             if last_sweep is not None and last_sweep[0] == "robust":
@@ -426,9 +700,14 @@ def transitions(steps):
             elif under == "f64_after_f32":
                 assert kind == "append" and dtypes[-2:] == ["f32", "f64"] and model_sweeps == 0, (i, s)
                 out.add("append_after_f32_then_f64")
+            elif under == "direct":
+                assert third and dtypes[-1] == "f64" and last_sweep is not None, (i, s)
             else:
-                assert kind == "set_prior_zero", (i, s)
+                assert kind in ("set_prior_zero", "set_prior") and (third or kind == "set_prior_zero"), (i, s)
                 model_sweeps = 0
+                if kind == "set_prior":
+                    prior_seg = [[], 0]
+            stale_sweep = last_sweep
             last_sweep = None
         elif kind == "append":
             out.add("append_under_" + s[2])
@@ -451,12 +730,20 @@ def transitions(steps):
             cands.append("list")
         elif kind in ("posterior", "posterior_run", "explore"):
             out.add(kind)
+        elif kind == "refuse" and s[1] == "f64_only_on_f32":
+            assert third and dtypes[-1] == "f32" and last_sweep is not None, (i, s)
+            out.add("refuse_f64_only_on_f32")
+        prev_change = change_label(s) if kind == "set_model" or kind in MODEL_STEPS or (kind == "append" and s[2] not in UNDER) else None
     if any(cands[j:j + 3] == ["list", "grid", "list"] for j in range(len(cands))):
         out.add("list->grid->list")
     if any(dtypes[j:j + 3] == ["f32", "f64", "f32"] for j in range(len(dtypes))):
         out.add("f32->f64->f32")
     assert pending is None, "a walk does not end on a read-only step"
     return out
+
+
+def walk_transitions(seed):
+    return transitions(make_walk(seed), third=seed >= THIRD_SEEDS[0])
 
 
 REQUIRED = ({f"lean{lv}->{k}_ready" for lv in (0, 1, 2) for k in READY_KINDS} |
@@ -467,15 +754,38 @@ REQUIRED = ({f"lean{lv}->{k}_ready" for lv in (0, 1, 2) for k in READY_KINDS} |
              "mask_refused_after_model_change", "robust_arrays_refused_after_remove", "robust_arrays_refused_after_append_block",
              "robust_arrays_refused_after_fit"} |
             {f"option_{k}_{v}" for k, v in NEW_OPTION_VALUES})
+# what seeds 16 .. add: the two new calls in front of every sweep kind, with each plan resident, on a list, behind each other, repeated
+# around a sweep and directly behind every model-changing step; each of the ten read-only calls directly behind some model change
+# (direct_leaders); the four dtype-free calls on an fp32 model and behind its updates; the prior and the new refusal
+REQUIRED3 = ({f"{c}->{k}_ready" for c in READ_ONLY3 for k in READY_KINDS if c in NEW_CALLS} |
+             {f"{c}_under_{u}" for c in NEW_CALLS for u in UNDER} | {c + "_on_list" for c in NEW_CALLS} | {"again_" + c for c in NEW_CALLS} |
+             {"expander_gain->sample_paths", "sample_paths->expander_gain", "expander_gain_one_bit", "sample_paths_output_0",
+              "sample_paths_output_last", "sample_paths_max", "sample_paths_min"} |
+             {f"direct:{m}->{c}" for m in CHANGES for c in NEW_CALLS} |
+             {"direct_read_robust_refused", "set_prior_segment", "refuse_f64_only_on_f32", "f32_append", "f32_append_block", "f32_remove",
+              "append_after_f32_then_f64"} |
+             {"f32_read_" + c for c in F32_READS})
 
 
-def read_only_followers(seen):
+def read_only_followers(seen, calls=READ_ONLY):
     """{read-only step: sweep kinds found behind it on posterior_ready} of a set of transition names."""
-    out = {k: set() for k in READ_ONLY}
+    out = {k: set() for k in calls}
     for name in seen:
         head, _, tail = name.partition("->")
         if head in out and tail.endswith("_ready"):
             out[head].add(tail[:-len("_ready")])
+    return out
+
+
+def direct_leaders(seen, f32=False):
+    """{read-only step: the model-changing steps found directly in front of it} of a set of transition names (``f32``: on an fp32
+    model, behind its updates)."""
+    out = {k: set() for k in (F32_READS if f32 else READ_ONLY3)}
+    head = "direct:f32:" if f32 else "direct:"
+    for name in seen:
+        if name.startswith(head) and (f32 or not name.startswith("direct:f32:")):
+            change, _, call = name[len(head):].partition("->")
+            out[call].add(change)
     return out
 
 
@@ -531,7 +841,7 @@ class Walk:
         self.last = None           # (kind, oracle result) of the last sweep that left masks
         self.cache = {}
         self.rng = np.random.default_rng(5000 + seed)
-        self.walk_problem = problem or WALK_PROBLEMS[seed % len(WALK_PROBLEMS)]
+        self.walk_problem = problem or walk_problem(seed)
         self.bound = _problem(self.walk_problem)["bound"]
         self.box = (self.bound[:, 0], self.bound[:, 1])     # of the resident candidates: the domain, or an INSIDE grid's small box
         self.append_kernels = set()     # posterior kernel of the sweep before each append
@@ -544,6 +854,15 @@ class Walk:
         self.rob_kept = None              # robust_arrays() behind the last robust sweep
         self.winner = None              # the last sweep's winner x [d], the seed of the refine steps
         self.last_sweep = None          # the last sweep's step
+        self.has_masks = False          # the last sweep left masks or robust arrays (also kept in the dry mode)
+        self.changed_by = None          # change_label of the model-changing step since which nothing has swept
+        self.stale = None               # (winner, last_sweep, last) of the last sweep in front of that change, and whether it was robust
+        self.stale_robust = False
+        self.kept = {}                  # new call -> (ds_ver, arguments, result) of its last run, for the "again" step
+        self.calls = []                 # per new call: {step, kind, kernel resident, on_list, dtype, direct (a change label or None)}
+        self.direct = {}                # read-only call -> the change labels it stood directly behind
+        self.devs = {}                  # new call -> the largest deviation from its reference
+        self.direct_robust = 0          # direct read-only calls around which robust_arrays() was asserted refused
 
     # references, cached on (dataset, candidates, arguments)
     def _ref(self, kind, *args):
@@ -569,6 +888,10 @@ class Walk:
             self.index = i
             try:
                 self.step(step)
+                if step[0] in SWEEPS:
+                    self.changed_by = None
+                elif self.last_sweep is None and change_label(step) is not None:
+                    self.changed_by = change_label(step)
             except Exception as e:                                 # noqa: BLE001
                 listing = "\n".join(f"  {j:3d} {s!r}" for j, s in enumerate(self.steps[:i + 1]))
                 raise AssertionError(f"history walk seed {self.seed}, step {i}: {step!r}\n"
@@ -581,7 +904,10 @@ class Walk:
 
     def _changed(self):
         """A candidate or model change: nothing the last sweep left is readable any more."""
+        if self.last_sweep is not None:
+            self.stale, self.stale_robust = (self.winner, self.last_sweep, self.last), self.last_sweep[0] == "robust"
         self.last, self.masks, self.rob_kept, self.winner, self.last_sweep = None, None, None, None, None
+        self.has_masks = False
 
     def _model_changed(self):
         """Behind a model-changing step: the masks are refused, and so are the robust arrays of an earlier robust sweep."""
@@ -595,17 +921,28 @@ class Walk:
 
     def _unchanged(self):
         """Behind a read-only step: the masks of the last sweep are still readable, byte for byte; so are the robust arrays."""
+        if not self.has_masks:
+            raise RuntimeError("a read-only step stands behind a sweep that left masks or robust arrays")
         if self.dry:
             return
-        if self.masks is None and self.rob_kept is None:
-            raise RuntimeError("a read-only step stands behind a sweep that left masks or robust arrays")
         for (k, c), m in (self.masks or {}).items():
             assert np.array_equal(self.eng.mask(k, c), m), ("mask changed by a read-only call", k, c)
         if self.rob_kept is not None:
             f, g = self.eng.robust_arrays()
             assert f.tobytes() == self.rob_kept[0].tobytes() and g.tobytes() == self.rob_kept[1].tobytes(), "robust arrays changed"
 
+    def _still_refused(self):
+        """Around a read-only call directly behind a model change: the masks stay refused, and so do the robust arrays of a robust
+        sweep in front of the change -- a reader waits for the factor, it does not make the last sweep's results readable again."""
+        if self.dry:
+            return
+        self._raises(lambda: self.eng.mask("S"))
+        if self.stale_robust:
+            self._raises(lambda: self.eng.robust_arrays())
+            self.direct_robust += 1
+
     def _keep_masks(self, names):
+        self.has_masks = True
         self.masks = None if self.dry else {(k, c): self.eng.mask(k, c) for k, c in names}
         self.rob_kept = None
 
@@ -661,6 +998,7 @@ class Walk:
             self.cand = ("grid", s[1])
             self.pts = oracle.grid_points(self.box[0], self.box[1], ALL_GRIDS[s[1]])
             self._changed()
+            self.changed_by = None
         elif kind == "set_points":
             pts = _list_points(self.walk_problem, s[1])
             if not self.dry:
@@ -669,13 +1007,17 @@ class Walk:
             self.pts = pts
             self.box = (self.bound[:, 0], self.bound[:, 1])
             self._changed()
+            self.changed_by = None
         elif kind == "set_model":
             self.problem, self.dtype = s[1], s[2]
             cfg = _problem(s[1])
             self.ds = {k: (list(v) if k == "invKopt" else np.array(v)) for k, v in cfg["ds"].items()}
             self.ds_ver += 1
+            use_invK = s[3] if len(s) > 3 else s[2] == "f64"
+            if s[2] == "f64" and not use_invK:          # (the library factors K itself: the oracle's inverse of the hyper-parameters)
+                self.ds["invKopt"] = oracle.build_invK(self.ds["X_norm"], self.ds["hypopt"])
             if not self.dry:
-                eng.set_model(self.ds, dtype=s[2], use_invK=s[2] == "f64")
+                eng.set_model(self.ds, dtype=s[2], use_invK=use_invK)
             self._changed()
         elif kind == "append":
             n_new = s[1]
@@ -723,16 +1065,30 @@ class Walk:
             if not self.dry:
                 eng.set_model(self.ds, dtype="f64", use_invK=True, mean_prior=self.ds["mean_prior"])
             self._model_changed()
-        elif kind in READ_ONLY:
-            if self.dtype != "f64" or self.last_sweep is None:
-                raise RuntimeError(f"{kind}: needs an fp64 model and a sweep before it")
-            getattr(self, "ro_" + kind)(*s[1:])
+        elif kind == "set_prior":
+            mp = np.array(PRIOR[:self.ds["Y_norm"].shape[1]])
+            self.ds = dict(self.ds, mean_prior=mp)
+            if not self.dry:
+                eng.set_model(self.ds, dtype="f64", use_invK=True, mean_prior=mp)
+            self._model_changed()
+        elif kind in READ_ONLY3:
+            self.read_only(kind, s[1:])
+        elif kind == "again":
+            ver, args, first = self.kept[s[1]]
+            if ver != self.ds_ver or self.last_sweep is None:
+                raise RuntimeError("again: the call is repeated on the same model, behind a sweep")
+            if not self.dry:
+                second = self.run_new(s[1], args)
+                for k in first:
+                    assert first[k].tobytes() == second[k].tobytes(), (s[1], "repeated behind a sweep", k)
             self._unchanged()
         elif kind == "option":
             if not self.dry:
                 eng.set_option(s[1], s[2])
         elif kind == "refuse":
-            if not self.dry:
+            if s[1] == "f64_only_on_f32":
+                self.refuse_f64_only()
+            elif not self.dry:
                 self.refuse(s[1])
         elif kind == "safeopt":
             self.safeopt(*s[1:])
@@ -816,9 +1172,9 @@ class Walk:
         self._margin("safeopt", ref)
         self.last_sweep = ("safeopt", b, lean, ready, quirk)
         if ref["empty_safe_set"]:
-            self.last, self.masks, self.rob_kept, self.winner = None, None, None, None
+            self.last, self.masks, self.rob_kept, self.winner, self.has_masks = None, None, None, None, False
             return None if self.dry else self._empty(ref, call)
-        self.winner = self.pts[ref["minimizer_index"]]
+        self.winner, self.has_masks = self.pts[ref["minimizer_index"]], True
         if self.dry:
             self.last = ("safeopt", ref)
             return
@@ -850,9 +1206,9 @@ class Walk:
         self._margin("goose", ref)
         self.last_sweep = ("goose", b, ready)
         if ref["empty_safe_set"]:
-            self.last, self.masks, self.rob_kept, self.winner = None, None, None, None
+            self.last, self.masks, self.rob_kept, self.winner, self.has_masks = None, None, None, None, False
             return None if self.dry else self._empty(ref, call)
-        self.winner = self.pts[ref["safe_min_index"]]
+        self.winner, self.has_masks = self.pts[ref["safe_min_index"]], True
         if self.dry:
             self.last = ("goose", ref)
             return
@@ -879,7 +1235,7 @@ class Walk:
         self._margin("tr", ref, x0, r)
         self.last_sweep = ("tr", b, r, ready)
         # (an empty trust region, or an empty safe set, is no error of sbo_sweep_tr: index -1 -- include/safebo.h: sbo_tr_result)
-        self.winner = self.pts[ref["index"]] if not ref["empty"] else None
+        self.winner, self.has_masks = (self.pts[ref["index"]] if not ref["empty"] else None), True
         if self.dry:
             return
         res = call()
@@ -891,6 +1247,7 @@ class Walk:
         ref = self._ref("robust", b, kind)
         self.last_sweep = ("robust", b, kind, ready)
         self.winner = self.pts[ref["index"]][:1] if ref["index"] >= 0 else None      # (axis 0 is the control, the fastest)
+        self.has_masks = True
         if self.dry:
             g = ref["g"] / np.maximum(1.0, self.ds["Y_std"])[1:, None]
             self.margins.append((self.index, "robust", float(np.min(np.abs(g))) if g.size else np.inf))
@@ -1042,3 +1399,107 @@ class Walk:
             ref, g = nll_grad_oracle.nll_grad(h, X, y)
             assert abs(nll[p] - ref) <= 1e-9 * max(1.0, abs(ref)), ("nll", p, nll[p], ref)
             assert np.all(np.abs(grad[p] - g) <= 1e-8 * nll_grad_oracle.grad_scale(h, X, y) + 1e-300), ("nll grad", p, grad[p], g)
+
+    # ---- seeds 16 ..: the two new calls, and read-only calls directly behind a model change or on an fp32 model ----------------------
+    def read_only(self, kind, args):
+        """A read-only step.  Behind a sweep: checked, and the sweep's masks and robust arrays are unchanged afterwards.  Directly
+        behind a model change (nothing has swept since): checked with the arguments the sweep in front of the change left -- its b,
+        its winner --, and mask("S") is refused before the call and still refused after it."""
+        if self.dtype != "f64" and kind not in F32_READS:
+            raise RuntimeError(f"{kind}: needs an fp64 model")
+        direct = self.last_sweep is None
+        if direct and (self.changed_by is None or self.stale is None):
+            raise RuntimeError(f"{kind}: needs a sweep before it, or a model change behind a sweep")
+        kernel = None if self.dry else int(self.eng.profile()["posterior_kernel"])
+        if direct:
+            self._still_refused()
+            self.winner, self.last_sweep, self.last = self.stale
+        try:
+            getattr(self, "ro_" + kind)(*args)
+        finally:
+            if direct:
+                self.winner, self.last_sweep, self.last = None, None, None
+        if direct:
+            self._still_refused()
+            self.direct.setdefault(kind, set()).add(("f32:" if self.dtype != "f64" else "") + self.changed_by)
+        else:
+            self._unchanged()
+        if kind in NEW_CALLS:
+            self.calls.append({"step": self.index, "kind": kind, "kernel": kernel, "on_list": self.cand[0] == "list", "dtype": self.dtype,
+                               "direct": self.changed_by if direct else None})
+
+    def _sharp(self, kind, *figures):
+        """A condition on the inputs, not on the device: the reference decides every count, witness and index by more than SHARP."""
+        self.margins.append((self.index, kind, float(min(figures))))
+        if not min(figures) > SHARP:
+            raise RuntimeError(f"{kind}: the reference is blunt {figures}: change this seed's draw, not the bar")
+
+    def _dev(self, kind, err):
+        self.devs[kind] = max(self.devs.get(kind, 0.0), err)
+
+    def run_new(self, kind, args):
+        """The engine's call of a new step from its kept arguments: every array it returns."""
+        if kind == "expander_gain":
+            S, T, b, cons = args
+            return self.eng.expander_gain(S, T, b, cons, return_margin=True)
+        pts, o, draws, maximize = args
+        return self.eng.sample_paths(pts, SP_PATHS, o, draws=draws, maximize=maximize, return_values=True)
+
+    def ro_expander_gain(self, mask, under=""):
+        """9 sources (the first the last sweep's winner, where there is one) against 257 targets in the box, b of the last sweep: count
+        and witness are expander_oracle.gain_naive's on the walk's rows exactly, margin within TOL64."""
+        lo, hi = self.box
+        S = self.rng.uniform(lo, hi, size=(EG_SOURCES, len(lo)))
+        T = self.rng.uniform(lo, hi, size=(EG_TARGETS, len(lo)))
+        if self.winner is not None and len(self.winner) == len(lo):
+            S[0] = self.winner
+        b, q = self.last_sweep[1], self.ds["Y_norm"].shape[1]
+        ref = expander_oracle.gain_naive(self.ds, b, S, T, mask)
+        self._sharp("expander_gain", *expander_oracle.sharpness(ref))
+        args = (S, T, b, None if mask == 0 else expander_oracle.constraints_of(q, mask))
+        self.kept["expander_gain"] = (self.ds_ver, args, None)
+        if self.dry:
+            return
+        got = self.run_new("expander_gain", args)
+        self.kept["expander_gain"] = (self.ds_ver, args, got)
+        assert np.array_equal(got["count"], ref["count"]), ("expander_gain count", got["count"], ref["count"])
+        assert np.array_equal(got["witness"], ref["witness"]), ("expander_gain witness", got["witness"], ref["witness"])
+        assert np.array_equal(got["expander"], ref["count"] > 0)
+        err = float(np.max(np.abs(got["margin"] - ref["margin"])))
+        self._dev("expander_gain", err)
+        assert err < expander_oracle.TOL64, ("expander_gain margin", err)
+
+    def ro_sample_paths(self, which, maximize, seed, under=""):
+        """257 points in the box, 17 paths of 257 features from SweepEngine.path_draws(seed), output 0 or q - 1 (whose prior mean is not
+        zero): the indices are paths_oracle.paths_solve's on the walk's rows exactly, the normalised values within TOL64."""
+        lo, hi = self.box
+        pts = self.rng.uniform(lo, hi, size=(SP_POINTS, len(lo)))
+        n, q = self.ds["Y_norm"].shape
+        o = q - 1 if which == "last" else 0
+        draws = SweepEngine.path_draws(len(lo), n, SP_PATHS, SP_FEATURES, seed)
+        f = paths_oracle.paths_solve(self.ds, o, draws, pts)
+        self._sharp("sample_paths", paths_oracle.sharpness(f, maximize))
+        args = (pts, o, draws, bool(maximize))
+        self.kept["sample_paths"] = (self.ds_ver, args, None)
+        if self.dry:
+            return
+        got = self.run_new("sample_paths", args)
+        self.kept["sample_paths"] = (self.ds_ver, args, got)
+        idx, _ = paths_oracle.best(f, maximize)
+        assert np.array_equal(got["index"], idx), ("sample_paths index", got["index"], idx)
+        assert got["value"].tobytes() == got["values"][got["index"], np.arange(SP_PATHS)].tobytes()
+        err = float(np.max(np.abs((got["values"] - self.ds["Y_mean"][o]) / self.ds["Y_std"][o] - f)))
+        self._dev("sample_paths", err)
+        assert err < paths_oracle.TOL64, ("sample_paths values", err)
+
+    def refuse_f64_only(self):
+        """mean_grad, lipschitz and refine on an fp32 model: refused, and the masks of the sweep before are unchanged."""
+        if self.dtype != "f32" or self.last_sweep is None:
+            raise RuntimeError("f64_only_on_f32: needs an fp32 model and a sweep before it")
+        lo, hi = self.box
+        x = np.array(self.winner) if self.winner is not None and len(self.winner) == len(lo) else 0.5 * (lo + hi)
+        if not self.dry:
+            self._raises(lambda: self.eng.mean_grad(x[None], infnorm=True))
+            self._raises(lambda: self.eng.lipschitz(lo, hi))
+            self._raises(lambda: self.eng.refine(self.last_sweep[1], x, 0, "lcb", lo=lo, hi=hi))
+        self._unchanged()

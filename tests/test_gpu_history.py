@@ -20,6 +20,8 @@ KERNELS = {}          # seed -> [(step, kind, posterior_kernel, set_path)] of th
 APPENDS = {}          # seed -> posterior kernels resident at each append
 REMOVES, BLOCKS = {}, {}      # ... at each removal, at each block append
 ROBUST_REFUSALS = {}          # seed -> model-changing steps behind which robust_arrays() was asserted refused
+CALLS, DIRECT, DEVS = {}, {}, {}      # seed -> the new calls as run, {read-only call: change labels directly in front}, largest deviations
+DIRECT_ROBUST = {}            # seed -> direct read-only calls around which robust_arrays() was asserted refused
 
 
 @pytest.fixture(scope="module")
@@ -42,6 +44,9 @@ def _run_walk(engine, seed):
         KERNELS[seed] = w.run()
         APPENDS[seed], REMOVES[seed], BLOCKS[seed] = w.append_kernels, w.remove_kernels, w.block_kernels
         ROBUST_REFUSALS[seed] = w.robust_refusals
+        CALLS[seed], DIRECT[seed], DEVS[seed], DIRECT_ROBUST[seed] = w.calls, w.direct, w.devs, w.direct_robust
+        if w.devs:
+            print("seed", seed, "largest deviation per new step kind:", w.devs)
     finally:
         for k, v in hw.DEFAULTS.items():
             engine.set_option(k, v)
@@ -55,7 +60,10 @@ def test_history_walk(engine, seed):
 def test_history_walks_took_every_kernel_path(engine):
     """Over all walks, every posterior kernel a 2-D problem or a list can take ran and was checked -- generic (1 / 2), K1g (3), K1b (4),
     K1i (6) --, both set paths (byte masks, column words), and an append, a removal and a block append each found each of K1i, K1b and
-    K1g resident; a removal, a block append and a fit each stood directly behind a robust sweep, whose arrays were then refused."""
+    K1g resident; a removal, a block append and a fit each stood directly behind a robust sweep, whose arrays were then refused.
+    expander_gain and sample_paths each ran with each of K1i, K1b and K1g resident, on a list, on an fp32 model, and directly behind
+    each model-changing step (where mask("S") was refused before the call and after it); each of the ten read-only calls ran directly
+    behind some model change, each of the four dtype-free ones directly behind an fp32 update."""
     for seed in hw.SEEDS:
         if seed not in KERNELS:
             _run_walk(engine, seed)
@@ -67,6 +75,18 @@ def test_history_walks_took_every_kernel_path(engine):
     assert {3, 4, 6} <= set().union(*APPENDS.values()), APPENDS
     assert {3, 4, 6} <= set().union(*REMOVES.values()) and {3, 4, 6} <= set().union(*BLOCKS.values()), (REMOVES, BLOCKS)
     assert sum(ROBUST_REFUSALS.values()) >= 3 and all(ROBUST_REFUSALS[seed] >= 1 for seed in (9, 12, 15)), ROBUST_REFUSALS
+    calls = [c for rec in CALLS.values() for c in rec]
+    direct = {k: set().union(*(d.get(k, set()) for d in DIRECT.values())) for k in hw.READ_ONLY3}
+    for kind in hw.NEW_CALLS:
+        mine = [c for c in calls if c["kind"] == kind]
+        resident = {c["kernel"] for c in mine if c["direct"] is None and not c["on_list"] and c["dtype"] == "f64"}
+        assert {3, 4, 6} <= resident, (kind, sorted(resident))
+        assert any(c["on_list"] for c in mine) and any(c["dtype"] == "f32" for c in mine), kind
+        assert set(hw.CHANGES) <= direct[kind], (kind, sorted(direct[kind]))
+    assert all(direct[k] for k in hw.READ_ONLY3), direct
+    assert all({d for d in direct[k] if d.startswith("f32:")} for k in hw.F32_READS), direct
+    assert sum(DIRECT_ROBUST.values()) >= 2, DIRECT_ROBUST
+    print("largest deviation per new step kind over all walks:", {k: max(d.get(k, 0.0) for d in DEVS.values()) for k in hw.NEW_CALLS})
 
 
 # ---- directed sequences ----------------------------------------------------------------------------------------------------------
@@ -381,13 +401,26 @@ def _ro_nll(eng, ds, res):
     assert np.isfinite(eng.nll_batch(ds["X_norm"], ds["Y_norm"][:, 0], H)).all()
 
 
-READ_ONLY = [_ro_loo, _ro_mean_grad, _ro_lipschitz, _ro_batch_select, _ro_refine, _ro_refine_sets, _ro_nll]
+def _ro_expander_gain(eng, ds, res):
+    lo, hi = _h_box()
+    rng = np.random.default_rng(34)
+    assert eng.expander_gain(rng.uniform(lo, hi, size=(9, 2)), rng.uniform(lo, hi, size=(257, 2)), 1.0)["count"].shape == (9,)
+
+
+def _ro_sample_paths(eng, ds, res):
+    lo, hi = _h_box()
+    out = eng.sample_paths(np.random.default_rng(35).uniform(lo, hi, size=(257, 2)), 17, 1, features=257, seed=36)
+    assert np.all(out["index"] >= 0) and np.isfinite(out["value"]).all()
+
+
+READ_ONLY = [_ro_loo, _ro_mean_grad, _ro_lipschitz, _ro_batch_select, _ro_refine, _ro_refine_sets, _ro_nll, _ro_expander_gain,
+             _ro_sample_paths]
 
 
 def test_read_only_calls_are_no_writers_of_the_resident_posterior(colpath):
     """Behind a lean-2 column-path sweep that skipped the tiles the plan's enclosures prove safe (the set phase reads what the
-    recording sweep stored there): model_loo, mean_grad, lipschitz, batch_select, refine, refine_sets and nll_batch leave the stored
-    posterior, the plan and its record alone -- the next lean-2 sweep skips exactly the census's tiles again and equals the fresh
+    recording sweep stored there): model_loo, mean_grad, lipschitz, batch_select, refine, refine_sets, nll_batch, expander_gain and
+    sample_paths leave the stored posterior, the plan and its record alone -- the next lean-2 sweep skips exactly the census's tiles again and equals the fresh
     engine's lean-0 sweep and the oracle, bit for bit."""
     eng, name, b = colpath, cases.WHOLE, 1.0
     ds = cases.config()["ds"]
