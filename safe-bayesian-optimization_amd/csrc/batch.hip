@@ -13,26 +13,24 @@
 // total order, there are no atomics: the value of a pool point depends on its coordinates only, not on m or on its place in the list.
 // The whole batch is enqueued without a host wait (a stop or a refused step turns the kernels behind it into no-ops through the
 // state block); one read-back follows.  Nothing resident is written.
+// The kernel expression, the observations' scaled coordinates, the whitening tile of k_batch_v0 and the two mat-vecs of k_batch_u are
+// whiten.hpp's, shared with expander.hip and paths.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include "internal.hpp"
-#include "device_common.hpp"
+#include "whiten.hpp"
 
 namespace sbo {
 
 constexpr int kBatThreads = 256;                 // k_batch_pass / k_batch_finish
 constexpr int kBatChunk = 512;                   // augmented observations of one LDS chunk of k_batch_pass (40 KiB at dpad = 8)
-constexpr int kBatV0Threads = 1024;              // k_batch_v0: P points x 1024 / P row lanes
-constexpr int kBatV0Rows = 4;                    // ... rows of M per row lane and step
-constexpr size_t kBatV0Lds = 128 * 1024;         // ... its K(X, tile) image [n][P]: P = 32 up to n = 512, 16 up to 1024, 8 up to SBO_MAX_N
+constexpr size_t kBatV0Lds = 128 * 1024;         // k_batch_v0: whiten_tile's image [n][P], P = whiten_tier(n): full at n = 512, 1024 and SBO_MAX_N
 constexpr int kBatMaxAug = SBO_MAX_N + SBO_MAX_BATCH;
 
 struct BatchArgs {                               // by value (kernarg segment)
-  int n, d, ld;                                  // observations of the model, input dimension, leading dimension n + n_pending + k of the scratch factor
-  int pad;
-  double X_mean[kMaxD], X_std[kMaxD], vinv[kMaxD];
-  double sf2, kappa, Y_std, min_std;             // kappa = sf2 + sn2, the diagonal entry sbo_model_append gives a new row
+  int n, ld;                                     // observations of the model, leading dimension n + n_pending + k of the scratch factor
+  OutParams op;                                  // the selected output
+  double kappa, Y_std, min_std;                  // kappa = sf2 + sn2, the diagonal entry sbo_model_append gives a new row
 };
 
 struct BatchState {                              // device: what the kernels of one call hand each other, and the result
@@ -41,143 +39,63 @@ struct BatchState {                              // device: what the kernels of 
   sbo_batch_result res;
 };
 
-// scaled coordinates b = (x - X_mean) / X_std * ell^-1/2 of a raw point and their sum of squares, axis order (GP_Safe.py:115-116)
-template <int D>
-__device__ __forceinline__ double bat_scale(const BatchArgs& A, const double* __restrict__ raw, bool on, double* b) {
-  double bsq = 0.0;
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    b[a] = (on && a < A.d) ? ((raw[a] - A.X_mean[a]) / A.X_std[a]) * A.vinv[a] : 0.0;
-    bsq += b[a] * b[a];
-  }
-  return bsq;
-}
-// sf2 exp(-1/2 dist) with the expanded distance (-2 a.b + |a|^2) + |b|^2 of the reference (GP_Safe.py:119), as sbo_model_append forms it
-template <int D>
-__device__ __forceinline__ double bat_k(double sf2, const double* a, double asq, const double* b, double bsq) {
-  double dot = 0.0;
-#pragma unroll
-  for (int t = 0; t < D; ++t) dot += a[t] * b[t];
-  return sf2 * exp(-0.5 * ((-2.0 * dot + asq) + bsq));
-}
-
-// ---- the observations in scaled coordinates: As [ld][D] (rows >= n: filled as points are conditioned on), sq [ld] -----------------
-template <int D>
-__global__ __launch_bounds__(256) void k_batch_prep(const BatchArgs A, const double* __restrict__ Xn /* [n][d] */, double* __restrict__ As,
-                                                    double* __restrict__ sq) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= A.n) return;
-  double s = 0.0;
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    const double v = a < A.d ? Xn[(size_t)i * A.d + a] * A.vinv[a] : 0.0;
-    As[(size_t)i * D + a] = v;
-    s += v * v;
-  }
-  sq[i] = s;
-}
-
 // ---- v_0 = sf2 - ||M k_x||^2 -------------------------------------------------------------------------------------------------------
-// A workgroup owns P pool points; thread (p, r) = (tid mod P, tid / P).  K(X, tile) is formed once into LDS as sK[j][p]; the rows of
-// t = M k_x are taken in blocks of (1024 / P) kBatV0Rows rows from the bottom up, a thread owning kBatV0Rows consecutive rows of its
-// point -- row i needs k[0 .. i] only, so a finished block's t overwrites the k entries nobody reads any more --, every row sum in
-// column order; at the end one thread per point adds the squares in row order.  Nothing above the diagonal of M is read.
+// A workgroup owns P pool points (whiten_tile, whiten.hpp); at the end one thread per point adds the squares in row order.
 template <int D>
-__global__ __launch_bounds__(kBatV0Threads) void k_batch_v0(const BatchArgs A, int P, const double* __restrict__ As, const double* __restrict__ sq,
-                                                            const double* __restrict__ M, const double* __restrict__ pool, long long m,
-                                                            double* __restrict__ v) {
+__global__ __launch_bounds__(kWhitenThreads) void k_batch_v0(const BatchArgs A, int P, const double* __restrict__ As, const double* __restrict__ sq,
+                                                             const double* __restrict__ M, const double* __restrict__ pool, long long m,
+                                                             double* __restrict__ v) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double* sK = reinterpret_cast<double*>(smem);             // [n][P]
-  const int n = A.n, ld = A.ld, tid = threadIdx.x, p = tid % P, r = tid / P, R = kBatV0Threads / P;
-  const long long i = (long long)blockIdx.x * P + p;
+  const int n = A.n, tid = threadIdx.x;
+  const long long i = (long long)blockIdx.x * P + tid % P;
   const bool on = i < m;
   double b[D];
-  const double bsq = bat_scale<D>(A, pool + (size_t)(on ? i : 0) * A.d, on, b);
-  for (int j = r; j < n; j += R) {
-    double a[D];
-#pragma unroll
-    for (int t = 0; t < D; ++t) a[t] = As[(size_t)j * D + t];
-    sK[j * P + p] = on ? bat_k<D>(A.sf2, a, sq[j], b, bsq) : 0.0;
-  }
-  __syncthreads();
-  const int RB = R * kBatV0Rows;
-  for (int blk = (n + RB - 1) / RB - 1; blk >= 0; --blk) {
-    const int i0 = blk * RB + r * kBatV0Rows, cnt = min(kBatV0Rows, n - i0);      // this thread's rows i0 .. i0 + cnt - 1 (cnt <= 0: none)
-    double t[kBatV0Rows];
-#pragma unroll
-    for (int u = 0; u < kBatV0Rows; ++u) t[u] = 0.0;
-    if (cnt > 0) {
-      const double* row[kBatV0Rows];
-#pragma unroll
-      for (int u = 0; u < kBatV0Rows; ++u) row[u] = M + (size_t)min(i0 + u, n - 1) * ld;    // (a missing row reads the last one; its sum is dropped)
-#pragma unroll 4
-      for (int j = 0; j <= i0; ++j) {
-        const double kj = sK[j * P + p];
-#pragma unroll
-        for (int u = 0; u < kBatV0Rows; ++u) t[u] = fma(row[u][j], kj, t[u]);
-      }
-#pragma unroll
-      for (int u = 1; u < kBatV0Rows; ++u)
-        if (u < cnt)
-          for (int j = i0 + 1; j <= i0 + u; ++j) t[u] = fma(row[u][j], sK[j * P + p], t[u]);
-    }
-    __syncthreads();                                    // (every k entry of this block of rows has been read)
-#pragma unroll
-    for (int u = 0; u < kBatV0Rows; ++u)
-      if (u < cnt) sK[(i0 + u) * P + p] = t[u];
-  }
-  __syncthreads();
-  if (tid < P && on) {                                  // (p == tid)
+  const double bsq = rbf_scale<D>(A.op, pool + (size_t)(on ? i : 0) * A.op.d, on, b);
+  whiten_tile<D>(sK, P, P, n, A.op.sf2, As, sq, M, A.ld, b, bsq, on);
+  if (tid < P && on) {                                  // (tid % P == tid)
     double s = 0.0;
     for (int j = 0; j < n; ++j) {
       const double t = sK[j * P + tid];
       s += t * t;
     }
-    v[i] = A.sf2 - s;
+    v[i] = A.op.sf2 - s;
   }
 }
 
 // ---- one conditioning step, the part that does not depend on the pool --------------------------------------------------------------
 // z = src[src_index] (a pending point) or, with src_index < 0, the pool point picked last.  One workgroup: k_z over the na augmented
-// observations, t = M_aug k_z (a wave per row, lanes along the row, butterfly), u = M_aug^T t (a thread per column, rows in order),
-// s = kappa - k_z . u.  s <= 0 sets `bad` and writes nothing; otherwise row na of the scratch factor becomes (-u / sqrt(s), 1 / sqrt(s))
-// and z joins the observation arrays as row na -- the resident factor is never written.
+// observations, t = M_aug k_z (factor_lower_mv), u = M_aug^T t (factor_upper_mv), s = kappa - k_z . u.  s <= 0 sets `bad` and writes
+// nothing; otherwise row na of the scratch factor becomes (-u / sqrt(s), 1 / sqrt(s)) and z joins the observation arrays as row na --
+// the resident factor is never written.
 template <int D>
-__global__ __launch_bounds__(1024) void k_batch_u(const BatchArgs A, int na, double* __restrict__ As, double* __restrict__ sq, double* __restrict__ M,
-                                                  const double* __restrict__ src, long long src_index, const double* __restrict__ pool,
-                                                  double* __restrict__ u, BatchState* __restrict__ st) {
+__global__ __launch_bounds__(kFactorMvThreads) void k_batch_u(const BatchArgs A, int na, double* __restrict__ As, double* __restrict__ sq,
+                                                              double* __restrict__ M, const double* __restrict__ src, long long src_index,
+                                                              const double* __restrict__ pool, double* __restrict__ u,
+                                                              BatchState* __restrict__ st) {
   __shared__ double kz[kBatMaxAug], tz[kBatMaxAug];
   __shared__ double red[16];
   __shared__ double s_sh;
   if (st->stop || st->bad) return;                      // (the same for the whole workgroup)
   const int ld = A.ld, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const double* raw = src_index >= 0 ? src + (size_t)src_index * A.d : pool + (size_t)st->res.index[st->res.n_selected - 1] * A.d;
+  const double* raw = src_index >= 0 ? src + (size_t)src_index * A.op.d : pool + (size_t)st->res.index[st->res.n_selected - 1] * A.op.d;
   double b[D];
-  const double bsq = bat_scale<D>(A, raw, true, b);
-  for (int j = tid; j < na; j += 1024) {
+  const double bsq = rbf_scale<D>(A.op, raw, true, b);
+  for (int j = tid; j < na; j += kFactorMvThreads) {
     double a[D];
 #pragma unroll
     for (int t = 0; t < D; ++t) a[t] = As[(size_t)j * D + t];
-    kz[j] = bat_k<D>(A.sf2, a, sq[j], b, bsq);
+    kz[j] = rbf_k<D>(A.op.sf2, a, sq[j], b, bsq);
   }
   __syncthreads();
-  for (int i = wave; i < na; i += 16) {
-    double s = 0.0;
-    for (int j = lane; j <= i; j += 64) s = fma(M[(size_t)i * ld + j], kz[j], s);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    if (lane == 0) tz[i] = s;
-  }
+  factor_lower_mv(M, ld, na, kz, tz, na);
   __syncthreads();
   double ku = 0.0;
-  for (int j = tid; j < na; j += 1024) {
-    double s = 0.0;
-    for (int i = j; i < na; ++i) s = fma(M[(size_t)i * ld + j], tz[i], s);
+  factor_upper_mv(M, ld, na, tz, [&](int j, double s) {
     u[j] = s;
     ku += kz[j] * s;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) ku += __shfl_xor(ku, off);
+  });
+  ku = wave_sum(ku);
   if (lane == 0) red[wave] = ku;
   __syncthreads();
   if (tid == 0) {
@@ -192,7 +110,7 @@ __global__ __launch_bounds__(1024) void k_batch_u(const BatchArgs A, int na, dou
   const double s = s_sh;
   if (!(s > 0.0)) return;
   const double rs = 1.0 / sqrt(s);
-  for (int j = tid; j < na; j += 1024) M[(size_t)na * ld + j] = -u[j] * rs;
+  for (int j = tid; j < na; j += kFactorMvThreads) M[(size_t)na * ld + j] = -u[j] * rs;
   if (tid == 0) {
     M[(size_t)na * ld + na] = rs;
     sq[na] = bsq;
@@ -229,7 +147,7 @@ __global__ __launch_bounds__(kBatThreads) void k_batch_pass(const BatchArgs A, i
     double vn = on ? v[i] : 0.0;
     if (update) {
       double b[D];
-      const double bsq = bat_scale<D>(A, pool + (size_t)(on ? i : 0) * A.d, on, b);
+      const double bsq = rbf_scale<D>(A.op, pool + (size_t)(on ? i : 0) * A.op.d, on, b);
       double acc = 0.0;
       for (int j0 = 0; j0 < na; j0 += kBatChunk) {
         const int cnt = min(kBatChunk, na - j0);
@@ -241,10 +159,10 @@ __global__ __launch_bounds__(kBatThreads) void k_batch_pass(const BatchArgs A, i
         }
         __syncthreads();
         if (on)
-          for (int j = 0; j < cnt; ++j) acc += bat_k<D>(A.sf2, sA + j * D, sS[j], b, bsq) * sU[j];
+          for (int j = 0; j < cnt; ++j) acc += rbf_k<D>(A.op.sf2, sA + j * D, sS[j], b, bsq) * sU[j];
       }
       if (on) {
-        const double c = bat_k<D>(A.sf2, z, zsq, b, bsq) - acc;
+        const double c = rbf_k<D>(A.op.sf2, z, zsq, b, bsq) - acc;
         vn = vn - c * c / s;
         v[i] = vn;
       }
@@ -301,13 +219,12 @@ template <int D>
 static int batch_enqueue(sbo_ctx* c, const BatchArgs& A, const BatBufs& B, long long m, int k, int n_pending, bool want_var) {
   hipStream_t st = c->stream;
   const int n = A.n;
-  hipLaunchKernelGGL((k_batch_prep<D>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, (const double*)B.Xn, B.As, B.sq);
-  SBO_HIP(hipGetLastError());
-  const int P = n <= 512 ? 32 : n <= 1024 ? 16 : 8;
+  SBO_HIP(obs_prep<D>(st, n, &A.op, 1, B.Xn, B.As, B.sq));      // (rows 0 .. n - 1 of As [ld][D], sq [ld]; k_batch_u fills the rest)
+  const int P = whiten_tier(n);
   const size_t lds = sizeof(double) * (size_t)n * P;
   if (lds > kBatV0Lds) return fail(SBO_E_UNSUPPORTED, "sbo_batch_select: the model is too large");      // (n <= SBO_MAX_N: never)
   SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_batch_v0<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBatV0Lds));
-  hipLaunchKernelGGL((k_batch_v0<D>), dim3((unsigned)((m + P - 1) / P)), dim3(kBatV0Threads), lds, st, A, P, (const double*)B.As,
+  hipLaunchKernelGGL((k_batch_v0<D>), dim3((unsigned)((m + P - 1) / P)), dim3(kWhitenThreads), lds, st, A, P, (const double*)B.As,
                      (const double*)B.sq, (const double*)B.M, (const double*)B.pool, m, B.v);
   SBO_HIP(hipGetLastError());
   const int nb = (int)std::min<long long>((m + kBatThreads - 1) / kBatThreads, 8192);
@@ -317,7 +234,7 @@ static int batch_enqueue(sbo_ctx* c, const BatchArgs& A, const BatBufs& B, long 
     return hipGetLastError();
   };
   auto condition = [&](int na, long long src_index) {
-    hipLaunchKernelGGL((k_batch_u<D>), dim3(1), dim3(1024), 0, st, A, na, B.As, B.sq, B.M, (const double*)B.pend, src_index,
+    hipLaunchKernelGGL((k_batch_u<D>), dim3(1), dim3(kFactorMvThreads), 0, st, A, na, B.As, B.sq, B.M, (const double*)B.pend, src_index,
                        (const double*)B.pool, B.u, B.st);
     hipError_t e = hipGetLastError();
     return e != hipSuccess ? e : pass(na);
@@ -365,21 +282,13 @@ extern "C" int sbo_batch_select(sbo_ctx* c, const sbo_batch_opts* opts, int64_t 
   const ModelConst& mc = c->mc;
   const int n = mc.n, d = mc.d, o = opts->output, k = opts->k, np = opts->n_pending;
   if (o < 0 || o >= mc.q) return fail(SBO_E_INVALID, "output out of range [0, q)");
-  for (size_t t = 0; t < (size_t)m * d; ++t)
-    if (!std::isfinite(pool[t])) return fail(SBO_E_INVALID, "pool holds a non-finite coordinate");
-  for (size_t t = 0; t < (size_t)np * d; ++t)
-    if (!std::isfinite(pending[t])) return fail(SBO_E_INVALID, "pending holds a non-finite coordinate");
+  if (!all_finite(pool, (size_t)m * d)) return fail(SBO_E_INVALID, "pool holds a non-finite coordinate");
+  if (!all_finite(pending, (size_t)np * d)) return fail(SBO_E_INVALID, "pending holds a non-finite coordinate");
   if ((rc = model_reader_begin(c, "sbo_batch_select", false))) return rc;        // (the scratch factor starts as a copy of the resident one)
   BatchArgs A{};
   A.n = n;
-  A.d = d;
   A.ld = n + np + k;
-  for (int a = 0; a < d; ++a) {
-    A.X_mean[a] = mc.X_mean[a];
-    A.X_std[a] = mc.X_std[a];
-    A.vinv[a] = mc.vinv[o][a];
-  }
-  A.sf2 = mc.sf2[o];
+  A.op = out_params(mc, o);
   A.kappa = mc.sf2[o] + mc.sn2[o];
   A.Y_std = mc.Y_std[o];
   A.min_std = opts->min_std;

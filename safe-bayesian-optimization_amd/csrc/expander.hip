@@ -7,10 +7,10 @@
 //   s = v_c(g) + sn2_c,   mu' = mu_c(x) + cov b sqrt(max(0, v_c(g))) / s,   v' = v_c(x) - cov^2 / s,
 //   z_c(x | g) = mu' - b sqrt(max(0, v')) + Y_mean[c] / Y_std[c],   Z(x | g) = min over the masked constraints of z_c(x | g)
 // and per source count = #{x : Z >= 0}, margin = max_x Z, witness = its index (lowest on a tie).
-//   k_exp_prep    the observations in the scaled coordinates of every masked constraint
+//   k_obs_prep    (whiten.hpp) the observations in the scaled coordinates of every masked constraint
 //   k_exp_w       the whitened residuals w = M_c (y_c - mp_c): mu_c(p) = mp_c + k_c(X, p) . alpha_c = mp_c + t_p . w
-//   k_exp_stage1  per (constraint, point): t_p [point][ldt] (zero beyond n), mu, v and the point's scaled coordinates; k_batch_v0's
-//                 scheme on a padded LDS image, O((ms + mt) n^2) on the vector units
+//   k_exp_stage1  per (constraint, point): t_p [point][ldt] (zero beyond n), mu, v and the point's scaled coordinates; whiten_tile
+//                 (whiten.hpp) on a padded LDS image, O((ms + mt) n^2) on the vector units
 //   k_exp_pairs   the hot path, O(ms mt n) per constraint on the matrix cores: a workgroup owns a 64 x 64 (source x target) tile, a wave
 //                 32 x 32 of it as 2 x 2 accumulators of MM<double> (v_mfma_f64_4x4x4, four per step); per constraint the K-loop runs
 //                 over LDS-staged slabs of t, the epilogue turns t_x . t_g into z_c and keeps the running Z in registers; behind the last
@@ -23,8 +23,7 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
-#include "internal.hpp"
-#include "device_common.hpp"
+#include "whiten.hpp"
 
 namespace sbo {
 
@@ -32,18 +31,16 @@ constexpr int kExpTile = 64;                     // sources x targets of one wor
 constexpr int kExpThreads = 256;                 // k_exp_pairs / k_exp_finish
 constexpr int kExpKSlab = 32;                    // observations of one LDS slab of k_exp_pairs; t rows are zero-padded to a multiple (ldt)
 constexpr int kExpGridTiles = 1024;              // workgroups k_exp_pairs aims at: target splits = min(target tiles, kExpGridTiles / source tiles)
-constexpr int kExpS1Threads = 1024;              // k_exp_stage1: P points x 1024 / P row lanes
-constexpr int kExpS1Rows = 4;                    // ... rows of M per row lane and step
-constexpr size_t kExpS1Lds = 144 * 1024;         // ... its K(X, tile) image [n][P + 1]: P = 32 up to n = 512, 16 up to 1024, 8 up to SBO_MAX_N
-static_assert(kExpTile == 64 && kExpThreads == 256 && kExpKSlab % 8 == 0, "k_exp_pairs: 4 waves of 32 x 32, slabs staged 8 observations per thread");
+constexpr size_t kExpS1Lds = 144 * 1024;         // k_exp_stage1: whiten_tile's image [n][P + 1], P = whiten_tier(n): full at SBO_MAX_N
+static_assert(kExpTile == 64 && kExpThreads == 256 && kExpKSlab == kSlabK, "k_exp_pairs: 4 waves of 32 x 32, slabs staged 8 observations per thread");
 
 struct ExpArgs {                                 // by value (kernarg segment)
   int n, d, ld, pad0;                            // observations, input dimension, leading dimension of the resident factor
   int ldt, nc, q, pad;                           // leading dimension of t (n rounded up to kExpKSlab), masked constraints, outputs of the model
   long long ms, mt;
   int out[kMaxQ];                                // [slot]: the output a masked constraint is
-  double X_mean[kMaxD], X_std[kMaxD];
-  double vinv[kMaxQ][kMaxD], sf2[kMaxQ], sn2[kMaxQ], mp[kMaxQ], shift[kMaxQ];    // per slot; shift = Y_mean / Y_std
+  OutParams op[kMaxQ];                           // [slot]
+  double shift[kMaxQ];                           // [slot]: Y_mean / Y_std
   double b;
 };
 
@@ -57,125 +54,45 @@ struct ExpBufs {
   ExpState* st;
 };
 
-// scaled coordinates (x - X_mean) / X_std * ell^-1/2 of a raw point under a constraint's length scales, and their sum of squares
-template <int D>
-__device__ __forceinline__ double exp_scale(const ExpArgs& A, int slot, const double* __restrict__ raw, bool on, double* b) {
-  double bsq = 0.0;
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    b[a] = (on && a < A.d) ? ((raw[a] - A.X_mean[a]) / A.X_std[a]) * A.vinv[slot][a] : 0.0;
-    bsq += b[a] * b[a];
-  }
-  return bsq;
-}
-// sf2 exp(-1/2 dist) with the expanded distance (-2 a.b + |a|^2) + |b|^2 of the reference (GP_Safe.py:119); a: the observation
-template <int D>
-__device__ __forceinline__ double exp_k(double sf2, const double* a, double asq, const double* b, double bsq) {
-  double dot = 0.0;
-#pragma unroll
-  for (int t = 0; t < D; ++t) dot += a[t] * b[t];
-  return sf2 * exp(-0.5 * ((-2.0 * dot + asq) + bsq));
-}
-
-// ---- the observations in the scaled coordinates of every slot: As [nc][n][D], sq [nc][n] ----------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void k_exp_prep(const ExpArgs A, const double* __restrict__ Xn /* [n][d] */, double* __restrict__ As,
-                                                  double* __restrict__ sq) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x, slot = blockIdx.y;
-  if (i >= A.n) return;
-  double s = 0.0;
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    const double v = a < A.d ? Xn[(size_t)i * A.d + a] * A.vinv[slot][a] : 0.0;
-    As[((size_t)slot * A.n + i) * D + a] = v;
-    s += v * v;
-  }
-  sq[(size_t)slot * A.n + i] = s;
-}
-
 // ---- the whitened residuals w = M (y - mp) of every slot: w [nc][ldt] ------------------------------------------------------------------
-// One workgroup per slot, a wave per row, lanes along the row, butterfly.  With t_p = M k_p the mean is mp + k_p . alpha = mp + t_p . w
-// (alpha = M^T M (y - mp)): the call rests on the factor and the data alone, so whatever leaves the first n rows of the factor as they
-// are -- an append and the removal of that row -- leaves the call's bits as they are.
-__global__ __launch_bounds__(1024) void k_exp_w(const ExpArgs A, const double* __restrict__ Yn /* [n][q] */, const double* __restrict__ F,
-                                                double* __restrict__ w) {
+// One workgroup per slot (factor_lower_mv, whiten.hpp).  With t_p = M k_p the mean is mp + k_p . alpha = mp + t_p . w (alpha = M^T M
+// (y - mp)): the call rests on the factor and the data alone, so whatever leaves the first n rows of the factor as they are -- an
+// append and the removal of that row -- leaves the call's bits as they are.
+__global__ __launch_bounds__(kFactorMvThreads) void k_exp_w(const ExpArgs A, const double* __restrict__ Yn /* [n][q] */,
+                                                            const double* __restrict__ F, double* __restrict__ w) {
   __shared__ double sy[SBO_MAX_N];
-  const int n = A.n, ld = A.ld, slot = blockIdx.x, o = A.out[slot], tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const double* M = F + (size_t)o * ld * ld;
-  for (int j = tid; j < n; j += 1024) sy[j] = Yn[(size_t)j * A.q + o] - A.mp[slot];
+  const int n = A.n, ld = A.ld, slot = blockIdx.x, o = A.out[slot];
+  for (int j = threadIdx.x; j < n; j += kFactorMvThreads) sy[j] = Yn[(size_t)j * A.q + o] - A.op[slot].mp;
   __syncthreads();
-  for (int i = wave; i < A.ldt; i += 16) {
-    double s = 0.0;
-    if (i < n)
-      for (int j = lane; j <= i; j += 64) s = fma(M[(size_t)i * ld + j], sy[j], s);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    if (lane == 0) w[(size_t)slot * A.ldt + i] = s;
-  }
+  factor_lower_mv(F + (size_t)o * ld * ld, ld, n, sy, w + (size_t)slot * A.ldt, A.ldt);
 }
 
 // ---- stage 1: t = M k_p, mu = mp + t . w, v = sf2 - ||t||^2 per (slot, point) ---------------------------------------------------
-// k_batch_v0's scheme: a workgroup owns P points of the list sources | targets; thread (p, r) = (tid mod P, tid / P).  K(X, tile) is
-// formed once into LDS as sK[j][p] with a leading dimension of P + 1 (the write-out below reads columns); the rows of t = M k are taken in blocks of (1024 / P) kExpS1Rows rows from the bottom up, a finished block's t
-// overwriting the k entries nobody reads any more; one thread per point adds the squares and the products with w in row order.  The image is then written
-// out as t [point][ldt], lanes along a row, zeros from n to ldt.
+// A workgroup owns P points of the list sources | targets (whiten_tile, whiten.hpp), the image with a leading dimension of P + 1 (the
+// write-out below reads columns); one thread per point adds the squares and the products with w in row order.  The image is then
+// written out as t [point][ldt], lanes along a row, zeros from n to ldt.
 template <int D>
-__global__ __launch_bounds__(kExpS1Threads) void k_exp_stage1(const ExpArgs A, int P, const double* __restrict__ As, const double* __restrict__ sq,
-                                                              const double* __restrict__ F, const double* __restrict__ w,
-                                                              const double* __restrict__ pts, double* __restrict__ T, double* __restrict__ mu,
-                                                              double* __restrict__ v, double* __restrict__ bs, double* __restrict__ bsq_out,
-                                                              ExpState* __restrict__ st) {
+__global__ __launch_bounds__(kWhitenThreads) void k_exp_stage1(const ExpArgs A, int P, const double* __restrict__ As, const double* __restrict__ sq,
+                                                               const double* __restrict__ F, const double* __restrict__ w,
+                                                               const double* __restrict__ pts, double* __restrict__ T, double* __restrict__ mu,
+                                                               double* __restrict__ v, double* __restrict__ bs, double* __restrict__ bsq_out,
+                                                               ExpState* __restrict__ st) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double* sK = reinterpret_cast<double*>(smem);             // [n][P + 1]
-  const int n = A.n, ld = A.ld, slot = blockIdx.y, o = A.out[slot], tid = threadIdx.x, p = tid % P, r = tid / P, R = kExpS1Threads / P, ldk = P + 1;
-  const long long m = A.ms + A.mt, i = (long long)blockIdx.x * P + p;
+  const int n = A.n, ld = A.ld, slot = blockIdx.y, o = A.out[slot], tid = threadIdx.x, ldk = P + 1;
+  const OutParams& op = A.op[slot];
+  const long long m = A.ms + A.mt, i = (long long)blockIdx.x * P + tid % P;
   const bool on = i < m;
-  const double* M = F + (size_t)o * ld * ld;
   const double* wo = w + (size_t)slot * A.ldt;
-  const double* Ao = As + (size_t)slot * n * D;
-  const double* so = sq + (size_t)slot * n;
   const size_t rec = (size_t)slot * m + (size_t)(on ? i : 0);
   double b[D];
-  const double bsq = exp_scale<D>(A, slot, pts + (size_t)(on ? i : 0) * A.d, on, b);
-  for (int j = r; j < n; j += R) {
-    double a[D];
-#pragma unroll
-    for (int t = 0; t < D; ++t) a[t] = Ao[(size_t)j * D + t];
-    sK[j * ldk + p] = on ? exp_k<D>(A.sf2[slot], a, so[j], b, bsq) : 0.0;
-  }
-  __syncthreads();
-  if (tid < P && on) {                                  // (p == tid)
+  const double bsq = rbf_scale<D>(op, pts + (size_t)(on ? i : 0) * A.d, on, b);
+  if (tid < P && on) {                                  // (tid % P == tid)
     bsq_out[rec] = bsq;
 #pragma unroll
     for (int t = 0; t < D; ++t) bs[rec * D + t] = b[t];
   }
-  const int RB = R * kExpS1Rows;
-  for (int blk = (n + RB - 1) / RB - 1; blk >= 0; --blk) {
-    const int i0 = blk * RB + r * kExpS1Rows, cnt = min(kExpS1Rows, n - i0);      // this thread's rows i0 .. i0 + cnt - 1 (cnt <= 0: none)
-    double t[kExpS1Rows];
-#pragma unroll
-    for (int u = 0; u < kExpS1Rows; ++u) t[u] = 0.0;
-    if (cnt > 0) {
-      const double* row[kExpS1Rows];
-#pragma unroll
-      for (int u = 0; u < kExpS1Rows; ++u) row[u] = M + (size_t)min(i0 + u, n - 1) * ld;    // (a missing row reads the last one; its sum is dropped)
-#pragma unroll 4
-      for (int j = 0; j <= i0; ++j) {
-        const double kj = sK[j * ldk + p];
-#pragma unroll
-        for (int u = 0; u < kExpS1Rows; ++u) t[u] = fma(row[u][j], kj, t[u]);
-      }
-#pragma unroll
-      for (int u = 1; u < kExpS1Rows; ++u)
-        if (u < cnt)
-          for (int j = i0 + 1; j <= i0 + u; ++j) t[u] = fma(row[u][j], sK[j * ldk + p], t[u]);
-    }
-    __syncthreads();                                    // (every k entry of this block of rows has been read)
-#pragma unroll
-    for (int u = 0; u < kExpS1Rows; ++u)
-      if (u < cnt) sK[(i0 + u) * ldk + p] = t[u];
-  }
-  __syncthreads();
+  whiten_tile<D>(sK, ldk, P, n, op.sf2, As + (size_t)slot * n * D, sq + (size_t)slot * n, F + (size_t)o * ld * ld, ld, b, bsq, on);
   if (tid < P && on) {
     double s = 0.0, dot = 0.0;
     for (int j = 0; j < n; ++j) {
@@ -183,13 +100,13 @@ __global__ __launch_bounds__(kExpS1Threads) void k_exp_stage1(const ExpArgs A, i
       s += t * t;
       dot = fma(t, wo[j], dot);
     }
-    const double vv = A.sf2[slot] - s;
+    const double vv = op.sf2 - s;
     v[rec] = vv;
-    mu[rec] = A.mp[slot] + dot;
-    if (i < A.ms && !(vv + A.sn2[slot] > 0.0)) st->bad = 1;      // (every writer stores the same value)
+    mu[rec] = op.mp + dot;
+    if (i < A.ms && !(vv + op.sn2 > 0.0)) st->bad = 1;      // (every writer stores the same value)
   }
   const int ldt = A.ldt;
-  for (int e = tid; e < P * ldt; e += kExpS1Threads) {
+  for (int e = tid; e < P * ldt; e += kWhitenThreads) {
     const int pp = e / ldt, j = e - pp * ldt;
     const long long ii = (long long)blockIdx.x * P + pp;
     if (ii < m) T[((size_t)slot * m + (size_t)ii) * ldt + j] = j < n ? sK[j * ldk + pp] : 0.0;
@@ -199,9 +116,8 @@ __global__ __launch_bounds__(kExpS1Threads) void k_exp_stage1(const ExpArgs A, i
 // ---- stage 2: the pair tiles ----------------------------------------------------------------------------------------------------------
 // Workgroup (bx, by): source tile bx, target tiles by, by + nsplit, ..  Wave w owns sources 32 (w >> 1) .. + 31 and targets 32 (w & 1) ..
 // + 31 of the tile: acc[a][c][t] of lane l is the pair (source 32 (w >> 1) + 16 a + 4 t + (l >> 4), target 32 (w & 1) + 16 c + (l & 15)),
-// the D layout of the 4x4x4 form (device_common.hpp).  LDS images of a slab, per block of 16 points and k-step of 4 observations:
-// sources in MM<double>'s packed A order (a lane's four row groups contiguous: one 32-byte read), targets as [k-slot][point] (lane l
-// reads element l).  Rows past ms / mt are staged as zeros and never counted.
+// the D layout of the 4x4x4 form (device_common.hpp).  LDS images of a slab (whiten.hpp): the sources are the A side, the targets the
+// B side.  Rows past ms / mt are staged as zeros and never counted.
 template <int D>
 __global__ __launch_bounds__(kExpThreads, 2) void k_exp_pairs(const ExpArgs A, int nsplit, long long ntt, const double* __restrict__ T,
                                                            const double* __restrict__ mu, const double* __restrict__ v,
@@ -218,9 +134,8 @@ __global__ __launch_bounds__(kExpThreads, 2) void k_exp_pairs(const ExpArgs A, i
   const long long m = A.ms + A.mt, g0 = (long long)blockIdx.x * kExpTile;
   const int ldt = A.ldt;
   const int srow = tid >> 2, sk = (tid & 3) * 8;          // staging: this thread's point of the tile and its 8 observations of the slab
-  // where observation sk + e (e = 0 .. 7: k-steps sk / 4 and sk / 4 + 1, slots e & 3) of point srow goes in the two images
-  const int posA = (srow >> 4) * BLK + (sk >> 2) * 64 + (srow & 3) * 4 + ((srow & 15) >> 2);      // + (e >> 2) * 64 + (e & 3) * 16
-  const int posB = (srow >> 4) * BLK + (sk >> 2) * 64 + (srow & 15);                               // + (e >> 2) * 64 + (e & 3) * 16
+  // where observation sk of point srow goes in the two images; observation sk + e, e = 0 .. 7: slab_col(e) behind it
+  const int posA = (srow >> 4) * BLK + slab_pos_a(srow, sk), posB = (srow >> 4) * BLK + slab_pos_b(srow, sk);
   long long run_cnt = 0, run_idx = kArgNone;              // threads 0 .. 63: source g0 + tid over this workgroup's target tiles
   double run_val = 0.0;
   for (long long tt = blockIdx.y; tt < ntt; tt += nsplit) {
@@ -238,7 +153,7 @@ __global__ __launch_bounds__(kExpThreads, 2) void k_exp_pairs(const ExpArgs A, i
       if (tid < kExpTile) {
         const bool on = g0 + tid < A.ms;
         const size_t rec = base + (size_t)(on ? g0 + tid : 0);
-        const double vg = on ? v[rec] : 0.0, s = on ? vg + A.sn2[slot] : 1.0;
+        const double vg = on ? v[rec] : 0.0, s = on ? vg + A.op[slot].sn2 : 1.0;
         gS[tid] = s;
         gCoef[tid] = on ? A.b * sqrt(fmax(0.0, vg)) / s : 0.0;
         gSq[tid] = on ? bsq[rec] : 0.0;
@@ -276,28 +191,16 @@ __global__ __launch_bounds__(kExpThreads, 2) void k_exp_pairs(const ExpArgs A, i
         __syncthreads();                                  // (the slab before this one has been read)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          sA[posA + e * 16] = s0[e];
-          sA[posA + 64 + e * 16] = s1[e];
-          sB[posB + e * 16] = t0[e];
-          sB[posB + 64 + e * 16] = t1[e];
+          sA[posA + slab_col(e)] = s0[e];
+          sA[posA + slab_col(4 + e)] = s1[e];
+          sB[posB + slab_col(e)] = t0[e];
+          sB[posB + slab_col(4 + e)] = t1[e];
         }
         __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < kExpKSlab / 4; ++kk) {
-          d4_t fa[2];
-          double fb[2];
-#pragma unroll
-          for (int a = 0; a < 2; ++a) fa[a] = MM<double>::load_a(sA + (2 * ws + a) * BLK, lane, kk);
-#pragma unroll
-          for (int c = 0; c < 2; ++c) fb[c] = sB[(2 * wt + c) * BLK + kk * 64 + lane];
-#pragma unroll
-          for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) acc[a][c] = MM<double>::mfma(fa[a], fb[c], acc[a][c]);
-        }
+        slab_mfma(sA + 2 * ws * BLK, BLK, sB + 2 * wt * BLK, BLK, lane, acc);
       }
       // epilogue of this constraint: t_x . t_g -> z_c(x | g), the running minimum (a NaN stays)
-      const double sf2 = A.sf2[slot], shift = A.shift[slot], bb = A.b;
+      const double sf2 = A.op[slot].sf2, shift = A.shift[slot], bb = A.b;
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
         const int col = 32 * wt + 16 * c + (lane & 15);
@@ -310,7 +213,7 @@ __global__ __launch_bounds__(kExpThreads, 2) void k_exp_pairs(const ExpArgs A, i
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
             const int row = 32 * ws + 16 * a + 4 * t + (lane >> 4);
-            const double cov = exp_k<D>(sf2, gB + row * LB, gSq[row], xb, xsq) - acc[a][c][t];
+            const double cov = rbf_k<D>(sf2, gB + row * LB, gSq[row], xb, xsq) - acc[a][c][t];
             const double m1 = xmu + cov * gCoef[row], v1 = xv - cov * cov / gS[row];
             const double z = (m1 - bb * sqrt(fmax(0.0, v1))) + shift;
             const double zo = Z[a][c][t];
@@ -388,15 +291,14 @@ static int expander_enqueue(sbo_ctx* c, const ExpArgs& A, const ExpBufs& B, int 
   hipStream_t st = c->stream;
   const int n = A.n;
   const long long m = A.ms + A.mt;
-  hipLaunchKernelGGL((k_exp_prep<D>), dim3((unsigned)((n + 255) / 256), (unsigned)A.nc), dim3(256), 0, st, A, (const double*)B.Xn, B.As, B.sq);
+  SBO_HIP(obs_prep<D>(st, n, A.op, A.nc, B.Xn, B.As, B.sq));
+  hipLaunchKernelGGL(k_exp_w, dim3((unsigned)A.nc), dim3(kFactorMvThreads), 0, st, A, (const double*)B.Yn, c->factor.F(), B.w);
   SBO_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_exp_w, dim3((unsigned)A.nc), dim3(1024), 0, st, A, (const double*)B.Yn, c->factor.F(), B.w);
-  SBO_HIP(hipGetLastError());
-  const int P = n <= 512 ? 32 : n <= 1024 ? 16 : 8;
+  const int P = whiten_tier(n);
   const size_t lds = sizeof(double) * (size_t)n * (P + 1);
   if (lds > kExpS1Lds) return fail(SBO_E_UNSUPPORTED, "sbo_expander_gain: the model is too large");      // (n <= SBO_MAX_N: never)
   SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_exp_stage1<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kExpS1Lds));
-  hipLaunchKernelGGL((k_exp_stage1<D>), dim3((unsigned)((m + P - 1) / P), (unsigned)A.nc), dim3(kExpS1Threads), lds, st, A, P, (const double*)B.As,
+  hipLaunchKernelGGL((k_exp_stage1<D>), dim3((unsigned)((m + P - 1) / P), (unsigned)A.nc), dim3(kWhitenThreads), lds, st, A, P, (const double*)B.As,
                      (const double*)B.sq, c->factor.F(), (const double*)B.w, (const double*)B.pts, B.T, B.mu, B.v, B.bs, B.bsq, B.st);
   SBO_HIP(hipGetLastError());
   const long long nst = (A.ms + kExpTile - 1) / kExpTile;
@@ -450,23 +352,14 @@ extern "C" int sbo_expander_gain(sbo_ctx* c, const sbo_expander_opts* opts, int6
     if (mask >> o & 1u) {
       const int s = A.nc++;
       A.out[s] = o;
-      for (int a = 0; a < d; ++a) A.vinv[s][a] = mc.vinv[o][a];
-      A.sf2[s] = mc.sf2[o];
-      A.sn2[s] = mc.sn2[o];
-      A.mp[s] = mc.mp[o];
+      A.op[s] = out_params(mc, o);
       A.shift[s] = mc.Y_mean[o] / mc.Y_std[o];
     }
-  for (int a = 0; a < d; ++a) {
-    A.X_mean[a] = mc.X_mean[a];
-    A.X_std[a] = mc.X_std[a];
-  }
   const size_t m = (size_t)ms + (size_t)mt;
   if (m * (size_t)A.ldt * (size_t)A.nc * sizeof(double) > SBO_EXPANDER_MAX_SCRATCH)
     return fail(SBO_E_UNSUPPORTED, "sbo_expander_gain: the whitened vectors need more than SBO_EXPANDER_MAX_SCRATCH bytes");
-  for (size_t t = 0; t < (size_t)ms * d; ++t)
-    if (!std::isfinite(sources[t])) return fail(SBO_E_INVALID, "sources holds a non-finite coordinate");
-  for (size_t t = 0; t < (size_t)mt * d; ++t)
-    if (!std::isfinite(targets[t])) return fail(SBO_E_INVALID, "targets holds a non-finite coordinate");
+  if (!all_finite(sources, (size_t)ms * d)) return fail(SBO_E_INVALID, "sources holds a non-finite coordinate");
+  if (!all_finite(targets, (size_t)mt * d)) return fail(SBO_E_INVALID, "targets holds a non-finite coordinate");
   if ((rc = model_reader_begin(c, "sbo_expander_gain", false))) return rc;
   A.ld = c->factor.ld();
   const long long ntt = ((long long)mt + kExpTile - 1) / kExpTile, nst = ((long long)ms + kExpTile - 1) / kExpTile;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <cmath>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -705,6 +706,12 @@ int factor_sync(sbo_ctx* c);      // wait for a deferred factorisation (sbo_ctx:
 // model_reader_check is the first half alone, for a call that needs d and q to check its arguments before it waits.
 int model_reader_check(const sbo_ctx* c, const char* who, bool need_f64);
 int model_reader_begin(sbo_ctx* c, const char* who, bool need_f64);
+// what the point calls ask of a caller's array before anything is copied
+inline bool all_finite(const double* p, size_t count) {
+  for (size_t t = 0; t < count; ++t)
+    if (!std::isfinite(p[t])) return false;
+  return true;
+}
 
 // Hands out consecutive blocks of one buffer, each at a multiple of `align` bytes.  A layout is one sequence of take() calls, run
 // once on a null base for the size and once on the buffer for the pointers.  `floor`: the least alignment of every block.

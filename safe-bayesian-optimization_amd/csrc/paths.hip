@@ -5,7 +5,7 @@
 //   c_s = M^T (M r_s),   r_s[j] = (y_j - mp) - prior_s(X_j) - sqrt(sn2) noise[s][j]   (M^T M = inv(K + sn2 I), the resident fp64 factor)
 // which is ONE matrix product per point tile: the A operand [point][F + n] is generated on the fly (cos features, then RBF columns),
 // the B operand [F + n][S] (scaled weights, then c) is small and lives in L2.
-//   k_path_prep    the observations in the output's scaled coordinates (as k_exp_prep) and their squares
+//   k_obs_prep     (whiten.hpp) the observations in the output's scaled coordinates and their squares
 //   k_path_bw      the feature rows of B
 //   k_path_main    the hot path on the matrix cores: a workgroup owns kPathTile points x all Spad paths, wave w points 32 w .. + 31 as
 //                  2 x Spad / 16 accumulators of MM<double> (v_mfma_f64_4x4x4, four per step).  The K axis is the F features rounded up
@@ -15,8 +15,7 @@
 //                  bounded grid walks the tiles; one partial per (workgroup, path).
 //                  The prior at the data is THIS kernel with the observations as the points and no observation slabs: no second
 //                  feature evaluator exists that could round differently.
-//   k_path_solve   per path: r, w = M r (a wave per row, butterfly, as k_exp_w), c = M^T w (a thread per column, rows in order) into
-//                  the observation rows of B
+//   k_path_solve   per path: r, w = M r (factor_lower_mv, whiten.hpp), c = M^T w (factor_upper_mv) into the observation rows of B
 //   k_path_finish  the partials in workgroup order -> the result block
 // Every sum over features and observations runs in an order fixed by (F, n) alone, (value, index) reductions are arg_take's total
 // order, there are no atomics: the value of (point, path) does not depend on m, on the point's place or on the other paths, and two
@@ -25,8 +24,7 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
-#include "internal.hpp"
-#include "device_common.hpp"
+#include "whiten.hpp"
 
 namespace sbo {
 
@@ -37,7 +35,7 @@ constexpr int kPathGridTiles = 1024;             // workgroups k_path_main aims 
 constexpr int kPathFinishThreads = 1024;         // k_path_finish: SBO_MAX_PATHS paths x 16 parts of the workgroups
 constexpr int kPathBlk = 16 * kPathKSlab;        // doubles of one 16-row block of a slab image
 constexpr int kPathBlkA = kPathBlk + 16;         // ... and the distance between two blocks of the A image (the four blocks a wave writes at once land in two bank halves)
-static_assert(kPathTile == 128 && kPathThreads == 256 && kPathKSlab == 32, "k_path_main: 4 waves of 32 points, a thread generates 16 columns of one point per slab");
+static_assert(kPathTile == 128 && kPathThreads == 256 && kPathKSlab == 32 && kPathKSlab == kSlabK, "k_path_main: 4 waves of 32 points, a thread generates 16 columns of one point per slab");
 static_assert(SBO_MAX_PATHS == 64, "k_path_main is instantiated for 16, 32 and 64 padded paths");
 
 struct PathArgs {                                // by value (kernarg segment)
@@ -45,8 +43,8 @@ struct PathArgs {                                // by value (kernarg segment)
   int F, S, Spad, o;                             // features, paths, paths rounded up to 16 | 32 | 64, the output
   int KF, KN, maximize, pad;                     // F and n rounded up to kPathKSlab (KN = 0: no observation part)
   long long m;                                   // points
-  double X_mean[kMaxD], X_std[kMaxD], vinv[kMaxD];
-  double sf2, sn2, mp, ymean, ystd, fscale;      // fscale = sqrt(2 sf2 / F)
+  OutParams op;                                  // the output
+  double ymean, ystd, fscale;                    // fscale = sqrt(2 sf2 / F)
 };
 
 struct PathBufs {
@@ -54,22 +52,6 @@ struct PathBufs {
   long long* pidx;
   sbo_paths_result* res;
 };
-
-// ---- the observations in the scaled coordinates of the output: As [n][D], sq [n] (k_exp_prep's arithmetic) ---------------------------
-template <int D>
-__global__ __launch_bounds__(256) void k_path_prep(const PathArgs A, const double* __restrict__ Xn /* [n][d] */, double* __restrict__ As,
-                                                   double* __restrict__ sq) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= A.n) return;
-  double s = 0.0;
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    const double v = a < A.d ? Xn[(size_t)i * A.d + a] * A.vinv[a] : 0.0;
-    As[(size_t)i * D + a] = v;
-    s += v * v;
-  }
-  sq[i] = s;
-}
 
 // ---- the feature rows of B: B [f][s] = fscale weights[s][f] (the buffer was zeroed: rows from F on and columns from S on stay zero) ---
 __global__ __launch_bounds__(256) void k_path_bw(const PathArgs A, const double* __restrict__ wt /* [S][F] */, double* __restrict__ B) {
@@ -81,8 +63,7 @@ __global__ __launch_bounds__(256) void k_path_bw(const PathArgs A, const double*
 
 // ---- the hot path -------------------------------------------------------------------------------------------------------------------
 // Thread t generates, per slab, columns 16 (t >> 7) .. + 15 of point t & 127 of the tile (the column is wave-uniform: its omega row or
-// observation is read once per wave).  LDS images of a slab, per block of 16 rows and k-step of 4 columns: the points in MM<double>'s
-// packed A order (a lane's four row groups contiguous: one 32-byte read), B as [k-slot][path] (lane l reads element l).  acc[a][c][t]
+// observation is read once per wave).  LDS images of a slab (whiten.hpp): the points are the A side, the paths the B side.  acc[a][c][t]
 // of lane l of wave w is (point 32 w + 16 a + 4 t + (l >> 4), path 16 c + (l & 15)), the D layout of the 4x4x4 form
 // (device_common.hpp).  Points past m generate zeros and are never stored or taken.
 // `pts` holds rows of d coordinates x with u = ((x - X_mean) / X_std) vinv: the raw points, or -- with X_mean = 0, X_std = 1, both exact
@@ -99,22 +80,15 @@ __global__ __launch_bounds__(kPathThreads, 2) void k_path_main(const PathArgs A,
   __shared__ long long rIdx[4][SP];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int gp = tid & (kPathTile - 1), gk = (tid >> 7) * 16;       // generation: this thread's point of the tile and its first column of the slab
-  const int posA = (gp >> 4) * kPathBlkA + (gk >> 2) * 64 + (gp & 3) * 4 + ((gp & 15) >> 2);      // + (e >> 2) * 64 + (e & 3) * 16
+  const int posA = (gp >> 4) * kPathBlkA + slab_pos_a(gp, gk);      // column gk + e, e = 0 .. 15: slab_col(e) behind it
   const int n = A.n, F = A.F;
   long long run_idx = kArgNone;                   // threads 0 .. SP - 1: path tid over this workgroup's tiles
   double run_val = 0.0;
   for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const long long p0 = tile * kPathTile;
     const bool on = p0 + gp < A.m;
-    double u[D], usq = 0.0;
-    {
-      const double* x = pts + (size_t)(on ? p0 + gp : 0) * A.d;
-#pragma unroll
-      for (int a = 0; a < D; ++a) {
-        u[a] = (on && a < A.d) ? ((x[a] - A.X_mean[a]) / A.X_std[a]) * A.vinv[a] : 0.0;
-        usq += u[a] * u[a];
-      }
-    }
+    double u[D];
+    const double usq = rbf_scale<D>(A.op, pts + (size_t)(on ? p0 + gp : 0) * A.d, on, u);
     d4_t acc[2][SB];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -133,15 +107,12 @@ __global__ __launch_bounds__(kPathThreads, 2) void k_path_main(const PathArgs A,
           arg += ph[f];
           g[e] = (on && f < F) ? cos(arg) : 0.0;
         }
-      } else {                                      // observations: sf2 exp(-1/2 dist), the expanded distance of the reference (GP_Safe.py:119)
+      } else {                                      // observations: rbf_k, their coordinates read from global memory
         const int j0 = __builtin_amdgcn_readfirstlane(k0 - A.KF + gk);
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int j = j0 + e, jj = j < n ? j : n - 1;
-          double dot = 0.0;
-#pragma unroll
-          for (int a = 0; a < D; ++a) dot += As[(size_t)jj * D + a] * u[a];
-          const double kv = A.sf2 * exp(-0.5 * ((-2.0 * dot + sq[jj]) + usq));
+          const double kv = rbf_k<D>(A.op.sf2, As + (size_t)jj * D, sq[jj], u, usq);
           g[e] = (on && j < n) ? kv : 0.0;
         }
       }
@@ -150,26 +121,14 @@ __global__ __launch_bounds__(kPathThreads, 2) void k_path_main(const PathArgs A,
       for (int i = 0; i < SB * 2; ++i) bv[i] = B[(size_t)k0 * SP + i * kPathThreads + tid];
       __syncthreads();                              // (the slab before this one has been read)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) sA[posA + (e >> 2) * 64 + (e & 3) * 16] = g[e];
+      for (int e = 0; e < 16; ++e) sA[posA + slab_col(e)] = g[e];
 #pragma unroll
       for (int i = 0; i < SB * 2; ++i) {
         const int idx = i * kPathThreads + tid, k = idx / SP, s = idx - k * SP;
-        sB[(s >> 4) * kPathBlk + (k >> 2) * 64 + (k & 3) * 16 + (s & 15)] = bv[i];
+        sB[(s >> 4) * kPathBlk + slab_pos_b(s, k)] = bv[i];
       }
       __syncthreads();
-#pragma unroll
-      for (int kk = 0; kk < kPathKSlab / 4; ++kk) {
-        d4_t fa[2];
-        double fb[SB];
-#pragma unroll
-        for (int a = 0; a < 2; ++a) fa[a] = MM<double>::load_a(sA + (2 * w + a) * kPathBlkA, lane, kk);
-#pragma unroll
-        for (int c = 0; c < SB; ++c) fb[c] = sB[c * kPathBlk + kk * 64 + lane];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-          for (int c = 0; c < SB; ++c) acc[a][c] = MM<double>::mfma(fa[a], fb[c], acc[a][c]);
-      }
+      slab_mfma(sA + 2 * w * kPathBlkA, kPathBlkA, sB, kPathBlk, lane, acc);
     }
     // epilogue: the values in the caller's units, and per path the arg-best over this tile's points
 #pragma unroll
@@ -182,7 +141,7 @@ __global__ __launch_bounds__(kPathThreads, 2) void k_path_main(const PathArgs A,
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const long long p = p0 + 32 * w + 16 * a + 4 * t + (lane >> 4);
-          const double v = A.ymean + A.ystd * (A.mp + acc[a][c][t]);
+          const double v = A.ymean + A.ystd * (A.op.mp + acc[a][c][t]);
           const bool in = p < A.m && s < A.S;
           if (vals && in) vals[(size_t)p * A.S + s] = v;
           arg_take(bvv, bk, A.maximize ? v : -v, (in && v == v) ? p : kArgNone);      // (a NaN is never taken)
@@ -211,30 +170,19 @@ __global__ __launch_bounds__(kPathThreads, 2) void k_path_main(const PathArgs A,
 }
 
 // ---- per path: the residual, w = M r, c = M^T w -> B [KF + j][s] --------------------------------------------------------------------
-// One workgroup per path.  w: a wave per row, lanes along the row, butterfly (k_exp_w).  c: a thread per column, the rows i = j .. n - 1
-// in order (lanes read consecutive columns of a row).  Both orders depend on n alone.
+// One workgroup per path; both orders depend on n alone.
 __global__ __launch_bounds__(1024) void k_path_solve(const PathArgs A, const double* __restrict__ Yn /* [n][q] */, const double* __restrict__ prior /* [n][S] */,
                                                      const double* __restrict__ nz /* [S][n] */, const double* __restrict__ Fm, double* __restrict__ B) {
+  static_assert(kFactorMvThreads == 1024, "k_path_solve is launched with the workgroup of factor_lower_mv / factor_upper_mv");
   __shared__ double sr[SBO_MAX_N], sw[SBO_MAX_N];
-  const int n = A.n, ld = A.ld, s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = A.n, ld = A.ld, s = blockIdx.x;
   const double* M = Fm + (size_t)A.o * ld * ld;
-  const double sn = sqrt(A.sn2);
-  for (int j = tid; j < n; j += 1024) sr[j] = ((Yn[(size_t)j * A.q + A.o] - A.mp) - prior[(size_t)j * A.S + s]) - sn * nz[(size_t)s * n + j];
+  const double sn = sqrt(A.op.sn2);
+  for (int j = threadIdx.x; j < n; j += 1024) sr[j] = ((Yn[(size_t)j * A.q + A.o] - A.op.mp) - prior[(size_t)j * A.S + s]) - sn * nz[(size_t)s * n + j];
   __syncthreads();
-  for (int i = wave; i < n; i += 16) {
-    double t = 0.0;
-    for (int j = lane; j <= i; j += 64) t = fma(M[(size_t)i * ld + j], sr[j], t);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
-    if (lane == 0) sw[i] = t;
-  }
+  factor_lower_mv(M, ld, n, sr, sw, n);
   __syncthreads();
-  for (int j = tid; j < n; j += 1024) {
-    double t = 0.0;
-#pragma unroll 8
-    for (int i = j; i < n; ++i) t = fma(M[(size_t)i * ld + j], sw[i], t);
-    B[(size_t)(A.KF + j) * A.Spad + s] = t;
-  }
+  factor_upper_mv(M, ld, n, sw, [&](int j, double t) { B[(size_t)(A.KF + j) * A.Spad + s] = t; });
 }
 
 // ---- per path: the workgroups in order -> the result block --------------------------------------------------------------------------
@@ -264,20 +212,19 @@ template <int D, int SB>
 static int paths_enqueue_sb(sbo_ctx* c, const PathArgs& A, const PathBufs& Bf, int nwg, long long ntiles) {
   hipStream_t st = c->stream;
   const int n = A.n;
-  hipLaunchKernelGGL((k_path_prep<D>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, (const double*)Bf.Xn, Bf.As, Bf.sq);
-  SBO_HIP(hipGetLastError());
+  SBO_HIP(obs_prep<D>(st, n, &A.op, 1, Bf.Xn, Bf.As, Bf.sq));
   hipLaunchKernelGGL(k_path_bw, dim3((unsigned)(((long long)A.F * A.S + 255) / 256)), dim3(256), 0, st, A, (const double*)Bf.wt, Bf.B);
   SBO_HIP(hipGetLastError());
   // the prior at the data: the observations as the points (already normalised: X_mean = 0, X_std = 1), no observation part, the bare sum
   PathArgs P = A;
   P.m = n;
   P.KN = 0;
-  P.mp = 0.0;
+  P.op.mp = 0.0;
   P.ymean = 0.0;
   P.ystd = 1.0;
   for (int a = 0; a < kMaxD; ++a) {
-    P.X_mean[a] = 0.0;
-    P.X_std[a] = 1.0;
+    P.op.X_mean[a] = 0.0;
+    P.op.X_std[a] = 1.0;
   }
   const long long ptiles = ((long long)n + kPathTile - 1) / kPathTile;
   hipLaunchKernelGGL((k_path_main<D, SB>), dim3((unsigned)ptiles), dim3(kPathThreads), 0, st, P, ptiles, (const double*)Bf.Xn, (const double*)Bf.om,
@@ -310,12 +257,6 @@ static void paths_clear(sbo_paths_result* r) {
     r->index[s] = -1;
     r->value[s] = std::numeric_limits<double>::quiet_NaN();
   }
-}
-
-static bool all_finite(const double* p, size_t count) {
-  for (size_t t = 0; t < count; ++t)
-    if (!std::isfinite(p[t])) return false;
-  return true;
 }
 
 }  // namespace sbo
@@ -355,14 +296,7 @@ extern "C" int sbo_sample_paths(sbo_ctx* c, const sbo_paths_opts* opts, const do
   A.KN = (n + kPathKSlab - 1) / kPathKSlab * kPathKSlab;
   A.maximize = opts->maximize;
   A.m = m;
-  for (int a = 0; a < kMaxD; ++a) {
-    A.X_mean[a] = a < d ? mc.X_mean[a] : 0.0;
-    A.X_std[a] = a < d ? mc.X_std[a] : 1.0;
-    A.vinv[a] = a < d ? mc.vinv[o][a] : 0.0;
-  }
-  A.sf2 = mc.sf2[o];
-  A.sn2 = mc.sn2[o];
-  A.mp = mc.mp[o];
+  A.op = out_params(mc, o);
   A.ymean = mc.Y_mean[o];
   A.ystd = mc.Y_std[o];
   A.fscale = std::sqrt(2.0 * mc.sf2[o] / (double)F);

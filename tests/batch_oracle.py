@@ -129,12 +129,12 @@ def variance_after(ds, o, pool, picks, pending=None):
 # The cases from FIRST_LARGE on reach what lies beyond, by the constants of csrc/batch.hip (tests/test_batch_cpu.py reads them from
 # the source and holds this list to them):
 #   k_batch_v0      P = 32 points per workgroup up to n = 512, 16 up to 1024, 8 up to SBO_MAX_N = 2048, hence 1024 / P row lanes and
-#                   RB = kBatV0Rows (4) * 1024 / P = 128 | 256 | 512 rows per block; its LDS image n * P * 8 bytes is exactly 128 KiB at
+#                   RB = kWhitenRows (4) * 1024 / P = 128 | 256 | 512 rows per block; its LDS image n * P * 8 bytes is exactly 128 KiB at
 #                   n = 512, 1024 and 2048 -- n in {512, 513, 1024, 1025, 2048}, a top block of one row at 513 and 1025, m = 33 and
 #                   m = 257 no multiple of P, m = 16 one workgroup;
 #   k_batch_pass    LDS chunks of kBatChunk = 512 augmented observations: na = n + n_pending + j runs 508 .. 523 (the second chunk
 #                   starts at one row and grows) and starts at exactly 512; more than two chunks from n = 1025 up;
-#   k_batch_u       strides of kBatV0Threads = 1024 columns and 16 rows: na runs 1023 .. 1030, and up to kBatMaxAug - 1 = 2111 with
+#   k_batch_u       strides of kFactorMvThreads = 1024 columns and 16 rows: na runs 1023 .. 1030, and up to kBatMaxAug - 1 = 2111 with
 #                   the leading dimension ld = 2112 its arrays are sized for;
 #   grid stride     k_batch_pass has at most 8192 workgroups of kBatThreads = 256: m = 2 097 152 + 513 gives 513 lanes a second
 #                   candidate of their own;

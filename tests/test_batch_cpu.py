@@ -13,7 +13,7 @@ where the recursion is the reference, it differs from one full 2112 x 2112 inver
 all but the last by 7.2e-14 at the last pick, which is the arg-max there.  Smallest top-two gaps: 2.2e-6 (n = 2048), 2.2e-5
 (n = 1020), 1.4e-4 (n = 505); the planted large-m pool: 2.3e-2, its batch the four planted rows.
 
-The case list is held to the constants of csrc/batch.hip, read from the source (test_the_case_list_covers_every_edge)."""
+The case list is held to the constants of csrc/batch.hip and csrc/whiten.hpp, read from the source (test_the_case_list_covers_every_edge)."""
 import ctypes as C
 import os
 import re
@@ -63,7 +63,7 @@ def test_the_two_routes_agree_and_the_case_is_sharp(i):
 
 def _constant(text, pattern, what):
     hit = re.search(pattern, text)
-    assert hit, f"csrc/batch.hip no longer states {what} in the form this test reads: revisit batch_oracle.CASES and the pattern"
+    assert hit, f"csrc/batch.hip or csrc/whiten.hpp no longer states {what} in the form this test reads: revisit batch_oracle.CASES and the pattern"
     return [int(g) for g in hit.groups()]
 
 
@@ -78,12 +78,16 @@ def test_the_case_list_covers_every_edge():
     assert len(new) == 10 and {c["use_invK"] for c in new} == {True, False} and len(col("seed")) == len(bo.CASES)
     # the constants of the kernels, from the source: a case at each of them
     text = open(os.path.join(ROOT, "safe-bayesian-optimization_amd", "csrc", "batch.hip")).read()
-    const = lambda name: _constant(text, r"constexpr\s+int\s+" + name + r"\s*=\s*(\d+)\s*;", name)[0]
-    chunk, threads, rows, v0threads = const("kBatChunk"), const("kBatThreads"), const("kBatV0Rows"), const("kBatV0Threads")
+    shared = open(os.path.join(ROOT, "safe-bayesian-optimization_amd", "csrc", "whiten.hpp")).read()     # whiten_tile, factor_*_mv
+    const = lambda name, src=text: _constant(src, r"constexpr\s+int\s+" + name + r"\s*=\s*(\d+)\s*;", name)[0]
+    chunk, threads, rows, v0threads = const("kBatChunk"), const("kBatThreads"), const("kWhitenRows", shared), const("kWhitenThreads", shared)
+    assert const("kFactorMvThreads", shared) == v0threads      # (k_batch_u's strides)
+    assert re.search(r"__launch_bounds__\(kWhitenThreads\)\s*void\s+k_batch_v0", text) and "const int P = whiten_tier(n);" in text
+    assert re.search(r"__launch_bounds__\(kFactorMvThreads\)\s*void\s+k_batch_u", text)
     cap = _constant(text, r"const\s+int\s+nb\s*=[^;]*\(m\s*\+\s*kBatThreads\s*-\s*1\)\s*/\s*kBatThreads\s*,\s*(\d+)\s*\)\s*;",
                     "the workgroup cap of k_batch_pass")[0]
-    t1, p1, t2, p2, p3 = _constant(text, r"const\s+int\s+P\s*=\s*n\s*<=\s*(\d+)\s*\?\s*(\d+)\s*:\s*n\s*<=\s*(\d+)\s*\?\s*(\d+)\s*:\s*(\d+)\s*;",
-                                   "the tiers of k_batch_v0")
+    t1, p1, t2, p2, p3 = _constant(shared, r"int\s+whiten_tier\(int\s+n\)\s*\{\s*return\s+n\s*<=\s*(\d+)\s*\?\s*(\d+)\s*:\s*n\s*<=\s*(\d+)\s*\?\s*(\d+)\s*:\s*(\d+)\s*;",
+                                   "the tiers of whiten_tile")
     max_n = int(re.search(r"#define\s+SBO_MAX_N\s+(\d+)", open(os.path.join(ROOT, "include", "safebo.h")).read()).group(1))
     assert (chunk, threads, rows, v0threads, cap, max_n) == (512, 256, 4, 1024, 8192, _lib.SBO_MAX_N) and cap * threads == bo.M_TRIP
     assert (t1, p1, t2, p2, p3) == (512, 32, 1024, 16, 8)

@@ -58,7 +58,10 @@ def test_the_case_list_covers_every_edge():
         "csrc/paths.hip no longer pads the paths in the form this test reads: revisit paths_oracle.CASES"
     assert re.search(r"nwg\s*=\s*\(int\)std::min<long long>\(ntiles,\s*kPathGridTiles\)\s*;", text), \
         "csrc/paths.hip no longer bounds its grid in the form this test reads: revisit paths_oracle.CASES"
-    assert re.search(r"__launch_bounds__\(1024\)\s*void\s+k_path_solve", text) and text.count("j += 1024") == 2, \
+    shared = open(os.path.join(ROOT, "safe-bayesian-optimization_amd", "csrc", "whiten.hpp")).read()     # factor_lower_mv, factor_upper_mv
+    assert re.search(r"__launch_bounds__\(1024\)\s*void\s+k_path_solve", text) and text.count("j += 1024") == 1 and \
+        _constant(shared, "kFactorMvThreads") == 1024 and shared.count("j += kFactorMvThreads") == 1 and \
+        shared.count("i += kFactorMvThreads / 64") == 1 and "static_assert(kFactorMvThreads == 1024" in text, \
         "k_path_solve no longer walks in strides of 1024: revisit the n of paths_oracle.CASES"
     header = open(os.path.join(ROOT, "include", "safebo.h")).read()
     max_n = int(re.search(r"#define\s+SBO_MAX_N\s+(\d+)", header).group(1))
