@@ -774,6 +774,51 @@ int sbo_sample_paths(sbo_ctx* ctx, const sbo_paths_opts* opts, const double* ome
                      const double* points /* [m][d], raw coordinates */, double* values_out /* [m][S] or NULL */,
                      sbo_paths_result* result);
 
+/* ---- the posterior of a point list as a multivariate normal ---- */
+#define SBO_JOINT_MAX_POINTS 2048          /* m of one call: the m x m images are 32 MiB each */
+typedef struct sbo_joint_opts {
+  int32_t output;     /* 0 .. q-1 */
+  int32_t n_draws;    /* S, 0 .. SBO_MAX_PATHS */
+  int32_t noise;      /* 0: covariance of the latent f; 1: of a new observation y (adds sn2 on the diagonal) */
+  int32_t maximize;   /* 0: per draw the arg-min over the points, 1: the arg-max */
+  double  jitter;     /* >= 0, finite; in units of sf2; added to the diagonal of the matrix that is factored, and only there */
+} sbo_joint_opts;
+typedef struct sbo_joint_result {
+  int64_t index[SBO_MAX_PATHS];  /* -1 past n_draws */
+  double  value[SBO_MAX_PATHS];  /* un-normalised; NaN where index is -1 */
+  double  pivot_min;             /* smallest pivot / its diagonal entry met by the factorisation (NaN when none ran) */
+  int64_t pivot_row;             /* its row (-1 when none ran) */
+} sbo_joint_result;
+
+/* Mean vector, full covariance and S exact joint draws of one output at points[m][d] (raw coordinates, as for sbo_batch_select),
+ * m <= SBO_JOINT_MAX_POINTS.  Normalised units, with the conventions of sbo_expander_gain above (t_p = M k(X, p), sn2 as there):
+ *   mu(p)    = mp + t_p . (M (y - mp))
+ *   C(p, p') = k(p, p') - t_p . t_p'       (k with the smaller of the two squared norms first in the expanded distance: symmetric bit for bit)
+ *   A        = C + (noise sn2 + jitter sf2) I = L L^T,  L lower with a positive diagonal
+ *   f_s      = mu + L z_s,   z [S][m] the caller's standard normal numbers (NULL exactly when S = 0): the library draws nothing
+ * mean_out [m] = Y_mean + Y_std mu; cov_out [m][m] = Y_std^2 (C + noise sn2 I), symmetric bit for bit, the jitter not in it; chol_out
+ * [m][m] = Y_std L in full, zeros above the diagonal -- the matrix that is factored is cov_out's image plus Y_std^2 jitter sf2 on its
+ * diagonal, so no scaling stands behind the factorisation --; draws_out [m][S], draws_out[p][s] = Y_mean + Y_std f_s(p); every array may
+ * be NULL.  result->index[s] / value[s]: the arg-min (maximize = 1: the arg-max) of draw s over the points and the value there, ties to
+ * the lowest index, a NaN never taken.  The factorisation (blocked, right-looking, panels of 64 columns) runs only when S > 0 or
+ * chol_out is given; a pivot that is not above 2^-40 times its diagonal entry of A fails the call (the message names the row): a
+ * jitter of 1e-8 never trips that on a positive semi-definite C, a duplicated point with jitter 0 and noise 0 always does.
+ * result->pivot_min / pivot_row: the smallest pivot relative to its diagonal entry, and its row (the lowest on a tie).
+ * fp64 on the resident fp64 factor whatever the model dtype.  C(i, j) depends on the two points and the model alone, rows 0 .. r of L on
+ * the first r + 1 points alone; every sum runs in an order fixed by the element's place and n, per-draw partials are combined in
+ * workgroup order, there are no atomics, and two calls return the same bits.  Waits first for a deferred factorisation of the model
+ * (one that fails: SBO_E_INVALID).  Reads the model only: candidates, posterior, masks, plans, guard band, audit counters and options
+ * are untouched, and a sweep behind the call equals one before it bit for bit.  One host wait.  No collectives (the model is replicated:
+ * any rank may call).
+ * SBO_E_INVALID: a NULL ctx, opts, points or result; z NULL with S > 0 or given with S = 0; m < 1; output, n_draws, noise or maximize out
+ * of range; jitter negative or non-finite; a non-finite coordinate or z entry; a failed pivot.  SBO_E_NO_MODEL without a model.
+ * SBO_E_UNSUPPORTED: m > SBO_JOINT_MAX_POINTS.  On any error the result is cleared (indices -1, values and pivot_min NaN, pivot_row -1)
+ * and no output array is written. */
+int sbo_posterior_joint(sbo_ctx* ctx, const sbo_joint_opts* opts, int64_t m, const double* points /* [m][d], raw coordinates */,
+                        const double* z /* [S][m] standard normals, NULL iff S == 0 */, double* mean_out /* [m] or NULL */,
+                        double* cov_out /* [m][m] or NULL */, double* chol_out /* [m][m] or NULL */, double* draws_out /* [m][S] or NULL */,
+                        sbo_joint_result* result);
+
 /* ---- plant evaluation ------------------------------------------ */
 /* The reference's William-Otto reactor (problems/WilliamOttoReactor_Problem.py:19-93), noise-free, for n input rows
  * u[n, 2] = (Fb, Tr): out[n, 3] = (get_objective, get_constraint1, get_constraint2), each the steady state of the six

@@ -305,14 +305,17 @@ class BO(GP):
         out = self.engine.batch_select(pool, k, 0, pend, min_std)
         return out["x"], out["std"]
 
-    def Thompson(self, k, seed=0, features=1024):
+    def Thompson(self, k, seed=0, features=1024, exact=False):
         """``k`` points to evaluate side by side by safe Thompson sampling -> (X [k, d], value [k]): ``k`` functions are drawn
         jointly from the objective's posterior (``SweepEngine.sample_paths``: pathwise conditioning on ``features`` random features,
         the draws of ``SweepEngine.path_draws(d, n, k, features, seed)``), and slot j goes to the minimiser of path j over the safe
         set S of the current model (its members in ascending flat index; ties to the lowest).  ``value`` is the path's value there.
         Proposals come in path order and may repeat; an empty S gives (empty [0, d], empty [0]).  The batch is diversified by the
-        posterior itself and needs no ``b`` for the objective.  This is not reference behaviour: the reference proposes one point
-        per iteration, from bounds."""
+        posterior itself and needs no ``b`` for the objective.  With ``exact`` the draws are exact: ``SweepEngine.posterior_joint``
+        on the same pool (the posterior's full covariance and its Cholesky factor, the draws of ``SweepEngine.joint_draws(|S|, k,
+        seed)``); ``features`` is not used, and a safe set above ``SBO_JOINT_MAX_POINTS`` members raises ValueError -- an exact joint
+        draw cannot be chunked, and there is no fallback to the paths.  This is not reference behaviour: the reference proposes one
+        point per iteration, from bounds."""
         from .engine import SweepEngine
         d = self.bound.shape[0]
         _, k, _, features, seed, _, _ = SweepEngine.path_arguments(d, self.n_fun, 0, np.zeros((1, d)), k, 0, features, seed)
@@ -320,7 +323,14 @@ class BO(GP):
         pool = self._all_points()[np.nonzero(self.engine.mask("S"))[0]]          # (ascending flat index)
         if pool.shape[0] == 0:
             return np.empty((0, d)), np.empty(0)
-        out = self.engine.sample_paths(pool, k, 0, features, seed)
+        if exact:
+            from . import _lib
+            if pool.shape[0] > _lib.SBO_JOINT_MAX_POINTS:
+                raise ValueError(f"Thompson(exact=True): the safe set has {pool.shape[0]} members, above SBO_JOINT_MAX_POINTS = "
+                                 f"{_lib.SBO_JOINT_MAX_POINTS}; an exact joint draw cannot be chunked (exact=False draws paths)")
+            out = self.engine.posterior_joint(pool, 0, k, seed, return_cov=False)
+        else:
+            out = self.engine.sample_paths(pool, k, 0, features, seed)
         return out["x"], out["value"]
 
     _pair_max_eval = 1600  # evaluations of one point per refined pair (a pair costs two, and has twice the variables)

@@ -22,6 +22,7 @@ SBO_MAX_PATHS = 64
 SBO_MAX_FEATURES = 8192
 SBO_PATHS_MAX_POINTS = 1 << 24
 SBO_PATHS_MAX_VALUES = 1 << 32
+SBO_JOINT_MAX_POINTS = 2048
 
 SBO_F64, SBO_F32 = 0, 1
 SBO_MEAN, SBO_UCB, SBO_LCB, SBO_VAR = 0, 1, 2, 3
@@ -172,6 +173,15 @@ class PathsResult(C.Structure):
     _fields_ = [("index", C.c_int64 * SBO_MAX_PATHS), ("value", C.c_double * SBO_MAX_PATHS)]
 
 
+class JointOpts(C.Structure):
+    _fields_ = [("output", C.c_int32), ("n_draws", C.c_int32), ("noise", C.c_int32), ("maximize", C.c_int32), ("jitter", C.c_double)]
+
+
+class JointResult(C.Structure):
+    _fields_ = [("index", C.c_int64 * SBO_MAX_PATHS), ("value", C.c_double * SBO_MAX_PATHS), ("pivot_min", C.c_double),
+                ("pivot_row", C.c_int64)]
+
+
 class Profile(C.Structure):
     _fields_ = [
         ("posterior_ms", C.c_double), ("classify_ms", C.c_double), ("expander_ms", C.c_double),
@@ -246,6 +256,7 @@ SYMBOLS = [
     ("sbo_batch_select", C.c_int, [_P, C.POINTER(BatchOpts), C.c_int64, _P, _P, _P, C.POINTER(BatchResult)]),
     ("sbo_expander_gain", C.c_int, [_P, C.POINTER(ExpanderOpts), C.c_int64, _P, C.c_int64, _P, _P, _P, _P]),
     ("sbo_sample_paths", C.c_int, [_P, C.POINTER(PathsOpts), _P, _P, _P, _P, C.c_int64, _P, _P, C.POINTER(PathsResult)]),
+    ("sbo_posterior_joint", C.c_int, [_P, C.POINTER(JointOpts), C.c_int64, _P, _P, _P, _P, _P, _P, C.POINTER(JointResult)]),
     ("sbo_plant_wo", C.c_int, [_P, C.c_int64, _P, _P]),
     ("sbo_profile_get", C.c_int, [_P, C.POINTER(Profile)]),
     ("sbo_set_option", C.c_int, [_P, C.c_char_p, C.c_int64]),

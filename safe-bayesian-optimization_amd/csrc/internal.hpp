@@ -631,6 +631,7 @@ struct sbo_ctx {
   sbo::DevBuf batchbuf;          // sbo_batch_select: the scratch factor that grows with the picks, the pool, its variances and the state block (batch.hip)
   sbo::DevBuf expbuf;            // sbo_expander_gain: the points, their whitened vectors and posteriors, the partials and the results (expander.hip)
   sbo::DevBuf pathbuf;           // sbo_sample_paths: the draws, the B operand (scaled weights, then the update coefficients), the points, the values, the partials and the result block (paths.hip)
+  sbo::DevBuf jointbuf;          // sbo_posterior_joint: the points, their whitened vectors, the covariance, the matrix that is factored in place, the draws, the partials and the result block (joint.hip)
   // What one per-constraint chain of the set phase enqueues on and scribbles in.  Lane 0 is the main stream's: everything before
   // the fork and after the join, every sweep of a model with one constraint and every sweep on several ranks uses it alone.  With
   // two or more constraints on one rank the chains are independent, so every other constraint goes to lane 1: stream2, its own

@@ -1,6 +1,6 @@
 // whiten.hpp -- what the point calls on the resident fp64 factor M (M^T M = inv(K + sn2 I)) share: sbo_batch_select (batch.hip),
-// sbo_expander_gain (expander.hip), sbo_sample_paths (paths.hip).  The three promise the same bits from call to call and across the
-// model's history; every rounding sequence they have in common is stated here once.
+// sbo_expander_gain (expander.hip), sbo_sample_paths (paths.hip), sbo_posterior_joint (joint.hip).  They promise the same bits from call
+// to call and across the model's history; every rounding sequence they have in common is stated here once.
 //   OutParams, out_params      the constants of one output, by value inside the callers' argument blocks
 //   rbf_scale, rbf_k           a raw point in the output's scaled coordinates; the kernel with the reference's expanded distance
 //   k_obs_prep                 the observations in the scaled coordinates of gridDim.y slots

@@ -870,6 +870,93 @@ class SweepEngine:
     _paths_chunk = L.SBO_PATHS_MAX_POINTS            # points of one call
     _paths_values = L.SBO_PATHS_MAX_VALUES           # bytes of values_out of one call
 
+    @staticmethod
+    def joint_draws(m: int, n_draws: int, seed=0):
+        """The randomness of ``posterior_joint`` in unit scale: ``z`` [S, m] standard normal from ``np.random.default_rng(seed)``."""
+        return np.random.default_rng(seed).standard_normal((n_draws, m))
+
+    @staticmethod
+    def joint_arguments(d: int, q: int, points, output=0, n_draws=0, seed=0, z=None, noise=False, jitter=1e-6, maximize=False):
+        """The checks of ``posterior_joint`` that need no device: (points [m, d], output, n_draws, seed, z [S, m] contiguous float64
+        or None, noise as 0 | 1, jitter, maximize as 0 | 1), or ValueError.  With ``z`` the number of draws is that of its rows.
+        ``d`` / ``q`` < 1 (no model yet): what depends on them is the library's to check.  A pool above ``SBO_JOINT_MAX_POINTS`` is
+        refused here: a joint draw cannot be chunked."""
+        pts = _f64(points)
+        if pts.ndim == 1:
+            pts = pts.reshape(1, -1)
+        if pts.ndim != 2 or pts.shape[0] < 1 or pts.shape[1] < 1 or (d >= 1 and pts.shape[1] != d):
+            raise ValueError("points must be [m, d] for the model's d, m >= 1")
+        if pts.shape[0] > L.SBO_JOINT_MAX_POINTS:
+            raise ValueError(f"at most SBO_JOINT_MAX_POINTS = {L.SBO_JOINT_MAX_POINTS} points per call (a joint draw cannot be chunked)")
+        for name, val in (("output", output), ("n_draws", n_draws), ("seed", seed)):
+            if isinstance(val, bool) or not isinstance(val, (int, np.integer)):
+                raise ValueError(f"{name} must be an integer")
+        if output < 0 or (q >= 1 and output >= q):
+            raise ValueError("output out of range [0, q)")
+        if seed < 0:
+            raise ValueError("seed must be >= 0")
+        for name, val in (("noise", noise), ("maximize", maximize)):
+            if not isinstance(val, (bool, np.bool_)) and not (isinstance(val, (int, np.integer)) and val in (0, 1)):
+                raise ValueError(f"{name} must be a bool")
+        if isinstance(jitter, bool) or not isinstance(jitter, (int, float, np.integer, np.floating)):
+            raise ValueError("jitter must be a number")
+        jitter = float(jitter)
+        if not np.isfinite(jitter) or jitter < 0.0:
+            raise ValueError("jitter must be finite and >= 0")
+        if z is not None:
+            z = np.ascontiguousarray(_f64(z))
+            if z.ndim == 1:
+                z = z.reshape(1, -1)
+            if z.ndim != 2 or z.shape[0] < 1 or z.shape[1] != pts.shape[0]:
+                raise ValueError("z must be [S, m], S >= 1")
+            if not np.all(np.isfinite(z)):
+                raise ValueError("z must be finite")
+            n_draws = z.shape[0]
+        if not 0 <= n_draws <= L.SBO_MAX_PATHS:
+            raise ValueError(f"n_draws must be in [0, {L.SBO_MAX_PATHS}]")
+        if not np.all(np.isfinite(pts)):
+            raise ValueError("points must be finite")
+        return pts, int(output), int(n_draws), int(seed), z, int(bool(noise)), jitter, int(bool(maximize))
+
+    def posterior_joint(self, points, output: int = 0, n_draws: int = 0, seed: int = 0, z=None, noise: bool = False, jitter: float = 1e-6,
+                        maximize: bool = False, return_cov: bool = True, return_chol: bool = False, return_draws: bool = False) -> dict:
+        """The posterior of ``output`` at ``points`` [m, d] as a multivariate normal (``sbo_posterior_joint``):
+        ``mean`` [m], with ``return_cov`` ``cov`` [m, m] (symmetric bit for bit; ``noise``: of a new observation, sn2 on the diagonal),
+        with ``return_chol`` ``chol`` [m, m] (lower, ``chol chol^T = cov + Y_std^2 jitter sf2 I``), and ``n_draws`` exact joint draws
+        ``mean + chol z_s`` from ``z`` [S, m] standard normals (default ``joint_draws(m, n_draws, seed)``): ``index`` [S] (per draw its
+        arg-min over the points, ``maximize``: arg-max; the lowest row on a tie), ``x`` [S, d], ``value`` [S] and, with
+        ``return_draws``, ``draws`` [m, S].  ``pivot_min`` / ``pivot_row``: the smallest pivot of the factorisation relative to its
+        diagonal entry and its row (NaN / -1 when no factor was needed).  ``jitter`` (in units of sf2) goes on the diagonal of the
+        matrix that is factored and nowhere else; a pivot below 2^-40 of its diagonal entry raises ValueError.  At most
+        ``SBO_JOINT_MAX_POINTS`` points: a joint draw cannot be chunked.  fp64 whatever the model dtype; nothing resident is touched.
+        This is not reference behaviour."""
+        pts, output, S, seed, z, noise, jitter, maximize = self.joint_arguments(self.d, self.q, points, output, n_draws, seed, z, noise,
+                                                                                jitter, maximize)
+        m = pts.shape[0]
+        if z is None and S > 0:
+            z = np.ascontiguousarray(self.joint_draws(m, S, seed))
+        opts, res = L.JointOpts(output, S, noise, maximize, jitter), L.JointResult()
+        mean = np.empty(m)
+        cov = np.empty((m, m)) if return_cov else None
+        chol = np.empty((m, m)) if return_chol else None
+        draws = np.empty((m, S)) if return_draws and S > 0 else None
+        L.check(self._lib.sbo_posterior_joint(self._ctx, C.byref(opts), m, _ptr(pts), _ptr(z), _ptr(mean), _ptr(cov), _ptr(chol), _ptr(draws),
+                                              C.byref(res)))
+        out = {"mean": mean}
+        if return_cov:
+            out["cov"] = cov
+        if return_chol:
+            out["chol"] = chol
+        if return_draws:
+            out["draws"] = draws if draws is not None else np.empty((m, 0))
+        if S > 0:
+            index = np.array(res.index[:S], dtype=np.int64)
+            x = np.full((S, pts.shape[1]), np.nan)
+            x[index >= 0] = pts[index[index >= 0]]
+            out["index"], out["x"], out["value"] = index, x, np.array(res.value[:S], dtype=np.float64)
+        out["pivot_min"], out["pivot_row"] = float(res.pivot_min), int(res.pivot_row)
+        return out
+
     def mask(self, which: str, c: int = 0) -> np.ndarray:
         w = {"S": L.SBO_MASK_S, "U": L.SBO_MASK_U, "M": L.SBO_MASK_M, "G": L.SBO_MASK_G, "O": L.SBO_MASK_O}[which]
         out = np.empty(self.n_local, dtype=np.uint8)
