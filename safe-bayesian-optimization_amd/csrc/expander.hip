@@ -7,13 +7,13 @@
 //   s = v_c(g) + sn2_c,   mu' = mu_c(x) + cov b sqrt(max(0, v_c(g))) / s,   v' = v_c(x) - cov^2 / s,
 //   z_c(x | g) = mu' - b sqrt(max(0, v')) + Y_mean[c] / Y_std[c],   Z(x | g) = min over the masked constraints of z_c(x | g)
 // and per source count = #{x : Z >= 0}, margin = max_x Z, witness = its index (lowest on a tie).
-//   k_obs_prep    (whiten.hpp) the observations in the scaled coordinates of every masked constraint
-//   k_exp_w       the whitened residuals w = M_c (y_c - mp_c): mu_c(p) = mp_c + k_c(X, p) . alpha_c = mp_c + t_p . w
-//   k_exp_stage1  per (constraint, point): t_p [point][ldt] (zero beyond n), mu, v and the point's scaled coordinates; whiten_tile
-//                 (whiten.hpp) on a padded LDS image, O((ms + mt) n^2) on the vector units
+//   k_obs_prep, k_whiten_resid   (through ObsResident, slab_tiles.hpp) the observations in the scaled coordinates of every masked constraint
+//                 and the whitened residuals w = M_c (y_c - mp_c): mu_c(p) = mp_c + k_c(X, p) . alpha_c = mp_c + t_p . w
+//   k_exp_stage1  per (constraint, point): t_p [point][ldt] (zero beyond n), mu, v and the point's scaled coordinates; whiten_stage1
+//                 (slab_tiles.hpp) on a padded LDS image, O((ms + mt) n^2) on the vector units
 //   k_exp_pairs   the hot path, O(ms mt n) per constraint on the matrix cores: a workgroup owns a 64 x 64 (source x target) tile, a wave
-//                 32 x 32 of it as 2 x 2 accumulators of MM<double> (v_mfma_f64_4x4x4, four per step); per constraint the K-loop runs
-//                 over LDS-staged slabs of t, the epilogue turns t_x . t_g into z_c and keeps the running Z in registers; behind the last
+//                 32 x 32 of it as 2 x 2 accumulators of MM<double> (v_mfma_f64_4x4x4, four per step); per constraint tile64_product
+//                 (slab_tiles.hpp) runs over LDS-staged slabs of t, the epilogue turns t_x . t_g into z_c and keeps the running Z in registers; behind the last
 //                 constraint a count and an arg-best per source row; the target tiles are split over the grid, one partial per
 //                 (split, source).  No [ms][mt] array exists.
 //   k_exp_finish  per source: the counts summed and the arg-best taken over the splits in order
@@ -23,20 +23,18 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
-#include "whiten.hpp"
+#include "slab_tiles.hpp"
 
 namespace sbo {
 
 constexpr int kExpTile = 64;                     // sources x targets of one workgroup tile of k_exp_pairs (2 x 2 waves of 32 x 32)
 constexpr int kExpThreads = 256;                 // k_exp_pairs / k_exp_finish
-constexpr int kExpKSlab = 32;                    // observations of one LDS slab of k_exp_pairs; t rows are zero-padded to a multiple (ldt)
 constexpr int kExpGridTiles = 1024;              // workgroups k_exp_pairs aims at: target splits = min(target tiles, kExpGridTiles / source tiles)
-constexpr size_t kExpS1Lds = 144 * 1024;         // k_exp_stage1: whiten_tile's image [n][P + 1], P = whiten_tier(n): full at SBO_MAX_N
-static_assert(kExpTile == 64 && kExpThreads == 256 && kExpKSlab == kSlabK, "k_exp_pairs: 4 waves of 32 x 32, slabs staged 8 observations per thread");
+static_assert(kExpTile == 64 && kExpThreads == kTileThreads, "k_exp_pairs: tile64_product's tile and workgroup");
 
 struct ExpArgs {                                 // by value (kernarg segment)
   int n, d, ld, pad0;                            // observations, input dimension, leading dimension of the resident factor
-  int ldt, nc, q, pad;                           // leading dimension of t (n rounded up to kExpKSlab), masked constraints, outputs of the model
+  int ldt, nc, q, pad;                           // leading dimension of t (n rounded up to kSlabK), masked constraints, outputs of the model
   long long ms, mt;
   int out[kMaxQ];                                // [slot]: the output a masked constraint is
   OutParams op[kMaxQ];                           // [slot]
@@ -49,28 +47,15 @@ struct ExpState {                                // device: the verdict of stage
 };
 
 struct ExpBufs {
-  double *Xn, *Yn, *As, *sq, *w, *pts, *T, *mu, *v, *bs, *bsq, *pval, *margin;
+  ObsResident obs;
+  double *pts, *T, *mu, *v, *bs, *bsq, *pval, *margin;
   long long *pcount, *pidx, *count, *witness;
   ExpState* st;
 };
 
-// ---- the whitened residuals w = M (y - mp) of every slot: w [nc][ldt] ------------------------------------------------------------------
-// One workgroup per slot (factor_lower_mv, whiten.hpp).  With t_p = M k_p the mean is mp + k_p . alpha = mp + t_p . w (alpha = M^T M
-// (y - mp)): the call rests on the factor and the data alone, so whatever leaves the first n rows of the factor as they are -- an
-// append and the removal of that row -- leaves the call's bits as they are.
-__global__ __launch_bounds__(kFactorMvThreads) void k_exp_w(const ExpArgs A, const double* __restrict__ Yn /* [n][q] */,
-                                                            const double* __restrict__ F, double* __restrict__ w) {
-  __shared__ double sy[SBO_MAX_N];
-  const int n = A.n, ld = A.ld, slot = blockIdx.x, o = A.out[slot];
-  for (int j = threadIdx.x; j < n; j += kFactorMvThreads) sy[j] = Yn[(size_t)j * A.q + o] - A.op[slot].mp;
-  __syncthreads();
-  factor_lower_mv(F + (size_t)o * ld * ld, ld, n, sy, w + (size_t)slot * A.ldt, A.ldt);
-}
-
 // ---- stage 1: t = M k_p, mu = mp + t . w, v = sf2 - ||t||^2 per (slot, point) ---------------------------------------------------
-// A workgroup owns P points of the list sources | targets (whiten_tile, whiten.hpp), the image with a leading dimension of P + 1 (the
-// write-out below reads columns); one thread per point adds the squares and the products with w in row order.  The image is then
-// written out as t [point][ldt], lanes along a row, zeros from n to ldt.
+// whiten_stage1 (slab_tiles.hpp) over the list sources | targets; this kernel's own: one thread per point adds the squares and the products
+// with w in row order.
 template <int D>
 __global__ __launch_bounds__(kWhitenThreads) void k_exp_stage1(const ExpArgs A, int P, const double* __restrict__ As, const double* __restrict__ sq,
                                                                const double* __restrict__ F, const double* __restrict__ w,
@@ -79,63 +64,43 @@ __global__ __launch_bounds__(kWhitenThreads) void k_exp_stage1(const ExpArgs A, 
                                                                ExpState* __restrict__ st) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double* sK = reinterpret_cast<double*>(smem);             // [n][P + 1]
-  const int n = A.n, ld = A.ld, slot = blockIdx.y, o = A.out[slot], tid = threadIdx.x, ldk = P + 1;
+  const int n = A.n, ld = A.ld, slot = blockIdx.y, o = A.out[slot], ldk = P + 1;
   const OutParams& op = A.op[slot];
-  const long long m = A.ms + A.mt, i = (long long)blockIdx.x * P + tid % P;
-  const bool on = i < m;
+  const long long m = A.ms + A.mt;
   const double* wo = w + (size_t)slot * A.ldt;
-  const size_t rec = (size_t)slot * m + (size_t)(on ? i : 0);
-  double b[D];
-  const double bsq = rbf_scale<D>(op, pts + (size_t)(on ? i : 0) * A.d, on, b);
-  if (tid < P && on) {                                  // (tid % P == tid)
-    bsq_out[rec] = bsq;
-#pragma unroll
-    for (int t = 0; t < D; ++t) bs[rec * D + t] = b[t];
-  }
-  whiten_tile<D>(sK, ldk, P, n, op.sf2, As + (size_t)slot * n * D, sq + (size_t)slot * n, F + (size_t)o * ld * ld, ld, b, bsq, on);
-  if (tid < P && on) {
-    double s = 0.0, dot = 0.0;
-    for (int j = 0; j < n; ++j) {
-      const double t = sK[j * ldk + tid];
-      s += t * t;
-      dot = fma(t, wo[j], dot);
-    }
-    const double vv = op.sf2 - s;
-    v[rec] = vv;
-    mu[rec] = op.mp + dot;
-    if (i < A.ms && !(vv + op.sn2 > 0.0)) st->bad = 1;      // (every writer stores the same value)
-  }
-  const int ldt = A.ldt;
-  for (int e = tid; e < P * ldt; e += kWhitenThreads) {
-    const int pp = e / ldt, j = e - pp * ldt;
-    const long long ii = (long long)blockIdx.x * P + pp;
-    if (ii < m) T[((size_t)slot * m + (size_t)ii) * ldt + j] = j < n ? sK[j * ldk + pp] : 0.0;
-  }
+  whiten_stage1<D>(sK, P, n, op, As + (size_t)slot * n * D, sq + (size_t)slot * n, F + (size_t)o * ld * ld, ld, pts, m, (size_t)slot * m, T, A.ldt, bs,
+                   bsq_out, [&](size_t rec, long long i, int col) {
+                     double s = 0.0, dot = 0.0;
+                     for (int j = 0; j < n; ++j) {
+                       const double t = sK[j * ldk + col];
+                       s += t * t;
+                       dot = fma(t, wo[j], dot);
+                     }
+                     const double vv = op.sf2 - s;
+                     v[rec] = vv;
+                     mu[rec] = op.mp + dot;
+                     if (i < A.ms && !(vv + op.sn2 > 0.0)) st->bad = 1;      // (every writer stores the same value)
+                   });
 }
 
 // ---- stage 2: the pair tiles ----------------------------------------------------------------------------------------------------------
 // Workgroup (bx, by): source tile bx, target tiles by, by + nsplit, ..  Wave w owns sources 32 (w >> 1) .. + 31 and targets 32 (w & 1) ..
-// + 31 of the tile: acc[a][c][t] of lane l is the pair (source 32 (w >> 1) + 16 a + 4 t + (l >> 4), target 32 (w & 1) + 16 c + (l & 15)),
-// the D layout of the 4x4x4 form (device_common.hpp).  LDS images of a slab (whiten.hpp): the sources are the A side, the targets the
-// B side.  Rows past ms / mt are staged as zeros and never counted.
+// + 31 of the tile: acc[a][c][t] is the pair (source tile64_row(a, t), target tile64_col(c)) (slab_tiles.hpp); the sources are the A
+// side of tile64_product, the targets the B side.  Rows past ms / mt are staged as zeros and never counted.
 template <int D>
 __global__ __launch_bounds__(kExpThreads, 2) void k_exp_pairs(const ExpArgs A, int nsplit, long long ntt, const double* __restrict__ T,
                                                            const double* __restrict__ mu, const double* __restrict__ v,
                                                            const double* __restrict__ bs, const double* __restrict__ bsq,
                                                            long long* __restrict__ pcount, double* __restrict__ pval, long long* __restrict__ pidx) {
   constexpr int LB = D + 1;                              // leading dimension of the coordinate images (targets are read 16 rows at a time)
-  constexpr int BLK = 16 * kExpKSlab;                    // doubles of one 16-point block of a slab image
-  __shared__ __attribute__((aligned(32))) double sA[kExpTile * kExpKSlab], sB[kExpTile * kExpKSlab];
+  __shared__ __attribute__((aligned(32))) double sA[kExpTile * kSlabK], sB[kExpTile * kSlabK];
   __shared__ double gS[kExpTile], gCoef[kExpTile], gSq[kExpTile], gB[kExpTile * LB];      // sources: s, b sqrt(max(0, v)) / s, |.|^2, coordinates
   __shared__ double xMu[kExpTile], xV[kExpTile], xSq[kExpTile], xB[kExpTile * LB];        // targets
   __shared__ long long rCnt[4][32], rIdx[4][32];
   __shared__ double rVal[4][32];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, ws = w >> 1, wt = w & 1;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const long long m = A.ms + A.mt, g0 = (long long)blockIdx.x * kExpTile;
-  const int ldt = A.ldt;
-  const int srow = tid >> 2, sk = (tid & 3) * 8;          // staging: this thread's point of the tile and its 8 observations of the slab
-  // where observation sk of point srow goes in the two images; observation sk + e, e = 0 .. 7: slab_col(e) behind it
-  const int posA = (srow >> 4) * BLK + slab_pos_a(srow, sk), posB = (srow >> 4) * BLK + slab_pos_b(srow, sk);
+  const int ldt = A.ldt, srow = tile64_stage_row();       // staging: this thread's point of the tile
   long long run_cnt = 0, run_idx = kArgNone;              // threads 0 .. 63: source g0 + tid over this workgroup's target tiles
   double run_val = 0.0;
   for (long long tt = blockIdx.y; tt < ntt; tt += nsplit) {
@@ -156,54 +121,24 @@ __global__ __launch_bounds__(kExpThreads, 2) void k_exp_pairs(const ExpArgs A, i
         const double vg = on ? v[rec] : 0.0, s = on ? vg + A.op[slot].sn2 : 1.0;
         gS[tid] = s;
         gCoef[tid] = on ? A.b * sqrt(fmax(0.0, vg)) / s : 0.0;
-        gSq[tid] = on ? bsq[rec] : 0.0;
-#pragma unroll
-        for (int t = 0; t < D; ++t) gB[tid * LB + t] = on ? bs[rec * D + t] : 0.0;
+        point_image<D>(gSq, gB, tid, bsq, bs, rec, on);
       } else if (tid < 2 * kExpTile) {
         const int c = tid - kExpTile;
         const bool on = x0 + c < A.mt;
         const size_t rec = base + (size_t)A.ms + (size_t)(on ? x0 + c : 0);
         xMu[c] = on ? mu[rec] : 0.0;
         xV[c] = on ? v[rec] : 0.0;
-        xSq[c] = on ? bsq[rec] : 0.0;
-#pragma unroll
-        for (int t = 0; t < D; ++t) xB[c * LB + t] = on ? bs[rec * D + t] : 0.0;
+        point_image<D>(xSq, xB, c, bsq, bs, rec, on);
       }
       d4_t acc[2][2];
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) acc[a][c] = d4_t{0.0, 0.0, 0.0, 0.0};
       const bool son = g0 + srow < A.ms, ton = x0 + srow < A.mt;
-      const double* Ts = T + (base + (size_t)(son ? g0 + srow : 0)) * ldt + sk;
-      const double* Tt = T + (base + (size_t)A.ms + (size_t)(ton ? x0 + srow : 0)) * ldt + sk;
-      for (int k0 = 0; k0 < ldt; k0 += kExpKSlab) {
-        d4_t s0, s1, t0, t1;
-        s0 = s1 = t0 = t1 = d4_t{0.0, 0.0, 0.0, 0.0};
-        if (son) {
-          s0 = *reinterpret_cast<const d4_t*>(Ts + k0);
-          s1 = *reinterpret_cast<const d4_t*>(Ts + k0 + 4);
-        }
-        if (ton) {
-          t0 = *reinterpret_cast<const d4_t*>(Tt + k0);
-          t1 = *reinterpret_cast<const d4_t*>(Tt + k0 + 4);
-        }
-        __syncthreads();                                  // (the slab before this one has been read)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          sA[posA + slab_col(e)] = s0[e];
-          sA[posA + slab_col(4 + e)] = s1[e];
-          sB[posB + slab_col(e)] = t0[e];
-          sB[posB + slab_col(4 + e)] = t1[e];
-        }
-        __syncthreads();
-        slab_mfma(sA + 2 * ws * BLK, BLK, sB + 2 * wt * BLK, BLK, lane, acc);
-      }
+      tile64_product(sA, sB, T + (base + (size_t)(son ? g0 + srow : 0)) * ldt, son,
+                     T + (base + (size_t)A.ms + (size_t)(ton ? x0 + srow : 0)) * ldt, ton, ldt, acc);
       // epilogue of this constraint: t_x . t_g -> z_c(x | g), the running minimum (a NaN stays)
       const double sf2 = A.op[slot].sf2, shift = A.shift[slot], bb = A.b;
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
-        const int col = 32 * wt + 16 * c + (lane & 15);
+        const int col = tile64_col(c);
         double xb[D];
 #pragma unroll
         for (int t = 0; t < D; ++t) xb[t] = xB[col * LB + t];
@@ -212,7 +147,7 @@ __global__ __launch_bounds__(kExpThreads, 2) void k_exp_pairs(const ExpArgs A, i
         for (int a = 0; a < 2; ++a)
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
-            const int row = 32 * ws + 16 * a + 4 * t + (lane >> 4);
+            const int row = tile64_row(a, t);
             const double cov = rbf_k<D>(sf2, gB + row * LB, gSq[row], xb, xsq) - acc[a][c][t];
             const double m1 = xmu + cov * gCoef[row], v1 = xv - cov * cov / gS[row];
             const double z = (m1 - bb * sqrt(fmax(0.0, v1))) + shift;
@@ -231,7 +166,7 @@ __global__ __launch_bounds__(kExpThreads, 2) void k_exp_pairs(const ExpArgs A, i
         double bv = 0.0;
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-          const long long x = x0 + 32 * wt + 16 * c + (lane & 15);
+          const long long x = x0 + tile64_col(c);
           const double z = Z[a][c][t];
           const bool on = x < A.mt;
           cnt += (on && z >= 0.0) ? 1 : 0;
@@ -245,7 +180,7 @@ __global__ __launch_bounds__(kExpThreads, 2) void k_exp_pairs(const ExpArgs A, i
           arg_take(bv, bk, ov, ok);
         }
         if ((lane & 15) == 0) {
-          const int row = 16 * a + 4 * t + (lane >> 4);    // of the wave's 32 sources
+          const int row = tile64_row(a, t) & 31;           // of the wave's 32 sources
           rCnt[w][row] = cnt;
           rVal[w][row] = bv;
           rIdx[w][row] = bk;
@@ -291,15 +226,11 @@ static int expander_enqueue(sbo_ctx* c, const ExpArgs& A, const ExpBufs& B, int 
   hipStream_t st = c->stream;
   const int n = A.n;
   const long long m = A.ms + A.mt;
-  SBO_HIP(obs_prep<D>(st, n, A.op, A.nc, B.Xn, B.As, B.sq));
-  hipLaunchKernelGGL(k_exp_w, dim3((unsigned)A.nc), dim3(kFactorMvThreads), 0, st, A, (const double*)B.Yn, c->factor.F(), B.w);
-  SBO_HIP(hipGetLastError());
-  const int P = whiten_tier(n);
-  const size_t lds = sizeof(double) * (size_t)n * (P + 1);
-  if (lds > kExpS1Lds) return fail(SBO_E_UNSUPPORTED, "sbo_expander_gain: the model is too large");      // (n <= SBO_MAX_N: never)
-  SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_exp_stage1<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kExpS1Lds));
-  hipLaunchKernelGGL((k_exp_stage1<D>), dim3((unsigned)((m + P - 1) / P), (unsigned)A.nc), dim3(kWhitenThreads), lds, st, A, P, (const double*)B.As,
-                     (const double*)B.sq, c->factor.F(), (const double*)B.w, (const double*)B.pts, B.T, B.mu, B.v, B.bs, B.bsq, B.st);
+  if (int rc = B.obs.prepare<D>(c, st, A.op, A.out, A.nc, A.ldt)) return rc;
+  Stage1Launch S1;
+  if (int rc = whiten_stage1_launch(k_exp_stage1<D>, "sbo_expander_gain", n, m, S1)) return rc;
+  hipLaunchKernelGGL((k_exp_stage1<D>), dim3(S1.blocks, (unsigned)A.nc), dim3(kWhitenThreads), S1.lds, st, A, S1.P, (const double*)B.obs.As,
+                     (const double*)B.obs.sq, c->factor.F(), (const double*)B.obs.w, (const double*)B.pts, B.T, B.mu, B.v, B.bs, B.bsq, B.st);
   SBO_HIP(hipGetLastError());
   const long long nst = (A.ms + kExpTile - 1) / kExpTile;
   hipLaunchKernelGGL((k_exp_pairs<D>), dim3((unsigned)nst, (unsigned)nsplit), dim3(kExpThreads), 0, st, A, nsplit, ntt, (const double*)B.T,
@@ -344,7 +275,7 @@ extern "C" int sbo_expander_gain(sbo_ctx* c, const sbo_expander_opts* opts, int6
   A.n = n;
   A.d = d;
   A.q = q;
-  A.ldt = (n + kExpKSlab - 1) / kExpKSlab * kExpKSlab;
+  A.ldt = (n + kSlabK - 1) / kSlabK * kSlabK;
   A.ms = ms;
   A.mt = mt;
   A.b = opts->b;
@@ -370,11 +301,7 @@ extern "C" int sbo_expander_gain(sbo_ctx* c, const sbo_expander_opts* opts, int6
   const size_t nc = (size_t)A.nc;
   ExpBufs B;
   auto layout = [&](Carve cv) {
-    cv.take(B.Xn, (size_t)n * d);
-    cv.take(B.Yn, (size_t)n * q);
-    cv.take(B.As, nc * n * D);
-    cv.take(B.sq, nc * n);
-    cv.take(B.w, nc * A.ldt);
+    B.obs.take(cv, mc, nc, A.ldt);
     cv.take(B.pts, m * d);
     cv.take(B.T, nc * m * A.ldt);
     cv.take(B.mu, nc * m);
@@ -394,8 +321,7 @@ extern "C" int sbo_expander_gain(sbo_ctx* c, const sbo_expander_opts* opts, int6
   hipStream_t st = c->stream;
   const ExpState init{};
   SBO_HIP(hipMemcpyAsync(B.st, &init, sizeof(init), hipMemcpyHostToDevice, st));
-  SBO_HIP(hipMemcpyAsync(B.Xn, c->h_Xnorm.data(), sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, st));
-  SBO_HIP(hipMemcpyAsync(B.Yn, c->h_Ynorm.data(), sizeof(double) * (size_t)n * q, hipMemcpyHostToDevice, st));
+  SBO_HIP(B.obs.upload(c, st));
   SBO_HIP(hipMemcpyAsync(B.pts, sources, sizeof(double) * (size_t)ms * d, hipMemcpyHostToDevice, st));
   SBO_HIP(hipMemcpyAsync(B.pts + (size_t)ms * d, targets, sizeof(double) * (size_t)mt * d, hipMemcpyHostToDevice, st));
   rc = with_dpad(D, [&](auto DD) { return expander_enqueue<DD()>(c, A, B, nsplit, ntt); });

@@ -743,6 +743,15 @@ template <class F> auto with_dpad(int dpad, F&& f) {
     default: return f(std::integral_constant<int, 8>{});
   }
 }
+// S paths or draws in padded columns, 16 | 32 | 64 (S = 1 does not pay for 64), and f(std::integral_constant<int, Spad / 16>)
+inline int spad_of(int S) { return S <= 16 ? 16 : S <= 32 ? 32 : 64; }
+template <class F> auto with_spad(int Spad, F&& f) {
+  switch (Spad) {
+    case 16: return f(std::integral_constant<int, 1>{});
+    case 32: return f(std::integral_constant<int, 2>{});
+    default: return f(std::integral_constant<int, 4>{});
+  }
+}
 
 // the posterior inside a sweep, without synchronisation or timing (api.hip); `out` (nullptr: not wanted) is reset first
 int posterior_enqueue(sbo_ctx* c, const PostRequest& req, PostOutcome* out);

@@ -7,20 +7,22 @@
 // sn2 I) is formed once per element, A' = cov + Y_std^2 (jitter sf2) I is factored as A' = L' L'^T, and chol_out is L' = Y_std L with no
 // scaling behind the factorisation (the factor of a one-point list is then the correctly rounded square root of the entry returned in
 // cov_out plus the jitter).  The pivot threshold is relative, so the scale does not enter it.
-//   k_obs_prep      (whiten.hpp) the observations in the output's scaled coordinates and their squares
-//   k_joint_w       the whitened residuals w = M (y - mp)
-//   k_joint_stage1  per point: t_p [point][ldt] (zero beyond n), mu, the mean in the caller's units, the scaled coordinates; whiten_tile
-//   k_joint_cov     C = Kpp - T T^T in 64 x 64 tiles of the lower triangle on the matrix cores (2 x 2 waves of 32 x 32, MM<double>, K in
+//   k_obs_prep, k_whiten_resid   (through ObsResident, slab_tiles.hpp) the observations in the output's scaled coordinates and their
+//                   squares; the whitened residuals w = M (y - mp)
+//   k_joint_stage1  per point: t_p [point][ldt] (zero beyond n), mu, the mean in the caller's units, the scaled coordinates;
+//                   whiten_stage1 (slab_tiles.hpp)
+//   k_joint_cov     C = Kpp - T T^T in 64 x 64 tiles of the lower triangle on the matrix cores (tile64_product, slab_tiles.hpp, K in
 //                   slabs of 32 over ldt); the epilogue takes k(p, p') with the smaller of the two squared norms first -- the expanded
 //                   distance is not symmetric in its rounding, the ordered one is --, subtracts the accumulator and stores the element
 //                   and its mirror from one register; the matrix to factor gets the same value plus the jitter on its diagonal
 //   k_joint_diag    blocked right-looking Cholesky, panels of 64 columns: the diagonal block by one workgroup in LDS, pivots checked
 //                   against 2^-40 of their diagonal entry, the relative minimum and its row into the state block
 //   k_joint_panel   L21 = A21 L11^-T, a workgroup per block of 64 rows, a row per lane
-//   k_joint_update  A22 -= L21 L21^T as lower-triangle tiles on the matrix cores over the whole chip
-//   k_joint_draw    F = L' Z^T per tile of 128 points x Spad draws (k_path_main's shape), the slabs above the diagonal skipped; epilogue:
-//                   Y_mean + (Y_std mu + acc), stored [m][S] where asked, the arg-best per draw as workgroup partials
-//   k_joint_finish  the partials in workgroup order and the pivot record -> the result block
+//   k_joint_update  A22 -= L21 L21^T as lower-triangle tiles on the matrix cores over the whole chip (tile64_product)
+//   k_joint_draw    F = L' Z^T per tile of 128 points x Spad draws (tile128_step, slab_tiles.hpp), the slabs above the diagonal skipped;
+//                   epilogue (tile128_arg_best): Y_mean + (Y_std mu + acc), stored [m][S] where asked, the arg-best per draw as
+//                   workgroup partials
+//   k_joint_finish  the partials of the workgroups (partials_merge) and the pivot record -> the result block
 //   k_joint_lower   the factor in full, zeros above the diagonal
 // Every sum runs in an order fixed by the element's (row, column) and n alone: C(i, j) depends on the two points and the model, rows
 // 0 .. r of L on the first r + 1 points, and two calls return the same bits.  No atomics.  One host wait; nothing resident is written.
@@ -29,18 +31,16 @@
 #include <cstring>
 #include <limits>
 #include <vector>
-#include "whiten.hpp"
+#include "slab_tiles.hpp"
 
 namespace sbo {
 
 constexpr int kJointTile = 64;                   // rows x columns of one workgroup tile of k_joint_cov / k_joint_update; the panel width
 constexpr int kJointThreads = 256;               // every kernel of the factorisation and the two products
 constexpr int kJointDrawTile = 128;              // points of one workgroup tile of k_joint_draw (4 waves x 32 points)
-constexpr int kJointBlk = 16 * kSlabK;           // doubles of one 16-row block of a slab image
-constexpr int kJointBlkA = kJointBlk + 16;       // ... and the distance between two blocks of k_joint_draw's A image (as k_path_main)
-constexpr size_t kJointS1Lds = 144 * 1024;       // k_joint_stage1: whiten_tile's image [n][P + 1], P = whiten_tier(n): full at SBO_MAX_N
 constexpr double kJointPivotRel = 0x1p-40;       // a pivot must exceed this times its diagonal entry of A
-static_assert(kJointTile == 64 && kJointThreads == 256 && kSlabK == 32, "4 waves of 32 x 32, slabs staged 8 columns per thread, panels of two slabs");
+static_assert(kJointTile == 64 && kJointThreads == kTileThreads && kJointTile == 2 * kSlabK, "tile64_product's tile and workgroup; panels of two slabs");
+static_assert(kJointDrawTile == kTile128, "k_joint_draw: tile128_step's tile");
 static_assert(SBO_MAX_PATHS == 64, "k_joint_draw is instantiated for 16, 32 and 64 padded draws");
 static_assert(SBO_JOINT_MAX_POINTS % kJointDrawTile == 0, "the padded order of the images is a multiple of both tiles");
 
@@ -59,7 +59,8 @@ struct JointState {                              // device: the record of the fa
 };
 
 struct JointBufs {
-  double *Xn, *Yn, *As, *sq, *w, *pts, *T, *mu, *mean, *bs, *bsq, *cov, *A, *dg, *rinv, *Lout, *Zt, *draws, *pval;
+  ObsResident obs;
+  double *pts, *T, *mu, *mean, *bs, *bsq, *cov, *A, *dg, *rinv, *Lout, *Zt, *draws, *pval;
   long long* pidx;
   JointState* st;
   sbo_joint_result* res;
@@ -72,17 +73,7 @@ __device__ __forceinline__ void joint_tile(int b, int& ti, int& tj) {
   tj = b - ti * (ti + 1) / 2;
 }
 
-// ---- the whitened residuals w = M (y - mp): w [ldt] (factor_lower_mv, whiten.hpp) -----------------------------------------------------
-__global__ __launch_bounds__(kFactorMvThreads) void k_joint_w(const JointArgs A, const double* __restrict__ Yn /* [n][q] */,
-                                                              const double* __restrict__ F, double* __restrict__ w) {
-  __shared__ double sy[SBO_MAX_N];
-  const int n = A.n, ld = A.ld;
-  for (int j = threadIdx.x; j < n; j += kFactorMvThreads) sy[j] = Yn[(size_t)j * A.q + A.o] - A.op.mp;
-  __syncthreads();
-  factor_lower_mv(F + (size_t)A.o * ld * ld, ld, n, sy, w, A.ldt);
-}
-
-// ---- stage 1: t = M k_p, mu = mp + t . w per point (k_exp_stage1's shape, one output) -------------------------------------------------
+// ---- stage 1: t = M k_p, mu = mp + t . w per point (whiten_stage1, slab_tiles.hpp; one output) -------------------------------------
 template <int D>
 __global__ __launch_bounds__(kWhitenThreads) void k_joint_stage1(const JointArgs A, int P, const double* __restrict__ As, const double* __restrict__ sq,
                                                                  const double* __restrict__ F, const double* __restrict__ w,
@@ -90,37 +81,20 @@ __global__ __launch_bounds__(kWhitenThreads) void k_joint_stage1(const JointArgs
                                                                  double* __restrict__ mean, double* __restrict__ bs, double* __restrict__ bsq_out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double* sK = reinterpret_cast<double*>(smem);             // [n][P + 1]
-  const int n = A.n, ld = A.ld, tid = threadIdx.x, ldk = P + 1, m = A.m;
-  const int i = blockIdx.x * P + tid % P;
-  const bool on = i < m;
-  const size_t rec = (size_t)(on ? i : 0);
-  double b[D];
-  const double bsq = rbf_scale<D>(A.op, pts + rec * A.d, on, b);
-  if (tid < P && on) {                                  // (tid % P == tid)
-    bsq_out[rec] = bsq;
-#pragma unroll
-    for (int t = 0; t < D; ++t) bs[rec * D + t] = b[t];
-  }
-  whiten_tile<D>(sK, ldk, P, n, A.op.sf2, As, sq, F + (size_t)A.o * ld * ld, ld, b, bsq, on);
-  if (tid < P && on) {
+  const int n = A.n, ld = A.ld, ldk = P + 1;
+  whiten_stage1<D>(sK, P, n, A.op, As, sq, F + (size_t)A.o * ld * ld, ld, pts, A.m, 0, T, A.ldt, bs, bsq_out, [&](size_t rec, long long, int col) {
     double dot = 0.0;
-    for (int j = 0; j < n; ++j) dot = fma(sK[j * ldk + tid], w[j], dot);
+    for (int j = 0; j < n; ++j) dot = fma(sK[j * ldk + col], w[j], dot);
     const double mv = A.op.mp + dot;
     mu[rec] = mv;
     mean[rec] = A.ymean + A.ystd * mv;
-  }
-  const int ldt = A.ldt;
-  for (int e = tid; e < P * ldt; e += kWhitenThreads) {
-    const int pp = e / ldt, j = e - pp * ldt;
-    const int ii = blockIdx.x * P + pp;
-    if (ii < m) T[(size_t)ii * ldt + j] = j < n ? sK[j * ldk + pp] : 0.0;
-  }
+  });
 }
 
 // ---- C = Kpp - T T^T: the tiles of the lower triangle ----------------------------------------------------------------------------------
-// Workgroup b owns tile (ti, tj): rows 64 ti .. + 63 are the A side, columns 64 tj .. + 63 the B side (k_exp_pairs' images and wave
-// layout: acc[a][c][t] of lane l of wave w is (row 32 (w >> 1) + 16 a + 4 t + (l >> 4), column 32 (w & 1) + 16 c + (l & 15))).  Rows
-// past m are staged as zeros and never stored.  Only elements with column <= row are stored, each with its mirror.
+// Workgroup b owns tile (ti, tj): rows 64 ti .. + 63 are the A side of tile64_product, columns 64 tj .. + 63 the B side; acc[a][c][t]
+// is the element (tile64_row(a, t), tile64_col(c)) of the tile (slab_tiles.hpp).  Rows past m are staged as zeros and never stored.
+// Only elements with column <= row are stored, each with its mirror.
 template <int D>
 __global__ __launch_bounds__(kJointThreads, 2) void k_joint_cov(const JointArgs A, const double* __restrict__ T, const double* __restrict__ bs,
                                                                 const double* __restrict__ bsq, double* __restrict__ cov /* [m][m] or null */,
@@ -128,60 +102,26 @@ __global__ __launch_bounds__(kJointThreads, 2) void k_joint_cov(const JointArgs 
   constexpr int LB = D + 1;
   __shared__ __attribute__((aligned(32))) double sA[kJointTile * kSlabK], sB[kJointTile * kSlabK];
   __shared__ double gSq[kJointTile], gB[kJointTile * LB], xSq[kJointTile], xB[kJointTile * LB];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, ws = w >> 1, wt = w & 1;
+  const int tid = threadIdx.x;
   int ti, tj;
   joint_tile((int)blockIdx.x, ti, tj);
   const int i0 = ti * kJointTile, j0 = tj * kJointTile, m = A.m, ldt = A.ldt;
   if (tid < kJointTile) {
     const bool on = i0 + tid < m;
-    const size_t rec = (size_t)(on ? i0 + tid : 0);
-    gSq[tid] = on ? bsq[rec] : 0.0;
-#pragma unroll
-    for (int t = 0; t < D; ++t) gB[tid * LB + t] = on ? bs[rec * D + t] : 0.0;
+    point_image<D>(gSq, gB, tid, bsq, bs, (size_t)(on ? i0 + tid : 0), on);
   } else if (tid < 2 * kJointTile) {
     const int c = tid - kJointTile;
     const bool on = j0 + c < m;
-    const size_t rec = (size_t)(on ? j0 + c : 0);
-    xSq[c] = on ? bsq[rec] : 0.0;
-#pragma unroll
-    for (int t = 0; t < D; ++t) xB[c * LB + t] = on ? bs[rec * D + t] : 0.0;
+    point_image<D>(xSq, xB, c, bsq, bs, (size_t)(on ? j0 + c : 0), on);
   }
-  const int srow = tid >> 2, sk = (tid & 3) * 8;          // staging: this thread's row of the tile and its 8 columns of the slab
-  const int posA = (srow >> 4) * kJointBlk + slab_pos_a(srow, sk), posB = (srow >> 4) * kJointBlk + slab_pos_b(srow, sk);
-  d4_t acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int c = 0; c < 2; ++c) acc[a][c] = d4_t{0.0, 0.0, 0.0, 0.0};
+  const int srow = tile64_stage_row();
   const bool son = i0 + srow < m, ton = j0 + srow < m;
-  const double* Ts = T + (size_t)(son ? i0 + srow : 0) * ldt + sk;
-  const double* Tt = T + (size_t)(ton ? j0 + srow : 0) * ldt + sk;
-  for (int k0 = 0; k0 < ldt; k0 += kSlabK) {
-    d4_t s0, s1, t0, t1;
-    s0 = s1 = t0 = t1 = d4_t{0.0, 0.0, 0.0, 0.0};
-    if (son) {
-      s0 = *reinterpret_cast<const d4_t*>(Ts + k0);
-      s1 = *reinterpret_cast<const d4_t*>(Ts + k0 + 4);
-    }
-    if (ton) {
-      t0 = *reinterpret_cast<const d4_t*>(Tt + k0);
-      t1 = *reinterpret_cast<const d4_t*>(Tt + k0 + 4);
-    }
-    __syncthreads();                                  // (the slab before this one has been read)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      sA[posA + slab_col(e)] = s0[e];
-      sA[posA + slab_col(4 + e)] = s1[e];
-      sB[posB + slab_col(e)] = t0[e];
-      sB[posB + slab_col(4 + e)] = t1[e];
-    }
-    __syncthreads();                                  // (also: the point images above are written; ldt >= kSlabK)
-    slab_mfma(sA + 2 * ws * kJointBlk, kJointBlk, sB + 2 * wt * kJointBlk, kJointBlk, lane, acc);
-  }
+  d4_t acc[2][2];
+  tile64_product(sA, sB, T + (size_t)(son ? i0 + srow : 0) * ldt, son, T + (size_t)(ton ? j0 + srow : 0) * ldt, ton, ldt, acc);
   const double sf2 = A.op.sf2;
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
-    const int col = 32 * wt + 16 * c + (lane & 15), j = j0 + col;
+    const int col = tile64_col(c), j = j0 + col;
     double xb[D];
 #pragma unroll
     for (int t = 0; t < D; ++t) xb[t] = xB[col * LB + t];
@@ -190,7 +130,7 @@ __global__ __launch_bounds__(kJointThreads, 2) void k_joint_cov(const JointArgs 
     for (int a = 0; a < 2; ++a)
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const int row = 32 * ws + 16 * a + 4 * t + (lane >> 4), i = i0 + row;
+        const int row = tile64_row(a, t), i = i0 + row;
         const double gsq = gSq[row];
         // the smaller squared norm first: the value is that of the pair, whichever of the two is the row
         const double cn = rbf_k<D>(sf2, gB + row * LB, fmin(gsq, xsq), xb, fmax(gsq, xsq)) - acc[a][c][t];
@@ -312,73 +252,40 @@ __global__ __launch_bounds__(kJointThreads) void k_joint_panel(const JointArgs A
 }
 
 // ---- Cholesky: A22 -= L21 L21^T, the tiles of the lower triangle behind panel kb ------------------------------------------------------
-// k_joint_cov's images and wave layout; both operands are rows of the panel's 64 columns (two slabs).
+// tile64_product as in k_joint_cov; both operands are rows of the panel's 64 columns (two slabs).
 __global__ __launch_bounds__(kJointThreads, 2) void k_joint_update(const JointArgs A, int kb, double* __restrict__ Aw) {
   __shared__ __attribute__((aligned(32))) double sA[kJointTile * kSlabK], sB[kJointTile * kSlabK];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, ws = w >> 1, wt = w & 1;
   int ti, tj;
   joint_tile((int)blockIdx.x, ti, tj);
   const int base = kb + kJointTile, i0 = base + ti * kJointTile, j0 = base + tj * kJointTile, m = A.m, lda = A.lda;
-  const int srow = tid >> 2, sk = (tid & 3) * 8;
-  const int posA = (srow >> 4) * kJointBlk + slab_pos_a(srow, sk), posB = (srow >> 4) * kJointBlk + slab_pos_b(srow, sk);
-  d4_t acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int c = 0; c < 2; ++c) acc[a][c] = d4_t{0.0, 0.0, 0.0, 0.0};
+  const int srow = tile64_stage_row();
   const bool son = i0 + srow < m, ton = j0 + srow < m;
-  const double* Ls = Aw + (size_t)(son ? i0 + srow : 0) * lda + kb + sk;
-  const double* Lt = Aw + (size_t)(ton ? j0 + srow : 0) * lda + kb + sk;
-  for (int k0 = 0; k0 < kJointTile; k0 += kSlabK) {
-    d4_t s0, s1, t0, t1;
-    s0 = s1 = t0 = t1 = d4_t{0.0, 0.0, 0.0, 0.0};
-    if (son) {
-      s0 = *reinterpret_cast<const d4_t*>(Ls + k0);
-      s1 = *reinterpret_cast<const d4_t*>(Ls + k0 + 4);
-    }
-    if (ton) {
-      t0 = *reinterpret_cast<const d4_t*>(Lt + k0);
-      t1 = *reinterpret_cast<const d4_t*>(Lt + k0 + 4);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      sA[posA + slab_col(e)] = s0[e];
-      sA[posA + slab_col(4 + e)] = s1[e];
-      sB[posB + slab_col(e)] = t0[e];
-      sB[posB + slab_col(4 + e)] = t1[e];
-    }
-    __syncthreads();
-    slab_mfma(sA + 2 * ws * kJointBlk, kJointBlk, sB + 2 * wt * kJointBlk, kJointBlk, lane, acc);
-  }
+  d4_t acc[2][2];
+  tile64_product(sA, sB, Aw + (size_t)(son ? i0 + srow : 0) * lda + kb, son, Aw + (size_t)(ton ? j0 + srow : 0) * lda + kb, ton, kJointTile, acc);
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
-    const int j = j0 + 32 * wt + 16 * c + (lane & 15);
+    const int j = j0 + tile64_col(c);
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const int i = i0 + 32 * ws + 16 * a + 4 * t + (lane >> 4);
+        const int i = i0 + tile64_row(a, t);
         if (i < m && j <= i) Aw[(size_t)i * lda + j] -= acc[a][c][t];
       }
   }
 }
 
 // ---- the draws: F = L Z^T ------------------------------------------------------------------------------------------------------------
-// A workgroup owns kJointDrawTile points x all Spad draws, wave w points 32 w .. + 31 (k_path_main's images and layout); thread t
-// stages columns 16 (t >> 7) .. + 15 of row t & 127 per slab, zeros right of the diagonal (the image's upper triangle is not the
-// factor's).  The slabs from the tile's last row on are skipped.  Zt [lda][Spad]: the caller's z transposed, zeros behind m and S.
+// A workgroup owns kJointDrawTile points x all Spad draws (the tile of slab_tiles.hpp: the points are the rows, the draws the columns);
+// a thread stages columns tile128_k() .. + 15 of row tile128_row() per slab, zeros right of the diagonal (the image's upper triangle is
+// not the factor's).  The slabs from the tile's last row on are skipped.  Zt [lda][Spad]: the caller's z transposed, zeros behind m and S.
 template <int SB>
 __global__ __launch_bounds__(kJointThreads, 2) void k_joint_draw(const JointArgs A, const double* __restrict__ L, const double* __restrict__ Zt,
                                                                  const double* __restrict__ mu, double* __restrict__ draws /* [m][S] or null */,
                                                                  double* __restrict__ pval, long long* __restrict__ pidx /* [grid][Spad] */) {
   constexpr int SP = 16 * SB;
-  __shared__ __attribute__((aligned(32))) double sA[(kJointDrawTile / 16) * kJointBlkA], sB[SB * kJointBlk];
-  __shared__ double rVal[4][SP];
-  __shared__ long long rIdx[4][SP];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, m = A.m;
-  const int gp = tid & (kJointDrawTile - 1), gk = (tid >> 7) * 16;
-  const int posA = (gp >> 4) * kJointBlkA + slab_pos_a(gp, gk);
+  __shared__ __attribute__((aligned(32))) Tile128Lds<SB> lds;
+  const int m = A.m, gp = tile128_row(), gk = tile128_k();
   const int p0 = (int)blockIdx.x * kJointDrawTile, pr = p0 + gp;
   const bool on = pr < m;
   const double* row = L + (size_t)(on ? pr : 0) * A.lda;
@@ -395,72 +302,24 @@ __global__ __launch_bounds__(kJointThreads, 2) void k_joint_draw(const JointArgs
       const int k = k0 + gk + e;
       g[e] = (on && k <= pr) ? row[k] : 0.0;
     }
-    double bv[SB * 2];
-#pragma unroll
-    for (int i = 0; i < SB * 2; ++i) bv[i] = Zt[(size_t)k0 * SP + i * kJointThreads + tid];
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 16; ++e) sA[posA + slab_col(e)] = g[e];
-#pragma unroll
-    for (int i = 0; i < SB * 2; ++i) {
-      const int idx = i * kJointThreads + tid, k = idx / SP, s = idx - k * SP;
-      sB[(s >> 4) * kJointBlk + slab_pos_b(s, k)] = bv[i];
-    }
-    __syncthreads();
-    slab_mfma(sA + 2 * w * kJointBlkA, kJointBlkA, sB, kJointBlk, lane, acc);
+    tile128_step(lds, g, Zt + (size_t)k0 * SP, acc);
   }
-#pragma unroll
-  for (int c = 0; c < SB; ++c) {
-    const int s = 16 * c + (lane & 15);
-    long long bk = kArgNone;
-    double bvv = 0.0;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int p = p0 + 32 * w + 16 * a + 4 * t + (lane >> 4);
-        const bool in = p < m && s < A.S;
-        const double v = A.ymean + (A.ystd * mu[p < m ? p : 0] + acc[a][c][t]);
-        if (draws && in) draws[(size_t)p * A.S + s] = v;
-        arg_take(bvv, bk, A.maximize ? v : -v, (in && v == v) ? (long long)p : kArgNone);      // (a NaN is never taken)
-      }
-#pragma unroll
-    for (int off = 16; off < 64; off <<= 1) {
-      const double ov = __shfl_xor(bvv, off);
-      const long long ok = __shfl_xor(bk, off);
-      arg_take(bvv, bk, ov, ok);
-    }
-    if (lane < 16) {
-      rVal[w][s] = bvv;
-      rIdx[w][s] = bk;
-    }
-  }
-  __syncthreads();
-  if (tid < SP) {
-    long long run_idx = kArgNone;
-    double run_val = 0.0;
-#pragma unroll
-    for (int ww = 0; ww < 4; ++ww) arg_take(run_val, run_idx, rVal[ww][tid], rIdx[ww][tid]);
-    pval[(size_t)blockIdx.x * SP + tid] = run_val;
-    pidx[(size_t)blockIdx.x * SP + tid] = run_idx;
-  }
+  long long run_idx = kArgNone;
+  double run_val = 0.0;
+  tile128_arg_best(lds, acc, p0, m, A.S, A.maximize, draws, [&](long long p, double x) { return A.ymean + (A.ystd * mu[p < m ? p : 0] + x); }, run_val,
+                   run_idx);
+  tile128_store_partial<SB>(pval, pidx, run_val, run_idx);
 }
 
-// ---- the partials in workgroup order and the pivot record -> the result block ----------------------------------------------------------
-__global__ __launch_bounds__(SBO_MAX_PATHS) void k_joint_finish(const JointArgs A, int nwg, const double* __restrict__ pval,
+// ---- the partials of the workgroups and the pivot record -> the result block -----------------------------------------------------------
+__global__ __launch_bounds__(kMergeThreads) void k_joint_finish(const JointArgs A, int nwg, const double* __restrict__ pval,
                                                                 const long long* __restrict__ pidx, const JointState* __restrict__ st,
                                                                 sbo_joint_result* __restrict__ res) {
-  const int s = threadIdx.x;
-  long long bk = kArgNone;
-  double bv = 0.0;
-  if (s < A.S)
-    for (int g = 0; g < nwg; ++g) arg_take(bv, bk, pval[(size_t)g * A.Spad + s], pidx[(size_t)g * A.Spad + s]);
-  res->index[s] = bk == kArgNone ? -1 : bk;
-  res->value[s] = bk == kArgNone ? __builtin_nan("") : (A.maximize ? bv : -bv);
-  if (s == 0) {
+  if (threadIdx.x == 0) {
     res->pivot_min = st->prow < 0 ? __builtin_nan("") : st->pmin;
     res->pivot_row = st->prow;
   }
+  partials_merge(A.S, A.Spad, A.maximize, nwg, pval, pidx, res->index, res->value);
 }
 
 // ---- the factor in full: zeros above the diagonal ------------------------------------------------------------------------------------
@@ -472,25 +331,15 @@ __global__ __launch_bounds__(kJointThreads) void k_joint_lower(const JointArgs A
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-template <int SB>
-static void joint_launch_draw(hipStream_t st, const JointArgs& A, const JointBufs& B, int nwg) {
-  hipLaunchKernelGGL((k_joint_draw<SB>), dim3((unsigned)nwg), dim3(kJointThreads), 0, st, A, (const double*)B.A, (const double*)B.Zt,
-                     (const double*)B.mu, B.draws, B.pval, B.pidx);
-}
-
 template <int D>
 static int joint_enqueue(sbo_ctx* c, const JointArgs& A, const JointBufs& B, bool want_cov, bool factorise, bool want_chol, int nwg) {
   hipStream_t st = c->stream;
   const int n = A.n, m = A.m;
-  SBO_HIP(obs_prep<D>(st, n, &A.op, 1, B.Xn, B.As, B.sq));
-  hipLaunchKernelGGL(k_joint_w, dim3(1), dim3(kFactorMvThreads), 0, st, A, (const double*)B.Yn, c->factor.F(), B.w);
-  SBO_HIP(hipGetLastError());
-  const int P = whiten_tier(n);
-  const size_t lds = sizeof(double) * (size_t)n * (P + 1);
-  if (lds > kJointS1Lds) return fail(SBO_E_UNSUPPORTED, "sbo_posterior_joint: the model is too large");      // (n <= SBO_MAX_N: never)
-  SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_joint_stage1<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kJointS1Lds));
-  hipLaunchKernelGGL((k_joint_stage1<D>), dim3((unsigned)((m + P - 1) / P)), dim3(kWhitenThreads), lds, st, A, P, (const double*)B.As,
-                     (const double*)B.sq, c->factor.F(), (const double*)B.w, (const double*)B.pts, B.T, B.mu, B.mean, B.bs, B.bsq);
+  if (int rc = B.obs.prepare<D>(c, st, &A.op, &A.o, 1, A.ldt)) return rc;
+  Stage1Launch S1;
+  if (int rc = whiten_stage1_launch(k_joint_stage1<D>, "sbo_posterior_joint", n, m, S1)) return rc;
+  hipLaunchKernelGGL((k_joint_stage1<D>), dim3(S1.blocks), dim3(kWhitenThreads), S1.lds, st, A, S1.P, (const double*)B.obs.As, (const double*)B.obs.sq,
+                     c->factor.F(), (const double*)B.obs.w, (const double*)B.pts, B.T, B.mu, B.mean, B.bs, B.bsq);
   SBO_HIP(hipGetLastError());
   const int nt = (m + kJointTile - 1) / kJointTile;          // tiles of 64 rows that hold a point
   if (want_cov || factorise) {
@@ -510,14 +359,13 @@ static int joint_enqueue(sbo_ctx* c, const JointArgs& A, const JointBufs& B, boo
     SBO_HIP(hipGetLastError());
   }
   if (A.S > 0) {
-    switch (A.Spad) {                               // S = 1 does not pay for 64 draws
-      case 16: joint_launch_draw<1>(st, A, B, nwg); break;
-      case 32: joint_launch_draw<2>(st, A, B, nwg); break;
-      default: joint_launch_draw<4>(st, A, B, nwg); break;
-    }
+    with_spad(A.Spad, [&](auto SB) {
+      hipLaunchKernelGGL((k_joint_draw<SB()>), dim3((unsigned)nwg), dim3(kJointThreads), 0, st, A, (const double*)B.A, (const double*)B.Zt,
+                         (const double*)B.mu, B.draws, B.pval, B.pidx);
+    });
     SBO_HIP(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_joint_finish, dim3(1), dim3(SBO_MAX_PATHS), 0, st, A, A.S > 0 ? nwg : 0, (const double*)B.pval, (const long long*)B.pidx,
+  hipLaunchKernelGGL(k_joint_finish, dim3(1), dim3(kMergeThreads), 0, st, A, A.S > 0 ? nwg : 0, (const double*)B.pval, (const long long*)B.pidx,
                      (const JointState*)B.st, B.res);
   SBO_HIP(hipGetLastError());
   if (want_chol) {
@@ -530,10 +378,7 @@ static int joint_enqueue(sbo_ctx* c, const JointArgs& A, const JointBufs& B, boo
 
 static void joint_clear(sbo_joint_result* r) {
   if (!r) return;
-  for (int s = 0; s < SBO_MAX_PATHS; ++s) {
-    r->index[s] = -1;
-    r->value[s] = std::numeric_limits<double>::quiet_NaN();
-  }
+  clear_index_value(r->index, r->value);
   r->pivot_min = std::numeric_limits<double>::quiet_NaN();
   r->pivot_row = -1;
 }
@@ -573,7 +418,7 @@ extern "C" int sbo_posterior_joint(sbo_ctx* c, const sbo_joint_opts* opts, int64
   A.ldt = (n + kSlabK - 1) / kSlabK * kSlabK;
   A.o = o;
   A.S = S;
-  A.Spad = S <= 16 ? 16 : S <= 32 ? 32 : 64;
+  A.Spad = spad_of(S);
   A.m = m;
   A.lda = (m + kJointDrawTile - 1) / kJointDrawTile * kJointDrawTile;
   A.maximize = opts->maximize;
@@ -592,11 +437,7 @@ extern "C" int sbo_posterior_joint(sbo_ctx* c, const sbo_joint_opts* opts, int64
   const size_t lda = (size_t)A.lda, Sp = (size_t)A.Spad, mm = (size_t)m;
   JointBufs B;
   auto layout = [&](Carve cv) {
-    cv.take(B.Xn, (size_t)n * d);
-    cv.take(B.Yn, (size_t)n * q);
-    cv.take(B.As, (size_t)n * D);
-    cv.take(B.sq, (size_t)n);
-    cv.take(B.w, (size_t)A.ldt);
+    B.obs.take(cv, mc, 1, A.ldt);
     cv.take(B.pts, mm * d);
     cv.take(B.T, mm * A.ldt);
     cv.take(B.mu, mm);
@@ -632,8 +473,7 @@ extern "C" int sbo_posterior_joint(sbo_ctx* c, const sbo_joint_opts* opts, int64
   sbo_joint_result out = cleared;
   hipError_t e = hipMemcpyAsync(B.st, &init, sizeof(init), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(B.res, &cleared, sizeof(cleared), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(B.Xn, c->h_Xnorm.data(), sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(B.Yn, c->h_Ynorm.data(), sizeof(double) * (size_t)n * q, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = B.obs.upload(c, st);
   if (e == hipSuccess) e = hipMemcpyAsync(B.pts, points, sizeof(double) * mm * d, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && S > 0) e = hipMemcpyAsync(B.Zt, zt.data(), sizeof(double) * lda * Sp, hipMemcpyHostToDevice, st);
   rc = e == hipSuccess ? with_dpad(D, [&](auto DD) { return joint_enqueue<DD()>(c, A, B, want_cov, factorise, want_chol, nwg); }) : SBO_OK;

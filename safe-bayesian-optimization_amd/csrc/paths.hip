@@ -5,18 +5,18 @@
 //   c_s = M^T (M r_s),   r_s[j] = (y_j - mp) - prior_s(X_j) - sqrt(sn2) noise[s][j]   (M^T M = inv(K + sn2 I), the resident fp64 factor)
 // which is ONE matrix product per point tile: the A operand [point][F + n] is generated on the fly (cos features, then RBF columns),
 // the B operand [F + n][S] (scaled weights, then c) is small and lives in L2.
-//   k_obs_prep     (whiten.hpp) the observations in the output's scaled coordinates and their squares
+//   k_obs_prep     (through ObsResident, slab_tiles.hpp) the observations in the output's scaled coordinates and their squares
 //   k_path_bw      the feature rows of B
 //   k_path_main    the hot path on the matrix cores: a workgroup owns kPathTile points x all Spad paths, wave w points 32 w .. + 31 as
 //                  2 x Spad / 16 accumulators of MM<double> (v_mfma_f64_4x4x4, four per step).  The K axis is the F features rounded up
-//                  to a slab, then the n observations rounded up to a slab; per slab of kPathKSlab columns every thread generates 16
-//                  elements of the A image (a column's value at a point is computed once and used by every path) and the [32][Spad]
-//                  slab of B is staged beside it.  Epilogue: un-normalise, store [m][S] where asked, a running arg-best per path.  A
-//                  bounded grid walks the tiles; one partial per (workgroup, path).
+//                  to a slab, then the n observations rounded up to a slab; per slab of kSlabK columns every thread generates 16
+//                  elements of the A image (a column's value at a point is computed once and used by every path) and tile128_step
+//                  (slab_tiles.hpp) stages the [32][Spad] slab of B beside it.  Epilogue (tile128_arg_best): un-normalise, store [m][S]
+//                  where asked, a running arg-best per path.  A bounded grid walks the tiles; one partial per (workgroup, path).
 //                  The prior at the data is THIS kernel with the observations as the points and no observation slabs: no second
 //                  feature evaluator exists that could round differently.
 //   k_path_solve   per path: r, w = M r (factor_lower_mv, whiten.hpp), c = M^T w (factor_upper_mv) into the observation rows of B
-//   k_path_finish  the partials in workgroup order -> the result block
+//   k_path_finish  the partials of the workgroups -> the result block (partials_merge, slab_tiles.hpp)
 // Every sum over features and observations runs in an order fixed by (F, n) alone, (value, index) reductions are arg_take's total
 // order, there are no atomics: the value of (point, path) does not depend on m, on the point's place or on the other paths, and two
 // calls return the same bits.  One read-back, one host wait; nothing resident is written.
@@ -24,31 +24,28 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
-#include "whiten.hpp"
+#include "slab_tiles.hpp"
 
 namespace sbo {
 
 constexpr int kPathTile = 128;                   // points of one workgroup tile of k_path_main (4 waves x 32 points)
 constexpr int kPathThreads = 256;                // k_path_main
-constexpr int kPathKSlab = 32;                   // columns of the K axis (features, then observations) of one LDS slab
 constexpr int kPathGridTiles = 1024;             // workgroups k_path_main aims at: min(point tiles, kPathGridTiles); each walks its tiles
-constexpr int kPathFinishThreads = 1024;         // k_path_finish: SBO_MAX_PATHS paths x 16 parts of the workgroups
-constexpr int kPathBlk = 16 * kPathKSlab;        // doubles of one 16-row block of a slab image
-constexpr int kPathBlkA = kPathBlk + 16;         // ... and the distance between two blocks of the A image (the four blocks a wave writes at once land in two bank halves)
-static_assert(kPathTile == 128 && kPathThreads == 256 && kPathKSlab == 32 && kPathKSlab == kSlabK, "k_path_main: 4 waves of 32 points, a thread generates 16 columns of one point per slab");
+static_assert(kPathTile == kTile128 && kPathThreads == kTileThreads, "k_path_main: tile128_step's tile and workgroup");
 static_assert(SBO_MAX_PATHS == 64, "k_path_main is instantiated for 16, 32 and 64 padded paths");
 
 struct PathArgs {                                // by value (kernarg segment)
   int n, d, ld, q;                               // observations, input dimension, leading dimension of the resident factor, outputs
   int F, S, Spad, o;                             // features, paths, paths rounded up to 16 | 32 | 64, the output
-  int KF, KN, maximize, pad;                     // F and n rounded up to kPathKSlab (KN = 0: no observation part)
+  int KF, KN, maximize, pad;                     // F and n rounded up to kSlabK (KN = 0: no observation part)
   long long m;                                   // points
   OutParams op;                                  // the output
   double ymean, ystd, fscale;                    // fscale = sqrt(2 sf2 / F)
 };
 
 struct PathBufs {
-  double *Xn, *Yn, *As, *sq, *om, *ph, *wt, *nz, *B, *prior, *pts, *vals, *pval;
+  ObsResident obs;                               // (without w)
+  double *om, *ph, *wt, *nz, *B, *prior, *pts, *vals, *pval;
   long long* pidx;
   sbo_paths_result* res;
 };
@@ -62,10 +59,9 @@ __global__ __launch_bounds__(256) void k_path_bw(const PathArgs A, const double*
 }
 
 // ---- the hot path -------------------------------------------------------------------------------------------------------------------
-// Thread t generates, per slab, columns 16 (t >> 7) .. + 15 of point t & 127 of the tile (the column is wave-uniform: its omega row or
-// observation is read once per wave).  LDS images of a slab (whiten.hpp): the points are the A side, the paths the B side.  acc[a][c][t]
-// of lane l of wave w is (point 32 w + 16 a + 4 t + (l >> 4), path 16 c + (l & 15)), the D layout of the 4x4x4 form
-// (device_common.hpp).  Points past m generate zeros and are never stored or taken.
+// Thread t generates, per slab, columns tile128_k() .. + 15 of point tile128_row() of the tile (the column is wave-uniform: its omega
+// row or observation is read once per wave).  The tile of slab_tiles.hpp: the points are the rows, the paths the columns.  Points past
+// m generate zeros and are never stored or taken.
 // `pts` holds rows of d coordinates x with u = ((x - X_mean) / X_std) vinv: the raw points, or -- with X_mean = 0, X_std = 1, both exact
 // -- the normalised observations.  The value is ymean + ystd (mp + sum): the caller's units, or -- with 0, 1, 0, all exact -- the sum.
 template <int D, int SB>
@@ -75,12 +71,8 @@ __global__ __launch_bounds__(kPathThreads, 2) void k_path_main(const PathArgs A,
                                                               const double* __restrict__ B /* [KF + KN][Spad] */, double* __restrict__ vals /* [m][S] or null */,
                                                               double* __restrict__ pval, long long* __restrict__ pidx /* [grid][Spad] or null */) {
   constexpr int SP = 16 * SB;
-  __shared__ __attribute__((aligned(32))) double sA[(kPathTile / 16) * kPathBlkA], sB[SB * kPathBlk];
-  __shared__ double rVal[4][SP];
-  __shared__ long long rIdx[4][SP];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int gp = tid & (kPathTile - 1), gk = (tid >> 7) * 16;       // generation: this thread's point of the tile and its first column of the slab
-  const int posA = (gp >> 4) * kPathBlkA + slab_pos_a(gp, gk);      // column gk + e, e = 0 .. 15: slab_col(e) behind it
+  __shared__ __attribute__((aligned(32))) Tile128Lds<SB> lds;
+  const int gp = tile128_row(), gk = tile128_k();     // generation: this thread's point of the tile and its first column of the slab
   const int n = A.n, F = A.F;
   long long run_idx = kArgNone;                   // threads 0 .. SP - 1: path tid over this workgroup's tiles
   double run_val = 0.0;
@@ -94,7 +86,7 @@ __global__ __launch_bounds__(kPathThreads, 2) void k_path_main(const PathArgs A,
     for (int a = 0; a < 2; ++a)
 #pragma unroll
       for (int c = 0; c < SB; ++c) acc[a][c] = d4_t{0.0, 0.0, 0.0, 0.0};
-    for (int k0 = 0; k0 < A.KF + A.KN; k0 += kPathKSlab) {
+    for (int k0 = 0; k0 < A.KF + A.KN; k0 += kSlabK) {
       double g[16];
       if (k0 < A.KF) {                              // features: cos(omega_f . u + phase_f)
         const int f0 = __builtin_amdgcn_readfirstlane(k0 + gk);
@@ -116,57 +108,12 @@ __global__ __launch_bounds__(kPathThreads, 2) void k_path_main(const PathArgs A,
           g[e] = (on && j < n) ? kv : 0.0;
         }
       }
-      double bv[SB * 2];                            // the slab of B: [32][Spad] row-major = 32 SP consecutive doubles
-#pragma unroll
-      for (int i = 0; i < SB * 2; ++i) bv[i] = B[(size_t)k0 * SP + i * kPathThreads + tid];
-      __syncthreads();                              // (the slab before this one has been read)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) sA[posA + slab_col(e)] = g[e];
-#pragma unroll
-      for (int i = 0; i < SB * 2; ++i) {
-        const int idx = i * kPathThreads + tid, k = idx / SP, s = idx - k * SP;
-        sB[(s >> 4) * kPathBlk + slab_pos_b(s, k)] = bv[i];
-      }
-      __syncthreads();
-      slab_mfma(sA + 2 * w * kPathBlkA, kPathBlkA, sB, kPathBlk, lane, acc);
+      tile128_step(lds, g, B + (size_t)k0 * SP, acc);
     }
     // epilogue: the values in the caller's units, and per path the arg-best over this tile's points
-#pragma unroll
-    for (int c = 0; c < SB; ++c) {
-      const int s = 16 * c + (lane & 15);
-      long long bk = kArgNone;
-      double bvv = 0.0;
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const long long p = p0 + 32 * w + 16 * a + 4 * t + (lane >> 4);
-          const double v = A.ymean + A.ystd * (A.op.mp + acc[a][c][t]);
-          const bool in = p < A.m && s < A.S;
-          if (vals && in) vals[(size_t)p * A.S + s] = v;
-          arg_take(bvv, bk, A.maximize ? v : -v, (in && v == v) ? p : kArgNone);      // (a NaN is never taken)
-        }
-#pragma unroll
-      for (int off = 16; off < 64; off <<= 1) {
-        const double ov = __shfl_xor(bvv, off);
-        const long long ok = __shfl_xor(bk, off);
-        arg_take(bvv, bk, ov, ok);
-      }
-      if (lane < 16) {
-        rVal[w][s] = bvv;
-        rIdx[w][s] = bk;
-      }
-    }
-    __syncthreads();
-    if (tid < SP)
-#pragma unroll
-      for (int ww = 0; ww < 4; ++ww) arg_take(run_val, run_idx, rVal[ww][tid], rIdx[ww][tid]);
-    // (the next tile's first barrier stands between these reads and its epilogue's writes)
+    tile128_arg_best(lds, acc, p0, A.m, A.S, A.maximize, vals, [&](long long, double x) { return A.ymean + A.ystd * (A.op.mp + x); }, run_val, run_idx);
   }
-  if (pidx && tid < SP) {
-    pval[(size_t)blockIdx.x * SP + tid] = run_val;
-    pidx[(size_t)blockIdx.x * SP + tid] = run_idx;
-  }
+  tile128_store_partial<SB>(pval, pidx, run_val, run_idx);
 }
 
 // ---- per path: the residual, w = M r, c = M^T w -> B [KF + j][s] --------------------------------------------------------------------
@@ -185,34 +132,18 @@ __global__ __launch_bounds__(1024) void k_path_solve(const PathArgs A, const dou
   factor_upper_mv(M, ld, n, sw, [&](int j, double t) { B[(size_t)(A.KF + j) * A.Spad + s] = t; });
 }
 
-// ---- per path: the workgroups in order -> the result block --------------------------------------------------------------------------
-// One workgroup: thread (s, part) = (tid & 63, tid >> 6) takes workgroups part, part + 16, .. of path s, then thread s the 16 parts in
-// order (arg_take's order is total: the winner is that of the workgroups taken one by one).
-__global__ __launch_bounds__(kPathFinishThreads) void k_path_finish(const PathArgs A, int nwg, const double* __restrict__ pval,
-                                                                    const long long* __restrict__ pidx, sbo_paths_result* __restrict__ res) {
-  constexpr int kParts = kPathFinishThreads / SBO_MAX_PATHS;
-  __shared__ double sv[kParts][SBO_MAX_PATHS];
-  __shared__ long long sk[kParts][SBO_MAX_PATHS];
-  const int s = threadIdx.x & (SBO_MAX_PATHS - 1), part = threadIdx.x / SBO_MAX_PATHS;
-  long long bk = kArgNone;
-  double bv = 0.0;
-  if (s < A.S)
-    for (int g = part; g < nwg; g += kParts) arg_take(bv, bk, pval[(size_t)g * A.Spad + s], pidx[(size_t)g * A.Spad + s]);
-  sv[part][s] = bv;
-  sk[part][s] = bk;
-  __syncthreads();
-  if (part) return;
-  for (int p = 1; p < kParts; ++p) arg_take(bv, bk, sv[p][s], sk[p][s]);
-  res->index[s] = bk == kArgNone ? -1 : bk;
-  res->value[s] = bk == kArgNone ? __builtin_nan("") : (A.maximize ? bv : -bv);
+// ---- per path: the workgroups' partials -> the result block ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kMergeThreads) void k_path_finish(const PathArgs A, int nwg, const double* __restrict__ pval,
+                                                               const long long* __restrict__ pidx, sbo_paths_result* __restrict__ res) {
+  partials_merge(A.S, A.Spad, A.maximize, nwg, pval, pidx, res->index, res->value);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
 template <int D, int SB>
-static int paths_enqueue_sb(sbo_ctx* c, const PathArgs& A, const PathBufs& Bf, int nwg, long long ntiles) {
+static int paths_enqueue(sbo_ctx* c, const PathArgs& A, const PathBufs& Bf, int nwg, long long ntiles) {
   hipStream_t st = c->stream;
   const int n = A.n;
-  SBO_HIP(obs_prep<D>(st, n, &A.op, 1, Bf.Xn, Bf.As, Bf.sq));
+  if (int rc = Bf.obs.prepare<D>(c, st, &A.op, &A.o, 1, 0)) return rc;
   hipLaunchKernelGGL(k_path_bw, dim3((unsigned)(((long long)A.F * A.S + 255) / 256)), dim3(256), 0, st, A, (const double*)Bf.wt, Bf.B);
   SBO_HIP(hipGetLastError());
   // the prior at the data: the observations as the points (already normalised: X_mean = 0, X_std = 1), no observation part, the bare sum
@@ -227,36 +158,19 @@ static int paths_enqueue_sb(sbo_ctx* c, const PathArgs& A, const PathBufs& Bf, i
     P.op.X_std[a] = 1.0;
   }
   const long long ptiles = ((long long)n + kPathTile - 1) / kPathTile;
-  hipLaunchKernelGGL((k_path_main<D, SB>), dim3((unsigned)ptiles), dim3(kPathThreads), 0, st, P, ptiles, (const double*)Bf.Xn, (const double*)Bf.om,
-                     (const double*)Bf.ph, (const double*)Bf.As, (const double*)Bf.sq, (const double*)Bf.B, Bf.prior, (double*)nullptr,
+  hipLaunchKernelGGL((k_path_main<D, SB>), dim3((unsigned)ptiles), dim3(kPathThreads), 0, st, P, ptiles, (const double*)Bf.obs.Xn, (const double*)Bf.om,
+                     (const double*)Bf.ph, (const double*)Bf.obs.As, (const double*)Bf.obs.sq, (const double*)Bf.B, Bf.prior, (double*)nullptr,
                      (long long*)nullptr);
   SBO_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_path_solve, dim3((unsigned)A.S), dim3(1024), 0, st, A, (const double*)Bf.Yn, (const double*)Bf.prior, (const double*)Bf.nz,
+  hipLaunchKernelGGL(k_path_solve, dim3((unsigned)A.S), dim3(1024), 0, st, A, (const double*)Bf.obs.Yn, (const double*)Bf.prior, (const double*)Bf.nz,
                      c->factor.F(), Bf.B);
   SBO_HIP(hipGetLastError());
   hipLaunchKernelGGL((k_path_main<D, SB>), dim3((unsigned)nwg), dim3(kPathThreads), 0, st, A, ntiles, (const double*)Bf.pts, (const double*)Bf.om,
-                     (const double*)Bf.ph, (const double*)Bf.As, (const double*)Bf.sq, (const double*)Bf.B, Bf.vals, Bf.pval, Bf.pidx);
+                     (const double*)Bf.ph, (const double*)Bf.obs.As, (const double*)Bf.obs.sq, (const double*)Bf.B, Bf.vals, Bf.pval, Bf.pidx);
   SBO_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_path_finish, dim3(1), dim3(kPathFinishThreads), 0, st, A, nwg, (const double*)Bf.pval, (const long long*)Bf.pidx, Bf.res);
+  hipLaunchKernelGGL(k_path_finish, dim3(1), dim3(kMergeThreads), 0, st, A, nwg, (const double*)Bf.pval, (const long long*)Bf.pidx, Bf.res);
   SBO_HIP(hipGetLastError());
   return SBO_OK;
-}
-
-template <int D>
-static int paths_enqueue(sbo_ctx* c, const PathArgs& A, const PathBufs& Bf, int nwg, long long ntiles) {
-  switch (A.Spad) {                                // S = 1 does not pay for 64 paths
-    case 16: return paths_enqueue_sb<D, 1>(c, A, Bf, nwg, ntiles);
-    case 32: return paths_enqueue_sb<D, 2>(c, A, Bf, nwg, ntiles);
-    default: return paths_enqueue_sb<D, 4>(c, A, Bf, nwg, ntiles);
-  }
-}
-
-static void paths_clear(sbo_paths_result* r) {
-  if (!r) return;
-  for (int s = 0; s < SBO_MAX_PATHS; ++s) {
-    r->index[s] = -1;
-    r->value[s] = std::numeric_limits<double>::quiet_NaN();
-  }
 }
 
 }  // namespace sbo
@@ -265,7 +179,7 @@ using namespace sbo;
 
 extern "C" int sbo_sample_paths(sbo_ctx* c, const sbo_paths_opts* opts, const double* omega, const double* phase, const double* weights,
                                 const double* noise, int64_t m, const double* points, double* values_out, sbo_paths_result* result) {
-  paths_clear(result);
+  if (result) clear_index_value(result->index, result->value);
   if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
   if (!opts || !omega || !phase || !weights || !noise || !points || !result) return fail(SBO_E_INVALID, "NULL argument");
   if (m < 1 || m > SBO_PATHS_MAX_POINTS) return fail(SBO_E_INVALID, "1 <= m <= SBO_PATHS_MAX_POINTS is required");
@@ -290,10 +204,10 @@ extern "C" int sbo_sample_paths(sbo_ctx* c, const sbo_paths_opts* opts, const do
   A.ld = c->factor.ld();
   A.F = F;
   A.S = S;
-  A.Spad = S <= 16 ? 16 : S <= 32 ? 32 : 64;
+  A.Spad = spad_of(S);
   A.o = o;
-  A.KF = (F + kPathKSlab - 1) / kPathKSlab * kPathKSlab;
-  A.KN = (n + kPathKSlab - 1) / kPathKSlab * kPathKSlab;
+  A.KF = (F + kSlabK - 1) / kSlabK * kSlabK;
+  A.KN = (n + kSlabK - 1) / kSlabK * kSlabK;
   A.maximize = opts->maximize;
   A.m = m;
   A.op = out_params(mc, o);
@@ -309,10 +223,7 @@ extern "C" int sbo_sample_paths(sbo_ctx* c, const sbo_paths_opts* opts, const do
   const size_t KF = (size_t)A.KF, Sp = (size_t)A.Spad;
   PathBufs Bf;
   auto layout = [&](Carve cv) {
-    cv.take(Bf.Xn, (size_t)n * d);
-    cv.take(Bf.Yn, (size_t)n * q);
-    cv.take(Bf.As, (size_t)n * D);
-    cv.take(Bf.sq, (size_t)n);
+    Bf.obs.take(cv, mc, 1, 0);
     cv.take(Bf.om, KF * D);
     cv.take(Bf.ph, KF);
     cv.take(Bf.wt, (size_t)S * F);
@@ -339,10 +250,10 @@ extern "C" int sbo_sample_paths(sbo_ctx* c, const sbo_paths_opts* opts, const do
   if (e == hipSuccess) e = hipMemcpyAsync(Bf.ph, phase, sizeof(double) * (size_t)F, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(Bf.wt, weights, sizeof(double) * (size_t)S * F, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(Bf.nz, noise, sizeof(double) * (size_t)S * n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(Bf.Xn, c->h_Xnorm.data(), sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(Bf.Yn, c->h_Ynorm.data(), sizeof(double) * (size_t)n * q, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = Bf.obs.upload(c, st);
   if (e == hipSuccess) e = hipMemcpyAsync(Bf.pts, points, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice, st);
-  rc = e == hipSuccess ? with_dpad(D, [&](auto DD) { return paths_enqueue<DD()>(c, A, Bf, nwg, ntiles); }) : SBO_OK;
+  auto enqueue = [&](auto DD) { return with_spad(A.Spad, [&](auto SB) { return paths_enqueue<DD(), SB()>(c, A, Bf, nwg, ntiles); }); };
+  rc = e == hipSuccess ? with_dpad(D, enqueue) : SBO_OK;
   if (e != hipSuccess || rc) {
     (void)hipStreamSynchronize(st);                     // (nothing of the call may still read the caller's arrays or `omp`)
     SBO_HIP(e);

@@ -6,7 +6,8 @@
 //   k_obs_prep                 the observations in the scaled coordinates of gridDim.y slots
 //   whiten_tile                t = M k_x for P points of a workgroup, in an LDS image
 //   factor_lower_mv / _upper_mv   M x and M^T t by one workgroup
-//   slab_pos_a / _b, slab_mfma the LDS images of a K-slab of MM<double> operands and the multiply step over one
+// What only the three calls with a matrix-core stage share -- the residual kernel, the stage-1 body, their resident observations and the
+// tile steps on the whitened vectors -- is in slab_tiles.hpp.
 // k_model_append (model.hip) sums with s += a * b, not fma, and guard.hip, lipschitz.hip, refine.hip and sets_recheck.inc.hpp keep the
 // data in other layouts: they share the kernel expression, not these sequences, and have pins of their own.
 #pragma once
@@ -18,7 +19,6 @@ namespace sbo {
 constexpr int kWhitenThreads = 1024;             // whiten_tile: P points x 1024 / P row lanes
 constexpr int kWhitenRows = 4;                   // ... rows of M per row lane and step
 constexpr int kFactorMvThreads = 1024;           // factor_lower_mv / factor_upper_mv: the workgroup they are written for
-constexpr int kSlabK = 32;                       // columns of the K axis of one LDS slab (slab_pos_a / _b, slab_mfma)
 
 // points per workgroup of whiten_tile: the image [n][P (+ 1)] stays within 128 (144) KiB up to SBO_MAX_N
 inline int whiten_tier(int n) { return n <= 512 ? 32 : n <= 1024 ? 16 : 8; }
@@ -160,32 +160,6 @@ __device__ __forceinline__ void factor_upper_mv(const double* M, int ld, int n, 
 #pragma unroll 8
     for (int i = j; i < n; ++i) s = fma(M[(size_t)i * ld + j], t[i], s);
     out(j, s);
-  }
-}
-
-// ---- a K-slab of MM<double> operands in LDS ----------------------------------------------------------------------------------------
-// Per block of 16 rows (points, or paths) and k-step of 4 columns: the A side in MM<double>'s packed order (a lane's four row groups
-// contiguous: one 32-byte read), the B side as [k-slot][row] (lane l reads element l).  Where column k of row r goes inside its block's
-// image -- on the A side MM<double>::pack_pos(r & 15, k & 3, k >> 2) --, and how far column k + e, e < 16, lies behind a k that is a
-// multiple of 4.
-__device__ __forceinline__ int slab_pos_a(int r, int k) { return (k >> 2) * 64 + (k & 3) * 16 + (r & 3) * 4 + ((r & 15) >> 2); }
-__device__ __forceinline__ int slab_pos_b(int r, int k) { return (k >> 2) * 64 + (k & 3) * 16 + (r & 15); }
-__device__ __forceinline__ constexpr int slab_col(int e) { return (e >> 2) * 64 + (e & 3) * 16; }
-// acc[a][c] += (block a of sA) x (block c of sB) over the slab; strideA / strideB: doubles between two blocks of an image
-template <int NA, int NB>
-__device__ __forceinline__ void slab_mfma(const double* sA, int strideA, const double* sB, int strideB, int lane, d4_t (&acc)[NA][NB]) {
-#pragma unroll
-  for (int kk = 0; kk < kSlabK / 4; ++kk) {
-    d4_t fa[NA];
-    double fb[NB];
-#pragma unroll
-    for (int a = 0; a < NA; ++a) fa[a] = MM<double>::load_a(sA + a * strideA, lane, kk);
-#pragma unroll
-    for (int c = 0; c < NB; ++c) fb[c] = sB[c * strideB + kk * 64 + lane];
-#pragma unroll
-    for (int a = 0; a < NA; ++a)
-#pragma unroll
-      for (int c = 0; c < NB; ++c) acc[a][c] = MM<double>::mfma(fa[a], fb[c], acc[a][c]);
   }
 }
 

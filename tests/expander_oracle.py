@@ -101,9 +101,10 @@ def sharpness(res):
 
 
 # ---- the committed cases of tests/test_gpu_expander_gain.py -------------------------------------------------------------------------
-# (n, ms, mt, d, q, mask, b, use_invK, seed), each edge once, not the product.  By the constants of csrc/expander.hip
+# (n, ms, mt, d, q, mask, b, use_invK, seed), each edge once, not the product.  By the constants of csrc/expander.hip and
+# csrc/slab_tiles.hpp (kSlabK, stage 1)
 # (tests/test_expander_gain_cpu.py reads them from the source and holds this list to them):
-#   k_exp_pairs    tiles of kExpTile = 64 sources x 64 targets: ms, mt in {1, 63, 64, 65, 257}; LDS slabs of kExpKSlab = 32 observations,
+#   k_exp_pairs    tiles of kExpTile = 64 sources x 64 targets: ms, mt in {1, 63, 64, 65, 257}; LDS slabs of kSlabK = 32 observations,
 #                  t rows zero-padded to a multiple: n = 32 | 33 and 64 | 65 (a last slab that is full | holds one observation), n = 1, 2;
 #                  the target tiles are split over min(tiles, kExpGridTiles / source tiles) workgroups per source tile: every case with
 #                  mt > 64 gives each source a second split, ms = 1 with mt = 257 five of them; ms = 257 (5 source tiles, 204 splits)

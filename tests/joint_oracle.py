@@ -71,7 +71,7 @@ ROUTES = (joint_solve, joint_invK, joint_white)
 
 # ---- the committed cases of tests/test_gpu_posterior_joint.py ------------------------------------------------------------------------
 # (n, m, S, d, q, output, maximize, noise, jitter, use_invK, seed), each edge once, not the product.  By the constants of
-# csrc/joint.hip (tests/test_posterior_joint_cpu.py reads them from the source and holds this list to them):
+# csrc/joint.hip and csrc/slab_tiles.hpp (kSlabK) (tests/test_posterior_joint_cpu.py reads them from the source and holds this list to them):
 #   k_joint_cov / _diag / _panel / _update   tiles and panels of kJointTile = 64: m in {1, 2, 63, 64, 65, 129, 257, 513} and the cap
 #                  SBO_JOINT_MAX_POINTS = 2048 (with n = 64); the K axis of the covariance in slabs of kSlabK = 32 over n: n in {1, 31,
 #                  32, 33, 300, 1025} and SBO_MAX_N = 2048 (with m = 65);

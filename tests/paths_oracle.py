@@ -79,10 +79,11 @@ def sharpness(values, maximize):
 
 
 # ---- the committed cases of tests/test_gpu_sample_paths.py ---------------------------------------------------------------------------
-# (n, m, F, S, d, q, output, maximize, use_invK, seed), each edge once, not the product.  By the constants of csrc/paths.hip
+# (n, m, F, S, d, q, output, maximize, use_invK, seed), each edge once, not the product.  By the constants of csrc/paths.hip and
+# csrc/slab_tiles.hpp (kSlabK)
 # (tests/test_sample_paths_cpu.py reads them from the source and holds this list to them):
 #   k_path_main    point tiles of kPathTile = 128: m in {1, 127, 128, 129, 513}; min(tiles, kPathGridTiles = 1024) workgroups walk the
-#                  tiles: m = 131 073 gives workgroup 0 a second tile of one point; the K axis in slabs of kPathKSlab = 32, the features
+#                  tiles: m = 131 073 gives workgroup 0 a second tile of one point; the K axis in slabs of kSlabK = 32, the features
 #                  rounded up to a slab, then the observations: F in {1, 31, 32, 33, 1024, 8192}, n in {1, 2, 31, 32, 33, 64, 65, 300};
 #                  F = 33 with n = 33: both kinds of column end in a slab that holds one of them; paths in blocks of 16, instantiated
 #                  for 16 | 32 | 64: S in {1, 15, 16, 17, 33, 64};

@@ -10,7 +10,7 @@ Agreement of the routes over the committed cases (normalised units, every z_c(x 
 route is the reference, it differs from the definition (two full 2049 x 2049 inverses, sources 0 and 64) by 5.2e-12.  The assertion
 is TOL64 = 1e-10.  Smallest |z| of a case: 2.1e-7 (n = 65, d = 6, q = 4, 198 147 values); smallest top-two gap: 1.2e-5 (n = 2).
 
-The case list is held to the constants of csrc/expander.hip and csrc/whiten.hpp, read from the source (test_the_case_list_covers_every_edge)."""
+The case list is held to the constants of csrc/expander.hip, csrc/whiten.hpp and csrc/slab_tiles.hpp, read from the source (test_the_case_list_covers_every_edge)."""
 import ctypes as C
 import os
 import re
@@ -54,21 +54,23 @@ def test_the_two_routes_agree_and_the_case_is_sharp(i):
 
 def _constant(text, pattern, what):
     hit = re.search(pattern, text)
-    assert hit, f"csrc/expander.hip or csrc/whiten.hpp no longer states {what} in the form this test reads: revisit expander_oracle.CASES and the pattern"
+    assert hit, f"csrc/expander.hip, csrc/whiten.hpp or csrc/slab_tiles.hpp no longer states {what} in the form this test reads: revisit expander_oracle.CASES and the pattern"
     return [int(g) for g in hit.groups()]
 
 
 def test_the_case_list_covers_every_edge():
     col = lambda key: {c[key] for c in eo.CASES}
     text = open(os.path.join(ROOT, "safe-bayesian-optimization_amd", "csrc", "expander.hip")).read()
-    shared = open(os.path.join(ROOT, "safe-bayesian-optimization_amd", "csrc", "whiten.hpp")).read()     # whiten_tile, the slab helpers
+    shared = open(os.path.join(ROOT, "safe-bayesian-optimization_amd", "csrc", "whiten.hpp")).read()     # whiten_tile
+    tiles = open(os.path.join(ROOT, "safe-bayesian-optimization_amd", "csrc", "slab_tiles.hpp")).read()  # stage 1, the slab and tile steps
     const = lambda name, src=text: _constant(src, r"constexpr\s+int\s+" + name + r"\s*=\s*(\d+)\s*;", name)[0]
-    tile, slab, grid, threads, rows = const("kExpTile"), const("kExpKSlab"), const("kExpGridTiles"), const("kWhitenThreads", shared), const("kWhitenRows", shared)
-    assert const("kSlabK", shared) == slab
-    assert re.search(r"__launch_bounds__\(kWhitenThreads\)\s*void\s+k_exp_stage1", text) and "const int P = whiten_tier(n);" in text
+    tile, slab, grid, threads, rows = const("kExpTile"), const("kSlabK", tiles), const("kExpGridTiles"), const("kWhitenThreads", shared), const("kWhitenRows", shared)
+    assert "tile64_product(sA, sB," in text and "k0 < K; k0 += kSlabK" in tiles       # (k_exp_pairs walks t in these slabs)
+    assert re.search(r"__launch_bounds__\(kWhitenThreads\)\s*void\s+k_exp_stage1", text) and "whiten_stage1_launch(k_exp_stage1<D>" in text and \
+        "const int P = whiten_tier(n);" in tiles
     t1, p1, t2, p2, p3 = _constant(shared, r"int\s+whiten_tier\(int\s+n\)\s*\{\s*return\s+n\s*<=\s*(\d+)\s*\?\s*(\d+)\s*:\s*n\s*<=\s*(\d+)\s*\?\s*(\d+)\s*:\s*(\d+)\s*;",
                                    "the tiers of whiten_tile")
-    lds = _constant(text, r"constexpr\s+size_t\s+kExpS1Lds\s*=\s*(\d+)\s*\*\s*1024\s*;", "kExpS1Lds")[0] * 1024
+    lds = _constant(tiles, r"constexpr\s+size_t\s+kWhitenS1Lds\s*=\s*(\d+)\s*\*\s*1024\s*;", "kWhitenS1Lds")[0] * 1024
     assert re.search(r"nsplit\s*=\s*\(int\)std::min<long long>\(ntt,\s*std::max<long long>\(1,\s*kExpGridTiles\s*/\s*nst\)\)\s*;", text), \
         "csrc/expander.hip no longer splits the targets in the form this test reads: revisit expander_oracle.CASES"
     header = open(os.path.join(ROOT, "include", "safebo.h")).read()

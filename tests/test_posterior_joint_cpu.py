@@ -55,10 +55,12 @@ def _constant(text, name):
 def test_the_case_list_covers_every_edge():
     col = lambda key: {c[key] for c in jo.CASES}
     text = open(os.path.join(ROOT, "safe-bayesian-optimization_amd", "csrc", "joint.hip")).read()
-    shared = open(os.path.join(ROOT, "safe-bayesian-optimization_amd", "csrc", "whiten.hpp")).read()
+    shared = open(os.path.join(ROOT, "safe-bayesian-optimization_amd", "csrc", "slab_tiles.hpp")).read()   # the slab and the two tiles
+    common = open(os.path.join(ROOT, "safe-bayesian-optimization_amd", "csrc", "internal.hpp")).read()     # spad_of, with_spad
     tile, draw, slab = _constant(text, "kJointTile"), _constant(text, "kJointDrawTile"), _constant(shared, "kSlabK")
-    assert (tile, draw, slab) == (64, 128, 32)
-    assert re.search(r"A\.Spad\s*=\s*S\s*<=\s*16\s*\?\s*16\s*:\s*S\s*<=\s*32\s*\?\s*32\s*:\s*64\s*;", text), \
+    assert (tile, draw, slab) == (64, 128, 32) and _constant(shared, "kTile128") == draw and "kJointDrawTile == kTile128" in text
+    assert "A.Spad = spad_of(S);" in text and "with_spad(A.Spad," in text and \
+        re.search(r"int\s+spad_of\(int\s+S\)\s*\{\s*return\s+S\s*<=\s*16\s*\?\s*16\s*:\s*S\s*<=\s*32\s*\?\s*32\s*:\s*64\s*;", common), \
         "csrc/joint.hip no longer pads the draws in the form this test reads: revisit joint_oracle.CASES"
     header = open(os.path.join(ROOT, "include", "safebo.h")).read()
     max_n = int(re.search(r"#define\s+SBO_MAX_N\s+(\d+)", header).group(1))

@@ -10,7 +10,7 @@ Agreement of the routes over the committed cases (normalised units, every value)
 Statistics of 4096 paths on F = 4096 features (n = 20, 8 points, three seeds, both outputs): the mean deviates by at most 3.3 standard
 errors, the variance by at most 4.5 - 6.4 % (without the noise term 52 - 58 %, with the scale sqrt(sf2 / F) 47 - 52 %; the bound is 25 %).
 
-The case list is held to the constants of csrc/paths.hip, read from the source (test_the_case_list_covers_every_edge)."""
+The case list is held to the constants of csrc/paths.hip, csrc/slab_tiles.hpp and csrc/internal.hpp, read from the source (test_the_case_list_covers_every_edge)."""
 import ctypes as C
 import os
 import re
@@ -45,16 +45,20 @@ def test_the_two_routes_agree_and_the_case_is_sharp(i):
 
 def _constant(text, name):
     hit = re.search(r"constexpr\s+int\s+" + name + r"\s*=\s*(\d+)\s*;", text)
-    assert hit, f"csrc/paths.hip no longer states {name} in the form this test reads: revisit paths_oracle.CASES and the pattern"
+    assert hit, f"csrc/paths.hip, csrc/slab_tiles.hpp or csrc/whiten.hpp no longer states {name} in the form this test reads: revisit paths_oracle.CASES and the pattern"
     return int(hit.group(1))
 
 
 def test_the_case_list_covers_every_edge():
     col = lambda key: {c[key] for c in po.CASES}
     text = open(os.path.join(ROOT, "safe-bayesian-optimization_amd", "csrc", "paths.hip")).read()
-    tile, slab, grid = _constant(text, "kPathTile"), _constant(text, "kPathKSlab"), _constant(text, "kPathGridTiles")
-    assert (tile, slab, grid) == (128, 32, 1024)
-    assert re.search(r"A\.Spad\s*=\s*S\s*<=\s*16\s*\?\s*16\s*:\s*S\s*<=\s*32\s*\?\s*32\s*:\s*64\s*;", text), \
+    tiles = open(os.path.join(ROOT, "safe-bayesian-optimization_amd", "csrc", "slab_tiles.hpp")).read()    # the slab and the 128-row tile
+    common = open(os.path.join(ROOT, "safe-bayesian-optimization_amd", "csrc", "internal.hpp")).read()     # spad_of, with_spad
+    tile, slab, grid = _constant(text, "kPathTile"), _constant(tiles, "kSlabK"), _constant(text, "kPathGridTiles")
+    assert (tile, slab, grid) == (128, 32, 1024) and _constant(tiles, "kTile128") == tile and "kPathTile == kTile128" in text
+    assert "k0 += kSlabK" in text and "tile128_step(lds, g," in text                     # (k_path_main walks its K axis in these slabs)
+    assert "A.Spad = spad_of(S);" in text and "with_spad(A.Spad," in text and \
+        re.search(r"int\s+spad_of\(int\s+S\)\s*\{\s*return\s+S\s*<=\s*16\s*\?\s*16\s*:\s*S\s*<=\s*32\s*\?\s*32\s*:\s*64\s*;", common), \
         "csrc/paths.hip no longer pads the paths in the form this test reads: revisit paths_oracle.CASES"
     assert re.search(r"nwg\s*=\s*\(int\)std::min<long long>\(ntiles,\s*kPathGridTiles\)\s*;", text), \
         "csrc/paths.hip no longer bounds its grid in the form this test reads: revisit paths_oracle.CASES"
