@@ -774,6 +774,49 @@ int sbo_sample_paths(sbo_ctx* ctx, const sbo_paths_opts* opts, const double* ome
                      const double* points /* [m][d], raw coordinates */, double* values_out /* [m][S] or NULL */,
                      sbo_paths_result* result);
 
+/* ---- sample-path optima refined off the grid ---- */
+#define SBO_REFINE_PATHS_MAX_STARTS 64
+typedef struct sbo_refine_paths_opts {
+  double   b;                 /* confidence multiplier of the constraints, as sbo_refine_opts.b                               */
+  int32_t  output;            /* the paths' output, 0 .. q-1                                                                  */
+  int32_t  n_paths;           /* S, 1 .. SBO_MAX_PATHS                                                                        */
+  int32_t  n_features;        /* F, 1 .. SBO_MAX_FEATURES                                                                     */
+  int32_t  n_starts;          /* K seeds per path, 1 .. SBO_REFINE_PATHS_MAX_STARTS                                           */
+  int32_t  maximize;          /* 0: minimise every path, 1: maximise                                                          */
+  uint32_t constraint_mask;   /* bit c (1 <= c < q): lcb_c(x) >= 0; bit 0 must be clear; 0: the box only                      */
+  int32_t  max_eval;          /* path + constraint evaluations per problem; as sbo_refine_opts.max_eval (default and ceiling)  */
+  int32_t  reserved;
+  double   lo[SBO_MAX_D], hi[SBO_MAX_D];   /* box (finite, lo <= hi); seeds outside it are infeasible, not clipped           */
+  double   tol;               /* as sbo_refine_opts.tol                                                                       */
+} sbo_refine_paths_opts;
+typedef struct sbo_refine_paths_result {
+  int64_t best[SBO_MAX_PATHS];            /* per path the start whose returned point is best (ties: lowest), -1: none usable / past S */
+  double  best_x[SBO_MAX_PATHS][SBO_MAX_D], best_value[SBO_MAX_PATHS];   /* zeros / NaN where best is -1 */
+  int64_t evaluations;                    /* summed over all S * K problems */
+  int32_t converged, reserved;            /* problems with SBO_REFINE_CONVERGED */
+} sbo_refine_paths_result;
+
+/* Problem (s, k) moves seeds[s][k] to a local optimum of path f_s over {x in the box, lcb_c(x) >= 0 for every c in constraint_mask}.
+ * f_s is the function sbo_sample_paths defines for the same draws (omega, phase, weights, noise: see there; the library applies the
+ * feature scale, the hyper-parameters and c_s = M^T (M r_s)), and both calls share one preparation.  One workgroup per problem runs
+ * sbo_refine's solver -- the projected BFGS and its barrier stages -- on the path's value and analytic gradient (O(F + n) per
+ * evaluation; with an empty mask nothing else is evaluated) and the constraints' exact fp64 posterior.  Then, as in sbo_refine, the
+ * seed and the problem's final and best-objective iterates are judged under exact values: the constraints by the exact list evaluator
+ * with the sweeps' closed predicates, the path by sbo_sample_paths' own evaluator.  So every returned point is feasible under the
+ * values sbo_bounds gives there, value_out[s][k] is bit for bit the entry values_out[.][s] sbo_sample_paths returns for the same draws
+ * at x_out[s][k], and it is no worse than the same figure at the seed (the seed itself at worst).  A seed outside the box or with a
+ * non-finite coordinate is SBO_REFINE_INFEASIBLE_SEED, returned unchanged (value NaN where non-finite).  status_out: sbo_refine_status.
+ * x_out [S][K][d], value_out [S][K], status_out [S][K] may be NULL.  Deterministic, no atomics: the result of problem (s, k) depends on
+ * S, the draws and its own seed, not on K or the other seeds.  Reads the model only, one host wait, no collectives.
+ * SBO_E_INVALID: a NULL ctx, opts, omega, phase, weights, noise, seeds or result; n_paths, n_features, n_starts or output out of range;
+ * maximize not 0 or 1; bit 0 of the mask set or a bit at or above q; a non-finite draw; a bad box, b or tol.  SBO_E_NO_MODEL without a
+ * model; SBO_E_UNSUPPORTED on an fp32 model.  On any error the result is cleared (best -1, values NaN, points and counts zero) and no
+ * output array is written. */
+int sbo_refine_paths(sbo_ctx* ctx, const sbo_refine_paths_opts* opts, const double* omega /* [F][d] */, const double* phase /* [F] */,
+                     const double* weights /* [S][F] */, const double* noise /* [S][n] */, const double* seeds /* [S][K][d] */,
+                     double* x_out /* [S][K][d] or NULL */, double* value_out /* [S][K] or NULL */, int32_t* status_out /* [S][K] or NULL */,
+                     sbo_refine_paths_result* result);
+
 /* ---- the posterior of a point list as a multivariate normal ---- */
 #define SBO_JOINT_MAX_POINTS 2048          /* m of one call: the m x m images are 32 MiB each */
 typedef struct sbo_joint_opts {

@@ -333,6 +333,24 @@ class BO(GP):
             out = self.engine.sample_paths(pool, k, 0, features, seed)
         return out["x"], out["value"]
 
+    def ThompsonRefined(self, k, seed=0, features=1024, starts=1):
+        """``Thompson(k, seed, features)`` with every path's minimiser refined off the grid -> (X [k, d], value [k])
+        (``SweepEngine.refine_paths``).  The pool and the ``sample_paths`` call are ``Thompson``'s; path s then
+        starts from its own grid arg-min and, with ``starts`` = j > 1, also from those of paths s+1 .. s+j-1 (mod k) -- all members
+        of S --, and moves to a local minimum of the path over the box and lcb_c >= 0 of every constraint under the class's ``b``,
+        on the same draws.  The result is the best start's point and the path's value there, never worse than the grid's and
+        feasible under ``lcb``.  Paths only: an exact joint draw (``Thompson(exact=True)``) is a vector, not a function, and has
+        nothing to refine.  A method of its own because ``Thompson``'s signature is pinned.  This is not reference behaviour."""
+        if isinstance(starts, bool) or not isinstance(starts, (int, np.integer)) or starts < 1:
+            raise ValueError("starts must be an integer >= 1")
+        X, value = self.Thompson(k, seed, features)
+        if X.shape[0] == 0 or np.any(np.isnan(X)):       # (an empty S; a path without a value on the pool has nothing to start from)
+            return X, value
+        k = X.shape[0]
+        seeds = X[(np.arange(k)[:, None] + np.arange(min(int(starts), k))[None, :]) % k]          # [k, j, d]
+        ref = self.engine.refine_paths(self.b, seeds, 0, features, seed, lo=self.bound[:, 0], hi=self.bound[:, 1])   # (the same draws)
+        return ref["best_x"], ref["best_value"]
+
     _pair_max_eval = 1600  # evaluations of one point per refined pair (a pair costs two, and has twice the variables)
 
     def _sweep_L(self, res, c):

@@ -22,6 +22,7 @@ SBO_MAX_PATHS = 64
 SBO_MAX_FEATURES = 8192
 SBO_PATHS_MAX_POINTS = 1 << 24
 SBO_PATHS_MAX_VALUES = 1 << 32
+SBO_REFINE_PATHS_MAX_STARTS = 64
 SBO_JOINT_MAX_POINTS = 2048
 
 SBO_F64, SBO_F32 = 0, 1
@@ -173,6 +174,18 @@ class PathsResult(C.Structure):
     _fields_ = [("index", C.c_int64 * SBO_MAX_PATHS), ("value", C.c_double * SBO_MAX_PATHS)]
 
 
+class RefinePathsOpts(C.Structure):
+    _fields_ = [("b", C.c_double), ("output", C.c_int32), ("n_paths", C.c_int32), ("n_features", C.c_int32), ("n_starts", C.c_int32),
+                ("maximize", C.c_int32), ("constraint_mask", C.c_uint32), ("max_eval", C.c_int32), ("reserved", C.c_int32),
+                ("lo", C.c_double * SBO_MAX_D), ("hi", C.c_double * SBO_MAX_D), ("tol", C.c_double)]
+
+
+class RefinePathsResult(C.Structure):
+    _fields_ = [("best", C.c_int64 * SBO_MAX_PATHS), ("best_x", (C.c_double * SBO_MAX_D) * SBO_MAX_PATHS),
+                ("best_value", C.c_double * SBO_MAX_PATHS), ("evaluations", C.c_int64), ("converged", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class JointOpts(C.Structure):
     _fields_ = [("output", C.c_int32), ("n_draws", C.c_int32), ("noise", C.c_int32), ("maximize", C.c_int32), ("jitter", C.c_double)]
 
@@ -256,6 +269,7 @@ SYMBOLS = [
     ("sbo_batch_select", C.c_int, [_P, C.POINTER(BatchOpts), C.c_int64, _P, _P, _P, C.POINTER(BatchResult)]),
     ("sbo_expander_gain", C.c_int, [_P, C.POINTER(ExpanderOpts), C.c_int64, _P, C.c_int64, _P, _P, _P, _P]),
     ("sbo_sample_paths", C.c_int, [_P, C.POINTER(PathsOpts), _P, _P, _P, _P, C.c_int64, _P, _P, C.POINTER(PathsResult)]),
+    ("sbo_refine_paths", C.c_int, [_P, C.POINTER(RefinePathsOpts), _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(RefinePathsResult)]),
     ("sbo_posterior_joint", C.c_int, [_P, C.POINTER(JointOpts), C.c_int64, _P, _P, _P, _P, _P, _P, C.POINTER(JointResult)]),
     ("sbo_plant_wo", C.c_int, [_P, C.c_int64, _P, _P]),
     ("sbo_profile_get", C.c_int, [_P, C.POINTER(Profile)]),

@@ -861,6 +861,27 @@ int launch_posterior_on_axes(sbo_ctx* c, int d, const long long* count, const do
                              unsigned long long* lmax);
 // the exact posterior of the generic kernel on an explicit fp64 list [N][d] (device), into caller-given arrays [q][N]
 int launch_posterior_on_list(sbo_ctx* c, const double* pts, long long N, double* mean_out, double* var_out);
+// paths.hip: the preparation of sbo_sample_paths for a caller that evaluates the paths itself (sbo_refine_paths, refine.hip).
+// paths_check_draws: the refusals of the draws (ranges, output, finite entries).  paths_prepare_list: the draws' device copies, the
+// B operand and the packed per-path image in sbo_ctx::pathbuf, with room for a list of m points -- valid until the next call that
+// carves pathbuf.  paths_eval_list: sbo_sample_paths' own evaluator (k_path_main) on pts -> vals, so a value of (point, path) is the
+// bit pattern sbo_sample_paths returns there.  Everything is enqueued on c->stream; the caller waits.
+struct PathDraws {
+  int output, S, F;
+  const double *omega, *phase, *weights, *noise;   // the caller's [F][d], [F], [S][F], [S][n]
+  std::vector<double> omega_padded;                // (the host image the upload reads: it lives until the caller's wait)
+};
+struct PathImage {
+  const double* Bt;        // [S][F + n]: path s' scaled weights, then c_s
+  const double *om, *ph;   // [KF][dpad], [KF]
+  const double *B, *As, *sq;   // the evaluator's operands: B [KF + KN][Spad], the scaled observations and their squares
+  double *pts, *vals;     // the caller's list [m][d] and its values [m][S]
+  int F, S, output;
+  long long m;
+};
+int paths_check_draws(const sbo_ctx* c, const PathDraws& dr);
+int paths_prepare_list(sbo_ctx* c, PathDraws& dr, long long m, PathImage* img);
+int paths_eval_list(sbo_ctx* c, const PathImage& img);
 // guard.hip: the exact evaluator that the band of the resident posterior was measured against, on a list; K1b's band (device,
 // enqueued behind the first posterior launch of a plan); a host-known band (K1t) or "none" (exact kernels)
 int guard_exact_list(sbo_ctx* c, const double* pts, long long N, double* mean_out, double* var_out);

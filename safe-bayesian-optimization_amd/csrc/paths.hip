@@ -16,6 +16,7 @@
 //                  The prior at the data is THIS kernel with the observations as the points and no observation slabs: no second
 //                  feature evaluator exists that could round differently.
 //   k_path_solve   per path: r, w = M r (factor_lower_mv, whiten.hpp), c = M^T w (factor_upper_mv) into the observation rows of B
+//   k_path_bt      the packed per-path image [S][F + n] of B's columns, for sbo_refine_paths' one-point evaluator (refine.hip)
 //   k_path_finish  the partials of the workgroups -> the result block (partials_merge, slab_tiles.hpp)
 // Every sum over features and observations runs in an order fixed by (F, n) alone, (value, index) reductions are arg_take's total
 // order, there are no atomics: the value of (point, path) does not depend on m, on the point's place or on the other paths, and two
@@ -45,7 +46,7 @@ struct PathArgs {                                // by value (kernarg segment)
 
 struct PathBufs {
   ObsResident obs;                               // (without w)
-  double *om, *ph, *wt, *nz, *B, *prior, *pts, *vals, *pval;
+  double *om, *ph, *wt, *nz, *B, *prior, *pts, *vals, *pval, *Bt;
   long long* pidx;
   sbo_paths_result* res;
 };
@@ -138,9 +139,83 @@ __global__ __launch_bounds__(kMergeThreads) void k_path_finish(const PathArgs A,
   partials_merge(A.S, A.Spad, A.maximize, nwg, pval, pidx, res->index, res->value);
 }
 
+// ---- per path: the packed image Bt [s][F + n] = B's feature rows, then its observation rows, of column s -------------------------------
+// (what a one-point evaluator of path s reads front to back: sbo_refine_paths' solver)
+__global__ __launch_bounds__(256) void k_path_bt(const PathArgs A, const double* __restrict__ B, double* __restrict__ Bt) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int w = A.F + A.n;
+  if (e >= (long long)A.S * w) return;
+  const int s = (int)(e / w), k = (int)(e - (long long)s * w);
+  Bt[e] = B[(size_t)(k < A.F ? k : A.KF + (k - A.F)) * A.Spad + s];
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------------
+// the argument block of a call on c's model: S paths of F features of output o at m points
+static PathArgs path_args(const sbo_ctx* c, int o, int S, int F, int maximize, long long m) {
+  const ModelConst& mc = c->mc;
+  PathArgs A{};
+  A.n = mc.n;
+  A.d = mc.d;
+  A.q = mc.q;
+  A.ld = c->factor.ld();
+  A.F = F;
+  A.S = S;
+  A.Spad = spad_of(S);
+  A.o = o;
+  A.KF = (F + kSlabK - 1) / kSlabK * kSlabK;
+  A.KN = (mc.n + kSlabK - 1) / kSlabK * kSlabK;
+  A.maximize = maximize;
+  A.m = m;
+  A.op = out_params(mc, o);
+  A.ymean = mc.Y_mean[o];
+  A.ystd = mc.Y_std[o];
+  A.fscale = std::sqrt(2.0 * mc.sf2[o] / (double)F);
+  return A;
+}
+
+// scratch: X_norm [n][d] | Y_norm [n][q] | scaled observations [n][dpad], their squares | omega [KF][dpad], phase [KF] (zero rows behind
+// F) | weights [S][F] | noise [S][n] | B [KF + KN][Spad] | the prior at the data [n][S] | the points | the values [m][S] where asked |
+// sbo_sample_paths: the partials [nwg][Spad], the result block | a caller that evaluates paths itself (image): Bt [S][F + n]
+static size_t paths_layout(Carve cv, const ModelConst& mc, const PathArgs& A, bool vals, int nwg, bool image, PathBufs& Bf) {
+  const size_t KF = (size_t)A.KF, Sp = (size_t)A.Spad;
+  Bf.obs.take(cv, mc, 1, 0);
+  cv.take(Bf.om, KF * mc.dpad);
+  cv.take(Bf.ph, KF);
+  cv.take(Bf.wt, (size_t)A.S * A.F);
+  cv.take(Bf.nz, (size_t)A.S * A.n);
+  cv.take(Bf.B, (KF + (size_t)A.KN) * Sp);
+  cv.take(Bf.prior, (size_t)A.n * A.S);
+  cv.take(Bf.pts, (size_t)A.m * A.d);
+  cv.take(Bf.vals, vals ? (size_t)A.m * A.S : 0);
+  cv.take(Bf.pval, (size_t)nwg * Sp);
+  cv.take(Bf.pidx, (size_t)nwg * Sp);
+  cv.take(Bf.res, image ? 0 : 1);
+  cv.take(Bf.Bt, image ? (size_t)A.S * (A.F + A.n) : 0);
+  return cv.off;
+}
+
+// the draws and the observations on their way to the device; dr.omega_padded: omega in padded lanes [KF][dpad], zero behind d and behind
+// F (a host block the copy reads: the caller waits for the stream before it lets go of dr)
+static hipError_t paths_upload(sbo_ctx* c, const PathArgs& A, const PathBufs& Bf, PathDraws& dr) {
+  hipStream_t st = c->stream;
+  const int D = c->mc.dpad, d = A.d, F = A.F, S = A.S, n = A.n;
+  const size_t KF = (size_t)A.KF, Sp = (size_t)A.Spad;
+  dr.omega_padded.assign(KF * D, 0.0);
+  for (int f = 0; f < F; ++f)
+    for (int a = 0; a < d; ++a) dr.omega_padded[(size_t)f * D + a] = dr.omega[(size_t)f * d + a];
+  hipError_t e = hipMemsetAsync(Bf.ph, 0, sizeof(double) * KF, st);
+  if (e == hipSuccess) e = hipMemsetAsync(Bf.B, 0, sizeof(double) * (KF + (size_t)A.KN) * Sp, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(Bf.om, dr.omega_padded.data(), sizeof(double) * KF * D, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(Bf.ph, dr.phase, sizeof(double) * (size_t)F, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(Bf.wt, dr.weights, sizeof(double) * (size_t)S * F, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(Bf.nz, dr.noise, sizeof(double) * (size_t)S * n, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = Bf.obs.upload(c, st);
+  return e;
+}
+
+// prepare: the scaled observations, the feature rows of B, the prior at the data, the observation rows of B
 template <int D, int SB>
-static int paths_enqueue(sbo_ctx* c, const PathArgs& A, const PathBufs& Bf, int nwg, long long ntiles) {
+static int paths_prepare(sbo_ctx* c, const PathArgs& A, const PathBufs& Bf) {
   hipStream_t st = c->stream;
   const int n = A.n;
   if (int rc = Bf.obs.prepare<D>(c, st, &A.op, &A.o, 1, 0)) return rc;
@@ -165,12 +240,54 @@ static int paths_enqueue(sbo_ctx* c, const PathArgs& A, const PathBufs& Bf, int 
   hipLaunchKernelGGL(k_path_solve, dim3((unsigned)A.S), dim3(1024), 0, st, A, (const double*)Bf.obs.Yn, (const double*)Bf.prior, (const double*)Bf.nz,
                      c->factor.F(), Bf.B);
   SBO_HIP(hipGetLastError());
-  hipLaunchKernelGGL((k_path_main<D, SB>), dim3((unsigned)nwg), dim3(kPathThreads), 0, st, A, ntiles, (const double*)Bf.pts, (const double*)Bf.om,
-                     (const double*)Bf.ph, (const double*)Bf.obs.As, (const double*)Bf.obs.sq, (const double*)Bf.B, Bf.vals, Bf.pval, Bf.pidx);
-  SBO_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_path_finish, dim3(1), dim3(kMergeThreads), 0, st, A, nwg, (const double*)Bf.pval, (const long long*)Bf.pidx, Bf.res);
+  return SBO_OK;
+}
+
+// evaluate a point list: pts [A.m][d] -> vals, and per (workgroup, path) the arg-best partials where pval / pidx are given
+template <int D, int SB>
+static int paths_evaluate(sbo_ctx* c, const PathArgs& A, int nwg, long long ntiles, const double* pts, const double* om, const double* ph,
+                          const double* As, const double* sq, const double* B, double* vals, double* pval, long long* pidx) {
+  hipLaunchKernelGGL((k_path_main<D, SB>), dim3((unsigned)nwg), dim3(kPathThreads), 0, c->stream, A, ntiles, pts, om, ph, As, sq, B, vals, pval, pidx);
   SBO_HIP(hipGetLastError());
   return SBO_OK;
+}
+
+static long long path_tiles(long long m) { return (m + kPathTile - 1) / kPathTile; }
+
+int paths_check_draws(const sbo_ctx* c, const PathDraws& dr) {
+  const ModelConst& mc = c->mc;
+  if (dr.S < 1 || dr.S > SBO_MAX_PATHS) return fail(SBO_E_INVALID, "n_paths must be in [1, SBO_MAX_PATHS]");
+  if (dr.F < 1 || dr.F > SBO_MAX_FEATURES) return fail(SBO_E_INVALID, "n_features must be in [1, SBO_MAX_FEATURES]");
+  if (dr.output < 0 || dr.output >= mc.q) return fail(SBO_E_INVALID, "output out of range [0, q)");
+  if (!all_finite(dr.omega, (size_t)dr.F * mc.d) || !all_finite(dr.phase, (size_t)dr.F) || !all_finite(dr.weights, (size_t)dr.S * dr.F) ||
+      !all_finite(dr.noise, (size_t)dr.S * mc.n))
+    return fail(SBO_E_INVALID, "omega, phase, weights or noise holds a non-finite entry");
+  return SBO_OK;
+}
+
+int paths_prepare_list(sbo_ctx* c, PathDraws& dr, long long m, PathImage* img) {
+  const ModelConst& mc = c->mc;
+  const PathArgs A = path_args(c, dr.output, dr.S, dr.F, 0, m);
+  PathBufs Bf;
+  int rc;
+  if ((rc = carve(c->pathbuf, [&](Carve cv) { return paths_layout(cv, mc, A, true, 0, true, Bf); }, 256))) return rc;
+  SBO_HIP(paths_upload(c, A, Bf, dr));
+  if ((rc = with_dpad(mc.dpad, [&](auto DD) { return with_spad(A.Spad, [&](auto SB) { return paths_prepare<DD(), SB()>(c, A, Bf); }); }))) return rc;
+  hipLaunchKernelGGL(k_path_bt, dim3((unsigned)(((long long)A.S * (A.F + A.n) + 255) / 256)), dim3(256), 0, c->stream, A, (const double*)Bf.B, Bf.Bt);
+  SBO_HIP(hipGetLastError());
+  *img = PathImage{Bf.Bt, Bf.om, Bf.ph, Bf.B, Bf.obs.As, Bf.obs.sq, Bf.pts, Bf.vals, dr.F, dr.S, dr.output, m};
+  return SBO_OK;
+}
+
+int paths_eval_list(sbo_ctx* c, const PathImage& img) {
+  const PathArgs A = path_args(c, img.output, img.S, img.F, 0, img.m);
+  const long long ntiles = path_tiles(img.m);
+  const int nwg = (int)std::min<long long>(ntiles, kPathGridTiles);
+  return with_dpad(c->mc.dpad, [&](auto DD) {
+    return with_spad(A.Spad, [&](auto SB) {
+      return paths_evaluate<DD(), SB()>(c, A, nwg, ntiles, img.pts, img.om, img.ph, img.As, img.sq, img.B, img.vals, nullptr, nullptr);
+    });
+  });
 }
 
 }  // namespace sbo
@@ -189,73 +306,36 @@ extern "C" int sbo_sample_paths(sbo_ctx* c, const sbo_paths_opts* opts, const do
   int rc;
   if ((rc = model_reader_check(c, "sbo_sample_paths", false))) return rc;        // (d and q, which the checks below need)
   const ModelConst& mc = c->mc;
-  const int n = mc.n, d = mc.d, q = mc.q, o = opts->output, S = opts->n_paths, F = opts->n_features;
-  if (o < 0 || o >= q) return fail(SBO_E_INVALID, "output out of range [0, q)");
+  const int d = mc.d, S = opts->n_paths;
+  PathDraws dr{opts->output, S, opts->n_features, omega, phase, weights, noise, {}};
+  if (dr.output < 0 || dr.output >= mc.q) return fail(SBO_E_INVALID, "output out of range [0, q)");
   if (values_out && (unsigned long long)m * (unsigned long long)S * sizeof(double) > SBO_PATHS_MAX_VALUES)
     return fail(SBO_E_UNSUPPORTED, "sbo_sample_paths: values_out needs more than SBO_PATHS_MAX_VALUES bytes");
-  if (!all_finite(omega, (size_t)F * d) || !all_finite(phase, (size_t)F) || !all_finite(weights, (size_t)S * F) || !all_finite(noise, (size_t)S * n))
-    return fail(SBO_E_INVALID, "omega, phase, weights or noise holds a non-finite entry");
+  if ((rc = paths_check_draws(c, dr))) return rc;
   if (!all_finite(points, (size_t)m * d)) return fail(SBO_E_INVALID, "points holds a non-finite coordinate");
   if ((rc = model_reader_begin(c, "sbo_sample_paths", false))) return rc;
-  PathArgs A{};
-  A.n = n;
-  A.d = d;
-  A.q = q;
-  A.ld = c->factor.ld();
-  A.F = F;
-  A.S = S;
-  A.Spad = spad_of(S);
-  A.o = o;
-  A.KF = (F + kSlabK - 1) / kSlabK * kSlabK;
-  A.KN = (n + kSlabK - 1) / kSlabK * kSlabK;
-  A.maximize = opts->maximize;
-  A.m = m;
-  A.op = out_params(mc, o);
-  A.ymean = mc.Y_mean[o];
-  A.ystd = mc.Y_std[o];
-  A.fscale = std::sqrt(2.0 * mc.sf2[o] / (double)F);
-  const long long ntiles = ((long long)m + kPathTile - 1) / kPathTile;
+  const PathArgs A = path_args(c, dr.output, S, dr.F, opts->maximize, m);
+  const long long ntiles = path_tiles(m);
   const int nwg = (int)std::min<long long>(ntiles, kPathGridTiles);
-  // scratch: X_norm [n][d] | Y_norm [n][q] | scaled observations [n][dpad], their squares | omega [KF][dpad], phase [KF] (zero rows behind
-  // F) | weights [S][F] | noise [S][n] | B [KF + KN][Spad] | the prior at the data [n][S] | the points | the values [m][S] where asked |
-  // the partials [nwg][Spad] | the result block
-  const int D = mc.dpad;
-  const size_t KF = (size_t)A.KF, Sp = (size_t)A.Spad;
   PathBufs Bf;
-  auto layout = [&](Carve cv) {
-    Bf.obs.take(cv, mc, 1, 0);
-    cv.take(Bf.om, KF * D);
-    cv.take(Bf.ph, KF);
-    cv.take(Bf.wt, (size_t)S * F);
-    cv.take(Bf.nz, (size_t)S * n);
-    cv.take(Bf.B, (KF + (size_t)A.KN) * Sp);
-    cv.take(Bf.prior, (size_t)n * S);
-    cv.take(Bf.pts, (size_t)m * d);
-    cv.take(Bf.vals, values_out ? (size_t)m * S : 0);
-    cv.take(Bf.pval, (size_t)nwg * Sp);
-    cv.take(Bf.pidx, (size_t)nwg * Sp);
-    cv.take(Bf.res, 1);
-    return cv.off;
-  };
-  if ((rc = carve(c->pathbuf, layout, 256))) return rc;
+  if ((rc = carve(c->pathbuf, [&](Carve cv) { return paths_layout(cv, mc, A, values_out != nullptr, nwg, false, Bf); }, 256))) return rc;
   if (!values_out) Bf.vals = nullptr;
   hipStream_t st = c->stream;
-  // omega in padded lanes [KF][dpad], zero behind d and behind F (the host block is read by the copy before the call returns: it is waited for)
-  std::vector<double> omp(KF * D, 0.0);
-  for (int f = 0; f < F; ++f)
-    for (int a = 0; a < d; ++a) omp[(size_t)f * D + a] = omega[(size_t)f * d + a];
-  SBO_HIP(hipMemsetAsync(Bf.ph, 0, sizeof(double) * KF, st));
-  SBO_HIP(hipMemsetAsync(Bf.B, 0, sizeof(double) * (KF + (size_t)A.KN) * Sp, st));
-  hipError_t e = hipMemcpyAsync(Bf.om, omp.data(), sizeof(double) * KF * D, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(Bf.ph, phase, sizeof(double) * (size_t)F, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(Bf.wt, weights, sizeof(double) * (size_t)S * F, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(Bf.nz, noise, sizeof(double) * (size_t)S * n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = Bf.obs.upload(c, st);
+  hipError_t e = paths_upload(c, A, Bf, dr);
   if (e == hipSuccess) e = hipMemcpyAsync(Bf.pts, points, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice, st);
-  auto enqueue = [&](auto DD) { return with_spad(A.Spad, [&](auto SB) { return paths_enqueue<DD(), SB()>(c, A, Bf, nwg, ntiles); }); };
-  rc = e == hipSuccess ? with_dpad(D, enqueue) : SBO_OK;
+  auto enqueue = [&](auto DD) {
+    return with_spad(A.Spad, [&](auto SB) {
+      if (int r = paths_prepare<DD(), SB()>(c, A, Bf)) return r;
+      return paths_evaluate<DD(), SB()>(c, A, nwg, ntiles, Bf.pts, Bf.om, Bf.ph, Bf.obs.As, Bf.obs.sq, Bf.B, Bf.vals, Bf.pval, Bf.pidx);
+    });
+  };
+  rc = e == hipSuccess ? with_dpad(mc.dpad, enqueue) : SBO_OK;
+  if (e == hipSuccess && !rc) {
+    hipLaunchKernelGGL(k_path_finish, dim3(1), dim3(kMergeThreads), 0, st, A, nwg, (const double*)Bf.pval, (const long long*)Bf.pidx, Bf.res);
+    e = hipGetLastError();
+  }
   if (e != hipSuccess || rc) {
-    (void)hipStreamSynchronize(st);                     // (nothing of the call may still read the caller's arrays or `omp`)
+    (void)hipStreamSynchronize(st);                     // (nothing of the call may still read the caller's arrays or the padded omega)
     SBO_HIP(e);
     return rc;
   }

@@ -220,6 +220,20 @@ __device__ bool ref_conf(const RefEval& E, int u, double b, double sgn, int d, d
   return true;
 }
 
+// the safe-set terms lcb_c(x) > 0 of the constraint slots, in slot order, added to the barrier sum (B, gB); false: the trial is rejected
+__device__ __forceinline__ bool ref_safe_terms(const RefineArgs& A, const RefEval& E, double& B, double* gB) {
+  const int d = A.mc.d;
+  for (int u = 0; u < A.nu; ++u) {
+    if (!((A.con_slots >> u) & 1)) continue;
+    double gc, ggc[kMaxD];
+    if (!ref_conf(E, u, A.b, -1.0, d, gc, ggc)) return false;
+    if (!(gc > 0.0)) return false;
+    B -= log(gc / A.mc.Y_std[A.outs[u]]);
+    for (int a = 0; a < d; ++a) gB[a] -= ggc[a] / gc;
+  }
+  return true;
+}
+
 // objective part (fo, go; obj = sign-adjusted objective) and barrier sum (B, gB) at x (pair: x, x') from the evaluation of its
 // points; false: the trial is rejected
 __device__ bool ref_terms(const RefineArgs& A, const RefEval* Ev, const double* x, double& fo, double* go, double& B, double* gB, double& obj) {
@@ -265,14 +279,7 @@ __device__ bool ref_terms(const RefineArgs& A, const RefEval* Ev, const double* 
     ok = ok && isfinite(go[a]);
   }
   B = 0.0;
-  for (int u = 0; u < A.nu; ++u) {
-    if (!((A.con_slots >> u) & 1)) continue;
-    double gc, ggc[kMaxD];
-    if (!ref_conf(E, u, b, -1.0, d, gc, ggc)) return false;
-    if (!(gc > 0.0)) return false;
-    B -= log(gc / A.mc.Y_std[A.outs[u]]);
-    for (int a = 0; a < d; ++a) gB[a] -= ggc[a] / gc;
-  }
+  if (!ref_safe_terms(A, E, B, gB)) return false;
   if (A.use_ball) {
     double ss = 0.0;
     for (int a = 0; a < d; ++a) ss += (x[a] - A.x0[a]) * (x[a] - A.x0[a]);
@@ -550,6 +557,181 @@ __global__ void k_refine_accept(const RefineArgs* __restrict__ Ap, long long S, 
   }
 }
 
+// ---- sbo_refine_paths: the objective is a posterior sample path f_s -------------------------------------------
+// RefineArgs holds the constraints alone (every slot a constraint, no objective slot, as with SBO_REFINE_DIST); the path comes as the
+// packed image of paths.hip.  Problem p = s K + k: path s = p / K, start k.
+struct RefPathArgs {               // by value (kernarg segment)
+  const double *Bt, *om, *ph;      // [S][F + n] scaled weights then c_s | omega [..][dpad] | phase
+  int F, o, K, pad;                // features, the paths' output, starts per path
+};
+
+// value and gradient (raw coordinates, un-normalised) of the path with image bt [F + n] at x -> pv [1 + d].  Threads stride over the
+// features (one sincos each), then over the observations under output o's hyper-parameters in ref_eval's form of k . alpha; the d + 1
+// columns are summed by block_sum_cols, so the order is fixed by (F, n, block size) alone.
+__device__ __noinline__ void ref_path_eval(const RefineArgs& A, const RefPathArgs& PA, const double* bt, const double* x, const double* Xn,
+                              double (*part)[kMaxD + 1], double* red, double* pv) {
+  const ModelConst& mc = A.mc;
+  const int n = mc.n, d = mc.d, dp = mc.dpad, o = PA.o, F = PA.F, tid = threadIdx.x, bd = blockDim.x;
+  double acc[kMaxD + 1];
+#pragma unroll
+  for (int a = 0; a < kMaxD + 1; ++a) acc[a] = 0.0;
+  {                                                 // the features: sum_f bt[f] cos(omega_f . u + phase_f), u = xn vinv
+    double u[kMaxD];
+#pragma unroll
+    for (int a = 0; a < kMaxD; ++a) u[a] = a < d ? ((x[a] - mc.X_mean[a]) / mc.X_std[a]) * mc.vinv[o][a] : 0.0;
+    for (int f = tid; f < F; f += bd) {
+      const double* omf = PA.om + (size_t)f * dp;
+      double arg = 0.0;
+#pragma unroll
+      for (int a = 0; a < kMaxD; ++a)
+        if (a < d) arg += omf[a] * u[a];
+      arg += PA.ph[f];
+      double sn, cs;
+      sincos(arg, &sn, &cs);
+      const double bf = bt[f], bs = -bf * sn;
+      acc[0] += bf * cs;
+#pragma unroll
+      for (int a = 0; a < kMaxD; ++a)
+        if (a < d) acc[1 + a] += bs * omf[a];
+    }
+#pragma unroll
+    for (int a = 0; a < kMaxD; ++a)
+      if (a < d) acc[1 + a] *= mc.vinv[o][a];       // (d u / d xn; the columns now hold d / d xn, as the observations' terms do)
+  }
+  const double* cf = bt + F;                        // c_s
+  const double sf2 = mc.sf2[o];
+  double xn[kMaxD];
+#pragma unroll
+  for (int a = 0; a < kMaxD; ++a) xn[a] = a < d ? (x[a] - mc.X_mean[a]) / mc.X_std[a] : 0.0;
+  for (int j = tid; j < n; j += bd) {
+    const double* Xj = Xn + (size_t)j * dp;
+    double dist = 0.0;
+#pragma unroll
+    for (int a = 0; a < kMaxD; ++a)
+      if (a < d) {
+        const double diff = Xj[a] - xn[a];
+        dist += diff * diff * mc.inv_ell[o][a];
+      }
+    const double ck = cf[j] * (sf2 * exp(-0.5 * dist));
+    acc[0] += ck;
+#pragma unroll
+    for (int a = 0; a < kMaxD; ++a)
+      if (a < d) acc[1 + a] += ck * (Xj[a] - xn[a]) * mc.inv_ell[o][a];
+  }
+  block_sum_cols(acc, d + 1, part, red);
+  if (tid == 0) {
+    const double ys = mc.Y_std[o];
+    pv[0] = ys * (mc.mp[o] + red[0]) + mc.Y_mean[o];
+    for (int a = 0; a < d; ++a) pv[1 + a] = ys * red[1 + a] / mc.X_std[a];
+  }
+  __syncthreads();
+}
+
+// ref_advance with the path as the objective: pv from ref_path_eval, the constraints' evaluation in E
+__device__ __noinline__ bool ref_path_advance(RefState& S, const RefineArgs& A, const RefEval& E, const double* pv, int o, double* trial) {
+  const int d = A.nz;
+  const double sg = A.maximize ? -1.0 : 1.0, ys = A.mc.Y_std[o];
+  double go[kMaxD], B = 0.0, gB[kMaxD];
+  const double obj = sg * pv[0], fo = obj / ys;
+  bool ok = isfinite(fo);
+  for (int a = 0; a < d; ++a) {
+    go[a] = sg * pv[1 + a] / ys;
+    gB[a] = 0.0;
+    ok = ok && isfinite(go[a]);
+  }
+  ok = ok && ref_safe_terms(A, E, B, gB) && isfinite(B);
+  for (int a = 0; a < d; ++a) ok = ok && isfinite(gB[a]);
+  return ref_step(S, A, ok, fo, go, B, gB, obj, 1, trial);
+}
+
+// One workgroup per problem.  seeds [P][d]; m0 / v0 [q][P] the exact values at the seeds (not read without constraints);
+// cand [2 P][d]: the final and the best-objective iterate
+template <bool kLds>
+__global__ __launch_bounds__(1024) void k_refine_path(const RefineArgs* __restrict__ Ap, const RefPathArgs PA, const double* __restrict__ F,
+                                                      const double* __restrict__ alpha, const double* __restrict__ Xn,
+                                                      const double* __restrict__ seeds, const double* __restrict__ m0,
+                                                      const double* __restrict__ v0, long long P, double* __restrict__ cand,
+                                                      int* __restrict__ st_out, int* __restrict__ nev_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ RefState R;
+  __shared__ RefEval E;
+  __shared__ double trial[kMaxD], red[2 * (kMaxD + 1)], uup[kRefWaves], pv[kMaxD + 1];
+  __shared__ double part[kRefWaves][kMaxD + 1];
+  __shared__ int go;
+  const RefineArgs& A = *Ap;
+  const int n = A.mc.n, d = A.mc.d;
+  const long long p = blockIdx.x;
+  const double* bt = PA.Bt + (size_t)(p / PA.K) * (PA.F + n);
+  double* kv = reinterpret_cast<double*>(smem);     // [n]
+  double* uv = kv + n;                              // [n]
+  double* Ml = uv + n;
+  if (kLds) ref_load_M(A, F, Ml);
+  if (threadIdx.x == 0) {
+    for (int a = 0; a < d; ++a) {
+      trial[a] = seeds[p * d + a];
+      R.s.x[a] = R.xb[a] = trial[a];
+      R.span[a] = A.hi[a] - A.lo[a];
+      R.D2[a] = R.span[a] * R.span[a];
+    }
+    const int fe = ref_feasible(A, trial, m0, v0, P, p);
+    R.nev = 0;
+    R.status = fe == 0 ? SBO_REFINE_INFEASIBLE_SEED : fe == 2 ? SBO_REFINE_ON_BOUNDARY : -1;
+    R.nbar = __popc((unsigned)A.con_slots);
+    R.phase = REF_PH_START;
+    pbfgs_reset_h(R.s, ref_box(R, A), d);
+    go = R.status < 0;
+  }
+  __syncthreads();
+  while (go) {
+    ref_eval<kLds, 1>(A, trial, F, Ml, alpha, Xn, kv, uv, part, red, uup, &E);   // (the constraint slots; nothing without them)
+    ref_path_eval(A, PA, bt, trial, Xn, part, red, pv);
+    if (threadIdx.x == 0) go = ref_path_advance(R, A, E, pv, PA.o, trial);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    for (int a = 0; a < d; ++a) {
+      cand[(2 * p) * d + a] = R.s.x[a];
+      cand[(2 * p + 1) * d + a] = R.xb[a];
+    }
+    st_out[p] = R.status;
+    nev_out[p] = R.nev;
+  }
+}
+
+// k_refine_accept with the path's exact values: vals [3 P][S] are k_path_main's on the list seeds | candidates, and problem p reads
+// column p / K of its rows.  m0 / v0 [q][P], m1 / v1 [q][2 P]
+__global__ void k_refine_path_accept(const RefineArgs* __restrict__ Ap, long long P, int K, int S, const double* __restrict__ pts,
+                                     const double* __restrict__ vals, const double* __restrict__ m0, const double* __restrict__ v0,
+                                     const double* __restrict__ m1, const double* __restrict__ v1, int* __restrict__ st,
+                                     double* __restrict__ x_out, double* __restrict__ val_out) {
+  const RefineArgs& A = *Ap;
+  const int d = A.nz;
+  const double sg = A.maximize ? -1.0 : 1.0;
+  const double* cand = pts + P * d;
+  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < P; p += (long long)gridDim.x * blockDim.x) {
+    const int s = (int)(p / K);
+    const double fs = vals[p * S + s];
+    int status = st[p];
+    int pick = -1;                                   // -1 seed, 0 final iterate, 1 best iterate
+    double fv = fs;
+    if (status != SBO_REFINE_INFEASIBLE_SEED && status != SBO_REFINE_ON_BOUNDARY) {
+      double best = 0.0;
+      for (int k = 0; k < 2; ++k) {
+        const long long g = 2 * p + k;
+        if (!ref_feasible(A, cand + g * d, m1, v1, 2 * P, g)) continue;
+        const double f = vals[(P + g) * S + s];
+        if (!(sg * f <= sg * fs)) continue;
+        if (pick < 0 || sg * f < best) { pick = k; best = sg * f; fv = f; }
+      }
+      if (pick < 0) status = SBO_REFINE_NO_PROGRESS;
+    }
+    const double* xs = pick < 0 ? pts + p * d : cand + (2 * p + pick) * d;
+    for (int a = 0; a < d; ++a) x_out[p * d + a] = xs[a];
+    val_out[p] = fv;
+    st[p] = status;
+  }
+}
+
 // the ceiling of max_eval: one launch holds a CU for max_eval evaluations of O(n^2) each, which keeps a call near a few seconds at n = 2048
 static int refine_eval_cap(int n) { return (int)std::min<double>(kRefMaxEval, std::max<double>(kRefDefaultEval, 4e9 / ((double)n * n))); }
 static int refine_threads(int n) { return n > 256 ? 1024 : 256; }
@@ -761,6 +943,127 @@ static int refine_problem(sbo_ctx* c, const sbo_refine_sets_opts* opts, int64_t 
   if (value_out) std::copy(hv.begin(), hv.end(), value_out);
   if (status_out)
     for (long long s = 0; s < S; ++s) status_out[s] = hs[s];
+  return SBO_OK;
+}
+
+template <bool kLds>
+static int refine_path_launch(sbo_ctx* c, size_t lds, int threads, long long P, const RefineArgs* dA, const RefPathArgs& PA, const double* dseed,
+                              const double* m0, const double* v0, double* cand, int* dst, int* dnev) {
+  SBO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_refine_path<kLds>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((k_refine_path<kLds>), dim3((unsigned)P), dim3(threads), lds, c->stream, dA, PA, c->factor.F(), c->factor.alpha(),
+                     (const double*)c->Xn.p, dseed, m0, v0, P, cand, dst, dnev);
+  SBO_HIP(hipGetLastError());
+  return SBO_OK;
+}
+
+static void refine_paths_clear(sbo_refine_paths_result* r) {
+  *r = sbo_refine_paths_result{};
+  for (int s = 0; s < SBO_MAX_PATHS; ++s) {
+    r->best[s] = -1;
+    r->best_value[s] = NAN;
+  }
+}
+
+// sbo_refine_paths behind its NULL / model / dtype checks: the options, the shared preparation of paths.hip (which also holds the list
+// seeds | candidates and the path's values there), the solver launch, the exact check, the best start per path
+static int refine_paths(sbo_ctx* c, const sbo_refine_paths_opts* opts, PathDraws& dr, const double* seeds, double* x_out, double* value_out,
+                        int32_t* status_out, sbo_refine_paths_result* result) {
+  const ModelConst& mc = c->mc;
+  const int d = mc.d, q = mc.q, S = opts->n_paths, K = opts->n_starts;
+  int rc;
+  if (K < 1 || K > SBO_REFINE_PATHS_MAX_STARTS) return fail(SBO_E_INVALID, "n_starts must be in [1, SBO_REFINE_PATHS_MAX_STARTS]");
+  if (opts->maximize != 0 && opts->maximize != 1) return fail(SBO_E_INVALID, "maximize must be 0 or 1");
+  if ((opts->constraint_mask & 1u) || (q < 32 && (opts->constraint_mask >> q) != 0))
+    return fail(SBO_E_INVALID, "constraint_mask: bit 0 must be clear and no bit may reach q");
+  if ((rc = refine_check(opts->b, opts->tol)) || (rc = refine_check_box(opts->lo, opts->hi, d)) || (rc = paths_check_draws(c, dr))) return rc;
+  if ((rc = model_reader_begin(c, "sbo_refine_paths", true))) return rc;
+  RefineArgs A{};
+  refine_fill(c, opts->tol, A);
+  A.max_eval = opts->max_eval > 0 ? std::min(opts->max_eval, refine_eval_cap(mc.n)) : kRefDefaultEval;
+  A.np = 1;
+  A.nz = d;
+  A.maximize = opts->maximize;
+  A.level_slot = A.link_slot = -1;
+  A.b = opts->b;
+  for (int o = 1; o < q; ++o)
+    if ((opts->constraint_mask >> o) & 1u) A.con_slots |= 1 << refine_slot(A, o);
+  for (int a = 0; a < d; ++a) {
+    A.lo[a] = opts->lo[a];
+    A.hi[a] = opts->hi[a];
+  }
+  const long long P = (long long)S * K;               // (<= 4096 workgroups)
+  // scratch: the arguments | mean0 var0 [q][P] | mean1 var1 [q][2 P] | x_out [P][d] | val [P] | status, evaluations [P]; the list
+  // seeds | candidates [3 P][d] and its path values [3 P][S] stand in the paths' own scratch
+  RefineArgs* dA;
+  double *m0, *v0, *m1, *v1, *dx, *dval;
+  int *dst, *dnev;
+  auto layout = [&](Carve cv) {
+    cv.take(dA, 1, 256);
+    cv.take(m0, q * (size_t)P, 256); cv.take(v0, q * (size_t)P);
+    cv.take(m1, 2 * q * (size_t)P); cv.take(v1, 2 * q * (size_t)P);
+    cv.take(dx, (size_t)P * d); cv.take(dval, P);
+    cv.take(dst, P); cv.take(dnev, P);
+    return cv.off;
+  };
+  if ((rc = carve(c->refbuf, layout))) return rc;
+  PathImage img{};
+  auto enqueue = [&]() -> int {
+    int r;
+    if ((r = paths_prepare_list(c, dr, 3 * P, &img))) return r;
+    double* cand = img.pts + (size_t)P * d;
+    SBO_HIP(hipMemcpyAsync(dA, &A, sizeof(RefineArgs), hipMemcpyHostToDevice, c->stream));
+    SBO_HIP(hipMemcpyAsync(img.pts, seeds, sizeof(double) * (size_t)P * d, hipMemcpyHostToDevice, c->stream));
+    if (A.nu && (r = launch_posterior_on_list(c, img.pts, P, m0, v0))) return r;
+    bool lds_tier;
+    const size_t lds = refine_lds_bytes(c, A.nu, 1, 0, lds_tier);
+    const int threads = refine_threads(mc.n);
+    const RefPathArgs PA{img.Bt, img.om, img.ph, img.F, img.output, K, 0};
+    r = lds_tier ? refine_path_launch<true>(c, lds, threads, P, dA, PA, img.pts, m0, v0, cand, dst, dnev)
+                 : refine_path_launch<false>(c, lds, threads, P, dA, PA, img.pts, m0, v0, cand, dst, dnev);
+    if (r) return r;
+    if (A.nu && (r = launch_posterior_on_list(c, cand, 2 * P, m1, v1))) return r;
+    if ((r = paths_eval_list(c, img))) return r;
+    hipLaunchKernelGGL(k_refine_path_accept, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, (const RefineArgs*)dA, P, K, S,
+                       (const double*)img.pts, (const double*)img.vals, (const double*)m0, (const double*)v0, (const double*)m1,
+                       (const double*)v1, dst, dx, dval);
+    SBO_HIP(hipGetLastError());
+    return SBO_OK;
+  };
+  std::vector<double> hz((size_t)P * d), hv(P);
+  std::vector<int> hs(2 * (size_t)P);
+  rc = enqueue();
+  hipError_t e = hipSuccess;
+  if (!rc) {
+    e = hipMemcpyAsync(hz.data(), dx, sizeof(double) * (size_t)P * d, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hv.data(), dval, sizeof(double) * P, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hs.data(), dst, sizeof(int) * 2 * (size_t)P, hipMemcpyDeviceToHost, c->stream);
+  }
+  const hipError_t ew = hipStreamSynchronize(c->stream);   // the one wait (nothing may still read the caller's arrays behind it)
+  if (rc) return rc;
+  SBO_HIP(e);
+  SBO_HIP(ew);
+  // per path the start whose returned point is best (ties: the lowest; infeasible seeds and NaN values never)
+  sbo_refine_paths_result res;
+  refine_paths_clear(&res);
+  const double sg = opts->maximize ? -1.0 : 1.0;
+  for (int s = 0; s < S; ++s) {
+    long long best = -1;
+    for (int k = 0; k < K; ++k) {
+      const size_t p = (size_t)s * K + k;
+      res.evaluations += hs[P + p];
+      if (hs[p] == SBO_REFINE_CONVERGED) ++res.converged;
+      if (hs[p] == SBO_REFINE_INFEASIBLE_SEED || std::isnan(hv[p])) continue;
+      if (best < 0 || sg * hv[p] < sg * hv[(size_t)s * K + best]) best = k;
+    }
+    res.best[s] = best;
+    if (best < 0) continue;
+    res.best_value[s] = hv[(size_t)s * K + best];
+    for (int a = 0; a < d; ++a) res.best_x[s][a] = hz[((size_t)s * K + best) * d + a];
+  }
+  *result = res;
+  if (x_out) std::copy(hz.begin(), hz.end(), x_out);
+  if (value_out) std::copy(hv.begin(), hv.end(), value_out);
+  if (status_out) std::copy(hs.begin(), hs.begin() + P, status_out);
   return SBO_OK;
 }
 
@@ -1314,6 +1617,17 @@ extern "C" int sbo_refine_robust(sbo_ctx* c, const sbo_refine_robust_opts* opts,
   if (!opts || !xc_seed || !result) return fail(SBO_E_INVALID, "NULL argument");
   if (const int rcm = model_reader_check(c, "sbo_refine_robust", true)) return rcm;
   return refine_robust(c, opts, xc_seed, scenarios_out, result);
+}
+
+extern "C" int sbo_refine_paths(sbo_ctx* c, const sbo_refine_paths_opts* opts, const double* omega, const double* phase, const double* weights,
+                                const double* noise, const double* seeds, double* x_out, double* value_out, int32_t* status_out,
+                                sbo_refine_paths_result* result) {
+  if (result) refine_paths_clear(result);
+  if (!c) return fail(SBO_E_INVALID, "ctx is NULL");
+  if (!opts || !omega || !phase || !weights || !noise || !seeds || !result) return fail(SBO_E_INVALID, "NULL argument");
+  if (const int rcm = model_reader_check(c, "sbo_refine_paths", true)) return rcm;
+  PathDraws dr{opts->output, opts->n_paths, opts->n_features, omega, phase, weights, noise, {}};
+  return refine_paths(c, opts, dr, seeds, x_out, value_out, status_out, result);
 }
 
 // the single-point case of the set problem: no level, no link, no unsafe_mask, and the constraints as its safe_mask

@@ -871,6 +871,72 @@ class SweepEngine:
     _paths_values = L.SBO_PATHS_MAX_VALUES           # bytes of values_out of one call
 
     @staticmethod
+    def refine_paths_arguments(d: int, q: int, n: int, b, seeds, output=0, features=1024, seed=0, draws=None, maximize=False,
+                               constraints=None, lo=None, hi=None, max_eval=None, tol=None):
+        """The checks of ``refine_paths`` that need no device: (seeds [S, K, d], b, output, features, seed, maximize as 0 | 1, draws
+        or None, constraint mask, lo [d], hi [d], max_eval, tol), or ValueError.  ``seeds`` [S, d] is K = 1; a seed may be
+        non-finite (the library reports it infeasible).  The draws, the output, the feature count and ``maximize`` are held to
+        ``path_arguments``; ``d`` / ``q`` / ``n`` < 1 (no model yet): what depends on them is the library's to check."""
+        sd = _f64(seeds)
+        if sd.ndim == 2:
+            sd = sd[:, None, :]
+        if sd.ndim != 3 or min(sd.shape) < 1 or (d >= 1 and sd.shape[2] != d):
+            raise ValueError("seeds must be [S, K, d] or [S, d] for the model's d")
+        S, K, dd = sd.shape
+        if K > L.SBO_REFINE_PATHS_MAX_STARTS:
+            raise ValueError(f"at most {L.SBO_REFINE_PATHS_MAX_STARTS} starts per path")
+        _, S, output, features, seed, maximize, draws = SweepEngine.path_arguments(d, q, n, np.zeros((1, dd)), S, output, features, seed,
+                                                                                   maximize, draws)
+        if isinstance(b, bool) or not isinstance(b, (int, float, np.integer, np.floating)) or not np.isfinite(b) or b < 0:
+            raise ValueError("b must be finite and >= 0")
+        mask = 0
+        for c in (range(1, max(q, 1)) if constraints is None else constraints):
+            if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 1 or c >= 32 or (q >= 1 and c >= q):
+                raise ValueError("constraints must be output indices in [1, q)")
+            mask |= 1 << int(c)
+        if lo is None or hi is None:
+            raise ValueError("refine_paths needs the box lo, hi")
+        lo, hi = _f64(lo).reshape(-1), _f64(hi).reshape(-1)
+        if lo.shape != (dd,) or hi.shape != (dd,):
+            raise ValueError("lo and hi must have shape [d]")
+        if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo <= hi)):
+            raise ValueError("the box needs finite lo <= hi")
+        if max_eval is not None and (isinstance(max_eval, bool) or not isinstance(max_eval, (int, np.integer))):
+            raise ValueError("max_eval must be an integer")
+        if tol is not None and np.isnan(tol):
+            raise ValueError("tol is NaN")
+        return (np.ascontiguousarray(sd), float(b), output, features, seed, maximize, draws, mask, lo, hi,
+                int(max_eval) if max_eval is not None else 0, float(tol) if tol is not None else 0.0)
+
+    def refine_paths(self, b: float, seeds, output: int = 0, features: int = 1024, seed: int = 0, draws=None, maximize: bool = False,
+                     constraints=None, *, lo, hi, max_eval: int | None = None, tol: float | None = None) -> dict:
+        """Sample-path optima off the grid (``sbo_refine_paths``): start k of path s, ``seeds`` [S, K, d] (or
+        [S, d]), moves to a local minimum (``maximize``: maximum) of path s of ``output`` -- the function ``sample_paths`` defines for
+        the same ``draws``, by default ``path_draws(d, n, S, features, seed)`` -- over the box [lo, hi] and lcb_c >= 0 under ``b``
+        (``constraints`` as in ``refine``: None = every constraint output, [] = the box only).  Every returned point is feasible
+        under the values ``bounds`` gives there; ``value`` is bit for bit the entry ``sample_paths`` returns at that point and no
+        worse than at the seed.  Returns ``x`` [S, K, d], ``value`` [S, K], ``status`` [S, K] (SBO_REFINE_*), per path ``best`` [S]
+        (the start, -1: none usable), ``best_x`` [S, d], ``best_value`` [S], and ``evaluations``, ``converged``.  fp64 models only;
+        nothing resident is touched."""
+        sd, b, output, F, seed, maximize, draws, mask, lo, hi, max_eval, tol = self.refine_paths_arguments(
+            self.d, self.q, self.n, b, seeds, output, features, seed, draws, maximize, constraints, lo, hi, max_eval, tol)
+        S, K, d = sd.shape
+        if draws is None:
+            draws = tuple(np.ascontiguousarray(a) for a in self.path_draws(d, max(self.n, 0), S, F, seed))
+        opts, res = L.RefinePathsOpts(), L.RefinePathsResult()
+        opts.b, opts.output, opts.n_paths, opts.n_features, opts.n_starts = b, output, S, F, K
+        opts.maximize, opts.constraint_mask, opts.max_eval, opts.tol = maximize, mask, max_eval, tol
+        for a in range(d):
+            opts.lo[a], opts.hi[a] = lo[a], hi[a]
+        x, val, st = np.empty((S, K, d)), np.empty((S, K)), np.empty((S, K), dtype=np.int32)
+        omega, phase, weights, noise = draws
+        L.check(self._lib.sbo_refine_paths(self._ctx, C.byref(opts), _ptr(omega), _ptr(phase), _ptr(weights), _ptr(noise), _ptr(sd),
+                                           _ptr(x), _ptr(val), _ptr(st), C.byref(res)))
+        return {"x": x, "value": val, "status": st, "best": np.array(res.best[:S], dtype=np.int64),
+                "best_x": np.array([list(res.best_x[s][:d]) for s in range(S)]), "best_value": np.array(res.best_value[:S]),
+                "evaluations": int(res.evaluations), "converged": int(res.converged)}
+
+    @staticmethod
     def joint_draws(m: int, n_draws: int, seed=0):
         """The randomness of ``posterior_joint`` in unit scale: ``z`` [S, m] standard normal from ``np.random.default_rng(seed)``."""
         return np.random.default_rng(seed).standard_normal((n_draws, m))
