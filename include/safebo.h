@@ -91,7 +91,10 @@ typedef struct sbo_sweep_opts {
                                       the tiles it proves safe throughout (k1_tiles_skipped_safe): there the set phase reads what the
                                       plan's first full evaluation stored, so any other writer of the resident posterior (another
                                       posterior kernel, sbo_posterior_run, a model / grid / option change) makes the next sweep of the
-                                      plan evaluate and record everything again.  A lean
+                                      plan evaluate and record everything again.  A later lean 2 sweep of a plan READS what an
+                                      earlier one stored (option "k1_resident"): the constraint's listed tiles and the objective's
+                                      tiles whose stored mean / var are the plan's are classified from memory, whatever b -- the
+                                      posterior does not depend on it (sbo_profile.k1_tiles_resident_c / _o).  A lean
                                       SafeOpt sweep of a model with constraints reports L[0] = 0: the objective's Lipschitz key is read by
                                       no sweep of the reference (its expanders use the constraints' keys, models/SafeOpt.py:110,
                                       models/GoOSE.py:100), and the interpolating posteriors then leave its gradient fields out.
@@ -224,6 +227,11 @@ typedef struct sbo_profile {
   /* ... and those it left unevaluated because the enclosures prove every candidate of the tile SAFE and outside the band (option
    * "k1_skip_safe"): every S bit, no U bit, the stored mean / var of the plan's recording sweep stand for the tile's values.          */
   int64_t k1_tiles_skipped_safe;
+  /* Option "k1_resident": posterior tiles the last sweep classified from the mean / var an earlier sweep of the plan stored, without
+   * running the GEMM phases again -- in the constraint's launch (the listed, evaluated tiles) and in the objective's (the tiles with a
+   * safe candidate whose stored values are the plan's).  Zero unless the sweep was a lean 2 sweep on the column path of a plan whose
+   * enclosures are recorded.                                                                                                        */
+  int64_t k1_tiles_resident_c, k1_tiles_resident_o;
   /* of guard_audit_samples: samples on tiles of either kind, where the audit checks the reference values against the tile's enclosure
    * (widened by the band) instead of the stored ones -- on a proved-safe tile also the stored values, which must lie inside the
    * enclosure bit for bit.  Cumulative, as guard_audit_samples.                                                                      */
@@ -893,6 +901,9 @@ int sbo_profile_get(sbo_ctx* ctx, sbo_profile* out);
  *                      evaluate, built per sweep (tiles left out are written by the lists' kernels); 0: one workgroup per tile (A/B checker)
  *   "k1_skip_safe"     1: lean-2 sweeps on that path also leave unevaluated the constraint tiles the plan's enclosures prove safe at this
  *                      sweep's b (sbo_profile.k1_tiles_skipped_safe); 0: only the tiles proved unsafe (A/B checker)
+ *   "k1_resident"      1: from a plan's second lean-2 sweep on that path on (k1_sched 1, enclosures recorded), the tiles whose stored mean /
+ *                      var are the plan's are classified from memory without their GEMM phases, and the constraint's Lipschitz rows come
+ *                      from the plan's record (sbo_profile.k1_tiles_resident_c / _o); 0: every sweep runs the GEMM phases (A/B checker)
  *   "col_overlap"      1: on that path the expander chain (distance transform, verdicts) runs on a second stream beside the objective's
  *                      posterior launch and the M part of the minimiser; 0: every kernel on the main stream
  *   "set_fuse"         1: 2-D grids of one rank share launches between independent set-phase kernels; 0: one launch per kernel

@@ -295,6 +295,7 @@ const OptRow kOptions[] = {
     OPT_RANGE(guard_audit_every, 1, 1 << 20, "guard_audit_every: 1 .. 1048576 sweeps", kOptNothing, hook_audit_every),
     OPT_RANGE(grad_defer, 0, 3, "grad_defer must be 0 .. 3", kOptInterp, nullptr),
     OPT_BOOL(k1_sched, kOptNothing, nullptr),
+    OPT_BOOL(k1_resident, kOptNothing, nullptr),        // (read per sweep: launch_posterior_gemm decides what it takes from memory)
     OPT_BOOL(k1_skip_safe, kOptNothing, nullptr),       // (read per sweep: the decision is taken at every sweep's b and band)
     OPT_BOOL(col_overlap, kOptNothing, nullptr),
     OPT_RANGE(col_queue, 64, 128, "col_queue must be within 64 .. 128 (the default)", kOptNothing, nullptr),

@@ -1591,7 +1591,9 @@ int bilinear_setup(sbo_ctx* c) {
   pl.ops = GemmOps();
   GemmOps& g = pl.ops;
   pl.encl_ready = false;
-  pl.bt_ready = false;       // (new tables below: stage 1 runs again with the plan's first launch)
+  pl.lrows_ready = false;
+  pl.omap_dirty = true;      // (a new plan: no tile of the objective holds its bits yet)
+  pl.bt_ready = false;      // (new tables below: stage 1 runs again with the plan's first launch)
   pl.setup_ms = 0.0;
   const auto t_begin = std::chrono::steady_clock::now();
   const bool timing = getenv("SBO_BL_TIMING") != nullptr;

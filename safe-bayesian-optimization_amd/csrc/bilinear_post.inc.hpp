@@ -630,9 +630,12 @@ __device__ __forceinline__ void wg_trace_row(int o, unsigned long long t0, unsig
 // may write them, and who drops the flags: BilinearPlan::encl_ready / vals_ready (internal.hpp).  The audit checks a sample on such a
 // tile both ways.
 __global__ __launch_bounds__(128) void k_bl_enclose(const double* __restrict__ mean, const double* __restrict__ var, long long cnt0,
-                                                    double* __restrict__ encl) {
+                                                    double* __restrict__ encl, const double* __restrict__ lrow1 /* the recording launch's
+                                                    rows of output 1 in the Lipschitz partials */, double* __restrict__ lrec /* nullptr, or
+                                                    where the plan keeps them (BilinearPlan::lrows_ready) */) {
   const int cell = threadIdx.x, cr = cell >> 4, cc = cell & 15;
   const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+  if (cell == 0 && lrec) lrec[tile] = lrow1[tile];
   const size_t base = ((size_t)blockIdx.y * 64 + (size_t)cr * 8) * (size_t)cnt0 + (size_t)blockIdx.x * 128 + (size_t)cc * 8;
   double mlo = 1e308, mhi = -1e308, vlo = 1e308, vhi = -1e308;
   bool fin = true;
@@ -692,9 +695,13 @@ __global__ __launch_bounds__(64 * kSchedWaves) void k_bl_sched_tiles1(const Mode
                                                          uint8_t* __restrict__ skip, unsigned int* __restrict__ list, int cap, unsigned long long* __restrict__ Sw,
                                                          unsigned long long* __restrict__ Uw, unsigned long long* __restrict__ Usum,
                                                          unsigned long long* __restrict__ slots, double* __restrict__ Lpart,
-                                                         unsigned long long* __restrict__ cpart, int pcap, int skip_safe /* option k1_skip_safe */) {
+                                                         unsigned long long* __restrict__ cpart, int pcap, int skip_safe /* option k1_skip_safe */,
+                                                         const double* __restrict__ lrec /* option k1_resident: nullptr, or the plan's rows of
+                                                         output 1 (BilinearPlan::lrows_ready) -- a tile's Lipschitz row comes from there and no
+                                                         tile is listed for its gradient phases: class 2 becomes 0, 5 becomes 4, 1 becomes 3 */,
+                                                         int count_res /* the listed tiles are classified from memory (k_bres<1>): counted */) {
   __shared__ unsigned long long sh_key[kSchedWaves];     // per wave: the Lipschitz key of a class-0 / class-4 tile (0: none)
-  __shared__ unsigned int sh_cnt[kSchedWaves];            // ... bit 0: a class-0 tile, bit 1: a tile proved unsafe (class 0 or 2), bit 2: a class-4 tile, bit 3: a tile proved safe (class 4 or 5)
+  __shared__ unsigned int sh_cnt[kSchedWaves];            // ... bit 0: a class-0 tile, bit 1: a tile proved unsafe (class 0 or 2), bit 2: a class-4 tile, bit 3: a tile proved safe (class 4 or 5), bit 4: a listed tile k_bres<1> classifies
   __shared__ unsigned long long sh_vmin[kSchedWaves], sh_rmax[kSchedWaves];   // ... a class-4 tile's variance / radius key (~0 / 0: none)
   const int lane = threadIdx.x & 63, wave = (int)(threadIdx.x >> 6), tile = (int)blockIdx.x * kSchedWaves + wave;
   unsigned long long my_key = 0ull, my_vmin = ~0ull, my_rmax = 0ull;
@@ -733,11 +740,11 @@ __global__ __launch_bounds__(64 * kSchedWaves) void k_bl_sched_tiles1(const Mode
       run3 = !(t1 + slack[3] < G1 * (1.0 - 1e-12));
       gfold = fmax(fabs(cg0 * t0), fabs(cg1 * t1));
     }
-    const bool grad = run2 || run3;
+    const bool grad = !lrec && (run2 || run3);             // (k1_resident: the row below holds what the gradient phases found)
     // (4 = proved safe, no gradient phase: no workgroup, written below; 5 = proved safe but runs gradient phases: listed like class 2)
     const unsigned int k = dec ? (grad ? 2u : 0u) : (sdec ? (grad ? 5u : 4u) : (grad ? 1u : 3u));
     if (lane == 0) skip[tile] = dec ? kSkipUnsafe : (sdec ? kSkipSafe : 0);
-    my_cnt = k == 0u ? 3u : (k == 2u ? 2u : (k == 4u ? 12u : (k == 5u ? 8u : 0u)));
+    my_cnt = k == 0u ? 3u : (k == 2u ? 2u : (k == 4u ? 12u : (k == 5u ? 8u : ((k == 3u && count_res) ? 16u : 0u))));
     if (k != 0u && k != 4u) {
       if (lane == 0) {
         // (p < cap whenever the counters started from zero; the test keeps a store inside the shard whatever they held)
@@ -764,7 +771,7 @@ __global__ __launch_bounds__(64 * kSchedWaves) void k_bl_sched_tiles1(const Mode
         Sw[w0 + h * 64 + lane] = ~0ull;
         Uw[w0 + h * 64 + lane] = 0ull;
       }
-      const double lrow = fmax(0.0, gfold);
+      const double lrow = lrec ? lrec[tile] : fmax(0.0, gfold);
       my_key = (unsigned long long)__double_as_longlong(lrow);
       my_vmin = kv < 1e300 ? ord_key(kv) : ~0ull;
       my_rmax = ku >= 0.0 ? ord_key(ku) : 0ull;
@@ -789,7 +796,7 @@ __global__ __launch_bounds__(64 * kSchedWaves) void k_bl_sched_tiles1(const Mode
         Uw[w0 + h * 64 + lane] = ~0ull;
         atomicOr(&Usum[(size_t)bx * 128 + h * 64 + lane], 1ull << by);      // (no return value: the wave does not wait for it)
       }
-      const double lrow = fmax(0.0, gfold);
+      const double lrow = lrec ? lrec[tile] : fmax(0.0, gfold);
       my_key = (unsigned long long)__double_as_longlong(lrow);               // (the key in post_partials' encoding)
       if (lane == 0) Lpart[((size_t)tgy + by) * tgx + bx] = lrow;
       // (post_partials' row of a tile with every candidate in U: no safe candidate, no decision in the band, no keys)
@@ -804,8 +811,8 @@ __global__ __launch_bounds__(64 * kSchedWaves) void k_bl_sched_tiles1(const Mode
   }
   if (lane == 0) { sh_key[wave] = my_key; sh_cnt[wave] = my_cnt; sh_vmin[wave] = my_vmin; sh_rmax[wave] = my_rmax; }
   __syncthreads();
-  if (threadIdx.x < 7) {
-    unsigned long long key = 0ull, n0 = 0ull, nskip = 0ull, n4 = 0ull, nsafe = 0ull, vmin = ~0ull, rmax = 0ull;
+  if (threadIdx.x < 8) {
+    unsigned long long key = 0ull, n0 = 0ull, nskip = 0ull, n4 = 0ull, nsafe = 0ull, nres = 0ull, vmin = ~0ull, rmax = 0ull;
 #pragma unroll
     for (int w = 0; w < kSchedWaves; ++w) {
       key = sh_key[w] > key ? sh_key[w] : key;
@@ -813,6 +820,7 @@ __global__ __launch_bounds__(64 * kSchedWaves) void k_bl_sched_tiles1(const Mode
       nskip += (sh_cnt[w] >> 1) & 1u;
       n4 += (sh_cnt[w] >> 2) & 1u;
       nsafe += (sh_cnt[w] >> 3) & 1u;
+      nres += (sh_cnt[w] >> 4) & 1u;
       vmin = sh_vmin[w] < vmin ? sh_vmin[w] : vmin;
       rmax = sh_rmax[w] > rmax ? sh_rmax[w] : rmax;
     }
@@ -824,6 +832,7 @@ __global__ __launch_bounds__(64 * kSchedWaves) void k_bl_sched_tiles1(const Mode
     if (threadIdx.x == 4 && nsafe) atomicAdd(&slots[(size_t)kSlotSkipSafe * kColSlots + slot], nsafe);
     if (threadIdx.x == 5 && vmin != ~0ull) atomicMin(&slots[(size_t)kSlotVmin1 * kColSlots + slot], vmin);
     if (threadIdx.x == 6 && rmax != 0ull) atomicMax(&slots[(size_t)kSlotRmax1 * kColSlots + slot], rmax);
+    if (threadIdx.x == 7 && nres) atomicAdd(&slots[(size_t)kSlotResC * kColSlots + slot], nres);
   }
 }
 
@@ -858,11 +867,16 @@ __device__ __forceinline__ unsigned int sched_rank3(int k, unsigned int (&base)[
 
 // The objective's list (one workgroup, behind the constraint's launch): the tiles that hold a safe candidate (field 1 of the
 // constraint's partial rows), in tile order.  The others' objective rows as their workgroups wrote them in a lean-2 sweep (no safe
-// candidate, no gradient phase): no u* key, no range of lcb_0, no variance key, Lipschitz row 0.  One shard, one end: [1] = 0.
+// candidate, no gradient phase): no u* key, no range of lcb_0, no variance key, Lipschitz row 0.  One shard; without `omap` one end: [1] = 0.
+// With it (option k1_resident) the tiles whose residency byte stands fill the back, and their count joins slot 0 of kSlotResO.
 // It also resets the counters of the constraint's list (`head1`), which is dead by now -- the constraint's launch, its only reader,
 // has finished on this stream --, for the next sweep's k_bl_sched_tiles1.
 __global__ __launch_bounds__(1024) void k_bl_sched_list2(unsigned long long* __restrict__ cpart, int pcap, int ntiles, unsigned int* __restrict__ list,
-                                                         double* __restrict__ Lpart0, unsigned int* __restrict__ head1) {
+                                                         double* __restrict__ Lpart0, unsigned int* __restrict__ head1,
+                                                         const uint8_t* __restrict__ omap /* option k1_resident: nullptr, or the plan's residency
+                                                         bytes -- the list is split by them, the tiles whose byte stands fill the back downwards
+                                                         (k_bres<2> reads their stored mean / var), the others the front (k_bpost<1, 2>) */,
+                                                         unsigned long long* __restrict__ slots) {
   __shared__ unsigned int sh[3 * 16];
   const int t = threadIdx.x;
   const unsigned long long* nS = cpart + (size_t)1 * pcap;
@@ -870,10 +884,10 @@ __global__ __launch_bounds__(1024) void k_bl_sched_list2(unsigned long long* __r
   unsigned int base[3] = {0u, 0u, 0u};
   for (int r = 0; r * 1024 < ntiles; ++r) {
     const int i = r * 1024 + t;
-    const bool in = i < ntiles, has = in && nS[i] != 0ull;
-    const unsigned int p = sched_rank3(has ? 0 : -1, base, sh);
+    const bool in = i < ntiles, has = in && nS[i] != 0ull, res = has && omap && omap[i] != 0;
+    const unsigned int p = sched_rank3(has ? (res ? 1 : 0) : -1, base, sh);
     if (has) {
-      list[kTlistHead + p] = (unsigned int)i;
+      list[kTlistHead + (res ? (unsigned int)(ntiles - 1) - p : p)] = (unsigned int)i;
     } else if (in) {
       Lpart0[i] = 0.0;
 #pragma unroll
@@ -883,7 +897,8 @@ __global__ __launch_bounds__(1024) void k_bl_sched_list2(unsigned long long* __r
   }
   if (t == 0) {
     list[0] = base[0];
-    list[1] = 0u;
+    list[1] = base[1];
+    if (base[1]) atomicAdd(&slots[(size_t)kSlotResO * kColSlots], (unsigned long long)base[1]);
   }
   if (t < kTlistShards) head1[t * kTlistHead] = head1[t * kTlistHead + 1] = 0u;
 }
@@ -919,10 +934,11 @@ __global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelCon
     // (shard i mod 2^tshift, entry i >> tshift of it: the front entries upwards, then the back entries from the last one down --
     // k_bl_sched_tiles1)
     const unsigned int sh = blockIdx.x & ((1u << px.tshift) - 1u), at = blockIdx.x >> px.tshift;
-    const unsigned int nfront = px.tlist[sh * kTlistHead], nback = px.tlist[sh * kTlistHead + 1];
+    const unsigned int nfront = px.tlist[sh * kTlistHead], nback = px.front_only ? 0u : px.tlist[sh * kTlistHead + 1];
     if (at >= nfront + nback) {
 #ifdef SBO_PHASE_CLOCKS
-      if (threadIdx.x == 0) { const unsigned long long t_ = wall_clock64(); wg_trace_row(o, t_, t_, t_, 0xffffffu, 3u); }
+      // (front_only: the rows of this dispatch index belong to k_bres<2>, which ran first)
+      if (threadIdx.x == 0 && !px.front_only) { const unsigned long long t_ = wall_clock64(); wg_trace_row(o, t_, t_, t_, 0xffffffu, 3u); }
 #endif
       return;                                   // (past the list: the tile was written by the list's kernels)
     }
@@ -1066,6 +1082,8 @@ __global__ __launch_bounds__(256, (RB == 2 ? 2 : 3)) void k_bpost(const ModelCon
     }
   }
   const bool skip_tile = (ROLE == 2 && obits && tile_nS == 0ull && px.lean >= 2) || cskip || csafe;
+  // (k1_resident: this workgroup stores the objective's mean / var of its tile -- the plan's bits: a later sweep may read them, k_bres<2>)
+  if (ROLE == 2 && obits && px.omap != nullptr && !cx.skip_store && cx.tid == 0) px.omap[ctile] = 1;
   if (!skip_tile)
     post_phase<0, RB, ROLE>(cx, BtA + (size_t)o * sBtA, P0f + (size_t)o * sP0f, KB0, eff ? eff[4 * o * es] : KS0, vo, sf2, ystd * ystd, 0.0, gmax, acc, xn0, pre,
                             VAo, SBo, KBm);
@@ -1153,6 +1171,137 @@ extern "C" int sbo_debug_wg_trace(unsigned long long* out /* [2][rows][8] */, in
   return 0;
 }
 #endif
+
+// Option k1_resident: the listed tiles of a lean-2 column-path launch classified from the mean / var an earlier launch of the plan
+// stored -- k_bpost's epilogue without its GEMM phases.  ROLE 1, the constraint (BilinearPlan::vals_ready stands: its regions hold the
+// plan's bits on every tile, which are the bits phases 0 / 1 would compute again -- invariant 1 at k_bl_enclose): post_classify_row on
+// the stored values, words, Usum, partial row and slots as k_bpost writes them; the tile's Lipschitz row is the plan's (`lrec`,
+// BilinearPlan::lrows_ready).  ROLE 2, the objective (the back entries of its list: tiles whose residency byte stands): post_objective
+// over the S bits of the constraint's words, u*, the range of lcb_0 and the variance key into the objective's partial row and slots; its
+// Lipschitz row is 0 as in every lean launch.  Nothing is stored to mean / var.
+// The thread <-> candidate mapping is the accumulators' (row 16 wave + 4 t + (lane >> 4), column 16 s2 + (lane & 15)), so the bit
+// pieces and the partials are assembled by the same code; every merge is an integer add, an OR, or a min / max of ordered keys, and
+// b and the band enter here exactly as they enter the epilogue: the results are k_bpost's bit for bit.  All 64 values of a thread are
+// requested before the first is used: there are no accumulators to hold.
+template <int ROLE>
+__global__ __launch_bounds__(256) void k_bres(const CandSpec cs, const double* __restrict__ mean, const double* __restrict__ var,
+                                              double* __restrict__ Lpart, double bconf, unsigned long long* __restrict__ cpart, int pcap,
+                                              const GuardBand* __restrict__ gb, const double* __restrict__ lrec, const PostExtra px) {
+  __shared__ double sh[4 * 6];
+  __shared__ unsigned int bits[4 * 128];
+  const int o = px.o0;
+  // (the entry of workgroup i: k_bpost's rule; the objective's light launch takes the back entries alone)
+  const unsigned int shd = blockIdx.x & ((1u << px.tshift) - 1u), at = blockIdx.x >> px.tshift;
+  const unsigned int nfront = ROLE == 2 ? 0u : px.tlist[shd * kTlistHead], nback = px.tlist[shd * kTlistHead + 1];
+#ifdef SBO_PHASE_CLOCKS
+  const unsigned long long clk_in_ = wall_clock64();      // (g_wg_trace: kind 4 = classified from memory, [1] = the loads have arrived)
+  unsigned long long clk_ld_ = clk_in_;
+#endif
+  if (at >= nfront + nback) {
+#ifdef SBO_PHASE_CLOCKS
+    if (threadIdx.x == 0) wg_trace_row(o, clk_in_, clk_in_, clk_in_, 0xffffffu, 3u);
+#endif
+    return;
+  }
+  const unsigned int ent = px.tlist[(kTlistHead << px.tshift) + shd * (unsigned int)px.tcap + (at < nfront ? at : (unsigned int)px.tcap - 1u - (at - nfront))];
+  const unsigned int tgx = (unsigned int)px.tgx, tgy = (unsigned int)px.tgy;
+  const unsigned int bx = (ent & 0xffffffu) % tgx, by = (ent & 0xffffffu) / tgx;
+  const size_t ctile = (size_t)by * tgx + bx, ntile = (size_t)tgx * tgy;
+  PostCtx cx;
+  cx.lds = sh;
+  cx.tid = threadIdx.x; cx.lane = cx.tid & 63; cx.wave = cx.tid >> 6;
+  cx.rb0 = by * 4; cx.cs0 = bx * 8;
+  cx.ucnt0 = (unsigned int)cs.count[0];
+  cx.var_rd = nullptr; cx.S = nullptr; cx.U = nullptr;
+  cx.bconf = bconf;
+  cx.bb = bconf * bconf;
+  cx.cS = cx.cU = cx.cB = 0;
+  cx.rmax = -1.0;
+  cx.role = ROLE;
+  cx.lds_bits = bits;
+  cx.umin = 1e300;
+  cx.xmin = 1e300;
+  cx.vminS = 1e300;
+  cx.skip_store = true;
+#pragma unroll
+  for (int s2 = 0; s2 < 8; ++s2) cx.bw[s2] = 0u;
+  cx.gb_on = ROLE == 1 && gb != nullptr;
+  cx.lband = cx.gb_on ? lcb_band(cx.bb, gb->dm[1], gb->dv[1]) : LcbBand{0.0, 0.0};
+  const unsigned int col_in = cx.lane & 15, row_in = cx.lane >> 4;
+  const double* const mo = mean + (size_t)o * cs.n_local;
+  const double* const vo = var + (size_t)o * cs.n_local;
+  double mv[4][8], vr[4][8];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const unsigned int line = (unsigned int)(cx.rb0 + cx.wave) * 16u + 4u * t + row_in;
+    const size_t g0 = (size_t)line * cx.ucnt0 + (unsigned int)cx.cs0 * 16u + col_in;
+#pragma unroll
+    for (int s2 = 0; s2 < 8; ++s2) {
+      mv[t][s2] = mo[g0 + s2 * 16];
+      vr[t][s2] = vo[g0 + s2 * 16];
+    }
+  }
+  if (ROLE == 2) {
+    // the thread's own S bits: rows 16 wave + 4 t + (lane >> 4) of the segment, column (cs0 + s2) 16 + (lane & 15)
+#pragma unroll
+    for (int s2 = 0; s2 < 8; ++s2) {
+      const unsigned long long w = px.cb.Sw[(size_t)by * cx.ucnt0 + (unsigned int)(cx.cs0 + s2) * 16u + col_in];
+      cx.bw[s2] = (unsigned int)(w >> (16 * cx.wave + (int)row_in)) & 0x1111u;
+    }
+  }
+#ifdef SBO_PHASE_CLOCKS
+  {
+    double sum_ = 0.0;                                    // (a use of every value: the clock below is read behind the loads)
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int s2 = 0; s2 < 8; ++s2) sum_ += mv[t][s2] + vr[t][s2];
+    if (__syncthreads_or(sum_ == 0x1p-1070 ? 1 : 0) == 0) clk_ld_ = wall_clock64();
+  }
+#endif
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    if (ROLE == 1) {
+      post_classify_row(cx, 4u * t + row_in, mv[t], vr[t]);
+    } else {
+#pragma unroll
+      for (int s2 = 0; s2 < 8; ++s2) post_objective(cx, ((cx.bw[s2] >> (4 * t)) & 1u) != 0u, mv[t][s2], vr[t][s2]);
+    }
+  }
+  if (ROLE == 1) {
+    // (|S| / |U| and the wave's 16-row pieces of every column: as the epilogue of k_bpost<1, 1>)
+#pragma unroll
+    for (int s2 = 0; s2 < 8; ++s2) { cx.cS += __popc(cx.bw[s2] & 0xffffu); cx.cU += __popc(cx.bw[s2] >> 16); }
+#pragma unroll
+    for (int s2 = 0; s2 < 8; ++s2) {
+      unsigned int w = cx.bw[s2];
+      w |= (unsigned int)__shfl_xor((int)w, 16);
+      w |= (unsigned int)__shfl_xor((int)w, 32);
+      if (cx.lane < 16) bits[cx.wave * 128 + s2 * 16 + cx.lane] = w;
+    }
+  }
+  const double gmax = ROLE == 1 ? lrec[ctile] : 0.0;
+  post_partials<4>(sh, cx.lane, cx.wave, gmax, ROLE == 1, cx.cS, cx.cU, ROLE == 2 ? -cx.umin : cx.rmax, cx.cB, cx.vminS,
+                   Lpart + ((size_t)o * tgy + by) * tgx + bx, cpart + (ROLE == 2 ? ntile : (size_t)0) + ctile, pcap, ROLE == 2, px.cb.slots,
+                   (int)(ctile & (kColSlots - 1)), o, ROLE == 1 ? (int)by : -1, (int)bx, cx.xmin, false);
+  if (ROLE == 1 && cx.tid < 128) {
+    unsigned long long sw = 0ull, uw = 0ull;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const unsigned int pc = bits[w * 128 + cx.tid];
+      sw |= (unsigned long long)(pc & 0xffffu) << (16 * w);
+      uw |= (unsigned long long)(pc >> 16) << (16 * w);
+    }
+    const size_t col = (size_t)cx.cs0 * 16u + cx.tid;
+    px.cb.Sw[(size_t)by * cx.ucnt0 + col] = sw;
+    px.cb.Uw[(size_t)by * cx.ucnt0 + col] = uw;
+    if (uw != 0ull) atomicOr(&px.cb.Usum[col], 1ull << by);
+  }
+#ifdef SBO_PHASE_CLOCKS
+  __syncthreads();
+  if (threadIdx.x == 0) wg_trace_row(o, clk_in_, clk_ld_, wall_clock64(), (unsigned int)ctile, 4u);
+#endif
+}
 
 
 // K1i's deferred gradient launch (r05): the two gradient series of every output on the tiles the gate names, nothing else -- on
@@ -1273,6 +1422,11 @@ struct GemmLaunch {
   PostExtra px;
   double* encl = nullptr;                     // column path, K1b: the plan's enclosures; this launch records them | a lean-2 launch uses them (px.encl)
   bool record_encl = false;
+  // option k1_resident (BilinearPlan::lrows_ready / omap_dirty; sbo_ctx::bl_res)
+  double* lrec = nullptr;                     // the plan's rows of output 1: recorded with the enclosures | read by k_bl_sched_tiles1 and k_bres<1> (res_rows)
+  uint8_t* omap = nullptr;                    // the objective's residency bytes; nullptr: the option is off
+  bool res_rows = false;                      // k_bl_sched_tiles1 takes the Lipschitz rows from lrec and lists no tile for its gradient phases
+  bool res_c = false, res_o = false;          // the constraint's listed tiles go to k_bres<1> | the objective's list is split, its back goes to k_bres<2>
   unsigned int *sched_l1 = nullptr, *sched_l2 = nullptr;      // the tile lists of the constraint's launch (kTlistShards shards of sched_cap1) and the objective's
   int sched_cap1 = 0;
   const GuardBand* gb_fused = nullptr;        // the fused classification counts its sign tests inside the plan's guard band
@@ -1407,6 +1561,38 @@ static int col_tile_lists(GemmLaunch& L) {
   return SBO_OK;
 }
 
+// Option k1_resident: what this launch takes from memory, and the plan's record of it (sbo_ctx::bl_res: the rows of output 1, the
+// objective's residency bytes).  The rows are recorded with the enclosures whatever the option says -- one store per tile and plan --, so
+// that switching it on finds them.  It takes effect on the path that has lists: K1b, lean 2, k1_sched, enclosures recorded.  The bytes
+// are kept only while the option is on: a launch without the map rewrites the plan's bits, so bytes that stand stay true, but the tiles
+// it stores for the first time go unrecorded -- the map starts again when the option comes back.
+static int col_resident(GemmLaunch& L) {
+  sbo_ctx* c = L.c;
+  const size_t rbytes = sizeof(double) * L.ntiles;
+  const void* was = c->bl_res.p;
+  if (int rc = ensure(c->bl_res, rbytes + L.ntiles)) return rc;
+  if (c->bl_res.p != was) {
+    c->bl.lrows_ready = false;
+    c->bl.omap_dirty = true;
+  }
+  L.lrec = (double*)c->bl_res.p;
+  if (!c->opt.k1_resident) {
+    c->bl.omap_dirty = true;
+    return SBO_OK;
+  }
+  const bool on = L.sched_l1 != nullptr && L.sched_l2 != nullptr && L.px.encl != nullptr;
+  L.res_rows = on && c->bl.lrows_ready;
+  L.res_c = L.res_rows && c->bl.vals_ready;
+  L.res_o = on;
+  L.omap = (uint8_t*)c->bl_res.p + rbytes;
+  if (c->bl.omap_dirty) {
+    SBO_HIP(hipMemsetAsync(L.omap, 0, L.ntiles, c->stream));
+    c->bl.omap_dirty = false;
+  }
+  L.px.omap = L.omap;
+  return SBO_OK;
+}
+
 // K1i's deferred gradient launch: the gradient phases alone, behind the gate on stream3 and behind stage 1 (its images): one launch for all outputs
 static int gemm_grad_deferred(GemmLaunch& L) {
   sbo_ctx* c = L.c;
@@ -1444,14 +1630,15 @@ static void gemm_post_part(GemmLaunch& L, int part) {
   if (L.sched_l1 && part == 0 && px.encl) {
     hipLaunchKernelGGL(k_bl_sched_tiles1, dim3((L.gx * L.gy + kSchedWaves - 1) / kSchedWaves), dim3(64 * kSchedWaves), 0, c->stream, c->mc, (const double*)px.encl, (int)(L.gx * L.gy), (int)L.gx,
                        (int)L.gy, (unsigned int)L.cnt0, L.req.fuse_b, L.gb_fused, g.gtmax, g.gkey, q, px.skip, L.sched_l1, L.sched_cap1, px.cb.Sw, px.cb.Uw,
-                       px.cb.Usum, px.cb.slots, L.lrows, rows.base, rows.cap, px.skip_safe);
+                       px.cb.Usum, px.cb.slots, L.lrows, rows.base, rows.cap, px.skip_safe, L.res_rows ? (const double*)L.lrec : (const double*)nullptr,
+                       L.res_c ? 1 : 0);
     px.tlist = L.sched_l1;
     px.tshift = kTlistShift;
     px.tcap = L.sched_cap1;
   }
   if (L.sched_l2 && part == 1) {
     hipLaunchKernelGGL(k_bl_sched_list2, dim3(1), dim3(1024), 0, c->stream, rows.base, rows.cap, (int)(L.gx * L.gy), L.sched_l2,
-                       L.lrows, L.sched_l1);
+                       L.lrows, L.sched_l1, L.res_o ? (const uint8_t*)L.omap : (const uint8_t*)nullptr, px.cb.slots);
     px.tlist = L.sched_l2;
     px.tshift = 0;
     px.tcap = (int)(L.gx * L.gy);
@@ -1460,18 +1647,35 @@ static void gemm_post_part(GemmLaunch& L, int part) {
   px.tgx = (int)L.gx;
   px.tgy = (int)L.gy;
   const dim3 grid = px.tlist ? dim3((unsigned)px.tcap << px.tshift) : dim3(L.gx, L.gy, (unsigned)(colw ? 1 : q));
-  hipExtLaunchKernelGGL(kpost, grid, dim3(256), L.lds, c->stream, nullptr,
-                        (L.req.lmax_defer && last) ? c->ev[1] : ((colw && part == 0) ? c->col.ev[0] : nullptr), 0,
-                        c->mc, cs, g.BtA, g.sBtA, g.P0f, g.sP0f, g.VA, g.sVA, g.SBf, g.sSBf, g.KB0, g.KS0, g.KBm, g.KSm, g.KBm2, g.nrb, g.ncs0,
-                        L.nlines, (double*)c->mean.p, (double*)c->var.p, L.defer ? L.lrows + (size_t)L.rows_out * q : L.lrows,
-                        (const double*)c->bl_small.p /* xn0 */, fuse ? (uint8_t*)(q > 2 ? c->fuseS.p : c->maskS.p) : (uint8_t*)nullptr,
-                        fuse ? (uint8_t*)(q > 2 ? c->fuseU.p : c->maskU.p) : (uint8_t*)nullptr, L.req.fuse_b, (unsigned long long*)c->cpart.p,
-                        c->cpart_cap, L.gb_fused, (const int*)g.eff, g.gtmax, g.gkey, g.imode, px);
+  // option k1_resident.  The constraint's listed tiles from memory: k_bres<1> in place of k_bpost<1, 1>, with its fork event.  The
+  // objective's: k_bres<2> over the back of its list first, then k_bpost<1, 2> over the front (empty when nothing changed since the
+  // last sweep: its workgroups exit at once), which carries the stop event as before.
+  px.front_only = 0;
+  const bool light_c = L.res_c && part == 0 && px.tlist != nullptr, light_o = L.res_o && part == 1 && px.tlist != nullptr;
+  if (light_c) {
+    hipExtLaunchKernelGGL(k_bres<1>, grid, dim3(256), 0, c->stream, nullptr, c->col.ev[0], 0, cs, (const double*)c->mean.p, (const double*)c->var.p,
+                          L.lrows, L.req.fuse_b, (unsigned long long*)c->cpart.p, c->cpart_cap, L.gb_fused, (const double*)L.lrec, px);
+  }
+  if (light_o) {
+    hipLaunchKernelGGL(k_bres<2>, grid, dim3(256), 0, c->stream, cs, (const double*)c->mean.p, (const double*)c->var.p, L.lrows, L.req.fuse_b,
+                       (unsigned long long*)c->cpart.p, c->cpart_cap, (const GuardBand*)nullptr, (const double*)nullptr, px);
+    px.front_only = 1;
+  }
+  if (!light_c) {
+    hipExtLaunchKernelGGL(kpost, grid, dim3(256), L.lds, c->stream, nullptr,
+                          (L.req.lmax_defer && last) ? c->ev[1] : ((colw && part == 0) ? c->col.ev[0] : nullptr), 0,
+                          c->mc, cs, g.BtA, g.sBtA, g.P0f, g.sP0f, g.VA, g.sVA, g.SBf, g.sSBf, g.KB0, g.KS0, g.KBm, g.KSm, g.KBm2, g.nrb, g.ncs0,
+                          L.nlines, (double*)c->mean.p, (double*)c->var.p, L.defer ? L.lrows + (size_t)L.rows_out * q : L.lrows,
+                          (const double*)c->bl_small.p /* xn0 */, fuse ? (uint8_t*)(q > 2 ? c->fuseS.p : c->maskS.p) : (uint8_t*)nullptr,
+                          fuse ? (uint8_t*)(q > 2 ? c->fuseU.p : c->maskU.p) : (uint8_t*)nullptr, L.req.fuse_b, (unsigned long long*)c->cpart.p,
+                          c->cpart_cap, L.gb_fused, (const int*)g.eff, g.gtmax, g.gkey, g.imode, px);
+  }
   if (colw && part == 0 && L.record_encl) {
     // (the plan's first constraint launch evaluated and stored every tile: its enclosures, ~270 MB read once per plan)
     hipLaunchKernelGGL(k_bl_enclose, dim3(L.gx, L.gy), dim3(128), 0, c->stream, (const double*)c->mean.p + (size_t)cs.n_local,
-                       (const double*)c->var.p + (size_t)cs.n_local, L.cnt0, L.encl);
+                       (const double*)c->var.p + (size_t)cs.n_local, L.cnt0, L.encl, (const double*)L.lrows + L.ntiles, L.lrec);
     c->bl.encl_ready = true;
+    c->bl.lrows_ready = L.lrec != nullptr;
   }
   // (a constraint's launch without a skip list evaluated and stored every tile: the stored values are the plan's again)
   if (colw && part == 0 && !L.interp && c->bl.encl_ready && !px.encl) c->bl.vals_ready = true;
@@ -1493,6 +1697,8 @@ static void gemm_flops(const GemmLaunch& L) {
   // flops issued on the matrix cores: stage 1 (when this launch ran it) + the four phases of stage 2 (KS0 + 3 KSm k-steps: the axis-0 gradient phase
   // runs on the mean phase's sums; 16 x 16 x 4 steps, 2 flops per multiply-add)
   c->last_k1_flops = (double)q * 2.0 * 1024.0 * (s1 * 4.0 * (double)g.nrb * g.KB0 * g.KB1 + tiles2 * (g.KS0 + 3 * g.KSm));
+  // (a 64 x 128 tile is 32 of the 16 x 16 blocks tiles2 counts: what sets.hip takes off for a tile classified from memory)
+  for (int o = 0; o < 2; ++o) c->last_k1_tile_flops[o] = 32.0 * 2.0 * 1024.0 * (g.KS0 + 3 * g.KSm);
   // Chebyshev core: the counts the kernels actually run to (k_cheb_trunc; copied to the pinned block when the plan was built --
   // they have arrived long before a sweep's result is read: a plan build is followed by the sweep's own synchronisation
   // before anyone asks for the profile).  Until then the upper bound above stands.
@@ -1503,6 +1709,7 @@ static void gemm_flops(const GemmLaunch& L) {
     if (ks < 1 || ks > g.KS0 || kb0 < 1 || kb0 > g.KB0 || kb1 < 1 || kb1 > g.KB1) return;
     // (the gradient phases run on the few tiles that can hold the maximum: not counted)
     f += 2.0 * 1024.0 * (s1 * 4.0 * (double)g.nrb * kb0 * kb1 + tiles2 * (ks + (g.gtmax ? 1 : 3) * g.KSm));
+    if (o < 2) c->last_k1_tile_flops[o] = 32.0 * 2.0 * 1024.0 * (ks + (g.gtmax ? 1 : 3) * g.KSm);
   }
   c->last_k1_flops = f;
 }
@@ -1532,6 +1739,7 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
     L.fuse = false;                    // (no byte masks: the words are the classification)
     if (!interp && (rc = col_enclosures(L))) return rc;
     if ((rc = col_tile_lists(L))) return rc;
+    if (!interp && (rc = col_resident(L))) return rc;
   }
   // (K1b's byte-mask launch stores the plan's values through another epilogue: not relied on -- BilinearPlan::encl_ready)
   if (!interp && !L.colw) post_regions_written(c);

@@ -189,7 +189,9 @@ enum ColSlotField { kSlotUmin = 0 /* min key of ucb_0 over S */, kSlotS, kSlotU,
                     kSlotRmax1 /* max key */, kSlotL0, kSlotL1 /* max of the gradient norms' bit patterns */,
                     kSlotRowMask /* word s: bit t set iff tile t of tile row s holds a safe candidate */,
                     kSlotSkip /* count: constraint tiles its enclosure proved unsafe, left unevaluated (r06) */,
-                    kSlotSkipSafe /* count: constraint tiles its enclosure proved safe, left unevaluated (option k1_skip_safe) */, kColSlotFields };
+                    kSlotSkipSafe /* count: constraint tiles its enclosure proved safe, left unevaluated (option k1_skip_safe) */,
+                    kSlotResC, kSlotResO /* counts: constraint / objective tiles classified from their stored mean / var (option k1_resident) */,
+                    kColSlotFields };
 __host__ __device__ inline bool col_slot_is_min(int f) { return f == kSlotUmin || f == kSlotVmin0 || f == kSlotVmin1; }
 constexpr unsigned int kTlistUnsafe = 0x80000000u, kTlistSafe = 0x40000000u;          // flag bits of a tile-list entry (the tile: ent & 0xffffff)
 constexpr unsigned char kSkipUnsafe = 1, kSkipSafe = 2;                                  // a tile's skip byte (bl_encl, behind the enclosures): 0 = evaluated
@@ -216,6 +218,11 @@ struct PostExtra {
   const unsigned int* tlist;
   int tshift, tcap;
   int tgx, tgy;  // the tile grid (tiles per row, tile rows) behind the list
+  // option k1_resident (BilinearPlan::lrows_ready / omap_dirty).  front_only: the launch takes the front entries of its list alone -- the
+  // back ones belong to the light launch (k_bres).  omap: nullptr, or the plan's residency bytes of the objective's tiles: a workgroup of
+  // the objective's launch that stores its tile raises the tile's byte.
+  int front_only;
+  uint8_t* omap;
 };
 
 // The operands of the GEMM posterior -- stage 1 (k_bstage1) and k_bpost -- as the plan that made them lays them out (K1b:
@@ -263,6 +270,17 @@ struct BilinearPlan {
   // plan rebuild.  Whoever adds a writer of sbo_ctx::mean / var must call post_regions_written (or post_values_patched).
   bool encl_ready = false;
   bool vals_ready = false;
+  // Option k1_resident: what a later sweep of the plan takes from memory instead of running the GEMM phases again (sbo_ctx::bl_res).
+  // INVARIANT (the constraint's values): vals_ready, above -- k_bres<1> classifies a listed tile from its stored mean / var.
+  // INVARIANT (lrows_ready): bl_res holds, per tile, the row of output 1 the plan's recording launch wrote into the Lipschitz partials
+  // (the maximum of the tile's gradient phases and its coarse samples: operands, gate and k-order are the plan's, b and the band do not
+  // enter).  Recorded by k_bl_enclose behind that launch; raised where encl_ready is raised and dropped wherever encl_ready is dropped.
+  // INVARIANT (the residency bytes, bl_res behind the rows): a tile's byte stands only if the OBJECTIVE's mean / var of that tile hold the
+  // bits a column-path launch of this plan stored, and nothing has written that region since.  Raised by the workgroups of k_bpost<1, 2>
+  // that store their tile; omap_dirty says that the bytes must be cleared before the next column-path launch reads or raises one: a new
+  // plan starts with it (bilinear_setup), post_regions_written and post_values_patched set it, a new buffer has it.
+  bool lrows_ready = false;
+  bool omap_dirty = true;
   // bl_BtA holds stage 1's images of THIS plan (k_bstage1 has been enqueued on its operands): launch_posterior_gemm runs stage 1 for
   // the plan's first launch only.  INVARIANT: stage 1 reads bl_P1A, bl_T4f and the counts `ops.eff` (in bl_cheb) and writes bl_BtA;
   // all four are written by the two plan builders and by nothing else -- bilinear_setup (k_cheb_tab<0>, k_cheb_t4f, k_cheb_trunc)
@@ -531,6 +549,7 @@ struct sbo_ctx {
     int lipschitz_lds = 1;  // (A/B checker): 1 sbo_lipschitz stages X_norm and the output's alpha in LDS when they fit, 0 it always streams them
     int list_index = -1;  // -1 the index for explicit lists above the exhaustive cap only, 0 never, 1 always
     int k1_sched = 1;             // 1 = K1b's two lean-2 column-path launches take their tiles from per-sweep lists; 0: one workgroup per tile
+    int k1_resident = 1;          // 1 = the second and later lean-2 column-path sweeps of a plan classify from the stored mean / var (k_bres); 0: every sweep runs the GEMM phases
     int k1_skip_safe = 1;         // 1 = a lean-2 column-path sweep leaves the constraint tiles its enclosures prove SAFE unevaluated too; 0: the unsafe ones only
     int comm_events = 0;     // an event pair per collective (MultiRank::comm_ev) whose elapsed times sbo_profile.comm_ms sums
     int col_path = 1;        // 0 = never
@@ -592,6 +611,7 @@ struct sbo_ctx {
   sbo::DevBuf bl_grad;  // K1b: which tiles run the gradient phases (per plan)
   sbo::DevBuf bl_lpart; // K1b: per-wave Lipschitz partials of k_bpost
   sbo::DevBuf bl_encl;  // K1b column path: per-cell enclosures of the constraint's posterior (per plan) + a skip byte per tile (per sweep)
+  sbo::DevBuf bl_res;   // K1b column path, option k1_resident (per plan): [tiles] rows of output 1's Lipschitz partials | [tiles] residency bytes of the objective
   sbo::ResetBuf bl_sched;       // K1b column path, lean 2 (r07): the tile lists of the constraint's and the objective's launch (PostExtra::tlist); neutral: the
                                 // counters of the constraint's list, at the head, are zero (k_bl_sched_list2; raised by col_set_phase at its end)
   sbo::Pinned h_stage;          // pinned staging of the K1b table build's single upload (the twin has one of its own)
@@ -621,6 +641,7 @@ struct sbo_ctx {
   bool posterior_valid = false;
   bool post_l0_missing = false;  // the resident posterior came from a lean sweep's launch: L_0 (Lmax[0]) was not computed
   int last_k1 = 0;               // kernel family of the last posterior launch (sbo_profile.posterior_kernel)
+  double last_k1_tile_flops[2] = {0.0, 0.0};   // K1b: of that, the share of one 64 x 128 tile of output 0 / 1 (its variance and mean phases)
   double last_k1_flops = 0.0;    // matrix-core flops it issued
   unsigned long long* Lmax = nullptr;   // [kMaxQ] keys: max ||grad MEAN_i||_inf over the candidates -- a view: ScalBlock::lip_keys of lane[0].scal
   // set workspace
@@ -811,9 +832,9 @@ int launch_posterior_gemm(sbo_ctx* c, bool interp, const PostRequest& req, PostO
 // (Not K1t's plan: it keys itself on the model's serial and the grid, tensor_applicable compares them.)
 // Somebody other than a K1b column-path launch of the resident plan writes (or is about to write) sbo_ctx::mean / var: the stored
 // values of the constraint are no longer the plan's on every tile (BilinearPlan::encl_ready).
-inline void post_regions_written(sbo_ctx* c) { c->bl.encl_ready = c->bl.vals_ready = false; }
+inline void post_regions_written(sbo_ctx* c) { c->bl.encl_ready = c->bl.vals_ready = c->bl.lrows_ready = false; c->bl.omap_dirty = true; }
 // ... single candidates of it are overwritten with other values (the guard's exact recheck): see BilinearPlan::vals_ready
-inline void post_values_patched(sbo_ctx* c) { c->bl.vals_ready = false; }
+inline void post_values_patched(sbo_ctx* c) { c->bl.vals_ready = false; c->bl.omap_dirty = true; }
 inline void plans_invalidate(sbo_ctx* c) {
   c->bl.valid = false;
   c->bi.valid = false;

@@ -956,6 +956,7 @@ int launch_posterior(sbo_ctx* c, const PostRequest& req, PostOutcome& out) {
   // the generic kernels, an fp32 model's -- drops the flag here, in the one place the family is chosen, and a plan built below starts
   // without it.
   const bool encl_kept = c->bl.valid && c->bl.encl_ready, vals_kept = encl_kept && c->bl.vals_ready;
+  const bool lrows_kept = encl_kept && c->bl.lrows_ready, omap_kept = c->bl.valid && !c->bl.omap_dirty;
   post_regions_written(c);
   // block-triangular contraction as issued: npad (npad + 16) / 2 multiply-adds per candidate and output
   const double tri_flops = (double)c->mc.q * c->mc.npad * (c->mc.npad + 16.0) * (double)c->cs.n_local;
@@ -978,6 +979,8 @@ int launch_posterior(sbo_ctx* c, const PostRequest& req, PostOutcome& out) {
         c->last_k1 = 4;
         c->bl.encl_ready = encl_kept;                        // (the same plan as when the enclosures were recorded: bilinear_setup did not run)
         c->bl.vals_ready = vals_kept;
+        c->bl.lrows_ready = lrows_kept;
+        c->bl.omap_dirty = !omap_kept;                       // (the objective's residency bytes: launch_posterior_gemm clears them where it must)
         return launch_posterior_gemm(c, false, req, out);    // (writes the Lipschitz keys itself)
       }
     }

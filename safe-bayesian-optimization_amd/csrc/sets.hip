@@ -52,6 +52,7 @@ struct SweepScalars {
   long long guard_slot[kArgSlots];
   long long tiles_skipped;                 // column path, lean 2: constraint tiles of the posterior left unevaluated (r06: kSlotSkip)
   long long tiles_skipped_safe;            // ... and those left unevaluated as proved safe (kSlotSkipSafe)
+  long long tiles_resident_c, tiles_resident_o;   // ... constraint / objective tiles classified from their stored mean / var (option k1_resident)
   // ---- device only ----
   unsigned long long ticket;               // workgroups of k_goose_finals that have finished their slot (zeroed with the block)
   long long n_guard_cls;                   // the classification's share of n_guard, the value it starts from
@@ -2206,6 +2207,11 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v
   c->prof.set_path = colpath ? 1 : 0;
   c->prof.k1_tiles_skipped = colpath ? h.tiles_skipped : 0;
   c->prof.k1_tiles_skipped_safe = colpath ? h.tiles_skipped_safe : 0;
+  c->prof.k1_tiles_resident_c = colpath ? h.tiles_resident_c : 0;
+  c->prof.k1_tiles_resident_o = colpath ? h.tiles_resident_o : 0;
+  // (gemm_flops counted the whole tile grid at enqueue time: the tiles this sweep classified from memory issued no GEMM phase)
+  if (colpath && !reuse)
+    c->last_k1_flops = std::max(0.0, c->last_k1_flops - (double)h.tiles_resident_c * c->last_k1_tile_flops[1] - (double)h.tiles_resident_o * c->last_k1_tile_flops[0]);
 
   memset(res, 0, sizeof(*res));
   res->count_S = h.count_S;

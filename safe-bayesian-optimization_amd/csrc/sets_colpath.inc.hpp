@@ -201,7 +201,7 @@ __device__ __forceinline__ void col_coarse_job(int blk, const ColGeom gm, const 
 // one wave reduces a field of the slot block (internal.hpp: ColSlotField): a load per lane, six shuffle steps; valid in every lane
 __device__ __forceinline__ unsigned long long col_slot_reduce(const unsigned long long* __restrict__ slots, int field) {
   unsigned long long v = slots[(size_t)field * kColSlots + (threadIdx.x & 63)];
-  const bool is_min = col_slot_is_min(field), is_sum = field == kSlotS || field == kSlotU || field == kSlotB || field == kSlotSkip || field == kSlotSkipSafe;
+  const bool is_min = col_slot_is_min(field), is_sum = field == kSlotS || field == kSlotU || field == kSlotB || field == kSlotSkip || field == kSlotSkipSafe || field == kSlotResC || field == kSlotResO;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const unsigned long long y = __shfl_xor(v, o);
@@ -217,11 +217,12 @@ __device__ __forceinline__ void col_merge1_body(const unsigned long long* __rest
   if (threadIdx.x < 64) {
     const unsigned long long cS = col_slot_reduce(slots, kSlotS), cU = col_slot_reduce(slots, kSlotU), cB = col_slot_reduce(slots, kSlotB);
     const unsigned long long vmin = col_slot_reduce(slots, kSlotVmin1), rmax = col_slot_reduce(slots, kSlotRmax1), l1 = col_slot_reduce(slots, kSlotL1);
-    const unsigned long long nskip = col_slot_reduce(slots, kSlotSkip), nsafe = col_slot_reduce(slots, kSlotSkipSafe);
+    const unsigned long long nskip = col_slot_reduce(slots, kSlotSkip), nsafe = col_slot_reduce(slots, kSlotSkipSafe), nresc = col_slot_reduce(slots, kSlotResC);
     if (threadIdx.x == 0) {
       Lmax[1] = l1;
       sc->tiles_skipped = (long long)nskip;
       sc->tiles_skipped_safe = (long long)nsafe;
+      sc->tiles_resident_c = (long long)nresc;
       sc->ustar_key = ~0ull;                       // (the objective's half: k_col_min, into its own block)
       sc->count_S = (long long)cS;
       sc->count_U = (long long)cU;
@@ -246,6 +247,7 @@ __device__ __forceinline__ void col_merge1_body(const unsigned long long* __rest
 struct ColScal2 {            // the objective's scalars, in their own block (the expander chain clears and fills SweepScalars concurrently)
   unsigned long long ustar_key, vmin0_key;
   double gb_du0;
+  unsigned long long res_o;  // objective tiles this sweep classified from memory (kSlotResO: k_bl_sched_list2, complete behind the objective's launches)
 };
 __device__ __forceinline__ void col_merge2_body(const unsigned long long* __restrict__ slots, unsigned long long& ustar_key,
                                                 unsigned long long& vmin0_key) {
@@ -437,9 +439,9 @@ __global__ __launch_bounds__(256) void k_col_min(const ColMinJob j) {
     du0 = j.gb->dm[0] + (any ? j.b * gb_dsqrt(vm, j.gb->dv[0]) : 0.0);
   }
   if (blockIdx.x == 0 && threadIdx.x < 64) {
-    const unsigned long long l0 = PART == 1 ? col_slot_reduce(j.slots, kSlotL0) : 0ull;
+    const unsigned long long l0 = PART == 1 ? col_slot_reduce(j.slots, kSlotL0) : col_slot_reduce(j.slots, kSlotResO);
     if (threadIdx.x == 0) {
-      if (PART == 0) { j.sc2->ustar_key = ukey; j.sc2->vmin0_key = vkey; j.sc2->gb_du0 = du0; }
+      if (PART == 0) { j.sc2->ustar_key = ukey; j.sc2->vmin0_key = vkey; j.sc2->gb_du0 = du0; j.sc2->res_o = l0; }
       else j.Lmax[0] = l0;
     }
   }
@@ -1007,6 +1009,7 @@ __global__ __launch_bounds__(256) void k_col_finals(const Best* __restrict__ reg
       hm->count_M = sc->count_M;
       sc->ustar_key = sc2->ustar_key;
       hm->ustar_key = sc2->ustar_key;
+      hm->tiles_resident_o = (long long)sc2->res_o;
       for (int t = 2; t < kArgSlots; ++t) hm->guard_slot[t] = 0;
     } else {
       // (the expander chain has finished before this launch: its counters are final)
@@ -1019,6 +1022,7 @@ __global__ __launch_bounds__(256) void k_col_finals(const Best* __restrict__ reg
       hm->n_guard = sc->n_guard;
       hm->tiles_skipped = sc->tiles_skipped;
       hm->tiles_skipped_safe = sc->tiles_skipped_safe;
+      hm->tiles_resident_c = sc->tiles_resident_c;
       for (int t = 0; t < kMaxQ; ++t) {
         hm->rmax_key[t] = sc->rmax_key[t];
         reinterpret_cast<unsigned long long*>(mirror + offsetof(PinnedBack, lip_keys))[t] = Lkeys[t];

@@ -20,7 +20,8 @@ import safebo_amd                                   # noqa: E402
 from safebo_amd import synthetic                    # noqa: E402
 
 ROWS = 1 << 13
-KINDS = ("evaluated", "skipped (partial rows only)", "skipped, gradient phases run", "past the tile list (exit at once)")
+KINDS = ("evaluated", "skipped (partial rows only)", "skipped, gradient phases run", "past the tile list (exit at once)",
+         "classified from memory (k_bres)")
 TICK_US = 0.01                                      # wall_clock64: 100 MHz
 
 
@@ -70,6 +71,10 @@ def report(name, d, out):
         m = d["kind"] == k
         if m.any():
             print(f"   partial rows + words + atomics, {nm:30s}: mean {part[m].mean():6.2f} us, total {part[m].sum():8.1f} us", file=out)
+    m = d["kind"] == 4
+    if m.any():          # (k_bres: [1] is the clock behind its loads -- entry -> loads arrived -> exit)
+        print(f"   classified from memory: loads {((d['tp'][m] - d['t0'][m]) * TICK_US).mean():6.2f} us, classification + partial rows + words "
+              f"{part[m].mean():6.2f} us (means)", file=out)
 
 
 def main():
@@ -77,6 +82,7 @@ def main():
     ap.add_argument("--sched", type=int, default=1, help="option k1_sched (0: one workgroup per tile, the grid before the tile lists)")
     ap.add_argument("--config", default="H")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--resident", type=int, default=1, help="option k1_resident (a library without it: ignored)")
     args = ap.parse_args()
     lib = safebo_amd._lib.load()
     fn = lib.sbo_debug_wg_trace
@@ -86,6 +92,10 @@ def main():
     cfg = synthetic.make_config(args.config)
     eng = safebo_amd.SweepEngine(0)
     eng.set_option("k1_sched", args.sched)
+    try:
+        eng.set_option("k1_resident", args.resident)
+    except ValueError:
+        pass
     eng.set_model(cfg["ds"], dtype="f64", use_invK=True)
     eng.set_grid(cfg["bound"][:, 0], cfg["bound"][:, 1], list(cfg["count"]))
     for _ in range(5):
