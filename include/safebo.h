@@ -232,6 +232,11 @@ typedef struct sbo_profile {
    * safe candidate whose stored values are the plan's).  Zero unless the sweep was a lean 2 sweep on the column path of a plan whose
    * enclosures are recorded.                                                                                                        */
   int64_t k1_tiles_resident_c, k1_tiles_resident_o;
+  /* Option "k1_cells": 8 x 8 cells of the k1_tiles_resident_c tiles whose stored mean / var the last sweep loaded and classified
+   * candidate by candidate -- the cells the plan's enclosures prove neither safe nor unsafe at that sweep's b and band; the other cells
+   * of those tiles got their bits from the proof.  Zero when the sweep did not take that path (then every cell of a resident tile is
+   * loaded: 128 x k1_tiles_resident_c).                                                                                              */
+  int64_t k1_cells_evaluated;
   /* of guard_audit_samples: samples on tiles of either kind, where the audit checks the reference values against the tile's enclosure
    * (widened by the band) instead of the stored ones -- on a proved-safe tile also the stored values, which must lie inside the
    * enclosure bit for bit.  Cumulative, as guard_audit_samples.                                                                      */
@@ -904,6 +909,9 @@ int sbo_profile_get(sbo_ctx* ctx, sbo_profile* out);
  *   "k1_resident"      1: from a plan's second lean-2 sweep on that path on (k1_sched 1, enclosures recorded), the tiles whose stored mean /
  *                      var are the plan's are classified from memory without their GEMM phases, and the constraint's Lipschitz rows come
  *                      from the plan's record (sbo_profile.k1_tiles_resident_c / _o); 0: every sweep runs the GEMM phases (A/B checker)
+ *   "k1_cells"         1: where k1_resident classifies the constraint's listed tiles from memory, one launch decides every tile and classifies
+ *                      the others per 8 x 8 cell -- a cell its enclosure proves safe or unsafe takes its bits from the proof, only the rest
+ *                      load their stored values (sbo_profile.k1_cells_evaluated); 0: the tile-list kernel and the per-tile launch (A/B checker)
  *   "col_overlap"      1: on that path the expander chain (distance transform, verdicts) runs on a second stream beside the objective's
  *                      posterior launch and the M part of the minimiser; 0: every kernel on the main stream
  *   "set_fuse"         1: 2-D grids of one rank share launches between independent set-phase kernels; 0: one launch per kernel

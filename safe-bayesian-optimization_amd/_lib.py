@@ -209,7 +209,8 @@ class Profile(C.Structure):
         ("guard_analytic_dm", C.c_double * SBO_MAX_Q), ("guard_analytic_dv", C.c_double * SBO_MAX_Q),
         ("guard_probe_dm", C.c_double * SBO_MAX_Q), ("guard_probe_dv", C.c_double * SBO_MAX_Q),
         ("k1_tiles_skipped", C.c_int64), ("k1_tiles_skipped_safe", C.c_int64),
-        ("k1_tiles_resident_c", C.c_int64), ("k1_tiles_resident_o", C.c_int64), ("guard_audit_skipped", C.c_int64),
+        ("k1_tiles_resident_c", C.c_int64), ("k1_tiles_resident_o", C.c_int64), ("k1_cells_evaluated", C.c_int64),
+        ("guard_audit_skipped", C.c_int64),
         ("list_index_build_ms", C.c_double), ("list_index_leaf_pairs", C.c_int64), ("list_index_nodes_skipped", C.c_int64),
         ("fp32_band_dm", C.c_double * SBO_MAX_Q), ("fp32_band_dv", C.c_double * SBO_MAX_Q),
     ]

@@ -297,6 +297,7 @@ const OptRow kOptions[] = {
     OPT_BOOL(k1_sched, kOptNothing, nullptr),
     OPT_BOOL(k1_resident, kOptNothing, nullptr),        // (read per sweep: launch_posterior_gemm decides what it takes from memory)
     OPT_BOOL(k1_skip_safe, kOptNothing, nullptr),       // (read per sweep: the decision is taken at every sweep's b and band)
+    OPT_BOOL(k1_cells, kOptNothing, nullptr),           // (read per sweep: gemm_post_part picks the head of a resident plan's lean-2 sweep)
     OPT_BOOL(col_overlap, kOptNothing, nullptr),
     OPT_RANGE(col_queue, 64, 128, "col_queue must be within 64 .. 128 (the default)", kOptNothing, nullptr),
     OPT_BOOL(scan_blocks, kOptNothing, nullptr),

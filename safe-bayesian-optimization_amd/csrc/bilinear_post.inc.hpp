@@ -191,6 +191,11 @@ __device__ __forceinline__ bool encl_safe(double mlo, double mhi, double vlo, do
 //   * the late exhaustive recheck (launch_exact_d -> edt_scan_body and the goose / expander kernels' rmax / L): the same cap;
 //   * the host: halo_learn / halo_for (sets.hip), multi-rank only -- the column path runs on one rank --, again rmax / L as a halo width.
 // Nobody compares it for equality, reports it, or takes an arg-max from it.
+// CELLS (option k1_cells, k_bhead): a tile the boundary of S crosses takes the same three values from each of its cells that is proved
+// safe and its candidates' own values from the cells it evaluates, merged by min / max.  vlo stays exact (the minimum over proved cells
+// of their smallest stored variance and over the evaluated safe candidates' own: S of the tile is exactly their union).  up / lo are
+// then an upper bound of max ucb_1 and a lower bound of min ucb_1 over the tile's safe candidates, tighter than a whole proved tile's
+// (a part of the terms is exact); the readers above take them in the same three ways, per tile, and nothing reads them per cell.
 struct EnclKeys { double vlo, up, lo; };
 __device__ __forceinline__ EnclKeys encl_keys(double mlo, double mhi, double vlo, double vhi, double bconf) {
   const float sfh = __builtin_amdgcn_sqrtf((float)vhi), sfl = __builtin_amdgcn_sqrtf((float)vlo);
@@ -1183,6 +1188,8 @@ extern "C" int sbo_debug_wg_trace(unsigned long long* out /* [2][rows][8] */, in
 // pieces and the partials are assembled by the same code; every merge is an integer add, an OR, or a min / max of ordered keys, and
 // b and the band enter here exactly as they enter the epilogue: the results are k_bpost's bit for bit.  All 64 values of a thread are
 // requested before the first is used: there are no accumulators to hold.
+// With option k1_cells (the default) the constraint's head is k_bhead, below; k_bres<1> stays for k1_cells 0, the A/B and identity
+// switch.  k_bres<2> is the objective's light launch either way.
 template <int ROLE>
 __global__ __launch_bounds__(256) void k_bres(const CandSpec cs, const double* __restrict__ mean, const double* __restrict__ var,
                                               double* __restrict__ Lpart, double bconf, unsigned long long* __restrict__ cpart, int pcap,
@@ -1300,6 +1307,343 @@ __global__ __launch_bounds__(256) void k_bres(const CandSpec cs, const double* _
 #ifdef SBO_PHASE_CLOCKS
   __syncthreads();
   if (threadIdx.x == 0) wg_trace_row(o, clk_in_, clk_ld_, wall_clock64(), (unsigned int)ctile, 4u);
+#endif
+}
+
+// post_classify_row for ONE candidate (k_bhead: a lane holds one candidate of an 8 x 8 cell): the same sign test, the same fallback
+// through the IEEE root for what the predicates leave open, the same band test, and for a safe candidate the same variance, range and
+// radius arithmetic -- statement for statement the row form's, which stays as it is (k_bpost's and k_bres' code objects do not move).
+// The radius filter compares against the LANE's running maximum instead of a thread's over 32 candidates: it only ever skips a
+// candidate whose upper bound cannot raise the maximum, so the maximum over any set of candidates is the same whatever the order.
+struct CandAcc { double vminS, xmin, rmax; };           // (1e300, 1e300, -1: none)
+__device__ __forceinline__ void post_classify_cand(double m, double v, double bconf, double bb, bool gb_on, const LcbBand& lband, bool& ge_out,
+                                                   bool& le_out, bool& near_out, CandAcc& a) {
+  constexpr double c = 1.0 + 0x1p-48, tiny = 1e-250, huge = 1e300;
+  const bool bok = bconf >= 0.0;
+  const double P = m * m, Q = bb * v;
+  near_out = false;
+  if (gb_on) {
+    const double gap = P > Q ? P - Q : Q - P, am = m < 0 ? -m : m;
+    near_out = !(gap > fma(am, lband.c1, lband.c0));                     // (NaN operands count as near)
+  }
+  const bool ok = bok && v >= 0.0, rng = P < huge && Q < huge;
+  const bool neg = ok && m < 0.0;
+  bool ge = ok && !neg && rng && P > tiny && P >= Q * c;
+  bool le = neg || (ok && rng && !ge && Q > tiny && P * c <= Q && m >= 0.0);
+  if (!ge && !le) {
+    const double sd = mul_rn(bconf, sqrt_rn(v));
+    ge = m >= sd;
+    le = m <= sd;
+  }
+  if (ge) {
+    a.vminS = v < a.vminS ? v : a.vminS;
+    const float sf = __builtin_amdgcn_sqrtf((float)v);
+    const double s_up = (double)sf * (1.0 + 0x1p-20) + 1e-18;
+    double s_lo = (double)sf * (1.0 - 0x1p-20) - 1e-18;
+    s_lo = s_lo > 0.0 ? s_lo : 0.0;
+    const bool fin = sf < 3.0e38f;
+    const double xu = m + bconf * s_up, xl = m + bconf * (fin ? s_lo : 0.0);
+    const double up = fin ? xu + (xu < 0 ? -xu : xu) * 0x1p-50 : 1e300, lo = xl - (xl < 0 ? -xl : xl) * 0x1p-50;
+    a.xmin = lo < a.xmin ? lo : a.xmin;
+    if (!(up <= a.rmax)) {
+      const double ucb = add_rn(m, mul_rn(bconf, sqrt_rn(v)));
+      if (ucb > a.rmax) a.rmax = ucb;
+    }
+  }
+  ge_out = ge;
+  le_out = le;
+}
+
+// Option k1_cells: the head of a lean-2 column-path sweep on a resident plan (res_c: the plan's Lipschitz rows and the constraint's
+// stored values stand) in ONE launch -- k_bl_sched_tiles1's tile decision and, for the tiles it would have listed, k_bres<1>'s
+// classification, cell by cell.  encl_unsafe / encl_safe are statements about a CELL (8 x 8 candidates); the boundary of S is a curve, so
+// of the 128 cells of a tile it crosses most are proved one way or the other by the enclosure the deciding wave holds anyway.  A cell
+// proved unsafe is its 64 U bits and 64 to |U|; a cell proved safe (k1_skip_safe) its 64 S bits, 64 to |S|, its smallest stored variance
+// (exact) and the ends of encl_keys (bounds: see EnclKeys); nothing of either is counted in the band -- exactly what the predicates
+// prove post_classify_row does with every candidate of the box.  Only the other cells -- undecided, NaN enclosures, b < 0 -- load
+// their 64 stored mean / var pairs and classify them (post_classify_cand).  This rests on invariant 2 at k_bl_enclose harder than
+// anything before: the stored values must be the plan's bits, inside the recorded enclosures bit for bit (the audit checks both).
+// Shape: a resident-sized grid of kHeadWaves-wave workgroups; in a round wave w DECIDES tile (kHeadWaves round + w) gridDim + block --
+// a stride of gridDim tiles apart, so the tiles of a workgroup are not neighbours on the grid (the boundary runs through neighbours:
+// what the shard rotation of the tile list was for).  Classes 0 and 4 are written by that wave as k_bl_sched_tiles1 writes them.  For
+// any other tile it builds the column words of the proved cells from four ballots, puts them in LDS and queues the undecided (tile,
+// cell) pairs; behind a barrier EVERY wave drains the queue, kHeadBatch cells to a batch, all loads of a batch requested before the
+// first is used, a lane per candidate (row lane & 7, column lane >> 3 of the cell: a ballot IS the cell's eight column bytes).  A
+// cell owns one byte of each of its eight column words, so the bytes are plain LDS stores; counts and keys join the tile's record in
+// LDS by integer adds and min / max of ordered keys whenever a wave moves on to another tile.  A tile with all 128 cells undecided
+// costs its workgroup 32 batches over four waves -- what k_bres<1> costs --, not four times that.  Behind a second barrier the
+// deciding wave writes the tile's words, Usum bits, Lipschitz row, partial row and row-mask bit; the slot scalars of all the
+// workgroup's tiles are merged in LDS and join ONE slot (sums, minima, maxima: the slot does not change them; what un-merged atomics
+// cost: k_bl_sched_tiles1).  No list, no fence, no ticket; no result depends on the order of anything.
+constexpr int kHeadWaves = 4, kHeadBatch = 4;
+struct HeadRec { unsigned int cS, cU, cB, ncell; unsigned long long vmin, rmax, xmin; };
+__global__ __launch_bounds__(64 * kHeadWaves) void k_bhead(const double* __restrict__ encl, int ntiles, int tgx, int tgy, unsigned int cnt0, double bconf,
+                                                           const GuardBand* __restrict__ gb, const double* __restrict__ mean1,
+                                                           const double* __restrict__ var1 /* output 1's stored values */,
+                                                           uint8_t* __restrict__ skip, unsigned long long* __restrict__ Sw,
+                                                           unsigned long long* __restrict__ Uw, unsigned long long* __restrict__ Usum,
+                                                           unsigned long long* __restrict__ slots, double* __restrict__ Lpart,
+                                                           unsigned long long* __restrict__ cpart, int pcap, int skip_safe,
+                                                           const double* __restrict__ lrec) {
+  __shared__ unsigned long long sh_w[kHeadWaves][2][128];    // a mixed tile's S / U column words
+  __shared__ unsigned short sh_q[kHeadWaves * 128];          // undecided cells: (wave that decided the tile) << 7 | cell
+  __shared__ HeadRec sh_rec[kHeadWaves];
+  __shared__ unsigned int sh_xy[kHeadWaves];                 // the tile's bx | by << 16
+  __shared__ unsigned int sh_qn;
+  __shared__ unsigned long long sh_acc[kHeadWaves][10];
+  const int lane = threadIdx.x & 63, wave = (int)(threadIdx.x >> 6);
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const double bb = bconf * bconf;
+  const bool gb_on = gb != nullptr;
+  const LcbBand lb = gb_on ? lcb_band(bb, gb->dm[1], gb->dv[1]) : LcbBand{0.0, 0.0};
+  // the wave's share of the slot scalars, over its tiles of every round (wave-uniform)
+  unsigned long long a_key = 0ull, a_vmin = ~0ull, a_rmax = 0ull;
+  unsigned int a_S = 0u, a_U = 0u, a_B = 0u, a_n0 = 0u, a_n4 = 0u, a_res = 0u, a_cells = 0u;      // (a wave's tiles: far below 2^32 candidates)
+#ifdef SBO_PHASE_CLOCKS
+  const unsigned long long clk_in_ = wall_clock64();        // (g_wg_trace: kind 5 = the head launch, [1] = the first round's decisions are made)
+  unsigned long long clk_dec_ = clk_in_;
+  unsigned int clk_tile_ = 0xffffffu;
+#endif
+  const int per_round = kHeadWaves * (int)gridDim.x;
+  for (int t0 = 0; t0 < ntiles; t0 += per_round) {          // (uniform over the workgroup: the barriers below are met by all)
+    const int tile = t0 + wave * (int)gridDim.x + (int)blockIdx.x;
+    const bool have = tile < ntiles;                        // (a whole wave or none of it)
+    if (threadIdx.x == 0) sh_qn = 0u;
+    __syncthreads();
+    bool mixed = false;
+    int bx = 0, by = 0;
+    double lrow = 0.0;
+    if (have) {
+      bx = tile % tgx;
+      by = tile / tgx;
+      lrow = lrec[tile];
+      a_key = (unsigned long long)__double_as_longlong(lrow) > a_key ? (unsigned long long)__double_as_longlong(lrow) : a_key;
+      bool us[2], sf[2];
+      double kv = 1e300, ku = -1.0, kl = 1e300;             // (the keys of the cells proved safe: encl_keys)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const double4 e = reinterpret_cast<const double4*>(encl)[(size_t)tile * 128 + h * 64 + lane];
+        us[h] = encl_unsafe(e.x, e.y, e.z, e.w, bconf, bb, gb_on, lb);
+        sf[h] = skip_safe != 0 && !us[h] && encl_safe(e.x, e.y, e.z, e.w, bconf, bb, gb_on, lb);
+        if (sf[h]) {
+          const EnclKeys ek = encl_keys(e.x, e.y, e.z, e.w, bconf);
+          kv = ek.vlo < kv ? ek.vlo : kv;
+          ku = ek.up > ku ? ek.up : ku;
+          kl = ek.lo < kl ? ek.lo : kl;
+        }
+      }
+      const unsigned long long mU[2] = {__ballot(us[0]), __ballot(us[1])}, mS[2] = {__ballot(sf[0]), __ballot(sf[1])};
+      const bool dec = (mU[0] & mU[1]) == ~0ull, sdec = (mS[0] & mS[1]) == ~0ull;
+      const size_t w0 = (size_t)by * cnt0 + (size_t)bx * 128;
+      if (lane == 0) {
+        skip[tile] = dec ? kSkipUnsafe : (sdec ? kSkipSafe : 0);
+        Lpart[((size_t)tgy + by) * tgx + bx] = lrow;
+      }
+      if (!dec) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+          const double ov = __shfl_xor(kv, off), ou = __shfl_xor(ku, off), ol = __shfl_xor(kl, off);
+          kv = ov < kv ? ov : kv;
+          ku = ou > ku ? ou : ku;
+          kl = ol < kl ? ol : kl;
+        }
+      }
+      const unsigned long long kvmin = kv < 1e300 ? ord_key(kv) : ~0ull, krmax = ku >= 0.0 ? ord_key(ku) : 0ull, kxmin = kl < 1e300 ? ord_key(kl) : ~0ull;
+      if (dec) {
+        // (class 0, as k_bl_sched_tiles1 writes it: every U bit, its bit of Usum in its 128 columns, |U| = 8192, no keys)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          Sw[w0 + h * 64 + lane] = 0ull;
+          Uw[w0 + h * 64 + lane] = ~0ull;
+          atomicOr(&Usum[(size_t)bx * 128 + h * 64 + lane], 1ull << by);      // (no return value: the wave does not wait for it)
+        }
+        if (lane < kFuseRow) {
+          unsigned long long v = 0ull;
+          if (lane == 0) v = ~0ull;
+          else if (lane == 2) v = 64ull * 128ull;
+          else if (lane >= kFuseVmin && lane < kFuseRmax) v = ~0ull;
+          cpart[(size_t)lane * pcap + tile] = v;
+        }
+        a_n0 += 1u;
+      } else if (sdec) {
+        // (class 4, as k_bl_sched_tiles1 writes it: every S bit, no U bit, its bit of the row mask, |S| = 8192, the keys of encl_keys)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          Sw[w0 + h * 64 + lane] = ~0ull;
+          Uw[w0 + h * 64 + lane] = 0ull;
+        }
+        if (lane == 0) atomicOr(&slots[(size_t)kSlotRowMask * kColSlots + by], 1ull << bx);      // (no return value)
+        if (lane < kFuseRow) {
+          unsigned long long v = 0ull;
+          if (lane == 0) v = kxmin;
+          else if (lane == 1) v = 64ull * 128ull;
+          else if (lane >= kFuseVmin && lane < kFuseRmax) v = lane == kFuseVmin + 1 ? kvmin : ~0ull;
+          else if (lane == kFuseRmax + 1) v = krmax;
+          cpart[(size_t)lane * pcap + tile] = v;
+        }
+        a_n4 += 1u;
+        a_vmin = kvmin < a_vmin ? kvmin : a_vmin;
+        a_rmax = krmax > a_rmax ? krmax : a_rmax;
+      } else {
+        mixed = true;
+        // the proved cells' bytes of the column words (cell 16 cr + cc is lane 16 (cr & 3) + cc of ballot cr >> 2); an undecided cell's
+        // byte is zero until the wave that classifies the cell stores it
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int cc = (h * 64 + lane) >> 3;
+          unsigned long long sw = 0ull, uw = 0ull;
+#pragma unroll
+          for (int cr = 0; cr < 8; ++cr) {
+            const int bit = 16 * (cr & 3) + cc;
+            sw |= ((mS[cr >> 2] >> bit) & 1ull) ? 0xffull << (8 * cr) : 0ull;
+            uw |= ((mU[cr >> 2] >> bit) & 1ull) ? 0xffull << (8 * cr) : 0ull;
+          }
+          sh_w[wave][0][h * 64 + lane] = sw;
+          sh_w[wave][1][h * 64 + lane] = uw;
+        }
+        const unsigned long long mN[2] = {~(mU[0] | mS[0]), ~(mU[1] | mS[1])};
+        const unsigned int n0 = (unsigned int)__popcll(mN[0]), n1 = (unsigned int)__popcll(mN[1]);
+        unsigned int base = 0u;
+        if (lane == 0) {
+          base = atomicAdd(&sh_qn, n0 + n1);
+          sh_rec[wave] = HeadRec{64u * (unsigned int)(__popcll(mS[0]) + __popcll(mS[1])), 64u * (unsigned int)(__popcll(mU[0]) + __popcll(mU[1])), 0u,
+                                 n0 + n1, kvmin, krmax, kxmin};
+          sh_xy[wave] = (unsigned int)bx | ((unsigned int)by << 16);
+        }
+        base = (unsigned int)__shfl((int)base, 0);
+        if ((mN[0] >> lane) & 1ull) sh_q[base + (unsigned int)__popcll(mN[0] & below)] = (unsigned short)((wave << 7) | lane);
+        if ((mN[1] >> lane) & 1ull) sh_q[base + n0 + (unsigned int)__popcll(mN[1] & below)] = (unsigned short)((wave << 7) | (64 + lane));
+      }
+    }
+    __syncthreads();
+#ifdef SBO_PHASE_CLOCKS
+    if (t0 == 0) clk_dec_ = wall_clock64();
+    if (mixed && clk_tile_ == 0xffffffu) clk_tile_ = (unsigned int)tile;
+#endif
+    {
+      // every wave drains the queue: batch i goes to wave i mod kHeadWaves
+      const unsigned int nq = sh_qn;
+      const unsigned int r8 = (unsigned int)lane & 7u, c8 = (unsigned int)lane >> 3;
+      CandAcc acc{1e300, 1e300, -1.0};
+      unsigned int cS = 0u, cU = 0u, cB = 0u;
+      int cur = -1;
+      auto flush = [&]() {
+        if (cur < 0) return;
+        double vm = acc.vminS, xm = acc.xmin, rm = acc.rmax;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+          const double ov = __shfl_xor(vm, off), ox = __shfl_xor(xm, off), orr = __shfl_xor(rm, off);
+          vm = ov < vm ? ov : vm;
+          xm = ox < xm ? ox : xm;
+          rm = orr > rm ? orr : rm;
+        }
+        if (lane == 0) {
+          HeadRec& r = sh_rec[cur];
+          if (cS) atomicAdd(&r.cS, cS);
+          if (cU) atomicAdd(&r.cU, cU);
+          if (cB) atomicAdd(&r.cB, cB);
+          if (vm < 1e300) atomicMin(&r.vmin, ord_key(vm));
+          if (xm < 1e300) atomicMin(&r.xmin, ord_key(xm));
+          if (rm >= 0.0) atomicMax(&r.rmax, ord_key(rm));
+        }
+        acc = CandAcc{1e300, 1e300, -1.0};
+        cS = cU = cB = 0u;
+      };
+      for (unsigned int b0 = (unsigned int)wave * kHeadBatch; b0 < nq; b0 += kHeadWaves * kHeadBatch) {
+        unsigned int ent[kHeadBatch];
+        double m[kHeadBatch], v[kHeadBatch];
+#pragma unroll
+        for (int k = 0; k < kHeadBatch; ++k) {
+          // (past the end of the queue: the batch's first entry again -- a load nobody uses, inside the grid)
+          ent[k] = (unsigned int)__builtin_amdgcn_readfirstlane((int)sh_q[b0 + k < nq ? b0 + k : b0]);
+          const unsigned int xy = (unsigned int)__builtin_amdgcn_readfirstlane((int)sh_xy[ent[k] >> 7]), cell = ent[k] & 127u;
+          const size_t g = ((size_t)(xy >> 16) * 64 + (size_t)(cell >> 4) * 8 + r8) * cnt0 + (size_t)(xy & 0xffffu) * 128 + (size_t)(cell & 15u) * 8 + c8;
+          m[k] = mean1[g];
+          v[k] = var1[g];
+        }
+#pragma unroll
+        for (int k = 0; k < kHeadBatch; ++k) {
+          if (b0 + k < nq) {
+            const int w = (int)(ent[k] >> 7);
+            const unsigned int cell = ent[k] & 127u;
+            if (w != cur) {
+              flush();
+              cur = w;
+            }
+            bool ge, le, nr;
+            post_classify_cand(m[k], v[k], bconf, bb, gb_on, lb, ge, le, nr, acc);
+            const unsigned long long gm = __ballot(ge), lm = __ballot(le);
+            cS += (unsigned int)__popcll(gm);
+            cU += (unsigned int)__popcll(lm);
+            cB += (unsigned int)__popcll(__ballot(nr));
+            // (byte c of a ballot: column c of the cell, rows 0..7 -- bits 8 (cell >> 4) .. + 7 of that column's word)
+            if (lane < 16) {
+              const unsigned long long bits = lane < 8 ? gm : lm;
+              reinterpret_cast<unsigned char*>(&sh_w[w][lane >> 3][(cell & 15u) * 8 + (lane & 7)])[cell >> 4] = (unsigned char)(bits >> (8 * (lane & 7)));
+            }
+          }
+        }
+      }
+      flush();
+    }
+    __syncthreads();
+    if (mixed) {
+      // the deciding wave writes what the tile's workgroup wrote (k_bres<1>: words, Usum, post_partials' row and scalars)
+      const size_t w0 = (size_t)by * cnt0 + (size_t)bx * 128;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const unsigned long long sw = sh_w[wave][0][h * 64 + lane], uw = sh_w[wave][1][h * 64 + lane];
+        Sw[w0 + h * 64 + lane] = sw;
+        Uw[w0 + h * 64 + lane] = uw;
+        if (uw != 0ull) atomicOr(&Usum[(size_t)bx * 128 + h * 64 + lane], 1ull << by);
+      }
+      const HeadRec r = sh_rec[wave];
+      if (lane == 0 && r.cS != 0u) atomicOr(&slots[(size_t)kSlotRowMask * kColSlots + by], 1ull << bx);
+      if (lane < kFuseRow) {
+        unsigned long long v = 0ull;
+        if (lane == 0) v = r.xmin;
+        else if (lane == 1) v = r.cS;
+        else if (lane == 2) v = r.cU;
+        else if (lane == 3) v = r.cB;
+        else if (lane >= kFuseVmin && lane < kFuseRmax) v = lane == kFuseVmin + 1 ? r.vmin : ~0ull;
+        else if (lane == kFuseRmax + 1) v = r.rmax;
+        cpart[(size_t)lane * pcap + tile] = v;
+      }
+      a_S += r.cS;
+      a_U += r.cU;
+      a_B += r.cB;
+      a_res += 1u;
+      a_cells += r.ncell;
+      a_vmin = r.vmin < a_vmin ? r.vmin : a_vmin;
+      a_rmax = r.rmax > a_rmax ? r.rmax : a_rmax;
+    }
+  }
+  if (lane == 0) {
+    unsigned long long* a = sh_acc[wave];
+    a[0] = a_key; a[1] = (unsigned long long)a_S + 64ull * 128ull * a_n4; a[2] = (unsigned long long)a_U + 64ull * 128ull * a_n0; a[3] = a_B; a[4] = a_n0; a[5] = a_n4;
+    a[6] = a_res; a[7] = a_cells;
+    a[8] = a_vmin; a[9] = a_rmax;
+  }
+  __syncthreads();
+  if (threadIdx.x < 10) {
+    const int f = (int)threadIdx.x;
+    unsigned long long x = sh_acc[0][f];
+#pragma unroll
+    for (int w = 1; w < kHeadWaves; ++w) {
+      const unsigned long long y = sh_acc[w][f];
+      x = f == 8 ? (y < x ? y : x) : ((f == 0 || f == 9) ? (y > x ? y : x) : x + y);
+    }
+    const int slot = (int)(blockIdx.x & (kColSlots - 1));
+    const int field = f == 0 ? kSlotL1 : f == 1 ? kSlotS : f == 2 ? kSlotU : f == 3 ? kSlotB : f == 4 ? kSlotSkip : f == 5 ? kSlotSkipSafe :
+                      f == 6 ? kSlotResC : f == 7 ? kSlotCells : f == 8 ? kSlotVmin1 : kSlotRmax1;
+    unsigned long long* p = &slots[(size_t)field * kColSlots + slot];
+    // (no return values: nobody waits for them)
+    if (f == 8) { if (x != ~0ull) atomicMin(p, x); }
+    else if (f == 0 || f == 9) { if (x != 0ull) atomicMax(p, x); }
+    else if (x != 0ull) atomicAdd(p, x);
+  }
+#ifdef SBO_PHASE_CLOCKS
+  if (threadIdx.x == 0) wg_trace_row(1, clk_in_, clk_dec_, wall_clock64(), clk_tile_, 5u);
 #endif
 }
 
@@ -1627,7 +1971,19 @@ static void gemm_post_part(GemmLaunch& L, int part) {
   const decltype(&k_bpost<1, 0>) kposts[3] = {k_bpost<1, 0>, k_bpost<1, 1>, k_bpost<1, 2>};
   const auto kpost = kposts[colw ? 1 + part : 0];
   px.tlist = nullptr;
-  if (L.sched_l1 && part == 0 && px.encl) {
+  // option k1_cells, a resident plan (res_c): the tile decisions and the listed tiles' classification in ONE launch, per cell, with
+  // the fork event -- no list, no k_bres<1>.  Resident-sized: a tile per wave and round, so the deciding waves of a workgroup sit a
+  // grid's width of tiles apart.
+  const bool head_c = L.res_c && c->opt.k1_cells && L.sched_l1 && part == 0 && px.encl;
+  if (head_c) {
+    const unsigned nt = L.gx * L.gy;
+    const unsigned hgrid = std::max(1u, std::min((nt + kHeadWaves - 1) / kHeadWaves, 4u * (unsigned)c->n_cu));
+    hipExtLaunchKernelGGL(k_bhead, dim3(hgrid), dim3(64 * kHeadWaves), 0, c->stream, nullptr, c->col.ev[0], 0, (const double*)px.encl, (int)nt, (int)L.gx,
+                          (int)L.gy, (unsigned int)L.cnt0, L.req.fuse_b, L.gb_fused, (const double*)c->mean.p + (size_t)cs.n_local,
+                          (const double*)c->var.p + (size_t)cs.n_local, px.skip, px.cb.Sw, px.cb.Uw, px.cb.Usum, px.cb.slots, L.lrows, rows.base,
+                          rows.cap, px.skip_safe, (const double*)L.lrec);
+  }
+  if (L.sched_l1 && part == 0 && px.encl && !head_c) {
     hipLaunchKernelGGL(k_bl_sched_tiles1, dim3((L.gx * L.gy + kSchedWaves - 1) / kSchedWaves), dim3(64 * kSchedWaves), 0, c->stream, c->mc, (const double*)px.encl, (int)(L.gx * L.gy), (int)L.gx,
                        (int)L.gy, (unsigned int)L.cnt0, L.req.fuse_b, L.gb_fused, g.gtmax, g.gkey, q, px.skip, L.sched_l1, L.sched_cap1, px.cb.Sw, px.cb.Uw,
                        px.cb.Usum, px.cb.slots, L.lrows, rows.base, rows.cap, px.skip_safe, L.res_rows ? (const double*)L.lrec : (const double*)nullptr,
@@ -1661,7 +2017,7 @@ static void gemm_post_part(GemmLaunch& L, int part) {
                        (unsigned long long*)c->cpart.p, c->cpart_cap, (const GuardBand*)nullptr, (const double*)nullptr, px);
     px.front_only = 1;
   }
-  if (!light_c) {
+  if (!light_c && !head_c) {
     hipExtLaunchKernelGGL(kpost, grid, dim3(256), L.lds, c->stream, nullptr,
                           (L.req.lmax_defer && last) ? c->ev[1] : ((colw && part == 0) ? c->col.ev[0] : nullptr), 0,
                           c->mc, cs, g.BtA, g.sBtA, g.P0f, g.sP0f, g.VA, g.sVA, g.SBf, g.sSBf, g.KB0, g.KS0, g.KBm, g.KSm, g.KBm2, g.nrb, g.ncs0,

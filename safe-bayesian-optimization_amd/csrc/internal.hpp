@@ -191,6 +191,7 @@ enum ColSlotField { kSlotUmin = 0 /* min key of ucb_0 over S */, kSlotS, kSlotU,
                     kSlotSkip /* count: constraint tiles its enclosure proved unsafe, left unevaluated (r06) */,
                     kSlotSkipSafe /* count: constraint tiles its enclosure proved safe, left unevaluated (option k1_skip_safe) */,
                     kSlotResC, kSlotResO /* counts: constraint / objective tiles classified from their stored mean / var (option k1_resident) */,
+                    kSlotCells /* count: 8 x 8 cells of those constraint tiles whose stored values were loaded (option k1_cells: k_bhead) */,
                     kColSlotFields };
 __host__ __device__ inline bool col_slot_is_min(int f) { return f == kSlotUmin || f == kSlotVmin0 || f == kSlotVmin1; }
 constexpr unsigned int kTlistUnsafe = 0x80000000u, kTlistSafe = 0x40000000u;          // flag bits of a tile-list entry (the tile: ent & 0xffffff)
@@ -551,6 +552,7 @@ struct sbo_ctx {
     int k1_sched = 1;             // 1 = K1b's two lean-2 column-path launches take their tiles from per-sweep lists; 0: one workgroup per tile
     int k1_resident = 1;          // 1 = the second and later lean-2 column-path sweeps of a plan classify from the stored mean / var (k_bres); 0: every sweep runs the GEMM phases
     int k1_skip_safe = 1;         // 1 = a lean-2 column-path sweep leaves the constraint tiles its enclosures prove SAFE unevaluated too; 0: the unsafe ones only
+    int k1_cells = 1;             // 1 = on a resident plan (k_bres<1> would run) one launch decides the constraint's tiles and classifies the listed ones per 8 x 8 cell (k_bhead); 0: k_bl_sched_tiles1 + k_bres<1>
     int comm_events = 0;     // an event pair per collective (MultiRank::comm_ev) whose elapsed times sbo_profile.comm_ms sums
     int col_path = 1;        // 0 = never
     int col_overlap = 1;     // 1 = the expander chain runs on stream3 beside the objective's posterior launch; 0: one stream

@@ -53,6 +53,7 @@ struct SweepScalars {
   long long tiles_skipped;                 // column path, lean 2: constraint tiles of the posterior left unevaluated (r06: kSlotSkip)
   long long tiles_skipped_safe;            // ... and those left unevaluated as proved safe (kSlotSkipSafe)
   long long tiles_resident_c, tiles_resident_o;   // ... constraint / objective tiles classified from their stored mean / var (option k1_resident)
+  long long cells_evaluated;               // ... 8 x 8 cells of the constraint's resident tiles whose stored values were loaded (option k1_cells: kSlotCells)
   // ---- device only ----
   unsigned long long ticket;               // workgroups of k_goose_finals that have finished their slot (zeroed with the block)
   long long n_guard_cls;                   // the classification's share of n_guard, the value it starts from
@@ -2209,6 +2210,7 @@ static int sweep_safeopt_t(sbo_ctx* c, const sbo_sweep_opts* o, const SetView& v
   c->prof.k1_tiles_skipped_safe = colpath ? h.tiles_skipped_safe : 0;
   c->prof.k1_tiles_resident_c = colpath ? h.tiles_resident_c : 0;
   c->prof.k1_tiles_resident_o = colpath ? h.tiles_resident_o : 0;
+  c->prof.k1_cells_evaluated = colpath ? h.cells_evaluated : 0;
   // (gemm_flops counted the whole tile grid at enqueue time: the tiles this sweep classified from memory issued no GEMM phase)
   if (colpath && !reuse)
     c->last_k1_flops = std::max(0.0, c->last_k1_flops - (double)h.tiles_resident_c * c->last_k1_tile_flops[1] - (double)h.tiles_resident_o * c->last_k1_tile_flops[0]);

@@ -201,7 +201,7 @@ __device__ __forceinline__ void col_coarse_job(int blk, const ColGeom gm, const 
 // one wave reduces a field of the slot block (internal.hpp: ColSlotField): a load per lane, six shuffle steps; valid in every lane
 __device__ __forceinline__ unsigned long long col_slot_reduce(const unsigned long long* __restrict__ slots, int field) {
   unsigned long long v = slots[(size_t)field * kColSlots + (threadIdx.x & 63)];
-  const bool is_min = col_slot_is_min(field), is_sum = field == kSlotS || field == kSlotU || field == kSlotB || field == kSlotSkip || field == kSlotSkipSafe || field == kSlotResC || field == kSlotResO;
+  const bool is_min = col_slot_is_min(field), is_sum = field == kSlotS || field == kSlotU || field == kSlotB || field == kSlotSkip || field == kSlotSkipSafe || field == kSlotResC || field == kSlotResO || field == kSlotCells;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const unsigned long long y = __shfl_xor(v, o);
@@ -217,12 +217,13 @@ __device__ __forceinline__ void col_merge1_body(const unsigned long long* __rest
   if (threadIdx.x < 64) {
     const unsigned long long cS = col_slot_reduce(slots, kSlotS), cU = col_slot_reduce(slots, kSlotU), cB = col_slot_reduce(slots, kSlotB);
     const unsigned long long vmin = col_slot_reduce(slots, kSlotVmin1), rmax = col_slot_reduce(slots, kSlotRmax1), l1 = col_slot_reduce(slots, kSlotL1);
-    const unsigned long long nskip = col_slot_reduce(slots, kSlotSkip), nsafe = col_slot_reduce(slots, kSlotSkipSafe), nresc = col_slot_reduce(slots, kSlotResC);
+    const unsigned long long nskip = col_slot_reduce(slots, kSlotSkip), nsafe = col_slot_reduce(slots, kSlotSkipSafe), nresc = col_slot_reduce(slots, kSlotResC), ncells = col_slot_reduce(slots, kSlotCells);
     if (threadIdx.x == 0) {
       Lmax[1] = l1;
       sc->tiles_skipped = (long long)nskip;
       sc->tiles_skipped_safe = (long long)nsafe;
       sc->tiles_resident_c = (long long)nresc;
+      sc->cells_evaluated = (long long)ncells;
       sc->ustar_key = ~0ull;                       // (the objective's half: k_col_min, into its own block)
       sc->count_S = (long long)cS;
       sc->count_U = (long long)cU;
@@ -1023,6 +1024,7 @@ __global__ __launch_bounds__(256) void k_col_finals(const Best* __restrict__ reg
       hm->tiles_skipped = sc->tiles_skipped;
       hm->tiles_skipped_safe = sc->tiles_skipped_safe;
       hm->tiles_resident_c = sc->tiles_resident_c;
+      hm->cells_evaluated = sc->cells_evaluated;
       for (int t = 0; t < kMaxQ; ++t) {
         hm->rmax_key[t] = sc->rmax_key[t];
         reinterpret_cast<unsigned long long*>(mirror + offsetof(PinnedBack, lip_keys))[t] = Lkeys[t];

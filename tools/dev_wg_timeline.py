@@ -21,7 +21,7 @@ from safebo_amd import synthetic                    # noqa: E402
 
 ROWS = 1 << 13
 KINDS = ("evaluated", "skipped (partial rows only)", "skipped, gradient phases run", "past the tile list (exit at once)",
-         "classified from memory (k_bres)")
+         "classified from memory (k_bres)", "head launch (k_bhead: tile decisions, undecided cells from memory)")
 TICK_US = 0.01                                      # wall_clock64: 100 MHz
 
 
@@ -75,6 +75,14 @@ def report(name, d, out):
     if m.any():          # (k_bres: [1] is the clock behind its loads -- entry -> loads arrived -> exit)
         print(f"   classified from memory: loads {((d['tp'][m] - d['t0'][m]) * TICK_US).mean():6.2f} us, classification + partial rows + words "
               f"{part[m].mean():6.2f} us (means)", file=out)
+    m = d["kind"] == 5
+    if m.any():          # (k_bhead: [1] is the clock behind the first round's tile decisions; the tile is the first mixed one the workgroup's wave 0 decided, 0xffffff: none)
+        dec, rest = (d["tp"][m] - d["t0"][m]) * TICK_US, part[m]
+        mixed = m & (d["tile"] != 0xFFFFFF)
+        print(f"   head launch: tile decisions mean {dec.mean():6.2f} us, max {dec.max():6.2f}; cells + tile outputs mean {rest.mean():6.2f} us, max {rest.max():6.2f}", file=out)
+        if mixed.any():
+            print(f"   ... workgroups whose wave 0 decided a mixed tile: {int(mixed.sum())}, life mean {((d['t1'][mixed] - d['t0'][mixed]) * TICK_US).mean():6.2f} us, "
+                  f"max {((d['t1'][mixed] - d['t0'][mixed]) * TICK_US).max():6.2f}", file=out)
 
 
 def main():
@@ -83,6 +91,7 @@ def main():
     ap.add_argument("--config", default="H")
     ap.add_argument("--out", default=None)
     ap.add_argument("--resident", type=int, default=1, help="option k1_resident (a library without it: ignored)")
+    ap.add_argument("--cells", type=int, default=1, help="option k1_cells (a library without it: ignored)")
     args = ap.parse_args()
     lib = safebo_amd._lib.load()
     fn = lib.sbo_debug_wg_trace
@@ -94,6 +103,10 @@ def main():
     eng.set_option("k1_sched", args.sched)
     try:
         eng.set_option("k1_resident", args.resident)
+    except ValueError:
+        pass
+    try:
+        eng.set_option("k1_cells", args.cells)
     except ValueError:
         pass
     eng.set_model(cfg["ds"], dtype="f64", use_invK=True)
@@ -109,7 +122,7 @@ def main():
     out = open(args.out, "w") if args.out else sys.stdout
     print(f"config {args.config}, lean 2, k1_sched {args.sched}: k1_tiles_skipped {prof['k1_tiles_skipped']}, k1_tiles_skipped_safe {prof['k1_tiles_skipped_safe']}, count_S {res['count_S']}, "
           f"posterior_ms {prof['posterior_ms']:.4f} (diagnostic build: a clock read and a barrier at each phase boundary)", file=out)
-    report("constraint launch k_bpost<1,1>", decode(buf[1]), out)
+    report("constraint launch (k_bhead, or k_bres<1> / k_bpost<1,1>)", decode(buf[1]), out)
     report("objective launch k_bpost<1,2>", decode(buf[0]), out)
     eng.close()
 
